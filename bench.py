@@ -16,7 +16,10 @@ and the recogniser's crops are cut from the boxes IT produced (`--boxes db`, the
 generator's own boxes instead).  `--models fast-real` runs the one real-weight detector with no overlay at all.
 
 Contract: python bench.py --gpus N --steps K --warmup W ; for N>1 launched by torch.distributed.run, one rank per
-GPU.  Rank 0 prints ONE JSON line.
+GPU.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the line; `--full` adds what
+else the benchmark measures after the timed region (the other recogniser batching modes, the per-kernel roofline pass, the
+secondary configurations and the CPU oracle baseline).  `--dump-outputs DIR` writes the last timed step's results (boxes,
+recogniser scores and texts of every frame, rank 0's gathered records) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -29,7 +32,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-MFMA_PEAK_TFLOPS = 2500.0     # dense fp16/bf16 MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md
+MFMA_PEAK_TFLOPS = 2500.0     # dense fp16/bf16 MFMA peak of the MI355X
 HBM_PEAK_GBS = 8000.0
 
 
@@ -77,6 +80,9 @@ def parse():
                     help="detector batches in flight: own = one torch stream each (torch's round-robin pool: whether two of them share a "
                          "hardware queue is left to the runtime), shared = ONE stream for all of them (in order, back to back), independent = "
                          "streams verified to run concurrently with each other and with the main stream (engine.Context.side_streams)")
+    ap.add_argument("--full", action="store_true", help="after the headline: the other rec modes (--other-mode-steps), the roofline pass, "
+                    "config.secondary and the CPU baseline (each still switched off by its --no-* flag); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's boxes, scores and texts as DIR/<name>.npy")
     ap.add_argument("--det-depth", type=int, default=2, help="detector batches in flight ahead of the one being recognised (2: two detector launches fill each other's tails, +3.6 % over 1 on one box; 3: +1.6 %)")
     return ap.parse_args()
 
@@ -239,6 +245,9 @@ def main():
     timed, det_maps, stage2_recognise, span, depth = W.timed, W.det_maps, W.stage2_recognise, W.span, W.depth
     out, dt = timed(args.warmup, args.steps)
     log(f"timed region ({args.rec_mode} rec batching): {args.warmup} warmup + {args.steps} steps in {dt:.3f}s")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, world * args.batch * (args.steps - 1))
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
     return finish(args, ctx, world, rank, W, out, dt, log, host_threads, build_secondary=lambda m, h, w_, b, **over: build_workload(
         args, ctx, world, rank, coll_dev, sync, log, m, h, w_, b, **over))
 
@@ -419,7 +428,7 @@ def finish(args, ctx, world, rank, W, out, dt, log, host_threads, build_secondar
     rec_modes = {args.rec_mode: {"value": round(world * args.batch * args.steps / dt, 2), "ms_per_step": round(1e3 * dt / args.steps, 3),
                                  "steps": args.steps}}
     for other in ("ragged", "reference", "bucketed"):
-        if other == args.rec_mode or args.other_mode_steps <= 0:
+        if other == args.rec_mode or args.other_mode_steps <= 0 or not args.full:
             continue
         pipe.rec_mode = other
         _o, dt2 = timed(1, args.other_mode_steps)
@@ -467,7 +476,7 @@ def finish(args, ctx, world, rank, W, out, dt, log, host_threads, build_secondar
             # the record exchange of every run_steps call); world 1 + VSE_FORCE_DIST=1 = the one-GPU rehearsal of the N > 1 path
             result["config"]["dist"] = {"backend": args.dist_backend, "world": world, "forced_on_one_rank": world == 1,
                                         "collective_device": str(W.coll_dev), "collectives": dict(parallel.COLLECTIVES)}
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             def profile_pass():                                  # the work of `span` steps, sequential, every op timed
                 ready = []
                 for k in range(span):
@@ -477,7 +486,7 @@ def finish(args, ctx, world, rank, W, out, dt, log, host_threads, build_secondar
                 stage2_recognise(ready)
             result["roofline"] = roofline(pipe, profile_pass, steps_per_call=span)     # rank 0 only: no collective
             log("roofline pass done")
-        if (args.secondary and not args.no_roofline and world == 1 and args.models == "server" and args.height == 1080
+        if (args.full and args.secondary and not args.no_roofline and world == 1 and args.models == "server" and args.height == 1080
                 and args.limit_side == 960):                      # (the default headline only; the A/B tools pass --no-roofline)
             # the other single-GPU configurations north_star names, through the same functions, a few timed steps each (the headline
             # above is untouched: it was measured first): BASELINE configs[2]'s frame size (4K frames, batch 32; det_limit_side_len
@@ -528,7 +537,7 @@ def finish(args, ctx, world, rank, W, out, dt, log, host_threads, build_secondar
                     sec[key] = {"error": repr(exc)[:300]}
                     torch.cuda.empty_cache()
             result["config"]["secondary"] = sec
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             from oracle import pipeline_ref as P
             cs = P.standin_charset(shim._ncls(rec[0])) if lang != "en" else P.en_charset()
             result["cpu_baseline"] = cpu_baseline(args, frames_np, truth, det, rec, cs, overlay_np)
@@ -538,6 +547,27 @@ def finish(args, ctx, world, rank, W, out, dt, log, host_threads, build_secondar
         dist.destroy_process_group()
         parallel.reset_gather_mode()
     return result
+
+
+def dump_outputs(path, out, first_frame):
+    """What a caller of the timed path receives for the last timed step (the gathered records of frames >= first_frame, in frame
+    order) -> path/<name>.npy: frame_numbers [F], box_counts [F] (float64), boxes [B, 4, 2], scores [B] (float32) and
+    text_codepoints [B, L] (float64, the recognised strings as Unicode code points, -1 past a string's end), boxes in frame order."""
+    recs = sorted((r for r in out if r[0] >= first_frame), key=lambda r: r[0])
+    boxes = [np.asarray(r[1], np.float32).reshape(-1, 4, 2) for r in recs]
+    texts = [t for r in recs for t, _s in r[2]]
+    codes = np.full((len(texts), max([1] + [len(t) for t in texts])), -1.0, np.float64)
+    for i, t in enumerate(texts):
+        codes[i, :len(t)] = [ord(c) for c in t]
+    arrays = {"frame_numbers": np.array([r[0] for r in recs], np.float64),
+              "box_counts": np.array([len(b) for b in boxes], np.float64),
+              "boxes": np.concatenate(boxes) if boxes else np.zeros((0, 4, 2), np.float32),
+              "scores": np.array([s for r in recs for _t, s in r[2]], np.float32),
+              "text_codepoints": codes}
+    assert len(arrays["scores"]) == len(arrays["boxes"]) == len(texts)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def detector_convs_block(W):

@@ -9,6 +9,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -29,18 +30,25 @@ def _run(cmd, env):
     return json.loads(lines[0])
 
 
-def test_bench_two_ranks_one_json_line(ctx):
+def test_bench_two_ranks_one_json_line(ctx, tmp_path):
     env = dict(os.environ, VSE_DIST_BACKEND="gloo", VSE_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     flags = ["--steps", "2", "--warmup", "1", "--batch", "16", "--no-cpu-baseline", "--no-roofline", "--no-secondary", "--other-mode-steps", "0"]
     two = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                "--master-port", str(_free_port()), "bench.py", "--gpus", "2"] + flags, env)
+                "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--dump-outputs", str(tmp_path / "two")] + flags, env)
     assert two["n_gpus"] == 2 and two["steps"] == 2 and two["warmup"] == 1 and two["scaling"] == "weak"
     assert two["config"]["records_gathered"] == 2 * 16 * 2            # ranks x frames per step x steps, gathered once
     assert two["config"]["frames_per_gpu_step"] == 16 and two["value"] > 0
     assert abs(two["value"] - 2 * 16 * 2 / (two["ms_per_step"] * 2 / 1e3)) < 0.02 * two["value"]      # whole-job frames / max time
-    one = _run([sys.executable, "bench.py", "--gpus", "1"] + flags, dict(os.environ))
+    one = _run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", str(tmp_path / "one")] + flags, dict(os.environ))
     assert one["n_gpus"] == 1 and one["config"]["records_gathered"] == 16 * 2
     assert one["config"]["boxes_last_step"] > 0
+    # --dump-outputs: the last timed step of the whole job (rank 0's gathered records), frames in order
+    for d, first, nf in ((tmp_path / "two", 2 * 16, 2 * 16), (tmp_path / "one", 16, 16)):
+        got = {n: np.load(d / (n + ".npy")) for n in ("frame_numbers", "box_counts", "boxes", "scores", "text_codepoints")}
+        assert got["frame_numbers"].tolist() == list(range(first, first + nf))
+        nb = int(got["box_counts"].sum())
+        assert nb > 0 and got["boxes"].shape == (nb, 4, 2) and got["scores"].shape == (nb,) and len(got["text_codepoints"]) == nb
+    assert nb == one["config"]["boxes_last_step"]
 
 
 def test_bench_one_rank_runs_every_collective_of_the_path_over_rccl(ctx):

@@ -1,5 +1,6 @@
 """Paddle inference data formats read without Paddle (paddle_io.py) and the shim's model-directory loading
 (det_model_dir / rec_model_dir of backend/tools/ocr.py:93-99 are DIRECTORIES holding inference.pdmodel + inference.pdiparams)."""
+import hashlib
 import os
 import struct
 
@@ -8,7 +9,9 @@ import pytest
 
 from vse_amd import modelzoo, paddle_io, shim
 
-REF_MODELS = "/root/reference/backend/models"
+# the reference checkout's backend/models/V3/ch_det_fast/inference.pdiparams: size and SHA-256
+REF_BLOB_BYTES = 2377917
+REF_BLOB_SHA256 = "7e9518c6ab706fe87842a8de1c098f990e67f9212b67c9ef8bc4bca6dc17b91a"
 
 
 # ---- a minimal protobuf writer for framework.proto's ProgramDesc (only what a tiny test graph needs) -------------------
@@ -129,20 +132,18 @@ def test_model_directory_without_blob_fails_loudly(tmp_path):
         shim._load_model(str(d))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="the reference checkout exists only in the build container")
-def test_reference_model_files_give_the_committed_descriptors():
-    """Every graph of the reference's backend/models decodes to the descriptor committed under models/, and the one weight
-    blob it ships (V3/ch_det_fast) to the committed tensors."""
-    n = 0
-    for ver in sorted(os.listdir(REF_MODELS)):
-        for name in sorted(os.listdir(os.path.join(REF_MODELS, ver))):
-            d = os.path.join(REF_MODELS, ver, name)
-            if not os.path.exists(os.path.join(d, "inference.pdmodel")):
-                continue
-            desc, weights = paddle_io.load_model_dir(d, f"{ver}_{name}")
-            assert desc == modelzoo.load_descriptor(f"{ver}_{name}")
-            if weights is not None:
-                ref = modelzoo.load_weights_npz(os.path.join(modelzoo.MODELS_DIR, f"{ver}_{name}.npz"))
-                assert set(ref) == set(weights) and all((ref[k] == weights[k]).all() for k in ref)
-            n += 1
-    assert n == 21
+def test_committed_weights_rebuild_the_reference_blob(tmp_path):
+    """The one weight blob the reference's backend/models ships (V3/ch_det_fast/inference.pdiparams) is the committed
+    models/V3_ch_det_fast.npz: written back in Paddle's stream format, the tensors give that file byte for byte (its size and
+    SHA-256 at the top of this module), and parse_params decodes that file to the committed tensors in the shapes the committed
+    descriptor declares."""
+    ref = modelzoo.load_weights_npz(os.path.join(modelzoo.MODELS_DIR, "V3_ch_det_fast.npz"))
+    desc = modelzoo.load_descriptor("V3_ch_det_fast")
+    assert set(ref) == set(desc["params"])
+    pdi = tmp_path / "inference.pdiparams"
+    paddle_io.write_params(str(pdi), ref)
+    blob = pdi.read_bytes()
+    assert len(blob) == REF_BLOB_BYTES and hashlib.sha256(blob).hexdigest() == REF_BLOB_SHA256
+    weights = paddle_io.parse_params(str(pdi), sorted(desc["params"]))
+    assert set(ref) == set(weights) and all((ref[k] == weights[k]).all() for k in ref)
+    assert all(list(weights[k].shape) == desc["params"][k]["dims"] for k in weights)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runs on the GPU box (via gpurun): bench + rocprofv3 kernel stats + separate PMC passes, all under gpurun_out/.
-R=$GRAFT_REPO_ROOT; TAG=${1:-r01}; shift; EXTRA="$@"      # EXTRA: more bench.py flags (e.g. --models fast for the mobile pair: tag r04_fast)
+R=$(cd "$(dirname "$0")/.." && pwd); TAG=${1:-r01}; shift; EXTRA="--full $@"      # EXTRA: bench.py flags (--full: the roofline pass, secondary, CPU baseline; more e.g. --models fast for the mobile pair: tag r04_fast)
 cd $R && python bench.py $EXTRA > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err
 cd /tmp; export TMPDIR=/tmp
 rm -rf $R/gpurun_out/prof_$TAG $R/gpurun_out/pmc_fetch_$TAG $R/gpurun_out/pmc_write_$TAG
