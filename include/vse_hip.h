@@ -212,6 +212,28 @@ int vse_ctc_collapse(vse_ctx* ctx, const void* d_idx_maxp, int b, int t, int32_t
 int vse_ctc_collapse_ragged(vse_ctx* ctx, const void* d_idx_maxp, int b, int t, const int32_t* d_tlen, int32_t* d_out_idx,
                             int32_t* d_out_len, float* d_out_conf, void* stream);
 
+/* ---- subtitle-change frame selector ----------------------------------------------------------------------------------- */
+/* Replaces: VideoSubFinder's frame search (the closed binary run by backend/main.py:378-505, extract_frame_by_vsf), which looks at
+ * every frame of the subtitle area and reports where each subtitle starts and stops.  Here the device part: per frame, the
+ * luma edge mask of the area and how much of it changed against the previous frame; the host turns the counts into
+ * intervals (vse_amd.frame_select.ChangeFrameSelector).
+ * Size in bytes of the caller-owned state that carries the previous frame's mask from one call to the next, for an area of
+ * area_h x area_w pixels (0 when the area is smaller than 3 x 3).  A fresh state is zero-filled. */
+size_t vse_frame_change_state_bytes(int area_h, int area_w);
+/* uint8 BGR frames [n, src_h, src_w, 3] (row pitch `pitch` bytes, frame stride `frame_stride` bytes) and the area
+ * [y0, y1) x [x0, x1) (at least 3 x 3, inside the frame) -> d_counts int32 [n, 3] = edges, appeared, vanished per frame:
+ *   Y = (29 B + 150 G + 77 R + 128) >> 8;
+ *   edge pixel = interior pixel of the area (y0 < y < y1 - 1, x0 < x < x1 - 1) with
+ *                max(|Y[y][x+1] - Y[y][x-1]|, |Y[y+1][x] - Y[y-1][x]|) >= edge_thresh;
+ *   edges = |E|, appeared = |E and not E'|, vanished = |E' and not E|, E' = the previous frame's edge pixels.
+ * Only pixels of the area are read (a caller may pass the area's rows alone).  d_state (vse_frame_change_state_bytes of this
+ * area, 8-byte aligned) holds the last frame's mask after the call; the first frame of the next call is compared with it, so
+ * batches of any size give the counts of one batch.  With `reset`, or on a fresh state, E' is empty for the first frame.
+ * Returns VSE_E_INVAL, without touching the device, for a degenerate or out-of-frame area. */
+int vse_frame_change(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride,
+                     int y0, int y1, int x0, int x1, int edge_thresh, void* d_state, int reset,
+                     int32_t* d_counts /* [n,3]: edges, appeared, vanished */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

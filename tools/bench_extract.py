@@ -5,7 +5,9 @@ region), real-weight detector (V3_ch_det_fast) + stand-in en recogniser, fully d
 
 usage: python tools/bench_extract.py [--frames 1024] [--batch 64] [--hold 12]
 Prints one JSON line per mode: fps sampler looking at every frame, batched and frame by frame (the reference's order of
-work), and the accurate mode (detector loop over every frame + OCR of the selected ones)."""
+work), and the accurate mode (detector loop over every frame + OCR of the selected ones).  First, fast mode with an area both
+ways: the fps sampler at the default extract_frequency (what that run fell back to) and the subtitle-change selector
+(frame_selector="change", VideoSubFinder's role); `ocr_frames` is the number of frames each run sent to OCR."""
 import argparse
 import json
 import os
@@ -14,7 +16,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
-from vse_amd import engine, extractor, modelzoo, pipeline, shim, staging, synth
+from vse_amd import engine, extractor, frame_select, modelzoo, pipeline, shim, staging, synth
 
 
 def main():
@@ -27,6 +29,7 @@ def main():
     ap.add_argument("--single", type=int, default=96, help="frames of the frame-by-frame run (slow)")
     ap.add_argument("--workers", type=int, default=4, help="copy threads of the pinned-slab uploader")
     ap.add_argument("--staged-only", action="store_true")
+    ap.add_argument("--change-only", action="store_true", help="only the two fast-mode-with-area rows (fps sampler / change selector)")
     a = ap.parse_args()
     ctx = engine.Context(0)
     det = modelzoo.get_model("V3_ch_det_fast", seed=0)
@@ -42,12 +45,16 @@ def main():
     fps = 24.0
 
     class Ocr:
+        frames = 0                                    # frames sent to OCR
+
         def predict(self, frame):
+            self.frames += 1
             b, r = pipe.ocr(torch.from_numpy(np.ascontiguousarray(frame)).to(ctx.tdev)[None])[0]
             return shim.OcrRecogniser.arrange(b, r)
 
     class OcrBatched(Ocr):
         def predict_batch(self, frames):
+            self.frames += len(frames)
             return [shim.OcrRecogniser.arrange(b, r) for b, r in pipe.ocr(frames)]
 
     def detect_stream(batches):
@@ -59,7 +66,11 @@ def main():
             return [shim.OcrRecogniser.arrange(b, r) for b, r in pipe.ocr_from_det(frames, dets)]
 
         def predict_stream(self, batches):
-            for out in pipe.ocr_stream(batches):
+            def counted():
+                for x in batches:
+                    self.frames += x.shape[0]
+                    yield x
+            for out in pipe.ocr_stream(counted()):
                 yield [shim.OcrRecogniser.arrange(b, r) for b, r in out]
 
     def detect(frames):
@@ -69,6 +80,10 @@ def main():
     area = extractor.SubtitleArea(ymin=int(0.75 * a.height), ymax=a.height, xmin=0, xmax=a.width)
     up = staging.Uploader(ctx.tdev, workers=a.workers)
     runs = [
+        ("fast mode + area: fps sampler at extract_frequency 3, staged upload + streamed detector", clip, OcrStreamed(),
+         dict(sub_area=area, mode="fast", extract_frequency=3, uploader=up)),
+        ("fast mode + area: subtitle-change selector, staged upload + streamed detector", clip, OcrStreamed(),
+         dict(sub_area=area, mode="fast", frame_selector="change", change_counter=frame_select.EngineCounter(ctx), uploader=up)),
         ("fps sampler, every frame, staged upload + streamed detector", clip, OcrStreamed(),
          dict(sub_area=None, mode="fast", extract_frequency=fps, uploader=up)),
         ("fps sampler, every frame, batched, staged upload", clip, OcrBatched(),
@@ -80,8 +95,10 @@ def main():
         ("fps sampler, every frame, frame by frame", clip[:a.single], Ocr(), dict(sub_area=None, mode="fast", extract_frequency=fps)),
         ("accurate mode, batched", clip, OcrBatched(), dict(sub_area=area, mode="accurate")),
     ]
-    if a.staged_only:
-        runs = runs[:4]
+    if a.change_only:
+        runs = runs[:2]
+    elif a.staged_only:
+        runs = runs[:6]
     for name, frames, ocr, kw in runs:
         src = extractor.ArraySource(frames, fps)
         ex = extractor.SubtitleExtractor(src, ocr, detect_batch=detect, drop_score=0.0, batch=a.batch, **kw)
@@ -89,12 +106,13 @@ def main():
                                               drop_score=0.0, batch=a.batch, **kw)
         ex_warm.run()
         torch.cuda.synchronize()
+        ocr.frames = 0
         t0 = time.time()
         text = ex.run()
         torch.cuda.synchronize()
         dt = time.time() - t0
         print(json.dumps({"mode": name, "frames": len(frames), "seconds": round(dt, 3), "frames_per_s": round(len(frames) / dt, 1),
-                          "raw_lines": len(ex.raw_lines), "srt_blocks": text.count(" --> "),
+                          "ocr_frames": ocr.frames, "raw_lines": len(ex.raw_lines), "srt_blocks": text.count(" --> "),
                           "frame_mb": round(a.height * a.width * 3 / 1e6, 2)}), flush=True)
 
 

@@ -47,6 +47,9 @@ struct vse_plan {
     long src_pitch, src_fstride;
 };
 
+int vse_frame_change_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
+                            void* d_state, int reset, int32_t* d_counts, void* stream);     // frame_change.hip
+
 extern "C" {
 
 const char* vse_last_error(void) { return g_err.c_str(); }
@@ -405,6 +408,27 @@ void vse_graph_destroy(vse_graph* g) {
     if (g->exec) (void)hipGraphExecDestroy(g->exec);
     if (g->graph) (void)hipGraphDestroy(g->graph);
     delete g;
+}
+
+// ---- subtitle-change frame selector (frame_change.hip) ---------------------------------------------------------------------
+size_t vse_frame_change_state_bytes(int area_h, int area_w) {
+    if (area_h < 3 || area_w < 3) return 0;
+    return 16 + (size_t)(area_h - 2) * (size_t)((area_w - 2 + 63) / 64) * 8;
+}
+
+int vse_frame_change(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0, int y1,
+                     int x0, int x1, int edge_thresh, void* d_state, int reset, int32_t* d_counts, void* stream) {
+    if (!c || !d_bgr || !d_state || !d_counts || n <= 0 || src_h <= 0 || src_w <= 0 || pitch < (int64_t)src_w * 3 ||
+        (n > 1 && frame_stride < (int64_t)(src_h - 1) * pitch + (int64_t)src_w * 3) || (reinterpret_cast<uintptr_t>(d_state) & 7)) {
+        set_err("vse_frame_change: bad arguments (n %d, frame %d x %d, pitch %lld, frame stride %lld)", n, src_h, src_w, (long long)pitch,
+                (long long)frame_stride);
+        return VSE_E_INVAL;
+    }
+    if (y0 < 0 || x0 < 0 || y1 > src_h || x1 > src_w || y1 - y0 < 3 || x1 - x0 < 3) {
+        set_err("vse_frame_change: area [%d, %d) x [%d, %d) is degenerate or outside the %d x %d frame", y0, y1, x0, x1, src_h, src_w);
+        return VSE_E_INVAL;
+    }
+    return vse_frame_change_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, d_state, reset, d_counts, stream);
 }
 
 int vse_plan_op_variant(vse_plan* p, int i) {

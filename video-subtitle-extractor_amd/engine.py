@@ -19,7 +19,7 @@ EXPORTS = [
     "vse_plan_width_levels", "vse_plan_profile", "vse_plan_op_variant", "vse_plan_op_kernel_name", "vse_det_preprocess", "vse_db_workspace_bytes",
     "vse_db_postprocess", "vse_rec_preprocess", "vse_rec_preprocess_scratch_bytes", "vse_ctc_collapse", "vse_ctc_collapse_ragged",
     "vse_det_forward", "vse_rec_forward", "vse_plan_set_source", "vse_plan_takes_frames",
-    "vse_rec_graph_create", "vse_graph_launch", "vse_graph_destroy",
+    "vse_rec_graph_create", "vse_graph_launch", "vse_graph_destroy", "vse_frame_change_state_bytes", "vse_frame_change",
 ]
 
 
@@ -117,6 +117,10 @@ def load_library(path=None):
                                      C.c_void_p]
     lib.vse_ctc_collapse_ragged.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p]
+    lib.vse_frame_change_state_bytes.restype = C.c_size_t
+    lib.vse_frame_change_state_bytes.argtypes = [C.c_int, C.c_int]
+    lib.vse_frame_change.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                     C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     if lib.vse_sizeof_op() != ir.OP_DT.itemsize or lib.vse_sizeof_view() != ir.VIEW_DT.itemsize:
         raise VseError(f"ABI mismatch: vse_op {lib.vse_sizeof_op()} vs {ir.OP_DT.itemsize}, "
                        f"vse_view {lib.vse_sizeof_view()} vs {ir.VIEW_DT.itemsize}")
@@ -312,6 +316,30 @@ class Context:
                                                 C.c_void_p(oi.data_ptr()), C.c_void_p(ol.data_ptr()),
                                                 C.c_void_p(oc.data_ptr()), self.stream()), "vse_ctc_collapse")
         return oi, ol, oc
+
+    # ---- subtitle-change frame selector -------------------------------------------------------------------------
+    def frame_change_state(self, area_h, area_w):
+        """A fresh (zero-filled) state for frame_change over an area of area_h x area_w pixels."""
+        nbytes = self.lib.vse_frame_change_state_bytes(area_h, area_w)
+        if not nbytes:
+            raise VseError(f"frame_change: an area of {area_h} x {area_w} pixels has no interior")
+        return self.torch.zeros(nbytes, dtype=self.torch.uint8, device=self.tdev)
+
+    def frame_change(self, frames_u8, area, edge_thresh, state, reset=False):
+        """frames_u8: cuda uint8 [n,H,W,3] (any row pitch / frame stride, pixels packed), area = (y0, y1, x0, x1) in its pixels,
+        state: frame_change_state of the area's size (carries the last frame's edge mask to the next call) ->
+        cuda int32 [n,3]: edges, appeared, vanished per frame (include/vse_hip.h vse_frame_change)."""
+        t = self.torch
+        assert frames_u8.dtype == t.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
+        assert frames_u8.stride(3) == 1 and frames_u8.stride(2) == 3
+        y0, y1, x0, x1 = (int(v) for v in area)
+        assert state.dtype == t.uint8 and state.is_contiguous() and state.numel() >= self.lib.vse_frame_change_state_bytes(y1 - y0, x1 - x0)
+        n, h, w, _ = frames_u8.shape
+        out = t.empty((n, 3), dtype=t.int32, device=self.tdev)
+        _check(self.lib.vse_frame_change(self.handle, C.c_void_p(frames_u8.data_ptr()), n, h, w, frames_u8.stride(1),
+                                         frames_u8.stride(0), y0, y1, x0, x1, int(edge_thresh), C.c_void_p(state.data_ptr()),
+                                         int(bool(reset)), C.c_void_p(out.data_ptr()), self.stream()), "vse_frame_change")
+        return out
 
 
 class Net:

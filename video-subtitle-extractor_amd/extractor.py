@@ -9,8 +9,9 @@ logic on the host.  Frames are independent, so the tasks of one video can also b
 and the per-frame records gathered on rank 0 (parallel.gather_records) before the sequential text logic runs.
 
 Pinned by tests/golden/extract.json (the reference's own producer / consumer / fps sampler executed on scripted inputs),
-frame_loop.json, srt.json, raw_filters.json and text_cleanup.json.  Not rebuilt: VideoSubFinder frame selection (closed binary), GUI
-progress plumbing; reformat.execute is text_cleanup.py with the word segmenter as a parameter (its corpus is not installed here).
+frame_loop.json, srt.json, raw_filters.json and text_cleanup.json.  Not rebuilt: VideoSubFinder itself (closed binary; its role,
+finding where each subtitle starts and stops, is frame_selector="change"), GUI progress plumbing; reformat.execute is
+text_cleanup.py with the word segmenter as a parameter (its corpus is not installed here).
 
 Frame sources: anything with `frame_count`, `fps`, `read(frame_no) -> uint8 BGR [H,W,3] | None` (1-based, like
 cap.set(CAP_PROP_POS_FRAMES, frame_no - 1); cap.read()) and `frames()` (decode order).  `ArraySource` wraps decoded frames;
@@ -180,12 +181,19 @@ class SubtitleExtractor:
 
     mode 'accurate' (+ a subtitle area): frames are chosen by the detector loop (frame_select.AccurateFrameSelector);
     otherwise by the fps sampler (the reference would use the closed VideoSubFinder binary in fast/auto mode when an area is
-    given; the sampler is what it runs without an area and on platforms without that binary)."""
+    given; the sampler is what it runs without an area and on platforms without that binary).
+    frame_selector="change" takes VideoSubFinder's role in fast / auto mode with an area: every frame of the area is compared
+    with the one before it on the device (frame_select.ChangeFrameSelector, `change_params` its keyword arguments,
+    `change_counter` its count_fn), one OCR task goes to the middle frame of each interval, and the SRT takes its times from
+    the intervals (srt.generate_subtitle_file_intervals); the intervals are kept on the object (`intervals`)."""
 
     def __init__(self, source, ocr, detect_batch=None, sub_area=None, mode="fast", language="ch", extract_frequency=3,
                  default_subtitle_area=None, drop_score=0.75, deviation_rate=0.0, threshold=80, batch=64,
                  watermark_decide=None, scene_text_decide=lambda band: True, shard=None, gather_device=None,
-                 word_segmentation=False, segment=None, uploader=None, detect_stream=None):
+                 word_segmentation=False, segment=None, uploader=None, detect_stream=None, frame_selector="fps", change_params=None,
+                 change_counter=None, delete_empty=True):
+        if frame_selector not in ("fps", "change"):
+            raise ValueError(f"frame_selector must be 'fps' or 'change', not {frame_selector!r}")
         self.source, self.ocr, self.detect_batch = source, ocr, detect_batch
         self.sub_area, self.mode, self.language = sub_area, mode, language
         self.extract_frequency, self.default_subtitle_area = extract_frequency, default_subtitle_area
@@ -199,8 +207,11 @@ class SubtitleExtractor:
         # detector of the next chunks stays in flight); ocr.predict_with_dets, when it exists, recognises from those boxes
         self.detect_stream = detect_stream
         self.word_segmentation, self.segment = word_segmentation, segment      # config.wordSegmentation (main.py:181-182)
+        self.frame_selector, self.change_params, self.change_counter = frame_selector, change_params, change_counter
+        self.delete_empty = delete_empty          # config.deleteEmptyTimeStamp (intervals of the change selector only)
         self.raw_lines = None
         self.short_lines = None
+        self.intervals = None
 
     def _uploader(self):
         if self.uploader == "auto":
@@ -217,6 +228,10 @@ class SubtitleExtractor:
                                                      detect_stream=self.detect_stream,
                                                      predict_with_dets=getattr(self.ocr, "predict_with_dets", None))
             return [(t[0], t[1], t[2], t[3], None, None) for t in sel.run(s.frames(), uploader=up)]
+        if self.sub_area is not None and self.mode in ("fast", "auto") and self.frame_selector == "change":
+            sel = frame_select.ChangeFrameSelector(self.change_counter, batch=self.batch, **(self.change_params or {}))
+            self.intervals = sel.run(s.frames(), self.sub_area, uploader=self._uploader())
+            return [(s.frame_count, rep, None, None, None, self.default_subtitle_area) for _start, _end, rep in self.intervals]
         return fps_tasks(s.frame_count, s.fps, self.extract_frequency, self.default_subtitle_area)
 
     def _predict_list(self, frames):
@@ -224,6 +239,7 @@ class SubtitleExtractor:
 
     def run(self):
         """-> SRT text.  raw_lines (normalised, as the reference rewrites raw.txt) and short_lines are kept on the object."""
+        self.intervals = None
         tasks = self.select_tasks()
         lines = run_ocr_tasks(self.source, tasks, self.ocr, self.sub_area, self.language, self.drop_score,
                               self.deviation_rate, self.batch, self.shard, self.gather_device, self._uploader())
@@ -231,8 +247,13 @@ class SubtitleExtractor:
             if self.watermark_decide is not None:               # the reference asks on stdin (main.py:164-170)
                 lines = raw_filters.filter_watermark(lines, self.watermark_decide)
             lines = raw_filters.filter_scene_text(lines, self.scene_text_decide) if lines else lines
-        text, self.short_lines, self.raw_lines = srt.generate_subtitle_file(lines, self.source.fps, self.threshold,
-                                                                              getattr(self.source, "pos_msec", None))
+        if self.intervals is not None:
+            text, self.raw_lines = srt.generate_subtitle_file_intervals(lines, self.intervals, self.source.fps, self.threshold,
+                                                                        getattr(self.source, "pos_msec", None), self.delete_empty)
+            self.short_lines = []
+        else:
+            text, self.short_lines, self.raw_lines = srt.generate_subtitle_file(lines, self.source.fps, self.threshold,
+                                                                                  getattr(self.source, "pos_msec", None))
         if self.word_segmentation:
             text, _ = text_cleanup.cleanup_srt(text, self.language, self.segment or text_cleanup.default_segmenter())
         return text

@@ -184,3 +184,126 @@ class AccurateFrameSelector:
         for f, b in zip(frames, dets):
             self._step(f, b)
         self._prefetched.clear()
+
+
+# ---- subtitle-change selection (fast / auto mode with an area) ---------------------------------------------------------
+def default_min_edges(area_h, area_w):
+    """Edge pixels a frame needs to count as showing a subtitle: 0.05 % of the area's interior, at least 64."""
+    return max(64, int(0.0005 * max(area_h - 2, 0) * max(area_w - 2, 0)))
+
+
+def change_intervals(counts, min_edges, change_ratio=0.5, min_frames=2):
+    """Per-frame (edges, appeared, vanished) of a whole clip -> [(start, end, rep)] with 1-based frame numbers.
+    A frame is present when edges >= min_edges; a cut falls between t-1 and t when presence changes, or when both are present
+    and (appeared + vanished) / (edges[t-1] + appeared) >= change_ratio (the union of the two masks); an interval is a maximal
+    run of present frames without a cut inside, kept when it is at least min_frames long; rep is its middle frame."""
+    out = []
+    start = None
+    prev_edges = 0
+
+    def close(end):
+        if start is not None and end - start + 1 >= min_frames:
+            out.append((start, end, (start + end) // 2))
+
+    for t, (e, a, v) in enumerate(counts, 1):
+        e, a, v = int(e), int(a), int(v)
+        if e < min_edges:
+            close(t - 1)
+            start = None
+        elif start is None:
+            start = t
+        else:
+            union = prev_edges + a
+            if union and (a + v) / union >= change_ratio:
+                close(t - 1)
+                start = t
+        prev_edges = e
+    close(len(counts))
+    return out
+
+
+class EngineCounter:
+    """count_fn of ChangeFrameSelector on the GPU (Context.frame_change): keeps the device state of the last area between calls."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self._state = None
+        self._shape = None
+
+    def __call__(self, frames, area, edge_thresh, reset):
+        t = self.ctx.torch
+        if not t.is_tensor(frames):
+            frames = t.from_numpy(frames).to(self.ctx.tdev)
+        y0, y1, x0, x1 = area
+        if self._shape != (y1 - y0, x1 - x0):
+            self._shape = (y1 - y0, x1 - x0)
+            self._state = self.ctx.frame_change_state(*self._shape)
+            reset = True
+        return self.ctx.frame_change(frames, area, edge_thresh, self._state, reset)
+
+
+class ChangeFrameSelector:
+    """The role of VideoSubFinder in fast / auto mode with a subtitle area (backend/main.py:137-147, 378-505): look at EVERY frame
+    of the area and report where each subtitle starts and stops, so that one frame per subtitle goes to OCR and the SRT takes
+    its times from the intervals (srt.generate_subtitle_file_intervals).  VideoSubFinder is a closed binary; this is not its
+    algorithm but the same role: per frame the device counts the area's luma edge pixels and how many of them appeared or
+    vanished against the frame before (vse_frame_change), and change_intervals turns those integers into intervals.
+    The defaults lean towards cutting: an extra cut costs one OCR call and the duplicate removal merges it again, a missed
+    change loses a subtitle.
+
+    count_fn(frames [n,h,w,3] uint8, area (y0, y1, x0, x1) in their pixels, edge_thresh, reset) -> [n,3] counts; it carries the
+    last frame's mask to the next call (reset on the first batch of a clip).  Default: EngineCounter on the shim's device."""
+
+    def __init__(self, count_fn=None, edge_thresh=128, change_ratio=0.5, min_edges=None, min_frames=2, batch=64):
+        self.count_fn = count_fn
+        self.edge_thresh, self.change_ratio, self.min_edges, self.min_frames = edge_thresh, change_ratio, min_edges, min_frames
+        self.batch = batch
+        self.counts = None
+        self.intervals = None
+
+    def run(self, frames, sub_area, uploader=None):
+        """frames: iterable of uint8 BGR frames in decode order; sub_area: .ymin .ymax .xmin .xmax in frame pixels (clipped to
+        the frame) -> [(start, end, rep)].  Only the area's rows are staged; with an uploader (staging.Uploader) they go through
+        pinned memory on its producer thread, which uploads the next batches while the counts of this one are resolved."""
+        import numpy as np
+        if self.count_fn is None:
+            from . import shim
+            self.count_fn = EngineCounter(shim._context())
+        it = iter(frames)
+        first = next(it, None)
+        if first is None:
+            self.counts, self.intervals = np.zeros((0, 3), np.int32), []
+            return self.intervals
+        h, w = first.shape[:2]
+        y0, y1 = max(0, int(sub_area.ymin)), min(h, int(sub_area.ymax))
+        x0, x1 = max(0, int(sub_area.xmin)), min(w, int(sub_area.xmax))
+        if y1 - y0 < 3 or x1 - x0 < 3:
+            raise ValueError(f"ChangeFrameSelector: subtitle area {sub_area} leaves less than 3 x 3 pixels of a {h} x {w} frame")
+        area = (0, y1 - y0, x0, x1)
+
+        def batches():
+            buf = [(None, first[y0:y1])]
+            for f in it:
+                if len(buf) == self.batch:
+                    yield buf
+                    buf = []
+                buf.append((None, f[y0:y1]))
+            if buf:
+                yield buf
+
+        out = []
+        if uploader is not None:
+            from . import staging
+            for k, (_items, staged) in enumerate(staging.prefetch(batches(), uploader)):
+                out.append(np.asarray(self._host(self.count_fn(staged.tensor(), area, self.edge_thresh, k == 0))))
+        else:
+            for k, items in enumerate(batches()):
+                out.append(np.asarray(self._host(self.count_fn(np.stack([f for _, f in items]), area, self.edge_thresh, k == 0))))
+        self.counts = np.concatenate(out)
+        min_edges = default_min_edges(y1 - y0, x1 - x0) if self.min_edges is None else self.min_edges
+        self.intervals = change_intervals(self.counts, min_edges, self.change_ratio, self.min_frames)
+        return self.intervals
+
+    @staticmethod
+    def _host(c):
+        return c.cpu() if hasattr(c, "cpu") else c

@@ -70,3 +70,46 @@ def make_frames(n, height=1080, width=1920, seed=0, p_two_lines=0.2, return_trut
         frames[f] = np.clip(img, 0, 255).astype(np.uint8)
         truth.append(tr)
     return (frames, truth) if return_truth else frames
+
+
+def make_clip(schedule, height=360, width=640, seed=0):
+    """A clip with held subtitles for the subtitle-change selector: uint8 BGR [n,height,width,3] + the true
+    [(start, end, text)] (1-based frame numbers, one entry per shown subtitle).
+
+    schedule: list of (text, frames) or (text, frames, fade); text None is a gap without a subtitle, `fade` > 0 blends the
+    first `fade` frames of that subtitle in at alpha (k + 1) / (fade + 1).  Every frame draws its background noise afresh
+    (the noise of make_frames); a text is rendered once and always drawn at the same place, one line centred in the
+    lower subtitle band, so back-to-back changes, gaps and the same text again after a gap are what the schedule says."""
+    rng = np.random.default_rng(seed)
+    n = sum(int(s[1]) for s in schedule)
+    frames = np.empty((n, height, width, 3), np.uint8)
+    grad = np.linspace(0, 40, height, dtype=np.float32)[:, None, None]
+    gh = max(12, int(60 * height / 1080.0))
+    y = int(0.99 * height) - gh - 8
+    glyphs = {}
+    truth = []
+    f = 0
+    for item in schedule:
+        text, count = item[0], int(item[1])
+        fade = int(item[2]) if len(item) > 2 else 0
+        if text is not None:
+            if text not in glyphs:
+                fill, outline = render_line(text, gh, np.random.default_rng([seed, *text.encode()]))
+                lw = min(fill.shape[1], int(0.88 * width))
+                glyphs[text] = (fill[:, :lw], outline[:, :lw])
+            truth.append((f + 1, f + count, text))
+        for k in range(count):
+            base = rng.integers(30, 91, size=((height + 3) // 4, (width + 3) // 4, 3), dtype=np.uint8)
+            img = np.repeat(np.repeat(base, 4, 0), 4, 1)[:height, :width].astype(np.float32) + grad
+            if text is not None:
+                fill, outline = glyphs[text]
+                lh, lw = fill.shape
+                x = (width - lw) // 2
+                yy = min(y, height - lh - 2)
+                a = (k + 1) / (fade + 1) if k < fade else 1.0
+                reg = img[yy:yy + lh, x:x + lw]
+                reg[outline > 0] *= 1.0 - a
+                reg[fill > 0] = reg[fill > 0] * (1.0 - a) + 255.0 * a
+            frames[f] = np.clip(img, 0, 255).astype(np.uint8)
+            f += 1
+    return frames, truth
