@@ -270,8 +270,8 @@ def test_segmented_concat_views_are_handled_or_refused_loudly():
 def test_se_gate_folds_into_depthwise_and_pointwise_consumers():
     """An SE output read only by the next stage's depthwise conv and by 1x1 convs (the detector's stage outputs: stage transition +
     FPN lateral) is never materialised: the depthwise conv applies the gate on load (F_GATE), each 1x1 conv reads per-image
-    weights W * gate (OP_WSCALE + F_IMGW, M tiles aligned to images).  Same result within the net tolerance; VSE_GATE_FOLD=0
-    restores the separate multiply."""
+    weights W * gate (OP_WSCALE + F_IMGW, M tiles aligned to images).  Same result within the net tolerance; compiler.GATE_FOLD =
+    False restores the separate multiply."""
     desc, w = net_ref.get_weights("V4_ch_det")
     x = np.random.default_rng(3).uniform(-1, 1, (2, 3, 128, 160)).astype(np.float16).astype(np.float32)
     ref = net_ref.run_graph(desc, w, x)[0].numpy()[:, 0]

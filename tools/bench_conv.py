@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
-"""Single-layer timing of the conv kernels on the GPU, per conv_gemm_kernel tile configuration.
+"""Single-layer timing of the conv kernels on the GPU, per kernel family the compiler may route a layer to.
 
-usage: python tools/bench_conv.py [--cfgs 0,3,4,5,6,8] [--layers name,name...]
+usage: python tools/bench_conv.py [--cfgs d,p,c] [--layers name,name...]
+  d: implicit GEMM only (conv_gemm_kernel, the launcher's tile configuration)
+  p: + conv_patch_kernel / conv_col_kernel
+  c: + conv_c3_kernel for any couts
 Each layer is a two-op graph (1x1 stem lifting the 3-channel feed to `cin`, then the conv under test); the conv under
-test is timed with HIP events (vse_plan_profile), min of 3.  VSE_GEMM_CFG is read by the launcher at every launch."""
+test is timed with HIP events (vse_plan_profile), min of 3."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -84,7 +87,9 @@ def graph(cin, cout, k, s, p):
 
 
 def main():
-    cfgs = [c for c in (sys.argv[sys.argv.index("--cfgs") + 1].split(",") if "--cfgs" in sys.argv else ["0"])]
+    cfgs = sys.argv[sys.argv.index("--cfgs") + 1].split(",") if "--cfgs" in sys.argv else ["d"]
+    if not set(cfgs) <= {"d", "p", "c"}:
+        sys.exit(f"unknown --cfgs {cfgs}: d, p, c")
     names = sys.argv[sys.argv.index("--layers") + 1].split(",") if "--layers" in sys.argv else list(LAYERS)
     ctx = engine.Context(0)
     for name in names:
@@ -92,9 +97,9 @@ def main():
         desc, wts = graph(cin, cout, k, s, p)
         from vse_amd import compiler
         nets = {}
-        # "p": conv_patch_kernel / conv_col_kernel allowed; "c": + conv_c3_kernel for any couts; numeric cfgs: implicit GEMM only
-        for key, mink in (("g", 1 << 30), ("p", 500), ("c", 100)):
-            compiler.PATCH_MIN_K = mink
+        mink = {"d": 1 << 30, "p": 500, "c": 100}
+        for key in cfgs:
+            compiler.PATCH_MIN_K = mink[key]
             nets[key] = engine.Net(ctx, desc, wts, want_probs=False)
         x = (torch.rand((n, h, w, 8), device="cuda") * 2 - 1).half()
         x[..., 3:] = 0
@@ -102,26 +107,20 @@ def main():
         ow = (w + 2 * p[1] - k[1]) // s[1] + 1
         flops = 2.0 * n * oh * ow * cout * cin * k[0] * k[1]
         row = []
-        ref = None
         for c in cfgs:
-            net = nets[c if c in ("p", "c") else "g"]
-            compiler.PATCH_MIN_K = (100 if c == "c" else 500) if c in ("p", "c") else 1 << 30      # plans are compiled lazily on the first run
+            net = nets[c]
+            compiler.PATCH_MIN_K = mink[c]      # plans are compiled lazily on the first run
             compiler.PATCH_MAX_COUT = 256 if c == "p" else 64       # "p": also try the patch kernel on wide layers (two+ cout tiles)
             compiler.COL3 = c == "c"
             compiler.COL3_MAX_COUT, compiler.COL3_MIN_TILE_EFF, compiler.COL3_WIDE_MIN_CIN = 4096, 0.0, 0
             compiler.COL3_MIN_K = 100
-            os.environ["VSE_GEMM_CFG"] = "" if c in ("p", "d") else c      # "d": the launcher's own choice
-            out = net.run(x)
+            net.run(x)
             torch.cuda.synchronize()
-            o = out[0].float()
-            if ref is None:
-                ref = o.clone()
-            same = bool(torch.equal(o, ref)) or c in ("p", "c")
             best = 1e9
             for _ in range(3):
                 ms, prog, var = net.profile(x)
                 best = min(best, float(ms[1]))
-            row.append(f"cfg{c}: {best:7.3f} ms {flops / best / 1e9:6.0f} TF/s{'' if same else ' MISMATCH'}")
+            row.append(f"cfg{c}: {best:7.3f} ms {flops / best / 1e9:6.0f} TF/s")
         print(f"{name:20s} " + " | ".join(row), flush=True)
         del net, nets, x
         torch.cuda.empty_cache()

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Register spills / scratch of every kernel of the PRODUCT build (hipcc -Rpass-analysis=kernel-resource-usage): prints the kernels whose
-# scratch size or spill count is not zero and exits 1 if there is one.  usage: bash tools/check_spills.sh [-DVSE_DEV_BUILD]
+# scratch size or spill count is not zero and exits 1 if there is one.  usage: bash tools/check_spills.sh
 R=$(cd "$(dirname "$0")/.." && pwd); C=$R/video-subtitle-extractor_amd/csrc; T=$(mktemp -d)
 for f in $(python3 -c "import sys; sys.path.insert(0, '$R'); import __graft_entry__ as g; print(' '.join(g.HIP_SOURCES))"); do
   ( /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off "$@" -Rpass-analysis=kernel-resource-usage -c $C/$f -o $T/$f.o 2> $T/$f.log ) &

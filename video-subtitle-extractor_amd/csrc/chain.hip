@@ -28,10 +28,6 @@
 #include <cstdlib>
 #include "conv_common.h"
 
-#ifndef VSE_CHAIN_ABL
-#define VSE_CHAIN_ABL 0      // timing-only ablations (tools/ablate_chain.sh; results are garbage): 1 no global stores, 2 no depthwise taps,
-#endif                       // 4 no MFMAs, 8 no activation / hi-lo split in the PW epilogue (bit mask)
-
 namespace {
 
 enum { CH_MAGIC = 0x43484e31, CH_HDR = 16, CH_BUF = 16, CH_STAGE = 28, CH_MAX_STAGES = 8, CH_MAX_BUFS = 10 };
@@ -78,10 +74,8 @@ __device__ __forceinline__ void dw_taps(const float* __restrict__ plane, int ew_
         for (int dx = 0; dx < K; ++dx) acc = fmaf(w[dy * K + dx], plane[dy * ew_in + dx], acc);
 }
 
-#ifndef VSE_CHAIN_LB
-#define VSE_CHAIN_LB 3        // blocks per CU the register budget is sized for (146 VGPRs: 3 without spills; 4 spills 10 VGPRs)
-#endif
-__global__ __launch_bounds__(256, VSE_CHAIN_LB) void chain_kernel(const ChainArgs a) {
+constexpr int CHAIN_BLOCKS_CU = 3;     // blocks per CU the register budget is sized for (146 VGPRs: 3 without spills; 4 spills 10 VGPRs)
+__global__ __launch_bounds__(256, CHAIN_BLOCKS_CU) void chain_kernel(const ChainArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     // The descriptor (<= 400 words) is copied into LDS once per block and read from there.  Read from global memory, hipcc turned the
     // per-stage reads into VECTOR loads + v_readfirstlane (the stage index is a loop variable): two or three DEPENDENT global round
@@ -268,8 +262,7 @@ __global__ __launch_bounds__(256, VSE_CHAIN_LB) void chain_kernel(const ChainArg
                 const char* xb = xhi + pix * stride + h * 16;
                 const char* xl = xlo + pix * stride + h * 16;
                 const char* wb = wfr + ((size_t)ct * nks * 64 + lane) * 16;
-                if (VSE_CHAIN_ABL & 4) {
-                } else if (haslo) {
+                if (haslo) {
                     for (int ks = 0; ks < nks; ++ks) {
                         const half8 bh = *reinterpret_cast<const half8*>(xb + ks * 32);
                         const half8 bl = *reinterpret_cast<const half8*>(xl + ks * 32);
@@ -306,7 +299,7 @@ __global__ __launch_bounds__(256, VSE_CHAIN_LB) void chain_kernel(const ChainArg
                     const float4v b0 = *reinterpret_cast<const float4v*>(bias + c0), b1 = *reinterpret_cast<const float4v*>(bias + c0 + 4);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) { v[j] = acc[8 * g + j] + b0[j]; v[4 + j] = acc[8 * g + 4 + j] + b1[j]; }
-                    if (!(VSE_CHAIN_ABL & 8)) vse_act_n<8>(v, act, act_a, act_b);
+                    vse_act_n<8>(v, act, act_a, act_b);
                     if (post) {
 #pragma unroll
                         for (int j = 0; j < 8; ++j) v[j] = v[j] * post_a + post_b;
@@ -343,7 +336,7 @@ __global__ __launch_bounds__(256, VSE_CHAIN_LB) void chain_kernel(const ChainArg
                             if (bo_lo >= 0) *reinterpret_cast<half8*>(lds + bo_lo + pix * bo_stride + c0 * 2) = lo;
                         }
                     }
-                    if (store && !(VSE_CHAIN_ABL & 1)) {
+                    if (store) {
                         if (s_shuf) {
                             // head tail: channel 4 r + c = output (4 iy + r, 4 ix + c) of the 4 x 4 block of input pixel (iy, ix); this
                             // lane's run c0 .. c0 + 7 = rows c0 / 4 and c0 / 4 + 1 of the block -> fp32 map [n][4 H][4 W]
@@ -398,7 +391,7 @@ __global__ __launch_bounds__(256, VSE_CHAIN_LB) void chain_kernel(const ChainArg
                         const float4v w0 = wr[0], w1 = wr[1], w2 = wr[2];
                         const float w[9] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3], w2[0]};
                         float acc = w2[1];
-                        if (!(VSE_CHAIN_ABL & 2)) dw_taps<3>(base + (size_t)j * pstride, ew_in, w, acc);
+                        dw_taps<3>(base + (size_t)j * pstride, ew_in, w, acc);
                         v[j] = acc;
                     }
                 } else {
@@ -408,12 +401,10 @@ __global__ __launch_bounds__(256, VSE_CHAIN_LB) void chain_kernel(const ChainArg
                         const float* wr = wl + (cg * 8 + j) * 28;
                         const float* pl = base + (size_t)j * pstride;
                         float acc = wr[25];
-                        if (!(VSE_CHAIN_ABL & 2)) {
 #pragma unroll
-                            for (int dy = 0; dy < 5; ++dy) {
+                        for (int dy = 0; dy < 5; ++dy) {
 #pragma unroll
-                                for (int dx = 0; dx < 5; ++dx) acc = fmaf(wr[dy * 5 + dx], pl[dy * ew_in + dx], acc);
-                            }
+                            for (int dx = 0; dx < 5; ++dx) acc = fmaf(wr[dy * 5 + dx], pl[dy * ew_in + dx], acc);
                         }
                         v[j] = acc;
                     }
@@ -439,7 +430,7 @@ __global__ __launch_bounds__(256, VSE_CHAIN_LB) void chain_kernel(const ChainArg
                         }
                     }
                 }
-                if (gout >= 0 && !(VSE_CHAIN_ABL & 1)) {
+                if (gout >= 0) {
                     const int iy = y0 + ry, ix = x0 + rx;
                     const int oy = ry - bo_ah, ox = rx - bo_aw;
                     if (iy >= 0 && iy < H && ix >= 0 && ix < W && oy >= 0 && oy < bo_th && ox >= 0 && ox < bo_tw && cg * 8 < gv.c) {
@@ -582,10 +573,8 @@ int launch_chain(const vse_op& o, const TView& in0, const TView& out, const TVie
     const int nstages = o.p[3], nbufs = o.p[4];
     if (nstages < 1 || nstages > CH_MAX_STAGES || nbufs < 1 || nbufs > CH_MAX_BUFS) return VSE_E_INVAL;
     // p[5] = 1 (compiler.py try_lower_head_tail): a 1x1 -> 1x1 chain with the pixel-shuffle map store — the register form
-    // (chain_pw2_kernel; VSE_HEAD_PW2=0 keeps the generic kernel for A/B runs)
-    static const bool pw2_on = !(vse_dev_getenv("VSE_HEAD_PW2") && atoi(vse_dev_getenv("VSE_HEAD_PW2")) == 0);
-    // (an image above 64 KiB — the ResNet detector's 64 -> 4 x 64 -> 16 tail — stays on the generic kernel)
-    if (o.p[5] == 1 && pw2_on && nstages == 2 && o.p[6] > 0 && o.p[6] <= 64 * 1024 && in0.c <= 64) {
+    // (chain_pw2_kernel; an image above 64 KiB — the ResNet detector's 64 -> 4 x 64 -> 16 tail — stays on the generic kernel)
+    if (o.p[5] == 1 && nstages == 2 && o.p[6] > 0 && o.p[6] <= 64 * 1024 && in0.c <= 64) {
         Pw2Args b;
         b.desc = reinterpret_cast<const int*>(wbase + o.w_off);
         b.blob = wbase + o.w_off;
@@ -627,7 +616,7 @@ int launch_chain(const vse_op& o, const TView& in0, const TView& out, const TVie
     // persistent grid: as many blocks as the chip holds at this LDS size (160 VGPRs: three 4-wave blocks per CU at most), a multiple of 8
     const int n_cu = vse_cu_count();
     if (!n_cu) return VSE_E_HIP;
-    const int per_cu = std::max(1, std::min(VSE_CHAIN_LB, (160 * 1024) / (lds_bytes + 2048)));
+    const int per_cu = std::max(1, std::min(CHAIN_BLOCKS_CU, (160 * 1024) / (lds_bytes + 2048)));
     unsigned grid = (unsigned)std::min<unsigned long long>(blocks, (unsigned long long)n_cu * per_cu);
     if (grid > 8) grid &= ~7u;
 #ifdef VSE_CHAIN_TRACE

@@ -16,7 +16,6 @@
 //   sync   = as conv_col_kernel: one raw s_barrier per step, vmcnt(1) (+ the patch DMAs at a chunk's first step).
 //   couts  = ceil(Np / 64) cout tiles per pixel tile (innermost in the block order: the tiles that share a patch run together).
 //   weights packed [cinp/16][3 dx][3 dy][Np][16] + 3 zero stages (compiler.col_weights, F_COL).
-#include <stdlib.h>
 #include "conv_common.h"
 #ifdef VSE_TRACE
 #include <stdio.h>
@@ -26,29 +25,15 @@
 #define TR_STAMP(i) do { } while (0)
 #endif
 
-#ifndef VSE_C3_XPRE
-#define VSE_C3_XPRE 0     // 1: ring one stage ahead of the consumer + the next step's first fragments read across the barrier (as
-                          // conv_col_kernel); 0: plain look-ahead of three stages.  With two blocks per CU the partner block covers
-                          // the barrier bubble, and a stage's DMA round trip (~5k cycles under load) needs the third step of slack.
-#endif
+// Weight ring: a plain look-ahead of three stages (not conv_col_kernel's ring one stage ahead of the consumer with the next step's
+// first fragments read across the barrier).  With two blocks per CU the partner block covers the barrier bubble, and a stage's DMA
+// round trip (~5k cycles under load) needs the third step of slack.
 // (Measured and removed: a PERSISTENT form — a block walking tiles lb, lb + 512, ... with the DMA ring running across tile
 // boundaries, so that only a block's first tile pays the prologue's DMA round trip.  Correct, but 9-25 % SLOWER on every
 // layer (128->128 0.687 -> 0.751 ms, 64->64 0.76 -> 0.96 ms): the epilogue's stores sit in the same in-order vmcnt queue as
 // the LDS-DMAs, so the first counted waits of the next tile also wait for the stores' HBM round trip.)
 #define C3RING 4
 #define C3BN 64
-// Timing-only ablations for the Winograd F(2x2, 3x3) go / no-go (EXPERIMENTS G; results are WRONG, never in a product build):
-//   VSE_C3_ABL = 1: 16 of the 36 MFMAs per chunk and wave (the MFMA count of the 16 frequency GEMMs over the same outputs), every DMA,
-//                   fragment read, wait and barrier unchanged — an UPPER bound for a Winograd form inside this skeleton (its 16 / 9 x
-//                   larger weight stream, input transform and output transform all cost extra);
-//   VSE_C3_ABL = 2: + 128 v_pk_add_f16 per chunk and wave (the packed adds of B^T d B on 8-channel fragments).
-#ifndef VSE_C3_ABL
-#define VSE_C3_ABL 0
-#endif
-typedef unsigned uint4v __attribute__((ext_vector_type(4)));
-#if VSE_C3_ABL && !defined(VSE_DEV_BUILD)
-#error "VSE_C3_ABL is a development-build ablation"
-#endif
 
 // BN = 64 couts per block (TN = 2 accumulator tiles per row) or, for layers with <= 32 couts (the mobile detectors' 96 -> 24 neck convs,
 // the server detector's 32 -> 32), BN = 32: half the MFMAs, half the weight stage; everything else is the same code.
@@ -165,11 +150,7 @@ __device__ __forceinline__ void conv_c3_body(const ConvParams& p) {
     issue_w(0);
     issue_w(1);
     issue_w(2);
-#if VSE_C3_XPRE
-    wait_vm<1>();                                       // constants, patch 0, stages 0 and 1
-#else
     wait_vm<2>();                                       // constants, patch 0, stage 0
-#endif
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     TR_STAMP(1);
@@ -183,15 +164,9 @@ __device__ __forceinline__ void conv_c3_body(const ConvParams& p) {
 #ifdef VSE_TRACE
         const unsigned long long tw0 = __builtin_amdgcn_s_memtime();
 #endif
-#if VSE_C3_XPRE
-        // open step s+1: own DMAs of stage s+2 landed (+ the next chunk's patch unless it was issued in this step)
-        if (dx == 0) wait_vm<1 + PNPL>();
-        else wait_vm<1>();
-#else
         // open step s+1: own DMAs of stage s+1 landed; two younger stages (and a patch issued after stage s+1) may fly
         if (dx == 2) wait_vm<2>();
         else wait_vm<2 + PNPL>();
-#endif
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
@@ -216,15 +191,6 @@ __device__ __forceinline__ void conv_c3_body(const ConvParams& p) {
     }
 
     half8 X0, X1, Wc[TN];
-#if VSE_C3_XPRE
-    {
-        const unsigned xe = xcol(0, 0), wv0 = wbase(0);
-        X0 = *reinterpret_cast<const half8*>(ldsb + xe);
-        X1 = *reinterpret_cast<const half8*>(ldsb + (xe ^ 16u) + ROWB);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) Wc[j] = *reinterpret_cast<const half8*>(ldsb + wv0 + j * 1024);
-    }
-#endif
     int s = 0;
 #pragma unroll 1
     for (int cc = 0; cc < nchunks; ++cc) {
@@ -237,14 +203,12 @@ __device__ __forceinline__ void conv_c3_body(const ConvParams& p) {
             unsigned xo = xe ^ 16u, xno = xne ^ 16u;
             asm volatile("" : "+v"(xe), "+v"(xo), "+v"(xne), "+v"(xno));
             const unsigned wv = wbase(s), wvn = wbase(s + 1);
-            half8 Wn[TN], Xn, Xn0;
-#if !VSE_C3_XPRE
+            half8 Wn[TN], Xn;
             X0 = *reinterpret_cast<const half8*>(ldsb + xe);
             X1 = *reinterpret_cast<const half8*>(ldsb + xo + ROWB);
 #pragma unroll
             for (int j = 0; j < TN; ++j) Wc[j] = *reinterpret_cast<const half8*>(ldsb + wv + j * 1024);
-            (void)wvn; (void)xne; (void)xno;
-#endif
+            (void)wvn; (void)xne; (void)xno;      // (next-step addresses: unused, kept so that the code stays the measured one)
             // tap dy = 0: rows k = 0, 1 (held); fetch W[1], row k = 2 (even)
 #pragma unroll
             for (int j = 0; j < TN; ++j) Wn[j] = *reinterpret_cast<const half8*>(ldsb + wv + j * 1024 + BN * 32);
@@ -264,54 +228,22 @@ __device__ __forceinline__ void conv_c3_body(const ConvParams& p) {
             for (int j = 0; j < TN; ++j) Wn[j] = *reinterpret_cast<const half8*>(ldsb + wv + j * 1024 + 2 * BN * 32);
             Xn = *reinterpret_cast<const half8*>(ldsb + xo + 3 * ROWB);
             __builtin_amdgcn_sched_group_barrier(0x100, TN + 1, 0);
-            if (!VSE_C3_ABL || dx == 0) {
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wc[j], X0, acc[0][j], 0, 0, 0);
                 acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wc[j], X1, acc[1][j], 0, 0, 0);
             }
             __builtin_amdgcn_sched_group_barrier(0x008, 2 * TN, 0);
-            } else {                                     // ablation: the fragments stay read (kept alive), no matrix work
-                asm volatile("" :: "v"(X0), "v"(Wc[0]));
-            }
-#if VSE_C3_ABL == 2
-            {
-                unsigned t0 = __builtin_bit_cast(uint4v, X0)[0], t1 = __builtin_bit_cast(uint4v, X0)[1], t2 = __builtin_bit_cast(uint4v, X1)[2], t3 = __builtin_bit_cast(uint4v, X1)[3];
-#pragma unroll
-                for (int r = 0; r < (dx == 0 ? 11 : 10); ++r) {          // 4 x (11 + 10 + 10) + ... ~ 128 packed adds per chunk
-                    asm volatile("v_pk_add_f16 %0, %0, %1\n\tv_pk_add_f16 %1, %1, %2\n\tv_pk_add_f16 %2, %2, %3\n\tv_pk_add_f16 %3, %3, %0"
-                                 : "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3));
-                }
-                asm volatile("" :: "v"(t0), "v"(t1), "v"(t2), "v"(t3));
-            }
-#endif
             X0 = X1; X1 = Xn;
 #pragma unroll
             for (int j = 0; j < TN; ++j) Wc[j] = Wn[j];
             // tap dy = 2: rows 2, 3
-#if VSE_C3_XPRE
-            // fetch the first fragments of step s+1 (visible since the barrier that opened this step)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) Wn[j] = *reinterpret_cast<const half8*>(ldsb + wvn + j * 1024);
-            Xn0 = *reinterpret_cast<const half8*>(ldsb + xne);
-            Xn = *reinterpret_cast<const half8*>(ldsb + xno + ROWB);
-            __builtin_amdgcn_sched_group_barrier(0x100, TN + 2, 0);
-#endif
-            if (!VSE_C3_ABL) {
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wc[j], X0, acc[0][j], 0, 0, 0);
                 acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Wc[j], X1, acc[1][j], 0, 0, 0);
             }
             __builtin_amdgcn_sched_group_barrier(0x008, 2 * TN, 0);
-            } else {
-                asm volatile("" :: "v"(X0), "v"(X1), "v"(Wc[0]));
-            }
-#if VSE_C3_XPRE
-            X0 = Xn0; X1 = Xn;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) Wc[j] = Wn[j];
-#endif
             close_step(dx);
         }
     }
@@ -385,17 +317,8 @@ int launch_conv_c3(const ConvParams& pin, int n_img, hipStream_t st) {
     ConvParams p = pin;
     if (!conv_c3_ok(p.kh, p.kw, p.sh, p.sw, p.ph, p.pw, p.cinp, p.flags)) return VSE_E_UNSUPPORTED;
     if ((double)p.Hs * p.Ws * p.in_ld > 2.0e9) return VSE_E_UNSUPPORTED;      // 32-bit in-image offsets
-#ifdef VSE_DEV_BUILD      // kernel experiments (conv_c3w.hip, forced tile shapes): compiled only into development builds
-    static const int wide = [] { const char* e = getenv("VSE_C3_WIDE"); return e && e[0] ? atoi(e) : 0; }();
-    if (wide == 1 && conv_c3w_ok(p)) return launch_conv_c3w(pin, n_img, st);
-    if (wide == 2 && p.Np == 128 && !(p.flags & F_HILO)) return launch_conv_col3w(pin, n_img, st);
-#endif
     int rw;
     conv_c3_plan(p.OH, p.OW, &rw);
-#ifdef VSE_DEV_BUILD
-    static const int force = [] { const char* e = getenv("VSE_C3_RW"); return e && e[0] ? atoi(e) : 0; }();
-    if (force == 8 || force == 4 || force == 2) rw = force;
-#endif
     const int cw = 8 / rw;
     const bool hlsum = (p.flags & F_HLSUM) != 0;
     if (hlsum && (p.Np > 32 || (p.flags & F_HILO))) return VSE_E_INVAL;

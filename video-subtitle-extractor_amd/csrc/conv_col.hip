@@ -25,12 +25,7 @@
 //            rows lie below the map only issue DMAs and take part in the barriers.
 //   weights are packed [chunk16][dx][dy][Np][16] by the compiler (F_COL) + 3 zero stages for the look-ahead.
 //   K order of the fp32 accumulation: chunk-major, then column-major taps — one K slice of 16 per MFMA, sequential.
-#include <stdlib.h>
 #include "conv_common.h"
-
-#ifndef VSE_COL_XPRE
-#define VSE_COL_XPRE 1    // read the next step's first fragments across the barrier (A/B: tools/ab.sh conv_col VSE_COL_XPRE)
-#endif
 
 #define CTH 16
 #define CTW 32
@@ -193,9 +188,6 @@ __global__ __launch_bounds__(512, 2) void conv_col_kernel(const ConvParams p) {
             wbase(s, wv);
             wbase(s + 1, wvn);
             if (wave_live) {
-#if !VSE_COL_XPRE
-                preload(xb, wv);
-#endif
 #pragma unroll
                 for (int dy = 0; dy < KH; ++dy) {
                     half8 Wn[TN], Xn, Xn0;
@@ -206,15 +198,13 @@ __global__ __launch_bounds__(512, 2) void conv_col_kernel(const ConvParams p) {
                         Xn = *reinterpret_cast<const half8*>(ldsb + xb + (dy + 2) * ROWB);
                         __builtin_amdgcn_sched_group_barrier(0x100, TN + 1, 0);
                     } else {
-#if VSE_COL_XPRE
-                        // the first fragments of step s+1: stage s+1 (and a next chunk's patch) became visible at the barrier
-                        // that opened this step
+                        // the first fragments of step s+1 (read across the barrier): stage s+1 (and a next chunk's patch) became
+                        // visible at the barrier that opened this step
 #pragma unroll
                         for (int j = 0; j < TN; ++j) Wn[j] = *reinterpret_cast<const half8*>(ldsb + wvn[j]);
                         Xn0 = *reinterpret_cast<const half8*>(ldsb + xbn);
                         Xn = *reinterpret_cast<const half8*>(ldsb + xbn + ROWB);
                         __builtin_amdgcn_sched_group_barrier(0x100, TN + 2, 0);
-#endif
                     }
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
@@ -228,12 +218,10 @@ __global__ __launch_bounds__(512, 2) void conv_col_kernel(const ConvParams p) {
 #pragma unroll
                         for (int j = 0; j < TN; ++j) Wc[j] = Wn[j];
                     } else {
-#if VSE_COL_XPRE
                         X0 = Xn0;
                         X1 = Xn;
 #pragma unroll
                         for (int j = 0; j < TN; ++j) Wc[j] = Wn[j];
-#endif
                     }
                 }
             }
@@ -270,19 +258,6 @@ bool conv_col_ok(int kh, int kw, int sh, int sw, int cinp, int Np, int flags) {
            && !(flags & (F_SRC2 | F_PIXSHUF | F_DOT1));
 }
 
-#ifdef VSE_DEV_BUILD
-// experiment (VSE_C3_WIDE=2, development builds only): 3x3 layers with 128 couts on this kernel's one-block-per-CU structure, all couts per block
-int launch_conv_col3w(const ConvParams& pin, int n_img, hipStream_t st) {
-    ConvParams p = pin;
-    p.ntn = 1;
-    p.tiles_h = (p.OH + CTH - 1) / CTH;
-    p.tiles_w = (p.OW + CTW - 1) / CTW;
-    const unsigned long long blocks = (unsigned long long)n_img * p.tiles_h * p.tiles_w;
-    if (blocks == 0 || blocks > 0x7fffffffull) return VSE_E_INVAL;
-    hipLaunchKernelGGL((conv_col_kernel<3, 128>), dim3((unsigned)blocks), dim3(512), 0, st, p);
-    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
-}
-#endif
 
 int launch_conv_col(const ConvParams& pin, int n_img, hipStream_t st) {
     ConvParams p = pin;

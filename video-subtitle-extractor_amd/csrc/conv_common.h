@@ -21,7 +21,7 @@ struct ConvParams {
     float act_a, act_b, post_a, post_b;
     int flags, coutp;
     unsigned ntn;       // number of cout tiles
-    unsigned ntiles;    // conv_c3w_kernel: pixel tiles of the launch (the persistent blocks share them out)
+    unsigned ntiles;    // conv_head_up2r_kernel: tiles of the launch (the persistent blocks share them out); conv_dwpw_rows_kernel: row stride
     int tiles_h, tiles_w;   // patch kernel: output tile grid per image
     const float* dotw;      // F_DOT1: per-cout weights of the fused 1-channel projection
     float dotb;
@@ -69,22 +69,6 @@ __device__ __forceinline__ void glds16_asm(const void* g, half_t* l) {
 // 2 GiB descriptors these kernels build, so the DMA writes zeros.
 #define OOB 0x80000000u
 typedef __attribute__((address_space(3))) void* ldsv_t;
-typedef int rsrc4_t __attribute__((ext_vector_type(4)));
-// raw buffer descriptor over [base, base + 2 GiB): stride 0, num_records 0x7fffffff, dword3 0x00020000 (what
-// __builtin_amdgcn_make_buffer_rsrc builds), as four SGPRs an asm statement can take
-__device__ __forceinline__ rsrc4_t make_rsrc4(const void* base) {
-    const unsigned long long b = (unsigned long long)base;
-    return rsrc4_t{(int)__builtin_amdgcn_readfirstlane((unsigned)b), (int)__builtin_amdgcn_readfirstlane((unsigned)(b >> 32) & 0xffffu),
-                   0x7fffffff, 0x00020000};
-}
-// `buffer_load_dwordx4 voff, rsrc, soff offen lds` as an asm statement (see glds16_asm for why); `l` is the wave-uniform
-// LDS destination.  The leading s_nop covers a descriptor / soffset SGPR freshly written by v_readfirstlane.
-__device__ __forceinline__ void bufdma16_asm(rsrc4_t rsrc, unsigned voff, int soff, const void* l) {
-    unsigned keep;
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lptr_t)l);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(soff), "s"(dst) : "memory");
-}
 
 template <int N> __device__ __forceinline__ void wait_vm() {
     static_assert(N >= 0 && N <= 16, "vmcnt literal");
@@ -175,12 +159,9 @@ __device__ __forceinline__ void conv_epilogue_tile(const ConvParams& p, const fl
 #pragma unroll
     for (int e = 0; e < 16; ++e) v[e] = acc[e] + bias[e];
     vse_act_n(v, p.act, p.act_a, p.act_b);
-#ifndef VSE_EPI_SKIP
-#define VSE_EPI_SKIP 1
-#endif
     // the scalar affine after the activation is the identity for all but a handful of layers: one uniform branch instead of
     // 16 multiply-adds per accumulator tile (the epilogue is VALU-bound)
-    if (!VSE_EPI_SKIP || p.post_a != 1.f || p.post_b != 0.f) {
+    if (p.post_a != 1.f || p.post_b != 0.f) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) v[e] = v[e] * p.post_a + p.post_b;
     }
@@ -298,7 +279,7 @@ __device__ __forceinline__ float conv_epilogue_dot(const ConvParams& p, const fl
 #pragma unroll
     for (int e = 0; e < 16; ++e) v[e] = acc[e] + bias[e];
     vse_act_n(v, p.act, p.act_a, p.act_b);
-    if (!VSE_EPI_SKIP || p.post_a != 1.f || p.post_b != 0.f) {        // as conv_epilogue_tile: the affine is the identity almost everywhere
+    if (p.post_a != 1.f || p.post_b != 0.f) {        // as conv_epilogue_tile: the affine is the identity almost everywhere
 #pragma unroll
         for (int e = 0; e < 16; ++e) v[e] = v[e] * p.post_a + p.post_b;
     }
@@ -312,7 +293,6 @@ __device__ __forceinline__ float conv_epilogue_dot(const ConvParams& p, const fl
 int launch_conv_patch(const ConvParams& p, int n_img, hipStream_t st);
 // one filter column per step over a 16-channel patch (conv_col.hip, F_COL): 9x9 / 7x7 / 5x5, <= 64 couts
 int launch_conv_col(const ConvParams& p, int n_img, hipStream_t st);
-int launch_conv_col3w(const ConvParams& p, int n_img, hipStream_t st);
 // depthwise k x k conv fused in front of a 1x1 conv (conv_dwpw.hip, F_DWPRE): p.kh / sh / ph = the depthwise geometry, p.dotw = its table
 int launch_conv_dwpw(const ConvParams& p, hipStream_t st);
 bool conv_dwpw_ok(int k, int s, int cinp, int Np, int flags);
@@ -320,9 +300,6 @@ int conv_dwpw_rows_stride(int k, int pad, int s, int cinp, int lo_in);      // s
 // 3x3 sibling, two blocks per CU (conv_c3.hip, F_COL with kh = kw = 3)
 int launch_conv_c3(const ConvParams& p, int n_img, hipStream_t st);
 double conv_c3_plan(int OH, int OW, int* rw_out);
-// all couts per block, one persistent block per CU (conv_c3w.hip): the 3x3 layers with 128 couts
-int launch_conv_c3w(const ConvParams& p, int n_img, hipStream_t st);
-bool conv_c3w_ok(const ConvParams& p);
 bool conv_c3_ok(int kh, int kw, int sh, int sw, int ph, int pw, int cinp, int flags);
 // pointwise conv over <= 64 input channels and <= 64 couts, no LDS staging (conv_pw.hip, F_PW)
 int launch_conv_pw(const ConvParams& p, hipStream_t st);

@@ -14,26 +14,19 @@
 //   output = the shared conv epilogue (bias, activation, residual, gate, pair store)
 // Bound: measured VALU (round 4 counters: ~500 vector instructions per 32-pixel tile and wave, the vector pipe 65-85 % busy) — by bytes it
 // would be HBM (input once + output; L1 serves k * k x the input bytes).  The taps are v_fma_mix_f32 (fp16 x fp32 + fp32, no conversions).
-#include <stdlib.h>
 #include <type_traits>
 #include "conv_common.h"
 
 // aux blob (fp32 words, ints by bit pattern): [0] k  [1] stride  [2] pad  [3] act  [4] act_a  [5] act_b  [6] post_a  [7] post_b, then the
 // depthwise table [k * k + 1][KS * 16]
-#ifdef VSE_DEV_BUILD
-// ablation mask of tools/ablate_dwpw.sh (development builds only): 1 no output stores, 2 only the centre tap is loaded and multiplied,
-// 4 all taps loaded but only the centre one multiplied, 8 no MFMAs
-__device__ int dwpw_abl_dev = 0;
-#define DWPW_ABL(bit) (abl & (bit))
-#else
-#define DWPW_ABL(bit) false
-#endif
+
+// 32-pixel tiles per wave; a block = 4 waves x DWPW_TPW tiles.  1 beats 2 by 2.8 % on the box-exact mobile detector (6.40 -> 6.22 ms; layer by
+// layer +-0, round 5) and 4 loses 3 %: a wave that stores and exits frees its slot for one that loads — stores share the in-order vmcnt queue
+// with the next tile's loads
+constexpr int DWPW_TPW = 1;
 
 template <int KS, int K, bool LO>
 __global__ __launch_bounds__(256, (KS <= 2 ? 4 : KS <= 4 ? 3 : 2)) void conv_dwpw_kernel(const ConvParams p) {
-#ifdef VSE_DEV_BUILD
-    const int abl = dwpw_abl_dev;
-#endif
     extern __shared__ __attribute__((aligned(16))) char dlds[];
     constexpr int ROWH = KS * 16 + 8, CP = KS * 16, K2 = K * K;
     const int ntile = (p.Np + 31) >> 5;
@@ -67,10 +60,7 @@ __global__ __launch_bounds__(256, (KS <= 2 ? 4 : KS <= 4 ? 3 : 2)) void conv_dwp
 
     __syncthreads();
     const int wr = conv_wrow(fx);
-#ifndef VSE_DWPW_TPW
-#define VSE_DWPW_TPW 1          // 32-pixel tiles per wave; a block = 4 waves x TPW tiles.  1 beats 2 by 2.8 % on the box-exact mobile detector (6.40 -> 6.22 ms; layer by layer +-0: tools/ab_dwpw_tpw.sh, round 5) and 4 loses 3 %: a wave that stores and exits frees its slot for one that loads — stores share the in-order vmcnt queue with the next tile's loads
-#endif
-    constexpr int TPW = VSE_DWPW_TPW;
+    constexpr int TPW = DWPW_TPW;
     const long m0 = (long)xcd_block(blockIdx.x, gridDim.x) * (128 * TPW) + wave * (32 * TPW);       // (XCD-contiguous block order: common.h)
     // one 32-pixel MFMA tile at a time (a rolled loop: the two tiles of a wave share no registers — unrolled, hipcc kept both tiles' loads,
     // fragments and accumulators live and spilled hundreds of bytes per lane)
@@ -109,12 +99,11 @@ __global__ __launch_bounds__(256, (KS <= 2 ? 4 : KS <= 4 ? 3 : 2)) void conv_dwp
                     if constexpr (LO) lv[dx] = *reinterpret_cast<const half8*>(rowp + (long)cx * p.in_ld + lo_in);
                 }
             };
-            const int dy_begin = DWPW_ABL(2) ? K / 2 : 0, dy_end = DWPW_ABL(2) ? K / 2 + 1 : K;
-            load_row(dy_begin, xr, lr);
+            load_row(0, xr, lr);
 #pragma unroll 1
-            for (int dy = dy_begin; dy < dy_end; ++dy) {
+            for (int dy = 0; dy < K; ++dy) {
                 half8 xn[K], ln[K];
-                load_row(dy + 1 < dy_end ? dy + 1 : dy, xn, ln);          // (the last iteration re-reads its own row: an L1 hit, no branch)
+                load_row(dy + 1 < K ? dy + 1 : dy, xn, ln);          // (the last iteration re-reads its own row: an L1 hit, no branch)
                 const int iy = iy0 + dy;
                 // A tap outside the image is zeroed on the PACKED halves (4 selects per vector) — only in tiles that touch the border:
                 // `inside` is wave-uniform (every lane's 3 x 3 window lies in the image: ~85 % of the tiles at 272 x 480), and the
@@ -123,11 +112,6 @@ __global__ __launch_bounds__(256, (KS <= 2 ? 4 : KS <= 4 ? 3 : 2)) void conv_dwp
                 auto taps = [&](auto sel) {
 #pragma unroll
                     for (int dx = 0; dx < K; ++dx) {
-                        if (DWPW_ABL(4) && dy != K / 2) {
-                            asm volatile("" :: "v"(xr[dx]));
-                            if constexpr (LO) asm volatile("" :: "v"(lr[dx]));
-                            continue;
-                        }
                         const int ix = ix0 + dx;
                         // (unsigned compares, bitwise and: a short-circuit && compiles to branches, which split the block)
                         const bool ok = ((unsigned)iy < (unsigned)p.H) & ((unsigned)ix < (unsigned)p.W);
@@ -171,14 +155,13 @@ __global__ __launch_bounds__(256, (KS <= 2 ? 4 : KS <= 4 ? 3 : 2)) void conv_dwp
             for (int ks = 0; ks < KS; ++ks) {
                 const half8 wh = *reinterpret_cast<const half8*>(swt + (j * 32 + wr) * ROWH + ks * 16 + fj * 8);
                 const half8 wl = *reinterpret_cast<const half8*>(swt + ((ntile + j) * 32 + wr) * ROWH + ks * 16 + fj * 8);
-                if (DWPW_ABL(8)) { acc[0] += (float)xh[ks][0] + (float)xl[ks][1] + (float)wh[0] + (float)wl[1]; continue; }
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh[ks], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh[ks], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl[ks], acc, 0, 0, 0);
             }
             float bias[16];
             conv_epilogue_consts(sbias, j * 32, lane, bias);
-            if (mraw < p.M && (!DWPW_ABL(1) || acc[3] == 1234.5678f)) conv_epilogue_tile(p, acc, bias, mraw, n, oh, ow, j * 32, lane);
+            if (mraw < p.M) conv_epilogue_tile(p, acc, bias, mraw, n, oh, ow, j * 32, lane);
         }
     }
 }
@@ -191,8 +174,8 @@ __global__ __launch_bounds__(256, (KS <= 2 ? 4 : KS <= 4 ? 3 : 2)) void conv_dwp
 // instead of 9 — and the block's prologue is paid once per 4 x RS x 32 pixels.  The filter rows of an input row are applied to the
 // (up to three) output rows it belongs to, each output row keeping its own fp32 accumulator: an accumulator still receives
 // bias, then filter row 0 (dx 0 hi, lo, dx 1 ...), row 1, row 2 IN THE ORDER OF conv_dwpw_kernel, the activation / hi + lo split / MFMA
-// order / epilogue are the same code — every output bit is the tile form's (development build: `tools/ab_env_digest.py VSE_DWPW_ROWS 0 1`,
-// identical digests of both mobile detectors; the product tests hold it to the emulator and to the real detector's boxes).
+// order / epilogue are the same code — every output bit is the tile form's (round 5: identical output digests of both mobile detectors
+// with either form; the product tests hold it to the emulator and to the real detector's boxes).
 //   stride 1: state = A (output row r: filter rows 0, 1 applied), B (row r + 1: filter row 0); input row r + 1 arrives:
 //             A += row 2 -> finished;  A(reused) = bias + row 0 (output row r + 2);  B += row 1;  roles swap.
 //   stride 2: state = A (output row r: filter row 0 applied); input row 2r: A += row 1; input row 2r + 1: A += row 2 -> finished;
@@ -453,15 +436,9 @@ __global__ __launch_bounds__(256, 2) void conv_dwpw_rows_kernel(const ConvParams
     }
 }
 
-// 5 x 5 filters stay on two launches (25 taps per lane: 0.21 against 0.09 + 0.04 ms, and the unrolled form spills): the 5 x 5 instantiations
-// exist in development builds only (VSE_DEV_BUILD, compiler.py VSE_DWPW_K=3,5)
-#ifdef VSE_DEV_BUILD
-#define DWPW_K5 1
-#else
-#define DWPW_K5 0
-#endif
+// 5 x 5 filters stay on two launches (25 taps per lane: 0.21 against 0.09 + 0.04 ms, and the unrolled form spills)
 bool conv_dwpw_ok(int k, int s, int cinp, int Np, int flags) {
-    return (k == 3 || (DWPW_K5 && k == 5)) && (s == 1 || s == 2) && (cinp & 7) == 0 && cinp <= 96 && Np <= 192 && (flags & F_HILO)
+    return k == 3 && (s == 1 || s == 2) && (cinp & 7) == 0 && cinp <= 96 && Np <= 192 && (flags & F_HILO)
            && !(flags & (F_SRC2 | F_DOT1 | F_PATCH | F_COL | F_PIXSHUF | F_IMGW | F_STEM));
 }
 
@@ -474,15 +451,8 @@ static int launch_dwpw_t(const ConvParams& p, hipStream_t st) {
             return hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dwpw_kernel<KS, K, LO>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess;
         }))
         return VSE_E_HIP;
-    const unsigned long long blocks = (unsigned long long)((p.M + 128 * VSE_DWPW_TPW - 1) / (128 * VSE_DWPW_TPW));
+    const unsigned long long blocks = (unsigned long long)((p.M + 128 * DWPW_TPW - 1) / (128 * DWPW_TPW));
     if (blocks == 0 || p.M >= 0x7fffffffl || lds > 128 * 1024) return VSE_E_INVAL;          // (32-bit pixel arithmetic: conv_pix_coords)
-#ifdef VSE_DEV_BUILD
-    static int abl_set = -1;
-    if (abl_set < 0) {
-        abl_set = getenv("VSE_DWPW_ABL") ? atoi(getenv("VSE_DWPW_ABL")) : 0;
-        if (hipMemcpyToSymbol(HIP_SYMBOL(dwpw_abl_dev), &abl_set, sizeof(int)) != hipSuccess) return VSE_E_HIP;
-    }
-#endif
     hipLaunchKernelGGL((conv_dwpw_kernel<KS, K, LO>), dim3((unsigned)blocks), dim3(256), lds, st, p);
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
@@ -534,14 +504,12 @@ static int launch_dwpw_rows_t(const ConvParams& pin, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
 
-// VSE_DWPW_ROWS=0 (development builds) keeps the tile form for A/B runs and the bit-identity check (tools/ab_env_digest.py)
 // Only PAIR inputs take it: on plain fp16 inputs (the layer-by-layer programs) the tile form measures the same or better (16 -> 32
 // @272 x 480: 0.373 vs 0.365 ms, 48 -> 48 @136 x 240: 0.215 vs 0.286) — half the gathers and half the multiply-adds per pixel leave
 // little for the strip walk to save.
 int conv_dwpw_rows_stride(int k, int pad, int s, int cinp, int lo_in) {
-    static const bool on = [] { const char* e = vse_dev_getenv("VSE_DWPW_ROWS"); return !(e && e[0] == '0'); }();
     const int ks = (cinp + 15) / 16;
-    return (on && lo_in != 0 && k == 3 && pad == 1 && ((s == 1 && ks <= DWPW_ROWS_MAX_KS_S1) || (s == 2 && ks <= DWPW_ROWS_MAX_KS))) ? s : 0;
+    return (lo_in != 0 && k == 3 && pad == 1 && ((s == 1 && ks <= DWPW_ROWS_MAX_KS_S1) || (s == 2 && ks <= DWPW_ROWS_MAX_KS))) ? s : 0;
 }
 static bool dwpw_rows_wanted(const ConvParams& p, int ks) { (void)ks; return conv_dwpw_rows_stride(p.kh, p.ph, p.sh, p.cinp, p.in_lo_off) != 0; }
 
@@ -558,12 +526,7 @@ int launch_conv_dwpw(const ConvParams& p, hipStream_t st) {
         }
 #undef DWPW_ROWS
     }
-#if DWPW_K5
-#define DWPW(KS_) (p.in_lo_off ? (p.kh == 3 ? launch_dwpw_t<KS_, 3, true>(p, st) : launch_dwpw_t<KS_, 5, true>(p, st)) \
-                               : (p.kh == 3 ? launch_dwpw_t<KS_, 3, false>(p, st) : launch_dwpw_t<KS_, 5, false>(p, st)))
-#else
 #define DWPW(KS_) (p.in_lo_off ? launch_dwpw_t<KS_, 3, true>(p, st) : launch_dwpw_t<KS_, 3, false>(p, st))
-#endif
     switch (ks) {
         case 1: return DWPW(1);
         case 2: return DWPW(2);

@@ -16,20 +16,11 @@
 //
 // Eligibility and the tile configuration are decided in launch_conv_gemm(); everything else stays on conv_mfma_kernel.
 
-#include <stdlib.h>
 #include <type_traits>
 #include "conv_common.h"
 
-#ifndef VSE_GEMM_NT_A
-#define VSE_GEMM_NT_A 0   // 1: non-temporal hint (aux = 2) on the ACTIVATION stream of the implicit GEMM (read once per launch by one block,
-                          // while the weight tiles are re-read by every block and should keep the L2); A/B: tools/ab.sh conv_gemm VSE_GEMM_NT_A
-#endif
-#ifndef VSE_GEMM_ASM
-#define VSE_GEMM_ASM 0    // 1: LDS-DMAs as asm statements (counted lgkmcnt waits survive; measured 1-3 % SLOWER here: the kernel is bound by the DMA stream, the asm form adds issue slots); 0: builtins.  A/B on one box: tools/ab.sh
-#endif
-#ifndef VSE_ABLATE
-#define VSE_ABLATE 0      // 1: no s_barrier  2: no fragment ds_reads  3: no DMA in the loop  4: no MFMA  5: no epilogue   (timing experiments only)
-#endif
+// The LDS-DMAs are builtins: as asm statements (counted lgkmcnt waits survive) they measured 1-3 % SLOWER — the kernel is bound by
+// the DMA stream, and the asm form adds issue slots.
 
 // BM x BN block tile (pixels x couts), WM x WN waves, BKT-deep K tiles in an ST-stage LDS ring.
 // MASK = 0: 1x1, no padding, K % 64 == 0 -> every (row, k) of a valid row is a real element, no tap mask.
@@ -103,13 +94,8 @@ void conv_gemm_kernel(const ConvParams p) {
         const long n = t / p.OH;
         pix0 = (n * p.Hs + (long)oh * p.sh - p.ph) * p.Ws + (long)ow * p.sw - p.pw;
     }
-#if VSE_GEMM_ASM
-    const rsrc4_t rsA = make_rsrc4(p.in + pix0 * p.in_ld);
-    const rsrc4_t rsW = make_rsrc4(wsrc + (long)n0 * ((p.flags & F_WK32) ? 32 : 64));
-#else
     const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + pix0 * p.in_ld), 0, 0x7fffffff, 0x00020000);
     const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)(wsrc + (long)n0 * ((p.flags & F_WK32) ? 32 : 64)), 0, 0x7fffffff, 0x00020000);
-#endif
 
     // ---- per-thread, loop-invariant offsets ------------------------------------------------------------------
     // wave instruction j of this wave covers tile rows (j*NW + wave)*RPI .. +RPI-1; lane l -> row + l/KV, physical
@@ -163,21 +149,13 @@ void conv_gemm_kernel(const ConvParams p) {
         for (int j = 0; j < NA; ++j) {
             unsigned off = voffA[j];
             if constexpr (MASK) off |= __builtin_amdgcn_ubfe(ntap[j], (unsigned)tap, 1u) << 31;   // v_bfe_u32 + v_lshl_or_b32
-#if VSE_GEMM_ASM
-            bufdma16_asm(rsA, off, soffA, base + (j * NW + wave) * RPI * BKT);
-#else
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (ldsv_t)(base + (j * NW + wave) * RPI * BKT), 16, (int)off, soffA, 0, VSE_GEMM_NT_A ? 2 : 0);
-#endif
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (ldsv_t)(base + (j * NW + wave) * RPI * BKT), 16, (int)off, soffA, 0, 0);
         }
         const int soffW = wk32 ? (int)((unsigned)kt * (BKT / 32) * wstep)
                          : BKT == 64 ? (int)((unsigned)kt * wstep) : (int)((unsigned)(kt >> 1) * wstep + (unsigned)(kt & 1) * 64u);
 #pragma unroll
         for (int j = 0; j < NB; ++j)
-#if VSE_GEMM_ASM
-            bufdma16_asm(rsW, voffW[j], soffW, base + BM * BKT + (j * NW + wave) * RPI * BKT);
-#else
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (ldsv_t)(base + BM * BKT + (j * NW + wave) * RPI * BKT), 16, (int)voffW[j], soffW, 0, 0);
-#endif
         kc += BKT;
         if (kc >= p.cinp) {
             kc = 0;
@@ -195,7 +173,7 @@ void conv_gemm_kernel(const ConvParams p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    conv_stage_consts<VSE_GEMM_ASM != 0>(sbias, p.bias, p.zero, n0, BN, p.Np, wave, lane);
+    conv_stage_consts(sbias, p.bias, p.zero, n0, BN, p.Np, wave, lane);
 #pragma unroll
     for (int s = 0; s < ST - 1; ++s)
         if (s < p.nk) issue(s, s);
@@ -224,13 +202,9 @@ void conv_gemm_kernel(const ConvParams p) {
         else if (ST >= 5 && rem == 2) wait_vm<2 * LPT>();
         else if (ST >= 4 && rem == 1) wait_vm<LPT>();
         else wait_vm<0>();
-#if VSE_ABLATE != 1
         __builtin_amdgcn_s_barrier();              // every thread's part of tile kt is in LDS; compute(kt-1) is over
-#endif
         asm volatile("" ::: "memory");
-#if VSE_ABLATE != 3
         if (kt + ST - 1 < p.nk) issue(kt + ST - 1, (S + ST - 1) % ST);
-#endif
         // fragment reads in groups of KG k sub-steps (<= 16 ds_read_b128 in flight), each followed by its MFMAs
         // (16-wave tiles run 4 waves per SIMD = 128 VGPRs: at most 8 fragments = 32 VGPRs in flight beside the accumulators)
         constexpr int FCAP = NW >= 16 ? 8 : 16;
@@ -242,18 +216,10 @@ void conv_gemm_kernel(const ConvParams p) {
             for (int ks = 0; ks < KG; ++ks) {
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
-#if VSE_ABLATE == 2
-                    wf[ks][j] = half8{(half_t)lane, 0, 0, 0, 0, 0, 0, 0};
-#else
                     wf[ks][j] = *reinterpret_cast<const half8*>(wptr[k0 + ks] + (S * STAGE_HALFS + j * 32 * BKT) * 2);
-#endif
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
-#if VSE_ABLATE == 2
-                    xf[ks][i] = half8{(half_t)kt, 0, 0, 0, 0, 0, 0, 0};
-#else
                     xf[ks][i] = *reinterpret_cast<const half8*>(xptr[k0 + ks] + (S * STAGE_HALFS + i * 32 * BKT) * 2);
-#endif
             }
 #pragma unroll
             for (int ks = 0; ks < KG; ++ks)
@@ -261,11 +227,7 @@ void conv_gemm_kernel(const ConvParams p) {
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
-#if VSE_ABLATE == 4
-                        acc[i][j][0] += (float)wf[ks][j][0] + (float)xf[ks][i][0];
-#else
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[ks][j], xf[ks][i], acc[i][j], 0, 0, 0);
-#endif
             __builtin_amdgcn_sched_group_barrier(0x100, KG * (TM + TN), 0);   // this group's ds_reads ...
             __builtin_amdgcn_sched_group_barrier(0x008, KG * TM * TN, 0);     // ... then its MFMAs
         }
@@ -301,15 +263,11 @@ void conv_gemm_kernel(const ConvParams p) {
         const int oh = (int)(t % p.OH);
         const long n = t / p.OH;
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
-#if VSE_ABLATE == 5
-            if (acc[i][j][0] == 12345.678f)
-#endif
-            {
-                float bias[16];
-                conv_epilogue_consts(sbias, wn * WTN + j * 32, lane, bias);
-                conv_epilogue_tile(p, acc[i][j], bias, m, n, oh, ow, n0 + wn * WTN + j * 32, lane);
-            }
+        for (int j = 0; j < TN; ++j) {
+            float bias[16];
+            conv_epilogue_consts(sbias, wn * WTN + j * 32, lane, bias);
+            conv_epilogue_tile(p, acc[i][j], bias, m, n, oh, ow, n0 + wn * WTN + j * 32, lane);
+        }
     }
 }
 
@@ -343,20 +301,12 @@ struct GemmCfg { int bm, bn, bk; };
 static const GemmCfg kCfg[] = {{128, 128, 32}, {256, 64, 32}, {256, 32, 32}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {256, 128, 32},
                                {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0},
                                {256, 256, 32}, {256, 192, 32}, {256, 256, 64}, {256, 192, 64}};
-constexpr int kNumCfg = sizeof(kCfg) / sizeof(kCfg[0]);
 
 // Which configuration serves a layer.  The kernel is bound by the L2 -> LDS fill (ablation: MFMAs and fragment reads
 // are free, the DMA stream and the store tail are not), so the choice minimises fetched bytes: one cout tile when the
 // couts fit 192 / 256 (the activation tile is then fetched once instead of 2-3 times), 256-pixel tiles (weights re-read
 // half as often), as long as the grid still fills the 256 CUs.  Zero-padded couts cost MFMA issue slots only.
 int conv_gemm_config(int Np, int cinp, long M) {
-#ifdef VSE_DEV_BUILD
-    const char* e = getenv("VSE_GEMM_CFG");          // experiments: force a configuration where it is legal
-    if (e && e[0]) {
-        const int c = atoi(e);
-        if (c >= 0 && c < kNumCfg && kCfg[c].bm && cinp % kCfg[c].bk == 0) return c;
-    }
-#endif
     auto ntn = [&](int bn) { return (long)((Np + bn - 1) / bn); };
     // the 16-wave tiles run 64-deep K tiles in a 2-stage ring where the channels allow it (whole 128-byte lines per
     // activation row and half the barriers; A/B on one box: -2..-4 %); the 8-wave 256 x 128 tile loses its second block per CU

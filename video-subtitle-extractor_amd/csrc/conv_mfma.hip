@@ -328,11 +328,8 @@ int launch_conv(const ConvArgs& a, hipStream_t st) {
         p.nkh = a.Kp / ((a.flags & F_WK32) ? 32 : 64);
         return launch_conv_smallm(p, st);
     }
-    static const bool use_gemm = [] { const char* e = vse_dev_getenv("VSE_CONV_GEMM"); return !(e && e[0] == '0'); }();
-    if (use_gemm) {
-        const int rc = launch_conv_gemm(p, a.Kp, st);
-        if (rc != VSE_E_UNSUPPORTED) return rc;
-    }
+    const int rc = launch_conv_gemm(p, a.Kp, st);
+    if (rc != VSE_E_UNSUPPORTED) return rc;
     if (a.flags & F_WK32) return VSE_E_UNSUPPORTED;     // 32-deep weight tiles are read by conv_gemm_kernel only
     const int bn = conv_tile_bn(a.Np);
     dim3 block(256);

@@ -23,26 +23,12 @@
 //   weights are packed [chunk][tap][Np][32] by the compiler for this kernel (F_PATCH) so the stream is sequential;
 //   taps in COLUMN-major order (dx outer, dy inner): consecutive taps of a column share one of their two activation
 //   fragments, which is carried in registers (LDS fragment reads per MFMA 1.0 -> 0.78 for 9x9).
-#include <stdlib.h>
 #include "conv_common.h"
 #ifdef VSE_TRACE
 #include <stdio.h>
 #include <vector>
 #endif
 
-#ifndef VSE_ABLATE
-#define VSE_ABLATE 0      // 1: no s_barrier  2: no fragment ds_reads  3: no weight/patch DMA  4: no MFMA   (timing experiments only)
-#endif
-
-#ifndef VSE_PIPE
-#define VSE_PIPE 1        // software-pipelined fast step (A/B on one box: tools/ab.sh conv_patch VSE_PIPE ...)
-#endif
-#ifndef VSE_PIPE128
-#define VSE_PIPE128 0     // ... also for the 128-cout LIGHT tile (spills: 68 bytes of scratch per lane)
-#endif
-#ifndef VSE_EDGE_SKIP
-#define VSE_EDGE_SKIP 1   // waves whose output rows lie below the map skip their fragment reads and MFMAs (A/B: tools/ab.sh)
-#endif
 #define PTW 32
 #define PRING 4
 
@@ -72,7 +58,8 @@ __global__ __launch_bounds__(512, MODE == 2 ? 4 : 2) void conv_patch_kernel(cons
     constexpr int RROWS = LIGHT ? BN : 64;          // weight rows per tap in a ring stage
     constexpr int TPS = LIGHT ? 2 : 4;              // filter taps per step: 16 / 32 MFMAs per wave between barriers
     constexpr int RING = (BIGP || LIGHT) ? 2 : PRING;   // weight ring stages (2 where LDS is tight: 960-pixel patch, two blocks per CU)
-    constexpr bool PIPE = VSE_ABLATE == 0 && VSE_PIPE && (VSE_PIPE128 || !(LIGHT && BN == 128));   // fast step (below); the 128-cout LIGHT tile has no registers to spare
+    // software-pipelined fast step (below); the 128-cout LIGHT tile has no registers to spare (with it: 68 bytes of scratch per lane)
+    constexpr bool PIPE = !(LIGHT && BN == 128);
     constexpr int LOOK = RING - 1;                  // stages in flight ahead of the one being consumed
     constexpr int PATCH_HALFS = PPIX * 32, WSTAGE_HALFS = TPS * RROWS * 32;
     // landing zone of surplus DMAs (whole wave instructions past the patch / past a 64-row weight stage)
@@ -182,7 +169,7 @@ __global__ __launch_bounds__(512, MODE == 2 ? 4 : 2) void conv_patch_kernel(cons
     // ragged bottom edge: a wave whose two output rows both lie below the map only takes part in the DMA issue and the
     // barriers; its partner on the SIMD gets the matrix pipe to itself, so a tile with half of its rows valid costs about
     // half a tile (136 rows under 16-row tiles: 8.5 tiles' worth of time instead of 9)
-    const bool wave_live = VSE_EDGE_SKIP == 0 || (oy0 + 2 * wpx) < p.OH;
+    const bool wave_live = (oy0 + 2 * wpx) < p.OH;
     const char* const ring_b = reinterpret_cast<const char*>(ring0);
 
     float16v acc[2][TN];
@@ -227,15 +214,12 @@ __global__ __launch_bounds__(512, MODE == 2 ? 4 : 2) void conv_patch_kernel(cons
                 if (pr == 1 || pr == 2) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
                 else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
             }
-#if VSE_ABLATE != 1
             __builtin_amdgcn_s_barrier();
-#endif
             asm volatile("" ::: "memory");
 #ifdef VSE_TRACE
             t_sync += __builtin_amdgcn_s_memtime() - tw0;
             if (s == 0) TR_STAMP(2);
 #endif
-#if VSE_ABLATE != 3
             if constexpr (BIGP || LIGHT) {                 // weights first: the patch may then outlive the next wait
                 issue_w(s + LOOK);
                 if (pr == 0) issue_patch(cc + 1, (cc + 1) & 1);
@@ -243,7 +227,6 @@ __global__ __launch_bounds__(512, MODE == 2 ? 4 : 2) void conv_patch_kernel(cons
                 if (pr == 0) issue_patch(cc + 1, (cc + 1) & 1);
                 issue_w(s + LOOK);
             }
-#endif
         };
         int pr = 0;
         // FAST STEPS: all TPS taps are real and at most one of them starts a filter column (kh >= TPS).  Straight-line code,
@@ -330,10 +313,6 @@ __global__ __launch_bounds__(512, MODE == 2 ? 4 : 2) void conv_patch_kernel(cons
                     if (!wave_live) break;
                     if (ks == 1 && klim1) break;           // channel tail <= 16: upper half of the chunk is all zeros
                     half8 wf[TN], xf[2];
-#if VSE_ABLATE == 2
-                    for (int j = 0; j < TN; ++j) for (int e = 0; e < 8; ++e) wf[j][e] = (half_t)(float)(q0 + e + j);
-                    for (int e = 0; e < 8; ++e) { xf[0][e] = (half_t)(float)(q1 + e); xf[1][e] = (half_t)(float)(q0 - e); }
-#else
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
                         wf[j] = *reinterpret_cast<const half8*>(ring_b + wsb + h * (RROWS * 64) + (woffb[j] ^ (ks << 5)));
@@ -341,16 +320,11 @@ __global__ __launch_bounds__(512, MODE == 2 ? 4 : 2) void conv_patch_kernel(cons
                     else xf[0] = xc[ks];
                     xf[1] = *reinterpret_cast<const half8*>(pb + (a1 ^ (ks << 5)));
                     xc[ks] = xf[1];
-#endif
 #pragma unroll
                     for (int i = 0; i < 2; ++i)
 #pragma unroll
                         for (int j = 0; j < TN; ++j)
-#if VSE_ABLATE == 4
-                            { acc[i][j][0] += (float)wf[j][0] * (float)xf[i][0]; asm volatile("" : "+v"(acc[i][j][0])); }
-#else
                             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[j], xf[i], acc[i][j], 0, 0, 0);
-#endif
                 }
                 if (++tap < taps) {
                     if (++dy == p.kh) { dy = 0; tapoff = ++dx; } else { tapoff += PW; }
@@ -423,14 +397,9 @@ __global__ __launch_bounds__(512, MODE == 2 ? 4 : 2) void conv_patch_kernel(cons
 //   mode 2 (LIGHT, 8-row tiles, 64 or 128 couts, two blocks per CU) when the halo patch of an 8 x 32 tile fits 352 pixels
 //   (3x3, 1xk) and no 1-channel projection is fused (that needs all couts of a pixel in one wave);
 //   else 64 couts per tile, 16-row tiles when they fit the 960-pixel patch (mode 1 above 640 pixels), else 8-row tiles.
-static int patch_light_policy() {       // VSE_PATCH_LIGHT: 0 never, 1 only layers with more than 64 couts, 2 every eligible layer
-    static const int v = [] { const char* e = vse_dev_getenv("VSE_PATCH_LIGHT"); return e && e[0] ? atoi(e) : 2; }();
-    return v;
-}
 void conv_patch_plan(int kh, int kw, int OH, int Np, int flags, int* th, int* bn, int* mode) {
     const bool fits = (8 + kh - 1) * (PTW + kw - 1) <= 352 && !(flags & (F_DOT1 | F_SRC2));
-    const int pol = patch_light_policy();
-    if (fits && (pol >= 2 || (pol == 1 && Np > 64))) {
+    if (fits) {
         *th = 8; *bn = Np > 64 ? 128 : 64; *mode = 2;
         return;
     }

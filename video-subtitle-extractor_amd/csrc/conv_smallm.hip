@@ -77,8 +77,7 @@ __global__ __launch_bounds__(64) void conv_smallm_hl_kernel(const ConvParams p) 
 
 // Layers this kernel serves: conv_gemm_kernel's unmasked 1x1 mode (mode 2) at stride 1 with at most 256 pixels, one weight stream.
 bool conv_smallm_shape_ok(int mode, long M, int sh, int sw, int same_hw, int flags, int cinp) {
-    static const bool on = [] { const char* e = vse_dev_getenv("VSE_SMALLM"); return !(e && e[0] == '0'); }();
-    return on && mode == 2 && M <= 256 && sh == 1 && sw == 1 && same_hw && !(flags & (F_IMGW | F_PIXSHUF | F_DOT1 | F_SRC2)) && (cinp & 15) == 0;
+    return mode == 2 && M <= 256 && sh == 1 && sw == 1 && same_hw && !(flags & (F_IMGW | F_PIXSHUF | F_DOT1 | F_SRC2)) && (cinp & 15) == 0;
 }
 bool conv_smallm_ok(const ConvParams& p, int mode) {
     return conv_smallm_shape_ok(mode, p.M, p.sh, p.sw, p.H == p.OH && p.W == p.OW && p.Hs == p.H && p.Ws == p.W, p.flags, p.cinp);
@@ -88,8 +87,7 @@ bool conv_smallm_ok(const ConvParams& p, int mode) {
 // sequence's [crops, 1, T, 120] layers.  Such a launch is a handful of K steps behind a prologue and in front of an epilogue on 13-50 of
 // 256 CUs (13-23 us launch to launch); here every wave is its own block with ALL its loads in flight at once.  Same K order, same bits.
 bool conv_smallk_shape_ok(int kh, int kw, int sh, int sw, int ph, int pw, int inshift, int same_hw, int flags, int cinp, long M, int Np) {
-    static const bool on = [] { const char* e = vse_dev_getenv("VSE_SMALLK"); return !(e && e[0] == '0'); }();
-    return on && kh == 1 && kw == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0 && !inshift && same_hw && cinp > 0 && cinp <= 256 && (cinp & 7) == 0
+    return kh == 1 && kw == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0 && !inshift && same_hw && cinp > 0 && cinp <= 256 && (cinp & 7) == 0
            && !(flags & (F_IMGW | F_PIXSHUF | F_DOT1 | F_SRC2 | F_PATCH | F_COL | F_PW | F_STEM | F_UP2HEAD | F_DWPRE | F_ONECH | F_TAIL2 | F_HLSUM))
            && M > 0 && ((M + 31) / 32) * ((Np + 31) / 32) <= 4096;
 }

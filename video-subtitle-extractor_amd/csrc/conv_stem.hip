@@ -16,9 +16,7 @@
 #include "conv_common.h"
 #include "resize_u8.h"
 
-#ifndef VSE_STEM_WIDE
-#define VSE_STEM_WIDE 1
-#endif
+
 #define ST_ROWS 8
 #define ST_COLS 32
 

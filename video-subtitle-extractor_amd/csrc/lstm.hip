@@ -156,16 +156,15 @@ __global__ __launch_bounds__(1024, 4) void lstm_mfma16_kernel(TView gates_f, TVi
     float c[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) c[i] = 0.f;
-#ifndef LSTM16_WQ
-#define LSTM16_WQ 2       // fragments in flight: 4 spills 15 VGPRs at the 128-register budget of 4 waves per SIMD and is 10 % SLOWER (2.46 vs 2.22 ms per layer, tools/ab_lstm_wq.sh, round 5); 8 spills ~25 and is 12 % slower still
-#endif
-    constexpr int WQ = LSTM16_WQ, SPC = WQ / 2, NCH = 16 / SPC;      // fragments in flight = SPC k-slices x two tiles; chunks per step
+    // WQ = 2 fragments in flight: 4 spills 15 VGPRs at the 128-register budget of 4 waves per SIMD and is 10 % SLOWER (2.46 vs 2.22 ms per
+    // layer, round 5); 8 spills ~25 and is 12 % slower still
+    constexpr int WQ = 2, SPC = WQ / 2, NCH = 16 / SPC;      // fragments in flight = SPC k-slices x two tiles; chunks per step
     half8 wq[WQ];
 #pragma unroll
     for (int f = 0; f < WQ; ++f) wq[f] = wfrag[(size_t)f * 64];
     auto fast_tanh = [](float x) { return 2.f / (1.f + __expf(-2.f * x)) - 1.f; };
     // gate pre-activations x . W_ih^T + b of the step (fp32, 16-byte pieces of 32 different rows per wave instruction: ~3 us of
-    // exposed latency per step when they were loaded at the step's start — tools/ablate_lstm.sh).  They are loaded ONE STEP AHEAD,
+    // exposed latency per step when they were loaded at the step's start — measured by ablation).  They are loaded ONE STEP AHEAD,
     // into the registers the cell arithmetic has just finished reading: the loads fly during the rest of the cell phase, the
     // barrier and the next step's MFMAs.
     float4v gx[4][2];
@@ -178,9 +177,7 @@ __global__ __launch_bounds__(1024, 4) void lstm_mfma16_kernel(TView gates_f, TVi
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 gx[g][q] = float4v{0.f, 0.f, 0.f, 0.f};
-#ifndef LSTM_ABL_NO_GX
                 if (act) gx[g][q] = *reinterpret_cast<const float4v*>(gp + g * 16 + 8 * q);
-#endif
             }
     };
     load_gx(0);
@@ -203,13 +200,9 @@ __global__ __launch_bounds__(1024, 4) void lstm_mfma16_kernel(TView gates_f, TVi
 #pragma unroll
                 for (int g = 0; g < 2; ++g) {
                     const half8 a = wq[u * 2 + g];
-#ifndef LSTM_ABL_NO_WLOAD
                     wq[u * 2 + g] = wnext[(size_t)(u * 2 + g) * 64];
-#endif
                     acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bh, acc[g], 0, 0, 0);
-#ifndef LSTM_ABL_NO_LO
                     acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bl, acc[g], 0, 0, 0);
-#endif
                 }
             }
         }
@@ -236,13 +229,9 @@ __global__ __launch_bounds__(1024, 4) void lstm_mfma16_kernel(TView gates_f, TVi
                 for (int e = 0; e < 4; ++e) {
                     const int i = 4 * q + e;
                     const float zi = acc[0][i], zf = acc[0][i + 8], zg = acc[1][i], zo = acc[1][i + 8];
-#ifdef LSTM_ABL_NO_CELL
-                    c[i] += zi + zf; const float h = zg + zo + c[i];
-#else
                     const float i_ = 1.f / (1.f + __expf(-zi)), f_ = 1.f / (1.f + __expf(-zf)), o_ = 1.f / (1.f + __expf(-zo));
                     c[i] = f_ * c[i] + i_ * fast_tanh(zg);
                     const float h = o_ * fast_tanh(c[i]);
-#endif
                     const half_t hi = (half_t)h;
                     hbuf[0][n][u0 + 8 * q + e] = hi;
                     hbuf[1][n][u0 + 8 * q + e] = (half_t)(h - (float)hi);

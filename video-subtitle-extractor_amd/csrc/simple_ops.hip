@@ -95,9 +95,6 @@ __global__ __launch_bounds__(256) void dwconv_kernel(TView in, TView out, TView 
     }
 }
 
-#ifndef VSE_DWROW_ABL
-#define VSE_DWROW_ABL 0
-#endif
 // Row-blocked variant: one thread produces FOUR consecutive output pixels of one row for one 8-channel group, so every
 // input vector of a filter row is loaded once for the outputs that share it ((4-1)*SW + KW loads instead of 4*KW) and every
 // weight vector once per tap instead of once per output.  Same accumulation order per output as dwconv_kernel (bias, then
@@ -145,9 +142,6 @@ __global__ __launch_bounds__(256) void dwconv_row_kernel(TView in, TView out, TV
 #pragma unroll
                 for (int c = 0; c < WIN; ++c) {
                     const int iw = iw0 + c;
-#if defined(VSE_DEV_BUILD) && VSE_DWROW_ABL == 2      // timing-only ablation: ONE gather per filter row (results wrong)
-                    if (c > 0) { x[c] = x[0]; continue; }
-#endif
                     x[c] = (!CHK || (iw >= 0 && iw < in.w)) ? ld8(in, rowpix + iw, g * 8 + coff) : half8{0, 0, 0, 0, 0, 0, 0, 0};
                 }
                 // all loads of the row first, arithmetic afterwards: multiplying each vector as it arrives serialises the loads
@@ -159,9 +153,6 @@ __global__ __launch_bounds__(256) void dwconv_row_kernel(TView in, TView out, TV
                 }
 #pragma unroll
                 for (int dx = 0; dx < KW; ++dx) {
-#if defined(VSE_DEV_BUILD) && VSE_DWROW_ABL == 1      // timing-only ablation: 1 / KW of the multiply-adds, every gather kept (results wrong)
-                    if (dx > 0) { asm volatile("" :: "v"(x[dx]), "v"(x[WIN - 1])); continue; }
-#endif
                     const float4v k0 = *reinterpret_cast<const float4v*>(w + (long)(dy * KW + dx) * in.c + g * 8);
                     const float4v k1 = *reinterpret_cast<const float4v*>(w + (long)(dy * KW + dx) * in.c + g * 8 + 4);
 #pragma unroll
@@ -206,7 +197,7 @@ __global__ __launch_bounds__(256) void dwconv_row_kernel(TView in, TView out, TV
 // column-walk form with 8 channels per thread and the table in LDS — 50 ds_read_b128 per input row — was 15 % SLOWER than the row kernel.)
 // Per accumulator the order is the row kernel's — bias, then taps row-major; rows outside the image skipped, columns outside read as zeros
 // (adding 0 * w is the skip, bit for bit, unless an accumulator is exactly -0) — and an fp32 fma of the exactly converted fp16 value is what
-// v_fma_mix_f32 computes: identical bits (development build: tools/ab_env_digest.py VSE_DW_COL 0 1).
+// v_fma_mix_f32 computes: identical bits (round 6: identical output digests with either kernel).
 // Plain fp16 tensors only (a pair input walks its hi rows, then its lo rows, into one chain: not streamable in that order), no gate, KW = KH
 // in {3, 5}, 'same' padding, horizontal stride 1, vertical stride 1 or 2: the mobile recognisers' depthwise layers.
 typedef float float2v __attribute__((ext_vector_type(2)));
@@ -315,108 +306,6 @@ __global__ __launch_bounds__(256) void dwconv_col_kernel(TView in, TView out, co
     }
 }
 
-#ifdef VSE_DEV_BUILD
-// (development builds only: measured, bit-identical to the row kernel and 10-25 % SLOWER on every model — DESIGN §3.2 log)
-// LDS-tile variant (round 4): the row kernel walks its kh filter rows as kh dependent global round trips per thread (loads of a row,
-// wait, ~200 VALU instructions, next row) at 3-4 waves per SIMD — on the mobile models' 5 x 5 layers it sits at 20 % of its bytes' time
-// (rec_fast: 14 depthwise layers = 39 % of the net).  Here a block of 256 threads owns TR output rows x 32 output columns x CGB 8-channel
-// groups (TR * CGB = 32): it pulls the input patch ((TR - 1) * sh + kh rows, 31 * SW + KW columns) into LDS with ONE batch of independent
-// 16-byte loads per thread (the SE gate applied on the way, once per element instead of once per use), and every thread then computes the
-// same four outputs as in the row kernel, its windows read from LDS.  Same arithmetic per output (bias, taps row-major, hi + lo weights
-// summed in fp32, padded taps skipped) -> bit-identical results.
-//   LDS layout: [plane hi | lo][row][column][CGB vectors of 16 bytes (+ pad)]; the pad (16 bytes for CGB = 4, 32 for CGB = 8) makes the 16
-//   lanes of a ds_read_b128 phase — CGB channel groups x 16 / CGB quads, quads 4 * SW columns apart — hit 16 distinct bank groups (SW = 1)
-template <int KW, int SW, int GM>
-__global__ __launch_bounds__(256) void dwconv_tile_kernel(TView in, TView out, TView gate, int hilo, const float* __restrict__ w,
-                                                          const float* __restrict__ bias, int kh, int sh, int ph, int pw,
-                                                          int act, float act_a, float act_b, float post_a, float post_b,
-                                                          const int* __restrict__ wl_out, int trl, int tiles_w, int tiles_h, int cgblocks) {
-    extern __shared__ __attribute__((aligned(16))) char tlds[];
-    constexpr int OUTW = 4, TC = 32, WIN = (OUTW - 1) * SW + KW, IC = (TC - 1) * SW + KW;
-    const int lo_off = ((hilo >> 1) & 0xfff) << 3, lo_in = ((hilo >> 13) & 0xfff) << 3;          // (see dwconv_kernel)
-    hilo &= 1;
-    const int TR = 1 << trl, cgbl = 5 - trl, CGB = 1 << cgbl;
-    const int IR = (TR - 1) * sh + kh;
-    const int colstride = CGB * 16 + (CGB == 4 ? 16 : CGB == 8 ? 32 : 0), rowstride = IC * colstride, plane = IR * rowstride;
-    const int cg = in.c >> 3;
-    unsigned b = xcd_block(blockIdx.x, gridDim.x);
-    const int cgb = (int)(b % (unsigned)cgblocks);  b /= (unsigned)cgblocks;
-    const int tx = (int)(b % (unsigned)tiles_w);  b /= (unsigned)tiles_w;
-    const int ty = (int)(b % (unsigned)tiles_h);
-    const long n = b / (unsigned)tiles_h;
-    const int cg0 = cgb * CGB, oy0 = ty * TR, ox0 = tx * TC;
-    const int iy0 = oy0 * sh - ph, ix0 = ox0 * SW - pw;
-    const int tid = threadIdx.x;
-    const bool dead_tile = wl_out != nullptr && ox0 >= wl_out[n];          // (ragged batch: right of the sample — zeros, nothing to read)
-    if (!dead_tile) {
-        const int nvec = IR * IC * CGB;
-        for (int v = tid; v < nvec; v += 256) {
-            const int g = v & (CGB - 1), rc = v >> cgbl, r = rc / IC, c = rc - r * IC;
-            const int iy = iy0 + r, ix = ix0 + c;
-            const bool ok = iy >= 0 && iy < in.h && ix >= 0 && ix < in.w && cg0 + g < cg;
-            half8 x = half8{0, 0, 0, 0, 0, 0, 0, 0}, xl = x;
-            if (ok) {
-                const long pix = (n * in.h + iy) * in.w + ix;
-                x = ld8(in, pix, (cg0 + g) * 8);
-                if constexpr (GM != 0) x = dw_gate_t<GM>(x, ld8(gate, n, (cg0 + g) * 8));
-                if (lo_in) xl = ld8(in, pix, (cg0 + g) * 8 + lo_in);
-            }
-            *reinterpret_cast<half8*>(tlds + r * rowstride + c * colstride + g * 16) = x;
-            if (lo_in) *reinterpret_cast<half8*>(tlds + plane + r * rowstride + c * colstride + g * 16) = xl;
-        }
-    }
-    __syncthreads();
-    const int g = tid & (CGB - 1), q = (tid >> cgbl) & 7, r = tid >> (cgbl + 3);
-    const int oh = oy0 + r, ow0 = ox0 + q * OUTW, gc = cg0 + g;
-    if (oh >= out.h || ow0 >= out.w || gc >= cg) return;
-    const int iw0 = ow0 * SW - pw;
-    float acc[OUTW][8];
-#pragma unroll
-    for (int o = 0; o < OUTW; ++o)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[o][e] = bias[gc * 8 + e];
-    if (!dead_tile) {
-        const char* base = tlds + (r * sh) * rowstride + (q * OUTW * SW) * colstride + g * 16;
-        for (int dyp = 0; dyp < (lo_in ? 2 * kh : kh); ++dyp) {
-            // (a pair input: every filter row is walked twice, over the hi and over the lo half of the same pixels)
-            const int dy = dyp < kh ? dyp : dyp - kh;
-            const int ih = oh * sh - ph + dy;
-            if (ih < 0 || ih >= in.h) continue;
-            const char* rowp = base + (dyp < kh ? 0 : plane) + dy * rowstride;
-            half8 x[WIN];
-#pragma unroll
-            for (int c = 0; c < WIN; ++c) x[c] = *reinterpret_cast<const half8*>(rowp + c * colstride);
-#pragma unroll
-            for (int dx = 0; dx < KW; ++dx) {
-                const float4v k0 = *reinterpret_cast<const float4v*>(w + (long)(dy * KW + dx) * in.c + gc * 8);
-                const float4v k1 = *reinterpret_cast<const float4v*>(w + (long)(dy * KW + dx) * in.c + gc * 8 + 4);
-#pragma unroll
-                for (int o = 0; o < OUTW; ++o) {
-                    const int iw = iw0 + o * SW + dx;
-                    if (iw < 0 || iw >= in.w) continue;           // the reference kernel skips padded taps (no +0 rounding issue, same sums)
-                    vse_fma_h8(acc[o], x[o * SW + dx], k0, k1);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int o = 0; o < OUTW; ++o) {
-        if (ow0 + o >= out.w) continue;
-        half8 rr, rl;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float v = vse_act(acc[o][e], act, act_a, act_b) * post_a + post_b;
-            rr[e] = (half_t)v;
-            rl[e] = (half_t)(v - (float)rr[e]);
-        }
-        if (wl_out != nullptr && ow0 + o >= wl_out[n]) rr = half8{0, 0, 0, 0, 0, 0, 0, 0};
-        st8(out, (n * out.h + oh) * out.w + ow0 + o, gc * 8, rr);
-        if (lo_off) st8(out, (n * out.h + oh) * out.w + ow0 + o, gc * 8 + lo_off, rl);
-    }
-}
-
-#endif
-
 // ------------------------------------------------------------------------------------------------ pooling
 // wl_in / wl_out (ragged batch): the sample's own input / output width — the window is clipped to the sample, not to the
 // batch tensor, and outputs right of the sample are zeros.
@@ -439,7 +328,8 @@ __global__ __launch_bounds__(256) void pool_kernel(TView in, TView out, int kh, 
         }
         if (is_max == 1) {
             // max pooling on the packed fp16 values themselves (v_pk_max_f16: 4 instructions per tap instead of 8 conversions + 8 fp32
-            // maxima; a maximum is exact in any precision: the same bits as the fp32 form below)
+            // maxima; a maximum is exact in any precision: the same bits as the fp32 form below, which the launcher no longer selects:
+            // is_max = 2 — kept so that the kernel's code stays the measured one)
             half8 m = {(half_t)-65504.f, (half_t)-65504.f, (half_t)-65504.f, (half_t)-65504.f, (half_t)-65504.f, (half_t)-65504.f, (half_t)-65504.f, (half_t)-65504.f};
             for (int dy = 0; dy < kh; ++dy) {
                 const int ih = oh * sh - ph + dy;
@@ -985,36 +875,6 @@ __global__ __launch_bounds__(256) void wscale_kernel(const half_t* __restrict__ 
     }
 }
 
-#ifdef VSE_DEV_BUILD
-// dwconv_tile_kernel: tile rows by the map height (least dead rows, then the taller tile), LDS by the patch; VSE_E_UNSUPPORTED -> row kernel
-template <int KW, int SW, int GM>
-static int launch_dw_tile(const TView& in0, const TView& out, const TView& gate, int hilo, const float* wk, const float* bk, const int* p,
-                          const float* f, const int* wl_out, hipStream_t st) {
-    const int kh = p[P_KH], sh = p[P_SH];
-    int trl = 3;
-    long best = -1;
-    for (int t = 3; t >= 1; --t) {
-        const long rows = (long)((out.h + (1 << t) - 1) >> t) << t;
-        if (best < 0 || rows < best) { best = rows; trl = t; }
-    }
-    const int TR = 1 << trl, CGB = 32 >> trl, IC = 31 * SW + KW, IR = (TR - 1) * sh + kh;
-    const int colstride = CGB * 16 + (CGB == 4 ? 16 : CGB == 8 ? 32 : 0);
-    const size_t lds = (size_t)(p[P_LO_RES] ? 2 : 1) * IR * IC * colstride;
-    if (lds > 150 * 1024) return VSE_E_UNSUPPORTED;
-    static VseDevOnce attr_once;          // (per device, thread-safe: common.h)
-    if (!vse_dev_once(attr_once, [] {
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_tile_kernel<KW, SW, GM>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess;
-        }))
-        return VSE_E_HIP;
-    const int cg = in0.c >> 3, cgblocks = (cg + CGB - 1) / CGB, tiles_w = (out.w + 31) / 32, tiles_h = (out.h + TR - 1) / TR;
-    const unsigned long long blocks = (unsigned long long)out.n * tiles_h * tiles_w * cgblocks;
-    if (blocks == 0 || blocks > 0x7fffffffull) return VSE_E_UNSUPPORTED;
-    hipLaunchKernelGGL((dwconv_tile_kernel<KW, SW, GM>), dim3((unsigned)blocks), dim3(256), lds, st, in0, out, gate, hilo, wk, bk, kh, sh, p[P_PH], p[P_PW],
-                       p[P_ACT], f[FS_ACT_A], f[FS_ACT_B], f[FS_POST_A], f[FS_POST_B], wl_out, trl, tiles_w, tiles_h, cgblocks);
-    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
-}
-#endif
-
 int launch_simple_op(const vse_op& op, const TView& in0, const TView& in1, const TView& in2, const TView& out,
                      const TView& out2, const char* wbase, const int* wl_in, const int* wl_out, hipStream_t st) {
     const int* p = op.p;
@@ -1035,14 +895,11 @@ int launch_simple_op(const vse_op& op, const TView& in0, const TView& in1, const
             if (!(op.flags & F_GATE)) gate.ptr = nullptr;
             else if (!in1.ptr || in1.c != in0.c || in1.n != in0.n || in1.esize != 2) return VSE_E_INVAL;
             // column-walk form (dwconv_col_kernel): plain fp16 tensors, no gate, square 3 x 3 / 5 x 5 'same' filters, horizontal stride 1
-            static const bool dw_col = [] { const char* e = vse_dev_getenv("VSE_DW_COL"); return !(e && e[0] == '0'); }();
-            if (dw_col && !gate.ptr && !p[P_LO_OUT] && !p[P_LO_RES] && kw == p[P_KH] && (kw == 3 || kw == 5) && sw == 1 && (p[P_SH] == 1 || p[P_SH] == 2)
+            if (!gate.ptr && !p[P_LO_OUT] && !p[P_LO_RES] && kw == p[P_KH] && (kw == 3 || kw == 5) && sw == 1 && (p[P_SH] == 1 || p[P_SH] == 2)
                 && p[P_PH] == kw / 2 && p[P_PW] == kw / 2 && out.w == in0.w && out.h == (in0.h + 2 * (kw / 2) - kw) / p[P_SH] + 1
                 && in0.ld * (long)in0.w * in0.h < 0x7fffffffl) {
-#ifndef VSE_DWCOL_OUTW
-#define VSE_DWCOL_OUTW 4
-#endif
-                const int outw = VSE_DWCOL_OUTW, cpn = in0.c >> 1, owq = (out.w + outw - 1) / outw;
+                constexpr int outw = 4;                                         // output columns per thread
+                const int cpn = in0.c >> 1, owq = (out.w + outw - 1) / outw;
                 const long cols = (long)out.n * owq * cpn;                     // one thread per (column strip, channel pair, row segment)
                 int nseg = (int)((262144 + cols - 1) / cols);                   // >= ~256 k threads where the map allows it, >= 4 rows per segment
                 if (nseg > (out.h + 3) / 4) nseg = (out.h + 3) / 4;
@@ -1054,33 +911,15 @@ int launch_simple_op(const vse_op& op, const TView& in0, const TView& in1, const
                 if (blocks > 0 && blocks <= 0x7fffffffull) {
 #define DW_COL(KH_, SH_, OW_) hipLaunchKernelGGL((dwconv_col_kernel<KH_, SH_, OW_>), dim3((unsigned)blocks), dim3(256), 0, st, in0, out, wk, bk, rs, nseg, \
                                                  p[P_ACT], f[FS_ACT_A], f[FS_ACT_B], f[FS_POST_A], f[FS_POST_B], wl_out)
-                    if (kw == 5 && p[P_SH] == 1) DW_COL(5, 1, VSE_DWCOL_OUTW);
-                    else if (kw == 5) DW_COL(5, 2, VSE_DWCOL_OUTW);
-                    else if (p[P_SH] == 1) DW_COL(3, 1, VSE_DWCOL_OUTW);
-                    else DW_COL(3, 2, VSE_DWCOL_OUTW);
+                    if (kw == 5 && p[P_SH] == 1) DW_COL(5, 1, outw);
+                    else if (kw == 5) DW_COL(5, 2, outw);
+                    else if (p[P_SH] == 1) DW_COL(3, 1, outw);
+                    else DW_COL(3, 2, outw);
 #undef DW_COL
                     break;
                 }
             }
             if ((kw == 3 || kw == 5) && (sw == 1 || sw == 2)) {
-#ifdef VSE_DEV_BUILD
-                // VSE_DW_TILE: 0 = row kernel only, 1 = LDS-tile kernel for 5 x 5 filters, 2 = for 3 x 3 filters too
-                static const int dw_tile = getenv("VSE_DW_TILE") ? atoi(getenv("VSE_DW_TILE")) : 0;
-                if (dw_tile >= (kw == 5 ? 1 : 2)) {
-                    int rc = VSE_E_UNSUPPORTED;
-#define DW_TILE(KW_, SW_) do { \
-                        if (!gate.ptr) rc = launch_dw_tile<KW_, SW_, 0>(in0, out, gate, hilo, wk, bk, p, f, wl_out, st); \
-                        else if (gmode == 1) rc = launch_dw_tile<KW_, SW_, 1>(in0, out, gate, hilo, wk, bk, p, f, wl_out, st); \
-                        else rc = launch_dw_tile<KW_, SW_, 2>(in0, out, gate, hilo, wk, bk, p, f, wl_out, st); } while (0)
-                    if (kw == 3 && sw == 1) DW_TILE(3, 1);
-                    else if (kw == 3) DW_TILE(3, 2);
-                    else if (sw == 1) DW_TILE(5, 1);
-                    else DW_TILE(5, 2);
-#undef DW_TILE
-                    if (rc == VSE_OK) break;
-                    if (rc != VSE_E_UNSUPPORTED) return rc;
-                }
-#endif
                 const long items4 = (long)out.n * out.h * ((out.w + 3) / 4) * (in0.c >> 3);
                 const dim3 g4(grid_for(items4, 256)), b4(256);
 #define DW_ROW(KW_, SW_) do { \
@@ -1105,10 +944,8 @@ int launch_simple_op(const vse_op& op, const TView& in0, const TView& in1, const
         case OP_POOL: {
             if ((in0.c & 7) || out.c != in0.c) return VSE_E_INVAL;
             const long items = (long)out.n * out.h * out.w * (in0.c >> 3);
-            // (is_max = 2: the fp32 form of the max, for A/B runs: VSE_POOL_PK=0)
-            static const int pk_off = vse_dev_getenv("VSE_POOL_PK") && atoi(vse_dev_getenv("VSE_POOL_PK")) == 0;
             hipLaunchKernelGGL(pool_kernel, dim3(grid_for(items, 256)), dim3(256), 0, st, in0, out, p[P_KH], p[P_KW],
-                               p[P_SH], p[P_SW], p[P_PH], p[P_PW], p[P_POOL_MAX] ? (pk_off ? 2 : 1) : 0, p[P_POOL_EXCL], wl_in, wl_out);
+                               p[P_SH], p[P_SW], p[P_PH], p[P_PW], p[P_POOL_MAX] ? 1 : 0, p[P_POOL_EXCL], wl_in, wl_out);
             break;
         }
         case OP_GAP: {

@@ -11,10 +11,10 @@ import numpy as np
 from . import compiler, ir
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("VSE_LIB_PATH") or os.path.join(_HERE, "libvse_hip.so")      # (VSE_LIB_PATH: ablation builds of tools/)
+LIB_PATH = os.environ.get("VSE_LIB_PATH") or os.path.join(_HERE, "libvse_hip.so")      # (VSE_LIB_PATH: a library built elsewhere)
 
 EXPORTS = [
-    "vse_init", "vse_destroy", "vse_last_error", "vse_sizeof_op", "vse_sizeof_view", "vse_abi_version", "vse_is_dev_build",
+    "vse_init", "vse_destroy", "vse_last_error", "vse_sizeof_op", "vse_sizeof_view", "vse_abi_version",
     "vse_weights_upload", "vse_weights_free", "vse_plan_create", "vse_plan_destroy", "vse_plan_run", "vse_plan_run_ragged",
     "vse_plan_width_levels", "vse_plan_profile", "vse_plan_op_variant", "vse_plan_op_kernel_name", "vse_det_preprocess", "vse_db_workspace_bytes",
     "vse_db_postprocess", "vse_rec_preprocess", "vse_rec_preprocess_scratch_bytes", "vse_ctc_collapse", "vse_ctc_collapse_ragged",
@@ -65,11 +65,7 @@ def load_library(path=None):
     for name in EXPORTS:
         if not hasattr(lib, name):
             raise VseError(f"libvse_hip.so does not export {name}")
-    if os.environ.get("VSE_DEV_BUILD", "0") == "1" and not lib.vse_is_dev_build():
-        # ir.dev_switch honours the compiler's experiment switches under VSE_DEV_BUILD=1; a PRODUCT library ignores its half of them
-        # (vse_dev_getenv) and refuses the experimental kernels: the two halves of an A/B arm would silently disagree
-        raise VseError(f"VSE_DEV_BUILD=1 but {path} is a product build: rebuild with `VSE_DEV_BUILD=1 python __graft_entry__.py --force` or "
-                       "point VSE_LIB_PATH at a development build (tools/build_ab.sh), or unset VSE_DEV_BUILD")
+
     lib.vse_last_error.restype = C.c_char_p
     lib.vse_sizeof_op.restype = C.c_size_t
     lib.vse_sizeof_view.restype = C.c_size_t
