@@ -267,11 +267,11 @@ def test_segmented_concat_views_are_handled_or_refused_loudly():
             compiler.compile_model(desc, wts, 1, 32, 48)
 
 
-def test_se_gate_folds_into_depthwise_and_pointwise_consumers():
+def test_se_gate_folds_into_consumers_unless_the_fold_is_refused(monkeypatch):
     """An SE output read only by the next stage's depthwise conv and by 1x1 convs (the detector's stage outputs: stage transition +
     FPN lateral) is never materialised: the depthwise conv applies the gate on load (F_GATE), each 1x1 conv reads per-image
-    weights W * gate (OP_WSCALE + F_IMGW, M tiles aligned to images).  Same result within the net tolerance; compiler.GATE_FOLD =
-    False restores the separate multiply."""
+    weights W * gate (OP_WSCALE + F_IMGW, M tiles aligned to images).  Same result within the net tolerance; without the fold
+    (Compiler._gate_foldable refusing) the separate multiply comes back."""
     desc, w = net_ref.get_weights("V4_ch_det")
     x = np.random.default_rng(3).uniform(-1, 1, (2, 3, 128, 160)).astype(np.float16).astype(np.float32)
     ref = net_ref.run_graph(desc, w, x)[0].numpy()[:, 0]
@@ -284,12 +284,8 @@ def test_se_gate_folds_into_depthwise_and_pointwise_consumers():
     assert len(gated) == 2
     got = ir_emul.Emulator(prog).run(ir_emul.to_nhwc8(x))[0][..., 0]
     assert np.abs(got - ref).max() < 5e-3
-    old = compiler.GATE_FOLD
-    try:
-        compiler.GATE_FOLD = False
-        plain = compiler.compile_model(desc, w, 2, 128, 160)
-    finally:
-        compiler.GATE_FOLD = old
+    monkeypatch.setattr(compiler.Compiler, "_gate_foldable", lambda *a: False)
+    plain = compiler.compile_model(desc, w, 2, 128, 160)
     k2 = [int(o["kind"]) for o in plain.ops]
     assert k2.count(ir.OP_WSCALE) == 0 and k2.count(ir.OP_SCALE) == 5
     assert np.abs(ir_emul.Emulator(plain).run(ir_emul.to_nhwc8(x))[0][..., 0] - ref).max() < 5e-3
@@ -473,11 +469,12 @@ def test_gated_lateral_falls_back_when_something_rides_behind_the_se_add(tail):
     assert np.abs(got - ref).max() < 5e-3 * max(1.0, np.abs(ref).max()), (tail, np.abs(got - ref).max())
 
 
-def test_head_tail_fusion_and_its_fallback(monkeypatch):
+def test_head_tail_fusion_and_its_fallback_without_the_head_form(monkeypatch):
     """F_TAIL2: the server detector's second head deconv (64 -> 1, the base map) rides in the first one's launch and its map is stored
     densely (ld 1) for the F_UP2HEAD conv.  The emulator decodes stage B from the MFMA fragments the kernel reads; with fp16 rounding
     of every stored tensor the fused and the separate programs give the same map.  A graph whose dense map would reach any other
-    reader (here: the head kernel switched off) compiles with the two launches instead (Tail2Unsupported -> retry)."""
+    reader (here: the head conv without the fused 1-channel projection the head kernel needs) compiles with the two launches instead
+    (Tail2Unsupported -> retry)."""
     desc, w = net_ref.get_weights("V4_ch_det")
     x = np.random.default_rng(3).uniform(-1, 1, (1, 3, 64, 96)).astype(np.float16).astype(np.float32)
     outs = {}
@@ -493,7 +490,7 @@ def test_head_tail_fusion_and_its_fallback(monkeypatch):
             assert len(head) == 1 and int(head[0]["in0"]["ld"]) == 1 and int(head[0]["in0"]["off"]) == int(o["out2"]["off"])
         outs[t2] = ir_emul.Emulator(prog, round_f16=True).run(ir_emul.to_nhwc8(x))[0]
     assert np.abs(outs[None] - outs[False]).max() < 2e-6 and outs[None].std() > 0
-    monkeypatch.setattr(compiler, "HEAD_UP2", False)
+    monkeypatch.setattr(compiler.Compiler, "_try_fuse_dot1", lambda *a: None)
     store, fb = compiler.WeightStore(), {}
     prog = compiler.compile_model(desc, w, 1, 64, 96, store=store, fallbacks=fb)
     assert not any(int(o["flags"]) & (ir.F_TAIL2 | ir.F_UP2HEAD) for o in prog.ops)

@@ -111,8 +111,8 @@ def main():
             net = nets[c]
             compiler.PATCH_MIN_K = mink[c]      # plans are compiled lazily on the first run
             compiler.PATCH_MAX_COUT = 256 if c == "p" else 64       # "p": also try the patch kernel on wide layers (two+ cout tiles)
-            compiler.COL3 = c == "c"
-            compiler.COL3_MAX_COUT, compiler.COL3_MIN_TILE_EFF, compiler.COL3_WIDE_MIN_CIN = 4096, 0.0, 0
+            compiler.COL3_MAX_COUT = 4096 if c == "c" else 0         # 0: no layer (coutp >= 8) goes to conv_c3_kernel
+            compiler.COL3_MIN_TILE_EFF, compiler.COL3_WIDE_MIN_CIN = 0.0, 0
             compiler.COL3_MIN_K = 100
             net.run(x)
             torch.cuda.synchronize()

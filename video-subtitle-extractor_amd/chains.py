@@ -22,9 +22,7 @@ import numpy as np
 
 from . import ir
 
-CHAIN = True
 CHAIN_MAX_STAGES = 6
-CHAIN_HEAD = True                # the DB head's two transposed convs as one chain (try_lower_head_tail)
 CHAIN_LDS_2 = 76 * 1024          # two blocks per CU (160 KiB of LDS)
 CHAIN_LDS_1 = 150 * 1024
 CHAIN_TILES = [(8, 32), (16, 16), (8, 16), (4, 32), (4, 16), (2, 32), (4, 8), (2, 16), (2, 8)]
@@ -268,7 +266,7 @@ class ChainMixin:
         HBM bytes (chain [i..j]: its input once — times the halo its tile reads —, its last output and every inner tensor
         another op needs; a lone stage: an ordinary conv op's reads and writes) under the LDS budget; the first segment is
         emitted here, the rest of the path is cut again (same optimum) when the lowering reaches it."""
-        if not (CHAIN and getattr(self, "chain", False)) or self.ragged:
+        if not self.chain or self.ragged:
             return False
         cand = self._chain_candidate(i0)
         if cand is None:
@@ -360,7 +358,7 @@ class ChainMixin:
         (CHS_SHUF).  The c1-channel tensor at twice the resolution (24 x 272 x 480 per frame, written and read back: 16 MB of the
         mobile detectors' 200 MB per frame) never exists."""
         # (also in the layer-by-layer program of a hi + lo net, chain=False: the register form chain_pw2_kernel replaces two launches)
-        if not (CHAIN and CHAIN_HEAD and (getattr(self, "chain", False) or getattr(self, "hilo", False))) or self.ragged:
+        if not (self.chain or self.hilo) or self.ragged:
             return False
         op0 = self.ops[i0]
         if op0["type"] != "conv2d_transpose":

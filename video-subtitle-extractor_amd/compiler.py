@@ -185,21 +185,13 @@ PATCH_MIN_K = 500
 PATCH_MAX_COUT = 64
 # smallest useful fraction of a tile grid (8/16 x 32 output pixels) for the patch kernel; below it the map is too ragged
 PATCH_MIN_TILE_EFF = 0.5
-# evaluate the PP-OCRv4 server detector's last 3x3 conv on the low-res grid (conv_head.hip)
-STEM = True         # conv_stem_kernel for 3x3 convs over <= 4 real channels
-GATE_DW = True      # SE gate folded into a depthwise consumer
-GATE_FOLD = True    # SE gate whose consumers are a depthwise conv and 1x1 convs: folded into them
-WK32 = True         # 32-deep weight tiles for conv_gemm_kernel (contiguous wave DMAs)
-HEAD_UP2 = True
-COL = True          # conv_col_kernel (one filter column per step) for 9x9 / 7x7 / 5x5 layers
-# below this tile efficiency the 8-row tiles of conv_patch_kernel win (measured: 17x30 map 0.163 vs 0.203 ms, 34x60 0.50 vs 0.43)
+# conv_col_kernel (one filter column per step, 9x9 / 7x7 / 5x5 layers): below this tile efficiency the 8-row tiles of
+# conv_patch_kernel win (measured: 17x30 map 0.163 vs 0.203 ms, 34x60 0.50 vs 0.43)
 COL_MIN_TILE_EFF = 0.75
 # conv_c3_kernel (3x3, two blocks per CU); cout / tile-efficiency limits from per-layer A/B runs
-COL3 = True
 COL3_MAX_COUT = 192     # per-layer A/B (tools/bench_conv.py --cfgs d,p,c): 224-cout layers tie or lose
-PW = True           # conv_pw_kernel for 1x1 convs (and 2x2 s2 transposed convs) over <= 64 input channels
+# conv_pw_kernel for 1x1 convs (and 2x2 s2 transposed convs) over <= 64 input channels
 PW_MAX_COUT = 64
-TAIL2 = True        # the server detector's second head deconv inside the first one's launch (F_TAIL2)
 COL3_MIN_K = 250    # 3x3 32->32 @136x240 (K = 288): 0.180 ms on the implicit GEMM, 0.115 ms here
 COL3_WIDE_MIN_CIN = 128    # layers with more than 64 couts (two+ cout tiles refetch the patch) only from 128 input channels on
 COL3_MIN_TILE_EFF = 0.8
@@ -207,16 +199,6 @@ COL3_MIN_TILE_EFF = 0.8
 # 48 px height; every plan of a model selects as if its maps were this wide (the choice only steers efficiency, never results
 # ACROSS plans of one process; a different value is a different set of summation orders)
 RAGGED_SEL_W = 768
-ONECH = True        # DB head: last transposed conv stores the fp32 map directly
-GATE_CONCAT = True  # SE output that only feeds a concat: multiplied by the copy into the slot
-DWPW = True         # depthwise conv fused in front of its 1x1 consumer (hi + lo nets: conv_dwpw.hip)
-# filter sizes sent there: 3x3 wins against depthwise + 1x1 launches (V4 16 -> 32 @272x480: 0.33 vs 0.44 ms); 5x5 loses (V3 64 -> 24
-# @68x120: 0.21 vs 0.14 ms: 25 taps of fp32 VALU work per 8 channels and lane, no window sharing between neighbouring pixels)
-DWPW_K = (3,)
-HLSUM = True        # 3x3 convs with <= 32 couts of a hi + lo net: hi | lo weight rows in one pass (F_HLSUM)
-SE_LATERAL = True   # 1x1 conv + SE block with shortcut -> one gated conv (F_OGATE)
-LSTM_MFMA = True    # batch-shared MFMA recurrence (csrc/lstm.hip) for 256-unit LSTMs
-LSTM_WAVES = 16     # 8: lstm_mfma_kernel, 16: lstm_mfma16_kernel (twice the loads in flight)
 
 
 def c3_tile_eff(oh, ow):
@@ -279,27 +261,34 @@ def check_attrs(ops):
 
 
 class Compiler(ChainMixin):
-    def __init__(self, desc, weights, batch, height, width, fetch_cols=(0,), want_probs=True,
-                 store=None, reuse=True, se_lateral=None, tail2=None):
+    def __init__(self, desc, weights, batch, height, width, fetch_cols=(0,), want_probs=True, store=None, reuse=True, hilo=False,
+                 ragged=False, input_norm=None, fuse_preprocess=False, chain=None, tail2=True, se_lateral=True):
+        """The plan options are those of compile_model."""
         self.desc = desc
-        self.tail2 = tail2                    # False: never fuse the head's second transposed conv into the first (F_TAIL2)
         self.W = dict(weights)
         self.ops = list(desc["ops"])
         check_attrs(self.ops)
+        self.hilo = bool(hilo)                # fp16 hi + lo weight pairs
+        # conv_patch_kernel has no two-pass K walk for hi + lo weights (the implicit-GEMM, stem and column kernels do)
+        self.use_patch = not self.hilo
+        # ragged plans (recognisers): every sample of the batch carries its own width; see ir.P_WLIN / Program.wlevels
+        self.ragged = bool(ragged)
+        self.input_norm = input_norm          # (mean3, std3): the plan takes RAW resized pixels + a ones channel (fold_input_norm)
+        self.fuse_preprocess = bool(fuse_preprocess)    # ... and the stem conv resizes them itself from the uint8 frames (F_U8SRC)
+        # 1x1 / depthwise chains as OP_CHAIN (chains.py), by default for the hi + lo nets (mobile detectors); the tensors that feed
+        # a chain are stored as fp16 hi + lo pairs
+        self.chain = self.hilo if chain is None else bool(chain)
+        self.tail2 = tail2 is not False       # False: never fuse the head's second transposed conv into the first (F_TAIL2)
         self.merged_gmac_credit = {}          # merged conv weight name -> algorithmic MAC factor of the original branches
-        self.hilo = False                     # fp16 hi + lo weight pairs (compile_model(hilo=True))
         self.pending_gate = {}                # SE output name -> gate view its depthwise consumer applies on load (F_GATE)
         self.pending_wgate = {}               # SE output name -> gate view its 1x1 conv consumers fold into per-image weights (F_IMGW)
-        # ragged plans (recognisers): every sample of the batch carries its own width; see ir.P_WLIN / Program.wlevels
-        self.ragged = False
         self.wlevels = [None]                 # level 0 = the input width
         self.wlevel_index = {}
-        self.sel_w0 = RAGGED_SEL_W            # kernel selection of a ragged plan looks at THIS input width, never at the batch's
-        self.input_norm = None                # (mean3, std3): see fold_input_norm
-        self.fuse_preprocess = False          # with input_norm: the stem conv reads the uint8 frames and resizes them itself (F_U8SRC)
+        self._out_level = 0                   # width level of the sequence the class softmax runs over (lower_softmax_out)
+        self.chain_res = None                 # while chains.py lays out a chain: its channel-minor tensors (residuals absorb_epilogue may take)
         self._merge_parallel_convs()
-        if SE_LATERAL if se_lateral is None else se_lateral:
-            self._rewrite_se_laterals()
+        if se_lateral is not False:
+            self._rewrite_se_laterals()       # 1x1 conv + SE block with shortcut -> one gated conv (F_OGATE)
         self.N, self.H, self.Wd = batch, height, width
         self.fetch_cols = tuple(fetch_cols)
         self.want_probs = want_probs
@@ -308,8 +297,6 @@ class Compiler(ChainMixin):
         self.ir_ops: List[dict] = []
         self.store = store if store is not None else WeightStore()
         self.reuse = reuse
-        self.use_patch = True
-        self.use_col = True                   # conv_col_kernel / conv_c3_kernel (they walk hi + lo weights; the patch kernel does not)
         self.done = set()
         self.outputs = []
         self.gmacs = 0.0
@@ -539,10 +526,11 @@ class Compiler(ChainMixin):
 
     def _concat_is_virtual(self, i):
         """2-input concat with a nearest-upsampled input whose ONLY consumer is a k x k stride-1 conv: the patch conv
-        kernel gathers both sources itself (second source with its own shift), nothing is copied."""
+        kernel gathers both sources itself (second source with its own shift), nothing is copied.  A consumer that runs on
+        another kernel (every conv of a hi + lo net) materialises the concat first (lower_conv)."""
         op = self.ops[i]
         ins = op["in"]["X"]
-        if len(ins) != 2 or not getattr(self, "use_patch", True):
+        if len(ins) != 2:
             return False
         if not any(self.ops[self.producer[n]]["type"] == "nearest_interp_v2" for n in ins if n in self.producer):
             return False
@@ -590,7 +578,7 @@ class Compiler(ChainMixin):
         """The tensor feeds an OP_CHAIN (chains.py): store it as an fp16 hi + lo pair so that the chain computes on ~22 bits of it
         instead of 11 — the one rounding per chain edge that is left once the intermediates live in LDS.  Ordinary consumers read
         the hi half (a plain fp16 tensor with a wider pixel stride)."""
-        if not (getattr(self, "chain", False) and getattr(self, "chain_lo", True)) or self.ragged:
+        if not self.chain or self.ragged:
             return False
         if name in self.placement or name in self.fetched_names:
             return False
@@ -684,14 +672,14 @@ class Compiler(ChainMixin):
 
     def sel_width(self, lvl, actual):
         """Width the kernel SELECTION sees for a tensor: in a ragged plan the width of level `lvl` for a nominal sample
-        (sel_w0 wide), so that every plan of the model — whatever its batch and widest sample — sends a layer to the same
+        (RAGGED_SEL_W wide), so that every plan of the model — whatever its batch and widest sample — sends a layer to the same
         kernel family and therefore sums its products in the same order (results are then bit-identical across batch
         compositions); otherwise the tensor's own width."""
         if not self.ragged or lvl is None:
             return actual
         def width(l):
             if l == 0:
-                return self.sel_w0
+                return RAGGED_SEL_W
             parent, k, s, p, ceil = self.wlevels[l]
             return int(level_width(width(parent), k, s, p, ceil))
         return width(lvl)
@@ -913,7 +901,7 @@ class Compiler(ChainMixin):
                     else:
                         break
                 elif (t == "elementwise_add" and allow_res and stage <= 1 and st["res"] is None
-                      and getattr(self, "chain_res", None) is not None and other in self.chain_res):
+                      and self.chain_res is not None and other in self.chain_res):
                     st["res"] = ("chain", other)          # chains.py: the residual is a channel-minor LDS buffer of the same chain
                     stage = 2
                 elif t == "elementwise_add" and allow_res and stage <= 1 and st["res"] is None:
@@ -1201,96 +1189,11 @@ class Compiler(ChainMixin):
             return self.lower_dwconv(i, inv, w, sh, sw, ph, pw)
         assert groups == 1, "only dense and depthwise convs occur (SURVEY App. E)"
         if t == "conv2d_transpose":
-            assert (sh, sw) == (2, 2) and w.shape[2:] == (2, 2) and (ph, pw) == (0, 0)
-            cin, cout = w.shape[0], w.shape[1]
-            ep = self.absorb_epilogue(outname, i, cout, allow_res=False)
-            inv = self.materialize(inv, outname)
-            coutp = rup(cout, 8)
-            # GEMM N ordered (dy,dx,co): W2[(dy,dx,co), ci]
-            w2 = np.zeros((4 * coutp, inv.span), np.float64)
-            wt = w.astype(np.float64) * ep["scale"].reshape(1, -1, 1, 1)
-            cm = inv.chmap()
-            for dy in range(2):
-                for dx in range(2):
-                    blk = np.zeros((coutp, inv.span))
-                    blk[:cout][:, cm] = wt[:, :, dy, dx].T
-                    w2[(dy * 2 + dx) * coutp:(dy * 2 + dx + 1) * coutp] = blk
-            Kp = rup(inv.span, ir.KT)
-            mat = np.zeros((4 * coutp, Kp))
-            mat[:, :inv.span] = w2
-            bias = np.zeros(4 * coutp, np.float32)
-            for q in range(4):
-                bias[q * coutp:q * coutp + cout] = ep["shift"]
-            oh, ow = inv.h * 2, inv.w * 2
-            tflags = ir.F_PIXSHUF | (ir.F_HILO if self.hilo else 0)
-            cons = self._live_consumers(ep["out_name"])
-            if cout == 1 and len(cons) == 1 and self.ops[cons[0]]["type"] == "fetch" and ONECH:
-                # the DB head's last layer (transposed conv to ONE channel + sigmoid) feeds the fetch: store the fp32 map itself
-                # (one float per output pixel) instead of 8-channel fp16 groups that a copy pass then narrows: 4x fewer bytes
-                # written and no copy (F_ONECH)
-                ob = self.new_buf(inv.n, oh, ow, 1, esize=4, ext=len(self.outputs) + 1)
-                self.outputs.append(dict(name=ep["out_name"], kind="map", n=inv.n, h=oh, w=ow, c=1, ld=1, esize=4))
-                out = View(ob, 0, inv.n, oh, ow, [(0, 1)], 1)
-                tflags |= ir.F_OUT_F32 | ir.F_ONECH
-            else:
-                out = self.alloc_out(ep["out_name"], inv.n, oh, ow, cout)
-            pw_ok = PW and inv.span % 8 == 0 and inv.span <= 64 and 4 * coutp <= (128 if self.hilo else 256) and inv.up == 0
-            tail = None
-            if (pw_ok and TAIL2 and self.tail2 is not False and not self.hilo and not self.ragged and inv.span in (32, 64) and cout > 1
-                    and (4 * coutp) % 32 == 0 and not (tflags & ir.F_ONECH) and ep["post_a"] == 1.0 and ep["post_b"] == 0.0
-                    and ep["act2"] == ir.ACT_NONE and out.buf.lo_off == 0):
-                tail = self._tail2_candidate(ep["out_name"], cout)
-            out2, aux_off, tp, tf = None, 0, {}, {}
-            if tail is not None:
-                # the head's SECOND transposed conv (c1 -> 1, 2x2 s2, + activation) in this launch (F_TAIL2, conv_pw_tail_kernel): stage B
-                # = a block-diagonal 1x1 conv over this op's 4 coutp channels (dy, dx, co) -> 16 outputs 4 r + c = pixel (4 y + r, 4 x + c)
-                # of the map, r = 2 dy + ey, c = 2 dx + ex; its fp16 weights are the separate launch's (w2 * scale2 rounded once)
-                ep2, w2 = tail["ep"], tail["w"].astype(np.float64) * float(tail["ep"]["scale"][0])
-                wb = np.zeros((16, 4 * coutp), np.float64)
-                for r in range(4):
-                    for c in range(4):
-                        q = ((r >> 1) * 2 + (c >> 1)) * coutp
-                        wb[4 * r + c, q:q + cout] = w2[:, 0, r & 1, c & 1]
-                fx = np.arange(16)
-                rows = (fx & ~12) | ((fx & 4) << 1) | ((fx & 8) >> 1)           # conv_wrow: the cout row MFMA row fx carries
-                nks2 = 4 * coutp // 16
-                frag = np.zeros((nks2, 2, 16, 8), np.float16)
-                for s_ in range(nks2):
-                    for fj in range(2):
-                        frag[s_, fj] = wb[rows][:, s_ * 16 + fj * 8:s_ * 16 + fj * 8 + 8].astype(np.float16)
-                aux_off = self.add_weights(("convTtail", wname, tail["wname"], ep2["out_name"]), frag.reshape(-1))
-                ub = self.new_buf(inv.n, 2 * oh, 2 * ow, 1, esize=2)
-                out2 = View(ub, 0, inv.n, 2 * oh, 2 * ow, [(0, 1)], 8, dense1=True)
-                tflags |= ir.F_TAIL2
-                tp = {ir.P_DOTACT: ep2["act"]}
-                tf = {ir.FS_PRE_B: float(np.float32(ep2["shift"][0]))}
-                assert ep2["act"] in (ir.ACT_NONE, ir.ACT_SIGMOID, ir.ACT_RELU), ep2      # (activations without parameters: the kernel passes none)
-            if pw_ok:
-                # few input channels: conv_pw_kernel streams the pixels straight from global memory (pixel-shuffle store as ever);
-                # hi + lo weights: two tables, the K slices walked twice over the same activation fragments
-                tflags |= ir.F_PW
-                Kp = rup(inv.span, 16)
-                w_off = self.add_weights(("convTpw", wname, tuple(inv.segs), ep["out_name"], self.hilo), self.pw_weights(mat[:, :Kp], self.hilo))
-            else:
-                w_off = self.add_weights(("convT", wname, tuple(inv.segs), ep["out_name"], self.hilo),
-                                         self.tile_weights(mat, hilo=self.hilo))
-            b_off = self.add_weights(("convTb", wname, ep["out_name"]), bias)
-            self.emit(ir.OP_CONV, ep["out_name"], [inv], out, flags=tflags,
-                      p={ir.P_KH: 1, ir.P_KW: 1, ir.P_SH: 1, ir.P_SW: 1, ir.P_PH: 0, ir.P_PW: 0,
-                         ir.P_ACT: ep["act"], ir.P_ACT2: 0, ir.P_COUT: 4 * coutp, ir.P_KTOT: Kp,
-                         ir.P_INSHIFT: 0, ir.P_RESSHIFT: 0, ir.P_CINP: inv.span, **tp},
-                      f={ir.FS_ACT_A: ep["act_a"], ir.FS_ACT_B: ep["act_b"], ir.FS_POST_A: ep["post_a"],
-                         ir.FS_POST_B: ep["post_b"], **tf}, w_off=w_off, b_off=b_off, aux_off=aux_off, out2=out2)
-            self.add_gmacs(inv.n * inv.h * inv.w * cin * cout * 4 / 1e9)
-            self.env[ep["out_name"]] = out
-            if tail is not None:
-                self.add_gmacs(inv.n * oh * ow * cout * 4 / 1e9)
-                self.env[tail["ep"]["out_name"]] = out2
-            return
+            return self.lower_conv_transpose(i, inv, w, sh, sw, ph, pw)
         cout, cin, kh, kw = w.shape
         assert cin == inv.c, (cin, inv.c, outname)
         pair_in = False
-        if (getattr(self, "chain", False) and getattr(self, "chain_lo", True) and (kh, kw, sh, sw, ph, pw) == (1, 1, 1, 1, 0, 0)
+        if (self.chain and (kh, kw, sh, sw, ph, pw) == (1, 1, 1, 1, 0, 0)
                 and inv.buf is not None and inv.buf.lo_off and inv.parts is None and inv.up == 0 and inv.coff == 0
                 and inv.segs == [(0, inv.c)] and op["in"]["Input"][0] not in self.pending_wgate):
             # the input is an fp16 hi + lo PAIR (it also feeds an OP_CHAIN, or was stored for this conv): a 1x1 conv consumes both
@@ -1335,11 +1238,11 @@ class Compiler(ChainMixin):
         rem16 = oh % 16
         rows16 = oh // 16 + ((0.35 + 0.65 * -(-rem16 // 2) / 8.0) if rem16 else 0.0)
         tile_eff_col = (oh * ow) / float(rows16 * 16 * -(-ow // 32) * 32)
-        col = (COL and (sh, sw) == (1, 1) and kh in (5, 7, 9) and 3 <= kw <= 17 and inv.span % 16 == 0 and coutp <= 64
-               and inv.parts is None and self.use_col and kh * kw * cin >= PATCH_MIN_K
+        col = ((sh, sw) == (1, 1) and kh in (5, 7, 9) and 3 <= kw <= 17 and inv.span % 16 == 0 and coutp <= 64
+               and inv.parts is None and kh * kw * cin >= PATCH_MIN_K
                and tile_eff_col >= COL_MIN_TILE_EFF and not self._dot1_candidate(ep["out_name"], cout))
-        c3 = (COL3 and (sh, sw) == (1, 1) and (kh, kw, ph, pw) == (3, 3, 1, 1) and inv.span % 16 == 0 and inv.parts is None
-              and self.use_col and kh * kw * cin >= min(PATCH_MIN_K, COL3_MIN_K) and coutp <= COL3_MAX_COUT
+        c3 = ((sh, sw) == (1, 1) and (kh, kw, ph, pw) == (3, 3, 1, 1) and inv.span % 16 == 0 and inv.parts is None
+              and kh * kw * cin >= min(PATCH_MIN_K, COL3_MIN_K) and coutp <= COL3_MAX_COUT
               and (coutp <= 64 or inv.span >= COL3_WIDE_MIN_CIN)
               and inv.src_h * inv.src_w * inv.buf.ld < 2_000_000_000      # 32-bit in-image offsets (launch_conv_c3 checks the same)
               and c3_tile_eff(oh, ow) >= COL3_MIN_TILE_EFF and not self._dot1_candidate(ep["out_name"], cout))
@@ -1391,13 +1294,13 @@ class Compiler(ChainMixin):
         head = (dot is not None and (flags & ir.F_SRC2) and res is None and (kh, kw, ph, pw) == (3, 3, 1, 1)
                 and in2shift == 1 and inv_main.up == 0 and inv_main.span == 8 and inv_main.c == 1
                 and inv.parts[1].span == 64 and inv.span == 72 and coutp <= 64
-                and (oh, ow) == (inv.parts[1].h, inv.parts[1].w) and oh % 2 == 0 and ow % 2 == 0 and HEAD_UP2 and not self.hilo)
+                and (oh, ow) == (inv.parts[1].h, inv.parts[1].w) and oh % 2 == 0 and ow % 2 == 0 and not self.hilo)
         if head:
             flags |= ir.F_UP2HEAD
             Kp = 2 * 4 * 4 * 32 + 32
             w_off = self.add_weights(("convh", wname, tuple(inv.segs), ep["out_name"]),
                                      lambda: self.head_up2_weights(self.pack_conv_weights(w, ep["scale"], inv)[0], inv.span))
-        elif (PW and (kh, kw, sh, sw, ph, pw) == (1, 1, 1, 1, 0, 0) and inv.parts is None and inv_main.up == 0 and dot is None
+        elif ((kh, kw, sh, sw, ph, pw) == (1, 1, 1, 1, 0, 0) and inv.parts is None and inv_main.up == 0 and dot is None
               and inv.span % 8 == 0 and inv.span <= (96 if self.hilo else 64) and coutp <= (128 if self.hilo else PW_MAX_COUT) and flags in (0, ir.F_RES)):
             # (hi + lo nets: the alternative is the generic kernel with K padded to 64 and walked twice — any cout count it can hold
             # is faster here)
@@ -1405,7 +1308,7 @@ class Compiler(ChainMixin):
             Kp = rup(inv.span, 16)          # weight rows are whole 16-channel K slices (zero columns behind the channels)
             w_off = self.add_weights(("convpw", wname, tuple(inv.segs), ep["out_name"], self.hilo),
                                      lambda: self.pw_weights(self.pack_conv_weights(w, ep["scale"], inv)[0][:, :rup(inv.span, 16)], self.hilo))
-        elif col and self.hilo and HLSUM and (kh, kw) == (3, 3) and coutp <= 32:
+        elif col and self.hilo and (kh, kw) == (3, 3) and coutp <= 32:
             # the 32-cout tile of conv_c3_kernel walks K twice for a hi + lo net with half its MFMA tile empty: ONE pass over a 64-row
             # stage [hi 32 | lo 32] instead, the two accumulator tiles added in the epilogue (F_HLSUM)
             Kp = kh * kw * inv.span
@@ -1430,7 +1333,7 @@ class Compiler(ChainMixin):
             w_off = self.add_weights(("convp", wname, tuple(inv.segs), ep["out_name"], ptaps),
                                      lambda: self.patch_weights(self.pack_conv_weights(w, ep["scale"], inv)[0], kh, kw,
                                                                 inv.span, ptaps))
-        elif (STEM and (kh, kw, ph, pw) == (3, 3, 1, 1) and (sh, sw) in ((1, 1), (2, 2)) and inv.span == 8 and cin <= 4
+        elif ((kh, kw, ph, pw) == (3, 3, 1, 1) and (sh, sw) in ((1, 1), (2, 2)) and inv.span == 8 and cin <= 4
               and coutp <= 64 and inv.parts is None and inv_main.up == 0 and dot is None and flags in (0, ir.F_RES)):
             # stem over an image-like input (conv_stem.hip)
             flags |= ir.F_STEM | (ir.F_HILO if self.hilo else 0)
@@ -1440,7 +1343,8 @@ class Compiler(ChainMixin):
             w_off = self.add_weights(("convs", wname, tuple(inv.segs), ep["out_name"], self.hilo),
                                      lambda: self.stem_weights(self.pack_conv_weights(w, ep["scale"], inv)[0], self.hilo))
         else:
-            wk32 = WK32 and dot is None and self.gemm_eligible(kh, kw, ph, pw, inv.span, inv_main.up, flags)
+            # 32-deep weight tiles for conv_gemm_kernel (contiguous wave DMAs)
+            wk32 = dot is None and self.gemm_eligible(kh, kw, ph, pw, inv.span, inv_main.up, flags)
             if wk32:
                 flags |= ir.F_WK32
             if self.hilo:
@@ -1498,11 +1402,102 @@ class Compiler(ChainMixin):
                      ir.P_INSHIFT: inv_main.up, ir.P_RESSHIFT: resshift, ir.P_CINP: inv.span, ir.P_IN2SHIFT: in2shift,
                      ir.P_LO_OUT: out.buf.lo_off,
                      ir.P_LO_RES: (res.buf.lo_off if (res is not None and res.buf is not None and not res.up and res.coff == 0
-                                                      and getattr(self, "chain", False)) else 0)},
+                                                      and self.chain) else 0)},
                   f={ir.FS_ACT_A: ep["act_a"], ir.FS_ACT_B: ep["act_b"], ir.FS_POST_A: ep["post_a"],
                      ir.FS_POST_B: ep["post_b"]}, w_off=w_off, b_off=b_off)
         self.add_gmacs(inv.n * oh * ow * (cin // 2 if pair_in else cin) * cout * self.merged_gmac_credit.get(wname, kh * kw) / 1e9)
         self.env[ep["out_name"]] = out
+
+    def lower_conv_transpose(self, i, inv, w, sh, sw, ph, pw):
+        """2x2 stride-2 transposed conv = a 1x1 conv to 4 coutp channels ordered (dy, dx, co) with a pixel-shuffle store (F_PIXSHUF)."""
+        op = self.ops[i]
+        outname = op["out"]["Output"][0]
+        wname = op["in"]["Filter"][0]
+        assert (sh, sw) == (2, 2) and w.shape[2:] == (2, 2) and (ph, pw) == (0, 0)
+        cin, cout = w.shape[0], w.shape[1]
+        ep = self.absorb_epilogue(outname, i, cout, allow_res=False)
+        inv = self.materialize(inv, outname)
+        coutp = rup(cout, 8)
+        # GEMM N ordered (dy,dx,co): W2[(dy,dx,co), ci]
+        w2 = np.zeros((4 * coutp, inv.span), np.float64)
+        wt = w.astype(np.float64) * ep["scale"].reshape(1, -1, 1, 1)
+        cm = inv.chmap()
+        for dy in range(2):
+            for dx in range(2):
+                blk = np.zeros((coutp, inv.span))
+                blk[:cout][:, cm] = wt[:, :, dy, dx].T
+                w2[(dy * 2 + dx) * coutp:(dy * 2 + dx + 1) * coutp] = blk
+        Kp = rup(inv.span, ir.KT)
+        mat = np.zeros((4 * coutp, Kp))
+        mat[:, :inv.span] = w2
+        bias = np.zeros(4 * coutp, np.float32)
+        for q in range(4):
+            bias[q * coutp:q * coutp + cout] = ep["shift"]
+        oh, ow = inv.h * 2, inv.w * 2
+        tflags = ir.F_PIXSHUF | (ir.F_HILO if self.hilo else 0)
+        cons = self._live_consumers(ep["out_name"])
+        if cout == 1 and len(cons) == 1 and self.ops[cons[0]]["type"] == "fetch":
+            # the DB head's last layer (transposed conv to ONE channel + sigmoid) feeds the fetch: store the fp32 map itself
+            # (one float per output pixel) instead of 8-channel fp16 groups that a copy pass then narrows: 4x fewer bytes
+            # written and no copy (F_ONECH)
+            ob = self.new_buf(inv.n, oh, ow, 1, esize=4, ext=len(self.outputs) + 1)
+            self.outputs.append(dict(name=ep["out_name"], kind="map", n=inv.n, h=oh, w=ow, c=1, ld=1, esize=4))
+            out = View(ob, 0, inv.n, oh, ow, [(0, 1)], 1)
+            tflags |= ir.F_OUT_F32 | ir.F_ONECH
+        else:
+            out = self.alloc_out(ep["out_name"], inv.n, oh, ow, cout)
+        pw_ok = inv.span % 8 == 0 and inv.span <= 64 and 4 * coutp <= (128 if self.hilo else 256) and inv.up == 0
+        tail = None
+        if (pw_ok and self.tail2 and not self.hilo and not self.ragged and inv.span in (32, 64) and cout > 1
+                and (4 * coutp) % 32 == 0 and not (tflags & ir.F_ONECH) and ep["post_a"] == 1.0 and ep["post_b"] == 0.0
+                and ep["act2"] == ir.ACT_NONE and out.buf.lo_off == 0):
+            tail = self._tail2_candidate(ep["out_name"], cout)
+        out2, aux_off, tp, tf = None, 0, {}, {}
+        if tail is not None:
+            # the head's SECOND transposed conv (c1 -> 1, 2x2 s2, + activation) in this launch (F_TAIL2, conv_pw_tail_kernel): stage B
+            # = a block-diagonal 1x1 conv over this op's 4 coutp channels (dy, dx, co) -> 16 outputs 4 r + c = pixel (4 y + r, 4 x + c)
+            # of the map, r = 2 dy + ey, c = 2 dx + ex; its fp16 weights are the separate launch's (w2 * scale2 rounded once)
+            ep2, w2 = tail["ep"], tail["w"].astype(np.float64) * float(tail["ep"]["scale"][0])
+            wb = np.zeros((16, 4 * coutp), np.float64)
+            for r in range(4):
+                for c in range(4):
+                    q = ((r >> 1) * 2 + (c >> 1)) * coutp
+                    wb[4 * r + c, q:q + cout] = w2[:, 0, r & 1, c & 1]
+            fx = np.arange(16)
+            rows = (fx & ~12) | ((fx & 4) << 1) | ((fx & 8) >> 1)           # conv_wrow: the cout row MFMA row fx carries
+            nks2 = 4 * coutp // 16
+            frag = np.zeros((nks2, 2, 16, 8), np.float16)
+            for s_ in range(nks2):
+                for fj in range(2):
+                    frag[s_, fj] = wb[rows][:, s_ * 16 + fj * 8:s_ * 16 + fj * 8 + 8].astype(np.float16)
+            aux_off = self.add_weights(("convTtail", wname, tail["wname"], ep2["out_name"]), frag.reshape(-1))
+            ub = self.new_buf(inv.n, 2 * oh, 2 * ow, 1, esize=2)
+            out2 = View(ub, 0, inv.n, 2 * oh, 2 * ow, [(0, 1)], 8, dense1=True)
+            tflags |= ir.F_TAIL2
+            tp = {ir.P_DOTACT: ep2["act"]}
+            tf = {ir.FS_PRE_B: float(np.float32(ep2["shift"][0]))}
+            assert ep2["act"] in (ir.ACT_NONE, ir.ACT_SIGMOID, ir.ACT_RELU), ep2      # (activations without parameters: the kernel passes none)
+        if pw_ok:
+            # few input channels: conv_pw_kernel streams the pixels straight from global memory (pixel-shuffle store as ever);
+            # hi + lo weights: two tables, the K slices walked twice over the same activation fragments
+            tflags |= ir.F_PW
+            Kp = rup(inv.span, 16)
+            w_off = self.add_weights(("convTpw", wname, tuple(inv.segs), ep["out_name"], self.hilo), self.pw_weights(mat[:, :Kp], self.hilo))
+        else:
+            w_off = self.add_weights(("convT", wname, tuple(inv.segs), ep["out_name"], self.hilo),
+                                     self.tile_weights(mat, hilo=self.hilo))
+        b_off = self.add_weights(("convTb", wname, ep["out_name"]), bias)
+        self.emit(ir.OP_CONV, ep["out_name"], [inv], out, flags=tflags,
+                  p={ir.P_KH: 1, ir.P_KW: 1, ir.P_SH: 1, ir.P_SW: 1, ir.P_PH: 0, ir.P_PW: 0,
+                     ir.P_ACT: ep["act"], ir.P_ACT2: 0, ir.P_COUT: 4 * coutp, ir.P_KTOT: Kp,
+                     ir.P_INSHIFT: 0, ir.P_RESSHIFT: 0, ir.P_CINP: inv.span, **tp},
+                  f={ir.FS_ACT_A: ep["act_a"], ir.FS_ACT_B: ep["act_b"], ir.FS_POST_A: ep["post_a"],
+                     ir.FS_POST_B: ep["post_b"], **tf}, w_off=w_off, b_off=b_off, aux_off=aux_off, out2=out2)
+        self.add_gmacs(inv.n * inv.h * inv.w * cin * cout * 4 / 1e9)
+        self.env[ep["out_name"]] = out
+        if tail is not None:
+            self.add_gmacs(inv.n * oh * ow * cout * 4 / 1e9)
+            self.env[tail["ep"]["out_name"]] = out2
 
     def lower_dwconv(self, i, inv, w, sh, sw, ph, pw):
         op = self.ops[i]
@@ -1536,16 +1531,16 @@ class Compiler(ChainMixin):
                   p={ir.P_KH: kh, ir.P_KW: kw, ir.P_SH: sh, ir.P_SW: sw, ir.P_PH: ph, ir.P_PW: pw,
                      ir.P_ACT: ep["act"], ir.P_LO_OUT: out.buf.lo_off,
                      # (P_LO_RES of a depthwise conv = the pair offset of its INPUT: both halves are filtered)
-                     ir.P_LO_RES: inv.buf.lo_off if (gate is None and inv.coff == 0 and getattr(self, "chain", False)) else 0},
+                     ir.P_LO_RES: inv.buf.lo_off if (gate is None and inv.coff == 0 and self.chain) else 0},
                   f={ir.FS_ACT_A: ep["act_a"], ir.FS_ACT_B: ep["act_b"], ir.FS_POST_A: ep["post_a"],
                      ir.FS_POST_B: ep["post_b"]}, w_off=w_off, b_off=b_off)
         self.add_gmacs(inv.n * oh * ow * c * kh * kw / 1e9)
         self.env[ep["out_name"]] = out
 
     def dwpw_eligible(self, i):
-        """Structural half of try_lower_dwpw, without side effects: op i is a depthwise conv (3x3 / 5x5, stride 1 / 2, <= 96 channels)
-        whose only reader — behind its own BN / activation — is a plain 1x1 conv with <= 192 couts."""
-        if not (DWPW and self.hilo) or self.ragged or i in self.done or not self.live[i]:
+        """Structural half of try_lower_dwpw, without side effects: op i is a 3x3 depthwise conv (stride 1 / 2, <= 96 channels) of a
+        hi + lo net whose only reader — behind its own BN / activation — is a plain 1x1 conv with <= 192 couts."""
+        if not self.hilo or self.ragged or i in self.done or not self.live[i]:
             return False
         op = self.ops[i]
         if op["type"] not in ("conv2d", "depthwise_conv2d"):
@@ -1559,7 +1554,9 @@ class Compiler(ChainMixin):
         sh, sw = a["strides"]
         pads = a["paddings"]
         ph, pw = (pads[0], pads[1]) if len(pads) == 2 else (pads[0], pads[2])
-        if kh != kw or kh not in DWPW_K or sh != sw or sh not in (1, 2) or ph != pw or ph != kh // 2 or c % 8 or c > 96:
+        # 3x3 only: it wins against depthwise + 1x1 launches (V4 16 -> 32 @272x480: 0.33 vs 0.44 ms); 5x5 loses (V3 64 -> 24 @68x120:
+        # 0.21 vs 0.14 ms: 25 taps of fp32 VALU work per 8 channels and lane, no window sharing between neighbouring pixels)
+        if kh != kw or kh != 3 or sh != sw or sh not in (1, 2) or ph != pw or ph != kh // 2 or c % 8 or c > 96:
             return False
         snapshot = set(self.done)
         try:
@@ -1658,7 +1655,7 @@ class Compiler(ChainMixin):
                   p={ir.P_KH: kh, ir.P_KW: kw, ir.P_SH: sh, ir.P_SW: sw, ir.P_PH: ph, ir.P_PW: pw, ir.P_ACT: ep["act"], ir.P_ACT2: ep["act2"],
                      ir.P_COUT: coutp, ir.P_KTOT: cp, ir.P_INSHIFT: 0, ir.P_RESSHIFT: 0, ir.P_CINP: inv.span,
                      ir.P_LO_OUT: out.buf.lo_off,
-                     ir.P_LO_IN: inv.buf.lo_off if (inv.coff == 0 and getattr(self, "chain_lo", True)) else 0,
+                     ir.P_LO_IN: inv.buf.lo_off if inv.coff == 0 else 0,
                      ir.P_LO_RES: (res.buf.lo_off if (res is not None and res.buf is not None and res.coff == 0) else 0)},
                   f={ir.FS_ACT_A: ep["act_a"], ir.FS_ACT_B: ep["act_b"], ir.FS_POST_A: ep["post_a"], ir.FS_POST_B: ep["post_b"]},
                   w_off=w_off, b_off=b_off, aux_off=aux_off)
@@ -1853,7 +1850,7 @@ class Compiler(ChainMixin):
             # SE gate whose only consumer is a depthwise conv (the stage transitions of the HGNet recognisers): the conv
             # applies the gate on load and the scaled tensor is never written
             cons2 = self._live_consumers(outname)
-            if GATE_DW and len(cons2) == 1 and outname not in self.placement and outname not in self.fetched_names:
+            if len(cons2) == 1 and outname not in self.placement and outname not in self.fetched_names:
                 o2 = self.ops[cons2[0]]
                 if o2["type"] in ("conv2d", "depthwise_conv2d") and o2["in"]["Input"][0] == outname:
                     w2 = self.W[o2["in"]["Filter"][0]]
@@ -1862,7 +1859,7 @@ class Compiler(ChainMixin):
                         self.pending_gate[outname] = (gate, flags)
                         self.env[outname] = big
                         return
-            if GATE_FOLD and self._gate_foldable(outname, big, flags):
+            if self._gate_foldable(outname, big, flags):
                 # every consumer applies the gate itself: the depthwise conv on load (F_GATE), the 1x1 convs through per-image
                 # weights W * gate (OP_WSCALE + F_IMGW) — the scaled tensor (a full read + write of the stage output) is never made
                 for j in cons2:
@@ -1872,7 +1869,7 @@ class Compiler(ChainMixin):
                         self.pending_wgate[outname] = gate
                 self.env[outname] = big
                 return
-            if GATE_CONCAT and self._only_feeds_concat(outname) and big.c % 8 == 0 and gate.c == big.c:
+            if self._only_feeds_concat(outname) and big.c % 8 == 0 and gate.c == big.c:
                 # the SE output is read by a concat only (directly or through a nearest up-sampling): the copy into the concat slot
                 # multiplies (lower_concat, gated OP_RESIZE) — no separate scale pass, one rounding instead of two
                 self.env[outname] = View(big.buf, big.coff, big.n, big.h, big.w, list(big.segs), big.span, big.up, big.tag, gate=(gate, flags))
@@ -2034,30 +2031,21 @@ class Compiler(ChainMixin):
         self._fetched = name
 
     @staticmethod
-    def lstm_gate_order(H, waves):
-        """Channel order of the gate pre-activations handed to the MFMA LSTM kernels: new[w * 4U + g * U + u] = old[g * H + w * U + u],
-        U = H / waves hidden units per wave."""
-        U = H // waves
-        return np.arange(4 * H).reshape(4, waves, U).transpose(1, 0, 2).reshape(-1)
+    def lstm_gate_order(H):
+        """Channel order of the gate pre-activations handed to the MFMA LSTM kernel (16 waves): new[w * 4U + g * U + u] =
+        old[g * H + w * U + u], U = H / 16 hidden units per wave."""
+        U = H // 16
+        return np.arange(4 * H).reshape(4, 16, U).transpose(1, 0, 2).reshape(-1)
 
     @staticmethod
     def lstm_fragments16(w_hh):
-        """The 16-wave form of lstm_fragments (lstm_mfma16_kernel): wave w owns units 16w .. 16w+15; tile 0 = [gate i | gate f],
-        tile 1 = [gate g | gate o] (rows 0-15 | 16-31); stream order [wave 16][k-slice 16][tile 2][k-half 2][row 32][8]."""
+        """W_hh [4H, H] (gate order i, f, g, o; H = 256) -> fp16 in the order lstm_mfma16_kernel streams it: wave w owns units
+        16w .. 16w+15; tile 0 = [gate i | gate f], tile 1 = [gate g | gate o] (rows 0-15 | 16-31); per (wave, 16-deep k slice, tile)
+        one MFMA A fragment, k = 16 s + 8 k-half + j; stream order [wave 16][k-slice 16][tile 2][k-half 2][row 32][8]."""
         H = w_hh.shape[1]
         assert w_hh.shape == (4 * H, H) and H == 256
         w6 = w_hh.reshape(2, 2, 16, 16, 16, 2, 8)                 # [tile][gate-in-tile][wave][unit][slice][k-half][j]
         return np.ascontiguousarray(w6.transpose(2, 4, 0, 5, 1, 3, 6)).astype(np.float16).reshape(-1)    # [wave][slice][tile][k-half][(gate, unit) = row][j]
-
-    @staticmethod
-    def lstm_fragments(w_hh):
-        """W_hh [4H, H] (gate order i, f, g, o; H = 256) -> fp16 in the order lstm_mfma_kernel streams it: wave w owns hidden
-        units 32w .. 32w+31; per (wave, 16-deep k slice, gate) — the order of the stream — one MFMA A fragment = [lane 64][8]: row = lane & 31 (unit
-        32w + row of that gate), k = 16 s + 8 (lane >> 5) + j."""
-        H = w_hh.shape[1]
-        assert w_hh.shape == (4 * H, H) and H == 256
-        w5 = w_hh.reshape(4, 8, 32, 16, 2, 8)                     # [gate][wave][row][slice][k-half][j]
-        return np.ascontiguousarray(w5.transpose(1, 3, 0, 4, 2, 5)).astype(np.float16).reshape(-1)       # [wave][slice][gate][k-half][row][j]
 
     def lower_rnn(self, i):
         op = self.ops[i]
@@ -2073,7 +2061,7 @@ class Compiler(ChainMixin):
         ncell = L * ndir
         cur = x
         name = op["out"]["Out"][0]
-        mfma = LSTM_MFMA and H == 256
+        mfma = H == 256               # batch-shared MFMA recurrence (csrc/lstm.hip) for 256-unit LSTMs
         for layer in range(L):
             outb = self.new_buf(cur.n, 1, cur.w, ndir * H)
             gate_views, frag = [], []
@@ -2087,15 +2075,15 @@ class Compiler(ChainMixin):
                     # the gate pre-activations leave the projection GEMM in the order the recurrent kernel reads them: the four
                     # gates of a wave's hidden units side by side ([wave][gate][unit in wave]: two whole cache lines per (wave,
                     # sample) instead of four half lines a kilobyte apart) — a permutation of the GEMM's output channels
-                    gperm = self.lstm_gate_order(H, LSTM_WAVES)
+                    gperm = self.lstm_gate_order(H)
                     w_ih, b = w_ih[gperm], b[gperm]
                 # input projection for all T as one GEMM (fp32 output to keep gate pre-activations exact-ish)
                 mat, coutp, Kp = self.pack_conv_weights(w_ih.reshape(4 * H, -1, 1, 1), np.ones(4 * H), cur)
                 gb = self.new_buf(cur.n, 1, cur.w, 4 * H, esize=4)
                 gates = View(gb, 0, cur.n, 1, cur.w, [(0, 4 * H)], 4 * H)
                 key = f"{name}:l{layer}d{d}"
-                w_off = self.add_weights(("lstm_ih", wl[2 * c], LSTM_WAVES if mfma else 0), self.tile_weights(mat))
-                b_off = self.add_weights(("lstm_b", wl[2 * c], LSTM_WAVES if mfma else 0), b.astype(np.float32))
+                w_off = self.add_weights(("lstm_ih", wl[2 * c], mfma), self.tile_weights(mat))
+                b_off = self.add_weights(("lstm_b", wl[2 * c], mfma), b.astype(np.float32))
                 self.emit(ir.OP_CONV, key + ":proj", [cur], gates, flags=ir.F_OUT_F32,
                           p={ir.P_KH: 1, ir.P_KW: 1, ir.P_SH: 1, ir.P_SW: 1, ir.P_PH: 0, ir.P_PW: 0,
                              ir.P_ACT: 0, ir.P_ACT2: 0, ir.P_COUT: coutp, ir.P_KTOT: Kp, ir.P_INSHIFT: 0,
@@ -2112,12 +2100,11 @@ class Compiler(ChainMixin):
                 self.add_gmacs(cur.n * cur.w * H * 4 * H / 1e9)
             if mfma:
                 # the recurrence of every direction of the layer in ONE launch (csrc/lstm.hip): batch-shared MFMA GEMM per step
-                whh_off = self.add_weights(("lstm_hh_mfma", LSTM_WAVES) + tuple(nm for nm, _ in frag),
-                                           lambda: np.concatenate([(self.lstm_fragments16 if LSTM_WAVES == 16 else self.lstm_fragments)(w)
-                                                                   for _, w in frag]))
+                whh_off = self.add_weights(("lstm_hh_mfma",) + tuple(nm for nm, _ in frag),
+                                           lambda: np.concatenate([self.lstm_fragments16(w) for _, w in frag]))
                 ov = View(outb, 0, cur.n, 1, cur.w, [(0, ndir * H)], ndir * H)
                 self.emit(ir.OP_LSTM, f"{name}:l{layer}", gate_views, ov, flags=ir.F_LSTM_MFMA,
-                          p={ir.P_HID: H, ir.P_REVERSE: 2 if ndir == 2 else 0, 2: LSTM_WAVES}, w_off=whh_off)
+                          p={ir.P_HID: H, ir.P_REVERSE: 2 if ndir == 2 else 0, ir.P_WAVES: 16}, w_off=whh_off)
                 self.add_gmacs(ndir * cur.n * cur.w * H * 4 * H / 1e9)
             cur = View(outb, 0, cur.n, 1, cur.w, [(0, ndir * H)], ndir * H, 0, "tbc")
         self.env[name] = cur
@@ -2236,7 +2223,7 @@ class Compiler(ChainMixin):
         return Program(ops=recs, weights=self.store, ws_bytes=int(ws_bytes), in_shape=(self.N, self.H, self.Wd, 8),
                        outputs=self.outputs, names=names, gmacs=self.gmacs,
                        op_gmacs=[o["gmac"] for o in self.ir_ops],
-                       wlevels=list(self.wlevels) if self.ragged else None, out_level=getattr(self, "_out_level", 0) or 0)
+                       wlevels=list(self.wlevels) if self.ragged else None, out_level=self._out_level or 0)
 
     def _final_view(self, v: View):
         r = self.vrec(v)
@@ -2251,13 +2238,16 @@ class Compiler(ChainMixin):
 
 
 def compile_model(desc, weights, batch, height, width, fetch_cols=(0,), want_probs=True, store=None, reuse=True, hilo=False,
-                  ragged=False, input_norm=None, fuse_preprocess=False, chain=None, tail2=None, se_lateral=None, fallbacks=None):
+                  ragged=False, input_norm=None, fuse_preprocess=False, chain=None, tail2=True, se_lateral=True, fallbacks=None):
     """reuse=False gives every buffer its own workspace range (debugging: all intermediates stay readable).
     hilo=True stores every conv / depthwise / transposed-conv weight as an fp16 hi + lo pair (F_HILO): ~22-bit weights for
     twice the MFMA work — for nets whose boxes must track an fp32 reference closely.
     ragged=True (recognisers): `width` is the widest sample of the batch; the plan runs with a per-sample width table
     (Program.width_table) and every sample gets the values a batch of its own width would have produced, bit for bit.
-    se_lateral=False / tail2=False: compile without that rewrite from the start; `fallbacks` (a dict): the rewrites this call had to
+    input_norm=(mean3, std3): the plan takes the raw resized pixels and folds the normalisation into the stem (fold_input_norm);
+    with fuse_preprocess=True the stem conv also resizes the uint8 frames itself (F_U8SRC).
+    chain: 1x1 / depthwise chains as OP_CHAIN (chains.py); None = the same as hilo.
+    se_lateral=False / tail2=False: compile without that rewrite from the start (any other value, None included, keeps it); `fallbacks` (a dict): the rewrites this call had to
     abandon are recorded there as {"tail2": False, "se_lateral": False} so that the caller (engine.Net) passes them for the next shape
     instead of paying the failed attempt again."""
     snap = store.snapshot() if store is not None else None
@@ -2265,16 +2255,8 @@ def compile_model(desc, weights, batch, height, width, fetch_cols=(0,), want_pro
     def build(se_lateral, tail2=tail2):
         if snap is not None:
             store.rollback(snap)         # blobs of an abandoned attempt leave the shared store (nothing refers to their offsets)
-        c = Compiler(desc, weights, batch, height, width, fetch_cols, want_probs, store, reuse, se_lateral=se_lateral, tail2=tail2)
-        c.ragged = bool(ragged)
-        c.hilo = bool(hilo)
-        c.input_norm = input_norm      # (mean3, std3): the plan takes RAW resized pixels + a ones channel (Compiler.fold_input_norm)
-        c.fuse_preprocess = bool(fuse_preprocess)    # ... and resizes them itself from the uint8 frames (F_U8SRC): the plan input IS the frames
-        c.chain = bool(hilo) if chain is None else bool(chain)      # 1x1 / depthwise chains as OP_CHAIN (chains.py): the hi + lo nets (mobile detectors)
-        c.chain_lo = True        # tensors that feed a chain are stored as fp16 hi + lo pairs
-        if c.hilo:
-            c.use_patch = False          # conv_patch_kernel has no two-pass K walk (the implicit-GEMM, stem and column kernels do)
-        return c.compile()
+        return Compiler(desc, weights, batch, height, width, fetch_cols, want_probs, store, reuse, hilo=hilo, ragged=ragged,
+                        input_norm=input_norm, fuse_preprocess=fuse_preprocess, chain=chain, tail2=tail2, se_lateral=se_lateral).compile()
     try:
         try:
             return build(se_lateral)

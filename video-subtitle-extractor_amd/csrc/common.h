@@ -199,8 +199,8 @@ struct ConvArgs {
 int launch_conv(const ConvArgs& a, hipStream_t st);
 int conv_tile_bn(int Np);   // which conv_mfma_kernel instantiation (BN = 128 / 64 / 32) serves Np output channels
 // wl_in / wl_out: per-sample widths of in0 / of the output in a ragged plan (device, [n]), else nullptr
-int launch_lstm_mfma(const TView& gf, const TView& gr, const TView& out, const half_t* whh, int rev_single, int ndir, int waves,
-                     const int* tl, hipStream_t st);
+int launch_lstm_mfma(const TView& gf, const TView& gr, const TView& out, const half_t* whh, int rev_single, int ndir, const int* tl,
+                     hipStream_t st);
 // OP_CHAIN (chain.hip): in0 = the chain's input tensor, out / out2 / out3 = the tensors it stores (out3 travels in the op's in2 slot)
 int launch_chain(const vse_op& op, const TView& in0, const TView& out, const TView& out2, const TView& out3, const char* wbase, hipStream_t st);
 int launch_simple_op(const vse_op& op, const TView& in0, const TView& in1, const TView& in2, const TView& out,
