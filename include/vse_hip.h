@@ -128,13 +128,11 @@ void vse_graph_destroy(vse_graph* graph);
  * vse_plan_run_ragged (NULL for an ordinary plan). */
 int vse_plan_profile(vse_plan* plan, void* ws, void* const* ext, int n_ext, const int32_t* d_widths, void* stream, float* ms);
 
-/* Which kernel instantiation op `i` dispatches to, as the name rocprofv3 reports ("conv_c3_kernel<4, 2>",
+/* Which kernel instantiation a record launches, as the name rocprofv3 reports ("conv_c3_kernel<4, 2>",
  * "conv_gemm_kernel<256, 256, 4, 4, 64, 2, 0>", "dwconv_kernel" ...): lets bench.py attribute the time vse_plan_profile
- * measures to the kernels of the committed rocprof summaries.  The string is thread-local and valid until the next call. */
-const char* vse_plan_op_kernel_name(vse_plan* plan, int i);
-/* The same as an integer key (kernel family x template parameters; 0 for non-conv ops) for per-layer A/B tools
- * (tools/bench_conv.py); the encoding is private to csrc/vse_runtime.hip — use vse_plan_op_kernel_name for anything shown. */
-int vse_plan_op_variant(vse_plan* plan, int i);
+ * measures to the kernels of the committed rocprof summaries.  Needs no plan, context or GPU; a conv record the library
+ * would refuse reads "(refused: <code>)".  The string is thread-local and valid until the next call. */
+const char* vse_op_kernel_name(const vse_op* op);
 
 /* ---- det pre-processing ----------------------------------------------------------------------------- */
 /* uint8 BGR frames [n, src_h, src_w, 3] (row pitch `pitch` bytes, frame stride `frame_stride` bytes) ->

@@ -52,12 +52,12 @@ def test_library_exports_header(built_lib):
     assert set(names) == set(engine.EXPORTS)
 
 
-def test_record_layouts_and_abi_version(built_lib):
-    """Record sizes agree between ir.py and the C structs; ABI version 3 (version 2 still exported vse_is_dev_build)."""
+def test_record_layouts_and_abi_version_4(built_lib):
+    """Record sizes agree between ir.py and the C structs; ABI version 4 (kernel names are read from a record, without a plan)."""
     lib = engine.load_library()
     assert lib.vse_sizeof_op() == ir.OP_DT.itemsize == 352
     assert lib.vse_sizeof_view() == ir.VIEW_DT.itemsize == 40
-    assert lib.vse_abi_version() == 3
+    assert lib.vse_abi_version() == 4
 
 
 def test_environment_switches_are_documented():

@@ -202,7 +202,7 @@ RAGGED_SEL_W = 768
 
 
 def c3_tile_eff(oh, ow):
-    """Mirror of conv_c3_plan (csrc/conv_c3.hip): best tile efficiency over the 16x32 / 8x64 / 4x128 tile shapes when waves
+    """Mirror of conv_c3_plan (conv_select in csrc/conv_select.hip): best tile efficiency over the 16x32 / 8x64 / 4x128 tile shapes when waves
     outside the map idle."""
     def axis(n, unit, waves):
         tile = unit * waves
@@ -1027,7 +1027,7 @@ class Compiler(ChainMixin):
 
     @staticmethod
     def gemm_eligible(kh, kw, ph, pw, cinp, inshift, flags):
-        """Mirror of conv_gemm_mode() (csrc/conv_gemm.hip): the layer runs on conv_gemm_kernel.  The launcher refuses an
+        """Mirror of conv_gemm_mode() (conv_select in csrc/conv_select.hip): the layer runs on conv_gemm_kernel.  The selector refuses an
         F_WK32 op it cannot send there, so a drift between the two rules fails loudly instead of computing garbage."""
         if inshift or (flags & (ir.F_PATCH | ir.F_DOT1 | ir.F_SRC2 | ir.F_UP2HEAD)):
             return False
@@ -1220,20 +1220,20 @@ class Compiler(ChainMixin):
                 raise UnsupportedGraph(f"ragged plan: conv {outname} reads a virtual concat")
             ow = self.sel_width(self.wl_after(inv.buf.wl, kw, sw, pw), ow)
         # k x k stride-1 convs on maps that tile well into 8x32 output patches go to the LDS-resident-patch kernel
-        pbn = 64 if rup(coutp, 64) < rup(coutp, 128) else 128          # mirrors conv_patch_bn / conv_patch_th in csrc
+        pbn = 64 if rup(coutp, 64) < rup(coutp, 128) else 128          # mirrors conv_patch_th (conv_select in csrc/conv_select.hip)
         pcap = 960 if pbn == 64 else 640
         th = 16 if (pbn == 64 and (16 + kh - 1) * (32 + kw - 1) <= pcap and -(-oh // 16) * 16 * 100 <= -(-oh // 8) * 8 * 112) else 8
         tile_eff = (oh * ow) / float(-(-oh // th) * th * -(-ow // 32) * 32)
         # (one block per CU: the fixed prologue/epilogue only amortises over a long enough K loop)
         patch_std = ((sh, sw) == (1, 1) and kh * kw >= 5 and (8 + kh - 1) * (32 + kw - 1) <= 640
                      and tile_eff >= PATCH_MIN_TILE_EFF and kh * kw * cin >= PATCH_MIN_K and coutp <= PATCH_MAX_COUT and self.use_patch)
-        # LIGHT variant (conv_patch_plan in csrc/conv_patch.hip): 8-row tiles whose halo patch fits 352 pixels (3x3, 1xk),
+        # LIGHT variant (conv_patch_plan, conv_select in csrc/conv_select.hip): 8-row tiles whose halo patch fits 352 pixels (3x3, 1xk),
         # 64 or 128 couts per tile, two blocks per CU; not combined with the fused 1-channel projection or a virtual concat
         tile_eff8 = (oh * ow) / float(-(-oh // 8) * 8 * -(-ow // 32) * 32)
         light_ok = ((sh, sw) == (1, 1) and kh * kw >= 5 and (8 + kh - 1) * (32 + kw - 1) <= 352 and tile_eff8 >= PATCH_MIN_TILE_EFF
                     and kh * kw * cin >= PATCH_MIN_K and self.use_patch and inv.parts is None
                     and coutp <= 128)
-        # column-per-step kernel (conv_col.hip, mirrors conv_col_ok): tall filters, <= 64 couts, 16-row tiles whose waves
+        # column-per-step kernel (conv_col.hip; mirrors conv_col_ok in conv_select): tall filters, <= 64 couts, 16-row tiles whose waves
         # below the map idle (a partial tile row costs ~0.35 + 0.65 * live waves / 8 of a full one)
         rem16 = oh % 16
         rows16 = oh // 16 + ((0.35 + 0.65 * -(-rem16 // 2) / 8.0) if rem16 else 0.0)

@@ -170,34 +170,7 @@ struct TView {
     int n, h, w, c, ld, esize;
 };
 
-// Kernel launchers implemented in the .hip files; all enqueue on `st`.
-struct ConvArgs {
-    TView in, res, out;
-    const half_t* w;      // tiled [K/64][Np][64]
-    const float* bias;    // [Np]
-    const half_t* zero;   // >= 64 bytes of device zeros
-    int kh, kw, sh, sw, ph, pw, act, act2, Np, Kp, inshift, resshift, cinp, flags;
-    float act_a, act_b, post_a, post_b;
-    // F_DOT1: fused 1x1 projection to one channel
-    const float* dotw;
-    float dotb;
-    int dotact;
-    TView dot_out;
-    // F_SRC2: second input source of a virtual channel concat
-    TView in2;
-    int in2shift;
-    // ragged plans: per-sample output widths (device, [n]); output pixels at x >= wl_out[n] are written as zeros
-    const int* wl_out;
-    int lo_off;           // P_LO_OUT: channel offset of the lo half of an fp16 hi + lo pair output (0 = plain fp16)
-    int res_lo_off;       // P_LO_RES: ... of the residual
-    int in_lo_off;        // P_LO_IN: ... of the input (F_DWPRE)
-    // F_U8SRC: the uint8 BGR frames the stem conv pre-processes itself (vse_plan_set_source)
-    const uint8_t* u8src;
-    int u8_h, u8_w;
-    long u8_pitch, u8_fstride;
-};
-int launch_conv(const ConvArgs& a, hipStream_t st);
-int conv_tile_bn(int Np);   // which conv_mfma_kernel instantiation (BN = 128 / 64 / 32) serves Np output channels
+// Kernel launchers implemented in the .hip files; all enqueue on `st` (the conv launchers: conv_common.h).
 // wl_in / wl_out: per-sample widths of in0 / of the output in a ragged plan (device, [n]), else nullptr
 int launch_lstm_mfma(const TView& gf, const TView& gr, const TView& out, const half_t* whh, int rev_single, int ndir, const int* tl,
                      hipStream_t st);

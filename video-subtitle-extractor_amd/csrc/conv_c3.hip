@@ -33,7 +33,6 @@
 // layer (128->128 0.687 -> 0.751 ms, 64->64 0.76 -> 0.96 ms): the epilogue's stores sit in the same in-order vmcnt queue as
 // the LDS-DMAs, so the first counted waits of the next tile also wait for the stores' HBM round trip.)
 #define C3RING 4
-#define C3BN 64
 
 // BN = 64 couts per block (TN = 2 accumulator tiles per row) or, for layers with <= 32 couts (the mobile detectors' 96 -> 24 neck convs,
 // the server detector's 32 -> 32), BN = 32: half the MFMAs, half the weight stage; everything else is the same code.
@@ -289,45 +288,19 @@ __global__ __launch_bounds__(512, 4) void conv_c3_kernel(const ConvParams p) { c
 template <int RW, int CW>
 __global__ __launch_bounds__(512, 4) void conv_c3n32_kernel(const ConvParams p) { conv_c3_body<RW, CW, 32>(p); }
 
-// Tile shape per map: estimated cost (in full tiles) of covering OH x OW with (2 RW) x (32 CW) tiles when waves outside the
-// map idle (a partial tile costs ~0.35 + 0.65 * live waves / 8 of a full one).  Mirrored by compiler.py (c3_tile_eff).
-static double c3_axis_cost(int n, int unit, int waves) {      // n pixels along an axis covered by tiles of `waves` x `unit`
-    const int tile = unit * waves, full = n / tile, rem = n - full * tile;
-    return full + (rem ? 0.35 + 0.65 * ((rem + unit - 1) / unit) / (double)waves : 0.0);
-}
-double conv_c3_plan(int OH, int OW, int* rw_out) {
-    double best = 0;
-    int brw = 8;
-    for (int rw = 8; rw >= 2; rw >>= 1) {
-        const int cw = 8 / rw;
-        // partial tiles in both directions: live fraction multiplies; approximate by the product of the axis costs
-        const double cost = c3_axis_cost(OH, 2, rw) * c3_axis_cost(OW, 32, cw) * 512.0;
-        const double eff = (double)OH * OW / cost;
-        if (eff > best + 1e-9) { best = eff; brw = rw; }
-    }
-    if (rw_out) *rw_out = brw;
-    return best;
-}
-bool conv_c3_ok(int kh, int kw, int sh, int sw, int ph, int pw, int cinp, int flags) {
-    return kh == 3 && kw == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && (cinp & 15) == 0
-           && !(flags & (F_SRC2 | F_PIXSHUF | F_DOT1));
-}
-
-int launch_conv_c3(const ConvParams& pin, int n_img, hipStream_t st) {
+// k.arg = RW, the 32-cout form; which layers it serves and the tile shape: conv_c3_ok / conv_c3_plan (conv_select.hip)
+int launch_conv_c3(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
     ConvParams p = pin;
-    if (!conv_c3_ok(p.kh, p.kw, p.sh, p.sw, p.ph, p.pw, p.cinp, p.flags)) return VSE_E_UNSUPPORTED;
     if ((double)p.Hs * p.Ws * p.in_ld > 2.0e9) return VSE_E_UNSUPPORTED;      // 32-bit in-image offsets
-    int rw;
-    conv_c3_plan(p.OH, p.OW, &rw);
-    const int cw = 8 / rw;
+    const int rw = k.arg[0], cw = 8 / rw;
     const bool hlsum = (p.flags & F_HLSUM) != 0;
     if (hlsum && (p.Np > 32 || (p.flags & F_HILO))) return VSE_E_INVAL;
-    const int bn = (p.Np <= 32 && !hlsum) ? 32 : C3BN;
+    const int bn = k.arg[1] ? 32 : C3BN;
     p.wnp = hlsum ? 64 : p.Np;
     p.ntn = hlsum ? 1u : (unsigned)((p.Np + bn - 1) / bn);
     p.tiles_h = (p.OH + 2 * rw - 1) / (2 * rw);
     p.tiles_w = (p.OW + 32 * cw - 1) / (32 * cw);
-    const unsigned long long blocks = (unsigned long long)n_img * p.tiles_h * p.tiles_w * p.ntn;
+    const unsigned long long blocks = (unsigned long long)conv_images(p) * p.tiles_h * p.tiles_w * p.ntn;
     if (blocks == 0 || blocks > 0x7fffffffull) return VSE_E_INVAL;
     const dim3 grid((unsigned)blocks), block(512);
 #ifdef VSE_TRACE

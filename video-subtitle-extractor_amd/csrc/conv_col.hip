@@ -28,8 +28,6 @@
 #include "conv_common.h"
 
 #define CTH 16
-#define CTW 32
-#define CPW 48            // patch row stride in pixels
 #define CRING 4
 
 template <int KH, int BN>
@@ -251,28 +249,20 @@ __global__ __launch_bounds__(512, 2) void conv_col_kernel(const ConvParams p) {
     }
 }
 
-// Eligibility (mirrored by compiler.py, which packs the weight stream for it, F_COL)
-int conv_col_bn(int Np) { return Np > 32 ? 64 : 32; }
-bool conv_col_ok(int kh, int kw, int sh, int sw, int cinp, int Np, int flags) {
-    return sh == 1 && sw == 1 && (kh == 9 || kh == 7 || kh == 5) && kw >= 3 && CTW + kw - 1 <= CPW && (cinp & 15) == 0 && Np <= 64
-           && !(flags & (F_SRC2 | F_PIXSHUF | F_DOT1));
-}
-
-
-int launch_conv_col(const ConvParams& pin, int n_img, hipStream_t st) {
+// k.arg = KH, BN; which layers it serves: conv_col_ok (conv_select.hip)
+int launch_conv_col(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
     ConvParams p = pin;
-    if (!conv_col_ok(p.kh, p.kw, p.sh, p.sw, p.cinp, p.Np, p.flags)) return VSE_E_UNSUPPORTED;
-    const int bn = conv_col_bn(p.Np);
+    const int kh = k.arg[0], bn = k.arg[1];
     p.ntn = (unsigned)((p.Np + bn - 1) / bn);
     p.tiles_h = (p.OH + CTH - 1) / CTH;
     p.tiles_w = (p.OW + CTW - 1) / CTW;
-    const unsigned long long blocks = (unsigned long long)n_img * p.tiles_h * p.tiles_w * p.ntn;
+    const unsigned long long blocks = (unsigned long long)conv_images(p) * p.tiles_h * p.tiles_w * p.ntn;
     if (blocks == 0 || blocks > 0x7fffffffull) return VSE_E_INVAL;
     const dim3 grid((unsigned)blocks), block(512);
-    if (p.kh == 9 && bn == 64) hipLaunchKernelGGL((conv_col_kernel<9, 64>), grid, block, 0, st, p);
-    else if (p.kh == 9) hipLaunchKernelGGL((conv_col_kernel<9, 32>), grid, block, 0, st, p);
-    else if (p.kh == 7 && bn == 64) hipLaunchKernelGGL((conv_col_kernel<7, 64>), grid, block, 0, st, p);
-    else if (p.kh == 7) hipLaunchKernelGGL((conv_col_kernel<7, 32>), grid, block, 0, st, p);
+    if (kh == 9 && bn == 64) hipLaunchKernelGGL((conv_col_kernel<9, 64>), grid, block, 0, st, p);
+    else if (kh == 9) hipLaunchKernelGGL((conv_col_kernel<9, 32>), grid, block, 0, st, p);
+    else if (kh == 7 && bn == 64) hipLaunchKernelGGL((conv_col_kernel<7, 64>), grid, block, 0, st, p);
+    else if (kh == 7) hipLaunchKernelGGL((conv_col_kernel<7, 32>), grid, block, 0, st, p);
     else if (bn == 64) hipLaunchKernelGGL((conv_col_kernel<5, 64>), grid, block, 0, st, p);
     else hipLaunchKernelGGL((conv_col_kernel<5, 32>), grid, block, 0, st, p);
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;

@@ -1,6 +1,16 @@
-// Shared by the implicit-GEMM conv kernel (conv_mfma.hip) and the LDS-resident-patch conv kernel (conv_patch.hip).
+// Shared by the conv kernels (conv_*.hip) and the host code that chooses and launches them (conv_select.hip).
 #pragma once
 #include "common.h"
+
+// Tile and table limits that a kernel and conv_select() both use
+#define PTW 32                  // conv_patch_kernel: output tile width
+#define CTW 32                  // conv_col_kernel: output tile width
+#define CPW 48                  // conv_col_kernel: patch row stride in pixels
+#define C3BN 64                 // conv_c3_kernel: couts per block
+#define PW_MAXN 256             // conv_pw_kernel: staged weight rows (couts)
+#define PW_MAXN_HILO 128        // ... with hi + lo weight tables
+#define DWPW_ROWS_MAX_KS 3      // conv_dwpw_rows_kernel: 16-channel slices at stride 2
+#define DWPW_ROWS_MAX_KS_S1 3   // ... at stride 1
 
 struct ConvParams {
     const half_t* in;
@@ -290,36 +300,71 @@ __device__ __forceinline__ float conv_epilogue_dot(const ConvParams& p, const fl
     return part;
 }
 
-int launch_conv_patch(const ConvParams& p, int n_img, hipStream_t st);
+// ---- which kernel serves a conv record (conv_select.hip) -------------------------------------------------------------------
+// conv_select() answers it from the record's parameters alone (no pointer, no HIP call); launch_conv() launches that answer and
+// vse_op_kernel_name() names it.  arg[] = the family's template arguments:
+//   CK_GEMM    kCfg index, MASK              conv_gemm_kernel<kCfg[i] (six), MASK>
+//   CK_SMALLM  KT, hi + lo                   conv_smallm_kernel<KT> / conv_smallm_hl_kernel<KT>
+//   CK_MFMA    BN (128 / 64 / 32), UPS       conv_mfma_kernel<BN == 128 ? 128 : 256, BN, BN == 128 ? 2 : 4, BN == 128 ? 2 : 1, UPS>
+//   CK_PATCH   TH, BN, MODE                  conv_patch_kernel<TH, BN, MODE>
+//   CK_COL     KH, BN                        conv_col_kernel<KH, BN>
+//   CK_C3      RW, 32-cout form              conv_c3_kernel<RW, 8 / RW> / conv_c3n32_kernel<RW, 8 / RW>
+//   CK_PW      KS, HILO, TAIL                conv_pw_kernel<KS, HILO> / conv_pw_tail_kernel<KS>
+//   CK_DWPW    KS, LO, S (0 = tile form)     conv_dwpw_kernel<KS, 3, LO> / conv_dwpw_rows_kernel<KS, LO, S>
+//   CK_HEAD    resident                      conv_head_up2r_kernel / conv_head_up2_kernel
+//   CK_STEM    S, HILO, U8                   conv_stem_kernel<S, S, HILO, U8>
+enum { CK_NONE = 0, CK_GEMM, CK_SMALLM, CK_MFMA, CK_PATCH, CK_COL, CK_C3, CK_PW, CK_DWPW, CK_HEAD, CK_STEM };
+struct ConvKernel {
+    int family;     // CK_NONE: refused before any launcher
+    int rc;         // != VSE_OK: refused with this code (a CK_PW refusal is reported by its launcher, after the launcher's own checks)
+    int arg[3];
+};
+
+// conv_gemm_kernel tile configurations (BM x BN, waves WM x WN, BK, stages).  Measured and dropped on MI355X (tools/bench_conv.py,
+// DESIGN.md): BK = 64 rings with 2-3 stages (fewer bytes in flight per CU, -5..-25 %), 4-stage 128 x 128 (2 blocks/CU, -10 %),
+// 512 x 128, 8-wave 256 x 256 (VGPR spills), and a persistent one-block-per-slot variant of every shape (-5..-15 %: the hardware
+// already overlaps one block's store tail with its neighbours' K loops, and stores share vmcnt with the LDS-DMAs); 4-stage rings for
+// the 16-wave tiles (128 / 112 KiB, 0..-12 %: more bytes in flight do not help, tools/ubench/fill.hip shows why: the L2 takes ~1
+// request per channel clock, i.e. ~32 B/clk/CU of 64-byte row segments chip-wide, HBM streams at ~10 B/clk/CU, and a stream that
+// mixes both gets ~15 B/clk/CU), BK 64 / 2 stages for 256 x 256 (8x slower: spills).
+//   0: 128 x 128,  4 waves (2 x 2), BK 32, 3 stages  (48 KiB LDS, 3 blocks/CU)  — the conv_mfma_kernel shape
+//   1: 256 x  64,  4 waves (4 x 1), BK 32, 3 stages  (60 KiB, 2 blocks/CU)
+//   2: 256 x  32,  4 waves (4 x 1), BK 32, 3 stages
+//   3: 256 x 128,  8 waves (4 x 2), BK 32, 3 stages  (72 KiB, 2 blocks/CU)
+//   4: 256 x 256, 16 waves (4 x 4), BK 32, 3 stages  (96 KiB, 1 block/CU)
+//   5: 256 x 192, 16 waves (8 x 2), BK 32, 3 stages  (96 KiB, 1 block/CU; weight rows staged as 256)
+//   6 / 7: the same two tiles with BK 64 and 2 stages (128 KiB) for layers with cin % 64 == 0
+struct GemmCfg { int bm, bn, wm, wn, bk, st; };
+constexpr GemmCfg kCfg[] = {{128, 128, 2, 2, 32, 3}, {256, 64, 4, 1, 32, 3}, {256, 32, 4, 1, 32, 3}, {256, 128, 4, 2, 32, 3},
+                            {256, 256, 4, 4, 32, 3}, {256, 192, 8, 2, 32, 3}, {256, 256, 4, 4, 64, 2}, {256, 192, 8, 2, 64, 2}};
+
+// geometry of the uint8 source frames of one run (F_U8SRC plans)
+struct SrcGeom { int h, w; long pitch, fstride; };
+// The parameters of a conv record: in / res / in2 / out / dot_out = its resolved in0 / in1 / in2 / out / out2 views, wts = the weight
+// blob, u8src = the frames of an F_U8SRC stem.  Naming passes null pointers: only the shapes count.
+ConvParams conv_params(const vse_op& o, const TView& in, const TView& res, const TView& in2, const TView& out, const TView& dot_out,
+                       const char* wts, const half_t* zero, const int* wl_out, const uint8_t* u8src, const SrcGeom& src);
+ConvKernel conv_select(const ConvParams& p, int Kp);       // Kp = the record's P_KTOT
+int conv_kernel_name(const ConvKernel& k, char* buf, size_t n);
+int launch_conv(const vse_op& o, const TView& in, const TView& res, const TView& in2, const TView& out, const TView& dot_out,
+                const char* wts, const half_t* zero, const int* wl_out, const uint8_t* u8src, const SrcGeom& src, hipStream_t st);
+// images of a launch (M = images x OH x OW)
+static inline long conv_images(const ConvParams& p) { return p.OH && p.OW ? p.M / ((long)p.OH * p.OW) : 0; }
+
+// The family launchers: map the choice to its instantiation, compute the grid, check what only a launch can (pointers, alignment)
+int launch_conv_gemm(const ConvParams& p, const ConvKernel& k, hipStream_t st);      // scalar-addressed implicit GEMM (conv_gemm.hip)
+int launch_conv_smallm(const ConvParams& p, const ConvKernel& k, hipStream_t st);    // 1x1 conv, operands from global memory (conv_smallm.hip)
+int launch_conv_mfma(const ConvParams& p, const ConvKernel& k, hipStream_t st);      // the general implicit GEMM (conv_mfma.hip)
+int launch_conv_patch(const ConvParams& p, const ConvKernel& k, hipStream_t st);     // LDS-resident patch (conv_patch.hip, F_PATCH)
 // one filter column per step over a 16-channel patch (conv_col.hip, F_COL): 9x9 / 7x7 / 5x5, <= 64 couts
-int launch_conv_col(const ConvParams& p, int n_img, hipStream_t st);
-// depthwise k x k conv fused in front of a 1x1 conv (conv_dwpw.hip, F_DWPRE): p.kh / sh / ph = the depthwise geometry, p.dotw = its table
-int launch_conv_dwpw(const ConvParams& p, hipStream_t st);
-bool conv_dwpw_ok(int k, int s, int cinp, int Np, int flags);
-int conv_dwpw_rows_stride(int k, int pad, int s, int cinp, int lo_in);      // stride of the row-streaming form (conv_dwpw_rows_kernel), 0 = the tile form
+int launch_conv_col(const ConvParams& p, const ConvKernel& k, hipStream_t st);
 // 3x3 sibling, two blocks per CU (conv_c3.hip, F_COL with kh = kw = 3)
-int launch_conv_c3(const ConvParams& p, int n_img, hipStream_t st);
-double conv_c3_plan(int OH, int OW, int* rw_out);
-bool conv_c3_ok(int kh, int kw, int sh, int sw, int ph, int pw, int cinp, int flags);
-// pointwise conv over <= 64 input channels and <= 64 couts, no LDS staging (conv_pw.hip, F_PW)
-int launch_conv_pw(const ConvParams& p, hipStream_t st);
-bool conv_pw_ok(int kh, int kw, int sh, int sw, int ph, int pw, int cinp, int Np, int inshift, int flags);
-int conv_col_bn(int Np);
-bool conv_col_ok(int kh, int kw, int sh, int sw, int cinp, int Np, int flags);
+int launch_conv_c3(const ConvParams& p, const ConvKernel& k, hipStream_t st);
+// pointwise conv over <= 64 input channels and <= 256 couts, no LDS staging (conv_pw.hip, F_PW)
+int launch_conv_pw(const ConvParams& p, const ConvKernel& k, hipStream_t st);
+// depthwise k x k conv fused in front of a 1x1 conv (conv_dwpw.hip, F_DWPRE): p.kh / sh / ph = the depthwise geometry, p.dotw = its table
+int launch_conv_dwpw(const ConvParams& p, const ConvKernel& k, hipStream_t st);
 // DB head evaluated on the low-resolution grid (conv_head.hip, F_UP2HEAD)
-int launch_conv_head_up2(const ConvParams& p, int n_img, hipStream_t st);
+int launch_conv_head(const ConvParams& p, const ConvKernel& k, hipStream_t st);
 // 3x3 stem over <= 4 real input channels (conv_stem.hip, F_STEM)
-int launch_conv_stem(const ConvParams& p, int n_img, hipStream_t st);
-// scalar-addressed implicit GEMM (conv_gemm.hip): VSE_E_UNSUPPORTED when the layer is not eligible
-int launch_conv_gemm(ConvParams& p, int Kp, hipStream_t st);
-int conv_gemm_config(int Np, int cinp, long M);
-// 1x1 conv over <= 256 pixels, operands straight from global memory (conv_smallm.hip); `mode` = conv_gemm_mode()
-bool conv_smallm_ok(const ConvParams& p, int mode);
-bool conv_smallm_shape_ok(int mode, long M, int sh, int sw, int same_hw, int flags, int cinp);
-bool conv_smallk_ok(const ConvParams& p);
-bool conv_smallk_shape_ok(int kh, int kw, int sh, int sw, int ph, int pw, int inshift, int same_hw, int flags, int cinp, long M, int Np);
-int launch_conv_smallm(const ConvParams& p, hipStream_t st);   // index into the tile-configuration table of conv_gemm.hip
-int conv_gemm_mode(int kh, int kw, int sh, int sw, int ph, int pw, int cinp, int Kp, int inshift, int flags);
-int conv_patch_th(int kh, int kw, int OH, int bn);
-int conv_patch_bn(int Np);
-void conv_patch_plan(int kh, int kw, int OH, int Np, int flags, int* th, int* bn, int* mode);
+int launch_conv_stem(const ConvParams& p, const ConvKernel& k, hipStream_t st);

@@ -436,12 +436,6 @@ __global__ __launch_bounds__(256, 2) void conv_dwpw_rows_kernel(const ConvParams
     }
 }
 
-// 5 x 5 filters stay on two launches (25 taps per lane: 0.21 against 0.09 + 0.04 ms, and the unrolled form spills)
-bool conv_dwpw_ok(int k, int s, int cinp, int Np, int flags) {
-    return k == 3 && (s == 1 || s == 2) && (cinp & 7) == 0 && cinp <= 96 && Np <= 192 && (flags & F_HILO)
-           && !(flags & (F_SRC2 | F_DOT1 | F_PATCH | F_COL | F_PIXSHUF | F_IMGW | F_STEM));
-}
-
 template <int KS, int K, bool LO>
 static int launch_dwpw_t(const ConvParams& p, hipStream_t st) {
     const int ntile = (p.Np + 31) >> 5;
@@ -456,12 +450,6 @@ static int launch_dwpw_t(const ConvParams& p, hipStream_t st) {
     hipLaunchKernelGGL((conv_dwpw_kernel<KS, K, LO>), dim3((unsigned)blocks), dim3(256), lds, st, p);
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
-
-// the row-streaming form takes 3 x 3 'same' filters (pad 1) over <= 3 slices of 16 channels: there the row-invariant depthwise weights
-// stay in registers (see LAUNDER in the kernel).  Wider units measured SLOWER than the tile form with the weight reads left in the row
-// loop (96 -> 192 @34 x 60, stride 2: 0.208 vs 0.168 ms) and spill with them hoisted: they keep the tile form.
-#define DWPW_ROWS_MAX_KS 3
-#define DWPW_ROWS_MAX_KS_S1 3
 
 // rows per strip segment of the row-streaming form: long strips amortise the two extra input rows and the block prologue, short ones keep
 // enough waves in flight on small maps (>= ~8 k waves where the map allows it)
@@ -504,20 +492,12 @@ static int launch_dwpw_rows_t(const ConvParams& pin, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
 
-// Only PAIR inputs take it: on plain fp16 inputs (the layer-by-layer programs) the tile form measures the same or better (16 -> 32
-// @272 x 480: 0.373 vs 0.365 ms, 48 -> 48 @136 x 240: 0.215 vs 0.286) — half the gathers and half the multiply-adds per pixel leave
-// little for the strip walk to save.
-int conv_dwpw_rows_stride(int k, int pad, int s, int cinp, int lo_in) {
-    const int ks = (cinp + 15) / 16;
-    return (lo_in != 0 && k == 3 && pad == 1 && ((s == 1 && ks <= DWPW_ROWS_MAX_KS_S1) || (s == 2 && ks <= DWPW_ROWS_MAX_KS))) ? s : 0;
-}
-static bool dwpw_rows_wanted(const ConvParams& p, int ks) { (void)ks; return conv_dwpw_rows_stride(p.kh, p.ph, p.sh, p.cinp, p.in_lo_off) != 0; }
-
 // p.kh / p.sh / p.ph describe the DEPTHWISE conv (the 1x1 conv has no geometry); p.dotw = the aux blob; p.in_lo_off = the input's pair offset
-int launch_conv_dwpw(const ConvParams& p, hipStream_t st) {
-    if (!conv_dwpw_ok(p.kh, p.sh, p.cinp, p.Np, p.flags) || p.kh != p.kw || p.sh != p.sw || p.ph != p.pw || !p.dotw) return VSE_E_UNSUPPORTED;
-    const int ks = (p.cinp + 15) / 16;
-    if (dwpw_rows_wanted(p, ks)) {
+// k.arg = KS, LO, the row-streaming form's stride (0 = the tile form); which layers it serves: conv_dwpw_ok (conv_select.hip)
+int launch_conv_dwpw(const ConvParams& p, const ConvKernel& k, hipStream_t st) {
+    if (!p.dotw) return VSE_E_INVAL;
+    const int ks = k.arg[0];
+    if (k.arg[2]) {
 #define DWPW_ROWS(KS_) launch_dwpw_rows_t<KS_, true>(p, st)
         switch (ks) {
             case 1: return DWPW_ROWS(1);
@@ -526,7 +506,7 @@ int launch_conv_dwpw(const ConvParams& p, hipStream_t st) {
         }
 #undef DWPW_ROWS
     }
-#define DWPW(KS_) (p.in_lo_off ? launch_dwpw_t<KS_, 3, true>(p, st) : launch_dwpw_t<KS_, 3, false>(p, st))
+#define DWPW(KS_) (k.arg[1] ? launch_dwpw_t<KS_, 3, true>(p, st) : launch_dwpw_t<KS_, 3, false>(p, st))
     switch (ks) {
         case 1: return DWPW(1);
         case 2: return DWPW(2);

@@ -14,7 +14,7 @@
 //     256 pixels x 128/256 couts raise the flops per fetched byte over the 128 x 128 x 32 tile of conv_mfma_kernel.
 //   * the ring is unrolled by stage, so every ds_read_b128 is `per-thread VGPR + immediate`.
 //
-// Eligibility and the tile configuration are decided in launch_conv_gemm(); everything else stays on conv_mfma_kernel.
+// Eligibility and the tile configuration (kCfg, conv_common.h) are decided by conv_select(); everything else stays on conv_mfma_kernel.
 
 #include <type_traits>
 #include "conv_common.h"
@@ -271,97 +271,39 @@ void conv_gemm_kernel(const ConvParams p) {
     }
 }
 
-// 0 = not eligible; 1 = masked variant; 2 = unmasked 1x1 variant
-int conv_gemm_mode(int kh, int kw, int sh, int sw, int ph, int pw, int cinp, int Kp, int inshift, int flags) {
-    (void)sh; (void)sw;
-    if (inshift || (flags & (F_PATCH | F_DOT1 | F_SRC2))) return 0;
-    if (cinp % 32) return 0;
-    if (kh * kw > 31) return 0;
-    if (kh < 2 * ph + 1 || kw < 2 * pw) return 0;
-    if (kh == 1 && kw == 1 && ph == 0 && pw == 0 && Kp == cinp) return 2;
-    return 1;
+template <int C>
+static void launch_cfg(const ConvParams& p, int mask, dim3 grid, hipStream_t st) {
+    constexpr GemmCfg g = kCfg[C];
+    dim3 block(64 * g.wm * g.wn);
+    if (mask) hipLaunchKernelGGL((conv_gemm_kernel<g.bm, g.bn, g.wm, g.wn, g.bk, g.st, 1>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((conv_gemm_kernel<g.bm, g.bn, g.wm, g.wn, g.bk, g.st, 0>), grid, block, 0, st, p);
 }
 
-// Tile configurations (BM x BN, waves, BK, stages).  Index = the `cfg` field of vse_plan_op_variant() (bench.py mirrors
-// the names).  Measured and dropped on MI355X (tools/bench_conv.py): BK = 64 rings with 2-3 stages (fewer
-// bytes in flight per CU, -5..-25 %), 4-stage 128 x 128 (2 blocks/CU, -10 %), 512 x 128, 8-wave 256 x 256 (VGPR
-// spills), and a persistent one-block-per-slot variant of every shape (-5..-15 %: the hardware already overlaps
-// one block's store tail with its neighbours' K loops, and stores share vmcnt with the LDS-DMAs); 4-stage rings for
-// the 16-wave tiles (128 / 112 KiB, 0..-12 %: more bytes in flight do not help, tools/ubench/fill.hip shows why: the
-// L2 takes ~1 request per channel clock, i.e. ~32 B/clk/CU of 64-byte row segments chip-wide, HBM streams at ~10 B/clk/CU,
-// and a stream that mixes both gets ~15 B/clk/CU), BK 64 / 2 stages for 256 x 256 (8x slower: spills).
-//   0: 128 x 128,  4 waves (2 x 2), BK 32, 3 stages  (48 KiB LDS, 3 blocks/CU)  — the conv_mfma_kernel shape
-//   1: 256 x  64,  4 waves (4 x 1), BK 32, 3 stages  (60 KiB, 2 blocks/CU)
-//   2: 256 x  32,  4 waves (4 x 1), BK 32, 3 stages
-//   6: 256 x 128,  8 waves (4 x 2), BK 32, 3 stages  (72 KiB, 2 blocks/CU)
-//  16: 256 x 256, 16 waves (4 x 4), BK 32, 3 stages  (96 KiB, 1 block/CU)
-//  17: 256 x 192, 16 waves (8 x 2), BK 32, 3 stages  (96 KiB, 1 block/CU; weight rows staged as 256)
-//  18 / 19: the same two tiles with BK 64 and 2 stages (128 KiB) for layers with cin % 64 == 0
-struct GemmCfg { int bm, bn, bk; };
-static const GemmCfg kCfg[] = {{128, 128, 32}, {256, 64, 32}, {256, 32, 32}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {256, 128, 32},
-                               {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0},
-                               {256, 256, 32}, {256, 192, 32}, {256, 256, 64}, {256, 192, 64}};
-
-// Which configuration serves a layer.  The kernel is bound by the L2 -> LDS fill (ablation: MFMAs and fragment reads
-// are free, the DMA stream and the store tail are not), so the choice minimises fetched bytes: one cout tile when the
-// couts fit 192 / 256 (the activation tile is then fetched once instead of 2-3 times), 256-pixel tiles (weights re-read
-// half as often), as long as the grid still fills the 256 CUs.  Zero-padded couts cost MFMA issue slots only.
-int conv_gemm_config(int Np, int cinp, long M) {
-    auto ntn = [&](int bn) { return (long)((Np + bn - 1) / bn); };
-    // the 16-wave tiles run 64-deep K tiles in a 2-stage ring where the channels allow it (whole 128-byte lines per
-    // activation row and half the barriers; A/B on one box: -2..-4 %); the 8-wave 256 x 128 tile loses its second block per CU
-    auto deep = [&](int c) { return cinp % 64 == 0 ? c + 2 : c; };          // 16 -> 18, 17 -> 19
-    if (Np <= 32) return 2;
-    if (Np <= 64) return 1;
-    const long mt = (M + 255) / 256;
-    if (Np <= 128) return mt >= 256 ? 6 : 0;
-    if (Np <= 192) return mt >= 192 ? deep(17) : (mt >= 128 ? 6 : 0);
-    const double w256 = (double)ntn(256) * 256 / Np, w192 = (double)ntn(192) * 192 / Np;
-    const bool pick256 = ntn(256) < ntn(192) || (ntn(256) == ntn(192) && w256 <= w192);
-    if (pick256 && mt * ntn(256) >= 192 && w256 <= 1.34) return deep(16);
-    if (mt * ntn(192) >= 192 && w192 <= 1.34) return deep(17);
-    if (mt * ntn(256) >= 192 && w256 <= 1.34) return deep(16);
-    return mt * ntn(128) >= 512 ? 6 : 0;
-}
-
-template <int BM, int BN, int WM, int WN, int BKT, int ST>
-static void launch_cfg(const ConvParams& p, int mode, dim3 grid, hipStream_t st) {
-    dim3 block(64 * WM * WN);
-    if (mode == 1) hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, BKT, ST, 1>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, BKT, ST, 0>), grid, block, 0, st, p);
-}
-
-int launch_conv_gemm(ConvParams& p, int Kp, hipStream_t st) {
-    const int mode = conv_gemm_mode(p.kh, p.kw, p.sh, p.sw, p.ph, p.pw, p.cinp, Kp, p.inshift, p.flags);
-    if (!mode) return VSE_E_UNSUPPORTED;
-    p.nkh = Kp / ((p.flags & F_WK32) ? 32 : 64);                         // (K tiles of one weight pass, as conv_smallm.hip walks them)
-    if (conv_smallm_ok(p, mode)) return launch_conv_smallm(p, st);       // a handful of pixels (SE gates): conv_smallm.hip
-    // 32-bit offsets: the rows of one block span at most BM output pixels (+ one image seam), the tap walk kh rows
-    const double span = ((double)512 * p.sw + (512.0 / p.OW + 3) * p.sh * p.Ws + (double)p.kh * p.Ws + p.kw) * p.in_ld * 2;
-    if (span > 1.9e9 || (double)Kp * p.Np * 2 > 1.9e9) return VSE_E_UNSUPPORTED;
-    const int c = conv_gemm_config(p.Np, p.cinp, p.M);
+// k.arg[0] = the kCfg configuration, k.arg[1] = MASK
+int launch_conv_gemm(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+    ConvParams p = pin;
+    const int c = k.arg[0];
     const GemmCfg& g = kCfg[c];
     p.ntn = (unsigned)((p.Np + g.bn - 1) / g.bn);
-    p.nk = Kp / g.bk;
-    p.nkh = p.nk;
+    p.nkh = p.nkh * 32 / g.bk;               // (nkh = Kp / 32 on entry)
+    p.nk = p.nkh;
     if (p.flags & F_HILO) p.nk *= 2;
     unsigned long long tiles = (unsigned long long)((p.M + g.bm - 1) / g.bm) * p.ntn;
     if (p.flags & F_IMGW) {
-        if (mode != 2 || p.hw_img <= 0 || p.M % p.hw_img) return VSE_E_UNSUPPORTED;      // unmasked 1x1 only
         p.tiles_img = (p.hw_img + g.bm - 1) / g.bm;
         tiles = (unsigned long long)(p.M / p.hw_img) * p.tiles_img * p.ntn;
     }
     if (tiles == 0 || tiles > 0x7fffffffull) return VSE_E_INVAL;
     dim3 grid((unsigned)tiles);
     switch (c) {
-        case 1: launch_cfg<256, 64, 4, 1, 32, 3>(p, mode, grid, st); break;
-        case 2: launch_cfg<256, 32, 4, 1, 32, 3>(p, mode, grid, st); break;
-        case 6: launch_cfg<256, 128, 4, 2, 32, 3>(p, mode, grid, st); break;
-        case 16: launch_cfg<256, 256, 4, 4, 32, 3>(p, mode, grid, st); break;
-        case 17: launch_cfg<256, 192, 8, 2, 32, 3>(p, mode, grid, st); break;
-        case 18: launch_cfg<256, 256, 4, 4, 64, 2>(p, mode, grid, st); break;
-        case 19: launch_cfg<256, 192, 8, 2, 64, 2>(p, mode, grid, st); break;
-        default: launch_cfg<128, 128, 2, 2, 32, 3>(p, mode, grid, st); break;
+        case 1: launch_cfg<1>(p, k.arg[1], grid, st); break;
+        case 2: launch_cfg<2>(p, k.arg[1], grid, st); break;
+        case 3: launch_cfg<3>(p, k.arg[1], grid, st); break;
+        case 4: launch_cfg<4>(p, k.arg[1], grid, st); break;
+        case 5: launch_cfg<5>(p, k.arg[1], grid, st); break;
+        case 6: launch_cfg<6>(p, k.arg[1], grid, st); break;
+        case 7: launch_cfg<7>(p, k.arg[1], grid, st); break;
+        default: launch_cfg<0>(p, k.arg[1], grid, st); break;
     }
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }

@@ -22,7 +22,6 @@
 //             parity (columns 2j, 2j+1)
 // weights stream (compiler.py head_up2_weights): [chunk][parity a*2+b][tap r*2+s][64][32] fp16, then [64][32] for u
 // (k = 3*dy + dx < 9, rest zero).
-#include <stdlib.h>
 #include <type_traits>
 #include "conv_common.h"
 
@@ -530,7 +529,8 @@ __global__ __launch_bounds__(512, 2) void conv_head_up2r_kernel(const ConvParams
 #endif
 }
 
-int launch_conv_head_up2(const ConvParams& pin, int n_img, hipStream_t st) {
+// k.arg[0]: the resident-weight form (conv_select.hip reads VSE_HEAD_RESIDENT)
+int launch_conv_head(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
     ConvParams p = pin;
     // u = in0: [n, 2Hl, 2Wl, 8-channel padded, 1 real]; x = in2: [n, Hl, Wl, 64], upsampled by 2
     if (!(p.flags & F_DOT1) || !(p.flags & F_SRC2) || p.in2_shift != 1 || p.inshift != 0) return VSE_E_INVAL;
@@ -540,10 +540,10 @@ int launch_conv_head_up2(const ConvParams& pin, int n_img, hipStream_t st) {
     if ((reinterpret_cast<uintptr_t>(p.dot_out) & 7) || ((2 * p.in2_ws * p.dot_ld) & 1)) return VSE_E_INVAL;
     p.tiles_h = (p.in2_hs + HT_ROWS - 1) / HT_ROWS;
     p.tiles_w = (p.in2_ws + HT_COLS - 1) / HT_COLS;
+    const long n_img = conv_images(p);
     const unsigned long long blocks = (unsigned long long)n_img * p.tiles_h * p.tiles_w;
     if (blocks == 0 || blocks > 0x7fffffffull) return VSE_E_INVAL;
-    static const int resident = [] { const char* e = getenv("VSE_HEAD_RESIDENT"); return e && e[0] ? atoi(e) : 1; }();
-    if (resident) {
+    if (k.arg[0]) {
         // resident-weight form: 16 x 32 tiles, persistent blocks, grid a multiple of 16 (8 XCDs x 2 row parities)
         p.tiles_h = (p.in2_hs + RT_ROWS - 1) / RT_ROWS;
         const unsigned long long tiles = (unsigned long long)n_img * p.tiles_h * p.tiles_w;

@@ -16,7 +16,6 @@
 //     -> activation2 -> fp16 (or fp32) store; 2x2/stride-2 transposed conv = same GEMM with a
 //     pixel-shuffle store.
 
-#include <stdlib.h>
 #include "conv_common.h"
 
 #define BK 32          // K elements per pipeline stage
@@ -222,123 +221,14 @@ __global__ __launch_bounds__(256, (BM + (BN < 64 ? 64 : BN)) <= 256 ? 3 : 2) voi
     }
 }
 
-int conv_tile_bn(int Np) {
-    // tile selection: minimise padded-N waste, prefer the widest tile on ties
-    auto padded = [&](int bn) { return ((Np + bn - 1) / bn) * bn; };
-    if (Np <= 32) return 32;
-    if (padded(64) < padded(128)) return 64;
-    return 128;
-}
-
-int launch_conv(const ConvArgs& a, hipStream_t st) {
-    ConvParams p;
-    p.trace = nullptr;
-    p.in = reinterpret_cast<const half_t*>(a.in.ptr);
-    p.w = a.w;
-    p.bias = a.bias;
-    p.res = reinterpret_cast<const half_t*>(a.res.ptr);
-    p.out = a.out.ptr;
-    p.Hs = a.in.h;
-    p.Ws = a.in.w;
-    p.H = a.in.h << a.inshift;
-    p.W = a.in.w << a.inshift;
-    p.in_ld = a.in.ld;
-    p.cinp = a.cinp;
-    p.inshift = a.inshift;
-    p.kh = a.kh; p.kw = a.kw; p.sh = a.sh; p.sw = a.sw; p.ph = a.ph; p.pw = a.pw;
-    p.OH = (p.H + 2 * a.ph - a.kh) / a.sh + 1;
-    p.OW = (p.W + 2 * a.pw - a.kw) / a.sw + 1;
-    p.M = (long)a.in.n * p.OH * p.OW;
-    p.Np = a.Np;
-    p.nk = a.Kp / BK;
-    p.nkh = p.nk;
-    if (a.flags & F_HILO) p.nk *= 2;          // second pass over the same activations with the lo weight tiles
-    p.zero = a.zero;
-    p.out_ld = a.out.ld;
-    p.out_f32 = (a.flags & F_OUT_F32) ? 1 : 0;
-    p.res_ld = a.res.ld;
-    p.resshift = a.resshift;
-    p.res_hs = a.res.h;
-    p.res_ws = a.res.w;
-    p.act = a.act; p.act2 = a.act2;
-    p.act_a = a.act_a; p.act_b = a.act_b; p.post_a = a.post_a; p.post_b = a.post_b;
-    p.flags = a.flags;
-    p.coutp = (a.flags & F_PIXSHUF) ? a.Np / 4 : a.Np;
-    if (a.flags & F_SRC2) {
-        if (!a.in2.ptr || a.in2.esize != 2 || (a.in2.ld & 7) || a.in.c + a.in2.c != a.cinp) return VSE_E_INVAL;
-        if ((a.in2.h << a.in2shift) != p.H || (a.in2.w << a.in2shift) != p.W) return VSE_E_INVAL;
-    } else if (a.in.c != a.cinp) {
-        return VSE_E_INVAL;
-    }
-    // (F_UP2HEAD reads ONE channel of in0 at pixel stride ld: the dense map of an F_TAIL2 producer has ld = 1)
-    if (a.in.esize != 2 || ((a.in.ld & 7) && !((a.flags & F_UP2HEAD) && a.in.ld == 1)) || (a.cinp & 7)) return VSE_E_INVAL;
-    if ((a.flags & F_RES) && (a.res.esize != 2 || (a.res.ld & 3))) return VSE_E_INVAL;
-    if ((!(a.flags & (F_DOT1 | F_ONECH)) && (a.out.ld & 3)) || (a.Np & 7)) return VSE_E_INVAL;
-    if ((a.flags & F_ONECH) && (!(a.flags & F_PIXSHUF) || !(a.flags & F_OUT_F32) || a.Np != 32 || a.out.ld != 1 || a.out.esize != 4 || (a.flags & F_RES)))
-        return VSE_E_INVAL;
-    // sanity on the output view: [n, OH(*2), OW(*2)]
-    const int mul = (a.flags & F_PIXSHUF) ? 2 : 1;
-    if (a.out.h != p.OH * mul || a.out.w != p.OW * mul || a.out.n != a.in.n) return VSE_E_INVAL;
-
-    p.vec16 = ((reinterpret_cast<uintptr_t>(a.out.ptr) & 15) == 0 && ((long)a.out.ld * a.out.esize) % 16 == 0 &&
-               (!(a.flags & F_RES) || ((reinterpret_cast<uintptr_t>(a.res.ptr) & 15) == 0 && (a.res.ld & 7) == 0))) ? 1 : 0;
-    p.dotw = a.dotw; p.dotb = a.dotb; p.dotact = a.dotact;
-    p.dot_out = a.dot_out.ptr; p.dot_f32 = a.dot_out.esize == 4; p.dot_ld = a.dot_out.ld;
-    p.in2 = reinterpret_cast<const half_t*>(a.in2.ptr); p.in2_ld = a.in2.ld; p.in2_shift = a.in2shift;
-    p.in2_hs = a.in2.h; p.in2_ws = a.in2.w; p.nv0 = a.in.c >> 3;
-    p.wimg_stride = 0; p.hw_img = 0; p.tiles_img = 0;
-    p.wl_out = a.wl_out;
-    p.lo_off = a.lo_off;
-    p.res_lo_off = (a.flags & F_RES) ? a.res_lo_off : 0;
-    if (p.res_lo_off && (!p.vec16 || a.resshift || (p.res_lo_off & 7))) return VSE_E_INVAL;
-    p.in_lo_off = (a.flags & F_DWPRE) ? a.in_lo_off : 0;
-    if (a.lo_off && (!p.vec16 || (a.flags & (F_OUT_F32 | F_ONECH | F_DOT1 | F_UP2HEAD)) || (a.lo_off & 7) || a.out.ld < a.lo_off + a.Np / ((a.flags & F_PIXSHUF) ? 4 : 1)))
-        return VSE_E_INVAL;
-    p.ogate = nullptr; p.ogate_ld = 0;
-    if (a.flags & F_OGATE) {
-        // (in2 carries the gate: not combined with the other users of that slot)
-        if ((a.flags & (F_SRC2 | F_IMGW | F_PIXSHUF | F_DOT1 | F_UP2HEAD)) || !a.in2.ptr || a.in2.esize != 2 || a.in2.n != a.in.n || a.in2.h != 1 || a.in2.w != 1
-            || a.in2.c < a.Np || (a.in2.ld & 7) || (reinterpret_cast<uintptr_t>(a.in2.ptr) & 15)) return VSE_E_INVAL;
-        p.ogate = reinterpret_cast<const half_t*>(a.in2.ptr);
-        p.ogate_ld = a.in2.ld;
-    }
-    p.u8src = a.u8src; p.u8_h = a.u8_h; p.u8_w = a.u8_w; p.u8_pitch = a.u8_pitch; p.u8_fstride = a.u8_fstride;
-    if ((a.flags & F_U8SRC) && (!(a.flags & F_STEM) || !a.u8src || a.u8_h <= 0 || a.u8_w <= 0)) return VSE_E_INVAL;
-    if (a.wl_out && (a.flags & (F_DOT1 | F_SRC2 | F_UP2HEAD | F_PIXSHUF))) return VSE_E_UNSUPPORTED;   // no per-sample width in these forms
-    if (a.flags & F_IMGW) {
-        // per-image weights (an SE gate folded into a 1x1 consumer): conv_gemm_kernel only
-        if (a.kh != 1 || a.kw != 1 || (a.flags & (F_SRC2 | F_DOT1 | F_PATCH | F_COL | F_PW | F_HILO | F_PIXSHUF))) return VSE_E_UNSUPPORTED;
-        p.wimg_stride = (long)a.Kp * a.Np;
-        p.hw_img = p.OH * p.OW;
-        return launch_conv_gemm(p, a.Kp, st);
-    }
-    if (a.flags & F_DWPRE) {
-        if (!(a.flags & F_PW) || a.inshift || !a.dotw || (p.in_lo_off && ((p.in_lo_off & 7) || a.in.ld < p.in_lo_off + a.cinp))) return VSE_E_INVAL;
-        return launch_conv_dwpw(p, st);
-    }
-    if ((a.flags & (F_DOT1 | F_SRC2)) && !(a.flags & (F_PATCH | F_COL))) return VSE_E_UNSUPPORTED;
-    if (!a.zero) return VSE_E_INVAL;
-    if (a.flags & F_UP2HEAD) return launch_conv_head_up2(p, a.in.n, st);
-    if (a.flags & F_STEM) return launch_conv_stem(p, a.in.n, st);
-    if (a.flags & F_PW) return launch_conv_pw(p, st);
-    if (a.flags & F_COL) return (p.kh == 3 && p.kw == 3) ? launch_conv_c3(p, a.in.n, st) : launch_conv_col(p, a.in.n, st);
-    if (a.flags & F_PATCH) return launch_conv_patch(p, a.in.n, st);
-    if (a.Kp % 64) return VSE_E_INVAL;
-    if (conv_smallk_ok(p)) {                             // a small 1x1 problem: one wave per 32 x 32 tile, all loads in flight (conv_smallm.hip)
-        p.nkh = a.Kp / ((a.flags & F_WK32) ? 32 : 64);
-        return launch_conv_smallm(p, st);
-    }
-    const int rc = launch_conv_gemm(p, a.Kp, st);
-    if (rc != VSE_E_UNSUPPORTED) return rc;
-    if (a.flags & F_WK32) return VSE_E_UNSUPPORTED;     // 32-deep weight tiles are read by conv_gemm_kernel only
-    const int bn = conv_tile_bn(a.Np);
-    dim3 block(256);
-    const int bm = bn == 128 ? 128 : 256;
-    p.ntn = (unsigned)((a.Np + bn - 1) / bn);
+int launch_conv_mfma(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+    ConvParams p = pin;
+    const int bn = k.arg[0], bm = bn == 128 ? 128 : 256;
+    p.ntn = (unsigned)((p.Np + bn - 1) / bn);
     const unsigned long long tiles = (unsigned long long)((p.M + bm - 1) / bm) * p.ntn;
     if (tiles == 0 || tiles > 0x7fffffffull) return VSE_E_INVAL;
-    dim3 grid((unsigned)tiles);
-    if (a.inshift) {
+    const dim3 grid((unsigned)tiles), block(256);
+    if (k.arg[1]) {
         if (bn == 128) hipLaunchKernelGGL((conv_mfma_kernel<128, 128, 2, 2, true>), grid, block, 0, st, p);
         else if (bn == 64) hipLaunchKernelGGL((conv_mfma_kernel<256, 64, 4, 1, true>), grid, block, 0, st, p);
         else hipLaunchKernelGGL((conv_mfma_kernel<256, 32, 4, 1, true>), grid, block, 0, st, p);

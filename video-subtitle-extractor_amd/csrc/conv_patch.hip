@@ -29,7 +29,6 @@
 #include <vector>
 #endif
 
-#define PTW 32
 #define PRING 4
 
 // -DVSE_TRACE: wave 0 of every block stamps s_memtime at phase boundaries into p.trace[block][8] (timing experiments
@@ -393,50 +392,18 @@ __global__ __launch_bounds__(512, MODE == 2 ? 4 : 2) void conv_patch_kernel(cons
 #endif
 }
 
-// Which variant serves a layer (mirrored by compiler.py, which packs the weight stream for it):
-//   mode 2 (LIGHT, 8-row tiles, 64 or 128 couts, two blocks per CU) when the halo patch of an 8 x 32 tile fits 352 pixels
-//   (3x3, 1xk) and no 1-channel projection is fused (that needs all couts of a pixel in one wave);
-//   else 64 couts per tile, 16-row tiles when they fit the 960-pixel patch (mode 1 above 640 pixels), else 8-row tiles.
-void conv_patch_plan(int kh, int kw, int OH, int Np, int flags, int* th, int* bn, int* mode) {
-    const bool fits = (8 + kh - 1) * (PTW + kw - 1) <= 352 && !(flags & (F_DOT1 | F_SRC2));
-    if (fits) {
-        *th = 8; *bn = Np > 64 ? 128 : 64; *mode = 2;
-        return;
-    }
-    *bn = 64;
-    *th = conv_patch_th(kh, kw, OH, 64);
-    *mode = (*th == 16 && (16 + kh - 1) * (PTW + kw - 1) > 640) ? 1 : 0;
-    if (*mode == 1 && Np <= 32 && !(flags & F_DOT1)) *bn = 32;      // half the MFMAs and weight DMAs of a 64-cout tile
-}
-int conv_patch_bn(int Np) {
-    (void)Np;
-    return 64;
-}
-
-// Tile height: 16 rows when the halo patch fits the LDS patch buffer (960 pixels for BN = 64, else 640) and the map
-// tiles at least as well as with 8 rows.
-int conv_patch_th(int kh, int kw, int OH, int bn) {
-    if (bn != 64) return 8;      // measured twice: a 16-row x 128-cout tile (64 px x 128 couts per wave, one block per CU, 3 or 4
-                                 // taps per step, pipelined fast step, 254 VGPRs) is 7-20 % slower than LIGHT's two 8-row blocks:
-                                 // a 3x3 K loop is too short to amortise an un-overlapped prologue + 128-cout epilogue
-    const int cap = 960;
-    if ((16 + kh - 1) * (PTW + kw - 1) > cap) return 8;
-    const int pad16 = (OH + 15) / 16 * 16, pad8 = (OH + 7) / 8 * 8;
-    return pad16 * 100 <= pad8 * 112 ? 16 : 8;      // accept <= 12 % extra row padding for the denser wave tile
-}
-
-int launch_conv_patch(const ConvParams& pin, int n_img, hipStream_t st) {
+// k.arg = TH, BN, MODE (conv_select.hip: conv_patch_plan)
+int launch_conv_patch(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
     ConvParams p = pin;
     if (p.sh != 1 || p.sw != 1 || p.kh * p.kw < 5 || (p.cinp & 7) || (p.flags & F_PIXSHUF)) return VSE_E_INVAL;
     if ((8 + p.kh - 1) * (PTW + p.kw - 1) > 640) return VSE_E_UNSUPPORTED;
-    int th, bn, mode;
-    conv_patch_plan(p.kh, p.kw, p.OH, p.Np, p.flags, &th, &bn, &mode);
+    const int th = k.arg[0], bn = k.arg[1], mode = k.arg[2];
     const bool big = mode == 1;
     p.ntn = (unsigned)((p.Np + bn - 1) / bn);
     if ((p.flags & F_DOT1) && (th != 16 || p.ntn != 1 || (p.flags & F_RES) || !p.dotw || !p.dot_out)) return VSE_E_UNSUPPORTED;
     p.tiles_h = (p.OH + th - 1) / th;
     p.tiles_w = (p.OW + PTW - 1) / PTW;
-    const unsigned long long blocks = (unsigned long long)n_img * p.tiles_h * p.tiles_w * p.ntn;
+    const unsigned long long blocks = (unsigned long long)conv_images(p) * p.tiles_h * p.tiles_w * p.ntn;
     if (blocks == 0 || blocks > 0x7fffffffull) return VSE_E_INVAL;
     const dim3 grid((unsigned)blocks), block(512);
 #ifdef VSE_TRACE

@@ -15,9 +15,6 @@
 // SAME activation fragments — hi slices, then lo slices, the order of the implicit-GEMM kernels' two-pass K walk.
 #include "conv_common.h"
 
-#define PW_MAXN 256
-#define PW_MAXN_HILO 128
-
 // F_TAIL2 (round 5; the server detector's head tail: transposed conv 2x2 s2 c0 -> c1 + BN + relu, whose output f feeds BOTH the local
 // refinement conv and a second transposed conv 2x2 s2 c1 -> 1 + sigmoid = the base map u): the second transposed conv rides in the
 // epilogue of the first.  The accumulator tile of stage A — lane = pixel, register 8 g + e = channel 32 j + 16 g + 8 h + e — rounded
@@ -176,31 +173,26 @@ __global__ __launch_bounds__(256, 3) void conv_pw_tail_kernel(const ConvParams p
     conv_pw_body<KS, false, true>(p, swt, sbias, swb);
 }
 
-bool conv_pw_ok(int kh, int kw, int sh, int sw, int ph, int pw, int cinp, int Np, int inshift, int flags) {
-    return kh == 1 && kw == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0 && inshift == 0 && (cinp & 7) == 0
-           && cinp <= ((flags & F_HILO) ? 96 : 64)      // (hi + lo nets: a 48-channel PAIR tensor is 96 input channels — round 5)
-           && Np <= ((flags & F_HILO) ? PW_MAXN_HILO : PW_MAXN) && !(flags & (F_SRC2 | F_DOT1 | F_PATCH | F_COL));
-}
-
-int launch_conv_pw(const ConvParams& p, hipStream_t st) {
-    if (!conv_pw_ok(p.kh, p.kw, p.sh, p.sw, p.ph, p.pw, p.cinp, p.Np, p.inshift, p.flags)) return VSE_E_UNSUPPORTED;
+// k.arg = KS, HILO, TAIL; which layers it serves: conv_pw_ok (conv_select.hip)
+int launch_conv_pw(const ConvParams& p, const ConvKernel& k, hipStream_t st) {
     const unsigned long long blocks = (unsigned long long)((p.M + 255) / 256);
     if (blocks == 0 || p.M >= 0x7fffffffl) return VSE_E_INVAL;          // (32-bit pixel arithmetic: conv_pix_coords)
     const dim3 grid((unsigned)blocks), block(256);
-    if (p.flags & F_TAIL2) {
+    if (k.arg[2]) {
         // stage A without residual / gate / affine / second activation, whole 32-cout tiles, a dense fp16 map out
         if ((p.flags & (F_HILO | F_RES | F_OGATE | F_DOT1 | F_ONECH)) || !(p.flags & F_PIXSHUF) || p.out_f32 || !p.vec16 || (p.Np & 31) || !p.dotw || !p.dot_out
             || p.dot_f32 || p.dot_ld != 1 || p.act2 || p.post_a != 1.f || p.post_b != 0.f || p.lo_off || p.wl_out
             || (reinterpret_cast<uintptr_t>(p.dot_out) & 7) || (reinterpret_cast<uintptr_t>(p.dotw) & 15)) return VSE_E_INVAL;
-        switch ((p.cinp + 15) / 16) {
+        if (k.rc != VSE_OK) return k.rc;
+        switch (k.arg[0]) {
             case 2: hipLaunchKernelGGL((conv_pw_tail_kernel<2>), grid, block, 0, st, p); break;
             case 4: hipLaunchKernelGGL((conv_pw_tail_kernel<4>), grid, block, 0, st, p); break;
             default: return VSE_E_UNSUPPORTED;
         }
         return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
     }
-    if (p.flags & F_HILO) {
-        switch ((p.cinp + 15) / 16) {
+    if (k.arg[1]) {
+        switch (k.arg[0]) {
             case 1: hipLaunchKernelGGL((conv_pw_kernel<1, true>), grid, block, 0, st, p); break;
             case 2: hipLaunchKernelGGL((conv_pw_kernel<2, true>), grid, block, 0, st, p); break;
             case 3: hipLaunchKernelGGL((conv_pw_kernel<3, true>), grid, block, 0, st, p); break;
@@ -211,7 +203,7 @@ int launch_conv_pw(const ConvParams& p, hipStream_t st) {
         }
         return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
     }
-    switch ((p.cinp + 15) / 16) {
+    switch (k.arg[0]) {
         case 1: hipLaunchKernelGGL((conv_pw_kernel<1>), grid, block, 0, st, p); break;
         case 2: hipLaunchKernelGGL((conv_pw_kernel<2>), grid, block, 0, st, p); break;
         case 3: hipLaunchKernelGGL((conv_pw_kernel<3>), grid, block, 0, st, p); break;

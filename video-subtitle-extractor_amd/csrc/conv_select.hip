@@ -1,0 +1,347 @@
+// Which kernel serves an OP_CONV record, decided in one place (host code only): the record -> ConvParams step, the selector with
+// the shape rules of every conv kernel family, the name of its answer, and launch_conv(), which checks the record, asks the
+// selector and hands the answer to the family's launcher.  The kernels and their launchers stay in their own files.
+#include <stdlib.h>
+#include <cstdio>
+#include "conv_common.h"
+
+// ---- shape rules of the kernel families -------------------------------------------------------------------------------------
+
+// conv_gemm_kernel: 0 = not eligible; 1 = masked variant; 2 = unmasked 1x1 variant
+static int conv_gemm_mode(int kh, int kw, int sh, int sw, int ph, int pw, int cinp, int Kp, int inshift, int flags) {
+    (void)sh; (void)sw;
+    if (inshift || (flags & (F_PATCH | F_DOT1 | F_SRC2))) return 0;
+    if (cinp % 32) return 0;
+    if (kh * kw > 31) return 0;
+    if (kh < 2 * ph + 1 || kw < 2 * pw) return 0;
+    if (kh == 1 && kw == 1 && ph == 0 && pw == 0 && Kp == cinp) return 2;
+    return 1;
+}
+// 32-bit offsets: the rows of one block span at most BM output pixels (+ one image seam), the tap walk kh rows
+static bool conv_gemm_span_ok(const ConvParams& p, int Kp) {
+    const double span = ((double)512 * p.sw + (512.0 / p.OW + 3) * p.sh * p.Ws + (double)p.kh * p.Ws + p.kw) * p.in_ld * 2;
+    return !(span > 1.9e9 || (double)Kp * p.Np * 2 > 1.9e9);
+}
+
+// Which kCfg configuration serves a layer.  The kernel is bound by the L2 -> LDS fill (ablation: MFMAs and fragment reads
+// are free, the DMA stream and the store tail are not), so the choice minimises fetched bytes: one cout tile when the
+// couts fit 192 / 256 (the activation tile is then fetched once instead of 2-3 times), 256-pixel tiles (weights re-read
+// half as often), as long as the grid still fills the 256 CUs.  Zero-padded couts cost MFMA issue slots only.
+static int conv_gemm_config(int Np, int cinp, long M) {
+    auto ntn = [&](int bn) { return (long)((Np + bn - 1) / bn); };
+    // the 16-wave tiles run 64-deep K tiles in a 2-stage ring where the channels allow it (whole 128-byte lines per
+    // activation row and half the barriers; A/B on one box: -2..-4 %); the 8-wave 256 x 128 tile loses its second block per CU
+    auto deep = [&](int c) { return cinp % 64 == 0 ? c + 2 : c; };          // 4 -> 6, 5 -> 7
+    if (Np <= 32) return 2;
+    if (Np <= 64) return 1;
+    const long mt = (M + 255) / 256;
+    if (Np <= 128) return mt >= 256 ? 3 : 0;
+    if (Np <= 192) return mt >= 192 ? deep(5) : (mt >= 128 ? 3 : 0);
+    const double w256 = (double)ntn(256) * 256 / Np, w192 = (double)ntn(192) * 192 / Np;
+    const bool pick256 = ntn(256) < ntn(192) || (ntn(256) == ntn(192) && w256 <= w192);
+    if (pick256 && mt * ntn(256) >= 192 && w256 <= 1.34) return deep(4);
+    if (mt * ntn(192) >= 192 && w192 <= 1.34) return deep(5);
+    if (mt * ntn(256) >= 192 && w256 <= 1.34) return deep(4);
+    return mt * ntn(128) >= 512 ? 3 : 0;
+}
+
+// conv_smallm_kernel: conv_gemm_kernel's unmasked 1x1 mode (mode 2) at stride 1 with at most 256 pixels, one weight stream.
+static bool conv_smallm_ok(const ConvParams& p, int mode, bool same_hw) {
+    return mode == 2 && p.M <= 256 && p.sh == 1 && p.sw == 1 && same_hw && !(p.flags & (F_IMGW | F_PIXSHUF | F_DOT1 | F_SRC2))
+           && (p.cinp & 15) == 0;
+}
+// ... and (round 5) SMALL 1x1 PROBLEMS whatever their route would be: <= 256 input channels (any multiple of 8: the SVTR necks' 120 / 240
+// are not multiples of 32 and ran on the 128 x 128 tile of conv_mfma_kernel), <= 4096 (32-cout x 32-pixel) wave tiles — a recogniser
+// sequence's [crops, 1, T, 120] layers.  Such a launch is a handful of K steps behind a prologue and in front of an epilogue on 13-50 of
+// 256 CUs (13-23 us launch to launch); there every wave is its own block with ALL its loads in flight at once.  Same K order, same bits.
+static bool conv_smallk_ok(const ConvParams& p, bool same_hw) {
+    return p.kh == 1 && p.kw == 1 && p.sh == 1 && p.sw == 1 && p.ph == 0 && p.pw == 0 && !p.inshift && same_hw && p.cinp > 0 && p.cinp <= 256
+           && (p.cinp & 7) == 0
+           && !(p.flags & (F_IMGW | F_PIXSHUF | F_DOT1 | F_SRC2 | F_PATCH | F_COL | F_PW | F_STEM | F_UP2HEAD | F_DWPRE | F_ONECH | F_TAIL2 | F_HLSUM))
+           && p.M > 0 && ((p.M + 31) / 32) * ((p.Np + 31) / 32) <= 4096;
+}
+
+// conv_mfma_kernel tile: minimise padded-N waste, prefer the widest tile on ties
+static int conv_tile_bn(int Np) {
+    auto padded = [&](int bn) { return ((Np + bn - 1) / bn) * bn; };
+    if (Np <= 32) return 32;
+    if (padded(64) < padded(128)) return 64;
+    return 128;
+}
+
+// conv_patch_kernel (mirrored by compiler.py, which packs the weight stream for it):
+//   mode 2 (LIGHT, 8-row tiles, 64 or 128 couts, two blocks per CU) when the halo patch of an 8 x 32 tile fits 352 pixels
+//   (3x3, 1xk) and no 1-channel projection is fused (that needs all couts of a pixel in one wave);
+//   else 64 couts per tile, 16-row tiles when they fit the 960-pixel patch (mode 1 above 640 pixels), else 8-row tiles.
+// Tile height: 16 rows when the halo patch fits the LDS patch buffer (960 pixels) and the map tiles at least as well as with
+// 8 rows.  (Measured twice: a 16-row x 128-cout tile — 64 px x 128 couts per wave, one block per CU, 3 or 4 taps per step,
+// pipelined fast step, 254 VGPRs — is 7-20 % slower than LIGHT's two 8-row blocks: a 3x3 K loop is too short to amortise an
+// un-overlapped prologue + 128-cout epilogue.)
+static int conv_patch_th(int kh, int kw, int OH) {
+    if ((16 + kh - 1) * (PTW + kw - 1) > 960) return 8;
+    const int pad16 = (OH + 15) / 16 * 16, pad8 = (OH + 7) / 8 * 8;
+    return pad16 * 100 <= pad8 * 112 ? 16 : 8;      // accept <= 12 % extra row padding for the denser wave tile
+}
+static void conv_patch_plan(int kh, int kw, int OH, int Np, int flags, int* th, int* bn, int* mode) {
+    const bool fits = (8 + kh - 1) * (PTW + kw - 1) <= 352 && !(flags & (F_DOT1 | F_SRC2));
+    if (fits) {
+        *th = 8; *bn = Np > 64 ? 128 : 64; *mode = 2;
+        return;
+    }
+    *bn = 64;
+    *th = conv_patch_th(kh, kw, OH);
+    *mode = (*th == 16 && (16 + kh - 1) * (PTW + kw - 1) > 640) ? 1 : 0;
+    if (*mode == 1 && Np <= 32 && !(flags & F_DOT1)) *bn = 32;      // half the MFMAs and weight DMAs of a 64-cout tile
+}
+
+// conv_col_kernel (mirrored by compiler.py, which packs the weight stream for it, F_COL)
+static int conv_col_bn(int Np) { return Np > 32 ? 64 : 32; }
+static bool conv_col_ok(int kh, int kw, int sh, int sw, int cinp, int Np, int flags) {
+    return sh == 1 && sw == 1 && (kh == 9 || kh == 7 || kh == 5) && kw >= 3 && CTW + kw - 1 <= CPW && (cinp & 15) == 0 && Np <= 64
+           && !(flags & (F_SRC2 | F_PIXSHUF | F_DOT1));
+}
+
+// conv_c3_kernel tile shape per map: estimated cost (in full tiles) of covering OH x OW with (2 RW) x (32 CW) tiles when waves outside
+// the map idle (a partial tile costs ~0.35 + 0.65 * live waves / 8 of a full one).  Mirrored by compiler.py (c3_tile_eff).
+static double c3_axis_cost(int n, int unit, int waves) {      // n pixels along an axis covered by tiles of `waves` x `unit`
+    const int tile = unit * waves, full = n / tile, rem = n - full * tile;
+    return full + (rem ? 0.35 + 0.65 * ((rem + unit - 1) / unit) / (double)waves : 0.0);
+}
+static double conv_c3_plan(int OH, int OW, int* rw_out) {
+    double best = 0;
+    int brw = 8;
+    for (int rw = 8; rw >= 2; rw >>= 1) {
+        const int cw = 8 / rw;
+        // partial tiles in both directions: live fraction multiplies; approximate by the product of the axis costs
+        const double cost = c3_axis_cost(OH, 2, rw) * c3_axis_cost(OW, 32, cw) * 512.0;
+        const double eff = (double)OH * OW / cost;
+        if (eff > best + 1e-9) { best = eff; brw = rw; }
+    }
+    if (rw_out) *rw_out = brw;
+    return best;
+}
+static bool conv_c3_ok(int kh, int kw, int sh, int sw, int ph, int pw, int cinp, int flags) {
+    return kh == 3 && kw == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && (cinp & 15) == 0
+           && !(flags & (F_SRC2 | F_PIXSHUF | F_DOT1));
+}
+
+static bool conv_pw_ok(int kh, int kw, int sh, int sw, int ph, int pw, int cinp, int Np, int inshift, int flags) {
+    return kh == 1 && kw == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0 && inshift == 0 && (cinp & 7) == 0
+           && cinp <= ((flags & F_HILO) ? 96 : 64)      // (hi + lo nets: a 48-channel PAIR tensor is 96 input channels — round 5)
+           && Np <= ((flags & F_HILO) ? PW_MAXN_HILO : PW_MAXN) && !(flags & (F_SRC2 | F_DOT1 | F_PATCH | F_COL));
+}
+
+// conv_dwpw: 5 x 5 filters stay on two launches (25 taps per lane: 0.21 against 0.09 + 0.04 ms, and the unrolled form spills)
+static bool conv_dwpw_ok(int k, int s, int cinp, int Np, int flags) {
+    return k == 3 && (s == 1 || s == 2) && (cinp & 7) == 0 && cinp <= 96 && Np <= 192 && (flags & F_HILO)
+           && !(flags & (F_SRC2 | F_DOT1 | F_PATCH | F_COL | F_PIXSHUF | F_IMGW | F_STEM));
+}
+// Stride of the row-streaming form (conv_dwpw_rows_kernel), 0 = the tile form.  The row-streaming form takes 3 x 3 'same' filters
+// (pad 1) over <= 3 slices of 16 channels: there the row-invariant depthwise weights stay in registers (see LAUNDER in the kernel).
+// Wider units measured SLOWER than the tile form with the weight reads left in the row loop (96 -> 192 @34 x 60, stride 2: 0.208 vs
+// 0.168 ms) and spill with them hoisted: they keep the tile form.  Only PAIR inputs take it: on plain fp16 inputs (the layer-by-layer
+// programs) the tile form measures the same or better (16 -> 32 @272 x 480: 0.373 vs 0.365 ms, 48 -> 48 @136 x 240: 0.215 vs 0.286) —
+// half the gathers and half the multiply-adds per pixel leave little for the strip walk to save.
+static int conv_dwpw_rows_stride(int k, int pad, int s, int cinp, int lo_in) {
+    const int ks = (cinp + 15) / 16;
+    return (lo_in != 0 && k == 3 && pad == 1 && ((s == 1 && ks <= DWPW_ROWS_MAX_KS_S1) || (s == 2 && ks <= DWPW_ROWS_MAX_KS))) ? s : 0;
+}
+
+// ---- record -> parameters -----------------------------------------------------------------------------------------------------
+
+ConvParams conv_params(const vse_op& o, const TView& in, const TView& res, const TView& in2, const TView& out, const TView& dot_out,
+                       const char* wts, const half_t* zero, const int* wl_out, const uint8_t* u8src, const SrcGeom& src) {
+    auto blob = [&](long off) { return wts ? wts + off : nullptr; };
+    const int flags = o.flags;
+    ConvParams p{};
+    p.in = reinterpret_cast<const half_t*>(in.ptr);
+    p.w = reinterpret_cast<const half_t*>((flags & F_IMGW) ? in2.ptr : blob(o.w_off));     // F_IMGW: per-image weights in the workspace
+    p.bias = reinterpret_cast<const float*>(blob(o.b_off));
+    p.res = reinterpret_cast<const half_t*>(res.ptr);
+    p.out = out.ptr;
+    p.zero = zero;
+    p.inshift = o.p[P_INSHIFT];
+    p.Hs = in.h;
+    p.Ws = in.w;
+    p.H = in.h << p.inshift;
+    p.W = in.w << p.inshift;
+    p.in_ld = in.ld;
+    p.cinp = o.p[P_CINP];
+    p.kh = o.p[P_KH]; p.kw = o.p[P_KW]; p.sh = o.p[P_SH]; p.sw = o.p[P_SW]; p.ph = o.p[P_PH]; p.pw = o.p[P_PW];
+    p.OH = (p.H + 2 * p.ph - p.kh) / p.sh + 1;
+    p.OW = (p.W + 2 * p.pw - p.kw) / p.sw + 1;
+    p.M = (long)in.n * p.OH * p.OW;
+    p.Np = o.p[P_COUT];
+    p.nk = o.p[P_KTOT] / 32;                  // conv_mfma_kernel's 32-deep K tiles (the other launchers derive theirs from nkh)
+    p.nkh = p.nk;
+    if (flags & F_HILO) p.nk *= 2;            // second pass over the same activations with the lo weight tiles
+    p.out_ld = out.ld;
+    p.out_f32 = (flags & F_OUT_F32) ? 1 : 0;
+    p.res_ld = res.ld;
+    p.resshift = o.p[P_RESSHIFT];
+    p.res_hs = res.h;
+    p.res_ws = res.w;
+    p.act = o.p[P_ACT]; p.act2 = o.p[P_ACT2];
+    p.act_a = o.f[FS_ACT_A]; p.act_b = o.f[FS_ACT_B]; p.post_a = o.f[FS_POST_A]; p.post_b = o.f[FS_POST_B];
+    p.flags = flags;
+    p.coutp = (flags & F_PIXSHUF) ? p.Np / 4 : p.Np;
+    p.vec16 = ((reinterpret_cast<uintptr_t>(out.ptr) & 15) == 0 && ((long)out.ld * out.esize) % 16 == 0 &&
+               (!(flags & F_RES) || ((reinterpret_cast<uintptr_t>(res.ptr) & 15) == 0 && (res.ld & 7) == 0))) ? 1 : 0;
+    p.dotw = reinterpret_cast<const float*>(blob(o.aux_off));
+    p.dotb = o.f[FS_PRE_B]; p.dotact = o.p[P_DOTACT];
+    p.dot_out = dot_out.ptr; p.dot_f32 = dot_out.esize == 4; p.dot_ld = dot_out.ld;
+    p.in2 = reinterpret_cast<const half_t*>(in2.ptr); p.in2_ld = in2.ld; p.in2_shift = o.p[P_IN2SHIFT];
+    p.in2_hs = in2.h; p.in2_ws = in2.w; p.nv0 = in.c >> 3;
+    if (flags & F_IMGW) {
+        p.wimg_stride = (long)o.p[P_KTOT] * p.Np;
+        p.hw_img = p.OH * p.OW;
+    }
+    p.wl_out = wl_out;
+    p.lo_off = o.p[P_LO_OUT];
+    p.res_lo_off = (flags & F_RES) ? o.p[P_LO_RES] : 0;
+    p.in_lo_off = (flags & F_DWPRE) ? o.p[P_LO_IN] : 0;
+    if (flags & F_OGATE) {                    // (in2 carries the gate)
+        p.ogate = reinterpret_cast<const half_t*>(in2.ptr);
+        p.ogate_ld = in2.ld;
+    }
+    if (flags & F_U8SRC) {
+        p.u8src = u8src;
+        p.u8_h = src.h; p.u8_w = src.w; p.u8_pitch = src.pitch; p.u8_fstride = src.fstride;
+    }
+    return p;
+}
+
+// ---- the selector -------------------------------------------------------------------------------------------------------------
+
+static bool head_resident() {
+    // the persistent resident-weight form unless VSE_HEAD_RESIDENT is a number that reads as 0
+    static const bool resident = [] { const char* e = getenv("VSE_HEAD_RESIDENT"); return e && e[0] ? atoi(e) != 0 : true; }();
+    return resident;
+}
+
+ConvKernel conv_select(const ConvParams& p, int Kp) {
+    auto refuse = [](int rc) { return ConvKernel{CK_NONE, rc, {0, 0, 0}}; };
+    auto pick = [](int family, int a0, int a1 = 0, int a2 = 0) { return ConvKernel{family, VSE_OK, {a0, a1, a2}}; };
+    const int f = p.flags;
+    const bool hilo = (f & F_HILO) != 0;
+    if (f & F_IMGW) {
+        // per-image weights (an SE gate folded into a 1x1 consumer): the unmasked conv_gemm_kernel only, M tiles aligned to images
+        if (p.kh != 1 || p.kw != 1 || (f & (F_SRC2 | F_DOT1 | F_PATCH | F_COL | F_PW | F_HILO | F_PIXSHUF))) return refuse(VSE_E_UNSUPPORTED);
+        const int mode = conv_gemm_mode(p.kh, p.kw, p.sh, p.sw, p.ph, p.pw, p.cinp, Kp, p.inshift, f);
+        if (mode != 2 || !conv_gemm_span_ok(p, Kp) || p.hw_img <= 0 || p.M % p.hw_img) return refuse(VSE_E_UNSUPPORTED);
+        return pick(CK_GEMM, conv_gemm_config(p.Np, p.cinp, p.M), 0);
+    }
+    if (f & F_DWPRE) {
+        if (!(f & F_PW) || p.inshift || (p.in_lo_off && ((p.in_lo_off & 7) || p.in_ld < p.in_lo_off + p.cinp))) return refuse(VSE_E_INVAL);
+        if (!conv_dwpw_ok(p.kh, p.sh, p.cinp, p.Np, f) || p.kh != p.kw || p.sh != p.sw || p.ph != p.pw) return refuse(VSE_E_UNSUPPORTED);
+        return pick(CK_DWPW, (p.cinp + 15) / 16, p.in_lo_off != 0, conv_dwpw_rows_stride(p.kh, p.ph, p.sh, p.cinp, p.in_lo_off));
+    }
+    if ((f & (F_DOT1 | F_SRC2)) && !(f & (F_PATCH | F_COL))) return refuse(VSE_E_UNSUPPORTED);
+    if (f & F_UP2HEAD) return pick(CK_HEAD, head_resident());
+    if (f & F_STEM) return pick(CK_STEM, p.sh == 2 ? 2 : 1, hilo, (f & F_U8SRC) != 0);
+    if (f & F_PW) {
+        if (!conv_pw_ok(p.kh, p.kw, p.sh, p.sw, p.ph, p.pw, p.cinp, p.Np, p.inshift, f)) return refuse(VSE_E_UNSUPPORTED);
+        const int ks = (p.cinp + 15) / 16;
+        ConvKernel k = pick(CK_PW, ks, hilo, (f & F_TAIL2) != 0);
+        if ((f & F_TAIL2) && ks != 2 && ks != 4) k.rc = VSE_E_UNSUPPORTED;      // (the tail is built for 32 and 64 input channels)
+        return k;
+    }
+    if (f & F_COL) {
+        if (p.kh == 3 && p.kw == 3) {
+            if (!conv_c3_ok(p.kh, p.kw, p.sh, p.sw, p.ph, p.pw, p.cinp, f)) return refuse(VSE_E_UNSUPPORTED);
+            int rw;
+            conv_c3_plan(p.OH, p.OW, &rw);
+            return pick(CK_C3, rw, p.Np <= 32 && !(f & F_HLSUM));     // F_HLSUM: the 64-row form (hi | lo)
+        }
+        if (!conv_col_ok(p.kh, p.kw, p.sh, p.sw, p.cinp, p.Np, f)) return refuse(VSE_E_UNSUPPORTED);
+        return pick(CK_COL, p.kh, conv_col_bn(p.Np));
+    }
+    if (f & F_PATCH) {
+        int th, bn, mode;
+        conv_patch_plan(p.kh, p.kw, p.OH, p.Np, f, &th, &bn, &mode);
+        return pick(CK_PATCH, th, bn, mode);
+    }
+    if (Kp % 64) return refuse(VSE_E_INVAL);
+    const int kt = (f & F_WK32) ? 32 : 64;
+    const bool same_hw = p.H == p.OH && p.W == p.OW && p.Hs == p.H && p.Ws == p.W;
+    if (conv_smallk_ok(p, same_hw)) return pick(CK_SMALLM, kt, hilo);        // a small 1x1 problem: one wave per 32 x 32 tile
+    const int mode = conv_gemm_mode(p.kh, p.kw, p.sh, p.sw, p.ph, p.pw, p.cinp, Kp, p.inshift, f);
+    if (mode && conv_smallm_ok(p, mode, same_hw)) return pick(CK_SMALLM, kt, hilo);   // a handful of pixels (SE gates)
+    if (mode && conv_gemm_span_ok(p, Kp)) return pick(CK_GEMM, conv_gemm_config(p.Np, p.cinp, p.M), mode == 1);
+    if (f & F_WK32) return refuse(VSE_E_UNSUPPORTED);     // 32-deep weight tiles are read by conv_gemm_kernel and conv_smallm only
+    return pick(CK_MFMA, conv_tile_bn(p.Np), p.inshift != 0);
+}
+
+// The instantiation `k` names, spelled as rocprofv3 reports the symbol (without "void " and the parameter list).
+int conv_kernel_name(const ConvKernel& k, char* buf, size_t n) {
+    const int* a = k.arg;
+    const char* tf[2] = {"false", "true"};
+    if (k.rc != VSE_OK) return snprintf(buf, n, "(refused: %d)", k.rc);
+    switch (k.family) {
+        case CK_GEMM: {
+            const GemmCfg& g = kCfg[a[0]];
+            return snprintf(buf, n, "conv_gemm_kernel<%d, %d, %d, %d, %d, %d, %d>", g.bm, g.bn, g.wm, g.wn, g.bk, g.st, a[1]);
+        }
+        case CK_SMALLM: return snprintf(buf, n, "conv_smallm%s_kernel<%d>", a[1] ? "_hl" : "", a[0]);
+        case CK_MFMA:
+            return snprintf(buf, n, "conv_mfma_kernel<%d, %d, %d, %d, %s>", a[0] == 128 ? 128 : 256, a[0], a[0] == 128 ? 2 : 4, a[0] == 128 ? 2 : 1,
+                            tf[a[1]]);
+        case CK_PATCH: return snprintf(buf, n, "conv_patch_kernel<%d, %d, %d>", a[0], a[1], a[2]);
+        case CK_COL: return snprintf(buf, n, "conv_col_kernel<%d, %d>", a[0], a[1]);
+        case CK_C3: return snprintf(buf, n, "conv_c3%s_kernel<%d, %d>", a[1] ? "n32" : "", a[0], 8 / a[0]);
+        case CK_PW:
+            return a[2] ? snprintf(buf, n, "conv_pw_tail_kernel<%d>", a[0]) : snprintf(buf, n, "conv_pw_kernel<%d, %s>", a[0], tf[a[1]]);
+        case CK_DWPW:
+            return a[2] ? snprintf(buf, n, "conv_dwpw_rows_kernel<%d, %s, %d>", a[0], tf[a[1]], a[2])
+                        : snprintf(buf, n, "conv_dwpw_kernel<%d, 3, %s>", a[0], tf[a[1]]);
+        case CK_HEAD: return snprintf(buf, n, a[0] ? "conv_head_up2r_kernel" : "conv_head_up2_kernel");
+        case CK_STEM: return snprintf(buf, n, "conv_stem_kernel<%d, %d, %s, %s>", a[0], a[0], tf[a[1]], tf[a[2]]);
+        default: return snprintf(buf, n, "?");
+    }
+}
+
+// ---- launch -----------------------------------------------------------------------------------------------------------------
+
+int launch_conv(const vse_op& o, const TView& in, const TView& res, const TView& in2, const TView& out, const TView& dot_out,
+                const char* wts, const half_t* zero, const int* wl_out, const uint8_t* u8src, const SrcGeom& src, hipStream_t st) {
+    const ConvParams p = conv_params(o, in, res, in2, out, dot_out, wts, zero, wl_out, u8src, src);
+    const int f = p.flags, Np = p.Np, cinp = p.cinp;
+    if (f & F_SRC2) {
+        if (!in2.ptr || in2.esize != 2 || (in2.ld & 7) || in.c + in2.c != cinp) return VSE_E_INVAL;
+        if ((in2.h << p.in2_shift) != p.H || (in2.w << p.in2_shift) != p.W) return VSE_E_INVAL;
+    } else if (in.c != cinp) {
+        return VSE_E_INVAL;
+    }
+    // (F_UP2HEAD reads ONE channel of in0 at pixel stride ld: the dense map of an F_TAIL2 producer has ld = 1)
+    if (in.esize != 2 || ((in.ld & 7) && !((f & F_UP2HEAD) && in.ld == 1)) || (cinp & 7)) return VSE_E_INVAL;
+    if ((f & F_RES) && (res.esize != 2 || (res.ld & 3))) return VSE_E_INVAL;
+    if ((!(f & (F_DOT1 | F_ONECH)) && (out.ld & 3)) || (Np & 7)) return VSE_E_INVAL;
+    if ((f & F_ONECH) && (!(f & F_PIXSHUF) || !(f & F_OUT_F32) || Np != 32 || out.ld != 1 || out.esize != 4 || (f & F_RES)))
+        return VSE_E_INVAL;
+    // sanity on the output view: [n, OH(*2), OW(*2)]
+    const int mul = (f & F_PIXSHUF) ? 2 : 1;
+    if (out.h != p.OH * mul || out.w != p.OW * mul || out.n != in.n) return VSE_E_INVAL;
+    if (p.res_lo_off && (!p.vec16 || p.resshift || (p.res_lo_off & 7))) return VSE_E_INVAL;
+    if (p.lo_off && (!p.vec16 || (f & (F_OUT_F32 | F_ONECH | F_DOT1 | F_UP2HEAD)) || (p.lo_off & 7) || out.ld < p.lo_off + Np / ((f & F_PIXSHUF) ? 4 : 1)))
+        return VSE_E_INVAL;
+    if ((f & F_OGATE) && ((f & (F_SRC2 | F_IMGW | F_PIXSHUF | F_DOT1 | F_UP2HEAD)) || !in2.ptr || in2.esize != 2 || in2.n != in.n || in2.h != 1
+                          || in2.w != 1 || in2.c < Np || (in2.ld & 7) || (reinterpret_cast<uintptr_t>(in2.ptr) & 15)))
+        return VSE_E_INVAL;
+    if ((f & F_U8SRC) && (!(f & F_STEM) || !p.u8src || p.u8_h <= 0 || p.u8_w <= 0)) return VSE_E_INVAL;
+    if (p.wl_out && (f & (F_DOT1 | F_SRC2 | F_UP2HEAD | F_PIXSHUF))) return VSE_E_UNSUPPORTED;   // no per-sample width in these forms
+    const ConvKernel k = conv_select(p, o.p[P_KTOT]);
+    if (k.family == CK_NONE) return k.rc;
+    if (!p.zero && !(f & (F_IMGW | F_DWPRE))) return VSE_E_INVAL;
+    switch (k.family) {
+        case CK_GEMM: return launch_conv_gemm(p, k, st);
+        case CK_SMALLM: return launch_conv_smallm(p, k, st);
+        case CK_MFMA: return launch_conv_mfma(p, k, st);
+        case CK_PATCH: return launch_conv_patch(p, k, st);
+        case CK_COL: return launch_conv_col(p, k, st);
+        case CK_C3: return launch_conv_c3(p, k, st);
+        case CK_PW: return launch_conv_pw(p, k, st);
+        case CK_DWPW: return launch_conv_dwpw(p, k, st);
+        case CK_HEAD: return launch_conv_head(p, k, st);
+        default: return launch_conv_stem(p, k, st);
+    }
+}

@@ -75,34 +75,16 @@ __global__ __launch_bounds__(64) void conv_smallm_hl_kernel(const ConvParams p) 
     conv_smallm_body<KT, true>(p, sbias);
 }
 
-// Layers this kernel serves: conv_gemm_kernel's unmasked 1x1 mode (mode 2) at stride 1 with at most 256 pixels, one weight stream.
-bool conv_smallm_shape_ok(int mode, long M, int sh, int sw, int same_hw, int flags, int cinp) {
-    return mode == 2 && M <= 256 && sh == 1 && sw == 1 && same_hw && !(flags & (F_IMGW | F_PIXSHUF | F_DOT1 | F_SRC2)) && (cinp & 15) == 0;
-}
-bool conv_smallm_ok(const ConvParams& p, int mode) {
-    return conv_smallm_shape_ok(mode, p.M, p.sh, p.sw, p.H == p.OH && p.W == p.OW && p.Hs == p.H && p.Ws == p.W, p.flags, p.cinp);
-}
-// ... and (round 5) SMALL 1x1 PROBLEMS whatever their route would be: <= 256 input channels (any multiple of 8: the SVTR necks' 120 / 240
-// are not multiples of 32 and ran on the 128 x 128 tile of conv_mfma_kernel), <= 4096 (32-cout x 32-pixel) wave tiles — a recogniser
-// sequence's [crops, 1, T, 120] layers.  Such a launch is a handful of K steps behind a prologue and in front of an epilogue on 13-50 of
-// 256 CUs (13-23 us launch to launch); here every wave is its own block with ALL its loads in flight at once.  Same K order, same bits.
-bool conv_smallk_shape_ok(int kh, int kw, int sh, int sw, int ph, int pw, int inshift, int same_hw, int flags, int cinp, long M, int Np) {
-    return kh == 1 && kw == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0 && !inshift && same_hw && cinp > 0 && cinp <= 256 && (cinp & 7) == 0
-           && !(flags & (F_IMGW | F_PIXSHUF | F_DOT1 | F_SRC2 | F_PATCH | F_COL | F_PW | F_STEM | F_UP2HEAD | F_DWPRE | F_ONECH | F_TAIL2 | F_HLSUM))
-           && M > 0 && ((M + 31) / 32) * ((Np + 31) / 32) <= 4096;
-}
-bool conv_smallk_ok(const ConvParams& p) {
-    return conv_smallk_shape_ok(p.kh, p.kw, p.sh, p.sw, p.ph, p.pw, p.inshift, p.H == p.OH && p.W == p.OW && p.Hs == p.H && p.Ws == p.W, p.flags, p.cinp,
-                                p.M, p.Np);
-}
-
-int launch_conv_smallm(const ConvParams& p, hipStream_t st) {
+// Which layers it serves: conv_select() (conv_select.hip).  k.arg[0] = KT, k.arg[1] = hi + lo.
+int launch_conv_smallm(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+    ConvParams p = pin;
+    p.nkh = p.nkh * 32 / k.arg[0];           // K tiles of one weight pass (nkh = Kp / 32 on entry)
     if ((p.M + 31) / 32 > 65535) return VSE_E_UNSUPPORTED;
     const dim3 grid((unsigned)((p.Np + 31) / 32), (unsigned)((p.M + 31) / 32)), block(64);
-    if (p.flags & F_HILO) {
-        if (p.flags & F_WK32) hipLaunchKernelGGL((conv_smallm_hl_kernel<32>), grid, block, 0, st, p);
+    if (k.arg[1]) {
+        if (k.arg[0] == 32) hipLaunchKernelGGL((conv_smallm_hl_kernel<32>), grid, block, 0, st, p);
         else hipLaunchKernelGGL((conv_smallm_hl_kernel<64>), grid, block, 0, st, p);
-    } else if (p.flags & F_WK32) hipLaunchKernelGGL((conv_smallm_kernel<32>), grid, block, 0, st, p);
+    } else if (k.arg[0] == 32) hipLaunchKernelGGL((conv_smallm_kernel<32>), grid, block, 0, st, p);
     else hipLaunchKernelGGL((conv_smallm_kernel<64>), grid, block, 0, st, p);
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }

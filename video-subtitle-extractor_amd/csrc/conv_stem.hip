@@ -224,27 +224,28 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(const ConvParams p) {
     }
 }
 
-int launch_conv_stem(const ConvParams& pin, int n_img, hipStream_t st) {
+// k.arg = S, HILO, U8
+int launch_conv_stem(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
     ConvParams p = pin;
     if (p.kh != 3 || p.kw != 3 || p.ph != 1 || p.pw != 1 || p.cinp != 8 || p.inshift != 0 || p.Np > 64 || p.Np < 1) return VSE_E_INVAL;
     if (p.flags & (F_PIXSHUF | F_DOT1 | F_SRC2 | F_PATCH | F_UP2HEAD)) return VSE_E_INVAL;
     if (!((p.sh == 1 && p.sw == 1) || (p.sh == 2 && p.sw == 2))) return VSE_E_INVAL;
     p.tiles_h = (p.OH + ST_ROWS - 1) / ST_ROWS;
     p.tiles_w = (p.OW + ST_COLS - 1) / ST_COLS;
-    const unsigned long long blocks = (unsigned long long)n_img * p.tiles_h * p.tiles_w;
+    const unsigned long long blocks = (unsigned long long)conv_images(p) * p.tiles_h * p.tiles_w;
     if (blocks == 0 || blocks > 0x7fffffffull) return VSE_E_INVAL;
     const dim3 grid((unsigned)blocks), block(256);
-    const bool hilo = p.flags & F_HILO;
-    if (p.flags & F_U8SRC) {
+    const bool s2 = k.arg[0] == 2, hilo = k.arg[1];
+    if (k.arg[2]) {
         if (!p.u8src || p.u8_h <= 0 || p.u8_w < 3) return VSE_E_INVAL;          // (8-byte row loads: >= 9 bytes per source row)
-        if (p.sh == 2 && hilo) hipLaunchKernelGGL((conv_stem_kernel<2, 2, true, true>), grid, block, 0, st, p);
-        else if (p.sh == 2) hipLaunchKernelGGL((conv_stem_kernel<2, 2, false, true>), grid, block, 0, st, p);
+        if (s2 && hilo) hipLaunchKernelGGL((conv_stem_kernel<2, 2, true, true>), grid, block, 0, st, p);
+        else if (s2) hipLaunchKernelGGL((conv_stem_kernel<2, 2, false, true>), grid, block, 0, st, p);
         else if (hilo) hipLaunchKernelGGL((conv_stem_kernel<1, 1, true, true>), grid, block, 0, st, p);
         else hipLaunchKernelGGL((conv_stem_kernel<1, 1, false, true>), grid, block, 0, st, p);
         return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
     }
-    if (p.sh == 2 && hilo) hipLaunchKernelGGL((conv_stem_kernel<2, 2, true>), grid, block, 0, st, p);
-    else if (p.sh == 2) hipLaunchKernelGGL((conv_stem_kernel<2, 2, false>), grid, block, 0, st, p);
+    if (s2 && hilo) hipLaunchKernelGGL((conv_stem_kernel<2, 2, true>), grid, block, 0, st, p);
+    else if (s2) hipLaunchKernelGGL((conv_stem_kernel<2, 2, false>), grid, block, 0, st, p);
     else if (hilo) hipLaunchKernelGGL((conv_stem_kernel<1, 1, true>), grid, block, 0, st, p);
     else hipLaunchKernelGGL((conv_stem_kernel<1, 1, false>), grid, block, 0, st, p);
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;

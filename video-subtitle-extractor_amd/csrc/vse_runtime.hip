@@ -55,7 +55,7 @@ extern "C" {
 const char* vse_last_error(void) { return g_err.c_str(); }
 size_t vse_sizeof_op(void) { return sizeof(vse_op); }
 size_t vse_sizeof_view(void) { return sizeof(vse_view); }
-int vse_abi_version(void) { return 3; }
+int vse_abi_version(void) { return 4; }
 
 int vse_init(int device_id, vse_ctx** out) {
     if (!out) return VSE_E_INVAL;
@@ -205,9 +205,6 @@ static inline TView resolve(const vse_view& v, char* ws, char* wts, void* const*
     return t;
 }
 
-// geometry of the uint8 source frames of one run (F_U8SRC plans)
-struct SrcGeom { int h, w; long pitch, fstride; };
-
 static int run_op(vse_plan* p, int i, char* ws, void* const* ext, const int32_t* wtab, hipStream_t st, const SrcGeom& src) {
     const vse_op& o = p->ops[i];
     // ragged plans: widths[level][n]
@@ -219,29 +216,8 @@ static int run_op(vse_plan* p, int i, char* ws, void* const* ext, const int32_t*
                 out2 = resolve(o.out2, ws, wts, ext);
     int rc;
     if (o.kind == OP_CONV) {
-        ConvArgs a;
-        a.in = in0; a.res = in1; a.out = out;
-        a.w = reinterpret_cast<const half_t*>(wts + o.w_off);
-        a.bias = reinterpret_cast<const float*>(wts + o.b_off);
-        a.zero = reinterpret_cast<const half_t*>(p->ctx->zero_page);
-        a.kh = o.p[P_KH]; a.kw = o.p[P_KW]; a.sh = o.p[P_SH]; a.sw = o.p[P_SW]; a.ph = o.p[P_PH]; a.pw = o.p[P_PW];
-        a.act = o.p[P_ACT]; a.act2 = o.p[P_ACT2]; a.Np = o.p[P_COUT]; a.Kp = o.p[P_KTOT];
-        a.inshift = o.p[P_INSHIFT]; a.resshift = o.p[P_RESSHIFT]; a.cinp = o.p[P_CINP]; a.flags = o.flags;
-        a.act_a = o.f[FS_ACT_A]; a.act_b = o.f[FS_ACT_B]; a.post_a = o.f[FS_POST_A]; a.post_b = o.f[FS_POST_B];
-        a.dotw = reinterpret_cast<const float*>(wts + o.aux_off);
-        a.dotb = o.f[FS_PRE_B]; a.dotact = o.p[P_DOTACT]; a.dot_out = out2;
-        a.in2 = in2; a.in2shift = o.p[P_IN2SHIFT];
-        if (o.flags & F_IMGW) a.w = reinterpret_cast<const half_t*>(in2.ptr);      // per-image weights in the workspace
-        a.wl_out = wl_out;
-        a.lo_off = o.p[P_LO_OUT];
-        a.res_lo_off = o.p[P_LO_RES];
-        a.in_lo_off = o.p[P_LO_IN];
-        a.u8src = nullptr; a.u8_h = a.u8_w = 0; a.u8_pitch = a.u8_fstride = 0;
-        if (o.flags & F_U8SRC) {
-            a.u8src = reinterpret_cast<const uint8_t*>(ext[0]);
-            a.u8_h = src.h; a.u8_w = src.w; a.u8_pitch = src.pitch; a.u8_fstride = src.fstride;
-        }
-        rc = launch_conv(a, st);
+        const uint8_t* u8src = (o.flags & F_U8SRC) ? reinterpret_cast<const uint8_t*>(ext[0]) : nullptr;
+        rc = launch_conv(o, in0, in1, in2, out, out2, wts, reinterpret_cast<const half_t*>(p->ctx->zero_page), wl_out, u8src, src, st);
     } else if (o.kind == OP_CHAIN) {
         rc = launch_chain(o, in0, out, out2, in2, wts, st);
     } else {
@@ -424,89 +400,22 @@ int vse_frame_change(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w,
     return vse_frame_change_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, d_state, reset, d_counts, stream);
 }
 
-int vse_plan_op_variant(vse_plan* p, int i) {
-    if (!p || i < 0 || i >= (int)p->ops.size()) return VSE_E_INVAL;
-    const vse_op& o = p->ops[i];
-    if (o.kind != OP_CONV) return 0;
-    if (o.flags & F_UP2HEAD) return 400000;   // conv_head_up2_kernel
-    if (o.flags & F_STEM) return 500000;      // conv_stem_kernel
-    if (o.flags & F_DWPRE) {
-        const int rs = conv_dwpw_rows_stride(o.p[P_KH], o.p[P_PH], o.p[P_SH], o.p[P_CINP], o.p[P_LO_IN]);
-        if (rs) return 860000 + 10 * ((o.p[P_CINP] + 15) / 16) + rs;                       // conv_dwpw_rows_kernel<KS, LO, S>
-        return 850000 + 10 * ((o.p[P_CINP] + 15) / 16) + o.p[P_KH];                        // conv_dwpw_kernel<KS, K, LO>
-    }
-    if (o.flags & F_PW) return ((o.flags & F_TAIL2) ? 810000 : 800000) + (o.p[P_CINP] + 15) / 16;   // conv_pw_kernel<KS> / conv_pw_tail_kernel<KS>
-    if ((o.flags & F_COL) && o.p[P_KH] == 3 && o.p[P_KW] == 3) {   // conv_c3_kernel<RW, 8 / RW>
-        int rw;
-        conv_c3_plan(o.out.h, o.out.w, &rw);
-        return 700000 + rw + ((o.p[P_COUT] <= 32 && !(o.flags & F_HLSUM)) ? 50000 : 0);      // + 50000: the 32-cout form conv_c3n32_kernel (F_HLSUM: the 64-row form, hi | lo)
-    }
-    if (o.flags & F_COL) return 600000 + 100 * o.p[P_KH] + conv_col_bn(o.p[P_COUT]);   // conv_col_kernel<KH, BN>
-    if (o.flags & F_PATCH) {   // conv_patch_kernel<TH, BN, BIGP> -> 100000*BIGP + 1000*TH + BN
-        // conv_patch_kernel<TH, BN, MODE> -> 100000*MODE + 1000*TH + BN
-        int th, bn, mode;
-        conv_patch_plan(o.p[P_KH], o.p[P_KW], (o.flags & F_DOT1) ? o.out2.h : o.out.h, o.p[P_COUT], o.flags, &th, &bn, &mode);
-        return 100000 * mode + 1000 * th + bn;
-    }
-    // conv_gemm_kernel configuration c, MASK m -> 200000 + 10*c + m; conv_mfma_kernel<.., UPS> -> 10000*UPS + BN
-    {
-        long m = (long)o.out.n * o.out.h * o.out.w;
-        if (conv_smallk_shape_ok(o.p[P_KH], o.p[P_KW], o.p[P_SH], o.p[P_SW], o.p[P_PH], o.p[P_PW], o.p[P_INSHIFT], o.in0.h == o.out.h && o.in0.w == o.out.w, o.flags,
-                                 o.p[P_CINP], m, o.p[P_COUT]))
-            return 900000 + ((o.flags & F_WK32) ? 32 : 64) + ((o.flags & F_HILO) ? 1000 : 0);   // conv_smallm_kernel<KT> (small 1x1 problems)
-    }
-    const int mode = conv_gemm_mode(o.p[P_KH], o.p[P_KW], o.p[P_SH], o.p[P_SW], o.p[P_PH], o.p[P_PW], o.p[P_CINP], o.p[P_KTOT], o.p[P_INSHIFT],
-                                    o.flags);
-    if (mode) {
-        long m = (long)o.out.n * o.out.h * o.out.w;
-        if (o.flags & F_PIXSHUF) m /= 4;
-        if (conv_smallm_shape_ok(mode, m, o.p[P_SH], o.p[P_SW], o.in0.h == o.out.h && o.in0.w == o.out.w, o.flags, o.p[P_CINP]))
-            return 900000 + ((o.flags & F_WK32) ? 32 : 64) + ((o.flags & F_HILO) ? 1000 : 0);   // conv_smallm_kernel<KT> (+ 1000: conv_smallm_hl_kernel)
-        return 200000 + 10 * conv_gemm_config(o.p[P_COUT], o.p[P_CINP], m) + (mode == 1 ? 1 : 0);
-    }
-    return (o.p[P_INSHIFT] ? 10000 : 0) + conv_tile_bn(o.p[P_COUT]);
-}
-
-// The kernel instantiation op `i` dispatches to, spelled the way rocprofv3 reports it (thread-local storage).
-const char* vse_plan_op_kernel_name(vse_plan* p, int i) {
+// The kernel a record launches, spelled as rocprofv3 reports it (thread-local storage); no plan, context or GPU needed.
+const char* vse_op_kernel_name(const vse_op* op) {
     static thread_local char buf[96];
     buf[0] = 0;
-    if (!p || i < 0 || i >= (int)p->ops.size()) return buf;
-    const vse_op& o = p->ops[i];
+    if (!op) return buf;
+    const vse_op& o = *op;
     static const char* simple[] = {"", "", "dwconv_kernel", "pool_kernel", "gap_kernel", "scale_kernel", "binary_kernel", "resize_kernel",
                                    "unary_kernel", "layernorm_kernel", "attn_kernel", "softmax_kernel", "lstm_kernel", "wscale_kernel", "chain_kernel"};
     if (o.kind != OP_CONV) {
         snprintf(buf, sizeof buf, "%s", (o.kind >= 2 && o.kind <= OP_CHAIN) ? simple[o.kind] : "?");
         return buf;
     }
-    const int code = vse_plan_op_variant(p, i);
-    if (code >= 901000) snprintf(buf, sizeof buf, "conv_smallm_hl_kernel<%d>", code - 901000);
-    else if (code >= 900000) snprintf(buf, sizeof buf, "conv_smallm_kernel<%d>", code - 900000);
-    else if (code >= 860000) snprintf(buf, sizeof buf, "conv_dwpw_rows_kernel<%d, %s, %d>", (code - 860000) / 10, o.p[P_LO_IN] ? "true" : "false", code % 10);
-    else if (code >= 850000) snprintf(buf, sizeof buf, "conv_dwpw_kernel<%d, %d, %s>", (code - 850000) / 10, code % 10, o.p[P_LO_IN] ? "true" : "false");
-    else if (code >= 810000) snprintf(buf, sizeof buf, "conv_pw_tail_kernel<%d>", code - 810000);
-    else if (code >= 800000) snprintf(buf, sizeof buf, "conv_pw_kernel<%d>", code - 800000);
-    else if (code >= 750000) snprintf(buf, sizeof buf, "conv_c3n32_kernel<%d, %d>", code - 750000, 8 / (code - 750000));
-    else if (code >= 700000) snprintf(buf, sizeof buf, "conv_c3_kernel<%d, %d>", code - 700000, 8 / (code - 700000));
-    else if (code >= 600000) snprintf(buf, sizeof buf, "conv_col_kernel<%d, %d>", (code - 600000) / 100, code % 100);
-    else if (code >= 500000) snprintf(buf, sizeof buf, "conv_stem_kernel");
-    else if (code >= 400000) {
-        // (the launcher's switch, conv_head.hip: the persistent resident-weight form unless VSE_HEAD_RESIDENT=0)
-        static const bool resident = [] { const char* e = getenv("VSE_HEAD_RESIDENT"); return !(e && e[0] == '0'); }();
-        snprintf(buf, sizeof buf, resident ? "conv_head_up2r_kernel" : "conv_head_up2_kernel");
-    }
-    else if (o.flags & F_PATCH) snprintf(buf, sizeof buf, "conv_patch_kernel<%d, %d, %d>", (code / 1000) % 100, code % 1000, code / 100000);
-    else if (code >= 200000) {
-        static const char* cfg[] = {"128, 128, 2, 2, 32, 3", "256, 64, 4, 1, 32, 3", "256, 32, 4, 1, 32, 3", "", "", "", "256, 128, 4, 2, 32, 3",
-                                    "", "", "", "", "", "", "", "", "", "256, 256, 4, 4, 32, 3", "256, 192, 8, 2, 32, 3",
-                                    "256, 256, 4, 4, 64, 2", "256, 192, 8, 2, 64, 2"};
-        const int c = (code - 200000) / 10;
-        snprintf(buf, sizeof buf, "conv_gemm_kernel<%s, %d>", (c >= 0 && c < 20) ? cfg[c] : "?", code % 10);
-    } else {
-        const int bn = code % 1000;
-        snprintf(buf, sizeof buf, "conv_mfma_kernel<%s, %s>", bn == 128 ? "128, 128, 2, 2" : (bn == 64 ? "256, 64, 4, 1" : "256, 32, 4, 1"),
-                 code >= 10000 ? "true" : "false");
-    }
+    auto shape = [](const vse_view& v) { return TView{nullptr, v.n, v.h, v.w, v.c, v.ld, v.esize}; };
+    const ConvParams p = conv_params(o, shape(o.in0), shape(o.in1), shape(o.in2), shape(o.out), shape(o.out2), nullptr, nullptr, nullptr, nullptr,
+                                     SrcGeom{0, 0, 0, 0});
+    conv_kernel_name(conv_select(p, o.p[P_KTOT]), buf, sizeof buf);
     return buf;
 }
 

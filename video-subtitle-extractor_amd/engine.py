@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("VSE_LIB_PATH") or os.path.join(_HERE, "libvse_hip.so"
 EXPORTS = [
     "vse_init", "vse_destroy", "vse_last_error", "vse_sizeof_op", "vse_sizeof_view", "vse_abi_version",
     "vse_weights_upload", "vse_weights_free", "vse_plan_create", "vse_plan_destroy", "vse_plan_run", "vse_plan_run_ragged",
-    "vse_plan_width_levels", "vse_plan_profile", "vse_plan_op_variant", "vse_plan_op_kernel_name", "vse_det_preprocess", "vse_db_workspace_bytes",
+    "vse_plan_width_levels", "vse_plan_profile", "vse_op_kernel_name", "vse_det_preprocess", "vse_db_workspace_bytes",
     "vse_db_postprocess", "vse_rec_preprocess", "vse_rec_preprocess_scratch_bytes", "vse_ctc_collapse", "vse_ctc_collapse_ragged",
     "vse_det_forward", "vse_rec_forward", "vse_plan_set_source", "vse_plan_takes_frames",
     "vse_rec_graph_create", "vse_graph_launch", "vse_graph_destroy", "vse_frame_change_state_bytes", "vse_frame_change",
@@ -97,9 +97,8 @@ def load_library(path=None):
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vse_plan_profile.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p,
                                      C.POINTER(C.c_float)]
-    lib.vse_plan_op_variant.argtypes = [C.c_void_p, C.c_int]
-    lib.vse_plan_op_kernel_name.argtypes = [C.c_void_p, C.c_int]
-    lib.vse_plan_op_kernel_name.restype = C.c_char_p
+    lib.vse_op_kernel_name.argtypes = [C.c_void_p]
+    lib.vse_op_kernel_name.restype = C.c_char_p
     lib.vse_det_preprocess.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                        C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                        C.c_void_p]
@@ -122,6 +121,14 @@ def load_library(path=None):
                        f"vse_view {lib.vse_sizeof_view()} vs {ir.VIEW_DT.itemsize}")
     _lib = lib
     return lib
+
+
+def op_kernel_names(ops):
+    """The kernel each record of an ir.OP_DT array launches, as rocprofv3 names it (vse_op_kernel_name; no GPU needed)."""
+    lib = load_library()
+    ops = np.ascontiguousarray(ops)
+    base = ops.ctypes.data
+    return [lib.vse_op_kernel_name(C.c_void_p(base + i * ops.itemsize)).decode() for i in range(len(ops))]
 
 
 def _check(rc, what):
@@ -559,7 +566,7 @@ class Net:
         self.last_outs = outs
         _check(self.ctx.lib.vse_plan_profile(handle, C.c_void_p(ws.data_ptr()), ptrs, len(ptrs), None, self.ctx.stream(), ms),
                "vse_plan_profile")
-        names = [self.ctx.lib.vse_plan_op_kernel_name(handle, i).decode() for i in range(len(prog.ops))]
+        names = op_kernel_names(prog.ops)
         return np.array(ms[:], dtype=np.float32), prog, names
 
     def rec_forward(self, x, widths=None, slot=0):
@@ -638,5 +645,5 @@ class Net:
         _check(self.ctx.lib.vse_plan_profile(handle, C.c_void_p(ws.data_ptr()), ptrs, len(ptrs),
                                              C.c_void_p(wt.data_ptr()) if wt is not None else None, self.ctx.stream(), ms),
                "vse_plan_profile")
-        variants = [self.ctx.lib.vse_plan_op_kernel_name(handle, i).decode() for i in range(len(prog.ops))]
+        variants = op_kernel_names(prog.ops)
         return np.array(ms[:], dtype=np.float32), prog, variants
