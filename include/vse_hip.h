@@ -228,6 +228,31 @@ int vse_frame_change(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_
                      int y0, int y1, int x0, int x1, int edge_thresh, void* d_state, int reset,
                      int32_t* d_counts /* [n,3]: edges, appeared, vanished */, void* stream);
 
+/* ---- timeline sync: audio template search ----------------------------------------------------------------------------- */
+/* Replaces: Sushi's WavStream.find_substream (backend/sushi/wav.py:179-189), cv2.matchTemplate(TM_SQDIFF_NORMED) of one group's
+ * source audio against a window of the destination audio.  Both streams are uint8.  A query takes the pattern
+ * p = src[src_off, src_off + m) and the window w = dst[dst_off, dst_off + win_len), n = win_len - m + 1 offsets; for every k < n:
+ *   X_k = sum p[i] w[k+i], S_k = sum w[k+i]^2, P = sum p[i]^2                 (exact integers)
+ *   num = (double) max(S_k - 2 X_k + P, 0), den = sqrt((double) S_k) * sqrt((double) P)
+ *   v_k = (float)(num / den) if num < den, else 1.0f (so den == 0 gives 1)
+ * and the result is the first k of the smallest v_k with v_k itself.  cv2 computes the same value with a float32 DFT cross term
+ * and a meanStdDev template norm, so its last bits and its argmin on near-ties can differ. */
+typedef struct {
+    int64_t src_off, m, dst_off, win_len;
+} vse_audio_query;
+typedef struct {
+    int32_t index;
+    float value;
+} vse_audio_match_result;
+/* Workspace bytes vse_audio_match needs for these nq queries (0 when one of them is invalid). */
+size_t vse_audio_match_workspace_bytes(const vse_audio_query* queries, int nq);
+/* 1 <= nq <= 3 host-side queries -> d_out[nq] (device, 8-byte aligned), in two launches on `stream`, with no device sync and no
+ * allocation.  d_ws: at least vse_audio_match_workspace_bytes of these queries, 256-byte aligned.  Returns VSE_E_INVAL, and
+ * launches nothing, when m < 1, a window is shorter than its pattern, a range lies outside its stream, nq is not in 1..3 or
+ * the workspace is too small. */
+int vse_audio_match(vse_ctx* ctx, const uint8_t* d_src, int64_t src_len, const uint8_t* d_dst, int64_t dst_len,
+                    const vse_audio_query* queries, int nq, void* d_ws, size_t ws_bytes, vse_audio_match_result* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

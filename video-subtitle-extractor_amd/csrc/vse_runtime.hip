@@ -49,6 +49,9 @@ struct vse_plan {
 
 int vse_frame_change_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
                             void* d_state, int reset, int32_t* d_counts, void* stream);     // frame_change.hip
+size_t vse_audio_match_ws(const long* m, const long* n, int nq);                                                       // audio_match.hip
+int vse_audio_match_launch(const uint8_t* const* pat, const uint8_t* const* win, const long* m, const long* n, int nq, void* d_ws,
+                           unsigned long long* d_out, void* stream);
 
 extern "C" {
 
@@ -398,6 +401,63 @@ int vse_frame_change(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w,
         return VSE_E_INVAL;
     }
     return vse_frame_change_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, d_state, reset, d_counts, stream);
+}
+
+// ---- timeline sync: audio template search (audio_match.hip) ------------------------------------------------------------------
+static const char* audio_query_error(const vse_audio_query& q, int64_t src_len, int64_t dst_len) {
+    if (q.m < 1) return "pattern length m < 1";
+    if (q.win_len < q.m) return "window shorter than the pattern";
+    if (q.src_off < 0 || q.src_off > src_len - q.m) return "pattern range outside the source stream";
+    if (q.dst_off < 0 || q.dst_off > dst_len - q.win_len) return "window range outside the destination stream";
+    if (q.win_len > INT32_MAX / 2) return "window longer than 2^30 bytes";
+    return nullptr;
+}
+
+size_t vse_audio_match_workspace_bytes(const vse_audio_query* queries, int nq) {
+    if (!queries || nq < 1 || nq > 3) return 0;
+    long m[3], n[3];
+    for (int i = 0; i < nq; ++i) {
+        if (audio_query_error(queries[i], INT64_MAX / 2, INT64_MAX / 2)) return 0;
+        m[i] = (long)queries[i].m;
+        n[i] = (long)(queries[i].win_len - queries[i].m + 1);
+    }
+    return vse_audio_match_ws(m, n, nq);
+}
+
+int vse_audio_match(vse_ctx* c, const uint8_t* d_src, int64_t src_len, const uint8_t* d_dst, int64_t dst_len, const vse_audio_query* queries,
+                    int nq, void* d_ws, size_t ws_bytes, vse_audio_match_result* d_out, void* stream) {
+    if (!c || !d_src || !d_dst || !queries || !d_ws || !d_out || (reinterpret_cast<uintptr_t>(d_out) & 7) ||
+        (reinterpret_cast<uintptr_t>(d_ws) & 255)) {
+        set_err("vse_audio_match: null or misaligned pointer");
+        return VSE_E_INVAL;
+    }
+    if (nq < 1 || nq > 3) {
+        set_err("vse_audio_match: %d queries (1..3 per call)", nq);
+        return VSE_E_INVAL;
+    }
+    const uint8_t* pat[3];
+    const uint8_t* win[3];
+    long m[3], n[3];
+    for (int i = 0; i < nq; ++i) {
+        const vse_audio_query& q = queries[i];
+        if (const char* why = audio_query_error(q, src_len, dst_len)) {
+            set_err("vse_audio_match: query %d (pattern %lld + %lld of %lld, window %lld + %lld of %lld): %s", i, (long long)q.src_off,
+                    (long long)q.m, (long long)src_len, (long long)q.dst_off, (long long)q.win_len, (long long)dst_len, why);
+            return VSE_E_INVAL;
+        }
+        pat[i] = d_src + q.src_off;
+        win[i] = d_dst + q.dst_off;
+        m[i] = (long)q.m;
+        n[i] = (long)(q.win_len - q.m + 1);
+    }
+    const size_t need = vse_audio_match_ws(m, n, nq);
+    if (ws_bytes < need) {
+        set_err("vse_audio_match: workspace of %zu bytes, %zu needed", ws_bytes, need);
+        return VSE_E_INVAL;
+    }
+    const int rc = vse_audio_match_launch(pat, win, m, n, nq, d_ws, reinterpret_cast<unsigned long long*>(d_out), stream);
+    if (rc != VSE_OK) set_err("vse_audio_match: launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
 }
 
 // The kernel a record launches, spelled as rocprofv3 reports it (thread-local storage); no plan, context or GPU needed.

@@ -20,6 +20,7 @@ EXPORTS = [
     "vse_db_postprocess", "vse_rec_preprocess", "vse_rec_preprocess_scratch_bytes", "vse_ctc_collapse", "vse_ctc_collapse_ragged",
     "vse_det_forward", "vse_rec_forward", "vse_plan_set_source", "vse_plan_takes_frames",
     "vse_rec_graph_create", "vse_graph_launch", "vse_graph_destroy", "vse_frame_change_state_bytes", "vse_frame_change",
+    "vse_audio_match_workspace_bytes", "vse_audio_match",
 ]
 
 
@@ -116,6 +117,10 @@ def load_library(path=None):
     lib.vse_frame_change_state_bytes.argtypes = [C.c_int, C.c_int]
     lib.vse_frame_change.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.vse_audio_match_workspace_bytes.restype = C.c_size_t
+    lib.vse_audio_match_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
+    lib.vse_audio_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
+                                    C.c_size_t, C.c_void_p, C.c_void_p]
     if lib.vse_sizeof_op() != ir.OP_DT.itemsize or lib.vse_sizeof_view() != ir.VIEW_DT.itemsize:
         raise VseError(f"ABI mismatch: vse_op {lib.vse_sizeof_op()} vs {ir.OP_DT.itemsize}, "
                        f"vse_view {lib.vse_sizeof_view()} vs {ir.VIEW_DT.itemsize}")
@@ -343,6 +348,33 @@ class Context:
                                          frames_u8.stride(0), y0, y1, x0, x1, int(edge_thresh), C.c_void_p(state.data_ptr()),
                                          int(bool(reset)), C.c_void_p(out.data_ptr()), self.stream()), "vse_frame_change")
         return out
+
+    # ---- timeline sync: audio template search ---------------------------------------------------------------------
+    def audio_match_workspace_bytes(self, queries):
+        """Workspace bytes of one audio_match call with these (src_off, m, dst_off, win_len) queries (0 if one is invalid)."""
+        q = _audio_queries(queries)
+        return self.lib.vse_audio_match_workspace_bytes(C.c_void_p(q.ctypes.data), len(q))
+
+    def audio_match(self, src_u8, dst_u8, queries, workspace=None):
+        """src_u8, dst_u8: contiguous cuda uint8 streams; queries: 1..3 of (src_off, m, dst_off, win_len) ->
+        cuda int32 [nq, 2]: first argmin offset, float32 bits of its value (.view(float32)[:, 1]), on the current stream
+        (include/vse_hip.h vse_audio_match).  workspace: cuda uint8 of at least audio_match_workspace_bytes (allocated if None)."""
+        t = self.torch
+        assert src_u8.dtype == t.uint8 and src_u8.is_contiguous() and dst_u8.dtype == t.uint8 and dst_u8.is_contiguous()
+        q = _audio_queries(queries)
+        if workspace is None:
+            need = self.lib.vse_audio_match_workspace_bytes(C.c_void_p(q.ctypes.data), len(q))
+            workspace = t.empty(max(need, 256), dtype=t.uint8, device=self.tdev)
+        out = t.empty((len(q), 2), dtype=t.int32, device=self.tdev)
+        _check(self.lib.vse_audio_match(self.handle, C.c_void_p(src_u8.data_ptr()), src_u8.numel(), C.c_void_p(dst_u8.data_ptr()),
+                                        dst_u8.numel(), C.c_void_p(q.ctypes.data), len(q), C.c_void_p(workspace.data_ptr()),
+                                        workspace.numel(), C.c_void_p(out.data_ptr()), self.stream()), "vse_audio_match")
+        return out
+
+
+def _audio_queries(queries):
+    q = np.ascontiguousarray(np.array([[int(v) for v in x] for x in queries], dtype=np.int64).reshape(-1, 4))
+    return q
 
 
 class Net:

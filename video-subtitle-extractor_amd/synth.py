@@ -2,6 +2,8 @@
 video on either box, so frames are generated: noisy dark background with a vertical gradient and 1-2 subtitle
 lines (white fill, black outline) inside the reference's default subtitle area
 (y in [0.78,0.99]*H, x in [0.05,0.95]*W; backend/config.py:49)."""
+import struct
+
 import numpy as np
 
 _WORDS = ("the quick brown fox jumps over a lazy dog while seven wizards quietly box with grumpy elves "
@@ -113,3 +115,100 @@ def make_clip(schedule, height=360, width=640, seed=0):
             frames[f] = np.clip(img, 0, 255).astype(np.uint8)
             f += 1
     return frames, truth
+
+
+# ---- audio for timeline sync ---------------------------------------------------------------------------------------------------
+# Built from the bit generator's raw 64-bit words and integer arithmetic only, so a seed gives the same samples (and WAV bytes)
+# on any numpy.  Content is made at AUDIO_BASE_RATE and held (sample-and-hold) to any output rate, so two renders of the same
+# content at different rates line up after resampling.
+
+AUDIO_BASE_RATE = 12000
+
+
+def _raw(seed, n):
+    return np.random.PCG64(seed).random_raw(n)
+
+
+def speech_content(seconds, seed, floor=200, syllable_ms=(80, 260), gap_ms=(30, 320), amp=(1500, 12000)):
+    """int32 [seconds * AUDIO_BASE_RATE]: syllable-like bursts of noise (random length, gap and loudness, with a 10 ms ramp on
+    each side) over a noise floor of +-floor."""
+    n = int(seconds * AUDIO_BASE_RATE)
+    words = _raw(seed, n + 3 * (n // 300 + 8))
+    noise = (words[:n] >> np.uint64(48)).astype(np.int64) - 32768             # uniform in [-32768, 32768)
+    env = np.full(n, floor, np.int64)
+    params = words[n:].reshape(-1, 3)
+    ms = AUDIO_BASE_RATE // 1000
+    at = 0
+    for w_len, w_gap, w_amp in params:
+        at += (gap_ms[0] + int(w_gap % np.uint64(gap_ms[1] - gap_ms[0]))) * ms
+        if at >= n:
+            break
+        length = (syllable_ms[0] + int(w_len % np.uint64(syllable_ms[1] - syllable_ms[0]))) * ms
+        a = amp[0] + int(w_amp % np.uint64(amp[1] - amp[0]))
+        ramp = 10 * ms
+        idx = np.arange(length)
+        shape = np.minimum(np.minimum(idx + 1, length - idx), ramp) * a // ramp
+        end = min(at + length, n)
+        env[at:end] = np.maximum(env[at:end], shape[:end - at])
+        at = end
+    return (noise * env) >> 15
+
+
+def noise_content(seconds, seed, level):
+    """int32 [seconds * AUDIO_BASE_RATE]: uniform noise of +-level (an inserted segment, or noise to add)."""
+    return _noise(int(seconds * AUDIO_BASE_RATE), seed, level)
+
+
+def _noise(n, seed, level):
+    return (((_raw(seed, n) >> np.uint64(48)).astype(np.int64) - 32768) * level) >> 15
+
+
+def render_audio(content, rate, channels=1, gain=(1, 1)):
+    """int32 content at AUDIO_BASE_RATE -> int16 [n, channels] at `rate` (sample-and-hold), scaled by gain[0] / gain[1]; the
+    channels after the first are the first at 3/4 and 1/2 ... of its level."""
+    content = np.asarray(content, np.int64)
+    n = len(content) * rate // AUDIO_BASE_RATE
+    x = content[np.arange(n, dtype=np.int64) * AUDIO_BASE_RATE // rate] * gain[0] // gain[1]
+    cols = [x * (4 - min(c, 3)) // 4 for c in range(channels)]
+    return np.clip(np.stack(cols, axis=1), -32768, 32767).astype(np.int16)
+
+
+def wav_bytes(samples, rate, extensible=False, chunks_before_data=()):
+    """int16 [n, channels] -> a 16-bit PCM WAV file (fmt EXTENSIBLE if asked; extra (id, payload) chunks before the data)."""
+    samples = np.asarray(samples, np.int16)
+    ch = samples.shape[1]
+    if extensible:
+        fmt = struct.pack("<HHIIHHHHIH14s", 0xFFFE, ch, rate, rate * 2 * ch, 2 * ch, 16, 22, 16, 0, 1,
+                          b"\x00\x00\x00\x00\x10\x00\x80\x00\x00\xaa\x00\x38\x9b\x71")
+    else:
+        fmt = struct.pack("<HHIIHH", 1, ch, rate, rate * 2 * ch, 2 * ch, 16)
+    body = b"WAVE" + b"fmt " + struct.pack("<I", len(fmt)) + fmt
+    for cid, payload in chunks_before_data:
+        body += cid + struct.pack("<I", len(payload)) + payload + (b"\x00" if len(payload) & 1 else b"")
+    data = samples.astype("<i2").tobytes()
+    body += b"data" + struct.pack("<I", len(data)) + data
+    return b"RIFF" + struct.pack("<I", len(body)) + body
+
+
+def audio_from_recipe(r):
+    """A WAV file (bytes) from a JSON-able recipe:
+    {"pieces": [["speech", seed, seconds, from_s, to_s] | ["noise", seed, seconds, level], ...],   # concatenated content
+     "rate": Hz, "channels": 1, "gain": [num, den], "noise": [seed, level] or None,               # noise added to the content
+     "trim": output samples dropped at the end, "extensible": bool, "list_chunk": bool}"""
+    parts = []
+    for p in r["pieces"]:
+        if p[0] == "speech":
+            _, seed, seconds, a, b = p
+            parts.append(speech_content(seconds, seed)[int(a * AUDIO_BASE_RATE):int(b * AUDIO_BASE_RATE)])
+        else:
+            _, seed, seconds, level = p
+            parts.append(noise_content(seconds, seed, level))
+    content = np.concatenate(parts)
+    if r.get("noise"):
+        seed, level = r["noise"]
+        content = content + _noise(len(content), seed, level)
+    x = render_audio(content, r.get("rate", AUDIO_BASE_RATE), r.get("channels", 1), tuple(r.get("gain", (1, 1))))
+    if r.get("trim"):
+        x = x[:len(x) - r["trim"]]
+    extra = [(b"LIST", b"INFOISFT\x05\x00\x00\x00synth\x00")] if r.get("list_chunk") else []
+    return wav_bytes(x, r.get("rate", AUDIO_BASE_RATE), extensible=r.get("extensible", False), chunks_before_data=extra)
