@@ -16,6 +16,10 @@
 //   sync   = as conv_col_kernel: one raw s_barrier per step, vmcnt(1) (+ the patch DMAs at a chunk's first step).
 //   couts  = ceil(Np / 64) cout tiles per pixel tile (innermost in the block order: the tiles that share a patch run together).
 //   weights packed [cinp/16][3 dx][3 dy][Np][16] + 3 zero stages (compiler.col_weights, F_COL).
+//   columns = VIRTUAL columns of a group of p.pack_g images (column packing, conv_common.h): a 240-wide map leaves a quarter of
+//            its 64-wide tiles half empty, four such maps side by side fill 15 tiles.  The 6 spare pixels of a patch row take the
+//            zero gaps between the images of a tile; a lane's fragment column gains one gap per seam left of it (computed once,
+//            nothing new in the K loop), and the epilogue turns the virtual column back into (image, column).
 #include "conv_common.h"
 #ifdef VSE_TRACE
 #include <stdio.h>
@@ -73,9 +77,11 @@ __device__ __forceinline__ void conv_c3_body(const ConvParams& p) {
     const int nt = t % p.ntn;  t /= p.ntn;
     const int tx = t % p.tiles_w;  t /= p.tiles_w;
     const int ty = t % p.tiles_h;
-    const long img = t / p.tiles_h;
+    // column packing (conv_common.h): ox0 is a VIRTUAL column of the block's image group; one image per group when pack_g == 1
     const int oy0 = ty * TH, ox0 = tx * TW, n0 = nt * BN;
-    if (conv_tile_right_of_sample<TH, TW>(p, img, oy0, ox0, n0, BN)) return;      // ragged batch: nothing to compute here
+    const ConvPackTile pk = conv_pack_tile(p, (int)(t / p.tiles_h), ox0, TW, 3);
+    if (ox0 >= pk.vw) return;                            // a short last group: no live image under this tile
+    if (conv_tile_right_of_sample<TH, TW>(p, pk.img0, oy0, ox0, n0, BN)) return;  // ragged batch (never packed): nothing to compute here
     const int nch1 = p.cinp >> 4;                        // 16-channel chunks of one pass over the input
     // F_HILO: fp16 hi + lo weight pairs — the lo stream follows the hi stream, the patch chunks are walked a second time into
     // the same accumulators (the implicit-GEMM kernels' two-pass K walk)
@@ -88,12 +94,13 @@ __device__ __forceinline__ void conv_c3_body(const ConvParams& p) {
         const int q = 32 * (wave + 8 * j) + (lane >> 1);
         const int kh_ = (lane & 1) ^ ((q >> 3) & 1);
         const int py = q / PW, px = q - py * PW;
-        const int iy = oy0 - 1 + py, ix = ox0 - 1 + px;
-        const bool ok = (py < PH) && (px < TW + 2) && (iy >= 0) && (iy < p.H) && (ix >= 0) && (ix < p.W);
-        const long o = ((img * p.Hs + (iy >> p.inshift)) * p.Ws + (ix >> p.inshift)) * (long)p.in_ld + kh_ * 8;
-        poff[j] = ok ? (int)(o - img * (long)p.Hs * p.Ws * p.in_ld) : -1;
+        const int iy = oy0 - 1 + py;
+        int g, ix;
+        const bool ok = conv_pack_src(p, pk, px, g, ix) && (py < PH) && (iy >= 0) && (iy < p.H);
+        const long o = (((long)g * p.Hs + (iy >> p.inshift)) * p.Ws + (ix >> p.inshift)) * (long)p.in_ld + kh_ * 8;
+        poff[j] = ok ? (int)o : -1;                        // from the group's first image
     }
-    const half_t* const in_img = p.in + img * (long)p.Hs * p.Ws * p.in_ld;
+    const half_t* const in_img = p.in + pk.img0 * (long)p.Hs * p.Ws * p.in_ld;
     const half_t* wptr;
     bool wok;
     const int wnp = p.wnp;                                 // weight rows per tap (= Np; F_HLSUM: hi 32 | lo 32)
@@ -129,12 +136,13 @@ __device__ __forceinline__ void conv_c3_body(const ConvParams& p) {
     const int wr0 = conv_wrow(fx);
     const unsigned woffb = (unsigned)(2 * PATCH_BYTES + wr0 * 32 + ((fj ^ ((wr0 >> 3) & 1)) << 4));
     const unsigned xrow0 = (unsigned)(2 * rw * ROWB);
+    const unsigned fcol = (unsigned)conv_pack_fragcol(p, pk, ox0, ox0 + 32 * cw + fx);   // = 32 cw + fx + one gap per seam left of the lane
     auto xcol = [&](int dx, int buf) -> unsigned {       // even-row base of the wave's fragments under column dx (odd rows: ^ 16)
-        const unsigned c = (unsigned)(32 * cw + fx + dx);
+        const unsigned c = fcol + (unsigned)dx;
         return (unsigned)buf * PATCH_BYTES + xrow0 + c * 32 + ((fj ^ ((c >> 3) & 1)) << 4);
     };
     const char* const ldsb = reinterpret_cast<const char*>(lds);
-    const bool wave_live = (oy0 + 2 * rw) < p.OH && (ox0 + 32 * cw) < p.OW;
+    const bool wave_live = (oy0 + 2 * rw) < p.OH && (ox0 + 32 * cw) < pk.vw;
 
     float16v acc[2][TN];
 #pragma unroll
@@ -252,8 +260,10 @@ __device__ __forceinline__ void conv_c3_body(const ConvParams& p) {
     // ---- epilogue ---------------------------------------------------------------------------------------------------
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        const int oy = oy0 + 2 * rw + i, ox = ox0 + 32 * cw + fx;
-        if (oy >= p.OH || ox >= p.OW) continue;
+        const int oy = oy0 + 2 * rw + i, v = ox0 + 32 * cw + fx;
+        if (oy >= p.OH || v >= pk.vw) continue;
+        const int g = (int)__umulhi((unsigned)v, p.pack_mag_ow), ox = v - g * p.OW;
+        const long img = pk.img0 + g;
         const long m = (img * p.OH + oy) * p.OW + ox;
         if constexpr (TN == 2) {
             if (p.flags & F_HLSUM) {                     // tile 0 = W_hi x, tile 1 = W_lo x of the same 32 couts
@@ -291,16 +301,17 @@ __global__ __launch_bounds__(512, 4) void conv_c3n32_kernel(const ConvParams p) 
 // k.arg = RW, the 32-cout form; which layers it serves and the tile shape: conv_c3_ok / conv_c3_plan (conv_select.hip)
 int launch_conv_c3(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
     ConvParams p = pin;
-    if ((double)p.Hs * p.Ws * p.in_ld > 2.0e9) return VSE_E_UNSUPPORTED;      // 32-bit in-image offsets
     const int rw = k.arg[0], cw = 8 / rw;
+    conv_pack_plan(p, 32 * cw, 6);                       // the patch rows are TW + 8 pixels apart, TW + 2 are read
+    if ((double)p.pack_g * p.Hs * p.Ws * p.in_ld > 2.0e9) conv_pack_plan(p, 32 * cw, -1);     // (no spare column: one image per group)
+    if ((double)p.Hs * p.Ws * p.in_ld > 2.0e9) return VSE_E_UNSUPPORTED;      // 32-bit offsets from the group's first image
     const bool hlsum = (p.flags & F_HLSUM) != 0;
     if (hlsum && (p.Np > 32 || (p.flags & F_HILO))) return VSE_E_INVAL;
     const int bn = k.arg[1] ? 32 : C3BN;
     p.wnp = hlsum ? 64 : p.Np;
     p.ntn = hlsum ? 1u : (unsigned)((p.Np + bn - 1) / bn);
     p.tiles_h = (p.OH + 2 * rw - 1) / (2 * rw);
-    p.tiles_w = (p.OW + 32 * cw - 1) / (32 * cw);
-    const unsigned long long blocks = (unsigned long long)conv_images(p) * p.tiles_h * p.tiles_w * p.ntn;
+    const unsigned long long blocks = (unsigned long long)((p.nimg + p.pack_g - 1) / p.pack_g) * p.tiles_h * p.tiles_w * p.ntn;
     if (blocks == 0 || blocks > 0x7fffffffull) return VSE_E_INVAL;
     const dim3 grid((unsigned)blocks), block(512);
 #ifdef VSE_TRACE

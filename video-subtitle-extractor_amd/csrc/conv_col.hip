@@ -23,6 +23,8 @@
 //            chunk's second step and vmcnt(WNPL) everywhere else.
 //   tile   = 16 x 32 output pixels x BN couts (64 | 32); 8 waves, wave w owns rows 2w, 2w+1 and all couts; waves whose
 //            rows lie below the map only issue DMAs and take part in the barriers.
+//   columns = VIRTUAL columns of a group of p.pack_g images (column packing, conv_common.h): the CPW - (CTW + kw - 1) spare pixels
+//            of a patch row take the pw zero columns between two images of a tile.
 //   weights are packed [chunk16][dx][dy][Np][16] by the compiler (F_COL) + 3 zero stages for the look-ahead.
 //   K order of the fp32 accumulation: chunk-major, then column-major taps — one K slice of 16 per MFMA, sequential.
 #include "conv_common.h"
@@ -62,11 +64,13 @@ __global__ __launch_bounds__(512, 2) void conv_col_kernel(const ConvParams p) {
     const int nt = t % p.ntn;  t /= p.ntn;
     const int tx = t % p.tiles_w;  t /= p.tiles_w;
     const int ty = t % p.tiles_h;
-    const long img = t / p.tiles_h;
+    // column packing (conv_common.h): ox0 is a VIRTUAL column of the block's image group; one image per group when pack_g == 1
     const int oy0 = ty * CTH, ox0 = tx * CTW, n0 = nt * BN;
-    if (conv_tile_right_of_sample<CTH, CTW>(p, img, oy0, ox0, n0, BN)) return;    // ragged batch: nothing to compute here
-
     const int kw = p.kw;
+    const ConvPackTile pk = conv_pack_tile(p, (int)(t / p.tiles_h), ox0, CTW, kw);
+    if (ox0 >= pk.vw) return;                            // a short last group: no live image under this tile
+    if (conv_tile_right_of_sample<CTH, CTW>(p, pk.img0, oy0, ox0, n0, BN)) return;    // ragged batch (never packed): nothing to compute here
+
     const int nch1 = p.cinp >> 4;
     const int nchunks = (p.flags & F_HILO) ? 2 * nch1 : nch1;      // F_HILO: second pass over the patch chunks with the lo weights
 
@@ -79,9 +83,10 @@ __global__ __launch_bounds__(512, 2) void conv_col_kernel(const ConvParams p) {
         const int q = 32 * (wave + 8 * j) + (lane >> 1);
         const int kh_ = (lane & 1) ^ ((q >> 3) & 1);               // logical k half stored in this lane's slot
         const int py = q / CPW, px = q - py * CPW;
-        const int iy = oy0 - p.ph + py, ix = ox0 - p.pw + px;
-        pok[j] = (q < PPIX) && (px < CTW + kw - 1) && (iy >= 0) && (iy < p.H) && (ix >= 0) && (ix < p.W);
-        poff[j] = ((img * p.Hs + (iy >> p.inshift)) * p.Ws + (ix >> p.inshift)) * (long)p.in_ld + kh_ * 8;
+        const int iy = oy0 - p.ph + py;
+        int g, ix;
+        pok[j] = conv_pack_src(p, pk, px, g, ix) && (q < PPIX) && (iy >= 0) && (iy < p.H);
+        poff[j] = (((pk.img0 + g) * p.Hs + (iy >> p.inshift)) * p.Ws + (ix >> p.inshift)) * (long)p.in_ld + kh_ * 8;
     }
     // weights: instruction i covers stage rows 32i .. 32i+31 (row = dy * BN + r)
     const half_t* wptr[WNPL];
@@ -126,8 +131,9 @@ __global__ __launch_bounds__(512, 2) void conv_col_kernel(const ConvParams p) {
         woffb[j] = (unsigned)(2 * PATCH_BYTES + r * 32 + ((fj ^ ((r >> 3) & 1)) << 4));
     }
     const unsigned xrow0 = (unsigned)(2 * wave * ROWB);
+    const unsigned fcol = (unsigned)conv_pack_fragcol(p, pk, ox0, ox0 + fx);      // = fx + one gap per seam left of the lane
     auto xcol = [&](int dx, int buf) -> unsigned {       // byte address of the wave's row-0 fragment under column dx
-        const unsigned c = (unsigned)(fx + dx);
+        const unsigned c = fcol + (unsigned)dx;
         return (unsigned)buf * PATCH_BYTES + xrow0 + c * 32 + ((fj ^ ((c >> 3) & 1)) << 4);
     };
     const char* const ldsb = reinterpret_cast<const char*>(lds);
@@ -237,8 +243,10 @@ __global__ __launch_bounds__(512, 2) void conv_col_kernel(const ConvParams p) {
     // ---- epilogue (one wave = all couts of its 64 pixels) -----------------------------------------------------------------
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        const int oy = oy0 + 2 * wave + i, ox = ox0 + fx;
-        if (oy >= p.OH || ox >= p.OW) continue;
+        const int oy = oy0 + 2 * wave + i, v = ox0 + fx;
+        if (oy >= p.OH || v >= pk.vw) continue;
+        const int g = (int)__umulhi((unsigned)v, p.pack_mag_ow), ox = v - g * p.OW;
+        const long img = pk.img0 + g;
         const long m = (img * p.OH + oy) * p.OW + ox;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
@@ -255,8 +263,8 @@ int launch_conv_col(const ConvParams& pin, const ConvKernel& k, hipStream_t st) 
     const int kh = k.arg[0], bn = k.arg[1];
     p.ntn = (unsigned)((p.Np + bn - 1) / bn);
     p.tiles_h = (p.OH + CTH - 1) / CTH;
-    p.tiles_w = (p.OW + CTW - 1) / CTW;
-    const unsigned long long blocks = (unsigned long long)conv_images(p) * p.tiles_h * p.tiles_w * p.ntn;
+    conv_pack_plan(p, CTW, CPW - (CTW + p.kw - 1));      // the patch rows are CPW pixels apart, CTW + kw - 1 are read
+    const unsigned long long blocks = (unsigned long long)((p.nimg + p.pack_g - 1) / p.pack_g) * p.tiles_h * p.tiles_w * p.ntn;
     if (blocks == 0 || blocks > 0x7fffffffull) return VSE_E_INVAL;
     const dim3 grid((unsigned)blocks), block(512);
     if (kh == 9 && bn == 64) hipLaunchKernelGGL((conv_col_kernel<9, 64>), grid, block, 0, st, p);

@@ -53,6 +53,10 @@ struct ConvParams {
     const uint8_t* u8src;   // F_U8SRC (stem): uint8 BGR frames [n][u8_h][u8_w][3], row pitch / frame stride in bytes
     int u8_h, u8_w;
     long u8_pitch, u8_fstride;
+    // conv_c3_kernel / conv_col_kernel: pack_g images of the batch share one virtual row band of pack_g * OW output columns that the
+    // tiles cover densely (conv_pack_group); 1 = every image is tiled on its own.  Set by the launchers.
+    int pack_g, nimg;                    // images per group, images of the launch
+    unsigned pack_mag_ow, pack_mag_d;    // conv_pack_magic(OW), conv_pack_magic(W + pw); 0 when pack_g == 1 (every quotient is 0)
 };
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
@@ -281,6 +285,49 @@ __device__ __forceinline__ bool conv_tile_right_of_sample(const ConvParams& p, l
     return true;
 }
 
+// Column packing (conv_c3_kernel, conv_col_kernel).  A map whose width is not a multiple of the tile width leaves the last column tile of
+// every row band partly empty, and a 32-lane fragment cannot be shortened: the detector's 240 / 120 / 60-wide maps cost 1/16 more
+// MFMAs than their outputs need.  So G images form one VIRTUAL row band: output column v = g * OW + ox (g = image of the group), tiled
+// by the same TW-wide tiles.  The input rows of the group are pictured as one AUGMENTED row: pw zero columns in front of every image,
+//     n = g * (W + pw) + pw + ix        (ix = the image's own column; n % (W + pw) < pw is a gap),
+// one shared gap between neighbours being enough, since pw is the conv's horizontal padding.  A tile's LDS patch is a plain window
+// of that row starting at n0 = ox0 + pw * (ox0 / OW), and the lane that owns output column v reads patch columns
+//     (v - ox0) + pw * (v / OW - ox0 / OW) + dx:
+// every seam between ox0 and v shifts it by one gap.  Each output pixel sees the values and the K order it sees unpacked.
+// The quotients are taken with a multiply-high: conv_pack_magic(d) is exact for dividends < 2^16 and d <= 2^16 (conv_pack_group
+// refuses larger maps).
+static inline unsigned conv_pack_magic(unsigned d) { return (unsigned)(0x100000000ull / d + 1); }
+struct ConvPackTile {
+    long img0;          // first image of the block's group
+    int vw;             // live virtual columns of the group (a short last group has fewer than pack_g * OW)
+    int vlast;          // last live virtual column of the tile
+    int g0;             // image (of the group) of the tile's first column
+    int n0;             // augmented column of patch column 0
+    int used;           // patch columns the tile's fragments read
+};
+// grp = the block's image group, ox0 = first virtual column of its tile, TW = tile width, KW = filter width.  Block-uniform.
+__device__ __forceinline__ ConvPackTile conv_pack_tile(const ConvParams& p, int grp, int ox0, int TW, int KW) {
+    ConvPackTile t;
+    t.img0 = (long)grp * p.pack_g;
+    t.vw = min(p.pack_g, p.nimg - grp * p.pack_g) * p.OW;
+    t.vlast = min(ox0 + TW, t.vw) - 1;
+    t.g0 = (int)__umulhi((unsigned)ox0, p.pack_mag_ow);
+    t.n0 = ox0 + p.pw * t.g0;
+    t.used = TW + KW - 1 + p.pw * ((int)__umulhi((unsigned)max(t.vlast, 0), p.pack_mag_ow) - t.g0);
+    return t;
+}
+// Patch column px of the tile -> (image of the group, input column); false: a gap or outside the group's live images
+__device__ __forceinline__ bool conv_pack_src(const ConvParams& p, const ConvPackTile& t, int px, int& g, int& ix) {
+    const unsigned n = (unsigned)(t.n0 + px);
+    g = (int)__umulhi(n, p.pack_mag_d);
+    ix = (int)n - g * (p.W + p.pw) - p.pw;
+    return px < t.used && ix >= 0 && ix < p.W && (long)g * p.OW < t.vw;
+}
+// Fragment column of the lane that owns virtual output column v (lanes right of the tile's live columns read what the last one reads)
+__device__ __forceinline__ int conv_pack_fragcol(const ConvParams& p, const ConvPackTile& t, int ox0, int v) {
+    return v - ox0 + p.pw * ((int)__umulhi((unsigned)max(min(v, t.vlast), 0), p.pack_mag_ow) - t.g0);
+}
+
 // F_DOT1 variant: returns this lane's partial  sum_c y[c] * dotw[c]  over the couts it owns in one accumulator tile
 // (y = the full epilogue value); nothing is stored.  Padded couts carry zero weights.
 __device__ __forceinline__ float conv_epilogue_dot(const ConvParams& p, const float16v& acc, const float (&bias)[16],
@@ -350,6 +397,12 @@ int launch_conv(const vse_op& o, const TView& in, const TView& res, const TView&
                 const char* wts, const half_t* zero, const int* wl_out, const uint8_t* u8src, const SrcGeom& src, hipStream_t st);
 // images of a launch (M = images x OH x OW)
 static inline long conv_images(const ConvParams& p) { return p.OH && p.OW ? p.M / ((long)p.OH * p.OW) : 0; }
+// Images per virtual row band for TW-wide tiles whose patch has `spare` unused columns and a `gap` of zero columns between images:
+// G from {1, 2, 4, 8, 16} (<= images) with the fewest live tiles, the smaller G on ties; a G whose worst tile holds more seams than
+// the spare columns take is left out.  1 when OW is a multiple of TW already.
+int conv_pack_group(long images, int OW, int TW, int spare, int gap);
+// fills p.pack_*, p.nimg and p.tiles_w for TW-wide tiles; `spare` as above.  Ragged plans and convs that change the width stay unpacked.
+void conv_pack_plan(ConvParams& p, int TW, int spare);
 
 // The family launchers: map the choice to its instantiation, compute the grid, check what only a launch can (pointers, alignment)
 int launch_conv_gemm(const ConvParams& p, const ConvKernel& k, hipStream_t st);      // scalar-addressed implicit GEMM (conv_gemm.hip)

@@ -125,6 +125,34 @@ static bool conv_c3_ok(int kh, int kw, int sh, int sw, int ph, int pw, int cinp,
            && !(flags & (F_SRC2 | F_PIXSHUF | F_DOT1));
 }
 
+// Column packing of conv_c3_kernel / conv_col_kernel (conv_common.h)
+int conv_pack_group(long images, int OW, int TW, int spare, int gap) {
+    if (OW <= 0 || OW % TW == 0 || images < 2 || spare < 0) return 1;
+    if (16L * (OW + gap) + TW + 64 >= 65536) return 1;                      // conv_pack_magic: dividends < 2^16
+    auto tiles = [&](long cols) { return (cols + TW - 1) / TW; };
+    long best = images * tiles(OW);
+    int bg = 1;
+    for (int G = 2; G <= 16 && G <= images; G *= 2) {
+        int seams = 0;                                                      // worst tile of a full group
+        for (long x0 = 0; x0 < (long)G * OW; x0 += TW) {
+            const long x1 = (x0 + TW < (long)G * OW ? x0 + TW : (long)G * OW) - 1;
+            seams = (int)(x1 / OW - x0 / OW) > seams ? (int)(x1 / OW - x0 / OW) : seams;
+        }
+        if (seams * gap > spare) continue;
+        const long cost = images / G * tiles((long)G * OW) + tiles(images % G * OW);      // live tiles: those of a short last group's empty
+        if (cost < best) { best = cost; bg = G; }                                        // columns return at once
+    }
+    return bg;
+}
+void conv_pack_plan(ConvParams& p, int TW, int spare) {
+    p.nimg = (int)conv_images(p);
+    const bool same_w = p.sw == 1 && p.OW == p.W && p.kw == 2 * p.pw + 1;
+    p.pack_g = (p.wl_out != nullptr || !same_w) ? 1 : conv_pack_group(p.nimg, p.OW, TW, spare, p.pw);
+    p.pack_mag_ow = p.pack_g > 1 ? conv_pack_magic((unsigned)p.OW) : 0u;
+    p.pack_mag_d = p.pack_g > 1 ? conv_pack_magic((unsigned)(p.W + p.pw)) : 0u;
+    p.tiles_w = (int)(((long)p.pack_g * p.OW + TW - 1) / TW);
+}
+
 static bool conv_pw_ok(int kh, int kw, int sh, int sw, int ph, int pw, int cinp, int Np, int inshift, int flags) {
     return kh == 1 && kw == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0 && inshift == 0 && (cinp & 7) == 0
            && cinp <= ((flags & F_HILO) ? 96 : 64)      // (hi + lo nets: a 48-channel PAIR tensor is 96 input channels — round 5)
