@@ -125,13 +125,15 @@ int vse_graph_launch(vse_graph* graph, void* stream);
 void vse_graph_destroy(vse_graph* graph);
 
 /* Per-op timing of one run with HIP events on `stream` (synchronises); ms[n_ops] filled.  d_widths as for
- * vse_plan_run_ragged (NULL for an ordinary plan). */
+ * vse_plan_run_ragged (NULL for an ordinary plan).  Where the plan runs a 3x3 conv and the max-pool record behind it as one
+ * kernel (conv_c3pool_kernel), the launch's time is the conv record's and the pool record reports exactly 0. */
 int vse_plan_profile(vse_plan* plan, void* ws, void* const* ext, int n_ext, const int32_t* d_widths, void* stream, float* ms);
 
 /* Which kernel instantiation a record launches, as the name rocprofv3 reports ("conv_c3_kernel<4, 2>",
  * "conv_gemm_kernel<256, 256, 4, 4, 64, 2, 0>", "dwconv_kernel" ...): lets bench.py attribute the time vse_plan_profile
  * measures to the kernels of the committed rocprof summaries.  Needs no plan, context or GPU; a conv record the library
- * would refuse reads "(refused: <code>)".  The string is thread-local and valid until the next call. */
+ * would refuse reads "(refused: <code>)".  The string is thread-local and valid until the next call.  A record is named on
+ * its own: a conv that a plan fuses with the pool behind it (see vse_plan_profile) is named as the unfused conv here. */
 const char* vse_op_kernel_name(const vse_op* op);
 
 /* ---- det pre-processing ----------------------------------------------------------------------------- */

@@ -2,6 +2,7 @@
 """Single-layer timing of the conv kernels on the GPU, per kernel family the compiler may route a layer to.
 
 usage: python tools/bench_conv.py [--cfgs d,p,c] [--layers name,name...]
+       python tools/bench_conv.py --pool [--layers name,name...]     (3x3 layers: conv + 3x3 / s2 max-pool, fused against the two launches)
   d: implicit GEMM only (conv_gemm_kernel, the launcher's tile configuration)
   p: + conv_patch_kernel / conv_col_kernel
   c: + conv_c3_kernel for any couts
@@ -86,7 +87,51 @@ def graph(cin, cout, k, s, p):
     return desc, wts
 
 
+def pool_graph(cin, cout, second_reader):
+    """lift -> 3x3 conv + bias + relu (t3) -> p = 3x3 / s2 / p1 max-pool, fetched; q = the same pool of the lifted input keeps that tensor alive
+    behind the conv (else the compiler lays p over it and the pair cannot run as one kernel).  second_reader: t3 is fetched too, which
+    keeps the plan from fusing: the same conv and pool as two launches."""
+    desc, wts = graph(cin, cout, (3, 3), (1, 1), (1, 1))
+    pool = {"pooling_type": "max", "ksize": [3, 3], "strides": [2, 2], "paddings": [1, 1], "ceil_mode": False, "exclusive": True,
+            "adaptive": False, "global_pooling": False, "padding_algorithm": "EXPLICIT"}
+    desc["ops"] = desc["ops"][:-1] + [
+        {"type": "pool2d", "in": {"X": ["t3"]}, "out": {"Out": ["p"]}, "attrs": dict(pool)},
+        {"type": "pool2d", "in": {"X": ["t0"]}, "out": {"Out": ["q"]}, "attrs": dict(pool)},
+        {"type": "fetch", "in": {"X": ["p"]}, "out": {"Out": ["fetch"]}, "attrs": {"col": 0}},
+        {"type": "fetch", "in": {"X": ["q"]}, "out": {"Out": ["fetch"]}, "attrs": {"col": 1}},
+        {"type": "fetch", "in": {"X": ["t3"]}, "out": {"Out": ["fetch"]}, "attrs": {"col": 2}}]
+    desc["var_shapes"].update({"t2": [-1, cout, -1, -1], "t3": [-1, cout, -1, -1], "p": [-1, cout, -1, -1], "q": [-1, cin, -1, -1]})
+    return desc, wts, (0, 1, 2) if second_reader else (0, 1)
+
+
+def pool_main(names):
+    """conv + max-pool as one kernel (conv_c3pool_kernel, where the plan fuses the pair) against conv and pool_kernel as two launches."""
+    ctx = engine.Context(0)
+    for name in names:
+        cin, cout, k, s, p, h, w, n = LAYERS[name]
+        if (k, s, p) != ((3, 3), (1, 1), (1, 1)):
+            continue
+        x = (torch.rand((n, h, w, 8), device="cuda") * 2 - 1).half()
+        x[..., 3:] = 0
+        row = []
+        for second_reader in (True, False):
+            desc, wts, cols = pool_graph(cin, cout, second_reader)
+            net = engine.Net(ctx, desc, wts, fetch_cols=cols)
+            net.run(x)
+            torch.cuda.synchronize()
+            best = (1e9, 0.0, 0.0, "")
+            for _ in range(5):
+                ms, prog, var = net.profile(x)
+                best = min(best, (float(ms[1] + ms[2]), float(ms[1]), float(ms[2]), var[1]))
+            row.append(f"{best[3]}: {best[1]:.3f} + pool {best[2]:.3f} = {best[0]:.3f} ms")
+            del net
+            torch.cuda.empty_cache()
+        print(f"{name:20s} " + " | ".join(row), flush=True)
+
+
 def main():
+    if "--pool" in sys.argv:
+        return pool_main(sys.argv[sys.argv.index("--layers") + 1].split(",") if "--layers" in sys.argv else ["det_3x3_64_128"])
     cfgs = sys.argv[sys.argv.index("--cfgs") + 1].split(",") if "--cfgs" in sys.argv else ["d"]
     if not set(cfgs) <= {"d", "p", "c"}:
         sys.exit(f"unknown --cfgs {cfgs}: d, p, c")

@@ -57,6 +57,8 @@ struct ConvParams {
     // tiles cover densely (conv_pack_group); 1 = every image is tiled on its own.  Set by the launchers.
     int pack_g, nimg;                    // images per group, images of the launch
     unsigned pack_mag_ow, pack_mag_d;    // conv_pack_magic(OW), conv_pack_magic(W + pw); 0 when pack_g == 1 (every quotient is 0)
+    // conv_c3pool_kernel: a block walks pool_seg tile rows of one column strip, pool_nseg strips cover the map's tiles_h.  Set by the launcher.
+    int pool_seg, pool_nseg;
 };
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
@@ -360,7 +362,8 @@ __device__ __forceinline__ float conv_epilogue_dot(const ConvParams& p, const fl
 //   CK_DWPW    KS, LO, S (0 = tile form)     conv_dwpw_kernel<KS, 3, LO> / conv_dwpw_rows_kernel<KS, LO, S>
 //   CK_HEAD    resident                      conv_head_up2r_kernel / conv_head_up2_kernel
 //   CK_STEM    S, HILO, U8                   conv_stem_kernel<S, S, HILO, U8>
-enum { CK_NONE = 0, CK_GEMM, CK_SMALLM, CK_MFMA, CK_PATCH, CK_COL, CK_C3, CK_PW, CK_DWPW, CK_HEAD, CK_STEM };
+//   CK_C3POOL  BN                            conv_c3pool_kernel<BN>      (a conv record + the max-pool record behind it: conv_pool_select)
+enum { CK_NONE = 0, CK_GEMM, CK_SMALLM, CK_MFMA, CK_PATCH, CK_COL, CK_C3, CK_PW, CK_DWPW, CK_HEAD, CK_STEM, CK_C3POOL };
 struct ConvKernel {
     int family;     // CK_NONE: refused before any launcher
     int rc;         // != VSE_OK: refused with this code (a CK_PW refusal is reported by its launcher, after the launcher's own checks)
@@ -395,6 +398,13 @@ ConvKernel conv_select(const ConvParams& p, int Kp);       // Kp = the record's 
 int conv_kernel_name(const ConvKernel& k, char* buf, size_t n);
 int launch_conv(const vse_op& o, const TView& in, const TView& res, const TView& in2, const TView& out, const TView& dot_out,
                 const char* wts, const half_t* zero, const int* wl_out, const uint8_t* u8src, const SrcGeom& src, hipStream_t st);
+// A 3x3 conv whose only reader is the 3x3 / stride-2 max-pool record behind it runs with that pool as ONE kernel (conv_c3pool.hip): the
+// conv's output tensor is then never written.  conv_pool_select() answers from the plan's records alone whether ops[i], ops[i + 1] are
+// such a pair (family CK_C3POOL, else CK_NONE); vse_plan_create asks once per plan, launch_conv_pool() launches the answer with the
+// conv's input view and the POOL's output view.
+ConvKernel conv_pool_select(const vse_op* ops, int n_ops, int i);
+int launch_conv_pool(const vse_op& conv, const ConvKernel& k, const TView& in, const TView& pool_out, const char* wts, const half_t* zero,
+                     hipStream_t st);
 // images of a launch (M = images x OH x OW)
 static inline long conv_images(const ConvParams& p) { return p.OH && p.OW ? p.M / ((long)p.OH * p.OW) : 0; }
 // Images per virtual row band for TW-wide tiles whose patch has `spare` unused columns and a `gap` of zero columns between images:
@@ -413,6 +423,8 @@ int launch_conv_patch(const ConvParams& p, const ConvKernel& k, hipStream_t st);
 int launch_conv_col(const ConvParams& p, const ConvKernel& k, hipStream_t st);
 // 3x3 sibling, two blocks per CU (conv_c3.hip, F_COL with kh = kw = 3)
 int launch_conv_c3(const ConvParams& p, const ConvKernel& k, hipStream_t st);
+// 3x3 conv + 3x3 / stride-2 max-pool in one kernel (conv_c3pool.hip): p.out / p.out_ld = the pool's output view
+int launch_conv_c3pool(const ConvParams& p, const ConvKernel& k, hipStream_t st);
 // pointwise conv over <= 64 input channels and <= 256 couts, no LDS staging (conv_pw.hip, F_PW)
 int launch_conv_pw(const ConvParams& p, const ConvKernel& k, hipStream_t st);
 // depthwise k x k conv fused in front of a 1x1 conv (conv_dwpw.hip, F_DWPRE): p.kh / sh / ph = the depthwise geometry, p.dotw = its table

@@ -324,8 +324,72 @@ int conv_kernel_name(const ConvKernel& k, char* buf, size_t n) {
                         : snprintf(buf, n, "conv_dwpw_kernel<%d, 3, %s>", a[0], tf[a[1]]);
         case CK_HEAD: return snprintf(buf, n, a[0] ? "conv_head_up2r_kernel" : "conv_head_up2_kernel");
         case CK_STEM: return snprintf(buf, n, "conv_stem_kernel<%d, %d, %s, %s>", a[0], a[0], tf[a[1]], tf[a[2]]);
+        case CK_C3POOL: return snprintf(buf, n, "conv_c3pool_kernel<%d>", a[0]);
         default: return snprintf(buf, n, "?");
     }
+}
+
+// ---- conv + max-pool pairs that run as one kernel ------------------------------------------------------------------------------
+
+// byte range [lo, hi) a view spans in its arena (channel slices of one buffer count as overlapping: conservative)
+static void view_span(const vse_view& v, int64_t* lo, int64_t* hi) {
+    *lo = v.off;
+    *hi = v.off + (((int64_t)v.n * v.h * v.w - 1) * v.ld + v.c) * v.esize;
+}
+static bool views_overlap(const vse_view& a, const vse_view& b) {
+    if (a.n == 0 || b.n == 0 || a.arena != b.arena) return false;
+    int64_t a0, a1, b0, b1;
+    view_span(a, &a0, &a1);
+    view_span(b, &b0, &b1);
+    return a0 < b1 && b0 < a1;
+}
+static bool same_view(const vse_view& a, const vse_view& b) {
+    return a.off == b.off && a.arena == b.arena && a.n == b.n && a.h == b.h && a.w == b.w && a.c == b.c && a.ld == b.ld && a.esize == b.esize;
+}
+
+// ops[i] = a 3x3 / stride-1 / pad-1 conv of conv_patch_kernel's LIGHT family with a plain epilogue (bias / BN / activation), ops[i + 1] = a
+// 3x3 / stride-2 / pad-1 max-pool whose one input is exactly the conv's output view, neither of them ragged; and the conv's output is DEAD
+// behind the pool: fused, that tensor is never written, so walking the later records, the first one that touches its bytes must write them
+// without reading them (or none touches them).  The fused kernel reads the conv's input while it writes the pool's output, which the
+// unfused pair never does at the same time: those two views must not share bytes either.
+ConvKernel conv_pool_select(const vse_op* ops, int n_ops, int i) {
+    const ConvKernel no{CK_NONE, VSE_OK, {0, 0, 0}};
+    if (!ops || i < 0 || i + 1 >= n_ops) return no;
+    const vse_op &c = ops[i], &q = ops[i + 1];
+    if (c.kind != OP_CONV || q.kind != OP_POOL) return no;
+    if (c.flags != F_PATCH || c.p[P_KH] != 3 || c.p[P_KW] != 3 || c.p[P_SH] != 1 || c.p[P_SW] != 1 || c.p[P_PH] != 1 || c.p[P_PW] != 1) return no;
+    if (c.p[P_INSHIFT] || c.p[P_LO_OUT] || c.p[P_WLIN] || c.p[P_WLOUT] || q.p[P_WLIN] || q.p[P_WLOUT]) return no;
+    if (c.in1.n || c.in2.n || c.out2.n || q.in1.n || q.in2.n || q.out2.n) return no;
+    if (!q.p[P_POOL_MAX] || q.p[P_KH] != 3 || q.p[P_KW] != 3 || q.p[P_SH] != 2 || q.p[P_SW] != 2 || q.p[P_PH] != 1 || q.p[P_PW] != 1) return no;
+    if (c.out.arena != 0 || c.out.esize != 2 || c.in0.esize != 2 || !same_view(c.out, q.in0)) return no;
+    if (c.out.n != c.in0.n || c.out.h != c.in0.h || c.out.w != c.in0.w || c.out.c != c.p[P_COUT] || (c.p[P_COUT] & 7)) return no;
+    if (q.out.esize != 2 || q.out.n != c.out.n || q.out.h != (c.out.h - 1) / 2 + 1 || q.out.w != (c.out.w - 1) / 2 + 1 || q.out.c != c.out.c ||
+        (q.out.ld & 7) || (q.out.off & 15))
+        return no;
+    if (views_overlap(c.in0, q.out) || views_overlap(c.out, q.out) || views_overlap(c.out, c.in0)) return no;
+    int th, bn, mode;
+    conv_patch_plan(3, 3, c.out.h, c.p[P_COUT], c.flags, &th, &bn, &mode);
+    if (mode != 2) return no;
+    for (int j = i + 2; j < n_ops; ++j) {
+        const vse_op& o = ops[j];
+        // (in2 and out2 carry an output of some kinds and an input of others: whichever, touching the tensor there counts as reading it)
+        if (views_overlap(o.in0, c.out) || views_overlap(o.in1, c.out) || views_overlap(o.in2, c.out) || views_overlap(o.out2, c.out)) return no;
+        if (views_overlap(o.out, c.out)) break;
+    }
+    return ConvKernel{CK_C3POOL, VSE_OK, {bn, 0, 0}};
+}
+
+int launch_conv_pool(const vse_op& conv, const ConvKernel& k, const TView& in, const TView& pool_out, const char* wts, const half_t* zero,
+                     hipStream_t st) {
+    if (k.family != CK_C3POOL || !in.ptr || !pool_out.ptr || !zero) return VSE_E_INVAL;
+    const TView none{nullptr, 0, 0, 0, 0, 0, 0};
+    // the conv's own output view is only a shape here: the kernel stores through the pool's
+    const TView shape{nullptr, conv.out.n, conv.out.h, conv.out.w, conv.out.c, conv.out.ld, conv.out.esize};
+    ConvParams p = conv_params(conv, in, none, none, shape, none, wts, zero, nullptr, nullptr, SrcGeom{0, 0, 0, 0});
+    if (in.c != p.cinp || (in.ld & 7)) return VSE_E_INVAL;
+    p.out = pool_out.ptr;
+    p.out_ld = pool_out.ld;
+    return launch_conv_c3pool(p, k, st);
 }
 
 // ---- launch -----------------------------------------------------------------------------------------------------------------

@@ -38,6 +38,7 @@ struct vse_plan {
     vse_ctx* ctx;
     int weights_id;
     std::vector<vse_op> ops;
+    std::vector<ConvKernel> pooled;   // per op: family CK_C3POOL = this conv runs with the max-pool record behind it as one kernel (conv_pool_select)
     size_t ws_bytes;
     int max_ext;
     int n_levels;                     // ragged plans: width levels referenced by the ops (0 = not a ragged plan)
@@ -192,6 +193,9 @@ int vse_plan_create(vse_ctx* c, int weights_id, const vse_op* ops, int n_ops, si
             }
         }
     }
+    // conv + max-pool pairs that run as one kernel: decided here, once, from the records (ragged plans stay as they are)
+    p->pooled.assign(n_ops, ConvKernel{CK_NONE, VSE_OK, {0, 0, 0}});
+    for (int i = 0; i + 1 < n_ops && !p->n_levels; ++i) p->pooled[i] = conv_pool_select(ops, n_ops, i);
     *out = p;
     return VSE_OK;
 }
@@ -218,7 +222,11 @@ static int run_op(vse_plan* p, int i, char* ws, void* const* ext, const int32_t*
                 in2 = resolve(o.in2, ws, wts, ext), out = resolve(o.out, ws, wts, ext),
                 out2 = resolve(o.out2, ws, wts, ext);
     int rc;
-    if (o.kind == OP_CONV) {
+    if (i > 0 && p->pooled[i - 1].family == CK_C3POOL) return VSE_OK;      // this pool ran inside the conv in front of it
+    if (p->pooled[i].family == CK_C3POOL) {
+        const TView pool_out = resolve(p->ops[i + 1].out, ws, wts, ext);
+        rc = launch_conv_pool(o, p->pooled[i], in0, pool_out, wts, reinterpret_cast<const half_t*>(p->ctx->zero_page), st);
+    } else if (o.kind == OP_CONV) {
         const uint8_t* u8src = (o.flags & F_U8SRC) ? reinterpret_cast<const uint8_t*>(ext[0]) : nullptr;
         rc = launch_conv(o, in0, in1, in2, out, out2, wts, reinterpret_cast<const half_t*>(p->ctx->zero_page), wl_out, u8src, src, st);
     } else if (o.kind == OP_CHAIN) {
@@ -495,6 +503,9 @@ int vse_plan_profile(vse_plan* p, void* ws, void* const* ext, int n_ext, const i
     }
     HIP_TRY(hipStreamSynchronize(st));
     for (int i = 0; i < n; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+    // a max-pool that ran inside the conv in front of it launched nothing: its time is the conv's, and it reports exactly 0
+    for (int i = 1; i < n; ++i)
+        if (p->pooled[i - 1].family == CK_C3POOL) ms[i] = 0.f;
     for (auto& e : ev) (void)hipEventDestroy(e);
     return VSE_OK;
 }

@@ -136,6 +136,18 @@ def op_kernel_names(ops):
     return [lib.vse_op_kernel_name(C.c_void_p(base + i * ops.itemsize)).decode() for i in range(len(ops))]
 
 
+def profiled_kernel_names(ops, ms):
+    """op_kernel_names for a profiled run.  A plan runs a 3x3 conv and the max-pool record behind it as ONE kernel where it may
+    (conv_pool_select, csrc/conv_select.hip); vse_plan_profile then gives the whole time to the conv and exactly 0 to the pool, and
+    here the conv is named as rocprofv3 names that launch: conv_c3pool_kernel<couts per tile of the conv's own kernel>."""
+    names = op_kernel_names(ops)
+    for i in range(1, len(names)):
+        if (int(ops[i]["kind"]) == ir.OP_POOL and int(ops[i - 1]["kind"]) == ir.OP_CONV and float(ms[i]) == 0.0
+                and names[i - 1].startswith("conv_patch_kernel<")):
+            names[i - 1] = "conv_c3pool_kernel<%s>" % names[i - 1].split(",")[1].strip()
+    return names
+
+
 def _check(rc, what):
     if rc < 0:
         raise VseError(f"{what} failed (rc={rc}): {load_library().vse_last_error().decode(errors='replace')}")
@@ -598,7 +610,7 @@ class Net:
         self.last_outs = outs
         _check(self.ctx.lib.vse_plan_profile(handle, C.c_void_p(ws.data_ptr()), ptrs, len(ptrs), None, self.ctx.stream(), ms),
                "vse_plan_profile")
-        names = op_kernel_names(prog.ops)
+        names = profiled_kernel_names(prog.ops, ms)
         return np.array(ms[:], dtype=np.float32), prog, names
 
     def rec_forward(self, x, widths=None, slot=0):
@@ -677,5 +689,5 @@ class Net:
         _check(self.ctx.lib.vse_plan_profile(handle, C.c_void_p(ws.data_ptr()), ptrs, len(ptrs),
                                              C.c_void_p(wt.data_ptr()) if wt is not None else None, self.ctx.stream(), ms),
                "vse_plan_profile")
-        variants = op_kernel_names(prog.ops)
+        variants = profiled_kernel_names(prog.ops, ms)
         return np.array(ms[:], dtype=np.float32), prog, variants
