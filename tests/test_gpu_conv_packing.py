@@ -81,7 +81,7 @@ def check_batch_equals_singles(ctx, desc, wts, rng, n, h, w, k, packs):
 
 # cin, cout, k, h, w, n, packs (the conv runs on a column kernel AND conv_pack_group puts several images into a group).
 # The heights steer conv_c3_plan: 31 rows take 16 x 32 tiles, 39 rows 8 x 64, 33-35 rows 4 x 128 at these widths.
-# Widths 33 and 70 tile too badly for the compiler to send them to a column kernel (c3_tile_eff / COL_MIN_TILE_EFF judge the map
+# Widths 33 and 70 tile too badly for the compiler to send them to a column kernel (conv_route.c3_tile_eff / RouteLimits.col_min_tile_eff judge the map
 # unpacked), and 31 columns on 32-wide tiles leave nothing to gain: those cases check that the batch still equals its images.
 # Tiles with several seams need maps narrower than half a tile, which the same routing keeps off these kernels.
 CASES = [

@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from vse_amd import engine
+from vse_amd.conv_route import RouteLimits
 
 LAYERS = {  # name: cin, cout, k, stride, pad, h, w, n
     "det_1x1_896_256": (896, 256, (1, 1), (1, 1), (0, 0), 136, 240, 64),
@@ -87,6 +88,14 @@ def graph(cin, cout, k, s, p):
     return desc, wts
 
 
+def cfg_limits(c):
+    """The routing thresholds of --cfgs letter c."""
+    return RouteLimits(patch_min_k={"d": 1 << 30, "p": 500, "c": 100}[c],
+                       patch_max_cout=256 if c == "p" else 64,       # "p": also try the patch kernel on wide layers (two+ cout tiles)
+                       col3_max_cout=4096 if c == "c" else 0,        # 0: no layer (coutp >= 8) goes to conv_c3_kernel
+                       col3_min_tile_eff=0.0, col3_wide_min_cin=0, col3_min_k=100)
+
+
 def pool_graph(cin, cout, second_reader):
     """lift -> 3x3 conv + bias + relu (t3) -> p = 3x3 / s2 / p1 max-pool, fetched; q = the same pool of the lifted input keeps that tensor alive
     behind the conv (else the compiler lays p over it and the pair cannot run as one kernel).  second_reader: t3 is fetched too, which
@@ -140,12 +149,7 @@ def main():
     for name in names:
         cin, cout, k, s, p, h, w, n = LAYERS[name]
         desc, wts = graph(cin, cout, k, s, p)
-        from vse_amd import compiler
-        nets = {}
-        mink = {"d": 1 << 30, "p": 500, "c": 100}
-        for key in cfgs:
-            compiler.PATCH_MIN_K = mink[key]
-            nets[key] = engine.Net(ctx, desc, wts, want_probs=False)
+        nets = {key: engine.Net(ctx, desc, wts, want_probs=False, limits=cfg_limits(key)) for key in cfgs}
         x = (torch.rand((n, h, w, 8), device="cuda") * 2 - 1).half()
         x[..., 3:] = 0
         oh = (h + 2 * p[0] - k[0]) // s[0] + 1
@@ -154,11 +158,6 @@ def main():
         row = []
         for c in cfgs:
             net = nets[c]
-            compiler.PATCH_MIN_K = mink[c]      # plans are compiled lazily on the first run
-            compiler.PATCH_MAX_COUT = 256 if c == "p" else 64       # "p": also try the patch kernel on wide layers (two+ cout tiles)
-            compiler.COL3_MAX_COUT = 4096 if c == "c" else 0         # 0: no layer (coutp >= 8) goes to conv_c3_kernel
-            compiler.COL3_MIN_TILE_EFF, compiler.COL3_WIDE_MIN_CIN = 0.0, 0
-            compiler.COL3_MIN_K = 100
             net.run(x)
             torch.cuda.synchronize()
             best = 1e9

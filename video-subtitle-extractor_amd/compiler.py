@@ -29,10 +29,7 @@ import numpy as np
 
 from . import ir
 from .chains import ChainMixin
-
-
-def rup(x, m):
-    return (x + m - 1) // m * m
+from .conv_route import RouteLimits, route_conv, rup
 
 
 # ------------------------------------------------------------------------------------------------ views
@@ -174,41 +171,16 @@ class WeightStore:
 # ------------------------------------------------------------------------------------------------ compiler
 _VIRTUAL = {"nearest_interp_v2", "flatten_contiguous_range", "transpose2", "reshape2", "squeeze2", "dropout",
             "assign", "shape", "fill_constant", "fill_constant_batch_size_like", "scale_noop"}
+_GEOM_1X1 = (1, 1, 1, 1, 0, 0)          # kh, kw, sh, sw, ph, pw of a linear layer as a conv
+_NO_EPILOGUE = dict(act=ir.ACT_NONE, act2=ir.ACT_NONE, act_a=0.0, act_b=0.0, post_a=1.0, post_b=0.0)
 _ACTS = {"relu": ir.ACT_RELU, "hard_swish": ir.ACT_HSWISH, "swish": ir.ACT_SWISH, "sigmoid": ir.ACT_SIGMOID,
          "hard_sigmoid": ir.ACT_HSIGMOID}
 
 
-# shortest K (taps x channels) worth a conv_patch_kernel launch
-PATCH_MIN_K = 500
-# most couts sent to the patch kernel: with more than 64 couts the 256-pixel implicit-GEMM tiles (conv_gemm.hip,
-# activation tile fetched once for 128-256 couts) measure 15-50 % faster than the patch kernel on MI355X
-PATCH_MAX_COUT = 64
-# smallest useful fraction of a tile grid (8/16 x 32 output pixels) for the patch kernel; below it the map is too ragged
-PATCH_MIN_TILE_EFF = 0.5
-# conv_col_kernel (one filter column per step, 9x9 / 7x7 / 5x5 layers): below this tile efficiency the 8-row tiles of
-# conv_patch_kernel win (measured: 17x30 map 0.163 vs 0.203 ms, 34x60 0.50 vs 0.43)
-COL_MIN_TILE_EFF = 0.75
-# conv_c3_kernel (3x3, two blocks per CU); cout / tile-efficiency limits from per-layer A/B runs
-COL3_MAX_COUT = 192     # per-layer A/B (tools/bench_conv.py --cfgs d,p,c): 224-cout layers tie or lose
-# conv_pw_kernel for 1x1 convs (and 2x2 s2 transposed convs) over <= 64 input channels
-PW_MAX_COUT = 64
-COL3_MIN_K = 250    # 3x3 32->32 @136x240 (K = 288): 0.180 ms on the implicit GEMM, 0.115 ms here
-COL3_WIDE_MIN_CIN = 128    # layers with more than 64 couts (two+ cout tiles refetch the patch) only from 128 input channels on
-COL3_MIN_TILE_EFF = 0.8
 # nominal sample width for the kernel selection of ragged (recogniser) plans: subtitle lines are several hundred pixels wide at
 # 48 px height; every plan of a model selects as if its maps were this wide (the choice only steers efficiency, never results
 # ACROSS plans of one process; a different value is a different set of summation orders)
 RAGGED_SEL_W = 768
-
-
-def c3_tile_eff(oh, ow):
-    """Mirror of conv_c3_plan (conv_select in csrc/conv_select.hip): best tile efficiency over the 16x32 / 8x64 / 4x128 tile shapes when waves
-    outside the map idle."""
-    def axis(n, unit, waves):
-        tile = unit * waves
-        full, rem = divmod(n, tile)
-        return full + ((0.35 + 0.65 * -(-rem // unit) / waves) if rem else 0.0)
-    return max(oh * ow / (axis(oh, 2, rw) * axis(ow, 32, 8 // rw) * 512.0) for rw in (8, 4, 2))
 
 
 class UnsupportedGraph(NotImplementedError):
@@ -262,15 +234,14 @@ def check_attrs(ops):
 
 class Compiler(ChainMixin):
     def __init__(self, desc, weights, batch, height, width, fetch_cols=(0,), want_probs=True, store=None, reuse=True, hilo=False,
-                 ragged=False, input_norm=None, fuse_preprocess=False, chain=None, tail2=True, se_lateral=True):
+                 ragged=False, input_norm=None, fuse_preprocess=False, chain=None, tail2=True, se_lateral=True, limits=None):
         """The plan options are those of compile_model."""
         self.desc = desc
         self.W = dict(weights)
         self.ops = list(desc["ops"])
         check_attrs(self.ops)
         self.hilo = bool(hilo)                # fp16 hi + lo weight pairs
-        # conv_patch_kernel has no two-pass K walk for hi + lo weights (the implicit-GEMM, stem and column kernels do)
-        self.use_patch = not self.hilo
+        self.limits = limits if limits is not None else RouteLimits()      # thresholds of the conv routing (conv_route.py)
         # ragged plans (recognisers): every sample of the batch carries its own width; see ir.P_WLIN / Program.wlevels
         self.ragged = bool(ragged)
         self.input_norm = input_norm          # (mean3, std3): the plan takes RAW resized pixels + a ones channel (fold_input_norm)
@@ -743,6 +714,17 @@ class Compiler(ChainMixin):
         self.ir_ops.append(rec)
         return rec
 
+    def emit_conv(self, name, ins, out, flags, geom, ep, coutp, ktot, cinp, w_off, b_off, inshift=0, resshift=0, p=None, f=None, aux_off=0,
+                  out2=None):
+        """An OP_CONV record: geom = (kh, kw, sh, sw, ph, pw), the activation and the scalar affines behind it from the absorbed epilogue
+        `ep`; `p` / `f`: the slots only some conv forms use (the others stay zero)."""
+        kh, kw, sh, sw, ph, pw = geom
+        return self.emit(ir.OP_CONV, name, ins, out, flags=flags,
+                         p={ir.P_KH: kh, ir.P_KW: kw, ir.P_SH: sh, ir.P_SW: sw, ir.P_PH: ph, ir.P_PW: pw, ir.P_ACT: ep["act"], ir.P_ACT2: ep["act2"],
+                            ir.P_COUT: coutp, ir.P_KTOT: ktot, ir.P_INSHIFT: inshift, ir.P_RESSHIFT: resshift, ir.P_CINP: cinp, **(p or {})},
+                         f={ir.FS_ACT_A: ep["act_a"], ir.FS_ACT_B: ep["act_b"], ir.FS_POST_A: ep["post_a"], ir.FS_POST_B: ep["post_b"], **(f or {})},
+                         w_off=w_off, b_off=b_off, aux_off=aux_off, out2=out2)
+
     def add_gmacs(self, g):
         """Algorithmic (unpadded) MACs of the op emitted last, in units of 1e9."""
         self.gmacs += g
@@ -1025,16 +1007,8 @@ class Compiler(ChainMixin):
             n_pw += 1
         return n_dw <= 1 and n_pw >= 1
 
-    @staticmethod
-    def gemm_eligible(kh, kw, ph, pw, cinp, inshift, flags):
-        """Mirror of conv_gemm_mode() (conv_select in csrc/conv_select.hip): the layer runs on conv_gemm_kernel.  The selector refuses an
-        F_WK32 op it cannot send there, so a drift between the two rules fails loudly instead of computing garbage."""
-        if inshift or (flags & (ir.F_PATCH | ir.F_DOT1 | ir.F_SRC2 | ir.F_UP2HEAD)):
-            return False
-        return cinp % 32 == 0 and kh * kw <= 31 and kh >= 2 * ph + 1 and kw >= 2 * pw
-
     def _dot1_candidate(self, name, cout):
-        """Structural half of _try_fuse_dot1 without side effects: the only consumer is a 1x1 conv to ONE channel."""
+        """Structural half of _try_fuse_dot1, without side effects: the only consumer is a 1x1 conv to ONE channel."""
         cons = self._live_consumers(name)
         if len(cons) != 1 or name in self.placement or self.ops[cons[0]]["type"] != "conv2d":
             return False
@@ -1043,20 +1017,14 @@ class Compiler(ChainMixin):
         return (tuple(self.W[op["in"]["Filter"][0]].shape) == (1, cout, 1, 1) and list(a["strides"]) == [1, 1]
                 and not any(a["paddings"]) and a.get("groups", 1) == 1)
 
-    def _try_fuse_dot1(self, name, cout, coutp):
-        """`name` (conv output after its epilogue) -> conv2d 1x1 to ONE channel (+bias, +sigmoid): fold it into the
+    def _try_fuse_dot1(self, name, cout, coutp, dims):
+        """`name` (conv output after its epilogue, dims = its n, h, w) -> conv2d 1x1 to ONE channel (+bias, +sigmoid): fold it into the
         producing conv's epilogue as a per-pixel dot product; the wide tensor is then never written to HBM."""
-        cons = self._live_consumers(name)
-        if len(cons) != 1 or name in self.placement:
+        if not self._dot1_candidate(name, cout):
             return None
-        j = cons[0]
+        j = self._live_consumers(name)[0]
         op = self.ops[j]
-        if op["type"] != "conv2d":
-            return None
-        a = op["attrs"]
         w2 = self.W[op["in"]["Filter"][0]]
-        if tuple(w2.shape) != (1, cout, 1, 1) or list(a["strides"]) != [1, 1] or any(a["paddings"]) or a.get("groups", 1) != 1:
-            return None
         done_before = set(self.done)
         ep2 = self.absorb_epilogue(op["out"]["Output"][0], j, 1, allow_res=False)
         ok = (ep2["act"] in (ir.ACT_NONE, ir.ACT_SIGMOID) and ep2["post_a"] == 1.0 and ep2["post_b"] == 0.0
@@ -1068,8 +1036,7 @@ class Compiler(ChainMixin):
         wv = np.zeros(coutp, np.float32)
         wv[:cout] = w2[0, :, 0, 0].astype(np.float64) * ep2["scale"][0]
         out_name = ep2["out_name"]
-        x = self.env_dims_tmp
-        n, h, w = x
+        n, h, w = dims
         fcons = self._live_consumers(out_name)
         if len(fcons) == 1 and self.ops[fcons[0]]["type"] == "fetch":
             ob = self.new_buf(n, h, w, 1, esize=4, ext=len(self.outputs) + 1)
@@ -1172,33 +1139,78 @@ class Compiler(ChainMixin):
         self.done.add(k)
         return dict(ep=ep2, w=w2, wname=wn)
 
+    def _conv_stream(self, r, wname, w, ep, inv):
+        """One packer per family (ConvRoute.family): the weight-store key of the layer's stream and a thunk for the array, which the store
+        calls on a miss.  `inv` is the view the kernel reads (the whole virtual concat for an F_SRC2 layer)."""
+        (kh, kw), span, hilo, wk32 = w.shape[2:], inv.span, self.hilo, r.family == "gemm_wk32"
+        ident = (wname, tuple(inv.segs), ep["out_name"])
+        mat = lambda: self.pack_conv_weights(w, ep["scale"], inv)[0]          # noqa: E731
+
+        def hlsum():       # 64 rows: [hi 32 | lo 32]
+            m = np.zeros((32, r.ktot), np.float64)
+            m[:rup(w.shape[0], 8)] = mat()[:, :r.ktot]
+            hi = m.astype(np.float16).astype(np.float64)
+            return self.col_weights(np.concatenate([hi, m - hi]), kh, kw, span, False)
+        col = (("convc",) + ident + (hilo,), lambda: self.col_weights(mat(), kh, kw, span, hilo))
+        # (the tap padding depends on the kernel variant the map size selects: part of the cache key)
+        patch = (("convp",) + ident + (r.ptaps,), lambda: self.patch_weights(mat(), kh, kw, span, r.ptaps))
+        tiles = (("conv",) + ident + (wk32, hilo), lambda: self.tile_weights(mat(), 32 if wk32 else ir.KT, hilo=hilo))
+        return {"head": (("convh",) + ident, lambda: self.head_up2_weights(mat(), span)),
+                "pw": (("convpw",) + ident + (hilo,), lambda: self.pw_weights(mat()[:, :r.ktot], hilo)),
+                "c3_hlsum": (("convc_hl",) + ident, hlsum), "c3": col, "col": col, "patch_light": patch, "patch_std": patch,
+                "stem": (("convs",) + ident + (hilo,), lambda: self.stem_weights(mat(), hilo)),
+                "gemm_wk32": tiles, "generic": tiles}[r.family]
+
+    @staticmethod
+    def _head_input(inv, oh, ow):
+        """The input is the virtual concat [1-channel full-resolution map u, x2-upsampled 64-channel map x] of the DB head (conv_route.route_conv)."""
+        if inv.parts is None:
+            return False
+        u, x = inv.parts
+        return (u.up == 0 and u.span == 8 and u.c == 1 and x.up == 1 and x.span == 64 and (oh, ow) == (x.h, x.w)
+                and oh % 2 == 0 and ow % 2 == 0)
+
+    def _out_gate(self, gname, outname, route, ep, cout, in2):
+        """An SE block with shortcut folded into this 1x1 conv (_rewrite_se_laterals): out = conv * (1 + gate[n, c]) (+ residual); the gate view.
+        The kernel evaluates (acc + bias) * (1 + gate) + residual.  The rewritten conv's output IS the SE block's output, so every affine /
+        activation absorb_epilogue folded lies BEHIND the gate in the graph: (conv * (1 + g)) * s + b — which is not (conv * s + b) * (1 + g).
+        Only the identity (and the residual add) may ride in this epilogue, and in2 must be free for the gate."""
+        gv = self.resolve(gname)
+        affine_id = bool(np.all(ep["scale"] == 1.0) and not np.any(ep["shift"]) and ep["post_a"] == 1.0 and ep["post_b"] == 0.0)
+        if (gv is None or (gv.h, gv.w) != (1, 1) or gv.c != cout or gv.segs != [(0, cout)] or gv.up or not affine_id or in2 is not None
+                or route.flags & (ir.F_PATCH | ir.F_COL | ir.F_STEM) or ep["act"] != ir.ACT_NONE or ep["act2"] != ir.ACT_NONE):
+            raise GatedConvUnsupported(f"gated conv {outname}: the gate / layer form is not supported (gate {gv and (gv.h, gv.w, gv.c, gv.segs, gv.up)}, "
+                                       f"family {route.family}, flags {route.flags:#x}, act {ep['act']}/{ep['act2']}, identity affine behind the "
+                                       f"gate: {affine_id}, in2 taken: {in2 is not None})")
+        return gv
+
     def lower_conv(self, i):
+        """Resolve the input, route the layer (conv_route.py), pack its weights for the routed family, emit the record."""
         op = self.ops[i]
         a = op["attrs"]
-        t = op["type"]
         wname = op["in"]["Filter"][0]
         w = self.W[wname]
-        inv = self.resolve(op["in"]["Input"][0])
+        inname = op["in"]["Input"][0]
+        inv = self.resolve(inname)
         assert inv is not None and inv.tag == "nchw", (i, op["in"])
         outname = op["out"]["Output"][0]
         sh, sw = a["strides"]
         pads = a["paddings"]
         ph, pw = (pads[0], pads[1]) if len(pads) == 2 else (pads[0], pads[2])
         groups = a.get("groups", 1)
-        if t == "depthwise_conv2d" or (groups > 1 and groups == w.shape[0] and w.shape[1] == 1):
+        if op["type"] == "depthwise_conv2d" or (groups > 1 and groups == w.shape[0] and w.shape[1] == 1):
             return self.lower_dwconv(i, inv, w, sh, sw, ph, pw)
         assert groups == 1, "only dense and depthwise convs occur (SURVEY App. E)"
-        if t == "conv2d_transpose":
+        if op["type"] == "conv2d_transpose":
             return self.lower_conv_transpose(i, inv, w, sh, sw, ph, pw)
         cout, cin, kh, kw = w.shape
         assert cin == inv.c, (cin, inv.c, outname)
-        pair_in = False
-        if (self.chain and (kh, kw, sh, sw, ph, pw) == (1, 1, 1, 1, 0, 0)
-                and inv.buf is not None and inv.buf.lo_off and inv.parts is None and inv.up == 0 and inv.coff == 0
-                and inv.segs == [(0, inv.c)] and op["in"]["Input"][0] not in self.pending_wgate):
+        geom = (kh, kw, sh, sw, ph, pw)
+        pair_in = (self.chain and geom == (1, 1, 1, 1, 0, 0) and inv.buf is not None and inv.buf.lo_off and inv.parts is None
+                   and inv.up == 0 and inv.coff == 0 and inv.segs == [(0, inv.c)] and inname not in self.pending_wgate)
+        if pair_in:
             # the input is an fp16 hi + lo PAIR (it also feeds an OP_CHAIN, or was stored for this conv): a 1x1 conv consumes both
             # halves with NO kernel change — the lo channels are more input channels with the same weights, W hi + W lo
-            pair_in = True
             lo_off = inv.buf.lo_off
             inv = View(inv.buf, 0, inv.n, inv.h, inv.w, [(0, inv.c), (lo_off, inv.c)], 2 * lo_off, 0, inv.tag)
             w = np.concatenate([w, w], axis=1)
@@ -1206,205 +1218,71 @@ class Compiler(ChainMixin):
         oh = (inv.h + 2 * ph - kh) // sh + 1
         ow = (inv.w + 2 * pw - kw) // sw + 1
         ep = self.absorb_epilogue(outname, i, cout, out_dims=(inv.n, oh, ow))
-        coutp, Kp = rup(cout, 8), rup(kh * kw * inv.span, ir.KT)
+        coutp = rup(cout, 8)
         bias = np.zeros(coutp, np.float32)
         bias[:cout] = ep["shift"]
         out = self.alloc_out(ep["out_name"], inv.n, oh, ow, cout, lo=self.wants_lo(ep["out_name"]))
         res = ep["res"]
-        flags = 0
-        # width the kernel selection sees: the map's own — or, in a ragged plan, the map width of a nominal sample, so that a
+        # ---- route.  The width the selection sees: the map's own — or, in a ragged plan, the map width of a nominal sample, so that a
         # layer runs on the same kernel family (same summation order) in every plan of the model
-        ow_real = ow
+        ow_sel = ow
         if self.ragged:
             if inv.buf is None:
                 raise UnsupportedGraph(f"ragged plan: conv {outname} reads a virtual concat")
-            ow = self.sel_width(self.wl_after(inv.buf.wl, kw, sw, pw), ow)
-        # k x k stride-1 convs on maps that tile well into 8x32 output patches go to the LDS-resident-patch kernel
-        pbn = 64 if rup(coutp, 64) < rup(coutp, 128) else 128          # mirrors conv_patch_th (conv_select in csrc/conv_select.hip)
-        pcap = 960 if pbn == 64 else 640
-        th = 16 if (pbn == 64 and (16 + kh - 1) * (32 + kw - 1) <= pcap and -(-oh // 16) * 16 * 100 <= -(-oh // 8) * 8 * 112) else 8
-        tile_eff = (oh * ow) / float(-(-oh // th) * th * -(-ow // 32) * 32)
-        # (one block per CU: the fixed prologue/epilogue only amortises over a long enough K loop)
-        patch_std = ((sh, sw) == (1, 1) and kh * kw >= 5 and (8 + kh - 1) * (32 + kw - 1) <= 640
-                     and tile_eff >= PATCH_MIN_TILE_EFF and kh * kw * cin >= PATCH_MIN_K and coutp <= PATCH_MAX_COUT and self.use_patch)
-        # LIGHT variant (conv_patch_plan, conv_select in csrc/conv_select.hip): 8-row tiles whose halo patch fits 352 pixels (3x3, 1xk),
-        # 64 or 128 couts per tile, two blocks per CU; not combined with the fused 1-channel projection or a virtual concat
-        tile_eff8 = (oh * ow) / float(-(-oh // 8) * 8 * -(-ow // 32) * 32)
-        light_ok = ((sh, sw) == (1, 1) and kh * kw >= 5 and (8 + kh - 1) * (32 + kw - 1) <= 352 and tile_eff8 >= PATCH_MIN_TILE_EFF
-                    and kh * kw * cin >= PATCH_MIN_K and self.use_patch and inv.parts is None
-                    and coutp <= 128)
-        # column-per-step kernel (conv_col.hip; mirrors conv_col_ok in conv_select): tall filters, <= 64 couts, 16-row tiles whose waves
-        # below the map idle (a partial tile row costs ~0.35 + 0.65 * live waves / 8 of a full one)
-        rem16 = oh % 16
-        rows16 = oh // 16 + ((0.35 + 0.65 * -(-rem16 // 2) / 8.0) if rem16 else 0.0)
-        tile_eff_col = (oh * ow) / float(rows16 * 16 * -(-ow // 32) * 32)
-        col = ((sh, sw) == (1, 1) and kh in (5, 7, 9) and 3 <= kw <= 17 and inv.span % 16 == 0 and coutp <= 64
-               and inv.parts is None and kh * kw * cin >= PATCH_MIN_K
-               and tile_eff_col >= COL_MIN_TILE_EFF and not self._dot1_candidate(ep["out_name"], cout))
-        c3 = ((sh, sw) == (1, 1) and (kh, kw, ph, pw) == (3, 3, 1, 1) and inv.span % 16 == 0 and inv.parts is None
-              and kh * kw * cin >= min(PATCH_MIN_K, COL3_MIN_K) and coutp <= COL3_MAX_COUT
-              and (coutp <= 64 or inv.span >= COL3_WIDE_MIN_CIN)
-              and inv.src_h * inv.src_w * inv.buf.ld < 2_000_000_000      # 32-bit in-image offsets (launch_conv_c3 checks the same)
-              and c3_tile_eff(oh, ow) >= COL3_MIN_TILE_EFF and not self._dot1_candidate(ep["out_name"], cout))
-        col = col or c3
-        if col:
-            patch_std = light_ok = False
-        patch = patch_std or light_ok
-        ow = ow_real
-        self.env_dims_tmp = (inv.n, oh, ow)
-        if patch:
-            flags |= ir.F_PATCH
-        if col:
-            flags |= ir.F_COL
-        in2shift = 0
-        if inv.parts is not None:
-            if patch:
-                flags |= ir.F_SRC2
-                part0, part1 = inv.parts
-                in2shift = part1.up
-                inv_main = part0
-            else:
-                inv = self.materialize(inv, outname)
-                inv_main = inv
+            ow_sel = self.sel_width(self.wl_after(inv.buf.wl, kw, sw, pw), ow)
+        facts = dict(cin=cin, cinp=inv.span, coutp=coutp, oh=oh, ow=ow_sel, hilo=self.hilo, concat=inv.parts is not None, inshift=inv.up,
+                     offsets_fit=inv.buf is not None and inv.src_h * inv.src_w * inv.buf.ld < 2_000_000_000, residual=res is not None,
+                     dot1_next=self._dot1_candidate(ep["out_name"], cout), limits=self.limits)
+        route = route_conv(*geom, **facts)
+        # ---- inputs: in0 = the tensor (the first part of a virtual concat the kernel gathers itself), in1 = the residual, in2 = the second part,
+        # the per-image weights or the output gate
+        in1 = in2 = None
+        in2shift = resshift = 0
+        if route.flags & ir.F_SRC2:      # the kernel gathers the two parts itself; any other family reads a copy of a virtual concat
+            inv_main, in2 = inv.parts
+            in2shift = in2.up
         else:
-            inv_main = inv
-        ins = [inv_main]
-        resshift = 0
+            inv = inv_main = self.materialize(inv, outname) if inv.parts is not None else inv
+        flags = 0
         if res is not None:
             assert (res.n, res.h, res.w, res.c) == (inv.n, oh, ow, cout), (outname, res, oh, ow, cout)
             assert res.segs == [(0, cout)]
             flags |= ir.F_RES
-            ins.append(res)
-            resshift = res.up
-        if flags & ir.F_SRC2:
-            while len(ins) < 2:
-                ins.append(None)
-            ins.append(inv.parts[1])
-        # (conv_patch_kernel's fused projection: one cout tile, no residual — launch_conv_patch refuses the rest)
-        dot = self._try_fuse_dot1(ep["out_name"], cout, coutp) if (patch_std and th == 16 and coutp <= pbn and res is None) else None
-        if patch:
-            # taps padded to whole kernel steps (2 taps in the LIGHT variant, else 4), channels to 32
-            light = light_ok and dot is None
-            assert light or patch_std
-            big = (not light) and th == 16 and (16 + kh - 1) * (32 + kw - 1) > 640
-            ptaps = rup(kh * kw, 2 if light else 4)
-            Kp = ptaps * rup(inv.span, 32)
-        # DB head of the PP-OCRv4 server detector: 3x3 over [1-channel full-res map, x2-upsampled 64-channel map] with
-        # the fused 1-channel projection -> evaluated on the low-res grid with folded 2x2 taps (conv_head.hip)
-        head = (dot is not None and (flags & ir.F_SRC2) and res is None and (kh, kw, ph, pw) == (3, 3, 1, 1)
-                and in2shift == 1 and inv_main.up == 0 and inv_main.span == 8 and inv_main.c == 1
-                and inv.parts[1].span == 64 and inv.span == 72 and coutp <= 64
-                and (oh, ow) == (inv.parts[1].h, inv.parts[1].w) and oh % 2 == 0 and ow % 2 == 0 and not self.hilo)
-        if head:
-            flags |= ir.F_UP2HEAD
-            Kp = 2 * 4 * 4 * 32 + 32
-            w_off = self.add_weights(("convh", wname, tuple(inv.segs), ep["out_name"]),
-                                     lambda: self.head_up2_weights(self.pack_conv_weights(w, ep["scale"], inv)[0], inv.span))
-        elif ((kh, kw, sh, sw, ph, pw) == (1, 1, 1, 1, 0, 0) and inv.parts is None and inv_main.up == 0 and dot is None
-              and inv.span % 8 == 0 and inv.span <= (96 if self.hilo else 64) and coutp <= (128 if self.hilo else PW_MAX_COUT) and flags in (0, ir.F_RES)):
-            # (hi + lo nets: the alternative is the generic kernel with K padded to 64 and walked twice — any cout count it can hold
-            # is faster here)
-            flags |= ir.F_PW | (ir.F_HILO if self.hilo else 0)
-            Kp = rup(inv.span, 16)          # weight rows are whole 16-channel K slices (zero columns behind the channels)
-            w_off = self.add_weights(("convpw", wname, tuple(inv.segs), ep["out_name"], self.hilo),
-                                     lambda: self.pw_weights(self.pack_conv_weights(w, ep["scale"], inv)[0][:, :rup(inv.span, 16)], self.hilo))
-        elif col and self.hilo and (kh, kw) == (3, 3) and coutp <= 32:
-            # the 32-cout tile of conv_c3_kernel walks K twice for a hi + lo net with half its MFMA tile empty: ONE pass over a 64-row
-            # stage [hi 32 | lo 32] instead, the two accumulator tiles added in the epilogue (F_HLSUM)
-            Kp = kh * kw * inv.span
-            flags |= ir.F_HLSUM
-
-            def pack_hl():
-                mat = np.zeros((32, Kp), np.float64)
-                m0 = self.pack_conv_weights(w, ep["scale"], inv)[0]
-                mat[:m0.shape[0]] = m0[:, :Kp]
-                hi = mat.astype(np.float16).astype(np.float64)
-                return self.col_weights(np.concatenate([hi, mat - hi]), kh, kw, inv.span, False)
-            w_off = self.add_weights(("convc_hl", wname, tuple(inv.segs), ep["out_name"]), pack_hl)
-        elif col:
-            Kp = kh * kw * inv.span
-            if self.hilo:
-                flags |= ir.F_HILO
-            w_off = self.add_weights(("convc", wname, tuple(inv.segs), ep["out_name"], self.hilo),
-                                     lambda: self.col_weights(self.pack_conv_weights(w, ep["scale"], inv)[0], kh, kw, inv.span,
-                                                              self.hilo))
-        elif patch:
-            # (the tap padding depends on the kernel variant the map size selects: part of the cache key)
-            w_off = self.add_weights(("convp", wname, tuple(inv.segs), ep["out_name"], ptaps),
-                                     lambda: self.patch_weights(self.pack_conv_weights(w, ep["scale"], inv)[0], kh, kw,
-                                                                inv.span, ptaps))
-        elif ((kh, kw, ph, pw) == (3, 3, 1, 1) and (sh, sw) in ((1, 1), (2, 2)) and inv.span == 8 and cin <= 4
-              and coutp <= 64 and inv.parts is None and inv_main.up == 0 and dot is None and flags in (0, ir.F_RES)):
-            # stem over an image-like input (conv_stem.hip)
-            flags |= ir.F_STEM | (ir.F_HILO if self.hilo else 0)
-            if self.fuse_preprocess and inv_main.buf.ext == 0:
-                flags |= ir.F_U8SRC              # the detector's pre-processing rides in the stem's patch staging (conv_stem.hip)
-                self._u8_fused = True
-            w_off = self.add_weights(("convs", wname, tuple(inv.segs), ep["out_name"], self.hilo),
-                                     lambda: self.stem_weights(self.pack_conv_weights(w, ep["scale"], inv)[0], self.hilo))
-        else:
-            # 32-deep weight tiles for conv_gemm_kernel (contiguous wave DMAs)
-            wk32 = dot is None and self.gemm_eligible(kh, kw, ph, pw, inv.span, inv_main.up, flags)
-            if wk32:
-                flags |= ir.F_WK32
-            if self.hilo:
-                flags |= ir.F_HILO
-            w_off = self.add_weights(("conv", wname, tuple(inv.segs), ep["out_name"], wk32, self.hilo),
-                                     lambda: self.tile_weights(self.pack_conv_weights(w, ep["scale"], inv)[0], 32 if wk32 else ir.KT,
-                                                               hilo=self.hilo))
-            wgate = self.pending_wgate.get(op["in"]["Input"][0])
-            if wgate is not None:
-                # the input is an SE output whose gate multiply was left to its consumers (_gate_foldable): this image's
-                # weights = W * gate (OP_WSCALE, fp16), read by conv_gemm_kernel through M tiles aligned to images (F_IMGW)
-                assert (kh, kw, sh, sw, ph, pw) == (1, 1, 1, 1, 0, 0) and dot is None and not (flags & ~(ir.F_RES | ir.F_WK32))
-                assert self.gemm_eligible(kh, kw, ph, pw, inv.span, inv_main.up, flags), outname
-                wbuf = self.new_buf(inv.n, 1, 1, Kp * coutp, esize=2)
-                wview = View(wbuf, 0, inv.n, 1, 1, [(0, Kp * coutp)], Kp * coutp)
-                self.emit(ir.OP_WSCALE, ep["out_name"] + ":wgate", [wgate], wview, p={0: Kp, 1: coutp, 2: 32 if wk32 else ir.KT},
-                          w_off=w_off)
-                flags |= ir.F_IMGW
-                while len(ins) < 2:
-                    ins.append(None)
-                ins.append(wview)
+            in1, resshift = res, res.up
+        dot = self._try_fuse_dot1(ep["out_name"], cout, coutp, (inv.n, oh, ow)) if route.may_fuse_dot1 else None
+        if dot is not None:
+            route = route_conv(*geom, **facts, dot1_fused=True, head_input=self._head_input(inv, oh, ow))
+        flags |= route.flags
+        if route.family == "stem" and self.fuse_preprocess and inv_main.buf.ext == 0:
+            flags |= ir.F_U8SRC              # the detector's pre-processing rides in the stem's patch staging (conv_stem.hip)
+            self._u8_fused = True
+        # ---- pack
+        w_off = self.add_weights(*self._conv_stream(route, wname, w, ep, inv))
+        wgate = self.pending_wgate.get(inname) if route.family in ("gemm_wk32", "generic") else None
+        if wgate is not None:
+            # the input is an SE output whose gate multiply was left to its consumers (_gate_foldable): this image's
+            # weights = W * gate (OP_WSCALE, fp16), read by conv_gemm_kernel through M tiles aligned to images (F_IMGW)
+            assert geom == (1, 1, 1, 1, 0, 0) and route.family == "gemm_wk32" and not self.hilo, (outname, route)
+            wsize = route.ktot * coutp
+            in2 = View(self.new_buf(inv.n, 1, 1, wsize, esize=2), 0, inv.n, 1, 1, [(0, wsize)], wsize)
+            self.emit(ir.OP_WSCALE, ep["out_name"] + ":wgate", [wgate], in2, p={0: route.ktot, 1: coutp, 2: 32}, w_off=w_off)
+            flags |= ir.F_IMGW
         b_off = self.add_weights(("convb", wname, ep["out_name"]), bias)
         if a.get("out_gate") is not None:
-            # an SE block with shortcut folded into this 1x1 conv (_rewrite_se_laterals): out = conv * (1 + gate[n, c]) (+ residual)
-            gv = self.resolve(a["out_gate"])
-            # The kernel evaluates (acc + bias) * (1 + gate) + residual.  The rewritten conv's output IS the SE block's output, so every
-            # affine / activation absorb_epilogue folded lies BEHIND the gate in the graph: (conv * (1 + g)) * s + b — which is not
-            # (conv * s + b) * (1 + g).  Only the identity (and the residual add) may ride in this epilogue.
-            affine_id = bool(np.all(ep["scale"] == 1.0) and not np.any(ep["shift"]) and ep["post_a"] == 1.0 and ep["post_b"] == 0.0)
-            if (gv is None or (gv.h, gv.w) != (1, 1) or gv.c != cout or gv.segs != [(0, cout)] or gv.up or dot is not None or not affine_id
-                    or flags & (ir.F_SRC2 | ir.F_IMGW | ir.F_PATCH | ir.F_COL | ir.F_STEM) or ep["act"] != ir.ACT_NONE or ep["act2"] != ir.ACT_NONE):
-                raise GatedConvUnsupported(f"gated conv {outname}: the gate / layer form is not supported (gate {gv and (gv.h, gv.w, gv.c, gv.segs, gv.up)}, "
-                                           f"flags {flags:#x}, act {ep['act']}/{ep['act2']}, identity affine behind the gate: {affine_id}, "
-                                           f"dot {dot is not None})")
+            in2 = self._out_gate(a["out_gate"], outname, route, ep, cout, in2)
             flags |= ir.F_OGATE
-            while len(ins) < 2:
-                ins.append(None)
-            ins.append(gv)
+        # ---- emit
+        ins = [inv_main, in1, in2]
         if dot is not None:
             aux_off = self.add_weights(("dot1", dot["wname"], ep["out_name"]), dot["w"])
-            self.emit(ir.OP_CONV, dot["out_name"], ins, dot["view"], flags=flags | ir.F_DOT1,
-                      p={ir.P_KH: kh, ir.P_KW: kw, ir.P_SH: sh, ir.P_SW: sw, ir.P_PH: ph, ir.P_PW: pw,
-                         ir.P_ACT: ep["act"], ir.P_ACT2: ep["act2"], ir.P_COUT: coutp, ir.P_KTOT: Kp,
-                         ir.P_INSHIFT: inv_main.up, ir.P_RESSHIFT: resshift, ir.P_CINP: inv.span, ir.P_DOTACT: dot["act"],
-                         ir.P_IN2SHIFT: in2shift},
-                      f={ir.FS_ACT_A: ep["act_a"], ir.FS_ACT_B: ep["act_b"], ir.FS_POST_A: ep["post_a"],
-                         ir.FS_POST_B: ep["post_b"], ir.FS_PRE_B: dot["b"]}, w_off=w_off, b_off=b_off,
-                      aux_off=aux_off, out2=dot["view"])
+            self.emit_conv(dot["out_name"], ins, dot["view"], flags, geom, ep, coutp, route.ktot, inv.span, w_off, b_off, inv_main.up, resshift,
+                           p={ir.P_DOTACT: dot["act"], ir.P_IN2SHIFT: in2shift}, f={ir.FS_PRE_B: dot["b"]}, aux_off=aux_off, out2=dot["view"])
             self.add_gmacs(inv.n * oh * ow * (cin * cout * kh * kw + cout) / 1e9)
             self.env[dot["out_name"]] = dot["view"]
             return
-        self.emit(ir.OP_CONV, ep["out_name"], ins, out, flags=flags,
-                  p={ir.P_KH: kh, ir.P_KW: kw, ir.P_SH: sh, ir.P_SW: sw, ir.P_PH: ph, ir.P_PW: pw,
-                     ir.P_ACT: ep["act"], ir.P_ACT2: ep["act2"], ir.P_COUT: coutp, ir.P_KTOT: Kp,
-                     ir.P_INSHIFT: inv_main.up, ir.P_RESSHIFT: resshift, ir.P_CINP: inv.span, ir.P_IN2SHIFT: in2shift,
-                     ir.P_LO_OUT: out.buf.lo_off,
-                     ir.P_LO_RES: (res.buf.lo_off if (res is not None and res.buf is not None and not res.up and res.coff == 0
-                                                      and self.chain) else 0)},
-                  f={ir.FS_ACT_A: ep["act_a"], ir.FS_ACT_B: ep["act_b"], ir.FS_POST_A: ep["post_a"],
-                     ir.FS_POST_B: ep["post_b"]}, w_off=w_off, b_off=b_off)
+        lo_res = res.buf.lo_off if (res is not None and res.buf is not None and not res.up and res.coff == 0 and self.chain) else 0
+        self.emit_conv(ep["out_name"], ins, out, flags, geom, ep, coutp, route.ktot, inv.span, w_off, b_off, inv_main.up, resshift,
+                       p={ir.P_IN2SHIFT: in2shift, ir.P_LO_OUT: out.buf.lo_off, ir.P_LO_RES: lo_res})
         self.add_gmacs(inv.n * oh * ow * (cin // 2 if pair_in else cin) * cout * self.merged_gmac_credit.get(wname, kh * kw) / 1e9)
         self.env[ep["out_name"]] = out
 
@@ -1487,12 +1365,8 @@ class Compiler(ChainMixin):
             w_off = self.add_weights(("convT", wname, tuple(inv.segs), ep["out_name"], self.hilo),
                                      self.tile_weights(mat, hilo=self.hilo))
         b_off = self.add_weights(("convTb", wname, ep["out_name"]), bias)
-        self.emit(ir.OP_CONV, ep["out_name"], [inv], out, flags=tflags,
-                  p={ir.P_KH: 1, ir.P_KW: 1, ir.P_SH: 1, ir.P_SW: 1, ir.P_PH: 0, ir.P_PW: 0,
-                     ir.P_ACT: ep["act"], ir.P_ACT2: 0, ir.P_COUT: 4 * coutp, ir.P_KTOT: Kp,
-                     ir.P_INSHIFT: 0, ir.P_RESSHIFT: 0, ir.P_CINP: inv.span, **tp},
-                  f={ir.FS_ACT_A: ep["act_a"], ir.FS_ACT_B: ep["act_b"], ir.FS_POST_A: ep["post_a"],
-                     ir.FS_POST_B: ep["post_b"], **tf}, w_off=w_off, b_off=b_off, aux_off=aux_off, out2=out2)
+        self.emit_conv(ep["out_name"], [inv], out, tflags, _GEOM_1X1, ep, 4 * coutp, Kp, inv.span, w_off, b_off, p={ir.P_ACT2: 0, **tp}, f=tf,
+                       aux_off=aux_off, out2=out2)
         self.add_gmacs(inv.n * inv.h * inv.w * cin * cout * 4 / 1e9)
         self.env[ep["out_name"]] = out
         if tail is not None:
@@ -1537,86 +1411,72 @@ class Compiler(ChainMixin):
         self.add_gmacs(inv.n * oh * ow * c * kh * kw / 1e9)
         self.env[ep["out_name"]] = out
 
-    def dwpw_eligible(self, i):
-        """Structural half of try_lower_dwpw, without side effects: op i is a 3x3 depthwise conv (stride 1 / 2, <= 96 channels) of a
-        hi + lo net whose only reader — behind its own BN / activation — is a plain 1x1 conv with <= 192 couts."""
+    def _match_dwpw(self, i):
+        """Op i is a 3x3 depthwise conv (stride 1 / 2, 'same' padding, <= 96 channels) of a hi + lo net whose only reader — behind its own
+        BN / activation — is a plain 1x1 conv with <= 192 couts: (stride, depthwise epilogue, index of the 1x1 conv, the ops the depthwise
+        epilogue absorbed), else None.  No side effects."""
         if not self.hilo or self.ragged or i in self.done or not self.live[i]:
-            return False
+            return None
         op = self.ops[i]
         if op["type"] not in ("conv2d", "depthwise_conv2d"):
-            return False
-        w = self.W[op["in"]["Filter"][0]]
+            return None
+        c, _, kh, kw = self.W[op["in"]["Filter"][0]].shape
+        if not self._is_dw(op, c):
+            return None
         a = op["attrs"]
-        groups = a.get("groups", 1)
-        if not (op["type"] == "depthwise_conv2d" or (groups > 1 and groups == w.shape[0] and w.shape[1] == 1)):
-            return False
-        c, _, kh, kw = w.shape
         sh, sw = a["strides"]
         pads = a["paddings"]
         ph, pw = (pads[0], pads[1]) if len(pads) == 2 else (pads[0], pads[2])
         # 3x3 only: it wins against depthwise + 1x1 launches (V4 16 -> 32 @272x480: 0.33 vs 0.44 ms); 5x5 loses (V3 64 -> 24 @68x120:
         # 0.21 vs 0.14 ms: 25 taps of fp32 VALU work per 8 channels and lane, no window sharing between neighbouring pixels)
-        if kh != kw or kh != 3 or sh != sw or sh not in (1, 2) or ph != pw or ph != kh // 2 or c % 8 or c > 96:
-            return False
+        if (kh, kw, ph, pw) != (3, 3, 1, 1) or sh != sw or sh not in (1, 2) or c % 8 or c > 96:
+            return None
         snapshot = set(self.done)
         try:
             ep_d = self.absorb_epilogue(op["out"]["Output"][0], i, c, allow_res=False)
+            absorbed = self.done - snapshot
         finally:
             self.done = snapshot
         dname = ep_d["out_name"]
         cons = self._live_consumers(dname)
         if len(cons) != 1 or dname in self.placement or dname in self.fetched_names or ep_d["act2"] != ir.ACT_NONE:
-            return False
+            return None
         o2 = self.ops[cons[0]]
         if o2["type"] != "conv2d" or o2["in"]["Input"][0] != dname or o2["attrs"].get("out_gate") is not None:
-            return False
+            return None
         w2 = self.W[o2["in"]["Filter"][0]]
         a2 = o2["attrs"]
-        return (a2.get("groups", 1) == 1 and tuple(w2.shape[1:]) == (c, 1, 1) and list(a2["strides"]) == [1, 1] and not any(a2["paddings"])
-                and rup(w2.shape[0], 8) <= 192)
+        if (a2.get("groups", 1) != 1 or tuple(w2.shape[1:]) != (c, 1, 1) or list(a2["strides"]) != [1, 1] or any(a2["paddings"])
+                or rup(w2.shape[0], 8) > 192):
+            return None
+        return sh, ep_d, cons[0], absorbed
+
+    def dwpw_eligible(self, i):
+        """Structural half of try_lower_dwpw, without side effects (chains.py asks before it lays out a chain)."""
+        return self._match_dwpw(i) is not None
 
     def try_lower_dwpw(self, i):
         """depthwise k x k conv whose only reader is a 1x1 stride-1 conv (the PP-LCNetV3 unit, the depthwise -> project half of a
         MobileNetV3 unit) in a hi + lo net -> ONE conv op (F_DWPRE, csrc/conv_dwpw.hip): the lane that needs 8 channels of a pixel as
         its MFMA B fragment COMPUTES them from the k x k neighbourhood (fp32, split into an fp16 hi + lo pair) instead of loading
         them.  The depthwise output — the widest tensor of the unit — is never written, read back or rounded."""
-        if not self.dwpw_eligible(i):
+        m = self._match_dwpw(i)
+        if m is None:
             return False
-        op = self.ops[i]
-        w = self.W[op["in"]["Filter"][0]]
-        a = op["attrs"]
-        groups = a.get("groups", 1)
-        if not (op["type"] == "depthwise_conv2d" or (op["type"] == "conv2d" and groups > 1 and groups == w.shape[0] and w.shape[1] == 1)):
-            return False
-        c, _, kh, kw = w.shape
-        sh, sw = a["strides"]
-        pads = a["paddings"]
-        ph, pw = (pads[0], pads[1]) if len(pads) == 2 else (pads[0], pads[2])
-        if kh != kw or kh not in (3, 5) or sh != sw or sh not in (1, 2) or ph != pw or c % 8 or c > 96:
-            return False
+        sh, ep_d, j, absorbed = m
+        op, o2 = self.ops[i], self.ops[j]
+        w, w2 = self.W[op["in"]["Filter"][0]], self.W[o2["in"]["Filter"][0]]
+        c, cout = w.shape[0], int(w2.shape[0])
+        kh = kw = 3
+        sw, ph, pw = sh, 1, 1
         inname = op["in"]["Input"][0]
         inv = self.resolve(inname)
         if (inv is None or inv.tag != "nchw" or inv.parts is not None or inv.up or inv.segs != [(0, inv.c)] or inv.c != c or inv.buf.esize != 2
                 or inv.coff % 8 or inname in self.pending_gate or inname in self.pending_wgate):
             return False
         snapshot = set(self.done)
-        ep_d = self.absorb_epilogue(op["out"]["Output"][0], i, c, allow_res=False)
+        self.done |= absorbed
         dname = ep_d["out_name"]
-        cons = self._live_consumers(dname)
-        ok = len(cons) == 1 and dname not in self.placement and dname not in self.fetched_names and ep_d["act2"] == ir.ACT_NONE
-        if ok:
-            o2 = self.ops[cons[0]]
-            ok = o2["type"] == "conv2d" and o2["in"]["Input"][0] == dname and o2["attrs"].get("out_gate") is None
-        if ok:
-            w2 = self.W[o2["in"]["Filter"][0]]
-            a2 = o2["attrs"]
-            ok = (a2.get("groups", 1) == 1 and tuple(w2.shape[1:]) == (c, 1, 1) and list(a2["strides"]) == [1, 1] and not any(a2["paddings"])
-                  and rup(w2.shape[0], 8) <= 192)
-        if not ok:
-            self.done = snapshot
-            return False
-        j = cons[0]
-        cout = int(w2.shape[0])
         oh = (inv.h + 2 * ph - kh) // sh + 1
         ow = (inv.w + 2 * pw - kw) // sw + 1
         ep = self.absorb_epilogue(o2["out"]["Output"][0], j, cout, out_dims=(inv.n, oh, ow))
@@ -1651,14 +1511,9 @@ class Compiler(ChainMixin):
         if res is not None:
             flags |= ir.F_RES
             ins.append(res)
-        self.emit(ir.OP_CONV, ep["out_name"], ins, out, flags=flags,
-                  p={ir.P_KH: kh, ir.P_KW: kw, ir.P_SH: sh, ir.P_SW: sw, ir.P_PH: ph, ir.P_PW: pw, ir.P_ACT: ep["act"], ir.P_ACT2: ep["act2"],
-                     ir.P_COUT: coutp, ir.P_KTOT: cp, ir.P_INSHIFT: 0, ir.P_RESSHIFT: 0, ir.P_CINP: inv.span,
-                     ir.P_LO_OUT: out.buf.lo_off,
-                     ir.P_LO_IN: inv.buf.lo_off if inv.coff == 0 else 0,
-                     ir.P_LO_RES: (res.buf.lo_off if (res is not None and res.buf is not None and res.coff == 0) else 0)},
-                  f={ir.FS_ACT_A: ep["act_a"], ir.FS_ACT_B: ep["act_b"], ir.FS_POST_A: ep["post_a"], ir.FS_POST_B: ep["post_b"]},
-                  w_off=w_off, b_off=b_off, aux_off=aux_off)
+        self.emit_conv(ep["out_name"], ins, out, flags, (kh, kw, sh, sw, ph, pw), ep, coutp, cp, inv.span, w_off, b_off, aux_off=aux_off,
+                       p={ir.P_LO_OUT: out.buf.lo_off, ir.P_LO_IN: inv.buf.lo_off if inv.coff == 0 else 0,
+                          ir.P_LO_RES: (res.buf.lo_off if (res is not None and res.buf is not None and res.coff == 0) else 0)})
         self.add_gmacs(inv.n * oh * ow * (c * k2 + c * cout) / 1e9)
         self.env[ep["out_name"]] = out
         return True
@@ -1701,12 +1556,7 @@ class Compiler(ChainMixin):
         w_off = self.add_weights(("lin", wname, tuple(x.segs), ep["out_name"]),
                                  lambda: self.tile_weights(self.pack_conv_weights(w4, ep["scale"], x)[0]))
         b_off = self.add_weights(("linb", wname, ep["out_name"]), bias)
-        self.emit(ir.OP_CONV, ep["out_name"], ins, out, flags=flags,
-                  p={ir.P_KH: 1, ir.P_KW: 1, ir.P_SH: 1, ir.P_SW: 1, ir.P_PH: 0, ir.P_PW: 0,
-                     ir.P_ACT: ep["act"], ir.P_ACT2: ep["act2"], ir.P_COUT: coutp, ir.P_KTOT: Kp,
-                     ir.P_INSHIFT: 0, ir.P_RESSHIFT: 0, ir.P_CINP: x.span},
-                  f={ir.FS_ACT_A: ep["act_a"], ir.FS_ACT_B: ep["act_b"], ir.FS_POST_A: ep["post_a"],
-                     ir.FS_POST_B: ep["post_b"]}, w_off=w_off, b_off=b_off)
+        self.emit_conv(ep["out_name"], ins, out, flags, _GEOM_1X1, ep, coutp, Kp, x.span, w_off, b_off)
         self.add_gmacs(x.n * x.h * x.w * cin * cout / 1e9)
         self.env[ep["out_name"]] = out
 
@@ -1792,15 +1642,7 @@ class Compiler(ChainMixin):
         pads = a["paddings"]
         ph, pw = (pads[0], pads[1]) if len(pads) == 2 else (pads[0], pads[2])
         ceil = bool(a.get("ceil_mode", False))
-
-        def osz(n, k, s, p):
-            if ceil:
-                o = -(-(n + 2 * p - k) // s) + 1
-                if (o - 1) * s >= n + p:
-                    o -= 1
-                return o
-            return (n + 2 * p - k) // s + 1
-        oh, ow = osz(x.h, kh, sh, ph), osz(x.w, kw, sw, pw)
+        oh, ow = level_width(x.h, kh, sh, ph, ceil), level_width(x.w, kw, sw, pw, ceil)
         x = self.need_dense(x, f"pool {name}")
         out = self.alloc_out(name, x.n, oh, ow, x.c)
         self.emit(ir.OP_POOL, name, [x], out,
@@ -2084,11 +1926,7 @@ class Compiler(ChainMixin):
                 key = f"{name}:l{layer}d{d}"
                 w_off = self.add_weights(("lstm_ih", wl[2 * c], mfma), self.tile_weights(mat))
                 b_off = self.add_weights(("lstm_b", wl[2 * c], mfma), b.astype(np.float32))
-                self.emit(ir.OP_CONV, key + ":proj", [cur], gates, flags=ir.F_OUT_F32,
-                          p={ir.P_KH: 1, ir.P_KW: 1, ir.P_SH: 1, ir.P_SW: 1, ir.P_PH: 0, ir.P_PW: 0,
-                             ir.P_ACT: 0, ir.P_ACT2: 0, ir.P_COUT: coutp, ir.P_KTOT: Kp, ir.P_INSHIFT: 0,
-                             ir.P_RESSHIFT: 0, ir.P_CINP: cur.span},
-                          f={ir.FS_POST_A: 1.0}, w_off=w_off, b_off=b_off)
+                self.emit_conv(key + ":proj", [cur], gates, ir.F_OUT_F32, _GEOM_1X1, _NO_EPILOGUE, coutp, Kp, cur.span, w_off, b_off)
                 self.add_gmacs(cur.n * cur.w * cur.c * 4 * H / 1e9)
                 if mfma:
                     gate_views.append(gates)
@@ -2238,7 +2076,7 @@ class Compiler(ChainMixin):
 
 
 def compile_model(desc, weights, batch, height, width, fetch_cols=(0,), want_probs=True, store=None, reuse=True, hilo=False,
-                  ragged=False, input_norm=None, fuse_preprocess=False, chain=None, tail2=True, se_lateral=True, fallbacks=None):
+                  ragged=False, input_norm=None, fuse_preprocess=False, chain=None, tail2=True, se_lateral=True, fallbacks=None, limits=None):
     """reuse=False gives every buffer its own workspace range (debugging: all intermediates stay readable).
     hilo=True stores every conv / depthwise / transposed-conv weight as an fp16 hi + lo pair (F_HILO): ~22-bit weights for
     twice the MFMA work — for nets whose boxes must track an fp32 reference closely.
@@ -2247,6 +2085,7 @@ def compile_model(desc, weights, batch, height, width, fetch_cols=(0,), want_pro
     input_norm=(mean3, std3): the plan takes the raw resized pixels and folds the normalisation into the stem (fold_input_norm);
     with fuse_preprocess=True the stem conv also resizes the uint8 frames itself (F_U8SRC).
     chain: 1x1 / depthwise chains as OP_CHAIN (chains.py); None = the same as hilo.
+    limits: a conv_route.RouteLimits, the thresholds of the conv routing; None = the product's (tools/bench_conv.py passes others).
     se_lateral=False / tail2=False: compile without that rewrite from the start (any other value, None included, keeps it); `fallbacks` (a dict): the rewrites this call had to
     abandon are recorded there as {"tail2": False, "se_lateral": False} so that the caller (engine.Net) passes them for the next shape
     instead of paying the failed attempt again."""
@@ -2256,7 +2095,8 @@ def compile_model(desc, weights, batch, height, width, fetch_cols=(0,), want_pro
         if snap is not None:
             store.rollback(snap)         # blobs of an abandoned attempt leave the shared store (nothing refers to their offsets)
         return Compiler(desc, weights, batch, height, width, fetch_cols, want_probs, store, reuse, hilo=hilo, ragged=ragged,
-                        input_norm=input_norm, fuse_preprocess=fuse_preprocess, chain=chain, tail2=tail2, se_lateral=se_lateral).compile()
+                        input_norm=input_norm, fuse_preprocess=fuse_preprocess, chain=chain, tail2=tail2, se_lateral=se_lateral,
+                        limits=limits).compile()
     try:
         try:
             return build(se_lateral)

@@ -7,7 +7,7 @@
 
 // ---- shape rules of the kernel families -------------------------------------------------------------------------------------
 
-// conv_gemm_kernel: 0 = not eligible; 1 = masked variant; 2 = unmasked 1x1 variant
+// conv_gemm_kernel: 0 = not eligible; 1 = masked variant; 2 = unmasked 1x1 variant.  (Mirrored by conv_route.py, gemm_ok: F_WK32.)
 static int conv_gemm_mode(int kh, int kw, int sh, int sw, int ph, int pw, int cinp, int Kp, int inshift, int flags) {
     (void)sh; (void)sw;
     if (inshift || (flags & (F_PATCH | F_DOT1 | F_SRC2))) return 0;
@@ -69,7 +69,7 @@ static int conv_tile_bn(int Np) {
     return 128;
 }
 
-// conv_patch_kernel (mirrored by compiler.py, which packs the weight stream for it):
+// conv_patch_kernel (mirrored by conv_route.py — patch_fits, patch_th, route_conv — for the compiler, which packs the weight stream for it):
 //   mode 2 (LIGHT, 8-row tiles, 64 or 128 couts, two blocks per CU) when the halo patch of an 8 x 32 tile fits 352 pixels
 //   (3x3, 1xk) and no 1-channel projection is fused (that needs all couts of a pixel in one wave);
 //   else 64 couts per tile, 16-row tiles when they fit the 960-pixel patch (mode 1 above 640 pixels), else 8-row tiles.
@@ -94,7 +94,7 @@ static void conv_patch_plan(int kh, int kw, int OH, int Np, int flags, int* th, 
     if (*mode == 1 && Np <= 32 && !(flags & F_DOT1)) *bn = 32;      // half the MFMAs and weight DMAs of a 64-cout tile
 }
 
-// conv_col_kernel (mirrored by compiler.py, which packs the weight stream for it, F_COL)
+// conv_col_kernel (mirrored by conv_route.py, col_ok; the compiler packs the weight stream for it, F_COL)
 static int conv_col_bn(int Np) { return Np > 32 ? 64 : 32; }
 static bool conv_col_ok(int kh, int kw, int sh, int sw, int cinp, int Np, int flags) {
     return sh == 1 && sw == 1 && (kh == 9 || kh == 7 || kh == 5) && kw >= 3 && CTW + kw - 1 <= CPW && (cinp & 15) == 0 && Np <= 64
@@ -102,7 +102,7 @@ static bool conv_col_ok(int kh, int kw, int sh, int sw, int cinp, int Np, int fl
 }
 
 // conv_c3_kernel tile shape per map: estimated cost (in full tiles) of covering OH x OW with (2 RW) x (32 CW) tiles when waves outside
-// the map idle (a partial tile costs ~0.35 + 0.65 * live waves / 8 of a full one).  Mirrored by compiler.py (c3_tile_eff).
+// the map idle (a partial tile costs ~0.35 + 0.65 * live waves / 8 of a full one).  Mirrored by conv_route.py (c3_tile_eff).
 static double c3_axis_cost(int n, int unit, int waves) {      // n pixels along an axis covered by tiles of `waves` x `unit`
     const int tile = unit * waves, full = n / tile, rem = n - full * tile;
     return full + (rem ? 0.35 + 0.65 * ((rem + unit - 1) / unit) / (double)waves : 0.0);
@@ -120,6 +120,7 @@ static double conv_c3_plan(int OH, int OW, int* rw_out) {
     if (rw_out) *rw_out = brw;
     return best;
 }
+// (mirrored by conv_route.py, c3_ok)
 static bool conv_c3_ok(int kh, int kw, int sh, int sw, int ph, int pw, int cinp, int flags) {
     return kh == 3 && kw == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && (cinp & 15) == 0
            && !(flags & (F_SRC2 | F_PIXSHUF | F_DOT1));
@@ -153,6 +154,7 @@ void conv_pack_plan(ConvParams& p, int TW, int spare) {
     p.tiles_w = (int)(((long)p.pack_g * p.OW + TW - 1) / TW);
 }
 
+// (mirrored by conv_route.py, pw_ok)
 static bool conv_pw_ok(int kh, int kw, int sh, int sw, int ph, int pw, int cinp, int Np, int inshift, int flags) {
     return kh == 1 && kw == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0 && inshift == 0 && (cinp & 7) == 0
            && cinp <= ((flags & F_HILO) ? 96 : 64)      // (hi + lo nets: a 48-channel PAIR tensor is 96 input channels — round 5)
