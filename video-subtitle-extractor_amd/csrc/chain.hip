@@ -93,9 +93,7 @@ __global__ __launch_bounds__(256, CHAIN_BLOCKS_CU) void chain_kernel(const Chain
     // staged once per block, the descriptor stays in the scalar cache, and the first LU x 256 input vectors of the NEXT tile are
     // loaded into registers while this tile's stages run — a tile's global-load latency (2-3 us under load, a third of an
     // un-pipelined tile) is off the critical path.
-    const unsigned nblk = gridDim.x, bid = blockIdx.x;
-    const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, slot = bid >> 3;
-    const unsigned vbid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+    const unsigned nblk = gridDim.x, bid = blockIdx.x, vbid = xcd_block(bid, nblk);
     const unsigned ntiles = (unsigned)a.n_img * tiles_h * tiles_w;
 
     const int* BF = D + CH_HDR;

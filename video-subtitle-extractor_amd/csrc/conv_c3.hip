@@ -71,9 +71,7 @@ __device__ __forceinline__ void conv_c3_body(const ConvParams& p) {
 #endif
     TR_STAMP(0);
 
-    const unsigned nblk = gridDim.x, bid = blockIdx.x;
-    const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, slot = bid >> 3;
-    unsigned t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+    unsigned t = xcd_block(blockIdx.x, gridDim.x);
     const int nt = t % p.ntn;  t /= p.ntn;
     const int tx = t % p.tiles_w;  t /= p.tiles_w;
     const int ty = t % p.tiles_h;
@@ -298,8 +296,15 @@ __global__ __launch_bounds__(512, 4) void conv_c3_kernel(const ConvParams p) { c
 template <int RW, int CW>
 __global__ __launch_bounds__(512, 4) void conv_c3n32_kernel(const ConvParams p) { conv_c3_body<RW, CW, 32>(p); }
 
-// k.arg = RW, the 32-cout form; which layers it serves and the tile shape: conv_c3_ok / conv_c3_plan (conv_select.hip)
-int launch_conv_c3(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+// arg = RW, the 32-cout form; which layers it serves and the tile shape: conv_c3_ok / conv_c3_plan (conv_select.hip)
+static const ConvInst kC3Inst[] = {
+    CONV_INST(8, 1, 0, conv_c3n32_kernel<8, 1>), CONV_INST(4, 1, 0, conv_c3n32_kernel<4, 2>), CONV_INST(2, 1, 0, conv_c3n32_kernel<2, 4>),
+    CONV_INST(8, 0, 0, conv_c3_kernel<8, 1>),    CONV_INST(4, 0, 0, conv_c3_kernel<4, 2>),    CONV_INST(2, 0, 0, conv_c3_kernel<2, 4>),
+};
+
+static int launch_conv_c3(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+    const ConvInst* inst = conv_inst(conv_c3_family(), k);
+    if (!inst) return VSE_E_UNSUPPORTED;
     ConvParams p = pin;
     const int rw = k.arg[0], cw = 8 / rw;
     conv_pack_plan(p, 32 * cw, 6);                       // the patch rows are TW + 8 pixels apart, TW + 2 are read
@@ -325,13 +330,7 @@ int launch_conv_c3(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
     (void)hipMemsetAsync(trace_dev, 0, blocks * 8 * sizeof(unsigned long long), st);
     p.trace = trace_dev;
 #endif
-    if (bn == 32) {
-        if (rw == 8) hipLaunchKernelGGL((conv_c3n32_kernel<8, 1>), grid, block, 0, st, p);
-        else if (rw == 4) hipLaunchKernelGGL((conv_c3n32_kernel<4, 2>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((conv_c3n32_kernel<2, 4>), grid, block, 0, st, p);
-    } else if (rw == 8) hipLaunchKernelGGL((conv_c3_kernel<8, 1>), grid, block, 0, st, p);
-    else if (rw == 4) hipLaunchKernelGGL((conv_c3_kernel<4, 2>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((conv_c3_kernel<2, 4>), grid, block, 0, st, p);
+    hipLaunchKernelGGL(inst->fn, grid, block, 0, st, p);
 #ifdef VSE_TRACE
     {
         (void)hipStreamSynchronize(st);
@@ -351,3 +350,4 @@ int launch_conv_c3(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
 #endif
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
+ConvFamily conv_c3_family() { return conv_family(launch_conv_c3, kC3Inst); }

@@ -42,9 +42,7 @@ __global__ __launch_bounds__(512, 4) void conv_c3pool_kernel(const ConvParams p)
     const int wpx = wave / WCO, wco = wave % WCO;
 
     // XCD-aware bijective block order (see conv_mfma.hip): contiguous logical range per XCD, cout tiles innermost
-    const unsigned nblk = gridDim.x, bid = blockIdx.x;
-    const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, slot = bid >> 3;
-    unsigned t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+    unsigned t = xcd_block(blockIdx.x, gridDim.x);
     const int nt = t % p.ntn;  t /= p.ntn;
     const int tx = t % p.tiles_w;  t /= p.tiles_w;
     const int seg = t % p.pool_nseg;
@@ -264,8 +262,12 @@ static void conv_c3pool_strips(long images, int tiles_h, int tiles_w, int ntn, i
     *nseg = (tiles_h + *seg - 1) / *seg;
 }
 
-// k.arg = BN (conv_select.hip: conv_pool_select); p = the conv's parameters with p.out / p.out_ld = the POOL's output view
-int launch_conv_c3pool(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+// arg = BN (conv_select.hip: conv_pool_select); p = the conv's parameters with p.out / p.out_ld = the POOL's output view
+static const ConvInst kC3poolInst[] = {CONV_INST(128, 0, 0, conv_c3pool_kernel<128>), CONV_INST(64, 0, 0, conv_c3pool_kernel<64>)};
+
+static int launch_conv_c3pool(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+    const ConvInst* inst = conv_inst(conv_c3pool_family(), k);
+    if (!inst) return VSE_E_UNSUPPORTED;
     ConvParams p = pin;
     if (p.kh != 3 || p.kw != 3 || p.sh != 1 || p.sw != 1 || p.ph != 1 || p.pw != 1 || (p.cinp & 7) || p.inshift || p.OH != p.H || p.OW != p.W)
         return VSE_E_INVAL;
@@ -278,8 +280,7 @@ int launch_conv_c3pool(const ConvParams& pin, const ConvKernel& k, hipStream_t s
     conv_c3pool_strips(conv_images(p), p.tiles_h, p.tiles_w, (int)p.ntn, &p.pool_seg, &p.pool_nseg);
     const unsigned long long blocks = (unsigned long long)conv_images(p) * p.pool_nseg * p.tiles_w * p.ntn;
     if (blocks == 0 || blocks > 0x7fffffffull) return VSE_E_INVAL;
-    const dim3 grid((unsigned)blocks), block(512);
-    if (bn == 128) hipLaunchKernelGGL((conv_c3pool_kernel<128>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((conv_c3pool_kernel<64>), grid, block, 0, st, p);
+    hipLaunchKernelGGL(inst->fn, dim3((unsigned)blocks), dim3(512), 0, st, p);
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
+ConvFamily conv_c3pool_family() { return conv_family(launch_conv_c3pool, kC3poolInst); }

@@ -58,9 +58,7 @@ __global__ __launch_bounds__(512, 2) void conv_col_kernel(const ConvParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     // XCD-aware bijective block order (see conv_mfma.hip)
-    const unsigned nblk = gridDim.x, bid = blockIdx.x;
-    const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, slot = bid >> 3;
-    unsigned t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+    unsigned t = xcd_block(blockIdx.x, gridDim.x);
     const int nt = t % p.ntn;  t /= p.ntn;
     const int tx = t % p.tiles_w;  t /= p.tiles_w;
     const int ty = t % p.tiles_h;
@@ -257,21 +255,23 @@ __global__ __launch_bounds__(512, 2) void conv_col_kernel(const ConvParams p) {
     }
 }
 
-// k.arg = KH, BN; which layers it serves: conv_col_ok (conv_select.hip)
-int launch_conv_col(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+// arg = KH, BN; which layers it serves: conv_col_ok (conv_select.hip)
+static const ConvInst kColInst[] = {
+    CONV_INST(9, 64, 0, conv_col_kernel<9, 64>), CONV_INST(9, 32, 0, conv_col_kernel<9, 32>), CONV_INST(7, 64, 0, conv_col_kernel<7, 64>),
+    CONV_INST(7, 32, 0, conv_col_kernel<7, 32>), CONV_INST(5, 64, 0, conv_col_kernel<5, 64>), CONV_INST(5, 32, 0, conv_col_kernel<5, 32>),
+};
+
+static int launch_conv_col(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+    const ConvInst* inst = conv_inst(conv_col_family(), k);
+    if (!inst) return VSE_E_UNSUPPORTED;
     ConvParams p = pin;
-    const int kh = k.arg[0], bn = k.arg[1];
+    const int bn = k.arg[1];
     p.ntn = (unsigned)((p.Np + bn - 1) / bn);
     p.tiles_h = (p.OH + CTH - 1) / CTH;
     conv_pack_plan(p, CTW, CPW - (CTW + p.kw - 1));      // the patch rows are CPW pixels apart, CTW + kw - 1 are read
     const unsigned long long blocks = (unsigned long long)((p.nimg + p.pack_g - 1) / p.pack_g) * p.tiles_h * p.tiles_w * p.ntn;
     if (blocks == 0 || blocks > 0x7fffffffull) return VSE_E_INVAL;
-    const dim3 grid((unsigned)blocks), block(512);
-    if (kh == 9 && bn == 64) hipLaunchKernelGGL((conv_col_kernel<9, 64>), grid, block, 0, st, p);
-    else if (kh == 9) hipLaunchKernelGGL((conv_col_kernel<9, 32>), grid, block, 0, st, p);
-    else if (kh == 7 && bn == 64) hipLaunchKernelGGL((conv_col_kernel<7, 64>), grid, block, 0, st, p);
-    else if (kh == 7) hipLaunchKernelGGL((conv_col_kernel<7, 32>), grid, block, 0, st, p);
-    else if (bn == 64) hipLaunchKernelGGL((conv_col_kernel<5, 64>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((conv_col_kernel<5, 32>), grid, block, 0, st, p);
+    hipLaunchKernelGGL(inst->fn, dim3((unsigned)blocks), dim3(512), 0, st, p);
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
+ConvFamily conv_col_family() { return conv_family(launch_conv_col, kColInst); }

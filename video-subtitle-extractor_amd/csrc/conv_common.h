@@ -351,24 +351,45 @@ __device__ __forceinline__ float conv_epilogue_dot(const ConvParams& p, const fl
 
 // ---- which kernel serves a conv record (conv_select.hip) -------------------------------------------------------------------
 // conv_select() answers it from the record's parameters alone (no pointer, no HIP call); launch_conv() launches that answer and
-// vse_op_kernel_name() names it.  arg[] = the family's template arguments:
-//   CK_GEMM    kCfg index, MASK              conv_gemm_kernel<kCfg[i] (six), MASK>
-//   CK_SMALLM  KT, hi + lo                   conv_smallm_kernel<KT> / conv_smallm_hl_kernel<KT>
-//   CK_MFMA    BN (128 / 64 / 32), UPS       conv_mfma_kernel<BN == 128 ? 128 : 256, BN, BN == 128 ? 2 : 4, BN == 128 ? 2 : 1, UPS>
-//   CK_PATCH   TH, BN, MODE                  conv_patch_kernel<TH, BN, MODE>
-//   CK_COL     KH, BN                        conv_col_kernel<KH, BN>
-//   CK_C3      RW, 32-cout form              conv_c3_kernel<RW, 8 / RW> / conv_c3n32_kernel<RW, 8 / RW>
-//   CK_PW      KS, HILO, TAIL                conv_pw_kernel<KS, HILO> / conv_pw_tail_kernel<KS>
-//   CK_DWPW    KS, LO, S (0 = tile form)     conv_dwpw_kernel<KS, 3, LO> / conv_dwpw_rows_kernel<KS, LO, S>
-//   CK_HEAD    resident                      conv_head_up2r_kernel / conv_head_up2_kernel
-//   CK_STEM    S, HILO, U8                   conv_stem_kernel<S, S, HILO, U8>
-//   CK_C3POOL  BN                            conv_c3pool_kernel<BN>      (a conv record + the max-pool record behind it: conv_pool_select)
-enum { CK_NONE = 0, CK_GEMM, CK_SMALLM, CK_MFMA, CK_PATCH, CK_COL, CK_C3, CK_PW, CK_DWPW, CK_HEAD, CK_STEM, CK_C3POOL };
+// vse_op_kernel_name() names it.  arg[] selects one instantiation of the family: what each slot means, and which instantiations exist,
+// is the family's table next to its launcher (conv_*.hip, CONV_INST).  CK_C3POOL = a conv record + the max-pool record behind it
+// (conv_pool_select).
+enum { CK_NONE = 0, CK_GEMM, CK_SMALLM, CK_MFMA, CK_PATCH, CK_COL, CK_C3, CK_PW, CK_DWPW, CK_HEAD, CK_STEM, CK_C3POOL, CK_FAMILIES };
 struct ConvKernel {
     int family;     // CK_NONE: refused before any launcher
     int rc;         // != VSE_OK: refused with this code (a CK_PW refusal is reported by its launcher, after the launcher's own checks)
     int arg[3];
 };
+
+// One kernel instantiation: the arg[] it serves, the kernel, and its name as rocprofv3 reports the symbol (without "void " and the
+// parameter list).  CONV_INST writes kernel and name from the same tokens, so spell EVERY template argument, defaulted ones too,
+// separated by ", ", booleans as true / false:  CONV_INST(9, 64, 0, conv_col_kernel<9, 64>).
+struct ConvInst {
+    int arg[3];
+    void (*fn)(const ConvParams);
+    const char* name;
+};
+#define CONV_INST(a0, a1, a2, ...) {{a0, a1, a2}, __VA_ARGS__, #__VA_ARGS__}
+// A family: its launcher (grid, block, LDS, parameter fix-ups, what only a launch can check) and its instantiations.  The launcher
+// launches conv_inst()'s entry and answers VSE_E_UNSUPPORTED when there is none; conv_kernel_name() prints the same entry's name.
+struct ConvFamily {
+    int (*launch)(const ConvParams& p, const ConvKernel& k, hipStream_t st);
+    const ConvInst* inst;
+    int n;
+};
+template <int N>
+static inline ConvFamily conv_family(int (*launch)(const ConvParams&, const ConvKernel&, hipStream_t), const ConvInst (&inst)[N]) {
+    return ConvFamily{launch, inst, N};
+}
+static inline const ConvInst* conv_inst(const ConvFamily& f, const ConvKernel& k) {
+    for (const ConvInst* e = f.inst; e != f.inst + f.n; ++e)
+        if (e->arg[0] == k.arg[0] && e->arg[1] == k.arg[1] && e->arg[2] == k.arg[2]) return e;
+    return nullptr;
+}
+// Defined beside the kernels (conv_gemm.hip ... conv_c3pool.hip), indexed by CK_* in conv_select.hip.  (Functions, not objects: a const
+// object of this type would be emitted into the device code as well.)
+ConvFamily conv_gemm_family(), conv_smallm_family(), conv_mfma_family(), conv_patch_family(), conv_col_family(), conv_c3_family(),
+    conv_pw_family(), conv_dwpw_family(), conv_head_family(), conv_stem_family(), conv_c3pool_family();
 
 // conv_gemm_kernel tile configurations (BM x BN, waves WM x WN, BK, stages).  Measured and dropped on MI355X (tools/bench_conv.py,
 // DESIGN.md): BK = 64 rings with 2-3 stages (fewer bytes in flight per CU, -5..-25 %), 4-stage 128 x 128 (2 blocks/CU, -10 %),
@@ -413,23 +434,3 @@ static inline long conv_images(const ConvParams& p) { return p.OH && p.OW ? p.M 
 int conv_pack_group(long images, int OW, int TW, int spare, int gap);
 // fills p.pack_*, p.nimg and p.tiles_w for TW-wide tiles; `spare` as above.  Ragged plans and convs that change the width stay unpacked.
 void conv_pack_plan(ConvParams& p, int TW, int spare);
-
-// The family launchers: map the choice to its instantiation, compute the grid, check what only a launch can (pointers, alignment)
-int launch_conv_gemm(const ConvParams& p, const ConvKernel& k, hipStream_t st);      // scalar-addressed implicit GEMM (conv_gemm.hip)
-int launch_conv_smallm(const ConvParams& p, const ConvKernel& k, hipStream_t st);    // 1x1 conv, operands from global memory (conv_smallm.hip)
-int launch_conv_mfma(const ConvParams& p, const ConvKernel& k, hipStream_t st);      // the general implicit GEMM (conv_mfma.hip)
-int launch_conv_patch(const ConvParams& p, const ConvKernel& k, hipStream_t st);     // LDS-resident patch (conv_patch.hip, F_PATCH)
-// one filter column per step over a 16-channel patch (conv_col.hip, F_COL): 9x9 / 7x7 / 5x5, <= 64 couts
-int launch_conv_col(const ConvParams& p, const ConvKernel& k, hipStream_t st);
-// 3x3 sibling, two blocks per CU (conv_c3.hip, F_COL with kh = kw = 3)
-int launch_conv_c3(const ConvParams& p, const ConvKernel& k, hipStream_t st);
-// 3x3 conv + 3x3 / stride-2 max-pool in one kernel (conv_c3pool.hip): p.out / p.out_ld = the pool's output view
-int launch_conv_c3pool(const ConvParams& p, const ConvKernel& k, hipStream_t st);
-// pointwise conv over <= 64 input channels and <= 256 couts, no LDS staging (conv_pw.hip, F_PW)
-int launch_conv_pw(const ConvParams& p, const ConvKernel& k, hipStream_t st);
-// depthwise k x k conv fused in front of a 1x1 conv (conv_dwpw.hip, F_DWPRE): p.kh / sh / ph = the depthwise geometry, p.dotw = its table
-int launch_conv_dwpw(const ConvParams& p, const ConvKernel& k, hipStream_t st);
-// DB head evaluated on the low-resolution grid (conv_head.hip, F_UP2HEAD)
-int launch_conv_head(const ConvParams& p, const ConvKernel& k, hipStream_t st);
-// 3x3 stem over <= 4 real input channels (conv_stem.hip, F_STEM)
-int launch_conv_stem(const ConvParams& p, const ConvKernel& k, hipStream_t st);

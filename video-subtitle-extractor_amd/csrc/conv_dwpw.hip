@@ -436,21 +436,6 @@ __global__ __launch_bounds__(256, 2) void conv_dwpw_rows_kernel(const ConvParams
     }
 }
 
-template <int KS, int K, bool LO>
-static int launch_dwpw_t(const ConvParams& p, hipStream_t st) {
-    const int ntile = (p.Np + 31) >> 5;
-    const size_t lds = (size_t)2 * ntile * 32 * (KS * 16 + 8) * 2 + (size_t)(K * K + 1) * KS * 16 * 4 + (size_t)ntile * 32 * 4;
-    static VseDevOnce attr_once;          // (per device, thread-safe: common.h)
-    if (!vse_dev_once(attr_once, [] {
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dwpw_kernel<KS, K, LO>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess;
-        }))
-        return VSE_E_HIP;
-    const unsigned long long blocks = (unsigned long long)((p.M + 128 * DWPW_TPW - 1) / (128 * DWPW_TPW));
-    if (blocks == 0 || p.M >= 0x7fffffffl || lds > 128 * 1024) return VSE_E_INVAL;          // (32-bit pixel arithmetic: conv_pix_coords)
-    hipLaunchKernelGGL((conv_dwpw_kernel<KS, K, LO>), dim3((unsigned)blocks), dim3(256), lds, st, p);
-    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
-}
-
 // rows per strip segment of the row-streaming form: long strips amortise the two extra input rows and the block prologue, short ones keep
 // enough waves in flight on small maps (>= ~8 k waves where the map allows it)
 static int dwpw_rows_per_segment(long nimg, int OH, int strips) {
@@ -462,59 +447,47 @@ static int dwpw_rows_per_segment(long nimg, int OH, int strips) {
     return (OH + nseg - 1) / nseg;                       // equal segments
 }
 
-template <int KS, bool LO>
-static int launch_dwpw_rows_t(const ConvParams& pin, hipStream_t st) {
+// arg = KS, LO, the row-streaming form's stride (0 = the tile form); which layers it serves: conv_dwpw_ok, conv_dwpw_rows_stride
+// (conv_select.hip).  The row form exists for pair inputs (LO) over <= DWPW_ROWS_MAX_KS slices only: wider units would spill.
+static const ConvInst kDwpwInst[] = {
+    CONV_INST(1, 1, 2, conv_dwpw_rows_kernel<1, true, 2>), CONV_INST(1, 1, 1, conv_dwpw_rows_kernel<1, true, 1>),
+    CONV_INST(2, 1, 2, conv_dwpw_rows_kernel<2, true, 2>), CONV_INST(2, 1, 1, conv_dwpw_rows_kernel<2, true, 1>),
+    CONV_INST(3, 1, 2, conv_dwpw_rows_kernel<3, true, 2>), CONV_INST(3, 1, 1, conv_dwpw_rows_kernel<3, true, 1>),
+    CONV_INST(1, 1, 0, conv_dwpw_kernel<1, 3, true>),      CONV_INST(1, 0, 0, conv_dwpw_kernel<1, 3, false>),
+    CONV_INST(2, 1, 0, conv_dwpw_kernel<2, 3, true>),      CONV_INST(2, 0, 0, conv_dwpw_kernel<2, 3, false>),
+    CONV_INST(3, 1, 0, conv_dwpw_kernel<3, 3, true>),      CONV_INST(3, 0, 0, conv_dwpw_kernel<3, 3, false>),
+    CONV_INST(4, 1, 0, conv_dwpw_kernel<4, 3, true>),      CONV_INST(4, 0, 0, conv_dwpw_kernel<4, 3, false>),
+    CONV_INST(5, 1, 0, conv_dwpw_kernel<5, 3, true>),      CONV_INST(5, 0, 0, conv_dwpw_kernel<5, 3, false>),
+    CONV_INST(6, 1, 0, conv_dwpw_kernel<6, 3, true>),      CONV_INST(6, 0, 0, conv_dwpw_kernel<6, 3, false>),
+};
+// the kernels take dynamic LDS: its limit is raised once per instantiation and device (thread-safe: common.h)
+static VseDevOnce dwpw_lds_once[sizeof(kDwpwInst) / sizeof(kDwpwInst[0])];
+
+// p.kh / p.sh / p.ph describe the DEPTHWISE conv, 3 x 3 (the 1x1 conv has no geometry); p.dotw = the aux blob; p.in_lo_off = the input's pair offset
+static int launch_conv_dwpw(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+    if (!pin.dotw) return VSE_E_INVAL;
+    const ConvInst* inst = conv_inst(conv_dwpw_family(), k);
+    if (!inst) return VSE_E_UNSUPPORTED;
     ConvParams p = pin;
-    const int ntile = (p.Np + 31) >> 5;
-    const size_t lds = (size_t)2 * ntile * 32 * (KS * 16 + 8) * 2 + (size_t)(9 + 1) * KS * 16 * 4 + (size_t)ntile * 32 * 4;
-    constexpr bool S1 = KS <= DWPW_ROWS_MAX_KS_S1;       // (the stride-1 form of wider units would spill: not instantiated)
-    static VseDevOnce attr_once;
-    if (!vse_dev_once(attr_once, [] {
-            bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dwpw_rows_kernel<KS, LO, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess;
-            if constexpr (S1)
-                ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dwpw_rows_kernel<KS, LO, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess;
-            return ok;
+    const int ks = k.arg[0], ntile = (p.Np + 31) >> 5;
+    const size_t lds = (size_t)2 * ntile * 32 * (ks * 16 + 8) * 2 + (size_t)(9 + 1) * ks * 16 * 4 + (size_t)ntile * 32 * 4;
+    if (!vse_dev_once(dwpw_lds_once[inst - kDwpwInst], [inst] {
+            return hipFuncSetAttribute(reinterpret_cast<const void*>(inst->fn), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess;
         }))
         return VSE_E_HIP;
-    const long nimg = p.M / ((long)p.OH * p.OW);
-    if (nimg <= 0 || p.M != nimg * p.OH * p.OW || p.M >= 0x7fffffffl || lds > 128 * 1024) return VSE_E_INVAL;
-    p.tiles_w = (p.OW + 31) / 32;
-    const int rs = dwpw_rows_per_segment(nimg, p.OH, p.tiles_w);
-    p.ntiles = (unsigned)rs;
-    p.tiles_h = (p.OH + rs - 1) / rs;
-    const unsigned long long waves = (unsigned long long)nimg * p.tiles_h * p.tiles_w;
-    const unsigned long long blocks = (waves + 3) / 4;
+    if (p.M >= 0x7fffffffl || lds > 128 * 1024) return VSE_E_INVAL;          // (32-bit pixel arithmetic: conv_pix_coords)
+    unsigned long long blocks = (unsigned long long)((p.M + 128 * DWPW_TPW - 1) / (128 * DWPW_TPW));
+    if (k.arg[2]) {                                      // the row-streaming form: one wave per strip segment
+        const long nimg = p.M / ((long)p.OH * p.OW);
+        if (nimg <= 0 || p.M != nimg * p.OH * p.OW || p.sh != k.arg[2]) return VSE_E_INVAL;
+        p.tiles_w = (p.OW + 31) / 32;
+        const int rs = dwpw_rows_per_segment(nimg, p.OH, p.tiles_w);
+        p.ntiles = (unsigned)rs;
+        p.tiles_h = (p.OH + rs - 1) / rs;
+        blocks = ((unsigned long long)nimg * p.tiles_h * p.tiles_w + 3) / 4;
+    }
     if (blocks == 0 || blocks > 0x7fffffffull) return VSE_E_INVAL;
-    if (p.sh == 1) {
-        if constexpr (S1) hipLaunchKernelGGL((conv_dwpw_rows_kernel<KS, LO, 1>), dim3((unsigned)blocks), dim3(256), lds, st, p);
-        else return VSE_E_UNSUPPORTED;
-    } else hipLaunchKernelGGL((conv_dwpw_rows_kernel<KS, LO, 2>), dim3((unsigned)blocks), dim3(256), lds, st, p);
+    hipLaunchKernelGGL(inst->fn, dim3((unsigned)blocks), dim3(256), lds, st, p);
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
-
-// p.kh / p.sh / p.ph describe the DEPTHWISE conv (the 1x1 conv has no geometry); p.dotw = the aux blob; p.in_lo_off = the input's pair offset
-// k.arg = KS, LO, the row-streaming form's stride (0 = the tile form); which layers it serves: conv_dwpw_ok (conv_select.hip)
-int launch_conv_dwpw(const ConvParams& p, const ConvKernel& k, hipStream_t st) {
-    if (!p.dotw) return VSE_E_INVAL;
-    const int ks = k.arg[0];
-    if (k.arg[2]) {
-#define DWPW_ROWS(KS_) launch_dwpw_rows_t<KS_, true>(p, st)
-        switch (ks) {
-            case 1: return DWPW_ROWS(1);
-            case 2: return DWPW_ROWS(2);
-            default: return DWPW_ROWS(3);
-        }
-#undef DWPW_ROWS
-    }
-#define DWPW(KS_) (k.arg[1] ? launch_dwpw_t<KS_, 3, true>(p, st) : launch_dwpw_t<KS_, 3, false>(p, st))
-    switch (ks) {
-        case 1: return DWPW(1);
-        case 2: return DWPW(2);
-        case 3: return DWPW(3);
-        case 4: return DWPW(4);
-        case 5: return DWPW(5);
-        case 6: return DWPW(6);
-        default: return VSE_E_UNSUPPORTED;
-    }
-#undef DWPW
-}
+ConvFamily conv_dwpw_family() { return conv_family(launch_conv_dwpw, kDwpwInst); }

@@ -62,9 +62,7 @@ void conv_gemm_kernel(const ConvParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
     // XCD-aware tile order, identical to conv_mfma_kernel
-    const unsigned nblk = gridDim.x, bid = blockIdx.x;
-    const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, slot = bid >> 3;
-    const unsigned logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+    const unsigned logical = xcd_block(blockIdx.x, gridDim.x);
     const unsigned mtile = logical / p.ntn, ntile = logical - mtile * p.ntn;
     // F_IMGW (per-image weights): M tiles are aligned to images, so that one tile has one weight matrix
     long m0 = (long)mtile * BM;
@@ -271,19 +269,26 @@ void conv_gemm_kernel(const ConvParams p) {
     }
 }
 
-template <int C>
-static void launch_cfg(const ConvParams& p, int mask, dim3 grid, hipStream_t st) {
-    constexpr GemmCfg g = kCfg[C];
-    dim3 block(64 * g.wm * g.wn);
-    if (mask) hipLaunchKernelGGL((conv_gemm_kernel<g.bm, g.bn, g.wm, g.wn, g.bk, g.st, 1>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((conv_gemm_kernel<g.bm, g.bn, g.wm, g.wn, g.bk, g.st, 0>), grid, block, 0, st, p);
+// arg = the kCfg configuration, MASK.  GEMM_INST spells the configuration's numbers (the kernel's name) and refuses to compile where
+// they are not kCfg[I]'s.  (The kernels lie in the code object in the order of their entries: configuration 0 has always come last.)
+template <int I, int BM, int BN, int WM, int WN, int BKT, int ST>
+constexpr int gemm_cfg_is() {
+    static_assert(kCfg[I].bm == BM && kCfg[I].bn == BN && kCfg[I].wm == WM && kCfg[I].wn == WN && kCfg[I].bk == BKT && kCfg[I].st == ST,
+                  "GEMM_INST: the spelled template arguments are not kCfg[I]");
+    return I;
 }
+#define GEMM_INST(I, ...) CONV_INST((gemm_cfg_is<I, __VA_ARGS__>()), 1, 0, conv_gemm_kernel<__VA_ARGS__, 1>), \
+                          CONV_INST((gemm_cfg_is<I, __VA_ARGS__>()), 0, 0, conv_gemm_kernel<__VA_ARGS__, 0>)
+static const ConvInst kGemmInst[] = {
+    GEMM_INST(1, 256, 64, 4, 1, 32, 3),  GEMM_INST(2, 256, 32, 4, 1, 32, 3),  GEMM_INST(3, 256, 128, 4, 2, 32, 3), GEMM_INST(4, 256, 256, 4, 4, 32, 3),
+    GEMM_INST(5, 256, 192, 8, 2, 32, 3), GEMM_INST(6, 256, 256, 4, 4, 64, 2), GEMM_INST(7, 256, 192, 8, 2, 64, 2), GEMM_INST(0, 128, 128, 2, 2, 32, 3),
+};
 
-// k.arg[0] = the kCfg configuration, k.arg[1] = MASK
-int launch_conv_gemm(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+static int launch_conv_gemm(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+    const ConvInst* inst = conv_inst(conv_gemm_family(), k);
+    if (!inst) return VSE_E_UNSUPPORTED;
     ConvParams p = pin;
-    const int c = k.arg[0];
-    const GemmCfg& g = kCfg[c];
+    const GemmCfg& g = kCfg[k.arg[0]];
     p.ntn = (unsigned)((p.Np + g.bn - 1) / g.bn);
     p.nkh = p.nkh * 32 / g.bk;               // (nkh = Kp / 32 on entry)
     p.nk = p.nkh;
@@ -294,16 +299,7 @@ int launch_conv_gemm(const ConvParams& pin, const ConvKernel& k, hipStream_t st)
         tiles = (unsigned long long)(p.M / p.hw_img) * p.tiles_img * p.ntn;
     }
     if (tiles == 0 || tiles > 0x7fffffffull) return VSE_E_INVAL;
-    dim3 grid((unsigned)tiles);
-    switch (c) {
-        case 1: launch_cfg<1>(p, k.arg[1], grid, st); break;
-        case 2: launch_cfg<2>(p, k.arg[1], grid, st); break;
-        case 3: launch_cfg<3>(p, k.arg[1], grid, st); break;
-        case 4: launch_cfg<4>(p, k.arg[1], grid, st); break;
-        case 5: launch_cfg<5>(p, k.arg[1], grid, st); break;
-        case 6: launch_cfg<6>(p, k.arg[1], grid, st); break;
-        case 7: launch_cfg<7>(p, k.arg[1], grid, st); break;
-        default: launch_cfg<0>(p, k.arg[1], grid, st); break;
-    }
+    hipLaunchKernelGGL(inst->fn, dim3((unsigned)tiles), dim3(64 * g.wm * g.wn), 0, st, p);
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
+ConvFamily conv_gemm_family() { return conv_family(launch_conv_gemm, kGemmInst); }

@@ -53,9 +53,7 @@ __global__ __launch_bounds__(512) void conv_head_up2_kernel(const ConvParams p) 
     const int wrow = wave >> 1, wco = wave & 1;
 
     // XCD-aware bijective block order (see conv_mfma.hip)
-    const unsigned nblk = gridDim.x, bid = blockIdx.x;
-    const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, slot = bid >> 3;
-    unsigned t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+    unsigned t = xcd_block(blockIdx.x, gridDim.x);
     const int tx = t % p.tiles_w;  t /= p.tiles_w;
     const int ty = t % p.tiles_h;
     const long img = t / p.tiles_h;
@@ -529,8 +527,12 @@ __global__ __launch_bounds__(512, 2) void conv_head_up2r_kernel(const ConvParams
 #endif
 }
 
-// k.arg[0]: the resident-weight form (conv_select.hip reads VSE_HEAD_RESIDENT)
-int launch_conv_head(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+// arg = the resident-weight form (conv_select.hip reads VSE_HEAD_RESIDENT)
+static const ConvInst kHeadInst[] = {CONV_INST(1, 0, 0, conv_head_up2r_kernel), CONV_INST(0, 0, 0, conv_head_up2_kernel)};
+
+static int launch_conv_head(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+    const ConvInst* inst = conv_inst(conv_head_family(), k);
+    if (!inst) return VSE_E_UNSUPPORTED;
     ConvParams p = pin;
     // u = in0: [n, 2Hl, 2Wl, 8-channel padded, 1 real]; x = in2: [n, Hl, Wl, 64], upsampled by 2
     if (!(p.flags & F_DOT1) || !(p.flags & F_SRC2) || p.in2_shift != 1 || p.inshift != 0) return VSE_E_INVAL;
@@ -559,7 +561,7 @@ int launch_conv_head(const ConvParams& pin, const ConvKernel& k, hipStream_t st)
         (void)hipMemsetAsync(trace_dev, 0, 256 * 20 * sizeof(unsigned long long), st);
         p.trace = grid <= 256 ? trace_dev : nullptr;
 #endif
-        hipLaunchKernelGGL(conv_head_up2r_kernel, dim3(grid), dim3(512), 0, st, p);
+        hipLaunchKernelGGL(inst->fn, dim3(grid), dim3(512), 0, st, p);
 #ifdef VSE_TRACE
         if (p.trace) {
             (void)hipStreamSynchronize(st);
@@ -582,6 +584,7 @@ int launch_conv_head(const ConvParams& pin, const ConvKernel& k, hipStream_t st)
 #endif
         return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
     }
-    hipLaunchKernelGGL(conv_head_up2_kernel, dim3((unsigned)blocks), dim3(512), 0, st, p);
+    hipLaunchKernelGGL(inst->fn, dim3((unsigned)blocks), dim3(512), 0, st, p);
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
+ConvFamily conv_head_family() { return conv_family(launch_conv_head, kHeadInst); }

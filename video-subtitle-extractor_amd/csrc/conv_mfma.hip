@@ -45,9 +45,7 @@ __global__ __launch_bounds__(256, (BM + (BN < 64 ? 64 : BN)) <= 256 ? 3 : 2) voi
     // tile first, so the kh x kw halo rows shared by neighbouring pixel tiles and the re-read of the activation
     // tile by the other cout tiles hit the same L2 instead of being fetched once per XCD.  Speed only: any
     // placement computes the same result.
-    const unsigned nblk = gridDim.x, bid = blockIdx.x;
-    const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, slot = bid >> 3;
-    const unsigned logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+    const unsigned logical = xcd_block(blockIdx.x, gridDim.x);
     const unsigned mtile = logical / p.ntn, ntile = logical - mtile * p.ntn;
     const long m0 = (long)mtile * BM;
     const int n0 = ntile * BN;
@@ -221,21 +219,22 @@ __global__ __launch_bounds__(256, (BM + (BN < 64 ? 64 : BN)) <= 256 ? 3 : 2) voi
     }
 }
 
-int launch_conv_mfma(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+// arg = BN, UPS (the input is read through a nearest-neighbour up-sampling: inshift)
+static const ConvInst kMfmaInst[] = {
+    CONV_INST(128, 1, 0, conv_mfma_kernel<128, 128, 2, 2, true>),  CONV_INST(64, 1, 0, conv_mfma_kernel<256, 64, 4, 1, true>),
+    CONV_INST(32, 1, 0, conv_mfma_kernel<256, 32, 4, 1, true>),    CONV_INST(128, 0, 0, conv_mfma_kernel<128, 128, 2, 2, false>),
+    CONV_INST(64, 0, 0, conv_mfma_kernel<256, 64, 4, 1, false>),   CONV_INST(32, 0, 0, conv_mfma_kernel<256, 32, 4, 1, false>),
+};
+
+static int launch_conv_mfma(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+    const ConvInst* inst = conv_inst(conv_mfma_family(), k);
+    if (!inst) return VSE_E_UNSUPPORTED;
     ConvParams p = pin;
     const int bn = k.arg[0], bm = bn == 128 ? 128 : 256;
     p.ntn = (unsigned)((p.Np + bn - 1) / bn);
     const unsigned long long tiles = (unsigned long long)((p.M + bm - 1) / bm) * p.ntn;
     if (tiles == 0 || tiles > 0x7fffffffull) return VSE_E_INVAL;
-    const dim3 grid((unsigned)tiles), block(256);
-    if (k.arg[1]) {
-        if (bn == 128) hipLaunchKernelGGL((conv_mfma_kernel<128, 128, 2, 2, true>), grid, block, 0, st, p);
-        else if (bn == 64) hipLaunchKernelGGL((conv_mfma_kernel<256, 64, 4, 1, true>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((conv_mfma_kernel<256, 32, 4, 1, true>), grid, block, 0, st, p);
-    } else {
-        if (bn == 128) hipLaunchKernelGGL((conv_mfma_kernel<128, 128, 2, 2, false>), grid, block, 0, st, p);
-        else if (bn == 64) hipLaunchKernelGGL((conv_mfma_kernel<256, 64, 4, 1, false>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((conv_mfma_kernel<256, 32, 4, 1, false>), grid, block, 0, st, p);
-    }
+    hipLaunchKernelGGL(inst->fn, dim3((unsigned)tiles), dim3(256), 0, st, p);
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
+ConvFamily conv_mfma_family() { return conv_family(launch_conv_mfma, kMfmaInst); }

@@ -83,9 +83,7 @@ __global__ __launch_bounds__(512, MODE == 2 ? 4 : 2) void conv_patch_kernel(cons
     TR_STAMP(0);
 
     // XCD-aware bijective block order (see conv_mfma.hip): contiguous logical range per XCD, cout tiles innermost
-    const unsigned nblk = gridDim.x, bid = blockIdx.x;
-    const unsigned q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, slot = bid >> 3;
-    unsigned t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+    unsigned t = xcd_block(blockIdx.x, gridDim.x);
     const int nt = t % p.ntn;  t /= p.ntn;
     const int tx = t % p.tiles_w;  t /= p.tiles_w;
     const int ty = t % p.tiles_h;
@@ -392,13 +390,19 @@ __global__ __launch_bounds__(512, MODE == 2 ? 4 : 2) void conv_patch_kernel(cons
 #endif
 }
 
-// k.arg = TH, BN, MODE (conv_select.hip: conv_patch_plan)
-int launch_conv_patch(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+// arg = TH, BN, MODE (conv_select.hip: conv_patch_plan)
+static const ConvInst kPatchInst[] = {
+    CONV_INST(8, 128, 2, conv_patch_kernel<8, 128, 2>), CONV_INST(8, 64, 2, conv_patch_kernel<8, 64, 2>),   CONV_INST(16, 32, 1, conv_patch_kernel<16, 32, 1>),
+    CONV_INST(16, 64, 1, conv_patch_kernel<16, 64, 1>), CONV_INST(16, 64, 0, conv_patch_kernel<16, 64, 0>), CONV_INST(8, 64, 0, conv_patch_kernel<8, 64, 0>),
+};
+
+static int launch_conv_patch(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+    const ConvInst* inst = conv_inst(conv_patch_family(), k);
+    if (!inst) return VSE_E_UNSUPPORTED;
     ConvParams p = pin;
     if (p.sh != 1 || p.sw != 1 || p.kh * p.kw < 5 || (p.cinp & 7) || (p.flags & F_PIXSHUF)) return VSE_E_INVAL;
     if ((8 + p.kh - 1) * (PTW + p.kw - 1) > 640) return VSE_E_UNSUPPORTED;
-    const int th = k.arg[0], bn = k.arg[1], mode = k.arg[2];
-    const bool big = mode == 1;
+    const int th = k.arg[0], bn = k.arg[1];
     p.ntn = (unsigned)((p.Np + bn - 1) / bn);
     if ((p.flags & F_DOT1) && (th != 16 || p.ntn != 1 || (p.flags & F_RES) || !p.dotw || !p.dot_out)) return VSE_E_UNSUPPORTED;
     p.tiles_h = (p.OH + th - 1) / th;
@@ -416,12 +420,7 @@ int launch_conv_patch(const ConvParams& pin, const ConvKernel& k, hipStream_t st
     }
     p.trace = trace_dev;
 #endif
-    if (mode == 2 && bn == 128) hipLaunchKernelGGL((conv_patch_kernel<8, 128, 2>), grid, block, 0, st, p);
-    else if (mode == 2) hipLaunchKernelGGL((conv_patch_kernel<8, 64, 2>), grid, block, 0, st, p);
-    else if (big && bn == 32) hipLaunchKernelGGL((conv_patch_kernel<16, 32, 1>), grid, block, 0, st, p);
-    else if (big) hipLaunchKernelGGL((conv_patch_kernel<16, 64, 1>), grid, block, 0, st, p);
-    else if (th == 16) hipLaunchKernelGGL((conv_patch_kernel<16, 64, 0>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((conv_patch_kernel<8, 64, 0>), grid, block, 0, st, p);
+    hipLaunchKernelGGL(inst->fn, grid, block, 0, st, p);
 #ifdef VSE_TRACE
     {
         (void)hipStreamSynchronize(st);
@@ -438,9 +437,10 @@ int launch_conv_patch(const ConvParams& pin, const ConvKernel& k, hipStream_t st
         }
         fprintf(stderr, "[patch trace] k%dx%d cin%d N%d %dx%d th%d big%d blocks %llu: per block (s_memtime ticks) setup %.0f, first wait %.0f, "
                 "loop %.0f (of which wait+barrier %.0f), epilogue %.0f; kernel span %llu ticks = %.1f block-lifetimes/slot\n",
-                p.kh, p.kw, p.cinp, p.Np, p.OH, p.OW, th, (int)big, blocks, d[0] / blocks, d[1] / blocks, d[2] / blocks, d[4] / blocks,
+                p.kh, p.kw, p.cinp, p.Np, p.OH, p.OW, th, (int)(k.arg[2] == 1), blocks, d[0] / blocks, d[1] / blocks, d[2] / blocks, d[4] / blocks,
                 d[3] / blocks, tmax - tmin, (double)(tmax - tmin) / ((d[0] + d[1] + d[2] + d[3]) / blocks));
     }
 #endif
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
+ConvFamily conv_patch_family() { return conv_family(launch_conv_patch, kPatchInst); }

@@ -159,7 +159,7 @@ __device__ __forceinline__ void conv_pw_body(const ConvParams& p, half_t* swt, f
     }
 }
 
-template <int KS, bool HILO = false>
+template <int KS, bool HILO>
 __global__ __launch_bounds__(256, (KS <= 2 ? 4 : KS <= 4 ? 3 : 2)) void conv_pw_kernel(const ConvParams p) {
     __shared__ __attribute__((aligned(16))) half_t swt[(HILO ? 2 * PW_MAXN_HILO : PW_MAXN) * (KS * 16 + 8)];
     __shared__ float sbias[PW_MAXN];
@@ -173,42 +173,27 @@ __global__ __launch_bounds__(256, 3) void conv_pw_tail_kernel(const ConvParams p
     conv_pw_body<KS, false, true>(p, swt, sbias, swb);
 }
 
-// k.arg = KS, HILO, TAIL; which layers it serves: conv_pw_ok (conv_select.hip)
-int launch_conv_pw(const ConvParams& p, const ConvKernel& k, hipStream_t st) {
+// arg = KS, HILO, TAIL; which layers it serves: conv_pw_ok (conv_select.hip)
+static const ConvInst kPwInst[] = {
+    CONV_INST(2, 0, 1, conv_pw_tail_kernel<2>),      CONV_INST(4, 0, 1, conv_pw_tail_kernel<4>),      CONV_INST(1, 1, 0, conv_pw_kernel<1, true>),
+    CONV_INST(2, 1, 0, conv_pw_kernel<2, true>),     CONV_INST(3, 1, 0, conv_pw_kernel<3, true>),     CONV_INST(4, 1, 0, conv_pw_kernel<4, true>),
+    CONV_INST(5, 1, 0, conv_pw_kernel<5, true>),     CONV_INST(6, 1, 0, conv_pw_kernel<6, true>),     CONV_INST(1, 0, 0, conv_pw_kernel<1, false>),
+    CONV_INST(2, 0, 0, conv_pw_kernel<2, false>),    CONV_INST(3, 0, 0, conv_pw_kernel<3, false>),    CONV_INST(4, 0, 0, conv_pw_kernel<4, false>),
+};
+
+static int launch_conv_pw(const ConvParams& p, const ConvKernel& k, hipStream_t st) {
     const unsigned long long blocks = (unsigned long long)((p.M + 255) / 256);
     if (blocks == 0 || p.M >= 0x7fffffffl) return VSE_E_INVAL;          // (32-bit pixel arithmetic: conv_pix_coords)
-    const dim3 grid((unsigned)blocks), block(256);
     if (k.arg[2]) {
         // stage A without residual / gate / affine / second activation, whole 32-cout tiles, a dense fp16 map out
         if ((p.flags & (F_HILO | F_RES | F_OGATE | F_DOT1 | F_ONECH)) || !(p.flags & F_PIXSHUF) || p.out_f32 || !p.vec16 || (p.Np & 31) || !p.dotw || !p.dot_out
             || p.dot_f32 || p.dot_ld != 1 || p.act2 || p.post_a != 1.f || p.post_b != 0.f || p.lo_off || p.wl_out
             || (reinterpret_cast<uintptr_t>(p.dot_out) & 7) || (reinterpret_cast<uintptr_t>(p.dotw) & 15)) return VSE_E_INVAL;
         if (k.rc != VSE_OK) return k.rc;
-        switch (k.arg[0]) {
-            case 2: hipLaunchKernelGGL((conv_pw_tail_kernel<2>), grid, block, 0, st, p); break;
-            case 4: hipLaunchKernelGGL((conv_pw_tail_kernel<4>), grid, block, 0, st, p); break;
-            default: return VSE_E_UNSUPPORTED;
-        }
-        return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
     }
-    if (k.arg[1]) {
-        switch (k.arg[0]) {
-            case 1: hipLaunchKernelGGL((conv_pw_kernel<1, true>), grid, block, 0, st, p); break;
-            case 2: hipLaunchKernelGGL((conv_pw_kernel<2, true>), grid, block, 0, st, p); break;
-            case 3: hipLaunchKernelGGL((conv_pw_kernel<3, true>), grid, block, 0, st, p); break;
-            case 4: hipLaunchKernelGGL((conv_pw_kernel<4, true>), grid, block, 0, st, p); break;
-            case 5: hipLaunchKernelGGL((conv_pw_kernel<5, true>), grid, block, 0, st, p); break;
-            case 6: hipLaunchKernelGGL((conv_pw_kernel<6, true>), grid, block, 0, st, p); break;
-            default: return VSE_E_UNSUPPORTED;
-        }
-        return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
-    }
-    switch (k.arg[0]) {
-        case 1: hipLaunchKernelGGL((conv_pw_kernel<1>), grid, block, 0, st, p); break;
-        case 2: hipLaunchKernelGGL((conv_pw_kernel<2>), grid, block, 0, st, p); break;
-        case 3: hipLaunchKernelGGL((conv_pw_kernel<3>), grid, block, 0, st, p); break;
-        case 4: hipLaunchKernelGGL((conv_pw_kernel<4>), grid, block, 0, st, p); break;
-        default: return VSE_E_UNSUPPORTED;
-    }
+    const ConvInst* inst = conv_inst(conv_pw_family(), k);
+    if (!inst) return VSE_E_UNSUPPORTED;
+    hipLaunchKernelGGL(inst->fn, dim3((unsigned)blocks), dim3(256), 0, st, p);
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
+ConvFamily conv_pw_family() { return conv_family(launch_conv_pw, kPwInst); }

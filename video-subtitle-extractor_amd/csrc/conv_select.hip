@@ -1,6 +1,7 @@
 // Which kernel serves an OP_CONV record, decided in one place (host code only): the record -> ConvParams step, the selector with
 // the shape rules of every conv kernel family, the name of its answer, and launch_conv(), which checks the record, asks the
-// selector and hands the answer to the family's launcher.  The kernels and their launchers stay in their own files.
+// selector and hands the answer to the family's launcher.  The kernels, their launchers and the tables of their instantiations stay
+// in their own files.
 #include <stdlib.h>
 #include <cstdio>
 #include "conv_common.h"
@@ -302,33 +303,28 @@ ConvKernel conv_select(const ConvParams& p, int Kp) {
     return pick(CK_MFMA, conv_tile_bn(p.Np), p.inshift != 0);
 }
 
-// The instantiation `k` names, spelled as rocprofv3 reports the symbol (without "void " and the parameter list).
+// ---- the families: launcher and instantiations of each (defined beside the kernels), by CK_* ---------------------------------------
+
+static const ConvFamily& conv_family_of(int family) {
+    static const ConvFamily fam[CK_FAMILIES] = {
+        ConvFamily{nullptr, nullptr, 0}, conv_gemm_family(), conv_smallm_family(), conv_mfma_family(), conv_patch_family(), conv_col_family(),
+        conv_c3_family(), conv_pw_family(), conv_dwpw_family(), conv_head_family(), conv_stem_family(), conv_c3pool_family()};
+    return fam[family > CK_NONE && family < CK_FAMILIES ? family : CK_NONE];
+}
+
+// a family outside the registry is refused like a choice outside the family's table
+static int conv_launch(const ConvParams& p, const ConvKernel& k, hipStream_t st) {
+    const ConvFamily& f = conv_family_of(k.family);
+    return f.launch ? f.launch(p, k, st) : VSE_E_UNSUPPORTED;
+}
+
+// The instantiation `k` names: the name in its table entry, which is the kernel the family's launcher launches for `k`.
 int conv_kernel_name(const ConvKernel& k, char* buf, size_t n) {
-    const int* a = k.arg;
-    const char* tf[2] = {"false", "true"};
     if (k.rc != VSE_OK) return snprintf(buf, n, "(refused: %d)", k.rc);
-    switch (k.family) {
-        case CK_GEMM: {
-            const GemmCfg& g = kCfg[a[0]];
-            return snprintf(buf, n, "conv_gemm_kernel<%d, %d, %d, %d, %d, %d, %d>", g.bm, g.bn, g.wm, g.wn, g.bk, g.st, a[1]);
-        }
-        case CK_SMALLM: return snprintf(buf, n, "conv_smallm%s_kernel<%d>", a[1] ? "_hl" : "", a[0]);
-        case CK_MFMA:
-            return snprintf(buf, n, "conv_mfma_kernel<%d, %d, %d, %d, %s>", a[0] == 128 ? 128 : 256, a[0], a[0] == 128 ? 2 : 4, a[0] == 128 ? 2 : 1,
-                            tf[a[1]]);
-        case CK_PATCH: return snprintf(buf, n, "conv_patch_kernel<%d, %d, %d>", a[0], a[1], a[2]);
-        case CK_COL: return snprintf(buf, n, "conv_col_kernel<%d, %d>", a[0], a[1]);
-        case CK_C3: return snprintf(buf, n, "conv_c3%s_kernel<%d, %d>", a[1] ? "n32" : "", a[0], 8 / a[0]);
-        case CK_PW:
-            return a[2] ? snprintf(buf, n, "conv_pw_tail_kernel<%d>", a[0]) : snprintf(buf, n, "conv_pw_kernel<%d, %s>", a[0], tf[a[1]]);
-        case CK_DWPW:
-            return a[2] ? snprintf(buf, n, "conv_dwpw_rows_kernel<%d, %s, %d>", a[0], tf[a[1]], a[2])
-                        : snprintf(buf, n, "conv_dwpw_kernel<%d, 3, %s>", a[0], tf[a[1]]);
-        case CK_HEAD: return snprintf(buf, n, a[0] ? "conv_head_up2r_kernel" : "conv_head_up2_kernel");
-        case CK_STEM: return snprintf(buf, n, "conv_stem_kernel<%d, %d, %s, %s>", a[0], a[0], tf[a[1]], tf[a[2]]);
-        case CK_C3POOL: return snprintf(buf, n, "conv_c3pool_kernel<%d>", a[0]);
-        default: return snprintf(buf, n, "?");
-    }
+    const ConvFamily& f = conv_family_of(k.family);
+    const ConvInst* inst = conv_inst(f, k);
+    if (!inst) return snprintf(buf, n, "(no instantiation: family %d<%d, %d, %d>)", k.family, k.arg[0], k.arg[1], k.arg[2]);
+    return snprintf(buf, n, "%s", inst->name);
 }
 
 // ---- conv + max-pool pairs that run as one kernel ------------------------------------------------------------------------------
@@ -391,7 +387,7 @@ int launch_conv_pool(const vse_op& conv, const ConvKernel& k, const TView& in, c
     if (in.c != p.cinp || (in.ld & 7)) return VSE_E_INVAL;
     p.out = pool_out.ptr;
     p.out_ld = pool_out.ld;
-    return launch_conv_c3pool(p, k, st);
+    return conv_launch(p, k, st);
 }
 
 // ---- launch -----------------------------------------------------------------------------------------------------------------
@@ -426,16 +422,5 @@ int launch_conv(const vse_op& o, const TView& in, const TView& res, const TView&
     const ConvKernel k = conv_select(p, o.p[P_KTOT]);
     if (k.family == CK_NONE) return k.rc;
     if (!p.zero && !(f & (F_IMGW | F_DWPRE))) return VSE_E_INVAL;
-    switch (k.family) {
-        case CK_GEMM: return launch_conv_gemm(p, k, st);
-        case CK_SMALLM: return launch_conv_smallm(p, k, st);
-        case CK_MFMA: return launch_conv_mfma(p, k, st);
-        case CK_PATCH: return launch_conv_patch(p, k, st);
-        case CK_COL: return launch_conv_col(p, k, st);
-        case CK_C3: return launch_conv_c3(p, k, st);
-        case CK_PW: return launch_conv_pw(p, k, st);
-        case CK_DWPW: return launch_conv_dwpw(p, k, st);
-        case CK_HEAD: return launch_conv_head(p, k, st);
-        default: return launch_conv_stem(p, k, st);
-    }
+    return conv_launch(p, k, st);
 }

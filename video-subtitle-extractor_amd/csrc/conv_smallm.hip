@@ -75,16 +75,20 @@ __global__ __launch_bounds__(64) void conv_smallm_hl_kernel(const ConvParams p) 
     conv_smallm_body<KT, true>(p, sbias);
 }
 
-// Which layers it serves: conv_select() (conv_select.hip).  k.arg[0] = KT, k.arg[1] = hi + lo.
-int launch_conv_smallm(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+// arg = KT, hi + lo; which layers it serves: conv_select() (conv_select.hip)
+static const ConvInst kSmallmInst[] = {
+    CONV_INST(32, 1, 0, conv_smallm_hl_kernel<32>), CONV_INST(64, 1, 0, conv_smallm_hl_kernel<64>),
+    CONV_INST(32, 0, 0, conv_smallm_kernel<32>), CONV_INST(64, 0, 0, conv_smallm_kernel<64>),
+};
+
+static int launch_conv_smallm(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+    const ConvInst* inst = conv_inst(conv_smallm_family(), k);
+    if (!inst) return VSE_E_UNSUPPORTED;
     ConvParams p = pin;
     p.nkh = p.nkh * 32 / k.arg[0];           // K tiles of one weight pass (nkh = Kp / 32 on entry)
     if ((p.M + 31) / 32 > 65535) return VSE_E_UNSUPPORTED;
     const dim3 grid((unsigned)((p.Np + 31) / 32), (unsigned)((p.M + 31) / 32)), block(64);
-    if (k.arg[1]) {
-        if (k.arg[0] == 32) hipLaunchKernelGGL((conv_smallm_hl_kernel<32>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((conv_smallm_hl_kernel<64>), grid, block, 0, st, p);
-    } else if (k.arg[0] == 32) hipLaunchKernelGGL((conv_smallm_kernel<32>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((conv_smallm_kernel<64>), grid, block, 0, st, p);
+    hipLaunchKernelGGL(inst->fn, grid, block, 0, st, p);
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
+ConvFamily conv_smallm_family() { return conv_family(launch_conv_smallm, kSmallmInst); }

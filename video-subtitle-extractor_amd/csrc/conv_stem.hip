@@ -28,7 +28,7 @@
 // from the uint8 BGR frame (cv2 fixed-point INTER_LINEAR, resize_u8.h: the bytes det_preprocess_kernel writes) and stages
 // [u0, u1, u2, 1] as fp16 (exact); the stem's weights carry the normalisation (compiler input_norm).  The 8-channel fp16 detector
 // input (8.4 MB per 544 x 960 frame) is never written or read.
-template <int SH, int SW, bool HILO, bool U8 = false>
+template <int SH, int SW, bool HILO, bool U8>
 __global__ __launch_bounds__(256) void conv_stem_kernel(const ConvParams p) {
     constexpr int PH_ = (ST_ROWS - 1) * SH + 3, PW_ = (ST_COLS - 1) * SW + 3, NPIX = PH_ * PW_;
     constexpr int NPIX4 = (NPIX * 4 + 7) & ~7;                                   // 16-byte aligned start of the weight tables
@@ -224,8 +224,17 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(const ConvParams p) {
     }
 }
 
-// k.arg = S, HILO, U8
-int launch_conv_stem(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+// arg = S (the stride, both ways), HILO, U8
+static const ConvInst kStemInst[] = {
+    CONV_INST(2, 1, 1, conv_stem_kernel<2, 2, true, true>),   CONV_INST(2, 0, 1, conv_stem_kernel<2, 2, false, true>),
+    CONV_INST(1, 1, 1, conv_stem_kernel<1, 1, true, true>),   CONV_INST(1, 0, 1, conv_stem_kernel<1, 1, false, true>),
+    CONV_INST(2, 1, 0, conv_stem_kernel<2, 2, true, false>),  CONV_INST(2, 0, 0, conv_stem_kernel<2, 2, false, false>),
+    CONV_INST(1, 1, 0, conv_stem_kernel<1, 1, true, false>),  CONV_INST(1, 0, 0, conv_stem_kernel<1, 1, false, false>),
+};
+
+static int launch_conv_stem(const ConvParams& pin, const ConvKernel& k, hipStream_t st) {
+    const ConvInst* inst = conv_inst(conv_stem_family(), k);
+    if (!inst) return VSE_E_UNSUPPORTED;
     ConvParams p = pin;
     if (p.kh != 3 || p.kw != 3 || p.ph != 1 || p.pw != 1 || p.cinp != 8 || p.inshift != 0 || p.Np > 64 || p.Np < 1) return VSE_E_INVAL;
     if (p.flags & (F_PIXSHUF | F_DOT1 | F_SRC2 | F_PATCH | F_UP2HEAD)) return VSE_E_INVAL;
@@ -234,19 +243,8 @@ int launch_conv_stem(const ConvParams& pin, const ConvKernel& k, hipStream_t st)
     p.tiles_w = (p.OW + ST_COLS - 1) / ST_COLS;
     const unsigned long long blocks = (unsigned long long)conv_images(p) * p.tiles_h * p.tiles_w;
     if (blocks == 0 || blocks > 0x7fffffffull) return VSE_E_INVAL;
-    const dim3 grid((unsigned)blocks), block(256);
-    const bool s2 = k.arg[0] == 2, hilo = k.arg[1];
-    if (k.arg[2]) {
-        if (!p.u8src || p.u8_h <= 0 || p.u8_w < 3) return VSE_E_INVAL;          // (8-byte row loads: >= 9 bytes per source row)
-        if (s2 && hilo) hipLaunchKernelGGL((conv_stem_kernel<2, 2, true, true>), grid, block, 0, st, p);
-        else if (s2) hipLaunchKernelGGL((conv_stem_kernel<2, 2, false, true>), grid, block, 0, st, p);
-        else if (hilo) hipLaunchKernelGGL((conv_stem_kernel<1, 1, true, true>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((conv_stem_kernel<1, 1, false, true>), grid, block, 0, st, p);
-        return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
-    }
-    if (s2 && hilo) hipLaunchKernelGGL((conv_stem_kernel<2, 2, true>), grid, block, 0, st, p);
-    else if (s2) hipLaunchKernelGGL((conv_stem_kernel<2, 2, false>), grid, block, 0, st, p);
-    else if (hilo) hipLaunchKernelGGL((conv_stem_kernel<1, 1, true>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((conv_stem_kernel<1, 1, false>), grid, block, 0, st, p);
+    if (k.arg[2] && (!p.u8src || p.u8_h <= 0 || p.u8_w < 3)) return VSE_E_INVAL;          // (8-byte row loads: >= 9 bytes per source row)
+    hipLaunchKernelGGL(inst->fn, dim3((unsigned)blocks), dim3(256), 0, st, p);
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
+ConvFamily conv_stem_family() { return conv_family(launch_conv_stem, kStemInst); }
