@@ -255,6 +255,32 @@ size_t vse_audio_match_workspace_bytes(const vse_audio_query* queries, int nq);
 int vse_audio_match(vse_ctx* ctx, const uint8_t* d_src, int64_t src_len, const uint8_t* d_dst, int64_t dst_len,
                     const vse_audio_query* queries, int nq, void* d_ws, size_t ws_bytes, vse_audio_match_result* d_out, void* stream);
 
+/* ---- timeline sync: scene cuts for keyframe snapping ------------------------------------------------------------------- */
+/* Replaces: the keyframes Sushi makes by piping the video through ffmpeg (scale=640:360) into SCXvid, an XviD first pass whose
+ * I-frame decisions mark the scene cuts (backend/sushi/demux.py:113-135).  Not XviD's algorithm but the same role: per frame, how
+ * many 16 x 16 macroblocks of a small luma plane the previous frame cannot predict within a search range; the host turns the
+ * counts into keyframes (vse_amd.keyframes.SceneCutDetector).  All integer arithmetic:
+ *   Y = (29 B + 150 G + 77 R + 128) >> 8;
+ *   plane A[y][x] = (sum of the scale x scale luma box at (y scale, x scale) + scale scale / 2) / (scale scale), of
+ *     ah = src_h / scale rows and aw = src_w / scale columns (source rows / columns beyond ah scale / aw scale are not read);
+ *   macroblocks: bh = ah / 16 by bw = aw / 16 (plane rows / columns beyond them belong to no block but are reference pixels);
+ *   inter_b = min over (dy, dx) in [-search, search]^2 of sum |A_t[16 by + y][16 bx + x] - P[16 by + dy + y][16 bx + dx + x]|,
+ *     P = the plane of frame t - 1, over the vectors whose displaced block lies wholly inside the plane;
+ *   m_b = (sum A_t + 128) >> 8, intra_b = sum |A_t - m_b|; block b is changed iff 2 inter_b > intra_b + bias;
+ *   d_counts[t] = (changed blocks, sum_b inter_b, sum_b intra_b); a frame without a predecessor gives (bh bw, 0, sum_b intra_b).
+ * d_state (vse_scene_change_state_bytes, 8-byte aligned, fresh = zero-filled) holds a flag and the last frame's plane after the
+ * call, and the first frame of the next call is compared with it: batches of any size give the counts of one batch.  With
+ * `reset`, or on a fresh state, the first frame has no predecessor.  d_ws (vse_scene_change_workspace_bytes, 4-byte aligned)
+ * holds the planes of the call.  Three launches on `stream`, no allocation, no device sync.
+ * Returns VSE_E_INVAL, and launches nothing, when scale is not in 1..8, search not in 0..8, bias not in 0..65535, ah or aw < 16,
+ * aw ah > 2^23 (the int32 sums stay exact below it), n is not in 1..65535 or the workspace is too small.
+ * The two size functions return 0 for a frame size and scale the call would refuse. */
+size_t vse_scene_change_state_bytes(int src_h, int src_w, int scale);
+size_t vse_scene_change_workspace_bytes(int n, int src_h, int src_w, int scale);
+int vse_scene_change(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int scale,
+                     int search, int bias, void* d_state, int reset, void* d_ws, size_t ws_bytes,
+                     int32_t* d_counts /* [n,3]: changed blocks, sum inter, sum intra */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,9 @@ struct vse_plan {
 
 int vse_frame_change_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
                             void* d_state, int reset, int32_t* d_counts, void* stream);     // frame_change.hip
+int vse_scene_change_plane_pitch(int aw);                                                                              // scene_cut.hip
+int vse_scene_change_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int scale, int ah, int aw, int search, int bias,
+                            void* d_state, int reset, void* d_ws, int32_t* d_counts, void* stream);
 size_t vse_audio_match_ws(const long* m, const long* n, int nq);                                                       // audio_match.hip
 int vse_audio_match_launch(const uint8_t* const* pat, const uint8_t* const* win, const long* m, const long* n, int nq, void* d_ws,
                            unsigned long long* d_out, void* stream);
@@ -409,6 +412,56 @@ int vse_frame_change(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w,
         return VSE_E_INVAL;
     }
     return vse_frame_change_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, d_state, reset, d_counts, stream);
+}
+
+// ---- timeline sync: scene cuts for keyframe snapping (scene_cut.hip) ---------------------------------------------------------
+// -> plane size; false when scale is out of range, the plane holds no macroblock or aw * ah > 2^23 (the int32 sums stay exact)
+static bool scene_plane_size(int src_h, int src_w, int scale, int* ah, int* aw) {
+    if (scale < 1 || scale > 8 || src_h <= 0 || src_w <= 0) return false;
+    *ah = src_h / scale;
+    *aw = src_w / scale;
+    return *ah >= 16 && *aw >= 16 && (int64_t)*ah * *aw <= (int64_t)1 << 23;
+}
+
+size_t vse_scene_change_state_bytes(int src_h, int src_w, int scale) {
+    int ah, aw;
+    if (!scene_plane_size(src_h, src_w, scale, &ah, &aw)) return 0;
+    return 16 + (size_t)ah * vse_scene_change_plane_pitch(aw);
+}
+
+size_t vse_scene_change_workspace_bytes(int n, int src_h, int src_w, int scale) {
+    int ah, aw;
+    if (n <= 0 || !scene_plane_size(src_h, src_w, scale, &ah, &aw)) return 0;
+    return (size_t)n * ah * vse_scene_change_plane_pitch(aw);
+}
+
+int vse_scene_change(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int scale, int search,
+                     int bias, void* d_state, int reset, void* d_ws, size_t ws_bytes, int32_t* d_counts, void* stream) {
+    if (!c || !d_bgr || !d_state || !d_ws || !d_counts || n <= 0 || n > 65535 || src_h <= 0 || src_w <= 0 || pitch < (int64_t)src_w * 3 ||
+        (n > 1 && frame_stride < (int64_t)(src_h - 1) * pitch + (int64_t)src_w * 3) || (reinterpret_cast<uintptr_t>(d_state) & 7) ||
+        (reinterpret_cast<uintptr_t>(d_ws) & 3)) {
+        set_err("vse_scene_change: bad arguments (n %d of 1..65535, frame %d x %d, pitch %lld, frame stride %lld, state 8-byte and workspace "
+                "4-byte aligned)", n, src_h, src_w, (long long)pitch, (long long)frame_stride);
+        return VSE_E_INVAL;
+    }
+    if (search < 0 || search > 8 || bias < 0 || bias > 65535) {
+        set_err("vse_scene_change: search radius %d (0..8) or bias %d (0..65535) out of range", search, bias);
+        return VSE_E_INVAL;
+    }
+    int ah, aw;
+    if (!scene_plane_size(src_h, src_w, scale, &ah, &aw)) {
+        set_err("vse_scene_change: scale %d (1..8) on a %d x %d frame: the plane must be at least 16 x 16 and at most 2^23 pixels", scale, src_h,
+                src_w);
+        return VSE_E_INVAL;
+    }
+    const size_t need = vse_scene_change_workspace_bytes(n, src_h, src_w, scale);
+    if (ws_bytes < need) {
+        set_err("vse_scene_change: workspace of %zu bytes, %zu needed", ws_bytes, need);
+        return VSE_E_INVAL;
+    }
+    const int rc = vse_scene_change_launch(d_bgr, n, pitch, frame_stride, scale, ah, aw, search, bias, d_state, reset, d_ws, d_counts, stream);
+    if (rc != VSE_OK) set_err("vse_scene_change: launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
 }
 
 // ---- timeline sync: audio template search (audio_match.hip) ------------------------------------------------------------------

@@ -20,7 +20,8 @@ EXPORTS = [
     "vse_db_postprocess", "vse_rec_preprocess", "vse_rec_preprocess_scratch_bytes", "vse_ctc_collapse", "vse_ctc_collapse_ragged",
     "vse_det_forward", "vse_rec_forward", "vse_plan_set_source", "vse_plan_takes_frames",
     "vse_rec_graph_create", "vse_graph_launch", "vse_graph_destroy", "vse_frame_change_state_bytes", "vse_frame_change",
-    "vse_audio_match_workspace_bytes", "vse_audio_match",
+    "vse_audio_match_workspace_bytes", "vse_audio_match", "vse_scene_change_state_bytes", "vse_scene_change_workspace_bytes",
+    "vse_scene_change",
 ]
 
 
@@ -121,6 +122,12 @@ def load_library(path=None):
     lib.vse_audio_match_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
     lib.vse_audio_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
                                     C.c_size_t, C.c_void_p, C.c_void_p]
+    lib.vse_scene_change_state_bytes.restype = C.c_size_t
+    lib.vse_scene_change_state_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.vse_scene_change_workspace_bytes.restype = C.c_size_t
+    lib.vse_scene_change_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.vse_scene_change.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     if lib.vse_sizeof_op() != ir.OP_DT.itemsize or lib.vse_sizeof_view() != ir.VIEW_DT.itemsize:
         raise VseError(f"ABI mismatch: vse_op {lib.vse_sizeof_op()} vs {ir.OP_DT.itemsize}, "
                        f"vse_view {lib.vse_sizeof_view()} vs {ir.VIEW_DT.itemsize}")
@@ -381,6 +388,34 @@ class Context:
         _check(self.lib.vse_audio_match(self.handle, C.c_void_p(src_u8.data_ptr()), src_u8.numel(), C.c_void_p(dst_u8.data_ptr()),
                                         dst_u8.numel(), C.c_void_p(q.ctypes.data), len(q), C.c_void_p(workspace.data_ptr()),
                                         workspace.numel(), C.c_void_p(out.data_ptr()), self.stream()), "vse_audio_match")
+        return out
+
+    # ---- timeline sync: scene cuts for keyframe snapping ----------------------------------------------------------
+    def scene_change_state(self, h, w, scale):
+        """A fresh (zero-filled) state for scene_change over frames of h x w pixels at this scale."""
+        nbytes = self.lib.vse_scene_change_state_bytes(int(h), int(w), int(scale))
+        if not nbytes:
+            raise VseError(f"scene_change: scale {scale} on {h} x {w} frames: the plane must be 16 x 16 .. 2^23 pixels, the scale 1..8")
+        return self.torch.zeros(nbytes, dtype=self.torch.uint8, device=self.tdev)
+
+    def scene_change(self, frames_u8, scale, search, bias, state, reset=False, workspace=None):
+        """frames_u8: cuda uint8 [n,H,W,3] (any row pitch / frame stride, pixels packed), state: scene_change_state of this frame
+        size and scale (carries the last frame's plane to the next call) -> cuda int32 [n,3]: changed macroblocks, sum of the
+        blocks' best inter SADs, sum of their intra deviations per frame (include/vse_hip.h vse_scene_change).
+        workspace: cuda uint8 of at least vse_scene_change_workspace_bytes (allocated if None)."""
+        t = self.torch
+        assert frames_u8.dtype == t.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
+        assert frames_u8.stride(3) == 1 and frames_u8.stride(2) == 3
+        n, h, w, _ = frames_u8.shape
+        assert state.dtype == t.uint8 and state.is_contiguous()
+        assert state.numel() >= max(self.lib.vse_scene_change_state_bytes(h, w, int(scale)), 1)
+        if workspace is None:
+            workspace = t.empty(max(self.lib.vse_scene_change_workspace_bytes(n, h, w, int(scale)), 256), dtype=t.uint8, device=self.tdev)
+        out = t.empty((n, 3), dtype=t.int32, device=self.tdev)
+        _check(self.lib.vse_scene_change(self.handle, C.c_void_p(frames_u8.data_ptr()), n, h, w, frames_u8.stride(1), frames_u8.stride(0),
+                                         int(scale), int(search), int(bias), C.c_void_p(state.data_ptr()), int(bool(reset)),
+                                         C.c_void_p(workspace.data_ptr()), workspace.numel(), C.c_void_p(out.data_ptr()), self.stream()),
+               "vse_scene_change")
         return out
 
 

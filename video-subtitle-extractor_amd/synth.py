@@ -117,6 +117,66 @@ def make_clip(schedule, height=360, width=640, seed=0):
     return frames, truth
 
 
+def make_scenes(scenes, height=360, width=640, seed=0):
+    """A clip of camera shots for the scene-cut finder: uint8 BGR [n,height,width,3] + the 0-based number of each scene's first frame.
+
+    scenes: a list of dicts, one per scene:
+      frames  number of frames;
+      pan     (dy, dx) source pixels the camera moves per frame, or a list of per-frame (dy, dx) steps (frame k of the scene is
+              displaced by the sum of the first k steps; a short list repeats its last step); default (0, 0);
+      hold    in-scene frame indices (>= 1) that repeat the frame before them byte for byte (a held frame);
+      text    (text, first, last): a subtitle line drawn over in-scene frames first..last, centred in the lower band.
+    A scene is a window into its own textured world (random 32- and 8-pixel cells around the scene's own mean colour), so a pan
+    shows the same texture displaced; every frame that is not held gets fresh noise of +-3 levels.  make_clip redraws its whole
+    background every frame and so has no motion to find."""
+    rng = np.random.default_rng(seed)
+    n = sum(int(sc["frames"]) for sc in scenes)
+    out = np.empty((n, height, width, 3), np.uint8)
+    cuts, f = [], 0
+    for sc in scenes:
+        count = int(sc["frames"])
+        pan = sc.get("pan", (0, 0))
+        steps = [tuple(pan)] if isinstance(pan[0], (int, np.integer)) else [tuple(p) for p in pan]
+        pos = [(0, 0)]
+        for k in range(1, count):
+            dy, dx = steps[min(k - 1, len(steps) - 1)]
+            pos.append((pos[-1][0] + int(dy), pos[-1][1] + int(dx)))
+        y_min, x_min = min(p[0] for p in pos), min(p[1] for p in pos)
+        wh = height + max(p[0] for p in pos) - y_min
+        ww = width + max(p[1] for p in pos) - x_min
+        mean = rng.integers(70, 186, size=3)
+        world = np.zeros((wh, ww, 3), np.int32) + mean
+        for cell, amp in ((32, 50), (8, 25)):
+            t = rng.integers(-amp, amp + 1, size=((wh + cell - 1) // cell, (ww + cell - 1) // cell, 1))
+            world += np.repeat(np.repeat(t, cell, 0), cell, 1)[:wh, :ww]
+        np.clip(world, 8, 247, out=world)
+        glyph = None
+        if sc.get("text"):
+            text, first, last = sc["text"]
+            gh = max(12, int(60 * height / 1080.0))
+            fill, outline = render_line(text, gh, np.random.default_rng([seed, *text.encode()]))
+            lw = min(fill.shape[1], int(0.88 * width))
+            glyph = (fill[:, :lw], outline[:, :lw], int(first), int(last))
+        hold = set(sc.get("hold", ()))
+        cuts.append(f)
+        for k in range(count):
+            if k in hold and k > 0:
+                out[f] = out[f - 1]
+            else:
+                y, x = pos[k][0] - y_min, pos[k][1] - x_min
+                img = world[y:y + height, x:x + width] + rng.integers(-3, 4, size=(height, width, 3))
+                if glyph is not None and glyph[2] <= k <= glyph[3]:
+                    fill, outline = glyph[0], glyph[1]
+                    lh, lw = fill.shape
+                    yy = min(int(0.99 * height) - lh - 8, height - lh - 2)
+                    reg = img[yy:yy + lh, (width - lw) // 2:(width - lw) // 2 + lw]
+                    reg[outline > 0] = 0
+                    reg[fill > 0] = 255
+                out[f] = np.clip(img, 0, 255).astype(np.uint8)
+            f += 1
+    return out, cuts
+
+
 # ---- audio for timeline sync ---------------------------------------------------------------------------------------------------
 # Built from the bit generator's raw 64-bit words and integer arithmetic only, so a seed gives the same samples (and WAV bytes)
 # on any numpy.  Content is made at AUDIO_BASE_RATE and held (sample-and-hold) to any output rate, so two renders of the same

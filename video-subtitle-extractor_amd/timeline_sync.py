@@ -6,11 +6,18 @@ so a script comes out byte for byte as Sushi writes it.  The one hot step, the t
 window of the destination audio (WavStream.find_substream, backend/sushi/wav.py:179-189), runs on the GPU
 (vse_audio_match, csrc/audio_match.hip); the three searches of one step of the loop go to the device as one call.
 
-Inputs are WAV files only: the project has no demuxer, so keyframes, timecodes, chapters and stream selection stay out.
+Sushi's second half is here too: shifted lines snap to scene cuts ("keyframes") of both releases, so a subtitle starts on the cut
+it started on in the source (snap_groups_to_keyframes and what it calls, with the same float operations in the same order).
+Keyframes come as files in Sushi's format or as lists of frame numbers, frame times from a constant fps or a timecodes file (v1 /
+v2); `python -m vse_amd.keyframes` finds a video's cuts on the GPU and writes such a file.
+
+Inputs are WAV files only: the project has no demuxer, so chapters, stream selection and keyframes made on the fly stay out.
 
     python -m vse_amd.timeline_sync --src a.wav --dst b.wav --script in.srt --output out.srt
+        [--src-keyframes a.kf.txt --dst-keyframes b.kf.txt --src-fps 23.976 --dst-fps 23.976]
 """
 import argparse
+import bisect
 import logging
 import math
 import os
@@ -279,10 +286,30 @@ class Event:
         assert other.chain_end() is not self, "circular link"
         self._link = other
 
+    def resolve_link(self):
+        assert self.linked
+        self._shift, self._diff = self._link.shift, self._link.diff
+        self._link = None
+
+    def adjust_shift(self, value):
+        assert not self.linked
+        self._shift += value
+
+    def adjust_additional_shifts(self, start_shift, end_shift):
+        assert not self.linked
+        self._start_shift += start_shift
+        self._end_shift += end_shift
+
+    @property
+    def shifted_start(self):
+        return self.start + self.shift + self._start_shift
+
+    @property
+    def shifted_end(self):
+        return self.end + self.shift + self._end_shift
+
     def apply_shift(self):
-        start = self.start + self.shift + self._start_shift
-        end = self.end + self.shift + self._end_shift
-        self.start, self.end = start, end
+        self.start, self.end = self.shifted_start, self.shifted_end
 
 
 _SRT_TIME = r"\d{1,2}:\d{1,2}:\d{1,2},\d+"
@@ -611,15 +638,264 @@ def calculate_shifts(searcher, src, dst, groups, normal_window, max_window, rewi
                 e.set_shift(s["shift"], s["diff"])
 
 
+# ---- frame times (backend/sushi/demux.py:138-227) ---------------------------------------------------------------------------------
+
+class CfrTimecodes:
+    """Constant frame rate: frame n starts at n * (1 / fps)."""
+
+    def __init__(self, fps):
+        self.frame_duration = 1.0 / fps
+
+    def get_frame_time(self, number):
+        return number * self.frame_duration
+
+    def get_frame_size(self, timestamp):
+        return self.frame_duration
+
+    def get_frame_number(self, timestamp):
+        return int(timestamp / self.frame_duration)
+
+
+class Timecodes:
+    """Frame start times from a timecodes file.  v2 lists every frame's time in ms and has no default rate: a frame past the list
+    takes the last time.  v1 gives a default fps and `first,last,fps` overrides: the list covers the frames up to the last
+    override (empty without overrides) and the default rate continues it."""
+
+    def __init__(self, times, default_fps):
+        self.times = times
+        self.default_frame_duration = 1.0 / default_fps if default_fps else None
+
+    def get_frame_time(self, number):
+        if -len(self.times) <= number < len(self.times):
+            return self.times[number]          # (a negative number counts from the end, as it does in Sushi's list lookup)
+        if not self.default_frame_duration:
+            if not self.times:
+                raise TimelineSyncError("The timecodes file lists no frame")
+            return self.times[-1]
+        if self.times:
+            return self.times[-1] + self.default_frame_duration * (number - len(self.times) + 1)
+        return number * self.default_frame_duration
+
+    def get_frame_number(self, timestamp):
+        if (not self.times or self.times[-1] < timestamp) and self.default_frame_duration:
+            return int((timestamp - sum(self.times)) / self.default_frame_duration)         # (the sum is Sushi's)
+        return bisect.bisect_left(self.times, timestamp)
+
+    def get_frame_size(self, timestamp):
+        number = bisect.bisect_left(self.times, timestamp)
+        c = self.get_frame_time(number)
+        if number == len(self.times):
+            return c - self.get_frame_time(number - 1)
+        return self.get_frame_time(number + 1) - c
+
+    @classmethod
+    def cfr(cls, fps):
+        return CfrTimecodes(fps)
+
+    @classmethod
+    def parse(cls, text):
+        lines = text.splitlines()
+        first = lines[0].lower().lstrip() if lines else ""
+        try:
+            if first.startswith("# timecode format v2") or first.startswith("# timestamp format v2"):
+                return cls([float(x) / 1000.0 for x in lines[1:]], None)
+            if first.startswith("# timecode format v1"):
+                default = float(lines[1].lower().replace("assume ", ""))
+                overrides = [(int(x[0]), int(x[1]), float(x[2])) for x in (ln.split(",") for ln in lines[2:])]
+                times = []
+                if overrides:
+                    fps = [default] * (overrides[-1][1] + 1)
+                    for a, b, f in overrides:
+                        fps[a:b + 1] = [f] * (b - a + 1)
+                    times = [0]
+                    for d in (1.0 / f for f in fps):
+                        times.append(times[-1] + d)
+                return cls(times, default)
+        except (ValueError, IndexError) as e:
+            raise TimelineSyncError(f"Malformed timecodes file: {e}")
+        raise TimelineSyncError("This timecodes format is not supported")
+
+    @classmethod
+    def from_file(cls, path):
+        try:
+            with open(path) as f:
+                return cls.parse(f.read())
+        except OSError:
+            raise TimelineSyncError(f"Timecodes file {path} not found")
+
+
+# ---- keyframe snapping (backend/sushi/__init__.py:33-56, 180-268) --------------------------------------------------------------------
+
+def interpolate_nones(data, points):
+    """The None entries of `data` take the value interpolated linearly over `points` from the entries that have one; [] when none
+    has."""
+    known = {p: v for p, v in zip(points, data) if v is not None}
+    if not known:
+        return []
+    missing = {p for p, v in zip(points, data) if v is None}
+    if not missing:
+        return data
+    table = sorted(known.items())
+    missing = sorted(x for x in missing if x not in known)
+    known.update(zip(missing, np.interp(x=missing, xp=[p for p, _ in table], fp=[v for _, v in table])))
+    return [known[p] if v is None else v for p, v in zip(points, data)]
+
+
+def get_distance_to_closest_kf(timestamp, keytimes):
+    """Signed distance to the nearest keyframe time (the earlier one on a tie)."""
+    idx = bisect.bisect_left(keytimes, timestamp)
+    if idx == 0:
+        kf = keytimes[0]
+    elif idx == len(keytimes):
+        kf = keytimes[-1]
+    else:
+        before, after = keytimes[idx - 1], keytimes[idx]
+        kf = after if after - timestamp < timestamp - before else before
+    return kf - timestamp
+
+
+def find_keyframe_shift(group, src_keytimes, dst_keytimes, src_timecodes, dst_timecodes, max_kf_distance):
+    """-> (start correction, end correction) of a group, None where the destination keyframe is further than the limit or the
+    correction itself would reach it."""
+    def distance(src_distance, dst_distance, limit):
+        if abs(dst_distance) > limit:
+            return None
+        shift = dst_distance - src_distance
+        return shift if abs(shift) < limit else None
+
+    first, last = group[0], group[-1]
+    src_start = get_distance_to_closest_kf(first.start, src_keytimes)
+    src_end = get_distance_to_closest_kf(last.end + src_timecodes.get_frame_size(last.end), src_keytimes)
+    dst_start = get_distance_to_closest_kf(first.shifted_start, dst_keytimes)
+    dst_end = get_distance_to_closest_kf(last.shifted_end + dst_timecodes.get_frame_size(last.end), dst_keytimes)
+    limit_start = src_timecodes.get_frame_size(first.start) * max_kf_distance
+    limit_end = src_timecodes.get_frame_size(first.end) * max_kf_distance
+    return distance(src_start, dst_start, limit_start), distance(src_end, dst_end, limit_end)
+
+
+def find_keyframes_distances(event, src_keytimes, dst_keytimes, timecodes, max_kf_distance):
+    """-> (start, end): how much further the destination keyframe is than the source one, 0 unless both and their difference are
+    within the limit."""
+    def distance(src_time, dst_time):
+        src = get_distance_to_closest_kf(src_time, src_keytimes)
+        dst = get_distance_to_closest_kf(dst_time, dst_keytimes)
+        limit = timecodes.get_frame_size(src_time) * max_kf_distance
+        if abs(src) < limit and abs(dst) < limit and abs(src - dst) < limit:
+            return dst - src
+        return 0
+
+    return distance(event.start, event.shifted_start), distance(event.end, event.shifted_end)
+
+
+def snap_groups_to_keyframes(events, chapter_times, max_ts_duration, max_ts_distance, src_keytimes, dst_keytimes, src_timecodes,
+                             dst_timecodes, max_kf_distance, kf_mode):
+    if not max_kf_distance:
+        return
+    groups = merge_short_lines_into_groups(events, chapter_times, max_ts_duration, max_ts_distance)
+
+    if kf_mode in ("all", "shift"):
+        # step 1: move whole lines without changing their duration (corrects a slightly imprecise audio shift)
+        shifts, times = [], []
+        for g in groups:
+            shifts.extend(find_keyframe_shift(g, src_keytimes, dst_keytimes, src_timecodes, dst_timecodes, max_kf_distance))
+            times.extend((g[0].shifted_start, g[-1].shifted_end))
+        shifts = interpolate_nones(shifts, times)
+        if len(shifts):
+            mean_shift = np.mean(shifts)
+            log.info("group %s-%s corrected by %s", format_time(events[0].start), format_time(events[-1].end), mean_shift)
+            for g, (start_shift, end_shift) in zip(groups, zip(*[iter(shifts)] * 2)):
+                if abs(start_shift - end_shift) > 0.001 and len(g) > 1:
+                    actual = min(start_shift, end_shift, key=lambda x: abs(x - mean_shift))
+                    log.warning("typesetting group at %s had different shifts at its start and end (%s and %s), shifting by %s",
+                                format_time(g[0].start), start_shift, end_shift, actual)
+                    for e in g:
+                        e.adjust_shift(actual)
+                else:
+                    for e in g:
+                        e.adjust_additional_shifts(start_shift, end_shift)
+
+    if kf_mode in ("all", "snap"):
+        # step 2: snap start and end separately (Sushi snaps the first line of a typesetting group too)
+        for g in groups:
+            start_shift, end_shift = find_keyframes_distances(g[0], src_keytimes, dst_keytimes, src_timecodes, max_kf_distance)
+            if abs(start_shift) > 0.01 or abs(end_shift) > 0.01:
+                log.info("snapping %s to keyframes, start by %s, end by %s", format_time(g[0].start), start_shift, end_shift)
+                g[0].adjust_additional_shifts(start_shift, end_shift)
+
+
+KF_OPTIONS = ("src_keyframes", "dst_keyframes", "src_fps", "dst_fps", "src_timecodes", "dst_timecodes")
+
+
+def _flag(name):
+    return "--" + name.replace("_", "-")
+
+
+def check_keyframe_options(src_keyframes=None, dst_keyframes=None, src_fps=None, dst_fps=None, src_timecodes=None, dst_timecodes=None,
+                           also_given=()):
+    """Refuse (TimelineSyncError naming the option) what Sushi refuses, and what it silently ignores.  also_given: further options
+    the caller saw (--kf-mode, --max-kf-distance) that have no effect without keyframes."""
+    v = dict(src_keyframes=src_keyframes, dst_keyframes=dst_keyframes, src_fps=src_fps, dst_fps=dst_fps, src_timecodes=src_timecodes,
+             dst_timecodes=dst_timecodes)
+    have = [k for k in ("src_keyframes", "dst_keyframes") if v[k] is not None]
+    if len(have) == 1:
+        other = "dst_keyframes" if have[0] == "src_keyframes" else "src_keyframes"
+        raise TimelineSyncError(f"{_flag(have[0])} without {_flag(other)}: either none or both of src and dst keyframes should be provided")
+    if not have:
+        useless = [_flag(k) for k in KF_OPTIONS[2:] if v[k] is not None] + list(also_given)
+        if useless:
+            raise TimelineSyncError(f"{', '.join(useless)}: no effect without --src-keyframes and --dst-keyframes")
+        return False
+    for side in ("src", "dst"):
+        kf, fps, tc = v[side + "_keyframes"], v[side + "_fps"], v[side + "_timecodes"]
+        if isinstance(kf, str):
+            if kf in ("auto", "make"):
+                raise TimelineSyncError(f"{_flag(side + '_keyframes')} {kf}: the inputs are WAV files, there is no video to make keyframes "
+                                        "from; make the file with `python -m vse_amd.keyframes VIDEO -o keyframes.txt`")
+            if not os.path.exists(kf):
+                raise TimelineSyncError(f"{_flag(side + '_keyframes')}: file {kf} doesn't exist")
+        if tc is not None and not os.path.exists(tc):
+            raise TimelineSyncError(f"{_flag(side + '_timecodes')}: file {tc} doesn't exist")
+        if fps is not None and tc is not None:
+            raise TimelineSyncError(f"{_flag(side + '_fps')} and {_flag(side + '_timecodes')}: both fps and timecodes file cannot be specified "
+                                    "at the same time")
+        if fps is None and tc is None:
+            raise TimelineSyncError(f"{_flag(side + '_keyframes')} needs {_flag(side + '_fps')} or {_flag(side + '_timecodes')}: fps or "
+                                    "timecodes must be provided if keyframes are used")
+        if fps is not None and not fps > 0:
+            raise TimelineSyncError(f"{_flag(side + '_fps')} {fps}: not a frame rate")
+    return True
+
+
+def _keytimes(keyframes, fps, timecodes_path):
+    """-> (timecodes, keyframe times) of one side; keyframes: a path (Sushi's file format) or a list of frame numbers."""
+    tc = Timecodes.cfr(fps) if fps else Timecodes.from_file(timecodes_path)
+    if isinstance(keyframes, str):
+        from .keyframes import parse_keyframes
+        frames = parse_keyframes(keyframes)
+    else:
+        frames = [int(f) for f in keyframes]
+        if 0 not in frames:
+            frames.insert(0, 0)
+    return tc, [tc.get_frame_time(f) for f in frames]
+
+
 def _extension(path):
     return os.path.splitext(path)[1].lower()
 
 
 def sync(src_wav, dst_wav, script_path, output_path, *, window=10, max_window=30, rewind_thresh=5, grouping=True, smooth_radius=3,
-         max_ts_duration=1001.0 / 24000.0 * 10, max_ts_distance=1001.0 / 24000.0 * 10, sample_rate=12000, search=None):
+         max_ts_duration=1001.0 / 24000.0 * 10, max_ts_distance=1001.0 / 24000.0 * 10, sample_rate=12000, search=None,
+         src_keyframes=None, dst_keyframes=None, src_fps=None, dst_fps=None, src_timecodes=None, dst_timecodes=None, max_kf_distance=2,
+         kf_mode="all"):
     """Retime `script_path` (.srt or .ass) from the audio of `src_wav` onto that of `dst_wav`, write `output_path` (same type).
     search: the searcher (None: the GPU one, GpuSearch).  Returns the searches made, in order:
-    [(src_off, m, dst_off, win_len, index, float32 value)] over the two uint8 streams."""
+    [(src_off, m, dst_off, win_len, index, float32 value)] over the two uint8 streams.
+    src_keyframes / dst_keyframes (both or none): a keyframes file or a list of frame numbers; each side then needs src_fps /
+    dst_fps or src_timecodes / dst_timecodes (a v1 / v2 file).  Lines whose start or end lies within max_kf_distance frames of a
+    keyframe on both sides snap to it; kf_mode: "shift" (whole lines), "snap" (start and end separately) or "all"."""
+    use_kf = check_keyframe_options(src_keyframes, dst_keyframes, src_fps, dst_fps, src_timecodes, dst_timecodes)
+    if kf_mode not in ("all", "shift", "snap"):
+        raise TimelineSyncError(f"--kf-mode {kf_mode}: one of shift, snap, all")
     for path, what in ((src_wav, "Source"), (dst_wav, "Destination"), (script_path, "Script")):
         if not os.path.exists(path):
             raise TimelineSyncError(f"{what} file doesn't exist")
@@ -631,6 +907,14 @@ def sync(src_wav, dst_wav, script_path, output_path, *, window=10, max_window=30
         raise TimelineSyncError("Unknown script type")
     if _extension(output_path) != ext:
         raise TimelineSyncError(f"Source and destination script file types don't match ({ext} vs {_extension(output_path)})")
+
+    if use_kf:
+        src_timecodes, src_keytimes = _keytimes(src_keyframes, src_fps, src_timecodes)
+        dst_timecodes, dst_keytimes = _keytimes(dst_keyframes, dst_fps, dst_timecodes)
+
+    def snap(part):
+        snap_groups_to_keyframes(part, [], max_ts_duration, max_ts_distance, src_keytimes, dst_keytimes, src_timecodes, dst_timecodes,
+                                 max_kf_distance, kf_mode)
 
     script = (AssScript if ext == ".ass" else SrtScript).from_file(script_path)
     script.events.sort(key=lambda e: e.start)
@@ -644,9 +928,18 @@ def sync(src_wav, dst_wav, script_path, output_path, *, window=10, max_window=30
     fix_near_borders(events)
     if grouping:
         smooth_events([e for e in events if not e.linked], smooth_radius)
-        for g in detect_groups(events):
+        groups = detect_groups(events)
+        for g in groups:
             avg = average_shifts(g)
             log.info("group %s-%s: %d lines, shift %s", format_time(g[0].start), format_time(g[-1].end), len(g), avg)
+    else:
+        groups = [events]
+    if use_kf:
+        for e in events:
+            if e.linked:
+                e.resolve_link()
+        for g in groups:
+            snap(g)
     for e in events:
         e.apply_shift()
     script.save(output_path)
@@ -655,9 +948,7 @@ def sync(src_wav, dst_wav, script_path, output_path, *, window=10, max_window=30
 
 # ---- CLI -----------------------------------------------------------------------------------------------------------------------
 
-_REFUSED = ["--max-kf-distance", "--kf-mode", "--test-shift-plot", "--src-audio", "--src-script", "--dst-audio", "--no-cleanup",
-            "--temp-dir", "--chapters", "--dst-keyframes", "--src-keyframes", "--dst-fps", "--src-fps", "--dst-timecodes",
-            "--src-timecodes"]
+_REFUSED = ["--test-shift-plot", "--src-audio", "--src-script", "--dst-audio", "--no-cleanup", "--temp-dir", "--chapters"]
 
 
 def _parser():
@@ -676,6 +967,14 @@ def _parser():
     p.add_argument("--max-ts-distance", default=1001.0 / 24000.0 * 10, type=float)
     p.add_argument("--sample-rate", default=12000, type=int)
     p.add_argument("--sample-type", default="uint8")
+    p.add_argument("--src-keyframes", default=None, help="source keyframes file (python -m vse_amd.keyframes writes one)")
+    p.add_argument("--dst-keyframes", default=None, help="destination keyframes file")
+    p.add_argument("--src-fps", default=None, type=float, help="fps of the source video (or --src-timecodes)")
+    p.add_argument("--dst-fps", default=None, type=float, help="fps of the destination video (or --dst-timecodes)")
+    p.add_argument("--src-timecodes", default=None, help="timecodes file (v1 / v2) of the source video")
+    p.add_argument("--dst-timecodes", default=None, help="timecodes file (v1 / v2) of the destination video")
+    p.add_argument("--max-kf-distance", default=None, type=float, help="maximum keyframe snapping distance in frames [2]")
+    p.add_argument("--kf-mode", default=None, choices=["shift", "snap", "all"], help="keyframe correction mode [all]")
     p.add_argument("-v", "--verbose", action="store_true")
     for flag in _REFUSED:
         p.add_argument(flag, nargs="?", const=True, default=None, help=argparse.SUPPRESS)
@@ -692,10 +991,15 @@ def main(argv=None):
         print(f"timeline_sync: not supported: {', '.join(given)} (WAV inputs and uint8 streams only)", file=sys.stderr)
         return 2
     output = args.output or args.dst + ".sushi" + _extension(args.script)
+    kf = {k: getattr(args, k) for k in KF_OPTIONS}
     try:
+        # the option checks come before the WAV and script existence checks
+        check_keyframe_options(**kf, also_given=[f for f, x in (("--kf-mode", args.kf_mode), ("--max-kf-distance", args.max_kf_distance))
+                                                 if x is not None])
         sync(args.src, args.dst, args.script, output, window=args.window, max_window=args.max_window, rewind_thresh=args.rewind_thresh,
              grouping=args.grouping, smooth_radius=args.smooth_radius, max_ts_duration=args.max_ts_duration,
-             max_ts_distance=args.max_ts_distance, sample_rate=args.sample_rate)
+             max_ts_distance=args.max_ts_distance, sample_rate=args.sample_rate, **kf,
+             max_kf_distance=2 if args.max_kf_distance is None else args.max_kf_distance, kf_mode=args.kf_mode or "all")
     except TimelineSyncError as e:
         print(f"timeline_sync: {e}", file=sys.stderr)
         return 2
