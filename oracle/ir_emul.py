@@ -153,7 +153,14 @@ class Emulator:
         self.ext[0] = np.ascontiguousarray(x_nhwc8.astype(np.float16)).view(np.uint8).reshape(-1)
         for k, o in enumerate(prog.outputs):
             self.ext[k + 1] = np.zeros(o["n"] * o["h"] * o["w"] * o["ld"] * o["esize"], dtype=np.uint8)
-        for k, r in enumerate(prog.ops):
+        self._run_ops()
+        outs = []
+        for k, o in enumerate(prog.outputs):
+            outs.append(self.ext[k + 1].view(np.float32).reshape(o["n"], o["h"], o["w"], o["ld"]).copy())
+        return outs
+
+    def _run_ops(self):
+        for k, r in enumerate(self.prog.ops):
             self.cur_op = k
             self.wl_in = self.wl_out = None
             if self.wtab is not None:
@@ -162,10 +169,17 @@ class Emulator:
                 if int(r["p"][ir.P_WLOUT]):
                     self.wl_out = self.wtab[int(r["p"][ir.P_WLOUT]) - 1]
             getattr(self, "_op%d" % int(r["kind"]))(r)
-        outs = []
-        for k, o in enumerate(prog.outputs):
-            outs.append(self.ext[k + 1].view(np.float32).reshape(o["n"], o["h"], o["w"], o["ld"]).copy())
-        return outs
+
+    def run_records(self, ext, wtab=None):
+        """The records of `prog.ops` on caller-owned external arenas, the way vse_plan_run_ragged takes them: ext[k] = the byte
+        image (any numpy array) of arena ir.ARENA_EXT0 + k, inputs and outputs alike; wtab = the int32 width table [levels][n] (None
+        for an ordinary plan).  Needs the byte-exact mode (round_f16=True); prog may be any object with ops, ws_bytes and
+        weights.array() (tests/op_harness.py runs single records this way).  -> the arenas after the run, as uint8 arrays."""
+        assert self.round, "external arenas are byte images: round_f16=True"
+        self.ext = {k: np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy() for k, a in enumerate(ext)}
+        self.wtab = None if wtab is None else np.asarray(wtab, np.int32)
+        self._run_ops()
+        return [self.ext[k] for k in range(len(ext))]
 
     @staticmethod
     def _up(t, shift):
@@ -513,9 +527,11 @@ class Emulator:
         x = self.read(r["in0"])
         c = x.shape[3]
         gb = self.wread(int(r["w_off"]), 2 * c, np.float32)
-        y = F.layer_norm(x, (c,), torch.from_numpy(gb[:c].copy()), torch.from_numpy(gb[c:].copy()),
+        # in float64: fp32 F.layer_norm is 5e-6 .. 9e-6 off on rows with a mean of 30 and a deviation of 0.5 (its one-pass variance
+        # cancels), three times what the kernel's two-pass fp32 evaluation is off — the reference must be the more accurate side
+        y = F.layer_norm(x.double(), (c,), torch.from_numpy(gb[:c].astype(np.float64)), torch.from_numpy(gb[c:].astype(np.float64)),
                          float(r["f"][ir.FS_EPS]))
-        self.write(r["out"], y)
+        self.write(r["out"], y.float())
 
     def _op10(self, r):  # ATTN
         heads, hd = int(r["p"][ir.P_HEADS]), int(r["p"][ir.P_HDIM])
@@ -568,12 +584,14 @@ class Emulator:
             c = torch.zeros(B, H)
             out = torch.zeros(B, 1, T, H)
             for t in (range(T - 1, -1, -1) if rev else range(T)):
-                z = g[:, 0, t] + h @ whh
+                # one matrix-vector product per sample: a sample's column of h . W_hh^T must not depend on the batch it rides in
+                # (csrc/lstm.hip), and a batched CPU GEMM sums in an order that changes with B
+                z = g[:, 0, t] + torch.stack([h[b] @ whh for b in range(B)])
                 i, f_, gg, o = z.chunk(4, dim=1)
                 c = torch.sigmoid(f_) * c + torch.sigmoid(i) * torch.tanh(gg)
                 h = torch.sigmoid(o) * torch.tanh(c)
-                if self.round and not (int(r["flags"]) & ir.F_LSTM_MFMA):
-                    h = h.half().float()            # (the MFMA kernel carries h as fp16 hi + lo: fp32-grade state)
+                # (both kernels carry fp32-grade state — lstm_kernel h in fp32, the MFMA kernel as fp16 hi + lo — and round only
+                # the value they store; write() does that)
                 out[:, 0, t] = h
             return out
         def gates_of(v):

@@ -1,0 +1,468 @@
+"""One-record plans: run a single `vse_op` record — one HIP kernel — on tensors the test chooses, on the GPU (run_gpu) and on the
+CPU emulator (run_emulator), and hold the result to a plain fp64 reference of the same operation.
+
+A plain helper module like tests/parity.py (no fixtures, no pytest settings).  It has four parts:
+
+  * builders for ir.VIEW_DT / ir.OP_DT records (the fields follow the comments of ir.py and the checks at the top of each `case` of
+    launch_simple_op, csrc/simple_ops.hip), and a weight blob with the compiler's 256-byte alignment;
+  * the kernel FORM a record selects (softmax_form, dwconv_form, lstm_form, pool_form): the launcher's own conditions, restated, so that a
+    test can assert that its case still reaches the path it was written for;
+  * run_gpu / run_emulator: the same records and the same byte images through vse_plan_run_ragged and through oracle/ir_emul.py;
+  * one reference per op, written for a numpy dtype: evaluated in float64 it is the reference, in float32 it measures `e32`, the distance
+    of a plain single-precision evaluation from it — the yardstick of the error bound.  None of them calls the emulator.
+
+The bound (never derived from what a kernel returns):
+    fp16 output:  |got - ref64| <= ulp16(|ref64|) + 8 e32          fp32 output:  |got - ref64| <= 16 ulp32(|ref64|) + 8 e32
+e32 = the largest |ref32 - ref64| over the tensor.  The ulp term is one rounding of a value that is itself slightly off; the factor 8
+covers another fp32 summation order and the fast __expf.
+"""
+import ctypes as C
+from dataclasses import dataclass, field
+from typing import Callable, List, Optional
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from vse_amd import compiler, ir
+
+VSE_E_INVAL, VSE_E_HIP, VSE_E_UNSUPPORTED = -1, -2, -3
+
+
+# ---------------------------------------------------------------------------------------------------------------- records
+def ext(k):
+    """Arena id of external pointer k (tensors[k] of run_gpu / run_emulator)."""
+    return ir.ARENA_EXT0 + k
+
+
+def view(arena, n, h, w, c, ld=None, esize=2, off=0):
+    """ir.VIEW_DT: [n,h,w] pixels of c channels, `ld` elements apart (default c), `off` BYTES into the arena."""
+    v = ir.empty_view()
+    v["off"], v["arena"] = off, arena
+    v["n"], v["h"], v["w"], v["c"] = n, h, w, c
+    v["ld"], v["esize"] = (c if ld is None else ld), esize
+    return v
+
+
+def op(kind, ins=(), out=None, out2=None, flags=0, p=None, f=None, w_off=0, b_off=0, aux_off=0, wl=(0, 0)):
+    """One ir.OP_DT record.  ins: up to three views (None = absent); p / f: {slot: value}; wl = (P_WLIN, P_WLOUT): 1 + width level."""
+    r = np.zeros(1, ir.OP_DT)
+    r["kind"], r["flags"] = kind, flags
+    for k, v in (p or {}).items():
+        r["p"][0, k] = v
+    for k, v in (f or {}).items():
+        r["f"][0, k] = v
+    r["p"][0, ir.P_WLIN], r["p"][0, ir.P_WLOUT] = wl
+    for name, v in zip(("in0", "in1", "in2"), list(ins) + [None] * (3 - len(ins))):
+        if v is not None:
+            r[name] = v
+    if out is not None:
+        r["out"] = out
+    if out2 is not None:
+        r["out2"] = out2
+    r["w_off"], r["b_off"], r["aux_off"] = w_off, b_off, aux_off
+    return r
+
+
+class Blob:
+    """Weight blob of a one-record plan: every table 256-byte aligned, like compiler.WeightStore."""
+
+    def __init__(self):
+        self.buf = bytearray()
+
+    def add(self, arr):
+        off = (len(self.buf) + 255) // 256 * 256
+        self.buf.extend(b"\0" * (off - len(self.buf)))
+        self.buf.extend(np.ascontiguousarray(arr).tobytes())
+        return off
+
+    def array(self):
+        return np.frombuffer(bytes(self.buf) + b"\0" * max(0, 16 - len(self.buf)), dtype=np.uint8).copy()
+
+
+def dwconv_op(in0, out, k, s, pad, w_off, b_off, act=ir.ACT_NONE, act_a=0.0, act_b=0.0, post_a=1.0, post_b=0.0, gate=None,
+              gate_res=False, lo_in=0, lo_out=0, hilo=False, wl=(0, 0)):
+    """k = (kh, kw), s = (sh, sw), pad = (ph, pw); gate = SE gate view [N,1,1,C] (F_GATE; gate_res: x * g + x); lo_in / lo_out = channel
+    offset of the lo half of an fp16 hi + lo pair input / output (P_LO_RES / P_LO_OUT)."""
+    flags = (ir.F_GATE | (ir.F_RES if gate_res else 0) if gate is not None else 0) | (ir.F_HILO if hilo else 0)
+    return op(ir.OP_DWCONV, [in0, gate], out, flags=flags, w_off=w_off, b_off=b_off, wl=wl,
+              p={ir.P_KH: k[0], ir.P_KW: k[1], ir.P_SH: s[0], ir.P_SW: s[1], ir.P_PH: pad[0], ir.P_PW: pad[1], ir.P_ACT: act,
+                 ir.P_LO_OUT: lo_out, ir.P_LO_RES: lo_in},
+              f={ir.FS_ACT_A: act_a, ir.FS_ACT_B: act_b, ir.FS_POST_A: post_a, ir.FS_POST_B: post_b})
+
+
+def pool_op(in0, out, k, s, pad, is_max, ceil=False, exclusive=True, wl=(0, 0)):
+    return op(ir.OP_POOL, [in0], out, wl=wl,
+              p={ir.P_KH: k[0], ir.P_KW: k[1], ir.P_SH: s[0], ir.P_SW: s[1], ir.P_PH: pad[0], ir.P_PW: pad[1],
+                 ir.P_POOL_MAX: int(is_max), ir.P_POOL_CEIL: int(ceil), ir.P_POOL_EXCL: int(exclusive)})
+
+
+def gap_op(in0, scratch, out, wl=(0, 0)):
+    """scratch = fp32 view [n, splits, 1, c] (the ragged row form: splits = in0.h)."""
+    return op(ir.OP_GAP, [in0, None, scratch], out, wl=wl)
+
+
+def layernorm_op(in0, out, eps, w_off, wl=(0, 0)):
+    """w_off -> fp32 [2 C]: scale, then bias."""
+    return op(ir.OP_LAYERNORM, [in0], out, f={ir.FS_EPS: eps}, w_off=w_off, wl=wl)
+
+
+def attn_op(qkv, out, heads, hd, scale, wl=(0, 0)):
+    return op(ir.OP_ATTN, [qkv], out, p={ir.P_HEADS: heads, ir.P_HDIM: hd}, f={ir.FS_SCALE: scale}, wl=wl)
+
+
+def softmax_op(in0, idx_maxp, probs, ncls, wl=(0, 0)):
+    return op(ir.OP_SOFTMAX, [in0], idx_maxp, out2=probs, p={ir.P_NCLS: ncls}, wl=wl)
+
+
+def lstm_op(gates, out, H, mode, w_off, mfma, wl=(0, 0)):
+    """gates: one view, or [forward, reverse] for mode 2 (MFMA form only)."""
+    gates = list(gates) if isinstance(gates, (list, tuple)) else [gates]
+    p = {ir.P_HID: H, ir.P_REVERSE: mode}
+    if mfma:
+        p[ir.P_WAVES] = 16
+    return op(ir.OP_LSTM, gates, out, flags=ir.F_LSTM_MFMA if mfma else 0, p=p, w_off=w_off, wl=wl)
+
+
+# ---------------------------------------------------------------------------------------------------------------- kernel forms
+def softmax_form(r):
+    """("reg", NV): softmax_reg_kernel<T, NV>, or ("scalar", 0): softmax_kernel — the conditions of `case OP_SOFTMAX` (the base pointer
+    of a tensor from torch's allocator is 16-byte aligned)."""
+    r = r[0] if r.ndim else r
+    es, ld, ncls = int(r["in0"]["esize"]), int(r["in0"]["ld"]), int(r["p"][ir.P_NCLS])
+    vw = 16 // es
+    nvec = (ncls + vw - 1) // vw
+    nvt = (nvec + 255) // 256
+    if int(r["in0"]["off"]) % 16 == 0 and (ld * es) % 16 == 0 and nvt <= 8 and ncls > 0 and nvec * vw <= ld:
+        return "reg", next(nv for nv in (1, 2, 4, 8) if nvt <= nv)
+    return "scalar", 0
+
+
+def dwconv_form(r):
+    """("col", nseg, rows per segment) | ("row", 0, 0) | ("generic", 0, 0): the conditions and the segment arithmetic of `case OP_DWCONV`."""
+    r = r[0] if r.ndim else r
+    p, i, o = r["p"], r["in0"], r["out"]
+    kh, kw, sh, sw, ph, pw = (int(p[k]) for k in range(6))
+    gated = bool(int(r["flags"]) & ir.F_GATE)
+    if (not gated and not p[ir.P_LO_OUT] and not p[ir.P_LO_RES] and kw == kh and kw in (3, 5) and sw == 1 and sh in (1, 2)
+            and ph == kw // 2 and pw == kw // 2 and int(o["w"]) == int(i["w"]) and int(o["h"]) == (int(i["h"]) + 2 * (kw // 2) - kw) // sh + 1):
+        cols = int(o["n"]) * ((int(o["w"]) + 3) // 4) * (int(i["c"]) >> 1)
+        nseg = max(1, min((262144 + cols - 1) // cols, (int(o["h"]) + 3) // 4))
+        rs = (int(o["h"]) + nseg - 1) // nseg
+        return "col", (int(o["h"]) + rs - 1) // rs, rs
+    if kw in (3, 5) and sw in (1, 2):
+        return "row", 0, 0
+    return "generic", 0, 0
+
+
+def lstm_form(r):
+    """"mfma" (lstm_mfma16_kernel) | "scalar" (lstm_kernel) | "refused"."""
+    r = r[0] if r.ndim else r
+    H, mode = int(r["p"][ir.P_HID]), int(r["p"][ir.P_REVERSE])
+    if int(r["flags"]) & ir.F_LSTM_MFMA:
+        return "mfma" if H == 256 and int(r["p"][ir.P_WAVES]) == 16 else "refused"
+    return "scalar" if H <= 256 and mode <= 1 else "refused"
+
+
+def pool_form(r):
+    """The branch of pool_kernel: "max" (packed fp16 maxima), "avg_excl" (divide by the taps inside), "avg_incl" (by the padded window)."""
+    r = r[0] if r.ndim else r
+    if int(r["p"][ir.P_POOL_MAX]):
+        return "max"
+    return "avg_excl" if int(r["p"][ir.P_POOL_EXCL]) else "avg_incl"
+
+
+# ---------------------------------------------------------------------------------------------------------------- running
+class OpRefused(RuntimeError):
+    """vse_plan_create / vse_plan_run_ragged returned a negative code."""
+
+    def __init__(self, rc, what, msg):
+        super().__init__(f"{what} rc={rc}: {msg}")
+        self.rc = rc
+
+
+@dataclass
+class Run:
+    """One plan run: the records, the weight blob, the byte images of the external arenas (tensors[k] = arena ext(k), inputs and
+    outputs alike; outputs pre-filled with NaN / -1 so that an element nobody wrote shows), the width table, the workspace size."""
+    ops: np.ndarray
+    blob: np.ndarray
+    tensors: List[np.ndarray]
+    widths: Optional[np.ndarray] = None
+    ws_bytes: int = 0
+
+
+@dataclass
+class Case:
+    """check(outs) gets, per run, the list of arenas after the run (same shapes and dtypes as Run.tensors), asserts, and returns the
+    worst error / bound.  refused: every run must return a negative code.  may_refuse: VSE_E_UNSUPPORTED is a valid answer too."""
+    name: str
+    runs: List[Run]
+    check: Optional[Callable] = None
+    refused: bool = False
+    may_refuse: bool = False
+    note: dict = field(default_factory=dict)
+
+
+def run_gpu(ctx, ops, weight_blob, tensors, widths=None, ws_bytes=0):
+    """A plan of these records on ctx's device; -> the external arenas after the run (numpy, shapes and dtypes of `tensors`)."""
+    t, lib = ctx.torch, ctx.lib
+    blob = np.ascontiguousarray(weight_blob, np.uint8)
+    if blob.nbytes < 16:
+        blob = np.concatenate([blob, np.zeros(16 - blob.nbytes, np.uint8)])
+    ops = np.ascontiguousarray(ops)
+    dev = [t.from_numpy(np.ascontiguousarray(a).copy()).to(ctx.tdev) for a in tensors]
+    ws = t.zeros(max(int(ws_bytes), 256), dtype=t.uint8, device=ctx.tdev)
+    wt = None
+    if widths is not None:
+        wt = t.from_numpy(np.ascontiguousarray(widths, np.int32).copy()).to(ctx.tdev)
+    t.cuda.synchronize(ctx.tdev)
+    wid = lib.vse_weights_upload(ctx.handle, blob.ctypes.data_as(C.c_void_p), blob.nbytes)
+    if wid < 0:
+        raise OpRefused(wid, "vse_weights_upload", lib.vse_last_error().decode(errors="replace"))
+    handle = C.c_void_p()
+    try:
+        rc = lib.vse_plan_create(ctx.handle, wid, ops.ctypes.data_as(C.c_void_p), len(ops), int(ws_bytes), C.byref(handle))
+        if rc < 0:
+            raise OpRefused(rc, "vse_plan_create", lib.vse_last_error().decode(errors="replace"))
+        ptrs = (C.c_void_p * len(dev))(*[d.data_ptr() for d in dev])
+        rc = lib.vse_plan_run_ragged(handle, C.c_void_p(ws.data_ptr()), ptrs, len(dev),
+                                     C.c_void_p(wt.data_ptr()) if wt is not None else None, ctx.stream())
+        if rc < 0:
+            raise OpRefused(rc, "vse_plan_run_ragged", lib.vse_last_error().decode(errors="replace"))
+        t.cuda.synchronize(ctx.tdev)
+        return [d.cpu().numpy() for d in dev]
+    finally:
+        if handle:
+            lib.vse_plan_destroy(handle)
+        lib.vse_weights_free(ctx.handle, wid)
+
+
+class _Weights:
+    def __init__(self, blob):
+        self.blob = blob
+
+    def array(self):
+        return self.blob
+
+
+class _StubProgram:
+    """What ir_emul.Emulator reads of a compiled Program."""
+
+    def __init__(self, ops, blob, ws_bytes, has_widths):
+        self.ops, self.ws_bytes, self.weights = ops, max(int(ws_bytes), 16), _Weights(np.ascontiguousarray(blob, np.uint8).copy())
+        self.outputs, self.wlevels = [], ([] if has_widths else None)
+
+
+def run_emulator(ops, weight_blob, tensors, widths=None, ws_bytes=0):
+    """The same records through oracle/ir_emul.py with every stored tensor rounded where the kernels round; -> like run_gpu."""
+    from oracle import ir_emul
+    emu = ir_emul.Emulator(_StubProgram(ops, weight_blob, ws_bytes, widths is not None), round_f16=True)
+    outs = emu.run_records(tensors, None if widths is None else np.ascontiguousarray(widths, np.int32))
+    return [o.view(a.dtype).reshape(a.shape) for o, a in zip(outs, tensors)]
+
+
+def run_case(case, runner):
+    """runner(ops, blob, tensors, widths, ws_bytes) = run_gpu bound to a context, or run_emulator.  -> worst error / bound (None for a
+    refused case)."""
+    outs = []
+    for r in case.runs:
+        try:
+            outs.append(runner(r.ops, r.blob, r.tensors, r.widths, r.ws_bytes))
+        except OpRefused as e:
+            if case.refused or (case.may_refuse and e.rc == VSE_E_UNSUPPORTED):
+                case.note["rc"] = e.rc
+                continue
+            raise
+        else:
+            assert not case.refused, (case.name, "ran, where the library must refuse the record")
+    if case.refused or (case.may_refuse and len(outs) < len(case.runs)):
+        return None
+    case.note["rc"] = 0
+    return case.check(outs)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the bound
+def f16(a):
+    """Round to fp16 (the values a kernel gets)."""
+    return np.asarray(a).astype(np.float16)
+
+
+def ulp16(a):
+    a = np.abs(np.asarray(a, np.float64))
+    return 2.0 ** (np.floor(np.log2(np.maximum(a, 2.0 ** -14))) - 10)
+
+
+def ulp32(a):
+    a = np.abs(np.asarray(a, np.float64))
+    return 2.0 ** (np.floor(np.log2(np.maximum(a, 2.0 ** -126))) - 23)
+
+
+def reference(fn):
+    """fn(dtype) -> array or tuple of arrays.  -> (float64 results, e32 per result)."""
+    r64, r32 = fn(np.float64), fn(np.float32)
+    if not isinstance(r64, tuple):
+        r64, r32 = (r64,), (r32,)
+    for a, b in zip(r64, r32):
+        assert a.dtype == np.float64 and b.dtype == np.float32, (a.dtype, b.dtype)
+    e32 = tuple(float(np.abs(b.astype(np.float64) - a).max()) if a.size else 0.0 for a, b in zip(r64, r32))
+    return r64, e32
+
+
+def ratio(got, ref64, e32, what, pair=False):
+    """Worst |got - ref64| / bound; asserts <= 1.  got: fp16 or fp32 array (the bound follows its dtype); pair: `got` is float64 hi + lo
+    of an fp16 pair tensor, held to 2^-20 relative + 8 e32."""
+    got = np.asarray(got)
+    assert got.shape == ref64.shape, (what, got.shape, ref64.shape)
+    if pair:
+        bound = np.abs(ref64) * 2.0 ** -20 + 2.0 ** -24 + 8 * e32          # (2^-24: the smallest fp16 step, a lo half cannot carry less)
+    elif got.dtype == np.float16:
+        bound = ulp16(ref64) + 8 * e32
+    else:
+        assert got.dtype == np.float32, got.dtype
+        bound = 16 * ulp32(ref64) + 8 * e32
+    err = np.abs(got.astype(np.float64) - ref64)
+    ok = err <= bound                    # (NaN — an element nobody wrote — compares false)
+    worst = float(np.nanmax(err / bound)) if err.size else 0.0
+    assert ok.all(), (what, "error / bound", worst, "at", tuple(int(v) for v in np.argwhere(~ok)[0]), "e32", e32,
+                      "unwritten" if np.isnan(got.astype(np.float64)).any() else "")
+    return worst
+
+
+# ---------------------------------------------------------------------------------------------------------------- references
+def ref_act(x, code, a=0.0, b=0.0):
+    dt = x.dtype.type
+    if code == ir.ACT_NONE:
+        return x
+    if code == ir.ACT_RELU:
+        return np.maximum(x, dt(0))
+    if code == ir.ACT_HSWISH:
+        return x * np.clip(x + dt(3), dt(0), dt(6)) / dt(6)
+    if code == ir.ACT_SWISH:
+        return x / (dt(1) + np.exp(-x))
+    if code == ir.ACT_SIGMOID:
+        return dt(1) / (dt(1) + np.exp(-x))
+    if code == ir.ACT_HSIGMOID:
+        return np.clip(x * dt(np.float32(a)) + dt(np.float32(b)), dt(0), dt(1))
+    raise ValueError(code)
+
+
+def mask_width(y, wl):
+    """Zeros right of each sample's width (what every producing kernel of a ragged plan stores there)."""
+    if wl is not None:
+        y = y.copy()
+        for n, wn in enumerate(wl):
+            y[n, :, int(wn):] = 0
+    return y
+
+
+def ref_dwconv(x, wk, bias, k, s, pad, act=ir.ACT_NONE, act_a=0.0, act_b=0.0, post_a=1.0, post_b=0.0, wl_out=None, dt=np.float64):
+    """x [n,h,w,c] (already gated / hi + lo summed), wk fp32 [kh*kw][c], bias fp32 [c] -> [n,oh,ow,c]."""
+    (kh, kw), (sh, sw), (ph, pw) = k, s, pad
+    n, h, w, c = x.shape
+    oh, ow = (h + 2 * ph - kh) // sh + 1, (w + 2 * pw - kw) // sw + 1
+    xp = np.zeros((n, h + 2 * ph + sh, w + 2 * pw + sw, c), dt)
+    xp[:, ph:ph + h, pw:pw + w] = x.astype(dt)
+    acc = np.broadcast_to(bias.astype(dt), (n, oh, ow, c)).copy()
+    for dy in range(kh):
+        for dx in range(kw):
+            acc += xp[:, dy:dy + sh * oh:sh, dx:dx + sw * ow:sw][:, :oh, :ow] * wk[dy * kw + dx].astype(dt)
+    y = ref_act(acc, act, act_a, act_b) * dt(np.float32(post_a)) + dt(np.float32(post_b))
+    return mask_width(y, wl_out)
+
+
+def ref_pool(x, k, s, pad, is_max, ceil, exclusive, wl_in=None, wl_out=None, out_w=None, dt=np.float64):
+    """Paddle's pool2d = F.max_pool2d / F.avg_pool2d(count_include_pad=not exclusive, ceil_mode=ceil).  wl_in: every sample is pooled
+    over its own width and written left-aligned into [n, oh, out_w, c]."""
+    tdt = torch.float64 if dt == np.float64 else torch.float32
+
+    def pool(xs):
+        xs = torch.from_numpy(np.ascontiguousarray(xs.astype(dt))).permute(0, 3, 1, 2)
+        if is_max:
+            y = F.max_pool2d(xs, k, s, pad, ceil_mode=ceil)
+        else:
+            y = F.avg_pool2d(xs, k, s, pad, ceil_mode=ceil, count_include_pad=not exclusive)
+        return y.permute(0, 2, 3, 1).to(tdt).numpy()
+    if wl_in is None:
+        return mask_width(pool(x), wl_out)
+    outs = [pool(x[n:n + 1, :, :int(wn)]) for n, wn in enumerate(wl_in)]
+    y = np.zeros((x.shape[0], outs[0].shape[1], out_w, x.shape[3]), dt)
+    for n, o in enumerate(outs):
+        y[n, :, :o.shape[2]] = o[0]
+    return mask_width(y, wl_out)
+
+
+def ref_gap(x, wl_in=None, dt=np.float64):
+    """[n,h,w,c] -> [n,1,1,c]: the mean over the map (over the sample's own width in a ragged batch)."""
+    n = x.shape[0]
+    y = np.zeros((n, 1, 1, x.shape[3]), dt)
+    for b in range(n):
+        xs = x[b].astype(dt) if wl_in is None else x[b, :, :int(wl_in[b])].astype(dt)
+        y[b, 0, 0] = xs.reshape(-1, x.shape[3]).sum(0, dtype=dt) / dt(xs.shape[0] * xs.shape[1])
+    return y
+
+
+def ref_layernorm(x, g, b, eps, wl_out=None, dt=np.float64):
+    """Two-pass mean / variance over the channels."""
+    x = x.astype(dt)
+    c = dt(x.shape[-1])
+    mean = x.sum(-1, keepdims=True, dtype=dt) / c
+    d = x - mean
+    var = (d * d).sum(-1, keepdims=True, dtype=dt) / c
+    y = d / np.sqrt(var + dt(np.float32(eps))) * g.astype(dt) + b.astype(dt)
+    return mask_width(y, wl_out)
+
+
+def ref_attn(qkv, heads, hd, scale, lens=None, dt=np.float64):
+    """qkv [B,1,T,3C] -> [B,1,T,C]; a sample's keys and queries end at its own length (rows behind it are zeros)."""
+    B, _, T, _ = qkv.shape
+    Cc = heads * hd
+    out = np.zeros((B, 1, T, Cc), dt)
+    for b in range(B):
+        tb = T if lens is None else int(lens[b])
+        x = qkv[b, 0, :tb].astype(dt).reshape(tb, 3, heads, hd)
+        q, k, v = x[:, 0] * dt(np.float32(scale)), x[:, 1], x[:, 2]
+        s = np.einsum("thd,uhd->htu", q, k)
+        s = np.exp(s - s.max(-1, keepdims=True))
+        a = s / s.sum(-1, keepdims=True, dtype=dt)
+        out[b, 0, :tb] = np.einsum("htu,uhd->thd", a, v).reshape(tb, Cc)
+    return out
+
+
+def ref_softmax(x, dt=np.float64):
+    """x [rows, ncls] -> (probabilities, 1 / sum = the largest probability)."""
+    x = x.astype(dt)
+    e = np.exp(x - x.max(-1, keepdims=True))
+    s = e.sum(-1, keepdims=True, dtype=dt)
+    return e / s, (dt(1) / s)[:, 0]
+
+
+def ref_lstm(g, w_hh, rev, lens=None, dt=np.float64):
+    """g [B,T,4H] = x.W_ih^T + b in gate order i, f, g, o; w_hh [4H,H] -> h [B,T,H]; the reverse pass starts at the sample's own end,
+    steps behind its length give zeros."""
+    B, T, H4 = g.shape
+    H = H4 // 4
+    w = w_hh.astype(dt)
+    out = np.zeros((B, T, H), dt)
+
+    def sig(z):
+        return dt(1) / (dt(1) + np.exp(-z))
+    for b in range(B):
+        tb = T if lens is None else int(lens[b])
+        h, c = np.zeros(H, dt), np.zeros(H, dt)
+        for t in (range(tb - 1, -1, -1) if rev else range(tb)):
+            z = g[b, t].astype(dt) + w @ h
+            c = sig(z[H:2 * H]) * c + sig(z[:H]) * np.tanh(z[2 * H:3 * H])
+            h = sig(z[3 * H:]) * np.tanh(c)
+            out[b, t] = h
+    return out
+
+
+def lstm_mfma_blob(w_hhs):
+    """The MFMA kernel's W_hh stream of one or two directions (Compiler.lstm_fragments16)."""
+    return np.concatenate([compiler.Compiler.lstm_fragments16(np.ascontiguousarray(w, np.float32)) for w in w_hhs])
+
+
+def lstm_mfma_gates(g):
+    """Gate pre-activations [.., 4H] in i, f, g, o order -> the channel order the MFMA kernel reads (Compiler.lstm_gate_order)."""
+    return np.ascontiguousarray(g[..., compiler.Compiler.lstm_gate_order(g.shape[-1] // 4)])
