@@ -281,6 +281,32 @@ int vse_scene_change(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_
                      int search, int bias, void* d_state, int reset, void* d_ws, size_t ws_bytes,
                      int32_t* d_counts /* [n,3]: changed blocks, sum inter, sum intra */, void* stream);
 
+/* ---- frame ingest: YUV 4:2:0 -> BGR ------------------------------------------------------------------------------------------ */
+/* Replaces: the colour conversion inside the reference's decoder, cv2.VideoCapture.read() (backend/main.py:228-376 sequentially,
+ * backend/tools/subtitle_ocr.py:173-204 by seeking), where FFmpeg's swscale turns the codec's yuv420p pictures into the BGR frame
+ * the callers get.  Here the decoder's 4:2:0 bytes are uploaded as they are (1.5 instead of 3 bytes per pixel) and converted on
+ * the device.  BT.601 limited range, nearest chroma (no interpolation, siting ignored), the fixed-point constants of
+ * cv2.cvtColor(COLOR_YUV2BGR_I420 / _NV12); swscale's chroma up-sampling filter differs, so these are not swscale's bits.
+ * All arithmetic int32, >> arithmetic, clip8(x) = min(max(x, 0), 255):
+ *   Y = luma[r][x], U and V from chroma row (r + row_parity) >> 1 and column x >> 1;
+ *   c = max(Y - 16, 0) * 1220542, u = U - 128, v = V - 128;
+ *   B = clip8((c + 2116026 u + 2^19) >> 20), G = clip8((c - 409993 u - 852492 v + 2^19) >> 20), R = clip8((c + 1673527 v + 2^19) >> 20).
+ * A packed (sub-)frame: h luma rows of w bytes, then ch = (h + row_parity + 1) >> 1 chroma rows of cw = (w + 1) >> 1 samples:
+ * layout 0 (I420) a U plane then a V plane, each ch x cw bytes; layout 1 (NV12) one plane of ch rows of 2 cw bytes, U then V.
+ * row_parity = 1 describes a band of rows that starts on an odd luma row of its frame (its first luma row is the SECOND row of
+ * its first chroma row), so a host can upload any band of rows without touching the rest of the frame.
+ * vse_yuv420_frame_bytes: that packed size; 0 for arguments vse_yuv420_to_bgr would refuse. */
+size_t vse_yuv420_frame_bytes(int h, int w, int row_parity);
+/* n packed frames at d_yuv, yuv_frame_stride bytes apart -> uint8 BGR [n, h, w, 3] at d_bgr (row pitch `pitch` bytes, frame stride
+ * bgr_frame_stride bytes).  One launch on `stream`, no allocation, no device sync; writes exactly the w * 3 bytes of each of the
+ * h rows of each frame (padding between rows and frames is never written).  No alignment is required; 16-byte aligned bases,
+ * pitch and strides with w % 16 == 0, even h and row_parity 0 take the 16-byte load / store kernel.
+ * Returns VSE_E_INVAL, and launches nothing, when h, w or n < 1, h * w > 2^31 - 1, layout or row_parity is not 0 | 1,
+ * pitch < 3 w, yuv_frame_stride < vse_yuv420_frame_bytes or bgr_frame_stride < (h - 1) pitch + 3 w. */
+int vse_yuv420_to_bgr(vse_ctx* ctx, const void* d_yuv, int n, int h, int w, int layout /* 0 = I420, 1 = NV12 */,
+                      int row_parity /* 0 | 1 */, int64_t yuv_frame_stride, void* d_bgr, int64_t pitch, int64_t bgr_frame_stride,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,9 @@
 filters -> SRT) on a synthetic 1080p clip held in HOST memory (so the PCIe upload of every frame is inside the timed
 region), real-weight detector (V3_ch_det_fast) + stand-in en recogniser, fully data-driven boxes.
 
-usage: python tools/bench_extract.py [--frames 1024] [--batch 64] [--hold 12]
+usage: python tools/bench_extract.py [--frames 1024] [--batch 64] [--hold 12] [--source bgr|i420]
+--source i420 holds the same clip as unconverted YUV 4:2:0 planes (ingest.Yuv420Frame, 1.5 bytes per pixel): the staged rows then
+pack and upload half the bytes and convert on the device (vse_yuv420_to_bgr); both sources time upload + OCR, not a disk.
 Prints one JSON line per mode: fps sampler looking at every frame, batched and frame by frame (the reference's order of
 work), and the accurate mode (detector loop over every frame + OCR of the selected ones).  First, fast mode with an area both
 ways: the fps sampler at the default extract_frequency (what that run fell back to) and the subtitle-change selector
@@ -16,7 +18,32 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
-from vse_amd import engine, extractor, frame_select, modelzoo, pipeline, shim, staging, synth
+from vse_amd import engine, extractor, frame_select, ingest, modelzoo, pipeline, shim, staging, synth
+
+
+class Yuv420ArraySource:
+    """extractor.ArraySource over ingest.Yuv420Frames held in host memory: read_raw / raw_frames hand out the planes (the staged
+    routes), read / frames the host conversion (every other route)."""
+
+    def __init__(self, raw, fps):
+        self._raw = raw
+        self.frame_count = len(raw)
+        self.fps = float(fps)
+
+    def read_raw(self, frame_no):
+        return self._raw[frame_no - 1] if 1 <= frame_no <= self.frame_count else None
+
+    def read(self, frame_no):
+        raw = self.read_raw(frame_no)
+        return None if raw is None else raw.to_bgr()
+
+    def raw_frames(self):
+        return iter(self._raw)
+
+    def frames(self):
+        return (f.to_bgr() for f in self._raw)
+
+    pos_msec = None
 
 
 def main():
@@ -29,6 +56,7 @@ def main():
     ap.add_argument("--single", type=int, default=96, help="frames of the frame-by-frame run (slow)")
     ap.add_argument("--workers", type=int, default=4, help="copy threads of the pinned-slab uploader")
     ap.add_argument("--staged-only", action="store_true")
+    ap.add_argument("--source", choices=("bgr", "i420"), default="bgr", help="what the host holds: BGR frames or YUV 4:2:0 planes")
     ap.add_argument("--change-only", action="store_true", help="only the two fast-mode-with-area rows (fps sampler / change selector)")
     a = ap.parse_args()
     ctx = engine.Context(0)
@@ -38,6 +66,11 @@ def main():
     n_sub = (a.frames + 2 * a.hold - 1) // (2 * a.hold)
     lit = synth.make_frames(min(n_sub, 48), a.height, a.width, seed=9)
     dark = np.full((a.height, a.width, 3), 40, np.uint8)
+    if a.source == "i420":
+        def raw(frame):
+            return ingest.Yuv420Frame(ingest.bgr_to_yuv420(frame), a.height, a.width, "i420")
+        lit, dark = [raw(f) for f in lit], raw(dark)
+    make_source = extractor.ArraySource if a.source == "bgr" else Yuv420ArraySource
     clip = []
     for k in range(n_sub):                                  # subtitle k for `hold` frames, then `hold` dark frames
         clip += [lit[k % len(lit)]] * a.hold + [dark] * a.hold
@@ -100,9 +133,9 @@ def main():
     elif a.staged_only:
         runs = runs[:6]
     for name, frames, ocr, kw in runs:
-        src = extractor.ArraySource(frames, fps)
+        src = make_source(frames, fps)
         ex = extractor.SubtitleExtractor(src, ocr, detect_batch=detect, drop_score=0.0, batch=a.batch, **kw)
-        ex_warm = extractor.SubtitleExtractor(extractor.ArraySource(frames[:5 * a.batch], fps), ocr, detect_batch=detect,
+        ex_warm = extractor.SubtitleExtractor(make_source(frames[:5 * a.batch], fps), ocr, detect_batch=detect,
                                               drop_score=0.0, batch=a.batch, **kw)
         ex_warm.run()
         torch.cuda.synchronize()
@@ -113,7 +146,7 @@ def main():
         dt = time.time() - t0
         print(json.dumps({"mode": name, "frames": len(frames), "seconds": round(dt, 3), "frames_per_s": round(len(frames) / dt, 1),
                           "ocr_frames": ocr.frames, "raw_lines": len(ex.raw_lines), "srt_blocks": text.count(" --> "),
-                          "frame_mb": round(a.height * a.width * 3 / 1e6, 2)}), flush=True)
+                          "source": a.source, "frame_mb": round(a.height * a.width * (3 if a.source == "bgr" else 1.5) / 1e6, 2)}), flush=True)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,216 @@
+// YUV 4:2:0 -> BGR (vse_yuv420_to_bgr, include/vse_hip.h): what a decoder hands out (planar I420, semi-planar NV12, 1.5 bytes per pixel)
+// becomes the uint8 BGR frames every other entry point takes, on the device, so the host stores, packs and uploads half the bytes.
+// BT.601 limited range, nearest chroma; the integers are the specification (tests/yuv_ref.py restates them in numpy, bit for bit):
+//   c = max(Y - 16, 0) * 1220542, u = U - 128, v = V - 128                      (U, V of chroma row (r + row_parity) >> 1, column x >> 1)
+//   B = clip8((c + 2116026 u + 2^19) >> 20), G = clip8((c - 409993 u - 852492 v + 2^19) >> 20), R = clip8((c + 1673527 v + 2^19) >> 20)
+// |sum| <= 560 969 128: int32 is exact.  Every factor fits 24 bits, so the products are the full-rate 24-bit multiplies.
+// HBM-bound byte work, 1.5 bytes read and 3 written per pixel.  Two kernels:
+//   fast     a lane owns 16 pixels x 2 rows: two 16-byte luma loads, 8 + 8 bytes of U and V (I420) or 16 bytes of UV (NV12), six 16-byte
+//            stores; the chroma terms are computed once for both rows.  Needs w % 16 == 0, even h, row_parity 0, and 16-byte aligned
+//            bases, pitch and frame strides.
+//   general  a lane owns 4 pixels of one row, any size / pitch / parity / byte alignment: dword stores where the row is 4-byte aligned
+//            and the 4 pixels exist, byte stores otherwise.
+#include <algorithm>
+#include <cstdio>
+
+#include "common.h"
+
+void vse_set_error(const char* msg);      // vse_runtime.hip
+
+namespace {
+
+constexpr int YUV_I420 = 0, YUV_NV12 = 1;
+constexpr int FAST_THREADS = 256, FAST_MAX_BLOCKS = 2048;
+constexpr int GEN_LANES = 64, GEN_ROWS = 4;        // block of the general kernel: 64 pixel groups x 4 rows
+constexpr long MAX_PIXELS = 0x7fffffffL;           // per frame: the per-frame work-item index stays an int
+
+struct ChromaTerms {
+    int b, g, r;      // the chroma part of each channel's sum, rounding constant included
+};
+
+__device__ __forceinline__ ChromaTerms chroma_terms(int U, int V) {
+    const int u = U - 128, v = V - 128;
+    ChromaTerms t;
+    t.b = __mul24(u, 2116026) + (1 << 19);
+    t.g = __mul24(u, -409993) + __mul24(v, -852492) + (1 << 19);
+    t.r = __mul24(v, 1673527) + (1 << 19);
+    return t;
+}
+
+// clip8(x >> 20), clamped BEFORE the shift (the same value: floor, then 0..255).  Shift-then-clamp is folded by hipcc into gfx950's
+// v_ashr_pk_u8_i32 wherever two neighbouring bytes of a dword come from it, and those bytes differed from the integers above on the
+// device (the G of a quad's third pixel read 127 for 124 at Y, U, V = 254, 255, 255) while the unfused ones were right.
+__device__ __forceinline__ unsigned clip8(int x) { return (unsigned)min(max(x, 0), (255 << 20) | 0xfffff) >> 20; }
+
+// 4 pixels (luma bytes of `yw`, low byte first; chroma terms t0 for pixels 0-1, t1 for pixels 2-3) -> 12 bytes B G R B G R ...
+__device__ __forceinline__ void bgr4(unsigned yw, const ChromaTerms& t0, const ChromaTerms& t1, unsigned& d0, unsigned& d1, unsigned& d2) {
+    unsigned b[4], g[4], r[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int y = (int)((yw >> (8 * k)) & 255u);
+        const int c = __mul24(max(y - 16, 0), 1220542);
+        const ChromaTerms& t = k < 2 ? t0 : t1;
+        b[k] = clip8(c + t.b);
+        g[k] = clip8(c + t.g);
+        r[k] = clip8(c + t.r);
+    }
+    d0 = b[0] | (g[0] << 8) | (r[0] << 16) | (b[1] << 24);
+    d1 = g[1] | (r[1] << 8) | (b[2] << 16) | (g[2] << 24);
+    d2 = r[2] | (b[3] << 8) | (g[3] << 16) | (r[3] << 24);
+}
+
+// 16 pixels of one row -> 48 bytes as three 16-byte stores
+__device__ __forceinline__ void row16(const uint4& y, const ChromaTerms (&t)[8], uint8_t* dst) {
+    const unsigned yw[4] = {y.x, y.y, y.z, y.w};
+    unsigned o[12];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) bgr4(yw[q], t[2 * q], t[2 * q + 1], o[3 * q], o[3 * q + 1], o[3 * q + 2]);
+    uint4* d = reinterpret_cast<uint4*>(dst);
+    d[0] = make_uint4(o[0], o[1], o[2], o[3]);
+    d[1] = make_uint4(o[4], o[5], o[6], o[7]);
+    d[2] = make_uint4(o[8], o[9], o[10], o[11]);
+}
+
+// Work item i of a frame = (row pair i / cgs, 16-pixel column group i % cgs); consecutive lanes take consecutive column groups, so
+// a wave's luma loads are contiguous and its stores cover contiguous 3 KiB runs of two output rows.  blockIdx.y strides the frames.
+template <int LAYOUT>
+__global__ __launch_bounds__(FAST_THREADS) void yuv420_fast_kernel(const uint8_t* __restrict__ src, int n, int h, int w, long sstride,
+                                                                   uint8_t* __restrict__ dst, long pitch, long dstride) {
+    const unsigned cgs = (unsigned)w >> 4, items = ((unsigned)h >> 1) * cgs;
+    const long plane = (long)h * w, cw = w >> 1;
+    for (int f = blockIdx.y; f < n; f += gridDim.y) {
+        const uint8_t* s = src + (long)f * sstride;
+        uint8_t* d = dst + (long)f * dstride;
+        for (unsigned i = blockIdx.x * FAST_THREADS + threadIdx.x; i < items; i += gridDim.x * FAST_THREADS) {
+            const unsigned rp = i / cgs, cg = i - rp * cgs;
+            const uint8_t* yp = s + (long)(2 * rp) * w + 16 * cg;
+            const uint4 y0 = *reinterpret_cast<const uint4*>(yp);
+            const uint4 y1 = *reinterpret_cast<const uint4*>(yp + w);
+            ChromaTerms t[8];
+            if (LAYOUT == YUV_I420) {
+                const uint8_t* up = s + plane + (long)rp * cw + 8 * cg;
+                const uint2 u = *reinterpret_cast<const uint2*>(up);
+                const uint2 v = *reinterpret_cast<const uint2*>(up + (plane >> 2));
+                const unsigned uw[2] = {u.x, u.y}, vw[2] = {v.x, v.y};
+#pragma unroll
+                for (int k = 0; k < 8; ++k) t[k] = chroma_terms((int)((uw[k >> 2] >> (8 * (k & 3))) & 255u), (int)((vw[k >> 2] >> (8 * (k & 3))) & 255u));
+            } else {
+                const uint4 uv = *reinterpret_cast<const uint4*>(s + plane + (long)rp * w + 16 * cg);
+                const unsigned q[4] = {uv.x, uv.y, uv.z, uv.w};
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const unsigned p = q[k >> 1] >> (16 * (k & 1));
+                    t[k] = chroma_terms((int)(p & 255u), (int)((p >> 8) & 255u));
+                }
+            }
+            uint8_t* o = d + (long)(2 * rp) * pitch + 48 * cg;
+            row16(y0, t, o);
+            row16(y1, t, o + pitch);
+        }
+    }
+}
+
+// Lane (threadIdx.x, threadIdx.y) = pixels 4 xg .. 4 xg + 3 of one row; blockIdx.y strides the rows, blockIdx.z the frames.
+template <int LAYOUT>
+__global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void yuv420_general_kernel(const uint8_t* __restrict__ src, int n, int h, int w, int parity,
+                                                                              long sstride, uint8_t* __restrict__ dst, long pitch, long dstride) {
+    const int x = 4 * (int)(blockIdx.x * GEN_LANES + threadIdx.x);
+    if (x >= w) return;
+    const int npx = min(4, w - x);
+    const long plane = (long)h * w, cw = (w + 1) >> 1, ch = (h + parity + 1) >> 1;
+    const int c0 = x >> 1, c1 = npx > 2 ? c0 + 1 : c0;         // chroma columns of pixels 0-1 and 2-3 (the second only if pixel 2 exists)
+    for (int f = blockIdx.z; f < n; f += gridDim.z) {
+        const uint8_t* s = src + (long)f * sstride;
+        uint8_t* d = dst + (long)f * dstride;
+        for (int r = blockIdx.y * GEN_ROWS + threadIdx.y; r < h; r += gridDim.y * GEN_ROWS) {
+            const uint8_t* yp = s + (long)r * w + x;
+            unsigned yw = 0;
+            if (npx == 4 && (reinterpret_cast<uintptr_t>(yp) & 3) == 0) {
+                yw = *reinterpret_cast<const unsigned*>(yp);
+            } else {
+                for (int k = 0; k < npx; ++k) yw |= (unsigned)yp[k] << (8 * k);
+            }
+            const long cr = (r + parity) >> 1;
+            ChromaTerms t0, t1;
+            if (LAYOUT == YUV_I420) {
+                const uint8_t* up = s + plane + cr * cw;
+                const uint8_t* vp = up + ch * cw;
+                t0 = chroma_terms(up[c0], vp[c0]);
+                t1 = chroma_terms(up[c1], vp[c1]);
+            } else {
+                const uint8_t* uv = s + plane + cr * 2 * cw;
+                t0 = chroma_terms(uv[2 * c0], uv[2 * c0 + 1]);
+                t1 = chroma_terms(uv[2 * c1], uv[2 * c1 + 1]);
+            }
+            unsigned o[3];
+            bgr4(yw, t0, t1, o[0], o[1], o[2]);
+            uint8_t* op = d + (long)r * pitch + 3 * (long)x;
+            if (npx == 4 && (reinterpret_cast<uintptr_t>(op) & 3) == 0) {
+                unsigned* o4 = reinterpret_cast<unsigned*>(op);
+                o4[0] = o[0];
+                o4[1] = o[1];
+                o4[2] = o[2];
+            } else {
+                for (int k = 0; k < 3 * npx; ++k) op[k] = (uint8_t)(o[k >> 2] >> (8 * (k & 3)));
+            }
+        }
+    }
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace
+
+extern "C" {
+
+size_t vse_yuv420_frame_bytes(int h, int w, int row_parity) {
+    if (h < 1 || w < 1 || row_parity < 0 || row_parity > 1 || (long)h * w > MAX_PIXELS) return 0;
+    const size_t cw = ((size_t)w + 1) >> 1, ch = ((size_t)h + row_parity + 1) >> 1;
+    return (size_t)h * w + 2 * cw * ch;
+}
+
+int vse_yuv420_to_bgr(vse_ctx* c, const void* d_yuv, int n, int h, int w, int layout, int row_parity, int64_t yuv_frame_stride,
+                      void* d_bgr, int64_t pitch, int64_t bgr_frame_stride, void* stream) {
+    const size_t frame = vse_yuv420_frame_bytes(h, w, row_parity);
+    if (!c || !d_yuv || !d_bgr || n < 1 || !frame || (layout != YUV_I420 && layout != YUV_NV12) || pitch < (int64_t)w * 3 ||
+        yuv_frame_stride < (int64_t)frame || bgr_frame_stride < (int64_t)(h - 1) * pitch + (int64_t)w * 3) {
+        char msg[320];
+        snprintf(msg, sizeof msg, "vse_yuv420_to_bgr: bad arguments (n %d, frame %d x %d of at most 2^31 - 1 pixels, layout %d of 0 | 1, row parity %d "
+                 "of 0 | 1, packed frame stride %lld of at least %zu, pitch %lld, output frame stride %lld)", n, h, w, layout, row_parity,
+                 (long long)yuv_frame_stride, frame, (long long)pitch, (long long)bgr_frame_stride);
+        vse_set_error(msg);
+        return VSE_E_INVAL;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_yuv);
+    uint8_t* dst = reinterpret_cast<uint8_t*>(d_bgr);
+    const bool fast = w % 16 == 0 && h % 2 == 0 && row_parity == 0 && pitch % 16 == 0 && yuv_frame_stride % 16 == 0 &&
+                      bgr_frame_stride % 16 == 0 && aligned16(src) && aligned16(dst);
+    if (fast) {
+        const long items = (long)(h / 2) * (w / 16);
+        const dim3 grid((unsigned)std::min<long>((items + FAST_THREADS - 1) / FAST_THREADS, FAST_MAX_BLOCKS), (unsigned)std::min(n, 65535));
+        if (layout == YUV_I420)
+            hipLaunchKernelGGL(yuv420_fast_kernel<YUV_I420>, grid, dim3(FAST_THREADS), 0, st, src, n, h, w, (long)yuv_frame_stride, dst, (long)pitch,
+                               (long)bgr_frame_stride);
+        else
+            hipLaunchKernelGGL(yuv420_fast_kernel<YUV_NV12>, grid, dim3(FAST_THREADS), 0, st, src, n, h, w, (long)yuv_frame_stride, dst, (long)pitch,
+                               (long)bgr_frame_stride);
+    } else {
+        const long groups = ((long)w + 3) / 4;
+        const dim3 grid((unsigned)((groups + GEN_LANES - 1) / GEN_LANES), (unsigned)std::min((h + GEN_ROWS - 1) / GEN_ROWS, 65535),
+                        (unsigned)std::min(n, 65535));
+        if (layout == YUV_I420)
+            hipLaunchKernelGGL(yuv420_general_kernel<YUV_I420>, grid, dim3(GEN_LANES, GEN_ROWS), 0, st, src, n, h, w, row_parity,
+                               (long)yuv_frame_stride, dst, (long)pitch, (long)bgr_frame_stride);
+        else
+            hipLaunchKernelGGL(yuv420_general_kernel<YUV_NV12>, grid, dim3(GEN_LANES, GEN_ROWS), 0, st, src, n, h, w, row_parity,
+                               (long)yuv_frame_stride, dst, (long)pitch, (long)bgr_frame_stride);
+    }
+    if (hipGetLastError() != hipSuccess) {
+        vse_set_error("vse_yuv420_to_bgr: launch failed");
+        return VSE_E_HIP;
+    }
+    return VSE_OK;
+}
+
+}  // extern "C"

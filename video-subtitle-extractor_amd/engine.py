@@ -23,6 +23,10 @@ EXPORTS = [
     "vse_audio_match_workspace_bytes", "vse_audio_match", "vse_scene_change_state_bytes", "vse_scene_change_workspace_bytes",
     "vse_scene_change",
 ]
+# Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
+# them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
+# this list for them.
+EXPORTS_NUMBERED = ["vse_yuv420_frame_bytes", "vse_yuv420_to_bgr"]
 
 
 class VseError(RuntimeError):
@@ -64,7 +68,7 @@ def load_library(path=None):
         raise VseError(f"{path} not found: run `python __graft_entry__.py` (hipcc --offload-arch=gfx950) first; "
                        "there is no CPU fallback for the OCR hot path")
     lib = C.CDLL(path)
-    for name in EXPORTS:
+    for name in EXPORTS + EXPORTS_NUMBERED:
         if not hasattr(lib, name):
             raise VseError(f"libvse_hip.so does not export {name}")
 
@@ -128,6 +132,10 @@ def load_library(path=None):
     lib.vse_scene_change_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.vse_scene_change.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
                                      C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    lib.vse_yuv420_frame_bytes.restype = C.c_size_t
+    lib.vse_yuv420_frame_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.vse_yuv420_to_bgr.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p,
+                                      C.c_int64, C.c_int64, C.c_void_p]
     if lib.vse_sizeof_op() != ir.OP_DT.itemsize or lib.vse_sizeof_view() != ir.VIEW_DT.itemsize:
         raise VseError(f"ABI mismatch: vse_op {lib.vse_sizeof_op()} vs {ir.OP_DT.itemsize}, "
                        f"vse_view {lib.vse_sizeof_view()} vs {ir.VIEW_DT.itemsize}")
@@ -417,6 +425,35 @@ class Context:
                                          C.c_void_p(workspace.data_ptr()), workspace.numel(), C.c_void_p(out.data_ptr()), self.stream()),
                "vse_scene_change")
         return out
+
+    # ---- frame ingest: YUV 4:2:0 -> BGR ---------------------------------------------------------------------------
+    def yuv420_to_bgr(self, packed_u8, n, h, w, layout="i420", row_parity=0, out=None):
+        """packed_u8: cuda uint8 holding n packed 4:2:0 (sub-)frames of h x w pixels (include/vse_hip.h vse_yuv420_to_bgr: luma rows,
+        then the chroma rows of layout "i420" | "nv12"), 1-D (frames back to back) or 2-D [n, stride] (frame stride = its row stride)
+        -> cuda uint8 [n,h,w,3] BGR on the current stream.  out: write into this tensor instead (it may be a strided view with packed
+        pixels; its pitch and frame stride are taken from it)."""
+        t = self.torch
+        n, h, w, row_parity = int(n), int(h), int(w), int(row_parity)
+        if layout not in YUV_LAYOUTS:
+            raise VseError(f"yuv420_to_bgr: layout {layout!r} is not one of {sorted(YUV_LAYOUTS)}")
+        assert packed_u8.dtype == t.uint8 and packed_u8.dim() in (1, 2) and packed_u8.stride(-1) == 1
+        frame = self.lib.vse_yuv420_frame_bytes(h, w, row_parity)
+        if packed_u8.dim() == 2:
+            assert packed_u8.shape[0] == n and packed_u8.shape[1] >= frame, (tuple(packed_u8.shape), n, frame)
+            sstride = packed_u8.stride(0) if n > 1 else max(packed_u8.stride(0), frame)
+        else:
+            assert packed_u8.numel() >= n * frame, (packed_u8.numel(), n, frame)
+            sstride = frame
+        if out is None:
+            out = t.empty((max(n, 0), max(h, 0), max(w, 0), 3), dtype=t.uint8, device=self.tdev)
+        assert out.dtype == t.uint8 and tuple(out.shape) == (n, h, w, 3) and out.stride(3) == 1 and out.stride(2) == 3
+        dstride = out.stride(0) if n > 1 else max(out.stride(0), (h - 1) * out.stride(1) + 3 * w)
+        _check(self.lib.vse_yuv420_to_bgr(self.handle, C.c_void_p(packed_u8.data_ptr()), n, h, w, YUV_LAYOUTS[layout], row_parity, sstride,
+                                          C.c_void_p(out.data_ptr()), out.stride(1), dstride, self.stream()), "vse_yuv420_to_bgr")
+        return out
+
+
+YUV_LAYOUTS = {"i420": 0, "nv12": 1}
 
 
 def _audio_queries(queries):

@@ -89,7 +89,8 @@ def run_ocr_tasks(source, tasks, ocr, sub_area=None, rec_char_type="ch", drop_sc
     cap.read(); tasks that carry a cached (dt_box, rec_res) — accurate mode — are not recognised again.
     uploader (staging.Uploader): batches are assembled in pinned memory and uploaded by a producer thread while the previous
     batch is recognised — the reference's producer / consumer pair at batch granularity; predict_batch then receives a
-    device uint8 tensor [n,H,W,3].  Without one the frames are stacked on the host.
+    device uint8 tensor [n,H,W,3] (a source with read_raw is read through it: its 4:2:0 planes are uploaded and converted on the
+    device).  Without one the frames are stacked on the host.
     shard=(rank, world): this rank recognises a contiguous slice of the tasks; every rank gets the records of all tasks back
     (one variable-length gather) and therefore returns the same lines.  -> list of raw.txt lines in task order."""
     tasks = [t for t in tasks if t[1] != -1]
@@ -98,13 +99,16 @@ def run_ocr_tasks(source, tasks, ocr, sub_area=None, rec_char_type="ch", drop_sc
         parallel.cap_host_threads(shard[1])       # one process per GPU: this rank's numpy / torch pools get cores / world threads
     results = {}                        # task index -> (dt_box, rec_res)
     batched = hasattr(ocr, "predict_batch")
+    # a YUV 4:2:0 source (ingest.Y4mSource / Yuv420Source) on the staged route hands out its planes: the uploader sends them as they
+    # are and converts on the device; every other route reads BGR ndarrays, converted on the host by the same integers
+    read = source.read_raw if batched and uploader is not None and hasattr(source, "read_raw") else source.read
 
     def batches():
         """lists of (task index, frame): consecutive readable tasks of one frame shape, at most `batch` of them"""
         pend = []
         for k in range(lo, hi):
             _total, no, dt_box, rec_res, _ms, default_area = tasks[k]
-            frame = source.read(no)
+            frame = read(no)
             if frame is None:
                 continue
             if dt_box is not None and rec_res is not None:
@@ -218,6 +222,12 @@ class SubtitleExtractor:
             self.uploader = staging.default_uploader() if hasattr(self.ocr, "predict_batch") else None
         return self.uploader
 
+    def _decode_order(self, uploader):
+        """The clip's frames for a selector: unconverted 4:2:0 planes where the source has them and an uploader converts them."""
+        if uploader is not None and hasattr(self.source, "raw_frames"):
+            return self.source.raw_frames()
+        return self.source.frames()
+
     def select_tasks(self):
         s = self.source
         if self.sub_area is not None and self.mode == "accurate" and self.detect_batch is not None:
@@ -227,10 +237,11 @@ class SubtitleExtractor:
                                                      predict_batch=getattr(self.ocr, "predict_batch", None) and self._predict_list,
                                                      detect_stream=self.detect_stream,
                                                      predict_with_dets=getattr(self.ocr, "predict_with_dets", None))
-            return [(t[0], t[1], t[2], t[3], None, None) for t in sel.run(s.frames(), uploader=up)]
+            return [(t[0], t[1], t[2], t[3], None, None) for t in sel.run(self._decode_order(up), uploader=up)]
         if self.sub_area is not None and self.mode in ("fast", "auto") and self.frame_selector == "change":
             sel = frame_select.ChangeFrameSelector(self.change_counter, batch=self.batch, **(self.change_params or {}))
-            self.intervals = sel.run(s.frames(), self.sub_area, uploader=self._uploader())
+            up = self._uploader()
+            self.intervals = sel.run(self._decode_order(up), self.sub_area, uploader=up)
             return [(s.frame_count, rep, None, None, None, self.default_subtitle_area) for _start, _end, rep in self.intervals]
         return fps_tasks(s.frame_count, s.fps, self.extract_frequency, self.default_subtitle_area)
 

@@ -75,7 +75,7 @@ class AccurateFrameSelector:
     def _ocr_of(self, no, frame):
         if no in self._prefetched:
             return self._prefetched.pop(no)
-        return self.predict(frame)
+        return self.predict(frame.to_bgr() if hasattr(frame, "to_bgr") else frame)      # (an unconverted ingest.Yuv420Frame)
 
     def _remember(self, no, frame):
         boxes, res = self._ocr_of(no, frame)

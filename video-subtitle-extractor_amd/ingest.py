@@ -12,8 +12,20 @@ Round 3: Motion-JPEG AVI (`ffmpeg -c:v mjpeg`, what many capture devices write) 
 every frame is a stand-alone baseline JPEG, and Pillow (libjpeg-turbo; importable on both boxes) decodes it.  The reference decodes
 the same stream with FFmpeg's own MJPEG decoder through cv2.VideoCapture: its IDCT / chroma up-sampling differ from libjpeg's by
 +-1..2 grey levels on some pixels, so this source is NOT bit-identical to the reference's decode (the uncompressed sources are).
+
+YUV 4:2:0 (Y4mSource, Yuv420Source): what every decoder produces before any colour conversion, at 1.5 bytes per pixel — `ffmpeg -pix_fmt
+yuv420p -f yuv4mpegpipe` (YUV4MPEG2, self-describing), `-f rawvideo` (headerless I420) and a hardware decoder's NV12 surfaces.  The files
+are memory-mapped; read() converts to BGR on the host (Yuv420Frame.to_bgr), read_raw() hands out the planes themselves (Yuv420Frame), which
+staging.Uploader packs into its pinned slab, uploads at half the bytes of a BGR frame and converts on the device (vse_yuv420_to_bgr): the
+same integers on both routes.  The conversion is BT.601 limited range with NEAREST chroma (the fixed-point constants of cv2.cvtColor
+COLOR_YUV2BGR_I420 / _NV12; the formula is in include/vse_hip.h).  The reference's cv2.VideoCapture converts with swscale: the same
+matrix, but a chroma up-sampling filter instead of the nearest sample, so these frames are NOT swscale's bits at chroma edges (luma-only
+content is).  Full-range (JPEG) YUV, 4:2:2 / 4:4:4 and more than 8 bits are refused; pipes are out of scope (a clip is read twice).
 """
+import mmap
+import os
 import struct
+from fractions import Fraction
 
 import numpy as np
 
@@ -212,9 +224,286 @@ class NpySource:
     pos_msec = None
 
 
-def open_source(path, fps=None):
+# ---- YUV 4:2:0 ------------------------------------------------------------------------------------------------------------------
+YUV_LAYOUTS = ("i420", "nv12")
+
+
+def _chroma_size(height, width):
+    return (height + 1) >> 1, (width + 1) >> 1
+
+
+class Yuv420Frame:
+    """Rows [y0, y1) of one 4:2:0 picture that has not been converted: the planes (views, e.g. into a file mapping) with `height`,
+    `width` and `layout` ("i420": planes = (Y [H,W], U [ch,cw], V [ch,cw]); "nv12": planes = (Y [H,W], UV [ch,2 cw])).
+    It stands where a BGR frame stands in the callers that only look at `.shape` and cut row bands: shape == (y1 - y0, width, 3),
+    frame[a:b] narrows the row range (one slice, step 1, Python slice rules; any other index is a TypeError), to_bgr() gives the
+    uint8 BGR ndarray, pack_into() the packed sub-frame vse_yuv420_to_bgr takes."""
+
+    def __init__(self, planes, height, width, layout="i420", y0=0, y1=None):
+        if layout not in YUV_LAYOUTS:
+            raise ValueError(f"layout must be one of {YUV_LAYOUTS}, not {layout!r}")
+        self.planes, self.height, self.width, self.layout = tuple(planes), int(height), int(width), layout
+        self.y0, self.y1 = int(y0), int(self.height if y1 is None else y1)
+        ch, cw = _chroma_size(self.height, self.width)
+        want = [(self.height, self.width)] + ([(ch, cw)] * 2 if layout == "i420" else [(ch, 2 * cw)])
+        if [tuple(p.shape) for p in self.planes] != want or not 0 <= self.y0 <= self.y1 <= self.height:
+            raise ValueError(f"{layout} planes of a {self.height} x {self.width} picture are {want}, rows {self.y0}:{self.y1} asked of "
+                             f"{[tuple(p.shape) for p in self.planes]}")
+
+    @property
+    def shape(self):
+        return (self.y1 - self.y0, self.width, 3)
+
+    def __getitem__(self, idx):
+        if not isinstance(idx, slice):
+            raise TypeError(f"a Yuv420Frame takes one row slice, not {idx!r}")
+        a, b, step = idx.indices(self.y1 - self.y0)
+        if step != 1:
+            raise TypeError(f"a Yuv420Frame takes a row slice of step 1, not {idx!r}")
+        return Yuv420Frame(self.planes, self.height, self.width, self.layout, self.y0 + a, self.y0 + max(a, b))
+
+    @property
+    def row_parity(self):
+        return self.y0 & 1
+
+    def _chroma_rows(self):
+        return self.y0 >> 1, (self.y1 + 1) >> 1
+
+    @property
+    def packed_bytes(self):
+        c0, c1 = self._chroma_rows()
+        return (self.y1 - self.y0) * self.width + 2 * (c1 - c0) * ((self.width + 1) >> 1)
+
+    def pack_into(self, dst_u8):
+        """The packed sub-frame (luma rows y0..y1, then chroma rows y0 >> 1 .. (y1 + 1) >> 1 of each plane; row parity y0 & 1) into the
+        first packed_bytes bytes of the 1-D uint8 array dst_u8: three contiguous copies for I420, two for NV12."""
+        c0, c1 = self._chroma_rows()
+        pos = 0
+        for plane, (a, b) in zip(self.planes, [(self.y0, self.y1)] + [(c0, c1)] * (len(self.planes) - 1)):
+            part = plane[a:b]
+            np.copyto(dst_u8[pos:pos + part.size].reshape(part.shape), part)
+            pos += part.size
+        return pos
+
+    def to_bgr(self):
+        """uint8 BGR [y1 - y0, W, 3]: BT.601 limited range, nearest chroma, the integers of vse_yuv420_to_bgr (include/vse_hip.h)."""
+        rows, cols = np.arange(self.y0, self.y1) >> 1, np.arange(self.width) >> 1
+        y = self.planes[0][self.y0:self.y1].astype(np.int32)
+        if self.layout == "i420":
+            u, v = (np.asarray(p)[rows][:, cols].astype(np.int32) for p in self.planes[1:])
+        else:
+            uv = np.asarray(self.planes[1])[rows]
+            u, v = uv[:, 2 * cols].astype(np.int32), uv[:, 2 * cols + 1].astype(np.int32)
+        c = np.maximum(y - 16, 0) * 1220542 + (1 << 19)
+        u -= 128
+        v -= 128
+        out = np.empty(self.shape, np.uint8)
+        out[..., 0] = np.clip((c + 2116026 * u) >> 20, 0, 255)
+        out[..., 1] = np.clip((c - 409993 * u - 852492 * v) >> 20, 0, 255)
+        out[..., 2] = np.clip((c + 1673527 * v) >> 20, 0, 255)
+        return out
+
+
+def bgr_to_yuv420(frame):
+    """uint8 BGR [H,W,3] -> (Y [H,W], U [ch,cw], V [ch,cw]) uint8: plain BT.601 limited-range forward transform, chroma the mean of
+    each 2 x 2 block (edge blocks of an odd size: of the pixels that exist).  Turns synthetic clips into test input; nothing is
+    specified about its rounding."""
+    f = np.asarray(frame, np.float64)
+    b, g, r = f[..., 0], f[..., 1], f[..., 2]
+    h, w = b.shape
+    ch, cw = _chroma_size(h, w)
+
+    def mean2(p):
+        q = np.pad(p, ((0, 2 * ch - h), (0, 2 * cw - w)), mode="edge")
+        return q.reshape(ch, 2, cw, 2).mean(axis=(1, 3))
+    y = 16.0 + (65.481 * r + 128.553 * g + 24.966 * b) / 255.0
+    u = 128.0 + mean2(-37.797 * r - 74.203 * g + 112.0 * b) / 255.0
+    v = 128.0 + mean2(112.0 * r - 93.786 * g - 18.214 * b) / 255.0
+    return tuple(np.clip(np.rint(p), 16, hi).astype(np.uint8) for p, hi in ((y, 235), (u, 240), (v, 240)))
+
+
+def _plane_bytes(frame_yuv, layout):
+    y, u, v = (np.ascontiguousarray(p, np.uint8) for p in frame_yuv)
+    ch, cw = _chroma_size(*y.shape)
+    if u.shape != (ch, cw) or v.shape != (ch, cw):
+        raise ValueError(f"chroma planes of a {y.shape[0]} x {y.shape[1]} picture are {ch} x {cw}, got {u.shape} and {v.shape}")
+    if layout == "i420":
+        return y.tobytes() + u.tobytes() + v.tobytes()
+    if layout == "nv12":
+        return y.tobytes() + np.stack([u, v], axis=2).tobytes()
+    raise ValueError(f"layout must be one of {YUV_LAYOUTS}, not {layout!r}")
+
+
+def write_y4m(path, frames_yuv, fps):
+    """YUV4MPEG2 file (what `ffmpeg -pix_fmt yuv420p -f yuv4mpegpipe` writes) of (Y, U, V) plane triples."""
+    frames_yuv = list(frames_yuv)
+    h, w = np.asarray(frames_yuv[0][0]).shape
+    rate = Fraction(fps).limit_denominator(100000)
+    with open(path, "wb") as fp:
+        fp.write(b"YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg\n" % (w, h, rate.numerator, rate.denominator))
+        for f in frames_yuv:
+            if np.asarray(f[0]).shape != (h, w):
+                raise ValueError("all frames of a Y4M file have one size")
+            fp.write(b"FRAME\n" + _plane_bytes(f, "i420"))
+
+
+def write_yuv420(path, frames_yuv, layout="i420"):
+    """Headerless file of consecutive frames (`ffmpeg -f rawvideo -pix_fmt yuv420p` / `nv12`) of (Y, U, V) plane triples."""
+    with open(path, "wb") as fp:
+        for f in frames_yuv:
+            fp.write(_plane_bytes(f, layout))
+
+
+class _Yuv420FileSource:
+    """The frame-source interface over a memory-mapped file whose frames start at self._offsets (packed I420 or NV12 pictures)."""
+
+    def _map(self, path):
+        self.path = path
+        self._fp = open(path, "rb")
+        size = os.fstat(self._fp.fileno()).st_size
+        self._mm = mmap.mmap(self._fp.fileno(), 0, access=mmap.ACCESS_READ) if size else None
+        self._buf = np.frombuffer(self._mm, np.uint8) if size else np.zeros(0, np.uint8)
+        return size
+
+    def _frame_bytes(self):
+        ch, cw = _chroma_size(self.height, self.width)
+        return self.height * self.width + 2 * ch * cw
+
+    def read_raw(self, frame_no):
+        """The planes of frame frame_no (1-based) as a Yuv420Frame of views into the mapping; None outside the clip."""
+        if not 1 <= frame_no <= self.frame_count:
+            return None
+        h, w = self.height, self.width
+        ch, cw = _chroma_size(h, w)
+        off = self._offsets[frame_no - 1]
+        luma = self._buf[off:off + h * w].reshape(h, w)
+        off += h * w
+        if self.layout == "i420":
+            planes = (luma, self._buf[off:off + ch * cw].reshape(ch, cw), self._buf[off + ch * cw:off + 2 * ch * cw].reshape(ch, cw))
+        else:
+            planes = (luma, self._buf[off:off + 2 * ch * cw].reshape(ch, 2 * cw))
+        return Yuv420Frame(planes, h, w, self.layout)
+
+    def read(self, frame_no):
+        raw = self.read_raw(frame_no)
+        return None if raw is None else raw.to_bgr()
+
+    def frames(self):
+        for no in range(1, self.frame_count + 1):
+            yield self.read(no)
+
+    def raw_frames(self):
+        for no in range(1, self.frame_count + 1):
+            yield self.read_raw(no)
+
+    def pos_msec(self, frame_no):
+        """As AviBgr24Source.pos_msec: the time stamp of the frame with 0-based index frame_no at a constant frame rate."""
+        return None if not 0 <= frame_no < self.frame_count else frame_no * 1000.0 / self.fps
+
+    def close(self):
+        self._buf = None
+        if self._mm is not None:
+            try:
+                self._mm.close()
+            except BufferError:           # frames handed out still view the mapping: it goes when they do
+                pass
+            self._mm = None
+        self._fp.close()
+
+
+class Y4mSource(_Yuv420FileSource):
+    """YUV4MPEG2 (.y4m) reader, memory-mapped, frames indexed once at open.  8-bit 4:2:0 progressive limited-range only: the header
+    tokens W H F (F0:0 or none: pass fps) I (p, ? or absent) A (ignored) C (absent, 420, 420jpeg, 420mpeg2, 420paldv; the siting they
+    name is ignored, see the module docstring) X... (ignored, except XCOLORRANGE=FULL, which is refused)."""
+
+    layout = "i420"
+
+    def __init__(self, path, fps=None):
+        size = self._map(path)
+        mm = self._mm
+        end = mm.find(b"\n", 0, 4096) if size else -1
+        if end < 0 or mm[:10] != b"YUV4MPEG2 ":
+            raise ValueError(f"{path}: not a YUV4MPEG2 file")
+        self.width = self.height = None
+        self.fps = None
+        for tok in mm[10:end].decode("ascii", "replace").split():
+            key, val = tok[0], tok[1:]
+            if key == "W":
+                self.width = int(val)
+            elif key == "H":
+                self.height = int(val)
+            elif key == "F":
+                num, _, den = val.partition(":")
+                if int(num) > 0 and int(den or 1) > 0:
+                    self.fps = int(num) / float(int(den or 1))
+            elif key == "I":
+                if val not in ("p", "?"):
+                    raise ValueError(f"{path}: interlaced video ({tok}) is not supported")
+            elif key == "C":
+                if val not in ("420", "420jpeg", "420mpeg2", "420paldv"):
+                    raise ValueError(f"{path}: chroma format {tok} is not supported, only 8-bit 4:2:0 (C420, C420jpeg, C420mpeg2, C420paldv)")
+            elif tok == "XCOLORRANGE=FULL":
+                raise ValueError(f"{path}: full-range video ({tok}) needs other conversion constants and is not supported")
+        if not self.width or not self.height or self.width < 1 or self.height < 1:
+            raise ValueError(f"{path}: the YUV4MPEG2 header carries no frame size")
+        if fps is not None:
+            self.fps = float(fps)
+        if self.fps is None:
+            raise ValueError(f"{path}: the YUV4MPEG2 header carries no frame rate (F0:0 or no F token): pass fps")
+        nbytes = self._frame_bytes()
+        self._offsets = []
+        pos = end + 1
+        while pos < size:
+            head = mm[pos:pos + 6]
+            if len(head) < 6 and b"FRAME"[:len(head)] == head[:5]:
+                break                      # the file ends inside a frame header: a truncated last frame
+            if head[:5] != b"FRAME" or head[5:6] not in (b" ", b"\n"):
+                raise ValueError(f"{path}: bytes at offset {pos} are neither a FRAME header nor the end of the file")
+            nl = mm.find(b"\n", pos + 5, pos + 4096)
+            if nl < 0:
+                if size - pos <= 4096:
+                    break                  # truncated inside the frame header's parameters
+                raise ValueError(f"{path}: the FRAME header at offset {pos} does not end")
+            if nl + 1 + nbytes > size:
+                break                      # a truncated last frame is not a frame
+            self._offsets.append(nl + 1)
+            pos = nl + 1 + nbytes
+        self.frame_count = len(self._offsets)
+
+
+class Yuv420Source(_Yuv420FileSource):
+    """Headerless file of consecutive 8-bit 4:2:0 frames (layout "i420": Y, U, V planes; "nv12": Y plane, interleaved UV plane), memory-
+    mapped.  A partial last frame is dropped."""
+
+    def __init__(self, path, width, height, fps, layout="i420"):
+        if layout not in YUV_LAYOUTS:
+            raise ValueError(f"layout must be one of {YUV_LAYOUTS}, not {layout!r}")
+        self.width, self.height, self.fps, self.layout = int(width), int(height), float(fps), layout
+        if self.width < 1 or self.height < 1:
+            raise ValueError(f"{path}: frame size {width} x {height}")
+        size = self._map(path)
+        nbytes = self._frame_bytes()
+        self.frame_count = size // nbytes
+        self._offsets = range(0, self.frame_count * nbytes, nbytes)
+
+
+_RAW_YUV_EXT = {".yuv": "i420", ".i420": "i420", ".nv12": "nv12"}
+
+
+def open_source(path, fps=None, size=None, layout=None):
+    """The source of a file by its extension: .npy (needs fps), .y4m, .yuv / .i420 / .nv12 (headerless: need size=(width, height) and
+    fps; `layout` overrides the extension's), anything else an AVI."""
+    ext = os.path.splitext(str(path))[1].lower()
     if str(path).endswith(".npy"):
         if fps is None:
             raise ValueError("a .npy frame stack carries no frame rate: pass fps")
         return NpySource(path, fps)
+    if ext == ".y4m":
+        return Y4mSource(path, fps)
+    if ext in _RAW_YUV_EXT:
+        if size is None:
+            raise ValueError(f"{path}: a headerless YUV file carries no frame size: pass size=(width, height)")
+        if fps is None:
+            raise ValueError(f"{path}: a headerless YUV file carries no frame rate: pass fps")
+        return Yuv420Source(path, size[0], size[1], fps, layout or _RAW_YUV_EXT[ext])
     return AviBgr24Source(path)

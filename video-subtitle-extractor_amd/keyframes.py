@@ -17,8 +17,10 @@ Known limit: a pan faster than search * scale source pixels per frame leaves eve
 as it does beyond SCXvid's own search range; so does a fade through black or a flash.
 
     python -m vse_amd.keyframes VIDEO -o keyframes.txt [--search N --bias N --cut-percent N --scale N --batch N]
+                                [--size WxH --layout i420|nv12]
 
-VIDEO is what ingest.open_source reads: uncompressed BGR24 or Motion-JPEG AVI, or a .npy frame stack.
+VIDEO is what ingest.open_source reads: uncompressed BGR24 or Motion-JPEG AVI, a .npy frame stack, YUV4MPEG2 (.y4m), or headerless
+YUV 4:2:0 (.yuv / .i420 / .nv12, with --size).
 """
 import argparse
 import sys
@@ -173,17 +175,28 @@ def parse_keyframes(path):
 def main(argv=None):
     p = argparse.ArgumentParser(prog="python -m vse_amd.keyframes", description="Find a video's scene cuts on the GPU and write them as a "
                                 "keyframes file for python -m vse_amd.timeline_sync --src-keyframes / --dst-keyframes.")
-    p.add_argument("video", help="uncompressed BGR24 or Motion-JPEG AVI, or a .npy frame stack")
+    p.add_argument("video", help="uncompressed BGR24 or Motion-JPEG AVI, a .npy frame stack, .y4m, or headerless .yuv / .i420 / .nv12")
     p.add_argument("-o", "--output", required=True, help="keyframes file to write")
     p.add_argument("--search", type=int, default=8, help="search radius in plane pixels, 0..8 [8]")
     p.add_argument("--bias", type=int, default=1024, help="a block changed iff 2 * inter > intra + bias [1024]")
     p.add_argument("--cut-percent", type=float, default=50, help="changed blocks that make a keyframe, in percent [50]")
     p.add_argument("--scale", type=int, default=None, help="box filter edge, 1..8 [width // 640]")
     p.add_argument("--batch", type=int, default=64, help="frames per device call [64]")
+    p.add_argument("--size", default=None, metavar="WxH", help="frame size of a headerless YUV 4:2:0 file")
+    p.add_argument("--layout", default=None, choices=("i420", "nv12"), help="plane layout of a headerless YUV 4:2:0 file [by extension]")
     args = p.parse_args(argv)
     from . import ingest
     try:
-        source = ingest.open_source(args.video, fps=1.0) if args.video.endswith(".npy") else ingest.open_source(args.video)
+        size = None
+        if args.size is not None:
+            w, sep, h = args.size.lower().partition("x")
+            if not (sep and w.isdigit() and h.isdigit()):
+                raise ValueError(f"--size takes WIDTHxHEIGHT, not {args.size!r}")
+            size = (int(w), int(h))
+        if args.video.lower().endswith((".npy", ".yuv", ".i420", ".nv12")):       # no frame rate in the file, and none is needed here
+            source = ingest.open_source(args.video, fps=1.0, size=size, layout=args.layout)
+        else:
+            source = ingest.open_source(args.video)
         if args.batch < 1:
             raise ValueError("--batch must be at least 1")
         kf, count = scan(source, None, args.batch, scale=args.scale, search=args.search, bias=args.bias, cut_percent=args.cut_percent)

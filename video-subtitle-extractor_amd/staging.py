@@ -10,6 +10,10 @@ producer thread while the current one is recognised (`prefetch`).
     up = Uploader(device)                         # torch.device / "cuda:0"
     for items, batch in prefetch(batches, up):    # batches: iterable of lists of (key, frame) with equal frame shapes
         dev = batch.tensor()                      # uint8 [n,H,W,3] on the device, ordered after the copy on the current stream
+
+Frames that are still YUV 4:2:0 (ingest.Yuv420Frame, from a source's read_raw / raw_frames) are packed into the slab as they are — 1.5
+bytes per pixel, half the slab copy and half the PCIe bytes of a BGR frame — and converted to BGR by one kernel on the copy stream
+(vse_yuv420_to_bgr), so a consumer sees the same uint8 [n,H,W,3] tensor either way.
 """
 import queue
 import threading
@@ -31,9 +35,11 @@ class StagedBatch:
 
 
 class Uploader:
-    def __init__(self, device, depth=3, workers=4):
+    def __init__(self, device, depth=3, workers=4, ctx=None):
+        """ctx: the engine.Context of `device` that converts YUV 4:2:0 batches (default: the shim's, obtained on the first such batch)."""
         import torch
         self.device = torch.device(device)
+        self._ctx = ctx
         self.depth = depth
         self._slabs = [None] * depth            # pinned uint8 buffers, grown on demand
         self._busy = [None] * depth             # event of the last copy out of each slab
@@ -56,6 +62,8 @@ class Uploader:
     def stage(self, frames):
         """list of equal-shaped uint8 frames (views are fine) -> StagedBatch"""
         import torch
+        if hasattr(frames[0], "pack_into"):
+            return self._stage_yuv420(frames)
         shape = tuple(frames[0].shape)
         per = int(np.prod(shape))
         k, slab = self._slab(per * len(frames))
@@ -65,6 +73,42 @@ class Uploader:
         with torch.cuda.stream(self._stream):
             dev = torch.empty((len(frames),) + shape, dtype=torch.uint8, device=self.device)
             dev.copy_(host, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self._stream)
+        self._busy[k] = ev
+        return StagedBatch(dev, ev)
+
+    def _context(self):
+        if self._ctx is None:
+            from . import shim
+            self._ctx = shim._context()
+        if self.device.index is not None and self._ctx.tdev.index != self.device.index:
+            raise ValueError(f"Uploader on {self.device} was given the engine context of {self._ctx.tdev}")
+        return self._ctx
+
+    def _stage_yuv420(self, frames):
+        """Yuv420Frames of one shape, layout and row parity -> StagedBatch of their BGR conversion: packed into the slab (frame stride
+        rounded up to 16 bytes, which the 16-byte kernel needs), one copy, one vse_yuv420_to_bgr on the copy stream."""
+        import torch
+        first = frames[0]
+        key = (tuple(first.shape), first.layout, first.row_parity)
+        for f in frames:
+            if not hasattr(f, "pack_into") or (tuple(f.shape), f.layout, f.row_parity) != key:
+                raise ValueError("Uploader.stage: the YUV 4:2:0 frames of a batch must share shape, layout and row parity (y0 & 1): "
+                                 f"{key} and {(tuple(f.shape), getattr(f, 'layout', None), getattr(f, 'row_parity', None))}")
+        ctx = self._context()
+        n, (h, w, _) = len(frames), first.shape
+        per = (first.packed_bytes + 15) & ~15
+        k, slab = self._slab(per * n)
+        host = slab[:per * n].view(n, per)
+        dst = host.numpy()
+        list(self._pool.map(lambda i: frames[i].pack_into(dst[i]), range(n)))
+        with torch.cuda.stream(self._stream):
+            # `packed` is allocated, filled and read on the copy stream alone: the caching allocator hands its block out again only to
+            # this stream, behind the conversion, so it may be dropped here (`dev` crosses streams: StagedBatch.tensor records that)
+            packed = torch.empty((n, per), dtype=torch.uint8, device=self.device)
+            packed.copy_(host, non_blocking=True)
+            dev = ctx.yuv420_to_bgr(packed, n, h, w, first.layout, first.row_parity)
             ev = torch.cuda.Event()
             ev.record(self._stream)
         self._busy[k] = ev
