@@ -230,6 +230,44 @@ int vse_frame_change(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_
                      int y0, int y1, int x0, int x1, int edge_thresh, void* d_state, int reset,
                      int32_t* d_counts /* [n,3]: edges, appeared, vanished */, void* stream);
 
+/* ---- subtitle-area locator --------------------------------------------------------------------------------------------- */
+/* Replaces: the rectangle a person draws in the reference's GUI (config.subtitleSelectionAreas, backend/config.py:49), which
+ * SubtitleExtractor.run needs before it can take either frame-accurate path (backend/main.py:137-147).  Not an algorithm of the
+ * reference but that role: a subtitle is strong luma edges that hold still for a while and then change all at once, a logo never
+ * changes, a scene changes all the time.  Here the device part: vse_frame_change's edge mask over a whole region, counted per CELL,
+ * with the interval automaton of vse_amd.frame_select.change_intervals run per cell on the device; the host turns the few integers
+ * per cell into a rectangle (vse_amd.area_locator.locate_area).
+ * Region [y0, y1) x [x0, x1) of area_h x area_w pixels, at least 3 x 3; E = the edge pixels of its interior exactly as defined for
+ * vse_frame_change.  Cell (j, i) = interior rows 8 j .. 8 j + 7 and interior columns 64 i .. 64 i + 63 (cut off at the interior's
+ * end); gy = ceil((area_h - 2) / 8) by gx = ceil((area_w - 2) / 64) cells.  Per cell and frame t, over the cell's pixels:
+ *   e[t] = |E|, a[t] = |E and not E'|, v[t] = |E' and not E|                  (E' = the previous frame's edge pixels)
+ *   present[t] = e[t] >= min_edges
+ *   ratio cut before t: present[t-1] and present[t] and e[t-1] + a[t] > 0 and (a[t] + v[t]) ratio_den >= ratio_num (e[t-1] + a[t])
+ *   a run = a maximal stretch of present frames without a ratio cut inside; when a run of L frames closes (a frame that is not
+ *   present, a ratio cut, or `flush`) and min_frames <= L <= max_frames: covered += L, runs += 1
+ *   present = number of present frames, cuts = number of ratio cuts.
+ * vse_frame_cells_dims: gy and gx of a region; VSE_E_INVAL below 3 x 3. */
+int vse_frame_cells_dims(int area_h, int area_w, int* gy, int* gx);
+/* Size in bytes of the caller-owned state (8-byte aligned) that carries each cell's last mask (e[t-1] is its population count) and
+ * the length of its open run from one call to the next; 0 below 3 x 3.  A fresh state is zero-filled. */
+size_t vse_frame_cells_state_bytes(int area_h, int area_w);
+/* n >= 0 uint8 BGR frames [n, src_h, src_w, 3] (pitch and frame stride as for vse_frame_change; only the region's pixels are read)
+ * -> d_totals int32 [gy, gx, 4] = covered, runs, present, cuts per cell, accumulated across calls: the call continues from d_state
+ * and from what d_totals holds, so a clip fed in batches of any size gives the totals of one call.  `reset` starts a clip: state and
+ * totals count from zero and E' is empty for the first frame.  `flush` closes the open runs after the last frame of the call (runs
+ * still open count nowhere until then); n == 0 with `flush` does only that.  d_cell_counts, when not NULL, receives int32
+ * [n, gy, gx, 3] = e, a, v per frame and cell; summed over the cells they are vse_frame_change's counts of the same area.
+ * One launch on `stream`, no allocation, no device sync; a block owns its cell for all frames of the call and alone writes the
+ * cell's state, totals and counts.  Returns VSE_E_INVAL, without touching the device, for a degenerate or out-of-frame region,
+ * n < 0, ratio_num < 1, ratio_den outside 1..1024, or not 1 <= min_frames <= max_frames. */
+int vse_frame_cells(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride,
+                    int y0, int y1, int x0, int x1, int edge_thresh,
+                    int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
+                    void* d_state, int reset, int flush,
+                    int32_t* d_totals      /* [gy,gx,4]: covered, runs, present, cuts; accumulated across calls */,
+                    int32_t* d_cell_counts /* nullable: [n,gy,gx,3] edges, appeared, vanished per frame and cell */,
+                    void* stream);
+
 /* ---- timeline sync: audio template search ----------------------------------------------------------------------------- */
 /* Replaces: Sushi's WavStream.find_substream (backend/sushi/wav.py:179-189), cv2.matchTemplate(TM_SQDIFF_NORMED) of one group's
  * source audio against a window of the destination audio.  Both streams are uint8.  A query takes the pattern

@@ -11,6 +11,9 @@
 // one packed word; the words of a chunk of frames meet in LDS, where one thread per frame compares each frame with the one
 // before it.  The previous mask of the tile is read from the caller's state at the start and written back at the end by the
 // same block: no block reads what another block writes, so a batch needs no second pass and no grid-wide ordering.
+//
+// Subtitle-area locator (vse_frame_cells): the same tiles and the same mask, but a tile is a CELL that keeps its own counts and runs
+// the interval automaton of frame_select.change_intervals on them (frame_cells_kernel below).
 #include "common.h"
 
 namespace {
@@ -93,6 +96,155 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_change_kernel(const uint8
     if (threadIdx.x == 0) *flag = 1u;
 }
 
+// ---- vse_frame_cells ------------------------------------------------------------------------------------------------------------
+// The tile and its mask words are frame_change_kernel's above, statement for statement, as two helpers.  frame_change_kernel keeps its
+// own inline copy: routed through these helpers it compiled to slightly different code and measured 0.3-0.6 % slower (64 x 1080p,
+// alternating with the inline build in one process), and that kernel's behaviour is not this one's to change.
+// What a lane reads of its block's tile; fixed for the whole kernel.
+struct TileLane {
+    int rows;       // interior rows of the tile that lie in the area
+    bool inner;     // the lane's column is an interior column
+    bool own;       // ... or the right border column (the horizontal neighbour of the last one), which is read too
+    bool extra;     // a wave's horizontal neighbours come from the lanes beside it; lanes 0 and 63 read the column outside the word themselves
+    int x, xe;      // frame column of the lane, and of that extra read
+};
+
+__device__ __forceinline__ TileLane tile_lane(int w, int iy0, int ih, int iw, int x0) {
+    const int lane = threadIdx.x & 63;
+    const int ix = w * 64 + lane;              // interior column of this lane
+    TileLane t;
+    t.rows = min(FC_ROWS, ih - iy0);
+    t.inner = ix < iw;
+    t.own = ix <= iw;
+    t.x = x0 + 1 + ix;
+    t.extra = t.inner && (lane == 0 || lane == 63);
+    t.xe = lane == 0 ? t.x - 1 : t.x + 1;
+    return t;
+}
+
+// msk[tl][k] = packed mask of the tile's interior row k in frame c0 + tl, for tl < cn: a wave per frame, the waves side by side.
+// src points at the tile's first halo row in frame 0 (rows 0 .. rows + 1 and columns x0 .. x0 + iw + 1 of the area are read only).
+__device__ __forceinline__ void tile_masks(const uint8_t* __restrict__ src, int c0, int cn, long pitch, long fstride, const TileLane& t,
+                                           int thresh, unsigned long long (*msk)[FC_ROWS]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int rows = t.rows;
+    for (int tl = wave; tl < cn; tl += FC_WAVES) {
+        const uint8_t* f = src + (long)(c0 + tl) * fstride;
+        int yc[FC_ROWS + 2], ye[FC_ROWS];
+#pragma unroll
+        for (int k = 0; k < FC_ROWS + 2; ++k) yc[k] = (k < rows + 2 && t.own) ? luma(f + (long)k * pitch + t.x * 3) : 0;
+#pragma unroll
+        for (int k = 0; k < FC_ROWS; ++k) ye[k] = (k < rows && t.extra) ? luma(f + (long)(k + 1) * pitch + t.xe * 3) : 0;
+#pragma unroll
+        for (int k = 0; k < FC_ROWS; ++k) {
+            unsigned long long b = 0;
+            if (k < rows) {                // block-uniform
+                const int l = __shfl_up(yc[k + 1], 1), r = __shfl_down(yc[k + 1], 1);
+                const int left = lane == 0 ? ye[k] : l, right = lane == 63 ? ye[k] : r;
+                const int e = max(abs(right - left), abs(yc[k + 2] - yc[k]));
+                b = __ballot(t.inner && e >= thresh);
+            }
+            if (lane == 0) msk[tl][k] = b;
+        }
+    }
+}
+
+// Per-cell state of vse_frame_cells: the FC_ROWS mask words of the cell's last frame, then the length of its open run.
+constexpr int CELL_STATE_WORDS = FC_ROWS + 1;
+
+struct CellRule {
+    int min_edges, ratio_num, ratio_den, min_frames, max_frames;
+};
+
+// One cell's interval automaton: frame_select.change_intervals in integers, with the run lengths summed instead of listed.
+// Every value here is the same in all lanes of the wave that walks it.
+struct CellRuns {
+    int run, covered, runs, present, cuts;
+    __device__ __forceinline__ void close(const CellRule& r) {
+        if (run >= r.min_frames && run <= r.max_frames) {
+            covered += run;
+            ++runs;
+        }
+        run = 0;
+    }
+    // is_present: edges >= min_edges; ratio_cut: the ratio test against the frame before (it counts only inside a run)
+    __device__ __forceinline__ void step(bool is_present, bool ratio_cut, const CellRule& r) {
+        if (!is_present) {
+            close(r);
+            return;
+        }
+        ++present;
+        if (run && ratio_cut) {
+            ++cuts;
+            close(r);
+        }
+        ++run;
+    }
+};
+
+// The grid is gx x gy cells; block (cx, cy) owns cell cy * gx + cx in state, totals and cell_counts alike, for all frames of the call.
+// src points at row y0 of frame 0.  Runs with n == 0 too (reset and flush only).
+__global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_kernel(const uint8_t* __restrict__ src, int n, long pitch, long fstride,
+                                                                    int x0, int ih, int iw, int thresh, CellRule rule,
+                                                                    unsigned long long* __restrict__ state, int reset, int flush,
+                                                                    int* __restrict__ totals, int* __restrict__ cell_counts) {
+    __shared__ unsigned long long msk[FC_CHUNK][FC_ROWS];
+    __shared__ unsigned long long prv[FC_ROWS];
+    static_assert(FC_CHUNK == 64, "the frames of a chunk are the lanes of wave 0");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int iy0 = blockIdx.y * FC_ROWS;
+    const long cell = (long)blockIdx.y * gridDim.x + blockIdx.x, cells = (long)gridDim.y * gridDim.x;
+    const TileLane t = tile_lane(blockIdx.x, iy0, ih, iw, x0);
+    unsigned long long* st = state + cell * CELL_STATE_WORDS;
+    int* tot = totals + cell * 4;
+    // words of rows outside the region are zero in every frame, so all FC_ROWS words are kept
+    if (threadIdx.x < FC_ROWS) prv[threadIdx.x] = reset ? 0ull : st[threadIdx.x];
+    CellRuns cr = {0, 0, 0, 0, 0};
+    if (wave == 0 && !reset) cr = {(int)st[FC_ROWS], tot[0], tot[1], tot[2], tot[3]};
+
+    for (int c0 = 0; c0 < n; c0 += FC_CHUNK) {
+        const int cn = min(FC_CHUNK, n - c0);
+        tile_masks(src + (long)iy0 * pitch, c0, cn, pitch, fstride, t, thresh, msk);
+        __syncthreads();
+        if (wave == 0) {                           // lane = frame of the chunk
+            const bool live = lane < cn;
+            int e = 0, a = 0, v = 0, ep = 0;
+            if (live) {
+#pragma unroll
+                for (int k = 0; k < FC_ROWS; ++k) {
+                    const unsigned long long cur = msk[lane][k], pre = lane ? msk[lane - 1][k] : prv[k];
+                    e += __popcll(cur);
+                    a += __popcll(cur & ~pre);
+                    v += __popcll(pre & ~cur);
+                    ep += __popcll(pre);           // edges[t-1]
+                }
+                if (cell_counts) {
+                    int* o = cell_counts + ((long)(c0 + lane) * cells + cell) * 3;
+                    o[0] = e;
+                    o[1] = a;
+                    o[2] = v;
+                }
+            }
+            const long long uni = ep + a;          // |E' or E|
+            const unsigned long long present = __ballot(live && e >= rule.min_edges);
+            const unsigned long long ratio = __ballot(live && uni > 0 && (long long)(a + v) * rule.ratio_den >= (long long)rule.ratio_num * uni);
+            for (int f = 0; f < cn; ++f) cr.step((present >> f) & 1, (ratio >> f) & 1, rule);
+        }
+        __syncthreads();
+        if (threadIdx.x < FC_ROWS) prv[threadIdx.x] = msk[cn - 1][threadIdx.x];
+        __syncthreads();
+    }
+    if (threadIdx.x < FC_ROWS) st[threadIdx.x] = prv[threadIdx.x];
+    if (threadIdx.x == 0) {
+        if (flush) cr.close(rule);
+        st[FC_ROWS] = (unsigned long long)cr.run;
+        tot[0] = cr.covered;
+        tot[1] = cr.runs;
+        tot[2] = cr.present;
+        tot[3] = cr.cuts;
+    }
+}
+
 }  // namespace
 
 // Called by vse_frame_change (vse_runtime.hip) after it has checked the geometry.
@@ -106,5 +258,21 @@ int vse_frame_change_launch(const void* d_bgr, int n, int64_t pitch, int64_t fra
     const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
     hipLaunchKernelGGL(frame_change_kernel, dim3(wpr, (ih + FC_ROWS - 1) / FC_ROWS), dim3(FC_WAVES * 64), 0, st, src, n, (long)pitch,
                        (long)frame_stride, x0, ih, iw, wpr, edge_thresh, words, flag, reset, reinterpret_cast<int*>(d_counts));
+    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+}
+
+int vse_frame_cells_state_words() { return CELL_STATE_WORDS; }
+
+// Called by vse_frame_cells (vse_runtime.hip) after it has checked the arguments.
+int vse_frame_cells_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
+                           int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames, void* d_state, int reset, int flush,
+                           int32_t* d_totals, int32_t* d_cell_counts, void* stream) {
+    const int ih = y1 - y0 - 2, iw = x1 - x0 - 2;
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
+    const CellRule rule = {min_edges, ratio_num, ratio_den, min_frames, max_frames};
+    hipLaunchKernelGGL(frame_cells_kernel, dim3((iw + 63) / 64, (ih + FC_ROWS - 1) / FC_ROWS), dim3(FC_WAVES * 64), 0,
+                       reinterpret_cast<hipStream_t>(stream), src, n, (long)pitch, (long)frame_stride, x0, ih, iw, edge_thresh, rule,
+                       reinterpret_cast<unsigned long long*>(d_state), reset, flush, reinterpret_cast<int*>(d_totals),
+                       reinterpret_cast<int*>(d_cell_counts));
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }

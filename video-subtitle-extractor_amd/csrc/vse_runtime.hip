@@ -50,6 +50,10 @@ struct vse_plan {
 
 int vse_frame_change_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
                             void* d_state, int reset, int32_t* d_counts, void* stream);     // frame_change.hip
+int vse_frame_cells_state_words();                                                                                     // frame_change.hip
+int vse_frame_cells_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
+                           int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames, void* d_state, int reset, int flush,
+                           int32_t* d_totals, int32_t* d_cell_counts, void* stream);                                    // frame_change.hip
 int vse_scene_change_plane_pitch(int aw);                                                                              // scene_cut.hip
 int vse_scene_change_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int scale, int ah, int aw, int search, int bias,
                             void* d_state, int reset, void* d_ws, int32_t* d_counts, void* stream);
@@ -412,6 +416,45 @@ int vse_frame_change(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w,
         return VSE_E_INVAL;
     }
     return vse_frame_change_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, d_state, reset, d_counts, stream);
+}
+
+// ---- subtitle-area locator (frame_change.hip) -------------------------------------------------------------------------------
+int vse_frame_cells_dims(int area_h, int area_w, int* gy, int* gx) {
+    if (area_h < 3 || area_w < 3 || !gy || !gx) return VSE_E_INVAL;
+    *gy = (area_h - 2 + 7) / 8;
+    *gx = (area_w - 2 + 63) / 64;
+    return VSE_OK;
+}
+
+size_t vse_frame_cells_state_bytes(int area_h, int area_w) {
+    int gy, gx;
+    if (vse_frame_cells_dims(area_h, area_w, &gy, &gx) != VSE_OK) return 0;
+    return (size_t)gy * gx * vse_frame_cells_state_words() * 8;
+}
+
+int vse_frame_cells(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0,
+                    int x1, int edge_thresh, int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames, void* d_state,
+                    int reset, int flush, int32_t* d_totals, int32_t* d_cell_counts, void* stream) {
+    if (!c || (!d_bgr && n > 0) || !d_state || !d_totals || n < 0 || src_h <= 0 || src_w <= 0 || pitch < (int64_t)src_w * 3 ||
+        (n > 1 && frame_stride < (int64_t)(src_h - 1) * pitch + (int64_t)src_w * 3) || (reinterpret_cast<uintptr_t>(d_state) & 7)) {
+        set_err("vse_frame_cells: bad arguments (n %d, frame %d x %d, pitch %lld, frame stride %lld, state 8-byte aligned)", n, src_h, src_w,
+                (long long)pitch, (long long)frame_stride);
+        return VSE_E_INVAL;
+    }
+    if (y0 < 0 || x0 < 0 || y1 > src_h || x1 > src_w || y1 - y0 < 3 || x1 - x0 < 3) {
+        set_err("vse_frame_cells: region [%d, %d) x [%d, %d) is degenerate or outside the %d x %d frame", y0, y1, x0, x1, src_h, src_w);
+        return VSE_E_INVAL;
+    }
+    if (ratio_num < 1 || ratio_den < 1 || ratio_den > 1024 || min_frames < 1 || max_frames < min_frames) {
+        set_err("vse_frame_cells: ratio %d / %d (numerator >= 1, denominator 1..1024) or run length %d..%d (1 <= min <= max) out of range",
+                ratio_num, ratio_den, min_frames, max_frames);
+        return VSE_E_INVAL;
+    }
+    if (n == 0 && !reset && !flush) return VSE_OK;
+    const int rc = vse_frame_cells_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, min_edges, ratio_num, ratio_den,
+                                          min_frames, max_frames, d_state, reset, flush, d_totals, d_cell_counts, stream);
+    if (rc != VSE_OK) set_err("vse_frame_cells: launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
 }
 
 // ---- timeline sync: scene cuts for keyframe snapping (scene_cut.hip) ---------------------------------------------------------

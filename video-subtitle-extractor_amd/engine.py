@@ -5,6 +5,7 @@ goes through the C ABI; there is NO fallback — if the library or a gfx950 GPU 
 """
 import ctypes as C
 import os
+from collections import namedtuple
 
 import numpy as np
 
@@ -21,7 +22,7 @@ EXPORTS = [
     "vse_det_forward", "vse_rec_forward", "vse_plan_set_source", "vse_plan_takes_frames",
     "vse_rec_graph_create", "vse_graph_launch", "vse_graph_destroy", "vse_frame_change_state_bytes", "vse_frame_change",
     "vse_audio_match_workspace_bytes", "vse_audio_match", "vse_scene_change_state_bytes", "vse_scene_change_workspace_bytes",
-    "vse_scene_change",
+    "vse_scene_change", "vse_frame_cells_dims", "vse_frame_cells_state_bytes", "vse_frame_cells",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -31,6 +32,18 @@ EXPORTS_NUMBERED = ["vse_yuv420_frame_bytes", "vse_yuv420_to_bgr"]
 
 class VseError(RuntimeError):
     pass
+
+
+# The integer parameters of vse_frame_cells (include/vse_hip.h): the edge threshold and the per-cell interval rule.
+CellParams = namedtuple("CellParams", "edge_thresh min_edges ratio_num ratio_den min_frames max_frames")
+
+
+class CellsState:
+    """What vse_frame_cells carries from one call to the next: `words` (the cells' last masks and open runs) and `totals`, cuda int32
+    [gy,gx,4] = covered, runs, present, cuts per cell so far."""
+
+    def __init__(self, words, totals):
+        self.words, self.totals = words, totals
 
 
 class DbParams(C.Structure):
@@ -122,6 +135,12 @@ def load_library(path=None):
     lib.vse_frame_change_state_bytes.argtypes = [C.c_int, C.c_int]
     lib.vse_frame_change.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.vse_frame_cells_dims.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.vse_frame_cells_state_bytes.restype = C.c_size_t
+    lib.vse_frame_cells_state_bytes.argtypes = [C.c_int, C.c_int]
+    lib.vse_frame_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vse_audio_match_workspace_bytes.restype = C.c_size_t
     lib.vse_audio_match_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
     lib.vse_audio_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
@@ -375,6 +394,42 @@ class Context:
                                          frames_u8.stride(0), y0, y1, x0, x1, int(edge_thresh), C.c_void_p(state.data_ptr()),
                                          int(bool(reset)), C.c_void_p(out.data_ptr()), self.stream()), "vse_frame_change")
         return out
+
+    # ---- subtitle-area locator ------------------------------------------------------------------------------------
+    def frame_cells_dims(self, area_h, area_w):
+        """(gy, gx): the cells of a region of area_h x area_w pixels (8 x 64 interior pixels each)."""
+        gy, gx = C.c_int(), C.c_int()
+        if self.lib.vse_frame_cells_dims(int(area_h), int(area_w), C.byref(gy), C.byref(gx)) != 0:
+            raise VseError(f"frame_cells: a region of {area_h} x {area_w} pixels has no interior")
+        return gy.value, gx.value
+
+    def frame_cells_state(self, area_h, area_w):
+        """A fresh CellsState (zero-filled) for frame_cells over a region of area_h x area_w pixels."""
+        gy, gx = self.frame_cells_dims(area_h, area_w)
+        t = self.torch
+        return CellsState(t.zeros(self.lib.vse_frame_cells_state_bytes(int(area_h), int(area_w)), dtype=t.uint8, device=self.tdev),
+                          t.zeros((gy, gx, 4), dtype=t.int32, device=self.tdev))
+
+    def frame_cells(self, frames_u8, area, params, state, reset=False, flush=False, want_counts=False):
+        """frames_u8: cuda uint8 [n,H,W,3] (any row pitch / frame stride, pixels packed; n may be 0, for a flush alone),
+        area = (y0, y1, x0, x1) in its pixels, params: CellParams, state: frame_cells_state of the area's size -> state.totals, the
+        cuda int32 [gy,gx,4] covered / runs / present / cuts per cell accumulated since the last reset (include/vse_hip.h
+        vse_frame_cells); with want_counts (totals, cuda int32 [n,gy,gx,3] edges / appeared / vanished per frame and cell)."""
+        t = self.torch
+        assert frames_u8.dtype == t.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
+        assert frames_u8.stride(3) == 1 and frames_u8.stride(2) == 3
+        y0, y1, x0, x1 = (int(v) for v in area)
+        gy, gx = self.frame_cells_dims(y1 - y0, x1 - x0)
+        assert state.words.numel() >= self.lib.vse_frame_cells_state_bytes(y1 - y0, x1 - x0) and tuple(state.totals.shape) == (gy, gx, 4)
+        n, h, w, _ = frames_u8.shape
+        counts = t.empty((n, gy, gx, 3), dtype=t.int32, device=self.tdev) if want_counts else None
+        p = CellParams(*(int(v) for v in params))
+        _check(self.lib.vse_frame_cells(self.handle, C.c_void_p(frames_u8.data_ptr()) if n else None, n, h, w, frames_u8.stride(1),
+                                        frames_u8.stride(0), y0, y1, x0, x1, p.edge_thresh, p.min_edges, p.ratio_num, p.ratio_den,
+                                        p.min_frames, p.max_frames, C.c_void_p(state.words.data_ptr()), int(bool(reset)),
+                                        int(bool(flush)), C.c_void_p(state.totals.data_ptr()),
+                                        C.c_void_p(counts.data_ptr()) if want_counts and n else None, self.stream()), "vse_frame_cells")
+        return (state.totals, counts) if want_counts else state.totals
 
     # ---- timeline sync: audio template search ---------------------------------------------------------------------
     def audio_match_workspace_bytes(self, queries):

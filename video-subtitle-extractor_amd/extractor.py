@@ -17,6 +17,7 @@ Frame sources: anything with `frame_count`, `fps`, `read(frame_no) -> uint8 BGR 
 cap.set(CAP_PROP_POS_FRAMES, frame_no - 1); cap.read()) and `frames()` (decode order).  `ArraySource` wraps decoded frames;
 ingest.py reads the lossless containers that need no codec (neither box has cv2 / ffmpeg).
 """
+import logging
 import re
 from collections import deque
 from types import SimpleNamespace
@@ -189,17 +190,22 @@ class SubtitleExtractor:
     frame_selector="change" takes VideoSubFinder's role in fast / auto mode with an area: every frame of the area is compared
     with the one before it on the device (frame_select.ChangeFrameSelector, `change_params` its keyword arguments,
     `change_counter` its count_fn), one OCR task goes to the middle frame of each interval, and the SRT takes its times from
-    the intervals (srt.generate_subtitle_file_intervals); the intervals are kept on the object (`intervals`)."""
+    the intervals (srt.generate_subtitle_file_intervals); the intervals are kept on the object (`intervals`).
+    sub_area="auto": nobody drew a box, so run() first looks for the subtitle band itself, one more pass over the clip's frames
+    on the device (area_locator.AreaLocator, `area_params` its keyword arguments), keeps what it found as `located_area` and goes
+    on exactly as if that area had been passed; when it finds none it warns and goes on exactly as with sub_area=None.  With
+    `shard`, every rank scans the same frames and gets the same integers, hence the same area."""
 
     def __init__(self, source, ocr, detect_batch=None, sub_area=None, mode="fast", language="ch", extract_frequency=3,
                  default_subtitle_area=None, drop_score=0.75, deviation_rate=0.0, threshold=80, batch=64,
                  watermark_decide=None, scene_text_decide=lambda band: True, shard=None, gather_device=None,
                  word_segmentation=False, segment=None, uploader=None, detect_stream=None, frame_selector="fps", change_params=None,
-                 change_counter=None, delete_empty=True):
+                 change_counter=None, delete_empty=True, area_params=None):
         if frame_selector not in ("fps", "change"):
             raise ValueError(f"frame_selector must be 'fps' or 'change', not {frame_selector!r}")
         self.source, self.ocr, self.detect_batch = source, ocr, detect_batch
-        self.sub_area, self.mode, self.language = sub_area, mode, language
+        self.auto_area, self.area_params, self.located_area = isinstance(sub_area, str) and sub_area == "auto", area_params, None
+        self.sub_area, self.mode, self.language = None if self.auto_area else sub_area, mode, language
         self.extract_frequency, self.default_subtitle_area = extract_frequency, default_subtitle_area
         self.drop_score, self.deviation_rate, self.threshold, self.batch = drop_score, deviation_rate, threshold, batch
         self.watermark_decide, self.scene_text_decide = watermark_decide, scene_text_decide
@@ -228,6 +234,17 @@ class SubtitleExtractor:
             return self.source.raw_frames()
         return self.source.frames()
 
+    def locate_area(self):
+        """sub_area="auto": find the area (area_locator.AreaLocator over the clip in decode order) and make it this run's sub_area."""
+        from . import area_locator
+        up = self._uploader()
+        loc = area_locator.AreaLocator(**{"batch": self.batch, **(self.area_params or {})})
+        self.sub_area = self.located_area = loc.run(self._decode_order(up), self.source.fps, uploader=up)
+        if self.located_area is None:
+            logging.getLogger(__name__).warning("sub_area='auto': no subtitle area found in %d frames; continuing without one "
+                                                "(fps sampler, scene-text filtering)", loc.frames_scanned)
+        return self.located_area
+
     def select_tasks(self):
         s = self.source
         if self.sub_area is not None and self.mode == "accurate" and self.detect_batch is not None:
@@ -251,6 +268,8 @@ class SubtitleExtractor:
     def run(self):
         """-> SRT text.  raw_lines (normalised, as the reference rewrites raw.txt) and short_lines are kept on the object."""
         self.intervals = None
+        if self.auto_area:
+            self.locate_area()
         tasks = self.select_tasks()
         lines = run_ocr_tasks(self.source, tasks, self.ocr, self.sub_area, self.language, self.drop_score,
                               self.deviation_rate, self.batch, self.shard, self.gather_device, self._uploader())
