@@ -268,6 +268,35 @@ int vse_frame_cells(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w
                     int32_t* d_cell_counts /* nullable: [n,gy,gx,3] edges, appeared, vanished per frame and cell */,
                     void* stream);
 
+/* ---- interval composite ------------------------------------------------------------------------------------------------- */
+/* Replaces: the picture VideoSubFinder hands to OCR for each subtitle it finds (the RGBImages the reference reads back at
+ * backend/main.py:378-505), which that closed binary builds from all frames of the subtitle, not from one of them.  Not its
+ * algorithm but the same idea: a subtitle stands still while the picture behind it moves, so a per-byte reduction over the frames of
+ * one interval of vse_frame_change keeps the text and flattens the background (vse_amd.frame_select.IntervalCompositor).  Whether
+ * that helps recognition on real footage is not measured here.  For every byte b of the area [y0, y1) x [x0, x1) x 3, over all
+ * frames accumulated since the last `reset`:
+ *   mn[b] = min, mx[b] = max, sm[b] = sum as uint32.
+ * Size in bytes of the caller-owned state (16-byte aligned) that holds mn, mx and sm of an area of area_h x area_w pixels: 6 bytes
+ * per byte of the area's rows, each row padded to a multiple of 16 bytes; 0 for an empty area.  Its layout is the library's. */
+size_t vse_interval_state_bytes(int area_h, int area_w);
+/* 1 <= n <= 65535 uint8 BGR frames [n, src_h, src_w, 3] (row pitch `pitch` bytes, frame stride `frame_stride` bytes) folded into
+ * d_state.  With `reset` the call starts from its own first frame and the state needs no particular content beforehand; without it
+ * the call continues the state, so an interval fed in batches of any size gives the state of one call.  Only the area's pixels are
+ * used, so a caller may pass the area's rows alone (where a row of the area does not start or end on a 4-byte boundary, the aligned
+ * 4 bytes around that end are fetched whole).  No alignment of frames, pitch or stride is required; a 16-byte aligned area start
+ * (base + 3 x0), pitch and frame stride take 16-byte loads.  One launch on `stream`, no allocation, no device sync.
+ * Returns VSE_E_INVAL, without touching the device, for an empty or out-of-frame area, n outside 1..65535, pitch < 3 src_w,
+ * frame_stride < (src_h - 1) pitch + 3 src_w when n > 1, or a state that is not 16-byte aligned. */
+int vse_interval_accumulate(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride,
+                            int y0, int y1, int x0, int x1, void* d_state, int reset, void* stream);
+/* d_state -> d_out uint8 [area_h, area_w, 3] with row pitch `out_pitch` bytes (exactly the 3 area_w bytes of each row are written):
+ *   mode 0: mn;  mode 1: mx;  mode 2: the mean, halves rounded up: (2 sm + frames) / (2 frames) in integer division.
+ * `frames` is the caller's count of the frames accumulated since the last reset, 1..4194304 (2^22): within it 2 sm + frames
+ * <= 2 * 255 * 2^22 + 2^22 < 2^32.  One launch on `stream`, no allocation, no device sync.
+ * Returns VSE_E_INVAL, leaving the output untouched, for an empty area, any other mode or count, or out_pitch < 3 area_w. */
+int vse_interval_composite(vse_ctx* ctx, const void* d_state, int area_h, int area_w, int frames, int mode /* 0 min, 1 max, 2 mean */,
+                           void* d_out, int64_t out_pitch, void* stream);
+
 /* ---- timeline sync: audio template search ----------------------------------------------------------------------------- */
 /* Replaces: Sushi's WavStream.find_substream (backend/sushi/wav.py:179-189), cv2.matchTemplate(TM_SQDIFF_NORMED) of one group's
  * source audio against a window of the destination audio.  Both streams are uint8.  A query takes the pattern

@@ -1,0 +1,256 @@
+// Interval composite (vse_interval_accumulate / vse_interval_composite, include/vse_hip.h): a subtitle stands still while the picture
+// behind it moves, so a per-byte reduction over the frames of one subtitle interval keeps the text and flattens the background.  The
+// integers are the specification (tests/interval_ref.py restates them in numpy, bit for bit), for every byte b of the area
+// [y0, y1) x [x0, x1) x 3 over the frames accumulated since the last reset:
+//   mn[b] = min, mx[b] = max, sm[b] = sum (uint32)
+//   composite: mode 0 = mn, 1 = mx, 2 = (2 sm + frames) / (2 frames)      (the mean, halves rounded up)
+// HBM-bound byte work: one pass over the area's bytes of every frame, six state bytes per area byte read and written once per call.
+//
+// Layout: a lane owns a 16-byte run of one area row (run c = bytes 16 c .. 16 c + 15 of the row's 3 area_w bytes), consecutive lanes
+// consecutive runs, for ALL frames of the call: mn / mx / sm of its 16 bytes stay in registers while IV_DEPTH frames' loads are in
+// flight, and the state is read and written once.  Frames are not split across lanes: a byte min / max has no atomic.
+// State: three planes over rows padded to whole runs (rb16 = 16 ceil(3 area_w / 16) bytes): mn, then mx (uint8 [area_h][rb16] each),
+// then sm (uint32 [area_h][rb16]); every state access is an aligned 16-byte one.  The padding bytes hold nothing of meaning.
+// Two loads of a run:
+//   wide     one 16-byte load; needs the run whole (16 area bytes) and 16-byte aligned in every frame: base + 3 x0, pitch and frame
+//            stride multiples of 16.
+//   general  any byte alignment, pitch and stride, and the short run that ends a row: the aligned dwords that hold the run's bytes
+//            (at most five), shifted into place.  No dword without a byte of the area's row is touched, so at most 3 bytes beside a
+//            row's ends are fetched with it and dropped; they share an aligned dword with a byte of the area.
+// The bytes are unpacked into ints before min / max / add and packed again by shifts: no packed-byte arithmetic in the source (see
+// clip8 in yuv.hip for what hipcc made of one on this target).
+#include <cstdio>
+
+#include "common.h"
+
+void vse_set_error(const char* msg);      // vse_runtime.hip
+
+namespace {
+
+constexpr int IV_THREADS = 64;       // one wave per block: a 1080p band is ~1100 waves, and whole waves spread evenly over the CUs
+constexpr int IV_DEPTH = 8;          // frames whose loads are in flight per lane
+constexpr int MAX_FRAMES = 4194304;  // composite: 2 sm + frames <= 2 * 255 * 2^22 + 2^22 < 2^32
+
+struct Acc {
+    unsigned mn[16], mx[16], sm[16];
+};
+
+__device__ __forceinline__ void fold(Acc& a, const unsigned (&w)[4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned b = (w[q] >> (8 * k)) & 255u;
+            a.mn[4 * q + k] = min(a.mn[4 * q + k], b);
+            a.mx[4 * q + k] = max(a.mx[4 * q + k], b);
+            a.sm[4 * q + k] += b;
+        }
+    }
+}
+
+__device__ __forceinline__ unsigned pack4(const unsigned* b) { return b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24); }
+
+// The raw dwords of one run in one frame: WIDE = the 16 bytes themselves; general = the aligned dwords around them.
+template <bool WIDE>
+struct Raw {
+    unsigned d[WIDE ? 4 : 5];
+    unsigned sh;      // general: bytes the run starts behind d[0]
+};
+
+template <bool WIDE>
+__device__ __forceinline__ Raw<WIDE> load_run(const uint8_t* p, int nb) {
+    Raw<WIDE> r;
+    if (WIDE) {
+        const uint4 v = *reinterpret_cast<const uint4*>(p);
+        r.d[0] = v.x, r.d[1] = v.y, r.d[2] = v.z, r.d[3] = v.w;
+        r.sh = 0;
+    } else {
+        r.sh = (unsigned)(reinterpret_cast<uintptr_t>(p) & 3);
+        const unsigned* q = reinterpret_cast<const unsigned*>(p - r.sh);
+        const int last = (int)((r.sh + (unsigned)nb + 3) >> 2) - 1;       // index of the last dword that holds a byte of the run (0..4)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) r.d[k] = q[min(k, last)];             // unconditional loads: all in flight at once
+    }
+    return r;
+}
+
+template <bool WIDE>
+__device__ __forceinline__ void unpack(const Raw<WIDE>& r, unsigned (&w)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (WIDE) {
+            w[k] = r.d[k];
+        } else {
+            const unsigned long long pair = ((unsigned long long)r.d[k + 1] << 32) | r.d[k];
+            w[k] = (unsigned)(pair >> (8 * r.sh));
+        }
+    }
+}
+
+// p = the run in frame 0.  Bytes of a short run beyond nb come out as whatever the clamped loads held: they land in state padding.
+template <bool WIDE>
+__device__ __forceinline__ void accumulate_run(Acc& a, const uint8_t* p, int n, long fstride, int nb) {
+    for (int f0 = 0; f0 < n; f0 += IV_DEPTH) {
+        Raw<WIDE> raw[IV_DEPTH];
+#pragma unroll
+        for (int u = 0; u < IV_DEPTH; ++u) raw[u] = load_run<WIDE>(p + (long)min(f0 + u, n - 1) * fstride, nb);
+#pragma unroll
+        for (int u = 0; u < IV_DEPTH; ++u) {
+            if (f0 + u < n) {          // uniform
+                unsigned w[4];
+                unpack<WIDE>(raw[u], w);
+                fold(a, w);
+            }
+        }
+    }
+}
+
+// src points at byte 3 x0 of row y0 of frame 0; rb = 3 area_w bytes per row in cpr = ceil(rb / 16) runs; items = area_h * cpr.
+template <bool WIDE>
+__global__ __launch_bounds__(IV_THREADS) void interval_accumulate_kernel(const uint8_t* __restrict__ src, int n, long pitch, long fstride,
+                                                                         int rb, unsigned cpr, unsigned items, uint8_t* __restrict__ state,
+                                                                         long plane, int reset) {
+    const unsigned i = blockIdx.x * IV_THREADS + threadIdx.x;
+    if (i >= items) return;
+    const unsigned r = i / cpr, c = i - r * cpr;
+    const int nb = min(16, rb - 16 * (int)c);
+    uint4* smn = reinterpret_cast<uint4*>(state + (long)i * 16);
+    uint4* smx = reinterpret_cast<uint4*>(state + plane + (long)i * 16);
+    uint4* ssm = reinterpret_cast<uint4*>(state + 2 * plane + (long)i * 64);
+    Acc a;
+    if (reset) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) a.mn[k] = 255u, a.mx[k] = 0u, a.sm[k] = 0u;
+    } else {
+        const uint4 vn = *smn, vx = *smx;
+        const unsigned wn[4] = {vn.x, vn.y, vn.z, vn.w}, wx[4] = {vx.x, vx.y, vx.z, vx.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint4 vs = ssm[q];
+            a.sm[4 * q] = vs.x, a.sm[4 * q + 1] = vs.y, a.sm[4 * q + 2] = vs.z, a.sm[4 * q + 3] = vs.w;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                a.mn[4 * q + k] = (wn[q] >> (8 * k)) & 255u;
+                a.mx[4 * q + k] = (wx[q] >> (8 * k)) & 255u;
+            }
+        }
+    }
+    const uint8_t* p = src + (long)r * pitch + 16 * (long)c;
+    if (WIDE && nb == 16)
+        accumulate_run<true>(a, p, n, fstride, nb);
+    else
+        accumulate_run<false>(a, p, n, fstride, nb);
+    *smn = make_uint4(pack4(a.mn), pack4(a.mn + 4), pack4(a.mn + 8), pack4(a.mn + 12));
+    *smx = make_uint4(pack4(a.mx), pack4(a.mx + 4), pack4(a.mx + 8), pack4(a.mx + 12));
+#pragma unroll
+    for (int q = 0; q < 4; ++q) ssm[q] = make_uint4(a.sm[4 * q], a.sm[4 * q + 1], a.sm[4 * q + 2], a.sm[4 * q + 3]);
+}
+
+// One run of the output per lane: exactly the nb bytes of the run are written, as one 16-byte store where the run is whole and
+// 16-byte aligned in the output, byte by byte otherwise.
+__global__ __launch_bounds__(IV_THREADS) void interval_composite_kernel(const uint8_t* __restrict__ state, long plane, int rb, unsigned cpr,
+                                                                        unsigned items, unsigned frames, int mode, uint8_t* __restrict__ out,
+                                                                        long out_pitch) {
+    const unsigned i = blockIdx.x * IV_THREADS + threadIdx.x;
+    if (i >= items) return;
+    const unsigned r = i / cpr, c = i - r * cpr;
+    const int nb = min(16, rb - 16 * (int)c);
+    unsigned w[4];
+    if (mode == 2) {
+        const uint4* ssm = reinterpret_cast<const uint4*>(state + 2 * plane + (long)i * 64);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint4 vs = ssm[q];
+            const unsigned s[4] = {vs.x, vs.y, vs.z, vs.w};
+            unsigned b[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) b[k] = ((2u * s[k] + frames) / (2u * frames)) & 255u;       // (a byte for every true count; padding may hold more)
+            w[q] = pack4(b);
+        }
+    } else {
+        const uint4 v = *reinterpret_cast<const uint4*>(state + (mode == 1 ? plane : 0) + (long)i * 16);
+        w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+    }
+    uint8_t* o = out + (long)r * out_pitch + 16 * (long)c;
+    if (nb == 16 && (reinterpret_cast<uintptr_t>(o) & 15) == 0) {
+        *reinterpret_cast<uint4*>(o) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+        for (int k = 0; k < nb; ++k) o[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+    }
+}
+
+// rows padded to whole runs; 0 where the area is empty or its runs do not fit the 32-bit work-item index
+size_t row_bytes16(int area_w) { return (((size_t)area_w * 3 + 15) / 16) * 16; }
+bool area_fits(int area_h, int area_w) {
+    return area_h >= 1 && area_w >= 1 && (size_t)area_h * (row_bytes16(area_w) / 16) <= 0x7fffffffu;
+}
+bool multiple16(int64_t v) { return (v & 15) == 0; }
+
+}  // namespace
+
+extern "C" {
+
+size_t vse_interval_state_bytes(int area_h, int area_w) {
+    if (!area_fits(area_h, area_w)) return 0;
+    return (size_t)area_h * row_bytes16(area_w) * 6;
+}
+
+int vse_interval_accumulate(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0, int y1,
+                            int x0, int x1, void* d_state, int reset, void* stream) {
+    char msg[320];
+    if (!c || !d_bgr || !d_state || n < 1 || n > 65535 || src_h < 1 || src_w < 1 || pitch < (int64_t)src_w * 3 ||
+        (n > 1 && frame_stride < (int64_t)(src_h - 1) * pitch + (int64_t)src_w * 3) || (reinterpret_cast<uintptr_t>(d_state) & 15)) {
+        snprintf(msg, sizeof msg, "vse_interval_accumulate: bad arguments (n %d of 1..65535, frame %d x %d, pitch %lld of at least 3 w, frame "
+                 "stride %lld, state 16-byte aligned)", n, src_h, src_w, (long long)pitch, (long long)frame_stride);
+        vse_set_error(msg);
+        return VSE_E_INVAL;
+    }
+    if (y0 < 0 || x0 < 0 || y1 > src_h || x1 > src_w || y1 <= y0 || x1 <= x0 || !area_fits(y1 - y0, x1 - x0)) {
+        snprintf(msg, sizeof msg, "vse_interval_accumulate: area [%d, %d) x [%d, %d) is empty or outside the %d x %d frame", y0, y1, x0, x1,
+                 src_h, src_w);
+        vse_set_error(msg);
+        return VSE_E_INVAL;
+    }
+    const int ah = y1 - y0, rb = (x1 - x0) * 3;
+    const unsigned cpr = (unsigned)(row_bytes16(x1 - x0) / 16), items = (unsigned)ah * cpr;
+    const long plane = (long)ah * (long)cpr * 16;
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (int64_t)y0 * pitch + (int64_t)x0 * 3;
+    uint8_t* state = reinterpret_cast<uint8_t*>(d_state);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((items + IV_THREADS - 1) / IV_THREADS), block(IV_THREADS);
+    const bool wide = (reinterpret_cast<uintptr_t>(src) & 15) == 0 && multiple16(pitch) && (n == 1 || multiple16(frame_stride));
+    if (wide)
+        hipLaunchKernelGGL(interval_accumulate_kernel<true>, grid, block, 0, st, src, n, (long)pitch, (long)frame_stride, rb, cpr, items, state,
+                           plane, reset);
+    else
+        hipLaunchKernelGGL(interval_accumulate_kernel<false>, grid, block, 0, st, src, n, (long)pitch, (long)frame_stride, rb, cpr, items, state,
+                           plane, reset);
+    if (hipGetLastError() != hipSuccess) {
+        vse_set_error("vse_interval_accumulate: launch failed");
+        return VSE_E_HIP;
+    }
+    return VSE_OK;
+}
+
+int vse_interval_composite(vse_ctx* c, const void* d_state, int area_h, int area_w, int frames, int mode, void* d_out, int64_t out_pitch,
+                           void* stream) {
+    if (!c || !d_state || !d_out || !area_fits(area_h, area_w) || frames < 1 || frames > MAX_FRAMES || mode < 0 || mode > 2 ||
+        out_pitch < (int64_t)area_w * 3 || (reinterpret_cast<uintptr_t>(d_state) & 15)) {
+        char msg[320];
+        snprintf(msg, sizeof msg, "vse_interval_composite: bad arguments (area %d x %d, frames %d of 1..%d, mode %d of 0 | 1 | 2, output pitch "
+                 "%lld of at least 3 w, state 16-byte aligned)", area_h, area_w, frames, MAX_FRAMES, mode, (long long)out_pitch);
+        vse_set_error(msg);
+        return VSE_E_INVAL;
+    }
+    const unsigned cpr = (unsigned)(row_bytes16(area_w) / 16), items = (unsigned)area_h * cpr;
+    hipLaunchKernelGGL(interval_composite_kernel, dim3((items + IV_THREADS - 1) / IV_THREADS), dim3(IV_THREADS), 0,
+                       reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const uint8_t*>(d_state), (long)area_h * (long)cpr * 16, area_w * 3,
+                       cpr, items, (unsigned)frames, mode, reinterpret_cast<uint8_t*>(d_out), (long)out_pitch);
+    if (hipGetLastError() != hipSuccess) {
+        vse_set_error("vse_interval_composite: launch failed");
+        return VSE_E_HIP;
+    }
+    return VSE_OK;
+}
+
+}  // extern "C"

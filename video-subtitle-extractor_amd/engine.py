@@ -23,6 +23,7 @@ EXPORTS = [
     "vse_rec_graph_create", "vse_graph_launch", "vse_graph_destroy", "vse_frame_change_state_bytes", "vse_frame_change",
     "vse_audio_match_workspace_bytes", "vse_audio_match", "vse_scene_change_state_bytes", "vse_scene_change_workspace_bytes",
     "vse_scene_change", "vse_frame_cells_dims", "vse_frame_cells_state_bytes", "vse_frame_cells",
+    "vse_interval_state_bytes", "vse_interval_accumulate", "vse_interval_composite",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -141,6 +142,11 @@ def load_library(path=None):
     lib.vse_frame_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vse_interval_state_bytes.restype = C.c_size_t
+    lib.vse_interval_state_bytes.argtypes = [C.c_int, C.c_int]
+    lib.vse_interval_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                            C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.vse_interval_composite.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
     lib.vse_audio_match_workspace_bytes.restype = C.c_size_t
     lib.vse_audio_match_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
     lib.vse_audio_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
@@ -431,6 +437,46 @@ class Context:
                                         C.c_void_p(counts.data_ptr()) if want_counts and n else None, self.stream()), "vse_frame_cells")
         return (state.totals, counts) if want_counts else state.totals
 
+    # ---- interval composite ---------------------------------------------------------------------------------------
+    def interval_state(self, area_h, area_w):
+        """A state for interval_accumulate over an area of area_h x area_w pixels (its first call passes reset=True)."""
+        nbytes = self.lib.vse_interval_state_bytes(int(area_h), int(area_w))
+        if not nbytes:
+            raise VseError(f"interval_accumulate: an area of {area_h} x {area_w} pixels is empty")
+        return self.torch.zeros(nbytes, dtype=self.torch.uint8, device=self.tdev)
+
+    def interval_accumulate(self, frames_u8, area, state, reset=False):
+        """frames_u8: cuda uint8 [n,H,W,3] (any row pitch / frame stride, pixels packed), area = (y0, y1, x0, x1) in its pixels,
+        state: interval_state of the area's size -> state, now holding the per-byte min, max and sum of the area over the frames
+        since the last reset (include/vse_hip.h vse_interval_accumulate)."""
+        t = self.torch
+        assert frames_u8.dtype == t.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
+        assert frames_u8.stride(3) == 1 and frames_u8.stride(2) == 3
+        y0, y1, x0, x1 = (int(v) for v in area)
+        assert state.dtype == t.uint8 and state.is_contiguous() and state.numel() >= max(self.lib.vse_interval_state_bytes(y1 - y0, x1 - x0), 1)
+        n, h, w, _ = frames_u8.shape
+        _check(self.lib.vse_interval_accumulate(self.handle, C.c_void_p(frames_u8.data_ptr()), n, h, w, frames_u8.stride(1),
+                                                frames_u8.stride(0), y0, y1, x0, x1, C.c_void_p(state.data_ptr()), int(bool(reset)),
+                                                self.stream()), "vse_interval_accumulate")
+        return state
+
+    def interval_composite(self, state, area_h, area_w, frames, mode, out=None):
+        """state: what interval_accumulate left for an area of area_h x area_w pixels, frames: how many it accumulated since the last
+        reset, mode: "min" | "max" | "mean" -> cuda uint8 [area_h, area_w, 3] (include/vse_hip.h vse_interval_composite).  out: write
+        into this tensor instead (it may be a strided view with packed pixels; its row pitch is taken from it)."""
+        t = self.torch
+        area_h, area_w = int(area_h), int(area_w)
+        if mode not in INTERVAL_MODES:
+            raise VseError(f"interval_composite: mode {mode!r} is not one of {sorted(INTERVAL_MODES)}")
+        assert state.dtype == t.uint8 and state.is_contiguous() and state.numel() >= max(self.lib.vse_interval_state_bytes(area_h, area_w), 1)
+        if out is None:
+            out = t.empty((max(area_h, 0), max(area_w, 0), 3), dtype=t.uint8, device=self.tdev)
+        assert out.dtype == t.uint8 and tuple(out.shape) == (area_h, area_w, 3) and out.stride(2) == 1 and out.stride(1) == 3
+        _check(self.lib.vse_interval_composite(self.handle, C.c_void_p(state.data_ptr()), area_h, area_w, int(frames), INTERVAL_MODES[mode],
+                                               C.c_void_p(out.data_ptr()), out.stride(0) if area_h > 1 else max(out.stride(0), 3 * area_w),
+                                               self.stream()), "vse_interval_composite")
+        return out
+
     # ---- timeline sync: audio template search ---------------------------------------------------------------------
     def audio_match_workspace_bytes(self, queries):
         """Workspace bytes of one audio_match call with these (src_off, m, dst_off, win_len) queries (0 if one is invalid)."""
@@ -509,6 +555,7 @@ class Context:
 
 
 YUV_LAYOUTS = {"i420": 0, "nv12": 1}
+INTERVAL_MODES = {"min": 0, "max": 1, "mean": 2}
 
 
 def _audio_queries(queries):

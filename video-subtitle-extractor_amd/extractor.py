@@ -52,6 +52,29 @@ class ArraySource:
     pos_msec = None        # no container timestamps: SRT time codes fall back to frame_no / fps (main.py:745-748)
 
 
+class CompositedSource:
+    """A frame source whose rep frames show the interval composite inside the subtitle area: read(no) is a copy of source.read(no)
+    with the area replaced by patches[no] (frame_select.IntervalCompositor) where there is one, and the plain frame otherwise.
+    area: the SubtitleArea the patches were made for; a patch goes where the area, clipped to the frame, starts.  Forwards fps,
+    frame_count and, where present, pos_msec.  No read_raw on purpose: a 4:2:0 source is then converted on the host, by the same integers."""
+
+    def __init__(self, source, area, patches):
+        self._source, self._patches = source, patches
+        self._y0, self._x0 = max(0, int(area.ymin)), max(0, int(area.xmin))
+        self.fps, self.frame_count = source.fps, source.frame_count
+        if hasattr(source, "pos_msec"):
+            self.pos_msec = source.pos_msec
+
+    def read(self, frame_no):
+        frame = self._source.read(frame_no)
+        patch = self._patches.get(frame_no)
+        if frame is None or patch is None:
+            return frame
+        out = np.array(frame, copy=True)
+        out[self._y0:self._y0 + patch.shape[0], self._x0:self._x0 + patch.shape[1]] = patch
+        return out
+
+
 def frame_preprocess(subtitle_area, frame):
     """Half-frame crop of subtitle_ocr.py:270-289 (a view, like the reference's slice)."""
     if subtitle_area == LOWER_PART:
@@ -191,6 +214,11 @@ class SubtitleExtractor:
     with the one before it on the device (frame_select.ChangeFrameSelector, `change_params` its keyword arguments,
     `change_counter` its count_fn), one OCR task goes to the middle frame of each interval, and the SRT takes its times from
     the intervals (srt.generate_subtitle_file_intervals); the intervals are kept on the object (`intervals`).
+    interval_image="min" | "max" | "mean" (change selector only; default "middle", the above): one recognition error on that single
+    frame is final, so the recogniser is instead shown, inside the area of the same middle frame, the per-pixel minimum (light
+    text) / maximum (dark text) / mean of ALL frames of the interval, one more pass over the area's rows on the device
+    (frame_select.IntervalCompositor, `composite_params` its keyword arguments); the pictures are kept as `interval_patches`.
+    Intervals and SRT times are untouched.  What it gains on real footage is not measured here.
     sub_area="auto": nobody drew a box, so run() first looks for the subtitle band itself, one more pass over the clip's frames
     on the device (area_locator.AreaLocator, `area_params` its keyword arguments), keeps what it found as `located_area` and goes
     on exactly as if that area had been passed; when it finds none it warns and goes on exactly as with sub_area=None.  With
@@ -200,9 +228,13 @@ class SubtitleExtractor:
                  default_subtitle_area=None, drop_score=0.75, deviation_rate=0.0, threshold=80, batch=64,
                  watermark_decide=None, scene_text_decide=lambda band: True, shard=None, gather_device=None,
                  word_segmentation=False, segment=None, uploader=None, detect_stream=None, frame_selector="fps", change_params=None,
-                 change_counter=None, delete_empty=True, area_params=None):
+                 change_counter=None, delete_empty=True, area_params=None, interval_image="middle", composite_params=None):
         if frame_selector not in ("fps", "change"):
             raise ValueError(f"frame_selector must be 'fps' or 'change', not {frame_selector!r}")
+        if interval_image not in ("middle",) + frame_select.COMPOSITE_MODES:
+            raise ValueError(f"interval_image must be 'middle' or one of {frame_select.COMPOSITE_MODES}, not {interval_image!r}")
+        if interval_image != "middle" and frame_selector != "change":
+            raise ValueError(f"interval_image={interval_image!r} composites the intervals of frame_selector='change', not {frame_selector!r}")
         self.source, self.ocr, self.detect_batch = source, ocr, detect_batch
         self.auto_area, self.area_params, self.located_area = isinstance(sub_area, str) and sub_area == "auto", area_params, None
         self.sub_area, self.mode, self.language = None if self.auto_area else sub_area, mode, language
@@ -219,6 +251,7 @@ class SubtitleExtractor:
         self.word_segmentation, self.segment = word_segmentation, segment      # config.wordSegmentation (main.py:181-182)
         self.frame_selector, self.change_params, self.change_counter = frame_selector, change_params, change_counter
         self.delete_empty = delete_empty          # config.deleteEmptyTimeStamp (intervals of the change selector only)
+        self.interval_image, self.composite_params, self.interval_patches = interval_image, composite_params, None
         self.raw_lines = None
         self.short_lines = None
         self.intervals = None
@@ -262,6 +295,15 @@ class SubtitleExtractor:
             return [(s.frame_count, rep, None, None, None, self.default_subtitle_area) for _start, _end, rep in self.intervals]
         return fps_tasks(s.frame_count, s.fps, self.extract_frequency, self.default_subtitle_area)
 
+    def composite_intervals(self, n_tasks):
+        """interval_image other than "middle": the picture of each interval this rank will recognise (with `shard`, the slice
+        run_ocr_tasks gives it) -> the source run_ocr_tasks reads, which shows them in the rep frames."""
+        up = self._uploader()
+        comp = frame_select.IntervalCompositor(**{"mode": self.interval_image, "batch": self.batch, **(self.composite_params or {})})
+        only = None if self.shard is None else range(*parallel.shard_range(n_tasks, *self.shard))
+        self.interval_patches = comp.run(self._decode_order(up), self.sub_area, self.intervals, self.source.fps, uploader=up, only=only)
+        return CompositedSource(self.source, self.sub_area, self.interval_patches)
+
     def _predict_list(self, frames):
         return self.ocr.predict_batch(frames if not isinstance(frames, list) else _stack(frames))
 
@@ -270,8 +312,12 @@ class SubtitleExtractor:
         self.intervals = None
         if self.auto_area:
             self.locate_area()
+        self.interval_patches = None
         tasks = self.select_tasks()
-        lines = run_ocr_tasks(self.source, tasks, self.ocr, self.sub_area, self.language, self.drop_score,
+        source = self.source
+        if self.interval_image != "middle" and self.intervals is not None:
+            source = self.composite_intervals(len(tasks))
+        lines = run_ocr_tasks(source, tasks, self.ocr, self.sub_area, self.language, self.drop_score,
                               self.deviation_rate, self.batch, self.shard, self.gather_device, self._uploader())
         if self.sub_area is None:
             if self.watermark_decide is not None:               # the reference asks on stdin (main.py:164-170)

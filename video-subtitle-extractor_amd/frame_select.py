@@ -222,6 +222,11 @@ def change_intervals(counts, min_edges, change_ratio=0.5, min_frames=2):
     return out
 
 
+def clip_area(sub_area, h, w):
+    """sub_area (.ymin .ymax .xmin .xmax in frame pixels) clipped to an h x w frame -> (y0, y1, x0, x1); empty when y1 <= y0 or x1 <= x0."""
+    return max(0, int(sub_area.ymin)), min(h, int(sub_area.ymax)), max(0, int(sub_area.xmin)), min(w, int(sub_area.xmax))
+
+
 class EngineCounter:
     """count_fn of ChangeFrameSelector on the GPU (Context.frame_change): keeps the device state of the last area between calls."""
 
@@ -275,8 +280,7 @@ class ChangeFrameSelector:
             self.counts, self.intervals = np.zeros((0, 3), np.int32), []
             return self.intervals
         h, w = first.shape[:2]
-        y0, y1 = max(0, int(sub_area.ymin)), min(h, int(sub_area.ymax))
-        x0, x1 = max(0, int(sub_area.xmin)), min(w, int(sub_area.xmax))
+        y0, y1, x0, x1 = clip_area(sub_area, h, w)
         if y1 - y0 < 3 or x1 - x0 < 3:
             raise ValueError(f"ChangeFrameSelector: subtitle area {sub_area} leaves less than 3 x 3 pixels of a {h} x {w} frame")
         area = (0, y1 - y0, x0, x1)
@@ -307,3 +311,126 @@ class ChangeFrameSelector:
     @staticmethod
     def _host(c):
         return c.cpu() if hasattr(c, "cpu") else c
+
+
+# ---- interval composite (one picture per interval of the change selector) ------------------------------------------------
+COMPOSITE_MODES = ("min", "max", "mean")
+
+
+def trim_range(start, end, fps, trim_seconds):
+    """The frames of the interval start..end (1-based, inclusive) that are composited: start + tr .. end - tr with
+    tr = min(round(trim_seconds * fps), (end - start) // 2), so at least one frame always remains."""
+    tr = min(int(round(trim_seconds * fps)), (end - start) // 2)
+    return start + tr, end - tr
+
+
+class EngineCompositor:
+    """accumulate_fn of IntervalCompositor on the GPU (Context.interval_accumulate / interval_composite): keeps the device state
+    of the last area and the frame count of the open interval between calls."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self._state = None
+        self._shape = None
+        self._count = 0
+
+    def __call__(self, frames, area, reset, mode=None):
+        t = self.ctx.torch
+        if not t.is_tensor(frames):
+            frames = t.from_numpy(frames).to(self.ctx.tdev)
+        y0, y1, x0, x1 = area
+        if self._shape != (y1 - y0, x1 - x0):
+            self._shape = (y1 - y0, x1 - x0)
+            self._state = self.ctx.interval_state(*self._shape)
+            reset = True
+        self.ctx.interval_accumulate(frames, area, self._state, reset)
+        self._count = len(frames) if reset else self._count + len(frames)
+        return None if mode is None else self.ctx.interval_composite(self._state, y1 - y0, x1 - x0, self._count, mode)
+
+
+class IntervalCompositor:
+    """One picture of the subtitle area per interval of ChangeFrameSelector, made of ALL its frames instead of the middle one: a
+    subtitle stands still while the picture behind it moves, so the per-pixel minimum (light text; `max` for dark text, `mean` to
+    average noise) over the interval keeps the text and flattens the background.  VideoSubFinder builds the pictures it hands to
+    OCR on the same idea; this is not its algorithm.  How much it helps recognition on real footage is not measured here (no
+    real clips, stand-in recogniser weights); the integers, the plumbing and the cost are pinned.
+
+    accumulate_fn(frames [n,h,w,3] uint8, area (y0, y1, x0, x1) in their pixels, reset, mode=None): folds the frames into the open
+    interval's per-byte min / max / sum (reset: the interval starts with these frames) and, with a mode, returns its composite
+    uint8 [y1-y0, x1-x0, 3].  Default: EngineCompositor on the shim's device.
+    Fades at either end of a subtitle would drag a `min` of light text down, so trim_seconds of frames are left out at both ends
+    (trim_range).  Host memory: one area patch per interval, kept in RAM; a 1080p default band (226 x 1728 pixels) is about 1 MB."""
+
+    def __init__(self, accumulate_fn=None, mode="min", trim_seconds=0.25, batch=64):
+        if mode not in COMPOSITE_MODES:
+            raise ValueError(f"IntervalCompositor: mode must be one of {COMPOSITE_MODES}, not {mode!r}")
+        self.accumulate_fn, self.mode, self.trim_seconds, self.batch = accumulate_fn, mode, trim_seconds, batch
+        self.area = None              # (y0, y1, x0, x1): the area clipped to the frame, where the patches belong
+        self.patches = None
+
+    def run(self, frames, sub_area, intervals, fps, uploader=None, only=None):
+        """frames: iterable of uint8 BGR frames in decode order (read once, and not beyond the last frame that is needed);
+        sub_area: clipped to the frame exactly as ChangeFrameSelector.run clips it; intervals: its [(start, end, rep)], ascending;
+        only: a range of interval indices (a rank's shard), the others are not composited -> {rep: uint8 ndarray [ah, aw, 3]}.
+        Only the area's rows of the frames inside a used range are staged; with an uploader (staging.Uploader) they go through
+        pinned memory on its producer thread."""
+        import numpy as np
+        if self.accumulate_fn is None:
+            from . import shim
+            self.accumulate_fn = EngineCompositor(shim._context())
+        todo = []                     # (first, last, rep) of the intervals to composite, ascending and disjoint
+        for k, (start, end, rep) in enumerate(intervals):
+            if only is None or k in only:
+                first, last = trim_range(start, end, fps, self.trim_seconds)
+                if todo and first <= todo[-1][1]:
+                    raise ValueError(f"IntervalCompositor: intervals must ascend without overlap, got {intervals[k - 1]} then {intervals[k]}")
+                todo.append((first, last, rep))
+        self.patches = {}
+        if not todo:
+            return self.patches
+        it = iter(frames)
+        geometry = []                 # [y0, y1, x0, x1] once the first frame has been seen
+
+        def rows(f):
+            if not geometry:
+                h, w = f.shape[:2]
+                y0, y1, x0, x1 = clip_area(sub_area, h, w)
+                if y1 <= y0 or x1 <= x0:
+                    raise ValueError(f"IntervalCompositor: subtitle area {sub_area} leaves nothing of a {h} x {w} frame")
+                geometry.extend((y0, y1, x0, x1))
+            return f[geometry[0]:geometry[1]]
+
+        def batches():
+            """lists of ((rep, opens the interval, closes it), area rows): consecutive frames of ONE interval, at most `batch`"""
+            no = 0
+            for first, last, rep in todo:
+                buf = []
+                while no < last:
+                    f = next(it, None)
+                    if f is None:
+                        raise ValueError(f"IntervalCompositor: the clip ends at frame {no}, inside or before the interval ending at {last}")
+                    no += 1
+                    if no < first:
+                        continue
+                    if len(buf) == self.batch:
+                        yield buf
+                        buf = []
+                    buf.append(((rep, no == first, no == last), rows(f)))
+                yield buf
+
+        def fold(items, data):
+            (rep, opens, _), (_, _, closes) = items[0][0], items[-1][0]
+            y0, y1, x0, x1 = geometry
+            out = self.accumulate_fn(data, (0, y1 - y0, x0, x1), opens, self.mode if closes else None)
+            if closes:
+                self.patches[rep] = out.cpu().numpy() if hasattr(out, "cpu") else np.array(out)
+
+        if uploader is not None:
+            from . import staging
+            for items, staged in staging.prefetch(batches(), uploader):
+                fold(items, staged.tensor())
+        else:
+            for items in batches():
+                fold(items, np.stack([f for _, f in items]))
+        self.area = tuple(geometry)
+        return self.patches
