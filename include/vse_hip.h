@@ -268,6 +268,35 @@ int vse_frame_cells(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w
                     int32_t* d_cell_counts /* nullable: [n,gy,gx,3] edges, appeared, vanished per frame and cell */,
                     void* stream);
 
+/* ---- held-edge frame selector ------------------------------------------------------------------------------------------- */
+/* Replaces: the same frame search of VideoSubFinder as vse_frame_change (backend/main.py:378-505, extract_frame_by_vsf), for
+ * footage whose background moves behind the subtitle.  vse_frame_change compares every edge pixel of the area with the frame
+ * before, so a textured background that pans makes every frame a cut and no subtitle is found.  A subtitle's edges hold still for
+ * many frames and a moving background's do not, so here only HELD edges are counted; the host runs the unchanged interval automaton
+ * on the counts (vse_amd.frame_select.HoldFrameSelector).  Not VideoSubFinder's algorithm; `hold` and the behaviour on real footage
+ * are not measured here (no real clips).  Known limit: background edges that stay on one pixel for `hold` frames still count (a
+ * static busy shot, a pan along an edge's own direction); they can add intervals between subtitles, which cost OCR calls and lose
+ * no subtitle.
+ * Frames of a clip are numbered 1..T; E_t = the edge pixels of the area's interior in frame t exactly as defined for
+ * vse_frame_change.  H_u, the held mask of frame u: pixel p is in H_u when p is in E_u and the maximal run of consecutive frames
+ * containing u in which p is an edge pixel is at least `hold` frames long; runs are cut off at frame 1 and, once `flush` is given,
+ * at the clip's last frame.  H_0 is empty.  The row of frame u is |H_u|, |H_u \ H_{u-1}|, |H_{u-1} \ H_u|.  hold == 1 gives
+ * vse_frame_change's counts.
+ * Size in bytes of the caller-owned state (8-byte aligned) that carries the open runs and the last counted mask from one call to the
+ * next; 0 below 3 x 3 or for hold outside 1..32.  A fresh state is zero-filled; its layout is the library's. */
+size_t vse_frame_hold_state_bytes(int area_h, int area_w, int hold);
+/* n >= 0 uint8 BGR frames [n, src_h, src_w, 3] (pitch and frame stride as for vse_frame_change; only the area's pixels are read, so a
+ * caller may pass the area's rows alone), the next frames of a clip of which `fed` frames went to earlier calls; fed == 0 starts a
+ * clip and the state's content is then ignored.  H_u needs the frames up to u + hold - 1, so the call writes, from row 0 of d_counts
+ * on, the rows of the frames max(0, fed - hold + 1) + 1 .. max(0, fed + n - hold + 1), and with `flush` (the clip ends with this
+ * call) up to fed + n; d_counts has room for n + hold - 1 rows.  n == 0 with `flush` only drains the pending rows.  A clip fed in
+ * batches of any sizes gives the rows of one call.  One launch sequence on `stream`, no allocation, no device sync; a block owns its
+ * 8 x 64 interior pixels for all frames of the call and alone reads and writes their state.  Returns VSE_E_INVAL, without touching
+ * the device, for a degenerate or out-of-frame area, hold outside 1..32, n < 0, fed < 0 or a NULL state. */
+int vse_frame_hold(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride,
+                   int y0, int y1, int x0, int x1, int edge_thresh, int hold, void* d_state, int64_t fed, int flush,
+                   int32_t* d_counts /* [n + hold - 1, 3]: held edges, appeared, vanished */, void* stream);
+
 /* ---- interval composite ------------------------------------------------------------------------------------------------- */
 /* Replaces: the picture VideoSubFinder hands to OCR for each subtitle it finds (the RGBImages the reference reads back at
  * backend/main.py:378-505), which that closed binary builds from all frames of the subtitle, not from one of them.  Not its

@@ -14,6 +14,9 @@
 //
 // Subtitle-area locator (vse_frame_cells): the same tiles and the same mask, but a tile is a CELL that keeps its own counts and runs
 // the interval automaton of frame_select.change_intervals on them (frame_cells_kernel below).
+//
+// Held-edge selector (vse_frame_hold): the same tiles and the same mask again, but only edge pixels that hold still for `hold` frames
+// are counted, so that the edges of a moving background drop out (frame_hold_kernel below).
 #include "common.h"
 
 namespace {
@@ -245,6 +248,98 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_kernel(const uint8_
     }
 }
 
+// ---- vse_frame_hold -------------------------------------------------------------------------------------------------------------
+// H_u = the edge pixels of frame u whose run of consecutive edge frames is at least `hold` frames long.  Per pixel, along the frames t:
+//   run[t]   = E[t] ? min(run[t-1] + 1, hold) : 0          S[t] = (run[t] == hold): a run of `hold` frames ends at t
+//   cover[t] = S[t] ? hold : max(cover[t-1] - 1, 0)         cover[t] > 0: some S in t-hold+1 .. t
+//   H[t-hold+1] = cover[t] > 0
+// (u lies in a run of >= hold frames exactly when a run of hold frames ends somewhere in u .. u+hold-1.)  So the mask of a frame comes out
+// hold - 1 steps late; a flush feeds hold - 1 frames without an edge, which cuts the runs off at the clip's end.  Steps before frame
+// `hold` cannot set S, so the rows of the frames "before frame 1" are empty masks: they are computed like the others and not written.
+//
+// The tile's mask words meet in LDS exactly as above.  Then wave k walks interior row k of the tile along the frames with lane = column:
+// two small counters per pixel in registers, the held pixels of a step gathered by a ballot into the word that replaces the mask word
+// in LDS (the words of a chunk enter and leave the walk with lane = frame, one LDS access each way), and the per-frame counting is
+// frame_change_kernel's on those words.  A pixel per lane keeps the walk at about ten instructions per frame on all eight waves;
+// counters bit-sliced into 64-bit planes would need one lane per word and a dependent chain several times as long on a single wave,
+// at the end of the block where nothing hides it.
+// State: one uint16 per pixel of the tile words (64 per word, [interior row][word][lane]): run | cover << 6 | held << 12, `held` being
+// the pixel's bit in the last mask that was counted.  Zero is the state before frame 1.
+constexpr int HOLD_WORD_BYTES = 64 * 2;
+
+__global__ __launch_bounds__(FC_WAVES * 64) void frame_hold_kernel(const uint8_t* __restrict__ src, int n, int steps, long pitch, long fstride,
+                                                                   int x0, int ih, int iw, int wpr, int thresh, int hold, int skip,
+                                                                   unsigned short* __restrict__ state, int fresh, int* __restrict__ counts) {
+    __shared__ unsigned long long msk[FC_CHUNK][FC_ROWS];
+    __shared__ unsigned long long prv[FC_ROWS];
+    static_assert(FC_WAVES == FC_ROWS, "wave k walks interior row k of the tile");
+    static_assert(FC_CHUNK == 64, "the frames of a chunk are the lanes of a wave");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int w = blockIdx.x, iy0 = blockIdx.y * FC_ROWS;
+    const TileLane t = tile_lane(w, iy0, ih, iw, x0);
+    const bool mine = wave < t.rows;           // wave-uniform; the words of the other rows stay zero
+    unsigned short* st = state + ((long)(iy0 + wave) * wpr + w) * 64 + lane;
+    int run = 0, cover = 0;
+    bool held = false;
+    if (mine && !fresh) {
+        const unsigned s = *st;
+        run = s & 63;
+        cover = (s >> 6) & 63;
+        held = (s >> 12) & 1;
+    }
+    {
+        const unsigned long long b = __ballot(held);
+        if (lane == 0) prv[wave] = b;
+    }
+
+    for (int c0 = 0; c0 < steps; c0 += FC_CHUNK) {
+        const int cn = min(FC_CHUNK, steps - c0);
+        const int real = max(0, min(cn, n - c0));          // the steps after frame n are the flush: no edge anywhere
+        tile_masks(src + (long)iy0 * pitch, c0, real, pitch, fstride, t, thresh, msk);
+        for (int i = real * FC_ROWS + threadIdx.x; i < cn * FC_ROWS; i += FC_WAVES * 64) msk[i / FC_ROWS][i % FC_ROWS] = 0ull;
+        __syncthreads();
+        if (mine) {
+            // lane = frame of the chunk for the words going in and out, lane = column for the walk: the walk itself stays out of LDS
+            const unsigned long long col = lane < cn ? msk[lane][wave] : 0ull;
+            const int lo = (int)(unsigned)col, hi = (int)(unsigned)(col >> 32);
+            unsigned long long out = 0ull;
+            for (int tl = 0; tl < cn; ++tl) {
+                const unsigned half = (unsigned)(lane < 32 ? __builtin_amdgcn_readlane(lo, tl) : __builtin_amdgcn_readlane(hi, tl));
+                const bool edge = (half >> (lane & 31)) & 1u;
+                run = edge ? min(run + 1, hold) : 0;
+                cover = run == hold ? hold : max(cover - 1, 0);
+                held = cover > 0;
+                const unsigned long long b = __ballot(held);
+                if (lane == tl) out = b;                   // mask of frame (this step) - hold + 1
+            }
+            if (lane < cn) msk[lane][wave] = out;
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < cn) {
+            const int tl = threadIdx.x, row = c0 + tl - skip;
+            if (row >= 0) {
+                int e = 0, a = 0, v = 0;
+#pragma unroll
+                for (int k = 0; k < FC_ROWS; ++k) {
+                    const unsigned long long cur = msk[tl][k], pre = tl ? msk[tl - 1][k] : prv[k];
+                    e += __popcll(cur);
+                    a += __popcll(cur & ~pre);
+                    v += __popcll(pre & ~cur);
+                }
+                // integer sums: the totals do not depend on the order the blocks arrive in
+                int* o = counts + (long)row * 3;
+                if (e) atomicAdd(o, e);
+                if (a) atomicAdd(o + 1, a);
+                if (v) atomicAdd(o + 2, v);
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < FC_ROWS) prv[threadIdx.x] = msk[cn - 1][threadIdx.x];
+        __syncthreads();
+    }
+    if (mine) *st = (unsigned short)(run | (cover << 6) | ((int)held << 12));
+}
+
 }  // namespace
 
 // Called by vse_frame_change (vse_runtime.hip) after it has checked the geometry.
@@ -274,5 +369,21 @@ int vse_frame_cells_launch(const void* d_bgr, int n, int64_t pitch, int64_t fram
                        reinterpret_cast<hipStream_t>(stream), src, n, (long)pitch, (long)frame_stride, x0, ih, iw, edge_thresh, rule,
                        reinterpret_cast<unsigned long long*>(d_state), reset, flush, reinterpret_cast<int*>(d_totals),
                        reinterpret_cast<int*>(d_cell_counts));
+    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+}
+
+size_t vse_frame_hold_word_bytes() { return HOLD_WORD_BYTES; }
+
+// Called by vse_frame_hold (vse_runtime.hip) after it has checked the arguments; steps = n (+ hold - 1 with a flush) > 0 and
+// skip = the steps whose frame lies before frame 1.
+int vse_frame_hold_launch(const void* d_bgr, int n, int steps, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                          int edge_thresh, int hold, int skip, void* d_state, int fresh, int32_t* d_counts, void* stream) {
+    const int ih = y1 - y0 - 2, iw = x1 - x0 - 2, wpr = (iw + 63) / 64;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (steps > skip && hipMemsetAsync(d_counts, 0, (size_t)(steps - skip) * 3 * sizeof(int32_t), st) != hipSuccess) return VSE_E_HIP;
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
+    hipLaunchKernelGGL(frame_hold_kernel, dim3(wpr, (ih + FC_ROWS - 1) / FC_ROWS), dim3(FC_WAVES * 64), 0, st, src, n, steps, (long)pitch,
+                       (long)frame_stride, x0, ih, iw, wpr, edge_thresh, hold, skip, reinterpret_cast<unsigned short*>(d_state), fresh,
+                       reinterpret_cast<int*>(d_counts));
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }

@@ -54,6 +54,9 @@ int vse_frame_cells_state_words();                                              
 int vse_frame_cells_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
                            int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames, void* d_state, int reset, int flush,
                            int32_t* d_totals, int32_t* d_cell_counts, void* stream);                                    // frame_change.hip
+size_t vse_frame_hold_word_bytes();                                                                                    // frame_change.hip
+int vse_frame_hold_launch(const void* d_bgr, int n, int steps, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                          int edge_thresh, int hold, int skip, void* d_state, int fresh, int32_t* d_counts, void* stream);   // frame_change.hip
 int vse_scene_change_plane_pitch(int aw);                                                                              // scene_cut.hip
 int vse_scene_change_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int scale, int ah, int aw, int search, int bias,
                             void* d_state, int reset, void* d_ws, int32_t* d_counts, void* stream);
@@ -454,6 +457,43 @@ int vse_frame_cells(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, 
     const int rc = vse_frame_cells_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, min_edges, ratio_num, ratio_den,
                                           min_frames, max_frames, d_state, reset, flush, d_totals, d_cell_counts, stream);
     if (rc != VSE_OK) set_err("vse_frame_cells: launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+// ---- held-edge frame selector (frame_change.hip) ------------------------------------------------------------------------------
+size_t vse_frame_hold_state_bytes(int area_h, int area_w, int hold) {
+    if (area_h < 3 || area_w < 3 || hold < 1 || hold > 32) return 0;
+    return (size_t)(area_h - 2) * (size_t)((area_w - 2 + 63) / 64) * vse_frame_hold_word_bytes();
+}
+
+int vse_frame_hold(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0,
+                   int x1, int edge_thresh, int hold, void* d_state, int64_t fed, int flush, int32_t* d_counts, void* stream) {
+    if (!c || (!d_bgr && n > 0) || !d_state || n < 0 || fed < 0 || src_h <= 0 || src_w <= 0 || pitch < (int64_t)src_w * 3 ||
+        (n > 1 && frame_stride < (int64_t)(src_h - 1) * pitch + (int64_t)src_w * 3) || (reinterpret_cast<uintptr_t>(d_state) & 7)) {
+        set_err("vse_frame_hold: bad arguments (n %d, fed %lld, frame %d x %d, pitch %lld, frame stride %lld, state 8-byte aligned)", n,
+                (long long)fed, src_h, src_w, (long long)pitch, (long long)frame_stride);
+        return VSE_E_INVAL;
+    }
+    if (y0 < 0 || x0 < 0 || y1 > src_h || x1 > src_w || y1 - y0 < 3 || x1 - x0 < 3) {
+        set_err("vse_frame_hold: area [%d, %d) x [%d, %d) is degenerate or outside the %d x %d frame", y0, y1, x0, x1, src_h, src_w);
+        return VSE_E_INVAL;
+    }
+    if (hold < 1 || hold > 32) {
+        set_err("vse_frame_hold: hold %d outside 1..32", hold);
+        return VSE_E_INVAL;
+    }
+    // the mask of a frame is known hold - 1 frames later: a flush feeds that many frames without an edge, and the first
+    // hold - 1 steps of a clip belong to no frame
+    const int64_t steps = (int64_t)n + (flush ? hold - 1 : 0);
+    const int skip = fed >= hold - 1 ? 0 : (int)(hold - 1 - fed);
+    if (steps == 0) return VSE_OK;
+    if (steps > INT32_MAX || (steps > skip && !d_counts)) {
+        set_err("vse_frame_hold: %lld steps need d_counts and must fit an int", (long long)steps);
+        return VSE_E_INVAL;
+    }
+    const int rc = vse_frame_hold_launch(d_bgr, n, (int)steps, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, hold, skip, d_state,
+                                         fed == 0, d_counts, stream);
+    if (rc != VSE_OK) set_err("vse_frame_hold: launch failed: %s", hipGetErrorString(hipGetLastError()));
     return rc;
 }
 

@@ -23,7 +23,7 @@ EXPORTS = [
     "vse_rec_graph_create", "vse_graph_launch", "vse_graph_destroy", "vse_frame_change_state_bytes", "vse_frame_change",
     "vse_audio_match_workspace_bytes", "vse_audio_match", "vse_scene_change_state_bytes", "vse_scene_change_workspace_bytes",
     "vse_scene_change", "vse_frame_cells_dims", "vse_frame_cells_state_bytes", "vse_frame_cells",
-    "vse_interval_state_bytes", "vse_interval_accumulate", "vse_interval_composite",
+    "vse_interval_state_bytes", "vse_interval_accumulate", "vse_interval_composite", "vse_frame_hold_state_bytes", "vse_frame_hold",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -142,6 +142,10 @@ def load_library(path=None):
     lib.vse_frame_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vse_frame_hold_state_bytes.restype = C.c_size_t
+    lib.vse_frame_hold_state_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.vse_frame_hold.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                   C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
     lib.vse_interval_state_bytes.restype = C.c_size_t
     lib.vse_interval_state_bytes.argtypes = [C.c_int, C.c_int]
     lib.vse_interval_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
@@ -436,6 +440,35 @@ class Context:
                                         int(bool(flush)), C.c_void_p(state.totals.data_ptr()),
                                         C.c_void_p(counts.data_ptr()) if want_counts and n else None, self.stream()), "vse_frame_cells")
         return (state.totals, counts) if want_counts else state.totals
+
+    # ---- held-edge frame selector ---------------------------------------------------------------------------------
+    def frame_hold_state(self, area_h, area_w, hold):
+        """A fresh (zero-filled) state for frame_hold over an area of area_h x area_w pixels with this `hold`."""
+        nbytes = self.lib.vse_frame_hold_state_bytes(int(area_h), int(area_w), int(hold))
+        if not nbytes:
+            raise VseError(f"frame_hold: an area of {area_h} x {area_w} pixels has no interior, or hold {hold} is outside 1..32")
+        return self.torch.zeros(nbytes, dtype=self.torch.uint8, device=self.tdev)
+
+    def frame_hold(self, frames_u8, area, edge_thresh, hold, state, fed, flush=False):
+        """frames_u8: cuda uint8 [n,H,W,3] (any row pitch / frame stride, pixels packed; n may be 0, for a flush alone), the next
+        frames of a clip of which `fed` went to earlier calls (0 starts a clip), area = (y0, y1, x0, x1) in its pixels, state:
+        frame_hold_state of the area's size and `hold` -> cuda int32 [rows,3]: held edges, appeared, vanished of the frames whose
+        held mask this call completes, which trail the frames fed by hold - 1 until `flush` (include/vse_hip.h vse_frame_hold)."""
+        t = self.torch
+        assert frames_u8.dtype == t.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
+        n, h, w, _ = frames_u8.shape
+        pitch, fstride = (frames_u8.stride(1), frames_u8.stride(0)) if n else (3 * w, 3 * w * h)      # (no frames: no strides to speak of)
+        assert not n or (frames_u8.stride(3) == 1 and frames_u8.stride(2) == 3)
+        y0, y1, x0, x1 = (int(v) for v in area)
+        hold, fed = int(hold), int(fed)
+        nbytes = self.lib.vse_frame_hold_state_bytes(y1 - y0, x1 - x0, hold)
+        assert nbytes and state.dtype == t.uint8 and state.is_contiguous() and state.numel() >= nbytes
+        rows = (fed + n if flush else max(0, fed + n - hold + 1)) - max(0, fed - hold + 1)
+        out = t.empty((n + hold - 1, 3), dtype=t.int32, device=self.tdev)
+        _check(self.lib.vse_frame_hold(self.handle, C.c_void_p(frames_u8.data_ptr()) if n else None, n, h, w, pitch,
+                                       fstride, y0, y1, x0, x1, int(edge_thresh), hold, C.c_void_p(state.data_ptr()),
+                                       fed, int(bool(flush)), C.c_void_p(out.data_ptr()), self.stream()), "vse_frame_hold")
+        return out[:rows]
 
     # ---- interval composite ---------------------------------------------------------------------------------------
     def interval_state(self, area_h, area_w):

@@ -214,6 +214,10 @@ class SubtitleExtractor:
     with the one before it on the device (frame_select.ChangeFrameSelector, `change_params` its keyword arguments,
     `change_counter` its count_fn), one OCR task goes to the middle frame of each interval, and the SRT takes its times from
     the intervals (srt.generate_subtitle_file_intervals); the intervals are kept on the object (`intervals`).
+    frame_selector="hold" is the change selector for footage whose background moves behind the subtitle: only edges that hold still
+    for a while are counted (frame_select.HoldFrameSelector, `change_params` its keyword arguments, `change_counter` its count_fn);
+    everything that follows "change" below follows "hold" the same way.  Its default hold of 0.3 s and its behaviour on real footage
+    are not measured here; background edges that stand still that long still count and can add intervals, never lose one.
     interval_image="min" | "max" | "mean" (change selector only; default "middle", the above): one recognition error on that single
     frame is final, so the recogniser is instead shown, inside the area of the same middle frame, the per-pixel minimum (light
     text) / maximum (dark text) / mean of ALL frames of the interval, one more pass over the area's rows on the device
@@ -229,12 +233,12 @@ class SubtitleExtractor:
                  watermark_decide=None, scene_text_decide=lambda band: True, shard=None, gather_device=None,
                  word_segmentation=False, segment=None, uploader=None, detect_stream=None, frame_selector="fps", change_params=None,
                  change_counter=None, delete_empty=True, area_params=None, interval_image="middle", composite_params=None):
-        if frame_selector not in ("fps", "change"):
-            raise ValueError(f"frame_selector must be 'fps' or 'change', not {frame_selector!r}")
+        if frame_selector not in ("fps", "change", "hold"):
+            raise ValueError(f"frame_selector must be 'fps', 'change' or 'hold', not {frame_selector!r}")
         if interval_image not in ("middle",) + frame_select.COMPOSITE_MODES:
             raise ValueError(f"interval_image must be 'middle' or one of {frame_select.COMPOSITE_MODES}, not {interval_image!r}")
-        if interval_image != "middle" and frame_selector != "change":
-            raise ValueError(f"interval_image={interval_image!r} composites the intervals of frame_selector='change', not {frame_selector!r}")
+        if interval_image != "middle" and frame_selector not in ("change", "hold"):
+            raise ValueError(f"interval_image={interval_image!r} composites the intervals of frame_selector='change' or 'hold', not {frame_selector!r}")
         self.source, self.ocr, self.detect_batch = source, ocr, detect_batch
         self.auto_area, self.area_params, self.located_area = isinstance(sub_area, str) and sub_area == "auto", area_params, None
         self.sub_area, self.mode, self.language = None if self.auto_area else sub_area, mode, language
@@ -292,6 +296,11 @@ class SubtitleExtractor:
             sel = frame_select.ChangeFrameSelector(self.change_counter, batch=self.batch, **(self.change_params or {}))
             up = self._uploader()
             self.intervals = sel.run(self._decode_order(up), self.sub_area, uploader=up)
+            return [(s.frame_count, rep, None, None, None, self.default_subtitle_area) for _start, _end, rep in self.intervals]
+        if self.sub_area is not None and self.mode in ("fast", "auto") and self.frame_selector == "hold":
+            sel = frame_select.HoldFrameSelector(self.change_counter, batch=self.batch, **(self.change_params or {}))
+            up = self._uploader()
+            self.intervals = sel.run(self._decode_order(up), self.sub_area, s.fps, uploader=up)
             return [(s.frame_count, rep, None, None, None, self.default_subtitle_area) for _start, _end, rep in self.intervals]
         return fps_tasks(s.frame_count, s.fps, self.extract_frequency, self.default_subtitle_area)
 

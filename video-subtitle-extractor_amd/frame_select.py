@@ -313,6 +313,118 @@ class ChangeFrameSelector:
         return c.cpu() if hasattr(c, "cpu") else c
 
 
+# ---- held-edge selection (the change selector for footage whose background moves) ------------------------------------------
+def hold_intervals(counts, min_edges, hold, change_ratio=0.5, min_frames=2):
+    """change_intervals on the held-edge counts of a whole clip (vse_frame_hold): the same automaton; an interval shorter than `hold`
+    frames cannot hold an edge for `hold` frames, so it is not kept either."""
+    return change_intervals(counts, min_edges, change_ratio, max(min_frames, hold))
+
+
+class EngineHoldCounter:
+    """count_fn of HoldFrameSelector on the GPU (Context.frame_hold): keeps the device state of the last area and `hold`, and the
+    number of frames of the clip fed so far, between calls."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self._state = None
+        self._key = None
+        self.fed = 0
+
+    def __call__(self, frames, area, edge_thresh, hold, fed, flush):
+        t = self.ctx.torch
+        if not t.is_tensor(frames):
+            frames = t.from_numpy(frames).to(self.ctx.tdev)
+        y0, y1, x0, x1 = area
+        if self._key != (y1 - y0, x1 - x0, hold):
+            if fed:
+                raise ValueError(f"EngineHoldCounter: the area or hold changed to {(y1 - y0, x1 - x0, hold)} after {fed} frames of a clip")
+            self._key = (y1 - y0, x1 - x0, hold)
+            self._state = self.ctx.frame_hold_state(*self._key)
+        if fed and fed != self.fed:
+            raise ValueError(f"EngineHoldCounter: fed {fed}, but {self.fed} frames of this clip went to earlier calls")
+        self.fed = fed + len(frames)
+        return self.ctx.frame_hold(frames, area, edge_thresh, hold, self._state, fed, flush)
+
+
+class HoldFrameSelector:
+    """ChangeFrameSelector for footage whose background moves behind the subtitle.  The change selector compares every edge pixel of the
+    area with the frame before; a textured background that pans puts hundreds of edge pixels into the band that all move every
+    frame, so every frame is a cut and no subtitle is found.  A subtitle's edges hold still for many frames and a moving background's
+    do not: here the device counts only HELD edges, edge pixels inside a run of at least `hold` consecutive edge frames at that pixel
+    (vse_frame_hold), and hold_intervals runs the unchanged automaton on those counts.  hold = 1 is ChangeFrameSelector.
+    `hold_frames`, or max(1, min(32, round(hold_seconds * fps))) when it is None; hold_seconds=0.3 and the behaviour on real footage
+    are not measured here (no real clips).  Known limit: background edges that stay on one pixel for `hold` frames still count (a
+    static busy shot, a pan along an edge's own direction: in a numpy prototype a horizontal pan at hold 2-5 added intervals in the
+    gaps); such intervals cost OCR calls and lose no subtitle.
+
+    count_fn(frames [n,h,w,3] uint8, area (y0, y1, x0, x1) in their pixels, edge_thresh, hold, fed, flush) -> [rows,3] counts of the
+    frames whose held mask the call completes: they trail the frames fed by hold - 1 until the flush (fed: frames of the clip given
+    to earlier calls, 0 on the first batch; flush: the clip ends with this call).  Default: EngineHoldCounter on the shim's device."""
+
+    def __init__(self, count_fn=None, hold_seconds=0.3, hold_frames=None, edge_thresh=128, change_ratio=0.5, min_edges=None,
+                 min_frames=2, batch=64):
+        self.count_fn = count_fn
+        self.hold_seconds, self.hold_frames = hold_seconds, hold_frames
+        self.edge_thresh, self.change_ratio, self.min_edges, self.min_frames = edge_thresh, change_ratio, min_edges, min_frames
+        self.batch = batch
+        self.hold = None              # the hold of the last run, in frames
+        self.counts = None
+        self.intervals = None
+
+    def run(self, frames, sub_area, fps, uploader=None):
+        """frames: iterable of uint8 BGR frames in decode order; sub_area: .ymin .ymax .xmin .xmax in frame pixels (clipped to the
+        frame); fps: the clip's frame rate (for hold_seconds) -> [(start, end, rep)].  Batches are staged as ChangeFrameSelector.run
+        stages them; after the last one a call without frames flushes the rows still pending."""
+        import numpy as np
+        if self.count_fn is None:
+            from . import shim
+            self.count_fn = EngineHoldCounter(shim._context())
+        hold = self.hold_frames if self.hold_frames is not None else max(1, min(32, int(round(self.hold_seconds * fps))))
+        if not 1 <= hold <= 32:
+            raise ValueError(f"HoldFrameSelector: hold_frames must be 1..32, not {hold}")
+        self.hold = hold
+        it = iter(frames)
+        first = next(it, None)
+        if first is None:
+            self.counts, self.intervals = np.zeros((0, 3), np.int32), []
+            return self.intervals
+        h, w = first.shape[:2]
+        y0, y1, x0, x1 = clip_area(sub_area, h, w)
+        if y1 - y0 < 3 or x1 - x0 < 3:
+            raise ValueError(f"HoldFrameSelector: subtitle area {sub_area} leaves less than 3 x 3 pixels of a {h} x {w} frame")
+        area = (0, y1 - y0, x0, x1)
+
+        def batches():
+            buf = [(None, first[y0:y1])]
+            for f in it:
+                if len(buf) == self.batch:
+                    yield buf
+                    buf = []
+                buf.append((None, f[y0:y1]))
+            yield buf
+
+        out, fed = [], 0
+        if uploader is not None:
+            from . import staging
+            staged = None
+            for items, staged in staging.prefetch(batches(), uploader):
+                out.append(self._host(self.count_fn(staged.tensor(), area, self.edge_thresh, hold, fed, False)))
+                fed += len(items)
+            empty = staged.tensor()[:0]
+        else:
+            for items in batches():
+                out.append(self._host(self.count_fn(np.stack([f for _, f in items]), area, self.edge_thresh, hold, fed, False)))
+                fed += len(items)
+            empty = np.zeros((0, y1 - y0, w, 3), np.uint8)
+        out.append(self._host(self.count_fn(empty, area, self.edge_thresh, hold, fed, True)))
+        self.counts = np.concatenate([np.asarray(c, np.int32).reshape(-1, 3) for c in out])
+        min_edges = default_min_edges(y1 - y0, x1 - x0) if self.min_edges is None else self.min_edges
+        self.intervals = hold_intervals(self.counts, min_edges, hold, self.change_ratio, self.min_frames)
+        return self.intervals
+
+    _host = staticmethod(ChangeFrameSelector._host)
+
+
 # ---- interval composite (one picture per interval of the change selector) ------------------------------------------------
 COMPOSITE_MODES = ("min", "max", "mean")
 
