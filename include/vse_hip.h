@@ -351,6 +351,58 @@ size_t vse_audio_match_workspace_bytes(const vse_audio_query* queries, int nq);
 int vse_audio_match(vse_ctx* ctx, const uint8_t* d_src, int64_t src_len, const uint8_t* d_dst, int64_t dst_len,
                     const vse_audio_query* queries, int nq, void* d_ws, size_t ws_bytes, vse_audio_match_result* d_out, void* stream);
 
+/* ---- timeline sync: WAV PCM -> uint8 search stream ------------------------------------------------------------------------ */
+/* Replaces: Sushi's WavStream.__init__ and what it calls (backend/sushi/wav.py:17-165): the WAV is read one second at a time,
+ * downmixed, resampled to the search rate by nearest index, padded with 10 s of the FILE's rate on each side, clipped to 3 x the
+ * medians of its non-negative and non-positive samples and scaled to 0..255.  Here the int16 PCM goes to the device as it is and
+ * the uint8 stream of vse_audio_match is built there, byte for byte the host's (vse_amd.timeline_sync.AudioStream).  Input: F =
+ * `frames` frames of C = `channels` interleaved int16 values at R = `rate` Hz; S = `sample_rate` <= R is the search rate.
+ *   ratio = S / (double)R, sample_count = ceil(F / (double)R * S), P = 10 R (counted at the file's rate: Sushi's quirk),
+ *   L = 20 R + sample_count, K = ceil(F / R) chunks of one second;
+ *   chunk k has n_k = min(R, F - k R) frames and gives new_k = rint(n_k * ratio) samples (the product in double, ties to even) at
+ *     at_k = P + k S; every full chunk gives S;
+ *   a sample is the exact integer s = the sum over the channels of its frame's int16 values; sample j of chunk k takes frame j
+ *     when S == R, else frame min((int64)floor((double)j * scale_k), n_k - 1), scale_k = 1.0 / ((double)new_k / (double)n_k),
+ *     all in double (cv2.resize's INTER_NEAREST index rule);
+ *   the chunk lengths can sum to one short of sample_count: that element is 0;
+ *   data[0:P] = data[P], data[L-P:L] = data[L-P-1] (which can be that zero);
+ *   f(s) = (float)s for C == 1, else (float)s / (float)C, a correctly rounded float32 divide; f is monotone;
+ *   hi = 3 m({s >= 0}), lo = 3 m({s <= 0}) over all L elements (zeros count in both sets), m of a set of n elements in ascending
+ *     order: f(element n / 2) for odd n, else (f(element n / 2 - 1) + f(element n / 2)) rounded to float32, then / 2; the
+ *     product with 3 rounded to float32;
+ *   out[i] = (uint8)(((min(max(f(s_i), lo), hi) - lo) / (hi - lo)) * 255.0f + 0.5f): four float32 operations, each rounded on
+ *     its own (no fused multiply-add, hi - lo rounded once), the conversion truncates.
+ * The medians are exact order statistics: one counting pass into 65535 C + 1 uint32 bins and one scan over the bins.
+ * vse_audio_stream_length: L.  vse_audio_stream_workspace_bytes: the bytes of the caller-owned workspace (the int32 samples and
+ * the bins; 256-byte aligned, no particular content beforehand).  Both return 0 for what feed and finish refuse: channels
+ * outside 1..8, rate < sample_rate, frames < 1, L > 2^31 - 1. */
+typedef struct {
+    uint32_t lo_bits, hi_bits;       /* lo and hi as float32 bits (a quiet NaN for an empty set) */
+    uint32_t count_ge0, count_le0;   /* sizes of the two sets */
+    int32_t status;                  /* 0 ok; 1: a set is empty or hi - lo == 0 (the host's "silence"), the stream is not written */
+    int32_t reserved[3];
+} vse_audio_stream_result;
+int64_t vse_audio_stream_length(int64_t frames, int channels, int rate, int sample_rate);
+size_t vse_audio_stream_workspace_bytes(int64_t frames, int channels, int rate, int sample_rate);
+/* One piece of the file's PCM -> the int32 samples of its chunks in the workspace: d_pcm (device, 2-byte aligned) holds
+ * piece_frames frames that start at second `first_second` of the file.  A piece is a whole number of seconds; only the piece that
+ * ends the file may end in its partial second.  Pieces may come in any order of calls on one stream, each chunk exactly once, so a
+ * long file goes through two staging buffers.  The workspace keeps nothing else between calls: it needs no begin or reset and
+ * serves the next file as it is.  One launch on `stream`, no allocation, no device sync; a 4-byte aligned piece of an even channel
+ * count takes 4-byte loads, and on the copy path (S == R) of mono / stereo a piece whose groups of four frames are 8- / 16-byte
+ * aligned takes one load per group.
+ * Returns VSE_E_INVAL, and launches nothing, for the arguments above, a workspace that is too small or not 256-byte aligned, a
+ * piece that is empty, outside the file, or not whole seconds and not the file's end, and, when S != R, a last chunk with
+ * new_k == 0 (the host's "too few to resample"). */
+int vse_audio_stream_feed(vse_ctx* ctx, const int16_t* d_pcm, int64_t piece_frames, int64_t first_second, int64_t frames, int channels,
+                          int rate, int sample_rate, void* d_ws, size_t ws_bytes, void* stream);
+/* After every chunk was fed on `stream` (or before it in stream order): counts, selects lo and hi, writes the result record
+ * d_result (device, 4-byte aligned) and, when its status is 0, the L bytes of d_out (device, any alignment; a 16-byte aligned
+ * one takes whole 16-byte stores).  A clear of the bins and three launches on `stream`, no allocation, no device sync.
+ * Returns VSE_E_INVAL, and launches nothing, for what vse_audio_stream_feed refuses of the same arguments. */
+int vse_audio_stream_finish(vse_ctx* ctx, int64_t frames, int channels, int rate, int sample_rate, void* d_ws, size_t ws_bytes,
+                            uint8_t* d_out, vse_audio_stream_result* d_result, void* stream);
+
 /* ---- timeline sync: scene cuts for keyframe snapping ------------------------------------------------------------------- */
 /* Replaces: the keyframes Sushi makes by piping the video through ffmpeg (scale=640:360) into SCXvid, an XviD first pass whose
  * I-frame decisions mark the scene cuts (backend/sushi/demux.py:113-135).  Not XviD's algorithm but the same role: per frame, how

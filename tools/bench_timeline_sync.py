@@ -2,17 +2,21 @@
 """Timeline sync cost on a synthesized long pair (vse_amd.timeline_sync).
 
 Default run: a 45-minute pair at 12 kHz mono (about 65 MB per WAV) whose destination has an offset, an inserted segment and a
-cut, with one line every ~3 s; and a 5-minute 48 kHz stereo pair for the host cost of downmixing and resampling.  Reports
-  * host stream preparation (WAV -> uint8 stream) per file;
+cut, with one line every ~3 s; a 5-minute and a 30-minute 48 kHz stereo pair for the cost of downmixing and resampling.  Reports
+  * stream preparation (WAV -> uint8 stream) per file, on the host (AudioStream) and on the device (DeviceAudioStream: file read,
+    upload, kernels and the read-back that waits for them), the two alternating, three times each after a warm-up: median and
+    spread (max - min);
   * GPU search time: device events around every vse_audio_match call, per call class and in total;
-  * end-to-end sync() time with the GPU searcher;
+  * end-to-end sync() time with the GPU searcher in both stream_build modes, alternating in the same way, and the share of it that
+    preparation takes in each;
   * the same run with the numpy searcher (tests/audio_match_ref.py: float64 FFT, not cv2), the queries of a call on a pool of
     --threads threads.
 --kernels: only fixed series of calls per class (small window, normal step of 3 queries, max-window step), for a separate
 `rocprofv3 --kernel-trace --stats` run; --trace <kernel_trace.csv> then joins that trace to the classes and prints kernel time,
 MACs (m x offsets, from the shapes) and the share of the i8 dense MFMA peak.
 
-usage: python tools/bench_timeline_sync.py [--minutes 45] [--threads 16] [--no-numpy] [--kernels [--reps 20]] [--trace CSV]"""
+usage: python tools/bench_timeline_sync.py [--minutes 45] [--sizes hd48k,main,hd30] [--threads 16] [--no-numpy] [--kernels [--reps 20]]
+       [--trace CSV]"""
 import argparse
 import csv
 import json
@@ -94,11 +98,92 @@ def call_class(nq, offsets):
     return "max" if offsets > 30 * RATE * 1.5 else "normal"
 
 
-def run_sync(tmp, search):
+def run_sync(tmp, search, stream_build="host"):
     t0 = time.perf_counter()
     log = ts.sync(os.path.join(tmp, "src.wav"), os.path.join(tmp, "dst.wav"), os.path.join(tmp, "in.srt"), os.path.join(tmp, "out.srt"),
-                  search=search)
+                  search=search, stream_build=stream_build)
     return time.perf_counter() - t0, log
+
+
+def timed(fn):
+    t0 = time.perf_counter()
+    fn()
+    return time.perf_counter() - t0
+
+
+def spread(xs):
+    """Three repeats -> their median, and (max - min) as the spread."""
+    return round(sorted(xs)[len(xs) // 2], 4), round(max(xs) - min(xs), 4)
+
+
+# name -> (minutes, recipe pair): the 5-minute 48 kHz stereo pair, the long 12 kHz mono pair, a 30-minute 48 kHz stereo pair
+def sizes(a):
+    return {"hd48k": (5, long_pair(5, 48000, 2, seed=43)), "main": (a.minutes, long_pair(a.minutes)),
+            "hd30": (30, long_pair(30, 48000, 2, seed=47))}
+
+
+def measure_pair(ctx, name, minutes, pair, a, res):
+    """Stream preparation per file on the host and on the device, and sync() end to end in both modes: the two modes alternate,
+    three times each after a warm-up, in this one process.  The device figure is a host clock around DeviceAudioStream: file
+    read (from the page cache: the WAVs were just written), upload, kernels and the read-back of the result record, which waits for
+    the device."""
+    with tempfile.TemporaryDirectory() as tmp:
+        for side, r in zip(("src", "dst"), pair):
+            with open(os.path.join(tmp, f"{side}.wav"), "wb") as f:
+                f.write(synth.audio_from_recipe(r))
+        text, nlines = script(minutes)
+        with open(os.path.join(tmp, "in.srt"), "w") as f:
+            f.write(text)
+        for side in ("src", "dst"):
+            p = os.path.join(tmp, f"{side}.wav")
+            res[f"wav_{name}_{side}_MB"] = round(os.path.getsize(p) / 1e6, 1)
+            dev = ts.DeviceAudioStream(p, ctx=ctx)                  # warm-up (module load, allocator) and the byte check
+            res[f"same_bytes_{name}_{side}"] = bool(np.array_equal(dev.data.cpu().numpy(), ts.AudioStream(p).data))
+            del dev
+            host, device = [], []
+            for _ in range(3):
+                host.append(timed(lambda: ts.AudioStream(p)))
+                device.append(timed(lambda: ts.DeviceAudioStream(p, ctx=ctx)))
+            res[f"prep_{name}_{side}_s"], res[f"prep_{name}_{side}_spread_s"] = spread(host)
+            res[f"prep_device_{name}_{side}_s"], res[f"prep_device_{name}_{side}_spread_s"] = spread(device)
+        gs = TimedGpuSearch(ctx)
+        run_sync(tmp, gs, "device")                                 # warm-up (module load, workspace)
+        times = {"host": [], "device": []}
+        logs = {}
+        for _ in range(3):
+            for mode in ("host", "device"):
+                gs.calls.clear()
+                t, logs[mode] = run_sync(tmp, gs, mode)
+                times[mode].append(t)
+        key = "sync_gpu" if name == "main" else f"sync_gpu_{name}"
+        res[f"{key}_s"], res[f"{key}_spread_s"] = spread(times["host"])
+        res[f"{key}_device_build_s"], res[f"{key}_device_build_spread_s"] = spread(times["device"])
+        res[f"same_searches_{name}"] = logs["host"] == logs["device"]
+        res[f"lines_{name}"] = nlines
+        res[f"search_gpu_total_{name}_s"] = round(sum(c[3] for c in gs.calls) / 1e3, 4)
+        for mode, pre in (("host", "prep"), ("device", "prep_device")):
+            prep = res[f"{pre}_{name}_src_s"] + res[f"{pre}_{name}_dst_s"]
+            total = res[f"{key}_s"] if mode == "host" else res[f"{key}_device_build_s"]
+            res[f"prep_share_of_sync_{name}_{mode}"] = round(prep / total, 3)
+        if name != "main":
+            return
+        per = {}
+        for nq, offs, macs, ms in gs.calls:
+            c = per.setdefault(call_class(nq, offs), [0, 0.0, 0])
+            c[0] += 1
+            c[1] += ms
+            c[2] += macs
+        for k, (n, ms, macs) in per.items():
+            res[f"calls_{k}"] = n
+            res[f"search_{k}_ms_per_call"] = round(ms / n, 4)
+            res[f"search_{k}_GMAC_per_call"] = round(macs / n / 1e9, 2)
+        res["lines"] = nlines
+        res["search_gpu_total_s"] = res["search_gpu_total_main_s"]
+        res["searches"] = len(logs["host"])
+        if not a.no_numpy:
+            res["sync_numpy_fft_not_cv2_s"], nlog = run_sync(tmp, ThreadedNumpySearch(a.threads))
+            res["numpy_threads"] = a.threads
+            res["numpy_same_searches"] = [x[:5] for x in nlog] == [x[:5] for x in logs["host"]]
 
 
 def main():
@@ -106,6 +191,7 @@ def main():
     ap.add_argument("--minutes", type=float, default=45)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--no-numpy", action="store_true")
+    ap.add_argument("--sizes", default="hd48k,main,hd30", help="which pairs to run, of hd48k, main, hd30")
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--trace", default=None)
@@ -117,41 +203,11 @@ def main():
     if a.kernels:
         return kernel_series(ctx, a.reps)
     res = {}
-    with tempfile.TemporaryDirectory() as tmp:
-        for name, (src, dst) in (("hd48k", long_pair(5, 48000, 2, seed=43)), ("main", long_pair(a.minutes))):
-            for side, r in (("src", src), ("dst", dst)):
-                with open(os.path.join(tmp, f"{side}.wav"), "wb") as f:
-                    f.write(synth.audio_from_recipe(r))
-            for side in ("src", "dst"):
-                p = os.path.join(tmp, f"{side}.wav")
-                t0 = time.perf_counter()
-                ts.AudioStream(p)
-                res[f"prep_{name}_{side}_s"] = round(time.perf_counter() - t0, 3)
-                res[f"wav_{name}_{side}_MB"] = round(os.path.getsize(p) / 1e6, 1)
-        text, nlines = script(a.minutes)
-        with open(os.path.join(tmp, "in.srt"), "w") as f:
-            f.write(text)
-        res["lines"] = nlines
-        gs = TimedGpuSearch(ctx)
-        run_sync(tmp, gs)                                   # warm-up (module load, workspace)
-        gs.calls.clear()
-        res["sync_gpu_s"], log = run_sync(tmp, gs)
-        per = {}
-        for nq, offs, macs, ms in gs.calls:
-            c = per.setdefault(call_class(nq, offs), [0, 0.0, 0])
-            c[0] += 1
-            c[1] += ms
-            c[2] += macs
-        for k, (n, ms, macs) in per.items():
-            res[f"calls_{k}"] = n
-            res[f"search_{k}_ms_per_call"] = round(ms / n, 4)
-            res[f"search_{k}_GMAC_per_call"] = round(macs / n / 1e9, 2)
-        res["search_gpu_total_s"] = round(sum(c[3] for c in gs.calls) / 1e3, 4)
-        res["searches"] = len(log)
-        if not a.no_numpy:
-            res["sync_numpy_fft_not_cv2_s"], nlog = run_sync(tmp, ThreadedNumpySearch(a.threads))
-            res["numpy_threads"] = a.threads
-            res["numpy_same_searches"] = [x[:5] for x in nlog] == [x[:5] for x in log]
+    table = sizes(a)
+    for name in a.sizes.split(","):
+        minutes, pair = table[name]
+        measure_pair(ctx, name, minutes, pair, a, res)
+        print(f"{name} done: {json.dumps(res)}", file=sys.stderr, flush=True)      # (progress; the result is the last line)
     print(json.dumps(res))
 
 

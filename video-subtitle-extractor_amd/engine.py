@@ -24,6 +24,7 @@ EXPORTS = [
     "vse_audio_match_workspace_bytes", "vse_audio_match", "vse_scene_change_state_bytes", "vse_scene_change_workspace_bytes",
     "vse_scene_change", "vse_frame_cells_dims", "vse_frame_cells_state_bytes", "vse_frame_cells",
     "vse_interval_state_bytes", "vse_interval_accumulate", "vse_interval_composite", "vse_frame_hold_state_bytes", "vse_frame_hold",
+    "vse_audio_stream_length", "vse_audio_stream_workspace_bytes", "vse_audio_stream_feed", "vse_audio_stream_finish",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -155,6 +156,14 @@ def load_library(path=None):
     lib.vse_audio_match_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
     lib.vse_audio_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
                                     C.c_size_t, C.c_void_p, C.c_void_p]
+    lib.vse_audio_stream_length.restype = C.c_int64
+    lib.vse_audio_stream_length.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int]
+    lib.vse_audio_stream_workspace_bytes.restype = C.c_size_t
+    lib.vse_audio_stream_workspace_bytes.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int]
+    lib.vse_audio_stream_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_size_t, C.c_void_p]
+    lib.vse_audio_stream_finish.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]
     lib.vse_scene_change_state_bytes.restype = C.c_size_t
     lib.vse_scene_change_state_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.vse_scene_change_workspace_bytes.restype = C.c_size_t
@@ -531,6 +540,49 @@ class Context:
                                         dst_u8.numel(), C.c_void_p(q.ctypes.data), len(q), C.c_void_p(workspace.data_ptr()),
                                         workspace.numel(), C.c_void_p(out.data_ptr()), self.stream()), "vse_audio_match")
         return out
+
+    # ---- timeline sync: WAV PCM -> uint8 search stream --------------------------------------------------------------
+    def audio_stream_length(self, frames, channels, rate, sample_rate):
+        """Elements of the uint8 stream of a WAV of `frames` frames (0 for what audio_stream_feed refuses)."""
+        return int(self.lib.vse_audio_stream_length(int(frames), int(channels), int(rate), int(sample_rate)))
+
+    def audio_stream_workspace(self, frames, channels, rate, sample_rate):
+        """A workspace for audio_stream_feed / audio_stream_finish of such a file (it needs no content and serves later files that
+        need no more bytes)."""
+        nbytes = self.lib.vse_audio_stream_workspace_bytes(int(frames), int(channels), int(rate), int(sample_rate))
+        if not nbytes:
+            raise VseError(f"audio_stream: {frames} frames of {channels} channels at {rate} Hz for a {sample_rate} Hz stream: 1..8 channels, "
+                           "a rate of at least the search rate, at least one frame and at most 2^31 - 1 stream elements")
+        return self.torch.empty(nbytes, dtype=self.torch.uint8, device=self.tdev)
+
+    def audio_stream_feed(self, pcm_i16, first_second, frames, channels, rate, sample_rate, workspace):
+        """pcm_i16: contiguous cuda int16 holding whole frames of the file from second `first_second` on (whole seconds, or up to the
+        file's end) -> their samples in `workspace`, on the current stream (include/vse_hip.h vse_audio_stream_feed)."""
+        t = self.torch
+        channels = int(channels)
+        assert pcm_i16.dtype == t.int16 and pcm_i16.is_contiguous() and (channels < 1 or pcm_i16.numel() % channels == 0)
+        assert workspace.dtype == t.uint8 and workspace.is_contiguous()
+        _check(self.lib.vse_audio_stream_feed(self.handle, C.c_void_p(pcm_i16.data_ptr()), pcm_i16.numel() // max(channels, 1), int(first_second),
+                                              int(frames), int(channels), int(rate), int(sample_rate), C.c_void_p(workspace.data_ptr()),
+                                              workspace.numel(), self.stream()), "vse_audio_stream_feed")
+
+    def audio_stream_finish(self, frames, channels, rate, sample_rate, workspace, out=None, result=None):
+        """-> (cuda uint8 [L] stream, cuda int32 [8] record: lo and hi as float32 bits, the sizes of the >= 0 and <= 0 sets, status) on
+        the current stream (include/vse_hip.h vse_audio_stream_finish).  With status 1 (an empty level range) `out` is not written.
+        out: a contiguous cuda uint8 tensor of L elements (any alignment) to write into."""
+        t = self.torch
+        length = self.audio_stream_length(frames, channels, rate, sample_rate)
+        if out is None:
+            out = t.empty(length, dtype=t.uint8, device=self.tdev)
+        if result is None:
+            result = t.empty(8, dtype=t.int32, device=self.tdev)
+        assert out.dtype == t.uint8 and out.is_contiguous() and out.numel() == length
+        assert result.dtype == t.int32 and result.is_contiguous() and result.numel() == 8
+        assert workspace.dtype == t.uint8 and workspace.is_contiguous()
+        _check(self.lib.vse_audio_stream_finish(self.handle, int(frames), int(channels), int(rate), int(sample_rate),
+                                                C.c_void_p(workspace.data_ptr()), workspace.numel(), C.c_void_p(out.data_ptr()),
+                                                C.c_void_p(result.data_ptr()), self.stream()), "vse_audio_stream_finish")
+        return out, result
 
     # ---- timeline sync: scene cuts for keyframe snapping ----------------------------------------------------------
     def scene_change_state(self, h, w, scale):

@@ -13,7 +13,7 @@ v2); `python -m vse_amd.keyframes` finds a video's cuts on the GPU and writes su
 
 Inputs are WAV files only: the project has no demuxer, so chapters, stream selection and keyframes made on the fly stay out.
 
-    python -m vse_amd.timeline_sync --src a.wav --dst b.wav --script in.srt --output out.srt
+    python -m vse_amd.timeline_sync --src a.wav --dst b.wav --script in.srt --output out.srt [--stream-build device]
         [--src-keyframes a.kf.txt --dst-keyframes b.kf.txt --src-fps 23.976 --dst-fps 23.976]
 """
 import argparse
@@ -178,11 +178,114 @@ class AudioStream:
         return start_time, s, max(e - s, 0)
 
 
+# ---- WAV -> uint8 stream on the device (include/vse_hip.h, the vse_audio_stream_* section) ---------------------------------------
+
+PIECE_BYTES = 64 << 20         # PCM bytes per staging buffer, at most (a second that is larger goes alone)
+MAX_DEVICE_CHANNELS = 8
+
+
+class _GpuStreamBuild:
+    """The product `build` of DeviceAudioStream: feed(pcm int16 [n, C], first_second) copies the piece into one of two pinned
+    buffers, uploads it and gathers it on the current stream while the host fills the other buffer; finish() counts, selects and
+    writes the stream, and reads the result record back (the one wait for the device)."""
+
+    def __init__(self, ctx, frames, channels, rate, sample_rate):
+        self.ctx = ctx
+        self.args = (frames, channels, rate, sample_rate)
+        self.ws = ctx.audio_stream_workspace(*self.args)
+        self.slabs = [None, None]        # (pinned int16, device int16, event recorded behind the upload that reads the pinned one)
+        self.turn = 0
+
+    def feed(self, pcm, first_second):
+        t = self.ctx.torch
+        n = int(pcm.shape[0]) * int(pcm.shape[1])
+        i, self.turn = self.turn, self.turn ^ 1
+        slab = self.slabs[i]
+        if slab is not None:
+            slab[2].synchronize()        # the upload out of this pinned buffer is done
+        if slab is None or slab[0].numel() < n:
+            slab = self.slabs[i] = (t.empty(n, dtype=t.int16, pin_memory=True), t.empty(n, dtype=t.int16, device=self.ctx.tdev),
+                                    t.cuda.Event())
+        host, dev, event = slab
+        host.numpy()[:n] = np.asarray(pcm).reshape(-1)
+        dev[:n].copy_(host[:n], non_blocking=True)
+        event.record()
+        self.ctx.audio_stream_feed(dev[:n], first_second, *self.args, self.ws)
+
+    def finish(self):
+        out, record = self.ctx.audio_stream_finish(*self.args, self.ws)
+        r = record.cpu().numpy()
+        lo, hi = r[:2].copy().view(np.float32)
+        status = int(r[4])
+        return (out if status == 0 else None), lo, hi, int(r[2]), int(r[3]), status
+
+
+class DeviceAudioStream(AudioStream):
+    """AudioStream built on the device: the WAV's PCM is memory-mapped, fed in pieces of whole seconds and turned into the same
+    uint8 stream there, so `data` is a cuda uint8 tensor that GpuSearch takes as it is.  `levels` = (lo, hi), the float32 clip
+    levels.  build(frames, channels, rate, sample_rate) -> an object with feed(pcm int16 [n, C], first_second) and finish() ->
+    (stream, lo, hi, size of the >= 0 set, size of the <= 0 set, status); None: the device one on `ctx`.  A file the device path
+    does not take (a data chunk shorter than its header claims, more than 8 channels, more than 4 GiB, no frame, a stream of
+    2^31 elements or more) goes through AudioStream itself: `data` is then its host array and `levels` is None.
+    piece_seconds: seconds per piece (None: what fits PIECE_BYTES); piece_order: a function of the list of pieces' first seconds
+    that returns the order to feed them in."""
+
+    def __init__(self, path, sample_rate=12000, ctx=None, build=None, *, piece_seconds=None, piece_order=None):
+        with open(path, "rb") as f:
+            channels, framerate, width, frames = _read_wav_header(f, path)
+            offset = f.tell()
+        if framerate < sample_rate:
+            raise TimelineSyncError(f"{path}: the sample rate {framerate} Hz is below the search rate {sample_rate} Hz")
+        file_size = os.path.getsize(path)
+        why = None
+        if channels > MAX_DEVICE_CHANNELS:
+            why = f"{channels} channels"
+        elif file_size > 0xFFFFFFFF:
+            why = "a file over 4 GiB"
+        elif file_size - offset < frames * channels * width:
+            why = "a data chunk shorter than its header claims"
+        elif frames < 1:
+            why = "no audio frame"
+        elif 2 * PADDING_SECONDS * framerate + math.ceil(frames / float(framerate) * sample_rate) > 2 ** 31 - 1:
+            why = "a stream of 2^31 elements or more"
+        self.levels = None
+        if why is not None:
+            log.info("%s: %s, the stream is built on the host", path, why)
+            super().__init__(path, sample_rate)
+            return
+        self.sample_rate = sample_rate
+        self.sample_count = math.ceil(frames / float(framerate) * sample_rate)
+        self.padding_size = 10 * framerate
+        seconds = -(-frames // framerate)
+        last = frames - (seconds - 1) * framerate
+        if sample_rate != framerate and int(round(last * (sample_rate / float(framerate)))) == 0:
+            raise TimelineSyncError(f"{path}: the last {last} frames are too few to resample")
+        if build is None:
+            if ctx is None:
+                from . import engine
+                ctx = engine.Context(0)
+            build = lambda *a: _GpuStreamBuild(ctx, *a)           # noqa: E731
+        builder = build(frames, channels, framerate, sample_rate)
+        if piece_seconds is None:
+            piece_seconds = max(PIECE_BYTES // (framerate * channels * width), 1)
+        pcm = np.memmap(path, dtype="<i2", mode="r", offset=offset, shape=(frames, channels))
+        firsts = list(range(0, seconds, piece_seconds))
+        for first in (piece_order(firsts) if piece_order else firsts):
+            builder.feed(pcm[first * framerate:(first + piece_seconds) * framerate], first)
+        del pcm
+        data, lo, hi, _, _, status = builder.finish()
+        if status != 0:
+            raise TimelineSyncError(f"{path}: the audio is (almost) all silence; its level range is empty")
+        self.data = data
+        self.levels = (np.float32(lo), np.float32(hi))
+
+
 # ---- searchers --------------------------------------------------------------------------------------------------------------
 
 class GpuSearch:
-    """The product searcher: load(src, dst) uploads both uint8 streams once; __call__([(src_off, m, dst_off, win_len)] * 1..3)
-    -> [(first argmin offset, float32 value)] from one vse_audio_match call (a grown workspace is reused)."""
+    """The product searcher: load(src, dst) uploads both uint8 streams once (a cuda uint8 tensor, DeviceAudioStream's, is taken as it
+    is); __call__([(src_off, m, dst_off, win_len)] * 1..3) -> [(first argmin offset, float32 value)] from one vse_audio_match call
+    (a grown workspace is reused)."""
 
     def __init__(self, ctx=None):
         if ctx is None:
@@ -193,8 +296,13 @@ class GpuSearch:
 
     def load(self, src, dst):
         t = self.ctx.torch
-        self.src = t.from_numpy(np.ascontiguousarray(src, np.uint8)).to(self.ctx.tdev)
-        self.dst = t.from_numpy(np.ascontiguousarray(dst, np.uint8)).to(self.ctx.tdev)
+
+        def device(x):
+            if isinstance(x, t.Tensor) and x.is_cuda and x.dtype == t.uint8 and x.is_contiguous():
+                return x
+            return t.from_numpy(np.ascontiguousarray(x, np.uint8)).to(self.ctx.tdev)
+
+        self.src, self.dst = device(src), device(dst)
 
     def __call__(self, queries):
         need = self.ctx.audio_match_workspace_bytes(queries)
@@ -886,16 +994,22 @@ def _extension(path):
 def sync(src_wav, dst_wav, script_path, output_path, *, window=10, max_window=30, rewind_thresh=5, grouping=True, smooth_radius=3,
          max_ts_duration=1001.0 / 24000.0 * 10, max_ts_distance=1001.0 / 24000.0 * 10, sample_rate=12000, search=None,
          src_keyframes=None, dst_keyframes=None, src_fps=None, dst_fps=None, src_timecodes=None, dst_timecodes=None, max_kf_distance=2,
-         kf_mode="all"):
+         kf_mode="all", stream_build="host"):
     """Retime `script_path` (.srt or .ass) from the audio of `src_wav` onto that of `dst_wav`, write `output_path` (same type).
     search: the searcher (None: the GPU one, GpuSearch).  Returns the searches made, in order:
     [(src_off, m, dst_off, win_len, index, float32 value)] over the two uint8 streams.
     src_keyframes / dst_keyframes (both or none): a keyframes file or a list of frame numbers; each side then needs src_fps /
     dst_fps or src_timecodes / dst_timecodes (a v1 / v2 file).  Lines whose start or end lies within max_kf_distance frames of a
-    keyframe on both sides snap to it; kf_mode: "shift" (whole lines), "snap" (start and end separately) or "all"."""
+    keyframe on both sides snap to it; kf_mode: "shift" (whole lines), "snap" (start and end separately) or "all".
+    stream_build: "host" builds the two uint8 streams with numpy (AudioStream), "device" on the GPU (DeviceAudioStream: the same
+    bytes); "device" needs the GPU searcher."""
     use_kf = check_keyframe_options(src_keyframes, dst_keyframes, src_fps, dst_fps, src_timecodes, dst_timecodes)
     if kf_mode not in ("all", "shift", "snap"):
         raise TimelineSyncError(f"--kf-mode {kf_mode}: one of shift, snap, all")
+    if stream_build not in ("host", "device"):
+        raise TimelineSyncError(f"--stream-build {stream_build}: one of host, device")
+    if stream_build == "device" and search is not None and not isinstance(search, GpuSearch):
+        raise TimelineSyncError("--stream-build device needs the GPU searcher: its streams stay on the device")
     for path, what in ((src_wav, "Source"), (dst_wav, "Destination"), (script_path, "Script")):
         if not os.path.exists(path):
             raise TimelineSyncError(f"{what} file doesn't exist")
@@ -918,8 +1032,14 @@ def sync(src_wav, dst_wav, script_path, output_path, *, window=10, max_window=30
 
     script = (AssScript if ext == ".ass" else SrtScript).from_file(script_path)
     script.events.sort(key=lambda e: e.start)
-    src = AudioStream(src_wav, sample_rate)
-    dst = AudioStream(dst_wav, sample_rate)
+    if stream_build == "device":
+        if search is None:
+            search = GpuSearch()
+        src = DeviceAudioStream(src_wav, sample_rate, ctx=search.ctx)
+        dst = DeviceAudioStream(dst_wav, sample_rate, ctx=search.ctx)
+    else:
+        src = AudioStream(src_wav, sample_rate)
+        dst = AudioStream(dst_wav, sample_rate)
     searcher = _Searcher(GpuSearch() if search is None else search, src, dst)
 
     groups = prepare_search_groups(script.events, src.duration_seconds, [], max_ts_duration, max_ts_distance)
@@ -967,6 +1087,8 @@ def _parser():
     p.add_argument("--max-ts-distance", default=1001.0 / 24000.0 * 10, type=float)
     p.add_argument("--sample-rate", default=12000, type=int)
     p.add_argument("--sample-type", default="uint8")
+    p.add_argument("--stream-build", default="host", choices=["host", "device"],
+                   help="where the two uint8 streams are built from the WAVs: numpy on the host, or the GPU (the same bytes) [host]")
     p.add_argument("--src-keyframes", default=None, help="source keyframes file (python -m vse_amd.keyframes writes one)")
     p.add_argument("--dst-keyframes", default=None, help="destination keyframes file")
     p.add_argument("--src-fps", default=None, type=float, help="fps of the source video (or --src-timecodes)")
@@ -999,7 +1121,8 @@ def main(argv=None):
         sync(args.src, args.dst, args.script, output, window=args.window, max_window=args.max_window, rewind_thresh=args.rewind_thresh,
              grouping=args.grouping, smooth_radius=args.smooth_radius, max_ts_duration=args.max_ts_duration,
              max_ts_distance=args.max_ts_distance, sample_rate=args.sample_rate, **kf,
-             max_kf_distance=2 if args.max_kf_distance is None else args.max_kf_distance, kf_mode=args.kf_mode or "all")
+             max_kf_distance=2 if args.max_kf_distance is None else args.max_kf_distance, kf_mode=args.kf_mode or "all",
+             stream_build=args.stream_build)
     except TimelineSyncError as e:
         print(f"timeline_sync: {e}", file=sys.stderr)
         return 2
