@@ -268,6 +268,59 @@ class Emulator:
                 pc = int(gv["c"])
                 self.write_pair(gv, int(r["p"][ir.P_CH_LO_OUT0 + g]), yo if pc == cout else F.pad(yo, (0, pc - cout)))
 
+    def conv_wmat(self, r, kh=None, kw=None):
+        """The weight matrix [Np][kh * kw * cinp] (K in (tap, channel) order, hi + lo summed) decoded from the stream of an OP_CONV record,
+        whatever family it was packed for (not F_UP2HEAD: folded taps).  kh, kw: the conv's own (1, 1 behind an F_DWPRE depthwise conv)."""
+        p = r["p"]
+        kh, kw = (int(p[0]) if kh is None else kh), (int(p[1]) if kw is None else kw)
+        Np, Kp, cinp = int(p[ir.P_COUT]), int(p[ir.P_KTOT]), int(p[ir.P_CINP])
+        KT = ir.KT
+        if int(r["flags"]) & ir.F_PW:
+            assert (kh, kw) == (1, 1) and Kp == (cinp + 15) // 16 * 16
+            wmat = self.wread(int(r["w_off"]), Np * Kp, np.float16).astype(np.float32).reshape(Np, Kp)
+            if int(r["flags"]) & ir.F_HILO:           # w = hi + lo (the lo table follows the hi table)
+                wmat = wmat + self.wread(int(r["w_off"]) + 2 * Np * Kp, Np * Kp, np.float16).astype(np.float32).reshape(Np, Kp)
+            assert not wmat[:, cinp:].any()
+            wmat = wmat[:, :cinp]
+        elif int(r["flags"]) & ir.F_COL and int(r["flags"]) & ir.F_HLSUM:
+            # 64-row stages [hi 32 | lo 32]: w = hi + lo (the kernel adds the two accumulator tiles)
+            assert cinp % 16 == 0 and Kp == kh * kw * cinp and Np <= 32 and (kh, kw) == (3, 3) and not int(r["flags"]) & ir.F_HILO
+            wt = self.wread(int(r["w_off"]), Kp * 64 + 3 * kh * 64 * 16, np.float16).astype(np.float32)
+            assert not wt[Kp * 64:].any()
+            w64 = np.ascontiguousarray(wt[:Kp * 64].reshape(cinp // 16, kw, kh, 64, 16).transpose(3, 2, 1, 0, 4)).reshape(64, Kp)
+            wmat = (w64[:32] + w64[32:])[:Np]
+        elif int(r["flags"]) & ir.F_COL:
+            assert cinp % 16 == 0 and Kp == kh * kw * cinp
+            npass = 2 if int(r["flags"]) & ir.F_HILO else 1          # w = hi + lo (the lo stream follows the hi stream)
+            wt = self.wread(int(r["w_off"]), npass * Kp * Np + 3 * kh * Np * 16, np.float16).astype(np.float32)
+            assert not wt[npass * Kp * Np:].any()           # the three zero stages of the DMA look-ahead
+            ws = wt[:Kp * Np] + wt[Kp * Np:2 * Kp * Np] if npass == 2 else wt[:Kp * Np]      # (no '+ 0.0': a -0 weight stays -0)
+            wmat = np.ascontiguousarray(ws.reshape(cinp // 16, kw, kh, Np, 16).transpose(3, 2, 1, 0, 4)).reshape(Np, Kp)
+        elif int(r["flags"]) & ir.F_PATCH:
+            taps = kh * kw
+            c32 = (cinp + 31) // 32 * 32
+            tp = Kp // c32                                  # taps padded to whole kernel steps by the compiler
+            wt = self.wread(int(r["w_off"]), tp * c32 * Np, np.float16).astype(np.float32)
+            wfull = wt.reshape(c32 // 32, tp, Np, 32).transpose(2, 1, 0, 3).reshape(Np, tp, c32)
+            assert not wfull[:, taps:].any() and not wfull[:, :, cinp:].any()
+            row_major = [(t % kw) * kh + t // kw for t in range(taps)]     # stream is column-major: t' = dx*kh + dy
+            wmat = np.ascontiguousarray(wfull[:, :taps, :cinp][:, row_major, :]).reshape(Np, taps * cinp)
+        elif int(r["flags"]) & ir.F_STEM:
+            wt = self.wread(int(r["w_off"]), Np * 80, np.float16).astype(np.float32)
+            if int(r["flags"]) & ir.F_HILO:
+                wt = wt + self.wread(int(r["w_off"]) + 2 * Np * 80, Np * 80, np.float16).astype(np.float32)
+            wt = wt.reshape(Np, 10, 8)
+            assert not wt[:, 9:].any() and not wt[:, :, 4:].any() and (kh, kw, cinp) == (3, 3, 8)
+            wmat = np.ascontiguousarray(wt[:, :9]).reshape(Np, 72)
+        else:
+            kt = 32 if int(r["flags"]) & ir.F_WK32 else KT
+            cnt = (Kp // kt) * Np * kt
+            wt = self.wread(int(r["w_off"]), cnt, np.float16).astype(np.float32)
+            if int(r["flags"]) & ir.F_HILO:           # w = hi + lo (the lo tiles follow the hi tiles)
+                wt = wt + self.wread(int(r["w_off"]) + 2 * cnt, cnt, np.float16).astype(np.float32)
+            wmat = wt.reshape(Kp // kt, Np, kt).transpose(1, 0, 2).reshape(Np, Kp)[:, :kh * kw * cinp]
+        return wmat
+
     def _op1(self, r):   # CONV
         p, f = r["p"], r["f"]
         kh, kw, sh, sw, ph, pw = (int(p[i]) for i in range(6))
@@ -329,50 +382,7 @@ class Emulator:
             x = xd.permute(0, 2, 3, 1)            # (the kernel keeps this as an fp16 hi + lo pair in registers: ~fp32)
             kh = kw = sh = sw = 1
             ph = pw = 0
-        if int(r["flags"]) & ir.F_PW:
-            assert (kh, kw) == (1, 1) and Kp == (cinp + 15) // 16 * 16
-            wmat = self.wread(int(r["w_off"]), Np * Kp, np.float16).astype(np.float32).reshape(Np, Kp)
-            if int(r["flags"]) & ir.F_HILO:           # w = hi + lo (the lo table follows the hi table)
-                wmat = wmat + self.wread(int(r["w_off"]) + 2 * Np * Kp, Np * Kp, np.float16).astype(np.float32).reshape(Np, Kp)
-            assert not wmat[:, cinp:].any()
-            wmat = wmat[:, :cinp]
-        elif int(r["flags"]) & ir.F_COL and int(r["flags"]) & ir.F_HLSUM:
-            # 64-row stages [hi 32 | lo 32]: w = hi + lo (the kernel adds the two accumulator tiles)
-            assert cinp % 16 == 0 and Kp == kh * kw * cinp and Np <= 32 and (kh, kw) == (3, 3) and not int(r["flags"]) & ir.F_HILO
-            wt = self.wread(int(r["w_off"]), Kp * 64 + 3 * kh * 64 * 16, np.float16).astype(np.float32)
-            assert not wt[Kp * 64:].any()
-            w64 = np.ascontiguousarray(wt[:Kp * 64].reshape(cinp // 16, kw, kh, 64, 16).transpose(3, 2, 1, 0, 4)).reshape(64, Kp)
-            wmat = (w64[:32] + w64[32:])[:Np]
-        elif int(r["flags"]) & ir.F_COL:
-            assert cinp % 16 == 0 and Kp == kh * kw * cinp
-            npass = 2 if int(r["flags"]) & ir.F_HILO else 1          # w = hi + lo (the lo stream follows the hi stream)
-            wt = self.wread(int(r["w_off"]), npass * Kp * Np + 3 * kh * Np * 16, np.float16).astype(np.float32)
-            assert not wt[npass * Kp * Np:].any()           # the three zero stages of the DMA look-ahead
-            ws = wt[:Kp * Np] + (wt[Kp * Np:2 * Kp * Np] if npass == 2 else 0.0)
-            wmat = np.ascontiguousarray(ws.reshape(cinp // 16, kw, kh, Np, 16).transpose(3, 2, 1, 0, 4)).reshape(Np, Kp)
-        elif int(r["flags"]) & ir.F_PATCH:
-            taps = kh * kw
-            c32 = (cinp + 31) // 32 * 32
-            tp = Kp // c32                                  # taps padded to whole kernel steps by the compiler
-            wt = self.wread(int(r["w_off"]), tp * c32 * Np, np.float16).astype(np.float32)
-            wfull = wt.reshape(c32 // 32, tp, Np, 32).transpose(2, 1, 0, 3).reshape(Np, tp, c32)
-            assert not wfull[:, taps:].any() and not wfull[:, :, cinp:].any()
-            row_major = [(t % kw) * kh + t // kw for t in range(taps)]     # stream is column-major: t' = dx*kh + dy
-            wmat = np.ascontiguousarray(wfull[:, :taps, :cinp][:, row_major, :]).reshape(Np, taps * cinp)
-        elif int(r["flags"]) & ir.F_STEM:
-            wt = self.wread(int(r["w_off"]), Np * 80, np.float16).astype(np.float32)
-            if int(r["flags"]) & ir.F_HILO:
-                wt = wt + self.wread(int(r["w_off"]) + 2 * Np * 80, Np * 80, np.float16).astype(np.float32)
-            wt = wt.reshape(Np, 10, 8)
-            assert not wt[:, 9:].any() and not wt[:, :, 4:].any() and (kh, kw, cinp) == (3, 3, 8)
-            wmat = np.ascontiguousarray(wt[:, :9]).reshape(Np, 72)
-        else:
-            kt = 32 if int(r["flags"]) & ir.F_WK32 else KT
-            cnt = (Kp // kt) * Np * kt
-            wt = self.wread(int(r["w_off"]), cnt, np.float16).astype(np.float32)
-            if int(r["flags"]) & ir.F_HILO:           # w = hi + lo (the lo tiles follow the hi tiles)
-                wt = wt + self.wread(int(r["w_off"]) + 2 * cnt, cnt, np.float16).astype(np.float32)
-            wmat = wt.reshape(Kp // kt, Np, kt).transpose(1, 0, 2).reshape(Np, Kp)[:, :kh * kw * cinp]
+        wmat = self.conv_wmat(r, kh, kw)
         bias = torch.from_numpy(self.wread(int(r["b_off"]), Np, np.float32).copy())
         if int(r["flags"]) & ir.F_IMGW:
             # per-image weights written by OP_WSCALE into the workspace (in2): [N][Kp/kt][Np][kt]
@@ -395,11 +405,11 @@ class Emulator:
             cp = Np // 4
             y = y.reshape(n, h, w, 2, 2, cp).permute(0, 1, 3, 2, 4, 5).reshape(n, 2 * h, 2 * w, cp)
         if flags & ir.F_RES:
-            res = self._up(self.read(r["in1"]), int(p[ir.P_RESSHIFT]))
+            res = self._up(self.read(r["in1"]), int(p[ir.P_RESSHIFT]))[:, :y.shape[1], :y.shape[2]]      # (odd maps: the last row / column of a pair)
             if int(p[ir.P_LO_RES]):           # the residual is an fp16 hi + lo pair
                 lv = r["in1"].copy()
                 lv["off"] = int(lv["off"]) + int(p[ir.P_LO_RES]) * int(lv["esize"])
-                res = res + self.read(lv)
+                res = res + self.read(lv)[:, :y.shape[1], :y.shape[2]]
             y[..., :res.shape[3]] += res[..., :y.shape[3]]
         y = _act(y, int(p[ir.P_ACT2]))
         if flags & ir.F_DOT1:

@@ -1,7 +1,9 @@
 """One-record plans: run a single `vse_op` record — one HIP kernel — on tensors the test chooses, on the GPU (run_gpu) and on the
 CPU emulator (run_emulator), and hold the result to a plain fp64 reference of the same operation.
 
-A plain helper module like tests/parity.py (no fixtures, no pytest settings).  It has four parts:
+A plain helper module like tests/parity.py (no fixtures, no pytest settings).  It has four parts (and, at the end, the same four for
+OP_CONV: conv_op, conv_pack — the compiler's own static packers —, conv_name — the library's own answer, vse_op_kernel_name —, ref_conv and
+conv_reference; the cases are tests/conv_cases.py):
 
   * builders for ir.VIEW_DT / ir.OP_DT records (the fields follow the comments of ir.py and the checks at the top of each `case` of
     launch_simple_op, csrc/simple_ops.hip), and a weight blob with the compiler's 256-byte alignment;
@@ -466,3 +468,165 @@ def lstm_mfma_blob(w_hhs):
 def lstm_mfma_gates(g):
     """Gate pre-activations [.., 4H] in i, f, g, o order -> the channel order the MFMA kernel reads (Compiler.lstm_gate_order)."""
     return np.ascontiguousarray(g[..., compiler.Compiler.lstm_gate_order(g.shape[-1] // 4)])
+
+
+# ---------------------------------------------------------------------------------------------------------------- OP_CONV
+# One conv record = one instantiation of one conv kernel family.  The fields follow conv_params and the checks at the top of launch_conv
+# (csrc/conv_select.hip); which instantiation a record selects is asked of the library (conv_name), never restated here.
+def conv_op(in0, out, k, s, pad, cout, ktot, cinp, w_off, b_off, flags=0, act=ir.ACT_NONE, act2=ir.ACT_NONE, act_a=0.0, act_b=0.0,
+            post_a=1.0, post_b=0.0, inshift=0, res=None, resshift=0, in2=None, in2shift=0, out2=None, aux_off=0, dotact=ir.ACT_NONE,
+            pre_b=0.0, lo_out=0, lo_res=0, lo_in=0, wl=(0, 0)):
+    """k = (kh, kw), s = (sh, sw), pad = (ph, pw); cout = P_COUT (GEMM N: padded couts, x 4 under F_PIXSHUF), ktot = P_KTOT (the padded K
+    of the weight stream), cinp = P_CINP (stored input channels, both sources of an F_SRC2 conv).  Views: in0; res = in1 (F_RES, read through
+    resshift, a hi + lo pair when lo_res); in2 = the second source (F_SRC2, in2shift), the per-image weights (F_IMGW) or the gate (F_OGATE);
+    out (a pair when lo_out); out2 = the 1-channel map of F_DOT1 / F_UP2HEAD / F_TAIL2 (dotact, pre_b = its activation and bias; aux_off =
+    its weights — or the depthwise table of F_DWPRE, whose geometry k / s / pad then is, with lo_in the pair offset of in0)."""
+    return op(ir.OP_CONV, [in0, res, in2], out, out2=out2, flags=flags, w_off=w_off, b_off=b_off, aux_off=aux_off, wl=wl,
+              p={ir.P_KH: k[0], ir.P_KW: k[1], ir.P_SH: s[0], ir.P_SW: s[1], ir.P_PH: pad[0], ir.P_PW: pad[1], ir.P_ACT: act, ir.P_ACT2: act2,
+                 ir.P_COUT: cout, ir.P_KTOT: ktot, ir.P_INSHIFT: inshift, ir.P_RESSHIFT: resshift, ir.P_CINP: cinp, ir.P_DOTACT: dotact,
+                 ir.P_IN2SHIFT: in2shift, ir.P_LO_OUT: lo_out, ir.P_LO_RES: lo_res, ir.P_LO_IN: lo_in},
+              f={ir.FS_ACT_A: act_a, ir.FS_ACT_B: act_b, ir.FS_POST_A: post_a, ir.FS_POST_B: post_b, ir.FS_PRE_B: pre_b})
+
+
+def conv_name(rec):
+    """The kernel instantiation the library launches for the record (vse_op_kernel_name: no GPU), e.g. "conv_col_kernel<9, 64>"."""
+    from vse_amd import engine
+    return engine.op_kernel_names(np.ascontiguousarray(rec).reshape(-1)[:1])[0]
+
+
+def _rup(x, m):
+    return (x + m - 1) // m * m
+
+
+CONV_FAMILY_FLAGS = {"tile64": 0, "tile32": ir.F_WK32, "pw": ir.F_PW, "stem": ir.F_STEM, "patch": ir.F_PATCH, "col": ir.F_COL,
+                     "hlsum": ir.F_COL | ir.F_HLSUM, "head": ir.F_PATCH | ir.F_SRC2 | ir.F_DOT1 | ir.F_UP2HEAD}
+
+
+def conv_pack(family, w, kh, kw, cinp, hilo=False, ptaps=0):
+    """The weight stream of one conv record, by the compiler's own packers.  w: float64 [Np][kh * kw * cinp], K in (tap, channel) order (a
+    hi + lo stream is split by the packer: hi = fp16(w), lo = fp16(w - hi)).  family: tile64 / tile32 ([Kp / kt][Np][kt]: conv_gemm,
+    conv_smallm, conv_mfma), pw ([Np][cinp -> 16]), stem, patch (ptaps = taps padded to whole kernel steps), col (conv_col, conv_c3),
+    hlsum (conv_c3 [hi 32 | lo 32]), head (conv_head_up2).  -> (the stream, P_KTOT)."""
+    Cm = compiler.Compiler
+    w = np.asarray(w, np.float64)
+    npad, K = w.shape
+    assert K == kh * kw * cinp, (K, kh, kw, cinp)
+
+    def padded(kp):
+        m = np.zeros((npad, kp), np.float64)
+        m[:, :K] = w
+        return m
+    if family in ("tile64", "tile32"):
+        kp = _rup(K, ir.KT)
+        return Cm.tile_weights(padded(kp), 32 if family == "tile32" else ir.KT, hilo=hilo).reshape(-1), kp
+    if family == "pw":
+        assert (kh, kw) == (1, 1)
+        kp = _rup(cinp, 16)
+        return Cm.pw_weights(padded(kp), hilo), kp
+    if family == "stem":
+        return Cm.stem_weights(padded(128), hilo), 128
+    if family == "patch":
+        assert not hilo and ptaps >= kh * kw
+        return Cm.patch_weights(padded(_rup(K, ir.KT)), kh, kw, cinp, ptaps), ptaps * _rup(cinp, 32)
+    if family == "col":
+        return Cm.col_weights(w, kh, kw, cinp, hilo), K
+    if family == "hlsum":
+        return Cm.hlsum_weights(w, kh, kw, cinp), K
+    if family == "head":
+        return Cm.head_up2_weights(w, cinp), 2 * 4 * 4 * 32 + 32
+    raise ValueError(family)
+
+
+def conv_seen_weights(w, hilo):
+    """The matrix a kernel sees of the float64 matrix handed to conv_pack: fp16(w), or hi + lo summed in float64."""
+    w = np.asarray(w, np.float64)
+    hi = w.astype(np.float16).astype(np.float64)
+    return hi + (w - hi).astype(np.float16).astype(np.float64) if hilo else hi
+
+
+def _up(t, shift):
+    return t if not shift else np.repeat(np.repeat(t, 1 << shift, axis=1), 1 << shift, axis=2)
+
+
+def _matmul(a, w, dt, seq):
+    """a [..., K] x w [N, K] -> [..., N] in dt; seq: strictly sequential over 16-channel chunks."""
+    if not seq:
+        return np.matmul(a, w.T)
+    acc = np.zeros(a.shape[:-1] + (w.shape[0],), dt)
+    for c0 in range(0, a.shape[-1], 16):
+        acc = acc + np.matmul(a[..., c0:c0 + 16], w[:, c0:c0 + 16].T)
+    return acc
+
+
+def ref_conv(x, w, bias, k, s, pad, dt=np.float64, seq=False, x2=None, inshift=0, in2shift=0, act=ir.ACT_NONE, act_a=0.0, act_b=0.0,
+             post_a=1.0, post_b=0.0, gate=None, pixshuf=False, res=None, resshift=0, act2=ir.ACT_NONE, wl_out=None, dot=None, tail2=None,
+             dwpre=None, wimg=None):
+    """The whole OP_CONV record, plainly.  x [n,h,w,c] (a pair tensor: hi + lo summed), x2 = the second source of a virtual concat, each read
+    through its own nearest-neighbour shift; w [Np][kh * kw * cinp] = the matrix the kernel sees (conv_seen_weights), K in (tap, channel)
+    order — wimg [n][Np][cinp]: one matrix per image (F_IMGW); bias fp32 [Np].  In the record's order: gather, (dwpre = (wd [c][k*k], shift
+    [c], act, act_a, act_b, post_a, post_b): the depthwise conv of F_DWPRE in front, whose geometry k / s / pad then is), conv, bias, act,
+    affine, (1 + gate [n, Np]), pixel-shuffle scatter (Np = 4 x couts in (dy, dx, co) order), residual (hi + lo summed, read through
+    resshift), act2, zeros right of wl_out[n]; then dot = (weights fp32 [Np], bias, act): -> the 1-channel projection [n,oh,ow,1] alone
+    (F_DOT1), or tail2 = (w2 [c1][2][2], bias, act): -> (y, the second 2x2 s2 transposed conv over fp16(y) [n,4h,4w,1]).
+    seq: the accumulation runs strictly sequentially over taps and 16-channel chunks (the second float32 evaluation of e32)."""
+    (kh, kw), (sh, sw), (ph, pw) = k, s, pad
+    f32 = lambda v: dt(np.float32(v))          # noqa: E731
+    x = _up(np.asarray(x).astype(dt), inshift)
+    if x2 is not None:
+        x = np.concatenate([x, _up(np.asarray(x2).astype(dt), in2shift)], axis=3)
+    if dwpre is not None:
+        wd, dshift, dact, da, db, dpa, dpb = dwpre
+        d = ref_dwconv(x, np.asarray(wd).T, np.asarray(dshift), k, s, pad, dact, da, db, dpa, dpb, dt=dt)
+        x, (kh, kw), (sh, sw), (ph, pw) = d, (1, 1), (1, 1), (0, 0)
+    n, h, wd_, c = x.shape
+    oh, ow = (h + 2 * ph - kh) // sh + 1, (wd_ + 2 * pw - kw) // sw + 1
+    xp = np.zeros((n, h + 2 * ph + sh, wd_ + 2 * pw + sw, c), dt)
+    xp[:, ph:ph + h, pw:pw + wd_] = x
+    if wimg is not None:
+        wi = np.asarray(wimg).astype(dt)
+        acc = np.stack([_matmul(xp[b:b + 1, :oh, :ow], wi[b], dt, seq)[0] for b in range(n)])
+        npad = wi.shape[1]
+    else:
+        w = np.asarray(w).astype(dt)
+        npad = w.shape[0]
+        assert w.shape[1] == kh * kw * c, (w.shape, kh, kw, c)
+        acc = np.zeros((n, oh, ow, npad), dt)
+        for dy in range(kh):
+            for dx in range(kw):
+                t = dy * kw + dx
+                acc = acc + _matmul(xp[:, dy:dy + sh * oh:sh, dx:dx + sw * ow:sw][:, :oh, :ow], w[:, t * c:(t + 1) * c], dt, seq)
+    y = acc + np.asarray(bias).astype(dt)
+    y = ref_act(y, act, act_a, act_b) * f32(post_a) + f32(post_b)
+    if gate is not None:
+        y = y * (dt(1) + np.asarray(gate).astype(dt)[:, None, None, :npad])
+    if pixshuf:
+        cp = npad // 4
+        y = y.reshape(n, oh, ow, 2, 2, cp).transpose(0, 1, 3, 2, 4, 5).reshape(n, 2 * oh, 2 * ow, cp)
+    if res is not None:
+        r = _up(np.asarray(res).astype(dt), resshift)[:, :y.shape[1], :y.shape[2]]
+        y = y.copy()
+        y[..., :r.shape[3]] += r[..., :y.shape[3]]
+    y = ref_act(y, act2)
+    y = mask_width(y, wl_out)
+    if dot is not None:
+        dw, dbias, dact = dot
+        z = (y * np.asarray(dw).astype(dt)).sum(-1, keepdims=True, dtype=dt) + f32(dbias)
+        return ref_act(z, dact)
+    if tail2 is not None:
+        return y, ref_tail2(y.astype(np.float16), *tail2, dt=dt)
+    return y
+
+
+def ref_tail2(y16, w2, bias, act, dt=np.float64):
+    """Stage B of F_TAIL2 on the fp16 values stage A stored: y16 [n,h,w,c1], w2 [c1][2][2] -> [n,2h,2w,1]."""
+    n, h, w, c1 = y16.shape
+    z = np.einsum("nhwc,cyx->nhywx", y16.astype(dt), np.asarray(w2).astype(dt)[:c1]).reshape(n, 2 * h, 2 * w, 1).astype(dt)
+    return ref_act(z + dt(np.float32(bias)), act)
+
+
+def conv_reference(fn):
+    """reference() for a conv: fn(dtype, seq) -> array or tuple; e32 = the larger of the library float32 evaluation and the strictly
+    sequential one (over taps and 16-channel chunks), each against float64.  -> (float64 results, e32 per result)."""
+    r64, e_lib = reference(lambda dt: fn(dt, False))
+    _, e_seq = reference(lambda dt: fn(dt, True) if dt == np.float32 else tuple(r64) if len(r64) > 1 else r64[0])
+    return r64, tuple(max(a, b) for a, b in zip(e_lib, e_seq))

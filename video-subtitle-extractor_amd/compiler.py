@@ -1081,6 +1081,49 @@ class Compiler(ChainMixin):
         return np.concatenate(parts + [np.zeros(3 * kh * npad * 16 + 512, np.float16)])
 
     @staticmethod
+    def hlsum_weights(mat, kh, kw, cinp):
+        """[Np <= 32][Kp] -> conv_c3_kernel's F_HLSUM stream: col_weights of 64 rows [hi 32 | lo 32], hi = fp16(w), lo = w - hi (ONE pass
+        over K; the kernel adds the two 32-cout accumulator tiles)."""
+        ktot = kh * kw * cinp
+        m = np.zeros((32, ktot), np.float64)
+        m[:mat.shape[0]] = mat[:, :ktot]
+        hi = m.astype(np.float16).astype(np.float64)
+        return Compiler.col_weights(np.concatenate([hi, m - hi]), kh, kw, cinp, False)
+
+    @staticmethod
+    def tail2_fragments(w2, coutp):
+        """F_TAIL2, stage B: w2 [c1][2][2] (the second 2x2 s2 transposed conv c1 -> 1, its scale folded) -> the MFMA A fragments
+        [4 coutp / 16][2][16][8] fp16 of a block-diagonal 1x1 conv over stage A's 4 coutp channels (dy, dx, co) -> 16 outputs 4 r + c
+        = pixel (4 y + r, 4 x + c) of the map, r = 2 dy + ey, c = 2 dx + ex."""
+        cout = w2.shape[0]
+        wb = np.zeros((16, 4 * coutp), np.float64)
+        for r in range(4):
+            for c in range(4):
+                q = ((r >> 1) * 2 + (c >> 1)) * coutp
+                wb[4 * r + c, q:q + cout] = w2[:, r & 1, c & 1]
+        fx = np.arange(16)
+        rows = (fx & ~12) | ((fx & 4) << 1) | ((fx & 8) >> 1)           # conv_wrow: the cout row MFMA row fx carries
+        nks2 = 4 * coutp // 16
+        frag = np.zeros((nks2, 2, 16, 8), np.float16)
+        for s_ in range(nks2):
+            for fj in range(2):
+                frag[s_, fj] = wb[rows][:, s_ * 16 + fj * 8:s_ * 16 + fj * 8 + 8].astype(np.float16)
+        return frag.reshape(-1)
+
+    @staticmethod
+    def dwpre_table(wd, shift, cp, k, s, pad, act, act_a=0.0, act_b=0.0, post_a=1.0, post_b=0.0):
+        """F_DWPRE aux blob: wd [c][k*k] (the depthwise filter, BN / affine folded), shift [c] -> 8 header words [k, s, pad, act (int32),
+        act_a, act_b, post_a, post_b] + the table [k*k + 1][cp] fp32 (last row = bias)."""
+        c, k2 = wd.shape
+        tab = np.zeros((k2 + 1, cp), np.float32)
+        tab[:k2, :c] = wd.T
+        tab[k2, :c] = shift
+        hdr = np.zeros(8, np.float32)
+        hdr.view(np.int32)[:4] = [k, s, pad, act]
+        hdr[4:] = [act_a, act_b, post_a, post_b]
+        return np.concatenate([hdr, tab.reshape(-1)])
+
+    @staticmethod
     def head_up2_weights(mat, cinp):
         """3x3 conv over concat[u (8 physical channels, 1 real), up2(x) (64 channels)], matrix [Np][9*cinp] in
         (tap, channel) order -> the stream of conv_head_up2_kernel:
@@ -1146,18 +1189,14 @@ class Compiler(ChainMixin):
         ident = (wname, tuple(inv.segs), ep["out_name"])
         mat = lambda: self.pack_conv_weights(w, ep["scale"], inv)[0]          # noqa: E731
 
-        def hlsum():       # 64 rows: [hi 32 | lo 32]
-            m = np.zeros((32, r.ktot), np.float64)
-            m[:rup(w.shape[0], 8)] = mat()[:, :r.ktot]
-            hi = m.astype(np.float16).astype(np.float64)
-            return self.col_weights(np.concatenate([hi, m - hi]), kh, kw, span, False)
         col = (("convc",) + ident + (hilo,), lambda: self.col_weights(mat(), kh, kw, span, hilo))
         # (the tap padding depends on the kernel variant the map size selects: part of the cache key)
         patch = (("convp",) + ident + (r.ptaps,), lambda: self.patch_weights(mat(), kh, kw, span, r.ptaps))
         tiles = (("conv",) + ident + (wk32, hilo), lambda: self.tile_weights(mat(), 32 if wk32 else ir.KT, hilo=hilo))
         return {"head": (("convh",) + ident, lambda: self.head_up2_weights(mat(), span)),
                 "pw": (("convpw",) + ident + (hilo,), lambda: self.pw_weights(mat()[:, :r.ktot], hilo)),
-                "c3_hlsum": (("convc_hl",) + ident, hlsum), "c3": col, "col": col, "patch_light": patch, "patch_std": patch,
+                "c3_hlsum": (("convc_hl",) + ident, lambda: self.hlsum_weights(mat(), kh, kw, span)), "c3": col, "col": col,
+                "patch_light": patch, "patch_std": patch,
                 "stem": (("convs",) + ident + (hilo,), lambda: self.stem_weights(mat(), hilo)),
                 "gemm_wk32": tiles, "generic": tiles}[r.family]
 
@@ -1336,19 +1375,7 @@ class Compiler(ChainMixin):
             # = a block-diagonal 1x1 conv over this op's 4 coutp channels (dy, dx, co) -> 16 outputs 4 r + c = pixel (4 y + r, 4 x + c)
             # of the map, r = 2 dy + ey, c = 2 dx + ex; its fp16 weights are the separate launch's (w2 * scale2 rounded once)
             ep2, w2 = tail["ep"], tail["w"].astype(np.float64) * float(tail["ep"]["scale"][0])
-            wb = np.zeros((16, 4 * coutp), np.float64)
-            for r in range(4):
-                for c in range(4):
-                    q = ((r >> 1) * 2 + (c >> 1)) * coutp
-                    wb[4 * r + c, q:q + cout] = w2[:, 0, r & 1, c & 1]
-            fx = np.arange(16)
-            rows = (fx & ~12) | ((fx & 4) << 1) | ((fx & 8) >> 1)           # conv_wrow: the cout row MFMA row fx carries
-            nks2 = 4 * coutp // 16
-            frag = np.zeros((nks2, 2, 16, 8), np.float16)
-            for s_ in range(nks2):
-                for fj in range(2):
-                    frag[s_, fj] = wb[rows][:, s_ * 16 + fj * 8:s_ * 16 + fj * 8 + 8].astype(np.float16)
-            aux_off = self.add_weights(("convTtail", wname, tail["wname"], ep2["out_name"]), frag.reshape(-1))
+            aux_off = self.add_weights(("convTtail", wname, tail["wname"], ep2["out_name"]), self.tail2_fragments(w2[:, 0], coutp))
             ub = self.new_buf(inv.n, 2 * oh, 2 * ow, 1, esize=2)
             out2 = View(ub, 0, inv.n, 2 * oh, 2 * ow, [(0, 1)], 8, dense1=True)
             tflags |= ir.F_TAIL2
@@ -1495,16 +1522,12 @@ class Compiler(ChainMixin):
         bias[:cout] = ep["shift"]
         # the depthwise table: [k*k + 1][Kp] fp32 (BN / affine folded; last row = bias), behind 8 header words
         k2 = kh * kw
-        tab = np.zeros((k2 + 1, cp), np.float32)
-        tab[:k2, :c] = (w.astype(np.float64)[:, 0] * ep_d["scale"].reshape(-1, 1, 1)).reshape(c, k2).T
-        tab[k2, :c] = ep_d["shift"]
-        hdr = np.zeros(8, np.float32)
-        hdr.view(np.int32)[:4] = [kh, sh, ph, ep_d["act"]]
-        hdr[4:] = [ep_d["act_a"], ep_d["act_b"], ep_d["post_a"], ep_d["post_b"]]
+        wd = (w.astype(np.float64)[:, 0] * ep_d["scale"].reshape(-1, 1, 1)).reshape(c, k2)
         wname, dwname = o2["in"]["Filter"][0], op["in"]["Filter"][0]
         w_off = self.add_weights(("dwpw_w", wname, ep["out_name"]), lambda: self.pw_weights(mat, True))
         b_off = self.add_weights(("dwpw_b", wname, ep["out_name"]), bias)
-        aux_off = self.add_weights(("dwpw_t", dwname, dname), np.concatenate([hdr, tab.reshape(-1)]))
+        aux_off = self.add_weights(("dwpw_t", dwname, dname), self.dwpre_table(wd, ep_d["shift"], cp, kh, sh, ph, ep_d["act"], ep_d["act_a"],
+                                                                               ep_d["act_b"], ep_d["post_a"], ep_d["post_b"]))
         out = self.alloc_out(ep["out_name"], inv.n, oh, ow, cout, lo=self.wants_lo(ep["out_name"]))
         flags = ir.F_PW | ir.F_HILO | ir.F_DWPRE
         ins = [inv]
