@@ -208,6 +208,32 @@ int vse_ctc_collapse(vse_ctx* ctx, const void* d_idx_maxp, int b, int t, int32_t
 int vse_ctc_collapse_ragged(vse_ctx* ctx, const void* d_idx_maxp, int b, int t, const int32_t* d_tlen, int32_t* d_out_idx,
                             int32_t* d_out_len, float* d_out_conf, void* stream);
 
+/* ---- CTC posterior fusion over the frames of one subtitle ------------------------------------------------------------------ */
+/* Replaces: nothing the reference computes itself; the role is VideoSubFinder's (the closed binary run by backend/main.py:378-505),
+ * which reads each subtitle from all of its frames, where the reference's own loop recognises ONE frame per subtitle
+ * (backend/tools/ocr.py:27) and a recognition error on that frame is final.  A subtitle stands still, so the same quad cut from K
+ * frames of its interval gives K crops of one geometry, the same number of time steps and the same alignment: the recogniser's
+ * per-step class probabilities are averaged before the arg-max and the result decodes with vse_ctc_collapse_ragged like any other
+ * row (vse_amd.pipeline.OcrPipeline.recognize_fused).  What that gains on real footage is not measured here (no real clips, stand-in
+ * recogniser weights).
+ * d_probs: [b, t] rows of ncls fp32 probabilities, the `probs` output of a recogniser plan; row (r, s) starts (r * t + s) * row_stride
+ * floats behind d_probs, row_stride >= ncls.  d_group (device, [g + 1]): ascending row offsets, group j = rows d_group[j] ..
+ * d_group[j + 1] - 1.  d_tlen (device, [g]) = the sequence length of each group, or NULL = t for every group.  For group j with member
+ * rows r0 < r1 < .. < r(K-1), 1 <= K <= 64, and every step s < tlen[j], all in float32, every operation rounded on its own:
+ *   acc[c] = p[r0][s][c], then acc[c] = acc[c] + p[rk][s][c] for k = 1 .. K - 1 in that order;
+ *   m[c] = acc[c] / (float)K                                     (a correctly rounded divide; no fused multiply-add anywhere)
+ *   idx = the smallest c whose m[c] is the largest, maxp = m[idx];
+ * d_idx_maxp[j][s] = {idx, maxp} as int32 / fp32 pairs [g, t, 2], the layout vse_ctc_collapse_ragged takes.  Steps s >= tlen[j] get
+ * {0, 0.0f}, and what their probability rows hold is never read.  K = 1 copies a row's arg-max and its probability.
+ * One launch on `stream`, no allocation, no device sync.  The library cannot check a device table: the kernel clamps every member row
+ * into 0 .. b - 1, K into 1 .. 64 and tlen into 0 .. t, so a wrong table gives wrong text and never an out-of-range access.  No
+ * alignment beyond the floats' own is required; steps whose member rows all start on a 16-byte boundary take 16-byte loads.
+ * Returns VSE_E_INVAL, and launches nothing, for a NULL pointer other than d_tlen, b, t, ncls or g < 1, row_stride < ncls,
+ * ncls > 2^30, or g * t >= 2^24 (one 256-thread block per group and step). */
+int vse_ctc_fuse(vse_ctx* ctx, const float* d_probs, int b, int t, int ncls, int64_t row_stride /* floats between (row, step) rows, >= ncls */,
+                 const int32_t* d_group /* device, [g + 1], ascending row offsets, group j = rows d_group[j] .. d_group[j+1] - 1 */, int g,
+                 const int32_t* d_tlen /* device, [g], or NULL = t for every group */, void* d_idx_maxp /* [g, t, 2] int32 / fp32 pairs */, void* stream);
+
 /* ---- subtitle-change frame selector ----------------------------------------------------------------------------------- */
 /* Replaces: VideoSubFinder's frame search (the closed binary run by backend/main.py:378-505, extract_frame_by_vsf), which looks at
  * every frame of the subtitle area and reports where each subtitle starts and stops.  Here the device part: per frame, the

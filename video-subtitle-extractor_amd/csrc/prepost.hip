@@ -740,3 +740,140 @@ extern "C" int vse_ctc_collapse(vse_ctx* c, const void* d_idx_maxp, int b, int t
                                 float* d_out_conf, void* stream) {
     return vse_ctc_collapse_ragged(c, d_idx_maxp, b, t, nullptr, d_out_idx, d_out_len, d_out_conf, stream);
 }
+
+// ================================================================================================ CTC posterior fusion
+// vse_ctc_fuse (include/vse_hip.h): the per-step class probabilities of the K member rows of a group (the same text line cut from K
+// frames of one subtitle interval) are averaged before the arg-max, in float32 and in member order, so that the output decodes with
+// ctc_collapse_kernel like any other row.  tests/ctc_fuse_ref.py restates the arithmetic in numpy, bit for bit.
+// One 256-thread block per (group, step).  The accumulators of a chunk of NV * 1024 classes stay in registers (6625 classes: NV = 7,
+// 26 of the 28 slots used) while the members are walked outermost with the next member's loads issued before the current one is added;
+// larger dictionaries loop over chunks.  HBM-bound: every probability is read once, eight bytes per (group, step) are written.
+// Two class -> (thread, slot) maps, chosen per block (uniform):
+//   wide     every member row of this step starts on a 16-byte boundary (base, row_stride and the row index allow it): slot (k, e) of
+//            thread i holds class 4 (256 k + i) + e of the chunk, one 16-byte load per k; the ncls % 4 classes behind the last whole
+//            vector ride in one more slot of threads 0 .. 2.
+//   general  any row: slot (k, e) holds class 256 (4 k + e) + i, dword loads, consecutive lanes consecutive classes.
+// Dictionaries have odd sizes (6625, 97), so with row_stride = ncls one step in four is wide.  Loads are unconditional with clamped
+// indices (all of a member's loads in flight at once); what a clamped slot accumulates is never looked at.
+// A malformed table cannot reach memory outside d_probs: member rows are clamped into 0 .. b - 1, K into 1 .. CF_MAXK, tlen into 0 .. t.
+#define CF_MAXK 64
+
+template <bool WIDE, int NV>
+struct CfVals {
+    float v[NV][4];
+    float tail;
+};
+
+template <bool WIDE, int NV>
+__device__ __forceinline__ void cf_load(CfVals<WIDE, NV>& x, const float* __restrict__ row, int cb, int ncls) {
+    const int tid = threadIdx.x;
+    if (WIDE) {
+        const int nfull = ncls >> 2;                                              // whole 16-byte vectors of a row (>= 1 here)
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            const float4v q = *reinterpret_cast<const float4v*>(row + 4 * (long)min((cb >> 2) + k * 256 + tid, nfull - 1));
+            x.v[k][0] = q[0]; x.v[k][1] = q[1]; x.v[k][2] = q[2]; x.v[k][3] = q[3];
+        }
+        x.tail = row[min(4 * nfull + tid, ncls - 1)];
+    } else {
+#pragma unroll
+        for (int k = 0; k < NV; ++k)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x.v[k][e] = row[min(cb + (4 * k + e) * 256 + tid, ncls - 1)];
+        x.tail = 0.f;
+    }
+}
+
+template <bool WIDE, int NV>
+__device__ __forceinline__ void cf_add(CfVals<WIDE, NV>& a, const CfVals<WIDE, NV>& x) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a.v[k][e] = __fadd_rn(a.v[k][e], x.v[k][e]);
+    if (WIDE) a.tail = __fadd_rn(a.tail, x.tail);
+}
+
+__device__ __forceinline__ int cf_row(int r0, int k, int b) { return r0 + min(k, b - 1 - r0); }     // member k of a group that starts at row r0
+
+__device__ __forceinline__ void cf_best(float m, int c, float& mx, int& mi) {
+    if (m > mx || (m == mx && c < mi)) { mx = m; mi = c; }
+}
+
+// -> this thread's largest mean and its smallest class index over all chunks.  p0 = step s of row 0; member k is row cf_row(r0, k, b).
+template <bool WIDE, int NV>
+__device__ __forceinline__ void cf_scan(const float* __restrict__ p0, long row_floats, int r0, int K, int b, int ncls, float& mx, int& mi) {
+    const int tid = threadIdx.x;
+    const float fk = (float)K;
+    for (int cb = 0; cb < ncls; cb += NV * 1024) {
+        CfVals<WIDE, NV> acc, nxt;
+        cf_load<WIDE, NV>(acc, p0 + (long)r0 * row_floats, cb, ncls);
+        if (K > 1) cf_load<WIDE, NV>(nxt, p0 + (long)cf_row(r0, 1, b) * row_floats, cb, ncls);
+        for (int k = 1; k < K; ++k) {
+            const CfVals<WIDE, NV> cur = nxt;
+            if (k + 1 < K) cf_load<WIDE, NV>(nxt, p0 + (long)cf_row(r0, k + 1, b) * row_floats, cb, ncls);
+            cf_add<WIDE, NV>(acc, cur);
+        }
+#pragma unroll
+        for (int k = 0; k < NV; ++k)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int c = WIDE ? cb + 4 * (k * 256 + tid) + e : cb + (4 * k + e) * 256 + tid;
+                const bool in = WIDE ? (c >> 2) < (ncls >> 2) : c < ncls;
+                if (in) cf_best(__fdiv_rn(acc.v[k][e], fk), c, mx, mi);
+            }
+        if (WIDE && (ncls & ~3) + tid < ncls) cf_best(__fdiv_rn(acc.tail, fk), (ncls & ~3) + tid, mx, mi);
+    }
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void ctc_fuse_kernel(const float* __restrict__ probs, int b, int t, int ncls, long row_stride,
+                                                       const int* __restrict__ group, const int* __restrict__ tlen, int2* __restrict__ out,
+                                                       int base_wide) {
+    __shared__ float smax[4];
+    __shared__ int sidx[4];
+    const int j = blockIdx.x / t, s = blockIdx.x - j * t;
+    const int len = tlen != nullptr ? min(max(tlen[j], 0), t) : t;
+    if (s >= len) {                                                               // (uniform) behind the group's sequence: nothing is read
+        if (threadIdx.x == 0) out[blockIdx.x] = make_int2(0, __float_as_int(0.f));
+        return;
+    }
+    const long g0 = group[j], g1 = group[j + 1];
+    const int r0 = (int)min(max(g0, 0L), (long)b - 1);
+    const int K = (int)min(max(g1 - g0, 1L), (long)CF_MAXK);
+    const long row_floats = (long)t * row_stride;                                 // floats between the same step of consecutive rows
+    const float* p0 = probs + (long)s * row_stride;
+    bool wide = base_wide != 0;                                                   // base 16-byte aligned and ncls >= 4; now every member's row
+    for (int k = 0; k < K; ++k) wide = wide && ((((long)cf_row(r0, k, b) * t + s) * row_stride) & 3) == 0;
+    float mx = -INFINITY;
+    int mi = 0x7fffffff;
+    if (wide) cf_scan<true, NV>(p0, row_floats, r0, K, b, ncls, mx, mi);
+    else cf_scan<false, NV>(p0, row_floats, r0, K, b, ncls, mx, mi);
+    // the block reduction of softmax_kernel: the larger value, then the smaller index
+    for (int o = 32; o >= 1; o >>= 1) {
+        const float om = __shfl_xor(mx, o);
+        const int oi = __shfl_xor(mi, o);
+        if (om > mx || (om == mx && oi < mi)) { mx = om; mi = oi; }
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { smax[wave] = mx; sidx[wave] = mi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        mx = smax[0]; mi = sidx[0];
+        for (int q = 1; q < 4; ++q)
+            if (smax[q] > mx || (smax[q] == mx && sidx[q] < mi)) { mx = smax[q]; mi = sidx[q]; }
+        out[blockIdx.x] = make_int2(mi < ncls ? mi : 0, __float_as_int(mx));      // (mi stays unset only when every mean is a NaN)
+    }
+}
+
+int vse_ctc_fuse_launch(const float* d_probs, int b, int t, int ncls, int64_t row_stride, const int32_t* d_group, int g, const int32_t* d_tlen,
+                        void* d_idx_maxp, void* stream) {
+    const dim3 grid((unsigned)((long)g * t)), block(256);
+    const int base_wide = (reinterpret_cast<uintptr_t>(d_probs) & 15) == 0 && ncls >= 4;
+    const int nvt = (ncls + 1023) / 1024;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define VSE_CF_LAUNCH(NV) hipLaunchKernelGGL((ctc_fuse_kernel<NV>), grid, block, 0, st, d_probs, b, t, ncls, (long)row_stride, d_group, d_tlen, \
+                                             reinterpret_cast<int2*>(d_idx_maxp), base_wide)
+    if (nvt <= 1) VSE_CF_LAUNCH(1); else if (nvt <= 2) VSE_CF_LAUNCH(2); else if (nvt <= 4) VSE_CF_LAUNCH(4); else VSE_CF_LAUNCH(7);
+#undef VSE_CF_LAUNCH
+    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+}

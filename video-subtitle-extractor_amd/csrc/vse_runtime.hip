@@ -48,6 +48,8 @@ struct vse_plan {
     long src_pitch, src_fstride;
 };
 
+int vse_ctc_fuse_launch(const float* d_probs, int b, int t, int ncls, int64_t row_stride, const int32_t* d_group, int g, const int32_t* d_tlen,
+                        void* d_idx_maxp, void* stream);                                                               // prepost.hip
 int vse_frame_change_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
                             void* d_state, int reset, int32_t* d_counts, void* stream);     // frame_change.hip
 int vse_frame_cells_state_words();                                                                                     // frame_change.hip
@@ -398,6 +400,20 @@ void vse_graph_destroy(vse_graph* g) {
     if (g->exec) (void)hipGraphExecDestroy(g->exec);
     if (g->graph) (void)hipGraphDestroy(g->graph);
     delete g;
+}
+
+// ---- CTC posterior fusion (prepost.hip) --------------------------------------------------------------------------------------
+int vse_ctc_fuse(vse_ctx* c, const float* d_probs, int b, int t, int ncls, int64_t row_stride, const int32_t* d_group, int g,
+                 const int32_t* d_tlen, void* d_idx_maxp, void* stream) {
+    if (!c || !d_probs || !d_group || !d_idx_maxp || b < 1 || t < 1 || ncls < 1 || g < 1 || row_stride < ncls ||
+        ncls > (1 << 30) || (int64_t)g * t >= (1 << 24) || (reinterpret_cast<uintptr_t>(d_probs) & 3)) {
+        set_err("vse_ctc_fuse: bad arguments (b %d, t %d, ncls %d, g %d: all >= 1, ncls <= 2^30, g * t < 2^24; row stride %lld >= ncls; non-NULL "
+                "4-byte aligned probabilities, group table and output)", b, t, ncls, g, (long long)row_stride);
+        return VSE_E_INVAL;
+    }
+    const int rc = vse_ctc_fuse_launch(d_probs, b, t, ncls, row_stride, d_group, g, d_tlen, d_idx_maxp, stream);
+    if (rc != VSE_OK) set_err("vse_ctc_fuse: launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
 }
 
 // ---- subtitle-change frame selector (frame_change.hip) ---------------------------------------------------------------------

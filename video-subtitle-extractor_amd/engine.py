@@ -24,7 +24,7 @@ EXPORTS = [
     "vse_audio_match_workspace_bytes", "vse_audio_match", "vse_scene_change_state_bytes", "vse_scene_change_workspace_bytes",
     "vse_scene_change", "vse_frame_cells_dims", "vse_frame_cells_state_bytes", "vse_frame_cells",
     "vse_interval_state_bytes", "vse_interval_accumulate", "vse_interval_composite", "vse_frame_hold_state_bytes", "vse_frame_hold",
-    "vse_audio_stream_length", "vse_audio_stream_workspace_bytes", "vse_audio_stream_feed", "vse_audio_stream_finish",
+    "vse_audio_stream_length", "vse_audio_stream_workspace_bytes", "vse_audio_stream_feed", "vse_audio_stream_finish", "vse_ctc_fuse",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -133,6 +133,8 @@ def load_library(path=None):
                                      C.c_void_p]
     lib.vse_ctc_collapse_ragged.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p]
+    lib.vse_ctc_fuse.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                 C.c_void_p]
     lib.vse_frame_change_state_bytes.restype = C.c_size_t
     lib.vse_frame_change_state_bytes.argtypes = [C.c_int, C.c_int]
     lib.vse_frame_change.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
@@ -389,6 +391,51 @@ class Context:
                                                 C.c_void_p(oi.data_ptr()), C.c_void_p(ol.data_ptr()),
                                                 C.c_void_p(oc.data_ptr()), self.stream()), "vse_ctc_collapse")
         return oi, ol, oc
+
+    def _upload_i32(self, tab):
+        """Stream-ordered upload of a small int32 host table through a ring of pinned buffers, as Net._upload_i32 does for the width
+        tables (a pageable copy would stall the host behind the recogniser launches queued on the stream)."""
+        t = self.torch
+        ring = self.__dict__.setdefault("_pin_ring", {"slots": [None] * 8, "next": 0})
+        i = ring["next"] % len(ring["slots"])
+        ring["next"] += 1
+        slot = ring["slots"][i]
+        if slot is not None:
+            slot[1].synchronize()             # the copy that last read this slot (8 uploads ago) has long finished
+        if slot is None or slot[0].numel() < tab.size:
+            slot = ring["slots"][i] = (t.empty(max(int(tab.size), 1024), dtype=t.int32).pin_memory(), t.cuda.Event())
+        pin = slot[0][:tab.size]
+        pin.numpy()[...] = tab
+        dev = t.empty(tab.shape, dtype=t.int32, device=self.tdev)
+        dev.copy_(pin, non_blocking=True)
+        slot[1].record(t.cuda.current_stream(self.tdev))
+        return dev
+
+    CTC_FUSE_MAX = 64         # member rows per group of ctc_fuse (include/vse_hip.h vse_ctc_fuse)
+
+    def ctc_fuse(self, probs, group, tlen=None):
+        """probs: cuda float32 [B,1,T,ncls], the probability output of a recogniser net built with want_probs=True (its last dimension
+        may be a view with a larger stride); group: host sequence of g + 1 row offsets, strictly ascending inside 0 .. B, group j =
+        rows group[j] .. group[j + 1] - 1, at most 64 of them; tlen: cuda int32 [g] sequence length per group (None: T) ->
+        idx_maxp cuda float32 [g,1,T,2] as ctc_collapse takes it: per step the arg-max and the value of the members' mean probabilities
+        (include/vse_hip.h vse_ctc_fuse).  The table is uploaded on the current stream."""
+        t = self.torch
+        assert probs.dtype == t.float32 and probs.dim() == 4 and probs.shape[1] == 1 and probs.stride(3) == 1, (probs.dtype, tuple(probs.shape))
+        b, _, tt, ncls = probs.shape
+        stride = probs.stride(2) if tt > 1 else max(probs.stride(2), ncls)
+        assert b < 2 or probs.stride(0) == tt * stride, "the (row, step) rows of probs must be evenly spaced"
+        tab = np.asarray(group, dtype=np.int64).reshape(-1)
+        g = tab.size - 1
+        if g < 1 or tab[0] < 0 or tab[-1] > b or np.any(np.diff(tab) < 1) or np.any(np.diff(tab) > self.CTC_FUSE_MAX):
+            raise VseError(f"ctc_fuse: group offsets {tab.tolist()} must ascend strictly inside 0 .. {b} in steps of at most {self.CTC_FUSE_MAX}")
+        if tlen is not None:
+            assert tlen.dtype == t.int32 and tlen.is_contiguous() and tlen.numel() == g
+        dev = self._upload_i32(tab.astype(np.int32))
+        out = t.empty((g, 1, tt, 2), dtype=t.float32, device=self.tdev)
+        _check(self.lib.vse_ctc_fuse(self.handle, C.c_void_p(probs.data_ptr()), b, tt, ncls, stride, C.c_void_p(dev.data_ptr()), g,
+                                     C.c_void_p(tlen.data_ptr()) if tlen is not None else None, C.c_void_p(out.data_ptr()), self.stream()),
+               "vse_ctc_fuse")
+        return out
 
     # ---- subtitle-change frame selector -------------------------------------------------------------------------
     def frame_change_state(self, area_h, area_w):

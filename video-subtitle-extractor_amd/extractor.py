@@ -223,6 +223,12 @@ class SubtitleExtractor:
     text) / maximum (dark text) / mean of ALL frames of the interval, one more pass over the area's rows on the device
     (frame_select.IntervalCompositor, `composite_params` its keyword arguments); the pictures are kept as `interval_patches`.
     Intervals and SRT times are untouched.  What it gains on real footage is not measured here.
+    interval_text="fused" (change / hold selector with interval_image="middle" only; default "single", the above): the other answer to
+    that single frame, in probability space: up to `samples` frames of each interval go through the recogniser, the boxes detected
+    once on the sample nearest to the middle frame, and the recogniser's per-step class probabilities are averaged on the device before
+    the CTC decode (frame_select.IntervalFuser, `fuse_params` its keyword arguments; fuse_fn defaults to ocr.predict_fused).  Each
+    task then carries its interval's (dt_box, rec_res), kept as `interval_results`, and is not recognised again.  It needs no knowledge
+    of the text's polarity; the recogniser runs once per sample.  What it gains on real footage is not measured here either.
     sub_area="auto": nobody drew a box, so run() first looks for the subtitle band itself, one more pass over the clip's frames
     on the device (area_locator.AreaLocator, `area_params` its keyword arguments), keeps what it found as `located_area` and goes
     on exactly as if that area had been passed; when it finds none it warns and goes on exactly as with sub_area=None.  With
@@ -232,13 +238,19 @@ class SubtitleExtractor:
                  default_subtitle_area=None, drop_score=0.75, deviation_rate=0.0, threshold=80, batch=64,
                  watermark_decide=None, scene_text_decide=lambda band: True, shard=None, gather_device=None,
                  word_segmentation=False, segment=None, uploader=None, detect_stream=None, frame_selector="fps", change_params=None,
-                 change_counter=None, delete_empty=True, area_params=None, interval_image="middle", composite_params=None):
+                 change_counter=None, delete_empty=True, area_params=None, interval_image="middle", composite_params=None,
+                 interval_text="single", fuse_params=None):
         if frame_selector not in ("fps", "change", "hold"):
             raise ValueError(f"frame_selector must be 'fps', 'change' or 'hold', not {frame_selector!r}")
         if interval_image not in ("middle",) + frame_select.COMPOSITE_MODES:
             raise ValueError(f"interval_image must be 'middle' or one of {frame_select.COMPOSITE_MODES}, not {interval_image!r}")
         if interval_image != "middle" and frame_selector not in ("change", "hold"):
             raise ValueError(f"interval_image={interval_image!r} composites the intervals of frame_selector='change' or 'hold', not {frame_selector!r}")
+        if interval_text not in ("single", "fused"):
+            raise ValueError(f"interval_text must be 'single' or 'fused', not {interval_text!r}")
+        if interval_text == "fused" and (frame_selector not in ("change", "hold") or interval_image != "middle"):
+            raise ValueError(f"interval_text='fused' reads the intervals of frame_selector='change' or 'hold' (not {frame_selector!r}) from their "
+                             f"own frames, interval_image='middle' (not {interval_image!r}): composites and fused posteriors do not combine")
         self.source, self.ocr, self.detect_batch = source, ocr, detect_batch
         self.auto_area, self.area_params, self.located_area = isinstance(sub_area, str) and sub_area == "auto", area_params, None
         self.sub_area, self.mode, self.language = None if self.auto_area else sub_area, mode, language
@@ -256,6 +268,7 @@ class SubtitleExtractor:
         self.frame_selector, self.change_params, self.change_counter = frame_selector, change_params, change_counter
         self.delete_empty = delete_empty          # config.deleteEmptyTimeStamp (intervals of the change selector only)
         self.interval_image, self.composite_params, self.interval_patches = interval_image, composite_params, None
+        self.interval_text, self.fuse_params, self.interval_results = interval_text, fuse_params, None
         self.raw_lines = None
         self.short_lines = None
         self.intervals = None
@@ -313,6 +326,18 @@ class SubtitleExtractor:
         self.interval_patches = comp.run(self._decode_order(up), self.sub_area, self.intervals, self.source.fps, uploader=up, only=only)
         return CompositedSource(self.source, self.sub_area, self.interval_patches)
 
+    def fuse_intervals(self, tasks):
+        """interval_text="fused": the (dt_box, rec_res) of each interval this rank will report (with `shard`, the slice run_ocr_tasks
+        gives it), read from several of its frames -> the tasks, those intervals' carrying their result."""
+        up = self._uploader()
+        params = {"batch": self.batch, **(self.fuse_params or {})}
+        if params.get("fuse_fn") is None and hasattr(self.ocr, "predict_fused"):
+            params["fuse_fn"] = self.ocr.predict_fused
+        only = None if self.shard is None else range(*parallel.shard_range(len(tasks), *self.shard))
+        self.interval_results = frame_select.IntervalFuser(**params).run(self._decode_order(up), self.intervals, self.source.fps, uploader=up,
+                                                                          only=only, default_area=self.default_subtitle_area)
+        return [t[:2] + tuple(self.interval_results[t[1]]) + t[4:] if t[1] in self.interval_results else t for t in tasks]
+
     def _predict_list(self, frames):
         return self.ocr.predict_batch(frames if not isinstance(frames, list) else _stack(frames))
 
@@ -326,6 +351,9 @@ class SubtitleExtractor:
         source = self.source
         if self.interval_image != "middle" and self.intervals is not None:
             source = self.composite_intervals(len(tasks))
+        self.interval_results = None
+        if self.interval_text == "fused" and self.intervals is not None:
+            tasks = self.fuse_intervals(tasks)
         lines = run_ocr_tasks(source, tasks, self.ocr, self.sub_area, self.language, self.drop_score,
                               self.deviation_rate, self.batch, self.shard, self.gather_device, self._uploader())
         if self.sub_area is None:

@@ -546,3 +546,98 @@ class IntervalCompositor:
                 fold(items, np.stack([f for _, f in items]))
         self.area = tuple(geometry)
         return self.patches
+
+
+# ---- interval fusion (several frames per interval of the change selector, fused in probability space) ----------------------
+def fuse_samples(start, end, rep, fps, samples, trim_seconds):
+    """The frames of the interval (start, end, rep) that are recognised together -> (frame numbers ascending, position of the one the
+    detector runs on).  first, last = trim_range(...), n = last - first + 1, K = min(samples, n): K == 1 is [rep]; otherwise
+    first + (i * (n - 1)) // (K - 1) for i in 0 .. K - 1, both ends included.  The detect member is the sample nearest to rep, the
+    earlier one on a tie."""
+    first, last = trim_range(start, end, fps, trim_seconds)
+    n = last - first + 1
+    k = min(int(samples), n)
+    nos = [rep] if k <= 1 else [first + (i * (n - 1)) // (k - 1) for i in range(k)]
+    return nos, min(range(len(nos)), key=lambda i: (abs(nos[i] - rep), i))
+
+
+class IntervalFuser:
+    """IntervalCompositor's sibling: instead of one picture made of all frames of an interval, up to `samples` frames of it go through
+    the recogniser and their per-step class probabilities are averaged before the CTC decode (shim.OcrRecogniser.predict_fused): the
+    boxes are detected once, on the sample nearest to the interval's middle frame, and read in every sample.  That needs no knowledge
+    of the text's polarity and also averages what is not background: compression noise, a glyph between two near-tied classes, a fade.
+    How much it helps recognition on real footage is not measured here (no real clips, stand-in recogniser weights); the integers,
+    the plumbing and the cost (the recogniser runs once per sample) are pinned.
+
+    fuse_fn(frames [n,h,w,3] uint8, groups) -> [(dt_box, rec_res)] per group; groups = [(indices of the members among these frames,
+    position in that list of the member to detect on)].  Default: predict_fused of one shim.OcrRecogniser on the shim's device.
+    Fades at either end are left out as the compositor leaves them out (trim_range, trim_seconds).  Whole intervals are gathered into
+    one call until one more would exceed `batch` frames."""
+
+    def __init__(self, fuse_fn=None, samples=5, trim_seconds=0.25, batch=64):
+        if samples < 1 or samples > batch:
+            raise ValueError(f"IntervalFuser: samples must be 1..batch ({batch}), not {samples}: an interval is never split over two calls")
+        self.fuse_fn, self.samples, self.trim_seconds, self.batch = fuse_fn, int(samples), trim_seconds, int(batch)
+        self.results = None
+
+    def run(self, frames, intervals, fps, uploader=None, only=None, default_area=None):
+        """frames: iterable of uint8 BGR frames in decode order (read once, and not beyond the last frame that is needed); intervals:
+        the selector's [(start, end, rep)], ascending; only: a range of interval indices (a rank's shard), the others are not read;
+        default_area: the half-frame crop a task's frame gets (extractor.frame_preprocess), applied to every sample
+        -> {rep: (dt_box, rec_res)}.  With an uploader (staging.Uploader) the sampled frames go through pinned memory on its producer
+        thread."""
+        import numpy as np
+        if self.fuse_fn is None:
+            from . import shim
+            self.fuse_fn = shim.OcrRecogniser().predict_fused
+        plan = [[]]                   # per call: [(rep, frame numbers, detect position)], whole intervals, at most `batch` frames
+        last_no = 0
+        for k, (start, end, rep) in enumerate(intervals):
+            if only is None or k in only:
+                nos, pos = fuse_samples(start, end, rep, fps, self.samples, self.trim_seconds)
+                if nos[0] <= last_no:
+                    raise ValueError(f"IntervalFuser: intervals must ascend without overlap, got {intervals[k - 1]} then {intervals[k]}")
+                last_no = nos[-1]
+                if plan[-1] and sum(len(n) for _r, n, _p in plan[-1]) + len(nos) > self.batch:
+                    plan.append([])
+                plan[-1].append((rep, nos, pos))
+        self.results = {}
+        if not plan[0]:
+            return self.results
+        it = iter(frames)
+
+        def batches():
+            """lists of (frame number, frame): the samples of one call's intervals, in decode order"""
+            from .extractor import frame_preprocess
+            no = 0
+            for call in plan:
+                buf = []
+                for _rep, nos, _pos in call:
+                    for want in nos:
+                        while no < want:
+                            f = next(it, None)
+                            if f is None:
+                                raise ValueError(f"IntervalFuser: the clip ends at frame {no}, before the sample at frame {want}")
+                            no += 1
+                        buf.append((no, frame_preprocess(default_area, f) if default_area is not None else f))
+                yield buf
+
+        def fuse(call, data):
+            groups, at = [], 0
+            for _rep, nos, pos in call:
+                groups.append((list(range(at, at + len(nos))), pos))
+                at += len(nos)
+            out = self.fuse_fn(data, groups)
+            if len(out) != len(call):
+                raise ValueError(f"IntervalFuser: fuse_fn returned {len(out)} results for {len(call)} intervals")
+            for (rep, _nos, _pos), r in zip(call, out):
+                self.results[rep] = r
+
+        if uploader is not None:
+            from . import staging
+            for call, (_items, staged) in zip(plan, staging.prefetch(batches(), uploader)):
+                fuse(call, staged.tensor())
+        else:
+            for call, items in zip(plan, batches()):
+                fuse(call, np.stack([np.asarray(f) for _, f in items]))
+        return self.results

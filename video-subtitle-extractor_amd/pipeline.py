@@ -402,6 +402,78 @@ class OcrPipeline:
                 out[i] = ("".join(self.charset[j] for j in ids), float(oc[k]))
         return out
 
+    # ---- recognition fused over the frames of one subtitle ----------------------------------------------
+    def _fuse_net(self):
+        """The recogniser once more, with the full probability tensor out (engine.Net(want_probs=True, ragged=True)): created on the
+        first recognize_fused, so a pipeline that never fuses compiles and allocates nothing for it."""
+        if getattr(self, "_fuse_rec", None) is None:
+            self._fuse_rec = engine.Net(self.ctx, self.rec.desc, self.rec.weights, want_probs=True, ragged=True)
+        return self._fuse_rec
+
+    def recognize_fused(self, frames, groups, return_parts=False, max_fuse_bytes=1 << 30):
+        """frames: cuda uint8 [N,H,W,3]; groups: list of (member frame indices, quads): every quad of a group is cut from each of its
+        1..64 member frames (a subtitle stands still: the same box in several frames of its interval), the recogniser's per-step class
+        probabilities of the members are averaged on the device (Context.ctc_fuse) and the mean is decoded like a single row
+        -> list per group of [(text, score)] in quad order, the format of recognize().  With one member, or members that show the same
+        pixels, that is recognize()'s result bit for bit ((p + p) / 2 == p).  What it gains on real footage is not measured here.
+        A group's quads are one grouping unit (the crops of one frame in recognize()): every crop keeps the padded width of its
+        reference chunk, the width groups are _groups()'s, and every row is then replicated once per member, adjacent: ragged rows do
+        not depend on the batch they ride in.  A quad's members never split over two launches; max_fuse_bytes bounds the probability
+        tensor of one launch (a memory bound, not a tuned number; one quad's members always fit).
+        return_parts: also the list, per launch, of dict(specs, crops, widths, img_w, probs, group, tlen, idx_maxp)."""
+        if self.rec_mode == "reference":
+            raise ValueError("recognize_fused replicates rows of a ragged batch; rec_mode='reference' has no batch-independent rows")
+        t = self.ctx.torch
+        n_frames = int(frames.shape[0])
+        members = []
+        for mem, _quads in groups:
+            mem = [int(m) for m in mem]
+            if not 1 <= len(mem) <= self.ctx.CTC_FUSE_MAX or min(mem) < 0 or max(mem) >= n_frames:
+                raise ValueError(f"recognize_fused: a group needs 1..{self.ctx.CTC_FUSE_MAX} member frames inside 0..{n_frames - 1}, got {mem}")
+            members.append(mem)
+        specs = self._crop_specs([quads for _mem, quads in groups])        # spec["frame"] = its group, the unit of the reference's chunks
+        results = [[("", 0.0)] * len(quads) for _mem, quads in groups]
+        parts = []
+        net = self._fuse_net() if specs else None
+        ncls = len(self.charset)
+        pending = []
+        for idx, img_w, widths in (self._groups(specs) if specs else []):
+            # rows of one launch: whole specs while the probability tensor (at most img_w / 4 steps per row) stays inside max_fuse_bytes
+            cap = max(1, int(max_fuse_bytes) // (-(-img_w // 4) * ncls * 4))
+            a = 0
+            while a < len(idx):
+                b, rows = a, 0
+                while b < len(idx) and (b == a or rows + len(members[specs[idx[b]]["frame"]]) <= cap):
+                    rows += len(members[specs[idx[b]]["frame"]])
+                    b += 1
+                crops, roww, offs = [], [], [0]
+                for i, wi in zip(idx[a:b], widths[a:b]):
+                    s = specs[i]
+                    rw = min(wi, int(math.ceil(self.rec_h * s["ratio"])))
+                    for m in members[s["frame"]]:
+                        crops.append(dict(quad=s["quad"], frame=m, crop_w=s["crop_w"], crop_h=s["crop_h"], resized_w=max(rw, 1),
+                                          rotate=s["rotate"]))
+                        roww.append(wi)
+                    offs.append(len(crops))
+                x = self.ctx.rec_preprocess(frames, crops, self.rec_h, img_w)
+                prog = net.program(len(crops), self.rec_h, img_w)
+                outs = net.run(x, widths=np.asarray(roww, np.int32))
+                probs = outs[[o["kind"] for o in prog.outputs].index("probs")]
+                # the sequence length of a group is that of its rows: the last level of the width table, from the host's copy
+                tlen = self.ctx._upload_i32(np.ascontiguousarray(prog.width_table(np.asarray(roww, np.int32))[prog.out_level][offs[:-1]], dtype=np.int32))
+                idx_maxp = self.ctx.ctc_fuse(probs, offs, tlen)
+                oi, ol, oc = self.ctx.ctc_collapse(idx_maxp, tlen)
+                pending.append((idx[a:b], oi, ol, oc))
+                if return_parts:
+                    parts.append(dict(specs=[(specs[i]["frame"], specs[i]["slot"]) for i in idx[a:b]], crops=crops, widths=roww, img_w=img_w,
+                                      probs=probs, group=offs, tlen=tlen, idx_maxp=idx_maxp))
+                a = b
+        for part, oi, ol, oc in pending:
+            oi, ol, oc = oi.cpu().numpy(), ol.cpu().numpy(), oc.cpu().numpy()
+            for k, i in enumerate(part):
+                results[specs[i]["frame"]][specs[i]["slot"]] = ("".join(self.charset[j] for j in oi[k, :ol[k]]), float(oc[k]))
+        return (results, parts) if return_parts else results
+
     # ---- TextSystem.__call__(img, cls=False) for a batch ------------------------------------------------
     def ocr(self, frames):
         """-> list per frame of (list of float32 [4,2] boxes, list of (text, score)) — paddleocr TextSystem output."""

@@ -421,6 +421,26 @@ class OcrRecogniser:
         for out in self.recogniser.stream(batches):
             yield [self.arrange(b, r) for b, r in out]
 
+    def predict_fused(self, frames, groups):
+        """frames: device uint8 [N,H,W,3] (or a host array of that shape); groups: list of (member frame indices, position in that list
+        of the member to detect on), one per subtitle interval: the detector runs as ONE batch on the detect members, the boxes of each
+        are then read in ALL members of its group with the recogniser's per-step class probabilities averaged before decoding
+        (OcrPipeline.recognize_fused) -> list of predict() results, one per group.  A group whose detector finds nothing gives what
+        predict gives for such a frame.  The reference reads one frame per subtitle (ocr.py:27); what fusing gains on real footage is
+        not measured here."""
+        if not self.recogniser:
+            self.recogniser = self.init_model()
+        import torch
+        pipe = self.recogniser.pipe
+        if not isinstance(frames, torch.Tensor):
+            frames = torch.from_numpy(np.ascontiguousarray(frames)).to(_context().tdev)
+        if not groups:
+            return []
+        det = pipe.detect(frames[[int(mem[pos]) for mem, pos in groups]])
+        ordered = [pipeline.sorted_boxes(b) for b in det]
+        rec = pipe.recognize_fused(frames, [(mem, boxes) for (mem, _pos), boxes in zip(groups, ordered)])
+        return [self.arrange(b, r) for b, r in pipe._filter(ordered, rec)]
+
     @classmethod
     def arrange(cls, detection_box, recognise_result):
         """Line grouping / ordering of ocr.py:28-86 (a3)."""
