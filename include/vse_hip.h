@@ -480,6 +480,15 @@ size_t vse_yuv420_frame_bytes(int h, int w, int row_parity);
 int vse_yuv420_to_bgr(vse_ctx* ctx, const void* d_yuv, int n, int h, int w, int layout /* 0 = I420, 1 = NV12 */,
                       int row_parity /* 0 | 1 */, int64_t yuv_frame_stride, void* d_bgr, int64_t pitch, int64_t bgr_frame_stride,
                       void* stream);
+/* vse_yuv420_to_bgr with the colour matrix chosen: matrix 0 = BT.601 (the call above: the same launcher, the same bytes), 1 = BT.709
+ * limited range, what HD encodes normally carry.  The same c, rounding term, shift, clip8, chroma sampling, layouts and kernels:
+ *   B = clip8((c + 2215014 u + 2^19) >> 20), G = clip8((c - 223607 u - 558796 v + 2^19) >> 20), R = clip8((c + 1879825 v + 2^19) >> 20),
+ * the factors round(k 2^20) of 2 (1 - Kb) 255/224, 2 Kb (1 - Kb) / Kg 255/224, 2 Kr (1 - Kr) / Kg 255/224 and 2 (1 - Kr) 255/224 with
+ * Kr = 0.2126, Kb = 0.0722, Kg = 1 - Kr - Kb.  Luma-only pictures (U = V = 128) come out identical under both matrices.
+ * Returns VSE_E_INVAL, and launches nothing, for what vse_yuv420_to_bgr refuses and for a matrix that is not 0 | 1. */
+int vse_yuv_to_bgr_matrix(vse_ctx* ctx, const void* d_yuv, int n, int h, int w, int layout /* 0 = I420, 1 = NV12 */,
+                          int row_parity /* 0 | 1 */, int64_t yuv_frame_stride, void* d_bgr, int64_t pitch, int64_t bgr_frame_stride,
+                          int matrix /* 0 = BT.601, 1 = BT.709 */, void* stream);
 
 #ifdef __cplusplus
 }

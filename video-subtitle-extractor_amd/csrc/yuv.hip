@@ -4,6 +4,11 @@
 //   c = max(Y - 16, 0) * 1220542, u = U - 128, v = V - 128                      (U, V of chroma row (r + row_parity) >> 1, column x >> 1)
 //   B = clip8((c + 2116026 u + 2^19) >> 20), G = clip8((c - 409993 u - 852492 v + 2^19) >> 20), R = clip8((c + 1673527 v + 2^19) >> 20)
 // |sum| <= 560 969 128: int32 is exact.  Every factor fits 24 bits, so the products are the full-rate 24-bit multiplies.
+// vse_yuv_to_bgr_matrix picks the matrix: 0 is the above, 1 is BT.709 limited range (what HD encodes normally carry), the same c, rounding
+// term, shift and clip8 with the chroma factors 2215014 (B), -223607 u - 558796 v (G), 1879825 (R) = round(k * 2^20) of 2 (1 - Kb) 255/224,
+// 2 Kb (1 - Kb) / Kg 255/224, 2 Kr (1 - Kr) / Kg 255/224, 2 (1 - Kr) 255/224 with Kr = 0.2126, Kb = 0.0722 (tests/yuv709_ref.py restates
+// them).  Each is below 2^23 and |sum| <= 573 540 604, so the same int32 / 24-bit argument holds.  The matrix is a template parameter of
+// both kernels: the factors stay literals.
 // HBM-bound byte work, 1.5 bytes read and 3 written per pixel.  Two kernels:
 //   fast     a lane owns 16 pixels x 2 rows: two 16-byte luma loads, 8 + 8 bytes of U and V (I420) or 16 bytes of UV (NV12), six 16-byte
 //            stores; the chroma terms are computed once for both rows.  Needs w % 16 == 0, even h, row_parity 0, and 16-byte aligned
@@ -20,6 +25,7 @@ void vse_set_error(const char* msg);      // vse_runtime.hip
 namespace {
 
 constexpr int YUV_I420 = 0, YUV_NV12 = 1;
+constexpr int BT601 = 0, BT709 = 1;
 constexpr int FAST_THREADS = 256, FAST_MAX_BLOCKS = 2048;
 constexpr int GEN_LANES = 64, GEN_ROWS = 4;        // block of the general kernel: 64 pixel groups x 4 rows
 constexpr long MAX_PIXELS = 0x7fffffffL;           // per frame: the per-frame work-item index stays an int
@@ -28,12 +34,15 @@ struct ChromaTerms {
     int b, g, r;      // the chroma part of each channel's sum, rounding constant included
 };
 
+template <int MATRIX>
 __device__ __forceinline__ ChromaTerms chroma_terms(int U, int V) {
+    constexpr int BU = MATRIX == BT709 ? 2215014 : 2116026, GU = MATRIX == BT709 ? -223607 : -409993;
+    constexpr int GV = MATRIX == BT709 ? -558796 : -852492, RV = MATRIX == BT709 ? 1879825 : 1673527;
     const int u = U - 128, v = V - 128;
     ChromaTerms t;
-    t.b = __mul24(u, 2116026) + (1 << 19);
-    t.g = __mul24(u, -409993) + __mul24(v, -852492) + (1 << 19);
-    t.r = __mul24(v, 1673527) + (1 << 19);
+    t.b = __mul24(u, BU) + (1 << 19);
+    t.g = __mul24(u, GU) + __mul24(v, GV) + (1 << 19);
+    t.r = __mul24(v, RV) + (1 << 19);
     return t;
 }
 
@@ -73,7 +82,7 @@ __device__ __forceinline__ void row16(const uint4& y, const ChromaTerms (&t)[8],
 
 // Work item i of a frame = (row pair i / cgs, 16-pixel column group i % cgs); consecutive lanes take consecutive column groups, so
 // a wave's luma loads are contiguous and its stores cover contiguous 3 KiB runs of two output rows.  blockIdx.y strides the frames.
-template <int LAYOUT>
+template <int LAYOUT, int MATRIX>
 __global__ __launch_bounds__(FAST_THREADS) void yuv420_fast_kernel(const uint8_t* __restrict__ src, int n, int h, int w, long sstride,
                                                                    uint8_t* __restrict__ dst, long pitch, long dstride) {
     const unsigned cgs = (unsigned)w >> 4, items = ((unsigned)h >> 1) * cgs;
@@ -93,14 +102,14 @@ __global__ __launch_bounds__(FAST_THREADS) void yuv420_fast_kernel(const uint8_t
                 const uint2 v = *reinterpret_cast<const uint2*>(up + (plane >> 2));
                 const unsigned uw[2] = {u.x, u.y}, vw[2] = {v.x, v.y};
 #pragma unroll
-                for (int k = 0; k < 8; ++k) t[k] = chroma_terms((int)((uw[k >> 2] >> (8 * (k & 3))) & 255u), (int)((vw[k >> 2] >> (8 * (k & 3))) & 255u));
+                for (int k = 0; k < 8; ++k) t[k] = chroma_terms<MATRIX>((int)((uw[k >> 2] >> (8 * (k & 3))) & 255u), (int)((vw[k >> 2] >> (8 * (k & 3))) & 255u));
             } else {
                 const uint4 uv = *reinterpret_cast<const uint4*>(s + plane + (long)rp * w + 16 * cg);
                 const unsigned q[4] = {uv.x, uv.y, uv.z, uv.w};
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     const unsigned p = q[k >> 1] >> (16 * (k & 1));
-                    t[k] = chroma_terms((int)(p & 255u), (int)((p >> 8) & 255u));
+                    t[k] = chroma_terms<MATRIX>((int)(p & 255u), (int)((p >> 8) & 255u));
                 }
             }
             uint8_t* o = d + (long)(2 * rp) * pitch + 48 * cg;
@@ -111,7 +120,7 @@ __global__ __launch_bounds__(FAST_THREADS) void yuv420_fast_kernel(const uint8_t
 }
 
 // Lane (threadIdx.x, threadIdx.y) = pixels 4 xg .. 4 xg + 3 of one row; blockIdx.y strides the rows, blockIdx.z the frames.
-template <int LAYOUT>
+template <int LAYOUT, int MATRIX>
 __global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void yuv420_general_kernel(const uint8_t* __restrict__ src, int n, int h, int w, int parity,
                                                                               long sstride, uint8_t* __restrict__ dst, long pitch, long dstride) {
     const int x = 4 * (int)(blockIdx.x * GEN_LANES + threadIdx.x);
@@ -135,12 +144,12 @@ __global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void yuv420_general_kernel(co
             if (LAYOUT == YUV_I420) {
                 const uint8_t* up = s + plane + cr * cw;
                 const uint8_t* vp = up + ch * cw;
-                t0 = chroma_terms(up[c0], vp[c0]);
-                t1 = chroma_terms(up[c1], vp[c1]);
+                t0 = chroma_terms<MATRIX>(up[c0], vp[c0]);
+                t1 = chroma_terms<MATRIX>(up[c1], vp[c1]);
             } else {
                 const uint8_t* uv = s + plane + cr * 2 * cw;
-                t0 = chroma_terms(uv[2 * c0], uv[2 * c0 + 1]);
-                t1 = chroma_terms(uv[2 * c1], uv[2 * c1 + 1]);
+                t0 = chroma_terms<MATRIX>(uv[2 * c0], uv[2 * c0 + 1]);
+                t1 = chroma_terms<MATRIX>(uv[2 * c1], uv[2 * c1 + 1]);
             }
             unsigned o[3];
             bgr4(yw, t0, t1, o[0], o[1], o[2]);
@@ -169,15 +178,15 @@ size_t vse_yuv420_frame_bytes(int h, int w, int row_parity) {
     return (size_t)h * w + 2 * cw * ch;
 }
 
-int vse_yuv420_to_bgr(vse_ctx* c, const void* d_yuv, int n, int h, int w, int layout, int row_parity, int64_t yuv_frame_stride,
-                      void* d_bgr, int64_t pitch, int64_t bgr_frame_stride, void* stream) {
+int vse_yuv_to_bgr_matrix(vse_ctx* c, const void* d_yuv, int n, int h, int w, int layout, int row_parity, int64_t yuv_frame_stride,
+                          void* d_bgr, int64_t pitch, int64_t bgr_frame_stride, int matrix, void* stream) {
     const size_t frame = vse_yuv420_frame_bytes(h, w, row_parity);
-    if (!c || !d_yuv || !d_bgr || n < 1 || !frame || (layout != YUV_I420 && layout != YUV_NV12) || pitch < (int64_t)w * 3 ||
-        yuv_frame_stride < (int64_t)frame || bgr_frame_stride < (int64_t)(h - 1) * pitch + (int64_t)w * 3) {
-        char msg[320];
+    if (!c || !d_yuv || !d_bgr || n < 1 || !frame || (layout != YUV_I420 && layout != YUV_NV12) || (matrix != BT601 && matrix != BT709) ||
+        pitch < (int64_t)w * 3 || yuv_frame_stride < (int64_t)frame || bgr_frame_stride < (int64_t)(h - 1) * pitch + (int64_t)w * 3) {
+        char msg[360];
         snprintf(msg, sizeof msg, "vse_yuv420_to_bgr: bad arguments (n %d, frame %d x %d of at most 2^31 - 1 pixels, layout %d of 0 | 1, row parity %d "
-                 "of 0 | 1, packed frame stride %lld of at least %zu, pitch %lld, output frame stride %lld)", n, h, w, layout, row_parity,
-                 (long long)yuv_frame_stride, frame, (long long)pitch, (long long)bgr_frame_stride);
+                 "of 0 | 1, packed frame stride %lld of at least %zu, pitch %lld, output frame stride %lld, matrix %d of 0 | 1)", n, h, w, layout,
+                 row_parity, (long long)yuv_frame_stride, frame, (long long)pitch, (long long)bgr_frame_stride, matrix);
         vse_set_error(msg);
         return VSE_E_INVAL;
     }
@@ -186,31 +195,32 @@ int vse_yuv420_to_bgr(vse_ctx* c, const void* d_yuv, int n, int h, int w, int la
     uint8_t* dst = reinterpret_cast<uint8_t*>(d_bgr);
     const bool fast = w % 16 == 0 && h % 2 == 0 && row_parity == 0 && pitch % 16 == 0 && yuv_frame_stride % 16 == 0 &&
                       bgr_frame_stride % 16 == 0 && aligned16(src) && aligned16(dst);
+    const int which = 2 * matrix + layout;
     if (fast) {
         const long items = (long)(h / 2) * (w / 16);
         const dim3 grid((unsigned)std::min<long>((items + FAST_THREADS - 1) / FAST_THREADS, FAST_MAX_BLOCKS), (unsigned)std::min(n, 65535));
-        if (layout == YUV_I420)
-            hipLaunchKernelGGL(yuv420_fast_kernel<YUV_I420>, grid, dim3(FAST_THREADS), 0, st, src, n, h, w, (long)yuv_frame_stride, dst, (long)pitch,
-                               (long)bgr_frame_stride);
-        else
-            hipLaunchKernelGGL(yuv420_fast_kernel<YUV_NV12>, grid, dim3(FAST_THREADS), 0, st, src, n, h, w, (long)yuv_frame_stride, dst, (long)pitch,
-                               (long)bgr_frame_stride);
+        const auto kernel = which == 0 ? yuv420_fast_kernel<YUV_I420, BT601> : which == 1 ? yuv420_fast_kernel<YUV_NV12, BT601>
+                          : which == 2 ? yuv420_fast_kernel<YUV_I420, BT709> : yuv420_fast_kernel<YUV_NV12, BT709>;
+        hipLaunchKernelGGL(kernel, grid, dim3(FAST_THREADS), 0, st, src, n, h, w, (long)yuv_frame_stride, dst, (long)pitch, (long)bgr_frame_stride);
     } else {
         const long groups = ((long)w + 3) / 4;
         const dim3 grid((unsigned)((groups + GEN_LANES - 1) / GEN_LANES), (unsigned)std::min((h + GEN_ROWS - 1) / GEN_ROWS, 65535),
                         (unsigned)std::min(n, 65535));
-        if (layout == YUV_I420)
-            hipLaunchKernelGGL(yuv420_general_kernel<YUV_I420>, grid, dim3(GEN_LANES, GEN_ROWS), 0, st, src, n, h, w, row_parity,
-                               (long)yuv_frame_stride, dst, (long)pitch, (long)bgr_frame_stride);
-        else
-            hipLaunchKernelGGL(yuv420_general_kernel<YUV_NV12>, grid, dim3(GEN_LANES, GEN_ROWS), 0, st, src, n, h, w, row_parity,
-                               (long)yuv_frame_stride, dst, (long)pitch, (long)bgr_frame_stride);
+        const auto kernel = which == 0 ? yuv420_general_kernel<YUV_I420, BT601> : which == 1 ? yuv420_general_kernel<YUV_NV12, BT601>
+                          : which == 2 ? yuv420_general_kernel<YUV_I420, BT709> : yuv420_general_kernel<YUV_NV12, BT709>;
+        hipLaunchKernelGGL(kernel, grid, dim3(GEN_LANES, GEN_ROWS), 0, st, src, n, h, w, row_parity, (long)yuv_frame_stride, dst, (long)pitch,
+                           (long)bgr_frame_stride);
     }
     if (hipGetLastError() != hipSuccess) {
         vse_set_error("vse_yuv420_to_bgr: launch failed");
         return VSE_E_HIP;
     }
     return VSE_OK;
+}
+
+int vse_yuv420_to_bgr(vse_ctx* c, const void* d_yuv, int n, int h, int w, int layout, int row_parity, int64_t yuv_frame_stride,
+                      void* d_bgr, int64_t pitch, int64_t bgr_frame_stride, void* stream) {
+    return vse_yuv_to_bgr_matrix(c, d_yuv, n, h, w, layout, row_parity, yuv_frame_stride, d_bgr, pitch, bgr_frame_stride, BT601, stream);
 }
 
 }  // extern "C"

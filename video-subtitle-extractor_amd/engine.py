@@ -25,10 +25,11 @@ EXPORTS = [
     "vse_scene_change", "vse_frame_cells_dims", "vse_frame_cells_state_bytes", "vse_frame_cells",
     "vse_interval_state_bytes", "vse_interval_accumulate", "vse_interval_composite", "vse_frame_hold_state_bytes", "vse_frame_hold",
     "vse_audio_stream_length", "vse_audio_stream_workspace_bytes", "vse_audio_stream_feed", "vse_audio_stream_finish", "vse_ctc_fuse",
+    "vse_yuv_to_bgr_matrix",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
-# this list for them.
+# this list for them (exactly these two, which is why vse_yuv_to_bgr_matrix is spelled without the 420).
 EXPORTS_NUMBERED = ["vse_yuv420_frame_bytes", "vse_yuv420_to_bgr"]
 
 
@@ -176,6 +177,8 @@ def load_library(path=None):
     lib.vse_yuv420_frame_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.vse_yuv420_to_bgr.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p,
                                       C.c_int64, C.c_int64, C.c_void_p]
+    lib.vse_yuv_to_bgr_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p,
+                                          C.c_int64, C.c_int64, C.c_int, C.c_void_p]
     if lib.vse_sizeof_op() != ir.OP_DT.itemsize or lib.vse_sizeof_view() != ir.VIEW_DT.itemsize:
         raise VseError(f"ABI mismatch: vse_op {lib.vse_sizeof_op()} vs {ir.OP_DT.itemsize}, "
                        f"vse_view {lib.vse_sizeof_view()} vs {ir.VIEW_DT.itemsize}")
@@ -660,13 +663,17 @@ class Context:
         return out
 
     # ---- frame ingest: YUV 4:2:0 -> BGR ---------------------------------------------------------------------------
-    def yuv420_to_bgr(self, packed_u8, n, h, w, layout="i420", row_parity=0, out=None):
+    def yuv420_to_bgr(self, packed_u8, n, h, w, layout="i420", row_parity=0, out=None, matrix=0):
         """packed_u8: cuda uint8 holding n packed 4:2:0 (sub-)frames of h x w pixels (include/vse_hip.h vse_yuv420_to_bgr: luma rows,
         then the chroma rows of layout "i420" | "nv12"), 1-D (frames back to back) or 2-D [n, stride] (frame stride = its row stride)
         -> cuda uint8 [n,h,w,3] BGR on the current stream.  out: write into this tensor instead (it may be a strided view with packed
-        pixels; its pitch and frame stride are taken from it)."""
+        pixels; its pitch and frame stride are taken from it).  matrix: 0 | "bt601" (vse_yuv420_to_bgr's integers) or 1 | "bt709"
+        (vse_yuv_to_bgr_matrix)."""
         t = self.torch
         n, h, w, row_parity = int(n), int(h), int(w), int(row_parity)
+        matrix = YUV_MATRICES.get(matrix, matrix)
+        if matrix not in (0, 1):
+            raise VseError(f"yuv420_to_bgr: matrix {matrix!r} is not one of {sorted(YUV_MATRICES)} (0 | 1)")
         if layout not in YUV_LAYOUTS:
             raise VseError(f"yuv420_to_bgr: layout {layout!r} is not one of {sorted(YUV_LAYOUTS)}")
         assert packed_u8.dtype == t.uint8 and packed_u8.dim() in (1, 2) and packed_u8.stride(-1) == 1
@@ -681,12 +688,18 @@ class Context:
             out = t.empty((max(n, 0), max(h, 0), max(w, 0), 3), dtype=t.uint8, device=self.tdev)
         assert out.dtype == t.uint8 and tuple(out.shape) == (n, h, w, 3) and out.stride(3) == 1 and out.stride(2) == 3
         dstride = out.stride(0) if n > 1 else max(out.stride(0), (h - 1) * out.stride(1) + 3 * w)
-        _check(self.lib.vse_yuv420_to_bgr(self.handle, C.c_void_p(packed_u8.data_ptr()), n, h, w, YUV_LAYOUTS[layout], row_parity, sstride,
-                                          C.c_void_p(out.data_ptr()), out.stride(1), dstride, self.stream()), "vse_yuv420_to_bgr")
+        if matrix == 0:
+            _check(self.lib.vse_yuv420_to_bgr(self.handle, C.c_void_p(packed_u8.data_ptr()), n, h, w, YUV_LAYOUTS[layout], row_parity, sstride,
+                                              C.c_void_p(out.data_ptr()), out.stride(1), dstride, self.stream()), "vse_yuv420_to_bgr")
+        else:
+            _check(self.lib.vse_yuv_to_bgr_matrix(self.handle, C.c_void_p(packed_u8.data_ptr()), n, h, w, YUV_LAYOUTS[layout], row_parity, sstride,
+                                                  C.c_void_p(out.data_ptr()), out.stride(1), dstride, matrix, self.stream()),
+                   "vse_yuv_to_bgr_matrix")
         return out
 
 
 YUV_LAYOUTS = {"i420": 0, "nv12": 1}
+YUV_MATRICES = {"bt601": 0, "bt709": 1}
 INTERVAL_MODES = {"min": 0, "max": 1, "mean": 2}
 
 

@@ -15,10 +15,15 @@ text_cleanup.py with the word segmenter as a parameter (its corpus is not instal
 
 Frame sources: anything with `frame_count`, `fps`, `read(frame_no) -> uint8 BGR [H,W,3] | None` (1-based, like
 cap.set(CAP_PROP_POS_FRAMES, frame_no - 1); cap.read()) and `frames()` (decode order).  `ArraySource` wraps decoded frames;
-ingest.py reads the lossless containers that need no codec (neither box has cv2 / ffmpeg).
+ingest.py reads the lossless containers that need no codec (neither box has cv2 / ffmpeg).  A source without `read` (ingest.Y4mStream:
+a pipe from any decoder) is sequential: SubtitleExtractor then works in one pass (`one_pass`).
+
+Command line: python -m vse_amd.extractor VIDEO|- [-o OUT.srt]   (main below).
 """
+import argparse
 import logging
 import re
+import sys
 from collections import deque
 from types import SimpleNamespace
 
@@ -73,6 +78,24 @@ class CompositedSource:
         out = np.array(frame, copy=True)
         out[self._y0:self._y0 + patch.shape[0], self._x0:self._x0 + patch.shape[1]] = patch
         return out
+
+
+class RetainedSource:
+    """The frames a one-pass run still holds, as the source run_ocr_tasks reads: read(no) is the BGR frame, read_raw(no), only where
+    the frames are unconverted ingest.Yuv420Frames, the planes (uploaded as they are and converted on the device)."""
+
+    def __init__(self, frames, fps, raw):
+        self._frames, self.fps, self.frame_count = frames, fps, None
+        if raw:
+            self.read_raw = frames.get
+
+    def read(self, frame_no):
+        f = self._frames.get(frame_no)
+        return f.to_bgr() if hasattr(f, "to_bgr") else f
+
+
+def _frame_nbytes(frame):
+    return sum(p.nbytes for p in frame.planes) if hasattr(frame, "planes") else frame.nbytes
 
 
 def frame_preprocess(subtitle_area, frame):
@@ -232,14 +255,29 @@ class SubtitleExtractor:
     sub_area="auto": nobody drew a box, so run() first looks for the subtitle band itself, one more pass over the clip's frames
     on the device (area_locator.AreaLocator, `area_params` its keyword arguments), keeps what it found as `located_area` and goes
     on exactly as if that area had been passed; when it finds none it warns and goes on exactly as with sub_area=None.  With
-    `shard`, every rank scans the same frames and gets the same integers, hence the same area."""
+    `shard`, every rank scans the same frames and gets the same integers, hence the same area.
+    one_pass (None: exactly when the source has no `read`, e.g. ingest.Y4mStream over a pipe; True forces it on a seekable source and
+    halves its decode work; False on a sequential source is a ValueError): the clip is read once, in decode order.  frame_selector="fps":
+    frame `no` is a task iff (no - 1) % max(1, int(fps // extract_frequency)) == 0 (fps_tasks' rule without the frame count); tasks go
+    to OCR `batch` at a time and nothing is kept.  "change" / "hold" with an area in fast / auto mode: the selector yields batch by batch
+    (iter_run), the middle frames of the intervals that closed are recognised `batch` at a time, and frames are kept only while they can
+    still become a middle frame: with t the last frame whose row the tracker has seen and s the start of the open run, frames
+    >= (s + t) // 2 (the middle can only move forward from there), frames > t without an open run, and the middle frames not yet
+    recognised; a run of L frames holds about L / 2 frames plus the batches in flight.  `retain_bytes` (default 4 GiB, a policy, not a
+    measurement: about 1380 frames of 1080p 4:2:0, so runs up to about 2700 frames stay exact) bounds them: when an open run exceeds
+    it, its oldest kept frame goes and that interval is recognised on max(middle, oldest frame still kept); start and end, hence the
+    SRT times, are untouched; `clamped_intervals` counts them and one warning is logged per run.  Where no interval was clamped, the
+    intervals, the frames recognised, raw_lines and the SRT equal those of the multi-pass run() on the same frames with the same
+    arguments (recognition does not depend on how frames are grouped into batches: tests/test_gpu_ragged.py).  Refused in one pass,
+    because they need a second look at frames already gone: sub_area="auto", mode="accurate" with an area, interval_image other than
+    "middle", interval_text="fused", shard."""
 
     def __init__(self, source, ocr, detect_batch=None, sub_area=None, mode="fast", language="ch", extract_frequency=3,
                  default_subtitle_area=None, drop_score=0.75, deviation_rate=0.0, threshold=80, batch=64,
                  watermark_decide=None, scene_text_decide=lambda band: True, shard=None, gather_device=None,
                  word_segmentation=False, segment=None, uploader=None, detect_stream=None, frame_selector="fps", change_params=None,
                  change_counter=None, delete_empty=True, area_params=None, interval_image="middle", composite_params=None,
-                 interval_text="single", fuse_params=None):
+                 interval_text="single", fuse_params=None, one_pass=None, retain_bytes=4 << 30):
         if frame_selector not in ("fps", "change", "hold"):
             raise ValueError(f"frame_selector must be 'fps', 'change' or 'hold', not {frame_selector!r}")
         if interval_image not in ("middle",) + frame_select.COMPOSITE_MODES:
@@ -272,6 +310,18 @@ class SubtitleExtractor:
         self.raw_lines = None
         self.short_lines = None
         self.intervals = None
+        self.one_pass = (not hasattr(source, "read")) if one_pass is None else bool(one_pass)
+        self.retain_bytes, self.clamped_intervals, self.peak_retained = retain_bytes, 0, 0
+        if not self.one_pass and not hasattr(source, "read"):
+            raise ValueError("one_pass=False needs a source with read(frame_no): this one is sequential and its frames cannot be looked at a second time")
+        if self.one_pass:
+            refused = [("sub_area='auto'", self.auto_area), ("mode='accurate' with a subtitle area", mode == "accurate" and sub_area is not None),
+                       (f"interval_image={interval_image!r}", interval_image != "middle"),
+                       (f"interval_text={interval_text!r}", interval_text != "single"), (f"shard={shard!r}", shard is not None)]
+            for what, hit in refused:
+                if hit:
+                    raise ValueError(f"{what} is not available in one pass (a sequential source, or one_pass=True): it needs a second look "
+                                     "at frames already gone")
 
     def _uploader(self):
         if self.uploader == "auto":
@@ -341,21 +391,97 @@ class SubtitleExtractor:
     def _predict_list(self, frames):
         return self.ocr.predict_batch(frames if not isinstance(frames, list) else _stack(frames))
 
+    # ---- one pass ---------------------------------------------------------------------------------------------------------------
+    def _recognise(self, frames, nos, uploader):
+        """raw.txt lines of the retained frames `nos`, through run_ocr_tasks like any other task list."""
+        tasks = [(getattr(self.source, "frame_count", None), no, None, None, None, self.default_subtitle_area) for no in nos]
+        raw = any(hasattr(frames[no], "pack_into") for no in nos)
+        return run_ocr_tasks(RetainedSource(frames, self.source.fps, raw), tasks, self.ocr, self.sub_area, self.language, self.drop_score,
+                             self.deviation_rate, self.batch, None, None, uploader)
+
+    def _one_pass_fps(self, frames, uploader):
+        step = max(1, int(self.source.fps // self.extract_frequency))
+        lines, held = [], {}
+        for no, frame in enumerate(frames, 1):
+            if (no - 1) % step:
+                continue
+            held[no] = frame
+            self.peak_retained = max(self.peak_retained, len(held))
+            if len(held) == self.batch:
+                lines += self._recognise(held, list(held), uploader)
+                held = {}
+        if held:
+            lines += self._recognise(held, list(held), uploader)
+        return lines
+
+    def _one_pass_intervals(self, frames, uploader):
+        s = self.source
+        if self.frame_selector == "change":
+            sel = frame_select.ChangeFrameSelector(self.change_counter, batch=self.batch, **(self.change_params or {}))
+            batches = sel.iter_run(frames, self.sub_area, uploader=uploader)
+        else:
+            sel = frame_select.HoldFrameSelector(self.change_counter, batch=self.batch, **(self.change_params or {}))
+            batches = sel.iter_run(frames, self.sub_area, s.fps, uploader=uploader)
+        # the recogniser's batches are staged while the selector's producer thread stages the next bands: a slab ring of their own
+        ocr_up = uploader.sibling() if uploader is not None else None
+        self.intervals = []
+        kept, nbytes = {}, 0              # frame number -> full frame, and their bytes
+        queue = []                        # middle frames of closed intervals, not yet recognised
+        lines, no = [], 0
+        try:
+            for items, closed in batches:
+                for full, _band in items:
+                    no += 1
+                    kept[no] = full
+                    nbytes += _frame_nbytes(full)
+                self.peak_retained = max(self.peak_retained, len(kept))
+                for start, end, rep in closed:
+                    if rep not in kept:                   # the cap took it: the oldest frame of the interval that is still there
+                        rep = min(k for k in kept if k >= rep)
+                        self.clamped_intervals += 1
+                        if self.clamped_intervals == 1:
+                            logging.getLogger(__name__).warning(
+                                "one pass: the interval %d..%d outgrew retain_bytes=%d; it is recognised on frame %d instead of its middle "
+                                "frame (its times are untouched; further such intervals are counted in clamped_intervals)",
+                                start, end, self.retain_bytes, rep)
+                    self.intervals.append((start, end, rep))
+                    queue.append(rep)
+                while len(queue) >= self.batch:
+                    lines += self._recognise(kept, queue[:self.batch], ocr_up)
+                    del queue[:self.batch]
+                t, open_start = sel.tracker.fed, sel.tracker.open_start
+                floor = t + 1 if open_start is None else (open_start + t) // 2
+                for k in [k for k in kept if k < floor and k not in queue]:
+                    nbytes -= _frame_nbytes(kept.pop(k))
+                if nbytes > self.retain_bytes and open_start is not None:
+                    for k in sorted(k for k in kept if k < t and k not in queue):       # frame t itself always stays
+                        nbytes -= _frame_nbytes(kept.pop(k))
+                        if nbytes <= self.retain_bytes:
+                            break
+            if queue:
+                lines += self._recognise(kept, queue, ocr_up)
+        finally:
+            batches.close()
+            if ocr_up is not None:
+                ocr_up.close()
+        return lines
+
+    def _run_one_pass(self):
+        self.clamped_intervals = self.peak_retained = 0
+        up = self._uploader()
+        frames = self._decode_order(up)
+        if self.sub_area is not None and self.mode in ("fast", "auto") and self.frame_selector in ("change", "hold"):
+            return self._one_pass_intervals(frames, up)
+        return self._one_pass_fps(frames, up)
+
     def run(self):
         """-> SRT text.  raw_lines (normalised, as the reference rewrites raw.txt) and short_lines are kept on the object."""
         self.intervals = None
-        if self.auto_area:
-            self.locate_area()
-        self.interval_patches = None
-        tasks = self.select_tasks()
-        source = self.source
-        if self.interval_image != "middle" and self.intervals is not None:
-            source = self.composite_intervals(len(tasks))
-        self.interval_results = None
-        if self.interval_text == "fused" and self.intervals is not None:
-            tasks = self.fuse_intervals(tasks)
-        lines = run_ocr_tasks(source, tasks, self.ocr, self.sub_area, self.language, self.drop_score,
-                              self.deviation_rate, self.batch, self.shard, self.gather_device, self._uploader())
+        if self.one_pass:
+            self.interval_patches = self.interval_results = None
+            lines = self._run_one_pass()
+        else:
+            lines = self._run_multi_pass()
         if self.sub_area is None:
             if self.watermark_decide is not None:               # the reference asks on stdin (main.py:164-170)
                 lines = raw_filters.filter_watermark(lines, self.watermark_decide)
@@ -371,8 +497,97 @@ class SubtitleExtractor:
             text, _ = text_cleanup.cleanup_srt(text, self.language, self.segment or text_cleanup.default_segmenter())
         return text
 
+    def _run_multi_pass(self):
+        if self.auto_area:
+            self.locate_area()
+        self.interval_patches = None
+        tasks = self.select_tasks()
+        source = self.source
+        if self.interval_image != "middle" and self.intervals is not None:
+            source = self.composite_intervals(len(tasks))
+        self.interval_results = None
+        if self.interval_text == "fused" and self.intervals is not None:
+            tasks = self.fuse_intervals(tasks)
+        return run_ocr_tasks(source, tasks, self.ocr, self.sub_area, self.language, self.drop_score,
+                             self.deviation_rate, self.batch, self.shard, self.gather_device, self._uploader())
+
     @staticmethod
     def srt2txt(srt_text):
         """main.py:1037-1043 (pysrt: every block's text, one block after the other)."""
         blocks = [b for b in re.split(r"\n(?=\d+\n\d\d:\d\d:\d\d,\d{3} --> )", srt_text) if b.strip()]
         return "".join(b.split("\n", 2)[2].rstrip("\n") + "\n" for b in blocks)
+
+
+def _parse_area(text):
+    if text == "auto":
+        return "auto"
+    parts = text.split(",")
+    if len(parts) != 4 or not all(p.strip().lstrip("-").isdigit() for p in parts):
+        raise ValueError(f"--area takes ymin,ymax,xmin,xmax or auto, not {text!r}")
+    return SubtitleArea(*(int(p) for p in parts))
+
+
+def main(argv=None, ocr=None, counter=None):
+    """ocr: the recogniser (None: shim.OcrRecogniser on the GPU, frames staged through staging.default_uploader, YUV 4:2:0 converted
+    on the device); counter: the change / hold selector's count_fn (None: the GPU's)."""
+    p = argparse.ArgumentParser(prog="python -m vse_amd.extractor", description="Extract a video's hard subtitles to SRT on the GPU.  "
+                                "`-` reads YUV4MPEG2 from standard input in one pass, e.g. "
+                                "`ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m vse_amd.extractor - -o film.srt`.")
+    p.add_argument("video", help="`-` (YUV4MPEG2 on standard input), or a file: uncompressed BGR24 or Motion-JPEG AVI, a .npy frame stack, "
+                   ".y4m, or headerless .yuv / .i420 / .nv12")
+    p.add_argument("-o", "--output", default=None, metavar="OUT.srt", help="write the SRT here [standard output]")
+    p.add_argument("--fps", type=float, default=None, help="frame rate, for input that carries none (.npy, headerless YUV, Y4M with F0:0)")
+    p.add_argument("--size", default=None, metavar="WxH", help="frame size of a headerless YUV 4:2:0 file")
+    p.add_argument("--layout", default=None, choices=("i420", "nv12"), help="plane layout of a headerless YUV 4:2:0 file [by extension]")
+    p.add_argument("--matrix", default="bt601", choices=("bt601", "bt709"), help="YUV 4:2:0 -> BGR matrix [bt601]; Y4M carries no tag "
+                   "for it, and HD encodes are normally BT.709")
+    p.add_argument("--area", default=None, metavar="ymin,ymax,xmin,xmax|auto", help="the subtitle area in frame pixels, or `auto` to "
+                   "look for it first (not in one pass) [none: the whole frame, fps sampler]")
+    p.add_argument("--selector", default="fps", choices=("fps", "change", "hold"), help="which frames go to OCR [fps]")
+    p.add_argument("--mode", default="fast", choices=("fast", "auto", "accurate"))
+    p.add_argument("--language", default="ch")
+    p.add_argument("--frequency", type=int, default=3, help="frames per second the fps sampler looks at [3]")
+    p.add_argument("--batch", type=int, default=64)
+    p.add_argument("--retain-gib", type=float, default=4.0, help="one pass: bound on the frames kept for the open subtitle, GiB [4]")
+    p.add_argument("--txt", default=None, metavar="OUT.txt", help="also write the subtitles' text alone (srt2txt)")
+    p.add_argument("--weights-dir", default=None, help="directory of <model id>.npz weight files")
+    p.add_argument("--allow-standin-weights", action="store_true", help="run with seeded stand-in weights where a model's are missing")
+    args = p.parse_args(argv)
+    from . import ingest
+    try:
+        size = None
+        if args.size is not None:
+            w, sep, h = args.size.lower().partition("x")
+            if not (sep and w.isdigit() and h.isdigit()):
+                raise ValueError(f"--size takes WIDTHxHEIGHT, not {args.size!r}")
+            size = (int(w), int(h))
+        area = None if args.area is None else _parse_area(args.area)
+        source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout, matrix=args.matrix)
+        uploader = None
+        if ocr is None:
+            if args.weights_dir is not None:
+                shim.config.weights_dir = args.weights_dir
+            if args.allow_standin_weights:
+                shim.config.allow_standin_weights = True
+            shim.config.language, shim.config.mode = args.language, args.mode
+            ocr, uploader = shim.OcrRecogniser(), staging.default_uploader()
+        ex = SubtitleExtractor(source, ocr, sub_area=area, mode=args.mode, language=args.language, extract_frequency=args.frequency,
+                               batch=args.batch, uploader=uploader, frame_selector=args.selector, change_counter=counter,
+                               retain_bytes=int(args.retain_gib * (1 << 30)))
+        text = ex.run()
+        if args.output is None:
+            sys.stdout.write(text)
+        else:
+            with open(args.output, "w", encoding="utf-8") as fp:
+                fp.write(text)
+        if args.txt is not None:
+            with open(args.txt, "w", encoding="utf-8") as fp:
+                fp.write(SubtitleExtractor.srt2txt(text))
+    except (OSError, ValueError) as e:
+        print(f"extractor: {e}", file=sys.stderr)
+        return 2
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

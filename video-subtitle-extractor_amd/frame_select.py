@@ -192,34 +192,55 @@ def default_min_edges(area_h, area_w):
     return max(64, int(0.0005 * max(area_h - 2, 0) * max(area_w - 2, 0)))
 
 
+class IntervalTracker:
+    """The subtitle-change automaton, fed in pieces.  A frame is present when edges >= min_edges; a cut falls between t-1 and t when
+    presence changes, or when both are present and (appeared + vanished) / (edges[t-1] + appeared) >= change_ratio (the union of the two
+    masks); an interval is a maximal run of present frames without a cut inside, kept when it is at least min_frames long; rep is its
+    middle frame.  feed(rows of (edges, appeared, vanished)) -> the intervals (start, end, rep), 1-based frame numbers, that those rows
+    closed; flush() closes the open run at the last fed frame.  `fed`: rows seen; `open_start`: first frame of the open run, or None
+    (a run still shorter than min_frames is open too)."""
+
+    def __init__(self, min_edges, change_ratio=0.5, min_frames=2):
+        self.min_edges, self.change_ratio, self.min_frames = min_edges, change_ratio, min_frames
+        self.fed = 0
+        self.open_start = None
+        self._prev_edges = 0
+
+    def _close(self, end, out):
+        if self.open_start is not None and end - self.open_start + 1 >= self.min_frames:
+            out.append((self.open_start, end, (self.open_start + end) // 2))
+
+    def feed(self, rows):
+        out = []
+        for e, a, v in rows:
+            e, a, v = int(e), int(a), int(v)
+            self.fed += 1
+            t = self.fed
+            if e < self.min_edges:
+                self._close(t - 1, out)
+                self.open_start = None
+            elif self.open_start is None:
+                self.open_start = t
+            else:
+                union = self._prev_edges + a
+                if union and (a + v) / union >= self.change_ratio:
+                    self._close(t - 1, out)
+                    self.open_start = t
+            self._prev_edges = e
+        return out
+
+    def flush(self):
+        out = []
+        self._close(self.fed, out)
+        self.open_start = None
+        return out
+
+
 def change_intervals(counts, min_edges, change_ratio=0.5, min_frames=2):
-    """Per-frame (edges, appeared, vanished) of a whole clip -> [(start, end, rep)] with 1-based frame numbers.
-    A frame is present when edges >= min_edges; a cut falls between t-1 and t when presence changes, or when both are present
-    and (appeared + vanished) / (edges[t-1] + appeared) >= change_ratio (the union of the two masks); an interval is a maximal
-    run of present frames without a cut inside, kept when it is at least min_frames long; rep is its middle frame."""
-    out = []
-    start = None
-    prev_edges = 0
-
-    def close(end):
-        if start is not None and end - start + 1 >= min_frames:
-            out.append((start, end, (start + end) // 2))
-
-    for t, (e, a, v) in enumerate(counts, 1):
-        e, a, v = int(e), int(a), int(v)
-        if e < min_edges:
-            close(t - 1)
-            start = None
-        elif start is None:
-            start = t
-        else:
-            union = prev_edges + a
-            if union and (a + v) / union >= change_ratio:
-                close(t - 1)
-                start = t
-        prev_edges = e
-    close(len(counts))
-    return out
+    """Per-frame (edges, appeared, vanished) of a whole clip -> [(start, end, rep)] with 1-based frame numbers: IntervalTracker fed
+    the whole clip at once, then flushed."""
+    tracker = IntervalTracker(min_edges, change_ratio, min_frames)
+    return tracker.feed(counts) + tracker.flush()
 
 
 def clip_area(sub_area, h, w):
@@ -270,43 +291,57 @@ class ChangeFrameSelector:
         """frames: iterable of uint8 BGR frames in decode order; sub_area: .ymin .ymax .xmin .xmax in frame pixels (clipped to
         the frame) -> [(start, end, rep)].  Only the area's rows are staged; with an uploader (staging.Uploader) they go through
         pinned memory on its producer thread, which uploads the next batches while the counts of this one are resolved."""
+        for _ in self.iter_run(frames, sub_area, uploader):
+            pass
+        return self.intervals
+
+    def iter_run(self, frames, sub_area, uploader=None):
+        """run() as a generator: per staged batch (items, the intervals its rows closed), items = [(full frame, its area rows)] in
+        decode order, so a caller that may need a frame again receives it with the batch itself; after the last batch one more
+        ([], the interval the end of the clip closed).  `tracker` (IntervalTracker) is in step with what has been yielded;
+        `intervals` grows as they close, `counts` is set when the generator is exhausted."""
         import numpy as np
         if self.count_fn is None:
             from . import shim
             self.count_fn = EngineCounter(shim._context())
+        self.counts, self.intervals, self.tracker = np.zeros((0, 3), np.int32), [], None
         it = iter(frames)
         first = next(it, None)
         if first is None:
-            self.counts, self.intervals = np.zeros((0, 3), np.int32), []
-            return self.intervals
+            return
         h, w = first.shape[:2]
         y0, y1, x0, x1 = clip_area(sub_area, h, w)
         if y1 - y0 < 3 or x1 - x0 < 3:
             raise ValueError(f"ChangeFrameSelector: subtitle area {sub_area} leaves less than 3 x 3 pixels of a {h} x {w} frame")
         area = (0, y1 - y0, x0, x1)
+        min_edges = default_min_edges(y1 - y0, x1 - x0) if self.min_edges is None else self.min_edges
+        self.tracker = IntervalTracker(min_edges, self.change_ratio, self.min_frames)
 
-        def batches():
-            buf = [(None, first[y0:y1])]
+        def batches(buf):
             for f in it:
                 if len(buf) == self.batch:
                     yield buf
                     buf = []
-                buf.append((None, f[y0:y1]))
-            if buf:
-                yield buf
+                buf.append((f, f[y0:y1]))
+            yield buf
 
-        out = []
+        todo = batches([(first, first[y0:y1])])
+        del first                         # a caller that drops a frame it was handed frees it
         if uploader is not None:
             from . import staging
-            for k, (_items, staged) in enumerate(staging.prefetch(batches(), uploader)):
-                out.append(np.asarray(self._host(self.count_fn(staged.tensor(), area, self.edge_thresh, k == 0))))
+            staged = ((items, sb.tensor) for items, sb in staging.prefetch(todo, uploader))
         else:
-            for k, items in enumerate(batches()):
-                out.append(np.asarray(self._host(self.count_fn(np.stack([f for _, f in items]), area, self.edge_thresh, k == 0))))
+            staged = ((items, lambda items=items: np.stack([band for _, band in items])) for items in todo)
+        out = []
+        for k, (items, data) in enumerate(staged):
+            out.append(np.asarray(self._host(self.count_fn(data(), area, self.edge_thresh, k == 0))))
+            closed = self.tracker.feed(out[-1])
+            self.intervals += closed
+            yield items, closed
         self.counts = np.concatenate(out)
-        min_edges = default_min_edges(y1 - y0, x1 - x0) if self.min_edges is None else self.min_edges
-        self.intervals = change_intervals(self.counts, min_edges, self.change_ratio, self.min_frames)
-        return self.intervals
+        closed = self.tracker.flush()
+        self.intervals += closed
+        yield [], closed
 
     @staticmethod
     def _host(c):
@@ -375,6 +410,15 @@ class HoldFrameSelector:
         """frames: iterable of uint8 BGR frames in decode order; sub_area: .ymin .ymax .xmin .xmax in frame pixels (clipped to the
         frame); fps: the clip's frame rate (for hold_seconds) -> [(start, end, rep)].  Batches are staged as ChangeFrameSelector.run
         stages them; after the last one a call without frames flushes the rows still pending."""
+        for _ in self.iter_run(frames, sub_area, fps, uploader):
+            pass
+        return self.intervals
+
+    def iter_run(self, frames, sub_area, fps, uploader=None):
+        """run() as a generator, as ChangeFrameSelector.iter_run: per staged batch (items = [(full frame, its area rows)], the intervals
+        its rows closed), then ([], what the flushed rows and the end of the clip closed).  The rows of a batch trail its frames by
+        hold - 1 until the flush: `tracker.fed` is the last frame whose row has been seen, and the frames behind it are still the
+        caller's to keep."""
         import numpy as np
         if self.count_fn is None:
             from . import shim
@@ -383,44 +427,52 @@ class HoldFrameSelector:
         if not 1 <= hold <= 32:
             raise ValueError(f"HoldFrameSelector: hold_frames must be 1..32, not {hold}")
         self.hold = hold
+        self.counts, self.intervals, self.tracker = np.zeros((0, 3), np.int32), [], None
         it = iter(frames)
         first = next(it, None)
         if first is None:
-            self.counts, self.intervals = np.zeros((0, 3), np.int32), []
-            return self.intervals
+            return
         h, w = first.shape[:2]
         y0, y1, x0, x1 = clip_area(sub_area, h, w)
         if y1 - y0 < 3 or x1 - x0 < 3:
             raise ValueError(f"HoldFrameSelector: subtitle area {sub_area} leaves less than 3 x 3 pixels of a {h} x {w} frame")
         area = (0, y1 - y0, x0, x1)
+        min_edges = default_min_edges(y1 - y0, x1 - x0) if self.min_edges is None else self.min_edges
+        self.tracker = IntervalTracker(min_edges, self.change_ratio, max(self.min_frames, hold))      # (hold_intervals' min_frames)
 
-        def batches():
-            buf = [(None, first[y0:y1])]
+        def batches(buf):
             for f in it:
                 if len(buf) == self.batch:
                     yield buf
                     buf = []
-                buf.append((None, f[y0:y1]))
+                buf.append((f, f[y0:y1]))
             yield buf
+
+        todo = batches([(first, first[y0:y1])])
+        del first                         # a caller that drops a frame it was handed frees it
+
+        def rows(c):
+            return np.asarray(self._host(c), np.int32).reshape(-1, 3)
 
         out, fed = [], 0
         if uploader is not None:
             from . import staging
-            staged = None
-            for items, staged in staging.prefetch(batches(), uploader):
-                out.append(self._host(self.count_fn(staged.tensor(), area, self.edge_thresh, hold, fed, False)))
-                fed += len(items)
-            empty = staged.tensor()[:0]
+            staged = ((items, sb.tensor) for items, sb in staging.prefetch(todo, uploader))
         else:
-            for items in batches():
-                out.append(self._host(self.count_fn(np.stack([f for _, f in items]), area, self.edge_thresh, hold, fed, False)))
-                fed += len(items)
-            empty = np.zeros((0, y1 - y0, w, 3), np.uint8)
-        out.append(self._host(self.count_fn(empty, area, self.edge_thresh, hold, fed, True)))
-        self.counts = np.concatenate([np.asarray(c, np.int32).reshape(-1, 3) for c in out])
-        min_edges = default_min_edges(y1 - y0, x1 - x0) if self.min_edges is None else self.min_edges
-        self.intervals = hold_intervals(self.counts, min_edges, hold, self.change_ratio, self.min_frames)
-        return self.intervals
+            staged = ((items, lambda items=items: np.stack([band for _, band in items])) for items in todo)
+        data = None
+        for items, get in staged:
+            data = get()
+            out.append(rows(self.count_fn(data, area, self.edge_thresh, hold, fed, False)))
+            fed += len(items)
+            closed = self.tracker.feed(out[-1])
+            self.intervals += closed
+            yield items, closed
+        out.append(rows(self.count_fn(data[:0], area, self.edge_thresh, hold, fed, True)))
+        self.counts = np.concatenate(out)
+        closed = self.tracker.feed(out[-1]) + self.tracker.flush()
+        self.intervals += closed
+        yield [], closed
 
     _host = staticmethod(ChangeFrameSelector._host)
 

@@ -20,7 +20,12 @@ staging.Uploader packs into its pinned slab, uploads at half the bytes of a BGR 
 same integers on both routes.  The conversion is BT.601 limited range with NEAREST chroma (the fixed-point constants of cv2.cvtColor
 COLOR_YUV2BGR_I420 / _NV12; the formula is in include/vse_hip.h).  The reference's cv2.VideoCapture converts with swscale: the same
 matrix, but a chroma up-sampling filter instead of the nearest sample, so these frames are NOT swscale's bits at chroma edges (luma-only
-content is).  Full-range (JPEG) YUV, 4:2:2 / 4:4:4 and more than 8 bits are refused; pipes are out of scope (a clip is read twice).
+content is).  matrix="bt709" on a frame or a source swaps the chroma factors for BT.709's (vse_yuv_to_bgr_matrix; HD encodes normally carry
+it); the default stays "bt601" because Y4M has no matrix tag.  Full-range (JPEG) YUV, 4:2:2 / 4:4:4 and more than 8 bits are refused.
+
+Pipes (Y4mStream): `ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m vse_amd.extractor -` puts compressed video of any
+codec through a decoder that is not ours; the stream is read once, front to back, never seeks and has no read(): its absence is how
+SubtitleExtractor sees that it must work in one pass.
 """
 import mmap
 import os
@@ -226,6 +231,14 @@ class NpySource:
 
 # ---- YUV 4:2:0 ------------------------------------------------------------------------------------------------------------------
 YUV_LAYOUTS = ("i420", "nv12")
+# chroma factors (B from u, G from u, G from v, R from v) of include/vse_hip.h: vse_yuv420_to_bgr / vse_yuv_to_bgr_matrix
+YUV_MATRICES = {"bt601": (2116026, -409993, -852492, 1673527), "bt709": (2215014, -223607, -558796, 1879825)}
+
+
+def _check_matrix(matrix):
+    if matrix not in YUV_MATRICES:
+        raise ValueError(f"matrix must be one of {tuple(YUV_MATRICES)}, not {matrix!r}")
+    return matrix
 
 
 def _chroma_size(height, width):
@@ -237,11 +250,13 @@ class Yuv420Frame:
     `width` and `layout` ("i420": planes = (Y [H,W], U [ch,cw], V [ch,cw]); "nv12": planes = (Y [H,W], UV [ch,2 cw])).
     It stands where a BGR frame stands in the callers that only look at `.shape` and cut row bands: shape == (y1 - y0, width, 3),
     frame[a:b] narrows the row range (one slice, step 1, Python slice rules; any other index is a TypeError), to_bgr() gives the
-    uint8 BGR ndarray, pack_into() the packed sub-frame vse_yuv420_to_bgr takes."""
+    uint8 BGR ndarray, pack_into() the packed sub-frame vse_yuv420_to_bgr takes.  `matrix` ("bt601" | "bt709") names the conversion
+    and travels with the slices."""
 
-    def __init__(self, planes, height, width, layout="i420", y0=0, y1=None):
+    def __init__(self, planes, height, width, layout="i420", y0=0, y1=None, matrix="bt601"):
         if layout not in YUV_LAYOUTS:
             raise ValueError(f"layout must be one of {YUV_LAYOUTS}, not {layout!r}")
+        self.matrix = _check_matrix(matrix)
         self.planes, self.height, self.width, self.layout = tuple(planes), int(height), int(width), layout
         self.y0, self.y1 = int(y0), int(self.height if y1 is None else y1)
         ch, cw = _chroma_size(self.height, self.width)
@@ -260,7 +275,7 @@ class Yuv420Frame:
         a, b, step = idx.indices(self.y1 - self.y0)
         if step != 1:
             raise TypeError(f"a Yuv420Frame takes a row slice of step 1, not {idx!r}")
-        return Yuv420Frame(self.planes, self.height, self.width, self.layout, self.y0 + a, self.y0 + max(a, b))
+        return Yuv420Frame(self.planes, self.height, self.width, self.layout, self.y0 + a, self.y0 + max(a, b), self.matrix)
 
     @property
     def row_parity(self):
@@ -285,8 +300,10 @@ class Yuv420Frame:
             pos += part.size
         return pos
 
-    def to_bgr(self):
-        """uint8 BGR [y1 - y0, W, 3]: BT.601 limited range, nearest chroma, the integers of vse_yuv420_to_bgr (include/vse_hip.h)."""
+    def to_bgr(self, matrix=None):
+        """uint8 BGR [y1 - y0, W, 3]: limited range, nearest chroma, the integers of vse_yuv420_to_bgr / vse_yuv_to_bgr_matrix
+        (include/vse_hip.h) for `matrix` (default: the frame's own)."""
+        bu, gu, gv, rv = YUV_MATRICES[_check_matrix(self.matrix if matrix is None else matrix)]
         rows, cols = np.arange(self.y0, self.y1) >> 1, np.arange(self.width) >> 1
         y = self.planes[0][self.y0:self.y1].astype(np.int32)
         if self.layout == "i420":
@@ -298,9 +315,9 @@ class Yuv420Frame:
         u -= 128
         v -= 128
         out = np.empty(self.shape, np.uint8)
-        out[..., 0] = np.clip((c + 2116026 * u) >> 20, 0, 255)
-        out[..., 1] = np.clip((c - 409993 * u - 852492 * v) >> 20, 0, 255)
-        out[..., 2] = np.clip((c + 1673527 * v) >> 20, 0, 255)
+        out[..., 0] = np.clip((c + bu * u) >> 20, 0, 255)
+        out[..., 1] = np.clip((c + gu * u + gv * v) >> 20, 0, 255)
+        out[..., 2] = np.clip((c + rv * v) >> 20, 0, 255)
         return out
 
 
@@ -357,6 +374,8 @@ def write_yuv420(path, frames_yuv, layout="i420"):
 class _Yuv420FileSource:
     """The frame-source interface over a memory-mapped file whose frames start at self._offsets (packed I420 or NV12 pictures)."""
 
+    matrix = "bt601"
+
     def _map(self, path):
         self.path = path
         self._fp = open(path, "rb")
@@ -382,7 +401,7 @@ class _Yuv420FileSource:
             planes = (luma, self._buf[off:off + ch * cw].reshape(ch, cw), self._buf[off + ch * cw:off + 2 * ch * cw].reshape(ch, cw))
         else:
             planes = (luma, self._buf[off:off + 2 * ch * cw].reshape(ch, 2 * cw))
-        return Yuv420Frame(planes, h, w, self.layout)
+        return Yuv420Frame(planes, h, w, self.layout, matrix=self.matrix)
 
     def read(self, frame_no):
         raw = self.read_raw(frame_no)
@@ -411,45 +430,52 @@ class _Yuv420FileSource:
         self._fp.close()
 
 
+def parse_y4m_header(line, name, fps=None, what="file"):
+    """The stream header `line` (bytes up to, not including, its newline; None when there is none within 4096 bytes) of the YUV4MPEG2
+    file or stream `name` -> (width, height, fps).  8-bit 4:2:0 progressive limited-range only: the tokens W H F (F0:0 or none: pass
+    fps) I (p, ? or absent) A (ignored) C (absent, 420, 420jpeg, 420mpeg2, 420paldv; the siting they name is ignored, see the module
+    docstring) X... (ignored, except XCOLORRANGE=FULL, which is refused)."""
+    if line is None or line[:10] != b"YUV4MPEG2 ":
+        raise ValueError(f"{name}: not a YUV4MPEG2 {what}")
+    width = height = rate = None
+    for tok in line[10:].decode("ascii", "replace").split():
+        key, val = tok[0], tok[1:]
+        if key == "W":
+            width = int(val)
+        elif key == "H":
+            height = int(val)
+        elif key == "F":
+            num, _, den = val.partition(":")
+            if int(num) > 0 and int(den or 1) > 0:
+                rate = int(num) / float(int(den or 1))
+        elif key == "I":
+            if val not in ("p", "?"):
+                raise ValueError(f"{name}: interlaced video ({tok}) is not supported")
+        elif key == "C":
+            if val not in ("420", "420jpeg", "420mpeg2", "420paldv"):
+                raise ValueError(f"{name}: chroma format {tok} is not supported, only 8-bit 4:2:0 (C420, C420jpeg, C420mpeg2, C420paldv)")
+        elif tok == "XCOLORRANGE=FULL":
+            raise ValueError(f"{name}: full-range video ({tok}) needs other conversion constants and is not supported")
+    if not width or not height or width < 1 or height < 1:
+        raise ValueError(f"{name}: the YUV4MPEG2 header carries no frame size")
+    if fps is not None:
+        rate = float(fps)
+    if rate is None:
+        raise ValueError(f"{name}: the YUV4MPEG2 header carries no frame rate (F0:0 or no F token): pass fps")
+    return width, height, rate
+
+
 class Y4mSource(_Yuv420FileSource):
-    """YUV4MPEG2 (.y4m) reader, memory-mapped, frames indexed once at open.  8-bit 4:2:0 progressive limited-range only: the header
-    tokens W H F (F0:0 or none: pass fps) I (p, ? or absent) A (ignored) C (absent, 420, 420jpeg, 420mpeg2, 420paldv; the siting they
-    name is ignored, see the module docstring) X... (ignored, except XCOLORRANGE=FULL, which is refused)."""
+    """YUV4MPEG2 (.y4m) reader, memory-mapped, frames indexed once at open.  The header is parse_y4m_header's."""
 
     layout = "i420"
 
-    def __init__(self, path, fps=None):
+    def __init__(self, path, fps=None, matrix="bt601"):
+        self.matrix = _check_matrix(matrix)
         size = self._map(path)
         mm = self._mm
         end = mm.find(b"\n", 0, 4096) if size else -1
-        if end < 0 or mm[:10] != b"YUV4MPEG2 ":
-            raise ValueError(f"{path}: not a YUV4MPEG2 file")
-        self.width = self.height = None
-        self.fps = None
-        for tok in mm[10:end].decode("ascii", "replace").split():
-            key, val = tok[0], tok[1:]
-            if key == "W":
-                self.width = int(val)
-            elif key == "H":
-                self.height = int(val)
-            elif key == "F":
-                num, _, den = val.partition(":")
-                if int(num) > 0 and int(den or 1) > 0:
-                    self.fps = int(num) / float(int(den or 1))
-            elif key == "I":
-                if val not in ("p", "?"):
-                    raise ValueError(f"{path}: interlaced video ({tok}) is not supported")
-            elif key == "C":
-                if val not in ("420", "420jpeg", "420mpeg2", "420paldv"):
-                    raise ValueError(f"{path}: chroma format {tok} is not supported, only 8-bit 4:2:0 (C420, C420jpeg, C420mpeg2, C420paldv)")
-            elif tok == "XCOLORRANGE=FULL":
-                raise ValueError(f"{path}: full-range video ({tok}) needs other conversion constants and is not supported")
-        if not self.width or not self.height or self.width < 1 or self.height < 1:
-            raise ValueError(f"{path}: the YUV4MPEG2 header carries no frame size")
-        if fps is not None:
-            self.fps = float(fps)
-        if self.fps is None:
-            raise ValueError(f"{path}: the YUV4MPEG2 header carries no frame rate (F0:0 or no F token): pass fps")
+        self.width, self.height, self.fps = parse_y4m_header(mm[:end] if end >= 0 else None, path, fps)
         nbytes = self._frame_bytes()
         self._offsets = []
         pos = end + 1
@@ -471,13 +497,97 @@ class Y4mSource(_Yuv420FileSource):
         self.frame_count = len(self._offsets)
 
 
+class Y4mStream:
+    """Y4mSource for a pipe: YUV4MPEG2 from any binary file object (sys.stdin.buffer, a pipe, a socket file), read once, front to back.
+    It never seeks and never asks for a size.  raw_frames() yields the Yuv420Frames in decode order, each owning its bytes (one buffer per
+    frame, filled by readinto until it is full: short reads are normal on a pipe); frames() yields their to_bgr().  There is no read /
+    read_raw: their absence is how a caller sees that the source is sequential.  frame_count is None until the stream is exhausted, then
+    the number of whole frames read; a stream that ends inside a FRAME header or inside a frame drops that partial frame, as Y4mSource
+    does; anything else where FRAME should stand is a ValueError naming the byte offset in the stream."""
+
+    layout = "i420"
+
+    def __init__(self, fileobj, fps=None, matrix="bt601", name="<stream>"):
+        self.matrix = _check_matrix(matrix)
+        self._fp, self.name = fileobj, name
+        self._pos = 0                 # bytes of the stream consumed
+        self._started = False
+        line = self._line(4096)
+        self.width, self.height, self.fps = parse_y4m_header(line, name, fps, what="stream")
+        self.frame_count = None
+
+    def _fill(self, view):
+        """readinto until `view` is full -> bytes read (less than len(view): the stream ended)."""
+        got = 0
+        while got < len(view):
+            n = self._fp.readinto(view[got:])
+            if not n:
+                break
+            got += n
+        self._pos += got
+        return got
+
+    def _line(self, limit):
+        """Bytes up to the next newline (consumed, not returned), at most `limit` of them; None when there is none (the stream ended, or
+        the line is longer); self._short then tells which."""
+        out = bytearray()
+        one = memoryview(bytearray(1))
+        self._short = False
+        while len(out) < limit:
+            if self._fill(one) < 1:
+                self._short = True
+                return None
+            if one[0] == 10:
+                return bytes(out)
+            out.append(one[0])
+        return None
+
+    def raw_frames(self):
+        if self._started:
+            raise ValueError(f"{self.name}: a Y4mStream is read once")
+        self._started = True
+        h, w = self.height, self.width
+        ch, cw = _chroma_size(h, w)
+        nbytes, count = h * w + 2 * ch * cw, 0
+        head = memoryview(bytearray(6))
+        while True:
+            pos = self._pos
+            got = self._fill(head)
+            if got < 6 and b"FRAME"[:got] == bytes(head[:min(got, 5)]):
+                break                      # the stream ends here, or inside a frame header: a truncated last frame
+            if bytes(head[:5]) != b"FRAME" or bytes(head[5:6]) not in (b" ", b"\n"):
+                raise ValueError(f"{self.name}: bytes at offset {pos} are neither a FRAME header nor the end of the stream")
+            if head[5] != 10 and self._line(4096 - 6) is None:
+                if self._short:
+                    break                  # truncated inside the frame header's parameters
+                raise ValueError(f"{self.name}: the FRAME header at offset {pos} does not end")
+            buf = np.empty(nbytes, np.uint8)
+            if self._fill(memoryview(buf)) < nbytes:
+                break                      # a truncated last frame is not a frame
+            count += 1
+            planes = (buf[:h * w].reshape(h, w), buf[h * w:h * w + ch * cw].reshape(ch, cw), buf[h * w + ch * cw:].reshape(ch, cw))
+            yield Yuv420Frame(planes, h, w, "i420", matrix=self.matrix)
+        self.frame_count = count
+
+    def frames(self):
+        for raw in self.raw_frames():
+            yield raw.to_bgr()
+
+    def pos_msec(self, frame_no):
+        """As _Yuv420FileSource.pos_msec once the stream is exhausted; before that every frame number from 0 up has a time stamp."""
+        if frame_no < 0 or (self.frame_count is not None and frame_no >= self.frame_count):
+            return None
+        return frame_no * 1000.0 / self.fps
+
+
 class Yuv420Source(_Yuv420FileSource):
     """Headerless file of consecutive 8-bit 4:2:0 frames (layout "i420": Y, U, V planes; "nv12": Y plane, interleaved UV plane), memory-
     mapped.  A partial last frame is dropped."""
 
-    def __init__(self, path, width, height, fps, layout="i420"):
+    def __init__(self, path, width, height, fps, layout="i420", matrix="bt601"):
         if layout not in YUV_LAYOUTS:
             raise ValueError(f"layout must be one of {YUV_LAYOUTS}, not {layout!r}")
+        self.matrix = _check_matrix(matrix)
         self.width, self.height, self.fps, self.layout = int(width), int(height), float(fps), layout
         if self.width < 1 or self.height < 1:
             raise ValueError(f"{path}: frame size {width} x {height}")
@@ -490,20 +600,24 @@ class Yuv420Source(_Yuv420FileSource):
 _RAW_YUV_EXT = {".yuv": "i420", ".i420": "i420", ".nv12": "nv12"}
 
 
-def open_source(path, fps=None, size=None, layout=None):
+def open_source(path, fps=None, size=None, layout=None, matrix="bt601"):
     """The source of a file by its extension: .npy (needs fps), .y4m, .yuv / .i420 / .nv12 (headerless: need size=(width, height) and
-    fps; `layout` overrides the extension's), anything else an AVI."""
+    fps; `layout` overrides the extension's), anything else an AVI; "-" is a Y4mStream over standard input.  `matrix` goes to the
+    YUV 4:2:0 sources."""
+    if str(path) == "-":
+        import sys
+        return Y4mStream(sys.stdin.buffer, fps, matrix, name="<stdin>")
     ext = os.path.splitext(str(path))[1].lower()
     if str(path).endswith(".npy"):
         if fps is None:
             raise ValueError("a .npy frame stack carries no frame rate: pass fps")
         return NpySource(path, fps)
     if ext == ".y4m":
-        return Y4mSource(path, fps)
+        return Y4mSource(path, fps, matrix)
     if ext in _RAW_YUV_EXT:
         if size is None:
             raise ValueError(f"{path}: a headerless YUV file carries no frame size: pass size=(width, height)")
         if fps is None:
             raise ValueError(f"{path}: a headerless YUV file carries no frame rate: pass fps")
-        return Yuv420Source(path, size[0], size[1], fps, layout or _RAW_YUV_EXT[ext])
+        return Yuv420Source(path, size[0], size[1], fps, layout or _RAW_YUV_EXT[ext], matrix)
     return AviBgr24Source(path)

@@ -13,7 +13,8 @@ producer thread while the current one is recognised (`prefetch`).
 
 Frames that are still YUV 4:2:0 (ingest.Yuv420Frame, from a source's read_raw / raw_frames) are packed into the slab as they are — 1.5
 bytes per pixel, half the slab copy and half the PCIe bytes of a BGR frame — and converted to BGR by one kernel on the copy stream
-(vse_yuv420_to_bgr), so a consumer sees the same uint8 [n,H,W,3] tensor either way.
+(vse_yuv420_to_bgr, or vse_yuv_to_bgr_matrix for frames that say matrix="bt709"), so a consumer sees the same uint8 [n,H,W,3] tensor
+either way.
 """
 import queue
 import threading
@@ -40,7 +41,7 @@ class Uploader:
         import torch
         self.device = torch.device(device)
         self._ctx = ctx
-        self.depth = depth
+        self.depth, self.workers = depth, workers
         self._slabs = [None] * depth            # pinned uint8 buffers, grown on demand
         self._busy = [None] * depth             # event of the last copy out of each slab
         self._k = 0
@@ -87,15 +88,16 @@ class Uploader:
         return self._ctx
 
     def _stage_yuv420(self, frames):
-        """Yuv420Frames of one shape, layout and row parity -> StagedBatch of their BGR conversion: packed into the slab (frame stride
-        rounded up to 16 bytes, which the 16-byte kernel needs), one copy, one vse_yuv420_to_bgr on the copy stream."""
+        """Yuv420Frames of one shape, layout, row parity and matrix -> StagedBatch of their BGR conversion: packed into the slab (frame
+        stride rounded up to 16 bytes, which the 16-byte kernel needs), one copy, one vse_yuv420_to_bgr (BT.601) or vse_yuv_to_bgr_matrix
+        (BT.709) on the copy stream."""
         import torch
         first = frames[0]
-        key = (tuple(first.shape), first.layout, first.row_parity)
+        key = (tuple(first.shape), first.layout, first.row_parity, first.matrix)
         for f in frames:
-            if not hasattr(f, "pack_into") or (tuple(f.shape), f.layout, f.row_parity) != key:
-                raise ValueError("Uploader.stage: the YUV 4:2:0 frames of a batch must share shape, layout and row parity (y0 & 1): "
-                                 f"{key} and {(tuple(f.shape), getattr(f, 'layout', None), getattr(f, 'row_parity', None))}")
+            if not hasattr(f, "pack_into") or (tuple(f.shape), f.layout, f.row_parity, f.matrix) != key:
+                raise ValueError("Uploader.stage: the YUV 4:2:0 frames of a batch must share shape, layout, row parity (y0 & 1) and matrix: "
+                                 f"{key} and {(tuple(f.shape), getattr(f, 'layout', None), getattr(f, 'row_parity', None), getattr(f, 'matrix', None))}")
         ctx = self._context()
         n, (h, w, _) = len(frames), first.shape
         per = (first.packed_bytes + 15) & ~15
@@ -108,11 +110,16 @@ class Uploader:
             # this stream, behind the conversion, so it may be dropped here (`dev` crosses streams: StagedBatch.tensor records that)
             packed = torch.empty((n, per), dtype=torch.uint8, device=self.device)
             packed.copy_(host, non_blocking=True)
-            dev = ctx.yuv420_to_bgr(packed, n, h, w, first.layout, first.row_parity)
+            dev = ctx.yuv420_to_bgr(packed, n, h, w, first.layout, first.row_parity, matrix=first.matrix)
             ev = torch.cuda.Event()
             ev.record(self._stream)
         self._busy[k] = ev
         return StagedBatch(dev, ev)
+
+    def sibling(self):
+        """Another Uploader on the same device and context, with slabs of its own: stage() hands its slabs out in turn and is meant for
+        ONE producer thread; a second producer at the same time (one pass: the selector's bands and the recogniser's frames) takes this."""
+        return Uploader(self.device, self.depth, self.workers, self._ctx)
 
     def bind_thread(self):
         """called once by a thread that is going to stage batches"""
