@@ -294,6 +294,29 @@ int vse_frame_cells(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w
                     int32_t* d_cell_counts /* nullable: [n,gy,gx,3] edges, appeared, vanished per frame and cell */,
                     void* stream);
 
+/* ---- edge-threshold calibration ---------------------------------------------------------------------------------------- */
+/* Replaces: nothing in the reference, which has no edge threshold; it serves the selectors and the locator above, whose constant
+ * edge_thresh = 128 describes white text with a black outline and finds nothing on yellow, shadowed, unoutlined or washed-out
+ * subtitles.  vse_frame_cells for nt thresholds (1 <= nt <= 8, ascending, distinct, each 1..255; a host array) in ONE pass over the
+ * frames: every pixel's bytes are read and its luma and gradient computed once per frame, and only the comparison, the cells' mask
+ * words, counts and automata are kept per threshold.  The host picks a threshold from the totals
+ * (vse_amd.area_locator.pick_edge_thresh).
+ * d_totals int32 [nt, gy, gx, 4]: d_totals[k] holds exactly the integers vse_frame_cells with edge_thresh = thresholds[k] leaves in
+ * its d_totals for the same frames, call sequence, `reset` and `flush` (batches of any sizes give the totals of one call; n == 0 with
+ * `flush` only closes the open runs).  There is no per-frame output.  d_state: vse_frame_cells_multi_state_bytes(area_h, area_w, nt)
+ * bytes, 8-byte aligned, zero-filled when fresh: nt times vse_frame_cells' state, threshold k's slice laid out as that one (0 for a
+ * region below 3 x 3 or nt outside 1..8).  A state belongs to one region size and one nt; the same thresholds go to every call of a clip.
+ * One launch on `stream`, no allocation, no device sync; a block owns its cell for all frames of the call and alone writes the cell's
+ * state and totals, for all thresholds.  Returns VSE_E_INVAL, without touching the device, for everything vse_frame_cells refuses,
+ * nt outside 1..8, thresholds NULL, not strictly ascending, or one outside 1..255. */
+size_t vse_frame_cells_multi_state_bytes(int area_h, int area_w, int nt);
+int vse_frame_cells_multi(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride,
+                          int y0, int y1, int x0, int x1, const int* thresholds /* host, [nt] */, int nt,
+                          int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
+                          void* d_state, int reset, int flush,
+                          int32_t* d_totals /* [nt,gy,gx,4]: covered, runs, present, cuts; accumulated across calls */,
+                          void* stream);
+
 /* ---- held-edge frame selector ------------------------------------------------------------------------------------------- */
 /* Replaces: the same frame search of VideoSubFinder as vse_frame_change (backend/main.py:378-505, extract_frame_by_vsf), for
  * footage whose background moves behind the subtitle.  vse_frame_change compares every edge pixel of the area with the frame

@@ -20,13 +20,28 @@ of a real film, with hard-coded logos, tickers or busy static scenery, is unmeas
   static_frac 0.95                    a cell present in 95 % of the scanned frames is a logo (clips shorter than max_seconds);
   pad_cells 1                         the rectangle is as coarse as the cells are, and the OCR filter wants the whole box inside.
 
-    python -m vse_amd.area_locator VIDEO [--fps F --size WxH --layout i420|nv12] [--probe START COUNT] [--json]
+Edge threshold per clip (edge_thresh="auto").  128 describes white text with a black outline; yellow text, a soft shadow, no outline
+over a bright scene or a washed-out transfer put the text's gradient below it, and then no cell ever holds an edge: no area, no
+intervals, an empty SRT.  The locator's own statistic tells working thresholds from failing ones (too high: nothing is an edge; too
+low: the noise becomes edges that change every frame, and every frame is a cut), so the device evaluates several thresholds in the
+same single pass (vse_frame_cells_multi: the bytes are read and the gradient computed once) and `pick_edge_thresh` takes the middle
+of the plateau of thresholds whose best grid row scores at least plateau_frac of the best one:
+  thresholds 24 32 48 64 96 128 160 192   about half an octave apart around the constant;
+  plateau_frac 0.9                        a judgement like the defaults above, not a measurement.
+With search_area set to a known subtitle area this is the calibration for a film whose box the user drew.
+Known limits: the calibration runs the CHANGE automaton.  On a moving textured background every frame is a cut at every threshold,
+nothing scores, and it falls back to 128 with a warning (a calibration on held edges is not part of this).  How the rule behaves on
+real footage is unmeasured: there are no real clips here.
 
-prints `ymin ymax xmin xmax`; VIDEO is what ingest.open_source reads.
+    python -m vse_amd.area_locator VIDEO [--fps F --size WxH --layout i420|nv12] [--probe START COUNT] [--edge-thresh auto|N] [--json]
+
+prints `ymin ymax xmin xmax` (and the chosen threshold as a fifth number when `--edge-thresh auto` was asked); VIDEO is what
+ingest.open_source reads.
 """
 import argparse
 import itertools
 import json
+import logging
 import sys
 from fractions import Fraction
 
@@ -35,11 +50,47 @@ import numpy as np
 from .engine import CellParams
 
 CELL_H, CELL_W = 8, 64          # interior pixels of a cell (the tile of csrc/frame_change.hip)
+AUTO_THRESHOLDS = (24, 32, 48, 64, 96, 128, 160, 192)      # what edge_thresh="auto" chooses from
+DEFAULT_EDGE_THRESH = 128       # the selectors' constant, and what "auto" falls back to when no threshold scores
 
 
 def cells_dims(area_h, area_w):
     """(gy, gx) of a region of area_h x area_w pixels: vse_frame_cells_dims."""
     return (area_h - 2 + CELL_H - 1) // CELL_H, (area_w - 2 + CELL_W - 1) // CELL_W
+
+
+def _covered(totals, frames_scanned, static_frac):
+    """int64 [..., gy, gx, 4] -> covered per cell after the logo rule: a cell present in static_frac of the frames counts 0."""
+    return np.where(totals[..., 2] >= static_frac * frames_scanned, 0, totals[..., 0])
+
+
+def edge_thresh_scores(totals, frames_scanned, static_frac=0.95):
+    """totals: int [nt,gy,gx,4] -> [nt] ints: per threshold the largest grid-row sum of covered after the logo rule, which is
+    locate_area's `best` on that threshold's totals."""
+    totals = np.asarray(totals, np.int64)
+    if totals.ndim != 4 or totals.shape[3] != 4:
+        raise ValueError(f"edge_thresh_scores: totals of shape {totals.shape}, not [nt, gy, gx, 4]")
+    return [int(v) for v in _covered(totals, frames_scanned, static_frac).sum(2).max(1)]
+
+
+def pick_edge_thresh(totals, thresholds, frames_scanned, static_frac=0.95, plateau_frac=0.9):
+    """totals: int [nt,gy,gx,4] of vse_frame_cells_multi at the ascending `thresholds` -> the index of the threshold to use, or None
+    when no threshold scores.  A pure function of integers: score[k] = edge_thresh_scores; the working set is the maximal contiguous
+    run of k around the arg-max (ties: the threshold nearest 128, then the lower one) with score[k] >= plateau_frac * max(score);
+    the result is that run's element (len - 1) // 2, the middle of the plateau, so that the choice has margin on both sides."""
+    thresholds = [int(v) for v in thresholds]
+    scores = edge_thresh_scores(totals, frames_scanned, static_frac)
+    if len(scores) != len(thresholds):
+        raise ValueError(f"pick_edge_thresh: totals for {len(scores)} thresholds, {len(thresholds)} given")
+    best = max(scores)
+    if best <= 0:
+        return None
+    k0 = k1 = min((k for k in range(len(scores)) if scores[k] == best), key=lambda k: (abs(thresholds[k] - DEFAULT_EDGE_THRESH), k))
+    while k0 > 0 and scores[k0 - 1] >= plateau_frac * best:
+        k0 -= 1
+    while k1 < len(scores) - 1 and scores[k1 + 1] >= plateau_frac * best:
+        k1 += 1
+    return k0 + (k1 - k0) // 2
 
 
 def locate_area(totals, frames_scanned, region, frame_hw, row_frac=0.25, col_frac=0.05, static_frac=0.95, pad_cells=1):
@@ -59,7 +110,7 @@ def locate_area(totals, frames_scanned, region, frame_hw, row_frac=0.25, col_fra
     gy, gx = cells_dims(y1 - y0, x1 - x0)
     if totals.shape != (gy, gx, 4):
         raise ValueError(f"locate_area: totals of shape {totals.shape} for a region of {gy} x {gx} cells")
-    covered = np.where(totals[..., 2] >= static_frac * frames_scanned, 0, totals[..., 0])
+    covered = _covered(totals, frames_scanned, static_frac)
     row_score = covered.sum(1)
     best = int(row_score.max())
     if best <= 0:
@@ -81,24 +132,28 @@ def locate_area(totals, frames_scanned, region, frame_hw, row_frac=0.25, col_fra
 
 
 class EngineCells:
-    """cells_fn of AreaLocator on the GPU (Context.frame_cells): keeps the device state of the last region between calls."""
+    """cells_fn of AreaLocator on the GPU (Context.frame_cells; with `thresholds`, Context.frame_cells_multi): keeps the device state
+    of the last region (and threshold count) between calls."""
 
     def __init__(self, ctx):
         self.ctx = ctx
         self._state = None
         self._key = None
 
-    def __call__(self, frames, area, params, reset, flush):
+    def __call__(self, frames, area, params, reset, flush, thresholds=None):
         t = self.ctx.torch
         y0, y1, x0, x1 = area
         if frames is None:
             frames = t.empty((0, y1, x1, 3), dtype=t.uint8, device=self.ctx.tdev)
         elif not t.is_tensor(frames):
             frames = t.from_numpy(np.ascontiguousarray(frames)).to(self.ctx.tdev)
-        if self._key != (y1 - y0, x1 - x0):
-            self._key = (y1 - y0, x1 - x0)
-            self._state = self.ctx.frame_cells_state(*self._key)
+        nt = None if thresholds is None else len(thresholds)
+        if self._key != (y1 - y0, x1 - x0, nt):
+            self._key = (y1 - y0, x1 - x0, nt)
+            self._state = self.ctx.frame_cells_state(y1 - y0, x1 - x0) if nt is None else self.ctx.frame_cells_multi_state(y1 - y0, x1 - x0, nt)
             reset = True
+        if nt is not None:
+            return self.ctx.frame_cells_multi(frames, area, thresholds, params, self._state, reset, flush)
         return self.ctx.frame_cells(frames, area, params, self._state, reset, flush)
 
 
@@ -109,12 +164,22 @@ class AreaLocator:
     totals since the last reset; it carries each cell's last mask and open run to the next call (reset on the first batch of a clip),
     and frames None with flush closes the open runs.  Default: EngineCells on the shim's device.
     probe = (first_frame, count): scan only `count` frames from the 1-based frame number first_frame on (default: the whole clip);
-    search_area (.ymin .ymax .xmin .xmax): scan only this part of the picture; locate_kwargs: locate_area's fractions and padding."""
+    search_area (.ymin .ymax .xmin .xmax): scan only this part of the picture; locate_kwargs: locate_area's fractions and padding.
+    edge_thresh="auto": the same single pass evaluates all `thresholds` (1..8, ascending, each 1..255): cells_fn is then called with
+    thresholds=that tuple as well, ignores params.edge_thresh and returns int [nt,gy,gx,4]; run() keeps `totals` of all thresholds,
+    `scores` (edge_thresh_scores) and `edge_thresh` (the threshold pick_edge_thresh chose, None when none scores: one warning, and
+    the callers fall back to 128) and locates the area on the chosen threshold's totals.  plateau_frac: pick_edge_thresh's."""
 
     def __init__(self, cells_fn=None, edge_thresh=128, min_edges=16, change_ratio=0.5, min_seconds=0.3, max_seconds=20.0, batch=64,
-                 probe=None, search_area=None, **locate_kwargs):
+                 probe=None, search_area=None, thresholds=AUTO_THRESHOLDS, plateau_frac=0.9, **locate_kwargs):
         self.cells_fn = cells_fn
-        self.edge_thresh, self.min_edges = int(edge_thresh), int(min_edges)
+        self.auto = isinstance(edge_thresh, str) and edge_thresh == "auto"
+        self.thresholds = tuple(int(v) for v in thresholds)
+        if self.auto and not (1 <= len(self.thresholds) <= 8 and all(1 <= v <= 255 for v in self.thresholds)
+                              and all(a < b for a, b in zip(self.thresholds, self.thresholds[1:]))):
+            raise ValueError(f"AreaLocator: thresholds {thresholds} are not 1..8 ascending values in 1..255")
+        self.edge_thresh, self.min_edges = None if self.auto else int(edge_thresh), int(min_edges)
+        self.plateau_frac, self.scores = plateau_frac, None
         self.ratio = Fraction(change_ratio).limit_denominator(1024)
         if self.ratio <= 0:
             raise ValueError(f"AreaLocator: change_ratio {change_ratio} is not at least 1 / 1024")
@@ -126,12 +191,12 @@ class AreaLocator:
 
     def params(self, fps):
         min_frames = max(2, round(self.min_seconds * fps))
-        return CellParams(self.edge_thresh, self.min_edges, self.ratio.numerator, self.ratio.denominator, min_frames,
+        return CellParams(0 if self.auto else self.edge_thresh, self.min_edges, self.ratio.numerator, self.ratio.denominator, min_frames,
                           max(min_frames, round(self.max_seconds * fps)))
 
     def run(self, frames, fps, uploader=None):
         """frames: iterable of uint8 BGR frames (or ingest.Yuv420Frame with an uploader) in decode order -> extractor.SubtitleArea or
-        None; `totals` (host int32 [gy,gx,4]) and `frames_scanned` are kept on the object.  Staged like ChangeFrameSelector.run:
+        None; `totals` (host int32 [gy,gx,4]; [nt,gy,gx,4] with edge_thresh="auto") and `frames_scanned` are kept on the object.  Staged like ChangeFrameSelector.run:
         whole frames, or the rows of search_area alone; with an uploader (staging.Uploader) through pinned memory on its producer
         thread.  The device keeps the totals: one read-back of a few KB after the last batch."""
         if self.cells_fn is None:
@@ -143,7 +208,9 @@ class AreaLocator:
             if first_frame < 1 or count < 1:
                 raise ValueError(f"AreaLocator: probe {self.probe} is not (first frame >= 1, count >= 1)")
             it = itertools.islice(it, first_frame - 1, first_frame - 1 + count)
-        self.totals, self.frames_scanned, self.area = None, 0, None
+        self.totals, self.frames_scanned, self.area, self.scores = None, 0, None, None
+        if self.auto:
+            self.edge_thresh = None
         first = next(it, None)
         if first is None:
             return None
@@ -156,6 +223,7 @@ class AreaLocator:
             raise ValueError(f"AreaLocator: the region [{y0}, {y1}) x [{x0}, {x1}) of a {h} x {w} frame is smaller than 3 x 3 pixels")
         area = (0, y1 - y0, x0, x1)
         params = self.params(fps)
+        cells = self.cells_fn if not self.auto else (lambda *a: self.cells_fn(*a, thresholds=self.thresholds))
 
         def batches():
             buf = [(None, first[y0:y1])]
@@ -170,16 +238,35 @@ class AreaLocator:
         if uploader is not None:
             from . import staging
             for k, (items, staged) in enumerate(staging.prefetch(batches(), uploader)):
-                self.cells_fn(staged.tensor(), area, params, k == 0, False)
+                cells(staged.tensor(), area, params, k == 0, False)
                 self.frames_scanned += len(items)
         else:
             for k, items in enumerate(batches()):
-                self.cells_fn(np.stack([f for _, f in items]), area, params, k == 0, False)
+                cells(np.stack([f for _, f in items]), area, params, k == 0, False)
                 self.frames_scanned += len(items)
-        totals = self.cells_fn(None, area, params, False, True)
+        totals = cells(None, area, params, False, True)
         self.totals = np.asarray(totals.cpu() if hasattr(totals, "cpu") else totals).astype(np.int32)
-        self.area = locate_area(self.totals, self.frames_scanned, (y0, y1, x0, x1), (h, w), **self.locate_kwargs)
+        chosen = self.totals
+        if self.auto:
+            static_frac = self.locate_kwargs.get("static_frac", 0.95)
+            self.scores = edge_thresh_scores(self.totals, self.frames_scanned, static_frac)
+            k = pick_edge_thresh(self.totals, self.thresholds, self.frames_scanned, static_frac, self.plateau_frac)
+            if k is None:
+                logging.getLogger(__name__).warning("edge_thresh='auto': none of the thresholds %s finds held edges in %d frames; falling "
+                                                    "back to %d", self.thresholds, self.frames_scanned, DEFAULT_EDGE_THRESH)
+                return None
+            self.edge_thresh, chosen = self.thresholds[k], self.totals[k]
+        self.area = locate_area(chosen, self.frames_scanned, (y0, y1, x0, x1), (h, w), **self.locate_kwargs)
         return self.area
+
+
+def parse_edge_thresh(text):
+    """`auto` or an integer 1..255 (the command lines' --edge-thresh)."""
+    if text == "auto":
+        return "auto"
+    if not (text.isdigit() and 1 <= int(text) <= 255):
+        raise ValueError(f"--edge-thresh takes auto or an integer 1..255, not {text!r}")
+    return int(text)
 
 
 def main(argv=None, cells_fn=None):
@@ -192,7 +279,10 @@ def main(argv=None, cells_fn=None):
     p.add_argument("--layout", default=None, choices=("i420", "nv12"), help="plane layout of a headerless YUV 4:2:0 file [by extension]")
     p.add_argument("--probe", type=int, nargs=2, default=None, metavar=("START", "COUNT"),
                    help="scan COUNT frames from the 1-based frame number START on [the whole clip]")
-    p.add_argument("--json", action="store_true", help="print a JSON object instead (area, frames scanned, grid size)")
+    p.add_argument("--edge-thresh", default=str(DEFAULT_EDGE_THRESH), metavar="auto|N", help="luma gradient that makes an edge pixel, or "
+                   "`auto` to choose it for this clip in the same pass (printed as a fifth number) [128]")
+    p.add_argument("--json", action="store_true", help="print a JSON object instead (area, frames scanned, grid size, edge threshold, "
+                   "and with `auto` the score of every threshold tried)")
     args = p.parse_args(argv)
     from . import ingest
     try:
@@ -203,7 +293,7 @@ def main(argv=None, cells_fn=None):
                 raise ValueError(f"--size takes WIDTHxHEIGHT, not {args.size!r}")
             size = (int(w), int(h))
         source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout)
-        loc = AreaLocator(cells_fn, probe=args.probe)
+        loc = AreaLocator(cells_fn, probe=args.probe, edge_thresh=parse_edge_thresh(args.edge_thresh))
         if cells_fn is None:
             from . import staging
             up = staging.default_uploader()
@@ -218,7 +308,10 @@ def main(argv=None, cells_fn=None):
         return 1
     if args.json:
         print(json.dumps({"ymin": area.ymin, "ymax": area.ymax, "xmin": area.xmin, "xmax": area.xmax,
-                          "frames_scanned": loc.frames_scanned, "cells": list(loc.totals.shape[:2])}))
+                          "frames_scanned": loc.frames_scanned, "cells": list(loc.totals.shape[-3:-1]), "edge_thresh": loc.edge_thresh,
+                          "scores": dict(zip(map(str, loc.thresholds), loc.scores)) if loc.auto else None}))
+    elif loc.auto:
+        print(area.ymin, area.ymax, area.xmin, area.xmax, loc.edge_thresh)
     else:
         print(area.ymin, area.ymax, area.xmin, area.xmax)
     return 0

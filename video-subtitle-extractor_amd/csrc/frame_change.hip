@@ -15,6 +15,9 @@
 // Subtitle-area locator (vse_frame_cells): the same tiles and the same mask, but a tile is a CELL that keeps its own counts and runs
 // the interval automaton of frame_select.change_intervals on them (frame_cells_kernel below).
 //
+// Threshold calibration (vse_frame_cells_multi): vse_frame_cells for several edge thresholds in one pass over the frames
+// (frame_cells_multi_kernel below).
+//
 // Held-edge selector (vse_frame_hold): the same tiles and the same mask again, but only edge pixels that hold still for `hold` frames
 // are counted, so that the edges of a moving background drop out (frame_hold_kernel below).
 #include "common.h"
@@ -248,6 +251,112 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_kernel(const uint8_
     }
 }
 
+// ---- vse_frame_cells_multi -------------------------------------------------------------------------------------------------------
+// frame_cells_kernel for up to FC_WAVES edge thresholds in one pass: a frame's bytes are read and its lumas and gradients computed once;
+// per threshold only the compare / ballot differs, and then the cell's mask words, counts and automaton.  The tile is tile_lane's; the mask
+// loop below is tile_masks' with the ballot repeated per threshold (tile_masks itself stays as it is: split into shared pieces it
+// compiled frame_cells_kernel and frame_hold_kernel to different code, and those kernels are not this one's to change).
+// Wave q then walks threshold q's automaton exactly as wave 0 does above, the thresholds side by side.  State and totals are nt
+// slices, each laid out as vse_frame_cells lays out its own.
+struct CellThresholds {
+    int t[FC_WAVES];        // ascending, each 1..255; those beyond the kernel's NT unused
+};
+
+// msk[(q * FC_CHUNK + tl) * FC_ROWS + k] = packed mask at threshold q of the tile's interior row k in frame c0 + tl, for tl < cn.
+template <int NT>
+__device__ __forceinline__ void tile_masks_multi(const uint8_t* __restrict__ src, int c0, int cn, long pitch, long fstride, const TileLane& t,
+                                                 const CellThresholds& th, unsigned long long* msk) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int rows = t.rows;
+    for (int tl = wave; tl < cn; tl += FC_WAVES) {
+        const uint8_t* f = src + (long)(c0 + tl) * fstride;
+        int yc[FC_ROWS + 2], ye[FC_ROWS];
+#pragma unroll
+        for (int k = 0; k < FC_ROWS + 2; ++k) yc[k] = (k < rows + 2 && t.own) ? luma(f + (long)k * pitch + t.x * 3) : 0;
+#pragma unroll
+        for (int k = 0; k < FC_ROWS; ++k) ye[k] = (k < rows && t.extra) ? luma(f + (long)(k + 1) * pitch + t.xe * 3) : 0;
+#pragma unroll
+        for (int k = 0; k < FC_ROWS; ++k) {
+            int e = -1;                    // below every threshold: the words of rows outside the area are zero
+            if (k < rows) {                // block-uniform
+                const int l = __shfl_up(yc[k + 1], 1), r = __shfl_down(yc[k + 1], 1);
+                const int left = lane == 0 ? ye[k] : l, right = lane == 63 ? ye[k] : r;
+                if (t.inner) e = max(abs(right - left), abs(yc[k + 2] - yc[k]));
+            }
+            unsigned long long b[NT];
+#pragma unroll
+            for (int q = 0; q < NT; ++q) b[q] = __ballot(e >= th.t[q]);
+            if (lane == 0) {
+#pragma unroll
+                for (int q = 0; q < NT; ++q) msk[(q * FC_CHUNK + tl) * FC_ROWS + k] = b[q];
+            }
+        }
+    }
+}
+
+// Grid and cell ownership as frame_cells_kernel; threshold q's state is state[(q * cells + cell) * CELL_STATE_WORDS ..] and its totals
+// totals[(q * cells + cell) * 4 ..].  NT = the number of thresholds, 1 .. FC_WAVES (a template parameter: the ballots of a row unroll
+// without a branch per threshold).  LDS: (FC_CHUNK + 1) * NT * FC_ROWS words, 32.5 KiB at NT = 8; at the 83 VGPRs of this kernel a CU
+// holds two blocks, which is 65 KiB of its 160.  Runs with n == 0 too (reset and flush only).
+template <int NT>
+__global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_multi_kernel(const uint8_t* __restrict__ src, int n, long pitch, long fstride,
+                                                                          int x0, int ih, int iw, CellThresholds th, CellRule rule,
+                                                                          unsigned long long* __restrict__ state, int reset, int flush,
+                                                                          int* __restrict__ totals) {
+    __shared__ unsigned long long msk[NT * FC_CHUNK * FC_ROWS];           // [NT][FC_CHUNK][FC_ROWS]
+    __shared__ unsigned long long prv[NT * FC_ROWS];
+    static_assert(FC_CHUNK == 64, "the frames of a chunk are the lanes of a wave");
+    static_assert(NT >= 1 && NT <= FC_WAVES, "wave q owns threshold q");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int iy0 = blockIdx.y * FC_ROWS;
+    const long cell = (long)blockIdx.y * gridDim.x + blockIdx.x, cells = (long)gridDim.y * gridDim.x;
+    const TileLane t = tile_lane(blockIdx.x, iy0, ih, iw, x0);
+    const bool mine = wave < NT;            // wave q owns threshold q
+    unsigned long long* st = state + ((long)wave * cells + cell) * CELL_STATE_WORDS;
+    int* tot = totals + ((long)wave * cells + cell) * 4;
+    unsigned long long* mq = msk + wave * FC_CHUNK * FC_ROWS;
+    unsigned long long* pq = prv + wave * FC_ROWS;
+    if (mine && lane < FC_ROWS) pq[lane] = reset ? 0ull : st[lane];
+    CellRuns cr = {0, 0, 0, 0, 0};
+    if (mine && !reset) cr = {(int)st[FC_ROWS], tot[0], tot[1], tot[2], tot[3]};
+
+    for (int c0 = 0; c0 < n; c0 += FC_CHUNK) {
+        const int cn = min(FC_CHUNK, n - c0);
+        tile_masks_multi<NT>(src + (long)iy0 * pitch, c0, cn, pitch, fstride, t, th, msk);
+        __syncthreads();
+        if (mine) {                                // lane = frame of the chunk
+            const bool live = lane < cn;
+            int e = 0, a = 0, v = 0, ep = 0;
+            if (live) {
+#pragma unroll
+                for (int k = 0; k < FC_ROWS; ++k) {
+                    const unsigned long long cur = mq[lane * FC_ROWS + k], pre = lane ? mq[(lane - 1) * FC_ROWS + k] : pq[k];
+                    e += __popcll(cur);
+                    a += __popcll(cur & ~pre);
+                    v += __popcll(pre & ~cur);
+                    ep += __popcll(pre);           // edges[t-1]
+                }
+            }
+            const long long uni = ep + a;          // |E' or E|
+            const unsigned long long present = __ballot(live && e >= rule.min_edges);
+            const unsigned long long ratio = __ballot(live && uni > 0 && (long long)(a + v) * rule.ratio_den >= (long long)rule.ratio_num * uni);
+            for (int f = 0; f < cn; ++f) cr.step((present >> f) & 1, (ratio >> f) & 1, rule);
+        }
+        __syncthreads();
+        if (mine && lane < FC_ROWS) pq[lane] = mq[(cn - 1) * FC_ROWS + lane];
+        __syncthreads();
+    }
+    if (mine && lane < FC_ROWS) st[lane] = pq[lane];
+    if (mine && lane == 0) {
+        if (flush) cr.close(rule);
+        st[FC_ROWS] = (unsigned long long)cr.run;
+        tot[0] = cr.covered;
+        tot[1] = cr.runs;
+        tot[2] = cr.present;
+        tot[3] = cr.cuts;
+    }
+}
+
 // ---- vse_frame_hold -------------------------------------------------------------------------------------------------------------
 // H_u = the edge pixels of frame u whose run of consecutive edge frames is at least `hold` frames long.  Per pixel, along the frames t:
 //   run[t]   = E[t] ? min(run[t-1] + 1, hold) : 0          S[t] = (run[t] == hold): a run of `hold` frames ends at t
@@ -369,6 +478,36 @@ int vse_frame_cells_launch(const void* d_bgr, int n, int64_t pitch, int64_t fram
                        reinterpret_cast<hipStream_t>(stream), src, n, (long)pitch, (long)frame_stride, x0, ih, iw, edge_thresh, rule,
                        reinterpret_cast<unsigned long long*>(d_state), reset, flush, reinterpret_cast<int*>(d_totals),
                        reinterpret_cast<int*>(d_cell_counts));
+    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+}
+
+int vse_frame_cells_multi_max() { return FC_WAVES; }
+
+// Called by vse_frame_cells_multi (vse_runtime.hip) after it has checked the arguments (1 <= nt <= vse_frame_cells_multi_max()).
+int vse_frame_cells_multi_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                                 const int* thresholds, int nt, int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
+                                 void* d_state, int reset, int flush, int32_t* d_totals, void* stream) {
+    const int ih = y1 - y0 - 2, iw = x1 - x0 - 2;
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
+    const CellRule rule = {min_edges, ratio_num, ratio_den, min_frames, max_frames};
+    CellThresholds th = {};
+    for (int q = 0; q < nt; ++q) th.t[q] = thresholds[q];
+    const dim3 grid((iw + 63) / 64, (ih + FC_ROWS - 1) / FC_ROWS), block(FC_WAVES * 64);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    unsigned long long* state = reinterpret_cast<unsigned long long*>(d_state);
+    int* totals = reinterpret_cast<int*>(d_totals);
+#define VSE_CELLS_MULTI(NT)                                                                                                              \
+    case NT:                                                                                                                             \
+        hipLaunchKernelGGL(frame_cells_multi_kernel<NT>, grid, block, 0, st, src, n, (long)pitch, (long)frame_stride, x0, ih, iw, th, rule, \
+                           state, reset, flush, totals);                                                                                 \
+        break;
+    switch (nt) {
+        VSE_CELLS_MULTI(1) VSE_CELLS_MULTI(2) VSE_CELLS_MULTI(3) VSE_CELLS_MULTI(4)
+        VSE_CELLS_MULTI(5) VSE_CELLS_MULTI(6) VSE_CELLS_MULTI(7) VSE_CELLS_MULTI(8)
+        default: return VSE_E_INVAL;
+    }
+#undef VSE_CELLS_MULTI
+    static_assert(FC_WAVES == 8, "one instantiation per number of thresholds");
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
 

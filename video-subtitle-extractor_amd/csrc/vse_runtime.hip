@@ -56,6 +56,10 @@ int vse_frame_cells_state_words();                                              
 int vse_frame_cells_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
                            int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames, void* d_state, int reset, int flush,
                            int32_t* d_totals, int32_t* d_cell_counts, void* stream);                                    // frame_change.hip
+int vse_frame_cells_multi_max();                                                                                       // frame_change.hip
+int vse_frame_cells_multi_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                                 const int* thresholds, int nt, int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
+                                 void* d_state, int reset, int flush, int32_t* d_totals, void* stream);
 size_t vse_frame_hold_word_bytes();                                                                                    // frame_change.hip
 int vse_frame_hold_launch(const void* d_bgr, int n, int steps, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
                           int edge_thresh, int hold, int skip, void* d_state, int fresh, int32_t* d_counts, void* stream);   // frame_change.hip
@@ -473,6 +477,47 @@ int vse_frame_cells(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, 
     const int rc = vse_frame_cells_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, min_edges, ratio_num, ratio_den,
                                           min_frames, max_frames, d_state, reset, flush, d_totals, d_cell_counts, stream);
     if (rc != VSE_OK) set_err("vse_frame_cells: launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+// ---- edge-threshold calibration: the locator's cells at several thresholds in one pass (frame_change.hip) ---------------------------
+size_t vse_frame_cells_multi_state_bytes(int area_h, int area_w, int nt) {
+    if (nt < 1 || nt > vse_frame_cells_multi_max()) return 0;
+    return (size_t)nt * vse_frame_cells_state_bytes(area_h, area_w);
+}
+
+int vse_frame_cells_multi(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0, int y1,
+                          int x0, int x1, const int* thresholds, int nt, int min_edges, int ratio_num, int ratio_den, int min_frames,
+                          int max_frames, void* d_state, int reset, int flush, int32_t* d_totals, void* stream) {
+    if (!c || (!d_bgr && n > 0) || !d_state || !d_totals || n < 0 || src_h <= 0 || src_w <= 0 || pitch < (int64_t)src_w * 3 ||
+        (n > 1 && frame_stride < (int64_t)(src_h - 1) * pitch + (int64_t)src_w * 3) || (reinterpret_cast<uintptr_t>(d_state) & 7)) {
+        set_err("vse_frame_cells_multi: bad arguments (n %d, frame %d x %d, pitch %lld, frame stride %lld, state 8-byte aligned)", n, src_h,
+                src_w, (long long)pitch, (long long)frame_stride);
+        return VSE_E_INVAL;
+    }
+    if (y0 < 0 || x0 < 0 || y1 > src_h || x1 > src_w || y1 - y0 < 3 || x1 - x0 < 3) {
+        set_err("vse_frame_cells_multi: region [%d, %d) x [%d, %d) is degenerate or outside the %d x %d frame", y0, y1, x0, x1, src_h, src_w);
+        return VSE_E_INVAL;
+    }
+    if (ratio_num < 1 || ratio_den < 1 || ratio_den > 1024 || min_frames < 1 || max_frames < min_frames) {
+        set_err("vse_frame_cells_multi: ratio %d / %d (numerator >= 1, denominator 1..1024) or run length %d..%d (1 <= min <= max) out of range",
+                ratio_num, ratio_den, min_frames, max_frames);
+        return VSE_E_INVAL;
+    }
+    if (!thresholds || nt < 1 || nt > vse_frame_cells_multi_max()) {
+        set_err("vse_frame_cells_multi: %d thresholds (1..%d, not NULL)", nt, vse_frame_cells_multi_max());
+        return VSE_E_INVAL;
+    }
+    for (int q = 0; q < nt; ++q) {
+        if (thresholds[q] < 1 || thresholds[q] > 255 || (q && thresholds[q] <= thresholds[q - 1])) {
+            set_err("vse_frame_cells_multi: threshold %d of %d is %d (each 1..255, ascending and distinct)", q, nt, thresholds[q]);
+            return VSE_E_INVAL;
+        }
+    }
+    if (n == 0 && !reset && !flush) return VSE_OK;
+    const int rc = vse_frame_cells_multi_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, thresholds, nt, min_edges, ratio_num,
+                                                ratio_den, min_frames, max_frames, d_state, reset, flush, d_totals, stream);
+    if (rc != VSE_OK) set_err("vse_frame_cells_multi: launch failed: %s", hipGetErrorString(hipGetLastError()));
     return rc;
 }
 

@@ -25,7 +25,7 @@ EXPORTS = [
     "vse_scene_change", "vse_frame_cells_dims", "vse_frame_cells_state_bytes", "vse_frame_cells",
     "vse_interval_state_bytes", "vse_interval_accumulate", "vse_interval_composite", "vse_frame_hold_state_bytes", "vse_frame_hold",
     "vse_audio_stream_length", "vse_audio_stream_workspace_bytes", "vse_audio_stream_feed", "vse_audio_stream_finish", "vse_ctc_fuse",
-    "vse_yuv_to_bgr_matrix",
+    "vse_yuv_to_bgr_matrix", "vse_frame_cells_multi_state_bytes", "vse_frame_cells_multi",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -146,6 +146,11 @@ def load_library(path=None):
     lib.vse_frame_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vse_frame_cells_multi_state_bytes.restype = C.c_size_t
+    lib.vse_frame_cells_multi_state_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.vse_frame_cells_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.vse_frame_hold_state_bytes.restype = C.c_size_t
     lib.vse_frame_hold_state_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.vse_frame_hold.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
@@ -499,6 +504,40 @@ class Context:
                                         int(bool(flush)), C.c_void_p(state.totals.data_ptr()),
                                         C.c_void_p(counts.data_ptr()) if want_counts and n else None, self.stream()), "vse_frame_cells")
         return (state.totals, counts) if want_counts else state.totals
+
+    # ---- edge-threshold calibration -------------------------------------------------------------------------------
+    def frame_cells_multi_state(self, area_h, area_w, nt):
+        """A fresh CellsState (zero-filled) for frame_cells_multi over a region of area_h x area_w pixels with nt thresholds; its
+        totals are cuda int32 [nt,gy,gx,4]."""
+        gy, gx = self.frame_cells_dims(area_h, area_w)
+        nbytes = self.lib.vse_frame_cells_multi_state_bytes(int(area_h), int(area_w), int(nt))
+        if not nbytes:
+            raise VseError(f"frame_cells_multi: {nt} thresholds (1..8)")
+        t = self.torch
+        return CellsState(t.zeros(nbytes, dtype=t.uint8, device=self.tdev), t.zeros((int(nt), gy, gx, 4), dtype=t.int32, device=self.tdev))
+
+    def frame_cells_multi(self, frames_u8, area, thresholds, params, state, reset=False, flush=False):
+        """frame_cells for every edge threshold of `thresholds` (1..8 of them, ascending, each 1..255) in one pass over the frames:
+        frames_u8, area, reset and flush as there, params: CellParams whose edge_thresh is ignored, state: frame_cells_multi_state of
+        the area's size and len(thresholds) -> state.totals, cuda int32 [nt,gy,gx,4], slice k being frame_cells' totals at
+        thresholds[k] (include/vse_hip.h vse_frame_cells_multi)."""
+        t = self.torch
+        assert frames_u8.dtype == t.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
+        assert frames_u8.stride(3) == 1 and frames_u8.stride(2) == 3
+        y0, y1, x0, x1 = (int(v) for v in area)
+        th = [int(v) for v in thresholds]
+        nt = len(th)
+        gy, gx = self.frame_cells_dims(y1 - y0, x1 - x0)
+        nbytes = self.lib.vse_frame_cells_multi_state_bytes(y1 - y0, x1 - x0, nt)
+        assert nbytes and state.words.numel() >= nbytes and tuple(state.totals.shape) == (nt, gy, gx, 4)
+        n, h, w, _ = frames_u8.shape
+        p = CellParams(*(int(v) for v in params))
+        _check(self.lib.vse_frame_cells_multi(self.handle, C.c_void_p(frames_u8.data_ptr()) if n else None, n, h, w, frames_u8.stride(1),
+                                              frames_u8.stride(0), y0, y1, x0, x1, (C.c_int * nt)(*th), nt, p.min_edges, p.ratio_num,
+                                              p.ratio_den, p.min_frames, p.max_frames, C.c_void_p(state.words.data_ptr()),
+                                              int(bool(reset)), int(bool(flush)), C.c_void_p(state.totals.data_ptr()), self.stream()),
+               "vse_frame_cells_multi")
+        return state.totals
 
     # ---- held-edge frame selector ---------------------------------------------------------------------------------
     def frame_hold_state(self, area_h, area_w, hold):

@@ -256,6 +256,13 @@ class SubtitleExtractor:
     on the device (area_locator.AreaLocator, `area_params` its keyword arguments), keeps what it found as `located_area` and goes
     on exactly as if that area had been passed; when it finds none it warns and goes on exactly as with sub_area=None.  With
     `shard`, every rank scans the same frames and gets the same integers, hence the same area.
+    change_params={"edge_thresh": "auto"} (frame_selector "change" or "hold"): the selectors' constant 128 describes white text with a
+    black outline; on yellow, shadowed, unoutlined or washed-out subtitles no pixel reaches it and the SRT comes out empty.  "auto"
+    chooses the threshold for this clip before the selector is built (area_locator.AreaLocator(edge_thresh="auto"), `area_params` its
+    keyword arguments; the selectors keep taking integers) and keeps it as `edge_thresh`: with sub_area="auto" the one locator pass
+    yields the area and the threshold, with a given area one calibration pass runs over the area's rows.  When no threshold scores
+    (no subtitles, or a textured background that moves behind them: the calibration uses the change automaton) it warns and uses 128.
+    How the choice behaves on real footage is not measured here.
     one_pass (None: exactly when the source has no `read`, e.g. ingest.Y4mStream over a pipe; True forces it on a seekable source and
     halves its decode work; False on a sequential source is a ValueError): the clip is read once, in decode order.  frame_selector="fps":
     frame `no` is a task iff (no - 1) % max(1, int(fps // extract_frequency)) == 0 (fps_tasks' rule without the frame count); tasks go
@@ -270,7 +277,7 @@ class SubtitleExtractor:
     intervals, the frames recognised, raw_lines and the SRT equal those of the multi-pass run() on the same frames with the same
     arguments (recognition does not depend on how frames are grouped into batches: tests/test_gpu_ragged.py).  Refused in one pass,
     because they need a second look at frames already gone: sub_area="auto", mode="accurate" with an area, interval_image other than
-    "middle", interval_text="fused", shard."""
+    "middle", interval_text="fused", shard, change_params' edge_thresh="auto"."""
 
     def __init__(self, source, ocr, detect_batch=None, sub_area=None, mode="fast", language="ch", extract_frequency=3,
                  default_subtitle_area=None, drop_score=0.75, deviation_rate=0.0, threshold=80, batch=64,
@@ -304,6 +311,11 @@ class SubtitleExtractor:
         self.detect_stream = detect_stream
         self.word_segmentation, self.segment = word_segmentation, segment      # config.wordSegmentation (main.py:181-182)
         self.frame_selector, self.change_params, self.change_counter = frame_selector, change_params, change_counter
+        et = (change_params or {}).get("edge_thresh", 128)
+        self.auto_thresh = isinstance(et, str) and et == "auto"
+        if isinstance(et, str) and not self.auto_thresh:
+            raise ValueError(f"change_params: edge_thresh must be an integer or 'auto', not {et!r}")
+        self.edge_thresh = None if self.auto_thresh else et          # "auto": the integer run() resolves it to
         self.delete_empty = delete_empty          # config.deleteEmptyTimeStamp (intervals of the change selector only)
         self.interval_image, self.composite_params, self.interval_patches = interval_image, composite_params, None
         self.interval_text, self.fuse_params, self.interval_results = interval_text, fuse_params, None
@@ -317,7 +329,8 @@ class SubtitleExtractor:
         if self.one_pass:
             refused = [("sub_area='auto'", self.auto_area), ("mode='accurate' with a subtitle area", mode == "accurate" and sub_area is not None),
                        (f"interval_image={interval_image!r}", interval_image != "middle"),
-                       (f"interval_text={interval_text!r}", interval_text != "single"), (f"shard={shard!r}", shard is not None)]
+                       (f"interval_text={interval_text!r}", interval_text != "single"), (f"shard={shard!r}", shard is not None),
+                       ("edge_thresh='auto'", self.auto_thresh)]
             for what, hit in refused:
                 if hit:
                     raise ValueError(f"{what} is not available in one pass (a sequential source, or one_pass=True): it needs a second look "
@@ -334,16 +347,48 @@ class SubtitleExtractor:
             return self.source.raw_frames()
         return self.source.frames()
 
-    def locate_area(self):
-        """sub_area="auto": find the area (area_locator.AreaLocator over the clip in decode order) and make it this run's sub_area."""
+    def _selects_intervals(self):
+        return self.sub_area is not None and self.mode in ("fast", "auto") and self.frame_selector in ("change", "hold")
+
+    def _locator(self, **kw):
         from . import area_locator
+        params = {"batch": self.batch, **(self.area_params or {}), **kw}
+        if self.auto_thresh and self.frame_selector in ("change", "hold"):
+            params["edge_thresh"] = "auto"
+        return area_locator.AreaLocator(**params)
+
+    def _keep_edge_thresh(self, loc):
+        """change_params' edge_thresh="auto": what the locator chose, or 128 when no threshold scored (the locator has warned)."""
+        from . import area_locator
+        if loc.auto:
+            self.edge_thresh = area_locator.DEFAULT_EDGE_THRESH if loc.edge_thresh is None else loc.edge_thresh
+
+    def locate_area(self):
+        """sub_area="auto": find the area (area_locator.AreaLocator over the clip in decode order) and make it this run's sub_area;
+        with change_params' edge_thresh="auto" the same pass chooses the selector's threshold."""
         up = self._uploader()
-        loc = area_locator.AreaLocator(**{"batch": self.batch, **(self.area_params or {})})
+        loc = self._locator()
         self.sub_area = self.located_area = loc.run(self._decode_order(up), self.source.fps, uploader=up)
+        self._keep_edge_thresh(loc)
         if self.located_area is None:
             logging.getLogger(__name__).warning("sub_area='auto': no subtitle area found in %d frames; continuing without one "
                                                 "(fps sampler, scene-text filtering)", loc.frames_scanned)
         return self.located_area
+
+    def calibrate_edge_thresh(self):
+        """change_params' edge_thresh="auto" with a given area: one pass over the area's rows (AreaLocator with search_area = the
+        area) -> the threshold, kept as `edge_thresh`."""
+        up = self._uploader()
+        loc = self._locator(search_area=self.sub_area)
+        loc.run(self._decode_order(up), self.source.fps, uploader=up)
+        self._keep_edge_thresh(loc)
+        return self.edge_thresh
+
+    def _change_params(self):
+        """The selector's keyword arguments, edge_thresh="auto" resolved to the integer."""
+        if not self.auto_thresh:
+            return self.change_params or {}
+        return {**self.change_params, "edge_thresh": 128 if self.edge_thresh is None else self.edge_thresh}
 
     def select_tasks(self):
         s = self.source
@@ -356,12 +401,12 @@ class SubtitleExtractor:
                                                      predict_with_dets=getattr(self.ocr, "predict_with_dets", None))
             return [(t[0], t[1], t[2], t[3], None, None) for t in sel.run(self._decode_order(up), uploader=up)]
         if self.sub_area is not None and self.mode in ("fast", "auto") and self.frame_selector == "change":
-            sel = frame_select.ChangeFrameSelector(self.change_counter, batch=self.batch, **(self.change_params or {}))
+            sel = frame_select.ChangeFrameSelector(self.change_counter, batch=self.batch, **self._change_params())
             up = self._uploader()
             self.intervals = sel.run(self._decode_order(up), self.sub_area, uploader=up)
             return [(s.frame_count, rep, None, None, None, self.default_subtitle_area) for _start, _end, rep in self.intervals]
         if self.sub_area is not None and self.mode in ("fast", "auto") and self.frame_selector == "hold":
-            sel = frame_select.HoldFrameSelector(self.change_counter, batch=self.batch, **(self.change_params or {}))
+            sel = frame_select.HoldFrameSelector(self.change_counter, batch=self.batch, **self._change_params())
             up = self._uploader()
             self.intervals = sel.run(self._decode_order(up), self.sub_area, s.fps, uploader=up)
             return [(s.frame_count, rep, None, None, None, self.default_subtitle_area) for _start, _end, rep in self.intervals]
@@ -417,10 +462,10 @@ class SubtitleExtractor:
     def _one_pass_intervals(self, frames, uploader):
         s = self.source
         if self.frame_selector == "change":
-            sel = frame_select.ChangeFrameSelector(self.change_counter, batch=self.batch, **(self.change_params or {}))
+            sel = frame_select.ChangeFrameSelector(self.change_counter, batch=self.batch, **self._change_params())
             batches = sel.iter_run(frames, self.sub_area, uploader=uploader)
         else:
-            sel = frame_select.HoldFrameSelector(self.change_counter, batch=self.batch, **(self.change_params or {}))
+            sel = frame_select.HoldFrameSelector(self.change_counter, batch=self.batch, **self._change_params())
             batches = sel.iter_run(frames, self.sub_area, s.fps, uploader=uploader)
         # the recogniser's batches are staged while the selector's producer thread stages the next bands: a slab ring of their own
         ocr_up = uploader.sibling() if uploader is not None else None
@@ -498,8 +543,12 @@ class SubtitleExtractor:
         return text
 
     def _run_multi_pass(self):
+        if self.auto_thresh:
+            self.edge_thresh = None
         if self.auto_area:
             self.locate_area()
+        elif self.auto_thresh and self._selects_intervals():
+            self.calibrate_edge_thresh()
         self.interval_patches = None
         tasks = self.select_tasks()
         source = self.source
@@ -527,9 +576,9 @@ def _parse_area(text):
     return SubtitleArea(*(int(p) for p in parts))
 
 
-def main(argv=None, ocr=None, counter=None):
+def main(argv=None, ocr=None, counter=None, cells_fn=None):
     """ocr: the recogniser (None: shim.OcrRecogniser on the GPU, frames staged through staging.default_uploader, YUV 4:2:0 converted
-    on the device); counter: the change / hold selector's count_fn (None: the GPU's)."""
+    on the device); counter: the change / hold selector's count_fn (None: the GPU's); cells_fn: the locator's (None: the GPU's)."""
     p = argparse.ArgumentParser(prog="python -m vse_amd.extractor", description="Extract a video's hard subtitles to SRT on the GPU.  "
                                 "`-` reads YUV4MPEG2 from standard input in one pass, e.g. "
                                 "`ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m vse_amd.extractor - -o film.srt`.")
@@ -544,6 +593,8 @@ def main(argv=None, ocr=None, counter=None):
     p.add_argument("--area", default=None, metavar="ymin,ymax,xmin,xmax|auto", help="the subtitle area in frame pixels, or `auto` to "
                    "look for it first (not in one pass) [none: the whole frame, fps sampler]")
     p.add_argument("--selector", default="fps", choices=("fps", "change", "hold"), help="which frames go to OCR [fps]")
+    p.add_argument("--edge-thresh", default="128", metavar="auto|N", help="change / hold selector: the luma gradient that makes an edge "
+                   "pixel, or `auto` to choose it for this clip first (not in one pass) [128]")
     p.add_argument("--mode", default="fast", choices=("fast", "auto", "accurate"))
     p.add_argument("--language", default="ch")
     p.add_argument("--frequency", type=int, default=3, help="frames per second the fps sampler looks at [3]")
@@ -562,6 +613,8 @@ def main(argv=None, ocr=None, counter=None):
                 raise ValueError(f"--size takes WIDTHxHEIGHT, not {args.size!r}")
             size = (int(w), int(h))
         area = None if args.area is None else _parse_area(args.area)
+        from .area_locator import parse_edge_thresh
+        edge_thresh = parse_edge_thresh(args.edge_thresh)
         source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout, matrix=args.matrix)
         uploader = None
         if ocr is None:
@@ -573,7 +626,9 @@ def main(argv=None, ocr=None, counter=None):
             ocr, uploader = shim.OcrRecogniser(), staging.default_uploader()
         ex = SubtitleExtractor(source, ocr, sub_area=area, mode=args.mode, language=args.language, extract_frequency=args.frequency,
                                batch=args.batch, uploader=uploader, frame_selector=args.selector, change_counter=counter,
-                               retain_bytes=int(args.retain_gib * (1 << 30)))
+                               retain_bytes=int(args.retain_gib * (1 << 30)),
+                               change_params=None if edge_thresh == 128 else {"edge_thresh": edge_thresh},
+                               area_params=None if cells_fn is None else {"cells_fn": cells_fn})
         text = ex.run()
         if args.output is None:
             sys.stdout.write(text)
