@@ -47,7 +47,9 @@ from fractions import Fraction
 
 import numpy as np
 
-from .engine import CellParams
+from . import staging
+from .engine import CellParams, DeviceState
+from .frame_select import band_batches
 
 CELL_H, CELL_W = 8, 64          # interior pixels of a cell (the tile of csrc/frame_change.hip)
 AUTO_THRESHOLDS = (24, 32, 48, 64, 96, 128, 160, 192)      # what edge_thresh="auto" chooses from
@@ -131,30 +133,19 @@ def locate_area(totals, frames_scanned, region, frame_hw, row_frac=0.25, col_fra
     return SubtitleArea(ymin=max(0, ymin), ymax=min(h, ymax), xmin=max(0, xmin), xmax=min(w, xmax))
 
 
-class EngineCells:
+class EngineCells(DeviceState):
     """cells_fn of AreaLocator on the GPU (Context.frame_cells; with `thresholds`, Context.frame_cells_multi): keeps the device state
     of the last region (and threshold count) between calls."""
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self._state = None
-        self._key = None
 
     def __call__(self, frames, area, params, reset, flush, thresholds=None):
         t = self.ctx.torch
         y0, y1, x0, x1 = area
-        if frames is None:
-            frames = t.empty((0, y1, x1, 3), dtype=t.uint8, device=self.ctx.tdev)
-        elif not t.is_tensor(frames):
-            frames = t.from_numpy(np.ascontiguousarray(frames)).to(self.ctx.tdev)
-        nt = None if thresholds is None else len(thresholds)
-        if self._key != (y1 - y0, x1 - x0, nt):
-            self._key = (y1 - y0, x1 - x0, nt)
-            self._state = self.ctx.frame_cells_state(y1 - y0, x1 - x0) if nt is None else self.ctx.frame_cells_multi_state(y1 - y0, x1 - x0, nt)
-            reset = True
-        if nt is not None:
-            return self.ctx.frame_cells_multi(frames, area, thresholds, params, self._state, reset, flush)
-        return self.ctx.frame_cells(frames, area, params, self._state, reset, flush)
+        frames = t.empty((0, y1, x1, 3), dtype=t.uint8, device=self.ctx.tdev) if frames is None else self._device(frames)
+        if thresholds is None:
+            reset = self._fresh((y1 - y0, x1 - x0), self.ctx.frame_cells_state) or reset
+            return self.ctx.frame_cells(frames, area, params, self._state, reset, flush)
+        reset = self._fresh((y1 - y0, x1 - x0, len(thresholds)), self.ctx.frame_cells_multi_state) or reset
+        return self.ctx.frame_cells_multi(frames, area, thresholds, params, self._state, reset, flush)
 
 
 class AreaLocator:
@@ -196,9 +187,9 @@ class AreaLocator:
 
     def run(self, frames, fps, uploader=None):
         """frames: iterable of uint8 BGR frames (or ingest.Yuv420Frame with an uploader) in decode order -> extractor.SubtitleArea or
-        None; `totals` (host int32 [gy,gx,4]; [nt,gy,gx,4] with edge_thresh="auto") and `frames_scanned` are kept on the object.  Staged like ChangeFrameSelector.run:
-        whole frames, or the rows of search_area alone; with an uploader (staging.Uploader) through pinned memory on its producer
-        thread.  The device keeps the totals: one read-back of a few KB after the last batch."""
+        None; `totals` (host int32 [gy,gx,4]; [nt,gy,gx,4] with edge_thresh="auto") and `frames_scanned` are kept on the object.  Whole
+        frames, or the rows of search_area alone, are batched by frame_select.band_batches and staged by staging.staged_batches.  The
+        device keeps the totals: one read-back of a few KB after the last batch."""
         if self.cells_fn is None:
             from . import shim
             self.cells_fn = EngineCells(shim._context())
@@ -211,39 +202,15 @@ class AreaLocator:
         self.totals, self.frames_scanned, self.area, self.scores = None, 0, None, None
         if self.auto:
             self.edge_thresh = None
-        first = next(it, None)
-        if first is None:
+        bands = band_batches(it, self.search_area, self.batch, "AreaLocator")
+        area = bands.area
+        if area is None:
             return None
-        h, w = first.shape[:2]
-        y0, y1, x0, x1 = 0, h, 0, w
-        if self.search_area is not None:
-            s = self.search_area
-            y0, y1, x0, x1 = max(0, int(s.ymin)), min(h, int(s.ymax)), max(0, int(s.xmin)), min(w, int(s.xmax))
-        if y1 - y0 < 3 or x1 - x0 < 3:
-            raise ValueError(f"AreaLocator: the region [{y0}, {y1}) x [{x0}, {x1}) of a {h} x {w} frame is smaller than 3 x 3 pixels")
-        area = (0, y1 - y0, x0, x1)
         params = self.params(fps)
         cells = self.cells_fn if not self.auto else (lambda *a: self.cells_fn(*a, thresholds=self.thresholds))
-
-        def batches():
-            buf = [(None, first[y0:y1])]
-            for f in it:
-                if len(buf) == self.batch:
-                    yield buf
-                    buf = []
-                buf.append((None, f[y0:y1]))
-            if buf:
-                yield buf
-
-        if uploader is not None:
-            from . import staging
-            for k, (items, staged) in enumerate(staging.prefetch(batches(), uploader)):
-                cells(staged.tensor(), area, params, k == 0, False)
-                self.frames_scanned += len(items)
-        else:
-            for k, items in enumerate(batches()):
-                cells(np.stack([f for _, f in items]), area, params, k == 0, False)
-                self.frames_scanned += len(items)
+        for items, data in staging.staged_batches(bands, uploader):
+            cells(data, area, params, not self.frames_scanned, False)
+            self.frames_scanned += len(items)
         totals = cells(None, area, params, False, True)
         self.totals = np.asarray(totals.cpu() if hasattr(totals, "cpu") else totals).astype(np.int32)
         chosen = self.totals
@@ -256,7 +223,7 @@ class AreaLocator:
                                                     "back to %d", self.thresholds, self.frames_scanned, DEFAULT_EDGE_THRESH)
                 return None
             self.edge_thresh, chosen = self.thresholds[k], self.totals[k]
-        self.area = locate_area(chosen, self.frames_scanned, (y0, y1, x0, x1), (h, w), **self.locate_kwargs)
+        self.area = locate_area(chosen, self.frames_scanned, bands.geometry, bands.frame_hw, **self.locate_kwargs)
         return self.area
 
 

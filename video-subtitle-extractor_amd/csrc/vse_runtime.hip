@@ -420,6 +420,34 @@ int vse_ctc_fuse(vse_ctx* c, const float* d_probs, int b, int t, int ncls, int64
     return rc;
 }
 
+// ---- argument checks shared by the vse_frame_* entry points: each sets the error text in the name of `who` and returns false ------
+// n frames of src_h x src_w pixels behind d_bgr (NULL only with n == 0, which min_n == 0 allows) and an 8-byte aligned state; `rest`:
+// the entry point's other pointers and counts are in order
+static bool check_frames(const char* who, bool rest, const void* d_bgr, int n, int min_n, int src_h, int src_w, int64_t pitch,
+                         int64_t frame_stride, const void* d_state) {
+    if (rest && d_state && (d_bgr || n <= 0) && n >= min_n && src_h > 0 && src_w > 0 && pitch >= (int64_t)src_w * 3 &&
+        (n <= 1 || frame_stride >= (int64_t)(src_h - 1) * pitch + (int64_t)src_w * 3) && !(reinterpret_cast<uintptr_t>(d_state) & 7))
+        return true;
+    set_err("%s: bad arguments (n %d of at least %d, frame %d x %d, pitch %lld, frame stride %lld, state 8-byte aligned, no NULL pointer)",
+            who, n, min_n, src_h, src_w, (long long)pitch, (long long)frame_stride);
+    return false;
+}
+
+// the rectangle [y0, y1) x [x0, x1), which the messages call `noun`, has an interior and lies inside the frame
+static bool check_area(const char* who, const char* noun, int y0, int y1, int x0, int x1, int src_h, int src_w) {
+    if (y0 >= 0 && x0 >= 0 && y1 <= src_h && x1 <= src_w && y1 - y0 >= 3 && x1 - x0 >= 3) return true;
+    set_err("%s: %s [%d, %d) x [%d, %d) is degenerate or outside the %d x %d frame", who, noun, y0, y1, x0, x1, src_h, src_w);
+    return false;
+}
+
+// the per-cell interval rule of the locator
+static bool check_rule(const char* who, int ratio_num, int ratio_den, int min_frames, int max_frames) {
+    if (ratio_num >= 1 && ratio_den >= 1 && ratio_den <= 1024 && min_frames >= 1 && max_frames >= min_frames) return true;
+    set_err("%s: ratio %d / %d (numerator >= 1, denominator 1..1024) or run length %d..%d (1 <= min <= max) out of range", who, ratio_num,
+            ratio_den, min_frames, max_frames);
+    return false;
+}
+
 // ---- subtitle-change frame selector (frame_change.hip) ---------------------------------------------------------------------
 size_t vse_frame_change_state_bytes(int area_h, int area_w) {
     if (area_h < 3 || area_w < 3) return 0;
@@ -428,16 +456,9 @@ size_t vse_frame_change_state_bytes(int area_h, int area_w) {
 
 int vse_frame_change(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0, int y1,
                      int x0, int x1, int edge_thresh, void* d_state, int reset, int32_t* d_counts, void* stream) {
-    if (!c || !d_bgr || !d_state || !d_counts || n <= 0 || src_h <= 0 || src_w <= 0 || pitch < (int64_t)src_w * 3 ||
-        (n > 1 && frame_stride < (int64_t)(src_h - 1) * pitch + (int64_t)src_w * 3) || (reinterpret_cast<uintptr_t>(d_state) & 7)) {
-        set_err("vse_frame_change: bad arguments (n %d, frame %d x %d, pitch %lld, frame stride %lld)", n, src_h, src_w, (long long)pitch,
-                (long long)frame_stride);
+    if (!check_frames("vse_frame_change", c && d_counts, d_bgr, n, 1, src_h, src_w, pitch, frame_stride, d_state) ||
+        !check_area("vse_frame_change", "area", y0, y1, x0, x1, src_h, src_w))
         return VSE_E_INVAL;
-    }
-    if (y0 < 0 || x0 < 0 || y1 > src_h || x1 > src_w || y1 - y0 < 3 || x1 - x0 < 3) {
-        set_err("vse_frame_change: area [%d, %d) x [%d, %d) is degenerate or outside the %d x %d frame", y0, y1, x0, x1, src_h, src_w);
-        return VSE_E_INVAL;
-    }
     return vse_frame_change_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, d_state, reset, d_counts, stream);
 }
 
@@ -458,21 +479,10 @@ size_t vse_frame_cells_state_bytes(int area_h, int area_w) {
 int vse_frame_cells(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0,
                     int x1, int edge_thresh, int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames, void* d_state,
                     int reset, int flush, int32_t* d_totals, int32_t* d_cell_counts, void* stream) {
-    if (!c || (!d_bgr && n > 0) || !d_state || !d_totals || n < 0 || src_h <= 0 || src_w <= 0 || pitch < (int64_t)src_w * 3 ||
-        (n > 1 && frame_stride < (int64_t)(src_h - 1) * pitch + (int64_t)src_w * 3) || (reinterpret_cast<uintptr_t>(d_state) & 7)) {
-        set_err("vse_frame_cells: bad arguments (n %d, frame %d x %d, pitch %lld, frame stride %lld, state 8-byte aligned)", n, src_h, src_w,
-                (long long)pitch, (long long)frame_stride);
+    if (!check_frames("vse_frame_cells", c && d_totals, d_bgr, n, 0, src_h, src_w, pitch, frame_stride, d_state) ||
+        !check_area("vse_frame_cells", "region", y0, y1, x0, x1, src_h, src_w) ||
+        !check_rule("vse_frame_cells", ratio_num, ratio_den, min_frames, max_frames))
         return VSE_E_INVAL;
-    }
-    if (y0 < 0 || x0 < 0 || y1 > src_h || x1 > src_w || y1 - y0 < 3 || x1 - x0 < 3) {
-        set_err("vse_frame_cells: region [%d, %d) x [%d, %d) is degenerate or outside the %d x %d frame", y0, y1, x0, x1, src_h, src_w);
-        return VSE_E_INVAL;
-    }
-    if (ratio_num < 1 || ratio_den < 1 || ratio_den > 1024 || min_frames < 1 || max_frames < min_frames) {
-        set_err("vse_frame_cells: ratio %d / %d (numerator >= 1, denominator 1..1024) or run length %d..%d (1 <= min <= max) out of range",
-                ratio_num, ratio_den, min_frames, max_frames);
-        return VSE_E_INVAL;
-    }
     if (n == 0 && !reset && !flush) return VSE_OK;
     const int rc = vse_frame_cells_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, min_edges, ratio_num, ratio_den,
                                           min_frames, max_frames, d_state, reset, flush, d_totals, d_cell_counts, stream);
@@ -489,21 +499,10 @@ size_t vse_frame_cells_multi_state_bytes(int area_h, int area_w, int nt) {
 int vse_frame_cells_multi(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0, int y1,
                           int x0, int x1, const int* thresholds, int nt, int min_edges, int ratio_num, int ratio_den, int min_frames,
                           int max_frames, void* d_state, int reset, int flush, int32_t* d_totals, void* stream) {
-    if (!c || (!d_bgr && n > 0) || !d_state || !d_totals || n < 0 || src_h <= 0 || src_w <= 0 || pitch < (int64_t)src_w * 3 ||
-        (n > 1 && frame_stride < (int64_t)(src_h - 1) * pitch + (int64_t)src_w * 3) || (reinterpret_cast<uintptr_t>(d_state) & 7)) {
-        set_err("vse_frame_cells_multi: bad arguments (n %d, frame %d x %d, pitch %lld, frame stride %lld, state 8-byte aligned)", n, src_h,
-                src_w, (long long)pitch, (long long)frame_stride);
+    if (!check_frames("vse_frame_cells_multi", c && d_totals, d_bgr, n, 0, src_h, src_w, pitch, frame_stride, d_state) ||
+        !check_area("vse_frame_cells_multi", "region", y0, y1, x0, x1, src_h, src_w) ||
+        !check_rule("vse_frame_cells_multi", ratio_num, ratio_den, min_frames, max_frames))
         return VSE_E_INVAL;
-    }
-    if (y0 < 0 || x0 < 0 || y1 > src_h || x1 > src_w || y1 - y0 < 3 || x1 - x0 < 3) {
-        set_err("vse_frame_cells_multi: region [%d, %d) x [%d, %d) is degenerate or outside the %d x %d frame", y0, y1, x0, x1, src_h, src_w);
-        return VSE_E_INVAL;
-    }
-    if (ratio_num < 1 || ratio_den < 1 || ratio_den > 1024 || min_frames < 1 || max_frames < min_frames) {
-        set_err("vse_frame_cells_multi: ratio %d / %d (numerator >= 1, denominator 1..1024) or run length %d..%d (1 <= min <= max) out of range",
-                ratio_num, ratio_den, min_frames, max_frames);
-        return VSE_E_INVAL;
-    }
     if (!thresholds || nt < 1 || nt > vse_frame_cells_multi_max()) {
         set_err("vse_frame_cells_multi: %d thresholds (1..%d, not NULL)", nt, vse_frame_cells_multi_max());
         return VSE_E_INVAL;
@@ -529,16 +528,9 @@ size_t vse_frame_hold_state_bytes(int area_h, int area_w, int hold) {
 
 int vse_frame_hold(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0,
                    int x1, int edge_thresh, int hold, void* d_state, int64_t fed, int flush, int32_t* d_counts, void* stream) {
-    if (!c || (!d_bgr && n > 0) || !d_state || n < 0 || fed < 0 || src_h <= 0 || src_w <= 0 || pitch < (int64_t)src_w * 3 ||
-        (n > 1 && frame_stride < (int64_t)(src_h - 1) * pitch + (int64_t)src_w * 3) || (reinterpret_cast<uintptr_t>(d_state) & 7)) {
-        set_err("vse_frame_hold: bad arguments (n %d, fed %lld, frame %d x %d, pitch %lld, frame stride %lld, state 8-byte aligned)", n,
-                (long long)fed, src_h, src_w, (long long)pitch, (long long)frame_stride);
+    if (!check_frames("vse_frame_hold", c && fed >= 0, d_bgr, n, 0, src_h, src_w, pitch, frame_stride, d_state) ||
+        !check_area("vse_frame_hold", "area", y0, y1, x0, x1, src_h, src_w))
         return VSE_E_INVAL;
-    }
-    if (y0 < 0 || x0 < 0 || y1 > src_h || x1 > src_w || y1 - y0 < 3 || x1 - x0 < 3) {
-        set_err("vse_frame_hold: area [%d, %d) x [%d, %d) is degenerate or outside the %d x %d frame", y0, y1, x0, x1, src_h, src_w);
-        return VSE_E_INVAL;
-    }
     if (hold < 1 || hold > 32) {
         set_err("vse_frame_hold: hold %d outside 1..32", hold);
         return VSE_E_INVAL;

@@ -49,6 +49,27 @@ class CellsState:
         self.words, self.totals = words, totals
 
 
+class DeviceState:
+    """Base of the callables that run a stateful kernel on a Context batch by batch (frame_select.EngineCounter, EngineHoldCounter,
+    EngineCompositor, area_locator.EngineCells, keyframes.EngineSceneCounter): host frames become a device tensor, and the device
+    state is allocated afresh when the geometry it was made for changes."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self._key = self._state = None
+
+    def _device(self, frames):
+        t = self.ctx.torch
+        return frames if t.is_tensor(frames) else t.from_numpy(np.ascontiguousarray(frames)).to(self.ctx.tdev)
+
+    def _fresh(self, key, make):
+        """-> True when `key` is not the last call's: the state is then a new make(*key), and the caller resets."""
+        if self._key == key:
+            return False
+        self._key, self._state = key, make(*key)
+        return True
+
+
 class DbParams(C.Structure):
     _fields_ = [("box_thresh", C.c_double), ("unclip_ratio", C.c_double), ("thresh", C.c_float),
                 ("max_candidates", C.c_int), ("min_size", C.c_int)]
@@ -237,6 +258,17 @@ class Context:
 
     def stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.tdev).cuda_stream)
+
+    def _frames_args(self, frames_u8, allow_empty=False):
+        """cuda uint8 [n,H,W,3] with packed pixels (any row pitch / frame stride) -> (pointer, n, h, w, pitch, frame stride) as the
+        entry points that read frames take them.  allow_empty: n == 0 (a flush alone) passes a NULL pointer and the strides of
+        packed frames: no frames, no strides to speak of."""
+        assert frames_u8.dtype == self.torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
+        n, h, w, _ = frames_u8.shape
+        if allow_empty and not n:
+            return None, 0, h, w, 3 * w, 3 * w * h
+        assert frames_u8.stride(3) == 1 and frames_u8.stride(2) == 3
+        return C.c_void_p(frames_u8.data_ptr()), n, h, w, frames_u8.stride(1), frames_u8.stride(0)
 
     # ---- streams ----------------------------------------------------------------------------------------
     def streams_concurrent(self, a, b, spin_cycles=1_500_000):
@@ -458,14 +490,11 @@ class Context:
         state: frame_change_state of the area's size (carries the last frame's edge mask to the next call) ->
         cuda int32 [n,3]: edges, appeared, vanished per frame (include/vse_hip.h vse_frame_change)."""
         t = self.torch
-        assert frames_u8.dtype == t.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
-        assert frames_u8.stride(3) == 1 and frames_u8.stride(2) == 3
+        frames = self._frames_args(frames_u8)
         y0, y1, x0, x1 = (int(v) for v in area)
         assert state.dtype == t.uint8 and state.is_contiguous() and state.numel() >= self.lib.vse_frame_change_state_bytes(y1 - y0, x1 - x0)
-        n, h, w, _ = frames_u8.shape
-        out = t.empty((n, 3), dtype=t.int32, device=self.tdev)
-        _check(self.lib.vse_frame_change(self.handle, C.c_void_p(frames_u8.data_ptr()), n, h, w, frames_u8.stride(1),
-                                         frames_u8.stride(0), y0, y1, x0, x1, int(edge_thresh), C.c_void_p(state.data_ptr()),
+        out = t.empty((frames[1], 3), dtype=t.int32, device=self.tdev)
+        _check(self.lib.vse_frame_change(self.handle, *frames, y0, y1, x0, x1, int(edge_thresh), C.c_void_p(state.data_ptr()),
                                          int(bool(reset)), C.c_void_p(out.data_ptr()), self.stream()), "vse_frame_change")
         return out
 
@@ -490,16 +519,14 @@ class Context:
         cuda int32 [gy,gx,4] covered / runs / present / cuts per cell accumulated since the last reset (include/vse_hip.h
         vse_frame_cells); with want_counts (totals, cuda int32 [n,gy,gx,3] edges / appeared / vanished per frame and cell)."""
         t = self.torch
-        assert frames_u8.dtype == t.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
-        assert frames_u8.stride(3) == 1 and frames_u8.stride(2) == 3
+        frames = self._frames_args(frames_u8, allow_empty=True)
+        n = frames[1]
         y0, y1, x0, x1 = (int(v) for v in area)
         gy, gx = self.frame_cells_dims(y1 - y0, x1 - x0)
         assert state.words.numel() >= self.lib.vse_frame_cells_state_bytes(y1 - y0, x1 - x0) and tuple(state.totals.shape) == (gy, gx, 4)
-        n, h, w, _ = frames_u8.shape
         counts = t.empty((n, gy, gx, 3), dtype=t.int32, device=self.tdev) if want_counts else None
         p = CellParams(*(int(v) for v in params))
-        _check(self.lib.vse_frame_cells(self.handle, C.c_void_p(frames_u8.data_ptr()) if n else None, n, h, w, frames_u8.stride(1),
-                                        frames_u8.stride(0), y0, y1, x0, x1, p.edge_thresh, p.min_edges, p.ratio_num, p.ratio_den,
+        _check(self.lib.vse_frame_cells(self.handle, *frames, y0, y1, x0, x1, p.edge_thresh, p.min_edges, p.ratio_num, p.ratio_den,
                                         p.min_frames, p.max_frames, C.c_void_p(state.words.data_ptr()), int(bool(reset)),
                                         int(bool(flush)), C.c_void_p(state.totals.data_ptr()),
                                         C.c_void_p(counts.data_ptr()) if want_counts and n else None, self.stream()), "vse_frame_cells")
@@ -521,19 +548,15 @@ class Context:
         frames_u8, area, reset and flush as there, params: CellParams whose edge_thresh is ignored, state: frame_cells_multi_state of
         the area's size and len(thresholds) -> state.totals, cuda int32 [nt,gy,gx,4], slice k being frame_cells' totals at
         thresholds[k] (include/vse_hip.h vse_frame_cells_multi)."""
-        t = self.torch
-        assert frames_u8.dtype == t.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
-        assert frames_u8.stride(3) == 1 and frames_u8.stride(2) == 3
+        frames = self._frames_args(frames_u8, allow_empty=True)
         y0, y1, x0, x1 = (int(v) for v in area)
         th = [int(v) for v in thresholds]
         nt = len(th)
         gy, gx = self.frame_cells_dims(y1 - y0, x1 - x0)
         nbytes = self.lib.vse_frame_cells_multi_state_bytes(y1 - y0, x1 - x0, nt)
         assert nbytes and state.words.numel() >= nbytes and tuple(state.totals.shape) == (nt, gy, gx, 4)
-        n, h, w, _ = frames_u8.shape
         p = CellParams(*(int(v) for v in params))
-        _check(self.lib.vse_frame_cells_multi(self.handle, C.c_void_p(frames_u8.data_ptr()) if n else None, n, h, w, frames_u8.stride(1),
-                                              frames_u8.stride(0), y0, y1, x0, x1, (C.c_int * nt)(*th), nt, p.min_edges, p.ratio_num,
+        _check(self.lib.vse_frame_cells_multi(self.handle, *frames, y0, y1, x0, x1, (C.c_int * nt)(*th), nt, p.min_edges, p.ratio_num,
                                               p.ratio_den, p.min_frames, p.max_frames, C.c_void_p(state.words.data_ptr()),
                                               int(bool(reset)), int(bool(flush)), C.c_void_p(state.totals.data_ptr()), self.stream()),
                "vse_frame_cells_multi")
@@ -553,18 +576,15 @@ class Context:
         frame_hold_state of the area's size and `hold` -> cuda int32 [rows,3]: held edges, appeared, vanished of the frames whose
         held mask this call completes, which trail the frames fed by hold - 1 until `flush` (include/vse_hip.h vse_frame_hold)."""
         t = self.torch
-        assert frames_u8.dtype == t.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
-        n, h, w, _ = frames_u8.shape
-        pitch, fstride = (frames_u8.stride(1), frames_u8.stride(0)) if n else (3 * w, 3 * w * h)      # (no frames: no strides to speak of)
-        assert not n or (frames_u8.stride(3) == 1 and frames_u8.stride(2) == 3)
+        frames = self._frames_args(frames_u8, allow_empty=True)
+        n = frames[1]
         y0, y1, x0, x1 = (int(v) for v in area)
         hold, fed = int(hold), int(fed)
         nbytes = self.lib.vse_frame_hold_state_bytes(y1 - y0, x1 - x0, hold)
         assert nbytes and state.dtype == t.uint8 and state.is_contiguous() and state.numel() >= nbytes
         rows = (fed + n if flush else max(0, fed + n - hold + 1)) - max(0, fed - hold + 1)
         out = t.empty((n + hold - 1, 3), dtype=t.int32, device=self.tdev)
-        _check(self.lib.vse_frame_hold(self.handle, C.c_void_p(frames_u8.data_ptr()) if n else None, n, h, w, pitch,
-                                       fstride, y0, y1, x0, x1, int(edge_thresh), hold, C.c_void_p(state.data_ptr()),
+        _check(self.lib.vse_frame_hold(self.handle, *frames, y0, y1, x0, x1, int(edge_thresh), hold, C.c_void_p(state.data_ptr()),
                                        fed, int(bool(flush)), C.c_void_p(out.data_ptr()), self.stream()), "vse_frame_hold")
         return out[:rows]
 
@@ -581,13 +601,10 @@ class Context:
         state: interval_state of the area's size -> state, now holding the per-byte min, max and sum of the area over the frames
         since the last reset (include/vse_hip.h vse_interval_accumulate)."""
         t = self.torch
-        assert frames_u8.dtype == t.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
-        assert frames_u8.stride(3) == 1 and frames_u8.stride(2) == 3
+        frames = self._frames_args(frames_u8)
         y0, y1, x0, x1 = (int(v) for v in area)
         assert state.dtype == t.uint8 and state.is_contiguous() and state.numel() >= max(self.lib.vse_interval_state_bytes(y1 - y0, x1 - x0), 1)
-        n, h, w, _ = frames_u8.shape
-        _check(self.lib.vse_interval_accumulate(self.handle, C.c_void_p(frames_u8.data_ptr()), n, h, w, frames_u8.stride(1),
-                                                frames_u8.stride(0), y0, y1, x0, x1, C.c_void_p(state.data_ptr()), int(bool(reset)),
+        _check(self.lib.vse_interval_accumulate(self.handle, *frames, y0, y1, x0, x1, C.c_void_p(state.data_ptr()), int(bool(reset)),
                                                 self.stream()), "vse_interval_accumulate")
         return state
 
@@ -687,16 +704,14 @@ class Context:
         blocks' best inter SADs, sum of their intra deviations per frame (include/vse_hip.h vse_scene_change).
         workspace: cuda uint8 of at least vse_scene_change_workspace_bytes (allocated if None)."""
         t = self.torch
-        assert frames_u8.dtype == t.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3
-        assert frames_u8.stride(3) == 1 and frames_u8.stride(2) == 3
-        n, h, w, _ = frames_u8.shape
+        frames = self._frames_args(frames_u8)
+        _, n, h, w = frames[:4]
         assert state.dtype == t.uint8 and state.is_contiguous()
         assert state.numel() >= max(self.lib.vse_scene_change_state_bytes(h, w, int(scale)), 1)
         if workspace is None:
             workspace = t.empty(max(self.lib.vse_scene_change_workspace_bytes(n, h, w, int(scale)), 256), dtype=t.uint8, device=self.tdev)
         out = t.empty((n, 3), dtype=t.int32, device=self.tdev)
-        _check(self.lib.vse_scene_change(self.handle, C.c_void_p(frames_u8.data_ptr()), n, h, w, frames_u8.stride(1), frames_u8.stride(0),
-                                         int(scale), int(search), int(bias), C.c_void_p(state.data_ptr()), int(bool(reset)),
+        _check(self.lib.vse_scene_change(self.handle, *frames, int(scale), int(search), int(bias), C.c_void_p(state.data_ptr()), int(bool(reset)),
                                          C.c_void_p(workspace.data_ptr()), workspace.numel(), C.c_void_p(out.data_ptr()), self.stream()),
                "vse_scene_change")
         return out

@@ -390,6 +390,11 @@ class SubtitleExtractor:
             return self.change_params or {}
         return {**self.change_params, "edge_thresh": 128 if self.edge_thresh is None else self.edge_thresh}
 
+    def _interval_selector(self):
+        """The change or hold selector of this run (`_selects_intervals`); both take run / iter_run(frames, sub_area, fps, uploader)."""
+        cls = frame_select.ChangeFrameSelector if self.frame_selector == "change" else frame_select.HoldFrameSelector
+        return cls(self.change_counter, batch=self.batch, **self._change_params())
+
     def select_tasks(self):
         s = self.source
         if self.sub_area is not None and self.mode == "accurate" and self.detect_batch is not None:
@@ -400,15 +405,9 @@ class SubtitleExtractor:
                                                      detect_stream=self.detect_stream,
                                                      predict_with_dets=getattr(self.ocr, "predict_with_dets", None))
             return [(t[0], t[1], t[2], t[3], None, None) for t in sel.run(self._decode_order(up), uploader=up)]
-        if self.sub_area is not None and self.mode in ("fast", "auto") and self.frame_selector == "change":
-            sel = frame_select.ChangeFrameSelector(self.change_counter, batch=self.batch, **self._change_params())
+        if self._selects_intervals():
             up = self._uploader()
-            self.intervals = sel.run(self._decode_order(up), self.sub_area, uploader=up)
-            return [(s.frame_count, rep, None, None, None, self.default_subtitle_area) for _start, _end, rep in self.intervals]
-        if self.sub_area is not None and self.mode in ("fast", "auto") and self.frame_selector == "hold":
-            sel = frame_select.HoldFrameSelector(self.change_counter, batch=self.batch, **self._change_params())
-            up = self._uploader()
-            self.intervals = sel.run(self._decode_order(up), self.sub_area, s.fps, uploader=up)
+            self.intervals = self._interval_selector().run(self._decode_order(up), self.sub_area, s.fps, uploader=up)
             return [(s.frame_count, rep, None, None, None, self.default_subtitle_area) for _start, _end, rep in self.intervals]
         return fps_tasks(s.frame_count, s.fps, self.extract_frequency, self.default_subtitle_area)
 
@@ -460,13 +459,8 @@ class SubtitleExtractor:
         return lines
 
     def _one_pass_intervals(self, frames, uploader):
-        s = self.source
-        if self.frame_selector == "change":
-            sel = frame_select.ChangeFrameSelector(self.change_counter, batch=self.batch, **self._change_params())
-            batches = sel.iter_run(frames, self.sub_area, uploader=uploader)
-        else:
-            sel = frame_select.HoldFrameSelector(self.change_counter, batch=self.batch, **self._change_params())
-            batches = sel.iter_run(frames, self.sub_area, s.fps, uploader=uploader)
+        sel = self._interval_selector()
+        batches = sel.iter_run(frames, self.sub_area, self.source.fps, uploader=uploader)
         # the recogniser's batches are staged while the selector's producer thread stages the next bands: a slab ring of their own
         ocr_up = uploader.sibling() if uploader is not None else None
         self.intervals = []
@@ -515,7 +509,7 @@ class SubtitleExtractor:
         self.clamped_intervals = self.peak_retained = 0
         up = self._uploader()
         frames = self._decode_order(up)
-        if self.sub_area is not None and self.mode in ("fast", "auto") and self.frame_selector in ("change", "hold"):
+        if self._selects_intervals():
             return self._one_pass_intervals(frames, up)
         return self._one_pass_fps(frames, up)
 

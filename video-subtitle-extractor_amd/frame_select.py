@@ -10,9 +10,19 @@ of a subtitle is the first frame whose in-area text has Levenshtein ratio <= thr
 first frame without an in-area box; cached OCR results older than 10 frames are evicted; when tasks are flushed the
 cached result is looked up by the CURRENT frame number (not the queued one), so a task carries boxes/text only when
 those coincide.
+
+The interval side (subtitle-change selection and what follows it) shares its plumbing: `band_batches` reads the first frame, clips
+the area and hands out batches of (full frame, the area's rows), keeping no frame behind; `staging.staged_batches` turns such batches
+into stacked data, through an uploader's pinned memory and producer thread or with np.stack on the host; `_IntervalSelector` is the
+one run / iter_run body of ChangeFrameSelector and HoldFrameSelector; and the Engine* callables keep their device state through
+`engine.DeviceState`.  area_locator.AreaLocator and keyframes.scan stand on the same pieces.
 """
 from collections import deque
+from contextlib import closing
+from itertools import islice
 
+from . import staging
+from .engine import DeviceState
 from .shim import get_coordinates
 
 
@@ -248,37 +258,47 @@ def clip_area(sub_area, h, w):
     return max(0, int(sub_area.ymin)), min(h, int(sub_area.ymax)), max(0, int(sub_area.xmin)), min(w, int(sub_area.xmax))
 
 
-class EngineCounter:
+class band_batches:
+    """The frames of a clip as batches of their band: iterating yields lists of (full frame, frame[y0:y1]) of at most `batch` frames,
+    in decode order, and keeps no reference to a frame once the list holding it has been handed out (a caller that drops a frame it
+    was handed frees it).  `region` (.ymin .ymax .xmin .xmax, or None for the whole frame) is clipped to the first frame, which is read
+    at once: `geometry` = (y0, y1, x0, x1) in frame pixels, `frame_hw`, and `area`, the same rectangle in the band's own pixels
+    (0, y1 - y0, x0, x1), are known before the first batch; all three are None when there is no frame.  ValueError in the name of
+    `who` when less than min_size x min_size pixels remain."""
+
+    def __init__(self, frames, region, batch, who, min_size=3):
+        self._it, self._batch = iter(frames), batch
+        self._head = list(islice(self._it, 1))
+        self.geometry = self.frame_hw = self.area = None
+        if self._head:
+            h, w = self._head[0].shape[:2]
+            y0, y1, x0, x1 = (0, h, 0, w) if region is None else clip_area(region, h, w)
+            if y1 - y0 < min_size or x1 - x0 < min_size:
+                raise ValueError(f"{who}: subtitle area {region} leaves less than {min_size} x {min_size} pixels of a {h} x {w} frame")
+            self.geometry, self.frame_hw, self.area = (y0, y1, x0, x1), (h, w), (0, y1 - y0, x0, x1)
+
+    def _take(self):
+        frames, self._head = self._head, []
+        frames.extend(islice(self._it, self._batch - len(frames)))
+        return [(f, f[self.geometry[0]:self.geometry[1]]) for f in frames]
+
+    def __iter__(self):
+        return iter(self._take, [])           # (no generator frame that would hold on to the list it yielded last)
+
+
+class EngineCounter(DeviceState):
     """count_fn of ChangeFrameSelector on the GPU (Context.frame_change): keeps the device state of the last area between calls."""
 
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self._state = None
-        self._shape = None
-
     def __call__(self, frames, area, edge_thresh, reset):
-        t = self.ctx.torch
-        if not t.is_tensor(frames):
-            frames = t.from_numpy(frames).to(self.ctx.tdev)
         y0, y1, x0, x1 = area
-        if self._shape != (y1 - y0, x1 - x0):
-            self._shape = (y1 - y0, x1 - x0)
-            self._state = self.ctx.frame_change_state(*self._shape)
-            reset = True
-        return self.ctx.frame_change(frames, area, edge_thresh, self._state, reset)
+        reset = self._fresh((y1 - y0, x1 - x0), self.ctx.frame_change_state) or reset
+        return self.ctx.frame_change(self._device(frames), area, edge_thresh, self._state, reset)
 
 
-class ChangeFrameSelector:
-    """The role of VideoSubFinder in fast / auto mode with a subtitle area (backend/main.py:137-147, 378-505): look at EVERY frame
-    of the area and report where each subtitle starts and stops, so that one frame per subtitle goes to OCR and the SRT takes
-    its times from the intervals (srt.generate_subtitle_file_intervals).  VideoSubFinder is a closed binary; this is not its
-    algorithm but the same role: per frame the device counts the area's luma edge pixels and how many of them appeared or
-    vanished against the frame before (vse_frame_change), and change_intervals turns those integers into intervals.
-    The defaults lean towards cutting: an extra cut costs one OCR call and the duplicate removal merges it again, a missed
-    change loses a subtitle.
-
-    count_fn(frames [n,h,w,3] uint8, area (y0, y1, x0, x1) in their pixels, edge_thresh, reset) -> [n,3] counts; it carries the
-    last frame's mask to the next call (reset on the first batch of a clip).  Default: EngineCounter on the shim's device."""
+class _IntervalSelector:
+    """The body ChangeFrameSelector and HoldFrameSelector share: frames -> band_batches -> staging.staged_batches -> count_fn ->
+    IntervalTracker.  A selector says which engine callable is its default count_fn, what the tracker's min_frames is (`_min_frames`),
+    how count_fn is called per batch (`_count`) and what follows the last batch (`_flush`)."""
 
     def __init__(self, count_fn=None, edge_thresh=128, change_ratio=0.5, min_edges=None, min_frames=2, batch=64):
         self.count_fn = count_fn
@@ -287,65 +307,73 @@ class ChangeFrameSelector:
         self.counts = None
         self.intervals = None
 
-    def run(self, frames, sub_area, uploader=None):
-        """frames: iterable of uint8 BGR frames in decode order; sub_area: .ymin .ymax .xmin .xmax in frame pixels (clipped to
-        the frame) -> [(start, end, rep)].  Only the area's rows are staged; with an uploader (staging.Uploader) they go through
-        pinned memory on its producer thread, which uploads the next batches while the counts of this one are resolved."""
-        for _ in self.iter_run(frames, sub_area, uploader):
+    def run(self, frames, sub_area, fps=None, uploader=None):
+        """frames: iterable of uint8 BGR frames in decode order; sub_area: .ymin .ymax .xmin .xmax in frame pixels (clipped to the
+        frame); fps: the clip's frame rate (the hold selector's hold_seconds; the change selector ignores it) -> [(start, end, rep)].
+        Only the area's rows are staged (band_batches), through `uploader` when there is one (staging.staged_batches)."""
+        for _ in self.iter_run(frames, sub_area, fps, uploader):
             pass
         return self.intervals
 
-    def iter_run(self, frames, sub_area, uploader=None):
+    def iter_run(self, frames, sub_area, fps=None, uploader=None):
         """run() as a generator: per staged batch (items, the intervals its rows closed), items = [(full frame, its area rows)] in
         decode order, so a caller that may need a frame again receives it with the batch itself; after the last batch one more
-        ([], the interval the end of the clip closed).  `tracker` (IntervalTracker) is in step with what has been yielded;
-        `intervals` grows as they close, `counts` is set when the generator is exhausted."""
+        ([], what the flushed rows and the end of the clip closed).  `tracker` (IntervalTracker) is in step with what has been
+        yielded: `tracker.fed` is the last frame whose row has been seen (the hold selector's rows trail its frames by hold - 1 until
+        the flush, and the frames behind it are still the caller's to keep); `intervals` grows as they close, `counts` is set when
+        the generator is exhausted."""
         import numpy as np
         if self.count_fn is None:
             from . import shim
-            self.count_fn = EngineCounter(shim._context())
+            self.count_fn = self.engine_count_fn(shim._context())
+        min_frames = self._min_frames(fps)
         self.counts, self.intervals, self.tracker = np.zeros((0, 3), np.int32), [], None
-        it = iter(frames)
-        first = next(it, None)
-        if first is None:
+        bands = band_batches(frames, sub_area, self.batch, type(self).__name__)
+        if bands.area is None:
             return
-        h, w = first.shape[:2]
-        y0, y1, x0, x1 = clip_area(sub_area, h, w)
-        if y1 - y0 < 3 or x1 - x0 < 3:
-            raise ValueError(f"ChangeFrameSelector: subtitle area {sub_area} leaves less than 3 x 3 pixels of a {h} x {w} frame")
-        area = (0, y1 - y0, x0, x1)
-        min_edges = default_min_edges(y1 - y0, x1 - x0) if self.min_edges is None else self.min_edges
-        self.tracker = IntervalTracker(min_edges, self.change_ratio, self.min_frames)
+        min_edges = default_min_edges(bands.area[1], bands.area[3] - bands.area[2]) if self.min_edges is None else self.min_edges
+        self.tracker = IntervalTracker(min_edges, self.change_ratio, min_frames)
 
-        def batches(buf):
-            for f in it:
-                if len(buf) == self.batch:
-                    yield buf
-                    buf = []
-                buf.append((f, f[y0:y1]))
-            yield buf
-
-        todo = batches([(first, first[y0:y1])])
-        del first                         # a caller that drops a frame it was handed frees it
-        if uploader is not None:
-            from . import staging
-            staged = ((items, sb.tensor) for items, sb in staging.prefetch(todo, uploader))
-        else:
-            staged = ((items, lambda items=items: np.stack([band for _, band in items])) for items in todo)
-        out = []
-        for k, (items, data) in enumerate(staged):
-            out.append(np.asarray(self._host(self.count_fn(data(), area, self.edge_thresh, k == 0))))
+        def feed(c):
+            out.append(np.asarray(c.cpu() if hasattr(c, "cpu") else c, np.int32).reshape(-1, 3))
             closed = self.tracker.feed(out[-1])
             self.intervals += closed
-            yield items, closed
-        self.counts = np.concatenate(out)
-        closed = self.tracker.flush()
-        self.intervals += closed
-        yield [], closed
+            return closed
 
-    @staticmethod
-    def _host(c):
-        return c.cpu() if hasattr(c, "cpu") else c
+        out, fed, data = [], 0, None
+        with closing(staging.staged_batches(bands, uploader)) as staged:
+            for items, data in staged:
+                closed = feed(self._count(data, bands.area, fed))
+                fed += len(items)
+                yield items, closed
+        closed = feed(self._flush(data, bands.area, fed))
+        self.counts = np.concatenate(out)
+        last = self.tracker.flush()
+        self.intervals += last
+        yield [], closed + last
+
+
+class ChangeFrameSelector(_IntervalSelector):
+    """The role of VideoSubFinder in fast / auto mode with a subtitle area (backend/main.py:137-147, 378-505): look at EVERY frame
+    of the area and report where each subtitle starts and stops, so that one frame per subtitle goes to OCR and the SRT takes
+    its times from the intervals (srt.generate_subtitle_file_intervals).  VideoSubFinder is a closed binary; this is not its
+    algorithm but the same role: per frame the device counts the area's luma edge pixels and how many of them appeared or
+    vanished against the frame before (vse_frame_change), and change_intervals turns those integers into intervals.
+    The defaults lean towards cutting: an extra cut costs one OCR call and the duplicate removal merges it again, a missed
+    change loses a subtitle.  run / iter_run: _IntervalSelector's.
+
+    count_fn(frames [n,h,w,3] uint8, area (y0, y1, x0, x1) in their pixels, edge_thresh, reset) -> [n,3] counts; it carries the
+    last frame's mask to the next call (reset on the first batch of a clip).  Default: EngineCounter on the shim's device."""
+    engine_count_fn = EngineCounter
+
+    def _min_frames(self, fps):
+        return self.min_frames
+
+    def _count(self, data, area, fed):
+        return self.count_fn(data, area, self.edge_thresh, fed == 0)
+
+    def _flush(self, data, area, fed):
+        return ()                         # every row came with its frame
 
 
 # ---- held-edge selection (the change selector for footage whose background moves) ------------------------------------------
@@ -355,33 +383,24 @@ def hold_intervals(counts, min_edges, hold, change_ratio=0.5, min_frames=2):
     return change_intervals(counts, min_edges, change_ratio, max(min_frames, hold))
 
 
-class EngineHoldCounter:
+class EngineHoldCounter(DeviceState):
     """count_fn of HoldFrameSelector on the GPU (Context.frame_hold): keeps the device state of the last area and `hold`, and the
     number of frames of the clip fed so far, between calls."""
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self._state = None
-        self._key = None
-        self.fed = 0
+    fed = 0
 
     def __call__(self, frames, area, edge_thresh, hold, fed, flush):
-        t = self.ctx.torch
-        if not t.is_tensor(frames):
-            frames = t.from_numpy(frames).to(self.ctx.tdev)
         y0, y1, x0, x1 = area
-        if self._key != (y1 - y0, x1 - x0, hold):
-            if fed:
-                raise ValueError(f"EngineHoldCounter: the area or hold changed to {(y1 - y0, x1 - x0, hold)} after {fed} frames of a clip")
-            self._key = (y1 - y0, x1 - x0, hold)
-            self._state = self.ctx.frame_hold_state(*self._key)
+        key = (y1 - y0, x1 - x0, hold)
+        if fed and self._key != key:
+            raise ValueError(f"EngineHoldCounter: the area or hold changed to {key} after {fed} frames of a clip")
+        self._fresh(key, self.ctx.frame_hold_state)
         if fed and fed != self.fed:
             raise ValueError(f"EngineHoldCounter: fed {fed}, but {self.fed} frames of this clip went to earlier calls")
         self.fed = fed + len(frames)
-        return self.ctx.frame_hold(frames, area, edge_thresh, hold, self._state, fed, flush)
+        return self.ctx.frame_hold(self._device(frames), area, edge_thresh, hold, self._state, fed, flush)
 
 
-class HoldFrameSelector:
+class HoldFrameSelector(_IntervalSelector):
     """ChangeFrameSelector for footage whose background moves behind the subtitle.  The change selector compares every edge pixel of the
     area with the frame before; a textured background that pans puts hundreds of edge pixels into the band that all move every
     frame, so every frame is a cut and no subtitle is found.  A subtitle's edges hold still for many frames and a moving background's
@@ -390,91 +409,32 @@ class HoldFrameSelector:
     `hold_frames`, or max(1, min(32, round(hold_seconds * fps))) when it is None; hold_seconds=0.3 and the behaviour on real footage
     are not measured here (no real clips).  Known limit: background edges that stay on one pixel for `hold` frames still count (a
     static busy shot, a pan along an edge's own direction: in a numpy prototype a horizontal pan at hold 2-5 added intervals in the
-    gaps); such intervals cost OCR calls and lose no subtitle.
+    gaps); such intervals cost OCR calls and lose no subtitle.  run / iter_run: _IntervalSelector's, with fps; after the last batch a
+    call without frames flushes the rows still pending.
 
     count_fn(frames [n,h,w,3] uint8, area (y0, y1, x0, x1) in their pixels, edge_thresh, hold, fed, flush) -> [rows,3] counts of the
     frames whose held mask the call completes: they trail the frames fed by hold - 1 until the flush (fed: frames of the clip given
     to earlier calls, 0 on the first batch; flush: the clip ends with this call).  Default: EngineHoldCounter on the shim's device."""
+    engine_count_fn = EngineHoldCounter
 
     def __init__(self, count_fn=None, hold_seconds=0.3, hold_frames=None, edge_thresh=128, change_ratio=0.5, min_edges=None,
                  min_frames=2, batch=64):
-        self.count_fn = count_fn
+        super().__init__(count_fn, edge_thresh, change_ratio, min_edges, min_frames, batch)
         self.hold_seconds, self.hold_frames = hold_seconds, hold_frames
-        self.edge_thresh, self.change_ratio, self.min_edges, self.min_frames = edge_thresh, change_ratio, min_edges, min_frames
-        self.batch = batch
         self.hold = None              # the hold of the last run, in frames
-        self.counts = None
-        self.intervals = None
 
-    def run(self, frames, sub_area, fps, uploader=None):
-        """frames: iterable of uint8 BGR frames in decode order; sub_area: .ymin .ymax .xmin .xmax in frame pixels (clipped to the
-        frame); fps: the clip's frame rate (for hold_seconds) -> [(start, end, rep)].  Batches are staged as ChangeFrameSelector.run
-        stages them; after the last one a call without frames flushes the rows still pending."""
-        for _ in self.iter_run(frames, sub_area, fps, uploader):
-            pass
-        return self.intervals
-
-    def iter_run(self, frames, sub_area, fps, uploader=None):
-        """run() as a generator, as ChangeFrameSelector.iter_run: per staged batch (items = [(full frame, its area rows)], the intervals
-        its rows closed), then ([], what the flushed rows and the end of the clip closed).  The rows of a batch trail its frames by
-        hold - 1 until the flush: `tracker.fed` is the last frame whose row has been seen, and the frames behind it are still the
-        caller's to keep."""
-        import numpy as np
-        if self.count_fn is None:
-            from . import shim
-            self.count_fn = EngineHoldCounter(shim._context())
+    def _min_frames(self, fps):
         hold = self.hold_frames if self.hold_frames is not None else max(1, min(32, int(round(self.hold_seconds * fps))))
         if not 1 <= hold <= 32:
             raise ValueError(f"HoldFrameSelector: hold_frames must be 1..32, not {hold}")
         self.hold = hold
-        self.counts, self.intervals, self.tracker = np.zeros((0, 3), np.int32), [], None
-        it = iter(frames)
-        first = next(it, None)
-        if first is None:
-            return
-        h, w = first.shape[:2]
-        y0, y1, x0, x1 = clip_area(sub_area, h, w)
-        if y1 - y0 < 3 or x1 - x0 < 3:
-            raise ValueError(f"HoldFrameSelector: subtitle area {sub_area} leaves less than 3 x 3 pixels of a {h} x {w} frame")
-        area = (0, y1 - y0, x0, x1)
-        min_edges = default_min_edges(y1 - y0, x1 - x0) if self.min_edges is None else self.min_edges
-        self.tracker = IntervalTracker(min_edges, self.change_ratio, max(self.min_frames, hold))      # (hold_intervals' min_frames)
+        return max(self.min_frames, hold)                  # (hold_intervals' min_frames)
 
-        def batches(buf):
-            for f in it:
-                if len(buf) == self.batch:
-                    yield buf
-                    buf = []
-                buf.append((f, f[y0:y1]))
-            yield buf
+    def _count(self, data, area, fed):
+        return self.count_fn(data, area, self.edge_thresh, self.hold, fed, False)
 
-        todo = batches([(first, first[y0:y1])])
-        del first                         # a caller that drops a frame it was handed frees it
-
-        def rows(c):
-            return np.asarray(self._host(c), np.int32).reshape(-1, 3)
-
-        out, fed = [], 0
-        if uploader is not None:
-            from . import staging
-            staged = ((items, sb.tensor) for items, sb in staging.prefetch(todo, uploader))
-        else:
-            staged = ((items, lambda items=items: np.stack([band for _, band in items])) for items in todo)
-        data = None
-        for items, get in staged:
-            data = get()
-            out.append(rows(self.count_fn(data, area, self.edge_thresh, hold, fed, False)))
-            fed += len(items)
-            closed = self.tracker.feed(out[-1])
-            self.intervals += closed
-            yield items, closed
-        out.append(rows(self.count_fn(data[:0], area, self.edge_thresh, hold, fed, True)))
-        self.counts = np.concatenate(out)
-        closed = self.tracker.feed(out[-1]) + self.tracker.flush()
-        self.intervals += closed
-        yield [], closed
-
-    _host = staticmethod(ChangeFrameSelector._host)
+    def _flush(self, data, area, fed):
+        return self.count_fn(data[:0], area, self.edge_thresh, self.hold, fed, True)
 
 
 # ---- interval composite (one picture per interval of the change selector) ------------------------------------------------
@@ -488,26 +448,15 @@ def trim_range(start, end, fps, trim_seconds):
     return start + tr, end - tr
 
 
-class EngineCompositor:
+class EngineCompositor(DeviceState):
     """accumulate_fn of IntervalCompositor on the GPU (Context.interval_accumulate / interval_composite): keeps the device state
     of the last area and the frame count of the open interval between calls."""
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self._state = None
-        self._shape = None
-        self._count = 0
+    _count = 0
 
     def __call__(self, frames, area, reset, mode=None):
-        t = self.ctx.torch
-        if not t.is_tensor(frames):
-            frames = t.from_numpy(frames).to(self.ctx.tdev)
         y0, y1, x0, x1 = area
-        if self._shape != (y1 - y0, x1 - x0):
-            self._shape = (y1 - y0, x1 - x0)
-            self._state = self.ctx.interval_state(*self._shape)
-            reset = True
-        self.ctx.interval_accumulate(frames, area, self._state, reset)
+        reset = self._fresh((y1 - y0, x1 - x0), self.ctx.interval_state) or reset
+        self.ctx.interval_accumulate(self._device(frames), area, self._state, reset)
         self._count = len(frames) if reset else self._count + len(frames)
         return None if mode is None else self.ctx.interval_composite(self._state, y1 - y0, x1 - x0, self._count, mode)
 
@@ -536,8 +485,7 @@ class IntervalCompositor:
         """frames: iterable of uint8 BGR frames in decode order (read once, and not beyond the last frame that is needed);
         sub_area: clipped to the frame exactly as ChangeFrameSelector.run clips it; intervals: its [(start, end, rep)], ascending;
         only: a range of interval indices (a rank's shard), the others are not composited -> {rep: uint8 ndarray [ah, aw, 3]}.
-        Only the area's rows of the frames inside a used range are staged; with an uploader (staging.Uploader) they go through
-        pinned memory on its producer thread."""
+        Only the area's rows of the frames inside a used range are staged (staging.staged_batches)."""
         import numpy as np
         if self.accumulate_fn is None:
             from . import shim
@@ -589,13 +537,8 @@ class IntervalCompositor:
             if closes:
                 self.patches[rep] = out.cpu().numpy() if hasattr(out, "cpu") else np.array(out)
 
-        if uploader is not None:
-            from . import staging
-            for items, staged in staging.prefetch(batches(), uploader):
-                fold(items, staged.tensor())
-        else:
-            for items in batches():
-                fold(items, np.stack([f for _, f in items]))
+        for items, data in staging.staged_batches(batches(), uploader):
+            fold(items, data)
         self.area = tuple(geometry)
         return self.patches
 
@@ -636,9 +579,7 @@ class IntervalFuser:
         """frames: iterable of uint8 BGR frames in decode order (read once, and not beyond the last frame that is needed); intervals:
         the selector's [(start, end, rep)], ascending; only: a range of interval indices (a rank's shard), the others are not read;
         default_area: the half-frame crop a task's frame gets (extractor.frame_preprocess), applied to every sample
-        -> {rep: (dt_box, rec_res)}.  With an uploader (staging.Uploader) the sampled frames go through pinned memory on its producer
-        thread."""
-        import numpy as np
+        -> {rep: (dt_box, rec_res)}.  The sampled frames are staged by staging.staged_batches."""
         if self.fuse_fn is None:
             from . import shim
             self.fuse_fn = shim.OcrRecogniser().predict_fused
@@ -685,11 +626,6 @@ class IntervalFuser:
             for (rep, _nos, _pos), r in zip(call, out):
                 self.results[rep] = r
 
-        if uploader is not None:
-            from . import staging
-            for call, (_items, staged) in zip(plan, staging.prefetch(batches(), uploader)):
-                fuse(call, staged.tensor())
-        else:
-            for call, items in zip(plan, batches()):
-                fuse(call, np.stack([np.asarray(f) for _, f in items]))
+        for call, (_items, data) in zip(plan, staging.staged_batches(batches(), uploader)):
+            fuse(call, data)
         return self.results

@@ -27,6 +27,8 @@ import sys
 
 import numpy as np
 
+from . import staging
+from .engine import DeviceState
 from .timeline_sync import TimelineSyncError
 
 MB = 16
@@ -37,23 +39,16 @@ def default_scale(width):
     return min(max(1, int(width) // 640), 8)
 
 
-class EngineSceneCounter:
+class EngineSceneCounter(DeviceState):
     """The counter of SceneCutDetector on the GPU (engine.Context.scene_change): keeps the device state and a workspace between
     calls."""
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self._key = self._state = self._ws = None
+    _ws = None
 
     def __call__(self, frames, scale, search, bias, reset):
         t = self.ctx.torch
-        if not t.is_tensor(frames):
-            frames = t.from_numpy(np.ascontiguousarray(frames)).to(self.ctx.tdev)
+        frames = self._device(frames)
         n, h, w, _ = frames.shape
-        if self._key != (h, w, scale):
-            self._key = (h, w, scale)
-            self._state = self.ctx.scene_change_state(h, w, scale)
-            reset = True
+        reset = self._fresh((h, w, scale), self.ctx.scene_change_state) or reset
         need = self.ctx.lib.vse_scene_change_workspace_bytes(n, h, w, scale)
         if self._ws is None or self._ws.numel() < need:
             self._ws = t.empty(max(need, 256), dtype=t.uint8, device=self.ctx.tdev)
@@ -119,23 +114,15 @@ def scan(source, ctx=None, batch=64, **detector_options):
         if group:
             yield group
 
-    def feed(first_frame, frames):
-        nonlocal det
-        if det is None:
-            det = SceneCutDetector(ctx, first_frame.shape[0], first_frame.shape[1], **detector_options)
-        keyframes.extend(det.feed(frames))
-
-    if on_engine:
-        from . import staging
-        up = staging.Uploader(ctx.tdev)
-        try:
-            for items, staged in staging.prefetch(batches(), up):
-                feed(items[0][1], staged.tensor())
-        finally:
+    up = staging.Uploader(ctx.tdev) if on_engine else None
+    try:
+        for items, data in staging.staged_batches(batches(), up):
+            if det is None:
+                det = SceneCutDetector(ctx, items[0][1].shape[0], items[0][1].shape[1], **detector_options)
+            keyframes.extend(det.feed(data))
+    finally:
+        if up is not None:
             up.close()
-    else:
-        for items in batches():
-            feed(items[0][1], np.stack([f for _, f in items]))
     return keyframes, (det.frames_seen if det else 0)
 
 

@@ -10,6 +10,8 @@ producer thread while the current one is recognised (`prefetch`).
     up = Uploader(device)                         # torch.device / "cuda:0"
     for items, batch in prefetch(batches, up):    # batches: iterable of lists of (key, frame) with equal frame shapes
         dev = batch.tensor()                      # uint8 [n,H,W,3] on the device, ordered after the copy on the current stream
+    for items, data in staged_batches(batches, up_or_none):     # the same, for a caller that also runs without an uploader:
+        ...                                       # data is that device tensor, or np.stack of the frames when up_or_none is None
 
 Frames that are still YUV 4:2:0 (ingest.Yuv420Frame, from a source's read_raw / raw_frames) are packed into the slab as they are — 1.5
 bytes per pixel, half the slab copy and half the PCIe bytes of a BGR frame — and converted to BGR by one kernel on the copy stream
@@ -179,3 +181,19 @@ def prefetch(batches, uploader, ahead=2):
                 q.get_nowait()
             except queue.Empty:
                 th.join(0.01)
+
+
+def staged_batches(batches, uploader):
+    """Iterate (items, data) over `batches` (lists of (key, frame)) for a consumer that takes its frames stacked: with an uploader
+    `data` is the device tensor of `prefetch`'s StagedBatch, without one np.stack of the frames on the host.  Closing the generator
+    closes `prefetch`, which stops its producer thread."""
+    if uploader is None:
+        for items in batches:
+            yield items, np.stack([np.asarray(f) for _, f in items])
+        return
+    staged = prefetch(batches, uploader)
+    try:
+        for items, sb in staged:
+            yield items, sb.tensor()
+    finally:
+        staged.close()
