@@ -346,6 +346,38 @@ int vse_frame_hold(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w,
                    int y0, int y1, int x0, int x1, int edge_thresh, int hold, void* d_state, int64_t fed, int flush,
                    int32_t* d_counts /* [n + hold - 1, 3]: held edges, appeared, vanished */, void* stream);
 
+/* ---- locator and calibration on held edges ------------------------------------------------------------------------------ */
+/* Replaces: nothing in the reference; it serves vse_frame_hold's footage.  vse_frame_cells and vse_frame_cells_multi run the cell
+ * automaton on vse_frame_change's edge masks, and behind a subtitle whose textured background moves every frame is a cut in every
+ * cell: no area, no threshold.  Here the same cells, automaton and thresholds on HELD masks.  For each of nt thresholds (as for
+ * vse_frame_cells_multi: 1 <= nt <= 8, ascending, distinct, each 1..255; a host array) H_u is vse_frame_hold's held mask of frame u
+ * at that threshold and `hold` (1..32), and per cell of 8 x 64 interior pixels (vse_frame_cells' cells) and frame u
+ *   e = |H_u|,  a = |H_u \ H_{u-1}|,  v = |H_{u-1} \ H_u|
+ * go in frame order to vse_frame_cells' unchanged automaton, which leaves covered, runs, present, cuts in d_totals [nt, gy, gx, 4].
+ * hold == 1 gives vse_frame_cells_multi's totals, integer for integer.  How the rule does on real footage is not measured here (no
+ * real clips).  Known limit: texture that holds still on a pixel for `hold` frames counts as held; at low thresholds fine, fast
+ * texture does (see EXPERIMENTS.md).
+ * Size in bytes of the caller-owned state (8-byte aligned, zero-filled when fresh, layout the library's: per threshold
+ * vse_frame_hold's pixel state and each cell's open run); 0 below 3 x 3, for nt outside 1..8 or hold outside 1..32.  A state belongs
+ * to one region size, nt and hold. */
+size_t vse_frame_cells_hold_state_bytes(int area_h, int area_w, int nt, int hold);
+/* n >= 0 frames as for vse_frame_hold, the next frames of a clip of which `fed` went to earlier calls; fed == 0 starts a clip: the
+ * state's content is ignored and the totals count from zero.  After a call without `flush` the totals cover the frames 1 ..
+ * max(0, fed + n - hold + 1), whose held masks are complete, with the last run left open; with `flush` (the clip ends with this call)
+ * they cover all fed + n frames and the open runs are closed.  n == 0 with `flush` only drains and closes.  Batches of any sizes give
+ * the totals of one call; the same thresholds, hold and rule go to every call of a clip.  d_cell_counts (nullable) receives, per
+ * threshold, e, a, v per cell for the frames whose rows this call completes, numbered from row 0 as vse_frame_hold numbers its rows
+ * (n + hold - 1 rows of room per threshold; rows the call does not complete are left alone); summed over the cells they are
+ * vse_frame_hold's rows.  One launch on `stream`, no allocation, no device sync; a block owns its cell for all frames of the call
+ * and alone reads and writes the cell's state, totals and counts, for all thresholds.  Returns VSE_E_INVAL, without touching the
+ * device, for everything vse_frame_cells_multi refuses, hold outside 1..32, fed < 0, or n + hold - 1 beyond INT32_MAX. */
+int vse_frame_cells_hold(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride,
+                         int y0, int y1, int x0, int x1, const int* thresholds /* host, [nt] */, int nt, int hold,
+                         int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
+                         void* d_state, int64_t fed, int flush,
+                         int32_t* d_totals /* [nt,gy,gx,4]: covered, runs, present, cuts; accumulated across calls */,
+                         int32_t* d_cell_counts /* nullable: [nt, n + hold - 1, gy, gx, 3] */, void* stream);
+
 /* ---- interval composite ------------------------------------------------------------------------------------------------- */
 /* Replaces: the picture VideoSubFinder hands to OCR for each subtitle it finds (the RGBImages the reference reads back at
  * backend/main.py:378-505), which that closed binary builds from all frames of the subtitle, not from one of them.  Not its

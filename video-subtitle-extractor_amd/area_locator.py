@@ -29,11 +29,20 @@ of the plateau of thresholds whose best grid row scores at least plateau_frac of
   thresholds 24 32 48 64 96 128 160 192   about half an octave apart around the constant;
   plateau_frac 0.9                        a judgement like the defaults above, not a measurement.
 With search_area set to a known subtitle area this is the calibration for a film whose box the user drew.
-Known limits: the calibration runs the CHANGE automaton.  On a moving textured background every frame is a cut at every threshold,
-nothing scores, and it falls back to 128 with a warning (a calibration on held edges is not part of this).  How the rule behaves on
-real footage is unmeasured: there are no real clips here.
+Known limits: the locator and the calibration run the CHANGE automaton unless `automaton="hold"`.  On a moving textured background
+every frame is a cut in every cell at every threshold, nothing scores, no area is found and "auto" falls back to 128 with a warning.
+How the rule behaves on real footage is unmeasured: there are no real clips here.
 
-    python -m vse_amd.area_locator VIDEO [--fps F --size WxH --layout i420|nv12] [--probe START COUNT] [--edge-thresh auto|N] [--json]
+Held edges (automaton="hold"), for the footage of frame_select.HoldFrameSelector: the same cells, automaton, thresholds and rule, but
+each cell counts the HELD mask of its frames (edge pixels that stay edges for `hold` frames; vse_frame_cells_hold), so the edges of a
+texture that moves behind the subtitle drop out before the automaton sees them.  `hold` is HoldFrameSelector's: hold_frames, else
+max(1, min(32, round(hold_seconds * fps))), and a run counts from max(min_frames, hold) frames on.  Known limit: texture that keeps
+an edge on a pixel for `hold` frames is held too.  At low thresholds fine, fast texture does that: on synth.make_moving_clip(amp=(120,
+120), cells=(8, 3)) with hold 8 the threshold 64 locates a wrong band and only the thresholds from 96 up the true one (EXPERIMENTS.md).
+Real footage is unmeasured here as well.
+
+    python -m vse_amd.area_locator VIDEO [--fps F --size WxH --layout i420|nv12] [--probe START COUNT] [--edge-thresh auto|N]
+                                         [--locator-automaton change|hold [--hold-seconds S | --hold-frames N]] [--json]
 
 prints `ymin ymax xmin xmax` (and the chosen threshold as a fifth number when `--edge-thresh auto` was asked); VIDEO is what
 ingest.open_source reads.
@@ -134,13 +143,25 @@ def locate_area(totals, frames_scanned, region, frame_hw, row_frac=0.25, col_fra
 
 
 class EngineCells(DeviceState):
-    """cells_fn of AreaLocator on the GPU (Context.frame_cells; with `thresholds`, Context.frame_cells_multi): keeps the device state
-    of the last region (and threshold count) between calls."""
+    """cells_fn of AreaLocator on the GPU (Context.frame_cells; with `thresholds`, Context.frame_cells_multi; with `hold`,
+    Context.frame_cells_hold at `thresholds` or at params.edge_thresh alone): keeps the device state of the last region (and threshold
+    count, and hold) between calls, and with a hold the number of frames fed since the last reset."""
 
-    def __call__(self, frames, area, params, reset, flush, thresholds=None):
+    def __init__(self, ctx):
+        super().__init__(ctx)
+        self.fed = 0
+
+    def __call__(self, frames, area, params, reset, flush, thresholds=None, hold=None):
         t = self.ctx.torch
         y0, y1, x0, x1 = area
         frames = t.empty((0, y1, x1, 3), dtype=t.uint8, device=self.ctx.tdev) if frames is None else self._device(frames)
+        if hold is not None:
+            ths = (params.edge_thresh,) if thresholds is None else tuple(thresholds)
+            if self._fresh((y1 - y0, x1 - x0, len(ths), int(hold)), self.ctx.frame_cells_hold_state) or reset:
+                self.fed = 0
+            totals = self.ctx.frame_cells_hold(frames, area, ths, hold, params, self._state, self.fed, flush)
+            self.fed += len(frames)
+            return totals[0] if thresholds is None else totals
         if thresholds is None:
             reset = self._fresh((y1 - y0, x1 - x0), self.ctx.frame_cells_state) or reset
             return self.ctx.frame_cells(frames, area, params, self._state, reset, flush)
@@ -159,10 +180,19 @@ class AreaLocator:
     edge_thresh="auto": the same single pass evaluates all `thresholds` (1..8, ascending, each 1..255): cells_fn is then called with
     thresholds=that tuple as well, ignores params.edge_thresh and returns int [nt,gy,gx,4]; run() keeps `totals` of all thresholds,
     `scores` (edge_thresh_scores) and `edge_thresh` (the threshold pick_edge_thresh chose, None when none scores: one warning, and
-    the callers fall back to 128) and locates the area on the chosen threshold's totals.  plateau_frac: pick_edge_thresh's."""
+    the callers fall back to 128) and locates the area on the chosen threshold's totals.  plateau_frac: pick_edge_thresh's.
+    automaton="hold" (default "change"; see the module text): cells_fn is called with hold=`hold` as a further keyword (and params'
+    min_frames at least `hold`) and counts held masks; `hold` is kept on the object: hold_frames, or max(1, min(32, round(hold_seconds
+    * fps))) when that is None.  With "change" cells_fn gets no such keyword."""
 
     def __init__(self, cells_fn=None, edge_thresh=128, min_edges=16, change_ratio=0.5, min_seconds=0.3, max_seconds=20.0, batch=64,
-                 probe=None, search_area=None, thresholds=AUTO_THRESHOLDS, plateau_frac=0.9, **locate_kwargs):
+                 probe=None, search_area=None, thresholds=AUTO_THRESHOLDS, plateau_frac=0.9, automaton="change", hold_seconds=0.3,
+                 hold_frames=None, **locate_kwargs):
+        if automaton not in ("change", "hold"):
+            raise ValueError(f"AreaLocator: automaton must be 'change' or 'hold', not {automaton!r}")
+        if hold_frames is not None and not 1 <= int(hold_frames) <= 32:
+            raise ValueError(f"AreaLocator: hold_frames must be 1..32, not {hold_frames}")
+        self.automaton, self.hold_seconds, self.hold_frames, self.hold = automaton, hold_seconds, hold_frames, None
         self.cells_fn = cells_fn
         self.auto = isinstance(edge_thresh, str) and edge_thresh == "auto"
         self.thresholds = tuple(int(v) for v in thresholds)
@@ -180,8 +210,14 @@ class AreaLocator:
         self.frames_scanned = 0
         self.area = None
 
+    def hold_for(self, fps):
+        """The hold in frames at this frame rate (HoldFrameSelector's rule), None with the change automaton."""
+        if self.automaton != "hold":
+            return None
+        return int(self.hold_frames) if self.hold_frames is not None else max(1, min(32, int(round(self.hold_seconds * fps))))
+
     def params(self, fps):
-        min_frames = max(2, round(self.min_seconds * fps))
+        min_frames = max(2, round(self.min_seconds * fps), self.hold_for(fps) or 0)
         return CellParams(0 if self.auto else self.edge_thresh, self.min_edges, self.ratio.numerator, self.ratio.denominator, min_frames,
                           max(min_frames, round(self.max_seconds * fps)))
 
@@ -207,7 +243,9 @@ class AreaLocator:
         if area is None:
             return None
         params = self.params(fps)
-        cells = self.cells_fn if not self.auto else (lambda *a: self.cells_fn(*a, thresholds=self.thresholds))
+        self.hold = self.hold_for(fps)
+        kw = {**({"thresholds": self.thresholds} if self.auto else {}), **({"hold": self.hold} if self.hold is not None else {})}
+        cells = self.cells_fn if not kw else (lambda *a: self.cells_fn(*a, **kw))
         for items, data in staging.staged_batches(bands, uploader):
             cells(data, area, params, not self.frames_scanned, False)
             self.frames_scanned += len(items)
@@ -219,8 +257,9 @@ class AreaLocator:
             self.scores = edge_thresh_scores(self.totals, self.frames_scanned, static_frac)
             k = pick_edge_thresh(self.totals, self.thresholds, self.frames_scanned, static_frac, self.plateau_frac)
             if k is None:
-                logging.getLogger(__name__).warning("edge_thresh='auto': none of the thresholds %s finds held edges in %d frames; falling "
-                                                    "back to %d", self.thresholds, self.frames_scanned, DEFAULT_EDGE_THRESH)
+                logging.getLogger(__name__).warning("edge_thresh='auto': none of the thresholds %s scores with the %s automaton in %d "
+                                                    "frames; falling back to %d", self.thresholds, self.automaton, self.frames_scanned,
+                                                    DEFAULT_EDGE_THRESH)
                 return None
             self.edge_thresh, chosen = self.thresholds[k], self.totals[k]
         self.area = locate_area(chosen, self.frames_scanned, bands.geometry, bands.frame_hw, **self.locate_kwargs)
@@ -248,8 +287,12 @@ def main(argv=None, cells_fn=None):
                    help="scan COUNT frames from the 1-based frame number START on [the whole clip]")
     p.add_argument("--edge-thresh", default=str(DEFAULT_EDGE_THRESH), metavar="auto|N", help="luma gradient that makes an edge pixel, or "
                    "`auto` to choose it for this clip in the same pass (printed as a fifth number) [128]")
+    p.add_argument("--locator-automaton", default="change", choices=("change", "hold"), help="what the cells count: every edge pixel, or "
+                   "with `hold` only edges that hold still, for a textured background that moves behind the subtitles [change]")
+    p.add_argument("--hold-seconds", type=float, default=0.3, help="with --locator-automaton hold: how long an edge must hold still [0.3]")
+    p.add_argument("--hold-frames", type=int, default=None, help="... the same in frames, 1..32 [from --hold-seconds and the frame rate]")
     p.add_argument("--json", action="store_true", help="print a JSON object instead (area, frames scanned, grid size, edge threshold, "
-                   "and with `auto` the score of every threshold tried)")
+                   "the automaton and its hold in frames, and with `auto` the score of every threshold tried)")
     args = p.parse_args(argv)
     from . import ingest
     try:
@@ -260,7 +303,8 @@ def main(argv=None, cells_fn=None):
                 raise ValueError(f"--size takes WIDTHxHEIGHT, not {args.size!r}")
             size = (int(w), int(h))
         source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout)
-        loc = AreaLocator(cells_fn, probe=args.probe, edge_thresh=parse_edge_thresh(args.edge_thresh))
+        loc = AreaLocator(cells_fn, probe=args.probe, edge_thresh=parse_edge_thresh(args.edge_thresh), automaton=args.locator_automaton,
+                          hold_seconds=args.hold_seconds, hold_frames=args.hold_frames)
         if cells_fn is None:
             from . import staging
             up = staging.default_uploader()
@@ -276,7 +320,8 @@ def main(argv=None, cells_fn=None):
     if args.json:
         print(json.dumps({"ymin": area.ymin, "ymax": area.ymax, "xmin": area.xmin, "xmax": area.xmax,
                           "frames_scanned": loc.frames_scanned, "cells": list(loc.totals.shape[-3:-1]), "edge_thresh": loc.edge_thresh,
-                          "scores": dict(zip(map(str, loc.thresholds), loc.scores)) if loc.auto else None}))
+                          "scores": dict(zip(map(str, loc.thresholds), loc.scores)) if loc.auto else None,
+                          "automaton": loc.automaton, "hold": loc.hold}))
     elif loc.auto:
         print(area.ymin, area.ymax, area.xmin, area.xmax, loc.edge_thresh)
     else:

@@ -20,6 +20,9 @@
 //
 // Held-edge selector (vse_frame_hold): the same tiles and the same mask again, but only edge pixels that hold still for `hold` frames
 // are counted, so that the edges of a moving background drop out (frame_hold_kernel below).
+//
+// Locator and calibration on held edges (vse_frame_cells_hold): the cells and their automaton at several thresholds, counted on the
+// held masks (frame_cells_hold_kernel below).
 #include "common.h"
 
 namespace {
@@ -449,6 +452,136 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_hold_kernel(const uint8_t
     if (mine) *st = (unsigned short)(run | (cover << 6) | ((int)held << 12));
 }
 
+// ---- vse_frame_cells_hold --------------------------------------------------------------------------------------------------------
+// The locator's cells (frame_cells_multi_kernel) on the held masks of frame_hold_kernel, for moving backgrounds: a block is a cell for all
+// frames of the call and for NT thresholds.  Three stages per chunk of steps, all pieces of the kernels above:
+//   tile_masks_multi  a frame's bytes, lumas and gradients once, the edge words of the NT thresholds side by side in LDS;
+//   the walk          frame_hold_kernel's: wave k walks interior row k with lane = column, here for the NT thresholds in one loop (NT
+//                     independent chains per step); the held words replace the edge words in LDS;
+//   the tail          frame_cells_multi_kernel's: wave q counts threshold q's words with lane = step and steps its CellRuns.
+// The held word of a frame comes out hold - 1 steps late, so the automaton is stepped only for the steps that belong to a frame
+// (row >= 0, frame_hold_kernel's `skip`); a flush is hold - 1 steps without an edge and then closes the runs.  Runs with steps == 0 too
+// (fresh and flush only).
+// Between the stages a lane keeps one register per threshold, run | cover << 6: 8 registers at NT = 8 under tile_masks_multi's 83.
+// State: pix[((q * ih + interior row) * wpr + word) * 64 + lane] = frame_hold_kernel's uint16 of threshold q (held: the pixel's bit in the
+// last word that was counted), and open_runs[q * cells + cell] = the length of the cell's open run.  Totals as frame_cells_multi_kernel.
+// cell_counts (nullable): [NT][count_rows][cells][3] = e, a, v of row `row` of this call, each written by the one block that owns it.
+template <int NT>
+__global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_hold_kernel(const uint8_t* __restrict__ src, int n, int steps, long pitch,
+                                                                         long fstride, int x0, int ih, int iw, CellThresholds th, CellRule rule,
+                                                                         int hold, int skip, unsigned short* __restrict__ pix,
+                                                                         int* __restrict__ open_runs, int fresh, int flush,
+                                                                         int* __restrict__ totals, int* __restrict__ cell_counts, int count_rows) {
+    __shared__ unsigned long long msk[NT * FC_CHUNK * FC_ROWS];           // [NT][FC_CHUNK][FC_ROWS]
+    __shared__ unsigned long long prv[NT * FC_ROWS];
+    static_assert(FC_WAVES == FC_ROWS, "wave k walks interior row k of the tile");
+    static_assert(FC_CHUNK == 64, "the steps of a chunk are the lanes of a wave");
+    static_assert(NT >= 1 && NT <= FC_WAVES, "wave q owns threshold q");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int iy0 = blockIdx.y * FC_ROWS, wpr = gridDim.x;
+    const long cell = (long)blockIdx.y * gridDim.x + blockIdx.x, cells = (long)gridDim.y * gridDim.x;
+    const TileLane t = tile_lane(blockIdx.x, iy0, ih, iw, x0);
+    const bool walks = wave < t.rows;          // wave-uniform; the words of the other rows stay zero
+    const bool mine = wave < NT;               // wave q owns threshold q
+    unsigned short* ps = pix + ((long)(iy0 + wave) * wpr + blockIdx.x) * 64 + lane;
+    const long pslice = (long)ih * wpr * 64;
+    int* tot = totals + ((long)wave * cells + cell) * 4;
+    unsigned long long* mq = msk + wave * FC_CHUNK * FC_ROWS;
+    unsigned long long* pq = prv + wave * FC_ROWS;
+    int rc[NT];                                // run | cover << 6
+#pragma unroll
+    for (int q = 0; q < NT; ++q) {
+        const unsigned s = (walks && !fresh) ? ps[q * pslice] : 0u;
+        const unsigned long long b = __ballot((s >> 12) & 1u);
+        if (lane == 0) prv[q * FC_ROWS + wave] = b;
+        rc[q] = (int)(s & 0xfffu);
+    }
+    CellRuns cr = {0, 0, 0, 0, 0};
+    if (mine && !fresh) cr = {open_runs[(long)wave * cells + cell], tot[0], tot[1], tot[2], tot[3]};
+
+    for (int c0 = 0; c0 < steps; c0 += FC_CHUNK) {
+        const int cn = min(FC_CHUNK, steps - c0);
+        const int real = max(0, min(cn, n - c0));          // the steps after frame n are the flush: no edge anywhere
+        tile_masks_multi<NT>(src + (long)iy0 * pitch, c0, real, pitch, fstride, t, th, msk);
+        for (int i = real * FC_ROWS + threadIdx.x; i < cn * FC_ROWS; i += FC_WAVES * 64) {
+#pragma unroll
+            for (int q = 0; q < NT; ++q) msk[q * FC_CHUNK * FC_ROWS + i] = 0ull;
+        }
+        __syncthreads();
+        if (walks) {
+            // lane = step of the chunk for the words going in and out, lane = column for the walk: the walk itself stays out of LDS
+            int lo[NT], hi[NT], run[NT], cover[NT];
+            unsigned long long out[NT];
+#pragma unroll
+            for (int q = 0; q < NT; ++q) {
+                const unsigned long long col = lane < cn ? msk[(q * FC_CHUNK + lane) * FC_ROWS + wave] : 0ull;
+                lo[q] = (int)(unsigned)col;
+                hi[q] = (int)(unsigned)(col >> 32);
+                out[q] = 0ull;
+                run[q] = rc[q] & 63;
+                cover[q] = rc[q] >> 6;
+            }
+            for (int tl = 0; tl < cn; ++tl) {
+#pragma unroll
+                for (int q = 0; q < NT; ++q) {
+                    const unsigned half = (unsigned)(lane < 32 ? __builtin_amdgcn_readlane(lo[q], tl) : __builtin_amdgcn_readlane(hi[q], tl));
+                    const bool edge = (half >> (lane & 31)) & 1u;
+                    run[q] = edge ? min(run[q] + 1, hold) : 0;
+                    cover[q] = run[q] == hold ? hold : max(cover[q] - 1, 0);
+                    const unsigned long long b = __ballot(cover[q] > 0);
+                    if (lane == tl) out[q] = b;            // held word of frame (this step) - hold + 1
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < NT; ++q) {
+                if (lane < cn) msk[(q * FC_CHUNK + lane) * FC_ROWS + wave] = out[q];
+                rc[q] = run[q] | (cover[q] << 6);
+            }
+        }
+        __syncthreads();
+        if (mine) {                                // lane = step of the chunk
+            const int row = c0 + lane - skip;      // the row of this call that the step completes; < 0: a step before frame 1
+            const bool live = lane < cn && row >= 0;
+            int e = 0, a = 0, v = 0, ep = 0;
+            if (live) {
+#pragma unroll
+                for (int k = 0; k < FC_ROWS; ++k) {
+                    const unsigned long long cur = mq[lane * FC_ROWS + k], pre = lane ? mq[(lane - 1) * FC_ROWS + k] : pq[k];
+                    e += __popcll(cur);
+                    a += __popcll(cur & ~pre);
+                    v += __popcll(pre & ~cur);
+                    ep += __popcll(pre);           // held edges of the frame before
+                }
+                if (cell_counts) {
+                    int* o = cell_counts + (((long)wave * count_rows + row) * cells + cell) * 3;
+                    o[0] = e;
+                    o[1] = a;
+                    o[2] = v;
+                }
+            }
+            const long long uni = ep + a;          // |H' or H|
+            const unsigned long long present = __ballot(live && e >= rule.min_edges);
+            const unsigned long long ratio = __ballot(live && uni > 0 && (long long)(a + v) * rule.ratio_den >= (long long)rule.ratio_num * uni);
+            for (int f = max(0, skip - c0); f < cn; ++f) cr.step((present >> f) & 1, (ratio >> f) & 1, rule);
+        }
+        __syncthreads();
+        if (mine && lane < FC_ROWS) pq[lane] = mq[(cn - 1) * FC_ROWS + lane];
+        __syncthreads();
+    }
+    if (walks) {
+#pragma unroll
+        for (int q = 0; q < NT; ++q) ps[q * pslice] = (unsigned short)(rc[q] | ((rc[q] >> 6) ? 1 << 12 : 0));
+    }
+    if (mine && lane == 0) {
+        if (flush) cr.close(rule);
+        open_runs[(long)wave * cells + cell] = cr.run;
+        tot[0] = cr.covered;
+        tot[1] = cr.runs;
+        tot[2] = cr.present;
+        tot[3] = cr.cuts;
+    }
+}
+
 }  // namespace
 
 // Called by vse_frame_change (vse_runtime.hip) after it has checked the geometry.
@@ -524,5 +657,47 @@ int vse_frame_hold_launch(const void* d_bgr, int n, int steps, int64_t pitch, in
     hipLaunchKernelGGL(frame_hold_kernel, dim3(wpr, (ih + FC_ROWS - 1) / FC_ROWS), dim3(FC_WAVES * 64), 0, st, src, n, steps, (long)pitch,
                        (long)frame_stride, x0, ih, iw, wpr, edge_thresh, hold, skip, reinterpret_cast<unsigned short*>(d_state), fresh,
                        reinterpret_cast<int*>(d_counts));
+    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+}
+
+// State of vse_frame_cells_hold for a region with an interior of ih x iw pixels: nt slices of frame_hold_kernel's pixel state, then the
+// open runs, int32 [nt][cells], padded to 8 bytes.
+static size_t cells_hold_pixel_bytes(int ih, int iw, int nt) { return (size_t)nt * ih * ((iw + 63) / 64) * HOLD_WORD_BYTES; }
+
+size_t vse_frame_cells_hold_bytes(int ih, int iw, int nt) {
+    const size_t cells = (size_t)((ih + FC_ROWS - 1) / FC_ROWS) * ((iw + 63) / 64);
+    return cells_hold_pixel_bytes(ih, iw, nt) + ((nt * cells * sizeof(int32_t) + 7) & ~(size_t)7);
+}
+
+// Called by vse_frame_cells_hold (vse_runtime.hip) after it has checked the arguments (1 <= nt <= vse_frame_cells_multi_max(), 1 <= hold <=
+// 32); steps = n (+ hold - 1 with a flush) >= 0, skip = the steps whose frame lies before frame 1, count_rows = the rows of d_cell_counts
+// per threshold.
+int vse_frame_cells_hold_launch(const void* d_bgr, int n, int steps, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                                const int* thresholds, int nt, int hold, int skip, int min_edges, int ratio_num, int ratio_den, int min_frames,
+                                int max_frames, void* d_state, int fresh, int flush, int32_t* d_totals, int32_t* d_cell_counts, int count_rows,
+                                void* stream) {
+    const int ih = y1 - y0 - 2, iw = x1 - x0 - 2;
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
+    const CellRule rule = {min_edges, ratio_num, ratio_den, min_frames, max_frames};
+    CellThresholds th = {};
+    for (int q = 0; q < nt; ++q) th.t[q] = thresholds[q];
+    const dim3 grid((iw + 63) / 64, (ih + FC_ROWS - 1) / FC_ROWS), block(FC_WAVES * 64);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    unsigned short* pix = reinterpret_cast<unsigned short*>(d_state);
+    int* open_runs = reinterpret_cast<int*>(reinterpret_cast<char*>(d_state) + cells_hold_pixel_bytes(ih, iw, nt));
+    int* totals = reinterpret_cast<int*>(d_totals);
+    int* cell_counts = reinterpret_cast<int*>(d_cell_counts);
+#define VSE_CELLS_HOLD(NT)                                                                                                               \
+    case NT:                                                                                                                             \
+        hipLaunchKernelGGL(frame_cells_hold_kernel<NT>, grid, block, 0, st, src, n, steps, (long)pitch, (long)frame_stride, x0, ih, iw, th, \
+                           rule, hold, skip, pix, open_runs, fresh, flush, totals, cell_counts, count_rows);                             \
+        break;
+    switch (nt) {
+        VSE_CELLS_HOLD(1) VSE_CELLS_HOLD(2) VSE_CELLS_HOLD(3) VSE_CELLS_HOLD(4)
+        VSE_CELLS_HOLD(5) VSE_CELLS_HOLD(6) VSE_CELLS_HOLD(7) VSE_CELLS_HOLD(8)
+        default: return VSE_E_INVAL;
+    }
+#undef VSE_CELLS_HOLD
+    static_assert(FC_WAVES == 8, "one instantiation per number of thresholds");
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }

@@ -63,6 +63,11 @@ int vse_frame_cells_multi_launch(const void* d_bgr, int n, int64_t pitch, int64_
 size_t vse_frame_hold_word_bytes();                                                                                    // frame_change.hip
 int vse_frame_hold_launch(const void* d_bgr, int n, int steps, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
                           int edge_thresh, int hold, int skip, void* d_state, int fresh, int32_t* d_counts, void* stream);   // frame_change.hip
+size_t vse_frame_cells_hold_bytes(int ih, int iw, int nt);                                                               // frame_change.hip
+int vse_frame_cells_hold_launch(const void* d_bgr, int n, int steps, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                                const int* thresholds, int nt, int hold, int skip, int min_edges, int ratio_num, int ratio_den, int min_frames,
+                                int max_frames, void* d_state, int fresh, int flush, int32_t* d_totals, int32_t* d_cell_counts, int count_rows,
+                                void* stream);                                                                         // frame_change.hip
 int vse_scene_change_plane_pitch(int aw);                                                                              // scene_cut.hip
 int vse_scene_change_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int scale, int ah, int aw, int search, int bias,
                             void* d_state, int reset, void* d_ws, int32_t* d_counts, void* stream);
@@ -547,6 +552,50 @@ int vse_frame_hold(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, i
     const int rc = vse_frame_hold_launch(d_bgr, n, (int)steps, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, hold, skip, d_state,
                                          fed == 0, d_counts, stream);
     if (rc != VSE_OK) set_err("vse_frame_hold: launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+// ---- locator and calibration on held edges (frame_change.hip) -------------------------------------------------------------------
+size_t vse_frame_cells_hold_state_bytes(int area_h, int area_w, int nt, int hold) {
+    if (area_h < 3 || area_w < 3 || nt < 1 || nt > vse_frame_cells_multi_max() || hold < 1 || hold > 32) return 0;
+    return vse_frame_cells_hold_bytes(area_h - 2, area_w - 2, nt);
+}
+
+int vse_frame_cells_hold(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0, int y1,
+                         int x0, int x1, const int* thresholds, int nt, int hold, int min_edges, int ratio_num, int ratio_den,
+                         int min_frames, int max_frames, void* d_state, int64_t fed, int flush, int32_t* d_totals,
+                         int32_t* d_cell_counts, void* stream) {
+    if (!check_frames("vse_frame_cells_hold", c && d_totals && fed >= 0, d_bgr, n, 0, src_h, src_w, pitch, frame_stride, d_state) ||
+        !check_area("vse_frame_cells_hold", "region", y0, y1, x0, x1, src_h, src_w) ||
+        !check_rule("vse_frame_cells_hold", ratio_num, ratio_den, min_frames, max_frames))
+        return VSE_E_INVAL;
+    if (!thresholds || nt < 1 || nt > vse_frame_cells_multi_max()) {
+        set_err("vse_frame_cells_hold: %d thresholds (1..%d, not NULL)", nt, vse_frame_cells_multi_max());
+        return VSE_E_INVAL;
+    }
+    for (int q = 0; q < nt; ++q) {
+        if (thresholds[q] < 1 || thresholds[q] > 255 || (q && thresholds[q] <= thresholds[q - 1])) {
+            set_err("vse_frame_cells_hold: threshold %d of %d is %d (each 1..255, ascending and distinct)", q, nt, thresholds[q]);
+            return VSE_E_INVAL;
+        }
+    }
+    if (hold < 1 || hold > 32) {
+        set_err("vse_frame_cells_hold: hold %d outside 1..32", hold);
+        return VSE_E_INVAL;
+    }
+    // as vse_frame_hold: the held mask of a frame is known hold - 1 frames later, a flush feeds that many frames without an edge, and
+    // the first hold - 1 steps of a clip belong to no frame
+    const int64_t steps = (int64_t)n + (flush ? hold - 1 : 0);
+    const int skip = fed >= hold - 1 ? 0 : (int)(hold - 1 - fed);
+    if ((int64_t)n + hold - 1 > INT32_MAX) {
+        set_err("vse_frame_cells_hold: %lld steps do not fit an int", (long long)n + hold - 1);
+        return VSE_E_INVAL;
+    }
+    if (n == 0 && !flush) return VSE_OK;
+    const int rc = vse_frame_cells_hold_launch(d_bgr, n, (int)steps, pitch, frame_stride, y0, y1, x0, x1, thresholds, nt, hold, skip, min_edges,
+                                               ratio_num, ratio_den, min_frames, max_frames, d_state, fed == 0, flush != 0, d_totals,
+                                               d_cell_counts, n + hold - 1, stream);
+    if (rc != VSE_OK) set_err("vse_frame_cells_hold: launch failed: %s", hipGetErrorString(hipGetLastError()));
     return rc;
 }
 

@@ -261,8 +261,11 @@ class SubtitleExtractor:
     chooses the threshold for this clip before the selector is built (area_locator.AreaLocator(edge_thresh="auto"), `area_params` its
     keyword arguments; the selectors keep taking integers) and keeps it as `edge_thresh`: with sub_area="auto" the one locator pass
     yields the area and the threshold, with a given area one calibration pass runs over the area's rows.  When no threshold scores
-    (no subtitles, or a textured background that moves behind them: the calibration uses the change automaton) it warns and uses 128.
-    How the choice behaves on real footage is not measured here.
+    (no subtitles, or a textured background that moves behind them: the calibration uses the change automaton unless
+    `automaton="hold"`) it warns and uses 128.  How the choice behaves on real footage is not measured here.
+    area_params={"automaton": "hold"}: the locator and the calibration count held edges (area_locator's module text), which is what a
+    textured background that moves behind the subtitles needs; with frame_selector="hold" they take the selector's hold_seconds /
+    hold_frames from change_params unless area_params sets its own.  Opt-in: without it nothing changes.
     one_pass (None: exactly when the source has no `read`, e.g. ingest.Y4mStream over a pipe; True forces it on a seekable source and
     halves its decode work; False on a sequential source is a ValueError): the clip is read once, in decode order.  frame_selector="fps":
     frame `no` is a task iff (no - 1) % max(1, int(fps // extract_frequency)) == 0 (fps_tasks' rule without the frame count); tasks go
@@ -353,6 +356,10 @@ class SubtitleExtractor:
     def _locator(self, **kw):
         from . import area_locator
         params = {"batch": self.batch, **(self.area_params or {}), **kw}
+        own = self.area_params or {}
+        if params.get("automaton") == "hold" and self.frame_selector == "hold" and "hold_seconds" not in own and "hold_frames" not in own:
+            # the locator and the calibration hold as long as the selector does, unless area_params says otherwise
+            params.update({k: v for k, v in (self.change_params or {}).items() if k in ("hold_seconds", "hold_frames")})
         if self.auto_thresh and self.frame_selector in ("change", "hold"):
             params["edge_thresh"] = "auto"
         return area_locator.AreaLocator(**params)
@@ -589,6 +596,8 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None):
     p.add_argument("--selector", default="fps", choices=("fps", "change", "hold"), help="which frames go to OCR [fps]")
     p.add_argument("--edge-thresh", default="128", metavar="auto|N", help="change / hold selector: the luma gradient that makes an edge "
                    "pixel, or `auto` to choose it for this clip first (not in one pass) [128]")
+    p.add_argument("--locator-automaton", default="change", choices=("change", "hold"), help="what `--area auto` and `--edge-thresh auto` "
+                   "count: every edge pixel, or with `hold` only edges that hold still (a textured background that moves) [change]")
     p.add_argument("--mode", default="fast", choices=("fast", "auto", "accurate"))
     p.add_argument("--language", default="ch")
     p.add_argument("--frequency", type=int, default=3, help="frames per second the fps sampler looks at [3]")
@@ -622,7 +631,8 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None):
                                batch=args.batch, uploader=uploader, frame_selector=args.selector, change_counter=counter,
                                retain_bytes=int(args.retain_gib * (1 << 30)),
                                change_params=None if edge_thresh == 128 else {"edge_thresh": edge_thresh},
-                               area_params=None if cells_fn is None else {"cells_fn": cells_fn})
+                               area_params={**({} if cells_fn is None else {"cells_fn": cells_fn}),
+                                            **({} if args.locator_automaton == "change" else {"automaton": args.locator_automaton})} or None)
         text = ex.run()
         if args.output is None:
             sys.stdout.write(text)
