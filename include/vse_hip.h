@@ -406,6 +406,23 @@ int vse_interval_accumulate(vse_ctx* ctx, const void* d_bgr, int n, int src_h, i
  * Returns VSE_E_INVAL, leaving the output untouched, for an empty area, any other mode or count, or out_pitch < 3 area_w. */
 int vse_interval_composite(vse_ctx* ctx, const void* d_state, int area_h, int area_w, int frames, int mode /* 0 min, 1 max, 2 mean */,
                            void* d_out, int64_t out_pitch, void* stream);
+/* The per-byte order statistic over time, the robust form of mn / mx above: for every byte b of the area [y0, y1) x [x0, x1) x 3 of
+ * 1 <= n <= VSE_INTERVAL_RANK_MAX uint8 BGR frames [n, src_h, src_w, 3] (row pitch `pitch` bytes, frame stride `frame_stride` bytes),
+ * the n values frame[f][b] sorted ascending, element `rank` (0-based: 0 is the minimum, n - 1 the maximum, (n - 1) / 2 the lower
+ * median) -> d_out uint8 [area_h, area_w, 3] with row pitch `out_pitch` bytes (exactly the 3 area_w bytes of each row are written).
+ * The temporal median of a subtitle that stands still over a picture that moves is the subtitle's own value at text pixels whatever
+ * its colour, and a minority of outlier frames (a flash, a cut one frame late) cannot move it
+ * (vse_amd.frame_select.IntervalQuantile, which hands it a few evenly spaced samples of an interval: exact over those samples, an
+ * estimate of the interval's quantile when it has more frames).  Whether that helps recognition on real footage is not measured here.
+ * Stateless; the frames are read only, and only the area's pixels are used, as vse_interval_accumulate uses them (where a row of the
+ * area does not start or end on a 4-byte boundary, the aligned 4 bytes around that end are fetched whole).  No alignment is
+ * required; a 4-byte aligned area start (base + 3 x0), pitch and frame stride take one aligned load per frame.  One launch on
+ * `stream`, no allocation, no device sync, no atomics.
+ * Returns VSE_E_INVAL, without touching the device, for everything vse_interval_accumulate refuses about frames, pitch, stride and
+ * area, n outside 1..VSE_INTERVAL_RANK_MAX, rank outside 0..n - 1, a NULL d_out, or out_pitch < 3 area_w. */
+#define VSE_INTERVAL_RANK_MAX 63
+int vse_interval_rank(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride,
+                      int y0, int y1, int x0, int x1, int rank, void* d_out, int64_t out_pitch, void* stream);
 
 /* ---- timeline sync: audio template search ----------------------------------------------------------------------------- */
 /* Replaces: Sushi's WavStream.find_substream (backend/sushi/wav.py:179-189), cv2.matchTemplate(TM_SQDIFF_NORMED) of one group's

@@ -19,6 +19,25 @@
 //            row's ends are fetched with it and dropped; they share an aligned dword with a byte of the area.
 // The bytes are unpacked into ints before min / max / add and packed again by shifts: no packed-byte arithmetic in the source (see
 // clip8 in yuv.hip for what hipcc made of one on this target).
+//
+// Interval rank (vse_interval_rank): the per-byte ORDER STATISTIC over the n <= 63 frames of one call: out[b] = element `rank` of the
+// ascending sort of frame[f][b].  Stateless, one launch, no atomics.
+// Layout: a lane owns ONE dword of an area row (dword c = bytes 4 c .. 4 c + 3 of the row's 3 area_w bytes) for all n frames, so the
+// n samples of its four bytes are n registers; a 16-byte run per lane, as above, would need 4 n.  The sample loops are unrolled over
+// a compile-time bucket KB of 8, 16, 32 or 64 slots (a runtime-indexed array would go to scratch); the slots from n on are filled
+// with 0xFF bytes without a load, which leaves the rank-th smallest as it is for every rank < n.
+// Two loads of a dword:
+//   wide     one aligned dword load; needs base + 3 x0, pitch and frame stride multiples of 4 (the short run that ends a row is
+//            then the aligned dword that holds its bytes).
+//   general  any byte alignment, pitch and stride: the one or two aligned dwords that hold the run's bytes, shifted into place.
+//            No dword without a byte of the area's row is touched.
+// Selection: per byte lane a bitwise binary search of the answer, most significant bit first: the answer is the largest t with
+// |{f : v[f] < t}| <= rank, that count never falls as t grows, so each of 8 rounds tries t | bit and keeps it when the count of
+// samples below it is at most rank.  No per-sample state beside the value.  Cost per OUTPUT byte: 8 rounds of KB compares (hipcc
+// selects the byte inside the compare, so nothing is extracted beforehand), KB / 2 selects and KB / 2 adds with carry (two compares
+// feed one add), about 16 KB + 40 vector instructions with everything around them; counted in the gfx950 ISA, wide loads: 171, 306,
+// 576 and 1116 per output byte at KB = 8, 16, 32, 64, and one s_nop per pair of compares.  The accumulate kernel spends 3 per byte
+// and frame (48 for 16 frames): this kernel is bound by the vector ALU, not by HBM (EXPERIMENTS.md, section V).
 #include <cstdio>
 
 #include "common.h"
@@ -179,12 +198,113 @@ __global__ __launch_bounds__(IV_THREADS) void interval_composite_kernel(const ui
     }
 }
 
+// ---- interval rank ----------------------------------------------------------------------------------------------------------
+// The samples of the run of nb bytes at p in frames 0 .. n - 1, slots from n on 0xFF bytes.  WIDE: p and fstride are 4-byte aligned and
+// a slot is one aligned dword.  General: the aligned dwords around the run (the second one only where it holds a byte of the run,
+// else the first again), the loads of up to 32 frames issued before the first is shifted into place.  Bytes of a slot beyond nb come
+// out as whatever those dwords held: they are never stored.
+// n sits in a vector register: the compiler then masks the lanes of each load (all or none) instead of branching around it; with a
+// chain of uniform branches it waited for each load before it issued the next.  No load is issued beyond the n frames.
+template <int KB, bool WIDE>
+__device__ __forceinline__ void load_samples(unsigned (&s)[KB], const uint8_t* p, int n, long fstride, int nb) {
+    int nv = n;
+    asm volatile("" : "+v"(nv));
+    if (WIDE) {
+#pragma unroll
+        for (int f = 0; f < KB; ++f) {
+            s[f] = 0xFFFFFFFFu;
+            if (f < nv) s[f] = *reinterpret_cast<const unsigned*>(p);
+            p += fstride;
+        }
+    } else {
+        // 32 frames at a time: their 64 raw dwords beside the slots already shifted into place stay near 100 registers at KB = 64
+        constexpr int CH = KB < 32 ? KB : 32;
+        const unsigned p0 = (unsigned)reinterpret_cast<uintptr_t>(p), fs = (unsigned)fstride;       // the low bits are all sh needs
+#pragma unroll
+        for (int c0 = 0; c0 < KB; c0 += CH) {
+            unsigned hi[CH];
+#pragma unroll
+            for (int u = 0; u < CH; ++u) {
+                const int f = c0 + u;
+                const unsigned sh = (p0 + (unsigned)f * fs) & 3u;
+                s[f] = hi[u] = 0xFFFFFFFFu;
+                if (f < nv) {
+                    const unsigned* q = reinterpret_cast<const unsigned*>(p - sh);
+                    s[f] = q[0];
+                    hi[u] = q[sh + (unsigned)nb > 4u ? 1 : 0];
+                }
+                p += fstride;
+            }
+#pragma unroll
+            for (int u = 0; u < CH; ++u) {
+                const int f = c0 + u;
+                const unsigned sh = (p0 + (unsigned)f * fs) & 3u;
+                s[f] = (unsigned)((((unsigned long long)hi[u] << 32) | s[f]) >> (8 * sh));
+            }
+        }
+    }
+}
+
+// Element `rank` of the ascending sort of byte SHIFT / 8 of the KB samples.
+template <int KB, int SHIFT>
+__device__ __forceinline__ unsigned select_byte(const unsigned (&s)[KB], unsigned rank) {
+    unsigned v[KB];
+#pragma unroll
+    for (int f = 0; f < KB; ++f) v[f] = (s[f] >> SHIFT) & 255u;
+    unsigned t = 0;
+#pragma unroll
+    for (unsigned bit = 128; bit; bit >>= 1) {
+        const unsigned cand = t | bit;
+        unsigned below = 0;
+#pragma unroll
+        for (int f = 0; f < KB; ++f) below += v[f] < cand ? 1u : 0u;
+        t = below <= rank ? cand : t;
+    }
+    return t;
+}
+
+// src points at byte 3 x0 of row y0 of frame 0; rb = 3 area_w bytes per row in dpr = ceil(rb / 4) dwords; items = area_h * dpr;
+// 1 <= n <= KB, n <= 63, rank < n.
+template <int KB, bool WIDE>
+__global__ __launch_bounds__(IV_THREADS) void interval_rank_kernel(const uint8_t* __restrict__ src, int n, long pitch, long fstride, int rb,
+                                                                   unsigned dpr, unsigned items, unsigned rank, uint8_t* __restrict__ out,
+                                                                   long out_pitch) {
+    const unsigned i = blockIdx.x * IV_THREADS + threadIdx.x;
+    if (i >= items) return;
+    const unsigned r = i / dpr, c = i - r * dpr;
+    const int nb = min(4, rb - 4 * (int)c);
+    const uint8_t* p = src + (long)r * pitch + 4 * (long)c;
+    unsigned s[KB];
+    load_samples<KB, WIDE>(s, p, n, fstride, nb);
+    const unsigned b0 = select_byte<KB, 0>(s, rank), b1 = select_byte<KB, 8>(s, rank), b2 = select_byte<KB, 16>(s, rank),
+                   b3 = select_byte<KB, 24>(s, rank);
+    const unsigned w = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+    uint8_t* o = out + (long)r * out_pitch + 4 * (long)c;
+    if (nb == 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
+        *reinterpret_cast<unsigned*>(o) = w;
+    } else {
+        for (int k = 0; k < nb; ++k) o[k] = (uint8_t)(w >> (8 * k));
+    }
+}
+
+template <int KB>
+void launch_rank(bool wide, dim3 grid, hipStream_t st, const uint8_t* src, int n, long pitch, long fstride, int rb, unsigned dpr, unsigned items,
+                 unsigned rank, uint8_t* out, long out_pitch) {
+    if (wide)
+        hipLaunchKernelGGL((interval_rank_kernel<KB, true>), grid, dim3(IV_THREADS), 0, st, src, n, pitch, fstride, rb, dpr, items, rank, out,
+                           out_pitch);
+    else
+        hipLaunchKernelGGL((interval_rank_kernel<KB, false>), grid, dim3(IV_THREADS), 0, st, src, n, pitch, fstride, rb, dpr, items, rank, out,
+                           out_pitch);
+}
+
 // rows padded to whole runs; 0 where the area is empty or its runs do not fit the 32-bit work-item index
 size_t row_bytes16(int area_w) { return (((size_t)area_w * 3 + 15) / 16) * 16; }
 bool area_fits(int area_h, int area_w) {
     return area_h >= 1 && area_w >= 1 && (size_t)area_h * (row_bytes16(area_w) / 16) <= 0x7fffffffu;
 }
 bool multiple16(int64_t v) { return (v & 15) == 0; }
+bool multiple4(int64_t v) { return (v & 3) == 0; }
 
 }  // namespace
 
@@ -248,6 +368,51 @@ int vse_interval_composite(vse_ctx* c, const void* d_state, int area_h, int area
                        cpr, items, (unsigned)frames, mode, reinterpret_cast<uint8_t*>(d_out), (long)out_pitch);
     if (hipGetLastError() != hipSuccess) {
         vse_set_error("vse_interval_composite: launch failed");
+        return VSE_E_HIP;
+    }
+    return VSE_OK;
+}
+
+int vse_interval_rank(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0,
+                      int x1, int rank, void* d_out, int64_t out_pitch, void* stream) {
+    char msg[320];
+    if (!c || !d_bgr || !d_out || n < 1 || n > VSE_INTERVAL_RANK_MAX || src_h < 1 || src_w < 1 || pitch < (int64_t)src_w * 3 ||
+        (n > 1 && frame_stride < (int64_t)(src_h - 1) * pitch + (int64_t)src_w * 3)) {
+        snprintf(msg, sizeof msg, "vse_interval_rank: bad arguments (n %d of 1..%d, frame %d x %d, pitch %lld of at least 3 w, frame stride %lld, "
+                 "an output)", n, VSE_INTERVAL_RANK_MAX, src_h, src_w, (long long)pitch, (long long)frame_stride);
+        vse_set_error(msg);
+        return VSE_E_INVAL;
+    }
+    if (y0 < 0 || x0 < 0 || y1 > src_h || x1 > src_w || y1 <= y0 || x1 <= x0 || !area_fits(y1 - y0, x1 - x0) ||
+        (size_t)(y1 - y0) * (((size_t)(x1 - x0) * 3 + 3) / 4) > 0x7fffffffu) {
+        snprintf(msg, sizeof msg, "vse_interval_rank: area [%d, %d) x [%d, %d) is empty or outside the %d x %d frame", y0, y1, x0, x1, src_h,
+                 src_w);
+        vse_set_error(msg);
+        return VSE_E_INVAL;
+    }
+    if (rank < 0 || rank >= n || out_pitch < (int64_t)(x1 - x0) * 3) {
+        snprintf(msg, sizeof msg, "vse_interval_rank: rank %d of 0..%d, output pitch %lld of at least 3 area_w = %d", rank, n - 1,
+                 (long long)out_pitch, (x1 - x0) * 3);
+        vse_set_error(msg);
+        return VSE_E_INVAL;
+    }
+    const int ah = y1 - y0, rb = (x1 - x0) * 3;
+    const unsigned dpr = (unsigned)((rb + 3) / 4), items = (unsigned)ah * dpr;
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (int64_t)y0 * pitch + (int64_t)x0 * 3;
+    uint8_t* out = reinterpret_cast<uint8_t*>(d_out);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((items + IV_THREADS - 1) / IV_THREADS);
+    const bool wide = (reinterpret_cast<uintptr_t>(src) & 3) == 0 && multiple4(pitch) && (n == 1 || multiple4(frame_stride));
+    if (n <= 8)
+        launch_rank<8>(wide, grid, st, src, n, (long)pitch, (long)frame_stride, rb, dpr, items, (unsigned)rank, out, (long)out_pitch);
+    else if (n <= 16)
+        launch_rank<16>(wide, grid, st, src, n, (long)pitch, (long)frame_stride, rb, dpr, items, (unsigned)rank, out, (long)out_pitch);
+    else if (n <= 32)
+        launch_rank<32>(wide, grid, st, src, n, (long)pitch, (long)frame_stride, rb, dpr, items, (unsigned)rank, out, (long)out_pitch);
+    else
+        launch_rank<64>(wide, grid, st, src, n, (long)pitch, (long)frame_stride, rb, dpr, items, (unsigned)rank, out, (long)out_pitch);
+    if (hipGetLastError() != hipSuccess) {
+        vse_set_error("vse_interval_rank: launch failed");
         return VSE_E_HIP;
     }
     return VSE_OK;

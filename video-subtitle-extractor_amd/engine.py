@@ -23,7 +23,8 @@ EXPORTS = [
     "vse_rec_graph_create", "vse_graph_launch", "vse_graph_destroy", "vse_frame_change_state_bytes", "vse_frame_change",
     "vse_audio_match_workspace_bytes", "vse_audio_match", "vse_scene_change_state_bytes", "vse_scene_change_workspace_bytes",
     "vse_scene_change", "vse_frame_cells_dims", "vse_frame_cells_state_bytes", "vse_frame_cells",
-    "vse_interval_state_bytes", "vse_interval_accumulate", "vse_interval_composite", "vse_frame_hold_state_bytes", "vse_frame_hold",
+    "vse_interval_state_bytes", "vse_interval_accumulate", "vse_interval_composite", "vse_interval_rank", "vse_frame_hold_state_bytes",
+    "vse_frame_hold",
     "vse_audio_stream_length", "vse_audio_stream_workspace_bytes", "vse_audio_stream_feed", "vse_audio_stream_finish", "vse_ctc_fuse",
     "vse_yuv_to_bgr_matrix", "vse_frame_cells_multi_state_bytes", "vse_frame_cells_multi",
     "vse_frame_cells_hold_state_bytes", "vse_frame_cells_hold",
@@ -187,6 +188,8 @@ def load_library(path=None):
     lib.vse_interval_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                             C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.vse_interval_composite.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.vse_interval_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
     lib.vse_audio_match_workspace_bytes.restype = C.c_size_t
     lib.vse_audio_match_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
     lib.vse_audio_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
@@ -667,6 +670,23 @@ class Context:
                                                self.stream()), "vse_interval_composite")
         return out
 
+    def interval_rank(self, frames_u8, area, rank, out=None):
+        """frames_u8: cuda uint8 [n,H,W,3], 1 <= n <= INTERVAL_RANK_MAX (any row pitch / frame stride, pixels packed), area = (y0, y1,
+        x0, x1) in its pixels, 0 <= rank < n -> cuda uint8 [y1-y0, x1-x0, 3]: per byte, element `rank` of the n frames' values sorted
+        ascending (include/vse_hip.h vse_interval_rank; rank 0 the minimum, n - 1 the maximum).  out: write into this tensor instead
+        (it may be a strided view with packed pixels; its row pitch is taken from it)."""
+        t = self.torch
+        frames = self._frames_args(frames_u8)
+        y0, y1, x0, x1 = (int(v) for v in area)
+        area_h, area_w = y1 - y0, x1 - x0
+        if out is None:
+            out = t.empty((max(area_h, 0), max(area_w, 0), 3), dtype=t.uint8, device=self.tdev)
+        assert out.dtype == t.uint8 and tuple(out.shape) == (area_h, area_w, 3) and out.stride(2) == 1 and out.stride(1) == 3
+        _check(self.lib.vse_interval_rank(self.handle, *frames, y0, y1, x0, x1, int(rank), C.c_void_p(out.data_ptr()),
+                                          out.stride(0) if area_h > 1 else max(out.stride(0), 3 * area_w), self.stream()),
+               "vse_interval_rank")
+        return out
+
     # ---- timeline sync: audio template search ---------------------------------------------------------------------
     def audio_match_workspace_bytes(self, queries):
         """Workspace bytes of one audio_match call with these (src_off, m, dst_off, win_len) queries (0 if one is invalid)."""
@@ -797,6 +817,7 @@ class Context:
 YUV_LAYOUTS = {"i420": 0, "nv12": 1}
 YUV_MATRICES = {"bt601": 0, "bt709": 1}
 INTERVAL_MODES = {"min": 0, "max": 1, "mean": 2}
+INTERVAL_RANK_MAX = 63          # VSE_INTERVAL_RANK_MAX (include/vse_hip.h): the frames of one vse_interval_rank call
 
 
 def _audio_queries(queries):

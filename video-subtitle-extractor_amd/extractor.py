@@ -227,6 +227,11 @@ def _boxes_list(arr):
     return [[(int(x), int(y)) for x, y in q] for q in np.asarray(arr).reshape(-1, 4, 2)]
 
 
+# what the recogniser may be shown for an interval: its middle frame, a composite of all its frames (frame_select.COMPOSITE_MODES),
+# or the per-pixel quantile of a few of them (frame_select.IntervalQuantile)
+INTERVAL_IMAGES = ("middle",) + frame_select.COMPOSITE_MODES + ("quantile",)
+
+
 class SubtitleExtractor:
     """run() = backend/main.py:103-191 without the GUI/process plumbing.
 
@@ -246,6 +251,13 @@ class SubtitleExtractor:
     text) / maximum (dark text) / mean of ALL frames of the interval, one more pass over the area's rows on the device
     (frame_select.IntervalCompositor, `composite_params` its keyword arguments); the pictures are kept as `interval_patches`.
     Intervals and SRT times are untouched.  What it gains on real footage is not measured here.
+    interval_image="quantile" (change / hold selector): the picture is instead the per-pixel quantile over time (default 0.5, the median)
+    of up to `samples` (default 15) evenly spaced frames of the interval (frame_select.IntervalQuantile, `composite_params` its keyword
+    arguments: quantile, samples, trim_seconds, rank_fn).  The median needs no knowledge of the text's polarity, and a minority of
+    outlier frames (a flash, a black frame, a cut found one frame late) cannot move it, where a single one ruins `min` / `max`; only
+    the samples are uploaded.  Exact over the trimmed interval when it has at most `samples` frames, an estimate from `samples` frames
+    otherwise.  Not available with frame_selector="fps", interval_text="fused" or in one pass.  What it gains on real footage is not
+    measured here either.
     interval_text="fused" (change / hold selector with interval_image="middle" only; default "single", the above): the other answer to
     that single frame, in probability space: up to `samples` frames of each interval go through the recogniser, the boxes detected
     once on the sample nearest to the middle frame, and the recogniser's per-step class probabilities are averaged on the device before
@@ -290,8 +302,8 @@ class SubtitleExtractor:
                  interval_text="single", fuse_params=None, one_pass=None, retain_bytes=4 << 30):
         if frame_selector not in ("fps", "change", "hold"):
             raise ValueError(f"frame_selector must be 'fps', 'change' or 'hold', not {frame_selector!r}")
-        if interval_image not in ("middle",) + frame_select.COMPOSITE_MODES:
-            raise ValueError(f"interval_image must be 'middle' or one of {frame_select.COMPOSITE_MODES}, not {interval_image!r}")
+        if interval_image not in INTERVAL_IMAGES:
+            raise ValueError(f"interval_image must be one of {INTERVAL_IMAGES}, not {interval_image!r}")
         if interval_image != "middle" and frame_selector not in ("change", "hold"):
             raise ValueError(f"interval_image={interval_image!r} composites the intervals of frame_selector='change' or 'hold', not {frame_selector!r}")
         if interval_text not in ("single", "fused"):
@@ -422,7 +434,10 @@ class SubtitleExtractor:
         """interval_image other than "middle": the picture of each interval this rank will recognise (with `shard`, the slice
         run_ocr_tasks gives it) -> the source run_ocr_tasks reads, which shows them in the rep frames."""
         up = self._uploader()
-        comp = frame_select.IntervalCompositor(**{"mode": self.interval_image, "batch": self.batch, **(self.composite_params or {})})
+        if self.interval_image == "quantile":
+            comp = frame_select.IntervalQuantile(**{"batch": self.batch, **(self.composite_params or {})})
+        else:
+            comp = frame_select.IntervalCompositor(**{"mode": self.interval_image, "batch": self.batch, **(self.composite_params or {})})
         only = None if self.shard is None else range(*parallel.shard_range(n_tasks, *self.shard))
         self.interval_patches = comp.run(self._decode_order(up), self.sub_area, self.intervals, self.source.fps, uploader=up, only=only)
         return CompositedSource(self.source, self.sub_area, self.interval_patches)
@@ -577,9 +592,11 @@ def _parse_area(text):
     return SubtitleArea(*(int(p) for p in parts))
 
 
-def main(argv=None, ocr=None, counter=None, cells_fn=None):
+def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None):
     """ocr: the recogniser (None: shim.OcrRecogniser on the GPU, frames staged through staging.default_uploader, YUV 4:2:0 converted
-    on the device); counter: the change / hold selector's count_fn (None: the GPU's); cells_fn: the locator's (None: the GPU's)."""
+    on the device); counter: the change / hold selector's count_fn (None: the GPU's); cells_fn: the locator's (None: the GPU's);
+    composite_fn: what makes the picture of `--interval-image`, the compositor's accumulate_fn for min / max / mean and the quantile's
+    rank_fn for quantile (None: the GPU's)."""
     p = argparse.ArgumentParser(prog="python -m vse_amd.extractor", description="Extract a video's hard subtitles to SRT on the GPU.  "
                                 "`-` reads YUV4MPEG2 from standard input in one pass, e.g. "
                                 "`ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m vse_amd.extractor - -o film.srt`.")
@@ -598,6 +615,13 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None):
                    "pixel, or `auto` to choose it for this clip first (not in one pass) [128]")
     p.add_argument("--locator-automaton", default="change", choices=("change", "hold"), help="what `--area auto` and `--edge-thresh auto` "
                    "count: every edge pixel, or with `hold` only edges that hold still (a textured background that moves) [change]")
+    p.add_argument("--interval-image", default="middle", choices=INTERVAL_IMAGES, help="change / hold selector: what the recogniser is "
+                   "shown for each subtitle: its middle frame, the per-pixel min (light text) / max (dark text) / mean of all its frames, "
+                   "or the per-pixel quantile of a few evenly spaced ones, which needs no polarity and shrugs off a flash or a late cut "
+                   "(not in one pass) [middle]")
+    p.add_argument("--quantile", type=float, default=0.5, metavar="Q", help="--interval-image quantile: 0..1, 0.5 the median [0.5]")
+    p.add_argument("--interval-samples", type=int, default=15, metavar="K", help="--interval-image quantile: frames sampled per subtitle, "
+                   "1..min(batch, 63); exact when the subtitle has no more frames, an estimate otherwise [15]")
     p.add_argument("--mode", default="fast", choices=("fast", "auto", "accurate"))
     p.add_argument("--language", default="ch")
     p.add_argument("--frequency", type=int, default=3, help="frames per second the fps sampler looks at [3]")
@@ -618,6 +642,12 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None):
         area = None if args.area is None else _parse_area(args.area)
         from .area_locator import parse_edge_thresh
         edge_thresh = parse_edge_thresh(args.edge_thresh)
+        composite_params = None
+        if args.interval_image == "quantile":
+            composite_params = {"quantile": args.quantile, "samples": args.interval_samples, "rank_fn": composite_fn}
+            frame_select.IntervalQuantile(**{"batch": args.batch, **composite_params})          # a bad value is refused before any work
+        elif args.interval_image != "middle":
+            composite_params = {"accumulate_fn": composite_fn}
         source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout, matrix=args.matrix)
         uploader = None
         if ocr is None:
@@ -629,7 +659,8 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None):
             ocr, uploader = shim.OcrRecogniser(), staging.default_uploader()
         ex = SubtitleExtractor(source, ocr, sub_area=area, mode=args.mode, language=args.language, extract_frequency=args.frequency,
                                batch=args.batch, uploader=uploader, frame_selector=args.selector, change_counter=counter,
-                               retain_bytes=int(args.retain_gib * (1 << 30)),
+                               retain_bytes=int(args.retain_gib * (1 << 30)), interval_image=args.interval_image,
+                               composite_params=composite_params,
                                change_params=None if edge_thresh == 128 else {"edge_thresh": edge_thresh},
                                area_params={**({} if cells_fn is None else {"cells_fn": cells_fn}),
                                             **({} if args.locator_automaton == "change" else {"automaton": args.locator_automaton})} or None)

@@ -22,7 +22,7 @@ from contextlib import closing
 from itertools import islice
 
 from . import staging
-from .engine import DeviceState
+from .engine import INTERVAL_RANK_MAX, DeviceState
 from .shim import get_coordinates
 
 
@@ -629,3 +629,104 @@ class IntervalFuser:
         for call, (_items, data) in zip(plan, staging.staged_batches(batches(), uploader)):
             fuse(call, data)
         return self.results
+
+
+# ---- interval quantile (a per-pixel order statistic over a few samples of each interval of the change selector) ---------------
+def quantile_rank(quantile, k):
+    """The 0-based rank among k sorted samples that stands for `quantile` in [0, 1], in integers: the quantile in thousandths times
+    k - 1, rounded to nearest with halves up.  0 -> 0 (the minimum), 1 -> k - 1 (the maximum), 0.5 with odd k -> the median."""
+    return (int(round(quantile * 1000)) * (k - 1) + 500) // 1000
+
+
+class EngineRanker(DeviceState):
+    """rank_fn of IntervalQuantile on the GPU (Context.interval_rank).  The kernel is stateless: nothing is kept between calls."""
+
+    def __call__(self, frames, area, rank):
+        return self.ctx.interval_rank(self._device(frames), area, rank)
+
+
+class IntervalQuantile:
+    """IntervalCompositor's robust sibling: one picture of the subtitle area per interval, each byte the `quantile` of that byte over up
+    to `samples` evenly spaced frames of the interval (fuse_samples, the frames IntervalFuser reads).  The temporal median of a subtitle
+    that stands still over a picture that moves is the subtitle's own value at text pixels whatever its colour, so nobody has to know
+    whether the text is light (`min`) or dark (`max`); a minority of outlier frames (a flash, a black frame, a cut found one frame
+    late, a half-faded frame) cannot move it, where one of them destroys a `min` or `max`; a low or high quantile is the robust form
+    of those two.  Only the samples are staged: min(samples, trimmed length) frames per interval instead of all of them.
+    The quantile is exact over the trimmed interval whenever that has at most `samples` frames and an estimate from `samples` frames
+    otherwise; an exact quantile over every frame is not attempted.  How much the picture helps recognition on real footage is not
+    measured here (no real clips, stand-in recogniser weights); the integers, the plumbing and the cost are pinned.
+
+    rank_fn(frames [k,h,w,3] uint8, area (y0, y1, x0, x1) in their pixels, rank) -> uint8 [y1-y0, x1-x0, 3]: per byte, element `rank`
+    (0-based) of the k frames' values sorted ascending.  Default: EngineRanker on the shim's device.  Each interval's rank is
+    quantile_rank(quantile, its number of samples).  Whole intervals are gathered into one staged batch until one more would exceed
+    `batch` frames; rank_fn is then called once per interval, on its slice of the batch."""
+
+    def __init__(self, rank_fn=None, quantile=0.5, samples=15, trim_seconds=0.25, batch=64):
+        if not 0 <= quantile <= 1:
+            raise ValueError(f"IntervalQuantile: quantile must be in [0, 1], not {quantile!r}")
+        if samples < 1 or samples > min(batch, INTERVAL_RANK_MAX):
+            raise ValueError(f"IntervalQuantile: samples must be 1..min(batch, {INTERVAL_RANK_MAX}) = {min(batch, INTERVAL_RANK_MAX)}, not "
+                             f"{samples}: an interval is ranked in one call of at most {INTERVAL_RANK_MAX} frames")
+        self.rank_fn, self.quantile, self.samples, self.trim_seconds, self.batch = rank_fn, quantile, int(samples), trim_seconds, int(batch)
+        self.area = None              # (y0, y1, x0, x1): the area clipped to the frame, where the patches belong
+        self.patches = None
+
+    def run(self, frames, sub_area, intervals, fps, uploader=None, only=None):
+        """frames: iterable of uint8 BGR frames in decode order (read once, and not beyond the last sample that is needed); sub_area:
+        clipped to the frame exactly as ChangeFrameSelector.run clips it; intervals: its [(start, end, rep)], ascending; only: a range
+        of interval indices (a rank's shard), the others are not read -> {rep: uint8 ndarray [ah, aw, 3]}.  Only the area's rows of
+        the sampled frames are staged (staging.staged_batches)."""
+        import numpy as np
+        if self.rank_fn is None:
+            from . import shim
+            self.rank_fn = EngineRanker(shim._context())
+        plan = [[]]                   # per staged batch: [(rep, frame numbers)], whole intervals, at most `batch` frames
+        last_no = 0
+        for k, (start, end, rep) in enumerate(intervals):
+            if only is None or k in only:
+                nos, _pos = fuse_samples(start, end, rep, fps, self.samples, self.trim_seconds)
+                if nos[0] <= last_no:
+                    raise ValueError(f"IntervalQuantile: intervals must ascend without overlap, got {intervals[k - 1]} then {intervals[k]}")
+                last_no = nos[-1]
+                if plan[-1] and sum(len(n) for _r, n in plan[-1]) + len(nos) > self.batch:
+                    plan.append([])
+                plan[-1].append((rep, nos))
+        self.patches = {}
+        if not plan[0]:
+            return self.patches
+        it = iter(frames)
+        geometry = []                 # [y0, y1, x0, x1] once the first frame has been seen
+
+        def rows(f):
+            if not geometry:
+                h, w = f.shape[:2]
+                y0, y1, x0, x1 = clip_area(sub_area, h, w)
+                if y1 <= y0 or x1 <= x0:
+                    raise ValueError(f"IntervalQuantile: subtitle area {sub_area} leaves nothing of a {h} x {w} frame")
+                geometry.extend((y0, y1, x0, x1))
+            return f[geometry[0]:geometry[1]]
+
+        def batches():
+            """lists of (frame number, area rows): the samples of one staged batch's intervals, in decode order"""
+            no = 0
+            for call in plan:
+                buf = []
+                for _rep, nos in call:
+                    for want in nos:
+                        while no < want:
+                            f = next(it, None)
+                            if f is None:
+                                raise ValueError(f"IntervalQuantile: the clip ends at frame {no}, before the sample at frame {want}")
+                            no += 1
+                        buf.append((no, rows(f)))
+                yield buf
+
+        for call, (_items, data) in zip(plan, staging.staged_batches(batches(), uploader)):
+            y0, y1, x0, x1 = geometry
+            at = 0
+            for rep, nos in call:
+                out = self.rank_fn(data[at:at + len(nos)], (0, y1 - y0, x0, x1), quantile_rank(self.quantile, len(nos)))
+                self.patches[rep] = out.cpu().numpy() if hasattr(out, "cpu") else np.array(out)
+                at += len(nos)
+        self.area = tuple(geometry)
+        return self.patches
