@@ -255,6 +255,24 @@ size_t vse_frame_change_state_bytes(int area_h, int area_w);
 int vse_frame_change(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride,
                      int y0, int y1, int x0, int x1, int edge_thresh, void* d_state, int reset,
                      int32_t* d_counts /* [n,3]: edges, appeared, vanished */, void* stream);
+/* Replaces: nothing in the reference; it serves the selectors above and below, which recognise each subtitle on ONE frame of its
+ * interval: a score by which the host picks that frame (vse_amd.frame_select.sharpest_rep) instead of taking the middle one, which in
+ * compressed video may as well be a coarse, half-faded or flashed frame.  Area, Y, interior and the edge pixels E of a frame exactly as
+ * for vse_frame_change; E' = the previous frame's edge pixels, empty on a fresh state or with `reset`.  Per frame:
+ *   g(p) = max(|Y[y][x+1] - Y[y][x-1]|, |Y[y+1][x] - Y[y-1][x]|)           (0..255; p is in E when g(p) >= edge_thresh)
+ *   K = E and E'     the edge pixels that were edge pixels one frame earlier: a subtitle's edges stand still, most of a moving
+ *                    background's do not
+ *   kept = |K|,  focus = the sum of g(p) over p in K.
+ * What it gains in recognition on real footage is not measured (no real clips).  Known limit: edges of a static background count in
+ * every frame alike, and on a busy static shot the score also rewards the background's sharpness.
+ * d_state has the size and the meaning of vse_frame_change's (vse_frame_change_state_bytes; the last frame's mask): frames fed in
+ * batches of any sizes give the rows of one call, and a state written by vse_frame_change may be continued here and the other way
+ * round.  Every element of d_focus is written.  One launch on `stream` behind the clearing of d_focus, no allocation, no device sync;
+ * the sums are integers and do not depend on the order of the blocks.  Returns VSE_E_INVAL, and launches nothing, for what
+ * vse_frame_change refuses, n < 1, or an interior of more than 2^23 pixels (focus <= 255 * 2^23 < 2^31; a 4K frame fits). */
+int vse_frame_focus(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride,
+                    int y0, int y1, int x0, int x1, int edge_thresh, void* d_state, int reset,
+                    int32_t* d_focus /* [n,2]: kept, focus */, void* stream);
 
 /* ---- subtitle-area locator --------------------------------------------------------------------------------------------- */
 /* Replaces: the rectangle a person draws in the reference's GUI (config.subtitleSelectionAreas, backend/config.py:49), which

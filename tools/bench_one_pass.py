@@ -11,11 +11,13 @@ upload and conversion on the device is inside the timed region.  Rows, each `--r
     pipe      the same bytes as YUV4MPEG2 through an OS pipe from a child process that only writes them (this file with --writer),
               read by ingest.Y4mStream: what `decoder | python -m vse_amd.extractor -` costs on the reading side
 
-for frame_selector "change" and "hold".  `peak_retained` is the largest number of frames a one-pass run held at once.  The run-to-run
+for frame_selector "change" and "hold", and for each of --interval-frames (middle: the default; sharpest: every frame scored by
+vse_frame_focus in the selector's pass, the sharpest of each interval recognised).  `peak_retained` is the largest number of frames a one-pass run held at once.  The run-to-run
 spread is to be read from the multi rows themselves (the machine's other work shares the host).  No decoder runs here: how a real
 `ffmpeg` pipe compares is not measured by this tool.
 
-usage: python tools/bench_one_pass.py [--frames 9216] [--hold 24] [--runs 4] [--selectors change,hold] [--rows multi,onepass,pipe]"""
+usage: python tools/bench_one_pass.py [--frames 9216] [--hold 24] [--runs 4] [--selectors change,hold] [--rows multi,onepass,pipe]
+                                      [--interval-frames middle]"""
 import argparse
 import json
 import os
@@ -82,6 +84,7 @@ def main():
     ap.add_argument("--runs", type=int, default=4)
     ap.add_argument("--selectors", default="change,hold")
     ap.add_argument("--rows", default="multi,onepass,pipe")
+    ap.add_argument("--interval-frames", default="middle", help="comma-separated: middle, sharpest")
     ap.add_argument("--rec", default="V4_ch_rec_fast", help="recogniser model id (stand-in weights)")
     ap.add_argument("--writer", default=None, metavar="NPY", help="(the pipe rows' child) write the clip of these pictures to standard output")
     a = ap.parse_args()
@@ -118,7 +121,7 @@ def main():
     npy = os.path.join(tmp, "pictures.npy")
     np.save(npy, np.stack([np.concatenate([np.ascontiguousarray(p).reshape(-1) for p in tr]) for tr in pictures]))
 
-    def run(row, selector, frames):
+    def run(row, selector, frames, interval_frame="middle"):
         counter = frame_select.EngineCounter(ctx) if selector == "change" else frame_select.EngineHoldCounter(ctx)
         child = None
         if row == "pipe":
@@ -128,7 +131,8 @@ def main():
         else:
             source = Yuv420ArraySource(clip[:frames], fps)
         ex = extractor.SubtitleExtractor(source, Ocr(), sub_area=area, mode="fast", frame_selector=selector, change_counter=counter,
-                                         uploader=up, drop_score=0.0, batch=a.batch, one_pass=None if row != "onepass" else True)
+                                         uploader=up, drop_score=0.0, batch=a.batch, one_pass=None if row != "onepass" else True,
+                                         **({} if interval_frame == "middle" else {"interval_frame": interval_frame}))
         torch.cuda.synchronize()
         t0 = time.time()
         text = ex.run()
@@ -141,12 +145,12 @@ def main():
 
     try:
         for selector in a.selectors.split(","):
-            for row in a.rows.split(","):
+            for row, interval_frame in ((r, f) for r in a.rows.split(",") for f in a.interval_frames.split(",")):
                 # warm-up: every plan the timed runs use is compiled and its workspace allocated (the pipe rows: on the clip's first batches)
-                run(row, selector, a.frames if row != "pipe" else min(a.frames, 5 * a.batch))
+                run(row, selector, a.frames if row != "pipe" else min(a.frames, 5 * a.batch), interval_frame)
                 for k in range(a.runs):
-                    dt, ex, text = run(row, selector, a.frames)
-                    print(json.dumps({"what": "one_pass", "row": row, "selector": selector, "run": k, "rec": a.rec, "frames": a.frames,
+                    dt, ex, text = run(row, selector, a.frames, interval_frame)
+                    print(json.dumps({"what": "one_pass", "row": row, "selector": selector, "interval_frame": interval_frame, "run": k, "rec": a.rec, "frames": a.frames,
                                       "frame": [a.height, a.width], "intervals": len(ex.intervals), "seconds": round(dt, 3),
                                       "frames_per_s": round(a.frames / dt, 1), "one_pass": ex.one_pass, "peak_retained": ex.peak_retained,
                                       "clamped_intervals": ex.clamped_intervals, "srt_blocks": text.count(" --> ")}), flush=True)

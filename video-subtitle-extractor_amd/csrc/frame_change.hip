@@ -23,6 +23,9 @@
 //
 // Locator and calibration on held edges (vse_frame_cells_hold): the cells and their automaton at several thresholds, counted on the
 // held masks (frame_cells_hold_kernel below).
+//
+// Sharpness of the edges that stand still (vse_frame_focus): the same tiles, mask and state as vse_frame_change, but per frame the
+// number of edge pixels that were edge pixels one frame earlier and the sum of their gradients (frame_focus_kernel below).
 #include "common.h"
 
 namespace {
@@ -582,6 +585,109 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_hold_kernel(const u
     }
 }
 
+// ---- vse_frame_focus ------------------------------------------------------------------------------------------------------------
+// Per frame, how sharp the edges are that already stood one frame earlier: K = E & E', kept = |K|, focus = the sum over K of the gradient
+// g = max(|Y[y][x+1] - Y[y][x-1]|, |Y[y+1][x] - Y[y-1][x]|), the value that E compares with the threshold.  The tile is tile_lane's and
+// the loads, lumas and gradients are tile_masks', statement for statement; what differs is who owns which frame.  A lane needs its own
+// pixel's bit of the frame before, not the packed word, so a wave takes CONSECUTIVE frames (wave q the frames q * per .. q * per + per - 1,
+// per = ceil(n / FC_WAVES)) and carries its eight rows' bits of the last frame in one register: no ballot, no LDS and no barrier between
+// the frames of a wave, and g is used where it is computed.  Only the first frame of a wave meets a mask that another wave (or the call
+// before) made: its bits and its eight gradients, one byte each in two registers, wait for the one barrier of the kernel, behind which the
+// last frame of every wave stands in LDS as packed words, the form the state keeps.  There is no chunk loop: n frames are n / 8 per wave.
+// The state is frame_change_kernel's, words and flag, read at the start and written at the end by the block that owns the tile.
+// A lane's sums of one frame travel as one integer, focus (<= 8 * 255) | kept (<= 8) << 20; summed over the wave focus < 2^17, kept <= 512.
+constexpr int FOCUS_KEPT_SHIFT = 20;
+
+// g[k] = the gradient of the lane's pixel in interior row k of the tile, f pointing at the tile's first halo row in one frame
+// -> bit k: that pixel is an edge pixel.
+__device__ __forceinline__ unsigned tile_gradients(const uint8_t* __restrict__ f, long pitch, const TileLane& t, int thresh, int (&g)[FC_ROWS]) {
+    const int lane = threadIdx.x & 63;
+    const int rows = t.rows;
+    int yc[FC_ROWS + 2], ye[FC_ROWS];
+#pragma unroll
+    for (int k = 0; k < FC_ROWS + 2; ++k) yc[k] = (k < rows + 2 && t.own) ? luma(f + (long)k * pitch + t.x * 3) : 0;
+#pragma unroll
+    for (int k = 0; k < FC_ROWS; ++k) ye[k] = (k < rows && t.extra) ? luma(f + (long)(k + 1) * pitch + t.xe * 3) : 0;
+    unsigned bits = 0;
+#pragma unroll
+    for (int k = 0; k < FC_ROWS; ++k) {
+        g[k] = 0;
+        if (k < rows) {                // block-uniform
+            const int l = __shfl_up(yc[k + 1], 1), r = __shfl_down(yc[k + 1], 1);
+            const int left = lane == 0 ? ye[k] : l, right = lane == 63 ? ye[k] : r;
+            g[k] = max(abs(right - left), abs(yc[k + 2] - yc[k]));
+            if (t.inner && g[k] >= thresh) bits |= 1u << k;
+        }
+    }
+    return bits;
+}
+
+// The wave's sums over the pixels in `kept` (bit k: the lane's pixel of row k) -> row `out` of the call's output, one atomic each.
+__device__ __forceinline__ void focus_add(unsigned kept, const int (&g)[FC_ROWS], int* out) {
+    int acc = __popc(kept) << FOCUS_KEPT_SHIFT;
+#pragma unroll
+    for (int k = 0; k < FC_ROWS; ++k) acc += (kept >> k) & 1u ? g[k] : 0;
+#pragma unroll
+    for (int o = 32; o; o >>= 1) acc += __shfl_xor(acc, o);
+    // integer sums: the totals do not depend on the order the blocks arrive in
+    if ((threadIdx.x & 63) == 0 && acc) {
+        atomicAdd(out, acc >> FOCUS_KEPT_SHIFT);
+        atomicAdd(out + 1, acc & ((1 << FOCUS_KEPT_SHIFT) - 1));
+    }
+}
+
+// src, words and flag as frame_change_kernel's; focus [n][2] = kept, focus, cleared before the launch.
+__global__ __launch_bounds__(FC_WAVES * 64) void frame_focus_kernel(const uint8_t* __restrict__ src, int n, long pitch, long fstride, int x0,
+                                                                    int ih, int iw, int wpr, int thresh, unsigned long long* __restrict__ words,
+                                                                    unsigned* flag, int reset, int* __restrict__ focus) {
+    __shared__ unsigned long long last[FC_WAVES][FC_ROWS];     // packed mask of the last frame of each wave
+    __shared__ unsigned long long prv[FC_ROWS];                // ... and of the last frame of the call before
+    static_assert(FC_ROWS == 8, "a frame's gradients are eight bytes in two registers");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int w = blockIdx.x, iy0 = blockIdx.y * FC_ROWS;
+    const TileLane t = tile_lane(w, iy0, ih, iw, x0);
+    unsigned long long* st = words + (long)iy0 * wpr + w;
+    // (the flag: see frame_change_kernel)
+    const bool use_prev = !reset && *(volatile unsigned*)flag != 0;
+    if (threadIdx.x < FC_ROWS) prv[threadIdx.x] = (use_prev && (int)threadIdx.x < t.rows) ? st[(long)threadIdx.x * wpr] : 0ull;
+    const int per = (n + FC_WAVES - 1) / FC_WAVES;
+    const int f0 = wave * per, f1 = min(n, f0 + per);          // this wave's frames; a wave that has some follows one that has some
+    unsigned first = 0, g_lo = 0, g_hi = 0;                    // the wave's first frame: its bits, and its gradients of rows 0..3 and 4..7
+    if (f0 < f1) {
+        const uint8_t* f = src + (long)f0 * fstride + (long)iy0 * pitch;
+        int g[FC_ROWS];
+        first = tile_gradients(f, pitch, t, thresh, g);
+        g_lo = (unsigned)g[0] | (unsigned)g[1] << 8 | (unsigned)g[2] << 16 | (unsigned)g[3] << 24;
+        g_hi = (unsigned)g[4] | (unsigned)g[5] << 8 | (unsigned)g[6] << 16 | (unsigned)g[7] << 24;
+        unsigned pre = first;
+        for (int fr = f0 + 1; fr < f1; ++fr) {
+            f += fstride;
+            const unsigned cur = tile_gradients(f, pitch, t, thresh, g);
+            focus_add(cur & pre, g, focus + (long)fr * 2);
+            pre = cur;
+        }
+#pragma unroll
+        for (int k = 0; k < FC_ROWS; ++k) {                    // bits of rows outside the area are zero
+            const unsigned long long b = __ballot((pre >> k) & 1u);
+            if (lane == 0) last[wave][k] = b;
+        }
+    }
+    __syncthreads();
+    if (f0 < f1) {
+        unsigned pre = 0;
+        int g[FC_ROWS];
+#pragma unroll
+        for (int k = 0; k < FC_ROWS; ++k) {
+            const unsigned long long word = wave ? last[wave - 1][k] : prv[k];
+            pre |= (unsigned)((word >> lane) & 1ull) << k;
+            g[k] = (int)(((k < 4 ? g_lo : g_hi) >> (8 * (k & 3))) & 255u);
+        }
+        focus_add(first & pre, g, focus + (long)f0 * 2);
+    }
+    if (wave == (n - 1) / per && lane < t.rows) st[(long)lane * wpr] = last[wave][lane];      // the wave that had the call's last frame
+    if (threadIdx.x == 0) *flag = 1u;
+}
+
 }  // namespace
 
 // Called by vse_frame_change (vse_runtime.hip) after it has checked the geometry.
@@ -595,6 +701,20 @@ int vse_frame_change_launch(const void* d_bgr, int n, int64_t pitch, int64_t fra
     const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
     hipLaunchKernelGGL(frame_change_kernel, dim3(wpr, (ih + FC_ROWS - 1) / FC_ROWS), dim3(FC_WAVES * 64), 0, st, src, n, (long)pitch,
                        (long)frame_stride, x0, ih, iw, wpr, edge_thresh, words, flag, reset, reinterpret_cast<int*>(d_counts));
+    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+}
+
+// Called by vse_frame_focus (vse_runtime.hip) after it has checked the geometry (n >= 1).
+int vse_frame_focus_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
+                           void* d_state, int reset, int32_t* d_focus, void* stream) {
+    const int ih = y1 - y0 - 2, iw = x1 - x0 - 2, wpr = (iw + 63) / 64;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (hipMemsetAsync(d_focus, 0, (size_t)n * 2 * sizeof(int32_t), st) != hipSuccess) return VSE_E_HIP;
+    unsigned* flag = reinterpret_cast<unsigned*>(d_state);
+    unsigned long long* words = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(d_state) + 16);
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
+    hipLaunchKernelGGL(frame_focus_kernel, dim3(wpr, (ih + FC_ROWS - 1) / FC_ROWS), dim3(FC_WAVES * 64), 0, st, src, n, (long)pitch,
+                       (long)frame_stride, x0, ih, iw, wpr, edge_thresh, words, flag, reset, reinterpret_cast<int*>(d_focus));
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
 

@@ -52,6 +52,8 @@ int vse_ctc_fuse_launch(const float* d_probs, int b, int t, int ncls, int64_t ro
                         void* d_idx_maxp, void* stream);                                                               // prepost.hip
 int vse_frame_change_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
                             void* d_state, int reset, int32_t* d_counts, void* stream);     // frame_change.hip
+int vse_frame_focus_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
+                           void* d_state, int reset, int32_t* d_focus, void* stream);      // frame_change.hip
 int vse_frame_cells_state_words();                                                                                     // frame_change.hip
 int vse_frame_cells_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
                            int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames, void* d_state, int reset, int flush,
@@ -465,6 +467,20 @@ int vse_frame_change(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w,
         !check_area("vse_frame_change", "area", y0, y1, x0, x1, src_h, src_w))
         return VSE_E_INVAL;
     return vse_frame_change_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, d_state, reset, d_counts, stream);
+}
+
+// ---- sharpness of the edges that stand still (frame_change.hip) ---------------------------------------------------------------
+int vse_frame_focus(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0, int y1,
+                    int x0, int x1, int edge_thresh, void* d_state, int reset, int32_t* d_focus, void* stream) {
+    if (!check_frames("vse_frame_focus", c && d_focus, d_bgr, n, 1, src_h, src_w, pitch, frame_stride, d_state) ||
+        !check_area("vse_frame_focus", "area", y0, y1, x0, x1, src_h, src_w))
+        return VSE_E_INVAL;
+    if ((int64_t)(y1 - y0 - 2) * (x1 - x0 - 2) > ((int64_t)1 << 23)) {
+        set_err("vse_frame_focus: the area's interior of %d x %d pixels exceeds 2^23, beyond which a frame's focus may not fit an int32",
+                y1 - y0 - 2, x1 - x0 - 2);
+        return VSE_E_INVAL;
+    }
+    return vse_frame_focus_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, d_state, reset, d_focus, stream);
 }
 
 // ---- subtitle-area locator (frame_change.hip) -------------------------------------------------------------------------------

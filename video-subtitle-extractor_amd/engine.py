@@ -27,7 +27,7 @@ EXPORTS = [
     "vse_frame_hold",
     "vse_audio_stream_length", "vse_audio_stream_workspace_bytes", "vse_audio_stream_feed", "vse_audio_stream_finish", "vse_ctc_fuse",
     "vse_yuv_to_bgr_matrix", "vse_frame_cells_multi_state_bytes", "vse_frame_cells_multi",
-    "vse_frame_cells_hold_state_bytes", "vse_frame_cells_hold",
+    "vse_frame_cells_hold_state_bytes", "vse_frame_cells_hold", "vse_frame_focus",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -163,6 +163,7 @@ def load_library(path=None):
     lib.vse_frame_change_state_bytes.argtypes = [C.c_int, C.c_int]
     lib.vse_frame_change.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.vse_frame_focus.argtypes = lib.vse_frame_change.argtypes
     lib.vse_frame_cells_dims.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.vse_frame_cells_state_bytes.restype = C.c_size_t
     lib.vse_frame_cells_state_bytes.argtypes = [C.c_int, C.c_int]
@@ -505,6 +506,19 @@ class Context:
         out = t.empty((frames[1], 3), dtype=t.int32, device=self.tdev)
         _check(self.lib.vse_frame_change(self.handle, *frames, y0, y1, x0, x1, int(edge_thresh), C.c_void_p(state.data_ptr()),
                                          int(bool(reset)), C.c_void_p(out.data_ptr()), self.stream()), "vse_frame_change")
+        return out
+
+    def frame_focus(self, frames_u8, area, edge_thresh, state, reset=False):
+        """frames_u8, area and state as for frame_change (the state is frame_change_state's and may pass between the two calls) ->
+        cuda int32 [n,2]: kept, focus per frame: the edge pixels that were edge pixels one frame earlier, and the sum of their
+        gradients (include/vse_hip.h vse_frame_focus)."""
+        t = self.torch
+        frames = self._frames_args(frames_u8)
+        y0, y1, x0, x1 = (int(v) for v in area)
+        assert state.dtype == t.uint8 and state.is_contiguous() and state.numel() >= self.lib.vse_frame_change_state_bytes(y1 - y0, x1 - x0)
+        out = t.empty((frames[1], 2), dtype=t.int32, device=self.tdev)
+        _check(self.lib.vse_frame_focus(self.handle, *frames, y0, y1, x0, x1, int(edge_thresh), C.c_void_p(state.data_ptr()),
+                                        int(bool(reset)), C.c_void_p(out.data_ptr()), self.stream()), "vse_frame_focus")
         return out
 
     # ---- subtitle-area locator ------------------------------------------------------------------------------------

@@ -230,6 +230,8 @@ def _boxes_list(arr):
 # what the recogniser may be shown for an interval: its middle frame, a composite of all its frames (frame_select.COMPOSITE_MODES),
 # or the per-pixel quantile of a few of them (frame_select.IntervalQuantile)
 INTERVAL_IMAGES = ("middle",) + frame_select.COMPOSITE_MODES + ("quantile",)
+# which single frame of an interval is recognised: its middle frame, or the one whose standing edges are sharpest (frame_select.sharpest_rep)
+INTERVAL_FRAMES = ("middle", "sharpest")
 
 
 class SubtitleExtractor:
@@ -292,14 +294,28 @@ class SubtitleExtractor:
     intervals, the frames recognised, raw_lines and the SRT equal those of the multi-pass run() on the same frames with the same
     arguments (recognition does not depend on how frames are grouped into batches: tests/test_gpu_ragged.py).  Refused in one pass,
     because they need a second look at frames already gone: sub_area="auto", mode="accurate" with an area, interval_image other than
-    "middle", interval_text="fused", shard, change_params' edge_thresh="auto"."""
+    "middle", interval_text="fused", shard, change_params' edge_thresh="auto".
+    interval_frame="sharpest" (change / hold selector with interval_image="middle" and interval_text="single" only; default "middle", all
+    of the above): the one frame an interval is recognised on is chosen instead of being the middle one, which in compressed video is as
+    likely as any other to be a coarse B-frame, a half-faded frame or a flash.  In the selector's own pass over the staged area rows the
+    device scores every frame by the gradients of the edge pixels that already stood one frame earlier (vse_frame_focus through the
+    selector's focus_fn; the rows are kept as `focus`), and each interval's rep becomes frame_select.sharpest_rep: the largest focus
+    among the frames that `trim_seconds` leaves at either end, the earliest of equals.  `frame_params`: trim_seconds (default 0.25) and
+    focus_fn (default frame_select.EngineFocus on the shim's device).  It needs no second look, so it is the one protection against a bad
+    middle frame that works in one pass, with the same intervals, recognised frames, raw_lines and SRT as in several passes; one pass then
+    keeps a frame only while it can still become its interval's rep: with T = round(trim_seconds * fps), of an open run s..t the frames
+    >= (s + t) // 2 while t - s < 2 T, afterwards the frames > t - T and the best frame so far among s + T .. t - T: about 2 T + 1 frames
+    plus the batches in flight however long the run, instead of half the run; `retain_bytes` remains the fallback behind it.  What it gains
+    in recognition on real footage is not measured here (no real clips, stand-in recogniser weights).  Known limit: edges of a static
+    background count alike in every frame, and on a busy static shot the score also rewards the background's sharpness."""
 
     def __init__(self, source, ocr, detect_batch=None, sub_area=None, mode="fast", language="ch", extract_frequency=3,
                  default_subtitle_area=None, drop_score=0.75, deviation_rate=0.0, threshold=80, batch=64,
                  watermark_decide=None, scene_text_decide=lambda band: True, shard=None, gather_device=None,
                  word_segmentation=False, segment=None, uploader=None, detect_stream=None, frame_selector="fps", change_params=None,
                  change_counter=None, delete_empty=True, area_params=None, interval_image="middle", composite_params=None,
-                 interval_text="single", fuse_params=None, one_pass=None, retain_bytes=4 << 30):
+                 interval_text="single", fuse_params=None, one_pass=None, retain_bytes=4 << 30, interval_frame="middle",
+                 frame_params=None):
         if frame_selector not in ("fps", "change", "hold"):
             raise ValueError(f"frame_selector must be 'fps', 'change' or 'hold', not {frame_selector!r}")
         if interval_image not in INTERVAL_IMAGES:
@@ -311,6 +327,18 @@ class SubtitleExtractor:
         if interval_text == "fused" and (frame_selector not in ("change", "hold") or interval_image != "middle"):
             raise ValueError(f"interval_text='fused' reads the intervals of frame_selector='change' or 'hold' (not {frame_selector!r}) from their "
                              f"own frames, interval_image='middle' (not {interval_image!r}): composites and fused posteriors do not combine")
+        if interval_frame not in INTERVAL_FRAMES:
+            raise ValueError(f"interval_frame must be one of {INTERVAL_FRAMES}, not {interval_frame!r}")
+        if interval_frame == "sharpest":
+            for name, value, wanted in (("frame_selector", frame_selector, ("change", "hold")), ("interval_image", interval_image, ("middle",)),
+                                        ("interval_text", interval_text, ("single",))):
+                if value not in wanted:
+                    raise ValueError(f"interval_frame='sharpest' chooses the one frame an interval of frame_selector='change' or 'hold' is "
+                                     f"recognised on (interval_image='middle', interval_text='single'); it does not combine with {name}={value!r}")
+            unknown = set(frame_params or {}) - {"trim_seconds", "focus_fn"}
+            if unknown:
+                raise ValueError(f"frame_params takes trim_seconds and focus_fn, not {sorted(unknown)}")
+        self.interval_frame, self.frame_params, self.focus = interval_frame, frame_params, None
         self.source, self.ocr, self.detect_batch = source, ocr, detect_batch
         self.auto_area, self.area_params, self.located_area = isinstance(sub_area, str) and sub_area == "auto", area_params, None
         self.sub_area, self.mode, self.language = None if self.auto_area else sub_area, mode, language
@@ -412,7 +440,13 @@ class SubtitleExtractor:
     def _interval_selector(self):
         """The change or hold selector of this run (`_selects_intervals`); both take run / iter_run(frames, sub_area, fps, uploader)."""
         cls = frame_select.ChangeFrameSelector if self.frame_selector == "change" else frame_select.HoldFrameSelector
-        return cls(self.change_counter, batch=self.batch, **self._change_params())
+        more = {}
+        if self.interval_frame == "sharpest":
+            more["focus_fn"] = (self.frame_params or {}).get("focus_fn") or frame_select.EngineFocus(shim._context())
+        return cls(self.change_counter, batch=self.batch, **self._change_params(), **more)
+
+    def _trim_seconds(self):
+        return (self.frame_params or {}).get("trim_seconds", 0.25)
 
     def select_tasks(self):
         s = self.source
@@ -426,7 +460,12 @@ class SubtitleExtractor:
             return [(t[0], t[1], t[2], t[3], None, None) for t in sel.run(self._decode_order(up), uploader=up)]
         if self._selects_intervals():
             up = self._uploader()
-            self.intervals = self._interval_selector().run(self._decode_order(up), self.sub_area, s.fps, uploader=up)
+            sel = self._interval_selector()
+            self.intervals = sel.run(self._decode_order(up), self.sub_area, s.fps, uploader=up)
+            if self.interval_frame == "sharpest":
+                self.focus = getattr(sel, "focus", None)            # (a clip without a frame leaves none, and no interval)
+                self.intervals = [(start, end, frame_select.sharpest_rep(start, end, self.focus, s.fps, self._trim_seconds()))
+                                  for start, end, _rep in self.intervals]
             return [(s.frame_count, rep, None, None, None, self.default_subtitle_area) for _start, _end, rep in self.intervals]
         return fps_tasks(s.frame_count, s.fps, self.extract_frequency, self.default_subtitle_area)
 
@@ -487,8 +526,13 @@ class SubtitleExtractor:
         ocr_up = uploader.sibling() if uploader is not None else None
         self.intervals = []
         kept, nbytes = {}, 0              # frame number -> full frame, and their bytes
-        queue = []                        # middle frames of closed intervals, not yet recognised
+        queue = []                        # rep frames of closed intervals, not yet recognised
         lines, no = [], 0
+        sharpest = self.interval_frame == "sharpest"
+        trim = int(round(self._trim_seconds() * self.source.fps)) if sharpest else 0
+        # interval_frame="sharpest": the best frame so far of the open run starting at best_of, among its frames best_of + trim .. best_to
+        best_of = best = None
+        best_to = 0
         try:
             for items, closed in batches:
                 for full, _band in items:
@@ -497,14 +541,16 @@ class SubtitleExtractor:
                     nbytes += _frame_nbytes(full)
                 self.peak_retained = max(self.peak_retained, len(kept))
                 for start, end, rep in closed:
+                    if sharpest:
+                        rep = frame_select.sharpest_rep(start, end, sel.focus, self.source.fps, self._trim_seconds())
                     if rep not in kept:                   # the cap took it: the oldest frame of the interval that is still there
                         rep = min(k for k in kept if k >= rep)
                         self.clamped_intervals += 1
                         if self.clamped_intervals == 1:
                             logging.getLogger(__name__).warning(
-                                "one pass: the interval %d..%d outgrew retain_bytes=%d; it is recognised on frame %d instead of its middle "
+                                "one pass: the interval %d..%d outgrew retain_bytes=%d; it is recognised on frame %d instead of its %s "
                                 "frame (its times are untouched; further such intervals are counted in clamped_intervals)",
-                                start, end, self.retain_bytes, rep)
+                                start, end, self.retain_bytes, rep, self.interval_frame)
                     self.intervals.append((start, end, rep))
                     queue.append(rep)
                 while len(queue) >= self.batch:
@@ -512,7 +558,18 @@ class SubtitleExtractor:
                     del queue[:self.batch]
                 t, open_start = sel.tracker.fed, sel.tracker.open_start
                 floor = t + 1 if open_start is None else (open_start + t) // 2
-                for k in [k for k in kept if k < floor and k not in queue]:
+                if sharpest and open_start is not None:
+                    # a frame stays only while it can still become the rep (sharpest_rep): while the run is shorter than two trims its
+                    # candidates lie at or behind its middle, as above; from then on they are open_start + trim .. end - trim, of which
+                    # the frames up to t - trim are decided among themselves (the best so far, the earliest of equals) and the later ones not yet
+                    if best_of != open_start:
+                        best_of, best, best_to = open_start, None, open_start + trim - 1
+                    if t - open_start >= 2 * trim:
+                        for k in range(best_to + 1, t - trim + 1):
+                            if best is None or sel.focus[k - 1, 1] > sel.focus[best - 1, 1]:
+                                best = k
+                        best_to, floor = t - trim, t - trim + 1
+                for k in [k for k in kept if k < floor and k not in queue and not (sharpest and open_start is not None and k == best)]:
                     nbytes -= _frame_nbytes(kept.pop(k))
                 if nbytes > self.retain_bytes and open_start is not None:
                     for k in sorted(k for k in kept if k < t and k not in queue):       # frame t itself always stays
@@ -521,6 +578,8 @@ class SubtitleExtractor:
                             break
             if queue:
                 lines += self._recognise(kept, queue, ocr_up)
+            if sharpest:
+                self.focus = getattr(sel, "focus", None)
         finally:
             batches.close()
             if ocr_up is not None:
@@ -537,7 +596,7 @@ class SubtitleExtractor:
 
     def run(self):
         """-> SRT text.  raw_lines (normalised, as the reference rewrites raw.txt) and short_lines are kept on the object."""
-        self.intervals = None
+        self.intervals = self.focus = None
         if self.one_pass:
             self.interval_patches = self.interval_results = None
             lines = self._run_one_pass()
@@ -592,11 +651,11 @@ def _parse_area(text):
     return SubtitleArea(*(int(p) for p in parts))
 
 
-def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None):
+def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, focus_fn=None):
     """ocr: the recogniser (None: shim.OcrRecogniser on the GPU, frames staged through staging.default_uploader, YUV 4:2:0 converted
     on the device); counter: the change / hold selector's count_fn (None: the GPU's); cells_fn: the locator's (None: the GPU's);
     composite_fn: what makes the picture of `--interval-image`, the compositor's accumulate_fn for min / max / mean and the quantile's
-    rank_fn for quantile (None: the GPU's)."""
+    rank_fn for quantile (None: the GPU's); focus_fn: what scores the frames of `--interval-frame sharpest` (None: the GPU's)."""
     p = argparse.ArgumentParser(prog="python -m vse_amd.extractor", description="Extract a video's hard subtitles to SRT on the GPU.  "
                                 "`-` reads YUV4MPEG2 from standard input in one pass, e.g. "
                                 "`ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m vse_amd.extractor - -o film.srt`.")
@@ -622,6 +681,9 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None):
     p.add_argument("--quantile", type=float, default=0.5, metavar="Q", help="--interval-image quantile: 0..1, 0.5 the median [0.5]")
     p.add_argument("--interval-samples", type=int, default=15, metavar="K", help="--interval-image quantile: frames sampled per subtitle, "
                    "1..min(batch, 63); exact when the subtitle has no more frames, an estimate otherwise [15]")
+    p.add_argument("--interval-frame", default="middle", choices=INTERVAL_FRAMES, help="change / hold selector: which single frame of each "
+                   "subtitle is recognised: its middle frame, or the one whose standing edges are sharpest, scored in the selector's own pass "
+                   "(works in one pass; not with --interval-image other than middle) [middle]")
     p.add_argument("--mode", default="fast", choices=("fast", "auto", "accurate"))
     p.add_argument("--language", default="ch")
     p.add_argument("--frequency", type=int, default=3, help="frames per second the fps sampler looks at [3]")
@@ -660,7 +722,8 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None):
         ex = SubtitleExtractor(source, ocr, sub_area=area, mode=args.mode, language=args.language, extract_frequency=args.frequency,
                                batch=args.batch, uploader=uploader, frame_selector=args.selector, change_counter=counter,
                                retain_bytes=int(args.retain_gib * (1 << 30)), interval_image=args.interval_image,
-                               composite_params=composite_params,
+                               composite_params=composite_params, interval_frame=args.interval_frame,
+                               frame_params=None if focus_fn is None else {"focus_fn": focus_fn},
                                change_params=None if edge_thresh == 128 else {"edge_thresh": edge_thresh},
                                area_params={**({} if cells_fn is None else {"cells_fn": cells_fn}),
                                             **({} if args.locator_automaton == "change" else {"automaton": args.locator_automaton})} or None)

@@ -15,7 +15,8 @@ The interval side (subtitle-change selection and what follows it) shares its plu
 the area and hands out batches of (full frame, the area's rows), keeping no frame behind; `staging.staged_batches` turns such batches
 into stacked data, through an uploader's pinned memory and producer thread or with np.stack on the host; `_IntervalSelector` is the
 one run / iter_run body of ChangeFrameSelector and HoldFrameSelector; and the Engine* callables keep their device state through
-`engine.DeviceState`.  area_locator.AreaLocator and keyframes.scan stand on the same pieces.
+`engine.DeviceState`.  area_locator.AreaLocator and keyframes.scan stand on the same pieces.  A selector given a `focus_fn` (EngineFocus,
+vse_frame_focus) also scores every frame in the same pass, and `sharpest_rep` picks an interval's frame by that score.
 """
 from collections import deque
 from contextlib import closing
@@ -295,13 +296,26 @@ class EngineCounter(DeviceState):
         return self.ctx.frame_change(self._device(frames), area, edge_thresh, self._state, reset)
 
 
+class EngineFocus(DeviceState):
+    """focus_fn of the selectors on the GPU (Context.frame_focus): keeps the device state of the last area between calls."""
+
+    def __call__(self, frames, area, edge_thresh, reset):
+        y0, y1, x0, x1 = area
+        reset = self._fresh((y1 - y0, x1 - x0), self.ctx.frame_change_state) or reset
+        return self.ctx.frame_focus(self._device(frames), area, edge_thresh, self._state, reset)
+
+
 class _IntervalSelector:
     """The body ChangeFrameSelector and HoldFrameSelector share: frames -> band_batches -> staging.staged_batches -> count_fn ->
     IntervalTracker.  A selector says which engine callable is its default count_fn, what the tracker's min_frames is (`_min_frames`),
-    how count_fn is called per batch (`_count`) and what follows the last batch (`_flush`)."""
+    how count_fn is called per batch (`_count`) and what follows the last batch (`_flush`).
+    focus_fn(frames [n,h,w,3] uint8, area, edge_thresh, reset) -> [n,2] kept, focus per frame (vse_frame_focus; it carries the last
+    frame's mask to the next call): when given, it is called once per batch on the same staged data as count_fn, with reset on the
+    first batch, and its rows are appended to `focus`, int64 [frames fed, 2], readable while iterating.  Focus rows belong to the
+    frames fed: they do not trail like the hold selector's counts.  None: no call, and `focus` is not touched."""
 
-    def __init__(self, count_fn=None, edge_thresh=128, change_ratio=0.5, min_edges=None, min_frames=2, batch=64):
-        self.count_fn = count_fn
+    def __init__(self, count_fn=None, edge_thresh=128, change_ratio=0.5, min_edges=None, min_frames=2, batch=64, focus_fn=None):
+        self.count_fn, self.focus_fn = count_fn, focus_fn
         self.edge_thresh, self.change_ratio, self.min_edges, self.min_frames = edge_thresh, change_ratio, min_edges, min_frames
         self.batch = batch
         self.counts = None
@@ -328,6 +342,8 @@ class _IntervalSelector:
             self.count_fn = self.engine_count_fn(shim._context())
         min_frames = self._min_frames(fps)
         self.counts, self.intervals, self.tracker = np.zeros((0, 3), np.int32), [], None
+        if self.focus_fn is not None:
+            self.focus = np.zeros((0, 2), np.int64)
         bands = band_batches(frames, sub_area, self.batch, type(self).__name__)
         if bands.area is None:
             return
@@ -341,9 +357,19 @@ class _IntervalSelector:
             return closed
 
         out, fed, data = [], 0, None
+        room = np.zeros((0, 2), np.int64)
         with closing(staging.staged_batches(bands, uploader)) as staged:
             for items, data in staged:
-                closed = feed(self._count(data, bands.area, fed))
+                counts = self._count(data, bands.area, fed)
+                if self.focus_fn is not None:             # (launched before the counts are read back: one wait for both)
+                    rows = self.focus_fn(data, bands.area, self.edge_thresh, fed == 0)
+                closed = feed(counts)
+                if self.focus_fn is not None:
+                    rows = np.asarray(rows.cpu() if hasattr(rows, "cpu") else rows, np.int64).reshape(-1, 2)
+                    if fed + len(rows) > len(room):           # `focus` is a view of `room`, which doubles when it is full
+                        room = np.concatenate([room[:fed], np.zeros((max(len(room), len(rows), 1024), 2), np.int64)])
+                    room[fed:fed + len(rows)] = rows
+                    self.focus = room[:fed + len(rows)]
                 fed += len(items)
                 yield items, closed
         closed = feed(self._flush(data, bands.area, fed))
@@ -418,8 +444,8 @@ class HoldFrameSelector(_IntervalSelector):
     engine_count_fn = EngineHoldCounter
 
     def __init__(self, count_fn=None, hold_seconds=0.3, hold_frames=None, edge_thresh=128, change_ratio=0.5, min_edges=None,
-                 min_frames=2, batch=64):
-        super().__init__(count_fn, edge_thresh, change_ratio, min_edges, min_frames, batch)
+                 min_frames=2, batch=64, focus_fn=None):
+        super().__init__(count_fn, edge_thresh, change_ratio, min_edges, min_frames, batch, focus_fn)
         self.hold_seconds, self.hold_frames = hold_seconds, hold_frames
         self.hold = None              # the hold of the last run, in frames
 
@@ -446,6 +472,17 @@ def trim_range(start, end, fps, trim_seconds):
     tr = min(round(trim_seconds * fps), (end - start) // 2), so at least one frame always remains."""
     tr = min(int(round(trim_seconds * fps)), (end - start) // 2)
     return start + tr, end - tr
+
+
+def sharpest_rep(start, end, focus, fps, trim_seconds=0.25):
+    """The frame on which the interval start..end (1-based, inclusive) is recognised with interval_frame="sharpest": among the frames
+    trim_range(start, end, fps, trim_seconds) leaves (fades at either end are left out as the compositor leaves them out; an interval
+    shorter than twice the trim keeps its middle) the one with the largest focus, the earliest of equals, hence the first candidate
+    when every focus is 0.  focus: per frame of the clip, row no - 1 for frame no: [frames, 2] kept, focus (a selector's `focus`), or
+    the focus column alone."""
+    first, last = trim_range(start, end, fps, trim_seconds)
+    col = [int(r[1]) if hasattr(r, "__len__") else int(r) for r in focus[first - 1:last]]
+    return first + max(range(len(col)), key=lambda i: (col[i], -i))
 
 
 class EngineCompositor(DeviceState):
