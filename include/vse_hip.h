@@ -342,8 +342,10 @@ int vse_frame_cells_multi(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int
  * many frames and a moving background's do not, so here only HELD edges are counted; the host runs the unchanged interval automaton
  * on the counts (vse_amd.frame_select.HoldFrameSelector).  Not VideoSubFinder's algorithm; `hold` and the behaviour on real footage
  * are not measured here (no real clips).  Known limit: background edges that stay on one pixel for `hold` frames still count (a
- * static busy shot, a pan along an edge's own direction); they can add intervals between subtitles, which cost OCR calls and lose
- * no subtitle.
+ * static busy shot, a pan along an edge's own direction).  While the background moves they only add intervals between subtitles,
+ * which cost OCR calls; once it stands still for as long as subtitles come and go they sit in the denominator of the host's cut ratio
+ * and in neither numerator, and a subtitle that vanishes or is replaced over more static edges than its own is merged with its
+ * neighbour and lost: vse_frame_hold_bounded below is for that footage.
  * Frames of a clip are numbered 1..T; E_t = the edge pixels of the area's interior in frame t exactly as defined for
  * vse_frame_change.  H_u, the held mask of frame u: pixel p is in H_u when p is in E_u and the maximal run of consecutive frames
  * containing u in which p is an edge pixel is at least `hold` frames long; runs are cut off at frame 1 and, once `flush` is given,
@@ -363,6 +365,33 @@ size_t vse_frame_hold_state_bytes(int area_h, int area_w, int hold);
 int vse_frame_hold(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride,
                    int y0, int y1, int x0, int x1, int edge_thresh, int hold, void* d_state, int64_t fed, int flush,
                    int32_t* d_counts /* [n + hold - 1, 3]: held edges, appeared, vanished */, void* stream);
+
+/* ---- held-edge frame selector with bounded runs ------------------------------------------------------------------------- */
+/* Replaces: nothing in the reference; vse_frame_hold for footage whose background also stands still.  A subtitle's edges hold for at
+ * least `hold` frames and at most some seconds; a channel logo's, a watermark's and a long static shot's hold far longer.  With E_t and
+ * the maximal runs of consecutive edge frames per pixel as defined for vse_frame_hold (cut off at frame 1 and, once `flush` is given,
+ * at the clip's last frame), B_u, the bounded mask of frame u: pixel p is in B_u when p is in E_u and the run containing u is L frames
+ * long with hold <= L <= max_hold.  B_0 is empty.  The row of frame u is |B_u|, |B_u \ B_{u-1}|, |B_{u-1} \ B_u|; max_hold >= the
+ * clip's length gives vse_frame_hold's rows.  Membership is per whole run: a run that grows beyond max_hold leaves every frame it
+ * covered, so a row is final only once max_hold further frames have been seen.  Known limits: a subtitle shown for more than max_hold
+ * frames disappears with the rest; a static shot shorter than max_hold still dilutes the host's cut ratio as before; pixels that
+ * flicker around the threshold on a static background make short runs that count and can add intervals in the gaps (OCR calls, no
+ * subtitle lost).  max_hold and the behaviour on real footage are not measured here (no real clips).
+ * Size in bytes of the caller-owned state (8-byte aligned): one run length per pixel, and the rows still pending, max_hold + 64 of
+ * them; 0 below 3 x 3 or for max_hold outside 1..4000.  A state belongs to one area size and one max_hold; its layout is the
+ * library's. */
+size_t vse_frame_hold_bounded_state_bytes(int area_h, int area_w, int max_hold);
+/* Frames, area, `fed`, `flush` and state as for vse_frame_hold: n >= 0 frames, the next of a clip of which `fed` went to earlier calls;
+ * fed == 0 starts a clip and the state's content is then ignored.  The call writes, from row 0 of d_counts on, the rows of the frames
+ * max(0, fed - max_hold) + 1 .. max(0, fed + n - max_hold), and with `flush` (the clip ends with this call) up to fed + n; d_counts has
+ * room for n + max_hold rows.  n == 0 with `flush` only drains the pending rows.  A clip fed in batches of any sizes, smaller or
+ * larger than max_hold, gives the rows of one call.  Launches on `stream` only (per 64 frames the walk over the tiles and one wave
+ * that finishes the rows), no allocation, no device sync; a block owns its 8 x 64 interior pixels and alone reads and writes their run
+ * lengths, and the pending rows are integer atomics, so the order of the blocks cannot change them.  Returns VSE_E_INVAL, without
+ * touching the device, for everything vse_frame_hold refuses, max_hold < hold or max_hold > 4000. */
+int vse_frame_hold_bounded(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride,
+                           int y0, int y1, int x0, int x1, int edge_thresh, int hold, int max_hold, void* d_state, int64_t fed,
+                           int flush, int32_t* d_counts /* [n + max_hold, 3]: bounded edges, appeared, vanished */, void* stream);
 
 /* ---- locator and calibration on held edges ------------------------------------------------------------------------------ */
 /* Replaces: nothing in the reference; it serves vse_frame_hold's footage.  vse_frame_cells and vse_frame_cells_multi run the cell

@@ -26,6 +26,10 @@
 //
 // Sharpness of the edges that stand still (vse_frame_focus): the same tiles, mask and state as vse_frame_change, but per frame the
 // number of edge pixels that were edge pixels one frame earlier and the sum of their gradients (frame_focus_kernel below).
+//
+// Held-edge selector with bounded runs (vse_frame_hold_bounded): frame_hold_kernel's tiles, mask and walk, but only edge pixels whose run
+// is hold .. max_hold frames long are counted, so that the edges of a background that stands still drop out too (frame_hold_bounded_kernel
+// and frame_hold_rows_kernel, at the end of the file).
 #include "common.h"
 
 namespace {
@@ -819,5 +823,153 @@ int vse_frame_cells_hold_launch(const void* d_bgr, int n, int steps, int64_t pit
     }
 #undef VSE_CELLS_HOLD
     static_assert(FC_WAVES == 8, "one instantiation per number of thresholds");
+    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+}
+
+// ---- vse_frame_hold_bounded -----------------------------------------------------------------------------------------------------
+// B_u = the edge pixels of frame u whose run of consecutive edge frames is L frames long with hold <= L <= max_hold: vse_frame_hold's
+// held edges without those that hold for too long (a logo, a static shot).  Membership is per whole run, so nothing is counted until a
+// run ends, and then everything about it is known: a run s..t in range is in B_s .. B_t, appears at s and vanishes at t + 1.  Per row
+// that is a difference array, a[s] += 1 and v[t + 1] += 1, with |B_u| = |B_{u-1}| + a[u] - v[u].
+//
+// The tile, its mask words and the walk are frame_hold_kernel's: wave k walks interior row k along the steps with lane = column.  Per
+// pixel one run length, saturating at max_hold + 1 (a run that long is out whatever follows).  At a step u where runs end in range the
+// wave counts them with one ballot (v[u], gathered with lane = step and summed over the tile's rows in LDS: one atomic per step and
+// block) and adds to a[u - L] once per distinct length L among the ending lanes, the lanes of one length found by a ballot each: a
+// subtitle's pixels start and end together, so that loop runs once where it matters.
+// The pending rows live in a ring in the caller's state, a and v per slot, row r in slot r % ring; integer atomics, so the order the
+// blocks arrive in cannot change them.  A launch covers at most FC_CHUNK steps, which with the max_hold rows a run can reach back bounds
+// the rows in flight: ring = max_hold + FC_CHUNK slots.  A flush is ONE step without an edge: every open run ends there.
+// frame_hold_rows_kernel, one wave behind each such launch on the same stream, turns the rows that can no longer change into counts (a
+// running sum of a - v whose carry stays in the state), writes them and clears their slots.
+// State: int32 [4] (the carry |B| of the last row written, then padding), the ring int32 [ring][2], then one uint16 run length per
+// pixel of the tile words laid out as frame_hold_kernel's.  A clip's first call clears carry and ring and ignores the run lengths.
+namespace {
+
+constexpr int HB_HEAD_BYTES = 16;
+
+// n frames, then steps - n steps without an edge (the flush), steps <= FC_CHUNK; slot0 = the ring slot of the first step's frame.
+__global__ __launch_bounds__(FC_WAVES * 64) void frame_hold_bounded_kernel(const uint8_t* __restrict__ src, int n, int steps, long pitch,
+                                                                           long fstride, int x0, int ih, int iw, int wpr, int thresh, int hold,
+                                                                           int max_hold, int slot0, int ring_slots,
+                                                                           unsigned short* __restrict__ state, int fresh, int* __restrict__ ring) {
+    __shared__ unsigned long long msk[FC_CHUNK][FC_ROWS];
+    static_assert(FC_WAVES == FC_ROWS, "wave k walks interior row k of the tile");
+    static_assert(FC_CHUNK == 64, "the steps of a launch are the lanes of a wave");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int w = blockIdx.x, iy0 = blockIdx.y * FC_ROWS;
+    const TileLane t = tile_lane(w, iy0, ih, iw, x0);
+    const bool mine = wave < t.rows;           // wave-uniform; the words of the other rows stay zero
+    unsigned short* st = state + ((long)(iy0 + wave) * wpr + w) * 64 + lane;
+    int run = (mine && !fresh) ? (int)*st : 0;
+
+    tile_masks(src + (long)iy0 * pitch, 0, n, pitch, fstride, t, thresh, msk);
+    for (int i = n * FC_ROWS + threadIdx.x; i < steps * FC_ROWS; i += FC_WAVES * 64) msk[i / FC_ROWS][i % FC_ROWS] = 0ull;
+    __syncthreads();
+    if (mine) {
+        // lane = step for the words going in and the counts going out, lane = column for the walk
+        const unsigned long long col = lane < steps ? msk[lane][wave] : 0ull;
+        const int lo = (int)(unsigned)col, hi = (int)(unsigned)(col >> 32);
+        int ended = 0;                         // runs of this row that ended in range at step `lane`
+        int slot = slot0;                      // ring slot of this step's frame
+        for (int tl = 0; tl < steps; ++tl) {
+            const unsigned half = (unsigned)(lane < 32 ? __builtin_amdgcn_readlane(lo, tl) : __builtin_amdgcn_readlane(hi, tl));
+            const bool edge = (half >> (lane & 31)) & 1u;
+            const int len = run;
+            run = edge ? min(run + 1, max_hold + 1) : 0;
+            const bool ends = !edge && len >= hold && len <= max_hold;
+            unsigned long long m = __ballot(ends);
+            if (m) {                           // wave-uniform
+                if (lane == tl) ended = __popcll(m);
+                do {
+                    const int l = __builtin_amdgcn_readlane(len, __ffsll((long long)m) - 1);
+                    const unsigned long long same = __ballot(ends && len == l);
+                    int s = slot - l;          // the run's first frame: 1 <= l <= max_hold < ring_slots
+                    if (s < 0) s += ring_slots;
+                    if (lane == 0) atomicAdd(ring + 2 * s, __popcll(same));
+                    m &= ~same;
+                } while (m);
+            }
+            slot = slot + 1 == ring_slots ? 0 : slot + 1;
+        }
+        if (lane < steps) msk[lane][wave] = (unsigned long long)ended;
+        *st = (unsigned short)run;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < steps) {
+        int v = 0;
+#pragma unroll
+        for (int k = 0; k < FC_ROWS; ++k) v += (int)msk[threadIdx.x][k];       // words of rows outside the area are zero
+        int s = slot0 + (int)threadIdx.x;      // < 2 * ring_slots: steps <= FC_CHUNK < ring_slots
+        if (s >= ring_slots) s -= ring_slots;
+        if (v) atomicAdd(ring + 2 * s + 1, v);
+    }
+}
+
+// One wave: the `rows` rows from ring slot `slot` on (rows <= ring_slots) -> out [rows][3] = |B|, appeared, vanished; their slots cleared.
+__global__ __launch_bounds__(64) void frame_hold_rows_kernel(int* __restrict__ ring, int* __restrict__ carry, int ring_slots, int slot, int rows,
+                                                             int* __restrict__ out) {
+    const int lane = threadIdx.x;
+    int e = *carry;
+    for (int base = 0; base < rows; base += 64) {
+        const int i = base + lane;
+        const bool live = i < rows;
+        int s = slot + i;
+        if (s >= ring_slots) s -= ring_slots;
+        const int a = live ? ring[2 * s] : 0, v = live ? ring[2 * s + 1] : 0;
+        int d = a - v;                         // inclusive scan over the lanes
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int up = __shfl_up(d, o);
+            if (lane >= o) d += up;
+        }
+        if (live) {
+            out[(long)i * 3] = e + d;
+            out[(long)i * 3 + 1] = a;
+            out[(long)i * 3 + 2] = v;
+            ring[2 * s] = 0;
+            ring[2 * s + 1] = 0;
+        }
+        e += __shfl(d, 63);
+    }
+    if (lane == 0) *carry = e;
+}
+
+}  // namespace
+
+size_t vse_frame_hold_bounded_bytes(int ih, int iw, int max_hold) {
+    return HB_HEAD_BYTES + (size_t)(max_hold + FC_CHUNK) * 2 * sizeof(int32_t) + (size_t)ih * ((iw + 63) / 64) * HOLD_WORD_BYTES;
+}
+
+// Called by vse_frame_hold_bounded (vse_runtime.hip) after it has checked the arguments (1 <= hold <= max_hold, n + flush >= 1).  The call
+// is worked through in pieces of FC_CHUNK steps, each a launch of the walk and, where it completes rows, one of the finishing kernel.
+int vse_frame_hold_bounded_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
+                                  int hold, int max_hold, void* d_state, int64_t fed, int flush, int32_t* d_counts, void* stream) {
+    const int ih = y1 - y0 - 2, iw = x1 - x0 - 2, wpr = (iw + 63) / 64;
+    const int ring_slots = max_hold + FC_CHUNK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    int* carry = reinterpret_cast<int*>(d_state);
+    int* ring = reinterpret_cast<int*>(reinterpret_cast<char*>(d_state) + HB_HEAD_BYTES);
+    unsigned short* pix = reinterpret_cast<unsigned short*>(ring + 2 * (size_t)ring_slots);
+    if (fed == 0 && hipMemsetAsync(d_state, 0, HB_HEAD_BYTES + (size_t)ring_slots * 2 * sizeof(int32_t), st) != hipSuccess) return VSE_E_HIP;
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
+    const int64_t first = fed > max_hold ? fed - max_hold : 0;         // rows up to this frame went out with earlier calls
+    int64_t written = first;
+    const int64_t total = (int64_t)n + (flush ? 1 : 0);
+    for (int64_t at = 0; at < total; at += FC_CHUNK) {
+        const int steps = (int)(total - at < FC_CHUNK ? total - at : FC_CHUNK);
+        const int frames = (int)(n - at < steps ? n - at : steps);
+        const int64_t done = fed + at + frames;                        // frames of the clip seen after this piece
+        hipLaunchKernelGGL(frame_hold_bounded_kernel, dim3(wpr, (ih + FC_ROWS - 1) / FC_ROWS), dim3(FC_WAVES * 64), 0, st,
+                           src + at * frame_stride, frames, steps, (long)pitch, (long)frame_stride, x0, ih, iw, wpr, edge_thresh, hold, max_hold,
+                           (int)((fed + at + 1) % ring_slots), ring_slots, pix, fed == 0 && at == 0, ring);
+        // a row is final once max_hold further frames have been seen: a run that still covers it is then too long
+        const int64_t upto = (flush && at + steps == total) ? done : (done > max_hold ? done - max_hold : 0);
+        if (upto > written) {                                          // at most max_hold + FC_CHUNK - 1 rows, the flush's
+            hipLaunchKernelGGL(frame_hold_rows_kernel, dim3(1), dim3(64), 0, st, ring, carry, ring_slots, (int)((written + 1) % ring_slots),
+                               (int)(upto - written), reinterpret_cast<int*>(d_counts) + (written - first) * 3);
+            written = upto;
+        }
+    }
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }

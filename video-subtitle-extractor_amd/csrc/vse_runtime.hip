@@ -65,6 +65,9 @@ int vse_frame_cells_multi_launch(const void* d_bgr, int n, int64_t pitch, int64_
 size_t vse_frame_hold_word_bytes();                                                                                    // frame_change.hip
 int vse_frame_hold_launch(const void* d_bgr, int n, int steps, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
                           int edge_thresh, int hold, int skip, void* d_state, int fresh, int32_t* d_counts, void* stream);   // frame_change.hip
+size_t vse_frame_hold_bounded_bytes(int ih, int iw, int max_hold);                                                       // frame_change.hip
+int vse_frame_hold_bounded_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
+                                  int hold, int max_hold, void* d_state, int64_t fed, int flush, int32_t* d_counts, void* stream);
 size_t vse_frame_cells_hold_bytes(int ih, int iw, int nt);                                                               // frame_change.hip
 int vse_frame_cells_hold_launch(const void* d_bgr, int n, int steps, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
                                 const int* thresholds, int nt, int hold, int skip, int min_edges, int ratio_num, int ratio_den, int min_frames,
@@ -568,6 +571,37 @@ int vse_frame_hold(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, i
     const int rc = vse_frame_hold_launch(d_bgr, n, (int)steps, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, hold, skip, d_state,
                                          fed == 0, d_counts, stream);
     if (rc != VSE_OK) set_err("vse_frame_hold: launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+// ---- held-edge frame selector with bounded runs (frame_change.hip) -------------------------------------------------------------
+constexpr int FRAME_HOLD_BOUNDED_MAX = 4000;       // the per-pixel run length is a uint16 and the ring of pending rows stays small
+
+size_t vse_frame_hold_bounded_state_bytes(int area_h, int area_w, int max_hold) {
+    if (area_h < 3 || area_w < 3 || max_hold < 1 || max_hold > FRAME_HOLD_BOUNDED_MAX) return 0;
+    return vse_frame_hold_bounded_bytes(area_h - 2, area_w - 2, max_hold);
+}
+
+int vse_frame_hold_bounded(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0, int y1,
+                           int x0, int x1, int edge_thresh, int hold, int max_hold, void* d_state, int64_t fed, int flush, int32_t* d_counts,
+                           void* stream) {
+    if (!check_frames("vse_frame_hold_bounded", c && fed >= 0, d_bgr, n, 0, src_h, src_w, pitch, frame_stride, d_state) ||
+        !check_area("vse_frame_hold_bounded", "area", y0, y1, x0, x1, src_h, src_w))
+        return VSE_E_INVAL;
+    if (hold < 1 || hold > 32 || max_hold < hold || max_hold > FRAME_HOLD_BOUNDED_MAX) {
+        set_err("vse_frame_hold_bounded: hold %d outside 1..32, or max_hold %d outside hold..%d", hold, max_hold, FRAME_HOLD_BOUNDED_MAX);
+        return VSE_E_INVAL;
+    }
+    if (n == 0 && !flush) return VSE_OK;
+    // the row of a frame is final max_hold frames later, or at the flush
+    const int64_t rows = (flush ? fed + n : std::max<int64_t>(0, fed + n - max_hold)) - std::max<int64_t>(0, fed - max_hold);
+    if (n == INT32_MAX || (rows > 0 && !d_counts)) {
+        set_err("vse_frame_hold_bounded: %lld rows need d_counts, and n + 1 must fit an int", (long long)rows);
+        return VSE_E_INVAL;
+    }
+    const int rc = vse_frame_hold_bounded_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, hold, max_hold, d_state, fed,
+                                                 flush != 0, d_counts, stream);
+    if (rc != VSE_OK) set_err("vse_frame_hold_bounded: launch failed: %s", hipGetErrorString(hipGetLastError()));
     return rc;
 }
 

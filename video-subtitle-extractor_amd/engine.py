@@ -28,6 +28,7 @@ EXPORTS = [
     "vse_audio_stream_length", "vse_audio_stream_workspace_bytes", "vse_audio_stream_feed", "vse_audio_stream_finish", "vse_ctc_fuse",
     "vse_yuv_to_bgr_matrix", "vse_frame_cells_multi_state_bytes", "vse_frame_cells_multi",
     "vse_frame_cells_hold_state_bytes", "vse_frame_cells_hold", "vse_frame_focus",
+    "vse_frame_hold_bounded_state_bytes", "vse_frame_hold_bounded",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -179,6 +180,10 @@ def load_library(path=None):
     lib.vse_frame_hold_state_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.vse_frame_hold.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
+    lib.vse_frame_hold_bounded_state_bytes.restype = C.c_size_t
+    lib.vse_frame_hold_bounded_state_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.vse_frame_hold_bounded.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
     lib.vse_frame_cells_hold_state_bytes.restype = C.c_size_t
     lib.vse_frame_cells_hold_state_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.vse_frame_cells_hold.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
@@ -611,6 +616,34 @@ class Context:
                                        fed, int(bool(flush)), C.c_void_p(out.data_ptr()), self.stream()), "vse_frame_hold")
         return out[:rows]
 
+    # ---- held-edge frame selector with bounded runs -----------------------------------------------------------------
+    def frame_hold_bounded_state(self, area_h, area_w, max_hold):
+        """A fresh (zero-filled) state for frame_hold_bounded over an area of area_h x area_w pixels with this `max_hold`."""
+        nbytes = self.lib.vse_frame_hold_bounded_state_bytes(int(area_h), int(area_w), int(max_hold))
+        if not nbytes:
+            raise VseError(f"frame_hold_bounded: an area of {area_h} x {area_w} pixels has no interior, or max_hold {max_hold} is "
+                           f"outside 1..{FRAME_HOLD_BOUNDED_MAX}")
+        return self.torch.zeros(nbytes, dtype=self.torch.uint8, device=self.tdev)
+
+    def frame_hold_bounded(self, frames_u8, area, edge_thresh, hold, max_hold, state, fed, flush=False):
+        """frame_hold counting only the edge pixels whose run is hold .. max_hold frames long: frames_u8, area, hold, fed and flush as
+        there, state: frame_hold_bounded_state of the area's size and `max_hold` -> cuda int32 [rows,3]: bounded edges, appeared,
+        vanished of the frames whose row this call completes, which trail the frames fed by max_hold until `flush` (include/vse_hip.h
+        vse_frame_hold_bounded)."""
+        t = self.torch
+        frames = self._frames_args(frames_u8, allow_empty=True)
+        n = frames[1]
+        y0, y1, x0, x1 = (int(v) for v in area)
+        hold, max_hold, fed = int(hold), int(max_hold), int(fed)
+        nbytes = self.lib.vse_frame_hold_bounded_state_bytes(y1 - y0, x1 - x0, max_hold)
+        assert nbytes and state.dtype == t.uint8 and state.is_contiguous() and state.numel() >= nbytes
+        rows = (fed + n if flush else max(0, fed + n - max_hold)) - max(0, fed - max_hold)
+        out = t.empty((n + max_hold, 3), dtype=t.int32, device=self.tdev)
+        _check(self.lib.vse_frame_hold_bounded(self.handle, *frames, y0, y1, x0, x1, int(edge_thresh), hold, max_hold,
+                                               C.c_void_p(state.data_ptr()), fed, int(bool(flush)), C.c_void_p(out.data_ptr()),
+                                               self.stream()), "vse_frame_hold_bounded")
+        return out[:rows]
+
     # ---- locator and calibration on held edges ---------------------------------------------------------------------
     def frame_cells_hold_state(self, area_h, area_w, nt, hold):
         """A fresh CellsState (zero-filled) for frame_cells_hold over a region of area_h x area_w pixels with nt thresholds and this
@@ -832,6 +865,7 @@ YUV_LAYOUTS = {"i420": 0, "nv12": 1}
 YUV_MATRICES = {"bt601": 0, "bt709": 1}
 INTERVAL_MODES = {"min": 0, "max": 1, "mean": 2}
 INTERVAL_RANK_MAX = 63          # VSE_INTERVAL_RANK_MAX (include/vse_hip.h): the frames of one vse_interval_rank call
+FRAME_HOLD_BOUNDED_MAX = 4000   # the largest max_hold of vse_frame_hold_bounded (include/vse_hip.h)
 
 
 def _audio_queries(queries):

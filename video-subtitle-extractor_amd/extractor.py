@@ -247,7 +247,13 @@ class SubtitleExtractor:
     frame_selector="hold" is the change selector for footage whose background moves behind the subtitle: only edges that hold still
     for a while are counted (frame_select.HoldFrameSelector, `change_params` its keyword arguments, `change_counter` its count_fn);
     everything that follows "change" below follows "hold" the same way.  Its default hold of 0.3 s and its behaviour on real footage
-    are not measured here; background edges that stand still that long still count and can add intervals, never lose one.
+    are not measured here; background edges that stand still that long still count: while the background moves they can add intervals,
+    never lose one, but over a static busy shot, a logo or a watermark they dilute the cut ratio and subtitles are merged and lost.
+    change_params={"max_hold_seconds": 12} (or "max_hold_frames"; frame_selector="hold" only) is for that footage: only edges that
+    hold for hold .. max_hold frames are counted, so what stands still for longer than a subtitle does drops out
+    (frame_select.HoldFrameSelector has the limits: a subtitle shown for longer than that disappears too, and 12-15 s is a guess).  The
+    selector's rows then trail its frames by max_hold, so one pass keeps about max_hold more frames (360 frames of 1080p 4:2:0 at 15 s
+    and 24 fps are 1.1 GB; `retain_bytes` stays the fallback).  The locator and the calibration (`area_params`) ignore it.
     interval_image="min" | "max" | "mean" (change selector only; default "middle", the above): one recognition error on that single
     frame is final, so the recogniser is instead shown, inside the area of the same middle frame, the per-pixel minimum (light
     text) / maximum (dark text) / mean of ALL frames of the interval, one more pass over the area's rows on the device
@@ -672,6 +678,9 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
     p.add_argument("--selector", default="fps", choices=("fps", "change", "hold"), help="which frames go to OCR [fps]")
     p.add_argument("--edge-thresh", default="128", metavar="auto|N", help="change / hold selector: the luma gradient that makes an edge "
                    "pixel, or `auto` to choose it for this clip first (not in one pass) [128]")
+    p.add_argument("--max-hold-seconds", type=float, default=None, metavar="S", help="--selector hold: count only edges that hold still for "
+                   "at most S seconds, so a static busy background, a logo or a watermark drops out; a subtitle shown for longer drops out "
+                   "too, and one pass keeps S seconds more of frames [none: no bound]")
     p.add_argument("--locator-automaton", default="change", choices=("change", "hold"), help="what `--area auto` and `--edge-thresh auto` "
                    "count: every edge pixel, or with `hold` only edges that hold still (a textured background that moves) [change]")
     p.add_argument("--interval-image", default="middle", choices=INTERVAL_IMAGES, help="change / hold selector: what the recogniser is "
@@ -704,6 +713,11 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
         area = None if args.area is None else _parse_area(args.area)
         from .area_locator import parse_edge_thresh
         edge_thresh = parse_edge_thresh(args.edge_thresh)
+        change_params = {} if edge_thresh == 128 else {"edge_thresh": edge_thresh}
+        if args.max_hold_seconds is not None:
+            if args.selector != "hold":
+                raise ValueError(f"--max-hold-seconds bounds the runs of `--selector hold`, not of `--selector {args.selector}`")
+            change_params["max_hold_seconds"] = args.max_hold_seconds
         composite_params = None
         if args.interval_image == "quantile":
             composite_params = {"quantile": args.quantile, "samples": args.interval_samples, "rank_fn": composite_fn}
@@ -724,7 +738,7 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
                                retain_bytes=int(args.retain_gib * (1 << 30)), interval_image=args.interval_image,
                                composite_params=composite_params, interval_frame=args.interval_frame,
                                frame_params=None if focus_fn is None else {"focus_fn": focus_fn},
-                               change_params=None if edge_thresh == 128 else {"edge_thresh": edge_thresh},
+                               change_params=change_params or None,
                                area_params={**({} if cells_fn is None else {"cells_fn": cells_fn}),
                                             **({} if args.locator_automaton == "change" else {"automaton": args.locator_automaton})} or None)
         text = ex.run()

@@ -23,7 +23,7 @@ from contextlib import closing
 from itertools import islice
 
 from . import staging
-from .engine import INTERVAL_RANK_MAX, DeviceState
+from .engine import FRAME_HOLD_BOUNDED_MAX, INTERVAL_RANK_MAX, DeviceState
 from .shim import get_coordinates
 
 
@@ -333,8 +333,8 @@ class _IntervalSelector:
         """run() as a generator: per staged batch (items, the intervals its rows closed), items = [(full frame, its area rows)] in
         decode order, so a caller that may need a frame again receives it with the batch itself; after the last batch one more
         ([], what the flushed rows and the end of the clip closed).  `tracker` (IntervalTracker) is in step with what has been
-        yielded: `tracker.fed` is the last frame whose row has been seen (the hold selector's rows trail its frames by hold - 1 until
-        the flush, and the frames behind it are still the caller's to keep); `intervals` grows as they close, `counts` is set when
+        yielded: `tracker.fed` is the last frame whose row has been seen (the hold selector's rows trail its frames by hold - 1, or with max_hold_*
+        by max_hold, until the flush, and the frames behind it are still the caller's to keep); `intervals` grows as they close, `counts` is set when
         the generator is exhausted."""
         import numpy as np
         if self.count_fn is None:
@@ -426,6 +426,25 @@ class EngineHoldCounter(DeviceState):
         return self.ctx.frame_hold(self._device(frames), area, edge_thresh, hold, self._state, fed, flush)
 
 
+class EngineBoundedHoldCounter(DeviceState):
+    """count_fn of HoldFrameSelector with max_hold_* on the GPU (Context.frame_hold_bounded): keeps the device state of the last area and
+    `max_hold`, and the number of frames of the clip fed so far, between calls."""
+    fed = 0
+    _hold = None
+
+    def __call__(self, frames, area, edge_thresh, hold, max_hold, fed, flush):
+        y0, y1, x0, x1 = area
+        key = (y1 - y0, x1 - x0, max_hold)
+        if fed and (self._key, self._hold) != (key, hold):
+            raise ValueError(f"EngineBoundedHoldCounter: the area, hold or max_hold changed to {key + (hold,)} after {fed} frames of a clip")
+        self._fresh(key, self.ctx.frame_hold_bounded_state)
+        self._hold = hold
+        if fed and fed != self.fed:
+            raise ValueError(f"EngineBoundedHoldCounter: fed {fed}, but {self.fed} frames of this clip went to earlier calls")
+        self.fed = fed + len(frames)
+        return self.ctx.frame_hold_bounded(self._device(frames), area, edge_thresh, hold, max_hold, self._state, fed, flush)
+
+
 class HoldFrameSelector(_IntervalSelector):
     """ChangeFrameSelector for footage whose background moves behind the subtitle.  The change selector compares every edge pixel of the
     area with the frame before; a textured background that pans puts hundreds of edge pixels into the band that all move every
@@ -435,32 +454,57 @@ class HoldFrameSelector(_IntervalSelector):
     `hold_frames`, or max(1, min(32, round(hold_seconds * fps))) when it is None; hold_seconds=0.3 and the behaviour on real footage
     are not measured here (no real clips).  Known limit: background edges that stay on one pixel for `hold` frames still count (a
     static busy shot, a pan along an edge's own direction: in a numpy prototype a horizontal pan at hold 2-5 added intervals in the
-    gaps); such intervals cost OCR calls and lose no subtitle.  run / iter_run: _IntervalSelector's, with fps; after the last batch a
-    call without frames flushes the rows still pending.
+    gaps).  While the background moves such intervals cost OCR calls and lose no subtitle; over a background that STANDS STILL they do
+    lose subtitles: its edges sit in the denominator of the automaton's cut ratio and in neither numerator, so once they outnumber the
+    text's own edges a subtitle that vanishes or is replaced makes no cut and is merged with its neighbour (a logo or watermark in the
+    band does the same in a milder form, and keeps every gap frame present).  `max_hold_seconds` / `max_hold_frames` are for that
+    footage: only runs of hold .. max_hold frames are counted (vse_frame_hold_bounded), a subtitle's edges holding for some seconds at
+    most and a logo's or a static shot's far longer.  Both None (the default): the path above, call for call.  Otherwise max_hold =
+    max_hold_frames, or round(max_hold_seconds * fps) when that is None; below hold or above 4000 is a ValueError.  Its limits: a
+    subtitle shown for longer than max_hold disappears with the background; a static shot shorter than max_hold dilutes the ratio as
+    before; pixels that flicker around the threshold make short runs and can add intervals in the gaps (OCR calls, no subtitle lost);
+    the rows then trail the frames by max_hold instead of hold - 1, which is what one pass keeps (360 frames of 1080p 4:2:0 at 15 s
+    and 24 fps are 1.1 GB).  12-15 s is a guess: nothing here is measured on real footage.
+    run / iter_run: _IntervalSelector's, with fps; after the last batch a call without frames flushes the rows still pending.
 
     count_fn(frames [n,h,w,3] uint8, area (y0, y1, x0, x1) in their pixels, edge_thresh, hold, fed, flush) -> [rows,3] counts of the
     frames whose held mask the call completes: they trail the frames fed by hold - 1 until the flush (fed: frames of the clip given
-    to earlier calls, 0 on the first batch; flush: the clip ends with this call).  Default: EngineHoldCounter on the shim's device."""
+    to earlier calls, 0 on the first batch; flush: the clip ends with this call).  Default: EngineHoldCounter on the shim's device.
+    With max_hold_*: count_fn(frames, area, edge_thresh, hold, max_hold, fed, flush), whose rows trail by max_hold.  Default:
+    EngineBoundedHoldCounter."""
     engine_count_fn = EngineHoldCounter
 
     def __init__(self, count_fn=None, hold_seconds=0.3, hold_frames=None, edge_thresh=128, change_ratio=0.5, min_edges=None,
-                 min_frames=2, batch=64, focus_fn=None):
+                 min_frames=2, batch=64, focus_fn=None, max_hold_seconds=None, max_hold_frames=None):
         super().__init__(count_fn, edge_thresh, change_ratio, min_edges, min_frames, batch, focus_fn)
         self.hold_seconds, self.hold_frames = hold_seconds, hold_frames
+        self.max_hold_seconds, self.max_hold_frames = max_hold_seconds, max_hold_frames
+        if max_hold_seconds is not None or max_hold_frames is not None:
+            self.engine_count_fn = EngineBoundedHoldCounter
         self.hold = None              # the hold of the last run, in frames
+        self.max_hold = None          # ... and its max_hold; None: runs are not bounded
 
     def _min_frames(self, fps):
         hold = self.hold_frames if self.hold_frames is not None else max(1, min(32, int(round(self.hold_seconds * fps))))
         if not 1 <= hold <= 32:
             raise ValueError(f"HoldFrameSelector: hold_frames must be 1..32, not {hold}")
         self.hold = hold
+        self.max_hold = None
+        if self.max_hold_frames is not None or self.max_hold_seconds is not None:
+            max_hold = int(self.max_hold_frames if self.max_hold_frames is not None else round(self.max_hold_seconds * fps))
+            if not hold <= max_hold <= FRAME_HOLD_BOUNDED_MAX:
+                raise ValueError(f"HoldFrameSelector: max_hold must be hold ({hold}) .. {FRAME_HOLD_BOUNDED_MAX} frames, not {max_hold}")
+            self.max_hold = max_hold
         return max(self.min_frames, hold)                  # (hold_intervals' min_frames)
 
+    def _args(self):
+        return (self.hold,) if self.max_hold is None else (self.hold, self.max_hold)
+
     def _count(self, data, area, fed):
-        return self.count_fn(data, area, self.edge_thresh, self.hold, fed, False)
+        return self.count_fn(data, area, self.edge_thresh, *self._args(), fed, False)
 
     def _flush(self, data, area, fed):
-        return self.count_fn(data[:0], area, self.edge_thresh, self.hold, fed, True)
+        return self.count_fn(data[:0], area, self.edge_thresh, *self._args(), fed, True)
 
 
 # ---- interval composite (one picture per interval of the change selector) ------------------------------------------------
