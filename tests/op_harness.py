@@ -3,7 +3,8 @@ CPU emulator (run_emulator), and hold the result to a plain fp64 reference of th
 
 A plain helper module like tests/parity.py (no fixtures, no pytest settings).  It has four parts (and, at the end, the same four for
 OP_CONV: conv_op, conv_pack — the compiler's own static packers —, conv_name — the library's own answer, vse_op_kernel_name —, ref_conv and
-conv_reference; the cases are tests/conv_cases.py):
+conv_reference; the cases are tests/conv_cases.py — and for OP_CHAIN: chain_stage, chain_op, chain_form, ref_chain, ref_shuffle, with the
+compiler's static chains.chain_plan / chain_pack as the packer; the cases are tests/chain_cases.py):
 
   * builders for ir.VIEW_DT / ir.OP_DT records (the fields follow the comments of ir.py and the checks at the top of each `case` of
     launch_simple_op, csrc/simple_ops.hip), and a weight blob with the compiler's 256-byte alignment;
@@ -630,3 +631,92 @@ def conv_reference(fn):
     r64, e_lib = reference(lambda dt: fn(dt, False))
     _, e_seq = reference(lambda dt: fn(dt, True) if dt == np.float32 else tuple(r64) if len(r64) > 1 else r64[0])
     return r64, tuple(max(a, b) for a, b in zip(e_lib, e_seq))
+
+
+# ---------------------------------------------------------------------------------------------------------------- OP_CHAIN
+# One chain record = one launch of chain_kernel or chain_pw2_kernel (csrc/chain.hip).  The blob comes from the compiler's own static
+# planner and packer (chains.chain_plan / chains.chain_pack); the record's p[] slots follow ChainMixin._chain_emit and the comment
+# above launch_chain.  The cases are tests/chain_cases.py.
+def chain_stage(kind, cin, cout, k=1, s=1, act=ir.ACT_NONE, act_a=0.0, act_b=0.0, post_a=1.0, post_b=0.0, res=-1, act2=ir.ACT_NONE,
+                gout=-1, shuf=0, wname=None, bias=None):
+    """A stage as chains.chain_plan / chain_pack read it: kind "pw" (1x1, stride 1) or "dw" (k x k depthwise, 'same' padding, stride s);
+    res = index of the channel-minor buffer the residual comes from (0 = the chain input, j + 1 = the output of stage j); gout = which
+    global output the stage stores (-1: none); bias fp32 [cout] (the epilogue's shift; its scale is 1: the weights come folded)."""
+    assert kind in ("pw", "dw") and (kind == "pw" or cin == cout)
+    ep = dict(act=act, act_a=act_a, act_b=act_b, post_a=post_a, post_b=post_b, act2=act2, scale=np.ones(cout, np.float64),
+              shift=np.zeros(cout, np.float32) if bias is None else np.asarray(bias, np.float32))
+    return dict(type=kind, k=k, s=s, cin=cin, cout=cout, wname=wname, ep=ep, res_buf=res, res_abs=res, gout=gout, shuf=shuf)
+
+
+def chain_op(in0, out, tiles, lds_total, nstages, img_bytes, w_off, out2=None, out3=None, pw2=0, lo_in=0, lo_out=(0, 0, 0), wl=(0, 0)):
+    """The OP_CHAIN record.  tiles = (tiles_h, tiles_w) of the last stage's output; lds_total = the dynamic LDS bytes of the plan;
+    img_bytes = bytes of the blob's LDS image; out3 (the third stored output) rides in the in2 slot; lo_in / lo_out[g] = channel offset of
+    the lo half of a hi + lo pair input / output g (0 = plain fp16)."""
+    return op(ir.OP_CHAIN, [in0, None, out3], out, out2=out2, w_off=w_off, wl=wl,
+              p={ir.P_CH_TILES_H: tiles[0], ir.P_CH_TILES_W: tiles[1], ir.P_CH_LDS: lds_total, ir.P_CH_NSTAGES: nstages,
+                 ir.P_CH_NBUFS: nstages + 1, ir.P_CH_PW2: pw2, ir.P_CH_IMG: img_bytes, ir.P_CH_LO_IN: lo_in,
+                 ir.P_CH_LO_OUT0: lo_out[0], ir.P_CH_LO_OUT1: lo_out[1], ir.P_CH_LO_OUT2: lo_out[2]})
+
+
+def chain_form(r):
+    """("pw2", blocks) | ("generic", blocks per CU): the conditions of launch_chain, restated (vse_op_kernel_name answers "chain_kernel" for
+    every OP_CHAIN record).  chain_pw2_kernel: P_CH_PW2, two stages, an LDS image of at most 64 KiB, at most 64 input channels."""
+    r = r[0] if r.ndim else r
+    p = r["p"]
+    if int(p[ir.P_CH_PW2]) == 1 and int(p[ir.P_CH_NSTAGES]) == 2 and 0 < int(p[ir.P_CH_IMG]) <= 64 * 1024 and int(r["in0"]["c"]) <= 64:
+        return "pw2", (int(r["in0"]["n"]) * int(r["in0"]["h"]) * int(r["in0"]["w"]) + 255) // 256
+    return "generic", max(1, min(3, (160 * 1024) // (int(p[ir.P_CH_LDS]) + 2048)))
+
+
+def chain_grid(r, n_cu):
+    """Blocks launch_chain starts for a record of the generic kernel on a device of n_cu compute units, and the tiles they share."""
+    r = r[0] if r.ndim else r
+    tiles = int(r["in0"]["n"]) * int(r["p"][ir.P_CH_TILES_H]) * int(r["p"][ir.P_CH_TILES_W])
+    grid = min(tiles, n_cu * chain_form(r)[1])
+    return (grid & ~7 if grid > 8 else grid), tiles
+
+
+def pair64(v):
+    """What an fp16 hi + lo pair keeps of a value, in float64 (the kernel splits the fp32 value: hi = fp16(v), lo = fp16(v - hi))."""
+    v = np.asarray(v, np.float64)
+    hi = v.astype(np.float16).astype(np.float64)
+    return hi + (v - hi).astype(np.float16).astype(np.float64)
+
+
+def ref_chain_stage(bufs, st, dt):
+    """One stage on the list of buffers so far ([n,h,w,c] arrays of dtype dt; buffer 0 = the chain input).  st: a chain_stage dict with
+    st["w_ref"] = the weights the kernel sees (1x1: float64 [cout][cin] = f16(w) + f16(w - f16(w)); depthwise: fp32 [k * k][c]) and the
+    fp32 bias st["ep"]["shift"]."""
+    ep, x = st["ep"], bufs[-1]
+    f32 = lambda v: dt(np.float32(v))          # noqa: E731
+    if st["type"] == "pw":
+        y = np.matmul(x, np.asarray(st["w_ref"]).astype(dt).T) + ep["shift"].astype(dt)
+        y = ref_act(y, ep["act"], ep["act_a"], ep["act_b"]) * f32(ep["post_a"]) + f32(ep["post_b"])
+    else:
+        k, s = st["k"], st["s"]
+        y = ref_dwconv(x, st["w_ref"], ep["shift"], (k, k), (s, s), (k // 2, k // 2), ep["act"], ep["act_a"], ep["act_b"], ep["post_a"],
+                       ep["post_b"], dt=dt)
+    if st["res_buf"] >= 0:
+        y = ref_act(y + bufs[st["res_buf"]], ep["act2"])
+    assert y.dtype == dt
+    return y
+
+
+def ref_chain(x, stages, dt=np.float64, pair=False):
+    """The whole chain, plainly: no tiles, no emulator.  x [n,h,w,c] float64 (a pair input: hi + lo summed).  Nothing is rounded between
+    the stages — unless pair: then every channel-minor intermediate (a stage output a 1x1 stage reads) passes through the hi + lo
+    rounding of the kernel's LDS buffers (evaluated in float64: the term e_pair of the bound).  -> [x, y_1, .., y_n]."""
+    bufs = [np.asarray(x).astype(dt)]
+    for j, st in enumerate(stages):
+        y = ref_chain_stage(bufs, st, dt)
+        if pair and j + 1 < len(stages) and stages[j + 1]["type"] == "pw":
+            y = pair64(y).astype(dt)
+        bufs.append(y)
+    return bufs
+
+
+def ref_shuffle(y):
+    """The pixel-shuffle store of a 16-channel stage: channel 4 r + c of input pixel (y, x) -> pixel (4 y + r, 4 x + c) of [n,4h,4w,1]."""
+    n, h, w, c = y.shape
+    assert c == 16
+    return y.reshape(n, h, w, 4, 4).transpose(0, 1, 3, 2, 4).reshape(n, 4 * h, 4 * w, 1)

@@ -15,6 +15,9 @@ Host side of the design (this file):
   * LDS plan: weight image first, then the stage buffers placed first-fit by liveness; the tile size is the largest one whose
     plan fits the budget of two blocks per CU (falls back to one);
   * the blob: descriptor words + LDS image (MFMA weight fragments in lane order, hi and lo passes; depthwise weight records).
+
+The planner and the packer are the module-level chain_plan / chain_pack: pure functions of a stage list, so that a test can plan and pack a
+chain of its own (a forced tile, a stage pattern no graph produces) without a Compiler (tests/chain_cases.py).
 """
 import struct
 
@@ -86,6 +89,164 @@ def regions_backward(stages, th, tw):
                    "Tw": cur["Tw"] * s, "aw": cur["aw"] * s + p, "Ew": (cur["Ew"] - 1) * s + k}
         regs[j] = dict(cur)
     return regs
+
+
+def chain_plan(stages, H, W, in_lo, tiles=CHAIN_TILES):
+    """Pick the tile (among `tiles`: a test forces one) and place the LDS buffers.  Writes nks / nct / w_lds / b_lds into the stages.
+    -> plan dict or None when nothing fits."""
+    n = len(stages)
+    # image size at every buffer's resolution
+    dims = [(H, W)]
+    for st in stages:
+        h, w = dims[-1]
+        if st["type"] == "dw" and st["s"] == 2:
+            h, w = (h + 2 * (st["k"] // 2) - st["k"]) // 2 + 1, (w + 2 * (st["k"] // 2) - st["k"]) // 2 + 1
+        dims.append((h, w))
+    # weights image
+    wbytes = 0
+    for st in stages:
+        if st["type"] == "pw":
+            st["nks"], st["nct"] = rup(st["cin"], 16) // 16, rup(st["cout"], 32) // 32
+            st["w_lds"] = wbytes
+            wbytes += 2 * st["nct"] * st["nks"] * 1024
+            st["b_lds"] = wbytes
+            wbytes += st["nct"] * 32 * 4
+        else:
+            st["w_lds"] = wbytes                      # per-channel records [k*k weights, bias, padding] of 12 / 28 floats
+            wbytes += st["cin"] * dw_rec(st["k"]) * 4
+    wbytes = rup(wbytes, 16)
+    # buffer kinds: buffer j feeds stage j (j < n); kind follows the consumer; the last stage has no LDS output
+    best = None
+    oh, ow = dims[-1]
+    for th, tw in tiles:
+        if th > rup(oh, 2) * 2 and (th, tw) != CHAIN_TILES[-1]:
+            continue
+        regs = regions_backward(stages, th, tw)
+        bufs = []
+        for j in range(n):
+            r = regs[j]
+            P = r["Eh"] * r["Ew"]
+            c = stages[j]["cin"]
+            if stages[j]["type"] == "pw":
+                cp = rup(c, 16)
+                stride = 2 * cp + 16
+                lo = in_lo if j == 0 else True
+                size = P * stride * (2 if lo else 1)
+                bufs.append(dict(kind=0, C=c, Cp=cp, stride=stride, P=P, lo=lo, size=rup(size, 16), reg=r, dims=dims[j]))
+            else:
+                stride = rup(P, 32)
+                bufs.append(dict(kind=1, C=c, Cp=c, stride=stride, P=P, lo=False, size=rup(c * stride * 4, 16), reg=r, dims=dims[j]))
+        # liveness: buffer j is written by stage j - 1 (input load = -1), read by stage j and by any residual reader
+        last = list(range(n))
+        for j, st in enumerate(stages):
+            if st["res_buf"] >= 0:
+                last[st["res_buf"]] = max(last[st["res_buf"]], j)
+        placed, total = [], wbytes
+        order = sorted(range(n), key=lambda j: (j - 1, -bufs[j]["size"]))
+        for j in order:
+            first_, last_ = j - 1, last[j]
+            off = wbytes
+            for (po, ps, pf, pl) in sorted(placed):
+                if pl < first_ or pf > last_:
+                    continue
+                if off + bufs[j]["size"] <= po:
+                    break
+                off = max(off, po + ps)
+            bufs[j]["off"] = off
+            placed.append((off, bufs[j]["size"], first_, last_))
+            total = max(total, off + bufs[j]["size"])
+        if total > CHAIN_LDS_1:
+            continue
+        # cost: estimated shader cycles of one tile per owned output pixel, from the s_memtime traces of the kernel (tools/
+        # trace_chain.sh): ~2.4 k per tile (input store, turn-over), ~0.6 k per stage (descriptor, barrier), a PW item (32 pixels x
+        # 32 couts) ~3 k + 0.6 k per 16-deep K slice, a DW item (64 pixels x 8 channels) ~0.7 k + 0.21 k per tap; four waves share
+        # the items of a stage; one block per CU instead of two costs its latency hiding
+        cyc = CHAIN_TILE_CYC
+        for j, st in enumerate(stages):
+            rp = regs[j + 1]["Eh"] * regs[j + 1]["Ew"]
+            if st["type"] == "pw":
+                items, per = -(-rp // 32) * st["nct"], 3000.0 + 600.0 * st["nks"]
+            else:
+                items, per = -(-rp // 64) * (st["cin"] // 8), 700.0 + 210.0 * st["k"] ** 2
+            cyc += CHAIN_STAGE_CYC + -(-items // 4) * per
+        blocks_cu = min(CHAIN_BLOCKS_CU, (160 * 1024) // (total + 2048))         # 146 VGPRs: three 4-wave blocks per CU at most
+        cost = cyc / float(th * tw) * {1: CHAIN_ONE_BLOCK, 2: CHAIN_TWO_BLOCKS}.get(blocks_cu, 1.0)
+        if best is None or cost < best["cost"]:
+            best = dict(cost=cost, th=th, tw=tw, regs=regs, bufs=[dict(b) for b in bufs], lds_total=total, wbytes=wbytes, dims=dims)
+    return best
+
+
+def chain_pack(stages, plan, weights):
+    """The blob of a planned chain: descriptor words (header, buffers, stages) + the LDS image (MFMA fragments and biases of the 1x1
+    stages, per-channel records of the depthwise stages).  stages: as chain_plan left them, each with its epilogue `ep`, `gout`, `res_buf`
+    and `wname`; weights: name -> array ([cout][cin][1][1] / [c][1][k][k]).  -> (blob uint8, bytes of the LDS image, meta per stage,
+    multiply-adds per image)."""
+    n = len(stages)
+    bufs, regs, dims = plan["bufs"], plan["regs"], plan["dims"]
+    oh, ow = dims[-1]
+    tiles_h, tiles_w = -(-oh // plan["th"]), -(-ow // plan["tw"])
+    hdr = np.zeros(ir.CH_HDR, np.int32)
+    hdr[[ir.CHH_MAGIC, ir.CHH_NSTAGES, ir.CHH_NBUFS, ir.CHH_LDSW_BYTES, ir.CHH_LDS_TOTAL, ir.CHH_TH, ir.CHH_TW, ir.CHH_TILES_H,
+         ir.CHH_TILES_W]] = [ir.CH_MAGIC, n, n + 1, plan["wbytes"], plan["lds_total"], plan["th"], plan["tw"], tiles_h, tiles_w]
+    bw = np.zeros((n + 1, ir.CH_BUF), np.int32)
+    # buffer n = the REGION of the last stage's output (kind 2: it is stored to global memory only; the kernel needs its tile
+    # geometry all the same — a depthwise last stage indexes its output pixels by it)
+    rl = regs[n]
+    bw[n, :15] = [2, 0, -1, stages[-1]["cout"], stages[-1]["cout"], 0, rl["Th"], rl["ah"], rl["Eh"], rl["Tw"], rl["aw"], rl["Ew"],
+                  rl["Eh"] * rl["Ew"], dims[n][0], dims[n][1]]
+    for j, b in enumerate(bufs):
+        r = b["reg"]
+        bw[j, :15] = [b["kind"], b["off"], (b["off"] + b["size"] // 2) if b["lo"] else -1, b["C"], b["Cp"], b["stride"],
+                      r["Th"], r["ah"], r["Eh"], r["Tw"], r["aw"], r["Ew"], b["P"], b["dims"][0], b["dims"][1]]
+    sw = np.zeros((n, ir.CH_STAGE), np.int32)
+    lds_img = np.zeros(plan["wbytes"], np.uint8)
+    meta = []
+    macs = 0.0
+    for j, st in enumerate(stages):
+        ep = st["ep"]
+        w = np.asarray(weights[st["wname"]]).astype(np.float64)
+        row = sw[j]
+        is_pw = st["type"] == "pw"
+        nxt_dw = j + 1 < n and stages[j + 1]["type"] == "dw"
+        row[[ir.CHS_TYPE, ir.CHS_IN, ir.CHS_OUT, ir.CHS_RES, ir.CHS_CIN, ir.CHS_COUT, ir.CHS_K, ir.CHS_S, ir.CHS_PAD, ir.CHS_ACT,
+             ir.CHS_GOUT, ir.CHS_MASK, ir.CHS_ACT2]] = [ir.CH_PW if is_pw else ir.CH_DW, j, j + 1, st["res_buf"],
+                                                        st["cin"], st["cout"], st["k"], st["s"], st["k"] // 2, ep["act"],
+                                                        st["gout"], 1 if nxt_dw else 0, ep["act2"]]
+        row[ir.CHS_SHUF] = int(st.get("shuf", 0))
+        row[ir.CHS_ACT_A], row[ir.CHS_ACT_B] = f2i(ep["act_a"]), f2i(ep["act_b"])
+        row[ir.CHS_POST_A], row[ir.CHS_POST_B] = f2i(ep["post_a"]), f2i(ep["post_b"])
+        h_out, w_out = dims[j + 1]
+        if is_pw:
+            mat = np.zeros((st["nct"] * 32, st["nks"] * 16), np.float64)
+            mat[:st["cout"], :st["cin"]] = w[:, :, 0, 0] * ep["scale"].reshape(-1, 1)
+            frags = pw_fragments(mat)
+            lds_img[st["w_lds"]:st["w_lds"] + frags.nbytes] = frags.reshape(-1).view(np.uint8)
+            bias = np.zeros(st["nct"] * 32, np.float32)
+            bias[:st["cout"]] = ep["shift"]
+            lds_img[st["b_lds"]:st["b_lds"] + bias.nbytes] = bias.view(np.uint8)
+            row[[ir.CHS_NKS, ir.CHS_NCT, ir.CHS_WLDS, ir.CHS_BLDS, ir.CHS_HASLO]] = [st["nks"], st["nct"], st["w_lds"], st["b_lds"],
+                                                                                       1 if bufs[j]["lo"] else 0]
+            macs += h_out * w_out * st["cin"] * st["cout"]
+            meta.append(dict(type="pw", w=mat[:st["cout"], :st["cin"]].copy(), b=np.asarray(ep["shift"], np.float64).copy()))
+        else:
+            k2 = st["k"] ** 2
+            wk = (w[:, 0] * ep["scale"].reshape(-1, 1, 1)).reshape(st["cin"], k2).astype(np.float32)
+            bk = np.asarray(ep["shift"], np.float32)
+            rec = np.zeros((st["cin"], dw_rec(st["k"])), np.float32)
+            rec[:, :k2] = wk
+            rec[:, k2] = bk
+            lds_img[st["w_lds"]:st["w_lds"] + rec.nbytes] = rec.reshape(-1).view(np.uint8)
+            row[ir.CHS_WLDS] = st["w_lds"]
+            macs += h_out * w_out * st["cin"] * k2
+            meta.append(dict(type="dw", w=wk.astype(np.float64).reshape(st["cin"], st["k"], st["k"]), b=bk.astype(np.float64)))
+    words = np.concatenate([hdr, bw.reshape(-1), sw.reshape(-1)])
+    img_off = rup(words.nbytes, 16)
+    hdr[ir.CHH_LDSIMG_OFF] = img_off
+    words = np.concatenate([hdr, bw.reshape(-1), sw.reshape(-1)])
+    blob = np.zeros(img_off + lds_img.nbytes, np.uint8)
+    blob[:words.nbytes] = words.view(np.uint8)
+    blob[img_off:] = lds_img
+    return blob, int(lds_img.nbytes), meta, macs
 
 
 class ChainMixin:
@@ -167,87 +328,7 @@ class ChainMixin:
         return stages
 
     def _chain_plan(self, stages, H, W, in_lo):
-        """Pick the tile and place the LDS buffers.  -> plan dict or None when nothing fits."""
-        n = len(stages)
-        # image size at every buffer's resolution
-        dims = [(H, W)]
-        for st in stages:
-            h, w = dims[-1]
-            if st["type"] == "dw" and st["s"] == 2:
-                h, w = (h + 2 * (st["k"] // 2) - st["k"]) // 2 + 1, (w + 2 * (st["k"] // 2) - st["k"]) // 2 + 1
-            dims.append((h, w))
-        # weights image
-        wbytes = 0
-        for st in stages:
-            if st["type"] == "pw":
-                st["nks"], st["nct"] = rup(st["cin"], 16) // 16, rup(st["cout"], 32) // 32
-                st["w_lds"] = wbytes
-                wbytes += 2 * st["nct"] * st["nks"] * 1024
-                st["b_lds"] = wbytes
-                wbytes += st["nct"] * 32 * 4
-            else:
-                st["w_lds"] = wbytes                      # per-channel records [k*k weights, bias, padding] of 12 / 28 floats
-                wbytes += st["cin"] * dw_rec(st["k"]) * 4
-        wbytes = rup(wbytes, 16)
-        # buffer kinds: buffer j feeds stage j (j < n); kind follows the consumer; the last stage has no LDS output
-        best = None
-        oh, ow = dims[-1]
-        for th, tw in CHAIN_TILES:
-            if th > rup(oh, 2) * 2 and (th, tw) != CHAIN_TILES[-1]:
-                continue
-            regs = regions_backward(stages, th, tw)
-            bufs = []
-            for j in range(n):
-                r = regs[j]
-                P = r["Eh"] * r["Ew"]
-                c = stages[j]["cin"]
-                if stages[j]["type"] == "pw":
-                    cp = rup(c, 16)
-                    stride = 2 * cp + 16
-                    lo = in_lo if j == 0 else True
-                    size = P * stride * (2 if lo else 1)
-                    bufs.append(dict(kind=0, C=c, Cp=cp, stride=stride, P=P, lo=lo, size=rup(size, 16), reg=r, dims=dims[j]))
-                else:
-                    stride = rup(P, 32)
-                    bufs.append(dict(kind=1, C=c, Cp=c, stride=stride, P=P, lo=False, size=rup(c * stride * 4, 16), reg=r, dims=dims[j]))
-            # liveness: buffer j is written by stage j - 1 (input load = -1), read by stage j and by any residual reader
-            last = list(range(n))
-            for j, st in enumerate(stages):
-                if st["res_buf"] >= 0:
-                    last[st["res_buf"]] = max(last[st["res_buf"]], j)
-            placed, total = [], wbytes
-            order = sorted(range(n), key=lambda j: (j - 1, -bufs[j]["size"]))
-            for j in order:
-                first_, last_ = j - 1, last[j]
-                off = wbytes
-                for (po, ps, pf, pl) in sorted(placed):
-                    if pl < first_ or pf > last_:
-                        continue
-                    if off + bufs[j]["size"] <= po:
-                        break
-                    off = max(off, po + ps)
-                bufs[j]["off"] = off
-                placed.append((off, bufs[j]["size"], first_, last_))
-                total = max(total, off + bufs[j]["size"])
-            if total > CHAIN_LDS_1:
-                continue
-            # cost: estimated shader cycles of one tile per owned output pixel, from the s_memtime traces of the kernel (tools/
-            # trace_chain.sh): ~2.4 k per tile (input store, turn-over), ~0.6 k per stage (descriptor, barrier), a PW item (32 pixels x
-            # 32 couts) ~3 k + 0.6 k per 16-deep K slice, a DW item (64 pixels x 8 channels) ~0.7 k + 0.21 k per tap; four waves share
-            # the items of a stage; one block per CU instead of two costs its latency hiding
-            cyc = CHAIN_TILE_CYC
-            for j, st in enumerate(stages):
-                rp = regs[j + 1]["Eh"] * regs[j + 1]["Ew"]
-                if st["type"] == "pw":
-                    items, per = -(-rp // 32) * st["nct"], 3000.0 + 600.0 * st["nks"]
-                else:
-                    items, per = -(-rp // 64) * (st["cin"] // 8), 700.0 + 210.0 * st["k"] ** 2
-                cyc += CHAIN_STAGE_CYC + -(-items // 4) * per
-            blocks_cu = min(CHAIN_BLOCKS_CU, (160 * 1024) // (total + 2048))         # 146 VGPRs: three 4-wave blocks per CU at most
-            cost = cyc / float(th * tw) * {1: CHAIN_ONE_BLOCK, 2: CHAIN_TWO_BLOCKS}.get(blocks_cu, 1.0)
-            if best is None or cost < best["cost"]:
-                best = dict(cost=cost, th=th, tw=tw, regs=regs, bufs=[dict(b) for b in bufs], lds_total=total, wbytes=wbytes, dims=dims)
-        return best
+        return chain_plan(stages, H, W, in_lo)
 
     def _chain_gouts(self, stages, inside):
         """Which stage outputs some op outside the chain still reads (the last one always is stored)."""
@@ -425,71 +506,12 @@ class ChainMixin:
 
     def _chain_emit(self, stages, plan, inv, gouts, map_out=False, macs_override=None):
         n = len(stages)
-        bufs, regs, dims = plan["bufs"], plan["regs"], plan["dims"]
+        bufs, dims = plan["bufs"], plan["dims"]
         N = inv.n
         oh, ow = dims[-1]
         tiles_h, tiles_w = -(-oh // plan["th"]), -(-ow // plan["tw"])
-        hdr = np.zeros(ir.CH_HDR, np.int32)
-        hdr[[ir.CHH_MAGIC, ir.CHH_NSTAGES, ir.CHH_NBUFS, ir.CHH_LDSW_BYTES, ir.CHH_LDS_TOTAL, ir.CHH_TH, ir.CHH_TW, ir.CHH_TILES_H,
-             ir.CHH_TILES_W]] = [ir.CH_MAGIC, n, n + 1, plan["wbytes"], plan["lds_total"], plan["th"], plan["tw"], tiles_h, tiles_w]
-        bw = np.zeros((n + 1, ir.CH_BUF), np.int32)
-        # buffer n = the REGION of the last stage's output (kind 2: it is stored to global memory only; the kernel needs its tile
-        # geometry all the same — a depthwise last stage indexes its output pixels by it)
-        rl = regs[n]
-        bw[n, :15] = [2, 0, -1, stages[-1]["cout"], stages[-1]["cout"], 0, rl["Th"], rl["ah"], rl["Eh"], rl["Tw"], rl["aw"], rl["Ew"],
-                      rl["Eh"] * rl["Ew"], dims[n][0], dims[n][1]]
-        for j, b in enumerate(bufs):
-            r = b["reg"]
-            bw[j, :15] = [b["kind"], b["off"], (b["off"] + b["size"] // 2) if b["lo"] else -1, b["C"], b["Cp"], b["stride"],
-                          r["Th"], r["ah"], r["Eh"], r["Tw"], r["aw"], r["Ew"], b["P"], b["dims"][0], b["dims"][1]]
-        sw = np.zeros((n, ir.CH_STAGE), np.int32)
-        lds_img = np.zeros(plan["wbytes"], np.uint8)
-        meta = []
-        macs = 0.0
-        for j, st in enumerate(stages):
-            ep = st["ep"]
-            w = self.W[st["wname"]].astype(np.float64)
-            row = sw[j]
-            is_pw = st["type"] == "pw"
-            nxt_dw = j + 1 < n and stages[j + 1]["type"] == "dw"
-            row[[ir.CHS_TYPE, ir.CHS_IN, ir.CHS_OUT, ir.CHS_RES, ir.CHS_CIN, ir.CHS_COUT, ir.CHS_K, ir.CHS_S, ir.CHS_PAD, ir.CHS_ACT,
-                 ir.CHS_GOUT, ir.CHS_MASK, ir.CHS_ACT2]] = [ir.CH_PW if is_pw else ir.CH_DW, j, j + 1, st["res_buf"],
-                                                            st["cin"], st["cout"], st["k"], st["s"], st["k"] // 2, ep["act"],
-                                                            st["gout"], 1 if nxt_dw else 0, ep["act2"]]
-            row[ir.CHS_SHUF] = int(st.get("shuf", 0))
-            row[ir.CHS_ACT_A], row[ir.CHS_ACT_B] = f2i(ep["act_a"]), f2i(ep["act_b"])
-            row[ir.CHS_POST_A], row[ir.CHS_POST_B] = f2i(ep["post_a"]), f2i(ep["post_b"])
-            h_out, w_out = dims[j + 1]
-            if is_pw:
-                mat = np.zeros((st["nct"] * 32, st["nks"] * 16), np.float64)
-                mat[:st["cout"], :st["cin"]] = w[:, :, 0, 0] * ep["scale"].reshape(-1, 1)
-                frags = pw_fragments(mat)
-                lds_img[st["w_lds"]:st["w_lds"] + frags.nbytes] = frags.reshape(-1).view(np.uint8)
-                bias = np.zeros(st["nct"] * 32, np.float32)
-                bias[:st["cout"]] = ep["shift"]
-                lds_img[st["b_lds"]:st["b_lds"] + bias.nbytes] = bias.view(np.uint8)
-                row[[ir.CHS_NKS, ir.CHS_NCT, ir.CHS_WLDS, ir.CHS_BLDS, ir.CHS_HASLO]] = [st["nks"], st["nct"], st["w_lds"], st["b_lds"],
-                                                                                           1 if bufs[j]["lo"] else 0]
-                macs += N * h_out * w_out * st["cin"] * st["cout"]
-                meta.append(dict(type="pw", w=mat[:st["cout"], :st["cin"]].copy(), b=np.asarray(ep["shift"], np.float64).copy()))
-            else:
-                k2 = st["k"] ** 2
-                wk = (w[:, 0] * ep["scale"].reshape(-1, 1, 1)).reshape(st["cin"], k2).astype(np.float32)
-                bk = np.asarray(ep["shift"], np.float32)
-                rec = np.zeros((st["cin"], dw_rec(st["k"])), np.float32)
-                rec[:, :k2] = wk
-                rec[:, k2] = bk
-                lds_img[st["w_lds"]:st["w_lds"] + rec.nbytes] = rec.reshape(-1).view(np.uint8)
-                row[ir.CHS_WLDS] = st["w_lds"]
-                macs += N * h_out * w_out * st["cin"] * k2
-                meta.append(dict(type="dw", w=wk.astype(np.float64).reshape(st["cin"], st["k"], st["k"]), b=bk.astype(np.float64)))
-        words = np.concatenate([hdr, bw.reshape(-1), sw.reshape(-1)])
-        img_off = rup(words.nbytes, 16)
-        hdr[ir.CHH_LDSIMG_OFF] = img_off
-        words = np.concatenate([hdr, bw.reshape(-1), sw.reshape(-1)])
-        blob = np.zeros(img_off + lds_img.nbytes, np.uint8)
-        blob[:words.nbytes] = words.view(np.uint8)
-        blob[img_off:] = lds_img
+        blob, img_bytes, meta, macs = chain_pack(stages, plan, self.W)
+        macs *= N
         # outputs
         outs = []
         for g, j in enumerate(gouts):
@@ -514,7 +536,7 @@ class ChainMixin:
                                                              ir.P_CH_NSTAGES: n, ir.P_CH_NBUFS: n + 1,
                                                              ir.P_CH_PW2: int(bool(map_out and n == 2 and all(st["type"] == "pw" for st in stages)
                                                                                    and stages[0]["cin"] <= 64 and stages[1]["cout"] <= 32)),
-                                                             ir.P_CH_IMG: int(lds_img.nbytes),
+                                                             ir.P_CH_IMG: img_bytes,
                                                              ir.P_CH_LO_IN: int(getattr(inv.buf, "lo_off", 0) or 0),
                                                              ir.P_CH_LO_OUT0: outs[0].buf.lo_off,
                                                              ir.P_CH_LO_OUT1: outs[1].buf.lo_off if len(outs) > 1 else 0,
