@@ -178,3 +178,7 @@ int launch_lstm_mfma(const TView& gf, const TView& gr, const TView& out, const h
 int launch_chain(const vse_op& op, const TView& in0, const TView& out, const TView& out2, const TView& out3, const char* wbase, hipStream_t st);
 int launch_simple_op(const vse_op& op, const TView& in0, const TView& in1, const TView& in2, const TView& out,
                      const TView& out2, const char* wbase, const int* wl_in, const int* wl_out, hipStream_t st);
+// the finish pass of an OP_GAP alone, over the first `slots` of the `splits` partial sums per image: for a conv that summed them itself
+int launch_gap_finish(const float* part, const TView& in0, const TView& out, int splits, int slots, hipStream_t st);
+// OP_SCALE + the OP_BINARY add behind it as one pass (scale_add_select): x * gate, rounded to fp16, + res -> activation -> out
+int launch_scale_add(const TView& x, const TView& gate, const TView& res, const TView& out, int act, hipStream_t st);

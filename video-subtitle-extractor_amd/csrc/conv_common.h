@@ -59,6 +59,11 @@ struct ConvParams {
     unsigned pack_mag_ow, pack_mag_d;    // conv_pack_magic(OW), conv_pack_magic(W + pw); 0 when pack_g == 1 (every quotient is 0)
     // conv_c3pool_kernel: a block walks pool_seg tile rows of one column strip, pool_nseg strips cover the map's tiles_h.  Set by the launcher.
     int pool_seg, pool_nseg;
+    // conv_gemm_kernel with the global-average pool behind it (conv_gap_select): != nullptr: M tiles are aligned to images (hw_img, tiles_img
+    // as for F_IMGW) and every block adds the column sums of the fp16 values it stores into slot (tile of the image) % gap_splits of
+    // gap_part[image][slot][gap_c] (fp32); gap_atomic: an image has more tiles than slots, the buffer was zeroed and the blocks add atomically.
+    float* gap_part;
+    int gap_splits, gap_c, gap_atomic;
 };
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
@@ -426,6 +431,28 @@ int launch_conv(const vse_op& o, const TView& in, const TView& res, const TView&
 ConvKernel conv_pool_select(const vse_op* ops, int n_ops, int i);
 int launch_conv_pool(const vse_op& conv, const ConvKernel& k, const TView& in, const TView& pool_out, const char* wts, const half_t* zero,
                      hipStream_t st);
+// A 1x1 conv of conv_gemm_kernel's unmasked form whose output feeds the global-average pool record behind it sums the pool's partials in
+// its own epilogue (conv_gemm.hip): the pool's pass over the tensor is not run, only its gap_finish_kernel.  conv_gap_select() answers
+// from the plan's records alone whether ops[i], ops[i + 1] are such a pair; vse_plan_create asks once per plan.  The partials go to the
+// pool's scratch view (in2) unless the compiler laid that over the conv's own input or output: then to `part_off`, bytes of the workspace
+// that are dead while the pair runs (the output of a later record that nothing touches before that record overwrites it).
+struct ConvGap {
+    int fused;          // 0: two launches, as the records say
+    int bm;             // row tile of the conv's configuration
+    int tiles_img;      // M tiles per image
+    int slots;          // slots gap_finish_kernel adds: min(splits, tiles_img)
+    int atomic;         // an image has more tiles than slots (at most twice as many): zero the partial buffer in front of the conv
+    int64_t part_off;   // workspace offset of the partial buffer [n][splits][c] fp32
+    int64_t part_bytes;
+};
+ConvGap conv_gap_select(const vse_op* ops, int n_ops, int i);
+// launch_conv for such a pair: `part` = the resolved partial buffer
+int launch_conv_gap(const vse_op& o, const ConvGap& g, const TView& in, const TView& out, const char* wts, const half_t* zero, float* part,
+                    int splits, hipStream_t st);
+// An SE gate multiply (OP_SCALE) directly followed by the residual add (OP_BINARY) that reads its product runs as one pass
+// (scale_add_kernel, simple_ops.hip) when the product is dead behind the add: 0 = two launches, 1 / 2 = fused, the add's in1 / in0 is
+// the residual.  Decided per plan like the pairs above; ragged plans included (element-wise: no summation order is involved).
+int scale_add_select(const vse_op* ops, int n_ops, int i);
 // images of a launch (M = images x OH x OW)
 static inline long conv_images(const ConvParams& p) { return p.OH && p.OW ? p.M / ((long)p.OH * p.OW) : 0; }
 // Images per virtual row band for TW-wide tiles whose patch has `spare` unused columns and a `gap` of zero columns between images:

@@ -13,6 +13,8 @@
 //   * BK = 64 configurations fetch whole 128-byte lines per row (one wave instruction = 8 rows x 128 B) and tiles of
 //     256 pixels x 128/256 couts raise the flops per fetched byte over the 128 x 128 x 32 tile of conv_mfma_kernel.
 //   * the ring is unrolled by stage, so every ds_read_b128 is `per-thread VGPR + immediate`.
+//   * the unmasked form can take the column sums of what it stores for the global-average pool record behind it (gap_part, a runtime
+//     branch of the epilogue; conv_gap_select in conv_select.hip decides per plan): that pool's pass over the tensor is then not run.
 //
 // Eligibility and the tile configuration (kCfg, conv_common.h) are decided by conv_select(); everything else stays on conv_mfma_kernel.
 
@@ -32,6 +34,11 @@ constexpr int gemm_waves_per_simd(int bm, int bn, int bkt, int st, int nw) {
     const int blocks = (160 * 1024) / (st * (bm + bnr) * bkt * 2 + bn * 4);
     const int w = blocks * nw / 4;
     return w < 1 ? 1 : (w > 4 ? 4 : w);
+}
+
+// v + (the value of the lane the DPP control names), all lanes active
+template <int CTRL> __device__ __forceinline__ float gap_dpp_add(float v) {
+    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
 }
 
 template <int BM, int BN, int WM, int WN, int BKT, int ST, int MASK>
@@ -65,14 +72,19 @@ void conv_gemm_kernel(const ConvParams p) {
     const unsigned logical = xcd_block(blockIdx.x, gridDim.x);
     const unsigned mtile = logical / p.ntn, ntile = logical - mtile * p.ntn;
     // F_IMGW (per-image weights): M tiles are aligned to images, so that one tile has one weight matrix
+    // ... and so are they when the block sums the global-average pool's partials (gap_part): a tile then belongs to one image, and an
+    // image's rows are grouped the same way wherever it sits in the batch
     long m0 = (long)mtile * BM;
     long mend = p.M;                                 // rows at or beyond it do not exist
     const half_t* wsrc = p.w;
-    if (p.flags & F_IMGW) {
-        const unsigned img = mtile / (unsigned)p.tiles_img, ti = mtile - img * (unsigned)p.tiles_img;
+    const bool gap = MASK == 0 && p.gap_part != nullptr;
+    unsigned img = 0, ti = 0;
+    if ((p.flags & F_IMGW) || gap) {
+        img = mtile / (unsigned)p.tiles_img;
+        ti = mtile - img * (unsigned)p.tiles_img;
         m0 = (long)img * p.hw_img + (long)ti * BM;
         mend = (long)(img + 1) * p.hw_img;
-        wsrc += (long)img * p.wimg_stride;
+        if (p.flags & F_IMGW) wsrc += (long)img * p.wimg_stride;
     }
     const int n0 = ntile * BN;
 
@@ -251,6 +263,75 @@ void conv_gemm_kernel(const ConvParams p) {
         }
     }
 
+    // ---- epilogue + column sums for the global-average pool behind this conv (conv_gap_select: plain epilogue, 16-byte stores) ------
+    // The sums are taken over the values AS STORED (after the activation, rounded to fp16), rows at or beyond mend left out, in a fixed
+    // order: the wave's row tiles in the lane, the 16 lanes of a DPP row, then — through LDS, the ring is free — the 2 WM half-tiles of
+    // the block in order.  Slot (tile of the image) % gap_splits takes the block's sums: a plain store, or with gap_atomic an atomic add
+    // to a zeroed slot that has at most two contributors (fp32 addition commutes, so the order of arrival does not show).
+    if (gap) {
+        __syncthreads();                               // every wave has left the K loop: the ring is free
+        float* const red = reinterpret_cast<float*>(lds);      // [2 * WM][BN]
+        long mrow[TM];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) mrow[i] = m0 + wm * WTM + i * 32 + (lane & 31);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            float bias[16];
+            conv_epilogue_consts(sbias, wn * WTN + j * 32, lane, bias);
+            const int cb = wn * WTN + j * 32 + (lane >> 5) * 8;      // first cout of this lane's run 0, inside the block's tile
+            float cs[16];
+#pragma unroll
+            for (int e = 0; e < 16; ++e) cs[e] = 0.f;
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                float v[16];
+#pragma unroll
+                for (int e = 0; e < 16; ++e) v[e] = acc[i][j][e] + bias[e];
+                vse_act_n(v, p.act, p.act_a, p.act_b);
+                if (p.post_a != 1.f || p.post_b != 0.f) {
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) v[e] = v[e] * p.post_a + p.post_b;
+                }
+                vse_act_n(v, p.act2, 0.f, 0.f);
+                const bool live = mrow[i] < mend;
+#pragma unroll
+                for (int g = 0; g < 2; ++g) {
+                    const float* w = v + g * 8;
+                    const half8 h8 = half8{(half_t)w[0], (half_t)w[1], (half_t)w[2], (half_t)w[3],
+                                           (half_t)w[4], (half_t)w[5], (half_t)w[6], (half_t)w[7]};
+                    if (live && n0 + cb + g * 16 < p.Np)
+                        *reinterpret_cast<half8*>(reinterpret_cast<half_t*>(p.out) + mrow[i] * p.out_ld + n0 + cb + g * 16) = h8;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) cs[g * 8 + e] += live ? (float)h8[e] : 0.f;
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                cs[e] = gap_dpp_add<0xB1>(cs[e]);      // quad_perm [1, 0, 3, 2]
+                cs[e] = gap_dpp_add<0x4E>(cs[e]);      // quad_perm [2, 3, 0, 1]
+                cs[e] = gap_dpp_add<0x141>(cs[e]);     // row_half_mirror
+                cs[e] = gap_dpp_add<0x140>(cs[e]);     // row_mirror: every lane holds the sum of its row of 16
+            }
+            if ((lane & 15) == 0) {
+                float* r = red + (wm * 2 + ((lane >> 4) & 1)) * BN + cb;
+#pragma unroll
+                for (int g = 0; g < 2; ++g)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) r[g * 16 + e] = cs[g * 8 + e];
+            }
+        }
+        __syncthreads();
+        if (tid < BN && n0 + tid < p.gap_c) {
+            float s = 0.f;
+#pragma unroll
+            for (int r = 0; r < 2 * WM; ++r) s += red[r * BN + tid];
+            float* dst = p.gap_part + ((long)img * p.gap_splits + (int)(ti % (unsigned)p.gap_splits)) * p.gap_c + n0 + tid;
+            if (p.gap_atomic) atomicAdd(dst, s);
+            else *dst = s;
+        }
+        return;
+    }
+
     // ---- epilogue (shared with conv_mfma_kernel) ---------------------------------------------------------------
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -294,10 +375,13 @@ static int launch_conv_gemm(const ConvParams& pin, const ConvKernel& k, hipStrea
     p.nk = p.nkh;
     if (p.flags & F_HILO) p.nk *= 2;
     unsigned long long tiles = (unsigned long long)((p.M + g.bm - 1) / g.bm) * p.ntn;
-    if (p.flags & F_IMGW) {
+    if (p.gap_part && (k.arg[1] != 0 || p.hw_img <= 0 || p.M % p.hw_img || p.gap_splits < 1 || g.bn > 64 * g.wm * g.wn)) return VSE_E_INVAL;
+    if ((p.flags & F_IMGW) || p.gap_part) {
         p.tiles_img = (p.hw_img + g.bm - 1) / g.bm;
         tiles = (unsigned long long)(p.M / p.hw_img) * p.tiles_img * p.ntn;
     }
+    // a slot takes one tile by a plain store, or two by atomic adds to the zeroed buffer (conv_gap_select decided for this row tile)
+    if (p.gap_part && (p.tiles_img > 2 * p.gap_splits || (p.gap_atomic != 0) != (p.tiles_img > p.gap_splits))) return VSE_E_INVAL;
     if (tiles == 0 || tiles > 0x7fffffffull) return VSE_E_INVAL;
     hipLaunchKernelGGL(inst->fn, dim3((unsigned)tiles), dim3(64 * g.wm * g.wn), 0, st, p);
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;

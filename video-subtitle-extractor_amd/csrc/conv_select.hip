@@ -390,6 +390,160 @@ int launch_conv_pool(const vse_op& conv, const ConvKernel& k, const TView& in, c
     return conv_launch(p, k, st);
 }
 
+// ---- 1x1 conv + global-average pool pairs: the conv sums the pool's partials -------------------------------------------------------
+
+static bool touches_range(const vse_view& v, int64_t lo, int64_t hi) {          // workspace bytes [lo, hi)
+    if (v.n == 0 || v.arena != 0) return false;
+    int64_t a, b;
+    view_span(v, &a, &b);
+    return a < hi && lo < b;
+}
+static bool reads_range(const vse_op& o, int64_t lo, int64_t hi) {              // (in2 / out2: as in conv_pool_select)
+    return touches_range(o.in0, lo, hi) || touches_range(o.in1, lo, hi) || touches_range(o.in2, lo, hi) || touches_range(o.out2, lo, hi);
+}
+
+// ops[i] = a 1x1 / stride-1 conv that conv_select sends to conv_gemm_kernel's unmasked form, with a plain epilogue (bias / BN / activation,
+// fp16, 16-byte stores), ops[i + 1] = a global-average pool over exactly the conv's output view with an fp32 scratch view [n][splits][c],
+// neither of them ragged, and an image has at most two row tiles per slot (two contributors to a zeroed slot add in either order to the
+// same bits; three would not).
+// The fused conv WRITES the partials while its other blocks still read its input, which the unfused pair never does: the compiler is free
+// to lay the pool's scratch over the conv's input, dead behind the conv (the server detector's second, third and last stage do).  Then the
+// partials go to other workspace bytes that are dead while the pair runs: the head of a later record's dense output (a view without
+// padding, rewritten whole) that no record from the pool to that one touches and that that record overwrites without reading it, or an
+// end of an earlier record's that nothing touches any more.  No such bytes: two launches.
+ConvGap conv_gap_select(const vse_op* ops, int n_ops, int i) {
+    const ConvGap no{0, 0, 0, 0, 0, 0, 0};
+    if (!ops || i < 0 || i + 1 >= n_ops) return no;
+    const vse_op &c = ops[i], &q = ops[i + 1];
+    if (c.kind != OP_CONV || q.kind != OP_GAP) return no;
+    if ((c.flags & ~F_WK32) || c.p[P_KH] != 1 || c.p[P_KW] != 1 || c.p[P_SH] != 1 || c.p[P_SW] != 1 || c.p[P_PH] || c.p[P_PW]) return no;
+    if (c.p[P_INSHIFT] || c.p[P_LO_OUT] || c.p[P_WLIN] || c.p[P_WLOUT] || q.p[P_WLIN] || q.p[P_WLOUT]) return no;
+    if (c.in1.n || c.in2.n || c.out2.n || q.in1.n || q.out2.n) return no;
+    if (c.in0.arena != 0 || c.out.arena != 0 || c.out.esize != 2 || c.in0.esize != 2 || !same_view(c.out, q.in0)) return no;
+    if (c.out.n < 1 || c.out.n != c.in0.n || c.out.h != c.in0.h || c.out.w != c.in0.w || c.out.c != c.p[P_COUT] || (c.out.ld & 7) || (c.out.off & 15))
+        return no;
+    const vse_view& s = q.in2;
+    if (s.arena != 0 || s.n != c.out.n || s.esize != 4 || s.h < 1 || s.w != 1 || s.c != c.out.c || s.ld != s.c || (s.off & 3)) return no;
+    if (q.out.arena != 0 || q.out.n != c.out.n || q.out.c != c.out.c || q.out.esize != 2) return no;
+    auto shape = [](const vse_view& v) { return TView{nullptr, v.n, v.h, v.w, v.c, v.ld, v.esize}; };
+    const TView none{nullptr, 0, 0, 0, 0, 0, 0};
+    const ConvParams p = conv_params(c, shape(c.in0), none, none, shape(c.out), none, nullptr, nullptr, nullptr, nullptr, SrcGeom{0, 0, 0, 0});
+    const ConvKernel k = conv_select(p, c.p[P_KTOT]);
+    if (k.family != CK_GEMM || k.rc != VSE_OK || k.arg[1] != 0 || c.in0.c != p.cinp) return no;
+    ConvGap g = no;
+    g.bm = kCfg[k.arg[0]].bm;
+    const long hw = (long)c.out.h * c.out.w;
+    if (hw < 1 || hw > 0x7fffffffl) return no;
+    g.tiles_img = (int)((hw + g.bm - 1) / g.bm);
+    if (g.tiles_img > 2 * s.h) return no;
+    g.slots = g.tiles_img < s.h ? g.tiles_img : s.h;
+    g.atomic = g.tiles_img > s.h;
+    g.part_bytes = (int64_t)s.n * s.h * s.c * 4;
+    auto free_of_the_pair = [&](int64_t lo, int64_t hi) {
+        return !touches_range(c.in0, lo, hi) && !touches_range(c.out, lo, hi) && !touches_range(q.out, lo, hi);
+    };
+    if (free_of_the_pair(s.off, s.off + g.part_bytes)) {
+        g.part_off = s.off;
+        g.fused = 1;
+        return g;
+    }
+    for (int j = i + 2; j < n_ops && !g.fused; ++j) {
+        const vse_view& r = ops[j].out;
+        int64_t lo, hi;
+        if (r.n == 0 || r.arena != 0 || r.ld != r.c || (r.off & 15)) continue;
+        view_span(r, &lo, &hi);
+        if (hi - lo < g.part_bytes) continue;
+        hi = lo + g.part_bytes;
+        if (!free_of_the_pair(lo, hi) || reads_range(ops[j], lo, hi)) continue;
+        if (ops[j].kind == OP_CONV && conv_pool_select(ops, n_ops, j).family == CK_C3POOL) continue;      // (never writes that view)
+        bool dead = true;
+        for (int m = i + 2; m < j && dead; ++m) dead = !reads_range(ops[m], lo, hi) && !touches_range(ops[m].out, lo, hi);
+        if (!dead) continue;
+        g.part_off = lo;
+        g.fused = 1;
+    }
+    // ... or the head or the tail of an EARLIER record's dense output that no record from the conv on touches again.  The next run finds
+    // the partials there: walking its records up to the conv, the first that touches those bytes must overwrite them whole without reading
+    // them.  (A conv that runs with its max-pool as one kernel never writes its output view and that pool never reads it: neither counts.)
+    auto runs_pooled = [&](int m) { return ops[m].kind == OP_CONV && conv_pool_select(ops, n_ops, m).family == CK_C3POOL; };
+    auto dead_from_here = [&](int64_t lo, int64_t hi) {
+        if (!free_of_the_pair(lo, hi)) return false;
+        for (int m = i; m < n_ops; ++m)
+            if (reads_range(ops[m], lo, hi) || touches_range(ops[m].out, lo, hi)) return false;
+        for (int m = 0; m < i; ++m) {
+            const bool pooled = runs_pooled(m);
+            if (m > 0 && ops[m].kind == OP_POOL && runs_pooled(m - 1)) {                  // (launches nothing; stores through its out)
+                if (touches_range(ops[m].in1, lo, hi) || touches_range(ops[m].in2, lo, hi) || touches_range(ops[m].out2, lo, hi)) return false;
+            } else if (reads_range(ops[m], lo, hi)) {
+                return false;
+            }
+            if (!touches_range(ops[m].out, lo, hi) || pooled) continue;
+            int64_t a, b;
+            view_span(ops[m].out, &a, &b);
+            return ops[m].out.ld == ops[m].out.c && a <= lo && hi <= b;
+        }
+        return true;
+    };
+    for (int j = 0; j < i && !g.fused; ++j) {
+        const vse_view& r = ops[j].out;
+        int64_t lo, hi;
+        if (r.n == 0 || r.arena != 0 || r.ld != r.c || (r.off & 15)) continue;
+        view_span(r, &lo, &hi);
+        if (hi - lo < g.part_bytes) continue;
+        const int64_t tail = (hi - g.part_bytes) & ~(int64_t)15;
+        if (dead_from_here(lo, lo + g.part_bytes)) g.part_off = lo, g.fused = 1;
+        else if (tail >= lo && dead_from_here(tail, tail + g.part_bytes)) g.part_off = tail, g.fused = 1;
+    }
+    return g.fused ? g : no;
+}
+
+int launch_conv_gap(const vse_op& o, const ConvGap& g, const TView& in, const TView& out, const char* wts, const half_t* zero, float* part,
+                    int splits, hipStream_t st) {
+    if (!g.fused || !in.ptr || !out.ptr || !part || !zero || splits < 1) return VSE_E_INVAL;
+    const TView none{nullptr, 0, 0, 0, 0, 0, 0};
+    ConvParams p = conv_params(o, in, none, none, out, none, wts, zero, nullptr, nullptr, SrcGeom{0, 0, 0, 0});
+    if (in.c != p.cinp || in.esize != 2 || (in.ld & 7) || (p.Np & 7) || !p.vec16 || out.h != p.OH || out.w != p.OW || out.n != in.n) return VSE_E_INVAL;
+    const ConvKernel k = conv_select(p, o.p[P_KTOT]);
+    if (k.family != CK_GEMM || k.rc != VSE_OK || k.arg[1] != 0 || kCfg[k.arg[0]].bm != g.bm) return VSE_E_INVAL;
+    p.hw_img = p.OH * p.OW;
+    p.gap_part = part;
+    p.gap_splits = splits;
+    p.gap_c = out.c;
+    p.gap_atomic = g.atomic;
+    return conv_launch(p, k, st);
+}
+
+// ---- SE gate multiply + residual add pairs that run as one pass ---------------------------------------------------------------------
+
+// ops[i] = an OP_SCALE without F_RES (x * gate), ops[i + 1] = an OP_BINARY add at the same resolution one of whose operands is exactly
+// the scale's output view, all four tensors of one shape, both records on the same width levels (the kernels of neither look at them);
+// and the product is DEAD behind the add (conv_pool_select's walk): fused, it is never written.  The fused pass reads x and the
+// residual while it writes the add's output, so that output may be x or the residual ITSELF (element for element) but may not
+// overlap them, or the gate, in any other way.  -> 0: two launches; 1 / 2: the add's in1 / in0 is the residual.
+int scale_add_select(const vse_op* ops, int n_ops, int i) {
+    if (!ops || i < 0 || i + 1 >= n_ops) return 0;
+    const vse_op &s = ops[i], &b = ops[i + 1];
+    if (s.kind != OP_SCALE || b.kind != OP_BINARY || s.flags || b.flags || b.p[0] || b.p[1]) return 0;
+    if (s.p[P_WLIN] != b.p[P_WLIN] || s.p[P_WLOUT] != b.p[P_WLOUT]) return 0;
+    const int which = same_view(s.out, b.in0) ? 1 : (same_view(s.out, b.in1) ? 2 : 0);
+    if (!which || s.out.arena != 0) return 0;
+    const vse_view &x = s.in0, &gate = s.in1, &res = which == 1 ? b.in1 : b.in0, &out = b.out;
+    const vse_view* big[4] = {&x, &s.out, &res, &out};
+    for (const vse_view* v : big)
+        if (v->n != x.n || v->h != x.h || v->w != x.w || v->c != x.c || v->esize != 2 || (v->ld & 7) || (v->off & 15) || v->n < 1) return 0;
+    if ((x.c & 7) || gate.n != x.n || gate.h != 1 || gate.w != 1 || gate.c != x.c || gate.esize != 2 || (gate.ld & 7) || (gate.off & 15)) return 0;
+    if (same_view(res, s.out)) return 0;                                        // (t + t)
+    if ((views_overlap(out, x) && !same_view(out, x)) || (views_overlap(out, res) && !same_view(out, res)) || views_overlap(out, gate)) return 0;
+    if (same_view(out, s.out)) return which;              // the add in place over the product: the same bytes hold the same sums afterwards
+    if (views_overlap(out, s.out)) return 0;
+    for (int j = i + 2; j < n_ops; ++j) {
+        const vse_op& o = ops[j];
+        if (views_overlap(o.in0, s.out) || views_overlap(o.in1, s.out) || views_overlap(o.in2, s.out) || views_overlap(o.out2, s.out)) return 0;
+        if (views_overlap(o.out, s.out)) break;
+    }
+    return which;
+}
+
 // ---- launch -----------------------------------------------------------------------------------------------------------------
 
 int launch_conv(const vse_op& o, const TView& in, const TView& res, const TView& in2, const TView& out, const TView& dot_out,

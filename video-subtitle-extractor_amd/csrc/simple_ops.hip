@@ -410,13 +410,15 @@ __global__ __launch_bounds__(256) void gap_partial_kernel(TView in, float* __res
         if (ch < in.c) part[((long)n * splits + s) * in.c + ch] = sum;
     }
 }
-__global__ void gap_finish_kernel(const float* __restrict__ part, TView out, int splits, float inv_hw) {
+// (slots <= splits: the slots that hold sums — all of them behind gap_partial_kernel, min(splits, tiles per image) behind a conv that
+// summed the partials itself, launch_gap_finish)
+__global__ void gap_finish_kernel(const float* __restrict__ part, TView out, int splits, int slots, float inv_hw) {
     const long total = (long)out.n * out.c;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const long n = i / out.c;
         const int c = (int)(i % out.c);
         float s = 0.f;
-        for (int q = 0; q < splits; ++q) s += part[(n * splits + q) * out.c + c];
+        for (int q = 0; q < slots; ++q) s += part[(n * splits + q) * out.c + c];
         reinterpret_cast<half_t*>(out.ptr)[n * out.ld + c] = (half_t)(s * inv_hw);
     }
 }
@@ -481,6 +483,30 @@ __global__ __launch_bounds__(256) void scale_kernel(TView x, TView s, TView out,
         for (int e = 0; e < 8; ++e) {
             const float v = (float)a[e] * (float)b[e];
             o[e] = (half_t)(add_x ? v + (float)a[e] : v);
+        }
+        st8(out, pix, g * 8, o);
+    }
+}
+
+// x * gate + r as ONE pass (scale_add_select, conv_select.hip): the product is rounded to fp16 before the add, exactly as scale_kernel
+// stored it for binary_kernel to read, so the result has the pair's bits; the product itself is never written.  `out` may be x or r itself
+// (every thread reads its vector before it writes it).
+__global__ __launch_bounds__(256) void scale_add_kernel(TView x, TView s, TView r, TView out, int act) {
+    const int cg = x.c >> 3;
+    const long hw = (long)x.h * x.w;
+    const long total = (long)x.n * hw * cg;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        int g;
+        const long pix = vse_divmod(i, cg, g);
+        const long n = pix / hw;
+        const half8 a = ld8(x, pix, g * 8);
+        const half8 b = ld8(s, n, g * 8);
+        const half8 y = ld8(r, pix, g * 8);
+        half8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const half_t prod = (half_t)((float)a[e] * (float)b[e]);
+            o[e] = (half_t)vse_act((float)prod + (float)y[e], act, 0.f, 0.f);
         }
         st8(out, pix, g * 8, o);
     }
@@ -875,6 +901,20 @@ __global__ __launch_bounds__(256) void wscale_kernel(const half_t* __restrict__ 
     }
 }
 
+int launch_gap_finish(const float* part, const TView& in0, const TView& out, int splits, int slots, hipStream_t st) {
+    if (!part || !out.ptr || (in0.c & 7) || out.c != in0.c || slots < 1 || slots > splits) return VSE_E_INVAL;
+    hipLaunchKernelGGL(gap_finish_kernel, dim3(grid_for((long)out.n * out.c, 256)), dim3(256), 0, st, part, out, splits, slots,
+                       1.f / ((float)in0.h * in0.w));
+    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+}
+
+int launch_scale_add(const TView& x, const TView& gate, const TView& res, const TView& out, int act, hipStream_t st) {
+    if (!x.ptr || !gate.ptr || !res.ptr || !out.ptr || (x.c & 7) || x.esize != 2) return VSE_E_INVAL;
+    const long items = (long)x.n * x.h * x.w * (x.c >> 3);
+    hipLaunchKernelGGL(scale_add_kernel, dim3(grid_for(items, 256)), dim3(256), 0, st, x, gate, res, out, act);
+    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+}
+
 int launch_simple_op(const vse_op& op, const TView& in0, const TView& in1, const TView& in2, const TView& out,
                      const TView& out2, const char* wbase, const int* wl_in, const int* wl_out, hipStream_t st) {
     const int* p = op.p;
@@ -963,7 +1003,7 @@ int launch_simple_op(const vse_op& op, const TView& in0, const TView& in1, const
             hipLaunchKernelGGL(gap_partial_kernel, grid, dim3(256), 0, st, in0, reinterpret_cast<float*>(in2.ptr), splits);
             const long items = (long)out.n * out.c;
             hipLaunchKernelGGL(gap_finish_kernel, dim3(grid_for(items, 256)), dim3(256), 0, st,
-                               reinterpret_cast<const float*>(in2.ptr), out, splits, 1.f / ((float)in0.h * in0.w));
+                               reinterpret_cast<const float*>(in2.ptr), out, splits, splits, 1.f / ((float)in0.h * in0.w));
             break;
         }
         case OP_SCALE: {

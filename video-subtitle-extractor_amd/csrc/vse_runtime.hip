@@ -39,6 +39,8 @@ struct vse_plan {
     int weights_id;
     std::vector<vse_op> ops;
     std::vector<ConvKernel> pooled;   // per op: family CK_C3POOL = this conv runs with the max-pool record behind it as one kernel (conv_pool_select)
+    std::vector<ConvGap> gapped;      // per op: fused = this 1x1 conv sums the partials of the global-average pool record behind it (conv_gap_select)
+    std::vector<int> scale_add;       // per op: != 0 = this OP_SCALE runs with the add record behind it as one pass (scale_add_select)
     size_t ws_bytes;
     int max_ext;
     int n_levels;                     // ragged plans: width levels referenced by the ops (0 = not a ragged plan)
@@ -222,6 +224,17 @@ int vse_plan_create(vse_ctx* c, int weights_id, const vse_op* ops, int n_ops, si
     // conv + max-pool pairs that run as one kernel: decided here, once, from the records (ragged plans stay as they are)
     p->pooled.assign(n_ops, ConvKernel{CK_NONE, VSE_OK, {0, 0, 0}});
     for (int i = 0; i + 1 < n_ops && !p->n_levels; ++i) p->pooled[i] = conv_pool_select(ops, n_ops, i);
+    // 1x1 conv + global-average pool pairs whose partial sums the conv takes itself (not in ragged plans: their pools sum row by row),
+    // and gate multiply + residual add pairs that run as one pass (ragged plans too): decided here as well
+    p->gapped.assign(n_ops, ConvGap{0, 0, 0, 0, 0, 0, 0});
+    p->scale_add.assign(n_ops, 0);
+    for (int i = 0; i + 1 < n_ops; ++i) {
+        if (!p->n_levels) {
+            const ConvGap g = conv_gap_select(ops, n_ops, i);
+            if (g.fused && g.part_off >= 0 && (size_t)(g.part_off + g.part_bytes) <= ws_bytes) p->gapped[i] = g;
+        }
+        p->scale_add[i] = scale_add_select(ops, n_ops, i);
+    }
     *out = p;
     return VSE_OK;
 }
@@ -249,7 +262,21 @@ static int run_op(vse_plan* p, int i, char* ws, void* const* ext, const int32_t*
                 out2 = resolve(o.out2, ws, wts, ext);
     int rc;
     if (i > 0 && p->pooled[i - 1].family == CK_C3POOL) return VSE_OK;      // this pool ran inside the conv in front of it
-    if (p->pooled[i].family == CK_C3POOL) {
+    if (i > 0 && p->scale_add[i - 1]) return VSE_OK;                       // this add ran with the gate multiply in front of it
+    if (i > 0 && p->gapped[i - 1].fused) {
+        // the conv in front of this pool left the partial sums: the finish pass alone
+        const ConvGap& g = p->gapped[i - 1];
+        rc = launch_gap_finish(reinterpret_cast<const float*>(ws + g.part_off), in0, out, o.in2.h, g.slots, st);
+    } else if (p->gapped[i].fused) {
+        const ConvGap& g = p->gapped[i];
+        float* part = reinterpret_cast<float*>(ws + g.part_off);
+        // two tiles add into one slot: the slots start from zero (otherwise every slot that is read is overwritten)
+        if (g.atomic && hipMemsetAsync(part, 0, (size_t)g.part_bytes, st) != hipSuccess) rc = VSE_E_HIP;
+        else rc = launch_conv_gap(o, g, in0, out, wts, reinterpret_cast<const half_t*>(p->ctx->zero_page), part, p->ops[i + 1].in2.h, st);
+    } else if (p->scale_add[i]) {
+        const vse_op& b = p->ops[i + 1];
+        rc = launch_scale_add(in0, in1, resolve(p->scale_add[i] == 1 ? b.in1 : b.in0, ws, wts, ext), resolve(b.out, ws, wts, ext), b.p[2], st);
+    } else if (p->pooled[i].family == CK_C3POOL) {
         const TView pool_out = resolve(p->ops[i + 1].out, ws, wts, ext);
         rc = launch_conv_pool(o, p->pooled[i], in0, pool_out, wts, reinterpret_cast<const half_t*>(p->ctx->zero_page), st);
     } else if (o.kind == OP_CONV) {
@@ -793,7 +820,7 @@ int vse_plan_profile(vse_plan* p, void* ws, void* const* ext, int n_ext, const i
     for (int i = 0; i < n; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
     // a max-pool that ran inside the conv in front of it launched nothing: its time is the conv's, and it reports exactly 0
     for (int i = 1; i < n; ++i)
-        if (p->pooled[i - 1].family == CK_C3POOL) ms[i] = 0.f;
+        if (p->pooled[i - 1].family == CK_C3POOL || p->scale_add[i - 1]) ms[i] = 0.f;      // (likewise an add that ran with its gate multiply)
     for (auto& e : ev) (void)hipEventDestroy(e);
     return VSE_OK;
 }
