@@ -425,6 +425,46 @@ int vse_frame_cells_hold(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int 
                          int32_t* d_totals /* [nt,gy,gx,4]: covered, runs, present, cuts; accumulated across calls */,
                          int32_t* d_cell_counts /* nullable: [nt, n + hold - 1, gy, gx, 3] */, void* stream);
 
+/* ---- locator and calibration on bounded runs ---------------------------------------------------------------------------- */
+/* Replaces: nothing in the reference; it serves vse_frame_hold_bounded's footage.  Behind a subtitle whose busy background stands
+ * still, vse_frame_cells_hold's cells keep their static edges in every frame: the cells of the subtitle itself are present throughout
+ * (the host's logo rule scores them 0) and elsewhere the static edges dilute every cut ratio.  Here the same cells, automaton and
+ * thresholds on BOUNDED masks.  For each of nt thresholds (as for vse_frame_cells_multi) B_u is vse_frame_hold_bounded's bounded mask
+ * of frame u at that threshold, `hold` (1..32) and `max_hold` (hold..4000), and per cell of 8 x 64 interior pixels (vse_frame_cells'
+ * cells) and frame u
+ *   e = |B_u|,  a = |B_u \ B_{u-1}|,  v = |B_{u-1} \ B_u|
+ * go in frame order to vse_frame_cells' unchanged automaton, which leaves covered, runs, present, cuts in d_totals [nt, gy, gx, 4].
+ * max_hold >= the clip's length gives vse_frame_cells_hold's totals, integer for integer.  Known limits, with vse_frame_hold_bounded's:
+ * a gap between two subtitles shorter than max_hold lets the background runs under the text count (the text cuts them to a length in
+ * range), which adds edges to the cells in the gap; a subtitle shown for more than max_hold frames vanishes from its cells; max_hold
+ * and the behaviour on real footage are not measured here (no real clips).
+ * Size in bytes of the caller-owned state (8-byte aligned, layout the library's): with ih = area_h - 2, iw = area_w - 2, words =
+ * ceil(iw / 64) and cells = ceil(ih / 8) * words it is, rounded up to 8,
+ *   nt * ih * words * 128                 one uint16 run length per pixel and threshold, as vse_frame_hold lays its pixels out
+ * + nt * cells * (max_hold + 64) * 4      the pending rows of every cell and threshold, one uint32 per row: a | v << 16 (a cell has
+ *                                         512 pixels, so neither count passes 512)
+ * + nt * cells * 8                        |B| of the cell's last finished row, and its open run
+ * (whole-frame 1080p, nt 8, max_hold 360: 33 MB + 55 MB); 0 below 3 x 3, for nt outside 1..8 or max_hold outside 1..4000.  A state
+ * belongs to one region size, nt and max_hold. */
+size_t vse_frame_cells_hold_bounded_state_bytes(int area_h, int area_w, int nt, int max_hold);
+/* Frames, `fed`, `flush` and the lag as for vse_frame_hold_bounded: a row is final once max_hold further frames have been seen.
+ * fed == 0 starts a clip: the state's content is ignored and the totals count from zero.  After a call without `flush` the totals
+ * cover the frames 1 .. max(0, fed + n - max_hold) with the last run left open; with `flush` (the clip ends with this call) they cover
+ * all fed + n frames and the open runs are closed.  n == 0 with `flush` only drains and closes.  Batches of any sizes, smaller or
+ * larger than max_hold, give the totals of one call; the same thresholds, hold, max_hold and rule go to every call of a clip.
+ * d_cell_counts (nullable) receives, per threshold, e, a, v per cell for the frames whose rows this call completes, numbered from row
+ * 0 as vse_frame_hold_bounded numbers its rows (n + max_hold rows of room per threshold; rows the call does not complete are left
+ * alone); summed over the cells they are vse_frame_hold_bounded's rows.  One kernel launch on `stream` (before a clip's first, a
+ * clear of the pending rows on the same stream), no allocation, no device sync; a block owns its cell for all frames of the call and
+ * alone reads and writes the cell's state, totals and counts, for all thresholds.  Returns VSE_E_INVAL, without touching the device,
+ * for everything vse_frame_cells_hold refuses, max_hold < hold, max_hold > 4000, or n + max_hold beyond INT32_MAX. */
+int vse_frame_cells_hold_bounded(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride,
+                                 int y0, int y1, int x0, int x1, const int* thresholds /* host, [nt] */, int nt, int hold, int max_hold,
+                                 int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
+                                 void* d_state, int64_t fed, int flush,
+                                 int32_t* d_totals /* [nt,gy,gx,4]: covered, runs, present, cuts; accumulated across calls */,
+                                 int32_t* d_cell_counts /* nullable: [nt, n + max_hold, gy, gx, 3] */, void* stream);
+
 /* ---- interval composite ------------------------------------------------------------------------------------------------- */
 /* Replaces: the picture VideoSubFinder hands to OCR for each subtitle it finds (the RGBImages the reference reads back at
  * backend/main.py:378-505), which that closed binary builds from all frames of the subtitle, not from one of them.  Not its

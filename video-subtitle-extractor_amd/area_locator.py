@@ -41,8 +41,19 @@ an edge on a pixel for `hold` frames is held too.  At low thresholds fine, fast 
 120), cells=(8, 3)) with hold 8 the threshold 64 locates a wrong band and only the thresholds from 96 up the true one (EXPERIMENTS.md).
 Real footage is unmeasured here as well.
 
+Bounded runs (automaton="hold" with max_hold_seconds / max_hold_frames), for the footage of HoldFrameSelector(max_hold_seconds=...): a busy
+background that STANDS STILL behind the subtitle (an interview, a news desk, shelves, a logo in the band).  On held masks its edges are
+present in every frame, so the subtitle's own cells fall to the logo rule and score 0, and elsewhere they dilute every cell's cut ratio.
+Here each cell counts the BOUNDED mask of its frames (edge pixels whose run is hold .. max_hold frames long; vse_frame_cells_hold_bounded):
+the static edges drop out before the automaton sees them.  max_hold is HoldFrameSelector's: max_hold_frames, else round(max_hold_seconds *
+fps), hold .. 4000.  Both None (the default): the held path above, call for call.  Known limits: a gap between two subtitles shorter than
+max_hold lets the background runs under the text count (the text cuts them to a length in range), so the cells stay present through the
+gap; a subtitle shown for longer than max_hold vanishes; a row is final only max_hold frames later, which the device keeps per cell (55 MB
+for whole-frame 1080p at max_hold 360 and eight thresholds); 12-15 s is a guess.  Nothing is measured on real footage.
+
     python -m vse_amd.area_locator VIDEO [--fps F --size WxH --layout i420|nv12] [--probe START COUNT] [--edge-thresh auto|N]
-                                         [--locator-automaton change|hold [--hold-seconds S | --hold-frames N]] [--json]
+                                         [--locator-automaton change|hold [--hold-seconds S | --hold-frames N]
+                                          [--max-hold-seconds S | --max-hold-frames N]] [--json]
 
 prints `ymin ymax xmin xmax` (and the chosen threshold as a fifth number when `--edge-thresh auto` was asked); VIDEO is what
 ingest.open_source reads.
@@ -57,7 +68,7 @@ from fractions import Fraction
 import numpy as np
 
 from . import staging
-from .engine import CellParams, DeviceState
+from .engine import FRAME_HOLD_BOUNDED_MAX, CellParams, DeviceState
 from .frame_select import band_batches
 
 CELL_H, CELL_W = 8, 64          # interior pixels of a cell (the tile of csrc/frame_change.hip)
@@ -144,17 +155,28 @@ def locate_area(totals, frames_scanned, region, frame_hw, row_frac=0.25, col_fra
 
 class EngineCells(DeviceState):
     """cells_fn of AreaLocator on the GPU (Context.frame_cells; with `thresholds`, Context.frame_cells_multi; with `hold`,
-    Context.frame_cells_hold at `thresholds` or at params.edge_thresh alone): keeps the device state of the last region (and threshold
-    count, and hold) between calls, and with a hold the number of frames fed since the last reset."""
+    Context.frame_cells_hold at `thresholds` or at params.edge_thresh alone; with `max_hold` as well, Context.frame_cells_hold_bounded):
+    keeps the device state of the last region (and threshold count, and hold or max_hold) between calls, and with a hold the number of
+    frames fed since the last reset."""
 
     def __init__(self, ctx):
         super().__init__(ctx)
         self.fed = 0
 
-    def __call__(self, frames, area, params, reset, flush, thresholds=None, hold=None):
+    def __call__(self, frames, area, params, reset, flush, thresholds=None, hold=None, max_hold=None):
         t = self.ctx.torch
         y0, y1, x0, x1 = area
         frames = t.empty((0, y1, x1, 3), dtype=t.uint8, device=self.ctx.tdev) if frames is None else self._device(frames)
+        if max_hold is not None:
+            if hold is None:
+                raise ValueError("EngineCells: max_hold needs a hold")
+            ths = (params.edge_thresh,) if thresholds is None else tuple(thresholds)
+            if self._fresh((y1 - y0, x1 - x0, len(ths), "max_hold", int(max_hold)),
+                           lambda h, w, nt, _, mh: self.ctx.frame_cells_hold_bounded_state(h, w, nt, mh)) or reset:
+                self.fed = 0
+            totals = self.ctx.frame_cells_hold_bounded(frames, area, ths, hold, max_hold, params, self._state, self.fed, flush)
+            self.fed += len(frames)
+            return totals[0] if thresholds is None else totals
         if hold is not None:
             ths = (params.edge_thresh,) if thresholds is None else tuple(thresholds)
             if self._fresh((y1 - y0, x1 - x0, len(ths), int(hold)), self.ctx.frame_cells_hold_state) or reset:
@@ -183,16 +205,27 @@ class AreaLocator:
     the callers fall back to 128) and locates the area on the chosen threshold's totals.  plateau_frac: pick_edge_thresh's.
     automaton="hold" (default "change"; see the module text): cells_fn is called with hold=`hold` as a further keyword (and params'
     min_frames at least `hold`) and counts held masks; `hold` is kept on the object: hold_frames, or max(1, min(32, round(hold_seconds
-    * fps))) when that is None.  With "change" cells_fn gets no such keyword."""
+    * fps))) when that is None.  With "change" cells_fn gets no such keyword.
+    max_hold_seconds / max_hold_frames (with automaton="hold" only; both None: the call above, keyword for keyword): cells_fn gets
+    max_hold=`max_hold` as well and counts bounded masks; `max_hold` is kept on the object: max_hold_frames, or round(max_hold_seconds *
+    fps) when that is None (HoldFrameSelector's rule); below `hold` or above 4000 is a ValueError."""
 
     def __init__(self, cells_fn=None, edge_thresh=128, min_edges=16, change_ratio=0.5, min_seconds=0.3, max_seconds=20.0, batch=64,
                  probe=None, search_area=None, thresholds=AUTO_THRESHOLDS, plateau_frac=0.9, automaton="change", hold_seconds=0.3,
-                 hold_frames=None, **locate_kwargs):
+                 hold_frames=None, max_hold_seconds=None, max_hold_frames=None, **locate_kwargs):
         if automaton not in ("change", "hold"):
             raise ValueError(f"AreaLocator: automaton must be 'change' or 'hold', not {automaton!r}")
         if hold_frames is not None and not 1 <= int(hold_frames) <= 32:
             raise ValueError(f"AreaLocator: hold_frames must be 1..32, not {hold_frames}")
+        self.bounded = max_hold_seconds is not None or max_hold_frames is not None
+        if self.bounded and automaton != "hold":
+            raise ValueError("AreaLocator: max_hold_seconds / max_hold_frames need automaton='hold'")
+        if max_hold_frames is not None and not 1 <= int(max_hold_frames) <= FRAME_HOLD_BOUNDED_MAX:
+            raise ValueError(f"AreaLocator: max_hold_frames must be 1..{FRAME_HOLD_BOUNDED_MAX}, not {max_hold_frames}")
+        if hold_frames is not None and max_hold_frames is not None and int(max_hold_frames) < int(hold_frames):
+            raise ValueError(f"AreaLocator: max_hold_frames {max_hold_frames} is below hold_frames {hold_frames}")
         self.automaton, self.hold_seconds, self.hold_frames, self.hold = automaton, hold_seconds, hold_frames, None
+        self.max_hold_seconds, self.max_hold_frames, self.max_hold = max_hold_seconds, max_hold_frames, None
         self.cells_fn = cells_fn
         self.auto = isinstance(edge_thresh, str) and edge_thresh == "auto"
         self.thresholds = tuple(int(v) for v in thresholds)
@@ -215,6 +248,20 @@ class AreaLocator:
         if self.automaton != "hold":
             return None
         return int(self.hold_frames) if self.hold_frames is not None else max(1, min(32, int(round(self.hold_seconds * fps))))
+
+    def max_hold_for(self, fps):
+        """The longest run that counts, in frames at this frame rate (HoldFrameSelector's rule), None when runs are not bounded."""
+        if not self.bounded:
+            return None
+        hold = self.hold_for(fps)
+        max_hold = int(self.max_hold_frames if self.max_hold_frames is not None else round(self.max_hold_seconds * fps))
+        if not hold <= max_hold <= FRAME_HOLD_BOUNDED_MAX:
+            raise ValueError(f"AreaLocator: max_hold must be hold ({hold}) .. {FRAME_HOLD_BOUNDED_MAX} frames, not {max_hold}")
+        return max_hold
+
+    def describe_automaton(self):
+        """How the warnings name the automaton: `change`, `hold`, or `hold` with its bounds."""
+        return self.automaton if self.max_hold is None else f"{self.automaton} (runs of {self.hold}..{self.max_hold} frames)"
 
     def params(self, fps):
         min_frames = max(2, round(self.min_seconds * fps), self.hold_for(fps) or 0)
@@ -243,8 +290,9 @@ class AreaLocator:
         if area is None:
             return None
         params = self.params(fps)
-        self.hold = self.hold_for(fps)
-        kw = {**({"thresholds": self.thresholds} if self.auto else {}), **({"hold": self.hold} if self.hold is not None else {})}
+        self.hold, self.max_hold = self.hold_for(fps), self.max_hold_for(fps)
+        kw = {**({"thresholds": self.thresholds} if self.auto else {}), **({"hold": self.hold} if self.hold is not None else {}),
+              **({"max_hold": self.max_hold} if self.max_hold is not None else {})}
         cells = self.cells_fn if not kw else (lambda *a: self.cells_fn(*a, **kw))
         for items, data in staging.staged_batches(bands, uploader):
             cells(data, area, params, not self.frames_scanned, False)
@@ -258,7 +306,7 @@ class AreaLocator:
             k = pick_edge_thresh(self.totals, self.thresholds, self.frames_scanned, static_frac, self.plateau_frac)
             if k is None:
                 logging.getLogger(__name__).warning("edge_thresh='auto': none of the thresholds %s scores with the %s automaton in %d "
-                                                    "frames; falling back to %d", self.thresholds, self.automaton, self.frames_scanned,
+                                                    "frames; falling back to %d", self.thresholds, self.describe_automaton(), self.frames_scanned,
                                                     DEFAULT_EDGE_THRESH)
                 return None
             self.edge_thresh, chosen = self.thresholds[k], self.totals[k]
@@ -291,9 +339,16 @@ def main(argv=None, cells_fn=None):
                    "with `hold` only edges that hold still, for a textured background that moves behind the subtitles [change]")
     p.add_argument("--hold-seconds", type=float, default=0.3, help="with --locator-automaton hold: how long an edge must hold still [0.3]")
     p.add_argument("--hold-frames", type=int, default=None, help="... the same in frames, 1..32 [from --hold-seconds and the frame rate]")
+    p.add_argument("--max-hold-seconds", type=float, default=None, help="with --locator-automaton hold: count only edges that hold still "
+                   "for at most this long, for a busy background that stands still behind the subtitles [no bound]")
+    p.add_argument("--max-hold-frames", type=int, default=None, help="... the same in frames, up to 4000 [from --max-hold-seconds and the "
+                   "frame rate]")
     p.add_argument("--json", action="store_true", help="print a JSON object instead (area, frames scanned, grid size, edge threshold, "
-                   "the automaton and its hold in frames, and with `auto` the score of every threshold tried)")
+                   "the automaton, its hold and max_hold in frames, and with `auto` the score of every threshold tried)")
     args = p.parse_args(argv)
+    if (args.max_hold_seconds is not None or args.max_hold_frames is not None) and args.locator_automaton != "hold":
+        print("area_locator: --max-hold-seconds / --max-hold-frames need --locator-automaton hold", file=sys.stderr)
+        return 2
     from . import ingest
     try:
         size = None
@@ -304,7 +359,8 @@ def main(argv=None, cells_fn=None):
             size = (int(w), int(h))
         source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout)
         loc = AreaLocator(cells_fn, probe=args.probe, edge_thresh=parse_edge_thresh(args.edge_thresh), automaton=args.locator_automaton,
-                          hold_seconds=args.hold_seconds, hold_frames=args.hold_frames)
+                          hold_seconds=args.hold_seconds, hold_frames=args.hold_frames, max_hold_seconds=args.max_hold_seconds,
+                          max_hold_frames=args.max_hold_frames)
         if cells_fn is None:
             from . import staging
             up = staging.default_uploader()
@@ -321,7 +377,7 @@ def main(argv=None, cells_fn=None):
         print(json.dumps({"ymin": area.ymin, "ymax": area.ymax, "xmin": area.xmin, "xmax": area.xmax,
                           "frames_scanned": loc.frames_scanned, "cells": list(loc.totals.shape[-3:-1]), "edge_thresh": loc.edge_thresh,
                           "scores": dict(zip(map(str, loc.thresholds), loc.scores)) if loc.auto else None,
-                          "automaton": loc.automaton, "hold": loc.hold}))
+                          "automaton": loc.automaton, "hold": loc.hold, "max_hold": loc.max_hold}))
     elif loc.auto:
         print(area.ymin, area.ymax, area.xmin, area.xmax, loc.edge_thresh)
     else:

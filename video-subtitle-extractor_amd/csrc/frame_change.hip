@@ -29,7 +29,10 @@
 //
 // Held-edge selector with bounded runs (vse_frame_hold_bounded): frame_hold_kernel's tiles, mask and walk, but only edge pixels whose run
 // is hold .. max_hold frames long are counted, so that the edges of a background that stands still drop out too (frame_hold_bounded_kernel
-// and frame_hold_rows_kernel, at the end of the file).
+// and frame_hold_rows_kernel, near the end of the file).
+//
+// Locator and calibration on bounded runs (vse_frame_cells_hold_bounded): the cells and their automaton at several thresholds, counted on
+// the bounded masks (frame_cells_hold_bounded_kernel, at the end of the file).
 #include "common.h"
 
 namespace {
@@ -971,5 +974,227 @@ int vse_frame_hold_bounded_launch(const void* d_bgr, int n, int64_t pitch, int64
             written = upto;
         }
     }
+    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+}
+
+// ---- vse_frame_cells_hold_bounded -------------------------------------------------------------------------------------------------
+// The locator's cells (frame_cells_hold_kernel) on the bounded masks of frame_hold_bounded_kernel, for busy backgrounds that stand still: a
+// block is a cell for all frames of the call and for NT thresholds.  Three stages per chunk of steps, all pieces of the kernels above:
+//   tile_masks_multi  a frame's bytes, lumas and gradients once, the edge words of the NT thresholds side by side in LDS;
+//   the walk          frame_hold_bounded_kernel's: wave k walks interior row k with lane = column and one saturating run length per pixel
+//                     and threshold; a run that ends in range at step u with length L is a[u - L] += 1 and v[u] += 1, one add per
+//                     distinct length among the ending lanes for a, one per step with an ending run for v (gathered with lane = step);
+//   the tail          for the rows that can no longer change (max_hold further frames seen, or the flush), wave q takes threshold q
+//                     with lane = row: e by frame_hold_rows_kernel's running sum of a - v with the carry in the state, the slot cleared,
+//                     cell_counts written, and CellRuns stepped with frame_cells_hold_kernel's two ballots.
+// The pending rows live in a ring PER CELL AND THRESHOLD in the caller's state, row r in slot r % ring, ring = max_hold + FC_CHUNK slots as
+// in frame_hold_bounded_kernel.  A slot is one uint32, a | v << 16: a cell has 512 pixels and each starts at most one run and ends at most one
+// in a frame, so neither half passes 512.  Only the block that owns the cell touches its ring.  Its eight row-waves add to a slot with
+// integer atomics and the tail takes a slot and clears it with one atomic exchange, so every access to the ring is served by the same
+// cache level; __syncthreads() orders the walk before the tail and the tail before the next chunk's walk.  No two blocks share a word.
+// A flush is ONE step without an edge, which ends every open run, then the tail over all rows that are left, then the runs are closed.
+// Rows are numbered within the call as vse_frame_hold_bounded numbers them: row i of the call is frame first + 1 + i of the clip, first =
+// max(0, fed - max_hold) being the last frame whose row went out with an earlier call; step j of the call (frame fed + 1 + j) is row
+// lagged + j, lagged = fed - first.  slot_w = the ring slot of row 0.
+// State: pix as frame_cells_hold_kernel's, the uint16 being the run length (saturating at max_hold + 1); ring uint32 [NT][cells][ring];
+// carry int32 [NT][cells] = |B| of the cell's last finished row; open_runs as frame_cells_hold_kernel's.  A clip's first call finds ring,
+// carry and open runs cleared by the launcher and ignores pix.
+namespace {
+
+template <int NT>
+__global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_hold_bounded_kernel(const uint8_t* __restrict__ src, int n, int steps, long pitch,
+                                                                                 long fstride, int x0, int ih, int iw, CellThresholds th,
+                                                                                 CellRule rule, int hold, int max_hold, int ring_slots, int slot_w,
+                                                                                 int lagged, unsigned short* __restrict__ pix, unsigned* ring,
+                                                                                 int* __restrict__ carry, int* __restrict__ open_runs, int fresh,
+                                                                                 int flush, int* __restrict__ totals, int* __restrict__ cell_counts,
+                                                                                 int count_rows) {
+    __shared__ unsigned long long msk[NT * FC_CHUNK * FC_ROWS];           // [NT][FC_CHUNK][FC_ROWS]
+    static_assert(FC_WAVES == FC_ROWS, "wave k walks interior row k of the tile");
+    static_assert(FC_CHUNK == 64, "the steps of a chunk are the lanes of a wave");
+    static_assert(NT >= 1 && NT <= FC_WAVES, "wave q owns threshold q");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int iy0 = blockIdx.y * FC_ROWS, wpr = gridDim.x;
+    const long cell = (long)blockIdx.y * gridDim.x + blockIdx.x, cells = (long)gridDim.y * gridDim.x;
+    const TileLane t = tile_lane(blockIdx.x, iy0, ih, iw, x0);
+    const bool walks = wave < t.rows;          // wave-uniform; the words of the other rows stay zero
+    const bool mine = wave < NT;               // wave q owns threshold q
+    unsigned short* ps = pix + ((long)(iy0 + wave) * wpr + blockIdx.x) * 64 + lane;
+    const long pslice = (long)ih * wpr * 64;
+    const long mycell = (long)(mine ? wave : 0) * cells + cell;
+    int* tot = totals + mycell * 4;
+    int run[NT];
+#pragma unroll
+    for (int q = 0; q < NT; ++q) run[q] = (walks && !fresh) ? (int)ps[q * pslice] : 0;
+    CellRuns cr = {0, 0, 0, 0, 0};
+    int ecar = 0;                              // |B| of the last finished row
+    if (mine && !fresh) {
+        cr = {open_runs[mycell], tot[0], tot[1], tot[2], tot[3]};
+        ecar = carry[mycell];
+    }
+    long done_rows = 0;                        // rows of this call that are finished
+
+    for (int c0 = 0; c0 < steps; c0 += FC_CHUNK) {
+        const int cn = min(FC_CHUNK, steps - c0);
+        const int real = max(0, min(cn, n - c0));          // the step after frame n is the flush: no edge anywhere
+        const int cslot = (int)(((long)slot_w + lagged + c0) % ring_slots);     // ring slot of the chunk's first step
+        tile_masks_multi<NT>(src + (long)iy0 * pitch, c0, real, pitch, fstride, t, th, msk);
+        for (int i = real * FC_ROWS + threadIdx.x; i < cn * FC_ROWS; i += FC_WAVES * 64) {
+#pragma unroll
+            for (int q = 0; q < NT; ++q) msk[q * FC_CHUNK * FC_ROWS + i] = 0ull;
+        }
+        __syncthreads();
+        if (walks) {
+            // lane = step of the chunk for the words going in and the counts going out, lane = column for the walk
+            int lo[NT], hi[NT], ended[NT];
+#pragma unroll
+            for (int q = 0; q < NT; ++q) {
+                const unsigned long long col = lane < cn ? msk[(q * FC_CHUNK + lane) * FC_ROWS + wave] : 0ull;
+                lo[q] = (int)(unsigned)col;
+                hi[q] = (int)(unsigned)(col >> 32);
+                ended[q] = 0;                  // runs of this row that ended in range at step `lane`
+            }
+            int slot = cslot;                  // ring slot of this step's frame
+            for (int tl = 0; tl < cn; ++tl) {
+#pragma unroll
+                for (int q = 0; q < NT; ++q) {
+                    const unsigned half = (unsigned)(lane < 32 ? __builtin_amdgcn_readlane(lo[q], tl) : __builtin_amdgcn_readlane(hi[q], tl));
+                    const bool edge = (half >> (lane & 31)) & 1u;
+                    const int len = run[q];
+                    run[q] = edge ? min(len + 1, max_hold + 1) : 0;
+                    const bool ends = !edge && len >= hold && len <= max_hold;
+                    unsigned long long m = __ballot(ends);
+                    if (m) {                   // wave-uniform
+                        unsigned* rq = ring + ((long)q * cells + cell) * ring_slots;
+                        if (lane == tl) ended[q] = __popcll(m);
+                        do {
+                            const int l = __builtin_amdgcn_readlane(len, __ffsll((long long)m) - 1);
+                            const unsigned long long same = __ballot(ends && len == l);
+                            int s = slot - l;  // the run's first frame: 1 <= l <= max_hold < ring_slots
+                            if (s < 0) s += ring_slots;
+                            if (lane == 0) atomicAdd(rq + s, (unsigned)__popcll(same));
+                            m &= ~same;
+                        } while (m);
+                    }
+                }
+                slot = slot + 1 == ring_slots ? 0 : slot + 1;
+            }
+            int s = cslot + lane;              // < 2 * ring_slots: FC_CHUNK < ring_slots
+            if (s >= ring_slots) s -= ring_slots;
+#pragma unroll
+            for (int q = 0; q < NT; ++q) {
+                if (ended[q]) atomicAdd(ring + ((long)q * cells + cell) * ring_slots + s, (unsigned)ended[q] << 16);      // lane < cn
+            }
+        }
+        __syncthreads();
+        // a row is final once max_hold further frames have been seen: a run that still covers it is then too long
+        const bool last = c0 + cn == steps;
+        const long seen = min(c0 + cn, n);
+        const long upto = (flush && last) ? (long)lagged + n : max(0l, lagged + seen - max_hold);
+        if (mine) {                                // lane = row
+            unsigned* rq = ring + mycell * ring_slots;
+            for (long base = done_rows; base < upto; base += FC_CHUNK) {
+                const long i = base + lane;
+                const bool live = i < upto;
+                int s = (int)((slot_w + base) % ring_slots) + lane;
+                if (s >= ring_slots) s -= ring_slots;
+                const unsigned word = live ? atomicExch(rq + s, 0u) : 0u;
+                const int a = (int)(word & 0xffffu), v = (int)(word >> 16);
+                int d = a - v;                     // inclusive scan over the lanes
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const int up = __shfl_up(d, o);
+                    if (lane >= o) d += up;
+                }
+                const int e = ecar + d, ep = e - a + v;        // |B_u|, |B_{u-1}|
+                if (live && cell_counts) {
+                    int* o = cell_counts + (((long)wave * count_rows + i) * cells + cell) * 3;
+                    o[0] = e;
+                    o[1] = a;
+                    o[2] = v;
+                }
+                const long long uni = ep + a;      // |B' or B|
+                const unsigned long long present = __ballot(live && e >= rule.min_edges);
+                const unsigned long long ratio = __ballot(live && uni > 0 && (long long)(a + v) * rule.ratio_den >= (long long)rule.ratio_num * uni);
+                const int cnt = (int)min((long)FC_CHUNK, upto - base);
+                for (int f = 0; f < cnt; ++f) cr.step((present >> f) & 1, (ratio >> f) & 1, rule);
+                ecar += __shfl(d, 63);
+            }
+        }
+        done_rows = max(done_rows, upto);
+    }
+    if (walks) {
+#pragma unroll
+        for (int q = 0; q < NT; ++q) ps[q * pslice] = (unsigned short)run[q];
+    }
+    if (mine && lane == 0) {
+        if (flush) cr.close(rule);
+        open_runs[mycell] = cr.run;
+        carry[mycell] = ecar;
+        tot[0] = cr.covered;
+        tot[1] = cr.runs;
+        tot[2] = cr.present;
+        tot[3] = cr.cuts;
+    }
+}
+
+// The parts of vse_frame_cells_hold_bounded's state for an interior of ih x iw pixels, in this order: pix, ring, carry, open runs.
+struct CellsHoldBoundedLayout {
+    size_t cells, pix_bytes, ring_bytes, per_cell_bytes, total;
+};
+
+CellsHoldBoundedLayout cells_hold_bounded_layout(int ih, int iw, int nt, int max_hold) {
+    CellsHoldBoundedLayout l;
+    l.cells = (size_t)((ih + FC_ROWS - 1) / FC_ROWS) * ((iw + 63) / 64);
+    l.pix_bytes = (size_t)nt * ih * ((iw + 63) / 64) * HOLD_WORD_BYTES;
+    l.ring_bytes = (size_t)nt * l.cells * (max_hold + FC_CHUNK) * sizeof(uint32_t);
+    l.per_cell_bytes = (size_t)nt * l.cells * sizeof(int32_t);
+    l.total = (l.pix_bytes + l.ring_bytes + 2 * l.per_cell_bytes + 7) & ~(size_t)7;
+    return l;
+}
+
+}  // namespace
+
+size_t vse_frame_cells_hold_bounded_bytes(int ih, int iw, int nt, int max_hold) { return cells_hold_bounded_layout(ih, iw, nt, max_hold).total; }
+
+// Called by vse_frame_cells_hold_bounded (vse_runtime.hip) after it has checked the arguments (1 <= nt <= vse_frame_cells_multi_max(), 1 <=
+// hold <= max_hold <= 4000, n + flush >= 1, n + max_hold fits an int); count_rows = the rows of d_cell_counts per threshold.  One launch, and
+// before a clip's first one a clear of everything in the state but the run lengths.
+int vse_frame_cells_hold_bounded_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                                        const int* thresholds, int nt, int hold, int max_hold, int min_edges, int ratio_num, int ratio_den,
+                                        int min_frames, int max_frames, void* d_state, int64_t fed, int flush, int32_t* d_totals,
+                                        int32_t* d_cell_counts, int count_rows, void* stream) {
+    const int ih = y1 - y0 - 2, iw = x1 - x0 - 2;
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
+    const CellRule rule = {min_edges, ratio_num, ratio_den, min_frames, max_frames};
+    CellThresholds th = {};
+    for (int q = 0; q < nt; ++q) th.t[q] = thresholds[q];
+    const dim3 grid((iw + 63) / 64, (ih + FC_ROWS - 1) / FC_ROWS), block(FC_WAVES * 64);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const CellsHoldBoundedLayout l = cells_hold_bounded_layout(ih, iw, nt, max_hold);
+    char* base = reinterpret_cast<char*>(d_state);
+    unsigned short* pix = reinterpret_cast<unsigned short*>(base);
+    unsigned* ring = reinterpret_cast<unsigned*>(base + l.pix_bytes);
+    int* carry = reinterpret_cast<int*>(base + l.pix_bytes + l.ring_bytes);
+    int* open_runs = reinterpret_cast<int*>(base + l.pix_bytes + l.ring_bytes + l.per_cell_bytes);
+    if (fed == 0 && hipMemsetAsync(ring, 0, l.ring_bytes + 2 * l.per_cell_bytes, st) != hipSuccess) return VSE_E_HIP;
+    const int ring_slots = max_hold + FC_CHUNK;
+    const int64_t first = fed > max_hold ? fed - max_hold : 0;         // rows up to this frame went out with earlier calls
+    const int steps = n + (flush ? 1 : 0);
+    int* totals = reinterpret_cast<int*>(d_totals);
+    int* cell_counts = reinterpret_cast<int*>(d_cell_counts);
+#define VSE_CELLS_HOLD_BOUNDED(NT)                                                                                                       \
+    case NT:                                                                                                                             \
+        hipLaunchKernelGGL(frame_cells_hold_bounded_kernel<NT>, grid, block, 0, st, src, n, steps, (long)pitch, (long)frame_stride, x0, ih, iw, \
+                           th, rule, hold, max_hold, ring_slots, (int)((first + 1) % ring_slots), (int)(fed - first), pix, ring, carry,    \
+                           open_runs, fed == 0, flush, totals, cell_counts, count_rows);                                                 \
+        break;
+    switch (nt) {
+        VSE_CELLS_HOLD_BOUNDED(1) VSE_CELLS_HOLD_BOUNDED(2) VSE_CELLS_HOLD_BOUNDED(3) VSE_CELLS_HOLD_BOUNDED(4)
+        VSE_CELLS_HOLD_BOUNDED(5) VSE_CELLS_HOLD_BOUNDED(6) VSE_CELLS_HOLD_BOUNDED(7) VSE_CELLS_HOLD_BOUNDED(8)
+        default: return VSE_E_INVAL;
+    }
+#undef VSE_CELLS_HOLD_BOUNDED
+    static_assert(FC_WAVES == 8, "one instantiation per number of thresholds");
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }

@@ -75,6 +75,11 @@ int vse_frame_cells_hold_launch(const void* d_bgr, int n, int steps, int64_t pit
                                 const int* thresholds, int nt, int hold, int skip, int min_edges, int ratio_num, int ratio_den, int min_frames,
                                 int max_frames, void* d_state, int fresh, int flush, int32_t* d_totals, int32_t* d_cell_counts, int count_rows,
                                 void* stream);                                                                         // frame_change.hip
+size_t vse_frame_cells_hold_bounded_bytes(int ih, int iw, int nt, int max_hold);                                        // frame_change.hip
+int vse_frame_cells_hold_bounded_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                                        const int* thresholds, int nt, int hold, int max_hold, int min_edges, int ratio_num, int ratio_den,
+                                        int min_frames, int max_frames, void* d_state, int64_t fed, int flush, int32_t* d_totals,
+                                        int32_t* d_cell_counts, int count_rows, void* stream);                         // frame_change.hip
 int vse_scene_change_plane_pitch(int aw);                                                                              // scene_cut.hip
 int vse_scene_change_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int scale, int ah, int aw, int search, int bias,
                             void* d_state, int reset, void* d_ws, int32_t* d_counts, void* stream);
@@ -673,6 +678,47 @@ int vse_frame_cells_hold(vse_ctx* c, const void* d_bgr, int n, int src_h, int sr
                                                ratio_num, ratio_den, min_frames, max_frames, d_state, fed == 0, flush != 0, d_totals,
                                                d_cell_counts, n + hold - 1, stream);
     if (rc != VSE_OK) set_err("vse_frame_cells_hold: launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+// ---- locator and calibration on bounded runs (frame_change.hip) -----------------------------------------------------------------
+size_t vse_frame_cells_hold_bounded_state_bytes(int area_h, int area_w, int nt, int max_hold) {
+    if (area_h < 3 || area_w < 3 || nt < 1 || nt > vse_frame_cells_multi_max() || max_hold < 1 || max_hold > FRAME_HOLD_BOUNDED_MAX) return 0;
+    return vse_frame_cells_hold_bounded_bytes(area_h - 2, area_w - 2, nt, max_hold);
+}
+
+int vse_frame_cells_hold_bounded(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0,
+                                 int y1, int x0, int x1, const int* thresholds, int nt, int hold, int max_hold, int min_edges, int ratio_num,
+                                 int ratio_den, int min_frames, int max_frames, void* d_state, int64_t fed, int flush, int32_t* d_totals,
+                                 int32_t* d_cell_counts, void* stream) {
+    if (!check_frames("vse_frame_cells_hold_bounded", c && d_totals && fed >= 0, d_bgr, n, 0, src_h, src_w, pitch, frame_stride, d_state) ||
+        !check_area("vse_frame_cells_hold_bounded", "region", y0, y1, x0, x1, src_h, src_w) ||
+        !check_rule("vse_frame_cells_hold_bounded", ratio_num, ratio_den, min_frames, max_frames))
+        return VSE_E_INVAL;
+    if (!thresholds || nt < 1 || nt > vse_frame_cells_multi_max()) {
+        set_err("vse_frame_cells_hold_bounded: %d thresholds (1..%d, not NULL)", nt, vse_frame_cells_multi_max());
+        return VSE_E_INVAL;
+    }
+    for (int q = 0; q < nt; ++q) {
+        if (thresholds[q] < 1 || thresholds[q] > 255 || (q && thresholds[q] <= thresholds[q - 1])) {
+            set_err("vse_frame_cells_hold_bounded: threshold %d of %d is %d (each 1..255, ascending and distinct)", q, nt, thresholds[q]);
+            return VSE_E_INVAL;
+        }
+    }
+    if (hold < 1 || hold > 32 || max_hold < hold || max_hold > FRAME_HOLD_BOUNDED_MAX) {
+        set_err("vse_frame_cells_hold_bounded: hold %d outside 1..32, or max_hold %d outside hold..%d", hold, max_hold, FRAME_HOLD_BOUNDED_MAX);
+        return VSE_E_INVAL;
+    }
+    // as vse_frame_hold_bounded: the row of a frame is final max_hold frames later, or at the flush, which is one step of its own
+    if ((int64_t)n + max_hold > INT32_MAX) {
+        set_err("vse_frame_cells_hold_bounded: %lld rows do not fit an int", (long long)n + max_hold);
+        return VSE_E_INVAL;
+    }
+    if (n == 0 && !flush) return VSE_OK;
+    const int rc = vse_frame_cells_hold_bounded_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, thresholds, nt, hold, max_hold, min_edges,
+                                                       ratio_num, ratio_den, min_frames, max_frames, d_state, fed, flush != 0, d_totals,
+                                                       d_cell_counts, n + max_hold, stream);
+    if (rc != VSE_OK) set_err("vse_frame_cells_hold_bounded: launch failed: %s", hipGetErrorString(hipGetLastError()));
     return rc;
 }
 

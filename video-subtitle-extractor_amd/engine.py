@@ -29,6 +29,7 @@ EXPORTS = [
     "vse_yuv_to_bgr_matrix", "vse_frame_cells_multi_state_bytes", "vse_frame_cells_multi",
     "vse_frame_cells_hold_state_bytes", "vse_frame_cells_hold", "vse_frame_focus",
     "vse_frame_hold_bounded_state_bytes", "vse_frame_hold_bounded",
+    "vse_frame_cells_hold_bounded_state_bytes", "vse_frame_cells_hold_bounded",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -189,6 +190,11 @@ def load_library(path=None):
     lib.vse_frame_cells_hold.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vse_frame_cells_hold_bounded_state_bytes.restype = C.c_size_t
+    lib.vse_frame_cells_hold_bounded_state_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.vse_frame_cells_hold_bounded.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                                 C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vse_interval_state_bytes.restype = C.c_size_t
     lib.vse_interval_state_bytes.argtypes = [C.c_int, C.c_int]
     lib.vse_interval_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
@@ -678,6 +684,44 @@ class Context:
                                              int(bool(flush)), C.c_void_p(state.totals.data_ptr()),
                                              C.c_void_p(counts.data_ptr()) if want_counts and counts.numel() else None, self.stream()),
                "vse_frame_cells_hold")
+        return (state.totals, counts[:, :rows]) if want_counts else state.totals
+
+    # ---- locator and calibration on bounded runs -------------------------------------------------------------------
+    def frame_cells_hold_bounded_state(self, area_h, area_w, nt, max_hold):
+        """A CellsState for frame_cells_hold_bounded over a region of area_h x area_w pixels with nt thresholds and this `max_hold`; its
+        totals are cuda int32 [nt,gy,gx,4]."""
+        gy, gx = self.frame_cells_dims(area_h, area_w)
+        nbytes = self.lib.vse_frame_cells_hold_bounded_state_bytes(int(area_h), int(area_w), int(nt), int(max_hold))
+        if not nbytes:
+            raise VseError(f"frame_cells_hold_bounded: {nt} thresholds (1..8) or max_hold {max_hold} (1..{FRAME_HOLD_BOUNDED_MAX})")
+        t = self.torch
+        return CellsState(t.zeros(nbytes, dtype=t.uint8, device=self.tdev), t.zeros((int(nt), gy, gx, 4), dtype=t.int32, device=self.tdev))
+
+    def frame_cells_hold_bounded(self, frames_u8, area, thresholds, hold, max_hold, params, state, fed, flush=False, want_counts=False):
+        """frame_cells_hold on the bounded masks of frame_hold_bounded: frames_u8, area, thresholds, hold, params and fed as there,
+        `max_hold` as for frame_hold_bounded, state: frame_cells_hold_bounded_state of the area's size, len(thresholds) and `max_hold`
+        -> state.totals, cuda int32 [nt,gy,gx,4]: the frames whose row is final, which trail the frames fed by max_hold, all of them
+        after `flush` (include/vse_hip.h vse_frame_cells_hold_bounded); with want_counts (totals, cuda int32 [nt,rows,gy,gx,3] bounded
+        edges / appeared / vanished per cell of the frames this call completes, frame_hold_bounded's rows cell by cell)."""
+        t = self.torch
+        frames = self._frames_args(frames_u8, allow_empty=True)
+        n = frames[1]
+        y0, y1, x0, x1 = (int(v) for v in area)
+        th = [int(v) for v in thresholds]
+        nt, hold, max_hold, fed = len(th), int(hold), int(max_hold), int(fed)
+        gy, gx = self.frame_cells_dims(y1 - y0, x1 - x0)
+        nbytes = self.lib.vse_frame_cells_hold_bounded_state_bytes(y1 - y0, x1 - x0, nt, max_hold)
+        assert nbytes and state.words.numel() >= nbytes and tuple(state.totals.shape) == (nt, gy, gx, 4)
+        rows = (fed + n if flush else max(0, fed + n - max_hold)) - max(0, fed - max_hold)
+        counts = t.empty((nt, n + max_hold, gy, gx, 3), dtype=t.int32, device=self.tdev) if want_counts else None
+        p = CellParams(*(int(v) for v in params))
+        _check(self.lib.vse_frame_cells_hold_bounded(self.handle, *frames, y0, y1, x0, x1, (C.c_int * nt)(*th), nt, hold, max_hold,
+                                                     p.min_edges, p.ratio_num, p.ratio_den, p.min_frames, p.max_frames,
+                                                     C.c_void_p(state.words.data_ptr()), fed, int(bool(flush)),
+                                                     C.c_void_p(state.totals.data_ptr()),
+                                                     C.c_void_p(counts.data_ptr()) if want_counts and counts.numel() else None,
+                                                     self.stream()),
+               "vse_frame_cells_hold_bounded")
         return (state.totals, counts[:, :rows]) if want_counts else state.totals
 
     # ---- interval composite ---------------------------------------------------------------------------------------

@@ -253,7 +253,8 @@ class SubtitleExtractor:
     hold for hold .. max_hold frames are counted, so what stands still for longer than a subtitle does drops out
     (frame_select.HoldFrameSelector has the limits: a subtitle shown for longer than that disappears too, and 12-15 s is a guess).  The
     selector's rows then trail its frames by max_hold, so one pass keeps about max_hold more frames (360 frames of 1080p 4:2:0 at 15 s
-    and 24 fps are 1.1 GB; `retain_bytes` stays the fallback).  The locator and the calibration (`area_params`) ignore it.
+    and 24 fps are 1.1 GB; `retain_bytes` stays the fallback).  The locator and the calibration do not inherit it: they bound their
+    runs only when `area_params` carries a max_hold_seconds / max_hold_frames of its own (below).
     interval_image="min" | "max" | "mean" (change selector only; default "middle", the above): one recognition error on that single
     frame is final, so the recogniser is instead shown, inside the area of the same middle frame, the per-pixel minimum (light
     text) / maximum (dark text) / mean of ALL frames of the interval, one more pass over the area's rows on the device
@@ -286,6 +287,11 @@ class SubtitleExtractor:
     area_params={"automaton": "hold"}: the locator and the calibration count held edges (area_locator's module text), which is what a
     textured background that moves behind the subtitles needs; with frame_selector="hold" they take the selector's hold_seconds /
     hold_frames from change_params unless area_params sets its own.  Opt-in: without it nothing changes.
+    area_params={"automaton": "hold", "max_hold_seconds": 12} (or "max_hold_frames"): the locator pass, and the calibration pass with a
+    given area, count only edges whose run is hold .. max_hold frames long (area_locator's module text has the limits), which is what
+    a busy background that stands still behind the subtitles needs: on held edges alone its cells fall to the logo rule and neither
+    an area nor a threshold is found.  It is NOT inherited from change_params as hold_seconds is: runs that set the selector's
+    max_hold_* together with automaton="hold" keep their results, and the locator bounds its runs only when area_params says so.
     one_pass (None: exactly when the source has no `read`, e.g. ingest.Y4mStream over a pipe; True forces it on a seekable source and
     halves its decode work; False on a sequential source is a ValueError): the clip is read once, in decode order.  frame_selector="fps":
     frame `no` is a task iff (no - 1) % max(1, int(fps // extract_frequency)) == 0 (fps_tasks' rule without the frame count); tasks go
@@ -683,6 +689,9 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
                    "too, and one pass keeps S seconds more of frames [none: no bound]")
     p.add_argument("--locator-automaton", default="change", choices=("change", "hold"), help="what `--area auto` and `--edge-thresh auto` "
                    "count: every edge pixel, or with `hold` only edges that hold still (a textured background that moves) [change]")
+    p.add_argument("--locator-max-hold-seconds", type=float, default=None, metavar="S", help="--locator-automaton hold: `--area auto` and "
+                   "`--edge-thresh auto` count only edges that hold still for at most S seconds (a busy background that stands still); "
+                   "independent of --max-hold-seconds [none: no bound]")
     p.add_argument("--interval-image", default="middle", choices=INTERVAL_IMAGES, help="change / hold selector: what the recogniser is "
                    "shown for each subtitle: its middle frame, the per-pixel min (light text) / max (dark text) / mean of all its frames, "
                    "or the per-pixel quantile of a few evenly spaced ones, which needs no polarity and shrugs off a flash or a late cut "
@@ -718,6 +727,9 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
             if args.selector != "hold":
                 raise ValueError(f"--max-hold-seconds bounds the runs of `--selector hold`, not of `--selector {args.selector}`")
             change_params["max_hold_seconds"] = args.max_hold_seconds
+        if args.locator_max_hold_seconds is not None and args.locator_automaton != "hold":
+            raise ValueError(f"--locator-max-hold-seconds bounds the runs of `--locator-automaton hold`, not of `--locator-automaton "
+                             f"{args.locator_automaton}`")
         composite_params = None
         if args.interval_image == "quantile":
             composite_params = {"quantile": args.quantile, "samples": args.interval_samples, "rank_fn": composite_fn}
@@ -740,7 +752,9 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
                                frame_params=None if focus_fn is None else {"focus_fn": focus_fn},
                                change_params=change_params or None,
                                area_params={**({} if cells_fn is None else {"cells_fn": cells_fn}),
-                                            **({} if args.locator_automaton == "change" else {"automaton": args.locator_automaton})} or None)
+                                            **({} if args.locator_automaton == "change" else {"automaton": args.locator_automaton}),
+                                            **({} if args.locator_max_hold_seconds is None
+                                               else {"max_hold_seconds": args.locator_max_hold_seconds})} or None)
         text = ex.run()
         if args.output is None:
             sys.stdout.write(text)
