@@ -510,6 +510,47 @@ int vse_interval_composite(vse_ctx* ctx, const void* d_state, int area_h, int ar
 #define VSE_INTERVAL_RANK_MAX 63
 int vse_interval_rank(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride,
                       int y0, int y1, int x0, int x1, int rank, void* d_out, int64_t out_pitch, void* stream);
+/* Replaces: the second pass over the clip that vse_interval_accumulate / vse_interval_composite need (the reference has none: its
+ * closed binary makes its pictures while it reads the film once, backend/main.py:378-505).  The same mn / mx / sm and the same three
+ * modes, made in the selector's own pass (vse_amd.frame_select.StreamingCompositor): one call folds any number of SEGMENTS of
+ * consecutive frames, writes the composite of every segment that ends a subtitle, and parks the frames whose fate is still open in
+ * a small ring on the device, so a sequential source (a pipe) needs no second look at frames already gone.
+ * Frames carry absolute 1-based numbers.  The n >= 0 frames of a call are frames fed + 1 .. fed + n (with n = 0, d_bgr may be
+ * NULL).  The state holds the accumulators of vse_interval_state_bytes and behind them `cap` ring slots of one area band each (rows
+ * padded to 16 bytes); frame f lives in slot f % cap.  A segment may read a batch frame, or a ring frame f <= fed with f > fed - cap
+ * that an earlier call stored and no later store has replaced: the caller keeps that book, the library checks only the numbers.
+ * After ALL segment reads of the call, the batch frames f >= store_from are written to their slots (area bytes only), so a segment
+ * sees the ring as earlier calls left it even where this call's stores replace what it reads.
+ * Segments ascend and are disjoint.  flags: 1 = CONTINUE, start from the state's accumulators (what an earlier call's last segment
+ * left there) instead of from `first` alone: only the first segment may; 2 = EMIT, write the composite of the segment (mode 0 mn,
+ * 1 mx, 2 the mean (2 sm + frames) / (2 frames) with `frames` = all frames folded into this picture, earlier calls included,
+ * 1..4194304) to patch `out`: d_out + out * out_stride, rows `out_pitch` bytes apart, exactly the 3 area_w bytes of each row.  Only
+ * the last segment may lack EMIT: its mn / mx / sm are then left in the accumulators for a later CONTINUE; after a call whose last
+ * segment EMITs their content is unspecified.  Nothing advances implicitly: the same batch may be passed again with the same fed
+ * and n (more segments than the maximum); stores are idempotent.
+ * Loads as vse_interval_accumulate's (16-byte ones where area start, pitch and frame stride allow, the aligned dwords around the
+ * area's bytes otherwise); ring slots are always 16-byte aligned.  At most one launch on `stream`, no allocation, no device sync,
+ * no atomics.
+ * Returns VSE_E_INVAL, without touching the device, for everything vse_interval_accumulate refuses about frames, pitch, stride and
+ * area (a NULL d_bgr only for n > 0; n outside 0..65535), cap < 1, fed negative or above 2^62 (fed + n must not overflow), nseg outside 0..VSE_INTERVAL_STREAM_MAX_SEGS, a segment with
+ * first > last or first < 1, out of order, or with a frame outside (fed - cap, fed + n], CONTINUE on a segment other than the first, a segment
+ * without EMIT that is not the last, unknown flag bits, mode outside 0..2, with an EMIT: a NULL d_out, a negative `out`, out_pitch
+ * < 3 area_w, and with mode 2 `frames` outside 1..4194304; or a state that is not 16-byte aligned. */
+typedef struct {
+    int64_t first, last;   /* absolute 1-based frame numbers, inclusive, first <= last */
+    int32_t flags;         /* VSE_INTERVAL_SEG_CONTINUE | VSE_INTERVAL_SEG_EMIT */
+    int32_t frames;        /* EMIT with mode 2: the frames folded into this picture, earlier calls included */
+    int32_t out;           /* EMIT: the patch written */
+} vse_interval_seg;
+#define VSE_INTERVAL_SEG_CONTINUE 1
+#define VSE_INTERVAL_SEG_EMIT 2
+#define VSE_INTERVAL_STREAM_MAX_SEGS 32
+/* vse_interval_state_bytes(area_h, area_w) + cap ring slots of area_h rows padded to 16 bytes; 0 for an empty area or cap < 1. */
+size_t vse_interval_stream_state_bytes(int area_h, int area_w, int cap);
+int vse_interval_stream(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride,
+                        int y0, int y1, int x0, int x1, void* d_state, int cap, int64_t fed,
+                        const vse_interval_seg* segs /* host, [nseg] */, int nseg, int64_t store_from, int mode /* 0 min, 1 max, 2 mean */,
+                        void* d_out, int64_t out_pitch, int64_t out_stride, void* stream);
 
 /* ---- timeline sync: audio template search ----------------------------------------------------------------------------- */
 /* Replaces: Sushi's WavStream.find_substream (backend/sushi/wav.py:179-189), cv2.matchTemplate(TM_SQDIFF_NORMED) of one group's

@@ -198,6 +198,136 @@ __global__ __launch_bounds__(IV_THREADS) void interval_composite_kernel(const ui
     }
 }
 
+// ---- interval stream ----------------------------------------------------------------------------------------------------------
+// vse_interval_stream: the accumulate and composite kernels above in ONE launch over any number of segments, plus a ring of parked
+// frames behind the accumulators (state = mn | mx | sm | cap slots of one padded band each, frame f in slot f % cap).  The lane layout
+// is the accumulate kernel's: a lane owns run i of the padded band for the whole call, in the batch, in every ring slot, in the
+// accumulators and in every patch, so its segment reads and its ring stores touch no byte another lane touches and their order is
+// program order within the lane: all segments first, then the stores.  Frames are numbered relative to the call, rel = f - fed:
+// rel >= 1 is batch frame rel - 1, rel <= 0 the ring frame in slot (fed % cap + rel) mod cap.  A segment is folded as up to three
+// runs of evenly strided frames (ring up to the wrap, ring behind it, batch), each through accumulate_run with IV_DEPTH loads in
+// flight; ring runs are whole and aligned whatever the area, so they always take the 16-byte load.  The segments travel as kernel
+// arguments (uniform, read through scalar loads): no device copy of host memory.
+struct StreamSegs {
+    int lo[VSE_INTERVAL_STREAM_MAX_SEGS], hi[VSE_INTERVAL_STREAM_MAX_SEGS];        // rel of first and last
+    int flags[VSE_INTERVAL_STREAM_MAX_SEGS], frames[VSE_INTERVAL_STREAM_MAX_SEGS], out[VSE_INTERVAL_STREAM_MAX_SEGS];
+};
+
+__device__ __forceinline__ void acc_reset(Acc& a) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) a.mn[k] = 255u, a.mx[k] = 0u, a.sm[k] = 0u;
+}
+
+// p = this lane's run in batch frame 0 (unused where n == 0), ring = its run in slot 0, slot = bytes from one slot to the next.
+template <bool WIDE>
+__device__ __forceinline__ void stream_lane(const uint8_t* p, int n, long fstride, int nb, uint8_t* ring, long slot, int cap, int base,
+                                            const StreamSegs& sg, int nseg, int store_rel, int mode, uint4* smn, uint4* smx, uint4* ssm,
+                                            uint8_t* o, long out_stride) {
+    Acc a;
+    for (int s = 0; s < nseg; ++s) {
+        const int lo = sg.lo[s], hi = sg.hi[s], flags = sg.flags[s];
+        if (flags & VSE_INTERVAL_SEG_CONTINUE) {          // (the first segment only)
+            const uint4 vn = *smn, vx = *smx;
+            const unsigned wn[4] = {vn.x, vn.y, vn.z, vn.w}, wx[4] = {vx.x, vx.y, vx.z, vx.w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint4 vs = ssm[q];
+                a.sm[4 * q] = vs.x, a.sm[4 * q + 1] = vs.y, a.sm[4 * q + 2] = vs.z, a.sm[4 * q + 3] = vs.w;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    a.mn[4 * q + k] = (wn[q] >> (8 * k)) & 255u;
+                    a.mx[4 * q + k] = (wx[q] >> (8 * k)) & 255u;
+                }
+            }
+        } else {
+            acc_reset(a);
+        }
+        if (lo <= 0) {
+            const int count = min(hi, 0) - lo + 1;
+            int s0 = base + lo;
+            s0 += s0 < 0 ? cap : 0;
+            const int c1 = min(count, cap - s0);
+            accumulate_run<true>(a, ring + (long)s0 * slot, c1, slot, 16);
+            accumulate_run<true>(a, ring, count - c1, slot, 16);
+        }
+        if (hi >= 1) {
+            const int blo = max(lo, 1);
+            accumulate_run<WIDE>(a, p + (long)(blo - 1) * fstride, hi - blo + 1, fstride, nb);
+        }
+        if (flags & VSE_INTERVAL_SEG_EMIT) {
+            unsigned w[4];
+            if (mode == 2) {
+                const unsigned frames = (unsigned)sg.frames[s];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    unsigned b[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) b[k] = ((2u * a.sm[4 * q + k] + frames) / (2u * frames)) & 255u;
+                    w[q] = pack4(b);
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    unsigned b[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) b[k] = mode == 1 ? a.mx[4 * q + k] : a.mn[4 * q + k];      // (selects: no pointer into registers)
+                    w[q] = pack4(b);
+                }
+            }
+            uint8_t* op = o + (long)sg.out[s] * out_stride;
+            if (nb == 16 && (reinterpret_cast<uintptr_t>(op) & 15) == 0) {
+                *reinterpret_cast<uint4*>(op) = make_uint4(w[0], w[1], w[2], w[3]);
+            } else {
+                for (int k = 0; k < nb; ++k) op[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+            }
+        } else {                                           // (the last segment only)
+            *smn = make_uint4(pack4(a.mn), pack4(a.mn + 4), pack4(a.mn + 8), pack4(a.mn + 12));
+            *smx = make_uint4(pack4(a.mx), pack4(a.mx + 4), pack4(a.mx + 8), pack4(a.mx + 12));
+#pragma unroll
+            for (int q = 0; q < 4; ++q) ssm[q] = make_uint4(a.sm[4 * q], a.sm[4 * q + 1], a.sm[4 * q + 2], a.sm[4 * q + 3]);
+        }
+    }
+    // the stores: batch frames rel = store_rel .. n into their slots, IV_DEPTH loads in flight
+    if (store_rel > n) return;
+    int sidx = (int)(((unsigned)base + (unsigned)store_rel) % (unsigned)cap);
+    for (int r0 = store_rel; r0 <= n; r0 += IV_DEPTH) {
+        Raw<WIDE> raw[IV_DEPTH];
+#pragma unroll
+        for (int u = 0; u < IV_DEPTH; ++u) raw[u] = load_run<WIDE>(p + (long)(min(r0 + u, n) - 1) * fstride, nb);
+#pragma unroll
+        for (int u = 0; u < IV_DEPTH; ++u) {
+            if (r0 + u <= n) {         // uniform
+                unsigned w[4];
+                unpack<WIDE>(raw[u], w);
+                *reinterpret_cast<uint4*>(ring + (long)sidx * slot) = make_uint4(w[0], w[1], w[2], w[3]);
+                sidx = sidx + 1 == cap ? 0 : sidx + 1;
+            }
+        }
+    }
+}
+
+// src, rb, cpr, items, plane as for interval_accumulate_kernel; the ring starts 6 planes into the state and a slot is one plane.
+template <bool WIDE>
+__global__ __launch_bounds__(IV_THREADS) void interval_stream_kernel(const uint8_t* __restrict__ src, int n, long pitch, long fstride, int rb,
+                                                                     unsigned cpr, unsigned items, uint8_t* state, long plane, int cap,
+                                                                     int base, const StreamSegs sg, int nseg, int store_rel, int mode,
+                                                                     uint8_t* __restrict__ out, long out_pitch, long out_stride) {
+    const unsigned i = blockIdx.x * IV_THREADS + threadIdx.x;
+    if (i >= items) return;
+    const unsigned r = i / cpr, c = i - r * cpr;
+    const int nb = min(16, rb - 16 * (int)c);
+    uint4* smn = reinterpret_cast<uint4*>(state + (long)i * 16);
+    uint4* smx = reinterpret_cast<uint4*>(state + plane + (long)i * 16);
+    uint4* ssm = reinterpret_cast<uint4*>(state + 2 * plane + (long)i * 64);
+    uint8_t* ring = state + 6 * plane + (long)i * 16;
+    const uint8_t* p = src + (long)r * pitch + 16 * (long)c;
+    uint8_t* o = out + (long)r * out_pitch + 16 * (long)c;
+    if (WIDE && nb == 16)
+        stream_lane<true>(p, n, fstride, nb, ring, plane, cap, base, sg, nseg, store_rel, mode, smn, smx, ssm, o, out_stride);
+    else
+        stream_lane<false>(p, n, fstride, nb, ring, plane, cap, base, sg, nseg, store_rel, mode, smn, smx, ssm, o, out_stride);
+}
+
 // ---- interval rank ----------------------------------------------------------------------------------------------------------
 // The samples of the run of nb bytes at p in frames 0 .. n - 1, slots from n on 0xFF bytes.  WIDE: p and fstride are 4-byte aligned and
 // a slot is one aligned dword.  General: the aligned dwords around the run (the second one only where it holds a byte of the run,
@@ -368,6 +498,90 @@ int vse_interval_composite(vse_ctx* c, const void* d_state, int area_h, int area
                        cpr, items, (unsigned)frames, mode, reinterpret_cast<uint8_t*>(d_out), (long)out_pitch);
     if (hipGetLastError() != hipSuccess) {
         vse_set_error("vse_interval_composite: launch failed");
+        return VSE_E_HIP;
+    }
+    return VSE_OK;
+}
+
+size_t vse_interval_stream_state_bytes(int area_h, int area_w, int cap) {
+    if (!area_fits(area_h, area_w) || cap < 1) return 0;
+    return (size_t)area_h * row_bytes16(area_w) * (6 + (size_t)cap);
+}
+
+int vse_interval_stream(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0,
+                        int x1, void* d_state, int cap, int64_t fed, const vse_interval_seg* segs, int nseg, int64_t store_from, int mode,
+                        void* d_out, int64_t out_pitch, int64_t out_stride, void* stream) {
+    char msg[400];
+    if (!c || !d_state || n < 0 || n > 65535 || (n > 0 && !d_bgr) || src_h < 1 || src_w < 1 || pitch < (int64_t)src_w * 3 ||
+        (n > 1 && frame_stride < (int64_t)(src_h - 1) * pitch + (int64_t)src_w * 3) || (reinterpret_cast<uintptr_t>(d_state) & 15)) {
+        snprintf(msg, sizeof msg, "vse_interval_stream: bad arguments (n %d of 0..65535, frame %d x %d, pitch %lld of at least 3 w, frame "
+                 "stride %lld, state 16-byte aligned)", n, src_h, src_w, (long long)pitch, (long long)frame_stride);
+        vse_set_error(msg);
+        return VSE_E_INVAL;
+    }
+    if (y0 < 0 || x0 < 0 || y1 > src_h || x1 > src_w || y1 <= y0 || x1 <= x0 || !area_fits(y1 - y0, x1 - x0)) {
+        snprintf(msg, sizeof msg, "vse_interval_stream: area [%d, %d) x [%d, %d) is empty or outside the %d x %d frame", y0, y1, x0, x1, src_h,
+                 src_w);
+        vse_set_error(msg);
+        return VSE_E_INVAL;
+    }
+    if (cap < 1 || fed < 0 || fed > ((int64_t)1 << 62) || nseg < 0 || nseg > VSE_INTERVAL_STREAM_MAX_SEGS || (nseg > 0 && !segs) || mode < 0 ||
+        mode > 2) {
+        snprintf(msg, sizeof msg, "vse_interval_stream: cap %d of at least 1, fed %lld of 0..2^62, %d segments of 0..%d, mode %d of 0 | 1 | 2",
+                 cap, (long long)fed, nseg, VSE_INTERVAL_STREAM_MAX_SEGS, mode);
+        vse_set_error(msg);
+        return VSE_E_INVAL;
+    }
+    StreamSegs sg = {};
+    int64_t prev = fed - cap;                 // every frame read is behind this one
+    for (int s = 0; s < nseg; ++s) {
+        const vse_interval_seg& g = segs[s];
+        const bool emit = g.flags & VSE_INTERVAL_SEG_EMIT;
+        const char* bad = nullptr;
+        if (g.first > g.last || g.first < 1 || g.first <= prev || g.last > fed + n)
+            bad = "its frames (1-based) must ascend behind the segment before it inside (fed - cap, fed + n]";
+        else if (g.flags & ~(VSE_INTERVAL_SEG_CONTINUE | VSE_INTERVAL_SEG_EMIT))
+            bad = "unknown flags";
+        else if ((g.flags & VSE_INTERVAL_SEG_CONTINUE) && s != 0)
+            bad = "only the first segment may CONTINUE";
+        else if (!emit && s != nseg - 1)
+            bad = "only the last segment may lack EMIT";
+        else if (emit && (!d_out || g.out < 0 || out_pitch < (int64_t)(x1 - x0) * 3))
+            bad = "an EMIT needs d_out, out >= 0 and out_pitch of at least 3 area_w";
+        else if (emit && mode == 2 && (g.frames < 1 || g.frames > MAX_FRAMES))
+            bad = "frames of a mean must be 1..4194304";
+        if (bad) {
+            snprintf(msg, sizeof msg, "vse_interval_stream: segment %d (frames %lld..%lld, flags %d, frames %d, out %d; fed %lld, n %d, cap %d): %s",
+                     s, (long long)g.first, (long long)g.last, g.flags, g.frames, g.out, (long long)fed, n, cap, bad);
+            vse_set_error(msg);
+            return VSE_E_INVAL;
+        }
+        prev = g.last;
+        sg.lo[s] = (int)(g.first - fed), sg.hi[s] = (int)(g.last - fed);         // in (-cap, n]
+        sg.flags[s] = g.flags, sg.frames[s] = emit && mode == 2 ? g.frames : 1, sg.out[s] = emit ? g.out : 0;
+    }
+    const int64_t from = store_from > fed + 1 ? store_from : fed + 1;
+    const int store_rel = from > fed + n ? n + 1 : (int)(from - fed);            // 1 .. n + 1
+    if (nseg == 0 && store_rel > n) return VSE_OK;                               // nothing to read, nothing to store
+    const int ah = y1 - y0, rb = (x1 - x0) * 3;
+    const unsigned cpr = (unsigned)(row_bytes16(x1 - x0) / 16), items = (unsigned)ah * cpr;
+    const long plane = (long)ah * (long)cpr * 16;
+    const uint8_t* src = n ? reinterpret_cast<const uint8_t*>(d_bgr) + (int64_t)y0 * pitch + (int64_t)x0 * 3 : nullptr;
+    const long kp = n ? (long)pitch : 0, ks = n > 1 ? (long)frame_stride : 0;    // (no stride to speak of without frames)
+    const dim3 grid((items + IV_THREADS - 1) / IV_THREADS), block(IV_THREADS);
+    const bool wide = n > 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && multiple16(pitch) && (n == 1 || multiple16(frame_stride));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    uint8_t* state = reinterpret_cast<uint8_t*>(d_state);
+    uint8_t* out = reinterpret_cast<uint8_t*>(d_out);
+    const int base = (int)(fed % cap);
+    if (wide)
+        hipLaunchKernelGGL(interval_stream_kernel<true>, grid, block, 0, st, src, n, kp, ks, rb, cpr, items, state, plane, cap, base, sg, nseg,
+                           store_rel, mode, out, (long)out_pitch, (long)out_stride);
+    else
+        hipLaunchKernelGGL(interval_stream_kernel<false>, grid, block, 0, st, src, n, kp, ks, rb, cpr, items, state, plane, cap, base, sg, nseg,
+                           store_rel, mode, out, (long)out_pitch, (long)out_stride);
+    if (hipGetLastError() != hipSuccess) {
+        vse_set_error("vse_interval_stream: launch failed");
         return VSE_E_HIP;
     }
     return VSE_OK;

@@ -30,6 +30,7 @@ EXPORTS = [
     "vse_frame_cells_hold_state_bytes", "vse_frame_cells_hold", "vse_frame_focus",
     "vse_frame_hold_bounded_state_bytes", "vse_frame_hold_bounded",
     "vse_frame_cells_hold_bounded_state_bytes", "vse_frame_cells_hold_bounded",
+    "vse_interval_stream_state_bytes", "vse_interval_stream",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -55,7 +56,7 @@ class CellsState:
 
 class DeviceState:
     """Base of the callables that run a stateful kernel on a Context batch by batch (frame_select.EngineCounter, EngineHoldCounter,
-    EngineCompositor, area_locator.EngineCells, keyframes.EngineSceneCounter): host frames become a device tensor, and the device
+    EngineCompositor, EngineStreamer, area_locator.EngineCells, keyframes.EngineSceneCounter): host frames become a device tensor, and the device
     state is allocated afresh when the geometry it was made for changes."""
 
     def __init__(self, ctx):
@@ -72,6 +73,11 @@ class DeviceState:
             return False
         self._key, self._state = key, make(*key)
         return True
+
+
+class IntervalSeg(C.Structure):
+    """vse_interval_seg (include/vse_hip.h)."""
+    _fields_ = [("first", C.c_int64), ("last", C.c_int64), ("flags", C.c_int32), ("frames", C.c_int32), ("out", C.c_int32)]
 
 
 class DbParams(C.Structure):
@@ -202,6 +208,11 @@ def load_library(path=None):
     lib.vse_interval_composite.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
     lib.vse_interval_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.vse_interval_stream_state_bytes.restype = C.c_size_t
+    lib.vse_interval_stream_state_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.vse_interval_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, C.c_void_p, C.c_int, C.c_int64, C.POINTER(IntervalSeg), C.c_int, C.c_int64, C.c_int,
+                                        C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
     lib.vse_audio_match_workspace_bytes.restype = C.c_size_t
     lib.vse_audio_match_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
     lib.vse_audio_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
@@ -778,6 +789,44 @@ class Context:
                "vse_interval_rank")
         return out
 
+    def interval_stream_state(self, area_h, area_w, cap):
+        """A state for interval_stream over an area of area_h x area_w pixels with a ring of `cap` frames."""
+        nbytes = self.lib.vse_interval_stream_state_bytes(int(area_h), int(area_w), int(cap))
+        if not nbytes:
+            raise VseError(f"interval_stream: an area of {area_h} x {area_w} pixels is empty, or cap {cap} is below 1")
+        return self.torch.zeros(nbytes, dtype=self.torch.uint8, device=self.tdev)
+
+    def interval_stream(self, frames_u8, area, state, cap, fed, segs, store_from, mode, out=None):
+        """frames_u8: cuda uint8 [n,H,W,3], n >= 0: the frames fed + 1 .. fed + n of the clip (any row pitch / frame stride, pixels
+        packed), area = (y0, y1, x0, x1) in its pixels, state: interval_stream_state of the area's size and `cap`, segs: up to
+        INTERVAL_STREAM_MAX_SEGS of (first, last, flags, frames[, out]) with absolute 1-based frame numbers and flags of
+        INTERVAL_SEG_CONTINUE | INTERVAL_SEG_EMIT (without `out`, the EMITs are numbered 0, 1, .. in order), store_from: the batch
+        frames from this number on are parked in the ring, mode: "min" | "max" | "mean" -> cuda uint8 [patches, y1-y0, x1-x0, 3], one
+        composite per EMIT (include/vse_hip.h vse_interval_stream).  out: write into this tensor instead (it may be a strided view
+        with packed pixels; its row pitch and patch stride are taken from it)."""
+        t = self.torch
+        frames = self._frames_args(frames_u8, allow_empty=True)
+        y0, y1, x0, x1 = (int(v) for v in area)
+        area_h, area_w = y1 - y0, x1 - x0
+        if mode not in INTERVAL_MODES:
+            raise VseError(f"interval_stream: mode {mode!r} is not one of {sorted(INTERVAL_MODES)}")
+        assert state.dtype == t.uint8 and state.is_contiguous()
+        assert state.numel() >= max(self.lib.vse_interval_stream_state_bytes(area_h, area_w, int(cap)), 1)
+        recs, emits = (IntervalSeg * max(len(segs), 1))(), 0
+        for k, g in enumerate(segs):
+            emit = bool(int(g[2]) & INTERVAL_SEG_EMIT)
+            recs[k] = IntervalSeg(int(g[0]), int(g[1]), int(g[2]), int(g[3]), int(g[4]) if len(g) > 4 else (emits if emit else 0))
+            emits = max(emits, recs[k].out + 1) if emit else emits
+        if out is None:
+            out = t.empty((emits, max(area_h, 0), max(area_w, 0), 3), dtype=t.uint8, device=self.tdev)
+        assert out.dtype == t.uint8 and tuple(out.shape[1:]) == (area_h, area_w, 3) and out.shape[0] >= emits
+        assert out.stride(3) == 1 and out.stride(2) == 3
+        _check(self.lib.vse_interval_stream(self.handle, *frames, y0, y1, x0, x1, C.c_void_p(state.data_ptr()), int(cap), int(fed), recs,
+                                            len(segs), int(store_from), INTERVAL_MODES[mode], C.c_void_p(out.data_ptr()) if emits else None,
+                                            out.stride(1) if area_h > 1 else max(out.stride(1), 3 * area_w), out.stride(0), self.stream()),
+               "vse_interval_stream")
+        return out
+
     # ---- timeline sync: audio template search ---------------------------------------------------------------------
     def audio_match_workspace_bytes(self, queries):
         """Workspace bytes of one audio_match call with these (src_off, m, dst_off, win_len) queries (0 if one is invalid)."""
@@ -908,6 +957,8 @@ class Context:
 YUV_LAYOUTS = {"i420": 0, "nv12": 1}
 YUV_MATRICES = {"bt601": 0, "bt709": 1}
 INTERVAL_MODES = {"min": 0, "max": 1, "mean": 2}
+INTERVAL_SEG_CONTINUE, INTERVAL_SEG_EMIT = 1, 2          # vse_interval_seg.flags (include/vse_hip.h)
+INTERVAL_STREAM_MAX_SEGS = 32   # VSE_INTERVAL_STREAM_MAX_SEGS: the segments of one vse_interval_stream call
 INTERVAL_RANK_MAX = 63          # VSE_INTERVAL_RANK_MAX (include/vse_hip.h): the frames of one vse_interval_rank call
 FRAME_HOLD_BOUNDED_MAX = 4000   # the largest max_hold of vse_frame_hold_bounded (include/vse_hip.h)
 

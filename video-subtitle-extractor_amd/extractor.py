@@ -260,6 +260,13 @@ class SubtitleExtractor:
     text) / maximum (dark text) / mean of ALL frames of the interval, one more pass over the area's rows on the device
     (frame_select.IntervalCompositor, `composite_params` its keyword arguments); the pictures are kept as `interval_patches`.
     Intervals and SRT times are untouched.  What it gains on real footage is not measured here.
+    composite_params={"streaming": True, ...} with interval_image="min" | "max" | "mean": the same pictures, byte for byte, made in the
+    selector's own pass (frame_select.StreamingCompositor folds each staged batch while it is on the device; the frames whose fate is
+    open wait in a small ring there), so the compositor's pass over the clip is saved and the option also works in one pass.  The other
+    keys it takes: `trim_seconds`, `stream_fn`, and `keep_patches` (one pass drops a picture once its frame is recognised, a film has
+    thousands of about 1 MB each; True keeps them as `interval_patches`, as several passes always do).  `streaming` and `keep_patches`
+    are this class's own and are taken out before the rest reaches a compositor; a falsy `streaming` is the run without the key.  Not with
+    interval_image="quantile" or "middle", interval_text="fused" or shard.
     interval_image="quantile" (change / hold selector): the picture is instead the per-pixel quantile over time (default 0.5, the median)
     of up to `samples` (default 15) evenly spaced frames of the interval (frame_select.IntervalQuantile, `composite_params` its keyword
     arguments: quantile, samples, trim_seconds, rank_fn).  The median needs no knowledge of the text's polarity, and a minority of
@@ -306,7 +313,7 @@ class SubtitleExtractor:
     intervals, the frames recognised, raw_lines and the SRT equal those of the multi-pass run() on the same frames with the same
     arguments (recognition does not depend on how frames are grouped into batches: tests/test_gpu_ragged.py).  Refused in one pass,
     because they need a second look at frames already gone: sub_area="auto", mode="accurate" with an area, interval_image other than
-    "middle", interval_text="fused", shard, change_params' edge_thresh="auto".
+    "middle" (unless composite_params says "streaming"), interval_text="fused", shard, change_params' edge_thresh="auto".
     interval_frame="sharpest" (change / hold selector with interval_image="middle" and interval_text="single" only; default "middle", all
     of the above): the one frame an interval is recognised on is chosen instead of being the middle one, which in compressed video is as
     likely as any other to be a coarse B-frame, a half-faded frame or a flash.  In the selector's own pass over the staged area rows the
@@ -336,6 +343,27 @@ class SubtitleExtractor:
             raise ValueError(f"interval_image={interval_image!r} composites the intervals of frame_selector='change' or 'hold', not {frame_selector!r}")
         if interval_text not in ("single", "fused"):
             raise ValueError(f"interval_text must be 'single' or 'fused', not {interval_text!r}")
+        # composite_params={"streaming": True}: the pictures are made in the selector's own pass (frame_select.StreamingCompositor).
+        # The keys that are this class's own, `streaming` and `keep_patches`, are taken out here; what remains goes to the compositor.
+        composite_params = None if composite_params is None else dict(composite_params)
+        self.streaming = bool(composite_params.pop("streaming", False)) if composite_params else False
+        self.keep_patches = bool(composite_params.pop("keep_patches", False)) if composite_params and self.streaming else False
+        if not self.streaming:
+            own = sorted(set(composite_params or {}) & {"keep_patches", "stream_fn"})
+            if own:
+                raise ValueError(f"composite_params: {own} belong to composite_params={{'streaming': True}} and mean nothing without it")
+        if self.streaming:
+            option = "composite_params={'streaming': True}"
+            if interval_image not in frame_select.COMPOSITE_MODES:
+                raise ValueError(f"{option} makes the min / max / mean picture of each interval in the selector's own pass; "
+                                 f"interval_image={interval_image!r} is not one of them")
+            if interval_text != "single":
+                raise ValueError(f"{option} does not combine with interval_text={interval_text!r}")
+            if shard is not None:
+                raise ValueError(f"{option} composites every interval where the selector runs; it does not combine with shard={shard!r}")
+            unknown = set(composite_params) - {"trim_seconds", "stream_fn"}
+            if unknown:
+                raise ValueError(f"{option} takes trim_seconds, stream_fn and keep_patches beside it, not {sorted(unknown)}")
         if interval_text == "fused" and (frame_selector not in ("change", "hold") or interval_image != "middle"):
             raise ValueError(f"interval_text='fused' reads the intervals of frame_selector='change' or 'hold' (not {frame_selector!r}) from their "
                              f"own frames, interval_image='middle' (not {interval_image!r}): composites and fused posteriors do not combine")
@@ -383,7 +411,7 @@ class SubtitleExtractor:
             raise ValueError("one_pass=False needs a source with read(frame_no): this one is sequential and its frames cannot be looked at a second time")
         if self.one_pass:
             refused = [("sub_area='auto'", self.auto_area), ("mode='accurate' with a subtitle area", mode == "accurate" and sub_area is not None),
-                       (f"interval_image={interval_image!r}", interval_image != "middle"),
+                       (f"interval_image={interval_image!r}", interval_image != "middle" and not self.streaming),
                        (f"interval_text={interval_text!r}", interval_text != "single"), (f"shard={shard!r}", shard is not None),
                        ("edge_thresh='auto'", self.auto_thresh)]
             for what, hit in refused:
@@ -455,6 +483,9 @@ class SubtitleExtractor:
         more = {}
         if self.interval_frame == "sharpest":
             more["focus_fn"] = (self.frame_params or {}).get("focus_fn") or frame_select.EngineFocus(shim._context())
+        if self.streaming:
+            more["compositor"] = self._compositor = frame_select.StreamingCompositor(
+                **{"mode": self.interval_image, **self.composite_params})
         return cls(self.change_counter, batch=self.batch, **self._change_params(), **more)
 
     def _trim_seconds(self):
@@ -474,6 +505,8 @@ class SubtitleExtractor:
             up = self._uploader()
             sel = self._interval_selector()
             self.intervals = sel.run(self._decode_order(up), self.sub_area, s.fps, uploader=up)
+            if self.streaming:
+                self.interval_patches = self._compositor.patches
             if self.interval_frame == "sharpest":
                 self.focus = getattr(sel, "focus", None)            # (a clip without a frame leaves none, and no interval)
                 self.intervals = [(start, end, frame_select.sharpest_rep(start, end, self.focus, s.fps, self._trim_seconds()))
@@ -509,11 +542,15 @@ class SubtitleExtractor:
         return self.ocr.predict_batch(frames if not isinstance(frames, list) else _stack(frames))
 
     # ---- one pass ---------------------------------------------------------------------------------------------------------------
-    def _recognise(self, frames, nos, uploader):
-        """raw.txt lines of the retained frames `nos`, through run_ocr_tasks like any other task list."""
+    def _recognise(self, frames, nos, uploader, patches=None):
+        """raw.txt lines of the retained frames `nos`, through run_ocr_tasks like any other task list.  patches ({frame number: the
+        area's picture}, a streaming composite): those frames are shown with it in the area (CompositedSource)."""
         tasks = [(getattr(self.source, "frame_count", None), no, None, None, None, self.default_subtitle_area) for no in nos]
-        raw = any(hasattr(frames[no], "pack_into") for no in nos)
-        return run_ocr_tasks(RetainedSource(frames, self.source.fps, raw), tasks, self.ocr, self.sub_area, self.language, self.drop_score,
+        raw = patches is None and any(hasattr(frames[no], "pack_into") for no in nos)
+        source = RetainedSource(frames, self.source.fps, raw)
+        if patches is not None:
+            source = CompositedSource(source, self.sub_area, patches)
+        return run_ocr_tasks(source, tasks, self.ocr, self.sub_area, self.language, self.drop_score,
                              self.deviation_rate, self.batch, None, None, uploader)
 
     def _one_pass_fps(self, frames, uploader):
@@ -540,6 +577,17 @@ class SubtitleExtractor:
         kept, nbytes = {}, 0              # frame number -> full frame, and their bytes
         queue = []                        # rep frames of closed intervals, not yet recognised
         lines, no = [], 0
+        # composite_params' streaming: the selector's compositor has the picture of every closed interval, under its middle frame
+        comp = sel.compositor if self.streaming else None
+        keep_patches = self.keep_patches
+
+        def recognise(nos):
+            got = self._recognise(kept, nos, ocr_up, None if comp is None else comp.patches)
+            if comp is not None and not keep_patches:
+                for no in nos:
+                    comp.patches.pop(no, None)
+            return got
+
         sharpest = self.interval_frame == "sharpest"
         trim = int(round(self._trim_seconds() * self.source.fps)) if sharpest else 0
         # interval_frame="sharpest": the best frame so far of the open run starting at best_of, among its frames best_of + trim .. best_to
@@ -563,10 +611,12 @@ class SubtitleExtractor:
                                 "one pass: the interval %d..%d outgrew retain_bytes=%d; it is recognised on frame %d instead of its %s "
                                 "frame (its times are untouched; further such intervals are counted in clamped_intervals)",
                                 start, end, self.retain_bytes, rep, self.interval_frame)
+                    if comp is not None and rep != (start + end) // 2:
+                        comp.patches[rep] = comp.patches.pop((start + end) // 2)      # (a clamped interval: its picture goes with the frame shown)
                     self.intervals.append((start, end, rep))
                     queue.append(rep)
                 while len(queue) >= self.batch:
-                    lines += self._recognise(kept, queue[:self.batch], ocr_up)
+                    lines += recognise(queue[:self.batch])
                     del queue[:self.batch]
                 t, open_start = sel.tracker.fed, sel.tracker.open_start
                 floor = t + 1 if open_start is None else (open_start + t) // 2
@@ -589,7 +639,9 @@ class SubtitleExtractor:
                         if nbytes <= self.retain_bytes:
                             break
             if queue:
-                lines += self._recognise(kept, queue, ocr_up)
+                lines += recognise(queue)
+            if keep_patches:
+                self.interval_patches = comp.patches
             if sharpest:
                 self.focus = getattr(sel, "focus", None)
         finally:
@@ -639,7 +691,9 @@ class SubtitleExtractor:
         self.interval_patches = None
         tasks = self.select_tasks()
         source = self.source
-        if self.interval_image != "middle" and self.intervals is not None:
+        if self.streaming and self.intervals is not None:
+            source = CompositedSource(self.source, self.sub_area, self.interval_patches)
+        elif self.interval_image != "middle" and self.intervals is not None:
             source = self.composite_intervals(len(tasks))
         self.interval_results = None
         if self.interval_text == "fused" and self.intervals is not None:
@@ -663,11 +717,12 @@ def _parse_area(text):
     return SubtitleArea(*(int(p) for p in parts))
 
 
-def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, focus_fn=None):
+def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, focus_fn=None, stream_fn=None):
     """ocr: the recogniser (None: shim.OcrRecogniser on the GPU, frames staged through staging.default_uploader, YUV 4:2:0 converted
     on the device); counter: the change / hold selector's count_fn (None: the GPU's); cells_fn: the locator's (None: the GPU's);
     composite_fn: what makes the picture of `--interval-image`, the compositor's accumulate_fn for min / max / mean and the quantile's
-    rank_fn for quantile (None: the GPU's); focus_fn: what scores the frames of `--interval-frame sharpest` (None: the GPU's)."""
+    rank_fn for quantile (None: the GPU's); focus_fn: what scores the frames of `--interval-frame sharpest` (None: the GPU's);
+    stream_fn: what makes the pictures of `--streaming-composite`, StreamingCompositor's stream_fn (None: the GPU's)."""
     p = argparse.ArgumentParser(prog="python -m vse_amd.extractor", description="Extract a video's hard subtitles to SRT on the GPU.  "
                                 "`-` reads YUV4MPEG2 from standard input in one pass, e.g. "
                                 "`ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m vse_amd.extractor - -o film.srt`.")
@@ -695,7 +750,9 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
     p.add_argument("--interval-image", default="middle", choices=INTERVAL_IMAGES, help="change / hold selector: what the recogniser is "
                    "shown for each subtitle: its middle frame, the per-pixel min (light text) / max (dark text) / mean of all its frames, "
                    "or the per-pixel quantile of a few evenly spaced ones, which needs no polarity and shrugs off a flash or a late cut "
-                   "(not in one pass) [middle]")
+                   "(not in one pass) [middle].  With --streaming-composite, min / max / mean also work in one pass.")
+    p.add_argument("--streaming-composite", action="store_true", help="--interval-image min / max / mean: make the pictures in the "
+                   "selector's own pass instead of a pass of their own, which also works in one pass (a pipe)")
     p.add_argument("--quantile", type=float, default=0.5, metavar="Q", help="--interval-image quantile: 0..1, 0.5 the median [0.5]")
     p.add_argument("--interval-samples", type=int, default=15, metavar="K", help="--interval-image quantile: frames sampled per subtitle, "
                    "1..min(batch, 63); exact when the subtitle has no more frames, an estimate otherwise [15]")
@@ -730,12 +787,20 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
         if args.locator_max_hold_seconds is not None and args.locator_automaton != "hold":
             raise ValueError(f"--locator-max-hold-seconds bounds the runs of `--locator-automaton hold`, not of `--locator-automaton "
                              f"{args.locator_automaton}`")
+        if args.streaming_composite and args.interval_image not in frame_select.COMPOSITE_MODES:
+            raise ValueError(f"--streaming-composite makes the picture of `--interval-image min`, `max` or `mean`, not of "
+                             f"`--interval-image {args.interval_image}`")
         composite_params = None
         if args.interval_image == "quantile":
             composite_params = {"quantile": args.quantile, "samples": args.interval_samples, "rank_fn": composite_fn}
             frame_select.IntervalQuantile(**{"batch": args.batch, **composite_params})          # a bad value is refused before any work
         elif args.interval_image != "middle":
             composite_params = {"accumulate_fn": composite_fn}
+        if args.streaming_composite:
+            if composite_fn is not None:
+                raise ValueError("--streaming-composite makes its pictures with stream_fn; the composite_fn given makes those of the "
+                                 "compositor's own pass and would not be called")
+            composite_params = {"streaming": True, **({} if stream_fn is None else {"stream_fn": stream_fn})}
         source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout, matrix=args.matrix)
         uploader = None
         if ocr is None:

@@ -16,7 +16,8 @@ the area and hands out batches of (full frame, the area's rows), keeping no fram
 into stacked data, through an uploader's pinned memory and producer thread or with np.stack on the host; `_IntervalSelector` is the
 one run / iter_run body of ChangeFrameSelector and HoldFrameSelector; and the Engine* callables keep their device state through
 `engine.DeviceState`.  area_locator.AreaLocator and keyframes.scan stand on the same pieces.  A selector given a `focus_fn` (EngineFocus,
-vse_frame_focus) also scores every frame in the same pass, and `sharpest_rep` picks an interval's frame by that score.
+vse_frame_focus) also scores every frame in the same pass, and `sharpest_rep` picks an interval's frame by that score.  A selector given
+a `compositor` (StreamingCompositor, vse_interval_stream) also makes each interval's min / max / mean picture in that pass.
 """
 from collections import deque
 from contextlib import closing
@@ -312,10 +313,14 @@ class _IntervalSelector:
     focus_fn(frames [n,h,w,3] uint8, area, edge_thresh, reset) -> [n,2] kept, focus per frame (vse_frame_focus; it carries the last
     frame's mask to the next call): when given, it is called once per batch on the same staged data as count_fn, with reset on the
     first batch, and its rows are appended to `focus`, int64 [frames fed, 2], readable while iterating.  Focus rows belong to the
-    frames fed: they do not trail like the hold selector's counts.  None: no call, and `focus` is not touched."""
+    frames fed: they do not trail like the hold selector's counts.  None: no call, and `focus` is not touched.
+    compositor (StreamingCompositor): when given, begin(fps, lag) is called before the first batch, with `lag` the number of frames by
+    which the rows trail (`_lag`), then compositor(data, area, n, tracker, closed) once per staged batch, after the tracker has been
+    fed and while the batch is still resident, and once more after the flush with n = 0 and the last closings.  None: nothing changes."""
 
-    def __init__(self, count_fn=None, edge_thresh=128, change_ratio=0.5, min_edges=None, min_frames=2, batch=64, focus_fn=None):
-        self.count_fn, self.focus_fn = count_fn, focus_fn
+    def __init__(self, count_fn=None, edge_thresh=128, change_ratio=0.5, min_edges=None, min_frames=2, batch=64, focus_fn=None,
+                 compositor=None):
+        self.count_fn, self.focus_fn, self.compositor = count_fn, focus_fn, compositor
         self.edge_thresh, self.change_ratio, self.min_edges, self.min_frames = edge_thresh, change_ratio, min_edges, min_frames
         self.batch = batch
         self.counts = None
@@ -349,6 +354,8 @@ class _IntervalSelector:
             return
         min_edges = default_min_edges(bands.area[1], bands.area[3] - bands.area[2]) if self.min_edges is None else self.min_edges
         self.tracker = IntervalTracker(min_edges, self.change_ratio, min_frames)
+        if self.compositor is not None:
+            self.compositor.begin(fps, self._lag())
 
         def feed(c):
             out.append(np.asarray(c.cpu() if hasattr(c, "cpu") else c, np.int32).reshape(-1, 3))
@@ -370,12 +377,16 @@ class _IntervalSelector:
                         room = np.concatenate([room[:fed], np.zeros((max(len(room), len(rows), 1024), 2), np.int64)])
                     room[fed:fed + len(rows)] = rows
                     self.focus = room[:fed + len(rows)]
+                if self.compositor is not None:
+                    self.compositor(data, bands.area, len(items), self.tracker, closed)
                 fed += len(items)
                 yield items, closed
         closed = feed(self._flush(data, bands.area, fed))
         self.counts = np.concatenate(out)
         last = self.tracker.flush()
         self.intervals += last
+        if self.compositor is not None:
+            self.compositor(data[:0], bands.area, 0, self.tracker, closed + last)
         yield [], closed + last
 
 
@@ -394,6 +405,9 @@ class ChangeFrameSelector(_IntervalSelector):
 
     def _min_frames(self, fps):
         return self.min_frames
+
+    def _lag(self):
+        return 0
 
     def _count(self, data, area, fed):
         return self.count_fn(data, area, self.edge_thresh, fed == 0)
@@ -475,8 +489,8 @@ class HoldFrameSelector(_IntervalSelector):
     engine_count_fn = EngineHoldCounter
 
     def __init__(self, count_fn=None, hold_seconds=0.3, hold_frames=None, edge_thresh=128, change_ratio=0.5, min_edges=None,
-                 min_frames=2, batch=64, focus_fn=None, max_hold_seconds=None, max_hold_frames=None):
-        super().__init__(count_fn, edge_thresh, change_ratio, min_edges, min_frames, batch, focus_fn)
+                 min_frames=2, batch=64, focus_fn=None, max_hold_seconds=None, max_hold_frames=None, compositor=None):
+        super().__init__(count_fn, edge_thresh, change_ratio, min_edges, min_frames, batch, focus_fn, compositor)
         self.hold_seconds, self.hold_frames = hold_seconds, hold_frames
         self.max_hold_seconds, self.max_hold_frames = max_hold_seconds, max_hold_frames
         if max_hold_seconds is not None or max_hold_frames is not None:
@@ -499,6 +513,9 @@ class HoldFrameSelector(_IntervalSelector):
 
     def _args(self):
         return (self.hold,) if self.max_hold is None else (self.hold, self.max_hold)
+
+    def _lag(self):
+        return self.hold - 1 if self.max_hold is None else self.max_hold
 
     def _count(self, data, area, fed):
         return self.count_fn(data, area, self.edge_thresh, *self._args(), fed, False)
@@ -622,6 +639,114 @@ class IntervalCompositor:
             fold(items, data)
         self.area = tuple(geometry)
         return self.patches
+
+
+# ---- streaming composite (the compositor's pictures, made in the selector's own pass) ------------------------------------------
+class EngineStreamer(DeviceState):
+    """stream_fn of StreamingCompositor on the GPU (Context.interval_stream): keeps the device state (accumulators and ring) of the
+    last area and `cap` between calls.  Nothing in the state is read that an earlier call of the same clip did not write, so a new
+    clip needs no reset; the area or cap may change only where a clip starts."""
+
+    def __call__(self, frames, area, cap, fed, segs, store_from, mode):
+        y0, y1, x0, x1 = area
+        key = (y1 - y0, x1 - x0, cap)
+        if fed and self._key != key:
+            raise ValueError(f"EngineStreamer: the area or cap changed to {key} after {fed} frames of a clip")
+        self._fresh(key, self.ctx.interval_stream_state)
+        return self.ctx.interval_stream(self._device(frames), area, self._state, cap, fed, segs, store_from, mode)
+
+
+class StreamingCompositor:
+    """IntervalCompositor's pictures without its pass over the clip: a selector given this as `compositor` hands it every staged batch
+    while that is still on the device, and the per-byte min / max / mean over trim_range of each interval is folded there and then
+    (vse_interval_stream).  What keeps IntervalCompositor waiting is only that an interval's end, hence its trimmed range, is unknown
+    when a frame arrives.  With T = round(trim_seconds * fps), frame k of an open run s..t belongs to the picture for certain once
+    t >= k + T and k >= s + T; the undecided frames, at most T + 1 of them plus the selector's lag L (frames whose rows have not come
+    yet), wait in a ring of cap = L + T + 1 area bands on the device.  Per batch, with t = tracker.fed and s = tracker.open_start:
+      every closed (start, end, rep): one segment max(first, folded_to + 1) .. last of trim_range(start, end), which CONTINUEs the
+        open-run fold when that belongs to `start`, and EMITs with frames = last - first + 1;
+      an open run with t - s > 2 T: the fold advances to t - T - 1 without EMIT, from s + T;  floor = t - T
+        (the last certain frame t - T is held back: the run may end at t, and the segment that EMITs it must have a frame);
+      an open run with t - s <= 2 T: nothing is folded;  floor = (s + t) // 2, the earliest frame the picture can start at;
+      no open run: floor = t + 1.
+    The batch frames from `floor` on are stored, the ring frames below it forgotten; that the ring never has to hold more than cap
+    frames is asserted on every call, as is that every frame a segment names is in the batch or the ring.  More than
+    INTERVAL_STREAM_MAX_SEGS segments go in several calls on the same batch, of which only the last stores.  A run dropped for
+    min_frames leaves a stale fold behind, which the next run's first segment does not CONTINUE.  The bytes are IntervalCompositor.run's.
+
+    stream_fn(frames [n,h,w,3] uint8, area (y0, y1, x0, x1) in their pixels, cap, fed, segs [(first, last, flags, frames)], store_from,
+    mode) -> [EMITs, y1-y0, x1-x0, 3] uint8, the composites of the EMIT segments in order (Context.interval_stream).  Default:
+    EngineStreamer on the shim's device.  `patches`: {rep: uint8 ndarray [ah, aw, 3]}, a plain dict as IntervalCompositor's: the
+    composites of a call are read back when it returns, one read-back per batch in which a subtitle ends (the selector has just read
+    that batch's counts back, so the device is waited for either way)."""
+
+    def __init__(self, stream_fn=None, mode="min", trim_seconds=0.25):
+        if mode not in COMPOSITE_MODES:
+            raise ValueError(f"StreamingCompositor: mode must be one of {COMPOSITE_MODES}, not {mode!r}")
+        self.stream_fn, self.mode, self.trim_seconds = stream_fn, mode, trim_seconds
+        self.area = None              # the area in the band's own pixels (0, y1 - y0, x0, x1), once a batch has been seen
+        self.patches = {}
+        self.cap = self.peak_ring = None
+
+    def begin(self, fps, lag):
+        """A clip starts: its frame rate and the frames by which the selector's rows trail its frames."""
+        if self.stream_fn is None:
+            from . import shim
+            self.stream_fn = EngineStreamer(shim._context())
+        self.fps, self.lag = fps, int(lag)
+        self.trim = int(round(self.trim_seconds * fps))
+        self.cap, self.peak_ring = self.lag + self.trim + 1, 0
+        self.patches = {}
+        self._fed = 0                 # frames handed over so far
+        self._floor = 1               # the ring holds the frames _floor .. _fed
+        self._fold_of, self._folded_to = None, 0          # the run whose fold the accumulators hold, and its last folded frame
+
+    def __call__(self, data, area, n, tracker, closed):
+        import numpy as np
+        from .engine import INTERVAL_SEG_CONTINUE, INTERVAL_SEG_EMIT, INTERVAL_STREAM_MAX_SEGS
+        T, fed = self.trim, self._fed
+        t, s = tracker.fed, tracker.open_start
+        assert fed + n - t <= self.lag or n == 0, f"StreamingCompositor: the rows trail by {fed + n - t} frames, more than the lag {self.lag}"
+        segs, reps = [], []
+        for start, end, rep in closed:
+            first, last = trim_range(start, end, self.fps, self.trim_seconds)
+            cont = self._fold_of == start
+            segs.append((max(first, self._folded_to + 1) if cont else first, last, (INTERVAL_SEG_CONTINUE if cont else 0) | INTERVAL_SEG_EMIT,
+                         last - first + 1))
+            reps.append(rep)
+            self._fold_of = None
+        if s is None:
+            floor = t + 1
+        elif t - s > 2 * T:
+            cont = self._fold_of == s
+            lo = self._folded_to + 1 if cont else s + T
+            if lo <= t - T - 1:
+                segs.append((lo, t - T - 1, INTERVAL_SEG_CONTINUE if cont else 0, 0))
+                self._fold_of, self._folded_to = s, t - T - 1
+            floor = t - T
+        else:
+            floor = (s + t) // 2
+        for k, (lo, hi, flags, _frames) in enumerate(segs):
+            assert lo <= hi and lo >= self._floor and hi <= fed + n and (k == 0 or lo > segs[k - 1][1]), \
+                f"StreamingCompositor: segment {lo}..{hi} is not in the ring from {self._floor} or the batch {fed + 1}..{fed + n}"
+            assert not (flags & INTERVAL_SEG_CONTINUE) or k == 0
+        held = fed + n - floor + 1
+        assert held <= self.cap and floor >= self._floor, f"StreamingCompositor: {held} frames to keep from {floor}, the ring holds {self.cap}"
+        self.peak_ring = max(self.peak_ring, held)
+        out = []
+        calls = [segs[k:k + INTERVAL_STREAM_MAX_SEGS] for k in range(0, len(segs), INTERVAL_STREAM_MAX_SEGS)] or [[]]
+        for k, part in enumerate(calls):
+            final = k == len(calls) - 1
+            if not part and (not n or floor > fed + n):
+                break                                     # nothing to read and nothing to store
+            res = self.stream_fn(data, area, self.cap, fed, part, floor if final else fed + n + 1, self.mode)
+            emits = sum(1 for g in part if g[2] & INTERVAL_SEG_EMIT)
+            if emits:
+                res = res.cpu().numpy() if hasattr(res, "cpu") else np.asarray(res)
+                out += [np.array(res[j]) for j in range(emits)]           # (copies: a patch does not keep its call's others alive)
+        assert len(out) == len(reps)
+        self.patches.update(zip(reps, out))
+        self.area, self._fed, self._floor = tuple(area), fed + n, floor
 
 
 # ---- interval fusion (several frames per interval of the change selector, fused in probability space) ----------------------
