@@ -690,6 +690,43 @@ int vse_yuv_to_bgr_matrix(vse_ctx* ctx, const void* d_yuv, int n, int h, int w, 
                           int row_parity /* 0 | 1 */, int64_t yuv_frame_stride, void* d_bgr, int64_t pitch, int64_t bgr_frame_stride,
                           int matrix /* 0 = BT.601, 1 = BT.709 */, void* stream);
 
+/* ---- frame ingest: any planar / semi-planar YUV -> BGR --------------------------------------------------------------------------- */
+/* What else a decoder hands out, converted by the same kind of integers, so that nothing is converted on the host in front of the pipe:
+ * 10-bit (HEVC Main10, Hi10P) and deeper, 4:2:2, 4:4:4, grey, full range (phone video, screen recordings, yuvj420p), BT.2020, and P010,
+ * the surface of a hardware decoder.  A format is plain integers:
+ *   sub_x, sub_y   log2 chroma subsampling: 0, 0 (4:4:4) | 1, 0 (4:2:2) | 1, 1 (4:2:0)
+ *   chroma         0 none (grey; sub_x = sub_y = 0) | 1 planar, U then V | 2 interleaved U V (semi-planar; 4:2:0 only: NV12, P010)
+ *   depth          8..16; depth 8 has 1-byte samples, 9..16 2-byte little-endian ones
+ *   msb            0: the value in the low bits, a word above 2^depth - 1 is clamped to it (yuv420p10le, Y4M); 1: in the high bits,
+ *                  value = word >> (16 - depth) (P010 / P012 / P016); 0 at depth 8
+ *   matrix         0 BT.601 | 1 BT.709 | 2 BT.2020 non-constant luminance;   full_range 0 | 1
+ * With s = depth - 8, U and V of chroma row (r + row_parity) >> sub_y and column x >> sub_x (nearest, no interpolation), int32, >>
+ * arithmetic:
+ *   limited: c = max(Y - (16 << s), 0) * KY_s;   full: c = Y * (2^20 >> s);   u = U - (128 << s), v = V - (128 << s) (grey: u = v = 0)
+ *   B = clip8((c + BU_s u + 2^19) >> 20), G = clip8((c + GU_s u + GV_s v + 2^19) >> 20), R = clip8((c + RV_s v + 2^19) >> 20)
+ *   K_s = sign(K_0) * ((|K_0| + ((1 << s) >> 1)) >> s)
+ * K_0 (KY; BU, GU, GV, RV): limited BT.601 and BT.709 the numbers of the two entries above (at s = 0 this is their formula, bit for
+ * bit), limited BT.2020 1220542; 2245811, -196426, -682019, 1760217 (BT.709's derivation with Kr = 0.2627, Kb = 0.0593); full range
+ * round(k 2^20) of 2 (1 - Kb), -2 Kb (1 - Kb) / Kg, -2 Kr (1 - Kr) / Kg, 2 (1 - Kr), without 255/224: BT.601 1858077, -360853, -748826,
+ * 1470104; BT.709 1945738, -196424, -490864, 1651297; BT.2020 1972791, -172546, -599107, 1546230.
+ * NO transfer function is applied: PQ / HLG material comes out flat (dim, low contrast); its text and edges remain.
+ * A packed (sub-)frame of luma rows [y0, y1): h = y1 - y0 rows of w samples, then chroma rows y0 >> sub_y .. ((y1 - 1) >> sub_y) + 1,
+ * that is ch = ((h - 1 + row_parity) >> sub_y) + 1 rows of cw = (w + sub_x) >> sub_x samples per plane (planar: U plane, V plane;
+ * semi-planar: one plane of rows of 2 cw samples), row_parity = y0 & sub_y.  For 8-bit 4:2:0 this is vse_yuv420_to_bgr's.
+ * vse_yuv_frame_bytes: that packed size in bytes; 0 for arguments vse_yuv_to_bgr_format would refuse. */
+size_t vse_yuv_frame_bytes(int h, int w, int sub_x, int sub_y, int chroma, int depth, int row_parity);
+/* n packed frames at d_yuv, yuv_frame_stride bytes apart -> uint8 BGR [n, h, w, 3] at d_bgr, as vse_yuv420_to_bgr: one launch on
+ * `stream`, no allocation, no device sync, exactly the w * 3 bytes of each row written.  8-bit 4:2:0 limited BT.601 / BT.709 runs
+ * vse_yuv_to_bgr_matrix's kernels and gives its bytes.  2-byte 4:2:0, planar or semi-planar, takes a 16-byte load / store kernel
+ * under vse_yuv420_to_bgr's conditions (16-byte aligned bases, pitch and strides, w % 16 == 0, even h, row_parity 0); everything else
+ * a kernel without conditions, except that 2-byte samples need a 2-byte aligned d_yuv and yuv_frame_stride.
+ * Returns VSE_E_INVAL, with the values in vse_last_error, and launches nothing, for a format outside the table above, h, w or n < 1,
+ * h * w > 2^31 - 1, row_parity outside 0..sub_y, that misalignment, pitch < 3 w, yuv_frame_stride < vse_yuv_frame_bytes or
+ * bgr_frame_stride < (h - 1) pitch + 3 w. */
+int vse_yuv_to_bgr_format(vse_ctx* ctx, const void* d_yuv, int n, int h, int w, int sub_x, int sub_y, int chroma, int depth, int msb,
+                          int matrix, int full_range, int row_parity, int64_t yuv_frame_stride, void* d_bgr, int64_t pitch,
+                          int64_t bgr_frame_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -331,6 +331,12 @@ def main(argv=None, cells_fn=None):
     p.add_argument("--fps", type=float, default=None, help="frame rate, for files that carry none (.npy, headerless YUV)")
     p.add_argument("--size", default=None, metavar="WxH", help="frame size of a headerless YUV 4:2:0 file")
     p.add_argument("--layout", default=None, choices=("i420", "nv12"), help="plane layout of a headerless YUV 4:2:0 file [by extension]")
+    p.add_argument("--matrix", default="bt601", choices=("bt601", "bt709", "bt2020"), help="YUV -> BGR matrix [bt601]; bt2020 needs "
+                   "--wide-yuv or --pix-fmt")
+    p.add_argument("--wide-yuv", action="store_true", help="Y4M: also accept 9 to 16 bits, 4:2:2, 4:4:4, grey and full range")
+    p.add_argument("--range", default="auto", choices=("auto", "limited", "full"), help="--wide-yuv / --pix-fmt: the colour range [auto]")
+    p.add_argument("--pix-fmt", default=None, metavar="NAME", help="pixel format of a headerless YUV file by FFmpeg's name (yuv420p10le, "
+                   "p010le ...) [by extension]")
     p.add_argument("--probe", type=int, nargs=2, default=None, metavar=("START", "COUNT"),
                    help="scan COUNT frames from the 1-based frame number START on [the whole clip]")
     p.add_argument("--edge-thresh", default=str(DEFAULT_EDGE_THRESH), metavar="auto|N", help="luma gradient that makes an edge pixel, or "
@@ -357,7 +363,8 @@ def main(argv=None, cells_fn=None):
             if not (sep and w.isdigit() and h.isdigit()):
                 raise ValueError(f"--size takes WIDTHxHEIGHT, not {args.size!r}")
             size = (int(w), int(h))
-        source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout)
+        source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout, matrix=args.matrix, wide=args.wide_yuv,
+                                    range=args.range, pix_fmt=args.pix_fmt)
         loc = AreaLocator(cells_fn, probe=args.probe, edge_thresh=parse_edge_thresh(args.edge_thresh), automaton=args.locator_automaton,
                           hold_seconds=args.hold_seconds, hold_frames=args.hold_frames, max_hold_seconds=args.max_hold_seconds,
                           max_hold_frames=args.max_hold_frames)

@@ -15,6 +15,27 @@
 //            bases, pitch and frame strides.
 //   general  a lane owns 4 pixels of one row, any size / pitch / parity / byte alignment: dword stores where the row is 4-byte aligned
 //            and the 4 pixels exist, byte stores otherwise.
+//
+// vse_yuv_to_bgr_format (include/vse_hip.h) widens this to what else a decoder hands out: 4:4:4 / 4:2:2 / 4:2:0 / grey, 8 to 16 bits (1-byte
+// samples at depth 8, 2-byte little-endian ones above, the value in the low bits or, P010-style, in the high bits), planar or semi-planar,
+// BT.601 / BT.709 / BT.2020 (non-constant luminance), limited or full range.  No transfer function is applied.  With s = depth - 8:
+//   Y, U, V = min(word >> shift, 2^depth - 1)           (shift = 16 - depth for high-bit words, else 0)
+//   c = max(Y - yoff, 0) * KY_s, u = U - (128 << s), v = V - (128 << s)   (yoff = 16 << s, limited; 0 and KY_0 = 2^20, full; grey: u = v = 0)
+//   B = clip8((c + BU_s u + 2^19) >> 20), G = clip8((c + GU_s u + GV_s v + 2^19) >> 20), R = clip8((c + RV_s v + 2^19) >> 20)
+//   K_s = sign(K_0) ((|K_0| + ((1 << s) >> 1)) >> s)
+// K_0: limited BT.601 / BT.709 the literals above; limited BT.2020 the same derivation with Kr = 0.2627, Kb = 0.0593: 2245811 (B), -196426 u
+// - 682019 v (G), 1760217 (R); full range round(k * 2^20) of 2 (1 - Kb), 2 Kb (1 - Kb) / Kg, 2 Kr (1 - Kr) / Kg, 2 (1 - Kr), no 255/224:
+// BT.601 1858077, -360853, -748826, 1470104; BT.709 1945738, -196424, -490864, 1651297; BT.2020 1972791, -172546, -599107, 1546230.
+// int32: Y - yoff < 2^depth and KY_s <= (KY_0 >> s) + 1, so c < 2^8 KY_0 + 2^16 <= 312 524 288; |u|, |v| <= 2^(depth - 1) and |K_s| <=
+// (|K_0| >> s) + 1, so a chroma product is at most 2^7 |K_0| + 2^15 and the largest sum, limited BT.2020's B, stays below 312 524 288 +
+// 287 496 576 + 2^19 = 600 545 152 (G's two products together are smaller: at most 2^7 (409993 + 852492) + 2^16, BT.601's); every operand
+// fits 24 signed bits (samples 17, |K_s| < 2^23), so the products are the 24-bit multiplies.  shift, 2^depth - 1, the two offsets and the
+// five factors are kernel arguments (wave-uniform); the kernels are templated on what changes the loads alone, the sample width and the
+// chroma arrangement:
+//   fast     2-byte 4:2:0, planar (yuv420p10le ...) or semi-planar (P010 ...): the shape of the 8-bit one, a lane owns 16 pixels x 2 rows:
+//            four 16-byte luma loads, two 16-byte chroma loads, six 16-byte stores, the chroma terms once for both rows.  Same conditions.
+//   general  any format: a lane owns 4 pixels of one row; 2-byte formats need 2-byte aligned bases and strides.
+// 8-bit 4:2:0 limited BT.601 / BT.709 goes to the two 8-bit kernels above and gives their bytes.
 #include <algorithm>
 #include <cstdio>
 
@@ -166,6 +187,183 @@ __global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void yuv420_general_kernel(co
     }
 }
 
+// ---- any format (vse_yuv_to_bgr_format) -----------------------------------------------------------------------------------------
+constexpr int CHROMA_NONE = 0, CHROMA_PLANAR = 1, CHROMA_SEMI = 2;
+
+struct YuvParams {
+    int shift, maxv;              // sample = min(word >> shift, maxv)
+    int yoff, coff;               // 16 << s (0: full range), 128 << s
+    int ky, bu, gu, gv, rv;       // K_s
+};
+
+__device__ __forceinline__ int sample_of(unsigned word, const YuvParams& p) { return min((int)(word >> p.shift), p.maxv); }
+
+__device__ __forceinline__ int luma_term(int Y, const YuvParams& p) { return __mul24(max(Y - p.yoff, 0), p.ky); }
+
+__device__ __forceinline__ ChromaTerms chroma_terms(int U, int V, const YuvParams& p) {
+    const int u = U - p.coff, v = V - p.coff;
+    ChromaTerms t;
+    t.b = __mul24(u, p.bu) + (1 << 19);
+    t.g = __mul24(u, p.gu) + __mul24(v, p.gv) + (1 << 19);
+    t.r = __mul24(v, p.rv) + (1 << 19);
+    return t;
+}
+
+// 4 pixels (luma terms c, chroma terms t) -> 12 bytes B G R B G R ...
+__device__ __forceinline__ void pack4(const int (&c)[4], const ChromaTerms (&t)[4], unsigned& d0, unsigned& d1, unsigned& d2) {
+    unsigned b[4], g[4], r[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        b[k] = clip8(c[k] + t[k].b);
+        g[k] = clip8(c[k] + t[k].g);
+        r[k] = clip8(c[k] + t[k].r);
+    }
+    d0 = b[0] | (g[0] << 8) | (r[0] << 16) | (b[1] << 24);
+    d1 = g[1] | (r[1] << 8) | (b[2] << 16) | (g[2] << 24);
+    d2 = r[2] | (b[3] << 8) | (g[3] << 16) | (r[3] << 24);
+}
+
+// 16 pixels of one row of 2-byte samples (ya: pixels 0-7, yb: pixels 8-15; t[k]: pixels 2 k, 2 k + 1) -> 48 bytes as three 16-byte stores
+__device__ __forceinline__ void row16_wide(const uint4& ya, const uint4& yb, const ChromaTerms (&t)[8], const YuvParams& p, uint8_t* dst) {
+    const unsigned yw[8] = {ya.x, ya.y, ya.z, ya.w, yb.x, yb.y, yb.z, yb.w};
+    unsigned o[12];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int c[4] = {luma_term(sample_of(yw[2 * q] & 0xffffu, p), p), luma_term(sample_of(yw[2 * q] >> 16, p), p),
+                          luma_term(sample_of(yw[2 * q + 1] & 0xffffu, p), p), luma_term(sample_of(yw[2 * q + 1] >> 16, p), p)};
+        const ChromaTerms tq[4] = {t[2 * q], t[2 * q], t[2 * q + 1], t[2 * q + 1]};
+        pack4(c, tq, o[3 * q], o[3 * q + 1], o[3 * q + 2]);
+    }
+    uint4* d = reinterpret_cast<uint4*>(dst);
+    d[0] = make_uint4(o[0], o[1], o[2], o[3]);
+    d[1] = make_uint4(o[4], o[5], o[6], o[7]);
+    d[2] = make_uint4(o[8], o[9], o[10], o[11]);
+}
+
+// yuv420_fast_kernel for 2-byte samples: the same work items and strides; sstride, the planes and the rows are counted in bytes.
+template <int CHROMA>
+__global__ __launch_bounds__(FAST_THREADS) void yuv420_wide_fast_kernel(const uint8_t* __restrict__ src, int n, int h, int w, long sstride,
+                                                                        uint8_t* __restrict__ dst, long pitch, long dstride, YuvParams p) {
+    const unsigned cgs = (unsigned)w >> 4, items = ((unsigned)h >> 1) * cgs;
+    const long lrow = 2L * w, plane = (long)h * lrow;              // bytes of a luma row (= of a semi-planar chroma row) and of the luma plane
+    for (int f = blockIdx.y; f < n; f += gridDim.y) {
+        const uint8_t* s = src + (long)f * sstride;
+        uint8_t* d = dst + (long)f * dstride;
+        for (unsigned i = blockIdx.x * FAST_THREADS + threadIdx.x; i < items; i += gridDim.x * FAST_THREADS) {
+            const unsigned rp = i / cgs, cg = i - rp * cgs;
+            const uint8_t* yp = s + (long)(2 * rp) * lrow + 32 * cg;
+            const uint4 y0a = *reinterpret_cast<const uint4*>(yp), y0b = *reinterpret_cast<const uint4*>(yp + 16);
+            const uint4 y1a = *reinterpret_cast<const uint4*>(yp + lrow), y1b = *reinterpret_cast<const uint4*>(yp + lrow + 16);
+            ChromaTerms t[8];
+            if (CHROMA == CHROMA_PLANAR) {
+                const uint8_t* up = s + plane + (long)rp * w + 16 * cg;          // a chroma row is w / 2 samples = w bytes
+                const uint4 u = *reinterpret_cast<const uint4*>(up);
+                const uint4 v = *reinterpret_cast<const uint4*>(up + (plane >> 2));
+                const unsigned uw[4] = {u.x, u.y, u.z, u.w}, vw[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    t[k] = chroma_terms(sample_of((uw[k >> 1] >> (16 * (k & 1))) & 0xffffu, p), sample_of((vw[k >> 1] >> (16 * (k & 1))) & 0xffffu, p), p);
+            } else {
+                const uint8_t* cp = s + plane + (long)rp * lrow + 32 * cg;
+                const uint4 a = *reinterpret_cast<const uint4*>(cp), b = *reinterpret_cast<const uint4*>(cp + 16);
+                const unsigned q[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+                for (int k = 0; k < 8; ++k) t[k] = chroma_terms(sample_of(q[k] & 0xffffu, p), sample_of(q[k] >> 16, p), p);
+            }
+            uint8_t* o = d + (long)(2 * rp) * pitch + 48 * cg;
+            row16_wide(y0a, y0b, t, p, o);
+            row16_wide(y1a, y1b, t, p, o + pitch);
+        }
+    }
+}
+
+// yuv420_general_kernel for any format: S is the sample type, the planes are counted in samples.  Chroma column (x + k) >> sub_x, chroma
+// row (r + parity) >> sub_y; with sub_x = 1 pixels 0-1 and 2-3 share their terms (x is a multiple of 4).
+template <typename S, int CHROMA>
+__global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void yuv_general_kernel(const S* __restrict__ src, int n, int h, int w, int sub_x, int sub_y,
+                                                                           int parity, long sstride, uint8_t* __restrict__ dst, long pitch,
+                                                                           long dstride, YuvParams p) {
+    const int x = 4 * (int)(blockIdx.x * GEN_LANES + threadIdx.x);
+    if (x >= w) return;
+    const int npx = min(4, w - x);
+    const long plane = (long)h * w, cw = (w + sub_x) >> sub_x, ch = ((h - 1 + parity) >> sub_y) + 1;
+    for (int f = blockIdx.z; f < n; f += gridDim.z) {
+        const S* s = src + (long)f * sstride;
+        uint8_t* d = dst + (long)f * dstride;
+        for (int r = blockIdx.y * GEN_ROWS + threadIdx.y; r < h; r += gridDim.y * GEN_ROWS) {
+            const S* yp = s + (long)r * w + x;
+            int c[4] = {0, 0, 0, 0};
+            if (npx == 4 && (reinterpret_cast<uintptr_t>(yp) & (4 * sizeof(S) - 1)) == 0) {
+                if (sizeof(S) == 1) {
+                    const unsigned yw = *reinterpret_cast<const unsigned*>(yp);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) c[k] = luma_term(sample_of((yw >> (8 * k)) & 255u, p), p);
+                } else {
+                    const uint2 yw = *reinterpret_cast<const uint2*>(yp);
+                    c[0] = luma_term(sample_of(yw.x & 0xffffu, p), p);
+                    c[1] = luma_term(sample_of(yw.x >> 16, p), p);
+                    c[2] = luma_term(sample_of(yw.y & 0xffffu, p), p);
+                    c[3] = luma_term(sample_of(yw.y >> 16, p), p);
+                }
+            } else {
+                for (int k = 0; k < npx; ++k) c[k] = luma_term(sample_of(yp[k], p), p);
+            }
+            ChromaTerms t[4];
+            if (CHROMA == CHROMA_NONE) {
+                t[0] = t[1] = t[2] = t[3] = chroma_terms(p.coff, p.coff, p);
+            } else {
+                const long cr = (r + parity) >> sub_y;
+                const S* up = s + plane + cr * cw * (CHROMA == CHROMA_SEMI ? 2 : 1);
+                const long vo = CHROMA == CHROMA_SEMI ? 1 : ch * cw;      // V behind U: the next sample, or the next plane
+                const int cs = CHROMA == CHROMA_SEMI ? 2 : 1;
+                const auto terms_of = [&](int k) {
+                    const int cx = (min(x + k, w - 1) >> sub_x) * cs;      // (a pixel past the row's end takes the last sample: it is not stored)
+                    return chroma_terms(sample_of(up[cx], p), sample_of(up[cx + vo], p), p);
+                };
+                t[0] = terms_of(0);
+                t[2] = terms_of(2);
+                if (sub_x) {
+                    t[1] = t[0];
+                    t[3] = t[2];
+                } else {
+                    t[1] = terms_of(1);
+                    t[3] = terms_of(3);
+                }
+            }
+            unsigned o[3];
+            pack4(c, t, o[0], o[1], o[2]);
+            uint8_t* op = d + (long)r * pitch + 3 * (long)x;
+            if (npx == 4 && (reinterpret_cast<uintptr_t>(op) & 3) == 0) {
+                unsigned* o4 = reinterpret_cast<unsigned*>(op);
+                o4[0] = o[0];
+                o4[1] = o[1];
+                o4[2] = o[2];
+            } else {
+                for (int k = 0; k < 3 * npx; ++k) op[k] = (uint8_t)(o[k >> 2] >> (8 * (k & 3)));
+            }
+        }
+    }
+}
+
+// {KY, BU, GU, GV, RV}_0 of [full_range][matrix]
+constexpr int YUV_K0[2][3][5] = {{{1220542, 2116026, -409993, -852492, 1673527},
+                                  {1220542, 2215014, -223607, -558796, 1879825},
+                                  {1220542, 2245811, -196426, -682019, 1760217}},
+                                 {{1 << 20, 1858077, -360853, -748826, 1470104},
+                                  {1 << 20, 1945738, -196424, -490864, 1651297},
+                                  {1 << 20, 1972791, -172546, -599107, 1546230}}};
+
+int scaled_factor(int k0, int s) {
+    const int m = ((k0 < 0 ? -k0 : k0) + ((1 << s) >> 1)) >> s;
+    return k0 < 0 ? -m : m;
+}
+
+bool format_ok(int sub_x, int sub_y, int chroma, int depth) {
+    const bool sub = (sub_x == 0 && sub_y == 0) || (sub_x == 1 && sub_y == 0) || (sub_x == 1 && sub_y == 1);
+    return sub && chroma >= CHROMA_NONE && chroma <= CHROMA_SEMI && depth >= 8 && depth <= 16 && (chroma != CHROMA_NONE || sub_x + sub_y == 0) &&
+           (chroma != CHROMA_SEMI || sub_x + sub_y == 2);
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
@@ -221,6 +419,80 @@ int vse_yuv_to_bgr_matrix(vse_ctx* c, const void* d_yuv, int n, int h, int w, in
 int vse_yuv420_to_bgr(vse_ctx* c, const void* d_yuv, int n, int h, int w, int layout, int row_parity, int64_t yuv_frame_stride,
                       void* d_bgr, int64_t pitch, int64_t bgr_frame_stride, void* stream) {
     return vse_yuv_to_bgr_matrix(c, d_yuv, n, h, w, layout, row_parity, yuv_frame_stride, d_bgr, pitch, bgr_frame_stride, BT601, stream);
+}
+
+size_t vse_yuv_frame_bytes(int h, int w, int sub_x, int sub_y, int chroma, int depth, int row_parity) {
+    if (h < 1 || w < 1 || !format_ok(sub_x, sub_y, chroma, depth) || row_parity < 0 || row_parity > sub_y || (long)h * w > MAX_PIXELS) return 0;
+    const size_t cw = ((size_t)w + sub_x) >> sub_x, ch = (((size_t)h - 1 + row_parity) >> sub_y) + 1;
+    return (depth > 8 ? 2 : 1) * ((size_t)h * w + (chroma ? 2 * cw * ch : 0));
+}
+
+int vse_yuv_to_bgr_format(vse_ctx* c, const void* d_yuv, int n, int h, int w, int sub_x, int sub_y, int chroma, int depth, int msb, int matrix,
+                          int full_range, int row_parity, int64_t yuv_frame_stride, void* d_bgr, int64_t pitch, int64_t bgr_frame_stride,
+                          void* stream) {
+    const size_t frame = vse_yuv_frame_bytes(h, w, sub_x, sub_y, chroma, depth, row_parity);
+    const int ss = depth > 8 ? 2 : 1;
+    if (!c || !d_yuv || !d_bgr || n < 1 || !frame || msb < 0 || msb > (ss == 2 ? 1 : 0) || matrix < 0 || matrix > 2 || full_range < 0 ||
+        full_range > 1 || pitch < (int64_t)w * 3 || yuv_frame_stride < (int64_t)frame ||
+        bgr_frame_stride < (int64_t)(h - 1) * pitch + (int64_t)w * 3 ||
+        (ss == 2 && ((reinterpret_cast<uintptr_t>(d_yuv) & 1) || (yuv_frame_stride & 1)))) {
+        char msg[560];
+        snprintf(msg, sizeof msg, "vse_yuv_to_bgr_format: bad arguments (n %d, frame %d x %d of at most 2^31 - 1 pixels, subsampling %d, %d of 0, 0 | "
+                 "1, 0 | 1, 1, chroma %d of 0 (with subsampling 0, 0) | 1 | 2 (with subsampling 1, 1), depth %d of 8..16, msb %d of 0 | 1 (0 at "
+                 "depth 8), matrix %d of 0 | 1 | 2, full range %d of 0 | 1, row parity %d of 0..%d, packed frame stride %lld of at least %zu, "
+                 "pitch %lld, output frame stride %lld, base %p and stride 2-byte aligned for 2-byte samples)", n, h, w, sub_x, sub_y, chroma,
+                 depth, msb, matrix, full_range, row_parity, sub_y == 1 ? 1 : 0, (long long)yuv_frame_stride, frame, (long long)pitch,
+                 (long long)bgr_frame_stride, d_yuv);
+        vse_set_error(msg);
+        return VSE_E_INVAL;
+    }
+    // what the 8-bit 4:2:0 kernels convert stays theirs
+    if (ss == 1 && sub_x == 1 && sub_y == 1 && chroma != CHROMA_NONE && !full_range && matrix <= BT709)
+        return vse_yuv_to_bgr_matrix(c, d_yuv, n, h, w, chroma - 1, row_parity, yuv_frame_stride, d_bgr, pitch, bgr_frame_stride, matrix, stream);
+    const int s = depth - 8;
+    const int* k0 = YUV_K0[full_range][matrix];
+    YuvParams p;
+    p.shift = msb ? 16 - depth : 0;
+    p.maxv = (1 << depth) - 1;
+    p.yoff = full_range ? 0 : 16 << s;
+    p.coff = 128 << s;
+    p.ky = scaled_factor(k0[0], s);
+    p.bu = scaled_factor(k0[1], s);
+    p.gu = scaled_factor(k0[2], s);
+    p.gv = scaled_factor(k0[3], s);
+    p.rv = scaled_factor(k0[4], s);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_yuv);
+    uint8_t* dst = reinterpret_cast<uint8_t*>(d_bgr);
+    const bool fast = ss == 2 && sub_x == 1 && sub_y == 1 && chroma != CHROMA_NONE && w % 16 == 0 && h % 2 == 0 && row_parity == 0 &&
+                      pitch % 16 == 0 && yuv_frame_stride % 16 == 0 && bgr_frame_stride % 16 == 0 && aligned16(src) && aligned16(dst);
+    if (fast) {
+        const long items = (long)(h / 2) * (w / 16);
+        const dim3 grid((unsigned)std::min<long>((items + FAST_THREADS - 1) / FAST_THREADS, FAST_MAX_BLOCKS), (unsigned)std::min(n, 65535));
+        const auto kernel = chroma == CHROMA_PLANAR ? yuv420_wide_fast_kernel<CHROMA_PLANAR> : yuv420_wide_fast_kernel<CHROMA_SEMI>;
+        hipLaunchKernelGGL(kernel, grid, dim3(FAST_THREADS), 0, st, src, n, h, w, (long)yuv_frame_stride, dst, (long)pitch, (long)bgr_frame_stride, p);
+    } else {
+        const long groups = ((long)w + 3) / 4;
+        const dim3 grid((unsigned)((groups + GEN_LANES - 1) / GEN_LANES), (unsigned)std::min((h + GEN_ROWS - 1) / GEN_ROWS, 65535),
+                        (unsigned)std::min(n, 65535));
+        const dim3 block(GEN_LANES, GEN_ROWS);
+        const long sstride = (long)yuv_frame_stride / ss;          // in samples
+        if (ss == 1) {
+            const auto kernel = chroma == CHROMA_NONE ? yuv_general_kernel<uint8_t, CHROMA_NONE>
+                              : chroma == CHROMA_PLANAR ? yuv_general_kernel<uint8_t, CHROMA_PLANAR> : yuv_general_kernel<uint8_t, CHROMA_SEMI>;
+            hipLaunchKernelGGL(kernel, grid, block, 0, st, src, n, h, w, sub_x, sub_y, row_parity, sstride, dst, (long)pitch, (long)bgr_frame_stride, p);
+        } else {
+            const auto kernel = chroma == CHROMA_NONE ? yuv_general_kernel<uint16_t, CHROMA_NONE>
+                              : chroma == CHROMA_PLANAR ? yuv_general_kernel<uint16_t, CHROMA_PLANAR> : yuv_general_kernel<uint16_t, CHROMA_SEMI>;
+            hipLaunchKernelGGL(kernel, grid, block, 0, st, reinterpret_cast<const uint16_t*>(src), n, h, w, sub_x, sub_y, row_parity, sstride, dst,
+                               (long)pitch, (long)bgr_frame_stride, p);
+        }
+    }
+    if (hipGetLastError() != hipSuccess) {
+        vse_set_error("vse_yuv_to_bgr_format: launch failed");
+        return VSE_E_HIP;
+    }
+    return VSE_OK;
 }
 
 }  // extern "C"

@@ -31,6 +31,7 @@ EXPORTS = [
     "vse_frame_hold_bounded_state_bytes", "vse_frame_hold_bounded",
     "vse_frame_cells_hold_bounded_state_bytes", "vse_frame_cells_hold_bounded",
     "vse_interval_stream_state_bytes", "vse_interval_stream",
+    "vse_yuv_frame_bytes", "vse_yuv_to_bgr_format",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -237,6 +238,9 @@ def load_library(path=None):
                                       C.c_int64, C.c_int64, C.c_void_p]
     lib.vse_yuv_to_bgr_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p,
                                           C.c_int64, C.c_int64, C.c_int, C.c_void_p]
+    lib.vse_yuv_frame_bytes.restype = C.c_size_t
+    lib.vse_yuv_frame_bytes.argtypes = [C.c_int] * 7
+    lib.vse_yuv_to_bgr_format.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 11 + [C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
     if lib.vse_sizeof_op() != ir.OP_DT.itemsize or lib.vse_sizeof_view() != ir.VIEW_DT.itemsize:
         raise VseError(f"ABI mismatch: vse_op {lib.vse_sizeof_op()} vs {ir.OP_DT.itemsize}, "
                        f"vse_view {lib.vse_sizeof_view()} vs {ir.VIEW_DT.itemsize}")
@@ -953,9 +957,36 @@ class Context:
                    "vse_yuv_to_bgr_matrix")
         return out
 
+    def yuv_to_bgr(self, packed, n, h, w, fmt, row_parity=0, out=None):
+        """packed: cuda uint8 holding n packed (sub-)frames of h x w pixels of the format `fmt` (an ingest.YuvFormat, or anything with its
+        integer attributes sub_x, sub_y, chroma, depth, msb, matrix, full_range; include/vse_hip.h vse_yuv_to_bgr_format), 1-D (frames back
+        to back) or 2-D [n, stride in bytes] -> cuda uint8 [n,h,w,3] BGR on the current stream.  out: as yuv420_to_bgr's."""
+        t = self.torch
+        n, h, w, row_parity = int(n), int(h), int(w), int(row_parity)
+        matrix = YUV_FORMAT_MATRICES.get(fmt.matrix, fmt.matrix)
+        if matrix not in (0, 1, 2):
+            raise VseError(f"yuv_to_bgr: matrix {fmt.matrix!r} is not one of {sorted(YUV_FORMAT_MATRICES)} (0 | 1 | 2)")
+        assert packed.dtype == t.uint8 and packed.dim() in (1, 2) and packed.stride(-1) == 1
+        frame = self.lib.vse_yuv_frame_bytes(h, w, int(fmt.sub_x), int(fmt.sub_y), int(fmt.chroma), int(fmt.depth), row_parity)
+        if packed.dim() == 2:
+            assert packed.shape[0] == n and packed.shape[1] >= frame, (tuple(packed.shape), n, frame)
+            sstride = packed.stride(0) if n > 1 else max(packed.stride(0), frame)
+        else:
+            assert packed.numel() >= n * frame, (packed.numel(), n, frame)
+            sstride = frame
+        if out is None:
+            out = t.empty((max(n, 0), max(h, 0), max(w, 0), 3), dtype=t.uint8, device=self.tdev)
+        assert out.dtype == t.uint8 and tuple(out.shape) == (n, h, w, 3) and out.stride(3) == 1 and out.stride(2) == 3
+        dstride = out.stride(0) if n > 1 else max(out.stride(0), (h - 1) * out.stride(1) + 3 * w)
+        _check(self.lib.vse_yuv_to_bgr_format(self.handle, C.c_void_p(packed.data_ptr()), n, h, w, int(fmt.sub_x), int(fmt.sub_y), int(fmt.chroma),
+                                              int(fmt.depth), int(fmt.msb), matrix, int(fmt.full_range), row_parity, sstride,
+                                              C.c_void_p(out.data_ptr()), out.stride(1), dstride, self.stream()), "vse_yuv_to_bgr_format")
+        return out
+
 
 YUV_LAYOUTS = {"i420": 0, "nv12": 1}
 YUV_MATRICES = {"bt601": 0, "bt709": 1}
+YUV_FORMAT_MATRICES = {"bt601": 0, "bt709": 1, "bt2020": 2}      # vse_yuv_to_bgr_format's
 INTERVAL_MODES = {"min": 0, "max": 1, "mean": 2}
 INTERVAL_SEG_CONTINUE, INTERVAL_SEG_EMIT = 1, 2          # vse_interval_seg.flags (include/vse_hip.h)
 INTERVAL_STREAM_MAX_SEGS = 32   # VSE_INTERVAL_STREAM_MAX_SEGS: the segments of one vse_interval_stream call

@@ -727,13 +727,19 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
                                 "`-` reads YUV4MPEG2 from standard input in one pass, e.g. "
                                 "`ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m vse_amd.extractor - -o film.srt`.")
     p.add_argument("video", help="`-` (YUV4MPEG2 on standard input), or a file: uncompressed BGR24 or Motion-JPEG AVI, a .npy frame stack, "
-                   ".y4m, or headerless .yuv / .i420 / .nv12")
+                   ".y4m, or headerless .yuv / .i420 / .nv12 / .p010")
     p.add_argument("-o", "--output", default=None, metavar="OUT.srt", help="write the SRT here [standard output]")
     p.add_argument("--fps", type=float, default=None, help="frame rate, for input that carries none (.npy, headerless YUV, Y4M with F0:0)")
     p.add_argument("--size", default=None, metavar="WxH", help="frame size of a headerless YUV 4:2:0 file")
     p.add_argument("--layout", default=None, choices=("i420", "nv12"), help="plane layout of a headerless YUV 4:2:0 file [by extension]")
-    p.add_argument("--matrix", default="bt601", choices=("bt601", "bt709"), help="YUV 4:2:0 -> BGR matrix [bt601]; Y4M carries no tag "
-                   "for it, and HD encodes are normally BT.709")
+    p.add_argument("--matrix", default="bt601", choices=("bt601", "bt709", "bt2020"), help="YUV -> BGR matrix [bt601]; Y4M carries no tag "
+                   "for it, and HD encodes are normally BT.709; bt2020 needs --wide-yuv or --pix-fmt")
+    p.add_argument("--wide-yuv", action="store_true", help="Y4M: also accept 9 to 16 bits, 4:2:2, 4:4:4, grey and full range (what "
+                   "`ffmpeg -strict -1 -f yuv4mpegpipe` writes without `-pix_fmt yuv420p`), converted on the GPU")
+    p.add_argument("--range", default="auto", choices=("auto", "limited", "full"), help="--wide-yuv / --pix-fmt: the colour range [auto: "
+                   "the Y4M header's XCOLORRANGE or the pixel format's own, else limited]")
+    p.add_argument("--pix-fmt", default=None, metavar="NAME", help="pixel format of a headerless YUV file by FFmpeg's name (yuv420p10le, "
+                   "yuv422p, yuv444p, gray, p010le, yuvj420p ...) [by extension; .p010 is p010le]")
     p.add_argument("--area", default=None, metavar="ymin,ymax,xmin,xmax|auto", help="the subtitle area in frame pixels, or `auto` to "
                    "look for it first (not in one pass) [none: the whole frame, fps sampler]")
     p.add_argument("--selector", default="fps", choices=("fps", "change", "hold"), help="which frames go to OCR [fps]")
@@ -801,7 +807,8 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
                 raise ValueError("--streaming-composite makes its pictures with stream_fn; the composite_fn given makes those of the "
                                  "compositor's own pass and would not be called")
             composite_params = {"streaming": True, **({} if stream_fn is None else {"stream_fn": stream_fn})}
-        source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout, matrix=args.matrix)
+        source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout, matrix=args.matrix, wide=args.wide_yuv,
+                                    range=args.range, pix_fmt=args.pix_fmt)
         uploader = None
         if ocr is None:
             if args.weights_dir is not None:

@@ -23,13 +23,20 @@ matrix, but a chroma up-sampling filter instead of the nearest sample, so these 
 content is).  matrix="bt709" on a frame or a source swaps the chroma factors for BT.709's (vse_yuv_to_bgr_matrix; HD encodes normally carry
 it); the default stays "bt601" because Y4M has no matrix tag.  Full-range (JPEG) YUV, 4:2:2 / 4:4:4 and more than 8 bits are refused.
 
+Other formats (YuvFormat, YuvFrame, YuvSource; Y4mSource / Y4mStream / open_source with wide=True): 9 to 16 bits, 4:2:2, 4:4:4, grey, full
+range, BT.2020 and P010-style semi-planar surfaces are accepted only when asked for, so that the refusals above stand.  A YuvFormat is the
+integers of include/vse_hip.h vse_yuv_to_bgr_format; YuvFrame.to_bgr and the device convert with the same integers (the 8-bit ones with
+factors scaled to the depth, nearest chroma, no transfer function: PQ / HLG material comes out flat, its text and edges remain).
+
 Pipes (Y4mStream): `ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m vse_amd.extractor -` puts compressed video of any
 codec through a decoder that is not ours; the stream is read once, front to back, never seeks and has no read(): its absence is how
 SubtitleExtractor sees that it must work in one pass.
 """
 import mmap
 import os
+import re
 import struct
+from collections import namedtuple
 from fractions import Fraction
 
 import numpy as np
@@ -321,6 +328,242 @@ class Yuv420Frame:
         return out
 
 
+# ---- any planar / semi-planar YUV (vse_yuv_to_bgr_format) --------------------------------------------------------------------------
+YUV_FORMAT_MATRICES = ("bt601", "bt709", "bt2020")
+YUV_RANGES = ("auto", "limited", "full")
+# (KY, BU, GU, GV, RV)_0 of include/vse_hip.h vse_yuv_to_bgr_format, by (full_range, matrix)
+YUV_K0 = {(0, "bt601"): (1220542,) + YUV_MATRICES["bt601"], (0, "bt709"): (1220542,) + YUV_MATRICES["bt709"],
+          (0, "bt2020"): (1220542, 2245811, -196426, -682019, 1760217),
+          (1, "bt601"): (1 << 20, 1858077, -360853, -748826, 1470104), (1, "bt709"): (1 << 20, 1945738, -196424, -490864, 1651297),
+          (1, "bt2020"): (1 << 20, 1972791, -172546, -599107, 1546230)}
+_SUBSAMPLING = {"444": (0, 0), "422": (1, 0), "420": (1, 1)}
+_PIX_FMT = re.compile(r"yuv(j?)(420|422|444)p(9|10|12|14|16)?(le|be)?$")
+_PIX_FMT_GRAY = re.compile(r"gr[ae]y(8|9|10|12|14|16)?(le|be)?$")
+_PIX_FMT_P0 = re.compile(r"p0(10|12|16)(le|be)?$")
+_Y4M_C = re.compile(r"(?:(420)(?:jpeg|mpeg2|paldv)|(420|422|444)(?:p(9|10|12|14|16))?|(mono)(?:p?(9|10|12|14|16))?)$")
+
+
+class YuvFormat(namedtuple("YuvFormat", "sub_x sub_y chroma depth msb matrix full_range")):
+    """A pixel format as the integers of include/vse_hip.h vse_yuv_to_bgr_format: sub_x, sub_y (log2 chroma subsampling), chroma (0 grey,
+    1 planar U then V, 2 interleaved UV), depth (8..16; 2-byte little-endian samples above 8), msb (1: the value in the word's high bits,
+    P010-style), matrix (a name of YUV_FORMAT_MATRICES) and full_range (0 | 1).  A tuple: equal formats compare and hash equal."""
+    __slots__ = ()
+
+    def __new__(cls, sub_x=1, sub_y=1, chroma=1, depth=8, msb=0, matrix="bt601", full_range=0):
+        self = super().__new__(cls, int(sub_x), int(sub_y), int(chroma), int(depth), int(msb), matrix, int(bool(full_range)))
+        if ((self.sub_x, self.sub_y) not in _SUBSAMPLING.values() or self.chroma not in (0, 1, 2) or not 8 <= self.depth <= 16
+                or self.msb not in ((0,) if self.depth == 8 else (0, 1)) or (self.chroma == 0 and (self.sub_x, self.sub_y) != (0, 0))
+                or (self.chroma == 2 and (self.sub_x, self.sub_y) != (1, 1))):
+            raise ValueError(f"not a YUV format: subsampling {self.sub_x}, {self.sub_y} of 0, 0 | 1, 0 | 1, 1, chroma {self.chroma} of 0 (4:4:4 "
+                             f"only) | 1 | 2 (4:2:0 only), depth {self.depth} of 8..16, msb {self.msb} of 0 | 1 (0 at depth 8)")
+        if matrix not in YUV_FORMAT_MATRICES:
+            raise ValueError(f"matrix must be one of {YUV_FORMAT_MATRICES}, not {matrix!r}")
+        return self
+
+    @property
+    def sample_bytes(self):
+        return 1 if self.depth == 8 else 2
+
+    @property
+    def sample_dtype(self):
+        return np.dtype(np.uint8) if self.depth == 8 else np.dtype("<u2")
+
+    def chroma_size(self, height, width):
+        return (height + self.sub_y) >> self.sub_y, (width + self.sub_x) >> self.sub_x
+
+    def plane_shapes(self, height, width):
+        """The planes of a height x width picture, in samples: [Y], [Y, U, V] or [Y, UV]."""
+        ch, cw = self.chroma_size(height, width)
+        return [(height, width)] + ([], [(ch, cw)] * 2, [(ch, 2 * cw)])[self.chroma]
+
+    def frame_bytes(self, height, width):
+        return self.sample_bytes * sum(r * c for r, c in self.plane_shapes(height, width))
+
+    def factors(self):
+        """-> (shift, maxv, yoff, coff, KY_s, BU_s, GU_s, GV_s, RV_s): sample = min(word >> shift, maxv) and the integers of the formula."""
+        s = self.depth - 8
+
+        def scaled(k):
+            m = (abs(k) + ((1 << s) >> 1)) >> s
+            return -m if k < 0 else m
+        return ((16 - self.depth if self.msb else 0), (1 << self.depth) - 1, 0 if self.full_range else 16 << s, 128 << s) + \
+            tuple(scaled(k) for k in YUV_K0[self.full_range, self.matrix])
+
+    @classmethod
+    def from_pix_fmt(cls, name, matrix="bt601", range="auto"):
+        """FFmpeg's name of a pixel format (yuv420p, yuvj420p, nv12, yuv422p, yuv444p, gray, yuv420p10le, yuv422p10le, yuv444p12le, gray10le,
+        p010le, p016le ...; i420 for yuv420p; 9, 10, 12, 14 and 16 bits; the `le` may be left out).  range: "auto" is limited, full for
+        the yuvj names; "limited" | "full" override it.  Big-endian samples and every other name are refused."""
+        if range not in YUV_RANGES:
+            raise ValueError(f"range must be one of {YUV_RANGES}, not {range!r}")
+        text = str(name).lower()
+        text = {"i420": "yuv420p", "p010": "p010le", "p012": "p012le", "p016": "p016le"}.get(text, text)
+        full, msb, chroma = 0, 0, 1
+        m = _PIX_FMT.match(text)
+        if m:
+            full, (sx, sy), depth, end = int(bool(m.group(1))), _SUBSAMPLING[m.group(2)], int(m.group(3) or 8), m.group(4)
+            ok = not (full and depth != 8) and not (depth == 8 and end)
+        elif text == "nv12":
+            (sx, sy), chroma, depth, end, ok = (1, 1), 2, 8, None, True
+        elif _PIX_FMT_P0.match(text):
+            m = _PIX_FMT_P0.match(text)
+            (sx, sy), chroma, depth, msb, end, ok = (1, 1), 2, int(m.group(1)), 1, m.group(2), True
+        elif _PIX_FMT_GRAY.match(text):
+            m = _PIX_FMT_GRAY.match(text)
+            (sx, sy), chroma, depth, end = (0, 0), 0, int(m.group(1) or 8), m.group(2)
+            ok = not (depth == 8 and end)
+        else:
+            ok, end = False, None
+        if end == "be":
+            raise ValueError(f"pixel format {name!r}: big-endian samples are not supported")
+        if not ok:
+            raise ValueError(f"pixel format {name!r} is not supported: planar yuv420p / yuv422p / yuv444p and gray at 8, 9, 10, 12, 14 or 16 "
+                             "bits (little-endian), yuvj420p / yuvj422p / yuvj444p, nv12, p010le / p012le / p016le")
+        if range != "auto":
+            full = int(range == "full")
+        return cls(sx, sy, chroma, depth, msb, matrix, full)
+
+    @classmethod
+    def from_y4m_tokens(cls, c_token=None, range_token=None, matrix="bt601", range="auto"):
+        """The format a YUV4MPEG2 header names: its C token (None: C420jpeg) and its XCOLORRANGE token (None: limited), both whole,
+        e.g. "C420p10" and "XCOLORRANGE=FULL".  range: "limited" | "full" override the header's.  ValueError names the token refused."""
+        if range not in YUV_RANGES:
+            raise ValueError(f"range must be one of {YUV_RANGES}, not {range!r}")
+        val = "420jpeg" if c_token is None else c_token[1:]
+        if "alpha" in val:
+            raise ValueError(f"an alpha plane ({c_token}) is not supported")
+        m = _Y4M_C.match(val)
+        if not m:
+            raise ValueError(f"chroma format {c_token} is not supported, only C420 (jpeg, mpeg2, paldv), C422, C444 and Cmono, each also at 9, "
+                             "10, 12, 14 or 16 bits (C420p10 ... Cmono10)")
+        sub, depth = m.group(1) or m.group(2) or m.group(4), int(m.group(3) or m.group(5) or 8)
+        if range_token not in (None, "XCOLORRANGE=FULL", "XCOLORRANGE=LIMITED"):
+            raise ValueError(f"colour range {range_token} is not supported, only XCOLORRANGE=FULL and XCOLORRANGE=LIMITED")
+        full = int(range_token == "XCOLORRANGE=FULL") if range == "auto" else int(range == "full")
+        sx, sy = _SUBSAMPLING.get(sub, (0, 0))
+        return cls(sx, sy, 0 if sub == "mono" else 1, depth, 0, matrix, full)
+
+
+class YuvFrame:
+    """Yuv420Frame for any YuvFormat `fmt`: rows [y0, y1) of one picture that has not been converted.  planes are views of samples (uint8,
+    or little-endian uint16 above 8 bits) of fmt.plane_shapes(height, width).  shape == (y1 - y0, width, 3), frame[a:b] narrows the row
+    range, to_bgr() gives the uint8 BGR ndarray by the integers of vse_yuv_to_bgr_format, pack_into() the packed sub-frame it takes."""
+
+    def __init__(self, planes, height, width, fmt, y0=0, y1=None):
+        if not isinstance(fmt, YuvFormat):
+            raise ValueError(f"fmt must be a YuvFormat, not {fmt!r}")
+        self.planes, self.height, self.width, self.fmt = tuple(planes), int(height), int(width), fmt
+        self.y0, self.y1 = int(y0), int(self.height if y1 is None else y1)
+        want = fmt.plane_shapes(self.height, self.width)
+        if ([tuple(p.shape) for p in self.planes] != want or any(p.dtype.itemsize != fmt.sample_bytes or p.dtype.kind != "u" for p in self.planes)
+                or not 0 <= self.y0 <= self.y1 <= self.height):
+            raise ValueError(f"the planes of a {self.height} x {self.width} picture of {fmt} are {want} of {fmt.sample_dtype}, rows "
+                             f"{self.y0}:{self.y1} asked of {[(tuple(p.shape), str(p.dtype)) for p in self.planes]}")
+
+    @property
+    def shape(self):
+        return (self.y1 - self.y0, self.width, 3)
+
+    @property
+    def matrix(self):
+        return self.fmt.matrix
+
+    def __getitem__(self, idx):
+        if not isinstance(idx, slice):
+            raise TypeError(f"a YuvFrame takes one row slice, not {idx!r}")
+        a, b, step = idx.indices(self.y1 - self.y0)
+        if step != 1:
+            raise TypeError(f"a YuvFrame takes a row slice of step 1, not {idx!r}")
+        return YuvFrame(self.planes, self.height, self.width, self.fmt, self.y0 + a, self.y0 + max(a, b))
+
+    @property
+    def row_parity(self):
+        return self.y0 & self.fmt.sub_y
+
+    def _chroma_rows(self):
+        c0 = self.y0 >> self.fmt.sub_y
+        return c0, (((self.y1 - 1) >> self.fmt.sub_y) + 1 if self.y1 > self.y0 else c0)
+
+    @property
+    def packed_bytes(self):
+        c0, c1 = self._chroma_rows()
+        return self.fmt.sample_bytes * ((self.y1 - self.y0) * self.width + sum((c1 - c0) * p.shape[1] for p in self.planes[1:]))
+
+    def pack_into(self, dst_u8):
+        """The packed sub-frame (luma rows y0..y1, then chroma rows y0 >> sub_y .. ((y1 - 1) >> sub_y) + 1 of each plane; row parity
+        y0 & sub_y) into the first packed_bytes bytes of the 1-D uint8 array dst_u8: one contiguous copy per plane, the samples as they
+        are (2 bytes each above 8 bits)."""
+        c0, c1 = self._chroma_rows()
+        pos = 0
+        for plane, (a, b) in zip(self.planes, [(self.y0, self.y1)] + [(c0, c1)] * (len(self.planes) - 1)):
+            part = plane[a:b]
+            nbytes = part.size * part.dtype.itemsize
+            np.copyto(dst_u8[pos:pos + nbytes].view(part.dtype).reshape(part.shape), part)
+            pos += nbytes
+        return pos
+
+    def to_bgr(self):
+        """uint8 BGR [y1 - y0, W, 3]: nearest chroma, the integers of vse_yuv_to_bgr_format (include/vse_hip.h) in int32."""
+        fmt = self.fmt
+        shift, maxv, yoff, coff, ky, bu, gu, gv, rv = fmt.factors()
+
+        def samples(a):
+            return np.minimum(np.asarray(a).astype(np.int32) >> shift, maxv)
+        c = np.maximum(samples(self.planes[0][self.y0:self.y1]) - yoff, 0) * np.int32(ky) + np.int32(1 << 19)
+        out = np.empty(self.shape, np.uint8)
+        if fmt.chroma == 0:
+            out[...] = np.clip(c >> 20, 0, 255)[..., None]
+            return out
+        rows, cols = np.arange(self.y0, self.y1) >> fmt.sub_y, np.arange(self.width) >> fmt.sub_x
+        if fmt.chroma == 1:
+            u, v = (samples(np.asarray(p)[rows][:, cols]) - coff for p in self.planes[1:])
+        else:
+            uv = np.asarray(self.planes[1])[rows]
+            u, v = samples(uv[:, 2 * cols]) - coff, samples(uv[:, 2 * cols + 1]) - coff
+        out[..., 0] = np.clip((c + np.int32(bu) * u) >> 20, 0, 255)
+        out[..., 1] = np.clip((c + np.int32(gu) * u + np.int32(gv) * v) >> 20, 0, 255)
+        out[..., 2] = np.clip((c + np.int32(rv) * v) >> 20, 0, 255)
+        return out
+
+
+def _planes_at(buf, off, height, width, fmt):
+    """The planes of one packed picture of `fmt` that starts at byte `off` of the 1-D uint8 array buf, as views (2-byte samples need no
+    alignment: numpy reads them where they are)."""
+    planes = []
+    for shp in fmt.plane_shapes(height, width):
+        nbytes = shp[0] * shp[1] * fmt.sample_bytes
+        planes.append(buf[off:off + nbytes].view(fmt.sample_dtype).reshape(shp))
+        off += nbytes
+    return tuple(planes)
+
+
+def write_yuv(path, frames_planes, fmt, fps=None, y4m=False):
+    """Frames given as plane tuples of `fmt` (fmt.plane_shapes, samples as integers) -> a headerless file (`ffmpeg -f rawvideo -pix_fmt
+    ...`), or with y4m=True and a frame rate the YUV4MPEG2 file `ffmpeg -f yuv4mpegpipe -strict -1` writes for that format (planar or grey,
+    value in the low bits)."""
+    frames_planes = [tuple(np.ascontiguousarray(p, fmt.sample_dtype) for p in f) for f in frames_planes]
+    h, w = frames_planes[0][0].shape
+    with open(path, "wb") as fp:
+        if y4m:
+            if fmt.chroma == 2 or fmt.msb:
+                raise ValueError(f"YUV4MPEG2 has no semi-planar or high-bit formats: {fmt}")
+            rate = Fraction(fps).limit_denominator(100000)
+            name = "mono" if fmt.chroma == 0 else {v: k for k, v in _SUBSAMPLING.items()}[fmt.sub_x, fmt.sub_y]
+            if fmt.depth > 8:
+                name += ("" if fmt.chroma == 0 else "p") + str(fmt.depth)
+            elif name == "420":
+                name = "420jpeg"
+            fp.write(b"YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C%s XCOLORRANGE=%s\n" % (w, h, rate.numerator, rate.denominator, name.encode(),
+                                                                                 b"FULL" if fmt.full_range else b"LIMITED"))
+        for f in frames_planes:
+            if [p.shape for p in f] != fmt.plane_shapes(h, w):
+                raise ValueError(f"the planes of a {h} x {w} picture of {fmt} are {fmt.plane_shapes(h, w)}, got {[p.shape for p in f]}")
+            if y4m:
+                fp.write(b"FRAME\n")
+            for p in f:
+                fp.write(p.tobytes())
+
+
 def bgr_to_yuv420(frame):
     """uint8 BGR [H,W,3] -> (Y [H,W], U [ch,cw], V [ch,cw]) uint8: plain BT.601 limited-range forward transform, chroma the mean of
     each 2 x 2 block (edge blocks of an odd size: of the pixels that exist).  Turns synthetic clips into test input; nothing is
@@ -375,6 +618,7 @@ class _Yuv420FileSource:
     """The frame-source interface over a memory-mapped file whose frames start at self._offsets (packed I420 or NV12 pictures)."""
 
     matrix = "bt601"
+    fmt = None                    # a YuvFormat: the frames are YuvFrames of it (YuvSource, Y4mSource(wide=True)); None: 8-bit 4:2:0 Yuv420Frames
 
     def _map(self, path):
         self.path = path
@@ -385,6 +629,8 @@ class _Yuv420FileSource:
         return size
 
     def _frame_bytes(self):
+        if self.fmt is not None:
+            return self.fmt.frame_bytes(self.height, self.width)
         ch, cw = _chroma_size(self.height, self.width)
         return self.height * self.width + 2 * ch * cw
 
@@ -395,6 +641,8 @@ class _Yuv420FileSource:
         h, w = self.height, self.width
         ch, cw = _chroma_size(h, w)
         off = self._offsets[frame_no - 1]
+        if self.fmt is not None:
+            return YuvFrame(_planes_at(self._buf, off, h, w, self.fmt), h, w, self.fmt)
         luma = self._buf[off:off + h * w].reshape(h, w)
         off += h * w
         if self.layout == "i420":
@@ -465,17 +713,69 @@ def parse_y4m_header(line, name, fps=None, what="file"):
     return width, height, rate
 
 
+def parse_y4m_header_wide(line, name, fps=None, what="file", matrix="bt601", range="auto"):
+    """parse_y4m_header for what `ffmpeg -f yuv4mpegpipe` (with -strict -1 above 8 bits) writes -> (width, height, fps, YuvFormat): C420*,
+    C422, C444 and Cmono, each also at 9, 10, 12, 14 or 16 bits, and XCOLORRANGE=FULL | LIMITED (range="limited" | "full" overrides the
+    header's; "auto" without a token is limited).  Refused, naming the token: interlaced video (It, Ib, Im), C411, an alpha plane, any other
+    C or XCOLORRANGE value and any parameter that is none of W H F I A C X."""
+    if line is None or line[:10] != b"YUV4MPEG2 ":
+        raise ValueError(f"{name}: not a YUV4MPEG2 {what}")
+    width = height = rate = c_token = range_token = None
+    for tok in line[10:].decode("ascii", "replace").split():
+        key, val = tok[0], tok[1:]
+        if key == "W" and val.isdigit():
+            width = int(val)
+        elif key == "H" and val.isdigit():
+            height = int(val)
+        elif key == "F":
+            num, _, den = val.partition(":")
+            if not (num.isdigit() and (den or "1").isdigit()):
+                raise ValueError(f"{name}: the frame rate {tok} is not a ratio of integers")
+            if int(num) > 0 and int(den or 1) > 0:
+                rate = int(num) / float(int(den or 1))
+        elif key == "I":
+            if val not in ("p", "?"):
+                raise ValueError(f"{name}: interlaced video ({tok}) is not supported")
+        elif key == "C":
+            c_token = tok
+        elif tok.startswith("XCOLORRANGE="):
+            range_token = tok
+        elif key not in ("A", "X"):
+            raise ValueError(f"{name}: the YUV4MPEG2 header's parameter {tok} is not known")
+    try:
+        fmt = YuvFormat.from_y4m_tokens(c_token, range_token, matrix, range)
+    except ValueError as e:
+        raise ValueError(f"{name}: {e}") from None
+    if not width or not height:
+        raise ValueError(f"{name}: the YUV4MPEG2 header carries no frame size")
+    if fps is not None:
+        rate = float(fps)
+    if rate is None:
+        raise ValueError(f"{name}: the YUV4MPEG2 header carries no frame rate (F0:0 or no F token): pass fps")
+    return width, height, rate, fmt
+
+
 class Y4mSource(_Yuv420FileSource):
-    """YUV4MPEG2 (.y4m) reader, memory-mapped, frames indexed once at open.  The header is parse_y4m_header's."""
+    """YUV4MPEG2 (.y4m) reader, memory-mapped, frames indexed once at open.  The header is parse_y4m_header's: 8-bit 4:2:0 limited range,
+    Yuv420Frames.  wide=True: parse_y4m_header_wide's, with `range` and a matrix of YUV_FORMAT_MATRICES; the frames are YuvFrames of
+    self.fmt (10-bit, 4:2:2, 4:4:4, grey, full range ...)."""
 
     layout = "i420"
 
-    def __init__(self, path, fps=None, matrix="bt601"):
-        self.matrix = _check_matrix(matrix)
+    def __init__(self, path, fps=None, matrix="bt601", wide=False, range="auto"):
+        if wide:
+            YuvFormat(matrix=matrix)        # a bad matrix is refused before the file is opened
+        else:
+            _check_matrix(matrix)
+        self.matrix = matrix
         size = self._map(path)
         mm = self._mm
         end = mm.find(b"\n", 0, 4096) if size else -1
-        self.width, self.height, self.fps = parse_y4m_header(mm[:end] if end >= 0 else None, path, fps)
+        line = mm[:end] if end >= 0 else None
+        if wide:
+            self.width, self.height, self.fps, self.fmt = parse_y4m_header_wide(line, path, fps, matrix=matrix, range=range)
+        else:
+            self.width, self.height, self.fps = parse_y4m_header(line, path, fps)
         nbytes = self._frame_bytes()
         self._offsets = []
         pos = end + 1
@@ -507,13 +807,22 @@ class Y4mStream:
 
     layout = "i420"
 
-    def __init__(self, fileobj, fps=None, matrix="bt601", name="<stream>"):
-        self.matrix = _check_matrix(matrix)
+    fmt = None                        # wide=True: the YuvFormat of the header; raw_frames() then yields YuvFrames (see Y4mSource)
+
+    def __init__(self, fileobj, fps=None, matrix="bt601", name="<stream>", wide=False, range="auto"):
+        if wide:
+            YuvFormat(matrix=matrix)
+        else:
+            _check_matrix(matrix)
+        self.matrix = matrix
         self._fp, self.name = fileobj, name
         self._pos = 0                 # bytes of the stream consumed
         self._started = False
         line = self._line(4096)
-        self.width, self.height, self.fps = parse_y4m_header(line, name, fps, what="stream")
+        if wide:
+            self.width, self.height, self.fps, self.fmt = parse_y4m_header_wide(line, name, fps, "stream", matrix, range)
+        else:
+            self.width, self.height, self.fps = parse_y4m_header(line, name, fps, what="stream")
         self.frame_count = None
 
     def _fill(self, view):
@@ -548,7 +857,7 @@ class Y4mStream:
         self._started = True
         h, w = self.height, self.width
         ch, cw = _chroma_size(h, w)
-        nbytes, count = h * w + 2 * ch * cw, 0
+        nbytes, count = (h * w + 2 * ch * cw if self.fmt is None else self.fmt.frame_bytes(h, w)), 0
         head = memoryview(bytearray(6))
         while True:
             pos = self._pos
@@ -565,6 +874,9 @@ class Y4mStream:
             if self._fill(memoryview(buf)) < nbytes:
                 break                      # a truncated last frame is not a frame
             count += 1
+            if self.fmt is not None:
+                yield YuvFrame(_planes_at(buf, 0, h, w, self.fmt), h, w, self.fmt)
+                continue
             planes = (buf[:h * w].reshape(h, w), buf[h * w:h * w + ch * cw].reshape(ch, cw), buf[h * w + ch * cw:].reshape(ch, cw))
             yield Yuv420Frame(planes, h, w, "i420", matrix=self.matrix)
         self.frame_count = count
@@ -597,27 +909,55 @@ class Yuv420Source(_Yuv420FileSource):
         self._offsets = range(0, self.frame_count * nbytes, nbytes)
 
 
+class YuvSource(_Yuv420FileSource):
+    """Yuv420Source for any YuvFormat: a headerless file of consecutive packed pictures of `fmt` (`ffmpeg -f rawvideo -pix_fmt NAME`, a
+    hardware decoder's P010 surfaces), memory-mapped; read_raw / raw_frames hand out YuvFrames.  A partial last frame is dropped."""
+
+    def __init__(self, path, width, height, fps, fmt):
+        if not isinstance(fmt, YuvFormat):
+            raise ValueError(f"fmt must be a YuvFormat, not {fmt!r}")
+        self.fmt, self.matrix = fmt, fmt.matrix
+        self.width, self.height, self.fps = int(width), int(height), float(fps)
+        if self.width < 1 or self.height < 1:
+            raise ValueError(f"{path}: frame size {width} x {height}")
+        size = self._map(path)
+        nbytes = self._frame_bytes()
+        self.frame_count = size // nbytes
+        self._offsets = range(0, self.frame_count * nbytes, nbytes)
+
+
 _RAW_YUV_EXT = {".yuv": "i420", ".i420": "i420", ".nv12": "nv12"}
+_RAW_PIX_FMT_EXT = {".p010": "p010le"}
 
 
-def open_source(path, fps=None, size=None, layout=None, matrix="bt601"):
+def open_source(path, fps=None, size=None, layout=None, matrix="bt601", wide=False, range="auto", pix_fmt=None):
     """The source of a file by its extension: .npy (needs fps), .y4m, .yuv / .i420 / .nv12 (headerless: need size=(width, height) and
     fps; `layout` overrides the extension's), anything else an AVI; "-" is a Y4mStream over standard input.  `matrix` goes to the
-    YUV 4:2:0 sources."""
+    YUV sources.  wide=True lets the Y4M readers accept what parse_y4m_header_wide does, with `range` ("auto": the header's).  pix_fmt
+    (a name of YuvFormat.from_pix_fmt; .p010 implies p010le) reads a headerless file of that format through YuvSource, with `range`
+    ("auto": the name's own) and any matrix of YUV_FORMAT_MATRICES; it needs size and fps."""
+    if range not in YUV_RANGES:
+        raise ValueError(f"range must be one of {YUV_RANGES}, not {range!r}")
     if str(path) == "-":
         import sys
-        return Y4mStream(sys.stdin.buffer, fps, matrix, name="<stdin>")
+        return Y4mStream(sys.stdin.buffer, fps, matrix, name="<stdin>", wide=wide, range=range)
     ext = os.path.splitext(str(path))[1].lower()
     if str(path).endswith(".npy"):
         if fps is None:
             raise ValueError("a .npy frame stack carries no frame rate: pass fps")
         return NpySource(path, fps)
     if ext == ".y4m":
-        return Y4mSource(path, fps, matrix)
-    if ext in _RAW_YUV_EXT:
+        return Y4mSource(path, fps, matrix, wide=wide, range=range)
+    if pix_fmt is None and layout is None:
+        pix_fmt = _RAW_PIX_FMT_EXT.get(ext)
+    if pix_fmt is not None or ext in _RAW_YUV_EXT:
         if size is None:
             raise ValueError(f"{path}: a headerless YUV file carries no frame size: pass size=(width, height)")
         if fps is None:
             raise ValueError(f"{path}: a headerless YUV file carries no frame rate: pass fps")
+        if pix_fmt is not None:
+            if layout is not None:
+                raise ValueError(f"{path}: pix_fmt {pix_fmt!r} names the plane layout; layout {layout!r} was given as well")
+            return YuvSource(path, size[0], size[1], fps, YuvFormat.from_pix_fmt(pix_fmt, matrix, range))
         return Yuv420Source(path, size[0], size[1], fps, layout or _RAW_YUV_EXT[ext], matrix)
     return AviBgr24Source(path)

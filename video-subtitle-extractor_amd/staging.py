@@ -16,7 +16,8 @@ producer thread while the current one is recognised (`prefetch`).
 Frames that are still YUV 4:2:0 (ingest.Yuv420Frame, from a source's read_raw / raw_frames) are packed into the slab as they are — 1.5
 bytes per pixel, half the slab copy and half the PCIe bytes of a BGR frame — and converted to BGR by one kernel on the copy stream
 (vse_yuv420_to_bgr, or vse_yuv_to_bgr_matrix for frames that say matrix="bt709"), so a consumer sees the same uint8 [n,H,W,3] tensor
-either way.
+either way.  Frames of any other format (ingest.YuvFrame: 10-bit, 4:2:2, 4:4:4, grey, full range, P010) go the same way through
+vse_yuv_to_bgr_format, keyed by shape, format and row parity.
 """
 import queue
 import threading
@@ -65,6 +66,8 @@ class Uploader:
     def stage(self, frames):
         """list of equal-shaped uint8 frames (views are fine) -> StagedBatch"""
         import torch
+        if hasattr(frames[0], "fmt"):
+            return self._stage_yuv(frames)
         if hasattr(frames[0], "pack_into"):
             return self._stage_yuv420(frames)
         shape = tuple(frames[0].shape)
@@ -113,6 +116,32 @@ class Uploader:
             packed = torch.empty((n, per), dtype=torch.uint8, device=self.device)
             packed.copy_(host, non_blocking=True)
             dev = ctx.yuv420_to_bgr(packed, n, h, w, first.layout, first.row_parity, matrix=first.matrix)
+            ev = torch.cuda.Event()
+            ev.record(self._stream)
+        self._busy[k] = ev
+        return StagedBatch(dev, ev)
+
+    def _stage_yuv(self, frames):
+        """ingest.YuvFrames of one shape, format and row parity -> StagedBatch of their BGR conversion: packed into the slab as they are
+        (3 bytes per pixel for 10-bit 4:2:0; frame stride rounded up to 16 bytes), one copy, one vse_yuv_to_bgr_format on the copy stream."""
+        import torch
+        first = frames[0]
+        key = (tuple(first.shape), first.fmt, first.row_parity)
+        for f in frames:
+            if (tuple(f.shape), getattr(f, "fmt", None), getattr(f, "row_parity", None)) != key:
+                raise ValueError("Uploader.stage: the YUV frames of a batch must share shape, format and row parity (y0 & sub_y): "
+                                 f"{key} and {(tuple(f.shape), getattr(f, 'fmt', None), getattr(f, 'row_parity', None))}")
+        ctx = self._context()
+        n, (h, w, _) = len(frames), first.shape
+        per = (first.packed_bytes + 15) & ~15
+        k, slab = self._slab(per * n)
+        host = slab[:per * n].view(n, per)
+        dst = host.numpy()
+        list(self._pool.map(lambda i: frames[i].pack_into(dst[i]), range(n)))
+        with torch.cuda.stream(self._stream):
+            packed = torch.empty((n, per), dtype=torch.uint8, device=self.device)          # (dropped here: see _stage_yuv420)
+            packed.copy_(host, non_blocking=True)
+            dev = ctx.yuv_to_bgr(packed, n, h, w, first.fmt, first.row_parity)
             ev = torch.cuda.Event()
             ev.record(self._stream)
         self._busy[k] = ev
