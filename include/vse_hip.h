@@ -727,6 +727,34 @@ int vse_yuv_to_bgr_format(vse_ctx* ctx, const void* d_yuv, int n, int h, int w, 
                           int matrix, int full_range, int row_parity, int64_t yuv_frame_stride, void* d_bgr, int64_t pitch,
                           int64_t bgr_frame_stride, void* stream);
 
+/* ---- frame ingest: interlaced YUV -> progressive YUV ------------------------------------------------------------------------------ */
+/* DVDs, 576i / 480i captures and 1080i broadcasts carry two fields of different times woven into one picture.  This turns n packed
+ * pictures of any format of vse_yuv_to_bgr_format's table into progressive pictures of the same format and layout
+ * (vse_yuv_frame_bytes(h, w, ..., row_parity 0)), which the conversions above then take unchanged.  Motion-adaptive: what did not change
+ * since the previous picture is woven (a subtitle keeps its full vertical resolution), what did is interpolated from the first field.
+ * The rule is applied to every plane on its own (Y, U, V, or the interleaved UV plane; the samples as stored words, no clamp), up and
+ * down a column only; row 0 of every plane is a top-field row.  For a plane of R rows, C the picture, P the previous picture:
+ *   out[y] = C[y]                        where y & 1 == keep (keep: the parity of the rows of the field first in time; top field first:
+ *                                        0), and for every y when R == 1
+ *   otherwise moved[x] = d_prev is NULL, or mode == 1, or |C[r][x] - P[r][x]| > T for any r of {y - 1, y, y + 1} inside [0, R)
+ *             a = C[y - 1] if y >= 1 else C[y + 1];   b = C[y + 1] if y + 1 < R else C[y - 1]
+ *             out[y][x] = moved[x] ? (a[x] + b[x] + 1) >> 1 : C[y][x]
+ *   T = thresh << (depth - 8), and << (16 - depth) more when msb = 1: thresh is in 8-bit levels.
+ * Picture f is at d_yuv + f yuv_frame_stride, its previous picture at d_prev + f prev_frame_stride, its result at d_out + f
+ * out_frame_stride: a run of consecutive frames passes d_prev = d_yuv - yuv_frame_stride and the same stride (the picture in front of
+ * the run must then be there), scattered frames are laid out as (previous, current) pairs with both strides doubled.  d_prev NULL: no
+ * frame has a previous picture, every frame is interpolated throughout.  One output frame per input frame.
+ * One launch on `stream`, no allocation, no device sync, exactly the packed bytes of each picture written.  A kernel of 16-byte loads and
+ * stores runs when every plane's base and row bytes and all frame strides are 16-byte aligned; otherwise one without conditions, except
+ * that 2-byte samples need 2-byte aligned bases and strides.
+ * Returns VSE_E_INVAL, with the values in vse_last_error, and launches nothing, for a format outside the table, keep or mode outside
+ * 0 | 1, thresh outside 0..255, n, h or w < 1, h * w > 2^31 - 1, a frame stride below the packed size (prev_frame_stride only with
+ * d_prev), 2-byte samples at an odd base or stride, or d_out equal to d_yuv or d_prev (the pictures must not overlap the output). */
+int vse_yuv_deinterlace(vse_ctx* ctx, const void* d_yuv, const void* d_prev /* NULL: no frame has a previous picture */, int n, int h, int w,
+                        int sub_x, int sub_y, int chroma, int depth, int msb, int keep /* 0 | 1 */, int mode /* 0 adaptive | 1 interpolate */,
+                        int thresh /* 8-bit levels, 0..255 */, int64_t yuv_frame_stride, int64_t prev_frame_stride, void* d_out,
+                        int64_t out_frame_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

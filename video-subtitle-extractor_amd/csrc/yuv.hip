@@ -36,6 +36,22 @@
 //            four 16-byte luma loads, two 16-byte chroma loads, six 16-byte stores, the chroma terms once for both rows.  Same conditions.
 //   general  any format: a lane owns 4 pixels of one row; 2-byte formats need 2-byte aligned bases and strides.
 // 8-bit 4:2:0 limited BT.601 / BT.709 goes to the two 8-bit kernels above and gives their bytes.
+//
+// vse_yuv_deinterlace (include/vse_hip.h) stands in front of all of them for interlaced pictures: packed pictures of any format above
+// become progressive pictures of the same format, which the conversions then take unchanged.  Motion-adaptive, per plane (Y, U, V or the
+// interleaved UV plane, the samples as stored words), up and down a column only; tests/deinterlace_ref.py restates it in int64:
+//   out[y] = C[y]                                                             rows of the first field (y & 1 == keep), and a one-row plane
+//   moved  = no previous picture, or mode interpolate, or |C[r] - P[r]| > T for a row r of {y - 1, y, y + 1} inside the plane
+//   out[y] = moved ? (a + b + 1) >> 1 : C[y],  a = C[y - 1] (C[y + 1] on row 0), b = C[y + 1] (C[y - 1] on the last row)
+// T = thresh << (depth - 8), and << (16 - depth) more for high-bit words: at most 255 << 8, and |C - P| < 2^16, so int32 is exact.
+// What stood still (a subtitle) keeps its full vertical resolution; what moved loses the second field.  HBM-bound byte work without
+// LDS, three packed pictures of traffic per frame (read C, read P, write), templated on the sample width alone:
+//   fast     a lane owns one 16-byte column of a plane and walks down a strip of 8 rows, carrying the row above and the row below with
+//            their `moved` masks in registers: every row of C and P is loaded once per strip, plus the strip's two halo rows.  The
+//            arithmetic is on whole dwords: the rounded mean is (a | b) - (((a ^ b) >> 1) & 0x7f7f7f7f) (0x7fff7fff for 2-byte
+//            samples) and the choice a mask.  Needs every plane's base and row bytes and all frame strides 16-byte aligned.
+//   general  the same walk on 4 samples, any width and byte alignment (2-byte samples: 2-byte aligned): the aligned dwords that hold them,
+//            shifted into place, sample by sample at the end of a row; dword stores where they are aligned, else sample by sample.
 #include <algorithm>
 #include <cstdio>
 
@@ -366,6 +382,210 @@ bool format_ok(int sub_x, int sub_y, int chroma, int depth) {
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// ---- deinterlace (vse_yuv_deinterlace) ---------------------------------------------------------------------------------------------
+constexpr int DEINT_STRIP = 8;        // rows a lane of the fast kernel walks down
+
+// The planes of one packed picture.  off and row are in bytes for the fast kernel and in samples for the general one; first[p] is the
+// fast kernel's work item at which plane p begins (items behind the last plane: the total).  Read with constant indices only, so the
+// struct stays in scalar registers.
+struct DeintPlanes {
+    int count;
+    int rows[3];
+    long off[3], row[3];
+    unsigned first[4];
+};
+
+// per sample of a dword: all ones where |c - p| > T
+template <typename S>
+__device__ __forceinline__ unsigned moved_word(unsigned c, unsigned p, int T) {
+    constexpr int BITS = 8 * sizeof(S), PER = 4 / sizeof(S);
+    constexpr unsigned ONES = (1u << BITS) - 1u;
+    unsigned m = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int d = (int)((c >> (BITS * k)) & ONES) - (int)((p >> (BITS * k)) & ONES);
+        m |= (d > T || -d > T) ? ONES << (BITS * k) : 0u;
+    }
+    return m;
+}
+
+// (a + b + 1) >> 1 of every sample of a dword
+template <typename S>
+__device__ __forceinline__ unsigned mean_word(unsigned a, unsigned b) {
+    return (a | b) - (((a ^ b) >> 1) & (sizeof(S) == 1 ? 0x7f7f7f7fu : 0x7fff7fffu));
+}
+
+// Work item i of a picture = (plane, strip of DEINT_STRIP rows, 16-byte column), columns fastest: consecutive lanes take consecutive
+// columns, so a wave's loads and stores of a row are contiguous.  blockIdx.y strides the frames.  prev == nullptr: every sample moved.
+template <typename S>
+__global__ __launch_bounds__(FAST_THREADS) void deinterlace_fast_kernel(const uint8_t* __restrict__ src, const uint8_t* __restrict__ prev, int n,
+                                                                        long sstride, long pstride, uint8_t* __restrict__ dst, long dstride,
+                                                                        DeintPlanes pl, int keep, int T) {
+    const bool adaptive = prev != nullptr;
+    const unsigned items = pl.first[3];
+    for (int f = blockIdx.y; f < n; f += gridDim.y) {
+        const uint8_t* s = src + (long)f * sstride;
+        const uint8_t* q = adaptive ? prev + (long)f * pstride : nullptr;
+        uint8_t* d = dst + (long)f * dstride;
+        for (unsigned i = blockIdx.x * FAST_THREADS + threadIdx.x; i < items; i += gridDim.x * FAST_THREADS) {
+            const bool p1 = i >= pl.first[1], p2 = i >= pl.first[2];
+            const unsigned j = i - (p2 ? pl.first[2] : p1 ? pl.first[1] : 0u);
+            const long rb = p2 ? pl.row[2] : p1 ? pl.row[1] : pl.row[0];
+            const int rows = p2 ? pl.rows[2] : p1 ? pl.rows[1] : pl.rows[0];
+            const unsigned cols = (unsigned)(rb >> 4), strip = j / cols, col = j - strip * cols;
+            const long base = (p2 ? pl.off[2] : p1 ? pl.off[1] : pl.off[0]) + 16L * col;
+            const int y0 = (int)strip * DEINT_STRIP, y1 = min(y0 + DEINT_STRIP, rows);
+            const auto load = [&](int y, uint4& c, uint4& m) {
+                c = *reinterpret_cast<const uint4*>(s + base + (long)y * rb);
+                if (adaptive) {
+                    const uint4 p = *reinterpret_cast<const uint4*>(q + base + (long)y * rb);
+                    m = make_uint4(moved_word<S>(c.x, p.x, T), moved_word<S>(c.y, p.y, T), moved_word<S>(c.z, p.z, T), moved_word<S>(c.w, p.w, T));
+                } else {
+                    m = make_uint4(~0u, ~0u, ~0u, ~0u);
+                }
+            };
+            uint4 ca, ma, cc, mc, cb, mb;                 // the row above, the row itself, the row below, each with its mask
+            load(y0, cc, mc);
+            ca = cc;
+            ma = make_uint4(0u, 0u, 0u, 0u);
+            if (y0 > 0) load(y0 - 1, ca, ma);
+            for (int y = y0; y < y1; ++y) {
+                cb = cc;
+                mb = make_uint4(0u, 0u, 0u, 0u);
+                const bool below = y + 1 < rows;
+                if (below) load(y + 1, cb, mb);
+                uint4 o = cc;
+                if ((y & 1) != keep && rows > 1) {
+                    const uint4 a = y > 0 ? ca : cb, b = below ? cb : ca;
+                    const uint4 m = make_uint4(ma.x | mc.x | mb.x, ma.y | mc.y | mb.y, ma.z | mc.z | mb.z, ma.w | mc.w | mb.w);
+                    o.x = (mean_word<S>(a.x, b.x) & m.x) | (cc.x & ~m.x);
+                    o.y = (mean_word<S>(a.y, b.y) & m.y) | (cc.y & ~m.y);
+                    o.z = (mean_word<S>(a.z, b.z) & m.z) | (cc.z & ~m.z);
+                    o.w = (mean_word<S>(a.w, b.w) & m.w) | (cc.w & ~m.w);
+                }
+                *reinterpret_cast<uint4*>(d + base + (long)y * rb) = o;
+                ca = cc;
+                ma = mc;
+                cc = cb;
+                mc = mb;
+            }
+        }
+    }
+}
+
+// 4 samples at p, of which ns exist, as dwords (low sample first).  All four: the aligned dwords they lie in, shifted into place (a
+// dword that holds one of the samples lies in the picture's buffer as far as the memory system cares, and the inputs are only read);
+// fewer (the end of a row): sample by sample.
+template <typename S>
+struct Quad {
+    unsigned v[sizeof(S) == 1 ? 1 : 2];
+};
+
+template <typename S>
+__device__ __forceinline__ Quad<S> load_quad(const S* p, int ns) {
+    constexpr int PER = 4 / sizeof(S), BITS = 8 * sizeof(S), DW = sizeof(S) == 1 ? 1 : 2;
+    Quad<S> q;
+    if (ns == 4) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+        const unsigned m = (unsigned)(a & 3);
+        const unsigned* w = reinterpret_cast<const unsigned*>(a - m);
+        if (m == 0) {
+#pragma unroll
+            for (int k = 0; k < DW; ++k) q.v[k] = w[k];
+        } else {
+            unsigned d[DW + 1];
+#pragma unroll
+            for (int k = 0; k <= DW; ++k) d[k] = w[k];
+#pragma unroll
+            for (int k = 0; k < DW; ++k) q.v[k] = (unsigned)((((unsigned long long)d[k + 1] << 32) | d[k]) >> (8 * m));
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < DW; ++k) q.v[k] = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < ns) q.v[k / PER] |= (unsigned)p[k] << (BITS * (k % PER));
+    }
+    return q;
+}
+
+// dword stores where p is 4-byte aligned and all four samples exist, sample by sample otherwise: no byte outside them is written
+template <typename S>
+__device__ __forceinline__ void store_quad(S* p, const Quad<S>& q, int ns) {
+    constexpr int PER = 4 / sizeof(S), BITS = 8 * sizeof(S), DW = sizeof(S) == 1 ? 1 : 2;
+    if (ns == 4 && (reinterpret_cast<uintptr_t>(p) & 3) == 0) {
+#pragma unroll
+        for (int k = 0; k < DW; ++k) reinterpret_cast<unsigned*>(p)[k] = q.v[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < ns) p[k] = (S)(q.v[k / PER] >> (BITS * (k % PER)));
+    }
+}
+
+// The fast kernel's walk on quads: lane (threadIdx.x, threadIdx.y) = samples 4 xg .. 4 xg + 3 of a strip of DEINT_STRIP rows of each plane;
+// blockIdx.y strides the strips, blockIdx.z the frames.  Strides, offsets and rows are counted in samples.
+template <typename S>
+__global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void deinterlace_general_kernel(const S* __restrict__ src, const S* __restrict__ prev, int n,
+                                                                                   long sstride, long pstride, S* __restrict__ dst, long dstride,
+                                                                                   DeintPlanes pl, int keep, int T) {
+    constexpr int DW = sizeof(S) == 1 ? 1 : 2;
+    const long x = 4L * (blockIdx.x * GEN_LANES + threadIdx.x);
+    const bool adaptive = prev != nullptr;
+    for (int f = blockIdx.z; f < n; f += gridDim.z) {
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            if (p >= pl.count || x >= pl.row[p]) continue;
+            const long rl = pl.row[p];
+            const int rows = pl.rows[p], ns = (int)min(4L, rl - x);
+            const S* s = src + (long)f * sstride + pl.off[p] + x;
+            const S* q = adaptive ? prev + (long)f * pstride + pl.off[p] + x : nullptr;
+            S* d = dst + (long)f * dstride + pl.off[p] + x;
+            const auto load = [&](int y, Quad<S>& c, Quad<S>& m) {
+                c = load_quad(s + (long)y * rl, ns);
+                if (adaptive) {
+                    const Quad<S> pq = load_quad(q + (long)y * rl, ns);
+#pragma unroll
+                    for (int k = 0; k < DW; ++k) m.v[k] = moved_word<S>(c.v[k], pq.v[k], T);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < DW; ++k) m.v[k] = ~0u;
+                }
+            };
+            for (int y0 = (blockIdx.y * GEN_ROWS + threadIdx.y) * DEINT_STRIP; y0 < rows; y0 += gridDim.y * GEN_ROWS * DEINT_STRIP) {
+                const int y1 = min(y0 + DEINT_STRIP, rows);
+                Quad<S> ca, ma, cc, mc, cb, mb;           // the row above, the row itself, the row below, each with its mask
+                load(y0, cc, mc);
+                ca = cc;
+#pragma unroll
+                for (int k = 0; k < DW; ++k) ma.v[k] = 0u;
+                if (y0 > 0) load(y0 - 1, ca, ma);
+                for (int y = y0; y < y1; ++y) {
+                    cb = cc;
+#pragma unroll
+                    for (int k = 0; k < DW; ++k) mb.v[k] = 0u;
+                    const bool below = y + 1 < rows;
+                    if (below) load(y + 1, cb, mb);
+                    Quad<S> o = cc;
+                    if ((y & 1) != keep && rows > 1) {
+                        const Quad<S> a = y > 0 ? ca : cb, b = below ? cb : ca;
+#pragma unroll
+                        for (int k = 0; k < DW; ++k) {
+                            const unsigned m = ma.v[k] | mc.v[k] | mb.v[k];
+                            o.v[k] = (mean_word<S>(a.v[k], b.v[k]) & m) | (cc.v[k] & ~m);
+                        }
+                    }
+                    store_quad(d + (long)y * rl, o, ns);
+                    ca = cc;
+                    ma = mc;
+                    cc = cb;
+                    mc = mb;
+                }
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -490,6 +710,81 @@ int vse_yuv_to_bgr_format(vse_ctx* c, const void* d_yuv, int n, int h, int w, in
     }
     if (hipGetLastError() != hipSuccess) {
         vse_set_error("vse_yuv_to_bgr_format: launch failed");
+        return VSE_E_HIP;
+    }
+    return VSE_OK;
+}
+
+int vse_yuv_deinterlace(vse_ctx* c, const void* d_yuv, const void* d_prev, int n, int h, int w, int sub_x, int sub_y, int chroma, int depth,
+                        int msb, int keep, int mode, int thresh, int64_t yuv_frame_stride, int64_t prev_frame_stride, void* d_out,
+                        int64_t out_frame_stride, void* stream) {
+    const size_t frame = vse_yuv_frame_bytes(h, w, sub_x, sub_y, chroma, depth, 0);
+    const int ss = depth > 8 ? 2 : 1;
+    const auto odd = [](const void* p, int64_t stride) { return (reinterpret_cast<uintptr_t>(p) & 1) || (stride & 1); };
+    if (!c || !d_yuv || !d_out || n < 1 || !frame || msb < 0 || msb > (ss == 2 ? 1 : 0) || keep < 0 || keep > 1 || mode < 0 || mode > 1 ||
+        thresh < 0 || thresh > 255 || yuv_frame_stride < (int64_t)frame || out_frame_stride < (int64_t)frame ||
+        (d_prev && prev_frame_stride < (int64_t)frame) || d_out == d_yuv || d_out == d_prev ||
+        (ss == 2 && (odd(d_yuv, yuv_frame_stride) || odd(d_out, out_frame_stride) || (d_prev && odd(d_prev, prev_frame_stride))))) {
+        char msg[560];
+        snprintf(msg, sizeof msg, "vse_yuv_deinterlace: bad arguments (n %d, frame %d x %d of at most 2^31 - 1 pixels, subsampling %d, %d of 0, 0 | "
+                 "1, 0 | 1, 1, chroma %d of 0 (with subsampling 0, 0) | 1 | 2 (with subsampling 1, 1), depth %d of 8..16, msb %d of 0 | 1 (0 at "
+                 "depth 8), keep %d of 0 | 1, mode %d of 0 | 1, thresh %d of 0..255, frame strides %lld, %lld (previous pictures) and %lld "
+                 "(output) of at least %zu, bases %p, %p, %p and strides 2-byte aligned for 2-byte samples, the output none of the inputs)",
+                 n, h, w, sub_x, sub_y, chroma, depth, msb, keep, mode, thresh, (long long)yuv_frame_stride, (long long)prev_frame_stride,
+                 (long long)out_frame_stride, frame, d_yuv, d_prev, d_out);
+        vse_set_error(msg);
+        return VSE_E_INVAL;
+    }
+    const long cw = ((long)w + sub_x) >> sub_x, ch = (((long)h - 1) >> sub_y) + 1, luma = (long)h * w;
+    DeintPlanes pl = {};
+    pl.count = chroma == CHROMA_NONE ? 1 : chroma == CHROMA_PLANAR ? 3 : 2;
+    pl.rows[0] = h;
+    pl.off[0] = 0;
+    pl.row[0] = w;
+    for (int p = 1; p < pl.count; ++p) {
+        pl.rows[p] = (int)ch;
+        pl.off[p] = luma + (p - 1) * ch * cw;
+        pl.row[p] = chroma == CHROMA_SEMI ? 2 * cw : cw;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_yuv);
+    const uint8_t* prev = mode == 0 ? reinterpret_cast<const uint8_t*>(d_prev) : nullptr;       // interpolate: no picture is compared
+    uint8_t* dst = reinterpret_cast<uint8_t*>(d_out);
+    bool fast = aligned16(src) && aligned16(dst) && yuv_frame_stride % 16 == 0 && out_frame_stride % 16 == 0 &&
+                (!prev || (aligned16(prev) && prev_frame_stride % 16 == 0));
+    for (int p = 0; p < pl.count; ++p) fast = fast && (pl.row[p] * ss) % 16 == 0;          // then every plane's offset is a multiple of 16 too
+    const int T = thresh << (depth - 8 + (msb ? 16 - depth : 0));
+    if (fast) {
+        long items = 0;
+        for (int p = 0; p < 3; ++p) {
+            pl.first[p] = (unsigned)items;
+            if (p >= pl.count) continue;
+            pl.off[p] *= ss;
+            pl.row[p] *= ss;
+            items += (pl.row[p] / 16) * ((pl.rows[p] + DEINT_STRIP - 1) / DEINT_STRIP);
+        }
+        pl.first[3] = (unsigned)items;
+        const dim3 grid((unsigned)std::min<long>((items + FAST_THREADS - 1) / FAST_THREADS, FAST_MAX_BLOCKS), (unsigned)std::min(n, 65535));
+        const auto kernel = ss == 1 ? deinterlace_fast_kernel<uint8_t> : deinterlace_fast_kernel<uint16_t>;
+        hipLaunchKernelGGL(kernel, grid, dim3(FAST_THREADS), 0, st, src, prev, n, (long)yuv_frame_stride, (long)prev_frame_stride, dst,
+                           (long)out_frame_stride, pl, keep, T);
+    } else {
+        const long groups = (std::max(pl.row[0], pl.row[pl.count - 1]) + 3) / 4;
+        const int strips = (h + DEINT_STRIP - 1) / DEINT_STRIP;
+        const dim3 grid((unsigned)((groups + GEN_LANES - 1) / GEN_LANES), (unsigned)std::min((strips + GEN_ROWS - 1) / GEN_ROWS, 65535),
+                        (unsigned)std::min(n, 65535));
+        const dim3 block(GEN_LANES, GEN_ROWS);
+        if (ss == 1) {
+            hipLaunchKernelGGL(deinterlace_general_kernel<uint8_t>, grid, block, 0, st, src, prev, n, (long)yuv_frame_stride, (long)prev_frame_stride,
+                               dst, (long)out_frame_stride, pl, keep, T);
+        } else {
+            hipLaunchKernelGGL(deinterlace_general_kernel<uint16_t>, grid, block, 0, st, reinterpret_cast<const uint16_t*>(src),
+                               reinterpret_cast<const uint16_t*>(prev), n, (long)yuv_frame_stride / 2, (long)prev_frame_stride / 2,
+                               reinterpret_cast<uint16_t*>(dst), (long)out_frame_stride / 2, pl, keep, T);
+        }
+    }
+    if (hipGetLastError() != hipSuccess) {
+        vse_set_error("vse_yuv_deinterlace: launch failed");
         return VSE_E_HIP;
     }
     return VSE_OK;

@@ -31,7 +31,7 @@ EXPORTS = [
     "vse_frame_hold_bounded_state_bytes", "vse_frame_hold_bounded",
     "vse_frame_cells_hold_bounded_state_bytes", "vse_frame_cells_hold_bounded",
     "vse_interval_stream_state_bytes", "vse_interval_stream",
-    "vse_yuv_frame_bytes", "vse_yuv_to_bgr_format",
+    "vse_yuv_frame_bytes", "vse_yuv_to_bgr_format", "vse_yuv_deinterlace",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -241,6 +241,7 @@ def load_library(path=None):
     lib.vse_yuv_frame_bytes.restype = C.c_size_t
     lib.vse_yuv_frame_bytes.argtypes = [C.c_int] * 7
     lib.vse_yuv_to_bgr_format.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 11 + [C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+    lib.vse_yuv_deinterlace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 11 + [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     if lib.vse_sizeof_op() != ir.OP_DT.itemsize or lib.vse_sizeof_view() != ir.VIEW_DT.itemsize:
         raise VseError(f"ABI mismatch: vse_op {lib.vse_sizeof_op()} vs {ir.OP_DT.itemsize}, "
                        f"vse_view {lib.vse_sizeof_view()} vs {ir.VIEW_DT.itemsize}")
@@ -983,10 +984,47 @@ class Context:
                                               C.c_void_p(out.data_ptr()), out.stride(1), dstride, self.stream()), "vse_yuv_to_bgr_format")
         return out
 
+    def yuv_deinterlace(self, packed, n, h, w, fmt, prev=None, prev_stride=None, keep=0, mode=0, thresh=10, out=None):
+        """packed: cuda uint8 holding n packed interlaced pictures of h x w pixels of the format `fmt` (as yuv_to_bgr's, row parity 0), 1-D
+        (back to back) or 2-D [n, stride in bytes] -> cuda uint8 [n, stride] of the progressive pictures in the same packing, on the current
+        stream (include/vse_hip.h vse_yuv_deinterlace).  prev: a cuda uint8 tensor whose first byte is the previous picture of frame 0 (None:
+        no frame has one, all are interpolated); frame f's previous picture lies f * prev_stride bytes behind it (default: prev's own row
+        stride when it is 2-D, else packed's frame stride), so a run of consecutive frames in one buffer passes the view that starts one
+        frame earlier.  keep: 0 top field first | 1 bottom field first; mode: 0 | "adaptive", 1 | "interpolate"; thresh in 8-bit levels.
+        out: write into this uint8 tensor (1-D or [n, stride]) instead; it must not overlap the inputs."""
+        t = self.torch
+        n, h, w = int(n), int(h), int(w)
+        mode = DEINTERLACE_MODES.get(mode, mode)
+        if mode not in (0, 1):
+            raise VseError(f"yuv_deinterlace: mode {mode!r} is not one of {sorted(DEINTERLACE_MODES)} (0 | 1)")
+        frame = self.lib.vse_yuv_frame_bytes(h, w, int(fmt.sub_x), int(fmt.sub_y), int(fmt.chroma), int(fmt.depth), 0)
+
+        def stride_of(a, what):
+            assert a.dtype == t.uint8 and a.dim() in (1, 2) and a.stride(-1) == 1, what
+            if a.dim() == 2:
+                assert a.shape[0] == n and a.shape[1] >= frame, (what, tuple(a.shape), n, frame)
+                return a.stride(0) if n > 1 else max(a.stride(0), frame)
+            assert a.numel() >= n * frame, (what, a.numel(), n, frame)
+            return frame
+        sstride = stride_of(packed, "packed")
+        if out is None:
+            out = t.empty((max(n, 0), (frame + 15) & ~15), dtype=t.uint8, device=self.tdev)
+        ostride = stride_of(out, "out")
+        pptr, pstride = None, 0
+        if prev is not None:
+            assert prev.dtype == t.uint8 and prev.stride(-1) == 1
+            pptr = C.c_void_p(prev.data_ptr())
+            pstride = int(prev_stride) if prev_stride is not None else (prev.stride(0) if prev.dim() == 2 and n > 1 else sstride)
+        _check(self.lib.vse_yuv_deinterlace(self.handle, C.c_void_p(packed.data_ptr()), pptr, n, h, w, int(fmt.sub_x), int(fmt.sub_y),
+                                            int(fmt.chroma), int(fmt.depth), int(fmt.msb), int(keep), mode, int(thresh), sstride, pstride,
+                                            C.c_void_p(out.data_ptr()), ostride, self.stream()), "vse_yuv_deinterlace")
+        return out
+
 
 YUV_LAYOUTS = {"i420": 0, "nv12": 1}
 YUV_MATRICES = {"bt601": 0, "bt709": 1}
 YUV_FORMAT_MATRICES = {"bt601": 0, "bt709": 1, "bt2020": 2}      # vse_yuv_to_bgr_format's
+DEINTERLACE_MODES = {"adaptive": 0, "interpolate": 1}            # vse_yuv_deinterlace's
 INTERVAL_MODES = {"min": 0, "max": 1, "mean": 2}
 INTERVAL_SEG_CONTINUE, INTERVAL_SEG_EMIT = 1, 2          # vse_interval_seg.flags (include/vse_hip.h)
 INTERVAL_STREAM_MAX_SEGS = 32   # VSE_INTERVAL_STREAM_MAX_SEGS: the segments of one vse_interval_stream call

@@ -95,7 +95,10 @@ class RetainedSource:
 
 
 def _frame_nbytes(frame):
-    return sum(p.nbytes for p in frame.planes) if hasattr(frame, "planes") else frame.nbytes
+    """Bytes a retained frame keeps alive: its planes, and for an ingest.InterlacedYuvFrame its previous picture's too (it pins them)."""
+    if not hasattr(frame, "planes"):
+        return frame.nbytes
+    return sum(p.nbytes for p in frame.planes) + sum(p.nbytes for p in getattr(frame, "prev", None) or ())
 
 
 def frame_preprocess(subtitle_area, frame):
@@ -740,6 +743,13 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
                    "the Y4M header's XCOLORRANGE or the pixel format's own, else limited]")
     p.add_argument("--pix-fmt", default=None, metavar="NAME", help="pixel format of a headerless YUV file by FFmpeg's name (yuv420p10le, "
                    "yuv422p, yuv444p, gray, p010le, yuvj420p ...) [by extension; .p010 is p010le]")
+    p.add_argument("--deinterlace", default=None, choices=("adaptive", "interpolate"), help="interlaced YUV (576i / 480i / 1080i: Y4M with "
+                   "It / Ib, or a headerless file with --pix-fmt and --field-order): deinterlace on the GPU, weaving what stood still "
+                   "(adaptive) or interpolating the second field throughout; turns --wide-yuv on")
+    p.add_argument("--field-order", default="auto", choices=("auto", "tff", "bff"), help="--deinterlace: which field comes first [auto: the "
+                   "Y4M header's It / Ib; Ip is then left as it is]; tff / bff override the header")
+    p.add_argument("--deinterlace-thresh", type=int, default=10, metavar="N", help="--deinterlace adaptive: a sample that changed by more "
+                   "than N 8-bit levels since the previous frame has moved, 0..255 [10]")
     p.add_argument("--area", default=None, metavar="ymin,ymax,xmin,xmax|auto", help="the subtitle area in frame pixels, or `auto` to "
                    "look for it first (not in one pass) [none: the whole frame, fps sampler]")
     p.add_argument("--selector", default="fps", choices=("fps", "change", "hold"), help="which frames go to OCR [fps]")
@@ -807,8 +817,11 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
                 raise ValueError("--streaming-composite makes its pictures with stream_fn; the composite_fn given makes those of the "
                                  "compositor's own pass and would not be called")
             composite_params = {"streaming": True, **({} if stream_fn is None else {"stream_fn": stream_fn})}
-        source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout, matrix=args.matrix, wide=args.wide_yuv,
-                                    range=args.range, pix_fmt=args.pix_fmt)
+        if args.deinterlace is None and (args.field_order != "auto" or args.deinterlace_thresh != 10):
+            raise ValueError("--field-order and --deinterlace-thresh belong to --deinterlace adaptive | interpolate")
+        source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout, matrix=args.matrix,
+                                    wide=args.wide_yuv or args.deinterlace is not None, range=args.range, pix_fmt=args.pix_fmt,
+                                    deinterlace=args.deinterlace, field_order=args.field_order, deinterlace_thresh=args.deinterlace_thresh)
         uploader = None
         if ocr is None:
             if args.weights_dir is not None:

@@ -28,6 +28,11 @@ range, BT.2020 and P010-style semi-planar surfaces are accepted only when asked 
 integers of include/vse_hip.h vse_yuv_to_bgr_format; YuvFrame.to_bgr and the device convert with the same integers (the 8-bit ones with
 factors scaled to the depth, nearest chroma, no transfer function: PQ / HLG material comes out flat, its text and edges remain).
 
+Interlaced video (InterlacedYuvFrame; deinterlace="adaptive" | "interpolate" on those readers, on top of wide=True): the pictures are two
+woven fields.  A frame carries the previous picture's planes beside its own; to_bgr() and the device (vse_yuv_deinterlace, through
+staging.Uploader) keep the first field's rows, weave what did not change since the previous picture and interpolate the rest, by the same
+integers.  Without the keyword interlaced headers are refused as before.
+
 Pipes (Y4mStream): `ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m vse_amd.extractor -` puts compressed video of any
 codec through a decoder that is not ours; the stream is read once, front to back, never seeks and has no read(): its absence is how
 SubtitleExtractor sees that it must work in one pass.
@@ -504,26 +509,138 @@ class YuvFrame:
 
     def to_bgr(self):
         """uint8 BGR [y1 - y0, W, 3]: nearest chroma, the integers of vse_yuv_to_bgr_format (include/vse_hip.h) in int32."""
-        fmt = self.fmt
-        shift, maxv, yoff, coff, ky, bu, gu, gv, rv = fmt.factors()
+        return _rows_to_bgr(self.fmt, self.planes[0][self.y0:self.y1], self.planes[1:], np.arange(self.y0, self.y1) >> self.fmt.sub_y, self.width)
 
-        def samples(a):
-            return np.minimum(np.asarray(a).astype(np.int32) >> shift, maxv)
-        c = np.maximum(samples(self.planes[0][self.y0:self.y1]) - yoff, 0) * np.int32(ky) + np.int32(1 << 19)
-        out = np.empty(self.shape, np.uint8)
-        if fmt.chroma == 0:
-            out[...] = np.clip(c >> 20, 0, 255)[..., None]
-            return out
-        rows, cols = np.arange(self.y0, self.y1) >> fmt.sub_y, np.arange(self.width) >> fmt.sub_x
-        if fmt.chroma == 1:
-            u, v = (samples(np.asarray(p)[rows][:, cols]) - coff for p in self.planes[1:])
-        else:
-            uv = np.asarray(self.planes[1])[rows]
-            u, v = samples(uv[:, 2 * cols]) - coff, samples(uv[:, 2 * cols + 1]) - coff
-        out[..., 0] = np.clip((c + np.int32(bu) * u) >> 20, 0, 255)
-        out[..., 1] = np.clip((c + np.int32(gu) * u + np.int32(gv) * v) >> 20, 0, 255)
-        out[..., 2] = np.clip((c + np.int32(rv) * v) >> 20, 0, 255)
+
+def _rows_to_bgr(fmt, luma, chroma, rows, width):
+    """YuvFrame.to_bgr on luma rows `luma` [n, width] whose chroma stands in row rows[k] of the planes `chroma` -> uint8 BGR [n, width, 3]."""
+    shift, maxv, yoff, coff, ky, bu, gu, gv, rv = fmt.factors()
+
+    def samples(a):
+        return np.minimum(np.asarray(a).astype(np.int32) >> shift, maxv)
+    c = np.maximum(samples(luma) - yoff, 0) * np.int32(ky) + np.int32(1 << 19)
+    out = np.empty((len(rows), width, 3), np.uint8)
+    if fmt.chroma == 0:
+        out[...] = np.clip(c >> 20, 0, 255)[..., None]
         return out
+    cols = np.arange(width) >> fmt.sub_x
+    if fmt.chroma == 1:
+        u, v = (samples(np.asarray(p)[rows][:, cols]) - coff for p in chroma)
+    else:
+        uv = np.asarray(chroma[0])[rows]
+        u, v = samples(uv[:, 2 * cols]) - coff, samples(uv[:, 2 * cols + 1]) - coff
+    out[..., 0] = np.clip((c + np.int32(bu) * u) >> 20, 0, 255)
+    out[..., 1] = np.clip((c + np.int32(gu) * u + np.int32(gv) * v) >> 20, 0, 255)
+    out[..., 2] = np.clip((c + np.int32(rv) * v) >> 20, 0, 255)
+    return out
+
+
+# ---- interlaced pictures (vse_yuv_deinterlace) ----------------------------------------------------------------------------------------
+DEINTERLACE_MODES = ("adaptive", "interpolate")
+FIELD_ORDERS = ("tff", "bff")
+
+
+def _check_deinterlace(deinterlace, field_order, thresh, orders=("auto",) + FIELD_ORDERS):
+    if deinterlace is not None and deinterlace not in DEINTERLACE_MODES:
+        raise ValueError(f"deinterlace must be None or one of {DEINTERLACE_MODES}, not {deinterlace!r}")
+    if field_order not in orders:
+        raise ValueError(f"field_order must be one of {orders}, not {field_order!r}")
+    if isinstance(thresh, bool) or int(thresh) != thresh or not 0 <= thresh <= 255:
+        raise ValueError(f"the deinterlace threshold is an integer of 0..255 (8-bit levels), not {thresh!r}")
+    return int(thresh)
+
+
+def deinterlace_rows(cur, prev, keep, thresh_words, a=0, b=None):
+    """Rows [a, b) of one plane deinterlaced by the rule of include/vse_hip.h vse_yuv_deinterlace: cur, prev (None: every sample moved)
+    are the whole plane's stored words, keep the parity of the rows that stay, thresh_words the threshold T in word units."""
+    rows = cur.shape[0]
+    b = rows if b is None else b
+    out = np.array(cur[a:b], copy=True)
+    if rows == 1 or b <= a:
+        return out
+    lo, hi = max(a - 1, 0), min(b + 1, rows)
+    c = np.asarray(cur[lo:hi]).astype(np.int32)
+    moved = np.ones(c.shape, bool) if prev is None else np.abs(c - np.asarray(prev[lo:hi]).astype(np.int32)) > thresh_words
+    for y in range(a + ((a ^ keep ^ 1) & 1), b, 2):              # the rows of the other field
+        up, down = (y - 1 if y >= 1 else y + 1), (y + 1 if y + 1 < rows else y - 1)
+        m = moved[max(y - 1, 0) - lo:min(y + 1, rows - 1) + 1 - lo].any(axis=0)
+        out[y - a] = np.where(m, (c[up - lo] + c[down - lo] + 1) >> 1, c[y - lo]).astype(out.dtype)
+    return out
+
+
+def _same_planes(a, b):
+    """Whether two plane tuples are the same memory (views made twice of one buffer are)."""
+    return a is b or (len(a) == len(b) and all(p.shape == q.shape and p.strides == q.strides and p.dtype == q.dtype
+                                               and p.__array_interface__["data"][0] == q.__array_interface__["data"][0] for p, q in zip(a, b)))
+
+
+class InterlacedYuvFrame(YuvFrame):
+    """A YuvFrame whose picture is two woven fields: rows [y0, y1) of the picture vse_yuv_deinterlace makes of `planes` and `prev`, the
+    plane tuple of the previous picture (None: the clip's first frame, interpolated throughout).  field_order "tff" | "bff" names the field
+    that comes first in time (its rows are kept), mode is "adaptive" (weave what did not change by more than `thresh` 8-bit levels) or
+    "interpolate".  frame[a:b] is the same class with the same prev; to_bgr() deinterlaces on the host by the same integers and converts
+    as YuvFrame does, so f[a:b].to_bgr() == f.to_bgr()[a:b]; staging.Uploader deinterlaces and converts on the device."""
+
+    def __init__(self, planes, height, width, fmt, prev=None, field_order="tff", mode="adaptive", thresh=10, y0=0, y1=None):
+        super().__init__(planes, height, width, fmt, y0, y1)
+        self.thresh = _check_deinterlace(mode, field_order, thresh, FIELD_ORDERS)
+        if mode is None:
+            raise ValueError(f"mode must be one of {DEINTERLACE_MODES}, not None")
+        self.field_order, self.mode = field_order, mode
+        self.prev = None if prev is None else tuple(prev)
+        if self.prev is not None and [(tuple(p.shape), p.dtype.itemsize, p.dtype.kind) for p in self.prev] != \
+                [(tuple(p.shape), p.dtype.itemsize, p.dtype.kind) for p in self.planes]:
+            raise ValueError(f"the previous picture's planes {[(tuple(p.shape), str(p.dtype)) for p in self.prev]} are not the picture's "
+                             f"{[(tuple(p.shape), str(p.dtype)) for p in self.planes]}")
+
+    @property
+    def keep(self):
+        return FIELD_ORDERS.index(self.field_order)
+
+    @property
+    def thresh_words(self):
+        return self.thresh << (self.fmt.depth - 8 + (16 - self.fmt.depth if self.fmt.msb else 0))
+
+    def __getitem__(self, idx):
+        if not isinstance(idx, slice):
+            raise TypeError(f"an InterlacedYuvFrame takes one row slice, not {idx!r}")
+        a, b, step = idx.indices(self.y1 - self.y0)
+        if step != 1:
+            raise TypeError(f"an InterlacedYuvFrame takes a row slice of step 1, not {idx!r}")
+        return InterlacedYuvFrame(self.planes, self.height, self.width, self.fmt, self.prev, self.field_order, self.mode, self.thresh,
+                                  self.y0 + a, self.y0 + max(a, b))
+
+    def _deinterlaced(self, k, a, b):
+        prev = None if self.prev is None or self.mode == "interpolate" else self.prev[k]
+        return deinterlace_rows(self.planes[k], prev, self.keep, self.thresh_words, a, b)
+
+    def deinterlaced_planes(self):
+        """The whole progressive picture's planes (not only rows [y0, y1)), in numpy by the rule."""
+        return tuple(self._deinterlaced(k, 0, None) for k in range(len(self.planes)))
+
+    def to_bgr(self):
+        c0, c1 = self._chroma_rows()
+        chroma = [self._deinterlaced(k, c0, c1) for k in range(1, len(self.planes))]
+        return _rows_to_bgr(self.fmt, self._deinterlaced(0, self.y0, self.y1), chroma, (np.arange(self.y0, self.y1) >> self.fmt.sub_y) - c0,
+                            self.width)
+
+    def band(self):
+        """(a, b): the rows packed for the device in place of [y0, y1): two more on either side, a rounded down to a multiple of 4 and b up to
+        even (both inside the picture), so that every plane of the packed band begins on a top-field row and the rows that get the band's
+        edge rule in place of the picture's are none of [y0, y1)."""
+        a = max(0, self.y0 - 2) & ~3
+        return a, min(self.height, (min(self.height, self.y1 + 2) + 1) & ~1)
+
+    @property
+    def band_bytes(self):
+        return self._band_frame(*self.band()).packed_bytes
+
+    def _band_frame(self, a, b, prev=False):
+        return YuvFrame(self.prev if prev else self.planes, self.height, self.width, self.fmt, a, b)
+
+    def pack_band_into(self, dst_u8, prev=False):
+        """YuvFrame.pack_into of rows band() of the picture (prev: of the previous picture) -> bytes written."""
+        return self._band_frame(*self.band(), prev=prev).pack_into(dst_u8)
 
 
 def _planes_at(buf, off, height, width, fmt):
@@ -537,10 +654,12 @@ def _planes_at(buf, off, height, width, fmt):
     return tuple(planes)
 
 
-def write_yuv(path, frames_planes, fmt, fps=None, y4m=False):
+def write_yuv(path, frames_planes, fmt, fps=None, y4m=False, interlace="p"):
     """Frames given as plane tuples of `fmt` (fmt.plane_shapes, samples as integers) -> a headerless file (`ffmpeg -f rawvideo -pix_fmt
     ...`), or with y4m=True and a frame rate the YUV4MPEG2 file `ffmpeg -f yuv4mpegpipe -strict -1` writes for that format (planar or grey,
-    value in the low bits)."""
+    value in the low bits).  interlace: the header's I token, "p" progressive | "t" top field first | "b" bottom field first."""
+    if interlace not in ("p", "t", "b"):
+        raise ValueError(f"interlace must be one of 'p', 't', 'b', not {interlace!r}")
     frames_planes = [tuple(np.ascontiguousarray(p, fmt.sample_dtype) for p in f) for f in frames_planes]
     h, w = frames_planes[0][0].shape
     with open(path, "wb") as fp:
@@ -553,8 +672,8 @@ def write_yuv(path, frames_planes, fmt, fps=None, y4m=False):
                 name += ("" if fmt.chroma == 0 else "p") + str(fmt.depth)
             elif name == "420":
                 name = "420jpeg"
-            fp.write(b"YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C%s XCOLORRANGE=%s\n" % (w, h, rate.numerator, rate.denominator, name.encode(),
-                                                                                 b"FULL" if fmt.full_range else b"LIMITED"))
+            fp.write(b"YUV4MPEG2 W%d H%d F%d:%d I%s A1:1 C%s XCOLORRANGE=%s\n" % (w, h, rate.numerator, rate.denominator, interlace.encode(),
+                                                                                 name.encode(), b"FULL" if fmt.full_range else b"LIMITED"))
         for f in frames_planes:
             if [p.shape for p in f] != fmt.plane_shapes(h, w):
                 raise ValueError(f"the planes of a {h} x {w} picture of {fmt} are {fmt.plane_shapes(h, w)}, got {[p.shape for p in f]}")
@@ -619,6 +738,15 @@ class _Yuv420FileSource:
 
     matrix = "bt601"
     fmt = None                    # a YuvFormat: the frames are YuvFrames of it (YuvSource, Y4mSource(wide=True)); None: 8-bit 4:2:0 Yuv420Frames
+    deinterlace = None            # "adaptive" | "interpolate" with field_order "tff" | "bff": the frames are InterlacedYuvFrames
+    field_order = None
+    deinterlace_thresh = 10
+    _last = None                  # (frame number, planes) of the last read_raw: the next frame's prev is then the same views
+
+    def _planes(self, frame_no):
+        if self._last is None or self._last[0] != frame_no:
+            self._last = (frame_no, _planes_at(self._buf, self._offsets[frame_no - 1], self.height, self.width, self.fmt))
+        return self._last[1]
 
     def _map(self, path):
         self.path = path
@@ -641,6 +769,9 @@ class _Yuv420FileSource:
         h, w = self.height, self.width
         ch, cw = _chroma_size(h, w)
         off = self._offsets[frame_no - 1]
+        if self.fmt is not None and self.field_order is not None:
+            prev = self._planes(frame_no - 1) if frame_no > 1 else None
+            return InterlacedYuvFrame(self._planes(frame_no), h, w, self.fmt, prev, self.field_order, self.deinterlace, self.deinterlace_thresh)
         if self.fmt is not None:
             return YuvFrame(_planes_at(self._buf, off, h, w, self.fmt), h, w, self.fmt)
         luma = self._buf[off:off + h * w].reshape(h, w)
@@ -668,7 +799,7 @@ class _Yuv420FileSource:
         return None if not 0 <= frame_no < self.frame_count else frame_no * 1000.0 / self.fps
 
     def close(self):
-        self._buf = None
+        self._buf = self._last = None
         if self._mm is not None:
             try:
                 self._mm.close()
@@ -718,9 +849,17 @@ def parse_y4m_header_wide(line, name, fps=None, what="file", matrix="bt601", ran
     C422, C444 and Cmono, each also at 9, 10, 12, 14 or 16 bits, and XCOLORRANGE=FULL | LIMITED (range="limited" | "full" overrides the
     header's; "auto" without a token is limited).  Refused, naming the token: interlaced video (It, Ib, Im), C411, an alpha plane, any other
     C or XCOLORRANGE value and any parameter that is none of W H F I A C X."""
+    return parse_y4m_header_fields(line, name, fps, what, matrix, range, None)[:4]
+
+
+def parse_y4m_header_fields(line, name, fps=None, what="file", matrix="bt601", range="auto", field_order="auto"):
+    """parse_y4m_header_wide for a reader that deinterlaces -> (width, height, fps, YuvFormat, order): order is "tff" | "bff" when the
+    pictures are woven fields, None when they are progressive.  field_order "auto" takes the header's word: It is "tff", Ib "bff", Ip, I?
+    and no I token progressive, and Im (mixed; the frames' own flags are not read) is refused; "tff" | "bff" say it in the header's place,
+    whatever its I token (mis-flagged files).  field_order None refuses every interlaced header, as parse_y4m_header_wide does."""
     if line is None or line[:10] != b"YUV4MPEG2 ":
         raise ValueError(f"{name}: not a YUV4MPEG2 {what}")
-    width = height = rate = c_token = range_token = None
+    width = height = rate = c_token = range_token = order = None
     for tok in line[10:].decode("ascii", "replace").split():
         key, val = tok[0], tok[1:]
         if key == "W" and val.isdigit():
@@ -735,7 +874,11 @@ def parse_y4m_header_wide(line, name, fps=None, what="file", matrix="bt601", ran
                 rate = int(num) / float(int(den or 1))
         elif key == "I":
             if val not in ("p", "?"):
-                raise ValueError(f"{name}: interlaced video ({tok}) is not supported")
+                if field_order is None or val not in ("t", "b", "m"):
+                    raise ValueError(f"{name}: interlaced video ({tok}) is not supported")
+                if val == "m" and field_order == "auto":
+                    raise ValueError(f"{name}: mixed interlacing ({tok}) names no field order: pass field_order \"tff\" or \"bff\"")
+                order = {"t": "tff", "b": "bff"}.get(val)
         elif key == "C":
             c_token = tok
         elif tok.startswith("XCOLORRANGE="):
@@ -752,17 +895,23 @@ def parse_y4m_header_wide(line, name, fps=None, what="file", matrix="bt601", ran
         rate = float(fps)
     if rate is None:
         raise ValueError(f"{name}: the YUV4MPEG2 header carries no frame rate (F0:0 or no F token): pass fps")
-    return width, height, rate, fmt
+    return width, height, rate, fmt, (field_order if field_order in FIELD_ORDERS else order)
 
 
 class Y4mSource(_Yuv420FileSource):
     """YUV4MPEG2 (.y4m) reader, memory-mapped, frames indexed once at open.  The header is parse_y4m_header's: 8-bit 4:2:0 limited range,
     Yuv420Frames.  wide=True: parse_y4m_header_wide's, with `range` and a matrix of YUV_FORMAT_MATRICES; the frames are YuvFrames of
-    self.fmt (10-bit, 4:2:2, 4:4:4, grey, full range ...)."""
+    self.fmt (10-bit, 4:2:2, 4:4:4, grey, full range ...).  deinterlace="adaptive" | "interpolate" (needs wide=True) accepts interlaced
+    headers as parse_y4m_header_fields reads them with `field_order`; the frames of woven fields are InterlacedYuvFrames, each with the
+    frame before it as its prev, read() and frames() deinterlace on the host."""
 
     layout = "i420"
 
-    def __init__(self, path, fps=None, matrix="bt601", wide=False, range="auto"):
+    def __init__(self, path, fps=None, matrix="bt601", wide=False, range="auto", deinterlace=None, field_order="auto", deinterlace_thresh=10):
+        self.deinterlace_thresh = _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
+        if deinterlace is not None and not wide:
+            raise ValueError(f"{path}: deinterlace={deinterlace!r} needs wide=True (the frames are YuvFrames)")
+        self.deinterlace = deinterlace
         if wide:
             YuvFormat(matrix=matrix)        # a bad matrix is refused before the file is opened
         else:
@@ -773,7 +922,8 @@ class Y4mSource(_Yuv420FileSource):
         end = mm.find(b"\n", 0, 4096) if size else -1
         line = mm[:end] if end >= 0 else None
         if wide:
-            self.width, self.height, self.fps, self.fmt = parse_y4m_header_wide(line, path, fps, matrix=matrix, range=range)
+            self.width, self.height, self.fps, self.fmt, self.field_order = parse_y4m_header_fields(
+                line, path, fps, "file", matrix, range, None if deinterlace is None else field_order)
         else:
             self.width, self.height, self.fps = parse_y4m_header(line, path, fps)
         nbytes = self._frame_bytes()
@@ -809,7 +959,14 @@ class Y4mStream:
 
     fmt = None                        # wide=True: the YuvFormat of the header; raw_frames() then yields YuvFrames (see Y4mSource)
 
-    def __init__(self, fileobj, fps=None, matrix="bt601", name="<stream>", wide=False, range="auto"):
+    deinterlace = field_order = None      # as Y4mSource's; the stream keeps the last frame's planes, the next frame's prev
+
+    def __init__(self, fileobj, fps=None, matrix="bt601", name="<stream>", wide=False, range="auto", deinterlace=None, field_order="auto",
+                 deinterlace_thresh=10):
+        self.deinterlace_thresh = _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
+        if deinterlace is not None and not wide:
+            raise ValueError(f"{name}: deinterlace={deinterlace!r} needs wide=True (the frames are YuvFrames)")
+        self.deinterlace = deinterlace
         if wide:
             YuvFormat(matrix=matrix)
         else:
@@ -820,7 +977,8 @@ class Y4mStream:
         self._started = False
         line = self._line(4096)
         if wide:
-            self.width, self.height, self.fps, self.fmt = parse_y4m_header_wide(line, name, fps, "stream", matrix, range)
+            self.width, self.height, self.fps, self.fmt, self.field_order = parse_y4m_header_fields(
+                line, name, fps, "stream", matrix, range, None if deinterlace is None else field_order)
         else:
             self.width, self.height, self.fps = parse_y4m_header(line, name, fps, what="stream")
         self.frame_count = None
@@ -859,6 +1017,7 @@ class Y4mStream:
         ch, cw = _chroma_size(h, w)
         nbytes, count = (h * w + 2 * ch * cw if self.fmt is None else self.fmt.frame_bytes(h, w)), 0
         head = memoryview(bytearray(6))
+        last = None
         while True:
             pos = self._pos
             got = self._fill(head)
@@ -874,6 +1033,11 @@ class Y4mStream:
             if self._fill(memoryview(buf)) < nbytes:
                 break                      # a truncated last frame is not a frame
             count += 1
+            if self.fmt is not None and self.field_order is not None:
+                planes = _planes_at(buf, 0, h, w, self.fmt)
+                yield InterlacedYuvFrame(planes, h, w, self.fmt, last, self.field_order, self.deinterlace, self.deinterlace_thresh)
+                last = planes
+                continue
             if self.fmt is not None:
                 yield YuvFrame(_planes_at(buf, 0, h, w, self.fmt), h, w, self.fmt)
                 continue
@@ -911,11 +1075,18 @@ class Yuv420Source(_Yuv420FileSource):
 
 class YuvSource(_Yuv420FileSource):
     """Yuv420Source for any YuvFormat: a headerless file of consecutive packed pictures of `fmt` (`ffmpeg -f rawvideo -pix_fmt NAME`, a
-    hardware decoder's P010 surfaces), memory-mapped; read_raw / raw_frames hand out YuvFrames.  A partial last frame is dropped."""
+    hardware decoder's P010 surfaces), memory-mapped; read_raw / raw_frames hand out YuvFrames.  A partial last frame is dropped.
+    deinterlace="adaptive" | "interpolate": the pictures are woven fields and the frames InterlacedYuvFrames; a headerless file names no
+    field order, so field_order must be "tff" or "bff"."""
 
-    def __init__(self, path, width, height, fps, fmt):
+    def __init__(self, path, width, height, fps, fmt, deinterlace=None, field_order="auto", deinterlace_thresh=10):
         if not isinstance(fmt, YuvFormat):
             raise ValueError(f"fmt must be a YuvFormat, not {fmt!r}")
+        self.deinterlace_thresh = _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
+        if deinterlace is not None:
+            if field_order == "auto":
+                raise ValueError(f"{path}: a headerless YUV file names no field order: pass field_order \"tff\" or \"bff\"")
+            self.deinterlace, self.field_order = deinterlace, field_order
         self.fmt, self.matrix = fmt, fmt.matrix
         self.width, self.height, self.fps = int(width), int(height), float(fps)
         if self.width < 1 or self.height < 1:
@@ -930,24 +1101,31 @@ _RAW_YUV_EXT = {".yuv": "i420", ".i420": "i420", ".nv12": "nv12"}
 _RAW_PIX_FMT_EXT = {".p010": "p010le"}
 
 
-def open_source(path, fps=None, size=None, layout=None, matrix="bt601", wide=False, range="auto", pix_fmt=None):
+def open_source(path, fps=None, size=None, layout=None, matrix="bt601", wide=False, range="auto", pix_fmt=None, deinterlace=None,
+                field_order="auto", deinterlace_thresh=10):
     """The source of a file by its extension: .npy (needs fps), .y4m, .yuv / .i420 / .nv12 (headerless: need size=(width, height) and
     fps; `layout` overrides the extension's), anything else an AVI; "-" is a Y4mStream over standard input.  `matrix` goes to the
     YUV sources.  wide=True lets the Y4M readers accept what parse_y4m_header_wide does, with `range` ("auto": the header's).  pix_fmt
     (a name of YuvFormat.from_pix_fmt; .p010 implies p010le) reads a headerless file of that format through YuvSource, with `range`
-    ("auto": the name's own) and any matrix of YUV_FORMAT_MATRICES; it needs size and fps."""
+    ("auto": the name's own) and any matrix of YUV_FORMAT_MATRICES; it needs size and fps.  deinterlace ("adaptive" | "interpolate"),
+    field_order and deinterlace_thresh go to the Y4M readers (with wide=True) and to YuvSource (with pix_fmt and a field order); no other
+    source takes them."""
     if range not in YUV_RANGES:
         raise ValueError(f"range must be one of {YUV_RANGES}, not {range!r}")
+    _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
+    fields = {} if deinterlace is None else dict(deinterlace=deinterlace, field_order=field_order, deinterlace_thresh=deinterlace_thresh)
     if str(path) == "-":
         import sys
-        return Y4mStream(sys.stdin.buffer, fps, matrix, name="<stdin>", wide=wide, range=range)
+        return Y4mStream(sys.stdin.buffer, fps, matrix, name="<stdin>", wide=wide, range=range, **fields)
     ext = os.path.splitext(str(path))[1].lower()
+    if fields and ext != ".y4m" and pix_fmt is None and (layout is not None or ext not in _RAW_PIX_FMT_EXT):
+        raise ValueError(f"{path}: deinterlace={deinterlace!r} reads YUV4MPEG2 (with wide=True) or a headerless YUV file named by pix_fmt")
     if str(path).endswith(".npy"):
         if fps is None:
             raise ValueError("a .npy frame stack carries no frame rate: pass fps")
         return NpySource(path, fps)
     if ext == ".y4m":
-        return Y4mSource(path, fps, matrix, wide=wide, range=range)
+        return Y4mSource(path, fps, matrix, wide=wide, range=range, **fields)
     if pix_fmt is None and layout is None:
         pix_fmt = _RAW_PIX_FMT_EXT.get(ext)
     if pix_fmt is not None or ext in _RAW_YUV_EXT:
@@ -958,6 +1136,6 @@ def open_source(path, fps=None, size=None, layout=None, matrix="bt601", wide=Fal
         if pix_fmt is not None:
             if layout is not None:
                 raise ValueError(f"{path}: pix_fmt {pix_fmt!r} names the plane layout; layout {layout!r} was given as well")
-            return YuvSource(path, size[0], size[1], fps, YuvFormat.from_pix_fmt(pix_fmt, matrix, range))
+            return YuvSource(path, size[0], size[1], fps, YuvFormat.from_pix_fmt(pix_fmt, matrix, range), **fields)
         return Yuv420Source(path, size[0], size[1], fps, layout or _RAW_YUV_EXT[ext], matrix)
     return AviBgr24Source(path)

@@ -17,7 +17,9 @@ Frames that are still YUV 4:2:0 (ingest.Yuv420Frame, from a source's read_raw / 
 bytes per pixel, half the slab copy and half the PCIe bytes of a BGR frame — and converted to BGR by one kernel on the copy stream
 (vse_yuv420_to_bgr, or vse_yuv_to_bgr_matrix for frames that say matrix="bt709"), so a consumer sees the same uint8 [n,H,W,3] tensor
 either way.  Frames of any other format (ingest.YuvFrame: 10-bit, 4:2:2, 4:4:4, grey, full range, P010) go the same way through
-vse_yuv_to_bgr_format, keyed by shape, format and row parity.
+vse_yuv_to_bgr_format, keyed by shape, format and row parity.  Interlaced pictures (ingest.InterlacedYuvFrame) are uploaded as they are,
+each beside its previous picture unless that is the frame before it in the batch, deinterlaced on the device (vse_yuv_deinterlace) and
+converted by the same call as the others.
 """
 import queue
 import threading
@@ -66,6 +68,8 @@ class Uploader:
     def stage(self, frames):
         """list of equal-shaped uint8 frames (views are fine) -> StagedBatch"""
         import torch
+        if hasattr(frames[0], "deinterlaced_planes"):
+            return self._stage_interlaced(frames)
         if hasattr(frames[0], "fmt"):
             return self._stage_yuv(frames)
         if hasattr(frames[0], "pack_into"):
@@ -142,6 +146,68 @@ class Uploader:
             packed = torch.empty((n, per), dtype=torch.uint8, device=self.device)          # (dropped here: see _stage_yuv420)
             packed.copy_(host, non_blocking=True)
             dev = ctx.yuv_to_bgr(packed, n, h, w, first.fmt, first.row_parity)
+            ev = torch.cuda.Event()
+            ev.record(self._stream)
+        self._busy[k] = ev
+        return StagedBatch(dev, ev)
+
+    def _stage_interlaced(self, frames):
+        """ingest.InterlacedYuvFrames of one shape, format, first row, field order, mode and threshold -> StagedBatch of the BGR conversion
+        of their deinterlaced rows.  Each frame's band() (the rows asked for, widened so that every plane starts on a top-field row and the
+        band's edge rows are none of those asked for) is packed into one slot of the slab; a frame whose prev is the planes of the frame
+        before it in the batch takes that frame's slot as its previous picture, any other frame with a prev packs it into the slot in
+        front of its own.  One copy; then one vse_yuv_deinterlace per run of frames whose slots are laid out alike (frames without prev:
+        NULL; chained frames: the slot before, stride of one slot; frames with their prev beside them: stride of two), one
+        vse_yuv_to_bgr_format over all the progressive bands, and the rows asked for cut out of it."""
+        import torch
+        first = frames[0]
+
+        def key_of(f):
+            return (tuple(f.shape), getattr(f, "fmt", None), getattr(f, "y0", None), getattr(f, "height", None), getattr(f, "field_order", None),
+                    getattr(f, "mode", None), getattr(f, "thresh", None))
+        key = key_of(first)
+        for f in frames:
+            if not hasattr(f, "deinterlaced_planes") or key_of(f) != key:
+                raise ValueError("Uploader.stage: the interlaced YUV frames of a batch must share shape, format, first row, picture height, "
+                                 f"field order, mode and threshold: {key} and {key_of(f)}")
+        from .ingest import _same_planes
+        ctx = self._context()
+        n, w = len(frames), first.width
+        a, b = first.band()
+        per = (first.band_bytes + 15) & ~15
+        # runs: [kind, index of the first frame, slot of its picture, frames]; kind 0 no prev, 1 the slot before (stride 1), 2 pairs (stride 2)
+        runs, jobs, slot = [], [], 0
+        for i, f in enumerate(frames):
+            if f.prev is None or f.mode == "interpolate":
+                kind = 0
+            elif i > 0 and _same_planes(f.prev, frames[i - 1].planes):
+                kind = 1
+            else:
+                kind = 2
+                jobs.append((slot, f, True))
+                slot += 1
+            if runs and runs[-1][0] == kind:
+                runs[-1][3] += 1
+            else:
+                runs.append([kind, i, slot, 1])
+            jobs.append((slot, f, False))
+            slot += 1
+        k, slab = self._slab(per * slot)
+        host = slab[:per * slot].view(slot, per)
+        dst = host.numpy()
+        list(self._pool.map(lambda j: j[1].pack_band_into(dst[j[0]], prev=j[2]), jobs))
+        with torch.cuda.stream(self._stream):
+            packed = torch.empty((slot, per), dtype=torch.uint8, device=self.device)        # (dropped here, like prog: see _stage_yuv420)
+            packed.copy_(host, non_blocking=True)
+            prog = torch.empty((n, per), dtype=torch.uint8, device=self.device)
+            for kind, i, at, count in runs:
+                step = 2 if kind == 2 else 1
+                cur = packed[at:].as_strided((count, per), (step * per, 1))
+                ctx.yuv_deinterlace(cur, count, b - a, w, first.fmt, prev=None if kind == 0 else packed[at - 1], prev_stride=step * per,
+                                    keep=first.keep, mode=first.mode, thresh=first.thresh, out=prog[i:i + count])
+            dev = ctx.yuv_to_bgr(prog, n, b - a, w, first.fmt, 0)
+            if (first.y0 - a, first.y1 - a) != (0, b - a):
+                dev = dev[:, first.y0 - a:first.y1 - a].contiguous()
             ev = torch.cuda.Event()
             ev.record(self._stream)
         self._busy[k] = ev

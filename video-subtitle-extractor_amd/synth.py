@@ -161,6 +161,25 @@ def make_moving_clip(schedule, height=120, width=320, pan=(2, 3), amp=(110, 60),
     return frames, truth
 
 
+def interlace_yuv420(field_rate_bgr, field_order="tff"):
+    """Pictures rendered at field rate (uint8 BGR [2 n, H, W, 3]; an odd last one is dropped) -> n interlaced 4:2:0 frames as (Y, U, V)
+    plane triples: each picture goes through ingest.bgr_to_yuv420 on its own, then the rows of every plane are woven: of frame k's two
+    pictures the earlier one gives the rows of the field that comes first (the even rows for "tff", the odd ones for "bff"), the later
+    one the others.  Chroma rows alternate between the fields as luma rows do, which is how interlaced 4:2:0 is stored."""
+    from .ingest import FIELD_ORDERS, bgr_to_yuv420
+    keep = FIELD_ORDERS.index(field_order)
+    out = []
+    for k in range(len(field_rate_bgr) // 2):
+        first, second = bgr_to_yuv420(field_rate_bgr[2 * k]), bgr_to_yuv420(field_rate_bgr[2 * k + 1])
+        woven = []
+        for a, b in zip(first, second):
+            p = np.array(b, copy=True)
+            p[keep::2] = a[keep::2]
+            woven.append(p)
+        out.append(tuple(woven))
+    return out
+
+
 def make_scenes(scenes, height=360, width=640, seed=0):
     """A clip of camera shots for the scene-cut finder: uint8 BGR [n,height,width,3] + the 0-based number of each scene's first frame.
 
