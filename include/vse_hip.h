@@ -709,7 +709,8 @@ int vse_yuv_to_bgr_matrix(vse_ctx* ctx, const void* d_yuv, int n, int h, int w, 
  * bit), limited BT.2020 1220542; 2245811, -196426, -682019, 1760217 (BT.709's derivation with Kr = 0.2627, Kb = 0.0593); full range
  * round(k 2^20) of 2 (1 - Kb), -2 Kb (1 - Kb) / Kg, -2 Kr (1 - Kr) / Kg, 2 (1 - Kr), without 255/224: BT.601 1858077, -360853, -748826,
  * 1470104; BT.709 1945738, -196424, -490864, 1651297; BT.2020 1972791, -172546, -599107, 1546230.
- * NO transfer function is applied: PQ / HLG material comes out flat (dim, low contrast); its text and edges remain.
+ * NO transfer function is applied here: PQ / HLG material comes out flat (dim, low contrast); its text and edges remain.
+ * vse_yuv_to_bgr_tonemap below is the conversion for such material.
  * A packed (sub-)frame of luma rows [y0, y1): h = y1 - y0 rows of w samples, then chroma rows y0 >> sub_y .. ((y1 - 1) >> sub_y) + 1,
  * that is ch = ((h - 1 + row_parity) >> sub_y) + 1 rows of cw = (w + sub_x) >> sub_x samples per plane (planar: U plane, V plane;
  * semi-planar: one plane of rows of 2 cw samples), row_parity = y0 & sub_y.  For 8-bit 4:2:0 this is vse_yuv420_to_bgr's.
@@ -726,6 +727,36 @@ size_t vse_yuv_frame_bytes(int h, int w, int sub_x, int sub_y, int chroma, int d
 int vse_yuv_to_bgr_format(vse_ctx* ctx, const void* d_yuv, int n, int h, int w, int sub_x, int sub_y, int chroma, int depth, int msb,
                           int matrix, int full_range, int row_parity, int64_t yuv_frame_stride, void* d_bgr, int64_t pitch,
                           int64_t bgr_frame_stride, void* stream);
+
+/* ---- frame ingest: HDR (PQ / HLG) YUV -> SDR BGR ----------------------------------------------------------------------------------- */
+/* UHD Blu-ray and streaming masters are PQ (SMPTE ST 2084), UHD broadcast is HLG (BT.2100), both normally 10-bit BT.2020: converted by
+ * vse_yuv_to_bgr_format they come out flat and desaturated.  This is that conversion with a transfer function, a tone curve and a gamut
+ * change behind it, all of them DATA: the device applies two tables and nine integers that the host builds (vse_amd.ingest.ToneMap) and
+ * knows nothing of PQ, HLG or curves, so its bytes are defined by exact integers like every other conversion here.
+ * The format table, shift, 2^depth - 1, the offsets, KY_s .. RV_s, the chroma sampling (nearest), row_parity and the packed layout are
+ * vse_yuv_to_bgr_format's.  All arithmetic int32, >> arithmetic, clip(lo, hi, x) = min(max(x, lo), hi):
+ *   u = U - (128 << s), v = V - (128 << s)  (grey: u = v = 0);   c = max(Y - yoff, 0) * KY_s + 2^15
+ *   E_B = clip(0, 4095, (c + BU_s u) >> 16), E_G = clip(0, 4095, (c + GU_s u + GV_s v) >> 16), E_R = clip(0, 4095, (c + RV_s v) >> 16)
+ *                                                 the R'G'B' code at 12 bits: vse_yuv_to_bgr_format's sums, nominal peak 4080 = 255 << 4
+ *   L_k = A[E_k]                                  A: uint16[4096], linear light behind the tone curve, 65535 = SDR white
+ *   P_r = clip(0, 65535, (M[r][0] L_R + M[r][1] L_G + M[r][2] L_B + 2^13) >> 14)       r = R, G, B;  M: int32[3][3], Q14, linear light
+ *   out_r = T[P_r < 4096 ? P_r : 3840 + (P_r >> 4)]
+ *                                                 T: uint8[7936], the output gamma: every P below 4096 (its steep foot), every 16th above
+ * and the bytes are stored B, G, R.  The positive entries of each row of M sum to at most 32767 and the negative ones to at least -32768:
+ * then every partial sum lies within [-32768 * 65535, 32767 * 65535 + 2^13] and int32 is exact.
+ * vse_yuv_tonemap_table_bytes: 4096 * 2 + 7936 = 16128, the table as the device takes it: A (little-endian uint16), then T. */
+size_t vse_yuv_tonemap_table_bytes(void);
+/* vse_yuv_to_bgr_format with the arithmetic above: one launch on `stream`, no allocation, no device sync, exactly the w * 3 bytes of each
+ * row written.  d_table: the 16128 bytes on the device, 16-byte aligned, read by the launch (keep them until it has run); gamut: M, nine
+ * integers on the host, row-major, rows R G B over columns R G B, read before the call returns.  Every block copies the table into LDS
+ * once and gathers from there.  2-byte 4:2:0, planar or semi-planar, takes the 16-byte load / store kernel under vse_yuv420_to_bgr's
+ * conditions, everything else (8-bit 4:2:0 included) the kernel without conditions.
+ * Returns VSE_E_INVAL, with the values in vse_last_error, and launches nothing, for everything vse_yuv_to_bgr_format refuses, a NULL
+ * d_table or one that is not 16-byte aligned, a NULL gamut, and a gamut row outside the bounds above. */
+int vse_yuv_to_bgr_tonemap(vse_ctx* ctx, const void* d_yuv, int n, int h, int w, int sub_x, int sub_y, int chroma, int depth, int msb,
+                           int matrix, int full_range, int row_parity, int64_t yuv_frame_stride, void* d_bgr, int64_t pitch,
+                           int64_t bgr_frame_stride, const void* d_table /* device, 16-byte aligned */,
+                           const int32_t* gamut /* host, 9 integers, row-major, rows R G B over columns R G B */, void* stream);
 
 /* ---- frame ingest: interlaced YUV -> progressive YUV ------------------------------------------------------------------------------ */
 /* DVDs, 576i / 480i captures and 1080i broadcasts carry two fields of different times woven into one picture.  This turns n packed

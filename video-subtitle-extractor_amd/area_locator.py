@@ -337,6 +337,12 @@ def main(argv=None, cells_fn=None):
     p.add_argument("--range", default="auto", choices=("auto", "limited", "full"), help="--wide-yuv / --pix-fmt: the colour range [auto]")
     p.add_argument("--pix-fmt", default=None, metavar="NAME", help="pixel format of a headerless YUV file by FFmpeg's name (yuv420p10le, "
                    "p010le ...) [by extension]")
+    p.add_argument("--transfer", default=None, choices=("pq", "hlg"), help="HDR video (needs --wide-yuv or --pix-fmt): undo PQ or HLG and "
+                   "tone-map to SDR on the GPU [none]")
+    p.add_argument("--white-nits", type=float, default=None, metavar="N", help="--transfer: the luminance that becomes SDR white [203]")
+    p.add_argument("--peak-nits", type=float, default=None, metavar="N", help="--transfer: the luminance the roll-off brings down to SDR "
+                   "white [1000]")
+    p.add_argument("--tone-curve", default=None, choices=("knee", "clip"), help="--transfer: roll highlights off, or clip at SDR white [knee]")
     p.add_argument("--probe", type=int, nargs=2, default=None, metavar=("START", "COUNT"),
                    help="scan COUNT frames from the 1-based frame number START on [the whole clip]")
     p.add_argument("--edge-thresh", default=str(DEFAULT_EDGE_THRESH), metavar="auto|N", help="luma gradient that makes an edge pixel, or "
@@ -363,8 +369,9 @@ def main(argv=None, cells_fn=None):
             if not (sep and w.isdigit() and h.isdigit()):
                 raise ValueError(f"--size takes WIDTHxHEIGHT, not {args.size!r}")
             size = (int(w), int(h))
+        from .extractor import tone_arguments
         source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout, matrix=args.matrix, wide=args.wide_yuv,
-                                    range=args.range, pix_fmt=args.pix_fmt)
+                                    range=args.range, pix_fmt=args.pix_fmt, **tone_arguments(args))
         loc = AreaLocator(cells_fn, probe=args.probe, edge_thresh=parse_edge_thresh(args.edge_thresh), automaton=args.locator_automaton,
                           hold_seconds=args.hold_seconds, hold_frames=args.hold_frames, max_hold_seconds=args.max_hold_seconds,
                           max_hold_frames=args.max_hold_frames)

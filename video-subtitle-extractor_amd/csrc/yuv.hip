@@ -37,6 +37,10 @@
 //   general  any format: a lane owns 4 pixels of one row; 2-byte formats need 2-byte aligned bases and strides.
 // 8-bit 4:2:0 limited BT.601 / BT.709 goes to the two 8-bit kernels above and gives their bytes.
 //
+// vse_yuv_to_bgr_tonemap (include/vse_hip.h) is the same two kernels with another end (ToneOut below in place of PlainOut): the sums are
+// shifted by 16 to 12-bit codes, which go through a linearising / tone-mapping table, a 3 x 3 gamut matrix and an output gamma table
+// (tests/tonemap_ref.py restates the integers).  The tables are staged into LDS once per block, so its launches cap the grid (TONE_MAX_BLOCKS).
+//
 // vse_yuv_deinterlace (include/vse_hip.h) stands in front of all of them for interlaced pictures: packed pictures of any format above
 // become progressive pictures of the same format, which the conversions then take unchanged.  Motion-adaptive, per plane (Y, U, V or the
 // interleaved UV plane, the samples as stored words), up and down a column only; tests/deinterlace_ref.py restates it in int64:
@@ -216,31 +220,94 @@ __device__ __forceinline__ int sample_of(unsigned word, const YuvParams& p) { re
 
 __device__ __forceinline__ int luma_term(int Y, const YuvParams& p) { return __mul24(max(Y - p.yoff, 0), p.ky); }
 
-__device__ __forceinline__ ChromaTerms chroma_terms(int U, int V, const YuvParams& p) {
+// `half` is the rounding constant of the shift that follows: 2^19 in front of >> 20, 2^15 in front of the tone-mapped route's >> 16
+__device__ __forceinline__ ChromaTerms chroma_terms(int U, int V, const YuvParams& p, int half = 1 << 19) {
     const int u = U - p.coff, v = V - p.coff;
     ChromaTerms t;
-    t.b = __mul24(u, p.bu) + (1 << 19);
-    t.g = __mul24(u, p.gu) + __mul24(v, p.gv) + (1 << 19);
-    t.r = __mul24(v, p.rv) + (1 << 19);
+    t.b = __mul24(u, p.bu) + half;
+    t.g = __mul24(u, p.gu) + __mul24(v, p.gv) + half;
+    t.r = __mul24(v, p.rv) + half;
     return t;
 }
 
+// What becomes of a pixel's three sums (luma term + chroma term, rounding constant included) is a policy of the two kernels below.
+// PlainOut: the bytes of vse_yuv_to_bgr_format.
+struct PlainOut {
+    struct Args {};
+    static constexpr bool TONE = false;
+    static constexpr int HALF = 1 << 19;
+    static __device__ __forceinline__ PlainOut begin(const Args&, int, int) { return PlainOut(); }
+    __device__ __forceinline__ void operator()(int c, const ChromaTerms& t, unsigned& b, unsigned& g, unsigned& r) const {
+        b = clip8(c + t.b);
+        g = clip8(c + t.g);
+        r = clip8(c + t.r);
+    }
+};
+
+// ToneOut: vse_yuv_to_bgr_tonemap.  The sums shifted by 16 are 12-bit codes E; L = A[E] is linear light, P = clip16((M L + 2^13) >> 14) the
+// gamut-mapped light, T[P < 4096 ? P : 3840 + (P >> 4)] the byte.  The kernel knows two tables and nine integers, nothing of PQ or HLG.
+// int32: a row of M has positive entries that sum to at most 32767 and negative ones that sum to at least -32768 (checked on the host)
+// and L <= 65535, so every partial sum lies in [-32768 * 65535, 32767 * 65535 + 2^13], inside int32; |M| <= 2^15 and L < 2^16 fit 24
+// signed bits, so the products are the 24-bit multiplies.  Both clips are made before their shift, as clip8's is.
+// The tables live in LDS, A then T as the host stores them (uint16[4096], uint8[7936]: 16 128 bytes): six gathers per pixel with
+// data-dependent addresses.  They are left packed: a bank is a dword, so neighbouring codes (2 of A, 4 of T) share one, and lanes of a
+// wave hold neighbouring pixels, whose codes in real pictures are close: equal dwords are one broadcast, near ones fall into
+// different banks.  Widening A to a dword per entry would spread the same codes over 32 banks no better and double the staging.
+constexpr int TONE_A = 4096, TONE_T = 7936, TONE_BYTES = 2 * TONE_A + TONE_T, TONE_VECS = TONE_BYTES / 16;
+static_assert(TONE_BYTES % 16 == 0, "the table is staged by 16-byte loads");
+
+struct ToneOut {
+    struct Args {
+        const uint4* table;      // device, 16-byte aligned: A then T
+        int m[9];                // rows R, G, B over columns R, G, B, Q14
+    };
+    static constexpr bool TONE = true;
+    static constexpr int HALF = 1 << 15;
+    const uint16_t* A;
+    const uint8_t* T;
+    int m[9];
+
+    // every thread of the block calls this once, before anything else: the block's copy of the table
+    static __device__ __forceinline__ ToneOut begin(const Args& a, int tid, int threads) {
+        __shared__ uint4 lds[TONE_VECS];
+        for (int i = tid; i < TONE_VECS; i += threads) lds[i] = a.table[i];
+        __syncthreads();
+        ToneOut o;
+        o.A = reinterpret_cast<const uint16_t*>(lds);
+        o.T = reinterpret_cast<const uint8_t*>(lds) + 2 * TONE_A;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) o.m[k] = a.m[k];
+        return o;
+    }
+    __device__ __forceinline__ int light(int sum) const { return A[min(max(sum, 0), (4095 << 16) | 0xffff) >> 16]; }
+    __device__ __forceinline__ unsigned byte_of(const int* row, int lr, int lg, int lb) const {
+        const int s = __mul24(row[0], lr) + __mul24(row[1], lg) + __mul24(row[2], lb) + (1 << 13);
+        const int p = min(max(s, 0), (65535 << 14) | 0x3fff) >> 14;
+        return T[p < 4096 ? p : 3840 + (p >> 4)];
+    }
+    __device__ __forceinline__ void operator()(int c, const ChromaTerms& t, unsigned& b, unsigned& g, unsigned& r) const {
+        const int lb = light(c + t.b), lg = light(c + t.g), lr = light(c + t.r);
+        r = byte_of(m, lr, lg, lb);
+        g = byte_of(m + 3, lr, lg, lb);
+        b = byte_of(m + 6, lr, lg, lb);
+    }
+};
+
 // 4 pixels (luma terms c, chroma terms t) -> 12 bytes B G R B G R ...
-__device__ __forceinline__ void pack4(const int (&c)[4], const ChromaTerms (&t)[4], unsigned& d0, unsigned& d1, unsigned& d2) {
+template <class OUT>
+__device__ __forceinline__ void pack4(const int (&c)[4], const ChromaTerms (&t)[4], const OUT& out, unsigned& d0, unsigned& d1, unsigned& d2) {
     unsigned b[4], g[4], r[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        b[k] = clip8(c[k] + t[k].b);
-        g[k] = clip8(c[k] + t[k].g);
-        r[k] = clip8(c[k] + t[k].r);
-    }
+    for (int k = 0; k < 4; ++k) out(c[k], t[k], b[k], g[k], r[k]);
     d0 = b[0] | (g[0] << 8) | (r[0] << 16) | (b[1] << 24);
     d1 = g[1] | (r[1] << 8) | (b[2] << 16) | (g[2] << 24);
     d2 = r[2] | (b[3] << 8) | (g[3] << 16) | (r[3] << 24);
 }
 
 // 16 pixels of one row of 2-byte samples (ya: pixels 0-7, yb: pixels 8-15; t[k]: pixels 2 k, 2 k + 1) -> 48 bytes as three 16-byte stores
-__device__ __forceinline__ void row16_wide(const uint4& ya, const uint4& yb, const ChromaTerms (&t)[8], const YuvParams& p, uint8_t* dst) {
+template <class OUT>
+__device__ __forceinline__ void row16_wide(const uint4& ya, const uint4& yb, const ChromaTerms (&t)[8], const YuvParams& p, const OUT& out,
+                                           uint8_t* dst) {
     const unsigned yw[8] = {ya.x, ya.y, ya.z, ya.w, yb.x, yb.y, yb.z, yb.w};
     unsigned o[12];
 #pragma unroll
@@ -248,7 +315,7 @@ __device__ __forceinline__ void row16_wide(const uint4& ya, const uint4& yb, con
         const int c[4] = {luma_term(sample_of(yw[2 * q] & 0xffffu, p), p), luma_term(sample_of(yw[2 * q] >> 16, p), p),
                           luma_term(sample_of(yw[2 * q + 1] & 0xffffu, p), p), luma_term(sample_of(yw[2 * q + 1] >> 16, p), p)};
         const ChromaTerms tq[4] = {t[2 * q], t[2 * q], t[2 * q + 1], t[2 * q + 1]};
-        pack4(c, tq, o[3 * q], o[3 * q + 1], o[3 * q + 2]);
+        pack4(c, tq, out, o[3 * q], o[3 * q + 1], o[3 * q + 2]);
     }
     uint4* d = reinterpret_cast<uint4*>(dst);
     d[0] = make_uint4(o[0], o[1], o[2], o[3]);
@@ -257,9 +324,12 @@ __device__ __forceinline__ void row16_wide(const uint4& ya, const uint4& yb, con
 }
 
 // yuv420_fast_kernel for 2-byte samples: the same work items and strides; sstride, the planes and the rows are counted in bytes.
-template <int CHROMA>
+// With ToneOut the launcher caps the grid, so that a block stages the table once and then walks several items and frames.
+template <int CHROMA, class OUT>
 __global__ __launch_bounds__(FAST_THREADS) void yuv420_wide_fast_kernel(const uint8_t* __restrict__ src, int n, int h, int w, long sstride,
-                                                                        uint8_t* __restrict__ dst, long pitch, long dstride, YuvParams p) {
+                                                                        uint8_t* __restrict__ dst, long pitch, long dstride, YuvParams p,
+                                                                        typename OUT::Args oa) {
+    const OUT out = OUT::begin(oa, threadIdx.x, FAST_THREADS);
     const unsigned cgs = (unsigned)w >> 4, items = ((unsigned)h >> 1) * cgs;
     const long lrow = 2L * w, plane = (long)h * lrow;              // bytes of a luma row (= of a semi-planar chroma row) and of the luma plane
     for (int f = blockIdx.y; f < n; f += gridDim.y) {
@@ -278,27 +348,29 @@ __global__ __launch_bounds__(FAST_THREADS) void yuv420_wide_fast_kernel(const ui
                 const unsigned uw[4] = {u.x, u.y, u.z, u.w}, vw[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
                 for (int k = 0; k < 8; ++k)
-                    t[k] = chroma_terms(sample_of((uw[k >> 1] >> (16 * (k & 1))) & 0xffffu, p), sample_of((vw[k >> 1] >> (16 * (k & 1))) & 0xffffu, p), p);
+                    t[k] = chroma_terms(sample_of((uw[k >> 1] >> (16 * (k & 1))) & 0xffffu, p), sample_of((vw[k >> 1] >> (16 * (k & 1))) & 0xffffu, p), p,
+                                         OUT::HALF);
             } else {
                 const uint8_t* cp = s + plane + (long)rp * lrow + 32 * cg;
                 const uint4 a = *reinterpret_cast<const uint4*>(cp), b = *reinterpret_cast<const uint4*>(cp + 16);
                 const unsigned q[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
 #pragma unroll
-                for (int k = 0; k < 8; ++k) t[k] = chroma_terms(sample_of(q[k] & 0xffffu, p), sample_of(q[k] >> 16, p), p);
+                for (int k = 0; k < 8; ++k) t[k] = chroma_terms(sample_of(q[k] & 0xffffu, p), sample_of(q[k] >> 16, p), p, OUT::HALF);
             }
             uint8_t* o = d + (long)(2 * rp) * pitch + 48 * cg;
-            row16_wide(y0a, y0b, t, p, o);
-            row16_wide(y1a, y1b, t, p, o + pitch);
+            row16_wide(y0a, y0b, t, p, out, o);
+            row16_wide(y1a, y1b, t, p, out, o + pitch);
         }
     }
 }
 
 // yuv420_general_kernel for any format: S is the sample type, the planes are counted in samples.  Chroma column (x + k) >> sub_x, chroma
 // row (r + parity) >> sub_y; with sub_x = 1 pixels 0-1 and 2-3 share their terms (x is a multiple of 4).
-template <typename S, int CHROMA>
+template <typename S, int CHROMA, class OUT>
 __global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void yuv_general_kernel(const S* __restrict__ src, int n, int h, int w, int sub_x, int sub_y,
                                                                            int parity, long sstride, uint8_t* __restrict__ dst, long pitch,
-                                                                           long dstride, YuvParams p) {
+                                                                           long dstride, YuvParams p, typename OUT::Args oa) {
+    const OUT out = OUT::begin(oa, (int)(threadIdx.y * GEN_LANES + threadIdx.x), GEN_LANES * GEN_ROWS);      // (before any lane leaves)
     const int x = 4 * (int)(blockIdx.x * GEN_LANES + threadIdx.x);
     if (x >= w) return;
     const int npx = min(4, w - x);
@@ -326,7 +398,7 @@ __global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void yuv_general_kernel(const
             }
             ChromaTerms t[4];
             if (CHROMA == CHROMA_NONE) {
-                t[0] = t[1] = t[2] = t[3] = chroma_terms(p.coff, p.coff, p);
+                t[0] = t[1] = t[2] = t[3] = chroma_terms(p.coff, p.coff, p, OUT::HALF);
             } else {
                 const long cr = (r + parity) >> sub_y;
                 const S* up = s + plane + cr * cw * (CHROMA == CHROMA_SEMI ? 2 : 1);
@@ -334,7 +406,7 @@ __global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void yuv_general_kernel(const
                 const int cs = CHROMA == CHROMA_SEMI ? 2 : 1;
                 const auto terms_of = [&](int k) {
                     const int cx = (min(x + k, w - 1) >> sub_x) * cs;      // (a pixel past the row's end takes the last sample: it is not stored)
-                    return chroma_terms(sample_of(up[cx], p), sample_of(up[cx + vo], p), p);
+                    return chroma_terms(sample_of(up[cx], p), sample_of(up[cx + vo], p), p, OUT::HALF);
                 };
                 t[0] = terms_of(0);
                 t[2] = terms_of(2);
@@ -347,7 +419,7 @@ __global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void yuv_general_kernel(const
                 }
             }
             unsigned o[3];
-            pack4(c, t, o[0], o[1], o[2]);
+            pack4(c, t, out, o[0], o[1], o[2]);
             uint8_t* op = d + (long)r * pitch + 3 * (long)x;
             if (npx == 4 && (reinterpret_cast<uintptr_t>(op) & 3) == 0) {
                 unsigned* o4 = reinterpret_cast<unsigned*>(op);
@@ -381,6 +453,75 @@ bool format_ok(int sub_x, int sub_y, int chroma, int depth) {
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+YuvParams yuv_params(int depth, int msb, int matrix, int full_range) {
+    const int s = depth - 8;
+    const int* k0 = YUV_K0[full_range][matrix];
+    YuvParams p;
+    p.shift = msb ? 16 - depth : 0;
+    p.maxv = (1 << depth) - 1;
+    p.yoff = full_range ? 0 : 16 << s;
+    p.coff = 128 << s;
+    p.ky = scaled_factor(k0[0], s);
+    p.bu = scaled_factor(k0[1], s);
+    p.gu = scaled_factor(k0[2], s);
+    p.gv = scaled_factor(k0[3], s);
+    p.rv = scaled_factor(k0[4], s);
+    return p;
+}
+
+// what vse_yuv_to_bgr_format and vse_yuv_to_bgr_tonemap both refuse; frame = vse_yuv_frame_bytes of the call
+bool format_call_ok(const vse_ctx* c, const void* d_yuv, int n, int h, int w, int depth, int msb, int matrix, int full_range, size_t frame,
+                    int64_t yuv_frame_stride, const void* d_bgr, int64_t pitch, int64_t bgr_frame_stride) {
+    const int ss = depth > 8 ? 2 : 1;
+    return c && d_yuv && d_bgr && n >= 1 && frame && msb >= 0 && msb <= (ss == 2 ? 1 : 0) && matrix >= 0 && matrix <= 2 && full_range >= 0 &&
+           full_range <= 1 && pitch >= (int64_t)w * 3 && yuv_frame_stride >= (int64_t)frame &&
+           bgr_frame_stride >= (int64_t)(h - 1) * pitch + (int64_t)w * 3 &&
+           !(ss == 2 && ((reinterpret_cast<uintptr_t>(d_yuv) & 1) || (yuv_frame_stride & 1)));
+}
+
+// Blocks of a tone-mapped launch: each stages the 16 128-byte table before its first pixel, so the grid is capped and blocks stride the
+// work.  Measured on 64 x 1080p / 16 x 2160p P010 (us per frame, 16-byte kernel; general kernel): 512 4.5 / 17.7; 12.4 / 43.5, 1024 3.9 /
+// 15.6; 8.6 / 29.5, 4096 3.4 / 14.1; 6.7 / 21.3, 8192 3.4 / 13.7; 5.6 / 20.8, 16384 3.4 / 13.7; 5.5 / 21.1: the copies cost less than idle
+// CUs do, and past 8192 nothing is gained.
+constexpr int TONE_MAX_BLOCKS = 8192;
+
+// The launch of an accepted call.  PlainOut: one block per 256 work items, as ever.  ToneOut: at most about TONE_MAX_BLOCKS blocks in all,
+// which stride the items, rows and frames.
+template <class OUT>
+void launch_format(const uint8_t* src, int n, int h, int w, int sub_x, int sub_y, int chroma, int ss, int row_parity, int64_t yuv_frame_stride,
+                   uint8_t* dst, int64_t pitch, int64_t bgr_frame_stride, const YuvParams& p, const typename OUT::Args& oa, hipStream_t st) {
+    constexpr bool tone = OUT::TONE;
+    const bool fast = ss == 2 && sub_x == 1 && sub_y == 1 && chroma != CHROMA_NONE && w % 16 == 0 && h % 2 == 0 && row_parity == 0 &&
+                      pitch % 16 == 0 && yuv_frame_stride % 16 == 0 && bgr_frame_stride % 16 == 0 && aligned16(src) && aligned16(dst);
+    if (fast) {
+        const long items = (long)(h / 2) * (w / 16);
+        const long gx = std::min<long>((items + FAST_THREADS - 1) / FAST_THREADS, tone ? TONE_MAX_BLOCKS : FAST_MAX_BLOCKS);
+        const long gy = tone ? std::min<long>(n, std::max<long>(TONE_MAX_BLOCKS / gx, 1)) : std::min(n, 65535);
+        const auto kernel = chroma == CHROMA_PLANAR ? yuv420_wide_fast_kernel<CHROMA_PLANAR, OUT> : yuv420_wide_fast_kernel<CHROMA_SEMI, OUT>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)gy), dim3(FAST_THREADS), 0, st, src, n, h, w, (long)yuv_frame_stride, dst,
+                           (long)pitch, (long)bgr_frame_stride, p, oa);
+        return;
+    }
+    const long groups = ((long)w + 3) / 4;
+    long gx = (groups + GEN_LANES - 1) / GEN_LANES, gy = std::min((h + GEN_ROWS - 1) / GEN_ROWS, 65535), gz = std::min(n, 65535);
+    if (tone) {
+        gy = std::min(gy, std::max<long>(TONE_MAX_BLOCKS / gx, 1));
+        gz = std::min(gz, std::max<long>(TONE_MAX_BLOCKS / (gx * gy), 1));
+    }
+    const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)gz), block(GEN_LANES, GEN_ROWS);
+    const long sstride = (long)yuv_frame_stride / ss;          // in samples
+    if (ss == 1) {
+        const auto kernel = chroma == CHROMA_NONE ? yuv_general_kernel<uint8_t, CHROMA_NONE, OUT>
+                          : chroma == CHROMA_PLANAR ? yuv_general_kernel<uint8_t, CHROMA_PLANAR, OUT> : yuv_general_kernel<uint8_t, CHROMA_SEMI, OUT>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, src, n, h, w, sub_x, sub_y, row_parity, sstride, dst, (long)pitch, (long)bgr_frame_stride, p, oa);
+    } else {
+        const auto kernel = chroma == CHROMA_NONE ? yuv_general_kernel<uint16_t, CHROMA_NONE, OUT>
+                          : chroma == CHROMA_PLANAR ? yuv_general_kernel<uint16_t, CHROMA_PLANAR, OUT> : yuv_general_kernel<uint16_t, CHROMA_SEMI, OUT>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, reinterpret_cast<const uint16_t*>(src), n, h, w, sub_x, sub_y, row_parity, sstride, dst,
+                           (long)pitch, (long)bgr_frame_stride, p, oa);
+    }
+}
 
 // ---- deinterlace (vse_yuv_deinterlace) ---------------------------------------------------------------------------------------------
 constexpr int DEINT_STRIP = 8;        // rows a lane of the fast kernel walks down
@@ -652,10 +793,7 @@ int vse_yuv_to_bgr_format(vse_ctx* c, const void* d_yuv, int n, int h, int w, in
                           void* stream) {
     const size_t frame = vse_yuv_frame_bytes(h, w, sub_x, sub_y, chroma, depth, row_parity);
     const int ss = depth > 8 ? 2 : 1;
-    if (!c || !d_yuv || !d_bgr || n < 1 || !frame || msb < 0 || msb > (ss == 2 ? 1 : 0) || matrix < 0 || matrix > 2 || full_range < 0 ||
-        full_range > 1 || pitch < (int64_t)w * 3 || yuv_frame_stride < (int64_t)frame ||
-        bgr_frame_stride < (int64_t)(h - 1) * pitch + (int64_t)w * 3 ||
-        (ss == 2 && ((reinterpret_cast<uintptr_t>(d_yuv) & 1) || (yuv_frame_stride & 1)))) {
+    if (!format_call_ok(c, d_yuv, n, h, w, depth, msb, matrix, full_range, frame, yuv_frame_stride, d_bgr, pitch, bgr_frame_stride)) {
         char msg[560];
         snprintf(msg, sizeof msg, "vse_yuv_to_bgr_format: bad arguments (n %d, frame %d x %d of at most 2^31 - 1 pixels, subsampling %d, %d of 0, 0 | "
                  "1, 0 | 1, 1, chroma %d of 0 (with subsampling 0, 0) | 1 | 2 (with subsampling 1, 1), depth %d of 8..16, msb %d of 0 | 1 (0 at "
@@ -669,47 +807,52 @@ int vse_yuv_to_bgr_format(vse_ctx* c, const void* d_yuv, int n, int h, int w, in
     // what the 8-bit 4:2:0 kernels convert stays theirs
     if (ss == 1 && sub_x == 1 && sub_y == 1 && chroma != CHROMA_NONE && !full_range && matrix <= BT709)
         return vse_yuv_to_bgr_matrix(c, d_yuv, n, h, w, chroma - 1, row_parity, yuv_frame_stride, d_bgr, pitch, bgr_frame_stride, matrix, stream);
-    const int s = depth - 8;
-    const int* k0 = YUV_K0[full_range][matrix];
-    YuvParams p;
-    p.shift = msb ? 16 - depth : 0;
-    p.maxv = (1 << depth) - 1;
-    p.yoff = full_range ? 0 : 16 << s;
-    p.coff = 128 << s;
-    p.ky = scaled_factor(k0[0], s);
-    p.bu = scaled_factor(k0[1], s);
-    p.gu = scaled_factor(k0[2], s);
-    p.gv = scaled_factor(k0[3], s);
-    p.rv = scaled_factor(k0[4], s);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_yuv);
-    uint8_t* dst = reinterpret_cast<uint8_t*>(d_bgr);
-    const bool fast = ss == 2 && sub_x == 1 && sub_y == 1 && chroma != CHROMA_NONE && w % 16 == 0 && h % 2 == 0 && row_parity == 0 &&
-                      pitch % 16 == 0 && yuv_frame_stride % 16 == 0 && bgr_frame_stride % 16 == 0 && aligned16(src) && aligned16(dst);
-    if (fast) {
-        const long items = (long)(h / 2) * (w / 16);
-        const dim3 grid((unsigned)std::min<long>((items + FAST_THREADS - 1) / FAST_THREADS, FAST_MAX_BLOCKS), (unsigned)std::min(n, 65535));
-        const auto kernel = chroma == CHROMA_PLANAR ? yuv420_wide_fast_kernel<CHROMA_PLANAR> : yuv420_wide_fast_kernel<CHROMA_SEMI>;
-        hipLaunchKernelGGL(kernel, grid, dim3(FAST_THREADS), 0, st, src, n, h, w, (long)yuv_frame_stride, dst, (long)pitch, (long)bgr_frame_stride, p);
-    } else {
-        const long groups = ((long)w + 3) / 4;
-        const dim3 grid((unsigned)((groups + GEN_LANES - 1) / GEN_LANES), (unsigned)std::min((h + GEN_ROWS - 1) / GEN_ROWS, 65535),
-                        (unsigned)std::min(n, 65535));
-        const dim3 block(GEN_LANES, GEN_ROWS);
-        const long sstride = (long)yuv_frame_stride / ss;          // in samples
-        if (ss == 1) {
-            const auto kernel = chroma == CHROMA_NONE ? yuv_general_kernel<uint8_t, CHROMA_NONE>
-                              : chroma == CHROMA_PLANAR ? yuv_general_kernel<uint8_t, CHROMA_PLANAR> : yuv_general_kernel<uint8_t, CHROMA_SEMI>;
-            hipLaunchKernelGGL(kernel, grid, block, 0, st, src, n, h, w, sub_x, sub_y, row_parity, sstride, dst, (long)pitch, (long)bgr_frame_stride, p);
-        } else {
-            const auto kernel = chroma == CHROMA_NONE ? yuv_general_kernel<uint16_t, CHROMA_NONE>
-                              : chroma == CHROMA_PLANAR ? yuv_general_kernel<uint16_t, CHROMA_PLANAR> : yuv_general_kernel<uint16_t, CHROMA_SEMI>;
-            hipLaunchKernelGGL(kernel, grid, block, 0, st, reinterpret_cast<const uint16_t*>(src), n, h, w, sub_x, sub_y, row_parity, sstride, dst,
-                               (long)pitch, (long)bgr_frame_stride, p);
-        }
-    }
+    launch_format<PlainOut>(reinterpret_cast<const uint8_t*>(d_yuv), n, h, w, sub_x, sub_y, chroma, ss, row_parity, yuv_frame_stride,
+                            reinterpret_cast<uint8_t*>(d_bgr), pitch, bgr_frame_stride, yuv_params(depth, msb, matrix, full_range), PlainOut::Args(),
+                            reinterpret_cast<hipStream_t>(stream));
     if (hipGetLastError() != hipSuccess) {
         vse_set_error("vse_yuv_to_bgr_format: launch failed");
+        return VSE_E_HIP;
+    }
+    return VSE_OK;
+}
+
+size_t vse_yuv_tonemap_table_bytes(void) { return TONE_BYTES; }
+
+int vse_yuv_to_bgr_tonemap(vse_ctx* c, const void* d_yuv, int n, int h, int w, int sub_x, int sub_y, int chroma, int depth, int msb, int matrix,
+                           int full_range, int row_parity, int64_t yuv_frame_stride, void* d_bgr, int64_t pitch, int64_t bgr_frame_stride,
+                           const void* d_table, const int32_t* gamut, void* stream) {
+    const size_t frame = vse_yuv_frame_bytes(h, w, sub_x, sub_y, chroma, depth, row_parity);
+    bool ok = format_call_ok(c, d_yuv, n, h, w, depth, msb, matrix, full_range, frame, yuv_frame_stride, d_bgr, pitch, bgr_frame_stride) &&
+              d_table && aligned16(d_table) && gamut;
+    for (int r = 0; ok && r < 3; ++r) {
+        long pos = 0, neg = 0;
+        for (int k = 0; k < 3; ++k) (gamut[3 * r + k] > 0 ? pos : neg) += gamut[3 * r + k];
+        ok = pos <= 32767 && neg >= -32768;
+    }
+    if (!ok) {
+        char msg[1024];
+        int g[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (int k = 0; gamut && k < 9; ++k) g[k] = gamut[k];
+        snprintf(msg, sizeof msg, "vse_yuv_to_bgr_tonemap: bad arguments (n %d, frame %d x %d of at most 2^31 - 1 pixels, subsampling %d, %d of 0, 0 | "
+                 "1, 0 | 1, 1, chroma %d of 0 (with subsampling 0, 0) | 1 | 2 (with subsampling 1, 1), depth %d of 8..16, msb %d of 0 | 1 (0 at "
+                 "depth 8), matrix %d of 0 | 1 | 2, full range %d of 0 | 1, row parity %d of 0..%d, packed frame stride %lld of at least %zu, "
+                 "pitch %lld, output frame stride %lld, base %p and stride 2-byte aligned for 2-byte samples, table %p 16-byte aligned, gamut %p "
+                 "[%d %d %d; %d %d %d; %d %d %d] with each row's positive entries summing to at most 32767 and its negative ones to at least "
+                 "-32768)", n, h, w, sub_x, sub_y, chroma, depth, msb, matrix, full_range, row_parity, sub_y == 1 ? 1 : 0,
+                 (long long)yuv_frame_stride, frame, (long long)pitch, (long long)bgr_frame_stride, d_yuv, d_table, (const void*)gamut, g[0], g[1],
+                 g[2], g[3], g[4], g[5], g[6], g[7], g[8]);
+        vse_set_error(msg);
+        return VSE_E_INVAL;
+    }
+    ToneOut::Args oa;
+    oa.table = reinterpret_cast<const uint4*>(d_table);
+    for (int k = 0; k < 9; ++k) oa.m[k] = gamut[k];
+    launch_format<ToneOut>(reinterpret_cast<const uint8_t*>(d_yuv), n, h, w, sub_x, sub_y, chroma, depth > 8 ? 2 : 1, row_parity, yuv_frame_stride,
+                           reinterpret_cast<uint8_t*>(d_bgr), pitch, bgr_frame_stride, yuv_params(depth, msb, matrix, full_range), oa,
+                           reinterpret_cast<hipStream_t>(stream));
+    if (hipGetLastError() != hipSuccess) {
+        vse_set_error("vse_yuv_to_bgr_tonemap: launch failed");
         return VSE_E_HIP;
     }
     return VSE_OK;

@@ -5,6 +5,7 @@ goes through the C ABI; there is NO fallback — if the library or a gfx950 GPU 
 """
 import ctypes as C
 import os
+import threading
 from collections import namedtuple
 
 import numpy as np
@@ -32,6 +33,7 @@ EXPORTS = [
     "vse_frame_cells_hold_bounded_state_bytes", "vse_frame_cells_hold_bounded",
     "vse_interval_stream_state_bytes", "vse_interval_stream",
     "vse_yuv_frame_bytes", "vse_yuv_to_bgr_format", "vse_yuv_deinterlace",
+    "vse_yuv_tonemap_table_bytes", "vse_yuv_to_bgr_tonemap",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -241,6 +243,9 @@ def load_library(path=None):
     lib.vse_yuv_frame_bytes.restype = C.c_size_t
     lib.vse_yuv_frame_bytes.argtypes = [C.c_int] * 7
     lib.vse_yuv_to_bgr_format.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 11 + [C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+    lib.vse_yuv_tonemap_table_bytes.restype = C.c_size_t
+    lib.vse_yuv_tonemap_table_bytes.argtypes = []
+    lib.vse_yuv_to_bgr_tonemap.argtypes = lib.vse_yuv_to_bgr_format.argtypes[:-1] + [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
     lib.vse_yuv_deinterlace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 11 + [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     if lib.vse_sizeof_op() != ir.OP_DT.itemsize or lib.vse_sizeof_view() != ir.VIEW_DT.itemsize:
         raise VseError(f"ABI mismatch: vse_op {lib.vse_sizeof_op()} vs {ir.OP_DT.itemsize}, "
@@ -292,6 +297,8 @@ class Context:
         self.handle = C.c_void_p()
         _check(self.lib.vse_init(device, C.byref(self.handle)), "vse_init")
         self.tdev = self.torch.device("cuda", device)
+        self._tone_tables = {}            # ingest.ToneMap -> (cuda uint8 [16128] table, its gamut as int32[9]): uploaded once
+        self._tone_lock = threading.Lock()
 
     def stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.tdev).cuda_stream)
@@ -958,10 +965,26 @@ class Context:
                    "vse_yuv_to_bgr_matrix")
         return out
 
-    def yuv_to_bgr(self, packed, n, h, w, fmt, row_parity=0, out=None):
+    def tone_table(self, tone):
+        """The device copy of an ingest.ToneMap's table (anything hashable with packed() -> the 16128 bytes and tables() -> (A, T, M)) and
+        its gamut as ctypes int32[9], uploaded on first use and kept for the context's life."""
+        with self._tone_lock:
+            hit = self._tone_tables.get(tone)
+            if hit is None:
+                t = self.torch
+                host = np.frombuffer(tone.packed(), np.uint8)
+                if host.size != self.lib.vse_yuv_tonemap_table_bytes():
+                    raise VseError(f"tone_table: a table of {host.size} bytes, not {self.lib.vse_yuv_tonemap_table_bytes()}")
+                dev = t.from_numpy(host.copy()).to(self.tdev)
+                t.cuda.current_stream(self.tdev).synchronize()          # any stream may read it from here on
+                hit = self._tone_tables[tone] = (dev, (C.c_int32 * 9)(*[int(v) for v in np.asarray(tone.tables()[2]).reshape(-1)]))
+            return hit
+
+    def yuv_to_bgr(self, packed, n, h, w, fmt, row_parity=0, out=None, tone=None):
         """packed: cuda uint8 holding n packed (sub-)frames of h x w pixels of the format `fmt` (an ingest.YuvFormat, or anything with its
         integer attributes sub_x, sub_y, chroma, depth, msb, matrix, full_range; include/vse_hip.h vse_yuv_to_bgr_format), 1-D (frames back
-        to back) or 2-D [n, stride in bytes] -> cuda uint8 [n,h,w,3] BGR on the current stream.  out: as yuv420_to_bgr's."""
+        to back) or 2-D [n, stride in bytes] -> cuda uint8 [n,h,w,3] BGR on the current stream.  out: as yuv420_to_bgr's.  tone: an
+        ingest.ToneMap: convert HDR material to SDR with its tables (vse_yuv_to_bgr_tonemap; see tone_table)."""
         t = self.torch
         n, h, w, row_parity = int(n), int(h), int(w), int(row_parity)
         matrix = YUV_FORMAT_MATRICES.get(fmt.matrix, fmt.matrix)
@@ -979,6 +1002,13 @@ class Context:
             out = t.empty((max(n, 0), max(h, 0), max(w, 0), 3), dtype=t.uint8, device=self.tdev)
         assert out.dtype == t.uint8 and tuple(out.shape) == (n, h, w, 3) and out.stride(3) == 1 and out.stride(2) == 3
         dstride = out.stride(0) if n > 1 else max(out.stride(0), (h - 1) * out.stride(1) + 3 * w)
+        if tone is not None:
+            table, gamut = self.tone_table(tone)
+            _check(self.lib.vse_yuv_to_bgr_tonemap(self.handle, C.c_void_p(packed.data_ptr()), n, h, w, int(fmt.sub_x), int(fmt.sub_y),
+                                                   int(fmt.chroma), int(fmt.depth), int(fmt.msb), matrix, int(fmt.full_range), row_parity, sstride,
+                                                   C.c_void_p(out.data_ptr()), out.stride(1), dstride, C.c_void_p(table.data_ptr()), gamut,
+                                                   self.stream()), "vse_yuv_to_bgr_tonemap")
+            return out
         _check(self.lib.vse_yuv_to_bgr_format(self.handle, C.c_void_p(packed.data_ptr()), n, h, w, int(fmt.sub_x), int(fmt.sub_y), int(fmt.chroma),
                                               int(fmt.depth), int(fmt.msb), matrix, int(fmt.full_range), row_parity, sstride,
                                               C.c_void_p(out.data_ptr()), out.stride(1), dstride, self.stream()), "vse_yuv_to_bgr_format")

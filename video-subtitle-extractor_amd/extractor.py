@@ -720,6 +720,16 @@ def _parse_area(text):
     return SubtitleArea(*(int(p) for p in parts))
 
 
+def tone_arguments(args):
+    """--transfer, --white-nits, --peak-nits and --tone-curve of a parsed command line -> the keywords ingest.open_source takes for them."""
+    params = {k: v for k, v in (("white_nits", args.white_nits), ("peak_nits", args.peak_nits), ("curve", args.tone_curve)) if v is not None}
+    if args.transfer is None:
+        if params:
+            raise ValueError("--white-nits, --peak-nits and --tone-curve belong to --transfer pq | hlg")
+        return {}
+    return {"transfer": args.transfer, "tone_params": params or None}
+
+
 def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, focus_fn=None, stream_fn=None):
     """ocr: the recogniser (None: shim.OcrRecogniser on the GPU, frames staged through staging.default_uploader, YUV 4:2:0 converted
     on the device); counter: the change / hold selector's count_fn (None: the GPU's); cells_fn: the locator's (None: the GPU's);
@@ -750,6 +760,14 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
                    "Y4M header's It / Ib; Ip is then left as it is]; tff / bff override the header")
     p.add_argument("--deinterlace-thresh", type=int, default=10, metavar="N", help="--deinterlace adaptive: a sample that changed by more "
                    "than N 8-bit levels since the previous frame has moved, 0..255 [10]")
+    p.add_argument("--transfer", default=None, choices=("pq", "hlg"), help="HDR video (needs --wide-yuv or --pix-fmt, normally with --matrix "
+                   "bt2020): undo PQ (UHD Blu-ray, streaming masters) or HLG (UHD broadcast) and tone-map to SDR on the GPU; Y4M carries no tag "
+                   "for it [none: the samples are taken as SDR and HDR material comes out flat]")
+    p.add_argument("--white-nits", type=float, default=None, metavar="N", help="--transfer: the luminance that becomes SDR white [203]")
+    p.add_argument("--peak-nits", type=float, default=None, metavar="N", help="--transfer, --tone-curve knee: the luminance that the "
+                   "roll-off brings down to SDR white [1000]")
+    p.add_argument("--tone-curve", default=None, choices=("knee", "clip"), help="--transfer: roll highlights off above 0.8 of SDR white, "
+                   "or clip at SDR white [knee]")
     p.add_argument("--area", default=None, metavar="ymin,ymax,xmin,xmax|auto", help="the subtitle area in frame pixels, or `auto` to "
                    "look for it first (not in one pass) [none: the whole frame, fps sampler]")
     p.add_argument("--selector", default="fps", choices=("fps", "change", "hold"), help="which frames go to OCR [fps]")
@@ -821,7 +839,8 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
             raise ValueError("--field-order and --deinterlace-thresh belong to --deinterlace adaptive | interpolate")
         source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout, matrix=args.matrix,
                                     wide=args.wide_yuv or args.deinterlace is not None, range=args.range, pix_fmt=args.pix_fmt,
-                                    deinterlace=args.deinterlace, field_order=args.field_order, deinterlace_thresh=args.deinterlace_thresh)
+                                    deinterlace=args.deinterlace, field_order=args.field_order, deinterlace_thresh=args.deinterlace_thresh,
+                                    **tone_arguments(args))
         uploader = None
         if ocr is None:
             if args.weights_dir is not None:

@@ -28,6 +28,10 @@ range, BT.2020 and P010-style semi-planar surfaces are accepted only when asked 
 integers of include/vse_hip.h vse_yuv_to_bgr_format; YuvFrame.to_bgr and the device convert with the same integers (the 8-bit ones with
 factors scaled to the depth, nearest chroma, no transfer function: PQ / HLG material comes out flat, its text and edges remain).
 
+HDR video (ToneMap; transfer="pq" | "hlg" on those readers): the frames carry a ToneMap, and YuvFrame.to_bgr and the device
+(vse_yuv_to_bgr_tonemap) convert by the same integers at 12 bits, then through the map's tables: the EOTF and a tone curve to linear light
+relative to SDR white, BT.2020 to BT.709 in linear light, the output gamma.  Y4M carries no transfer tag: it is the caller's to say.
+
 Interlaced video (InterlacedYuvFrame; deinterlace="adaptive" | "interpolate" on those readers, on top of wide=True): the pictures are two
 woven fields.  A frame carries the previous picture's planes beside its own; to_bgr() and the device (vse_yuv_deinterlace, through
 staging.Uploader) keep the first field's rows, weave what did not change since the previous picture and interpolate the rest, by the same
@@ -449,14 +453,176 @@ class YuvFormat(namedtuple("YuvFormat", "sub_x sub_y chroma depth msb matrix ful
         return cls(sx, sy, 0 if sub == "mono" else 1, depth, 0, matrix, full)
 
 
+# ---- HDR: PQ / HLG -> SDR (vse_yuv_to_bgr_tonemap) ----------------------------------------------------------------------------------
+TONE_TRANSFERS = ("pq", "hlg")
+TONE_PRIMARIES = ("bt2020", "bt709")
+TONE_CURVES = ("knee", "clip")
+TONE_CODES, TONE_GAMMA_ENTRIES, TONE_PEAK_CODE = 4096, 7936, 4080           # A's and T's lengths; the 12-bit code of R'G'B' = 1
+_CHROMATICITIES = {"bt709": ((0.64, 0.33), (0.30, 0.60), (0.15, 0.06)), "bt2020": ((0.708, 0.292), (0.170, 0.797), (0.131, 0.046))}
+_D65 = (0.3127, 0.3290)
+_HLG_A = 0.17883277
+_HLG_B, _HLG_C = 1.0 - 4.0 * _HLG_A, 0.5 - _HLG_A * np.log(4.0 * _HLG_A)
+_PQ_M1, _PQ_M2, _PQ_C1, _PQ_C2, _PQ_C3 = 2610.0 / 16384, 2523.0 / 4096 * 128, 3424.0 / 4096, 2413.0 / 4096 * 32, 2392.0 / 4096 * 32
+
+
+def _rgb_to_xyz(primaries):
+    xy = np.array(_CHROMATICITIES[primaries], np.float64)
+    cols = np.stack([xy[:, 0] / xy[:, 1], np.ones(3), (1.0 - xy[:, 0] - xy[:, 1]) / xy[:, 1]])
+    white = np.array([_D65[0] / _D65[1], 1.0, (1.0 - _D65[0] - _D65[1]) / _D65[1]])
+    return cols * np.linalg.solve(cols, white)
+
+
+def bt2020_to_bt709():
+    """The 3 x 3 matrix from linear BT.2020 RGB to linear BT.709 RGB (float64, rows and columns R G B), from the chromaticities and D65."""
+    return np.linalg.solve(_rgb_to_xyz("bt709"), _rgb_to_xyz("bt2020"))
+
+
+def pq_eotf(e):
+    """SMPTE ST 2084: the non-linear signal 0..1 -> nits, 0..10 000 (float64)."""
+    p = np.power(np.clip(np.asarray(e, np.float64), 0.0, 1.0), 1.0 / _PQ_M2)
+    return 10000.0 * np.power(np.maximum(p - _PQ_C1, 0.0) / (_PQ_C2 - _PQ_C3 * p), 1.0 / _PQ_M1)
+
+
+def pq_inverse_eotf(nits):
+    y = np.power(np.clip(np.asarray(nits, np.float64) / 10000.0, 0.0, 1.0), _PQ_M1)
+    return np.power((_PQ_C1 + _PQ_C2 * y) / (1.0 + _PQ_C3 * y), _PQ_M2)
+
+
+def hlg_nits(e):
+    """BT.2100 HLG, PER CHANNEL: the inverse OETF, then 1000 * E ** 1.2 nits (a 1000-nit display's system gamma).  The true OOTF applies
+    that gamma to the luminance of the three channels together; per channel it shifts saturated colours (a known limit)."""
+    e = np.clip(np.asarray(e, np.float64), 0.0, 1.0)
+    scene = np.where(e <= 0.5, e * e / 3.0, (np.exp((e - _HLG_C) / _HLG_A) + _HLG_B) / 12.0)
+    return 1000.0 * np.power(scene, 1.2)
+
+
+def hlg_inverse_nits(nits):
+    """The inverse of hlg_nits: nits 0..1000 -> the HLG signal 0..1."""
+    scene = np.power(np.clip(np.asarray(nits, np.float64) / 1000.0, 0.0, 1.0), 1.0 / 1.2)
+    return np.where(scene <= 1.0 / 12.0, np.sqrt(3.0 * scene), _HLG_A * np.log(np.maximum(12.0 * scene - _HLG_B, 1e-300)) + _HLG_C)
+
+
+class ToneMap(namedtuple("ToneMap", "transfer primaries white_nits peak_nits curve knee gamma")):
+    """How HDR material becomes the SDR BGR the detector and the recogniser were made for: the data of include/vse_hip.h
+    vse_yuv_to_bgr_tonemap.  transfer "pq" | "hlg"; primaries "bt2020" (mapped to BT.709 in linear light) | "bt709" (left alone); white_nits
+    the luminance that becomes SDR white (BT.2408's 203); curve "clip" cuts there, "knee" is linear up to `knee` of white and rolls
+    everything from there to peak_nits off into the rest; gamma the output gamma.  A tuple: equal maps compare and hash equal, and the
+    tables are built once per distinct map.  Tone mapping is per channel (saturated highlights shift in hue), there is no dynamic metadata
+    and no constant-luminance BT.2020; 203, 1000 and 0.8 are conventions and guesses, not measurements."""
+    __slots__ = ()
+
+    def __new__(cls, transfer, primaries="bt2020", white_nits=203.0, peak_nits=1000.0, curve="knee", knee=0.8, gamma=2.4):
+        if transfer not in TONE_TRANSFERS:
+            raise ValueError(f"transfer must be one of {TONE_TRANSFERS}, not {transfer!r}")
+        if primaries not in TONE_PRIMARIES:
+            raise ValueError(f"primaries must be one of {TONE_PRIMARIES}, not {primaries!r}")
+        if curve not in TONE_CURVES:
+            raise ValueError(f"curve must be one of {TONE_CURVES}, not {curve!r}")
+        try:
+            white_nits, peak_nits, knee, gamma = float(white_nits), float(peak_nits), float(knee), float(gamma)
+        except (TypeError, ValueError):
+            raise ValueError(f"white_nits, peak_nits, knee and gamma are numbers, not {(white_nits, peak_nits, knee, gamma)!r}") from None
+        if not (1.0 <= white_nits <= 10000.0 and white_nits <= peak_nits <= 10000.0):
+            raise ValueError(f"white_nits {white_nits} and peak_nits {peak_nits} must be 1 <= white_nits <= peak_nits <= 10000")
+        if not 0.0 < knee < 1.0:
+            raise ValueError(f"knee {knee} must lie inside (0, 1)")
+        if not 1.0 <= gamma <= 4.0:
+            raise ValueError(f"gamma {gamma} must be 1..4")
+        return super().__new__(cls, transfer, primaries, white_nits, peak_nits, curve, knee, gamma)
+
+    def nits(self, e):
+        """The signal 0..1 of one channel -> nits."""
+        return pq_eotf(e) if self.transfer == "pq" else hlg_nits(e)
+
+    def tone_curve(self, x):
+        """Light relative to white_nits -> light relative to SDR white, 0..1."""
+        x = np.asarray(x, np.float64)
+        if self.curve == "clip":
+            return np.minimum(x, 1.0)
+        p = self.peak_nits / self.white_nits
+        s = (p - self.knee) / (1.0 - self.knee)
+        t = np.minimum(np.maximum(x - self.knee, 0.0) / (p - self.knee), 1.0)
+        return np.where(x <= self.knee, x, self.knee + (1.0 - self.knee) * s * t / (1.0 + (s - 1.0) * t))
+
+    def tables(self):
+        """-> (A uint16[4096], T uint8[7936], M int32[3, 3]) of vse_yuv_to_bgr_tonemap, read-only, built once per map."""
+        return _tone_tables(self)
+
+    def packed(self):
+        """The 16 128 bytes the device takes: A (little-endian), then T."""
+        a, t, _ = self.tables()
+        return a.astype("<u2").tobytes() + t.tobytes()
+
+
+_TONE_TABLES = {}
+
+
+def _tone_tables(tone):
+    hit = _TONE_TABLES.get(tone)
+    if hit is None:
+        code = np.minimum(np.arange(TONE_CODES, dtype=np.float64) / TONE_PEAK_CODE, 1.0)
+        a = np.round(65535.0 * tone.tone_curve(tone.nits(code) / tone.white_nits)).astype(np.uint16)
+        j = np.arange(TONE_GAMMA_ENTRIES, dtype=np.float64)
+        lin = np.where(j < 4096, j, (j - 3840.0) * 16.0 + 8.0) / 65535.0
+        t = np.round(255.0 * np.power(lin, 1.0 / tone.gamma)).astype(np.uint8)
+        if tone.primaries == "bt709":
+            m = np.eye(3, dtype=np.int32) * 16384
+        else:
+            m = np.round(16384.0 * bt2020_to_bt709()).astype(np.int32)
+            for r in range(3):
+                m[r, r] += 16384 - int(m[r].sum())            # every row sums to exactly 1: grey stays grey
+        check_gamut(m)
+        for arr in (a, t, m):
+            arr.setflags(write=False)
+        hit = _TONE_TABLES[tone] = (a, t, m)
+    return hit
+
+
+def check_gamut(m):
+    """The bounds vse_yuv_to_bgr_tonemap puts on M (int32 stays exact): per row, positive entries sum to <= 32767, negative ones to >= -32768."""
+    m = np.asarray(m, np.int64).reshape(3, 3)
+    for r in range(3):
+        if m[r][m[r] > 0].sum() > 32767 or m[r][m[r] < 0].sum() < -32768:
+            raise ValueError(f"gamut row {r} {m[r].tolist()}: positive entries may sum to at most 32767, negative ones to at least -32768")
+    return m
+
+
+def _check_tone(tone):
+    if tone is not None and not (hasattr(tone, "tables") and hasattr(tone, "packed")):
+        raise ValueError(f"tone must be None or a ToneMap, not {tone!r}")
+    return tone
+
+
+def _source_tone(name, transfer, tone_params, matrix, takes):
+    """The ToneMap a YUV source attaches to its frames (None without transfer).  primaries default to the matrix's.  takes: whether the
+    source yields YuvFrames."""
+    if transfer is None:
+        if tone_params:
+            raise ValueError(f"{name}: tone_params {sorted(tone_params)} belong to transfer='pq' | 'hlg'")
+        return None
+    if transfer not in TONE_TRANSFERS:
+        raise ValueError(f"{name}: transfer must be None or one of {TONE_TRANSFERS}, not {transfer!r}")
+    if not takes:
+        raise ValueError(f"{name}: transfer={transfer!r} needs wide=True or pix_fmt (the frames are YuvFrames; 8-bit 4:2:0 Yuv420Frames "
+                         "and BGR sources carry no tone map)")
+    params = dict(tone_params or {})
+    unknown = set(params) - set(ToneMap._fields[1:])
+    if unknown:
+        raise ValueError(f"{name}: tone_params takes {ToneMap._fields[1:]}, not {sorted(unknown)}")
+    params.setdefault("primaries", "bt2020" if matrix == "bt2020" else "bt709")
+    return ToneMap(transfer, **params)
+
+
 class YuvFrame:
     """Yuv420Frame for any YuvFormat `fmt`: rows [y0, y1) of one picture that has not been converted.  planes are views of samples (uint8,
     or little-endian uint16 above 8 bits) of fmt.plane_shapes(height, width).  shape == (y1 - y0, width, 3), frame[a:b] narrows the row
-    range, to_bgr() gives the uint8 BGR ndarray by the integers of vse_yuv_to_bgr_format, pack_into() the packed sub-frame it takes."""
+    range, to_bgr() gives the uint8 BGR ndarray by the integers of vse_yuv_to_bgr_format, pack_into() the packed sub-frame it takes.
+    tone: a ToneMap; to_bgr() and the device then convert by the integers of vse_yuv_to_bgr_tonemap; it travels with the slices."""
 
-    def __init__(self, planes, height, width, fmt, y0=0, y1=None):
+    def __init__(self, planes, height, width, fmt, y0=0, y1=None, tone=None):
         if not isinstance(fmt, YuvFormat):
             raise ValueError(f"fmt must be a YuvFormat, not {fmt!r}")
+        self.tone = _check_tone(tone)
         self.planes, self.height, self.width, self.fmt = tuple(planes), int(height), int(width), fmt
         self.y0, self.y1 = int(y0), int(self.height if y1 is None else y1)
         want = fmt.plane_shapes(self.height, self.width)
@@ -479,7 +645,7 @@ class YuvFrame:
         a, b, step = idx.indices(self.y1 - self.y0)
         if step != 1:
             raise TypeError(f"a YuvFrame takes a row slice of step 1, not {idx!r}")
-        return YuvFrame(self.planes, self.height, self.width, self.fmt, self.y0 + a, self.y0 + max(a, b))
+        return YuvFrame(self.planes, self.height, self.width, self.fmt, self.y0 + a, self.y0 + max(a, b), self.tone)
 
     @property
     def row_parity(self):
@@ -508,30 +674,42 @@ class YuvFrame:
         return pos
 
     def to_bgr(self):
-        """uint8 BGR [y1 - y0, W, 3]: nearest chroma, the integers of vse_yuv_to_bgr_format (include/vse_hip.h) in int32."""
-        return _rows_to_bgr(self.fmt, self.planes[0][self.y0:self.y1], self.planes[1:], np.arange(self.y0, self.y1) >> self.fmt.sub_y, self.width)
+        """uint8 BGR [y1 - y0, W, 3]: nearest chroma, the integers of vse_yuv_to_bgr_format (include/vse_hip.h) in int32, or with a
+        tone those of vse_yuv_to_bgr_tonemap."""
+        return _rows_to_bgr(self.fmt, self.planes[0][self.y0:self.y1], self.planes[1:], np.arange(self.y0, self.y1) >> self.fmt.sub_y, self.width,
+                            self.tone)
 
 
-def _rows_to_bgr(fmt, luma, chroma, rows, width):
+def _rows_to_bgr(fmt, luma, chroma, rows, width, tone=None):
     """YuvFrame.to_bgr on luma rows `luma` [n, width] whose chroma stands in row rows[k] of the planes `chroma` -> uint8 BGR [n, width, 3]."""
     shift, maxv, yoff, coff, ky, bu, gu, gv, rv = fmt.factors()
+    half, down, top = (1 << 19, 20, 255) if tone is None else (1 << 15, 16, TONE_CODES - 1)
 
     def samples(a):
         return np.minimum(np.asarray(a).astype(np.int32) >> shift, maxv)
-    c = np.maximum(samples(luma) - yoff, 0) * np.int32(ky) + np.int32(1 << 19)
-    out = np.empty((len(rows), width, 3), np.uint8)
+    c = np.maximum(samples(luma) - yoff, 0) * np.int32(ky) + np.int32(half)
     if fmt.chroma == 0:
-        out[...] = np.clip(c >> 20, 0, 255)[..., None]
-        return out
-    cols = np.arange(width) >> fmt.sub_x
-    if fmt.chroma == 1:
-        u, v = (samples(np.asarray(p)[rows][:, cols]) - coff for p in chroma)
+        codes = [np.clip(c >> down, 0, top)] * 3
     else:
-        uv = np.asarray(chroma[0])[rows]
-        u, v = samples(uv[:, 2 * cols]) - coff, samples(uv[:, 2 * cols + 1]) - coff
-    out[..., 0] = np.clip((c + np.int32(bu) * u) >> 20, 0, 255)
-    out[..., 1] = np.clip((c + np.int32(gu) * u + np.int32(gv) * v) >> 20, 0, 255)
-    out[..., 2] = np.clip((c + np.int32(rv) * v) >> 20, 0, 255)
+        cols = np.arange(width) >> fmt.sub_x
+        if fmt.chroma == 1:
+            u, v = (samples(np.asarray(p)[rows][:, cols]) - coff for p in chroma)
+        else:
+            uv = np.asarray(chroma[0])[rows]
+            u, v = samples(uv[:, 2 * cols]) - coff, samples(uv[:, 2 * cols + 1]) - coff
+        codes = [np.clip((c + np.int32(bu) * u) >> down, 0, top), np.clip((c + np.int32(gu) * u + np.int32(gv) * v) >> down, 0, top),
+                 np.clip((c + np.int32(rv) * v) >> down, 0, top)]
+    out = np.empty((len(rows), width, 3), np.uint8)
+    if tone is None:
+        for k in range(3):
+            out[..., k] = codes[k]
+        return out
+    # vse_yuv_to_bgr_tonemap: A, the gamut matrix in linear light (rows and columns R G B; the codes are B G R), T; int32 throughout
+    table_a, table_t, m = tone.tables()
+    lb, lg, lr = (table_a[e].astype(np.int32) for e in codes)
+    for k, r in ((2, 0), (1, 1), (0, 2)):
+        p = np.clip((np.int32(m[r][0]) * lr + np.int32(m[r][1]) * lg + np.int32(m[r][2]) * lb + np.int32(1 << 13)) >> 14, 0, 65535)
+        out[..., k] = table_t[np.where(p < 4096, p, 3840 + (p >> 4))]
     return out
 
 
@@ -581,8 +759,8 @@ class InterlacedYuvFrame(YuvFrame):
     "interpolate".  frame[a:b] is the same class with the same prev; to_bgr() deinterlaces on the host by the same integers and converts
     as YuvFrame does, so f[a:b].to_bgr() == f.to_bgr()[a:b]; staging.Uploader deinterlaces and converts on the device."""
 
-    def __init__(self, planes, height, width, fmt, prev=None, field_order="tff", mode="adaptive", thresh=10, y0=0, y1=None):
-        super().__init__(planes, height, width, fmt, y0, y1)
+    def __init__(self, planes, height, width, fmt, prev=None, field_order="tff", mode="adaptive", thresh=10, y0=0, y1=None, tone=None):
+        super().__init__(planes, height, width, fmt, y0, y1, tone)
         self.thresh = _check_deinterlace(mode, field_order, thresh, FIELD_ORDERS)
         if mode is None:
             raise ValueError(f"mode must be one of {DEINTERLACE_MODES}, not None")
@@ -608,7 +786,7 @@ class InterlacedYuvFrame(YuvFrame):
         if step != 1:
             raise TypeError(f"an InterlacedYuvFrame takes a row slice of step 1, not {idx!r}")
         return InterlacedYuvFrame(self.planes, self.height, self.width, self.fmt, self.prev, self.field_order, self.mode, self.thresh,
-                                  self.y0 + a, self.y0 + max(a, b))
+                                  self.y0 + a, self.y0 + max(a, b), self.tone)
 
     def _deinterlaced(self, k, a, b):
         prev = None if self.prev is None or self.mode == "interpolate" else self.prev[k]
@@ -622,7 +800,7 @@ class InterlacedYuvFrame(YuvFrame):
         c0, c1 = self._chroma_rows()
         chroma = [self._deinterlaced(k, c0, c1) for k in range(1, len(self.planes))]
         return _rows_to_bgr(self.fmt, self._deinterlaced(0, self.y0, self.y1), chroma, (np.arange(self.y0, self.y1) >> self.fmt.sub_y) - c0,
-                            self.width)
+                            self.width, self.tone)
 
     def band(self):
         """(a, b): the rows packed for the device in place of [y0, y1): two more on either side, a rounded down to a multiple of 4 and b up to
@@ -741,6 +919,7 @@ class _Yuv420FileSource:
     deinterlace = None            # "adaptive" | "interpolate" with field_order "tff" | "bff": the frames are InterlacedYuvFrames
     field_order = None
     deinterlace_thresh = 10
+    tone = None                   # a ToneMap (transfer="pq" | "hlg" on the readers of YuvFrames): the frames carry it
     _last = None                  # (frame number, planes) of the last read_raw: the next frame's prev is then the same views
 
     def _planes(self, frame_no):
@@ -771,9 +950,10 @@ class _Yuv420FileSource:
         off = self._offsets[frame_no - 1]
         if self.fmt is not None and self.field_order is not None:
             prev = self._planes(frame_no - 1) if frame_no > 1 else None
-            return InterlacedYuvFrame(self._planes(frame_no), h, w, self.fmt, prev, self.field_order, self.deinterlace, self.deinterlace_thresh)
+            return InterlacedYuvFrame(self._planes(frame_no), h, w, self.fmt, prev, self.field_order, self.deinterlace, self.deinterlace_thresh,
+                                      tone=self.tone)
         if self.fmt is not None:
-            return YuvFrame(_planes_at(self._buf, off, h, w, self.fmt), h, w, self.fmt)
+            return YuvFrame(_planes_at(self._buf, off, h, w, self.fmt), h, w, self.fmt, tone=self.tone)
         luma = self._buf[off:off + h * w].reshape(h, w)
         off += h * w
         if self.layout == "i420":
@@ -903,11 +1083,14 @@ class Y4mSource(_Yuv420FileSource):
     Yuv420Frames.  wide=True: parse_y4m_header_wide's, with `range` and a matrix of YUV_FORMAT_MATRICES; the frames are YuvFrames of
     self.fmt (10-bit, 4:2:2, 4:4:4, grey, full range ...).  deinterlace="adaptive" | "interpolate" (needs wide=True) accepts interlaced
     headers as parse_y4m_header_fields reads them with `field_order`; the frames of woven fields are InterlacedYuvFrames, each with the
-    frame before it as its prev, read() and frames() deinterlace on the host."""
+    frame before it as its prev, read() and frames() deinterlace on the host.  transfer="pq" | "hlg" (needs wide=True; Y4M carries no tag for
+    it) with tone_params (ToneMap's fields but transfer; primaries default to "bt2020" under matrix="bt2020", else "bt709") attaches a
+    ToneMap to the frames: HDR material comes out as SDR."""
 
     layout = "i420"
 
-    def __init__(self, path, fps=None, matrix="bt601", wide=False, range="auto", deinterlace=None, field_order="auto", deinterlace_thresh=10):
+    def __init__(self, path, fps=None, matrix="bt601", wide=False, range="auto", deinterlace=None, field_order="auto", deinterlace_thresh=10,
+                 transfer=None, tone_params=None):
         self.deinterlace_thresh = _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
         if deinterlace is not None and not wide:
             raise ValueError(f"{path}: deinterlace={deinterlace!r} needs wide=True (the frames are YuvFrames)")
@@ -916,6 +1099,7 @@ class Y4mSource(_Yuv420FileSource):
             YuvFormat(matrix=matrix)        # a bad matrix is refused before the file is opened
         else:
             _check_matrix(matrix)
+        self.tone = _source_tone(path, transfer, tone_params, matrix, wide)
         self.matrix = matrix
         size = self._map(path)
         mm = self._mm
@@ -961,8 +1145,10 @@ class Y4mStream:
 
     deinterlace = field_order = None      # as Y4mSource's; the stream keeps the last frame's planes, the next frame's prev
 
+    tone = None                       # as Y4mSource's (transfer, tone_params)
+
     def __init__(self, fileobj, fps=None, matrix="bt601", name="<stream>", wide=False, range="auto", deinterlace=None, field_order="auto",
-                 deinterlace_thresh=10):
+                 deinterlace_thresh=10, transfer=None, tone_params=None):
         self.deinterlace_thresh = _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
         if deinterlace is not None and not wide:
             raise ValueError(f"{name}: deinterlace={deinterlace!r} needs wide=True (the frames are YuvFrames)")
@@ -971,6 +1157,7 @@ class Y4mStream:
             YuvFormat(matrix=matrix)
         else:
             _check_matrix(matrix)
+        self.tone = _source_tone(name, transfer, tone_params, matrix, wide)
         self.matrix = matrix
         self._fp, self.name = fileobj, name
         self._pos = 0                 # bytes of the stream consumed
@@ -1035,11 +1222,11 @@ class Y4mStream:
             count += 1
             if self.fmt is not None and self.field_order is not None:
                 planes = _planes_at(buf, 0, h, w, self.fmt)
-                yield InterlacedYuvFrame(planes, h, w, self.fmt, last, self.field_order, self.deinterlace, self.deinterlace_thresh)
+                yield InterlacedYuvFrame(planes, h, w, self.fmt, last, self.field_order, self.deinterlace, self.deinterlace_thresh, tone=self.tone)
                 last = planes
                 continue
             if self.fmt is not None:
-                yield YuvFrame(_planes_at(buf, 0, h, w, self.fmt), h, w, self.fmt)
+                yield YuvFrame(_planes_at(buf, 0, h, w, self.fmt), h, w, self.fmt, tone=self.tone)
                 continue
             planes = (buf[:h * w].reshape(h, w), buf[h * w:h * w + ch * cw].reshape(ch, cw), buf[h * w + ch * cw:].reshape(ch, cw))
             yield Yuv420Frame(planes, h, w, "i420", matrix=self.matrix)
@@ -1077,11 +1264,12 @@ class YuvSource(_Yuv420FileSource):
     """Yuv420Source for any YuvFormat: a headerless file of consecutive packed pictures of `fmt` (`ffmpeg -f rawvideo -pix_fmt NAME`, a
     hardware decoder's P010 surfaces), memory-mapped; read_raw / raw_frames hand out YuvFrames.  A partial last frame is dropped.
     deinterlace="adaptive" | "interpolate": the pictures are woven fields and the frames InterlacedYuvFrames; a headerless file names no
-    field order, so field_order must be "tff" or "bff"."""
+    field order, so field_order must be "tff" or "bff".  transfer, tone_params: as Y4mSource's."""
 
-    def __init__(self, path, width, height, fps, fmt, deinterlace=None, field_order="auto", deinterlace_thresh=10):
+    def __init__(self, path, width, height, fps, fmt, deinterlace=None, field_order="auto", deinterlace_thresh=10, transfer=None, tone_params=None):
         if not isinstance(fmt, YuvFormat):
             raise ValueError(f"fmt must be a YuvFormat, not {fmt!r}")
+        self.tone = _source_tone(path, transfer, tone_params, fmt.matrix, True)
         self.deinterlace_thresh = _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
         if deinterlace is not None:
             if field_order == "auto":
@@ -1102,23 +1290,28 @@ _RAW_PIX_FMT_EXT = {".p010": "p010le"}
 
 
 def open_source(path, fps=None, size=None, layout=None, matrix="bt601", wide=False, range="auto", pix_fmt=None, deinterlace=None,
-                field_order="auto", deinterlace_thresh=10):
+                field_order="auto", deinterlace_thresh=10, transfer=None, tone_params=None):
     """The source of a file by its extension: .npy (needs fps), .y4m, .yuv / .i420 / .nv12 (headerless: need size=(width, height) and
     fps; `layout` overrides the extension's), anything else an AVI; "-" is a Y4mStream over standard input.  `matrix` goes to the
     YUV sources.  wide=True lets the Y4M readers accept what parse_y4m_header_wide does, with `range` ("auto": the header's).  pix_fmt
     (a name of YuvFormat.from_pix_fmt; .p010 implies p010le) reads a headerless file of that format through YuvSource, with `range`
     ("auto": the name's own) and any matrix of YUV_FORMAT_MATRICES; it needs size and fps.  deinterlace ("adaptive" | "interpolate"),
     field_order and deinterlace_thresh go to the Y4M readers (with wide=True) and to YuvSource (with pix_fmt and a field order); no other
-    source takes them."""
+    source takes them.  transfer ("pq" | "hlg") and tone_params (ToneMap's other fields) go to the same readers under the same
+    conditions: HDR material is tone-mapped to SDR; every other source refuses them."""
     if range not in YUV_RANGES:
         raise ValueError(f"range must be one of {YUV_RANGES}, not {range!r}")
     _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
     fields = {} if deinterlace is None else dict(deinterlace=deinterlace, field_order=field_order, deinterlace_thresh=deinterlace_thresh)
+    if transfer is not None or tone_params:
+        fields.update(transfer=transfer, tone_params=tone_params)
     if str(path) == "-":
         import sys
         return Y4mStream(sys.stdin.buffer, fps, matrix, name="<stdin>", wide=wide, range=range, **fields)
     ext = os.path.splitext(str(path))[1].lower()
     if fields and ext != ".y4m" and pix_fmt is None and (layout is not None or ext not in _RAW_PIX_FMT_EXT):
+        if deinterlace is None:
+            _source_tone(path, transfer, tone_params, matrix, False)         # raises, naming the option
         raise ValueError(f"{path}: deinterlace={deinterlace!r} reads YUV4MPEG2 (with wide=True) or a headerless YUV file named by pix_fmt")
     if str(path).endswith(".npy"):
         if fps is None:

@@ -17,7 +17,8 @@ Frames that are still YUV 4:2:0 (ingest.Yuv420Frame, from a source's read_raw / 
 bytes per pixel, half the slab copy and half the PCIe bytes of a BGR frame — and converted to BGR by one kernel on the copy stream
 (vse_yuv420_to_bgr, or vse_yuv_to_bgr_matrix for frames that say matrix="bt709"), so a consumer sees the same uint8 [n,H,W,3] tensor
 either way.  Frames of any other format (ingest.YuvFrame: 10-bit, 4:2:2, 4:4:4, grey, full range, P010) go the same way through
-vse_yuv_to_bgr_format, keyed by shape, format and row parity.  Interlaced pictures (ingest.InterlacedYuvFrame) are uploaded as they are,
+vse_yuv_to_bgr_format, keyed by shape, format, row parity and tone map (frames with an ingest.ToneMap, HDR material, convert through
+vse_yuv_to_bgr_tonemap; the map's table is uploaded once per context).  Interlaced pictures (ingest.InterlacedYuvFrame) are uploaded as they are,
 each beside its previous picture unless that is the frame before it in the batch, deinterlaced on the device (vse_yuv_deinterlace) and
 converted by the same call as the others.
 """
@@ -126,15 +127,19 @@ class Uploader:
         return StagedBatch(dev, ev)
 
     def _stage_yuv(self, frames):
-        """ingest.YuvFrames of one shape, format and row parity -> StagedBatch of their BGR conversion: packed into the slab as they are
-        (3 bytes per pixel for 10-bit 4:2:0; frame stride rounded up to 16 bytes), one copy, one vse_yuv_to_bgr_format on the copy stream."""
+        """ingest.YuvFrames of one shape, format, row parity and tone map -> StagedBatch of their BGR conversion: packed into the slab as
+        they are (3 bytes per pixel for 10-bit 4:2:0; frame stride rounded up to 16 bytes), one copy, one vse_yuv_to_bgr_format (with a
+        tone map: vse_yuv_to_bgr_tonemap) on the copy stream."""
         import torch
         first = frames[0]
-        key = (tuple(first.shape), first.fmt, first.row_parity)
+
+        def key_of(f):
+            return (tuple(f.shape), getattr(f, "fmt", None), getattr(f, "row_parity", None), getattr(f, "tone", None))
+        key = key_of(first)
         for f in frames:
-            if (tuple(f.shape), getattr(f, "fmt", None), getattr(f, "row_parity", None)) != key:
-                raise ValueError("Uploader.stage: the YUV frames of a batch must share shape, format and row parity (y0 & sub_y): "
-                                 f"{key} and {(tuple(f.shape), getattr(f, 'fmt', None), getattr(f, 'row_parity', None))}")
+            if key_of(f) != key:
+                raise ValueError("Uploader.stage: the YUV frames of a batch must share shape, format, row parity (y0 & sub_y) and tone map: "
+                                 f"{key} and {key_of(f)}")
         ctx = self._context()
         n, (h, w, _) = len(frames), first.shape
         per = (first.packed_bytes + 15) & ~15
@@ -145,31 +150,31 @@ class Uploader:
         with torch.cuda.stream(self._stream):
             packed = torch.empty((n, per), dtype=torch.uint8, device=self.device)          # (dropped here: see _stage_yuv420)
             packed.copy_(host, non_blocking=True)
-            dev = ctx.yuv_to_bgr(packed, n, h, w, first.fmt, first.row_parity)
+            dev = ctx.yuv_to_bgr(packed, n, h, w, first.fmt, first.row_parity, tone=first.tone)
             ev = torch.cuda.Event()
             ev.record(self._stream)
         self._busy[k] = ev
         return StagedBatch(dev, ev)
 
     def _stage_interlaced(self, frames):
-        """ingest.InterlacedYuvFrames of one shape, format, first row, field order, mode and threshold -> StagedBatch of the BGR conversion
+        """ingest.InterlacedYuvFrames of one shape, format, first row, field order, mode, threshold and tone map -> StagedBatch of the BGR conversion
         of their deinterlaced rows.  Each frame's band() (the rows asked for, widened so that every plane starts on a top-field row and the
         band's edge rows are none of those asked for) is packed into one slot of the slab; a frame whose prev is the planes of the frame
         before it in the batch takes that frame's slot as its previous picture, any other frame with a prev packs it into the slot in
         front of its own.  One copy; then one vse_yuv_deinterlace per run of frames whose slots are laid out alike (frames without prev:
         NULL; chained frames: the slot before, stride of one slot; frames with their prev beside them: stride of two), one
-        vse_yuv_to_bgr_format over all the progressive bands, and the rows asked for cut out of it."""
+        vse_yuv_to_bgr_format (with a tone map: vse_yuv_to_bgr_tonemap) over all the progressive bands, and the rows asked for cut out of it."""
         import torch
         first = frames[0]
 
         def key_of(f):
             return (tuple(f.shape), getattr(f, "fmt", None), getattr(f, "y0", None), getattr(f, "height", None), getattr(f, "field_order", None),
-                    getattr(f, "mode", None), getattr(f, "thresh", None))
+                    getattr(f, "mode", None), getattr(f, "thresh", None), getattr(f, "tone", None))
         key = key_of(first)
         for f in frames:
             if not hasattr(f, "deinterlaced_planes") or key_of(f) != key:
                 raise ValueError("Uploader.stage: the interlaced YUV frames of a batch must share shape, format, first row, picture height, "
-                                 f"field order, mode and threshold: {key} and {key_of(f)}")
+                                 f"field order, mode, threshold and tone map: {key} and {key_of(f)}")
         from .ingest import _same_planes
         ctx = self._context()
         n, w = len(frames), first.width
@@ -205,7 +210,7 @@ class Uploader:
                 cur = packed[at:].as_strided((count, per), (step * per, 1))
                 ctx.yuv_deinterlace(cur, count, b - a, w, first.fmt, prev=None if kind == 0 else packed[at - 1], prev_stride=step * per,
                                     keep=first.keep, mode=first.mode, thresh=first.thresh, out=prog[i:i + count])
-            dev = ctx.yuv_to_bgr(prog, n, b - a, w, first.fmt, 0)
+            dev = ctx.yuv_to_bgr(prog, n, b - a, w, first.fmt, 0, tone=first.tone)
             if (first.y0 - a, first.y1 - a) != (0, b - a):
                 dev = dev[:, first.y0 - a:first.y1 - a].contiguous()
             ev = torch.cuda.Event()

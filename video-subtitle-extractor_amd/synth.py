@@ -180,6 +180,40 @@ def interlace_yuv420(field_rate_bgr, field_order="tff"):
     return out
 
 
+def hdr_grade(frames_bgr, white_nits=203.0, transfer="pq", depth=10, sub=(1, 1)):
+    """SDR frames (uint8 BGR [n, H, W, 3]) graded as HDR video -> n (Y, U, V) plane triples of BT.2020 non-constant-luminance limited-range
+    samples at `depth` bits (uint16; uint8 at depth 8), chroma subsampled by sub = (sub_x, sub_y) as the mean of each block.  The inverse
+    of what ingest.ToneMap undoes, in float64: BGR -> gamma 2.4 linear light -> BT.709 to BT.2020 primaries -> nits (SDR white at
+    white_nits) -> the PQ inverse EOTF, or the inverse of ingest.hlg_nits per channel.  For tests and benchmarks; nothing is specified
+    about its rounding."""
+    from . import ingest
+    if transfer not in ingest.TONE_TRANSFERS:
+        raise ValueError(f"transfer must be one of {ingest.TONE_TRANSFERS}, not {transfer!r}")
+    sub_x, sub_y = sub
+    to2020 = np.linalg.inv(ingest.bt2020_to_bt709())
+    kr, kb = 0.2627, 0.0593
+    kg = 1.0 - kr - kb
+    scale = float(1 << (depth - 8))
+    dtype = np.uint8 if depth == 8 else np.dtype("<u2")
+    out = []
+    for f in frames_bgr:
+        lin = np.power(np.asarray(f, np.float64)[..., ::-1] / 255.0, 2.4)                       # R G B
+        nits = np.clip(lin @ to2020.T, 0.0, None) * white_nits
+        e = ingest.pq_inverse_eotf(nits) if transfer == "pq" else ingest.hlg_inverse_nits(nits)
+        r, g, b = e[..., 0], e[..., 1], e[..., 2]
+        y = kr * r + kg * g + kb * b
+        h, w = y.shape
+        ch, cw = (h + sub_y) >> sub_y, (w + sub_x) >> sub_x
+
+        def mean(p):
+            q = np.pad(p, ((0, (ch << sub_y) - h), (0, (cw << sub_x) - w)), mode="edge")
+            return q.reshape(ch, 1 << sub_y, cw, 1 << sub_x).mean(axis=(1, 3))
+        planes = ((219.0 * y + 16.0) * scale, (224.0 * mean((b - y) / (2.0 * (1.0 - kb))) + 128.0) * scale,
+                  (224.0 * mean((r - y) / (2.0 * (1.0 - kr))) + 128.0) * scale)
+        out.append(tuple(np.clip(np.rint(p), 0, (1 << depth) - 1).astype(dtype) for p in planes))
+    return out
+
+
 def make_scenes(scenes, height=360, width=640, seed=0):
     """A clip of camera shots for the scene-cut finder: uint8 BGR [n,height,width,3] + the 0-based number of each scene's first frame.
 
