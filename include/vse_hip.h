@@ -786,6 +786,44 @@ int vse_yuv_deinterlace(vse_ctx* ctx, const void* d_yuv, const void* d_prev /* N
                         int thresh /* 8-bit levels, 0..255 */, int64_t yuv_frame_stride, int64_t prev_frame_stride, void* d_out,
                         int64_t out_frame_stride, void* stream);
 
+/* ---- frame ingest: film carried in interlaced video -> the film's pictures (field matching) ----------------------------------------- */
+/* Much interlaced material is progressive film whose fields were dealt into interlaced frames: 3:2 pulldown (NTSC DVDs, 480i, 1080i60),
+ * or fields shifted by one (mostly PAL).  Every picture of the film is still in the stream, whole; its second field merely sits in the
+ * neighbouring frame.  This call weaves each frame's fields with the partner that combs least and so gives the film's pictures back
+ * byte for byte, without a per-sample threshold; a frame that combs with every partner is video and gets vse_yuv_deinterlace's adaptive
+ * rule.  One output frame per input frame (the duplicate of a pulldown cycle stays in), no lookahead, no cadence, one choice per frame.
+ * Layouts, formats and `keep` are vse_yuv_deinterlace's.  Per frame, C the picture, P the previous one, R luma rows, w columns:
+ *   candidates   each a whole picture; every plane follows the same choice, row by row of that plane (row 0 of a plane is a top-field row)
+ *     choice 0  c    every row from C
+ *     choice 1  p1   rows of parity keep from C, the other rows from P     (the frame's first field with the previous frame's second)
+ *     choice 2  p2   rows of parity keep from P, the other rows from C     (the frame's second field with the previous frame's first)
+ *   comb count   on the luma plane of a candidate W alone, the samples as stored words: for every row 1 <= y <= R - 2 and every column
+ *                d1 = W[y] - W[y - 1], d2 = W[y] - W[y + 1];  combed iff (d1 > T and d2 > T) or (d1 < -T and d2 < -T)   (strict)
+ *                T = comb_thresh << (depth - 8), and << (16 - depth) more when msb = 1.  The count is the number of combed samples;
+ *                R < 3 counts 0 for every candidate.  |d| < 2^16 and T <= 255 << 8: int32 is exact; a count is at most 2^31 - 1.
+ *   choice       the smallest count; ties go to c, then p1, then p2.  d_prev NULL: only c exists.
+ *   fallback     when comb_limit >= 0 and best * 1000 > comb_limit * w * (R - 2), in 64 bits (best: the chosen candidate's count), the frame
+ *                is video: choice 3, and its output is exactly what vse_yuv_deinterlace makes of it in mode adaptive with the same keep
+ *                and `thresh` (d_prev NULL: every sample interpolated).  comb_limit < 0 never falls back.  (R = 1 makes the right side
+ *                negative: choice 3, whose output is C, as choice 0's.)
+ * comb_thresh 10 and comb_limit 20 per mille are the host's defaults; both are conventions and guesses, nothing is measured on real
+ * footage.  The counts are taken over the luma rows of the picture handed in: a caller that hands in a band of rows gets the band's choice.
+ * d_stats: uint32[n][4] on the device: the counts of c, p1 and p2 (0 for p1 and p2 with d_prev NULL) and the choice 0..3.
+ * Everything is enqueued on `stream`: the call zeroes d_stats itself, a count kernel reads the luma of C and P once (16-byte columns where
+ * the luma base, row bytes and the input strides are 16-byte aligned, 4 samples otherwise) and adds per-wave integer sums into d_stats
+ * with atomics, and a weave kernel, which derives the choice from the counts in every block, writes the pictures; each plane on its own
+ * takes 16-byte moves where its base and row bytes and all strides are 16-byte aligned (the 720-byte luma rows of a DVD do, its
+ * 360-byte chroma rows do not), dwords or single samples otherwise.  No allocation, no device sync; exactly the packed bytes of each
+ * picture and the 16 n bytes of d_stats are written; the inputs are only read.
+ * Returns VSE_E_INVAL, with the values in vse_last_error, and launches nothing, for everything vse_yuv_deinterlace refuses (it has no
+ * mode), a NULL d_stats or one that is not 4-byte aligned, comb_thresh outside 0..255, comb_limit above 1000, and a d_stats that overlaps
+ * the pictures (from the first byte of the first to the last byte of the last picture of d_yuv, d_prev or d_out). */
+int vse_yuv_field_match(vse_ctx* ctx, const void* d_yuv, const void* d_prev /* NULL: no frame has a previous picture */, int n, int h, int w,
+                        int sub_x, int sub_y, int chroma, int depth, int msb, int keep /* 0 | 1 */, int comb_thresh /* 8-bit levels, 0..255 */,
+                        int comb_limit /* per mille, < 0: never fall back */, int thresh /* the fallback's, 8-bit levels, 0..255 */,
+                        int64_t yuv_frame_stride, int64_t prev_frame_stride, void* d_out, int64_t out_frame_stride,
+                        void* d_stats /* device, uint32[n][4]: count c, p1, p2, choice 0..3 */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

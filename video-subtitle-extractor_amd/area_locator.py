@@ -337,6 +337,15 @@ def main(argv=None, cells_fn=None):
     p.add_argument("--range", default="auto", choices=("auto", "limited", "full"), help="--wide-yuv / --pix-fmt: the colour range [auto]")
     p.add_argument("--pix-fmt", default=None, metavar="NAME", help="pixel format of a headerless YUV file by FFmpeg's name (yuv420p10le, "
                    "p010le ...) [by extension]")
+    p.add_argument("--deinterlace", default=None, choices=("adaptive", "interpolate", "match"), help="interlaced YUV (Y4M with It / Ib, or a "
+                   "headerless file with --pix-fmt and --field-order): deinterlace on the GPU as the extractor does; match is for film "
+                   "carried in interlaced video (3:2 pulldown, shifted fields); turns --wide-yuv on [none]")
+    p.add_argument("--field-order", default="auto", choices=("auto", "tff", "bff"), help="--deinterlace: which field comes first [auto: the "
+                   "Y4M header's]")
+    p.add_argument("--deinterlace-thresh", type=int, default=10, metavar="N", help="--deinterlace adaptive: a sample that changed by more "
+                   "than N 8-bit levels since the previous frame has moved, 0..255 [10]")
+    from .extractor import add_match_arguments, match_arguments
+    add_match_arguments(p)
     p.add_argument("--transfer", default=None, choices=("pq", "hlg"), help="HDR video (needs --wide-yuv or --pix-fmt): undo PQ or HLG and "
                    "tone-map to SDR on the GPU [none]")
     p.add_argument("--white-nits", type=float, default=None, metavar="N", help="--transfer: the luminance that becomes SDR white [203]")
@@ -370,8 +379,13 @@ def main(argv=None, cells_fn=None):
                 raise ValueError(f"--size takes WIDTHxHEIGHT, not {args.size!r}")
             size = (int(w), int(h))
         from .extractor import tone_arguments
-        source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout, matrix=args.matrix, wide=args.wide_yuv,
-                                    range=args.range, pix_fmt=args.pix_fmt, **tone_arguments(args))
+        if args.deinterlace is None and (args.field_order != "auto" or args.deinterlace_thresh != 10):
+            raise ValueError("--field-order and --deinterlace-thresh belong to --deinterlace adaptive | interpolate | match")
+        fields = {} if args.deinterlace is None else dict(deinterlace=args.deinterlace, field_order=args.field_order,
+                                                          deinterlace_thresh=args.deinterlace_thresh)
+        source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout, matrix=args.matrix,
+                                    wide=args.wide_yuv or args.deinterlace is not None, range=args.range, pix_fmt=args.pix_fmt,
+                                    **fields, **match_arguments(args), **tone_arguments(args))
         loc = AreaLocator(cells_fn, probe=args.probe, edge_thresh=parse_edge_thresh(args.edge_thresh), automaton=args.locator_automaton,
                           hold_seconds=args.hold_seconds, hold_frames=args.hold_frames, max_hold_seconds=args.max_hold_seconds,
                           max_hold_frames=args.max_hold_frames)

@@ -56,6 +56,21 @@
 //            samples) and the choice a mask.  Needs every plane's base and row bytes and all frame strides 16-byte aligned.
 //   general  the same walk on 4 samples, any width and byte alignment (2-byte samples: 2-byte aligned): the aligned dwords that hold them,
 //            shifted into place, sample by sample at the end of a row; dword stores where they are aligned, else sample by sample.
+//
+// vse_yuv_field_match (include/vse_hip.h) stands in the deinterlacer's place for film carried in interlaced video (3:2 pulldown, fields
+// shifted by one): every picture of the film is still in the stream, its second field in the neighbouring frame.  Per frame three whole
+// pictures are candidates: the frame as stored (c), its first field with the previous frame's second (p1), its second field with the
+// previous frame's first (p2); the one whose luma combs least is copied out, and a frame whose best candidate still combs in more than
+// comb_limit per mille of its samples is video and gets the adaptive rule above (tests/field_match_ref.py restates it in int64).  Three
+// enqueues on the stream, no LDS, no scratch: a memset of the stats, then
+//   count    luma only, read once: the deinterlacer's walk (16-byte columns, or 4 samples where the luma rows are not 16-byte aligned)
+//            with rows y - 1, y, y + 1 of both pictures in registers and three comb tests per row (C alone; C between P's rows; P
+//            between C's rows, the last two booked to p1 or p2 by the row's parity); per-lane integer counts, a wave reduction by
+//            shuffles, one integer atomic per wave and candidate into the frame's stats.
+//   weave    every block reads its frame's three counts and derives the choice (uniform over the frame; one thread stores it); choices
+//            0 to 2 copy each row of each plane from C or P, choice 3 runs the deinterlacer's strip walk (deint_strip16 /
+//            deint_strip_quad, shared with its kernels).  The planes whose base and row bytes are 16-byte aligned go through one launch
+//            of 16-byte moves, the others (the 360-byte chroma rows of a DVD under its 720-byte luma rows) through one of quads.
 #include <algorithm>
 #include <cstdio>
 
@@ -556,8 +571,70 @@ __device__ __forceinline__ unsigned mean_word(unsigned a, unsigned b) {
     return (a | b) - (((a ^ b) >> 1) & (sizeof(S) == 1 ? 0x7f7f7f7fu : 0x7fff7fffu));
 }
 
-// Work item i of a picture = (plane, strip of DEINT_STRIP rows, 16-byte column), columns fastest: consecutive lanes take consecutive
-// columns, so a wave's loads and stores of a row are contiguous.  blockIdx.y strides the frames.  prev == nullptr: every sample moved.
+// Rows [y0, y1) of one 16-byte column of a plane of `rows` rows of rb bytes (s, q, d: the picture, its previous picture and the output,
+// at the column's first byte; adaptive false: q is not read, every sample moved), by the rule: the walk of the fast kernel, shared with the field
+// matcher's fallback (field_weave_fast_kernel).
+template <typename S>
+__device__ __forceinline__ void deint_strip16(const uint8_t* __restrict__ s, const uint8_t* __restrict__ q, uint8_t* __restrict__ d, long rb,
+                                              int rows, int y0, int y1, int keep, int T, bool adaptive) {
+    const auto load = [&](int y, uint4& c, uint4& m) {
+        c = *reinterpret_cast<const uint4*>(s + (long)y * rb);
+        if (adaptive) {
+            const uint4 p = *reinterpret_cast<const uint4*>(q + (long)y * rb);
+            m = make_uint4(moved_word<S>(c.x, p.x, T), moved_word<S>(c.y, p.y, T), moved_word<S>(c.z, p.z, T), moved_word<S>(c.w, p.w, T));
+        } else {
+            m = make_uint4(~0u, ~0u, ~0u, ~0u);
+        }
+    };
+    uint4 ca, ma, cc, mc, cb, mb;                 // the row above, the row itself, the row below, each with its mask
+    load(y0, cc, mc);
+    ca = cc;
+    ma = make_uint4(0u, 0u, 0u, 0u);
+    if (y0 > 0) load(y0 - 1, ca, ma);
+    for (int y = y0; y < y1; ++y) {
+        cb = cc;
+        mb = make_uint4(0u, 0u, 0u, 0u);
+        const bool below = y + 1 < rows;
+        if (below) load(y + 1, cb, mb);
+        uint4 o = cc;
+        if ((y & 1) != keep && rows > 1) {
+            const uint4 a = y > 0 ? ca : cb, b = below ? cb : ca;
+            const uint4 m = make_uint4(ma.x | mc.x | mb.x, ma.y | mc.y | mb.y, ma.z | mc.z | mb.z, ma.w | mc.w | mb.w);
+            o.x = (mean_word<S>(a.x, b.x) & m.x) | (cc.x & ~m.x);
+            o.y = (mean_word<S>(a.y, b.y) & m.y) | (cc.y & ~m.y);
+            o.z = (mean_word<S>(a.z, b.z) & m.z) | (cc.z & ~m.z);
+            o.w = (mean_word<S>(a.w, b.w) & m.w) | (cc.w & ~m.w);
+        }
+        *reinterpret_cast<uint4*>(d + (long)y * rb) = o;
+        ca = cc;
+        ma = mc;
+        cc = cb;
+        mc = mb;
+    }
+}
+
+// Work item i of the planes `pl` -> its plane's rows and row bytes, its strip's rows [y0, y1) and the byte offset of its 16-byte column
+// in the picture.  Item = (plane, strip of DEINT_STRIP rows, 16-byte column), columns fastest: consecutive lanes take consecutive columns,
+// so a wave's loads and stores of a row are contiguous.
+struct DeintItem {
+    long base, rb;
+    int rows, y0, y1;
+};
+
+__device__ __forceinline__ DeintItem deint_item(const DeintPlanes& pl, unsigned i) {
+    const bool p1 = i >= pl.first[1], p2 = i >= pl.first[2];
+    const unsigned j = i - (p2 ? pl.first[2] : p1 ? pl.first[1] : 0u);
+    DeintItem it;
+    it.rb = p2 ? pl.row[2] : p1 ? pl.row[1] : pl.row[0];
+    it.rows = p2 ? pl.rows[2] : p1 ? pl.rows[1] : pl.rows[0];
+    const unsigned cols = (unsigned)(it.rb >> 4), strip = j / cols, col = j - strip * cols;
+    it.base = (p2 ? pl.off[2] : p1 ? pl.off[1] : pl.off[0]) + 16L * col;
+    it.y0 = (int)strip * DEINT_STRIP;
+    it.y1 = min(it.y0 + DEINT_STRIP, it.rows);
+    return it;
+}
+
+// blockIdx.x strides the work items of a picture (deint_item), blockIdx.y the frames.  prev == nullptr: every sample moved.
 template <typename S>
 __global__ __launch_bounds__(FAST_THREADS) void deinterlace_fast_kernel(const uint8_t* __restrict__ src, const uint8_t* __restrict__ prev, int n,
                                                                         long sstride, long pstride, uint8_t* __restrict__ dst, long dstride,
@@ -569,47 +646,8 @@ __global__ __launch_bounds__(FAST_THREADS) void deinterlace_fast_kernel(const ui
         const uint8_t* q = adaptive ? prev + (long)f * pstride : nullptr;
         uint8_t* d = dst + (long)f * dstride;
         for (unsigned i = blockIdx.x * FAST_THREADS + threadIdx.x; i < items; i += gridDim.x * FAST_THREADS) {
-            const bool p1 = i >= pl.first[1], p2 = i >= pl.first[2];
-            const unsigned j = i - (p2 ? pl.first[2] : p1 ? pl.first[1] : 0u);
-            const long rb = p2 ? pl.row[2] : p1 ? pl.row[1] : pl.row[0];
-            const int rows = p2 ? pl.rows[2] : p1 ? pl.rows[1] : pl.rows[0];
-            const unsigned cols = (unsigned)(rb >> 4), strip = j / cols, col = j - strip * cols;
-            const long base = (p2 ? pl.off[2] : p1 ? pl.off[1] : pl.off[0]) + 16L * col;
-            const int y0 = (int)strip * DEINT_STRIP, y1 = min(y0 + DEINT_STRIP, rows);
-            const auto load = [&](int y, uint4& c, uint4& m) {
-                c = *reinterpret_cast<const uint4*>(s + base + (long)y * rb);
-                if (adaptive) {
-                    const uint4 p = *reinterpret_cast<const uint4*>(q + base + (long)y * rb);
-                    m = make_uint4(moved_word<S>(c.x, p.x, T), moved_word<S>(c.y, p.y, T), moved_word<S>(c.z, p.z, T), moved_word<S>(c.w, p.w, T));
-                } else {
-                    m = make_uint4(~0u, ~0u, ~0u, ~0u);
-                }
-            };
-            uint4 ca, ma, cc, mc, cb, mb;                 // the row above, the row itself, the row below, each with its mask
-            load(y0, cc, mc);
-            ca = cc;
-            ma = make_uint4(0u, 0u, 0u, 0u);
-            if (y0 > 0) load(y0 - 1, ca, ma);
-            for (int y = y0; y < y1; ++y) {
-                cb = cc;
-                mb = make_uint4(0u, 0u, 0u, 0u);
-                const bool below = y + 1 < rows;
-                if (below) load(y + 1, cb, mb);
-                uint4 o = cc;
-                if ((y & 1) != keep && rows > 1) {
-                    const uint4 a = y > 0 ? ca : cb, b = below ? cb : ca;
-                    const uint4 m = make_uint4(ma.x | mc.x | mb.x, ma.y | mc.y | mb.y, ma.z | mc.z | mb.z, ma.w | mc.w | mb.w);
-                    o.x = (mean_word<S>(a.x, b.x) & m.x) | (cc.x & ~m.x);
-                    o.y = (mean_word<S>(a.y, b.y) & m.y) | (cc.y & ~m.y);
-                    o.z = (mean_word<S>(a.z, b.z) & m.z) | (cc.z & ~m.z);
-                    o.w = (mean_word<S>(a.w, b.w) & m.w) | (cc.w & ~m.w);
-                }
-                *reinterpret_cast<uint4*>(d + base + (long)y * rb) = o;
-                ca = cc;
-                ma = mc;
-                cc = cb;
-                mc = mb;
-            }
+            const DeintItem it = deint_item(pl, i);
+            deint_strip16<S>(s + it.base, q + it.base, d + it.base, it.rb, it.rows, it.y0, it.y1, keep, T, adaptive);
         }
     }
 }
@@ -664,13 +702,57 @@ __device__ __forceinline__ void store_quad(S* p, const Quad<S>& q, int ns) {
     }
 }
 
+// deint_strip16 on quads: rows [y0, y1) of ns samples of a plane of `rows` rows of rl samples (s, q, d at the quad's first sample)
+template <typename S>
+__device__ __forceinline__ void deint_strip_quad(const S* __restrict__ s, const S* __restrict__ q, S* __restrict__ d, long rl, int rows, int ns,
+                                                 int y0, int y1, int keep, int T, bool adaptive) {
+    constexpr int DW = sizeof(S) == 1 ? 1 : 2;
+    const auto load = [&](int y, Quad<S>& c, Quad<S>& m) {
+        c = load_quad(s + (long)y * rl, ns);
+        if (adaptive) {
+            const Quad<S> pq = load_quad(q + (long)y * rl, ns);
+#pragma unroll
+            for (int k = 0; k < DW; ++k) m.v[k] = moved_word<S>(c.v[k], pq.v[k], T);
+        } else {
+#pragma unroll
+            for (int k = 0; k < DW; ++k) m.v[k] = ~0u;
+        }
+    };
+    Quad<S> ca, ma, cc, mc, cb, mb;           // the row above, the row itself, the row below, each with its mask
+    load(y0, cc, mc);
+    ca = cc;
+#pragma unroll
+    for (int k = 0; k < DW; ++k) ma.v[k] = 0u;
+    if (y0 > 0) load(y0 - 1, ca, ma);
+    for (int y = y0; y < y1; ++y) {
+        cb = cc;
+#pragma unroll
+        for (int k = 0; k < DW; ++k) mb.v[k] = 0u;
+        const bool below = y + 1 < rows;
+        if (below) load(y + 1, cb, mb);
+        Quad<S> o = cc;
+        if ((y & 1) != keep && rows > 1) {
+            const Quad<S> a = y > 0 ? ca : cb, b = below ? cb : ca;
+#pragma unroll
+            for (int k = 0; k < DW; ++k) {
+                const unsigned m = ma.v[k] | mc.v[k] | mb.v[k];
+                o.v[k] = (mean_word<S>(a.v[k], b.v[k]) & m) | (cc.v[k] & ~m);
+            }
+        }
+        store_quad(d + (long)y * rl, o, ns);
+        ca = cc;
+        ma = mc;
+        cc = cb;
+        mc = mb;
+    }
+}
+
 // The fast kernel's walk on quads: lane (threadIdx.x, threadIdx.y) = samples 4 xg .. 4 xg + 3 of a strip of DEINT_STRIP rows of each plane;
 // blockIdx.y strides the strips, blockIdx.z the frames.  Strides, offsets and rows are counted in samples.
 template <typename S>
 __global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void deinterlace_general_kernel(const S* __restrict__ src, const S* __restrict__ prev, int n,
                                                                                    long sstride, long pstride, S* __restrict__ dst, long dstride,
                                                                                    DeintPlanes pl, int keep, int T) {
-    constexpr int DW = sizeof(S) == 1 ? 1 : 2;
     const long x = 4L * (blockIdx.x * GEN_LANES + threadIdx.x);
     const bool adaptive = prev != nullptr;
     for (int f = blockIdx.z; f < n; f += gridDim.z) {
@@ -682,45 +764,225 @@ __global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void deinterlace_general_kern
             const S* s = src + (long)f * sstride + pl.off[p] + x;
             const S* q = adaptive ? prev + (long)f * pstride + pl.off[p] + x : nullptr;
             S* d = dst + (long)f * dstride + pl.off[p] + x;
-            const auto load = [&](int y, Quad<S>& c, Quad<S>& m) {
-                c = load_quad(s + (long)y * rl, ns);
-                if (adaptive) {
-                    const Quad<S> pq = load_quad(q + (long)y * rl, ns);
+            for (int y0 = (blockIdx.y * GEN_ROWS + threadIdx.y) * DEINT_STRIP; y0 < rows; y0 += gridDim.y * GEN_ROWS * DEINT_STRIP)
+                deint_strip_quad<S>(s, q, d, rl, rows, ns, y0, min(y0 + DEINT_STRIP, rows), keep, T, adaptive);
+        }
+    }
+}
+
+// ---- field matching (vse_yuv_field_match) ------------------------------------------------------------------------------------------
+// The comb test of include/vse_hip.h on every sample of a dword: m the row in the middle, a and b the rows above and below -> how many
+// samples stand out of both neighbours by more than T, the same way.
+template <typename S>
+__device__ __forceinline__ unsigned comb_word(unsigned m, unsigned a, unsigned b, int T) {
+    constexpr int BITS = 8 * sizeof(S), PER = 4 / sizeof(S);
+    constexpr unsigned ONES = (1u << BITS) - 1u;
+    unsigned count = 0;
 #pragma unroll
-                    for (int k = 0; k < DW; ++k) m.v[k] = moved_word<S>(c.v[k], pq.v[k], T);
-                } else {
+    for (int k = 0; k < PER; ++k) {
+        const int v = (int)((m >> (BITS * k)) & ONES);
+        const int d1 = v - (int)((a >> (BITS * k)) & ONES), d2 = v - (int)((b >> (BITS * k)) & ONES);
+        count += (min(d1, d2) > T || max(d1, d2) < -T) ? 1u : 0u;
+    }
+    return count;
+}
+
+template <typename S>
+__device__ __forceinline__ unsigned comb16(const uint4& m, const uint4& a, const uint4& b, int T) {
+    return comb_word<S>(m.x, a.x, b.x, T) + comb_word<S>(m.y, a.y, b.y, T) + comb_word<S>(m.z, a.z, b.z, T) + comb_word<S>(m.w, a.w, b.w, T);
+}
+
+// A wave's sums of the three counts -> one atomic per candidate into the frame's stats, from lane 0 (zeros add nothing and are skipped:
+// the call has zeroed the stats).  `lane`: the thread's index in its wave.
+__device__ __forceinline__ void add_counts(unsigned* stats, unsigned lane, unsigned c, unsigned p1, unsigned p2) {
 #pragma unroll
-                    for (int k = 0; k < DW; ++k) m.v[k] = ~0u;
+    for (int off = 32; off > 0; off >>= 1) {
+        c += __shfl_down(c, off, 64);
+        p1 += __shfl_down(p1, off, 64);
+        p2 += __shfl_down(p2, off, 64);
+    }
+    if (lane == 0) {
+        if (c) atomicAdd(stats + 0, c);
+        if (p1) atomicAdd(stats + 1, p1);
+        if (p2) atomicAdd(stats + 2, p2);
+    }
+}
+
+// The count over luma: item i of a frame = (strip of DEINT_STRIP rows, 16-byte column), columns fastest; a lane walks down its strip with
+// rows y - 1, y, y + 1 of the picture and of the previous one in registers and makes three tests per row: the picture alone (c), the
+// picture's row between the previous picture's (p1 on a row of parity keep, else p2), the previous picture's row between the picture's
+// (p2 on a row of parity keep, else p1).  Rows 0 and rows - 1 have one neighbour and are not tested.  prev == nullptr: c alone.
+template <typename S>
+__global__ __launch_bounds__(FAST_THREADS) void field_count_fast_kernel(const uint8_t* __restrict__ src, const uint8_t* __restrict__ prev, int n,
+                                                                        long sstride, long pstride, int rows, long rb, int keep, int T,
+                                                                        unsigned* __restrict__ stats) {
+    const bool pair = prev != nullptr;
+    const unsigned cols = (unsigned)(rb >> 4), items = cols * (unsigned)((rows + DEINT_STRIP - 1) / DEINT_STRIP);
+    for (int f = blockIdx.y; f < n; f += gridDim.y) {
+        const uint8_t* s = src + (long)f * sstride;
+        const uint8_t* q = pair ? prev + (long)f * pstride : nullptr;
+        unsigned nc = 0, n1 = 0, n2 = 0;
+        for (unsigned i = blockIdx.x * FAST_THREADS + threadIdx.x; i < items; i += gridDim.x * FAST_THREADS) {
+            const unsigned strip = i / cols, col = i - strip * cols;
+            const int y0 = max((int)strip * DEINT_STRIP, 1), y1 = min((int)strip * DEINT_STRIP + DEINT_STRIP, rows - 1);
+            if (y0 >= y1) continue;
+            const long base = 16L * col;
+            const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+            uint4 ca = *reinterpret_cast<const uint4*>(s + base + (long)(y0 - 1) * rb), cc = *reinterpret_cast<const uint4*>(s + base + (long)y0 * rb);
+            uint4 pa = zero, pc = zero, cb, pb = zero;
+            if (pair) {
+                pa = *reinterpret_cast<const uint4*>(q + base + (long)(y0 - 1) * rb);
+                pc = *reinterpret_cast<const uint4*>(q + base + (long)y0 * rb);
+            }
+            for (int y = y0; y < y1; ++y) {
+                cb = *reinterpret_cast<const uint4*>(s + base + (long)(y + 1) * rb);
+                nc += comb16<S>(cc, ca, cb, T);
+                if (pair) {
+                    pb = *reinterpret_cast<const uint4*>(q + base + (long)(y + 1) * rb);
+                    const unsigned cur_mid = comb16<S>(cc, pa, pb, T), prev_mid = comb16<S>(pc, ca, cb, T);
+                    const bool first = (y & 1) == keep;
+                    n1 += first ? cur_mid : prev_mid;
+                    n2 += first ? prev_mid : cur_mid;
                 }
-            };
-            for (int y0 = (blockIdx.y * GEN_ROWS + threadIdx.y) * DEINT_STRIP; y0 < rows; y0 += gridDim.y * GEN_ROWS * DEINT_STRIP) {
-                const int y1 = min(y0 + DEINT_STRIP, rows);
-                Quad<S> ca, ma, cc, mc, cb, mb;           // the row above, the row itself, the row below, each with its mask
-                load(y0, cc, mc);
                 ca = cc;
-#pragma unroll
-                for (int k = 0; k < DW; ++k) ma.v[k] = 0u;
-                if (y0 > 0) load(y0 - 1, ca, ma);
+                cc = cb;
+                pa = pc;
+                pc = pb;
+            }
+        }
+        add_counts(stats + 4L * f, threadIdx.x & 63u, nc, n1, n2);
+    }
+}
+
+// The same count on quads (any width and byte alignment): lane (threadIdx.x, threadIdx.y) = 4 samples of strips of DEINT_STRIP rows;
+// blockIdx.y strides the strips, blockIdx.z the frames; a block's row of 64 lanes is one wave.  Strides and rows are counted in samples.
+// Samples behind the end of a row are zero in every row (load_quad) and never comb.
+template <typename S>
+__global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void field_count_general_kernel(const S* __restrict__ src, const S* __restrict__ prev, int n,
+                                                                                   long sstride, long pstride, int rows, long rl, int keep, int T,
+                                                                                   unsigned* __restrict__ stats) {
+    constexpr int DW = sizeof(S) == 1 ? 1 : 2;
+    const long x = 4L * (blockIdx.x * GEN_LANES + threadIdx.x);
+    const bool pair = prev != nullptr;
+    for (int f = blockIdx.z; f < n; f += gridDim.z) {
+        unsigned nc = 0, n1 = 0, n2 = 0;
+        if (x < rl) {
+            const int ns = (int)min(4L, rl - x);
+            const S* s = src + (long)f * sstride + x;
+            const S* q = pair ? prev + (long)f * pstride + x : nullptr;
+            for (int t0 = (blockIdx.y * GEN_ROWS + threadIdx.y) * DEINT_STRIP; t0 < rows; t0 += gridDim.y * GEN_ROWS * DEINT_STRIP) {
+                const int y0 = max(t0, 1), y1 = min(t0 + DEINT_STRIP, rows - 1);
+                if (y0 >= y1) continue;
+                Quad<S> ca = load_quad(s + (long)(y0 - 1) * rl, ns), cc = load_quad(s + (long)y0 * rl, ns), cb, pa = {}, pc = {}, pb = {};
+                if (pair) {
+                    pa = load_quad(q + (long)(y0 - 1) * rl, ns);
+                    pc = load_quad(q + (long)y0 * rl, ns);
+                }
                 for (int y = y0; y < y1; ++y) {
-                    cb = cc;
+                    cb = load_quad(s + (long)(y + 1) * rl, ns);
+                    if (pair) pb = load_quad(q + (long)(y + 1) * rl, ns);
+                    unsigned cur_mid = 0, prev_mid = 0;
 #pragma unroll
-                    for (int k = 0; k < DW; ++k) mb.v[k] = 0u;
-                    const bool below = y + 1 < rows;
-                    if (below) load(y + 1, cb, mb);
-                    Quad<S> o = cc;
-                    if ((y & 1) != keep && rows > 1) {
-                        const Quad<S> a = y > 0 ? ca : cb, b = below ? cb : ca;
-#pragma unroll
-                        for (int k = 0; k < DW; ++k) {
-                            const unsigned m = ma.v[k] | mc.v[k] | mb.v[k];
-                            o.v[k] = (mean_word<S>(a.v[k], b.v[k]) & m) | (cc.v[k] & ~m);
+                    for (int k = 0; k < DW; ++k) {
+                        nc += comb_word<S>(cc.v[k], ca.v[k], cb.v[k], T);
+                        if (pair) {
+                            cur_mid += comb_word<S>(cc.v[k], pa.v[k], pb.v[k], T);
+                            prev_mid += comb_word<S>(pc.v[k], ca.v[k], cb.v[k], T);
                         }
                     }
-                    store_quad(d + (long)y * rl, o, ns);
+                    const bool first = (y & 1) == keep;
+                    n1 += first ? cur_mid : prev_mid;
+                    n2 += first ? prev_mid : cur_mid;
                     ca = cc;
-                    ma = mc;
                     cc = cb;
-                    mc = mb;
+                    pa = pc;
+                    pc = pb;
+                }
+            }
+        }
+        add_counts(stats + 4L * f, threadIdx.x, nc, n1, n2);
+    }
+}
+
+// What the weave kernels need beside the pictures: the fallback's bound (limit_on: comb_limit >= 0; bound = comb_limit * w * (R - 2)),
+// and whether this launch stores the choice (one of the launches of a call does: the one that holds the luma plane).
+struct MatchRule {
+    long bound;
+    int limit_on, store;
+};
+
+// The choice of include/vse_hip.h from a frame's three counts (wave-uniform: every lane reads the same three words).
+__device__ __forceinline__ int field_choice(const unsigned* stats, bool pair, const MatchRule& rule) {
+    const unsigned c = stats[0], p1 = stats[1], p2 = stats[2];
+    unsigned best = c;
+    int choice = 0;
+    if (pair && p1 < best) {
+        best = p1;
+        choice = 1;
+    }
+    if (pair && p2 < best) {
+        best = p2;
+        choice = 2;
+    }
+    return rule.limit_on && (long)best * 1000L > rule.bound ? 3 : choice;
+}
+
+// Whether row y of a plane comes from the picture (else from the previous one) under choice 0, 1 or 2
+__device__ __forceinline__ bool row_from_picture(int choice, int y, int keep) { return choice == 0 || ((y & 1) == keep) == (choice == 1); }
+
+// The weave of the planes `pl` (the ones whose base, row bytes and strides are 16-byte aligned; deint_item's work items): choice 0 to 2
+// copies each row from the picture or the previous one, choice 3 is the deinterlacer's adaptive rule.
+template <typename S>
+__global__ __launch_bounds__(FAST_THREADS) void field_weave_fast_kernel(const uint8_t* __restrict__ src, const uint8_t* __restrict__ prev, int n,
+                                                                        long sstride, long pstride, uint8_t* __restrict__ dst, long dstride,
+                                                                        DeintPlanes pl, int keep, int T, unsigned* stats, MatchRule rule) {
+    const bool pair = prev != nullptr;
+    const unsigned items = pl.first[3];
+    for (int f = blockIdx.y; f < n; f += gridDim.y) {
+        const uint8_t* s = src + (long)f * sstride;
+        const uint8_t* q = pair ? prev + (long)f * pstride : nullptr;
+        uint8_t* d = dst + (long)f * dstride;
+        const int choice = field_choice(stats + 4L * f, pair, rule);
+        if (rule.store && blockIdx.x == 0 && threadIdx.x == 0) stats[4L * f + 3] = (unsigned)choice;
+        for (unsigned i = blockIdx.x * FAST_THREADS + threadIdx.x; i < items; i += gridDim.x * FAST_THREADS) {
+            const DeintItem it = deint_item(pl, i);
+            if (choice == 3) {
+                deint_strip16<S>(s + it.base, q + it.base, d + it.base, it.rb, it.rows, it.y0, it.y1, keep, T, pair);
+            } else {
+                for (int y = it.y0; y < it.y1; ++y) {
+                    const uint8_t* from = row_from_picture(choice, y, keep) ? s : q;
+                    *reinterpret_cast<uint4*>(d + it.base + (long)y * it.rb) = *reinterpret_cast<const uint4*>(from + it.base + (long)y * it.rb);
+                }
+            }
+        }
+    }
+}
+
+// The weave of the other planes, on quads: dword moves where a quad's four samples exist and lie 4-byte aligned, else sample by sample.
+template <typename S>
+__global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void field_weave_general_kernel(const S* __restrict__ src, const S* __restrict__ prev, int n,
+                                                                                   long sstride, long pstride, S* __restrict__ dst, long dstride,
+                                                                                   DeintPlanes pl, int keep, int T, unsigned* stats, MatchRule rule) {
+    const long x = 4L * (blockIdx.x * GEN_LANES + threadIdx.x);
+    const bool pair = prev != nullptr;
+    for (int f = blockIdx.z; f < n; f += gridDim.z) {
+        const int choice = field_choice(stats + 4L * f, pair, rule);
+        if (rule.store && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && threadIdx.y == 0) stats[4L * f + 3] = (unsigned)choice;
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            if (p >= pl.count || x >= pl.row[p]) continue;
+            const long rl = pl.row[p];
+            const int rows = pl.rows[p], ns = (int)min(4L, rl - x);
+            const S* s = src + (long)f * sstride + pl.off[p] + x;
+            const S* q = pair ? prev + (long)f * pstride + pl.off[p] + x : nullptr;
+            S* d = dst + (long)f * dstride + pl.off[p] + x;
+            for (int y0 = (blockIdx.y * GEN_ROWS + threadIdx.y) * DEINT_STRIP; y0 < rows; y0 += gridDim.y * GEN_ROWS * DEINT_STRIP) {
+                const int y1 = min(y0 + DEINT_STRIP, rows);
+                if (choice == 3) {
+                    deint_strip_quad<S>(s, q, d, rl, rows, ns, y0, y1, keep, T, pair);
+                } else {
+                    for (int y = y0; y < y1; ++y)
+                        store_quad(d + (long)y * rl, load_quad((row_from_picture(choice, y, keep) ? s : q) + (long)y * rl, ns), ns);
                 }
             }
         }
@@ -928,6 +1190,132 @@ int vse_yuv_deinterlace(vse_ctx* c, const void* d_yuv, const void* d_prev, int n
     }
     if (hipGetLastError() != hipSuccess) {
         vse_set_error("vse_yuv_deinterlace: launch failed");
+        return VSE_E_HIP;
+    }
+    return VSE_OK;
+}
+
+int vse_yuv_field_match(vse_ctx* c, const void* d_yuv, const void* d_prev, int n, int h, int w, int sub_x, int sub_y, int chroma, int depth,
+                        int msb, int keep, int comb_thresh, int comb_limit, int thresh, int64_t yuv_frame_stride, int64_t prev_frame_stride,
+                        void* d_out, int64_t out_frame_stride, void* d_stats, void* stream) {
+    const size_t frame = vse_yuv_frame_bytes(h, w, sub_x, sub_y, chroma, depth, 0);
+    const int ss = depth > 8 ? 2 : 1;
+    const auto odd = [](const void* p, int64_t stride) { return (reinterpret_cast<uintptr_t>(p) & 1) || (stride & 1); };
+    bool ok = c && d_yuv && d_out && d_stats && n >= 1 && frame && msb >= 0 && msb <= (ss == 2 ? 1 : 0) && keep >= 0 && keep <= 1 &&
+              comb_thresh >= 0 && comb_thresh <= 255 && comb_limit <= 1000 && thresh >= 0 && thresh <= 255 &&
+              (reinterpret_cast<uintptr_t>(d_stats) & 3) == 0 && yuv_frame_stride >= (int64_t)frame && out_frame_stride >= (int64_t)frame &&
+              (!d_prev || prev_frame_stride >= (int64_t)frame) && d_out != d_yuv && d_out != d_prev &&
+              !(ss == 2 && (odd(d_yuv, yuv_frame_stride) || odd(d_out, out_frame_stride) || (d_prev && odd(d_prev, prev_frame_stride))));
+    if (ok) {
+        // the stats lie apart from every picture: from the first byte of a run's first picture to the last byte of its last one
+        const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_stats), s1 = s0 + 16 * (uintptr_t)n;
+        const auto apart = [&](const void* p, int64_t stride) {
+            const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = a + (uintptr_t)(n - 1) * (uintptr_t)stride + frame;
+            return !p || s1 <= a || b <= s0;
+        };
+        ok = apart(d_yuv, yuv_frame_stride) && apart(d_prev, prev_frame_stride) && apart(d_out, out_frame_stride);
+    }
+    if (!ok) {
+        char msg[720];
+        snprintf(msg, sizeof msg, "vse_yuv_field_match: bad arguments (n %d, frame %d x %d of at most 2^31 - 1 pixels, subsampling %d, %d of 0, 0 | "
+                 "1, 0 | 1, 1, chroma %d of 0 (with subsampling 0, 0) | 1 | 2 (with subsampling 1, 1), depth %d of 8..16, msb %d of 0 | 1 (0 at "
+                 "depth 8), keep %d of 0 | 1, comb_thresh %d of 0..255, comb_limit %d of at most 1000, thresh %d of 0..255, frame strides %lld, "
+                 "%lld (previous pictures) and %lld (output) of at least %zu, bases %p, %p, %p and strides 2-byte aligned for 2-byte samples, "
+                 "the output none of the inputs, stats %p 4-byte aligned and apart from the pictures)",
+                 n, h, w, sub_x, sub_y, chroma, depth, msb, keep, comb_thresh, comb_limit, thresh, (long long)yuv_frame_stride,
+                 (long long)prev_frame_stride, (long long)out_frame_stride, frame, d_yuv, d_prev, d_out, d_stats);
+        vse_set_error(msg);
+        return VSE_E_INVAL;
+    }
+    const long cw = ((long)w + sub_x) >> sub_x, ch = (((long)h - 1) >> sub_y) + 1, luma = (long)h * w;
+    const int count = chroma == CHROMA_NONE ? 1 : chroma == CHROMA_PLANAR ? 3 : 2;
+    int rows[3] = {h, (int)ch, (int)ch};
+    long off[3] = {0, luma, luma + ch * cw}, row[3] = {w, chroma == CHROMA_SEMI ? 2 * cw : cw, cw};          // in samples
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_yuv);
+    const uint8_t* prev = reinterpret_cast<const uint8_t*>(d_prev);
+    uint8_t* dst = reinterpret_cast<uint8_t*>(d_out);
+    unsigned* stats = reinterpret_cast<unsigned*>(d_stats);
+    const int up = depth - 8 + (msb ? 16 - depth : 0);
+    const int comb_t = comb_thresh << up, T = thresh << up;
+    if (hipMemsetAsync(d_stats, 0, 16 * (size_t)n, st) != hipSuccess) {
+        vse_set_error("vse_yuv_field_match: clearing the stats failed");
+        return VSE_E_HIP;
+    }
+    // ---- the count, over luma: 16-byte columns where the inputs allow them
+    const bool in16 = aligned16(src) && yuv_frame_stride % 16 == 0 && (!prev || (aligned16(prev) && prev_frame_stride % 16 == 0));
+    if (h >= 3) {
+        const int strips = (h + DEINT_STRIP - 1) / DEINT_STRIP;
+        if (in16 && ((long)w * ss) % 16 == 0) {
+            const long items = ((long)w * ss / 16) * strips;
+            const dim3 grid((unsigned)std::min<long>((items + FAST_THREADS - 1) / FAST_THREADS, FAST_MAX_BLOCKS), (unsigned)std::min(n, 65535));
+            const auto kernel = ss == 1 ? field_count_fast_kernel<uint8_t> : field_count_fast_kernel<uint16_t>;
+            hipLaunchKernelGGL(kernel, grid, dim3(FAST_THREADS), 0, st, src, prev, n, (long)yuv_frame_stride, (long)prev_frame_stride, h,
+                               (long)w * ss, keep, comb_t, stats);
+        } else {
+            const long groups = ((long)w + 3) / 4;
+            const dim3 grid((unsigned)((groups + GEN_LANES - 1) / GEN_LANES), (unsigned)std::min((strips + GEN_ROWS - 1) / GEN_ROWS, 65535),
+                            (unsigned)std::min(n, 65535));
+            const dim3 block(GEN_LANES, GEN_ROWS);
+            if (ss == 1) {
+                hipLaunchKernelGGL(field_count_general_kernel<uint8_t>, grid, block, 0, st, src, prev, n, (long)yuv_frame_stride,
+                                   (long)prev_frame_stride, h, (long)w, keep, comb_t, stats);
+            } else {
+                hipLaunchKernelGGL(field_count_general_kernel<uint16_t>, grid, block, 0, st, reinterpret_cast<const uint16_t*>(src),
+                                   reinterpret_cast<const uint16_t*>(prev), n, (long)yuv_frame_stride / 2, (long)prev_frame_stride / 2, h, (long)w,
+                                   keep, comb_t, stats);
+            }
+        }
+    }
+    // ---- the weave: every plane on its own takes 16-byte moves where its base and row bytes allow them, quads otherwise
+    const bool all16 = in16 && aligned16(dst) && out_frame_stride % 16 == 0;
+    DeintPlanes fast = {}, gen = {};
+    MatchRule fast_rule = {(long)comb_limit * w * ((long)h - 2), comb_limit >= 0 ? 1 : 0, 0}, gen_rule = fast_rule;
+    long items = 0, gen_row = 0;
+    int gen_rows = 0;
+    for (int p = 0; p < count; ++p) {
+        if (all16 && (off[p] * ss) % 16 == 0 && (row[p] * ss) % 16 == 0) {
+            const int k = fast.count++;
+            fast.rows[k] = rows[p];
+            fast.off[k] = off[p] * ss;
+            fast.row[k] = row[p] * ss;
+            fast.first[k] = (unsigned)items;
+            items += (fast.row[k] / 16) * ((rows[p] + DEINT_STRIP - 1) / DEINT_STRIP);
+            if (p == 0) fast_rule.store = 1;
+        } else {
+            const int k = gen.count++;
+            gen.rows[k] = rows[p];
+            gen.off[k] = off[p];
+            gen.row[k] = row[p];
+            gen_row = std::max(gen_row, row[p]);
+            gen_rows = std::max(gen_rows, rows[p]);
+            if (p == 0) gen_rule.store = 1;
+        }
+    }
+    for (int k = fast.count; k < 4; ++k) fast.first[k] = (unsigned)items;
+    if (fast.count) {
+        const dim3 grid((unsigned)std::min<long>((items + FAST_THREADS - 1) / FAST_THREADS, FAST_MAX_BLOCKS), (unsigned)std::min(n, 65535));
+        const auto kernel = ss == 1 ? field_weave_fast_kernel<uint8_t> : field_weave_fast_kernel<uint16_t>;
+        hipLaunchKernelGGL(kernel, grid, dim3(FAST_THREADS), 0, st, src, prev, n, (long)yuv_frame_stride, (long)prev_frame_stride, dst,
+                           (long)out_frame_stride, fast, keep, T, stats, fast_rule);
+    }
+    if (gen.count) {
+        const long groups = (gen_row + 3) / 4;
+        const int strips = (gen_rows + DEINT_STRIP - 1) / DEINT_STRIP;
+        const dim3 grid((unsigned)((groups + GEN_LANES - 1) / GEN_LANES), (unsigned)std::min((strips + GEN_ROWS - 1) / GEN_ROWS, 65535),
+                        (unsigned)std::min(n, 65535));
+        const dim3 block(GEN_LANES, GEN_ROWS);
+        if (ss == 1) {
+            hipLaunchKernelGGL(field_weave_general_kernel<uint8_t>, grid, block, 0, st, src, prev, n, (long)yuv_frame_stride,
+                               (long)prev_frame_stride, dst, (long)out_frame_stride, gen, keep, T, stats, gen_rule);
+        } else {
+            hipLaunchKernelGGL(field_weave_general_kernel<uint16_t>, grid, block, 0, st, reinterpret_cast<const uint16_t*>(src),
+                               reinterpret_cast<const uint16_t*>(prev), n, (long)yuv_frame_stride / 2, (long)prev_frame_stride / 2,
+                               reinterpret_cast<uint16_t*>(dst), (long)out_frame_stride / 2, gen, keep, T, stats, gen_rule);
+        }
+    }
+    if (hipGetLastError() != hipSuccess) {
+        vse_set_error("vse_yuv_field_match: launch failed");
         return VSE_E_HIP;
     }
     return VSE_OK;

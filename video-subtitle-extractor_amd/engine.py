@@ -32,7 +32,7 @@ EXPORTS = [
     "vse_frame_hold_bounded_state_bytes", "vse_frame_hold_bounded",
     "vse_frame_cells_hold_bounded_state_bytes", "vse_frame_cells_hold_bounded",
     "vse_interval_stream_state_bytes", "vse_interval_stream",
-    "vse_yuv_frame_bytes", "vse_yuv_to_bgr_format", "vse_yuv_deinterlace",
+    "vse_yuv_frame_bytes", "vse_yuv_to_bgr_format", "vse_yuv_deinterlace", "vse_yuv_field_match",
     "vse_yuv_tonemap_table_bytes", "vse_yuv_to_bgr_tonemap",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
@@ -247,6 +247,8 @@ def load_library(path=None):
     lib.vse_yuv_tonemap_table_bytes.argtypes = []
     lib.vse_yuv_to_bgr_tonemap.argtypes = lib.vse_yuv_to_bgr_format.argtypes[:-1] + [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
     lib.vse_yuv_deinterlace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 11 + [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.vse_yuv_field_match.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 12 + [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                                                                                 C.c_void_p]
     if lib.vse_sizeof_op() != ir.OP_DT.itemsize or lib.vse_sizeof_view() != ir.VIEW_DT.itemsize:
         raise VseError(f"ABI mismatch: vse_op {lib.vse_sizeof_op()} vs {ir.OP_DT.itemsize}, "
                        f"vse_view {lib.vse_sizeof_view()} vs {ir.VIEW_DT.itemsize}")
@@ -1049,6 +1051,43 @@ class Context:
                                             int(fmt.chroma), int(fmt.depth), int(fmt.msb), int(keep), mode, int(thresh), sstride, pstride,
                                             C.c_void_p(out.data_ptr()), ostride, self.stream()), "vse_yuv_deinterlace")
         return out
+
+    def yuv_field_match(self, packed, n, h, w, fmt, prev=None, prev_stride=None, keep=0, comb_thresh=10, comb_limit=20, thresh=10, out=None,
+                        stats=None):
+        """yuv_deinterlace's arguments and layouts -> (cuda uint8 [n, stride] of the field-matched pictures, cuda int32 [n, 4] of each
+        frame's comb counts of the candidates c, p1, p2 and its choice 0..3), on the current stream (include/vse_hip.h vse_yuv_field_match):
+        each frame is woven from its own fields or with a field of the previous picture, whichever combs least; a frame that combs by
+        more than comb_limit per mille (None: never) of its luma samples with every partner gets the adaptive rule with `thresh`.
+        prev None: no frame has a previous picture.  stats: write into this int32 [n, 4] tensor instead (the uint32 words of the device)."""
+        t = self.torch
+        n, h, w = int(n), int(h), int(w)
+        frame = self.lib.vse_yuv_frame_bytes(h, w, int(fmt.sub_x), int(fmt.sub_y), int(fmt.chroma), int(fmt.depth), 0)
+
+        def stride_of(a, what):
+            assert a.dtype == t.uint8 and a.dim() in (1, 2) and a.stride(-1) == 1, what
+            if a.dim() == 2:
+                assert a.shape[0] == n and a.shape[1] >= frame, (what, tuple(a.shape), n, frame)
+                return a.stride(0) if n > 1 else max(a.stride(0), frame)
+            assert a.numel() >= n * frame, (what, a.numel(), n, frame)
+            return frame
+        sstride = stride_of(packed, "packed")
+        if out is None:
+            out = t.empty((max(n, 0), (frame + 15) & ~15), dtype=t.uint8, device=self.tdev)
+        ostride = stride_of(out, "out")
+        if stats is None:
+            stats = t.empty((max(n, 0), 4), dtype=t.int32, device=self.tdev)
+        assert stats.dtype == t.int32 and tuple(stats.shape) == (n, 4) and stats.is_contiguous()
+        pptr, pstride = None, 0
+        if prev is not None:
+            assert prev.dtype == t.uint8 and prev.stride(-1) == 1
+            pptr = C.c_void_p(prev.data_ptr())
+            pstride = int(prev_stride) if prev_stride is not None else (prev.stride(0) if prev.dim() == 2 and n > 1 else sstride)
+        _check(self.lib.vse_yuv_field_match(self.handle, C.c_void_p(packed.data_ptr()), pptr, n, h, w, int(fmt.sub_x), int(fmt.sub_y),
+                                            int(fmt.chroma), int(fmt.depth), int(fmt.msb), int(keep), int(comb_thresh),
+                                            -1 if comb_limit is None else int(comb_limit), int(thresh), sstride, pstride,
+                                            C.c_void_p(out.data_ptr()), ostride, C.c_void_p(stats.data_ptr()), self.stream()),
+               "vse_yuv_field_match")
+        return out, stats
 
 
 YUV_LAYOUTS = {"i420": 0, "nv12": 1}

@@ -730,6 +730,32 @@ def tone_arguments(args):
     return {"transfer": args.transfer, "tone_params": params or None}
 
 
+def add_match_arguments(p):
+    """--comb-thresh and --comb-limit of `--deinterlace match`, for the command lines that take it."""
+    p.add_argument("--comb-thresh", type=int, default=None, metavar="N", help="--deinterlace match: a luma sample that stands out of the "
+                   "rows above and below it by more than N 8-bit levels, the same way, is combed, 0..255 [10]")
+    p.add_argument("--comb-limit", default=None, metavar="N|off", help="--deinterlace match: a frame whose best weave still has more than "
+                   "N per mille of its luma samples combed is video and gets the adaptive rule, 0..1000; off: never [20]")
+
+
+def match_arguments(args):
+    """--comb-thresh and --comb-limit of a parsed command line -> the keywords ingest.open_source takes for them."""
+    if args.comb_thresh is None and args.comb_limit is None:
+        return {}
+    if args.deinterlace != "match":
+        raise ValueError("--comb-thresh and --comb-limit belong to --deinterlace match")
+    out = {}
+    if args.comb_thresh is not None:
+        if not 0 <= args.comb_thresh <= 255:
+            raise ValueError(f"--comb-thresh takes 0..255 (8-bit levels), not {args.comb_thresh}")
+        out["comb_thresh"] = args.comb_thresh
+    if args.comb_limit is not None:
+        if args.comb_limit != "off" and not (args.comb_limit.isdigit() and int(args.comb_limit) <= 1000):
+            raise ValueError(f"--comb-limit takes 0..1000 (per mille) or off, not {args.comb_limit!r}")
+        out["comb_limit"] = None if args.comb_limit == "off" else int(args.comb_limit)
+    return out
+
+
 def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, focus_fn=None, stream_fn=None):
     """ocr: the recogniser (None: shim.OcrRecogniser on the GPU, frames staged through staging.default_uploader, YUV 4:2:0 converted
     on the device); counter: the change / hold selector's count_fn (None: the GPU's); cells_fn: the locator's (None: the GPU's);
@@ -753,13 +779,16 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
                    "the Y4M header's XCOLORRANGE or the pixel format's own, else limited]")
     p.add_argument("--pix-fmt", default=None, metavar="NAME", help="pixel format of a headerless YUV file by FFmpeg's name (yuv420p10le, "
                    "yuv422p, yuv444p, gray, p010le, yuvj420p ...) [by extension; .p010 is p010le]")
-    p.add_argument("--deinterlace", default=None, choices=("adaptive", "interpolate"), help="interlaced YUV (576i / 480i / 1080i: Y4M with "
-                   "It / Ib, or a headerless file with --pix-fmt and --field-order): deinterlace on the GPU, weaving what stood still "
-                   "(adaptive) or interpolating the second field throughout; turns --wide-yuv on")
+    p.add_argument("--deinterlace", default=None, choices=("adaptive", "interpolate", "match"), help="interlaced YUV (576i / 480i / 1080i: "
+                   "Y4M with It / Ib, or a headerless file with --pix-fmt and --field-order): deinterlace on the GPU, weaving what stood still "
+                   "(adaptive), interpolating the second field throughout, or, for film carried in interlaced video (3:2 pulldown, shifted "
+                   "fields), weaving each frame with the partner field that combs least (match: the film's own pictures; a frame that "
+                   "combs with every partner gets adaptive); turns --wide-yuv on")
     p.add_argument("--field-order", default="auto", choices=("auto", "tff", "bff"), help="--deinterlace: which field comes first [auto: the "
                    "Y4M header's It / Ib; Ip is then left as it is]; tff / bff override the header")
     p.add_argument("--deinterlace-thresh", type=int, default=10, metavar="N", help="--deinterlace adaptive: a sample that changed by more "
                    "than N 8-bit levels since the previous frame has moved, 0..255 [10]")
+    add_match_arguments(p)
     p.add_argument("--transfer", default=None, choices=("pq", "hlg"), help="HDR video (needs --wide-yuv or --pix-fmt, normally with --matrix "
                    "bt2020): undo PQ (UHD Blu-ray, streaming masters) or HLG (UHD broadcast) and tone-map to SDR on the GPU; Y4M carries no tag "
                    "for it [none: the samples are taken as SDR and HDR material comes out flat]")
@@ -836,11 +865,11 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
                                  "compositor's own pass and would not be called")
             composite_params = {"streaming": True, **({} if stream_fn is None else {"stream_fn": stream_fn})}
         if args.deinterlace is None and (args.field_order != "auto" or args.deinterlace_thresh != 10):
-            raise ValueError("--field-order and --deinterlace-thresh belong to --deinterlace adaptive | interpolate")
+            raise ValueError("--field-order and --deinterlace-thresh belong to --deinterlace adaptive | interpolate | match")
         source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout, matrix=args.matrix,
                                     wide=args.wide_yuv or args.deinterlace is not None, range=args.range, pix_fmt=args.pix_fmt,
                                     deinterlace=args.deinterlace, field_order=args.field_order, deinterlace_thresh=args.deinterlace_thresh,
-                                    **tone_arguments(args))
+                                    **match_arguments(args), **tone_arguments(args))
         uploader = None
         if ocr is None:
             if args.weights_dir is not None:

@@ -35,7 +35,10 @@ relative to SDR white, BT.2020 to BT.709 in linear light, the output gamma.  Y4M
 Interlaced video (InterlacedYuvFrame; deinterlace="adaptive" | "interpolate" on those readers, on top of wide=True): the pictures are two
 woven fields.  A frame carries the previous picture's planes beside its own; to_bgr() and the device (vse_yuv_deinterlace, through
 staging.Uploader) keep the first field's rows, weave what did not change since the previous picture and interpolate the rest, by the same
-integers.  Without the keyword interlaced headers are refused as before.
+integers.  Without the keyword interlaced headers are refused as before.  deinterlace="match" is for film carried in interlaced video
+(3:2 pulldown, fields shifted by one): every picture of the film is still in the stream, its second field in the neighbouring frame, and
+each frame is woven whole with the partner field that combs least (vse_yuv_field_match), which gives the film's pictures back byte for
+byte; a frame that combs with every partner falls back to the adaptive rule.  Frame count and times stay one to one.
 
 Pipes (Y4mStream): `ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m vse_amd.extractor -` puts compressed video of any
 codec through a decoder that is not ours; the stream is read once, front to back, never seeks and has no read(): its absence is how
@@ -714,8 +717,53 @@ def _rows_to_bgr(fmt, luma, chroma, rows, width, tone=None):
 
 
 # ---- interlaced pictures (vse_yuv_deinterlace) ----------------------------------------------------------------------------------------
-DEINTERLACE_MODES = ("adaptive", "interpolate")
+DEINTERLACE_MODES = ("adaptive", "interpolate", "match")
 FIELD_ORDERS = ("tff", "bff")
+MATCH_CHOICES = ("c", "p1", "p2", "adaptive")          # vse_yuv_field_match's choices 0..3
+
+
+def _check_match(comb_thresh, comb_limit):
+    """mode "match"'s comb threshold (8-bit levels) and fallback limit (per mille of the luma samples tested; None: never fall back)
+    -> (comb_thresh, comb_limit) as integers."""
+    if isinstance(comb_thresh, bool) or not isinstance(comb_thresh, (int, np.integer)) or not 0 <= comb_thresh <= 255:
+        raise ValueError(f"the comb threshold is an integer of 0..255 (8-bit levels), not {comb_thresh!r}")
+    if comb_limit is not None and (isinstance(comb_limit, bool) or not isinstance(comb_limit, (int, np.integer)) or not 0 <= comb_limit <= 1000):
+        raise ValueError(f"the comb limit is None or an integer of 0..1000 (per mille), not {comb_limit!r}")
+    return int(comb_thresh), None if comb_limit is None else int(comb_limit)
+
+
+def comb_count(mid, above, below, t):
+    """How many samples of the rows `mid` stand out of the rows above and below them by more than t, the same way (int64 arrays of one
+    shape): the comb test of include/vse_hip.h vse_yuv_field_match."""
+    d1, d2 = mid - above, mid - below
+    return int(np.count_nonzero(((d1 > t) & (d2 > t)) | ((d1 < -t) & (d2 < -t))))
+
+
+def field_match_counts(cur, prev, keep, t):
+    """The comb counts (c, p1, p2) of vse_yuv_field_match's three candidates over the luma rows `cur` of a picture (or band) and `prev` of
+    the previous one (None: (c, 0, 0)), whose row 0 is a top-field row; t in word units."""
+    rows = cur.shape[0]
+    if rows < 3:
+        return 0, 0, 0
+    c = np.asarray(cur).astype(np.int64)
+    counts = [comb_count(c[1:-1], c[:-2], c[2:], t), 0, 0]
+    if prev is not None:
+        p = np.asarray(prev).astype(np.int64)
+        first = (np.arange(rows) & 1) == keep                  # the rows of the field first in time
+        for k, own in ((1, first), (2, ~first)):               # p1: those rows from the picture; p2: the other rows
+            w = np.where(own[:, None], c, p)
+            counts[k] = comb_count(w[1:-1], w[:-2], w[2:], t)
+    return tuple(counts)
+
+
+def field_match_choice(counts, rows, width, comb_limit, paired=True):
+    """vse_yuv_field_match's choice 0..3 from the three counts: the smallest (ties: c, p1, p2; without a previous picture only c), or 3
+    where it exceeds comb_limit per mille of width * (rows - 2) samples (None: never)."""
+    best, choice = counts[0], 0
+    for k in ((1, 2) if paired else ()):
+        if counts[k] < best:
+            best, choice = counts[k], k
+    return 3 if comb_limit is not None and best * 1000 > comb_limit * width * (rows - 2) else choice
 
 
 def _check_deinterlace(deinterlace, field_order, thresh, orders=("auto",) + FIELD_ORDERS):
@@ -757,11 +805,20 @@ class InterlacedYuvFrame(YuvFrame):
     plane tuple of the previous picture (None: the clip's first frame, interpolated throughout).  field_order "tff" | "bff" names the field
     that comes first in time (its rows are kept), mode is "adaptive" (weave what did not change by more than `thresh` 8-bit levels) or
     "interpolate".  frame[a:b] is the same class with the same prev; to_bgr() deinterlaces on the host by the same integers and converts
-    as YuvFrame does, so f[a:b].to_bgr() == f.to_bgr()[a:b]; staging.Uploader deinterlaces and converts on the device."""
+    as YuvFrame does, so f[a:b].to_bgr() == f.to_bgr()[a:b]; staging.Uploader deinterlaces and converts on the device.
+    mode "match" (film carried in interlaced video: 3:2 pulldown, shifted fields) follows vse_yuv_field_match instead: the whole frame is
+    woven from its own fields or with a field of prev, whichever combs least by `comb_thresh` 8-bit levels (match_stats()), and a frame
+    that combs by more than `comb_limit` per mille (None: never) with every partner is video and gets the adaptive rule with `thresh`.
+    The counts are taken over the luma rows of band(), which is what the device is handed, so the host and the device agree; a slice may
+    therefore choose differently from the whole frame, and f[a:b].to_bgr() == f.to_bgr()[a:b] is promised only where both make the same
+    choice (always in a static band, where the candidates are equal)."""
 
-    def __init__(self, planes, height, width, fmt, prev=None, field_order="tff", mode="adaptive", thresh=10, y0=0, y1=None, tone=None):
+    def __init__(self, planes, height, width, fmt, prev=None, field_order="tff", mode="adaptive", thresh=10, y0=0, y1=None, tone=None,
+                 comb_thresh=10, comb_limit=20):
         super().__init__(planes, height, width, fmt, y0, y1, tone)
         self.thresh = _check_deinterlace(mode, field_order, thresh, FIELD_ORDERS)
+        self.comb_thresh, self.comb_limit = _check_match(comb_thresh, comb_limit)
+        self._stats = None
         if mode is None:
             raise ValueError(f"mode must be one of {DEINTERLACE_MODES}, not None")
         self.field_order, self.mode = field_order, mode
@@ -786,9 +843,28 @@ class InterlacedYuvFrame(YuvFrame):
         if step != 1:
             raise TypeError(f"an InterlacedYuvFrame takes a row slice of step 1, not {idx!r}")
         return InterlacedYuvFrame(self.planes, self.height, self.width, self.fmt, self.prev, self.field_order, self.mode, self.thresh,
-                                  self.y0 + a, self.y0 + max(a, b), self.tone)
+                                  self.y0 + a, self.y0 + max(a, b), self.tone, self.comb_thresh, self.comb_limit)
+
+    def match_stats(self):
+        """mode "match": (count c, count p1, count p2, choice 0..3) of vse_yuv_field_match over the luma rows of band()."""
+        if self.mode != "match":
+            raise ValueError(f"match_stats() belongs to mode \"match\", not {self.mode!r}")
+        if self._stats is None:
+            a, b = self.band()
+            t = self.comb_thresh << (self.fmt.depth - 8 + (16 - self.fmt.depth if self.fmt.msb else 0))
+            counts = field_match_counts(self.planes[0][a:b], None if self.prev is None else self.prev[0][a:b], self.keep, t)
+            self._stats = counts + (field_match_choice(counts, b - a, self.width, self.comb_limit, self.prev is not None),)
+        return self._stats
 
     def _deinterlaced(self, k, a, b):
+        if self.mode == "match":
+            choice = self.match_stats()[3]
+            if choice < 3:
+                out = np.array(self.planes[k][a:b], copy=True)
+                if choice:                                         # p1: the other field's rows from prev; p2: the first field's
+                    rows = ((np.arange(a, a + len(out)) & 1) == self.keep) == (choice == 2)
+                    out[rows] = self.prev[k][a:b][rows]
+                return out
         prev = None if self.prev is None or self.mode == "interpolate" else self.prev[k]
         return deinterlace_rows(self.planes[k], prev, self.keep, self.thresh_words, a, b)
 
@@ -919,6 +995,7 @@ class _Yuv420FileSource:
     deinterlace = None            # "adaptive" | "interpolate" with field_order "tff" | "bff": the frames are InterlacedYuvFrames
     field_order = None
     deinterlace_thresh = 10
+    comb_thresh, comb_limit = 10, 20      # deinterlace "match"'s (InterlacedYuvFrame)
     tone = None                   # a ToneMap (transfer="pq" | "hlg" on the readers of YuvFrames): the frames carry it
     _last = None                  # (frame number, planes) of the last read_raw: the next frame's prev is then the same views
 
@@ -951,7 +1028,7 @@ class _Yuv420FileSource:
         if self.fmt is not None and self.field_order is not None:
             prev = self._planes(frame_no - 1) if frame_no > 1 else None
             return InterlacedYuvFrame(self._planes(frame_no), h, w, self.fmt, prev, self.field_order, self.deinterlace, self.deinterlace_thresh,
-                                      tone=self.tone)
+                                      tone=self.tone, comb_thresh=self.comb_thresh, comb_limit=self.comb_limit)
         if self.fmt is not None:
             return YuvFrame(_planes_at(self._buf, off, h, w, self.fmt), h, w, self.fmt, tone=self.tone)
         luma = self._buf[off:off + h * w].reshape(h, w)
@@ -1081,7 +1158,8 @@ def parse_y4m_header_fields(line, name, fps=None, what="file", matrix="bt601", r
 class Y4mSource(_Yuv420FileSource):
     """YUV4MPEG2 (.y4m) reader, memory-mapped, frames indexed once at open.  The header is parse_y4m_header's: 8-bit 4:2:0 limited range,
     Yuv420Frames.  wide=True: parse_y4m_header_wide's, with `range` and a matrix of YUV_FORMAT_MATRICES; the frames are YuvFrames of
-    self.fmt (10-bit, 4:2:2, 4:4:4, grey, full range ...).  deinterlace="adaptive" | "interpolate" (needs wide=True) accepts interlaced
+    self.fmt (10-bit, 4:2:2, 4:4:4, grey, full range ...).  deinterlace="adaptive" | "interpolate" | "match" (needs wide=True; "match",
+    for film carried in interlaced video, takes comb_thresh and comb_limit, None: never fall back: InterlacedYuvFrame) accepts interlaced
     headers as parse_y4m_header_fields reads them with `field_order`; the frames of woven fields are InterlacedYuvFrames, each with the
     frame before it as its prev, read() and frames() deinterlace on the host.  transfer="pq" | "hlg" (needs wide=True; Y4M carries no tag for
     it) with tone_params (ToneMap's fields but transfer; primaries default to "bt2020" under matrix="bt2020", else "bt709") attaches a
@@ -1090,8 +1168,9 @@ class Y4mSource(_Yuv420FileSource):
     layout = "i420"
 
     def __init__(self, path, fps=None, matrix="bt601", wide=False, range="auto", deinterlace=None, field_order="auto", deinterlace_thresh=10,
-                 transfer=None, tone_params=None):
+                 transfer=None, tone_params=None, comb_thresh=10, comb_limit=20):
         self.deinterlace_thresh = _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
+        self.comb_thresh, self.comb_limit = _check_match(comb_thresh, comb_limit)
         if deinterlace is not None and not wide:
             raise ValueError(f"{path}: deinterlace={deinterlace!r} needs wide=True (the frames are YuvFrames)")
         self.deinterlace = deinterlace
@@ -1148,8 +1227,9 @@ class Y4mStream:
     tone = None                       # as Y4mSource's (transfer, tone_params)
 
     def __init__(self, fileobj, fps=None, matrix="bt601", name="<stream>", wide=False, range="auto", deinterlace=None, field_order="auto",
-                 deinterlace_thresh=10, transfer=None, tone_params=None):
+                 deinterlace_thresh=10, transfer=None, tone_params=None, comb_thresh=10, comb_limit=20):
         self.deinterlace_thresh = _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
+        self.comb_thresh, self.comb_limit = _check_match(comb_thresh, comb_limit)
         if deinterlace is not None and not wide:
             raise ValueError(f"{name}: deinterlace={deinterlace!r} needs wide=True (the frames are YuvFrames)")
         self.deinterlace = deinterlace
@@ -1222,7 +1302,8 @@ class Y4mStream:
             count += 1
             if self.fmt is not None and self.field_order is not None:
                 planes = _planes_at(buf, 0, h, w, self.fmt)
-                yield InterlacedYuvFrame(planes, h, w, self.fmt, last, self.field_order, self.deinterlace, self.deinterlace_thresh, tone=self.tone)
+                yield InterlacedYuvFrame(planes, h, w, self.fmt, last, self.field_order, self.deinterlace, self.deinterlace_thresh, tone=self.tone,
+                                         comb_thresh=self.comb_thresh, comb_limit=self.comb_limit)
                 last = planes
                 continue
             if self.fmt is not None:
@@ -1263,14 +1344,16 @@ class Yuv420Source(_Yuv420FileSource):
 class YuvSource(_Yuv420FileSource):
     """Yuv420Source for any YuvFormat: a headerless file of consecutive packed pictures of `fmt` (`ffmpeg -f rawvideo -pix_fmt NAME`, a
     hardware decoder's P010 surfaces), memory-mapped; read_raw / raw_frames hand out YuvFrames.  A partial last frame is dropped.
-    deinterlace="adaptive" | "interpolate": the pictures are woven fields and the frames InterlacedYuvFrames; a headerless file names no
+    deinterlace="adaptive" | "interpolate" | "match" (with comb_thresh, comb_limit): the pictures are woven fields and the frames InterlacedYuvFrames; a headerless file names no
     field order, so field_order must be "tff" or "bff".  transfer, tone_params: as Y4mSource's."""
 
-    def __init__(self, path, width, height, fps, fmt, deinterlace=None, field_order="auto", deinterlace_thresh=10, transfer=None, tone_params=None):
+    def __init__(self, path, width, height, fps, fmt, deinterlace=None, field_order="auto", deinterlace_thresh=10, transfer=None, tone_params=None,
+                 comb_thresh=10, comb_limit=20):
         if not isinstance(fmt, YuvFormat):
             raise ValueError(f"fmt must be a YuvFormat, not {fmt!r}")
         self.tone = _source_tone(path, transfer, tone_params, fmt.matrix, True)
         self.deinterlace_thresh = _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
+        self.comb_thresh, self.comb_limit = _check_match(comb_thresh, comb_limit)
         if deinterlace is not None:
             if field_order == "auto":
                 raise ValueError(f"{path}: a headerless YUV file names no field order: pass field_order \"tff\" or \"bff\"")
@@ -1290,19 +1373,24 @@ _RAW_PIX_FMT_EXT = {".p010": "p010le"}
 
 
 def open_source(path, fps=None, size=None, layout=None, matrix="bt601", wide=False, range="auto", pix_fmt=None, deinterlace=None,
-                field_order="auto", deinterlace_thresh=10, transfer=None, tone_params=None):
+                field_order="auto", deinterlace_thresh=10, transfer=None, tone_params=None, comb_thresh=10, comb_limit=20):
     """The source of a file by its extension: .npy (needs fps), .y4m, .yuv / .i420 / .nv12 (headerless: need size=(width, height) and
     fps; `layout` overrides the extension's), anything else an AVI; "-" is a Y4mStream over standard input.  `matrix` goes to the
     YUV sources.  wide=True lets the Y4M readers accept what parse_y4m_header_wide does, with `range` ("auto": the header's).  pix_fmt
     (a name of YuvFormat.from_pix_fmt; .p010 implies p010le) reads a headerless file of that format through YuvSource, with `range`
-    ("auto": the name's own) and any matrix of YUV_FORMAT_MATRICES; it needs size and fps.  deinterlace ("adaptive" | "interpolate"),
-    field_order and deinterlace_thresh go to the Y4M readers (with wide=True) and to YuvSource (with pix_fmt and a field order); no other
+    ("auto": the name's own) and any matrix of YUV_FORMAT_MATRICES; it needs size and fps.  deinterlace ("adaptive" | "interpolate" |
+    "match", the last with comb_thresh and comb_limit), field_order and deinterlace_thresh go to the Y4M readers (with wide=True) and to YuvSource (with pix_fmt and a field order); no other
     source takes them.  transfer ("pq" | "hlg") and tone_params (ToneMap's other fields) go to the same readers under the same
     conditions: HDR material is tone-mapped to SDR; every other source refuses them."""
     if range not in YUV_RANGES:
         raise ValueError(f"range must be one of {YUV_RANGES}, not {range!r}")
     _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
+    _check_match(comb_thresh, comb_limit)
+    if deinterlace != "match" and (comb_thresh, comb_limit) != (10, 20):
+        raise ValueError(f"comb_thresh and comb_limit belong to deinterlace=\"match\", not to deinterlace={deinterlace!r}")
     fields = {} if deinterlace is None else dict(deinterlace=deinterlace, field_order=field_order, deinterlace_thresh=deinterlace_thresh)
+    if deinterlace == "match":
+        fields.update(comb_thresh=comb_thresh, comb_limit=comb_limit)
     if transfer is not None or tone_params:
         fields.update(transfer=transfer, tone_params=tone_params)
     if str(path) == "-":

@@ -19,7 +19,8 @@ bytes per pixel, half the slab copy and half the PCIe bytes of a BGR frame — a
 either way.  Frames of any other format (ingest.YuvFrame: 10-bit, 4:2:2, 4:4:4, grey, full range, P010) go the same way through
 vse_yuv_to_bgr_format, keyed by shape, format, row parity and tone map (frames with an ingest.ToneMap, HDR material, convert through
 vse_yuv_to_bgr_tonemap; the map's table is uploaded once per context).  Interlaced pictures (ingest.InterlacedYuvFrame) are uploaded as they are,
-each beside its previous picture unless that is the frame before it in the batch, deinterlaced on the device (vse_yuv_deinterlace) and
+each beside its previous picture unless that is the frame before it in the batch, deinterlaced on the device (vse_yuv_deinterlace, or
+vse_yuv_field_match for frames of mode "match") and
 converted by the same call as the others.
 """
 import queue
@@ -162,19 +163,21 @@ class Uploader:
         band's edge rows are none of those asked for) is packed into one slot of the slab; a frame whose prev is the planes of the frame
         before it in the batch takes that frame's slot as its previous picture, any other frame with a prev packs it into the slot in
         front of its own.  One copy; then one vse_yuv_deinterlace per run of frames whose slots are laid out alike (frames without prev:
-        NULL; chained frames: the slot before, stride of one slot; frames with their prev beside them: stride of two), one
+        NULL; chained frames: the slot before, stride of one slot; frames with their prev beside them: stride of two; frames of mode
+        "match", which share their comb threshold and limit too: vse_yuv_field_match in the same runs), one
         vse_yuv_to_bgr_format (with a tone map: vse_yuv_to_bgr_tonemap) over all the progressive bands, and the rows asked for cut out of it."""
         import torch
         first = frames[0]
 
         def key_of(f):
             return (tuple(f.shape), getattr(f, "fmt", None), getattr(f, "y0", None), getattr(f, "height", None), getattr(f, "field_order", None),
-                    getattr(f, "mode", None), getattr(f, "thresh", None), getattr(f, "tone", None))
+                    getattr(f, "mode", None), getattr(f, "thresh", None), getattr(f, "tone", None), getattr(f, "comb_thresh", None),
+                    getattr(f, "comb_limit", None))
         key = key_of(first)
         for f in frames:
             if not hasattr(f, "deinterlaced_planes") or key_of(f) != key:
                 raise ValueError("Uploader.stage: the interlaced YUV frames of a batch must share shape, format, first row, picture height, "
-                                 f"field order, mode, threshold and tone map: {key} and {key_of(f)}")
+                                 f"field order, mode, threshold, tone map, comb threshold and comb limit: {key} and {key_of(f)}")
         from .ingest import _same_planes
         ctx = self._context()
         n, w = len(frames), first.width
@@ -205,10 +208,17 @@ class Uploader:
             packed = torch.empty((slot, per), dtype=torch.uint8, device=self.device)        # (dropped here, like prog: see _stage_yuv420)
             packed.copy_(host, non_blocking=True)
             prog = torch.empty((n, per), dtype=torch.uint8, device=self.device)
+            stats = torch.empty((n, 4), dtype=torch.int32, device=self.device) if first.mode == "match" else None      # (dropped here too)
             for kind, i, at, count in runs:
                 step = 2 if kind == 2 else 1
                 cur = packed[at:].as_strided((count, per), (step * per, 1))
-                ctx.yuv_deinterlace(cur, count, b - a, w, first.fmt, prev=None if kind == 0 else packed[at - 1], prev_stride=step * per,
+                before = None if kind == 0 else packed[at - 1]
+                if first.mode == "match":
+                    ctx.yuv_field_match(cur, count, b - a, w, first.fmt, prev=before, prev_stride=step * per, keep=first.keep,
+                                        comb_thresh=first.comb_thresh, comb_limit=first.comb_limit, thresh=first.thresh, out=prog[i:i + count],
+                                        stats=stats[i:i + count])
+                    continue
+                ctx.yuv_deinterlace(cur, count, b - a, w, first.fmt, prev=before, prev_stride=step * per,
                                     keep=first.keep, mode=first.mode, thresh=first.thresh, out=prog[i:i + count])
             dev = ctx.yuv_to_bgr(prog, n, b - a, w, first.fmt, 0, tone=first.tone)
             if (first.y0 - a, first.y1 - a) != (0, b - a):

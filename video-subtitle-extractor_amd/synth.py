@@ -180,6 +180,39 @@ def interlace_yuv420(field_rate_bgr, field_order="tff"):
     return out
 
 
+TELECINE_PATTERNS = {"32": ((0, 0), (1, 1), (1, 2), (2, 3), (3, 3)), "32b": ((0, 0), (1, 1), (2, 1), (3, 2), (3, 3))}
+
+
+def telecine(planes_list, pattern="32", field_order="tff"):
+    """Progressive pictures (plane tuples of one format, e.g. ingest.bgr_to_yuv420's) dealt into interlaced frames, as film is carried in
+    interlaced video -> (the woven plane tuples, per stored frame the indices (picture of its first field, picture of its second field)).
+    The first field is the one first in time: the top one (the even rows of every plane) for "tff", the bottom one for "bff".
+      "32"     3:2 pulldown, four pictures A B C D to five frames: At Ab, Bt Bb, Bt Cb, Ct Db, Dt Db (t the first field, b the second)
+      "32b"    its other phase, the second field running ahead: At Ab, Bt Bb, Ct Bb, Dt Cb, Dt Db
+      "shift"  fields shifted by one: frame k holds the first field of picture k and the second field of picture k - 1 (frame 0: picture 0)
+    A pulldown cycle that the pictures end in is cut where a field's picture is missing."""
+    from .ingest import FIELD_ORDERS
+    if field_order not in FIELD_ORDERS:
+        raise ValueError(f"field_order must be one of {FIELD_ORDERS}, not {field_order!r}")
+    if pattern != "shift" and pattern not in TELECINE_PATTERNS:
+        raise ValueError(f"pattern must be one of {sorted(TELECINE_PATTERNS) + ['shift']}, not {pattern!r}")
+    keep = FIELD_ORDERS.index(field_order)
+    n = len(planes_list)
+    if pattern == "shift":
+        pairs = [(k, max(k - 1, 0)) for k in range(n)]
+    else:
+        pairs = [(base + a, base + b) for base in range(0, n, 4) for a, b in TELECINE_PATTERNS[pattern] if max(base + a, base + b) < n]
+    woven = []
+    for first, second in pairs:
+        frame = []
+        for a, b in zip(planes_list[first], planes_list[second]):
+            p = np.array(b, copy=True)
+            p[keep::2] = np.asarray(a)[keep::2]
+            frame.append(p)
+        woven.append(tuple(frame))
+    return woven, pairs
+
+
 def hdr_grade(frames_bgr, white_nits=203.0, transfer="pq", depth=10, sub=(1, 1)):
     """SDR frames (uint8 BGR [n, H, W, 3]) graded as HDR video -> n (Y, U, V) plane triples of BT.2020 non-constant-luminance limited-range
     samples at `depth` bits (uint16; uint8 at depth 8), chroma subsampled by sub = (sub_x, sub_y) as the mean of each block.  The inverse
