@@ -824,6 +824,42 @@ int vse_yuv_field_match(vse_ctx* ctx, const void* d_yuv, const void* d_prev /* N
                         int64_t yuv_frame_stride, int64_t prev_frame_stride, void* d_out, int64_t out_frame_stride,
                         void* d_stats /* device, uint32[n][4]: count c, p1, p2, choice 0..3 */, void* stream);
 
+/* ---- frame ingest: anamorphic YUV -> square pixels (horizontal resample) ---------------------------------------------------------------- */
+/* DVDs, HDV, DVCPRO HD and much 1080i broadcast store pixels that are not square: 720 columns shown as 854 (sample aspect ratio 32:27),
+ * 1048 (16:11) or 640 (8:9), 1440 shown as 1920 (4:3).  This turns n packed pictures of any format of vse_yuv_to_bgr_format's table into
+ * packed pictures of the same format and height whose rows are w_out columns long, every plane resampled along its rows; it stands behind
+ * vse_yuv_deinterlace / vse_yuv_field_match (combing is a property of stored columns) and in front of the conversions, which take any
+ * width.  Rows do not interact: a band of rows gives exactly the whole picture's rows.
+ * The filter is DATA: the device knows tables, nothing of bicubic or Lanczos (vse_amd.ingest.Resample builds them).  A table for a plane
+ * of P output columns and K taps (K even, 2..16) is left[P] (int32) followed by coef[P][K] (int16), P (4 + 2 K) bytes, 16-byte aligned.
+ * For a plane of pw stored columns, every row and every output column x, int32, >> arithmetic:
+ *   acc = sum over k < K of coef[x][k] * S[clamp(left[x] + k, 0, pw - 1)]
+ *   out = clip(0, 2^depth - 1, (acc + 8192) >> 14)
+ * S is the stored sample as a value: the word itself, or with msb = 1 the word >> (16 - depth), and the result is then stored
+ * << (16 - depth).  Luma takes the luma table (w_in -> w_out columns), every chroma plane the chroma table (cw_in -> cw_out, cw = (w +
+ * sub_x) >> sub_x); a semi-planar UV plane is a plane of cw columns of two components: entry x is applied to U at 2 (left + k) and to V
+ * at 2 (left + k) + 1.  Grey has no chroma table.  The host guarantees sum over k of |coef[x][k]| <= 32767 for every x (ingest.Resample
+ * and the Python binding check it; this call cannot read the device tables) and |left| <= 2^30: with 16-bit samples every partial sum
+ * then stays below 2^31.  The table whose every row is one tap of 16384 at left[x] = x gives the input back (valid samples).
+ * vse_yuv_resample_table_bytes: P (4 + 2 K) for `columns` = P and `taps` = K; 0 for columns < 1 or taps odd or outside 2..16. */
+size_t vse_yuv_resample_table_bytes(int columns, int taps);
+/* Picture f at d_yuv + f yuv_frame_stride (vse_yuv_frame_bytes(h, w_in, ..., row_parity) bytes) -> d_out + f out_frame_stride
+ * (vse_yuv_frame_bytes(h, w_out, ...) bytes).  One launch on `stream`, no allocation, no device sync, no LDS; exactly the packed bytes of
+ * each output picture are written, the inputs and the tables are only read (keep the tables until the launch has run).  A lane owns four
+ * output samples of a strip of 8 rows with their table entries in registers and loads every source sample on its own, by its clamped
+ * index, in both forms (no wide loads, no staging).  The forms differ in the store alone: where both pictures' bases, every plane's
+ * row bytes and the frame strides are 16-byte aligned the four samples always go out as one 4-byte store (8-byte for 2-byte samples);
+ * otherwise as a dword where they exist and lie 4-byte aligned and sample by sample where not; 2-byte samples need 2-byte aligned
+ * bases and strides.
+ * Returns VSE_E_INVAL, with the values in vse_last_error, and launches nothing, for a format outside the table, n, h, w_in or w_out < 1,
+ * h * max(w_in, w_out) > 2^31 - 1, row_parity outside 0..sub_y, taps odd or outside 2..16 (taps_c only where the format has chroma), a NULL
+ * or misaligned d_table_y, a NULL or misaligned d_table_c where the format has chroma, a frame stride below the packed size, 2-byte samples
+ * at an odd base or stride, and a d_out whose pictures (first byte of the first to last byte of the last) overlap the input pictures or a table. */
+int vse_yuv_resample(vse_ctx* ctx, const void* d_yuv, int n, int h, int w_in, int w_out, int sub_x, int sub_y, int chroma, int depth, int msb,
+                     int row_parity, const void* d_table_y /* device, 16-byte aligned */, int taps_y,
+                     const void* d_table_c /* device, 16-byte aligned; NULL for grey */, int taps_c, int64_t yuv_frame_stride, void* d_out,
+                     int64_t out_frame_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -344,8 +344,9 @@ def main(argv=None, cells_fn=None):
                    "Y4M header's]")
     p.add_argument("--deinterlace-thresh", type=int, default=10, metavar="N", help="--deinterlace adaptive: a sample that changed by more "
                    "than N 8-bit levels since the previous frame has moved, 0..255 [10]")
-    from .extractor import add_match_arguments, match_arguments
+    from .extractor import add_match_arguments, add_square_arguments, match_arguments, square_arguments
     add_match_arguments(p)
+    add_square_arguments(p)
     p.add_argument("--transfer", default=None, choices=("pq", "hlg"), help="HDR video (needs --wide-yuv or --pix-fmt): undo PQ or HLG and "
                    "tone-map to SDR on the GPU [none]")
     p.add_argument("--white-nits", type=float, default=None, metavar="N", help="--transfer: the luminance that becomes SDR white [203]")
@@ -385,7 +386,7 @@ def main(argv=None, cells_fn=None):
                                                           deinterlace_thresh=args.deinterlace_thresh)
         source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout, matrix=args.matrix,
                                     wide=args.wide_yuv or args.deinterlace is not None, range=args.range, pix_fmt=args.pix_fmt,
-                                    **fields, **match_arguments(args), **tone_arguments(args))
+                                    **fields, **match_arguments(args), **tone_arguments(args), **square_arguments(args))
         loc = AreaLocator(cells_fn, probe=args.probe, edge_thresh=parse_edge_thresh(args.edge_thresh), automaton=args.locator_automaton,
                           hold_seconds=args.hold_seconds, hold_frames=args.hold_frames, max_hold_seconds=args.max_hold_seconds,
                           max_hold_frames=args.max_hold_frames)

@@ -71,6 +71,24 @@
 //            0 to 2 copy each row of each plane from C or P, choice 3 runs the deinterlacer's strip walk (deint_strip16 /
 //            deint_strip_quad, shared with its kernels).  The planes whose base and row bytes are 16-byte aligned go through one launch
 //            of 16-byte moves, the others (the 360-byte chroma rows of a DVD under its 720-byte luma rows) through one of quads.
+//
+// vse_yuv_resample (include/vse_hip.h) stands behind those two and in front of the conversions for anamorphic pictures (DVD, HDV: pixels
+// that are not square): packed pictures of w_in columns become packed pictures of w_out columns of the same format and height, every plane
+// resampled along its rows.  The device knows tables, not filters (ingest.Resample builds them; tests/resample_ref.py restates the integers
+// in int64): per plane left[P] (int32) and coef[P][K] (int16, Q14), K even and 2..16, and for a plane of pw stored columns
+//   acc = sum over k < K of coef[x][k] * S[clamp(left[x] + k, 0, pw - 1)],   out = clip(0, 2^depth - 1, (acc + 8192) >> 14)
+// S the stored word, or word >> (16 - depth) for high-bit words (the result is stored << (16 - depth)); an interleaved UV plane is a plane
+// of cw columns of two components that share the chroma table.  The host keeps sum |coef[x]| <= 32767, so with 16-bit samples every partial
+// sum stays below 2^31; coefficients and samples fit 24 signed bits, so the products are the 24-bit multiplies.  One launch, no LDS, no
+// scratch, no atomics: a lane owns four output samples of a plane (four columns, or two U V pairs) and walks down a strip of 8 rows
+// with its columns' left and coefficients in registers (the table is read once per lane, not once per row); every source sample is a load
+// of its own by its clamped index, which the vector cache serves (neighbouring lanes read neighbouring samples).  Templated on the sample
+// width, planar / interleaved chroma, and an upper bound on the tap pairs (1, 2, 3, 4 or 8: the unrolled form keeps the coefficients in
+// registers), in two forms that differ in the store alone (the loads are per sample in both; nothing is loaded wide or staged):
+//   fast     every plane's base and row bytes and all strides 16-byte aligned: the four samples are always one 4-byte store (8-byte for
+//            2-byte samples), without a test
+//   general  any width and byte alignment (2-byte samples: 2-byte aligned): a dword where the four samples exist and lie aligned, sample
+//            by sample otherwise (the 854-byte rows of a 16:9 NTSC DVD alternate between the two)
 #include <algorithm>
 #include <cstdio>
 
@@ -989,6 +1007,128 @@ __global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void field_weave_general_kern
     }
 }
 
+// ---- horizontal resample (vse_yuv_resample) ---------------------------------------------------------------------------------------------
+constexpr int RES_STRIP = 8;           // rows a lane walks down with its columns' table entries in registers
+constexpr int RES_MAX_TAPS = 16;
+
+// The planes of the packed input and output pictures, in samples.  pin / pout: stored and output columns per component (an interleaved UV
+// row has 2 pin samples in and 2 pout out); left / coef: the plane's table on the device (coef rows of `taps` int16, read as dwords: taps
+// is even).  Read with constant indices only, so the struct stays in scalar registers.
+struct ResPlanes {
+    int count;
+    int rows[3], pin[3], pout[3], taps[3];
+    long off_in[3], off_out[3];
+    const int* left[3];
+    const unsigned* coef[3];
+};
+
+// One plane for one lane.  The lane owns output samples [4 g, 4 g + 4) of every row: COLS = 4 columns of a planar row, or 2 columns (U V U V)
+// of an interleaved one.  Their `left` and coefficients (two int16 per dword, TP dwords per column: TP is the instantiation's bound on tap
+// pairs, so that the loops unroll without a test, every index is a constant, nothing goes to scratch and a row's loads are all in flight
+// together; a pair at or past `taps` is zero, and zero times a sample that exists adds nothing) are loaded once and kept over all frames
+// and strips of the lane.  A source sample is loaded by its clamped index, so every read lies inside its row whatever the table says; the sums are 24-bit multiplies (|coef| <= 2^15,
+// sample < 2^16).  ALIGNED: every output quad exists whole and lies 4-sample aligned (the launcher has checked bases, row bytes and
+// strides): one dword / two-dword store; otherwise store_quad decides per quad.
+template <typename S, bool SEMI, bool ALIGNED, int TP>
+__device__ __forceinline__ void resample_plane(const S* __restrict__ src, S* __restrict__ dst, int n, long sstride, long dstride, int rows, int pin,
+                                               int pout, int taps, const int* __restrict__ left, const unsigned* __restrict__ coef, long g,
+                                               int strip0, int strip_step, int f0, int f_step, int shift, int maxv) {
+    constexpr int COLS = SEMI ? 2 : 4, COMPS = SEMI ? 2 : 1, PER = 4 / sizeof(S), BITS = 8 * sizeof(S);
+    const long x0 = g * COLS;
+    if (x0 >= pout) return;
+    const int ncols = (int)min((long)COLS, pout - x0), ns = ncols * COMPS;
+    int lf[COLS];
+    unsigned cf[COLS][TP];
+#pragma unroll
+    for (int c = 0; c < COLS; ++c) {
+        const long x = min(x0 + c, (long)pout - 1);           // (a column past the row's end repeats the last one: it is not stored)
+        lf[c] = left[x];
+#pragma unroll
+        for (int j = 0; j < TP; ++j) cf[c][j] = 2 * j < taps ? coef[x * (taps >> 1) + j] : 0u;
+    }
+    const long rin = (long)pin * COMPS, rout = (long)pout * COMPS;
+    const int top = (maxv << 14) | 0x3fff;
+    for (int f = f0; f < n; f += f_step) {
+        const S* s = src + (long)f * sstride;
+        S* d = dst + (long)f * dstride + x0 * COMPS;
+        for (int y0 = strip0; y0 < rows; y0 += strip_step) {
+            const int y1 = min(y0 + RES_STRIP, rows);
+#pragma unroll 1          // (one row's loads in flight per lane: unrolled rows cost registers, and with them the waves that hide the latency)
+            for (int y = y0; y < y1; ++y) {
+                const S* row = s + (long)y * rin;
+                int acc[4] = {0, 0, 0, 0};
+#pragma unroll
+                for (int c = 0; c < COLS; ++c) {
+                    // The clamped indices are made anew in every row (an add and a v_med3 per tap): hoisted out of the row loop they are
+                    // 2 TP registers per column, which at 8 pairs spilled to scratch and at 2 already halved the waves per SIMD.
+                    int l = lf[c];
+                    asm volatile("" : "+v"(l));
+#pragma unroll
+                    for (int j = 0; j < TP; ++j) {
+                        const int k0 = (int)(short)(cf[c][j] & 0xffffu), k1 = (int)cf[c][j] >> 16;
+                        const int i0 = min(max(l + 2 * j, 0), pin - 1) * COMPS, i1 = min(max(l + 2 * j + 1, 0), pin - 1) * COMPS;
+#pragma unroll
+                        for (int e = 0; e < COMPS; ++e)
+                            acc[c * COMPS + e] += __mul24(k0, (int)row[i0 + e] >> shift) + __mul24(k1, (int)row[i1 + e] >> shift);
+                    }
+                }
+                Quad<S> q;
+#pragma unroll
+                for (int k = 0; k < (int)(sizeof(q.v) / sizeof(q.v[0])); ++k) q.v[k] = 0u;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const unsigned v = (unsigned)(min(max(acc[k] + 8192, 0), top) >> 14) << shift;          // (clamped before the shift, as clip8)
+                    q.v[k / PER] |= v << (BITS * (k % PER));
+                }
+                S* o = d + (long)y * rout;
+                if (ALIGNED) {
+#pragma unroll
+                    for (int k = 0; k < (int)(sizeof(q.v) / sizeof(q.v[0])); ++k) reinterpret_cast<unsigned*>(o)[k] = q.v[k];
+                } else {
+                    store_quad(o, q, ns);
+                }
+            }
+        }
+    }
+}
+
+// Lane (threadIdx.x, threadIdx.y) = output samples 4 g .. 4 g + 3 of strips of RES_STRIP rows of each plane; blockIdx.y strides the strips,
+// blockIdx.z the frames.  Strides and offsets are counted in samples.  ALIGNED is the fast kernel, TP the bound on the tap pairs of
+// both tables (see resample_plane).
+template <typename S, bool SEMI, bool ALIGNED, int TP>
+__global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void resample_kernel(const S* __restrict__ src, int n, long sstride, S* __restrict__ dst,
+                                                                        long dstride, ResPlanes pl, int shift, int maxv) {
+    const long g = (long)blockIdx.x * GEN_LANES + threadIdx.x;
+    const int strip0 = (int)(blockIdx.y * GEN_ROWS + threadIdx.y) * RES_STRIP, strip_step = (int)gridDim.y * GEN_ROWS * RES_STRIP;
+    resample_plane<S, false, ALIGNED, TP>(src + pl.off_in[0], dst + pl.off_out[0], n, sstride, dstride, pl.rows[0], pl.pin[0], pl.pout[0], pl.taps[0],
+                                      pl.left[0], pl.coef[0], g, strip0, strip_step, (int)blockIdx.z, (int)gridDim.z, shift, maxv);
+#pragma unroll
+    for (int p = 1; p < 3; ++p) {
+        if (p >= pl.count) continue;
+        resample_plane<S, SEMI, ALIGNED, TP>(src + pl.off_in[p], dst + pl.off_out[p], n, sstride, dstride, pl.rows[p], pl.pin[p], pl.pout[p],
+                                         pl.taps[p], pl.left[p], pl.coef[p], g, strip0, strip_step, (int)blockIdx.z, (int)gridDim.z, shift, maxv);
+    }
+}
+
+bool resample_table_ok(int columns, int taps) { return columns >= 1 && taps >= 2 && taps <= RES_MAX_TAPS && taps % 2 == 0; }
+
+// The instantiation of an accepted call: tap pairs 1, 2, 3, 4 (what bilinear, bicubic and Lanczos-3 need up to a reduction of 4 : 3) or 8.
+template <typename S, int TP>
+auto resample_kernel_of(bool semi, bool fast) -> decltype(&resample_kernel<S, false, false, TP>) {
+    return fast ? (semi ? resample_kernel<S, true, true, TP> : resample_kernel<S, false, true, TP>)
+                : (semi ? resample_kernel<S, true, false, TP> : resample_kernel<S, false, false, TP>);
+}
+
+template <typename S>
+void launch_resample(const void* d_yuv, int n, long sstride, void* d_out, long dstride, const ResPlanes& pl, int shift, int maxv, bool semi,
+                     bool fast, int pairs, dim3 grid, dim3 block, hipStream_t st) {
+    const auto kernel = pairs <= 1 ? resample_kernel_of<S, 1>(semi, fast) : pairs == 2 ? resample_kernel_of<S, 2>(semi, fast)
+                      : pairs == 3 ? resample_kernel_of<S, 3>(semi, fast) : pairs == 4 ? resample_kernel_of<S, 4>(semi, fast)
+                      : resample_kernel_of<S, RES_MAX_TAPS / 2>(semi, fast);
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, reinterpret_cast<const S*>(d_yuv), n, sstride, reinterpret_cast<S*>(d_out), dstride, pl, shift,
+                       maxv);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1316,6 +1456,90 @@ int vse_yuv_field_match(vse_ctx* c, const void* d_yuv, const void* d_prev, int n
     }
     if (hipGetLastError() != hipSuccess) {
         vse_set_error("vse_yuv_field_match: launch failed");
+        return VSE_E_HIP;
+    }
+    return VSE_OK;
+}
+
+size_t vse_yuv_resample_table_bytes(int columns, int taps) {
+    return resample_table_ok(columns, taps) ? (size_t)columns * (4 + 2 * (size_t)taps) : 0;
+}
+
+int vse_yuv_resample(vse_ctx* c, const void* d_yuv, int n, int h, int w_in, int w_out, int sub_x, int sub_y, int chroma, int depth, int msb,
+                     int row_parity, const void* d_table_y, int taps_y, const void* d_table_c, int taps_c, int64_t yuv_frame_stride, void* d_out,
+                     int64_t out_frame_stride, void* stream) {
+    const size_t frame_in = vse_yuv_frame_bytes(h, w_in, sub_x, sub_y, chroma, depth, row_parity);
+    const size_t frame_out = vse_yuv_frame_bytes(h, w_out, sub_x, sub_y, chroma, depth, row_parity);
+    const int ss = depth > 8 ? 2 : 1;
+    const bool has_chroma = frame_in && chroma != CHROMA_NONE;
+    const long cw_in = ((long)w_in + (sub_x & 1)) >> (sub_x & 1), cw_out = ((long)w_out + (sub_x & 1)) >> (sub_x & 1);
+    const size_t table_y = frame_out ? vse_yuv_resample_table_bytes(w_out, taps_y) : 0;
+    const size_t table_c = has_chroma && frame_out ? vse_yuv_resample_table_bytes((int)cw_out, taps_c) : 0;
+    const auto odd = [](const void* p, int64_t stride) { return (reinterpret_cast<uintptr_t>(p) & 1) || (stride & 1); };
+    bool ok = c && d_yuv && d_out && n >= 1 && frame_in && frame_out && msb >= 0 && msb <= (ss == 2 ? 1 : 0) && table_y && d_table_y &&
+              aligned16(d_table_y) && (!has_chroma || (table_c && d_table_c && aligned16(d_table_c))) && yuv_frame_stride >= (int64_t)frame_in &&
+              out_frame_stride >= (int64_t)frame_out && !(ss == 2 && (odd(d_yuv, yuv_frame_stride) || odd(d_out, out_frame_stride)));
+    if (ok) {
+        // the output lies apart from the input pictures (first byte of the first to last byte of the last) and from both tables
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + (uintptr_t)(n - 1) * (uintptr_t)out_frame_stride + frame_out;
+        const auto apart = [&](const void* p, size_t bytes) {
+            const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+            return !p || !bytes || o1 <= a || a + bytes <= o0;
+        };
+        ok = apart(d_yuv, (size_t)(n - 1) * (size_t)yuv_frame_stride + frame_in) && apart(d_table_y, table_y) &&
+             apart(has_chroma ? d_table_c : nullptr, table_c);
+    }
+    if (!ok) {
+        char msg[900];
+        snprintf(msg, sizeof msg, "vse_yuv_resample: bad arguments (n %d, frame %d x %d -> %d columns, each of at most 2^31 - 1 pixels, subsampling "
+                 "%d, %d of 0, 0 | 1, 0 | 1, 1, chroma %d of 0 (with subsampling 0, 0) | 1 | 2 (with subsampling 1, 1), depth %d of 8..16, msb %d of "
+                 "0 | 1 (0 at depth 8), row parity %d of 0..%d, taps %d (luma) and %d (chroma) even and of 2..16, tables %p and %p 16-byte aligned "
+                 "(the chroma table only where the format has chroma), frame strides %lld of at least %zu and %lld (output) of at least %zu, bases "
+                 "%p, %p and strides 2-byte aligned for 2-byte samples, the output apart from the pictures and the tables)",
+                 n, h, w_in, w_out, sub_x, sub_y, chroma, depth, msb, row_parity, sub_y == 1 ? 1 : 0, taps_y, taps_c, d_table_y, d_table_c,
+                 (long long)yuv_frame_stride, frame_in, (long long)out_frame_stride, frame_out, d_yuv, d_out);
+        vse_set_error(msg);
+        return VSE_E_INVAL;
+    }
+    const long ch = (((long)h - 1 + row_parity) >> sub_y) + 1;
+    ResPlanes pl = {};
+    pl.count = chroma == CHROMA_NONE ? 1 : chroma == CHROMA_PLANAR ? 3 : 2;
+    const int comps = chroma == CHROMA_SEMI ? 2 : 1;
+    for (int p = 0; p < pl.count; ++p) {
+        const bool luma = p == 0;
+        const uint8_t* table = reinterpret_cast<const uint8_t*>(luma ? d_table_y : d_table_c);
+        pl.rows[p] = luma ? h : (int)ch;
+        pl.pin[p] = luma ? w_in : (int)cw_in;
+        pl.pout[p] = luma ? w_out : (int)cw_out;
+        pl.taps[p] = luma ? taps_y : taps_c;
+        pl.off_in[p] = luma ? 0 : (long)h * w_in + (p - 1) * ch * cw_in;
+        pl.off_out[p] = luma ? 0 : (long)h * w_out + (p - 1) * ch * cw_out;
+        pl.left[p] = reinterpret_cast<const int*>(table);
+        pl.coef[p] = reinterpret_cast<const unsigned*>(table + 4L * pl.pout[p]);
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // the fast kernel: every output quad whole and on a 4-sample boundary
+    bool fast = aligned16(d_yuv) && aligned16(d_out) && yuv_frame_stride % 16 == 0 && out_frame_stride % 16 == 0;
+    for (int p = 0; p < pl.count; ++p) {
+        const long cs = p == 0 ? 1 : comps;
+        fast = fast && (pl.pin[p] * cs * ss) % 16 == 0 && (pl.pout[p] * cs * ss) % 16 == 0 && (pl.off_in[p] * ss) % 16 == 0 &&
+               (pl.off_out[p] * ss) % 16 == 0;
+    }
+    const long groups = ((long)w_out + 3) / 4;          // (no chroma row has more quads than the luma row: 2 cw_out <= w_out + 1)
+    const int strips = (h + RES_STRIP - 1) / RES_STRIP;
+    const dim3 grid((unsigned)((groups + GEN_LANES - 1) / GEN_LANES), (unsigned)std::min((strips + GEN_ROWS - 1) / GEN_ROWS, 65535),
+                    (unsigned)std::min(n, 65535));
+    const dim3 block(GEN_LANES, GEN_ROWS);
+    const int shift = msb ? 16 - depth : 0, maxv = (1 << depth) - 1;
+    const bool semi = chroma == CHROMA_SEMI;
+    const int pairs = std::max(taps_y, has_chroma ? taps_c : 0) / 2;
+    if (ss == 1)
+        launch_resample<uint8_t>(d_yuv, n, (long)yuv_frame_stride, d_out, (long)out_frame_stride, pl, shift, maxv, semi, fast, pairs, grid, block, st);
+    else
+        launch_resample<uint16_t>(d_yuv, n, (long)yuv_frame_stride / 2, d_out, (long)out_frame_stride / 2, pl, shift, maxv, semi, fast, pairs, grid,
+                                  block, st);
+    if (hipGetLastError() != hipSuccess) {
+        vse_set_error("vse_yuv_resample: launch failed");
         return VSE_E_HIP;
     }
     return VSE_OK;

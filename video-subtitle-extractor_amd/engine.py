@@ -33,7 +33,7 @@ EXPORTS = [
     "vse_frame_cells_hold_bounded_state_bytes", "vse_frame_cells_hold_bounded",
     "vse_interval_stream_state_bytes", "vse_interval_stream",
     "vse_yuv_frame_bytes", "vse_yuv_to_bgr_format", "vse_yuv_deinterlace", "vse_yuv_field_match",
-    "vse_yuv_tonemap_table_bytes", "vse_yuv_to_bgr_tonemap",
+    "vse_yuv_tonemap_table_bytes", "vse_yuv_to_bgr_tonemap", "vse_yuv_resample_table_bytes", "vse_yuv_resample",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -246,6 +246,10 @@ def load_library(path=None):
     lib.vse_yuv_tonemap_table_bytes.restype = C.c_size_t
     lib.vse_yuv_tonemap_table_bytes.argtypes = []
     lib.vse_yuv_to_bgr_tonemap.argtypes = lib.vse_yuv_to_bgr_format.argtypes[:-1] + [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
+    lib.vse_yuv_resample_table_bytes.restype = C.c_size_t
+    lib.vse_yuv_resample_table_bytes.argtypes = [C.c_int, C.c_int]
+    lib.vse_yuv_resample.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 10 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
+                                     C.c_int64, C.c_void_p]
     lib.vse_yuv_deinterlace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 11 + [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     lib.vse_yuv_field_match.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 12 + [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                                                                                  C.c_void_p]
@@ -301,6 +305,7 @@ class Context:
         self.tdev = self.torch.device("cuda", device)
         self._tone_tables = {}            # ingest.ToneMap -> (cuda uint8 [16128] table, its gamut as int32[9]): uploaded once
         self._tone_lock = threading.Lock()
+        self._resample_tables = {}        # (ingest.Resample, sub_x, has chroma) -> ((cuda uint8 luma table, taps), (chroma table, taps) | None)
 
     def stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.tdev).cuda_stream)
@@ -1088,6 +1093,71 @@ class Context:
                                             C.c_void_p(out.data_ptr()), ostride, C.c_void_p(stats.data_ptr()), self.stream()),
                "vse_yuv_field_match")
         return out, stats
+
+    def resample_tables(self, resample, fmt):
+        """The device copies of an ingest.Resample's tables for the format `fmt` (anything hashable with in_width, out_width, tables(fmt)
+        -> ((left, coef), (left, coef) | None) and packed(fmt) -> (luma bytes, chroma bytes | None)): ((cuda uint8 table, taps), the same
+        for chroma or None), uploaded on first use and kept for the context's life.  vse_yuv_resample cannot read them, so the bounds
+        that keep its int32 sums exact are checked here: |left| <= 2^30 and every row's sum of |coef| <= 32767."""
+        key = (resample, int(fmt.sub_x), bool(fmt.chroma))
+        with self._tone_lock:
+            hit = self._resample_tables.get(key)
+            if hit is None:
+                t = self.torch
+                cw = (int(resample.out_width) + int(fmt.sub_x)) >> int(fmt.sub_x)
+                devs = []
+                for what, tab, raw, cols in zip(("luma", "chroma"), resample.tables(fmt), resample.packed(fmt), (int(resample.out_width), cw)):
+                    if tab is None:
+                        devs.append(None)
+                        continue
+                    left, coef = np.asarray(tab[0]), np.asarray(tab[1])
+                    taps = int(coef.shape[1]) if coef.ndim == 2 else 0
+                    host = np.frombuffer(raw, np.uint8)
+                    want = self.lib.vse_yuv_resample_table_bytes(cols, taps)
+                    if not want or left.shape != (cols,) or coef.shape != (cols, taps) or host.size != want:
+                        raise VseError(f"resample_tables: the {what} table of {cols} columns has left {left.shape}, coef {coef.shape} (taps even, "
+                                       f"2..16) and {host.size} bytes of {want}")
+                    if np.abs(left.astype(np.int64)).max() > 1 << 30 or np.abs(coef.astype(np.int64)).sum(axis=1).max() > 32767:
+                        raise VseError(f"resample_tables: the {what} table breaks |left| <= 2^30 or a row's sum of |coef| <= 32767 (max "
+                                       f"{int(np.abs(coef.astype(np.int64)).sum(axis=1).max())}): int32 would not be exact")
+                    devs.append((t.from_numpy(host.copy()).to(self.tdev), taps))
+                if devs[0] is None or (devs[1] is None) != (not fmt.chroma):
+                    raise VseError(f"resample_tables: {fmt} takes a luma table and {'a' if fmt.chroma else 'no'} chroma table")
+                t.cuda.current_stream(self.tdev).synchronize()          # any stream may read them from here on
+                hit = self._resample_tables[key] = tuple(devs)
+            return hit
+
+    def yuv_resample(self, packed, n, h, w_in, fmt, resample, row_parity=0, out=None):
+        """packed: cuda uint8 holding n packed (sub-)frames of h x w_in pixels of the format `fmt` (as yuv_to_bgr's), 1-D (back to back) or
+        2-D [n, stride in bytes] -> cuda uint8 [n, stride] of the pictures resampled along their rows to resample.out_width columns, in the
+        same packing, on the current stream (include/vse_hip.h vse_yuv_resample).  resample: an ingest.Resample (see resample_tables) whose
+        in_width is w_in.  out: write into this uint8 tensor (1-D or [n, stride]) instead; it must not overlap the input or the tables."""
+        t = self.torch
+        n, h, w_in, row_parity = int(n), int(h), int(w_in), int(row_parity)
+        if int(resample.in_width) != w_in:
+            raise VseError(f"yuv_resample: the tables are for {resample.in_width} stored columns, the pictures have {w_in}")
+        w_out = int(resample.out_width)
+        form = (int(fmt.sub_x), int(fmt.sub_y), int(fmt.chroma), int(fmt.depth))
+        frame_in = self.lib.vse_yuv_frame_bytes(h, w_in, *form, row_parity)
+        frame_out = self.lib.vse_yuv_frame_bytes(h, w_out, *form, row_parity)
+
+        def stride_of(a, frame, what):
+            assert a.dtype == t.uint8 and a.dim() in (1, 2) and a.stride(-1) == 1, what
+            if a.dim() == 2:
+                assert a.shape[0] == n and a.shape[1] >= frame, (what, tuple(a.shape), n, frame)
+                return a.stride(0) if n > 1 else max(a.stride(0), frame)
+            assert a.numel() >= n * frame, (what, a.numel(), n, frame)
+            return frame
+        sstride = stride_of(packed, frame_in, "packed")
+        if out is None:
+            out = t.empty((max(n, 0), (frame_out + 15) & ~15), dtype=t.uint8, device=self.tdev)
+        ostride = stride_of(out, frame_out, "out")
+        luma, chroma = self.resample_tables(resample, fmt)
+        _check(self.lib.vse_yuv_resample(self.handle, C.c_void_p(packed.data_ptr()), n, h, w_in, w_out, *form, int(fmt.msb), row_parity,
+                                         C.c_void_p(luma[0].data_ptr()), luma[1], None if chroma is None else C.c_void_p(chroma[0].data_ptr()),
+                                         0 if chroma is None else chroma[1], sstride, C.c_void_p(out.data_ptr()), ostride, self.stream()),
+               "vse_yuv_resample")
+        return out
 
 
 YUV_LAYOUTS = {"i420": 0, "nv12": 1}

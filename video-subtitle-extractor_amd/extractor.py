@@ -756,6 +756,33 @@ def match_arguments(args):
     return out
 
 
+def add_square_arguments(p):
+    """--square-pixels, --sar and --resample-filter, for the command lines that take them."""
+    p.add_argument("--square-pixels", action="store_true", help="anamorphic YUV (DVD, HDV, DVCPRO HD, 1440-column broadcast): resample "
+                   "every frame to square pixels on the GPU by the Y4M header's sample aspect ratio (its A token), so that the detector "
+                   "and the recogniser see glyphs of their true width and --area is in display pixels; --size stays the stored size; "
+                   "a ratio of 1:1 or none changes nothing [off]")
+    p.add_argument("--sar", default=None, metavar="N:D", help="the sample aspect ratio, in the header's place (32:27 and 8:9 NTSC DVD, 16:11 "
+                   "PAL DVD 16:9, 4:3 HDV); the only way for a headerless YUV file; turns --square-pixels on")
+    p.add_argument("--resample-filter", default=None, choices=("bicubic", "bilinear", "lanczos"), help="--square-pixels / --sar: the "
+                   "filter [bicubic]")
+
+
+def square_arguments(args):
+    """--square-pixels, --sar and --resample-filter of a parsed command line -> the keywords ingest.open_source takes for them."""
+    sar = None
+    if args.sar is not None:
+        num, sep, den = args.sar.partition(":")
+        if not (sep and num.isdigit() and den.isdigit() and int(num) > 0 and int(den) > 0):
+            raise ValueError(f"--sar takes NUM:DEN of positive integers, not {args.sar!r}")
+        sar = (int(num), int(den))
+    if not args.square_pixels and sar is None:
+        if args.resample_filter is not None:
+            raise ValueError("--resample-filter belongs to --square-pixels or --sar N:D")
+        return {}
+    return {"square_pixels": True, "sar": sar, "resample_filter": args.resample_filter or "bicubic"}
+
+
 def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, focus_fn=None, stream_fn=None):
     """ocr: the recogniser (None: shim.OcrRecogniser on the GPU, frames staged through staging.default_uploader, YUV 4:2:0 converted
     on the device); counter: the change / hold selector's count_fn (None: the GPU's); cells_fn: the locator's (None: the GPU's);
@@ -789,6 +816,7 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
     p.add_argument("--deinterlace-thresh", type=int, default=10, metavar="N", help="--deinterlace adaptive: a sample that changed by more "
                    "than N 8-bit levels since the previous frame has moved, 0..255 [10]")
     add_match_arguments(p)
+    add_square_arguments(p)
     p.add_argument("--transfer", default=None, choices=("pq", "hlg"), help="HDR video (needs --wide-yuv or --pix-fmt, normally with --matrix "
                    "bt2020): undo PQ (UHD Blu-ray, streaming masters) or HLG (UHD broadcast) and tone-map to SDR on the GPU; Y4M carries no tag "
                    "for it [none: the samples are taken as SDR and HDR material comes out flat]")
@@ -869,7 +897,7 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
         source = ingest.open_source(args.video, fps=args.fps, size=size, layout=args.layout, matrix=args.matrix,
                                     wide=args.wide_yuv or args.deinterlace is not None, range=args.range, pix_fmt=args.pix_fmt,
                                     deinterlace=args.deinterlace, field_order=args.field_order, deinterlace_thresh=args.deinterlace_thresh,
-                                    **match_arguments(args), **tone_arguments(args))
+                                    **match_arguments(args), **tone_arguments(args), **square_arguments(args))
         uploader = None
         if ocr is None:
             if args.weights_dir is not None:

@@ -44,6 +44,7 @@ Pipes (Y4mStream): `ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | pyth
 codec through a decoder that is not ours; the stream is read once, front to back, never seeks and has no read(): its absence is how
 SubtitleExtractor sees that it must work in one pass.
 """
+import logging
 import mmap
 import os
 import re
@@ -616,16 +617,208 @@ def _source_tone(name, transfer, tone_params, matrix, takes):
     return ToneMap(transfer, **params)
 
 
+# ---- anamorphic pictures -> square pixels (vse_yuv_resample) -------------------------------------------------------------------------
+RESAMPLE_FILTERS = ("bicubic", "bilinear", "lanczos")
+RESAMPLE_MAX_TAPS = 16
+_FILTER_SUPPORT = {"bicubic": 2.0, "bilinear": 1.0, "lanczos": 3.0}
+_log = logging.getLogger(__name__)
+
+
+def display_width(width, num, den):
+    """The columns a picture of `width` stored columns is shown with at the sample aspect ratio num:den: the nearest even number."""
+    return 2 * ((int(width) * int(num) + int(den)) // (2 * int(den)))
+
+
+def _filter_kernel(name, t):
+    a = np.abs(np.asarray(t, np.float64))
+    if name == "bilinear":
+        return np.maximum(1.0 - a, 0.0)
+    if name == "bicubic":                 # Catmull-Rom: B = 0, C = 1/2
+        return np.where(a < 1.0, (1.5 * a - 2.5) * a * a + 1.0, np.where(a < 2.0, ((-0.5 * a + 2.5) * a - 4.0) * a + 2.0, 0.0))
+    return np.where(a < 3.0, np.sinc(a) * np.sinc(a / 3.0), 0.0)
+
+
+def resample_taps(pw_in, pw_out, name):
+    """The taps a table of `name` from pw_in to pw_out columns needs: the smallest even number >= 2 support max(1, pw_in / pw_out)."""
+    need = int(np.ceil(2.0 * _FILTER_SUPPORT[name] * max(1.0, pw_in / pw_out)))
+    return need + (need & 1)
+
+
+def _check_taps(pw_in, pw_out, name):
+    taps = resample_taps(pw_in, pw_out, name)
+    if taps > RESAMPLE_MAX_TAPS:
+        raise ValueError(f"resample filter {name!r} from {pw_in} to {pw_out} columns needs {taps} taps, more than the {RESAMPLE_MAX_TAPS} "
+                         "the device takes: choose a narrower filter or a smaller reduction")
+    return taps
+
+
+def check_resample_table(left, coef):
+    """The bounds vse_yuv_resample's int32 sums rest on: taps even and 2..16, |left| <= 2^30, every row's sum of |coef| <= 32767."""
+    left, coef = np.asarray(left), np.asarray(coef)
+    if coef.ndim != 2 or left.shape != coef.shape[:1] or coef.shape[1] % 2 or not 2 <= coef.shape[1] <= RESAMPLE_MAX_TAPS:
+        raise ValueError(f"a resample table is left[P] and coef[P][K] with K even and 2..{RESAMPLE_MAX_TAPS}, not {left.shape} and {coef.shape}")
+    worst = int(np.abs(coef.astype(np.int64)).sum(axis=1).max())
+    if worst > 32767 or int(np.abs(left.astype(np.int64)).max()) > 1 << 30:
+        raise ValueError(f"a resample table's rows may sum to at most 32767 in absolute values (here {worst}) and |left| <= 2^30")
+
+
+def resample_table(pw_in, pw_out, name):
+    """-> (left int32[pw_out], coef int16[pw_out, K]) of include/vse_hip.h vse_yuv_resample for one plane, built in float64: centre c =
+    (x + 1/2) pw_in / pw_out - 1/2, the filter stretched by max(1, pw_in / pw_out), left = floor(c - support stretch) + 1, the weights
+    normalised, rounded to Q14 and the rounding remainder added to the largest tap, so that every row sums to exactly 16384."""
+    taps = _check_taps(pw_in, pw_out, name)
+    stretch = max(1.0, pw_in / pw_out)
+    c = (np.arange(pw_out, dtype=np.float64) + 0.5) * pw_in / pw_out - 0.5
+    left = np.floor(c - _FILTER_SUPPORT[name] * stretch).astype(np.int64) + 1
+    w = _filter_kernel(name, (left[:, None] + np.arange(taps)[None, :] - c[:, None]) / stretch)
+    w /= w.sum(axis=1, keepdims=True)
+    q = np.rint(w * 16384.0).astype(np.int64)
+    q[np.arange(pw_out), np.argmax(w, axis=1)] += 16384 - q.sum(axis=1)
+    left, coef = left.astype(np.int32), q.astype(np.int16)
+    check_resample_table(left, coef)
+    for a in (left, coef):
+        a.setflags(write=False)
+    return left, coef
+
+
+def resample_rows(rows, left, coef, comps=1, shift=0, maxv=255):
+    """The arithmetic of vse_yuv_resample on rows [r, pw * comps] of stored words (comps 2: an interleaved UV plane) -> [r, P * comps] of
+    the same dtype: acc = sum coef[x][k] S[clamp(left[x] + k, 0, pw - 1)], out = clip(0, maxv, (acc + 8192) >> 14), S = word >> shift and
+    the result << shift."""
+    rows = np.asarray(rows)
+    s = rows.astype(np.int32) >> shift
+    pw = s.shape[1] // comps
+    out = np.empty((s.shape[0], len(left) * comps), rows.dtype)
+    idx = np.clip(left.astype(np.int64)[:, None] + np.arange(coef.shape[1])[None, :], 0, pw - 1)
+    for e in range(comps):
+        acc = np.zeros((s.shape[0], len(left)), np.int32)
+        for k in range(coef.shape[1]):
+            acc += s[:, idx[:, k] * comps + e] * coef[:, k].astype(np.int32)
+        out[:, e::comps] = np.clip((acc + np.int32(8192)) >> 14, 0, maxv) << shift
+    return out
+
+
+_RESAMPLE_TABLES = {}
+
+
+class Resample(namedtuple("Resample", "in_width out_width filter")):
+    """How pictures of in_width stored columns become pictures of out_width columns (anamorphic video shown with square pixels): the data
+    of include/vse_hip.h vse_yuv_resample.  filter "bicubic" (Catmull-Rom) | "bilinear" | "lanczos" (a = 3).  A tuple: equal resamples
+    compare and hash equal, and the tables are built once per distinct one.  ValueError when the filter needs more than 16 taps."""
+    __slots__ = ()
+
+    def __new__(cls, in_width, out_width, filter="bicubic"):
+        if filter not in RESAMPLE_FILTERS:
+            raise ValueError(f"resample filter must be one of {RESAMPLE_FILTERS}, not {filter!r}")
+        if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1 for v in (in_width, out_width)):
+            raise ValueError(f"a resample takes widths of at least 1 column, not {in_width!r} -> {out_width!r}")
+        self = super().__new__(cls, int(in_width), int(out_width), filter)
+        _check_taps(self.in_width, self.out_width, filter)
+        return self
+
+    @classmethod
+    def from_sar(cls, width, num, den, filter="bicubic"):
+        """The resample that shows `width` stored columns at the sample aspect ratio num:den (display_width)."""
+        out = display_width(width, num, den)
+        if out < 2:
+            raise ValueError(f"sample aspect ratio {num}:{den} shows {width} columns as {out}")
+        return cls(width, out, filter)
+
+    def tables(self, fmt):
+        """-> ((left, coef) of luma, (left, coef) of the chroma planes or None for grey), read-only (resample_table)."""
+        key = (self, fmt.sub_x, bool(fmt.chroma))
+        hit = _RESAMPLE_TABLES.get(key)
+        if hit is None:
+            chroma = None
+            if fmt.chroma:
+                chroma = resample_table(fmt.chroma_size(1, self.in_width)[1], fmt.chroma_size(1, self.out_width)[1], self.filter)
+            hit = _RESAMPLE_TABLES[key] = (resample_table(self.in_width, self.out_width, self.filter), chroma)
+        return hit
+
+    def packed(self, fmt):
+        """The tables as the device takes them: (luma bytes, chroma bytes or None), each left (little-endian int32) then coef (int16)."""
+        return tuple(None if t is None else t[0].astype("<i4").tobytes() + t[1].astype("<i2").tobytes() for t in self.tables(fmt))
+
+    def planes(self, fmt, planes):
+        """Plane rows of `fmt` (stored words) -> the same rows resampled, by the integers of vse_yuv_resample in numpy."""
+        shift, maxv = (16 - fmt.depth if fmt.msb else 0), (1 << fmt.depth) - 1
+        luma, chroma = self.tables(fmt)
+        return tuple(resample_rows(p, *(chroma if k else luma), comps=2 if k and fmt.chroma == 2 else 1, shift=shift, maxv=maxv)
+                     for k, p in enumerate(planes))
+
+
+def _check_resample(resample, width):
+    if resample is not None:
+        if not (hasattr(resample, "tables") and hasattr(resample, "packed") and hasattr(resample, "out_width")):
+            raise ValueError(f"resample must be None or a Resample, not {resample!r}")
+        if resample.in_width != width:
+            raise ValueError(f"the resample is for {resample.in_width} stored columns, the picture has {width}")
+    return resample
+
+
+def parse_y4m_aspect(line):
+    """The sample aspect ratio (num, den) of a YUV4MPEG2 stream header's A token; None without one, for A0:0 (unknown) and for anything
+    that is not a ratio of integers."""
+    for tok in (line or b"")[10:].decode("ascii", "replace").split():
+        m = re.match(r"A(\d+):(\d+)$", tok)
+        if m:
+            num, den = int(m.group(1)), int(m.group(2))
+            return (num, den) if num > 0 and den > 0 else None
+    return None
+
+
+def _check_sar(name, square_pixels, sar, resample_filter):
+    """The sources' three options, checked -> whether the option is on."""
+    if resample_filter not in RESAMPLE_FILTERS:
+        raise ValueError(f"{name}: resample_filter must be one of {RESAMPLE_FILTERS}, not {resample_filter!r}")
+    if sar is not None:
+        if (not isinstance(sar, (tuple, list)) or len(sar) != 2
+                or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1 for v in sar)):
+            raise ValueError(f"{name}: sar must be None or (num, den) of positive integers, not {sar!r}")
+    if not (square_pixels or sar is not None) and resample_filter != "bicubic":
+        raise ValueError(f"{name}: resample_filter belongs to square_pixels=True or sar=(num, den)")
+    return bool(square_pixels) or sar is not None
+
+
+def _y4m_width(line):
+    """The W token of a YUV4MPEG2 stream header as an integer; None where the header has none (its parser then says so)."""
+    for tok in (line or b"")[10:].decode("ascii", "replace").split():
+        if tok[0] == "W" and tok[1:].isdigit():
+            return int(tok[1:])
+    return None
+
+
+def _source_resample(name, width, header, square_pixels, sar, resample_filter):
+    """The one decision of a source's three options: the Resample its frames carry, from sar, else with square_pixels from the header's
+    ratio; None with the option off, and None with exactly one log line where it is on and there is nothing to do: no ratio, 1:1, or a
+    ratio that shows the stored width.  width None (a header without one): None, the header's parser refuses it."""
+    if not _check_sar(name, square_pixels, sar, resample_filter) or not width:
+        return None
+    ratio = tuple(int(v) for v in sar) if sar is not None else header
+    if ratio is None or ratio[0] == ratio[1]:
+        _log.info("%s: %s: the frames are left as stored", name, "no sample aspect ratio" if ratio is None else "square pixels (1:1)")
+        return None
+    r = Resample.from_sar(width, ratio[0], ratio[1], resample_filter)
+    if r.out_width == width:
+        _log.info("%s: sample aspect ratio %d:%d shows %d columns as %d: the frames are left as stored", name, ratio[0], ratio[1], width, width)
+        return None
+    return r
+
+
 class YuvFrame:
     """Yuv420Frame for any YuvFormat `fmt`: rows [y0, y1) of one picture that has not been converted.  planes are views of samples (uint8,
     or little-endian uint16 above 8 bits) of fmt.plane_shapes(height, width).  shape == (y1 - y0, width, 3), frame[a:b] narrows the row
     range, to_bgr() gives the uint8 BGR ndarray by the integers of vse_yuv_to_bgr_format, pack_into() the packed sub-frame it takes.
-    tone: a ToneMap; to_bgr() and the device then convert by the integers of vse_yuv_to_bgr_tonemap; it travels with the slices."""
+    tone: a ToneMap; to_bgr() and the device then convert by the integers of vse_yuv_to_bgr_tonemap; it travels with the slices.
+    resample: a Resample whose in_width is `width` (anamorphic video): every plane's rows are resampled to resample.out_width columns by
+    the integers of vse_yuv_resample before the conversion, on the host in to_bgr() and on the device in staging.Uploader; shape then
+    reports the output width, while width, the planes and the packing stay the stored ones."""
 
-    def __init__(self, planes, height, width, fmt, y0=0, y1=None, tone=None):
+    def __init__(self, planes, height, width, fmt, y0=0, y1=None, tone=None, resample=None):
         if not isinstance(fmt, YuvFormat):
             raise ValueError(f"fmt must be a YuvFormat, not {fmt!r}")
         self.tone = _check_tone(tone)
+        self.resample = _check_resample(resample, int(width))
         self.planes, self.height, self.width, self.fmt = tuple(planes), int(height), int(width), fmt
         self.y0, self.y1 = int(y0), int(self.height if y1 is None else y1)
         want = fmt.plane_shapes(self.height, self.width)
@@ -636,7 +829,7 @@ class YuvFrame:
 
     @property
     def shape(self):
-        return (self.y1 - self.y0, self.width, 3)
+        return (self.y1 - self.y0, self.width if self.resample is None else self.resample.out_width, 3)
 
     @property
     def matrix(self):
@@ -648,7 +841,7 @@ class YuvFrame:
         a, b, step = idx.indices(self.y1 - self.y0)
         if step != 1:
             raise TypeError(f"a YuvFrame takes a row slice of step 1, not {idx!r}")
-        return YuvFrame(self.planes, self.height, self.width, self.fmt, self.y0 + a, self.y0 + max(a, b), self.tone)
+        return YuvFrame(self.planes, self.height, self.width, self.fmt, self.y0 + a, self.y0 + max(a, b), self.tone, self.resample)
 
     @property
     def row_parity(self):
@@ -678,7 +871,12 @@ class YuvFrame:
 
     def to_bgr(self):
         """uint8 BGR [y1 - y0, W, 3]: nearest chroma, the integers of vse_yuv_to_bgr_format (include/vse_hip.h) in int32, or with a
-        tone those of vse_yuv_to_bgr_tonemap."""
+        tone those of vse_yuv_to_bgr_tonemap; with a resample the rows of every plane go through the integers of vse_yuv_resample first."""
+        if self.resample is not None:
+            c0, c1 = self._chroma_rows()
+            rows = self.resample.planes(self.fmt, (self.planes[0][self.y0:self.y1],) + tuple(p[c0:c1] for p in self.planes[1:]))
+            return _rows_to_bgr(self.fmt, rows[0], rows[1:], (np.arange(self.y0, self.y1) >> self.fmt.sub_y) - c0, self.resample.out_width,
+                                self.tone)
         return _rows_to_bgr(self.fmt, self.planes[0][self.y0:self.y1], self.planes[1:], np.arange(self.y0, self.y1) >> self.fmt.sub_y, self.width,
                             self.tone)
 
@@ -805,7 +1003,8 @@ class InterlacedYuvFrame(YuvFrame):
     plane tuple of the previous picture (None: the clip's first frame, interpolated throughout).  field_order "tff" | "bff" names the field
     that comes first in time (its rows are kept), mode is "adaptive" (weave what did not change by more than `thresh` 8-bit levels) or
     "interpolate".  frame[a:b] is the same class with the same prev; to_bgr() deinterlaces on the host by the same integers and converts
-    as YuvFrame does, so f[a:b].to_bgr() == f.to_bgr()[a:b]; staging.Uploader deinterlaces and converts on the device.
+    as YuvFrame does, so f[a:b].to_bgr() == f.to_bgr()[a:b]; staging.Uploader deinterlaces and converts on the device.  With a resample
+    (YuvFrame's) the order is deinterlace or match, then resample, then convert.
     mode "match" (film carried in interlaced video: 3:2 pulldown, shifted fields) follows vse_yuv_field_match instead: the whole frame is
     woven from its own fields or with a field of prev, whichever combs least by `comb_thresh` 8-bit levels (match_stats()), and a frame
     that combs by more than `comb_limit` per mille (None: never) with every partner is video and gets the adaptive rule with `thresh`.
@@ -814,8 +1013,8 @@ class InterlacedYuvFrame(YuvFrame):
     choice (always in a static band, where the candidates are equal)."""
 
     def __init__(self, planes, height, width, fmt, prev=None, field_order="tff", mode="adaptive", thresh=10, y0=0, y1=None, tone=None,
-                 comb_thresh=10, comb_limit=20):
-        super().__init__(planes, height, width, fmt, y0, y1, tone)
+                 comb_thresh=10, comb_limit=20, resample=None):
+        super().__init__(planes, height, width, fmt, y0, y1, tone, resample)
         self.thresh = _check_deinterlace(mode, field_order, thresh, FIELD_ORDERS)
         self.comb_thresh, self.comb_limit = _check_match(comb_thresh, comb_limit)
         self._stats = None
@@ -843,7 +1042,7 @@ class InterlacedYuvFrame(YuvFrame):
         if step != 1:
             raise TypeError(f"an InterlacedYuvFrame takes a row slice of step 1, not {idx!r}")
         return InterlacedYuvFrame(self.planes, self.height, self.width, self.fmt, self.prev, self.field_order, self.mode, self.thresh,
-                                  self.y0 + a, self.y0 + max(a, b), self.tone, self.comb_thresh, self.comb_limit)
+                                  self.y0 + a, self.y0 + max(a, b), self.tone, self.comb_thresh, self.comb_limit, self.resample)
 
     def match_stats(self):
         """mode "match": (count c, count p1, count p2, choice 0..3) of vse_yuv_field_match over the luma rows of band()."""
@@ -875,8 +1074,11 @@ class InterlacedYuvFrame(YuvFrame):
     def to_bgr(self):
         c0, c1 = self._chroma_rows()
         chroma = [self._deinterlaced(k, c0, c1) for k in range(1, len(self.planes))]
-        return _rows_to_bgr(self.fmt, self._deinterlaced(0, self.y0, self.y1), chroma, (np.arange(self.y0, self.y1) >> self.fmt.sub_y) - c0,
-                            self.width, self.tone)
+        luma, width = self._deinterlaced(0, self.y0, self.y1), self.width
+        if self.resample is not None:                              # deinterlace or match, then resample, then convert
+            rows = self.resample.planes(self.fmt, [luma] + chroma)
+            luma, chroma, width = rows[0], rows[1:], self.resample.out_width
+        return _rows_to_bgr(self.fmt, luma, chroma, (np.arange(self.y0, self.y1) >> self.fmt.sub_y) - c0, width, self.tone)
 
     def band(self):
         """(a, b): the rows packed for the device in place of [y0, y1): two more on either side, a rounded down to a multiple of 4 and b up to
@@ -908,10 +1110,11 @@ def _planes_at(buf, off, height, width, fmt):
     return tuple(planes)
 
 
-def write_yuv(path, frames_planes, fmt, fps=None, y4m=False, interlace="p"):
+def write_yuv(path, frames_planes, fmt, fps=None, y4m=False, interlace="p", aspect=(1, 1)):
     """Frames given as plane tuples of `fmt` (fmt.plane_shapes, samples as integers) -> a headerless file (`ffmpeg -f rawvideo -pix_fmt
     ...`), or with y4m=True and a frame rate the YUV4MPEG2 file `ffmpeg -f yuv4mpegpipe -strict -1` writes for that format (planar or grey,
-    value in the low bits).  interlace: the header's I token, "p" progressive | "t" top field first | "b" bottom field first."""
+    value in the low bits).  interlace: the header's I token, "p" progressive | "t" top field first | "b" bottom field first; aspect:
+    its A token, the sample aspect ratio (num, den)."""
     if interlace not in ("p", "t", "b"):
         raise ValueError(f"interlace must be one of 'p', 't', 'b', not {interlace!r}")
     frames_planes = [tuple(np.ascontiguousarray(p, fmt.sample_dtype) for p in f) for f in frames_planes]
@@ -926,8 +1129,9 @@ def write_yuv(path, frames_planes, fmt, fps=None, y4m=False, interlace="p"):
                 name += ("" if fmt.chroma == 0 else "p") + str(fmt.depth)
             elif name == "420":
                 name = "420jpeg"
-            fp.write(b"YUV4MPEG2 W%d H%d F%d:%d I%s A1:1 C%s XCOLORRANGE=%s\n" % (w, h, rate.numerator, rate.denominator, interlace.encode(),
-                                                                                 name.encode(), b"FULL" if fmt.full_range else b"LIMITED"))
+            fp.write(b"YUV4MPEG2 W%d H%d F%d:%d I%s A%d:%d C%s XCOLORRANGE=%s\n" % (w, h, rate.numerator, rate.denominator, interlace.encode(),
+                                                                                   int(aspect[0]), int(aspect[1]), name.encode(),
+                                                                                   b"FULL" if fmt.full_range else b"LIMITED"))
         for f in frames_planes:
             if [p.shape for p in f] != fmt.plane_shapes(h, w):
                 raise ValueError(f"the planes of a {h} x {w} picture of {fmt} are {fmt.plane_shapes(h, w)}, got {[p.shape for p in f]}")
@@ -997,6 +1201,7 @@ class _Yuv420FileSource:
     deinterlace_thresh = 10
     comb_thresh, comb_limit = 10, 20      # deinterlace "match"'s (InterlacedYuvFrame)
     tone = None                   # a ToneMap (transfer="pq" | "hlg" on the readers of YuvFrames): the frames carry it
+    resample = None               # a Resample (square_pixels=True | sar=(num, den) on the readers of YuvFrames): the frames carry it
     _last = None                  # (frame number, planes) of the last read_raw: the next frame's prev is then the same views
 
     def _planes(self, frame_no):
@@ -1028,9 +1233,9 @@ class _Yuv420FileSource:
         if self.fmt is not None and self.field_order is not None:
             prev = self._planes(frame_no - 1) if frame_no > 1 else None
             return InterlacedYuvFrame(self._planes(frame_no), h, w, self.fmt, prev, self.field_order, self.deinterlace, self.deinterlace_thresh,
-                                      tone=self.tone, comb_thresh=self.comb_thresh, comb_limit=self.comb_limit)
+                                      tone=self.tone, comb_thresh=self.comb_thresh, comb_limit=self.comb_limit, resample=self.resample)
         if self.fmt is not None:
-            return YuvFrame(_planes_at(self._buf, off, h, w, self.fmt), h, w, self.fmt, tone=self.tone)
+            return YuvFrame(_planes_at(self._buf, off, h, w, self.fmt), h, w, self.fmt, tone=self.tone, resample=self.resample)
         luma = self._buf[off:off + h * w].reshape(h, w)
         off += h * w
         if self.layout == "i420":
@@ -1163,14 +1368,18 @@ class Y4mSource(_Yuv420FileSource):
     headers as parse_y4m_header_fields reads them with `field_order`; the frames of woven fields are InterlacedYuvFrames, each with the
     frame before it as its prev, read() and frames() deinterlace on the host.  transfer="pq" | "hlg" (needs wide=True; Y4M carries no tag for
     it) with tone_params (ToneMap's fields but transfer; primaries default to "bt2020" under matrix="bt2020", else "bt709") attaches a
-    ToneMap to the frames: HDR material comes out as SDR."""
+    ToneMap to the frames: HDR material comes out as SDR.  square_pixels=True (the header's A token), sar=(num, den) (in its place) and
+    resample_filter attach a Resample from the stored width to display_width() of it: the frames are then YuvFrames whatever `wide` says,
+    their shape is the display size and to_bgr() / the Uploader resample every plane along its rows before the conversion; a ratio of
+    1:1, no ratio, or one that shows the stored width changes nothing (one line is logged)."""
 
     layout = "i420"
 
     def __init__(self, path, fps=None, matrix="bt601", wide=False, range="auto", deinterlace=None, field_order="auto", deinterlace_thresh=10,
-                 transfer=None, tone_params=None, comb_thresh=10, comb_limit=20):
+                 transfer=None, tone_params=None, comb_thresh=10, comb_limit=20, square_pixels=False, sar=None, resample_filter="bicubic"):
         self.deinterlace_thresh = _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
         self.comb_thresh, self.comb_limit = _check_match(comb_thresh, comb_limit)
+        _check_sar(path, square_pixels, sar, resample_filter)
         if deinterlace is not None and not wide:
             raise ValueError(f"{path}: deinterlace={deinterlace!r} needs wide=True (the frames are YuvFrames)")
         self.deinterlace = deinterlace
@@ -1184,7 +1393,9 @@ class Y4mSource(_Yuv420FileSource):
         mm = self._mm
         end = mm.find(b"\n", 0, 4096) if size else -1
         line = mm[:end] if end >= 0 else None
-        if wide:
+        # decided before the parser is chosen: where nothing is attached the header goes to today's parser, with today's refusals
+        self.resample = _source_resample(path, _y4m_width(line), parse_y4m_aspect(line), square_pixels, sar, resample_filter)
+        if wide or self.resample is not None:       # resampled frames are YuvFrames whatever `wide` says
             self.width, self.height, self.fps, self.fmt, self.field_order = parse_y4m_header_fields(
                 line, path, fps, "file", matrix, range, None if deinterlace is None else field_order)
         else:
@@ -1226,10 +1437,14 @@ class Y4mStream:
 
     tone = None                       # as Y4mSource's (transfer, tone_params)
 
+    resample = None                   # as Y4mSource's (square_pixels, sar, resample_filter)
+
     def __init__(self, fileobj, fps=None, matrix="bt601", name="<stream>", wide=False, range="auto", deinterlace=None, field_order="auto",
-                 deinterlace_thresh=10, transfer=None, tone_params=None, comb_thresh=10, comb_limit=20):
+                 deinterlace_thresh=10, transfer=None, tone_params=None, comb_thresh=10, comb_limit=20, square_pixels=False, sar=None,
+                 resample_filter="bicubic"):
         self.deinterlace_thresh = _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
         self.comb_thresh, self.comb_limit = _check_match(comb_thresh, comb_limit)
+        _check_sar(name, square_pixels, sar, resample_filter)
         if deinterlace is not None and not wide:
             raise ValueError(f"{name}: deinterlace={deinterlace!r} needs wide=True (the frames are YuvFrames)")
         self.deinterlace = deinterlace
@@ -1243,7 +1458,8 @@ class Y4mStream:
         self._pos = 0                 # bytes of the stream consumed
         self._started = False
         line = self._line(4096)
-        if wide:
+        self.resample = _source_resample(name, _y4m_width(line), parse_y4m_aspect(line), square_pixels, sar, resample_filter)
+        if wide or self.resample is not None:
             self.width, self.height, self.fps, self.fmt, self.field_order = parse_y4m_header_fields(
                 line, name, fps, "stream", matrix, range, None if deinterlace is None else field_order)
         else:
@@ -1303,11 +1519,11 @@ class Y4mStream:
             if self.fmt is not None and self.field_order is not None:
                 planes = _planes_at(buf, 0, h, w, self.fmt)
                 yield InterlacedYuvFrame(planes, h, w, self.fmt, last, self.field_order, self.deinterlace, self.deinterlace_thresh, tone=self.tone,
-                                         comb_thresh=self.comb_thresh, comb_limit=self.comb_limit)
+                                         comb_thresh=self.comb_thresh, comb_limit=self.comb_limit, resample=self.resample)
                 last = planes
                 continue
             if self.fmt is not None:
-                yield YuvFrame(_planes_at(buf, 0, h, w, self.fmt), h, w, self.fmt, tone=self.tone)
+                yield YuvFrame(_planes_at(buf, 0, h, w, self.fmt), h, w, self.fmt, tone=self.tone, resample=self.resample)
                 continue
             planes = (buf[:h * w].reshape(h, w), buf[h * w:h * w + ch * cw].reshape(ch, cw), buf[h * w + ch * cw:].reshape(ch, cw))
             yield Yuv420Frame(planes, h, w, "i420", matrix=self.matrix)
@@ -1345,12 +1561,14 @@ class YuvSource(_Yuv420FileSource):
     """Yuv420Source for any YuvFormat: a headerless file of consecutive packed pictures of `fmt` (`ffmpeg -f rawvideo -pix_fmt NAME`, a
     hardware decoder's P010 surfaces), memory-mapped; read_raw / raw_frames hand out YuvFrames.  A partial last frame is dropped.
     deinterlace="adaptive" | "interpolate" | "match" (with comb_thresh, comb_limit): the pictures are woven fields and the frames InterlacedYuvFrames; a headerless file names no
-    field order, so field_order must be "tff" or "bff".  transfer, tone_params: as Y4mSource's."""
+    field order, so field_order must be "tff" or "bff".  transfer, tone_params: as Y4mSource's.  sar=(num, den), resample_filter: as
+    Y4mSource's; a headerless file carries no ratio, so square_pixels=True alone changes nothing."""
 
     def __init__(self, path, width, height, fps, fmt, deinterlace=None, field_order="auto", deinterlace_thresh=10, transfer=None, tone_params=None,
-                 comb_thresh=10, comb_limit=20):
+                 comb_thresh=10, comb_limit=20, square_pixels=False, sar=None, resample_filter="bicubic"):
         if not isinstance(fmt, YuvFormat):
             raise ValueError(f"fmt must be a YuvFormat, not {fmt!r}")
+        _check_sar(path, square_pixels, sar, resample_filter)
         self.tone = _source_tone(path, transfer, tone_params, fmt.matrix, True)
         self.deinterlace_thresh = _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
         self.comb_thresh, self.comb_limit = _check_match(comb_thresh, comb_limit)
@@ -1362,6 +1580,7 @@ class YuvSource(_Yuv420FileSource):
         self.width, self.height, self.fps = int(width), int(height), float(fps)
         if self.width < 1 or self.height < 1:
             raise ValueError(f"{path}: frame size {width} x {height}")
+        self.resample = _source_resample(path, self.width, None, square_pixels, sar, resample_filter)      # (no header: sar says the ratio)
         size = self._map(path)
         nbytes = self._frame_bytes()
         self.frame_count = size // nbytes
@@ -1373,7 +1592,8 @@ _RAW_PIX_FMT_EXT = {".p010": "p010le"}
 
 
 def open_source(path, fps=None, size=None, layout=None, matrix="bt601", wide=False, range="auto", pix_fmt=None, deinterlace=None,
-                field_order="auto", deinterlace_thresh=10, transfer=None, tone_params=None, comb_thresh=10, comb_limit=20):
+                field_order="auto", deinterlace_thresh=10, transfer=None, tone_params=None, comb_thresh=10, comb_limit=20, square_pixels=False,
+                sar=None, resample_filter="bicubic"):
     """The source of a file by its extension: .npy (needs fps), .y4m, .yuv / .i420 / .nv12 (headerless: need size=(width, height) and
     fps; `layout` overrides the extension's), anything else an AVI; "-" is a Y4mStream over standard input.  `matrix` goes to the
     YUV sources.  wide=True lets the Y4M readers accept what parse_y4m_header_wide does, with `range` ("auto": the header's).  pix_fmt
@@ -1381,7 +1601,11 @@ def open_source(path, fps=None, size=None, layout=None, matrix="bt601", wide=Fal
     ("auto": the name's own) and any matrix of YUV_FORMAT_MATRICES; it needs size and fps.  deinterlace ("adaptive" | "interpolate" |
     "match", the last with comb_thresh and comb_limit), field_order and deinterlace_thresh go to the Y4M readers (with wide=True) and to YuvSource (with pix_fmt and a field order); no other
     source takes them.  transfer ("pq" | "hlg") and tone_params (ToneMap's other fields) go to the same readers under the same
-    conditions: HDR material is tone-mapped to SDR; every other source refuses them."""
+    conditions: HDR material is tone-mapped to SDR; every other source refuses them.  square_pixels (use the Y4M header's sample aspect
+    ratio), sar=(num, den) (say it in its place; the only way for a headerless file) and resample_filter ("bicubic" | "bilinear" |
+    "lanczos") go to the Y4M readers and to the headerless YUV files: anamorphic video is resampled to square pixels, the frames are
+    YuvFrames whatever `wide` says (a headerless 8-bit 4:2:0 file is then read through YuvSource), and a ratio of 1:1 or none changes
+    nothing; the other sources refuse them."""
     if range not in YUV_RANGES:
         raise ValueError(f"range must be one of {YUV_RANGES}, not {range!r}")
     _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
@@ -1393,10 +1617,15 @@ def open_source(path, fps=None, size=None, layout=None, matrix="bt601", wide=Fal
         fields.update(comb_thresh=comb_thresh, comb_limit=comb_limit)
     if transfer is not None or tone_params:
         fields.update(transfer=transfer, tone_params=tone_params)
+    square = {}
+    if _check_sar(path, square_pixels, sar, resample_filter):
+        square = dict(square_pixels=square_pixels, sar=sar, resample_filter=resample_filter)
     if str(path) == "-":
         import sys
-        return Y4mStream(sys.stdin.buffer, fps, matrix, name="<stdin>", wide=wide, range=range, **fields)
+        return Y4mStream(sys.stdin.buffer, fps, matrix, name="<stdin>", wide=wide, range=range, **fields, **square)
     ext = os.path.splitext(str(path))[1].lower()
+    if square and ext != ".y4m" and pix_fmt is None and ext not in _RAW_PIX_FMT_EXT and ext not in _RAW_YUV_EXT:
+        raise ValueError(f"{path}: square_pixels / sar resample YUV4MPEG2 and headerless YUV files; BGR sources have square pixels")
     if fields and ext != ".y4m" and pix_fmt is None and (layout is not None or ext not in _RAW_PIX_FMT_EXT):
         if deinterlace is None:
             _source_tone(path, transfer, tone_params, matrix, False)         # raises, naming the option
@@ -1406,7 +1635,7 @@ def open_source(path, fps=None, size=None, layout=None, matrix="bt601", wide=Fal
             raise ValueError("a .npy frame stack carries no frame rate: pass fps")
         return NpySource(path, fps)
     if ext == ".y4m":
-        return Y4mSource(path, fps, matrix, wide=wide, range=range, **fields)
+        return Y4mSource(path, fps, matrix, wide=wide, range=range, **fields, **square)
     if pix_fmt is None and layout is None:
         pix_fmt = _RAW_PIX_FMT_EXT.get(ext)
     if pix_fmt is not None or ext in _RAW_YUV_EXT:
@@ -1417,6 +1646,14 @@ def open_source(path, fps=None, size=None, layout=None, matrix="bt601", wide=Fal
         if pix_fmt is not None:
             if layout is not None:
                 raise ValueError(f"{path}: pix_fmt {pix_fmt!r} names the plane layout; layout {layout!r} was given as well")
-            return YuvSource(path, size[0], size[1], fps, YuvFormat.from_pix_fmt(pix_fmt, matrix, range), **fields)
+            return YuvSource(path, size[0], size[1], fps, YuvFormat.from_pix_fmt(pix_fmt, matrix, range), **fields, **square)
+        resample = _source_resample(path, int(size[0]), None, square_pixels, sar, resample_filter)          # decided, and logged, here
+        if resample is not None:
+            name = {"i420": "yuv420p", "nv12": "nv12"}.get(layout or _RAW_YUV_EXT[ext])
+            if name is None:
+                raise ValueError(f"layout must be one of {YUV_LAYOUTS}, not {layout!r}")
+            src = YuvSource(path, size[0], size[1], fps, YuvFormat.from_pix_fmt(name, _check_matrix(matrix)))
+            src.resample = resample
+            return src
         return Yuv420Source(path, size[0], size[1], fps, layout or _RAW_YUV_EXT[ext], matrix)
     return AviBgr24Source(path)

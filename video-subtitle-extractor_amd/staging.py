@@ -21,7 +21,8 @@ vse_yuv_to_bgr_format, keyed by shape, format, row parity and tone map (frames w
 vse_yuv_to_bgr_tonemap; the map's table is uploaded once per context).  Interlaced pictures (ingest.InterlacedYuvFrame) are uploaded as they are,
 each beside its previous picture unless that is the frame before it in the batch, deinterlaced on the device (vse_yuv_deinterlace, or
 vse_yuv_field_match for frames of mode "match") and
-converted by the same call as the others.
+converted by the same call as the others.  Frames that carry an ingest.Resample (anamorphic video) are uploaded with their stored
+columns and resampled to square pixels on the device (vse_yuv_resample) between those two steps; the batch key gains the resample.
 """
 import queue
 import threading
@@ -128,21 +129,22 @@ class Uploader:
         return StagedBatch(dev, ev)
 
     def _stage_yuv(self, frames):
-        """ingest.YuvFrames of one shape, format, row parity and tone map -> StagedBatch of their BGR conversion: packed into the slab as
-        they are (3 bytes per pixel for 10-bit 4:2:0; frame stride rounded up to 16 bytes), one copy, one vse_yuv_to_bgr_format (with a
-        tone map: vse_yuv_to_bgr_tonemap) on the copy stream."""
+        """ingest.YuvFrames of one shape, format, row parity, tone map and resample -> StagedBatch of their BGR conversion: packed into the
+        slab as they are (3 bytes per pixel for 10-bit 4:2:0; frame stride rounded up to 16 bytes), one copy, with a resample one
+        vse_yuv_resample, one vse_yuv_to_bgr_format (with a tone map: vse_yuv_to_bgr_tonemap) on the copy stream."""
         import torch
         first = frames[0]
 
         def key_of(f):
-            return (tuple(f.shape), getattr(f, "fmt", None), getattr(f, "row_parity", None), getattr(f, "tone", None))
+            return (tuple(f.shape), getattr(f, "fmt", None), getattr(f, "row_parity", None), getattr(f, "tone", None), getattr(f, "resample", None))
         key = key_of(first)
         for f in frames:
             if key_of(f) != key:
-                raise ValueError("Uploader.stage: the YUV frames of a batch must share shape, format, row parity (y0 & sub_y) and tone map: "
-                                 f"{key} and {key_of(f)}")
+                raise ValueError("Uploader.stage: the YUV frames of a batch must share shape, format, row parity (y0 & sub_y), tone map and "
+                                 f"resample: {key} and {key_of(f)}")
         ctx = self._context()
         n, (h, w, _) = len(frames), first.shape
+        resample = getattr(first, "resample", None)
         per = (first.packed_bytes + 15) & ~15
         k, slab = self._slab(per * n)
         host = slab[:per * n].view(n, per)
@@ -151,6 +153,8 @@ class Uploader:
         with torch.cuda.stream(self._stream):
             packed = torch.empty((n, per), dtype=torch.uint8, device=self.device)          # (dropped here: see _stage_yuv420)
             packed.copy_(host, non_blocking=True)
+            if resample is not None:                   # (the resampled pictures are dropped here too)
+                packed = ctx.yuv_resample(packed, n, h, first.width, first.fmt, resample, first.row_parity)
             dev = ctx.yuv_to_bgr(packed, n, h, w, first.fmt, first.row_parity, tone=first.tone)
             ev = torch.cuda.Event()
             ev.record(self._stream)
@@ -165,19 +169,20 @@ class Uploader:
         front of its own.  One copy; then one vse_yuv_deinterlace per run of frames whose slots are laid out alike (frames without prev:
         NULL; chained frames: the slot before, stride of one slot; frames with their prev beside them: stride of two; frames of mode
         "match", which share their comb threshold and limit too: vse_yuv_field_match in the same runs), one
-        vse_yuv_to_bgr_format (with a tone map: vse_yuv_to_bgr_tonemap) over all the progressive bands, and the rows asked for cut out of it."""
+        vse_yuv_to_bgr_format (with a tone map: vse_yuv_to_bgr_tonemap) over all the progressive bands, and the rows asked for cut out of it.
+        Frames with a resample (shared too) get one vse_yuv_resample over all the progressive bands in front of the conversion."""
         import torch
         first = frames[0]
 
         def key_of(f):
             return (tuple(f.shape), getattr(f, "fmt", None), getattr(f, "y0", None), getattr(f, "height", None), getattr(f, "field_order", None),
                     getattr(f, "mode", None), getattr(f, "thresh", None), getattr(f, "tone", None), getattr(f, "comb_thresh", None),
-                    getattr(f, "comb_limit", None))
+                    getattr(f, "comb_limit", None), getattr(f, "resample", None))
         key = key_of(first)
         for f in frames:
             if not hasattr(f, "deinterlaced_planes") or key_of(f) != key:
                 raise ValueError("Uploader.stage: the interlaced YUV frames of a batch must share shape, format, first row, picture height, "
-                                 f"field order, mode, threshold, tone map, comb threshold and comb limit: {key} and {key_of(f)}")
+                                 f"field order, mode, threshold, tone map, comb threshold, comb limit and resample: {key} and {key_of(f)}")
         from .ingest import _same_planes
         ctx = self._context()
         n, w = len(frames), first.width
@@ -220,6 +225,8 @@ class Uploader:
                     continue
                 ctx.yuv_deinterlace(cur, count, b - a, w, first.fmt, prev=before, prev_stride=step * per,
                                     keep=first.keep, mode=first.mode, thresh=first.thresh, out=prog[i:i + count])
+            if first.resample is not None:             # deinterlace or match, then resample over all the progressive bands, then convert
+                prog, w = ctx.yuv_resample(prog, n, b - a, w, first.fmt, first.resample, 0), first.resample.out_width
             dev = ctx.yuv_to_bgr(prog, n, b - a, w, first.fmt, 0, tone=first.tone)
             if (first.y0 - a, first.y1 - a) != (0, b - a):
                 dev = dev[:, first.y0 - a:first.y1 - a].contiguous()
