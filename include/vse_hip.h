@@ -860,6 +860,44 @@ int vse_yuv_resample(vse_ctx* ctx, const void* d_yuv, int n, int h, int w_in, in
                      const void* d_table_c /* device, 16-byte aligned; NULL for grey */, int taps_c, int64_t yuv_frame_stride, void* d_out,
                      int64_t out_frame_stride, void* stream);
 
+/* ---- frame ingest: UHD and other oversized YUV -> fewer rows (vertical scale) ------------------------------------------------------------ */
+/* The vertical counterpart of vse_yuv_resample: n packed pictures of any format of vse_yuv_to_bgr_format's table, h_in rows high, become
+ * packed pictures of the same format and width that are h_out rows high, every plane filtered down (or up) its columns.  The order of the
+ * ingest line is vertical, then horizontal (vse_yuv_resample), then the conversion, each pass rounding to the stored depth; the integers
+ * depend on that order.  The device knows tables, not filters (vse_amd.ingest.VScale builds them).  A table for a plane of Q output rows
+ * and K taps (K even, 2..16) is top[Q] (int32) followed by coef[Q][K] (int16, Q14): the layout of the horizontal table, so
+ * vse_yuv_resample_table_bytes(Q, K) is its size; 16-byte aligned.  For a plane of ph stored rows, every column x and every output row y,
+ * int32, >> arithmetic:
+ *   acc = sum over k < K of coef[y][k] * S[clamp(top[y] + k, 0, ph - 1)][x]
+ *   out = clip(0, 2^depth - 1, (acc + 8192) >> 14)
+ * S the stored word, or with msb = 1 the word >> (16 - depth), the result then stored << (16 - depth).  Luma takes the luma table (h_in ->
+ * h_out rows), every chroma plane the chroma table (ch_in -> ch_out, ch = (h + sub_y) >> sub_y); an interleaved UV plane is a plane of
+ * 2 cw samples per row.  Grey has no chroma table.  The host guarantees sum over k of |coef[y][k]| <= 32767 for every y and |top| <= 2^30
+ * (the Python binding checks both; this call cannot read the device tables).
+ * ROW BANDS.  Input picture f, at d_yuv + f yuv_frame_stride, is the packed band of stored luma rows [s0, s1) of a picture of h_in rows:
+ * row parity s0 & sub_y, chroma rows s0 >> sub_y .. ((s1 - 1) >> sub_y) + 1, vse_yuv_frame_bytes(s1 - s0, w, ..., s0 & sub_y) bytes.  The
+ * output, at d_out + f out_frame_stride, is the packed band of output rows [y0, y1) of a picture of h_out rows: parity y0 & sub_y, chroma
+ * rows y0 >> sub_y .. ((y1 - 1) >> sub_y) + 1.  Both tables are indexed in whole-picture rows.  A source row index is clamped to the
+ * picture as above and then to the band handed in, so every load lies inside its input whatever the table says.  With a band that holds
+ * every source row that rows [y0, y1) read with a coefficient other than zero, in every plane, the second clamp changes nothing: such a
+ * band gives exactly the whole picture's rows, unconditionally.  This call cannot read the tables; the Python binding, which has them,
+ * refuses a band that does not cover that support.
+ * One launch on `stream`, no allocation, no device sync, no LDS; exactly the packed bytes of each output picture are written, the inputs
+ * and the tables are only read (keep the tables until the launch has run).  A lane owns a run of one plane row and a wave makes one
+ * output row at a time; top[y], the coefficients and the clamped source rows are the same in every lane of a wave.  Where both bases, both frame
+ * strides and every plane's row bytes and plane offsets in both bands are 16-byte aligned the run is 16 bytes, loaded once per tap and
+ * stored once; otherwise it is four samples, loaded and stored as dwords where they exist and lie aligned and sample by sample where not
+ * (2-byte samples need 2-byte aligned bases and strides).
+ * Returns VSE_E_INVAL, with the values in vse_last_error, and launches nothing, for a format outside the table, n, w, h_in or h_out < 1,
+ * h_in * w or h_out * w > 2^31 - 1, a band that is empty or not inside its picture, taps odd or outside 2..16 (taps_c only where the
+ * format has chroma), a NULL or misaligned d_table_y, a NULL or misaligned d_table_c where the format has chroma, a frame stride below
+ * the packed size, 2-byte samples at an odd base or stride, and a d_out whose pictures (first byte of the first to last byte of the
+ * last) overlap the input pictures or a table. */
+int vse_yuv_vscale(vse_ctx* ctx, const void* d_yuv, int n, int w, int h_in, int h_out, int s0, int s1, int y0, int y1, int sub_x, int sub_y,
+                   int chroma, int depth, int msb, const void* d_table_y /* device, 16-byte aligned */, int taps_y,
+                   const void* d_table_c /* device, 16-byte aligned; NULL for grey */, int taps_c, int64_t yuv_frame_stride, void* d_out,
+                   int64_t out_frame_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,18 @@
 //            2-byte samples), without a test
 //   general  any width and byte alignment (2-byte samples: 2-byte aligned): a dword where the four samples exist and lie aligned, sample
 //            by sample otherwise (the 854-byte rows of a 16:9 NTSC DVD alternate between the two)
+//
+// vse_yuv_vscale (include/vse_hip.h) stands in front of that for UHD and other oversized progressive pictures: packed pictures of h_in
+// rows become packed pictures of h_out rows of the same format and width, every plane filtered down its columns by a table of the same
+// layout (top[Q], coef[Q][K]; ingest.VScale builds them, tests/vscale_ref.py restates the integers).  Input and output are row bands of
+// their pictures (stored luma rows [s0, s1) in, output rows [y0, y1) out, chroma rows by the packing's rule), the tables are indexed in
+// whole-picture rows, and a source row is clamped to the picture and then to the band, so no table can make a load leave the input.
+// This pass coalesces by itself: a lane owns a run of a plane row, a wave makes one output row at a time, K row loads and one store per
+// output row; the output row is the same in all lanes of a wave, so top, the coefficients and the clamped rows are scalar.  Templated
+// on the sample width and a bound on the tap pairs (1, 2, 3, 4, 6, 8), in two forms:
+//   fast     bases, frame strides and every plane's row bytes and offsets in both bands 16-byte aligned: the run is 16 bytes, one
+//            load per tap and one store
+//   general  any width, pitch and byte alignment: the run is four samples through load_quad / store_quad
 #include <algorithm>
 #include <cstdio>
 
@@ -1129,6 +1141,113 @@ void launch_resample(const void* d_yuv, int n, long sstride, void* d_out, long d
                        maxv);
 }
 
+// ---- vertical scale (vse_yuv_vscale) ----------------------------------------------------------------------------------------------------
+// The planes of the packed input and output bands, in samples.  rl: samples per row (an interleaved UV row has 2 cw); ph: the rows of the
+// WHOLE input picture's plane, [b0, b1) the rows of it the input band holds, [o0, o1) the output rows to make, all in whole-picture rows
+// of the plane; top / coef: the plane's table (coef rows of `taps` int16, read as dwords).  Read with constant indices only.
+struct VsPlanes {
+    int count;
+    int rl[3], ph[3], b0[3], b1[3], o0[3], o1[3], taps[3];
+    long off_in[3], off_out[3];
+    const int* top[3];
+    const unsigned* coef[3];
+};
+
+// One plane for one lane.  The lane owns samples [V g, V g + V) of every row: FAST, V is the 16 bytes of one load or store (the launcher
+// has checked bases, row bytes and strides); otherwise 4 samples through load_quad / store_quad, which decide per quad.  A wave makes
+// one output row at a time, rows row0, row0 + row_step, ... (strips of 2, 4 and 8 consecutive rows per wave measured up to 8, 40 and 92 %
+// slower: EXPERIMENTS.md AG); the row is the same in all its lanes (row0 comes from readfirstlane), so top[r], the coefficient
+// dwords and the clamped source rows are scalar; TP is the instantiation's bound on the tap pairs (a pair at or past `taps` is zero and
+// reads a row that exists).  A source row is clamped to the picture and then to the band, so every load lies inside the input
+// whatever the table says.
+template <typename S, bool FAST, int TP>
+__device__ __forceinline__ void vscale_plane(const S* __restrict__ src, S* __restrict__ dst, int n, long sstride, long dstride, int rl, int ph,
+                                             int b0, int b1, int o0, int o1, int taps, const int* __restrict__ top,
+                                             const unsigned* __restrict__ coef, long g, int row0, int row_step, int f0, int f_step, int shift,
+                                             int maxv) {
+    constexpr int V = FAST ? 16 / (int)sizeof(S) : 4, PER = 4 / (int)sizeof(S), BITS = 8 * (int)sizeof(S), DW = V / PER;
+    constexpr unsigned ONES = (1u << BITS) - 1u;
+    const long x0 = g * V;
+    if (x0 >= rl) return;
+    const int ns = (int)min((long)V, (long)rl - x0);
+    const int rows = o1 - o0, hi = (maxv << 14) | 0x3fff;
+    for (int f = f0; f < n; f += f_step) {
+        const S* s = src + (long)f * sstride + x0;
+        S* d = dst + (long)f * dstride + x0;
+#pragma unroll 1
+        for (int t = row0; t < rows; t += row_step) {
+            const int r = o0 + t, tp = top[r];
+            const unsigned* cr = coef + (long)r * (taps >> 1);
+            int acc[V];
+#pragma unroll
+            for (int k = 0; k < V; ++k) acc[k] = 0;
+#pragma unroll
+            for (int j = 0; j < TP; ++j) {
+                const unsigned c = 2 * j < taps ? cr[j] : 0u;
+                const int kk[2] = {(int)(short)(c & 0xffffu), (int)c >> 16};
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const int i = min(max(min(max(tp + 2 * j + e, 0), ph - 1), b0), b1 - 1) - b0;
+                    const S* p = s + (long)i * rl;
+                    unsigned w[DW];
+                    if constexpr (FAST) {
+                        const uint4 v = *reinterpret_cast<const uint4*>(p);
+                        w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+                    } else {
+                        const Quad<S> q = load_quad(p, ns);
+#pragma unroll
+                        for (int k = 0; k < DW; ++k) w[k] = q.v[k];
+                    }
+#pragma unroll
+                    for (int k = 0; k < V; ++k) acc[k] += __mul24(kk[e], (int)((w[k / PER] >> (BITS * (k % PER))) & ONES) >> shift);
+                }
+            }
+            unsigned o[DW];
+#pragma unroll
+            for (int k = 0; k < DW; ++k) o[k] = 0u;
+#pragma unroll
+            for (int k = 0; k < V; ++k)
+                o[k / PER] |= ((unsigned)(min(max(acc[k] + 8192, 0), hi) >> 14) << shift) << (BITS * (k % PER));
+            S* out = d + (long)t * rl;
+            if constexpr (FAST) {
+                *reinterpret_cast<uint4*>(out) = make_uint4(o[0], o[1], o[2], o[3]);
+            } else {
+                Quad<S> q;
+#pragma unroll
+                for (int k = 0; k < DW; ++k) q.v[k] = o[k];
+                store_quad(out, q, ns);
+            }
+        }
+    }
+}
+
+// Lane (threadIdx.x, threadIdx.y) = samples V g .. V g + V - 1 of output rows of each plane; a wave is one threadIdx.y (the block is
+// GEN_LANES = 64 wide), blockIdx.y strides the rows, blockIdx.z the frames.  Strides and offsets are counted in samples.
+template <typename S, bool FAST, int TP>
+__global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void vscale_kernel(const S* __restrict__ src, int n, long sstride, S* __restrict__ dst,
+                                                                      long dstride, VsPlanes pl, int shift, int maxv) {
+    const long g = (long)blockIdx.x * GEN_LANES + threadIdx.x;
+    const int row0 = __builtin_amdgcn_readfirstlane((int)(blockIdx.y * GEN_ROWS + threadIdx.y)), row_step = (int)gridDim.y * GEN_ROWS;
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+        if (p >= pl.count) continue;
+        vscale_plane<S, FAST, TP>(src + pl.off_in[p], dst + pl.off_out[p], n, sstride, dstride, pl.rl[p], pl.ph[p], pl.b0[p], pl.b1[p], pl.o0[p],
+                                  pl.o1[p], pl.taps[p], pl.top[p], pl.coef[p], g, row0, row_step, (int)blockIdx.z, (int)gridDim.z, shift, maxv);
+    }
+}
+
+// The instantiation of an accepted call: tap pairs 1, 2, 3, 4, 6 (bilinear, bicubic and Lanczos-3 down to a reduction of 2 : 1) or 8.
+template <typename S>
+void launch_vscale(const void* d_yuv, int n, long sstride, void* d_out, long dstride, const VsPlanes& pl, int shift, int maxv, bool fast,
+                   int pairs, dim3 grid, dim3 block, hipStream_t st) {
+#define VSE_VS(TP) (fast ? vscale_kernel<S, true, TP> : vscale_kernel<S, false, TP>)
+    const auto kernel = pairs <= 1 ? VSE_VS(1) : pairs == 2 ? VSE_VS(2) : pairs == 3 ? VSE_VS(3) : pairs == 4 ? VSE_VS(4)
+                      : pairs <= 6 ? VSE_VS(6) : VSE_VS(RES_MAX_TAPS / 2);
+#undef VSE_VS
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, reinterpret_cast<const S*>(d_yuv), n, sstride, reinterpret_cast<S*>(d_out), dstride, pl, shift,
+                       maxv);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1540,6 +1659,91 @@ int vse_yuv_resample(vse_ctx* c, const void* d_yuv, int n, int h, int w_in, int 
                                   block, st);
     if (hipGetLastError() != hipSuccess) {
         vse_set_error("vse_yuv_resample: launch failed");
+        return VSE_E_HIP;
+    }
+    return VSE_OK;
+}
+
+int vse_yuv_vscale(vse_ctx* c, const void* d_yuv, int n, int w, int h_in, int h_out, int s0, int s1, int y0, int y1, int sub_x, int sub_y,
+                   int chroma, int depth, int msb, const void* d_table_y, int taps_y, const void* d_table_c, int taps_c, int64_t yuv_frame_stride,
+                   void* d_out, int64_t out_frame_stride, void* stream) {
+    // the whole pictures bound the products of rows and columns; the bands are parts of them
+    const bool whole = vse_yuv_frame_bytes(h_in, w, sub_x, sub_y, chroma, depth, 0) && vse_yuv_frame_bytes(h_out, w, sub_x, sub_y, chroma, depth, 0);
+    const bool bands = whole && s0 >= 0 && s0 < s1 && s1 <= h_in && y0 >= 0 && y0 < y1 && y1 <= h_out;
+    const size_t frame_in = bands ? vse_yuv_frame_bytes(s1 - s0, w, sub_x, sub_y, chroma, depth, s0 & sub_y) : 0;
+    const size_t frame_out = bands ? vse_yuv_frame_bytes(y1 - y0, w, sub_x, sub_y, chroma, depth, y0 & sub_y) : 0;
+    const int ss = depth > 8 ? 2 : 1;
+    const bool has_chroma = frame_in && chroma != CHROMA_NONE;
+    const int sy = sub_y & 1;
+    const int ch_out = (int)(((long)h_out + sy) >> sy);
+    const size_t table_y = frame_out ? vse_yuv_resample_table_bytes(h_out, taps_y) : 0;
+    const size_t table_c = has_chroma && frame_out ? vse_yuv_resample_table_bytes(ch_out, taps_c) : 0;
+    const auto odd = [](const void* p, int64_t stride) { return (reinterpret_cast<uintptr_t>(p) & 1) || (stride & 1); };
+    bool ok = c && d_yuv && d_out && n >= 1 && frame_in && frame_out && msb >= 0 && msb <= (ss == 2 ? 1 : 0) && table_y && d_table_y &&
+              aligned16(d_table_y) && (!has_chroma || (table_c && d_table_c && aligned16(d_table_c))) && yuv_frame_stride >= (int64_t)frame_in &&
+              out_frame_stride >= (int64_t)frame_out && !(ss == 2 && (odd(d_yuv, yuv_frame_stride) || odd(d_out, out_frame_stride)));
+    if (ok) {
+        // the output lies apart from the input pictures (first byte of the first to last byte of the last) and from both tables
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + (uintptr_t)(n - 1) * (uintptr_t)out_frame_stride + frame_out;
+        const auto apart = [&](const void* p, size_t bytes) {
+            const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+            return !p || !bytes || o1 <= a || a + bytes <= o0;
+        };
+        ok = apart(d_yuv, (size_t)(n - 1) * (size_t)yuv_frame_stride + frame_in) && apart(d_table_y, table_y) &&
+             apart(has_chroma ? d_table_c : nullptr, table_c);
+    }
+    if (!ok) {
+        char msg[1000];
+        snprintf(msg, sizeof msg, "vse_yuv_vscale: bad arguments (n %d, frames of %d columns and %d -> %d rows, each of at most 2^31 - 1 pixels, "
+                 "stored rows %d:%d and output rows %d:%d inside them and not empty, subsampling %d, %d of 0, 0 | 1, 0 | 1, 1, chroma %d of 0 (with "
+                 "subsampling 0, 0) | 1 | 2 (with subsampling 1, 1), depth %d of 8..16, msb %d of 0 | 1 (0 at depth 8), taps %d (luma) and %d "
+                 "(chroma) even and of 2..16, tables %p and %p 16-byte aligned (the chroma table only where the format has chroma), frame strides "
+                 "%lld of at least %zu and %lld (output) of at least %zu, bases %p, %p and strides 2-byte aligned for 2-byte samples, the output "
+                 "apart from the pictures and the tables)",
+                 n, w, h_in, h_out, s0, s1, y0, y1, sub_x, sub_y, chroma, depth, msb, taps_y, taps_c, d_table_y, d_table_c,
+                 (long long)yuv_frame_stride, frame_in, (long long)out_frame_stride, frame_out, d_yuv, d_out);
+        vse_set_error(msg);
+        return VSE_E_INVAL;
+    }
+    const int cw = (int)(((long)w + (sub_x & 1)) >> (sub_x & 1));
+    const int rlc = chroma == CHROMA_SEMI ? 2 * cw : cw;
+    const int cb0 = s0 >> sy, cb1 = ((s1 - 1) >> sy) + 1, co0 = y0 >> sy, co1 = ((y1 - 1) >> sy) + 1;
+    VsPlanes pl = {};
+    pl.count = chroma == CHROMA_NONE ? 1 : chroma == CHROMA_PLANAR ? 3 : 2;
+    for (int p = 0; p < pl.count; ++p) {
+        const bool luma = p == 0;
+        const uint8_t* table = reinterpret_cast<const uint8_t*>(luma ? d_table_y : d_table_c);
+        pl.rl[p] = luma ? w : rlc;
+        pl.ph[p] = luma ? h_in : (int)(((long)h_in + sy) >> sy);
+        pl.b0[p] = luma ? s0 : cb0;
+        pl.b1[p] = luma ? s1 : cb1;
+        pl.o0[p] = luma ? y0 : co0;
+        pl.o1[p] = luma ? y1 : co1;
+        pl.taps[p] = luma ? taps_y : taps_c;
+        pl.off_in[p] = luma ? 0 : (long)(s1 - s0) * w + (long)(p - 1) * (cb1 - cb0) * rlc;
+        pl.off_out[p] = luma ? 0 : (long)(y1 - y0) * w + (long)(p - 1) * (co1 - co0) * rlc;
+        pl.top[p] = reinterpret_cast<const int*>(table);
+        pl.coef[p] = reinterpret_cast<const unsigned*>(table + 4L * (luma ? h_out : ch_out));
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // the fast kernel: every plane's rows of both bands start on a 16-byte boundary and are whole 16-byte runs
+    bool fast = aligned16(d_yuv) && aligned16(d_out) && yuv_frame_stride % 16 == 0 && out_frame_stride % 16 == 0;
+    for (int p = 0; p < pl.count; ++p)
+        fast = fast && ((long)pl.rl[p] * ss) % 16 == 0 && (pl.off_in[p] * ss) % 16 == 0 && (pl.off_out[p] * ss) % 16 == 0;
+    const long widest = std::max((long)w, (long)(pl.count > 1 ? rlc : 0)), per = fast ? 16 / ss : 4;
+    const long groups = (widest + per - 1) / per;
+    const int rows = y1 - y0;                                     // (no chroma plane has more output rows than luma)
+    const dim3 grid((unsigned)((groups + GEN_LANES - 1) / GEN_LANES), (unsigned)std::min((rows + GEN_ROWS - 1) / GEN_ROWS, 65535),
+                    (unsigned)std::min(n, 65535));
+    const dim3 block(GEN_LANES, GEN_ROWS);
+    const int shift = msb ? 16 - depth : 0, maxv = (1 << depth) - 1;
+    const int pairs = std::max(taps_y, has_chroma ? taps_c : 0) / 2;
+    if (ss == 1)
+        launch_vscale<uint8_t>(d_yuv, n, (long)yuv_frame_stride, d_out, (long)out_frame_stride, pl, shift, maxv, fast, pairs, grid, block, st);
+    else
+        launch_vscale<uint16_t>(d_yuv, n, (long)yuv_frame_stride / 2, d_out, (long)out_frame_stride / 2, pl, shift, maxv, fast, pairs, grid, block, st);
+    if (hipGetLastError() != hipSuccess) {
+        vse_set_error("vse_yuv_vscale: launch failed");
         return VSE_E_HIP;
     }
     return VSE_OK;

@@ -34,6 +34,7 @@ EXPORTS = [
     "vse_interval_stream_state_bytes", "vse_interval_stream",
     "vse_yuv_frame_bytes", "vse_yuv_to_bgr_format", "vse_yuv_deinterlace", "vse_yuv_field_match",
     "vse_yuv_tonemap_table_bytes", "vse_yuv_to_bgr_tonemap", "vse_yuv_resample_table_bytes", "vse_yuv_resample",
+    "vse_yuv_vscale",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -250,6 +251,8 @@ def load_library(path=None):
     lib.vse_yuv_resample_table_bytes.argtypes = [C.c_int, C.c_int]
     lib.vse_yuv_resample.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 10 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
                                      C.c_int64, C.c_void_p]
+    lib.vse_yuv_vscale.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 13 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
+                                   C.c_int64, C.c_void_p]
     lib.vse_yuv_deinterlace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 11 + [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     lib.vse_yuv_field_match.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 12 + [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                                                                                  C.c_void_p]
@@ -306,6 +309,7 @@ class Context:
         self._tone_tables = {}            # ingest.ToneMap -> (cuda uint8 [16128] table, its gamut as int32[9]): uploaded once
         self._tone_lock = threading.Lock()
         self._resample_tables = {}        # (ingest.Resample, sub_x, has chroma) -> ((cuda uint8 luma table, taps), (chroma table, taps) | None)
+        self._vscale_tables = {}          # (ingest.VScale, sub_y, has chroma) -> the same, each with its rows' support (lo, hi) on the host
 
     def stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.tdev).cuda_stream)
@@ -1157,6 +1161,90 @@ class Context:
                                          C.c_void_p(luma[0].data_ptr()), luma[1], None if chroma is None else C.c_void_p(chroma[0].data_ptr()),
                                          0 if chroma is None else chroma[1], sstride, C.c_void_p(out.data_ptr()), ostride, self.stream()),
                "vse_yuv_resample")
+        return out
+
+    def vscale_tables(self, vscale, fmt):
+        """The device copies of an ingest.VScale's tables for the format `fmt` (anything hashable with in_height, out_height, tables(fmt)
+        -> ((top, coef), (top, coef) | None) and packed(fmt) -> (luma bytes, chroma bytes | None)): ((cuda uint8 table, taps, lo, hi), the
+        same for chroma or None), uploaded on first use and kept for the context's life.  lo, hi: per output row the stored rows [lo, hi)
+        of the plane that it reads with a coefficient other than zero (ingest.table_support), for the band check of yuv_vscale.
+        vse_yuv_vscale cannot read the tables, so the bounds that keep its int32 sums exact are checked here: |top| <= 2^30 and every
+        row's sum of |coef| <= 32767."""
+        from .ingest import table_support
+        sy = int(fmt.sub_y)
+        key = (vscale, sy, bool(fmt.chroma))
+        with self._tone_lock:
+            hit = self._vscale_tables.get(key)
+            if hit is None:
+                t = self.torch
+                h_in, h_out = int(vscale.in_height), int(vscale.out_height)
+                devs = []
+                for what, tab, raw, rows, ph in zip(("luma", "chroma"), vscale.tables(fmt), vscale.packed(fmt), (h_out, (h_out + sy) >> sy),
+                                                    (h_in, (h_in + sy) >> sy)):
+                    if tab is None:
+                        devs.append(None)
+                        continue
+                    top, coef = np.asarray(tab[0]), np.asarray(tab[1])
+                    taps = int(coef.shape[1]) if coef.ndim == 2 else 0
+                    host = np.frombuffer(raw, np.uint8)
+                    want = self.lib.vse_yuv_resample_table_bytes(rows, taps)
+                    if not want or top.shape != (rows,) or coef.shape != (rows, taps) or host.size != want:
+                        raise VseError(f"vscale_tables: the {what} table of {rows} rows has top {top.shape}, coef {coef.shape} (taps even, "
+                                       f"2..16) and {host.size} bytes of {want}")
+                    if np.abs(top.astype(np.int64)).max() > 1 << 30 or np.abs(coef.astype(np.int64)).sum(axis=1).max() > 32767:
+                        raise VseError(f"vscale_tables: the {what} table breaks |top| <= 2^30 or a row's sum of |coef| <= 32767 (max "
+                                       f"{int(np.abs(coef.astype(np.int64)).sum(axis=1).max())}): int32 would not be exact")
+                    devs.append((t.from_numpy(host.copy()).to(self.tdev), taps) + table_support(top, coef, ph))
+                if devs[0] is None or (devs[1] is None) != (not fmt.chroma):
+                    raise VseError(f"vscale_tables: {fmt} takes a luma table and {'a' if fmt.chroma else 'no'} chroma table")
+                t.cuda.current_stream(self.tdev).synchronize()          # any stream may read them from here on
+                hit = self._vscale_tables[key] = tuple(devs)
+            return hit
+
+    def yuv_vscale(self, packed, n, h_in, w, fmt, vscale, s0, s1, y0, y1, out=None):
+        """packed: cuda uint8 holding n packed bands of stored luma rows [s0, s1) of pictures of h_in x w pixels of the format `fmt` (what
+        ingest.YuvFrame.pack_into writes), 1-D (back to back) or 2-D [n, stride in bytes] -> cuda uint8 [n, stride] of the packed bands of
+        output rows [y0, y1) of the pictures scaled to vscale.out_height rows, same width, on the current stream (include/vse_hip.h
+        vse_yuv_vscale).  vscale: an ingest.VScale (see vscale_tables) whose in_height is h_in.  The band must hold every stored row that
+        rows [y0, y1) read in every plane (VScale.source_rows gives the smallest one): the device clamps to the band, and a band that is
+        too small would give other rows than the whole picture's.  out: write into this uint8 tensor (1-D or [n, stride]) instead; it
+        must not overlap the input or the tables."""
+        t = self.torch
+        n, h_in, w, s0, s1, y0, y1 = (int(v) for v in (n, h_in, w, s0, s1, y0, y1))
+        if int(vscale.in_height) != h_in:
+            raise VseError(f"yuv_vscale: the tables are for {vscale.in_height} stored rows, the pictures have {h_in}")
+        h_out, sy = int(vscale.out_height), int(fmt.sub_y)
+        form = (int(fmt.sub_x), sy, int(fmt.chroma), int(fmt.depth))
+        luma, chroma = self.vscale_tables(vscale, fmt)
+        if not (0 <= s0 < s1 <= h_in and 0 <= y0 < y1 <= h_out):
+            raise VseError(f"yuv_vscale: stored rows {s0}:{s1} of {h_in} and output rows {y0}:{y1} of {h_out} must lie inside their pictures "
+                           "and not be empty")
+        for what, tab, (a, b), (r0, r1) in (("luma", luma, (s0, s1), (y0, y1)),
+                                            ("chroma", chroma, (s0 >> sy, ((s1 - 1) >> sy) + 1), (y0 >> sy, ((y1 - 1) >> sy) + 1))):
+            if tab is None:
+                continue
+            lo, hi = int(tab[2][r0:r1].min()), int(tab[3][r0:r1].max())
+            if lo < hi and not (a <= lo and hi <= b):
+                raise VseError(f"yuv_vscale: the band of stored rows {s0}:{s1} holds {what} rows {a}:{b}, output rows {y0}:{y1} read {what} "
+                               f"rows {lo}:{hi}: the band does not cover the support")
+        frame_in = self.lib.vse_yuv_frame_bytes(s1 - s0, w, *form, s0 & sy)
+        frame_out = self.lib.vse_yuv_frame_bytes(y1 - y0, w, *form, y0 & sy)
+
+        def stride_of(a, frame, what):
+            assert a.dtype == t.uint8 and a.dim() in (1, 2) and a.stride(-1) == 1, what
+            if a.dim() == 2:
+                assert a.shape[0] == n and a.shape[1] >= frame, (what, tuple(a.shape), n, frame)
+                return a.stride(0) if n > 1 else max(a.stride(0), frame)
+            assert a.numel() >= n * frame, (what, a.numel(), n, frame)
+            return frame
+        sstride = stride_of(packed, frame_in, "packed")
+        if out is None:
+            out = t.empty((max(n, 0), (frame_out + 15) & ~15), dtype=t.uint8, device=self.tdev)
+        ostride = stride_of(out, frame_out, "out")
+        _check(self.lib.vse_yuv_vscale(self.handle, C.c_void_p(packed.data_ptr()), n, w, h_in, h_out, s0, s1, y0, y1, *form, int(fmt.msb),
+                                       C.c_void_p(luma[0].data_ptr()), luma[1], None if chroma is None else C.c_void_p(chroma[0].data_ptr()),
+                                       0 if chroma is None else chroma[1], sstride, C.c_void_p(out.data_ptr()), ostride, self.stream()),
+               "vse_yuv_vscale")
         return out
 
 

@@ -757,30 +757,45 @@ def match_arguments(args):
 
 
 def add_square_arguments(p):
-    """--square-pixels, --sar and --resample-filter, for the command lines that take them."""
+    """--square-pixels, --sar, --scale and --resample-filter, for the command lines that take them."""
     p.add_argument("--square-pixels", action="store_true", help="anamorphic YUV (DVD, HDV, DVCPRO HD, 1440-column broadcast): resample "
                    "every frame to square pixels on the GPU by the Y4M header's sample aspect ratio (its A token), so that the detector "
                    "and the recogniser see glyphs of their true width and --area is in display pixels; --size stays the stored size; "
                    "a ratio of 1:1 or none changes nothing [off]")
     p.add_argument("--sar", default=None, metavar="N:D", help="the sample aspect ratio, in the header's place (32:27 and 8:9 NTSC DVD, 16:11 "
                    "PAL DVD 16:9, 4:3 HDV); the only way for a headerless YUV file; turns --square-pixels on")
-    p.add_argument("--resample-filter", default=None, choices=("bicubic", "bilinear", "lanczos"), help="--square-pixels / --sar: the "
-                   "filter [bicubic]")
+    p.add_argument("--scale", default=None, metavar="H|WxH", help="oversized YUV (UHD): scale every frame to H rows on the GPU before "
+                   "anything else sees it, keeping the display aspect, or to W x H exactly; the detector, the recogniser and --area then "
+                   "work in output pixels, --size stays the stored size; not with --deinterlace; the size the picture already has changes "
+                   "nothing [off]")
+    p.add_argument("--resample-filter", default=None, choices=("bicubic", "bilinear", "lanczos"), help="--square-pixels / --sar / --scale: "
+                   "the filter [bicubic]")
 
 
 def square_arguments(args):
-    """--square-pixels, --sar and --resample-filter of a parsed command line -> the keywords ingest.open_source takes for them."""
+    """--square-pixels, --sar, --scale and --resample-filter of a parsed command line -> the keywords ingest.open_source takes for them."""
     sar = None
     if args.sar is not None:
         num, sep, den = args.sar.partition(":")
         if not (sep and num.isdigit() and den.isdigit() and int(num) > 0 and int(den) > 0):
             raise ValueError(f"--sar takes NUM:DEN of positive integers, not {args.sar!r}")
         sar = (int(num), int(den))
+    scale = None
+    if getattr(args, "scale", None) is not None:
+        parts = args.scale.lower().split("x")
+        if not (1 <= len(parts) <= 2 and all(v.isdigit() and int(v) > 0 for v in parts)):
+            raise ValueError(f"--scale takes H or WxH of positive integers, not {args.scale!r}")
+        scale = int(parts[0]) if len(parts) == 1 else (int(parts[0]), int(parts[1]))
     if not args.square_pixels and sar is None:
+        if scale is not None:
+            return {"scale": scale, "resample_filter": args.resample_filter or "bicubic"}
         if args.resample_filter is not None:
-            raise ValueError("--resample-filter belongs to --square-pixels or --sar N:D")
+            raise ValueError("--resample-filter belongs to --square-pixels, --sar N:D or --scale H|WxH")
         return {}
-    return {"square_pixels": True, "sar": sar, "resample_filter": args.resample_filter or "bicubic"}
+    out = {"square_pixels": True, "sar": sar, "resample_filter": args.resample_filter or "bicubic"}
+    if scale is not None:
+        out["scale"] = scale
+    return out
 
 
 def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, focus_fn=None, stream_fn=None):

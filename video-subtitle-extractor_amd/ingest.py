@@ -747,6 +747,113 @@ class Resample(namedtuple("Resample", "in_width out_width filter")):
                      for k, p in enumerate(planes))
 
 
+# ---- UHD and other oversized pictures -> fewer rows (vse_yuv_vscale) ------------------------------------------------------------------
+def vscale_rows(plane, top, coef, r0, r1, shift=0, maxv=255):
+    """The arithmetic of vse_yuv_vscale on one whole stored plane [ph, row samples] -> rows [r0, r1) of the output plane, same dtype: acc
+    = sum coef[y][k] S[clamp(top[y] + k, 0, ph - 1)], out = clip(0, maxv, (acc + 8192) >> 14), S = word >> shift and the result << shift."""
+    plane = np.asarray(plane)
+    s = plane.astype(np.int32) >> shift
+    idx = np.clip(top[r0:r1].astype(np.int64)[:, None] + np.arange(coef.shape[1])[None, :], 0, s.shape[0] - 1)
+    acc = np.zeros((max(r1 - r0, 0), s.shape[1]), np.int32)
+    for k in range(coef.shape[1]):
+        acc += s[idx[:, k]] * coef[r0:r1, k].astype(np.int32)[:, None]
+    return (np.clip((acc + np.int32(8192)) >> 14, 0, maxv) << shift).astype(plane.dtype)
+
+
+def table_support(top, coef, ph):
+    """-> (lo int64[Q], hi int64[Q]): the stored rows [lo[y], hi[y]) of a plane of ph rows that output row y of a vertical table reads with
+    a coefficient other than zero, after the clamp to the picture; lo = ph and hi = 0 for a row whose coefficients are all zero."""
+    top, coef = np.asarray(top, np.int64), np.asarray(coef)
+    idx = np.clip(top[:, None] + np.arange(coef.shape[1])[None, :], 0, ph - 1)
+    used = coef != 0
+    return np.where(used, idx, ph).min(axis=1), np.where(used, idx + 1, 0).max(axis=1)
+
+
+def band_for_support(spans, sub_y, height):
+    """spans: [(lo, hi) of luma rows, (lo, hi) of chroma rows or None], each the union of a band's support in whole-picture rows of its
+    plane (lo >= hi: nothing is read) -> (s0, s1), the smallest band of stored luma rows whose luma rows [s0, s1) and chroma rows [s0 >>
+    sub_y, ((s1 - 1) >> sub_y) + 1) hold both; (0, 1) where nothing is read at all."""
+    (lo, hi), chroma = spans[0], spans[1]
+    if chroma is not None and chroma[0] < chroma[1]:
+        c_lo, c_hi = (chroma[0] << sub_y) + sub_y, ((chroma[1] - 1) << sub_y) + 1          # the last s0 and the first s1 that hold them
+        lo, hi = (min(lo, c_lo), max(hi, c_hi)) if lo < hi else (c_lo, c_hi)
+    if lo >= hi:
+        return 0, 1
+    return int(lo), int(min(hi, height))
+
+
+_VSCALE_TABLES = {}
+
+
+class VScale(namedtuple("VScale", "in_height out_height filter")):
+    """How pictures of in_height stored rows become pictures of out_height rows (UHD and other oversized video): the data of
+    include/vse_hip.h vse_yuv_vscale.  The tables are resample_table(in_height, out_height, filter) and the same over the chroma heights:
+    same centres, stretch, Q14 rounding and rows summing to 16384 as the horizontal Resample's.  A tuple: equal scales compare and hash
+    equal, and the tables are built once per distinct one.  ValueError when the filter needs more than 16 taps."""
+    __slots__ = ()
+
+    def __new__(cls, in_height, out_height, filter="bicubic"):
+        if filter not in RESAMPLE_FILTERS:
+            raise ValueError(f"vscale filter must be one of {RESAMPLE_FILTERS}, not {filter!r}")
+        if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1 for v in (in_height, out_height)):
+            raise ValueError(f"a vscale takes heights of at least 1 row, not {in_height!r} -> {out_height!r}")
+        self = super().__new__(cls, int(in_height), int(out_height), filter)
+        _check_taps(self.in_height, self.out_height, filter)
+        return self
+
+    def tables(self, fmt):
+        """-> ((top, coef) of luma, (top, coef) of the chroma planes or None for grey), read-only (resample_table over the rows)."""
+        key = (self, fmt.sub_y, bool(fmt.chroma))
+        hit = _VSCALE_TABLES.get(key)
+        if hit is None:
+            chroma = None
+            if fmt.chroma:
+                chroma = resample_table(fmt.chroma_size(self.in_height, 1)[0], fmt.chroma_size(self.out_height, 1)[0], self.filter)
+            hit = _VSCALE_TABLES[key] = (resample_table(self.in_height, self.out_height, self.filter), chroma)
+        return hit
+
+    def packed(self, fmt):
+        """The tables as the device takes them: (luma bytes, chroma bytes or None), each top (little-endian int32) then coef (int16)."""
+        return tuple(None if t is None else t[0].astype("<i4").tobytes() + t[1].astype("<i2").tobytes() for t in self.tables(fmt))
+
+    def _chroma_rows(self, fmt, y0, y1):
+        return y0 >> fmt.sub_y, (((y1 - 1) >> fmt.sub_y) + 1 if y1 > y0 else y0 >> fmt.sub_y)
+
+    def planes(self, fmt, planes, y0=0, y1=None):
+        """The whole stored planes of a picture of `fmt` (stored words, in_height rows) -> the planes of the packed band of output rows
+        [y0, y1): luma rows y0..y1 and chroma rows y0 >> sub_y .. ((y1 - 1) >> sub_y) + 1, by the integers of vse_yuv_vscale in numpy."""
+        y1 = self.out_height if y1 is None else y1
+        shift, maxv = (16 - fmt.depth if fmt.msb else 0), (1 << fmt.depth) - 1
+        luma, chroma = self.tables(fmt)
+        c0, c1 = self._chroma_rows(fmt, y0, y1)
+        return tuple(vscale_rows(p, *(chroma if k else luma), *((c0, c1) if k else (y0, y1)), shift=shift, maxv=maxv) for k, p in enumerate(planes))
+
+    def source_rows(self, fmt, y0, y1):
+        """-> (s0, s1): the smallest band of stored luma rows whose luma rows and chroma rows (s0 >> sub_y .. ((s1 - 1) >> sub_y) + 1) hold
+        every row that output rows [y0, y1) read with a coefficient other than zero, in every plane."""
+        if not 0 <= y0 < y1 <= self.out_height:
+            return 0, 0
+        luma, chroma = self.tables(fmt)
+        spans = []
+        for tab, ph, (a, b) in ((luma, self.in_height, (y0, y1)),
+                                (chroma, fmt.chroma_size(self.in_height, 1)[0] if fmt.chroma else 0, self._chroma_rows(fmt, y0, y1))):
+            if tab is None:
+                spans.append(None)
+                continue
+            lo, hi = table_support(tab[0][a:b], tab[1][a:b], ph)
+            spans.append((int(lo.min()), int(hi.max())))
+        return band_for_support(spans, fmt.sub_y, self.in_height)
+
+
+def _check_vscale(vscale, height):
+    if vscale is not None:
+        if not (hasattr(vscale, "tables") and hasattr(vscale, "packed") and hasattr(vscale, "out_height") and hasattr(vscale, "source_rows")):
+            raise ValueError(f"vscale must be None or a VScale, not {vscale!r}")
+        if vscale.in_height != height:
+            raise ValueError(f"the vscale is for {vscale.in_height} stored rows, the picture has {height}")
+    return vscale
+
+
 def _check_resample(resample, width):
     if resample is not None:
         if not (hasattr(resample, "tables") and hasattr(resample, "packed") and hasattr(resample, "out_width")):
@@ -767,32 +874,44 @@ def parse_y4m_aspect(line):
     return None
 
 
-def _check_sar(name, square_pixels, sar, resample_filter):
-    """The sources' three options, checked -> whether the option is on."""
+def _check_sar(name, square_pixels, sar, resample_filter, scale=None):
+    """The sources' options that resample, checked -> whether square_pixels / sar is on."""
     if resample_filter not in RESAMPLE_FILTERS:
         raise ValueError(f"{name}: resample_filter must be one of {RESAMPLE_FILTERS}, not {resample_filter!r}")
     if sar is not None:
         if (not isinstance(sar, (tuple, list)) or len(sar) != 2
                 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1 for v in sar)):
             raise ValueError(f"{name}: sar must be None or (num, den) of positive integers, not {sar!r}")
-    if not (square_pixels or sar is not None) and resample_filter != "bicubic":
-        raise ValueError(f"{name}: resample_filter belongs to square_pixels=True or sar=(num, den)")
+    if scale is not None:
+        sizes = scale if isinstance(scale, (tuple, list)) else (scale,)
+        if not 1 <= len(sizes) <= 2 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1 for v in sizes):
+            raise ValueError(f"{name}: scale must be None, a height or (width, height) of positive integers, not {scale!r}")
+    if not (square_pixels or sar is not None or scale is not None) and resample_filter != "bicubic":
+        raise ValueError(f"{name}: resample_filter belongs to square_pixels=True, sar=(num, den) or scale=")
     return bool(square_pixels) or sar is not None
 
 
-def _y4m_width(line):
-    """The W token of a YUV4MPEG2 stream header as an integer; None where the header has none (its parser then says so)."""
+def _y4m_size_token(line, letter):
+    """The W or H token of a YUV4MPEG2 stream header as an integer; None where the header has none (its parser then says so)."""
     for tok in (line or b"")[10:].decode("ascii", "replace").split():
-        if tok[0] == "W" and tok[1:].isdigit():
+        if tok[0] == letter and tok[1:].isdigit():
             return int(tok[1:])
     return None
 
 
-def _source_resample(name, width, header, square_pixels, sar, resample_filter):
+def _y4m_width(line):
+    return _y4m_size_token(line, "W")
+
+
+def _y4m_height(line):
+    return _y4m_size_token(line, "H")
+
+
+def _source_resample(name, width, header, square_pixels, sar, resample_filter, scale=None):
     """The one decision of a source's three options: the Resample its frames carry, from sar, else with square_pixels from the header's
     ratio; None with the option off, and None with exactly one log line where it is on and there is nothing to do: no ratio, 1:1, or a
     ratio that shows the stored width.  width None (a header without one): None, the header's parser refuses it."""
-    if not _check_sar(name, square_pixels, sar, resample_filter) or not width:
+    if not _check_sar(name, square_pixels, sar, resample_filter, scale) or not width:
         return None
     ratio = tuple(int(v) for v in sar) if sar is not None else header
     if ratio is None or ratio[0] == ratio[1]:
@@ -805,6 +924,32 @@ def _source_resample(name, width, header, square_pixels, sar, resample_filter):
     return r
 
 
+def _source_scale(name, width, height, header, square_pixels, sar, resample_filter, scale, deinterlace=None):
+    """The one decision of a source's scale= beside its square_pixels / sar -> (the VScale, the Resample) its frames carry.  scale None:
+    (None, _source_resample's).  scale=H keeps the display aspect: the width is the nearest even number to display width * H / height,
+    the display width being the stored one or the one square_pixels / sar gives; scale=(W, H) says both.  One horizontal table goes from
+    the stored width straight to W.  A scale that asks for the size the picture already has attaches nothing and logs exactly one line.
+    width or height None (a header without one): nothing, the header's parser refuses it."""
+    square = _source_resample(name, width, header, square_pixels, sar, resample_filter, scale)
+    if scale is None:
+        return None, square
+    if deinterlace is not None:
+        raise ValueError(f"{name}: scale does not go with deinterlace={deinterlace!r}: interlaced pictures are not scaled vertically")
+    if not width or not height:
+        return None, None
+    shown = width if square is None else square.out_width
+    if isinstance(scale, (tuple, list)) and len(scale) == 2:
+        out_w, out_h = int(scale[0]), int(scale[1])
+    else:
+        out_h = int(scale[0] if isinstance(scale, (tuple, list)) else scale)
+        out_w = max(2, 2 * ((shown * out_h + height) // (2 * height)))
+    vscale = VScale(height, out_h, resample_filter) if out_h != height else None
+    resample = Resample(width, out_w, resample_filter) if out_w != width else None
+    if vscale is None and resample is None:
+        _log.info("%s: scale to %d x %d is the stored size: the frames are left as stored", name, out_w, out_h)
+    return vscale, resample
+
+
 class YuvFrame:
     """Yuv420Frame for any YuvFormat `fmt`: rows [y0, y1) of one picture that has not been converted.  planes are views of samples (uint8,
     or little-endian uint16 above 8 bits) of fmt.plane_shapes(height, width).  shape == (y1 - y0, width, 3), frame[a:b] narrows the row
@@ -812,18 +957,24 @@ class YuvFrame:
     tone: a ToneMap; to_bgr() and the device then convert by the integers of vse_yuv_to_bgr_tonemap; it travels with the slices.
     resample: a Resample whose in_width is `width` (anamorphic video): every plane's rows are resampled to resample.out_width columns by
     the integers of vse_yuv_resample before the conversion, on the host in to_bgr() and on the device in staging.Uploader; shape then
-    reports the output width, while width, the planes and the packing stay the stored ones."""
+    reports the output width, while width, the planes and the packing stay the stored ones.
+    vscale: a VScale whose in_height is `height` (UHD and other oversized video): every plane is scaled down its columns by the integers of
+    vse_yuv_vscale first (vertical, then horizontal, then the conversion).  shape, y0, y1 and frame[a:b] then count OUTPUT rows; height,
+    width, the planes and the packing stay the stored ones: band() is the stored rows that output rows [y0, y1) need, and packed_bytes,
+    pack_into() and row_parity describe that band.  f[a:b].to_bgr() == f.to_bgr()[a:b] for every slice."""
 
-    def __init__(self, planes, height, width, fmt, y0=0, y1=None, tone=None, resample=None):
+    def __init__(self, planes, height, width, fmt, y0=0, y1=None, tone=None, resample=None, vscale=None):
         if not isinstance(fmt, YuvFormat):
             raise ValueError(f"fmt must be a YuvFormat, not {fmt!r}")
         self.tone = _check_tone(tone)
         self.resample = _check_resample(resample, int(width))
+        self.vscale = _check_vscale(vscale, int(height))
         self.planes, self.height, self.width, self.fmt = tuple(planes), int(height), int(width), fmt
-        self.y0, self.y1 = int(y0), int(self.height if y1 is None else y1)
+        rows = self.height if vscale is None else int(vscale.out_height)           # y0, y1 count output rows
+        self.y0, self.y1 = int(y0), int(rows if y1 is None else y1)
         want = fmt.plane_shapes(self.height, self.width)
         if ([tuple(p.shape) for p in self.planes] != want or any(p.dtype.itemsize != fmt.sample_bytes or p.dtype.kind != "u" for p in self.planes)
-                or not 0 <= self.y0 <= self.y1 <= self.height):
+                or not 0 <= self.y0 <= self.y1 <= rows):
             raise ValueError(f"the planes of a {self.height} x {self.width} picture of {fmt} are {want} of {fmt.sample_dtype}, rows "
                              f"{self.y0}:{self.y1} asked of {[(tuple(p.shape), str(p.dtype)) for p in self.planes]}")
 
@@ -841,28 +992,37 @@ class YuvFrame:
         a, b, step = idx.indices(self.y1 - self.y0)
         if step != 1:
             raise TypeError(f"a YuvFrame takes a row slice of step 1, not {idx!r}")
-        return YuvFrame(self.planes, self.height, self.width, self.fmt, self.y0 + a, self.y0 + max(a, b), self.tone, self.resample)
+        return YuvFrame(self.planes, self.height, self.width, self.fmt, self.y0 + a, self.y0 + max(a, b), self.tone, self.resample, self.vscale)
+
+    def _stored_rows(self):          # (InterlacedYuvFrame has a band() of its own; this is what the packing of THIS class goes by)
+        return (self.y0, self.y1) if self.vscale is None else self.vscale.source_rows(self.fmt, self.y0, self.y1)
+
+    def band(self):
+        """(a, b): the stored luma rows packed for the device: [y0, y1) itself, or with a vscale the smallest band that holds what output
+        rows [y0, y1) read in every plane (VScale.source_rows)."""
+        return self._stored_rows()
 
     @property
     def row_parity(self):
-        return self.y0 & self.fmt.sub_y
+        return self._stored_rows()[0] & self.fmt.sub_y
 
     def _chroma_rows(self):
-        c0 = self.y0 >> self.fmt.sub_y
-        return c0, (((self.y1 - 1) >> self.fmt.sub_y) + 1 if self.y1 > self.y0 else c0)
+        a, b = self._stored_rows()
+        c0 = a >> self.fmt.sub_y
+        return c0, (((b - 1) >> self.fmt.sub_y) + 1 if b > a else c0)
 
     @property
     def packed_bytes(self):
-        c0, c1 = self._chroma_rows()
-        return self.fmt.sample_bytes * ((self.y1 - self.y0) * self.width + sum((c1 - c0) * p.shape[1] for p in self.planes[1:]))
+        (a, b), (c0, c1) = self._stored_rows(), self._chroma_rows()
+        return self.fmt.sample_bytes * ((b - a) * self.width + sum((c1 - c0) * p.shape[1] for p in self.planes[1:]))
 
     def pack_into(self, dst_u8):
         """The packed sub-frame (luma rows y0..y1, then chroma rows y0 >> sub_y .. ((y1 - 1) >> sub_y) + 1 of each plane; row parity
-        y0 & sub_y) into the first packed_bytes bytes of the 1-D uint8 array dst_u8: one contiguous copy per plane, the samples as they
-        are (2 bytes each above 8 bits)."""
+        y0 & sub_y; with a vscale the same of band() in y0, y1's place) into the first packed_bytes bytes of the 1-D uint8 array dst_u8:
+        one contiguous copy per plane, the samples as they are (2 bytes each above 8 bits)."""
         c0, c1 = self._chroma_rows()
         pos = 0
-        for plane, (a, b) in zip(self.planes, [(self.y0, self.y1)] + [(c0, c1)] * (len(self.planes) - 1)):
+        for plane, (a, b) in zip(self.planes, [self._stored_rows()] + [(c0, c1)] * (len(self.planes) - 1)):
             part = plane[a:b]
             nbytes = part.size * part.dtype.itemsize
             np.copyto(dst_u8[pos:pos + nbytes].view(part.dtype).reshape(part.shape), part)
@@ -871,7 +1031,14 @@ class YuvFrame:
 
     def to_bgr(self):
         """uint8 BGR [y1 - y0, W, 3]: nearest chroma, the integers of vse_yuv_to_bgr_format (include/vse_hip.h) in int32, or with a
-        tone those of vse_yuv_to_bgr_tonemap; with a resample the rows of every plane go through the integers of vse_yuv_resample first."""
+        tone those of vse_yuv_to_bgr_tonemap; with a resample the rows of every plane go through the integers of vse_yuv_resample first,
+        and with a vscale the columns go through those of vse_yuv_vscale before that: vertical, then horizontal, then the conversion."""
+        if self.vscale is not None:
+            rows, width = self.vscale.planes(self.fmt, self.planes, self.y0, self.y1), self.width
+            if self.resample is not None:
+                rows, width = self.resample.planes(self.fmt, rows), self.resample.out_width
+            return _rows_to_bgr(self.fmt, rows[0], rows[1:], (np.arange(self.y0, self.y1) >> self.fmt.sub_y) - (self.y0 >> self.fmt.sub_y), width,
+                                self.tone)
         if self.resample is not None:
             c0, c1 = self._chroma_rows()
             rows = self.resample.planes(self.fmt, (self.planes[0][self.y0:self.y1],) + tuple(p[c0:c1] for p in self.planes[1:]))
@@ -1013,7 +1180,9 @@ class InterlacedYuvFrame(YuvFrame):
     choice (always in a static band, where the candidates are equal)."""
 
     def __init__(self, planes, height, width, fmt, prev=None, field_order="tff", mode="adaptive", thresh=10, y0=0, y1=None, tone=None,
-                 comb_thresh=10, comb_limit=20, resample=None):
+                 comb_thresh=10, comb_limit=20, resample=None, vscale=None):
+        if vscale is not None:
+            raise ValueError("an InterlacedYuvFrame takes no vscale: interlaced pictures are not scaled vertically")
         super().__init__(planes, height, width, fmt, y0, y1, tone, resample)
         self.thresh = _check_deinterlace(mode, field_order, thresh, FIELD_ORDERS)
         self.comb_thresh, self.comb_limit = _check_match(comb_thresh, comb_limit)
@@ -1202,6 +1371,7 @@ class _Yuv420FileSource:
     comb_thresh, comb_limit = 10, 20      # deinterlace "match"'s (InterlacedYuvFrame)
     tone = None                   # a ToneMap (transfer="pq" | "hlg" on the readers of YuvFrames): the frames carry it
     resample = None               # a Resample (square_pixels=True | sar=(num, den) on the readers of YuvFrames): the frames carry it
+    vscale = None                 # a VScale (scale=H | (W, H) on the same readers): the frames carry it
     _last = None                  # (frame number, planes) of the last read_raw: the next frame's prev is then the same views
 
     def _planes(self, frame_no):
@@ -1235,7 +1405,7 @@ class _Yuv420FileSource:
             return InterlacedYuvFrame(self._planes(frame_no), h, w, self.fmt, prev, self.field_order, self.deinterlace, self.deinterlace_thresh,
                                       tone=self.tone, comb_thresh=self.comb_thresh, comb_limit=self.comb_limit, resample=self.resample)
         if self.fmt is not None:
-            return YuvFrame(_planes_at(self._buf, off, h, w, self.fmt), h, w, self.fmt, tone=self.tone, resample=self.resample)
+            return YuvFrame(_planes_at(self._buf, off, h, w, self.fmt), h, w, self.fmt, tone=self.tone, resample=self.resample, vscale=self.vscale)
         luma = self._buf[off:off + h * w].reshape(h, w)
         off += h * w
         if self.layout == "i420":
@@ -1371,15 +1541,20 @@ class Y4mSource(_Yuv420FileSource):
     ToneMap to the frames: HDR material comes out as SDR.  square_pixels=True (the header's A token), sar=(num, den) (in its place) and
     resample_filter attach a Resample from the stored width to display_width() of it: the frames are then YuvFrames whatever `wide` says,
     their shape is the display size and to_bgr() / the Uploader resample every plane along its rows before the conversion; a ratio of
-    1:1, no ratio, or one that shows the stored width changes nothing (one line is logged)."""
+    1:1, no ratio, or one that shows the stored width changes nothing (one line is logged).  scale=H | (W, H) (UHD and other oversized
+    video; not with deinterlace) attaches a VScale from the stored height to H and one Resample from the stored width straight to W; H
+    alone keeps the display aspect: W is the nearest even number to display width * H / height.  The frames' shape is then (H, W, 3),
+    to_bgr() / the Uploader scale vertically, then horizontally, then convert; the size the picture already has changes nothing (one
+    line is logged).  The source's width and height stay the stored ones; vscale and resample say what the frames carry."""
 
     layout = "i420"
 
     def __init__(self, path, fps=None, matrix="bt601", wide=False, range="auto", deinterlace=None, field_order="auto", deinterlace_thresh=10,
-                 transfer=None, tone_params=None, comb_thresh=10, comb_limit=20, square_pixels=False, sar=None, resample_filter="bicubic"):
+                 transfer=None, tone_params=None, comb_thresh=10, comb_limit=20, square_pixels=False, sar=None, resample_filter="bicubic",
+                 scale=None):
         self.deinterlace_thresh = _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
         self.comb_thresh, self.comb_limit = _check_match(comb_thresh, comb_limit)
-        _check_sar(path, square_pixels, sar, resample_filter)
+        _check_sar(path, square_pixels, sar, resample_filter, scale)
         if deinterlace is not None and not wide:
             raise ValueError(f"{path}: deinterlace={deinterlace!r} needs wide=True (the frames are YuvFrames)")
         self.deinterlace = deinterlace
@@ -1394,8 +1569,9 @@ class Y4mSource(_Yuv420FileSource):
         end = mm.find(b"\n", 0, 4096) if size else -1
         line = mm[:end] if end >= 0 else None
         # decided before the parser is chosen: where nothing is attached the header goes to today's parser, with today's refusals
-        self.resample = _source_resample(path, _y4m_width(line), parse_y4m_aspect(line), square_pixels, sar, resample_filter)
-        if wide or self.resample is not None:       # resampled frames are YuvFrames whatever `wide` says
+        self.vscale, self.resample = _source_scale(path, _y4m_width(line), _y4m_height(line), parse_y4m_aspect(line), square_pixels, sar,
+                                                   resample_filter, scale, deinterlace)
+        if wide or self.resample is not None or self.vscale is not None:       # resampled frames are YuvFrames whatever `wide` says
             self.width, self.height, self.fps, self.fmt, self.field_order = parse_y4m_header_fields(
                 line, path, fps, "file", matrix, range, None if deinterlace is None else field_order)
         else:
@@ -1438,13 +1614,14 @@ class Y4mStream:
     tone = None                       # as Y4mSource's (transfer, tone_params)
 
     resample = None                   # as Y4mSource's (square_pixels, sar, resample_filter)
+    vscale = None                     # as Y4mSource's (scale)
 
     def __init__(self, fileobj, fps=None, matrix="bt601", name="<stream>", wide=False, range="auto", deinterlace=None, field_order="auto",
                  deinterlace_thresh=10, transfer=None, tone_params=None, comb_thresh=10, comb_limit=20, square_pixels=False, sar=None,
-                 resample_filter="bicubic"):
+                 resample_filter="bicubic", scale=None):
         self.deinterlace_thresh = _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
         self.comb_thresh, self.comb_limit = _check_match(comb_thresh, comb_limit)
-        _check_sar(name, square_pixels, sar, resample_filter)
+        _check_sar(name, square_pixels, sar, resample_filter, scale)
         if deinterlace is not None and not wide:
             raise ValueError(f"{name}: deinterlace={deinterlace!r} needs wide=True (the frames are YuvFrames)")
         self.deinterlace = deinterlace
@@ -1458,8 +1635,9 @@ class Y4mStream:
         self._pos = 0                 # bytes of the stream consumed
         self._started = False
         line = self._line(4096)
-        self.resample = _source_resample(name, _y4m_width(line), parse_y4m_aspect(line), square_pixels, sar, resample_filter)
-        if wide or self.resample is not None:
+        self.vscale, self.resample = _source_scale(name, _y4m_width(line), _y4m_height(line), parse_y4m_aspect(line), square_pixels, sar,
+                                                   resample_filter, scale, deinterlace)
+        if wide or self.resample is not None or self.vscale is not None:
             self.width, self.height, self.fps, self.fmt, self.field_order = parse_y4m_header_fields(
                 line, name, fps, "stream", matrix, range, None if deinterlace is None else field_order)
         else:
@@ -1523,7 +1701,7 @@ class Y4mStream:
                 last = planes
                 continue
             if self.fmt is not None:
-                yield YuvFrame(_planes_at(buf, 0, h, w, self.fmt), h, w, self.fmt, tone=self.tone, resample=self.resample)
+                yield YuvFrame(_planes_at(buf, 0, h, w, self.fmt), h, w, self.fmt, tone=self.tone, resample=self.resample, vscale=self.vscale)
                 continue
             planes = (buf[:h * w].reshape(h, w), buf[h * w:h * w + ch * cw].reshape(ch, cw), buf[h * w + ch * cw:].reshape(ch, cw))
             yield Yuv420Frame(planes, h, w, "i420", matrix=self.matrix)
@@ -1565,10 +1743,10 @@ class YuvSource(_Yuv420FileSource):
     Y4mSource's; a headerless file carries no ratio, so square_pixels=True alone changes nothing."""
 
     def __init__(self, path, width, height, fps, fmt, deinterlace=None, field_order="auto", deinterlace_thresh=10, transfer=None, tone_params=None,
-                 comb_thresh=10, comb_limit=20, square_pixels=False, sar=None, resample_filter="bicubic"):
+                 comb_thresh=10, comb_limit=20, square_pixels=False, sar=None, resample_filter="bicubic", scale=None):
         if not isinstance(fmt, YuvFormat):
             raise ValueError(f"fmt must be a YuvFormat, not {fmt!r}")
-        _check_sar(path, square_pixels, sar, resample_filter)
+        _check_sar(path, square_pixels, sar, resample_filter, scale)
         self.tone = _source_tone(path, transfer, tone_params, fmt.matrix, True)
         self.deinterlace_thresh = _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
         self.comb_thresh, self.comb_limit = _check_match(comb_thresh, comb_limit)
@@ -1580,7 +1758,8 @@ class YuvSource(_Yuv420FileSource):
         self.width, self.height, self.fps = int(width), int(height), float(fps)
         if self.width < 1 or self.height < 1:
             raise ValueError(f"{path}: frame size {width} x {height}")
-        self.resample = _source_resample(path, self.width, None, square_pixels, sar, resample_filter)      # (no header: sar says the ratio)
+        self.vscale, self.resample = _source_scale(path, self.width, self.height, None, square_pixels, sar, resample_filter, scale,
+                                                   deinterlace)      # (no header: sar says the ratio)
         size = self._map(path)
         nbytes = self._frame_bytes()
         self.frame_count = size // nbytes
@@ -1593,7 +1772,7 @@ _RAW_PIX_FMT_EXT = {".p010": "p010le"}
 
 def open_source(path, fps=None, size=None, layout=None, matrix="bt601", wide=False, range="auto", pix_fmt=None, deinterlace=None,
                 field_order="auto", deinterlace_thresh=10, transfer=None, tone_params=None, comb_thresh=10, comb_limit=20, square_pixels=False,
-                sar=None, resample_filter="bicubic"):
+                sar=None, resample_filter="bicubic", scale=None):
     """The source of a file by its extension: .npy (needs fps), .y4m, .yuv / .i420 / .nv12 (headerless: need size=(width, height) and
     fps; `layout` overrides the extension's), anything else an AVI; "-" is a Y4mStream over standard input.  `matrix` goes to the
     YUV sources.  wide=True lets the Y4M readers accept what parse_y4m_header_wide does, with `range` ("auto": the header's).  pix_fmt
@@ -1605,7 +1784,9 @@ def open_source(path, fps=None, size=None, layout=None, matrix="bt601", wide=Fal
     ratio), sar=(num, den) (say it in its place; the only way for a headerless file) and resample_filter ("bicubic" | "bilinear" |
     "lanczos") go to the Y4M readers and to the headerless YUV files: anamorphic video is resampled to square pixels, the frames are
     YuvFrames whatever `wide` says (a headerless 8-bit 4:2:0 file is then read through YuvSource), and a ratio of 1:1 or none changes
-    nothing; the other sources refuse them."""
+    nothing; the other sources refuse them.  scale=H | (W, H) goes to the same readers, shares resample_filter and does not go with
+    deinterlace: every frame is scaled to H rows on the device before anything else sees it (UHD to 1080 rows, say), H alone keeping the
+    display aspect; the size the picture already has changes nothing."""
     if range not in YUV_RANGES:
         raise ValueError(f"range must be one of {YUV_RANGES}, not {range!r}")
     _check_deinterlace(deinterlace, field_order, deinterlace_thresh)
@@ -1618,13 +1799,19 @@ def open_source(path, fps=None, size=None, layout=None, matrix="bt601", wide=Fal
     if transfer is not None or tone_params:
         fields.update(transfer=transfer, tone_params=tone_params)
     square = {}
-    if _check_sar(path, square_pixels, sar, resample_filter):
+    if _check_sar(path, square_pixels, sar, resample_filter, scale) or scale is not None:
         square = dict(square_pixels=square_pixels, sar=sar, resample_filter=resample_filter)
+        if scale is not None:
+            square["scale"] = scale
+            if deinterlace is not None:
+                raise ValueError(f"{path}: scale does not go with deinterlace={deinterlace!r}: interlaced pictures are not scaled vertically")
     if str(path) == "-":
         import sys
         return Y4mStream(sys.stdin.buffer, fps, matrix, name="<stdin>", wide=wide, range=range, **fields, **square)
     ext = os.path.splitext(str(path))[1].lower()
     if square and ext != ".y4m" and pix_fmt is None and ext not in _RAW_PIX_FMT_EXT and ext not in _RAW_YUV_EXT:
+        if scale is not None:
+            raise ValueError(f"{path}: scale takes YUV4MPEG2 and headerless YUV files; BGR sources are not scaled")
         raise ValueError(f"{path}: square_pixels / sar resample YUV4MPEG2 and headerless YUV files; BGR sources have square pixels")
     if fields and ext != ".y4m" and pix_fmt is None and (layout is not None or ext not in _RAW_PIX_FMT_EXT):
         if deinterlace is None:
@@ -1647,13 +1834,13 @@ def open_source(path, fps=None, size=None, layout=None, matrix="bt601", wide=Fal
             if layout is not None:
                 raise ValueError(f"{path}: pix_fmt {pix_fmt!r} names the plane layout; layout {layout!r} was given as well")
             return YuvSource(path, size[0], size[1], fps, YuvFormat.from_pix_fmt(pix_fmt, matrix, range), **fields, **square)
-        resample = _source_resample(path, int(size[0]), None, square_pixels, sar, resample_filter)          # decided, and logged, here
-        if resample is not None:
+        vscale, resample = _source_scale(path, int(size[0]), int(size[1]), None, square_pixels, sar, resample_filter, scale)  # decided, and logged, here
+        if resample is not None or vscale is not None:
             name = {"i420": "yuv420p", "nv12": "nv12"}.get(layout or _RAW_YUV_EXT[ext])
             if name is None:
                 raise ValueError(f"layout must be one of {YUV_LAYOUTS}, not {layout!r}")
             src = YuvSource(path, size[0], size[1], fps, YuvFormat.from_pix_fmt(name, _check_matrix(matrix)))
-            src.resample = resample
+            src.vscale, src.resample = vscale, resample
             return src
         return Yuv420Source(path, size[0], size[1], fps, layout or _RAW_YUV_EXT[ext], matrix)
     return AviBgr24Source(path)

@@ -23,6 +23,9 @@ each beside its previous picture unless that is the frame before it in the batch
 vse_yuv_field_match for frames of mode "match") and
 converted by the same call as the others.  Frames that carry an ingest.Resample (anamorphic video) are uploaded with their stored
 columns and resampled to square pixels on the device (vse_yuv_resample) between those two steps; the batch key gains the resample.
+Frames that carry an ingest.VScale (UHD and other oversized video) are uploaded as the band of stored rows that their output rows need
+(YuvFrame.band()) and scaled down on the device first (vse_yuv_vscale): vertical, then horizontal, then the conversion, all on the copy
+stream; the batch key gains the vscale and the first output row.
 """
 import queue
 import threading
@@ -131,20 +134,26 @@ class Uploader:
     def _stage_yuv(self, frames):
         """ingest.YuvFrames of one shape, format, row parity, tone map and resample -> StagedBatch of their BGR conversion: packed into the
         slab as they are (3 bytes per pixel for 10-bit 4:2:0; frame stride rounded up to 16 bytes), one copy, with a resample one
-        vse_yuv_resample, one vse_yuv_to_bgr_format (with a tone map: vse_yuv_to_bgr_tonemap) on the copy stream."""
+        vse_yuv_resample, one vse_yuv_to_bgr_format (with a tone map: vse_yuv_to_bgr_tonemap) on the copy stream.  Frames with a vscale
+        (shared too, as is their first output row) pack band(), and one vse_yuv_vscale runs in front of the others."""
         import torch
         first = frames[0]
 
         def key_of(f):
-            return (tuple(f.shape), getattr(f, "fmt", None), getattr(f, "row_parity", None), getattr(f, "tone", None), getattr(f, "resample", None))
+            key = (tuple(f.shape), getattr(f, "fmt", None), getattr(f, "row_parity", None), getattr(f, "tone", None), getattr(f, "resample", None))
+            scale = getattr(f, "vscale", None)
+            return key if scale is None else key + (scale, getattr(f, "y0", None))
         key = key_of(first)
+        vscale = getattr(first, "vscale", None)
         for f in frames:
             if key_of(f) != key:
                 raise ValueError("Uploader.stage: the YUV frames of a batch must share shape, format, row parity (y0 & sub_y), tone map and "
-                                 f"resample: {key} and {key_of(f)}")
+                                 f"resample{'' if vscale is None and getattr(f, 'vscale', None) is None else ', vscale and first row (y0)'}: "
+                                 f"{key} and {key_of(f)}")
         ctx = self._context()
         n, (h, w, _) = len(frames), first.shape
         resample = getattr(first, "resample", None)
+        parity = first.row_parity
         per = (first.packed_bytes + 15) & ~15
         k, slab = self._slab(per * n)
         host = slab[:per * n].view(n, per)
@@ -153,9 +162,12 @@ class Uploader:
         with torch.cuda.stream(self._stream):
             packed = torch.empty((n, per), dtype=torch.uint8, device=self.device)          # (dropped here: see _stage_yuv420)
             packed.copy_(host, non_blocking=True)
+            if vscale is not None:                     # vertical, then horizontal, then convert; the band becomes output rows y0:y1
+                packed = ctx.yuv_vscale(packed, n, first.height, first.width, first.fmt, vscale, *first.band(), first.y0, first.y1)
+                parity = first.y0 & first.fmt.sub_y
             if resample is not None:                   # (the resampled pictures are dropped here too)
-                packed = ctx.yuv_resample(packed, n, h, first.width, first.fmt, resample, first.row_parity)
-            dev = ctx.yuv_to_bgr(packed, n, h, w, first.fmt, first.row_parity, tone=first.tone)
+                packed = ctx.yuv_resample(packed, n, h, first.width, first.fmt, resample, parity)
+            dev = ctx.yuv_to_bgr(packed, n, h, w, first.fmt, parity, tone=first.tone)
             ev = torch.cuda.Event()
             ev.record(self._stream)
         self._busy[k] = ev
