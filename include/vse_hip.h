@@ -551,6 +551,32 @@ int vse_interval_stream(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int s
                         int y0, int y1, int x0, int x1, void* d_state, int cap, int64_t fed,
                         const vse_interval_seg* segs /* host, [nseg] */, int nseg, int64_t store_from, int mode /* 0 min, 1 max, 2 mean */,
                         void* d_out, int64_t out_pitch, int64_t out_stride, void* stream);
+/* vse_interval_rank on frames that wait in the ring of a vse_interval_stream state, so a subtitle's quantile picture
+ * (vse_amd.frame_select.StreamingQuantile) is made in the selector's own pass, without a second look at frames already gone: a call
+ * of vse_interval_stream with nseg = 0 and store_from = fed + 1 parks a whole batch, and once a subtitle's end is known its samples
+ * are ranked where they lie.  d_state: a state of vse_interval_stream_state_bytes(area_h, area_w, cap); only its ring is read, and
+ * neither the accumulators nor the ring are written.  `fed`: the frames of the clip stored so far, as the next vse_interval_stream
+ * call would be told.  For each of the 0 <= ngroups <= VSE_INTERVAL_RING_MAX_GROUPS groups and every byte b of the area: the n
+ * values ring[frames[k] % cap][b] sorted ascending, element `rank` -> patch `out`: d_out + out * out_stride, rows `out_pitch` bytes
+ * apart, exactly the 3 area_w bytes of each row: the bytes vse_interval_rank gives for the same frames laid out contiguously.
+ * Every named frame must lie in (fed - cap, fed] and be one that an earlier call stored and no later store has replaced: the caller
+ * keeps that book, the library checks only the numbers.  Patches of one call must not overlap.
+ * Slot rows are 16-byte aligned, so every load is one aligned dword.  One launch on `stream` for all groups (none for ngroups = 0,
+ * which returns VSE_OK), no allocation, no device sync, no atomics; the groups travel as kernel arguments.
+ * Returns VSE_E_INVAL, without touching the device, for a NULL context, state or d_out, a state that is not 16-byte aligned, an area
+ * that vse_interval_stream_state_bytes sizes as 0, cap < 1, fed negative or above 2^62, ngroups outside
+ * 0..VSE_INTERVAL_RING_MAX_GROUPS, n outside 1..VSE_INTERVAL_RANK_MAX, rank outside 0..n - 1, frames that do not ascend strictly or
+ * lie outside (fed - cap, fed] (or below 1), a negative `out`, or out_pitch < 3 area_w. */
+#define VSE_INTERVAL_RING_MAX_GROUPS 8
+typedef struct {
+    int32_t n;        /* 1..VSE_INTERVAL_RANK_MAX samples */
+    int32_t rank;     /* 0..n-1 */
+    int32_t out;      /* patch written: d_out + out * out_stride */
+    int64_t frames[VSE_INTERVAL_RANK_MAX];   /* absolute 1-based frame numbers, strictly ascending */
+} vse_interval_ring_group;
+int vse_interval_ring_rank(vse_ctx* ctx, const void* d_state, int area_h, int area_w, int cap, int64_t fed,
+                           const vse_interval_ring_group* groups /* host, [ngroups] */, int ngroups,
+                           void* d_out, int64_t out_pitch, int64_t out_stride, void* stream);
 
 /* ---- timeline sync: audio template search ----------------------------------------------------------------------------- */
 /* Replaces: Sushi's WavStream.find_substream (backend/sushi/wav.py:179-189), cv2.matchTemplate(TM_SQDIFF_NORMED) of one group's

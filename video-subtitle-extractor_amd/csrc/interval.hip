@@ -428,6 +428,84 @@ void launch_rank(bool wide, dim3 grid, hipStream_t st, const uint8_t* src, int n
                            out_pitch);
 }
 
+// ---- interval ring rank -------------------------------------------------------------------------------------------------------
+// vse_interval_ring_rank: the rank kernel above on samples that are not evenly strided: the frames a group names sit in the ring
+// of a vse_interval_stream state (frame f in slot f % cap), so consecutive samples are slots apart by whatever the sampling and the
+// wrap make of them.  The host turns frame numbers into slots; the table of all groups travels as a kernel argument (uniform, read
+// through scalar loads, as StreamSegs), indexed by blockIdx.y.  A lane owns one aligned dword of a slot row for all samples of its
+// group: slot rows are padded to 16 bytes, so there is the wide load only.  One launch serves groups of any n: the kernel is
+// instantiated for the bucket KB of the LARGEST n of the call and holds the bodies of the buckets up to it behind uniform branches, so
+// a group of 5 samples beside one of 63 does the compares of 8 slots, in the registers of 64.  Only the ring is read; nothing but the
+// patches is written.
+// Resource report (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage): interval_ring_rank_kernel<8> 19 VGPRs, <16> 29,
+// <32> 45, <64> 77; 0 bytes of scratch and of LDS each, no dynamic stack: the dynamic group index stays a scalar offset into
+// the kernel arguments.
+struct RingGroups {
+    int n[VSE_INTERVAL_RING_MAX_GROUPS], rank[VSE_INTERVAL_RING_MAX_GROUPS], out[VSE_INTERVAL_RING_MAX_GROUPS];
+    int slot[VSE_INTERVAL_RING_MAX_GROUPS][64];       // slot of sample k; from n on unused (63 samples at most: the last is never read)
+};
+
+// p = this lane's dword in slot 0, plane = bytes from one slot to the next.  The loads as load_samples<KB, true> issues them: n in a
+// vector register, so none beyond the n samples.
+template <int KB>
+__device__ __forceinline__ unsigned ring_rank_dword(const uint8_t* p, long plane, const int (&slot)[64], int n, unsigned rank) {
+    unsigned s[KB];
+    int nv = n;
+    asm volatile("" : "+v"(nv));
+    // 16 slots at a time are fetched into scalar registers before the first masked load that needs one: left inside the masked
+    // blocks, every scalar load was waited for on its own, sample after sample.
+    constexpr int CH = KB < 16 ? KB : 16;
+#pragma unroll
+    for (int c0 = 0; c0 < KB; c0 += CH) {
+        int sl[CH];
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            sl[u] = slot[c0 + u];
+            asm volatile("" : "+s"(sl[u]));
+        }
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            s[c0 + u] = 0xFFFFFFFFu;
+            if (c0 + u < nv) s[c0 + u] = *reinterpret_cast<const unsigned*>(p + (long)sl[u] * plane);
+        }
+    }
+    const unsigned b0 = select_byte<KB, 0>(s, rank), b1 = select_byte<KB, 8>(s, rank), b2 = select_byte<KB, 16>(s, rank),
+                   b3 = select_byte<KB, 24>(s, rank);
+    return b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+}
+
+// The smallest bucket of 8 .. KB that holds n (uniform branches).
+template <int KB>
+__device__ __forceinline__ unsigned ring_rank_bucket(const uint8_t* p, long plane, const int (&slot)[64], int n, unsigned rank) {
+    if constexpr (KB > 8) {
+        if (n <= KB / 2) return ring_rank_bucket<KB / 2>(p, plane, slot, n, rank);
+    }
+    return ring_rank_dword<KB>(p, plane, slot, n, rank);
+}
+
+// ring = slot 0 of the state's ring; rb = 3 area_w bytes per row of rb16 = 16 ceil(rb / 16) in the ring, in dpr = ceil(rb / 4) dwords;
+// items = area_h * dpr; plane = area_h * rb16.  grid.y = groups; every group's n <= KBMAX.
+template <int KBMAX>
+__global__ __launch_bounds__(IV_THREADS) void interval_ring_rank_kernel(const uint8_t* __restrict__ ring, long plane, int rb, unsigned rb16,
+                                                                        unsigned dpr, unsigned items, const RingGroups rg,
+                                                                        uint8_t* __restrict__ out, long out_pitch, long out_stride) {
+    const unsigned i = blockIdx.x * IV_THREADS + threadIdx.x;
+    if (i >= items) return;
+    const unsigned g = blockIdx.y;
+    const int n = rg.n[g];
+    const unsigned rank = (unsigned)rg.rank[g];
+    const unsigned r = i / dpr, c = i - r * dpr;
+    const int nb = min(4, rb - 4 * (int)c);
+    const uint8_t* p = ring + (long)r * rb16 + 4 * (long)c;
+    const unsigned w = ring_rank_bucket<KBMAX>(p, plane, rg.slot[g], n, rank);
+    uint8_t* o = out + (long)rg.out[g] * out_stride + (long)r * out_pitch + 4 * (long)c;
+    if (nb == 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
+        *reinterpret_cast<unsigned*>(o) = w;
+    } else {
+        for (int k = 0; k < nb; ++k) o[k] = (uint8_t)(w >> (8 * k));
+    }
+}
+
 // rows padded to whole runs; 0 where the area is empty or its runs do not fit the 32-bit work-item index
 size_t row_bytes16(int area_w) { return (((size_t)area_w * 3 + 15) / 16) * 16; }
 bool area_fits(int area_h, int area_w) {
@@ -627,6 +705,71 @@ int vse_interval_rank(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w
         launch_rank<64>(wide, grid, st, src, n, (long)pitch, (long)frame_stride, rb, dpr, items, (unsigned)rank, out, (long)out_pitch);
     if (hipGetLastError() != hipSuccess) {
         vse_set_error("vse_interval_rank: launch failed");
+        return VSE_E_HIP;
+    }
+    return VSE_OK;
+}
+
+int vse_interval_ring_rank(vse_ctx* c, const void* d_state, int area_h, int area_w, int cap, int64_t fed, const vse_interval_ring_group* groups,
+                           int ngroups, void* d_out, int64_t out_pitch, int64_t out_stride, void* stream) {
+    char msg[400];
+    if (!c || !d_state || (reinterpret_cast<uintptr_t>(d_state) & 15) || !d_out || !area_fits(area_h, area_w) ||
+        (size_t)area_h * (((size_t)area_w * 3 + 3) / 4) > 0x7fffffffu || cap < 1 || fed < 0 || fed > ((int64_t)1 << 62) || ngroups < 0 ||
+        ngroups > VSE_INTERVAL_RING_MAX_GROUPS || (ngroups > 0 && !groups) || out_pitch < (int64_t)area_w * 3) {
+        snprintf(msg, sizeof msg, "vse_interval_ring_rank: bad arguments (a state, 16-byte aligned, and an output; area %d x %d, cap %d of at "
+                 "least 1, fed %lld of 0..2^62, %d groups of 0..%d, output pitch %lld of at least 3 area_w)", area_h, area_w, cap,
+                 (long long)fed, ngroups, VSE_INTERVAL_RING_MAX_GROUPS, (long long)out_pitch);
+        vse_set_error(msg);
+        return VSE_E_INVAL;
+    }
+    RingGroups rg = {};
+    int nmax = 0;
+    for (int g = 0; g < ngroups; ++g) {
+        const vse_interval_ring_group& q = groups[g];
+        const char* bad = nullptr;
+        if (q.n < 1 || q.n > VSE_INTERVAL_RANK_MAX)
+            bad = "n must be 1..VSE_INTERVAL_RANK_MAX";
+        else if (q.rank < 0 || q.rank >= q.n)
+            bad = "rank must be 0..n - 1";
+        else if (q.out < 0)
+            bad = "out must not be negative";
+        int64_t prev = fed - cap > 0 ? fed - cap : 0;         // every frame named is behind this one (and 1-based)
+        for (int k = 0; !bad && k < q.n; ++k) {
+            if (q.frames[k] <= prev || q.frames[k] > fed) bad = "its frames (1-based) must ascend strictly inside (fed - cap, fed]";
+            prev = q.frames[k];
+        }
+        if (bad) {
+            snprintf(msg, sizeof msg, "vse_interval_ring_rank: group %d (n %d, rank %d, out %d; fed %lld, cap %d): %s", g, q.n, q.rank, q.out,
+                     (long long)fed, cap, bad);
+            vse_set_error(msg);
+            return VSE_E_INVAL;
+        }
+        rg.n[g] = q.n, rg.rank[g] = q.rank, rg.out[g] = q.out;
+        for (int k = 0; k < q.n; ++k) rg.slot[g][k] = (int)(q.frames[k] % cap);
+        nmax = q.n > nmax ? q.n : nmax;
+    }
+    if (ngroups == 0) return VSE_OK;
+    const int rb = area_w * 3;
+    const unsigned rb16 = (unsigned)row_bytes16(area_w), dpr = (unsigned)((rb + 3) / 4), items = (unsigned)area_h * dpr;
+    const long plane = (long)area_h * (long)rb16;
+    const uint8_t* ring = reinterpret_cast<const uint8_t*>(d_state) + 6 * plane;
+    uint8_t* out = reinterpret_cast<uint8_t*>(d_out);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((items + IV_THREADS - 1) / IV_THREADS, (unsigned)ngroups), block(IV_THREADS);
+    if (nmax <= 8)
+        hipLaunchKernelGGL(interval_ring_rank_kernel<8>, grid, block, 0, st, ring, plane, rb, rb16, dpr, items, rg, out, (long)out_pitch,
+                           (long)out_stride);
+    else if (nmax <= 16)
+        hipLaunchKernelGGL(interval_ring_rank_kernel<16>, grid, block, 0, st, ring, plane, rb, rb16, dpr, items, rg, out, (long)out_pitch,
+                           (long)out_stride);
+    else if (nmax <= 32)
+        hipLaunchKernelGGL(interval_ring_rank_kernel<32>, grid, block, 0, st, ring, plane, rb, rb16, dpr, items, rg, out, (long)out_pitch,
+                           (long)out_stride);
+    else
+        hipLaunchKernelGGL(interval_ring_rank_kernel<64>, grid, block, 0, st, ring, plane, rb, rb16, dpr, items, rg, out, (long)out_pitch,
+                           (long)out_stride);
+    if (hipGetLastError() != hipSuccess) {
+        vse_set_error("vse_interval_ring_rank: launch failed");
         return VSE_E_HIP;
     }
     return VSE_OK;

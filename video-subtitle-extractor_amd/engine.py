@@ -31,7 +31,7 @@ EXPORTS = [
     "vse_frame_cells_hold_state_bytes", "vse_frame_cells_hold", "vse_frame_focus",
     "vse_frame_hold_bounded_state_bytes", "vse_frame_hold_bounded",
     "vse_frame_cells_hold_bounded_state_bytes", "vse_frame_cells_hold_bounded",
-    "vse_interval_stream_state_bytes", "vse_interval_stream",
+    "vse_interval_stream_state_bytes", "vse_interval_stream", "vse_interval_ring_rank",
     "vse_yuv_frame_bytes", "vse_yuv_to_bgr_format", "vse_yuv_deinterlace", "vse_yuv_field_match",
     "vse_yuv_tonemap_table_bytes", "vse_yuv_to_bgr_tonemap", "vse_yuv_resample_table_bytes", "vse_yuv_resample",
     "vse_yuv_vscale",
@@ -82,6 +82,11 @@ class DeviceState:
 class IntervalSeg(C.Structure):
     """vse_interval_seg (include/vse_hip.h)."""
     _fields_ = [("first", C.c_int64), ("last", C.c_int64), ("flags", C.c_int32), ("frames", C.c_int32), ("out", C.c_int32)]
+
+
+class IntervalRingGroup(C.Structure):
+    """vse_interval_ring_group (include/vse_hip.h)."""
+    _fields_ = [("n", C.c_int32), ("rank", C.c_int32), ("out", C.c_int32), ("frames", C.c_int64 * 63)]
 
 
 class DbParams(C.Structure):
@@ -217,6 +222,8 @@ def load_library(path=None):
     lib.vse_interval_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
                                         C.c_int, C.c_void_p, C.c_int, C.c_int64, C.POINTER(IntervalSeg), C.c_int, C.c_int64, C.c_int,
                                         C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+    lib.vse_interval_ring_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_int64, C.c_int64, C.c_void_p]
     lib.vse_audio_match_workspace_bytes.restype = C.c_size_t
     lib.vse_audio_match_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
     lib.vse_audio_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
@@ -850,6 +857,38 @@ class Context:
                "vse_interval_stream")
         return out
 
+    def interval_ring_rank(self, state, area_h, area_w, cap, fed, groups, out=None):
+        """state: an interval_stream_state of area_h x area_w pixels and `cap`, into whose ring interval_stream has stored the frames
+        up to `fed`; groups: up to INTERVAL_RING_MAX_GROUPS of (frame numbers, rank[, out]): 1 .. INTERVAL_RANK_MAX absolute 1-based
+        frame numbers, strictly ascending, inside (fed - cap, fed], and 0 <= rank < their count (without `out`, group k writes patch
+        k) -> cuda uint8 [patches, area_h, area_w, 3]: per byte, element `rank` of the named frames' values sorted ascending
+        (include/vse_hip.h vse_interval_ring_rank).  The state is only read.  out: write into this tensor instead (it may be a
+        strided view with packed pixels; its row pitch and patch stride are taken from it)."""
+        t = self.torch
+        area_h, area_w = int(area_h), int(area_w)
+        assert state.dtype == t.uint8 and state.is_contiguous()
+        assert state.numel() >= max(self.lib.vse_interval_stream_state_bytes(area_h, area_w, int(cap)), 1)
+        if len(groups) > INTERVAL_RING_MAX_GROUPS:
+            raise VseError(f"interval_ring_rank: {len(groups)} groups, at most {INTERVAL_RING_MAX_GROUPS} go in one call")
+        recs, patches = (IntervalRingGroup * max(len(groups), 1))(), 0
+        for k, g in enumerate(groups):
+            nos = [int(v) for v in g[0]]
+            if len(nos) > INTERVAL_RANK_MAX:
+                raise VseError(f"interval_ring_rank: group {k} names {len(nos)} frames, at most {INTERVAL_RANK_MAX} are ranked")
+            recs[k].n, recs[k].rank, recs[k].out = len(nos), int(g[1]), int(g[2]) if len(g) > 2 else k
+            recs[k].frames[:len(nos)] = nos
+            patches = max(patches, recs[k].out + 1)
+        if out is None:
+            out = t.empty((patches, max(area_h, 0), max(area_w, 0), 3), dtype=t.uint8, device=self.tdev)
+            if not groups:
+                return out                                # (no patch, no memory to name as d_out: nothing to ask the library for)
+        assert out.dtype == t.uint8 and tuple(out.shape[1:]) == (area_h, area_w, 3) and out.shape[0] >= patches
+        assert out.stride(3) == 1 and out.stride(2) == 3
+        _check(self.lib.vse_interval_ring_rank(self.handle, C.c_void_p(state.data_ptr()), area_h, area_w, int(cap), int(fed), recs, len(groups),
+                                               C.c_void_p(out.data_ptr()), out.stride(1) if area_h > 1 else max(out.stride(1), 3 * area_w),
+                                               out.stride(0), self.stream()), "vse_interval_ring_rank")
+        return out
+
     # ---- timeline sync: audio template search ---------------------------------------------------------------------
     def audio_match_workspace_bytes(self, queries):
         """Workspace bytes of one audio_match call with these (src_off, m, dst_off, win_len) queries (0 if one is invalid)."""
@@ -1256,6 +1295,7 @@ INTERVAL_MODES = {"min": 0, "max": 1, "mean": 2}
 INTERVAL_SEG_CONTINUE, INTERVAL_SEG_EMIT = 1, 2          # vse_interval_seg.flags (include/vse_hip.h)
 INTERVAL_STREAM_MAX_SEGS = 32   # VSE_INTERVAL_STREAM_MAX_SEGS: the segments of one vse_interval_stream call
 INTERVAL_RANK_MAX = 63          # VSE_INTERVAL_RANK_MAX (include/vse_hip.h): the frames of one vse_interval_rank call
+INTERVAL_RING_MAX_GROUPS = 8    # VSE_INTERVAL_RING_MAX_GROUPS: the groups of one vse_interval_ring_rank call
 FRAME_HOLD_BOUNDED_MAX = 4000   # the largest max_hold of vse_frame_hold_bounded (include/vse_hip.h)
 
 

@@ -269,14 +269,24 @@ class SubtitleExtractor:
     keys it takes: `trim_seconds`, `stream_fn`, and `keep_patches` (one pass drops a picture once its frame is recognised, a film has
     thousands of about 1 MB each; True keeps them as `interval_patches`, as several passes always do).  `streaming` and `keep_patches`
     are this class's own and are taken out before the rest reaches a compositor; a falsy `streaming` is the run without the key.  Not with
-    interval_image="quantile" or "middle", interval_text="fused" or shard.
+    interval_image="middle", interval_text="fused", interval_frame="sharpest" or shard.
     interval_image="quantile" (change / hold selector): the picture is instead the per-pixel quantile over time (default 0.5, the median)
     of up to `samples` (default 15) evenly spaced frames of the interval (frame_select.IntervalQuantile, `composite_params` its keyword
     arguments: quantile, samples, trim_seconds, rank_fn).  The median needs no knowledge of the text's polarity, and a minority of
     outlier frames (a flash, a black frame, a cut found one frame late) cannot move it, where a single one ruins `min` / `max`; only
     the samples are uploaded.  Exact over the trimmed interval when it has at most `samples` frames, an estimate from `samples` frames
-    otherwise.  Not available with frame_selector="fps", interval_text="fused" or in one pass.  What it gains on real footage is not
-    measured here either.
+    otherwise.  Not available with frame_selector="fps" or interval_text="fused", nor as it stands in one pass.  What it gains on real
+    footage is not measured here either.
+    composite_params={"streaming": True, "ring_seconds": S, ...} with interval_image="quantile": the same pictures, byte for byte, made
+    in the selector's own pass, which also works in one pass (a pipe): the area band of every frame is parked in a ring on the device
+    and a subtitle's samples are ranked there once its end is known (frame_select.StreamingQuantile, vse_interval_ring_rank), which
+    also saves the quantile's own decode and upload in several passes.  `ring_seconds` must be given: the ring is device memory that
+    the caller grants (about 1.2 MB per frame of a 1080p default band), and {"streaming": True} alone stays the ValueError it was.  It
+    is a policy, and the command line takes 60: every subtitle whose trimmed range is at most that long is ranked on exactly the
+    several-pass samples; a longer one whose first sample has left the ring is ranked on samples of its last ring_seconds or so and
+    counted in `clamped_quantiles`, with one warning per clip.  The other keys it takes: `quantile`, `samples`, `trim_seconds`,
+    `ring_fn` and `keep_patches`.  Not with interval_text="fused", interval_frame="sharpest" or shard: fusion in one pass needs whole
+    frames, not bands.
     interval_text="fused" (change / hold selector with interval_image="middle" only; default "single", the above): the other answer to
     that single frame, in probability space: up to `samples` frames of each interval go through the recogniser, the boxes detected
     once on the sample nearest to the middle frame, and the recogniser's per-step class probabilities are averaged on the device before
@@ -316,7 +326,7 @@ class SubtitleExtractor:
     intervals, the frames recognised, raw_lines and the SRT equal those of the multi-pass run() on the same frames with the same
     arguments (recognition does not depend on how frames are grouped into batches: tests/test_gpu_ragged.py).  Refused in one pass,
     because they need a second look at frames already gone: sub_area="auto", mode="accurate" with an area, interval_image other than
-    "middle" (unless composite_params says "streaming"), interval_text="fused", shard, change_params' edge_thresh="auto".
+    "middle" (unless composite_params says "streaming": min / max / mean and the quantile), interval_text="fused", shard, change_params' edge_thresh="auto".
     interval_frame="sharpest" (change / hold selector with interval_image="middle" and interval_text="single" only; default "middle", all
     of the above): the one frame an interval is recognised on is chosen instead of being the middle one, which in compressed video is as
     likely as any other to be a coarse B-frame, a half-faded frame or a flash.  In the selector's own pass over the staged area rows the
@@ -346,27 +356,38 @@ class SubtitleExtractor:
             raise ValueError(f"interval_image={interval_image!r} composites the intervals of frame_selector='change' or 'hold', not {frame_selector!r}")
         if interval_text not in ("single", "fused"):
             raise ValueError(f"interval_text must be 'single' or 'fused', not {interval_text!r}")
-        # composite_params={"streaming": True}: the pictures are made in the selector's own pass (frame_select.StreamingCompositor).
+        # composite_params={"streaming": True}: the pictures are made in the selector's own pass (frame_select.StreamingCompositor, or
+        # StreamingQuantile for interval_image="quantile").
         # The keys that are this class's own, `streaming` and `keep_patches`, are taken out here; what remains goes to the compositor.
         composite_params = None if composite_params is None else dict(composite_params)
         self.streaming = bool(composite_params.pop("streaming", False)) if composite_params else False
         self.keep_patches = bool(composite_params.pop("keep_patches", False)) if composite_params and self.streaming else False
         if not self.streaming:
-            own = sorted(set(composite_params or {}) & {"keep_patches", "stream_fn"})
+            own = sorted(set(composite_params or {}) & {"keep_patches", "stream_fn", "ring_fn", "ring_seconds"})
             if own:
                 raise ValueError(f"composite_params: {own} belong to composite_params={{'streaming': True}} and mean nothing without it")
         if self.streaming:
             option = "composite_params={'streaming': True}"
-            if interval_image not in frame_select.COMPOSITE_MODES:
+            if interval_image not in frame_select.COMPOSITE_MODES + ("quantile",):
                 raise ValueError(f"{option} makes the min / max / mean picture of each interval in the selector's own pass; "
                                  f"interval_image={interval_image!r} is not one of them")
             if interval_text != "single":
                 raise ValueError(f"{option} does not combine with interval_text={interval_text!r}")
             if shard is not None:
                 raise ValueError(f"{option} composites every interval where the selector runs; it does not combine with shard={shard!r}")
-            unknown = set(composite_params) - {"trim_seconds", "stream_fn"}
-            if unknown:
-                raise ValueError(f"{option} takes trim_seconds, stream_fn and keep_patches beside it, not {sorted(unknown)}")
+            if interval_image == "quantile":
+                if "ring_seconds" not in composite_params:
+                    raise ValueError(f"{option} with interval_image='quantile' keeps the area's rows of every frame in a ring on the device "
+                                     "until a subtitle's end is known: say how many seconds of them with ring_seconds (the command line "
+                                     "takes 60; about 1.2 MB per frame of a 1080p band)")
+                unknown = set(composite_params) - {"quantile", "samples", "trim_seconds", "ring_seconds", "ring_fn"}
+                if unknown:
+                    raise ValueError(f"{option} with interval_image='quantile' takes quantile, samples, trim_seconds, ring_seconds, ring_fn "
+                                     f"and keep_patches beside it, not {sorted(unknown)}")
+            else:
+                unknown = set(composite_params) - {"trim_seconds", "stream_fn"}
+                if unknown:
+                    raise ValueError(f"{option} takes trim_seconds, stream_fn and keep_patches beside it, not {sorted(unknown)}")
         if interval_text == "fused" and (frame_selector not in ("change", "hold") or interval_image != "middle"):
             raise ValueError(f"interval_text='fused' reads the intervals of frame_selector='change' or 'hold' (not {frame_selector!r}) from their "
                              f"own frames, interval_image='middle' (not {interval_image!r}): composites and fused posteriors do not combine")
@@ -410,6 +431,7 @@ class SubtitleExtractor:
         self.intervals = None
         self.one_pass = (not hasattr(source, "read")) if one_pass is None else bool(one_pass)
         self.retain_bytes, self.clamped_intervals, self.peak_retained = retain_bytes, 0, 0
+        self.clamped_quantiles = 0        # streaming quantile: intervals that reached back beyond the ring (StreamingQuantile.clamped)
         if not self.one_pass and not hasattr(source, "read"):
             raise ValueError("one_pass=False needs a source with read(frame_no): this one is sequential and its frames cannot be looked at a second time")
         if self.one_pass:
@@ -486,7 +508,9 @@ class SubtitleExtractor:
         more = {}
         if self.interval_frame == "sharpest":
             more["focus_fn"] = (self.frame_params or {}).get("focus_fn") or frame_select.EngineFocus(shim._context())
-        if self.streaming:
+        if self.streaming and self.interval_image == "quantile":
+            more["compositor"] = self._compositor = frame_select.StreamingQuantile(**{"batch": self.batch, **self.composite_params})
+        elif self.streaming:
             more["compositor"] = self._compositor = frame_select.StreamingCompositor(
                 **{"mode": self.interval_image, **self.composite_params})
         return cls(self.change_counter, batch=self.batch, **self._change_params(), **more)
@@ -510,6 +534,7 @@ class SubtitleExtractor:
             self.intervals = sel.run(self._decode_order(up), self.sub_area, s.fps, uploader=up)
             if self.streaming:
                 self.interval_patches = self._compositor.patches
+                self.clamped_quantiles = getattr(self._compositor, "clamped", 0)
             if self.interval_frame == "sharpest":
                 self.focus = getattr(sel, "focus", None)            # (a clip without a frame leaves none, and no interval)
                 self.intervals = [(start, end, frame_select.sharpest_rep(start, end, self.focus, s.fps, self._trim_seconds()))
@@ -645,6 +670,7 @@ class SubtitleExtractor:
                 lines += recognise(queue)
             if keep_patches:
                 self.interval_patches = comp.patches
+            self.clamped_quantiles = getattr(comp, "clamped", 0)
             if sharpest:
                 self.focus = getattr(sel, "focus", None)
         finally:
@@ -798,12 +824,13 @@ def square_arguments(args):
     return out
 
 
-def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, focus_fn=None, stream_fn=None):
+def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, focus_fn=None, stream_fn=None, ring_fn=None):
     """ocr: the recogniser (None: shim.OcrRecogniser on the GPU, frames staged through staging.default_uploader, YUV 4:2:0 converted
     on the device); counter: the change / hold selector's count_fn (None: the GPU's); cells_fn: the locator's (None: the GPU's);
     composite_fn: what makes the picture of `--interval-image`, the compositor's accumulate_fn for min / max / mean and the quantile's
     rank_fn for quantile (None: the GPU's); focus_fn: what scores the frames of `--interval-frame sharpest` (None: the GPU's);
-    stream_fn: what makes the pictures of `--streaming-composite`, StreamingCompositor's stream_fn (None: the GPU's)."""
+    stream_fn: what makes the min / max / mean pictures of `--streaming-composite`, StreamingCompositor's stream_fn (None: the GPU's);
+    ring_fn: what makes its quantile pictures, StreamingQuantile's ring_fn (None: the GPU's)."""
     p = argparse.ArgumentParser(prog="python -m vse_amd.extractor", description="Extract a video's hard subtitles to SRT on the GPU.  "
                                 "`-` reads YUV4MPEG2 from standard input in one pass, e.g. "
                                 "`ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m vse_amd.extractor - -o film.srt`.")
@@ -856,12 +883,16 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
     p.add_argument("--interval-image", default="middle", choices=INTERVAL_IMAGES, help="change / hold selector: what the recogniser is "
                    "shown for each subtitle: its middle frame, the per-pixel min (light text) / max (dark text) / mean of all its frames, "
                    "or the per-pixel quantile of a few evenly spaced ones, which needs no polarity and shrugs off a flash or a late cut "
-                   "(not in one pass) [middle].  With --streaming-composite, min / max / mean also work in one pass.")
-    p.add_argument("--streaming-composite", action="store_true", help="--interval-image min / max / mean: make the pictures in the "
-                   "selector's own pass instead of a pass of their own, which also works in one pass (a pipe)")
+                   "[middle].  Other than middle, they work in one pass only with --streaming-composite.")
+    p.add_argument("--streaming-composite", action="store_true", help="--interval-image min / max / mean / quantile: make the pictures "
+                   "in the selector's own pass instead of a pass of their own, which also works in one pass (a pipe)")
     p.add_argument("--quantile", type=float, default=0.5, metavar="Q", help="--interval-image quantile: 0..1, 0.5 the median [0.5]")
     p.add_argument("--interval-samples", type=int, default=15, metavar="K", help="--interval-image quantile: frames sampled per subtitle, "
-                   "1..min(batch, 63); exact when the subtitle has no more frames, an estimate otherwise [15]")
+                   "1..min(batch, 63), with --streaming-composite 1..63; exact when the subtitle has no more frames, an estimate "
+                   "otherwise [15]")
+    p.add_argument("--ring-seconds", type=float, default=None, metavar="S", help="--interval-image quantile --streaming-composite: the "
+                   "area's rows of about this many seconds wait on the GPU (1.2 MB per frame of a 1080p band); a subtitle shown for "
+                   "longer gets the quantile of its last S seconds or so [60]")
     p.add_argument("--interval-frame", default="middle", choices=INTERVAL_FRAMES, help="change / hold selector: which single frame of each "
                    "subtitle is recognised: its middle frame, or the one whose standing edges are sharpest, scored in the selector's own pass "
                    "(works in one pass; not with --interval-image other than middle) [middle]")
@@ -893,16 +924,27 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
         if args.locator_max_hold_seconds is not None and args.locator_automaton != "hold":
             raise ValueError(f"--locator-max-hold-seconds bounds the runs of `--locator-automaton hold`, not of `--locator-automaton "
                              f"{args.locator_automaton}`")
-        if args.streaming_composite and args.interval_image not in frame_select.COMPOSITE_MODES:
+        ring = args.streaming_composite and args.interval_image == "quantile"
+        if args.streaming_composite and not ring and args.interval_image not in frame_select.COMPOSITE_MODES:
             raise ValueError(f"--streaming-composite makes the picture of `--interval-image min`, `max` or `mean`, not of "
                              f"`--interval-image {args.interval_image}`")
+        if args.ring_seconds is not None and not ring:
+            raise ValueError("--ring-seconds sizes the ring of `--interval-image quantile --streaming-composite` and means nothing without them")
         composite_params = None
-        if args.interval_image == "quantile":
+        if ring:
+            if composite_fn is not None or stream_fn is not None:
+                raise ValueError("--streaming-composite makes the pictures of `--interval-image quantile` with ring_fn; the "
+                                 f"{'composite_fn' if composite_fn is not None else 'stream_fn'} given makes other pictures and would not be called")
+            composite_params = {"streaming": True, "quantile": args.quantile, "samples": args.interval_samples,
+                                "ring_seconds": 60.0 if args.ring_seconds is None else args.ring_seconds,
+                                **({} if ring_fn is None else {"ring_fn": ring_fn})}
+            frame_select.StreamingQuantile(**{k: v for k, v in composite_params.items() if k != "streaming"})       # a bad value is refused before any work
+        elif args.interval_image == "quantile":
             composite_params = {"quantile": args.quantile, "samples": args.interval_samples, "rank_fn": composite_fn}
             frame_select.IntervalQuantile(**{"batch": args.batch, **composite_params})          # a bad value is refused before any work
         elif args.interval_image != "middle":
             composite_params = {"accumulate_fn": composite_fn}
-        if args.streaming_composite:
+        if args.streaming_composite and not ring:
             if composite_fn is not None:
                 raise ValueError("--streaming-composite makes its pictures with stream_fn; the composite_fn given makes those of the "
                                  "compositor's own pass and would not be called")

@@ -17,14 +17,15 @@ into stacked data, through an uploader's pinned memory and producer thread or wi
 one run / iter_run body of ChangeFrameSelector and HoldFrameSelector; and the Engine* callables keep their device state through
 `engine.DeviceState`.  area_locator.AreaLocator and keyframes.scan stand on the same pieces.  A selector given a `focus_fn` (EngineFocus,
 vse_frame_focus) also scores every frame in the same pass, and `sharpest_rep` picks an interval's frame by that score.  A selector given
-a `compositor` (StreamingCompositor, vse_interval_stream) also makes each interval's min / max / mean picture in that pass.
+a `compositor` (StreamingCompositor, vse_interval_stream) also makes each interval's min / max / mean picture in that pass, or
+(StreamingQuantile, vse_interval_ring_rank) its quantile picture.
 """
 from collections import deque
 from contextlib import closing
 from itertools import islice
 
 from . import staging
-from .engine import FRAME_HOLD_BOUNDED_MAX, INTERVAL_RANK_MAX, DeviceState
+from .engine import FRAME_HOLD_BOUNDED_MAX, INTERVAL_RANK_MAX, INTERVAL_RING_MAX_GROUPS, DeviceState
 from .shim import get_coordinates
 
 
@@ -314,7 +315,7 @@ class _IntervalSelector:
     frame's mask to the next call): when given, it is called once per batch on the same staged data as count_fn, with reset on the
     first batch, and its rows are appended to `focus`, int64 [frames fed, 2], readable while iterating.  Focus rows belong to the
     frames fed: they do not trail like the hold selector's counts.  None: no call, and `focus` is not touched.
-    compositor (StreamingCompositor): when given, begin(fps, lag) is called before the first batch, with `lag` the number of frames by
+    compositor (StreamingCompositor or StreamingQuantile): when given, begin(fps, lag) is called before the first batch, with `lag` the number of frames by
     which the rows trail (`_lag`), then compositor(data, area, n, tracker, closed) once per staged batch, after the tracker has been
     fed and while the batch is still resident, and once more after the flush with n = 0 and the last closings.  None: nothing changes."""
 
@@ -936,3 +937,128 @@ class IntervalQuantile:
                 at += len(nos)
         self.area = tuple(geometry)
         return self.patches
+
+
+# ---- streaming quantile (the quantile's pictures, made in the selector's own pass) ---------------------------------------------
+class EngineRingRanker(DeviceState):
+    """ring_fn of StreamingQuantile on the GPU: Context.interval_stream with no segments parks the batch in the ring, then
+    Context.interval_ring_rank ranks the groups where their frames lie.  Keeps the device state (of which only the ring is used) of
+    the last area and `cap` between calls.  Nothing in the ring is read that an earlier call of the same clip did not write, so a new
+    clip needs no reset; the area or cap may change only where a clip starts."""
+
+    def __call__(self, frames, area, cap, fed, n, groups):
+        y0, y1, x0, x1 = area
+        key = (y1 - y0, x1 - x0, cap)
+        if fed and self._key != key:
+            raise ValueError(f"EngineRingRanker: the area or cap changed to {key} after {fed} frames of a clip")
+        self._fresh(key, self.ctx.interval_stream_state)
+        if n:
+            self.ctx.interval_stream(self._device(frames), area, self._state, cap, fed, [], fed + 1, "min")
+        return self.ctx.interval_ring_rank(self._state, y1 - y0, x1 - x0, cap, fed + n, groups)
+
+
+class StreamingQuantile:
+    """IntervalQuantile's pictures without its pass over the clip, hence also from a pipe: a selector given this as `compositor` hands
+    it every staged batch while that is still on the device; the area band of EVERY frame is parked in a ring of `cap` bands there
+    (frame f in slot f % cap), and when a subtitle's end is known its samples, fuse_samples' frames as IntervalQuantile reads them,
+    are ranked where they lie (vse_interval_ring_rank).  The second look at frames already gone costs device memory, not a decode.
+    `ring_seconds` is a policy, not a measurement: with R = round(ring_seconds * fps), T = round(trim_seconds * fps), L the selector's
+    lag and B its batch, cap = R + T + L + B + 1, and every interval whose TRIMMED range has at most R + 1 frames is ranked on exactly
+    IntervalQuantile's samples.  The argument: an interval (start, end) closes in the call that brings the row of frame end + 1, so
+    end >= t', the last row seen before this call, and t' >= fed - L for the frames `fed` handed over before it (asserted); the call
+    stores n <= B frames first, after which the ring holds oldest = fed + n - cap + 1 onwards.  The first sample is first = last -
+    (frames - 1) with last >= end - T, so first >= fed - L - T - (frames - 1) >= fed + n - cap + 1 whenever frames <= R + 1.
+    A longer interval whose first sample has left the ring is sampled over [oldest, last] instead: K = min(samples, last - oldest +
+    1) frames oldest + (i (last - oldest)) // (K - 1), and for K == 1 the frame of the ring nearest to rep; it counts in `clamped`
+    and one warning is logged per clip, the treatment the extractor's retain_bytes gets.  Its picture then describes the end of the
+    subtitle only; its times are untouched.  A 1080p default band is 1.18 MB, so 60 s at 24 fps are about 1.8 GB of device memory.
+    That every frame named is in the ring is asserted on every call.
+
+    ring_fn(frames [n,h,w,3] uint8, area (y0, y1, x0, x1) in their pixels, cap, fed, n, groups) -> [len(groups), y1-y0, x1-x0, 3] uint8:
+    the n frames are frames fed + 1 .. fed + n of the clip and are stored first; then for each group (frame numbers, rank) per byte
+    element `rank` (0-based) of the named frames' values sorted ascending; at most INTERVAL_RING_MAX_GROUPS groups per call (more go
+    in further calls with n = 0).  Default: EngineRingRanker on the shim's device.  `patches`: {rep: uint8 ndarray [ah, aw, 3]}, a
+    plain dict as IntervalQuantile's, read back once per batch in which a subtitle ends."""
+
+    def __init__(self, ring_fn=None, quantile=0.5, samples=15, trim_seconds=0.25, ring_seconds=60.0, batch=64):
+        if not 0 <= quantile <= 1:
+            raise ValueError(f"StreamingQuantile: quantile must be in [0, 1], not {quantile!r}")
+        if samples < 1 or samples > INTERVAL_RANK_MAX:
+            raise ValueError(f"StreamingQuantile: samples must be 1..{INTERVAL_RANK_MAX}, not {samples}: an interval is ranked in one "
+                             f"group of at most {INTERVAL_RANK_MAX} frames")
+        if not ring_seconds >= 0:
+            raise ValueError(f"StreamingQuantile: ring_seconds must not be negative, not {ring_seconds!r}")
+        self.ring_fn, self.quantile, self.samples, self.trim_seconds = ring_fn, quantile, int(samples), trim_seconds
+        self.ring_seconds, self.batch = ring_seconds, int(batch)
+        self.area = None              # the area in the band's own pixels (0, y1 - y0, x0, x1), once a batch has been seen
+        self.patches = {}
+        self.cap = self.peak_ring = None
+        self.clamped = 0              # intervals of the last clip that reached back beyond the ring
+
+    def begin(self, fps, lag):
+        """A clip starts: its frame rate and the frames by which the selector's rows trail its frames."""
+        if self.ring_fn is None:
+            from . import shim
+            self.ring_fn = EngineRingRanker(shim._context())
+        self.fps, self.lag = fps, int(lag)
+        self.trim = int(round(self.trim_seconds * fps))
+        self.whole = int(round(self.ring_seconds * fps))          # R: trimmed ranges of up to R + 1 frames are certainly in the ring
+        self.cap, self.peak_ring, self.clamped = self.whole + self.trim + self.lag + self.batch + 1, 0, 0
+        self.patches = {}
+        self._fed = 0                 # frames handed over (and stored) so far
+        self._seen = 0                # tracker.fed after the last call: no interval that closes later ends before it
+
+    def _samples(self, start, end, rep, oldest):
+        """-> (the frames ranked for this interval, whether the ring cut them short)."""
+        nos, _pos = fuse_samples(start, end, rep, self.fps, self.samples, self.trim_seconds)
+        if nos[0] >= oldest:
+            return nos, False
+        first, last = trim_range(start, end, self.fps, self.trim_seconds)
+        assert last - first + 1 > self.whole + 1 and oldest <= last, \
+            f"StreamingQuantile: {start}..{end} (trimmed {first}..{last}) is not in the ring from {oldest}, cap {self.cap}"
+        m = last - oldest + 1
+        k = min(self.samples, m)
+        return ([max(rep, oldest)] if k <= 1 else [oldest + (i * (m - 1)) // (k - 1) for i in range(k)]), True
+
+    def __call__(self, data, area, n, tracker, closed):
+        import numpy as np
+        fed, after = self._fed, self._fed + n
+        assert n <= self.batch, f"StreamingQuantile: a batch of {n} frames, the ring was sized for {self.batch}"
+        assert after - tracker.fed <= self.lag or n == 0, \
+            f"StreamingQuantile: the rows trail by {after - tracker.fed} frames, more than the lag {self.lag}"
+        oldest = max(1, after - self.cap + 1)         # what the ring holds once this batch is stored: oldest .. after
+        groups, reps = [], []
+        for start, end, rep in closed:
+            assert self._seen <= end <= after, f"StreamingQuantile: {start}..{end} closed after the rows up to {self._seen} had been seen"
+            nos, cut = self._samples(start, end, rep, oldest)
+            assert all(oldest <= f <= after for f in nos) and all(a < b for a, b in zip(nos, nos[1:])), \
+                f"StreamingQuantile: the samples {nos} of {start}..{end} are not in the ring {oldest}..{after}"
+            if cut:
+                self.clamped += 1
+                if self.clamped == 1:
+                    import logging
+                    logging.getLogger(__name__).warning(
+                        "streaming quantile: the interval %d..%d reaches back beyond the ring of %d frames (ring_seconds=%s); its picture "
+                        "is made of the frames %d..%d (its times are untouched; further such intervals are counted in clamped)",
+                        start, end, self.cap, self.ring_seconds, nos[0], nos[-1])
+            self.peak_ring = max(self.peak_ring, after - nos[0] + 1)
+            groups.append((nos, quantile_rank(self.quantile, len(nos))))
+            reps.append(rep)
+        outs = []
+        for k in range(0, max(len(groups), 1), INTERVAL_RING_MAX_GROUPS):
+            part = groups[k:k + INTERVAL_RING_MAX_GROUPS]
+            if k == 0 and (n or part):                    # the batch is stored by the first call
+                res = self.ring_fn(data, area, self.cap, fed, n, part)
+            elif part:
+                res = self.ring_fn(data[:0], area, self.cap, after, 0, part)
+            if part:
+                outs.append(res)
+        if outs:                                          # one read-back per batch in which a subtitle ends
+            if hasattr(outs[0], "cpu"):
+                import torch
+                got = (outs[0] if len(outs) == 1 else torch.cat(outs)).cpu().numpy()
+            else:
+                got = np.concatenate([np.asarray(o) for o in outs])
+            assert len(got) == len(reps)
+            self.patches.update((rep, np.array(got[j])) for j, rep in enumerate(reps))      # (copies: a patch keeps no other alive)
+        self.area, self._fed, self._seen = tuple(area), after, tracker.fed
