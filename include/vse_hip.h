@@ -334,6 +334,32 @@ int vse_frame_cells_multi(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int
                           void* d_state, int reset, int flush,
                           int32_t* d_totals /* [nt,gy,gx,4]: covered, runs, present, cuts; accumulated across calls */,
                           void* stream);
+/* Replaces: nothing in the reference; it serves a selector that has to choose its edge threshold while the frames go by (a pipe, which
+ * cannot be read twice: vse_amd.frame_select.CalibratingChangeSelector).  vse_frame_cells_multi with one more output.  The cells tile
+ * the interior of the region, 8 x 64 interior pixels each, and their edge pixels are vse_frame_change's, so a frame's (e, a, v) summed
+ * over all cells at thresholds[q] are vse_frame_change's counts of that frame on the same rectangle at edge_thresh = thresholds[q]:
+ *   d_totals and d_state: bit for bit what vse_frame_cells_multi leaves for the same calls; the state is that entry's
+ *     (vse_frame_cells_multi_state_bytes(area_h, area_w, nt)) and may pass between the two entries in the middle of a clip.
+ *   d_counts int32 [n, nt, 3]: d_counts[f][q] = edges, appeared, vanished, integer for integer what vse_frame_change writes for frame f
+ *     at edge_thresh = thresholds[q] on the area [y0, y1) x [x0, x1), fed in the same batches from the same start; `reset` or a fresh
+ *     state means an empty previous mask in both.  Every element is written; n == 0 writes none (d_counts may then be NULL).
+ * One launch on `stream` behind the clearing of d_counts, no allocation, no device sync; the sums are integers and do not depend on the
+ * order of the blocks.  Returns VSE_E_INVAL, without touching the device, for everything vse_frame_cells_multi refuses or d_counts
+ * NULL with n > 0. */
+int vse_frame_cells_counts(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride,
+                           int y0, int y1, int x0, int x1, const int* thresholds /* host, [nt] */, int nt,
+                           int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
+                           void* d_state, int reset, int flush,
+                           int32_t* d_totals /* [nt,gy,gx,4], as vse_frame_cells_multi */,
+                           int32_t* d_counts /* [n,nt,3]: edges, appeared, vanished of the WHOLE area at thresholds[q] */, void* stream);
+/* Slice q (0 <= q < nt) of such a state, of a region of area_h x area_w pixels -> d_change_state, a vse_frame_change state of the same
+ * area (vse_frame_change_state_bytes(area_h, area_w) bytes, 8-byte aligned): the cells' last mask words laid out as that entry keeps
+ * them, every word written, the flag set.  After it vse_frame_change or vse_frame_focus at edge_thresh = thresholds[q] on the following
+ * frames give the rows that an uninterrupted run of theirs from the clip's start gives.  The cells' state is only read.  One small
+ * launch on `stream`, no allocation, no device sync.  Returns VSE_E_INVAL, and launches nothing, for an area below 3 x 3, nt outside
+ * 1..8, q outside 0..nt - 1, a NULL or misaligned pointer. */
+int vse_frame_cells_export_state(vse_ctx* ctx, const void* d_cells_state, int area_h, int area_w, int nt, int q, void* d_change_state,
+                                 void* stream);
 
 /* ---- held-edge frame selector ------------------------------------------------------------------------------------------- */
 /* Replaces: the same frame search of VideoSubFinder as vse_frame_change (backend/main.py:378-505, extract_frame_by_vsf), for

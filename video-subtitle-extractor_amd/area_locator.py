@@ -29,6 +29,10 @@ of the plateau of thresholds whose best grid row scores at least plateau_frac of
   thresholds 24 32 48 64 96 128 160 192   about half an octave apart around the constant;
   plateau_frac 0.9                        a judgement like the defaults above, not a measurement.
 With search_area set to a known subtitle area this is the calibration for a film whose box the user drew.
+That calibration also runs inside the change selector's own pass, without a pass of its own (frame_select.CalibratingChangeSelector,
+vse_frame_cells_counts; SubtitleExtractor's area_params={"streaming": True}): the cells of search_area tile the interior of the
+selector's area and their mask is the selector's, so the kernel that keeps these totals also hands back the selector's counts at every
+threshold, and `edge_thresh_scores` / `pick_edge_thresh` below decide on the same integers after the window's last frame.
 Known limits: the locator and the calibration run the CHANGE automaton unless `automaton="hold"`.  On a moving textured background
 every frame is a cut in every cell at every threshold, nothing scores, no area is found and "auto" falls back to 128 with a warning.
 How the rule behaves on real footage is unmeasured: there are no real clips here.

@@ -370,6 +370,94 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_multi_kernel(const 
     }
 }
 
+// ---- vse_frame_cells_counts -----------------------------------------------------------------------------------------------------
+// frame_cells_multi_kernel with one more output: the cells tile the interior of the region exactly as frame_change_kernel's tiles tile the
+// interior of its area, and the mask is the same statement for statement, so a frame's (e, a, v) summed over all cells at threshold q is
+// what frame_change_kernel counts on that area at th.t[q].  Each live lane adds its cell's three integers into
+// counts[((c0 + lane) * NT + q) * 3 ..] (cleared by the launcher ahead of the kernel); zeros are skipped as frame_change_kernel skips
+// them, and integer sums do not depend on the order the blocks arrive in.  Everything else is frame_cells_multi_kernel line for line,
+// which keeps its own copy: that kernel is not this one's to change.  No LDS beyond that kernel's ((FC_CHUNK + 1) * NT * FC_ROWS words,
+// 4160 B at NT = 1, 33280 B at NT = 8), no scratch; 95 VGPRs at NT = 1, 107 at NT = 8 (the compiler's resource usage for gfx950;
+// frame_cells_multi_kernel<NT> has 92 and 102), which leaves the waves per SIMD where that kernel has them, 5 and 4, and two blocks of
+// NT = 8 on a CU.  Runs with n == 0 too (reset and flush only; nothing is added to counts).
+template <int NT>
+__global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_counts_kernel(const uint8_t* __restrict__ src, int n, long pitch, long fstride,
+                                                                           int x0, int ih, int iw, CellThresholds th, CellRule rule,
+                                                                           unsigned long long* __restrict__ state, int reset, int flush,
+                                                                           int* __restrict__ totals, int* __restrict__ counts) {
+    __shared__ unsigned long long msk[NT * FC_CHUNK * FC_ROWS];           // [NT][FC_CHUNK][FC_ROWS]
+    __shared__ unsigned long long prv[NT * FC_ROWS];
+    static_assert(FC_CHUNK == 64, "the frames of a chunk are the lanes of a wave");
+    static_assert(NT >= 1 && NT <= FC_WAVES, "wave q owns threshold q");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int iy0 = blockIdx.y * FC_ROWS;
+    const long cell = (long)blockIdx.y * gridDim.x + blockIdx.x, cells = (long)gridDim.y * gridDim.x;
+    const TileLane t = tile_lane(blockIdx.x, iy0, ih, iw, x0);
+    const bool mine = wave < NT;            // wave q owns threshold q
+    unsigned long long* st = state + ((long)wave * cells + cell) * CELL_STATE_WORDS;
+    int* tot = totals + ((long)wave * cells + cell) * 4;
+    unsigned long long* mq = msk + wave * FC_CHUNK * FC_ROWS;
+    unsigned long long* pq = prv + wave * FC_ROWS;
+    if (mine && lane < FC_ROWS) pq[lane] = reset ? 0ull : st[lane];
+    CellRuns cr = {0, 0, 0, 0, 0};
+    if (mine && !reset) cr = {(int)st[FC_ROWS], tot[0], tot[1], tot[2], tot[3]};
+
+    for (int c0 = 0; c0 < n; c0 += FC_CHUNK) {
+        const int cn = min(FC_CHUNK, n - c0);
+        tile_masks_multi<NT>(src + (long)iy0 * pitch, c0, cn, pitch, fstride, t, th, msk);
+        __syncthreads();
+        if (mine) {                                // lane = frame of the chunk
+            const bool live = lane < cn;
+            int e = 0, a = 0, v = 0, ep = 0;
+            if (live) {
+#pragma unroll
+                for (int k = 0; k < FC_ROWS; ++k) {
+                    const unsigned long long cur = mq[lane * FC_ROWS + k], pre = lane ? mq[(lane - 1) * FC_ROWS + k] : pq[k];
+                    e += __popcll(cur);
+                    a += __popcll(cur & ~pre);
+                    v += __popcll(pre & ~cur);
+                    ep += __popcll(pre);           // edges[t-1]
+                }
+                // the whole area's counts of frame c0 + lane at threshold `wave`: c0 + lane < n and wave < NT, inside [n][NT][3]
+                int* o = counts + ((long)(c0 + lane) * NT + wave) * 3;
+                if (e) atomicAdd(o, e);
+                if (a) atomicAdd(o + 1, a);
+                if (v) atomicAdd(o + 2, v);
+            }
+            const long long uni = ep + a;          // |E' or E|
+            const unsigned long long present = __ballot(live && e >= rule.min_edges);
+            const unsigned long long ratio = __ballot(live && uni > 0 && (long long)(a + v) * rule.ratio_den >= (long long)rule.ratio_num * uni);
+            for (int f = 0; f < cn; ++f) cr.step((present >> f) & 1, (ratio >> f) & 1, rule);
+        }
+        __syncthreads();
+        if (mine && lane < FC_ROWS) pq[lane] = mq[(cn - 1) * FC_ROWS + lane];
+        __syncthreads();
+    }
+    if (mine && lane < FC_ROWS) st[lane] = pq[lane];
+    if (mine && lane == 0) {
+        if (flush) cr.close(rule);
+        st[FC_ROWS] = (unsigned long long)cr.run;
+        tot[0] = cr.covered;
+        tot[1] = cr.runs;
+        tot[2] = cr.present;
+        tot[3] = cr.cuts;
+    }
+}
+
+// Slice q of a vse_frame_cells_multi state -> a vse_frame_change state of the same area: a thread per interior row and word copies mask
+// word iy % FC_ROWS of cell (iy / FC_ROWS, w).  cell_state points at slice q's first cell; words is the change state behind its header.
+// Every word of the change state is written (ih * wpr of them; rows beyond the interior have no word there), then the flag.
+__global__ __launch_bounds__(256) void frame_cells_export_kernel(const unsigned long long* __restrict__ cell_state, int ih, int wpr,
+                                                                 unsigned long long* __restrict__ words, unsigned* flag) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (long)ih * wpr) {
+        const int iy = (int)(i / wpr), w = (int)(i % wpr);
+        const long cell = (long)(iy / FC_ROWS) * wpr + w;          // gx == wpr
+        words[i] = cell_state[cell * CELL_STATE_WORDS + iy % FC_ROWS];
+    }
+    if (i == 0) *flag = 1u;
+}
+
 // ---- vse_frame_hold -------------------------------------------------------------------------------------------------------------
 // H_u = the edge pixels of frame u whose run of consecutive edge frames is at least `hold` frames long.  Per pixel, along the frames t:
 //   run[t]   = E[t] ? min(run[t-1] + 1, hold) : 0          S[t] = (run[t] == hold): a run of `hold` frames ends at t
@@ -768,6 +856,50 @@ int vse_frame_cells_multi_launch(const void* d_bgr, int n, int64_t pitch, int64_
     }
 #undef VSE_CELLS_MULTI
     static_assert(FC_WAVES == 8, "one instantiation per number of thresholds");
+    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+}
+
+// Called by vse_frame_cells_counts (vse_runtime.hip) after it has checked the arguments as vse_frame_cells_multi does.  d_counts is
+// cleared on the stream ahead of the kernel, which adds into it.
+int vse_frame_cells_counts_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                                  const int* thresholds, int nt, int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
+                                  void* d_state, int reset, int flush, int32_t* d_totals, int32_t* d_counts, void* stream) {
+    const int ih = y1 - y0 - 2, iw = x1 - x0 - 2;
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
+    const CellRule rule = {min_edges, ratio_num, ratio_den, min_frames, max_frames};
+    CellThresholds th = {};
+    for (int q = 0; q < nt; ++q) th.t[q] = thresholds[q];
+    const dim3 grid((iw + 63) / 64, (ih + FC_ROWS - 1) / FC_ROWS), block(FC_WAVES * 64);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    unsigned long long* state = reinterpret_cast<unsigned long long*>(d_state);
+    int* totals = reinterpret_cast<int*>(d_totals);
+    int* counts = reinterpret_cast<int*>(d_counts);
+    if (nt < 1 || nt > FC_WAVES) return VSE_E_INVAL;
+    if (n > 0 && hipMemsetAsync(d_counts, 0, (size_t)n * nt * 3 * sizeof(int32_t), st) != hipSuccess) return VSE_E_HIP;
+#define VSE_CELLS_COUNTS(NT)                                                                                                             \
+    case NT:                                                                                                                             \
+        hipLaunchKernelGGL(frame_cells_counts_kernel<NT>, grid, block, 0, st, src, n, (long)pitch, (long)frame_stride, x0, ih, iw, th, rule, \
+                           state, reset, flush, totals, counts);                                                                         \
+        break;
+    switch (nt) {
+        VSE_CELLS_COUNTS(1) VSE_CELLS_COUNTS(2) VSE_CELLS_COUNTS(3) VSE_CELLS_COUNTS(4)
+        VSE_CELLS_COUNTS(5) VSE_CELLS_COUNTS(6) VSE_CELLS_COUNTS(7) VSE_CELLS_COUNTS(8)
+        default: return VSE_E_INVAL;
+    }
+#undef VSE_CELLS_COUNTS
+    static_assert(FC_WAVES == 8, "one instantiation per number of thresholds");
+    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+}
+
+// Called by vse_frame_cells_export_state (vse_runtime.hip) after it has checked the area and 0 <= q < nt <= vse_frame_cells_multi_max().
+int vse_frame_cells_export_launch(const void* d_cells_state, int area_h, int area_w, int q, void* d_change_state, void* stream) {
+    const int ih = area_h - 2, iw = area_w - 2, wpr = (iw + 63) / 64;
+    const long cells = (long)((ih + FC_ROWS - 1) / FC_ROWS) * wpr, nwords = (long)ih * wpr;
+    const unsigned long long* slice = reinterpret_cast<const unsigned long long*>(d_cells_state) + (long)q * cells * CELL_STATE_WORDS;
+    unsigned* flag = reinterpret_cast<unsigned*>(d_change_state);
+    unsigned long long* words = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(d_change_state) + 16);
+    hipLaunchKernelGGL(frame_cells_export_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                       slice, ih, wpr, words, flag);
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
 

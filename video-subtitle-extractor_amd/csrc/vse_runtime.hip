@@ -64,6 +64,10 @@ int vse_frame_cells_multi_max();                                                
 int vse_frame_cells_multi_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
                                  const int* thresholds, int nt, int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
                                  void* d_state, int reset, int flush, int32_t* d_totals, void* stream);
+int vse_frame_cells_counts_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                                  const int* thresholds, int nt, int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
+                                  void* d_state, int reset, int flush, int32_t* d_totals, int32_t* d_counts, void* stream);   // frame_change.hip
+int vse_frame_cells_export_launch(const void* d_cells_state, int area_h, int area_w, int q, void* d_change_state, void* stream);   // frame_change.hip
 size_t vse_frame_hold_word_bytes();                                                                                    // frame_change.hip
 int vse_frame_hold_launch(const void* d_bgr, int n, int steps, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
                           int edge_thresh, int hold, int skip, void* d_state, int fresh, int32_t* d_counts, void* stream);   // frame_change.hip
@@ -573,6 +577,45 @@ int vse_frame_cells_multi(vse_ctx* c, const void* d_bgr, int n, int src_h, int s
     const int rc = vse_frame_cells_multi_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, thresholds, nt, min_edges, ratio_num,
                                                 ratio_den, min_frames, max_frames, d_state, reset, flush, d_totals, stream);
     if (rc != VSE_OK) set_err("vse_frame_cells_multi: launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+// ---- calibration and selector counts in one pass (frame_change.hip) -------------------------------------------------------------------
+int vse_frame_cells_counts(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0, int y1,
+                           int x0, int x1, const int* thresholds, int nt, int min_edges, int ratio_num, int ratio_den, int min_frames,
+                           int max_frames, void* d_state, int reset, int flush, int32_t* d_totals, int32_t* d_counts, void* stream) {
+    if (!check_frames("vse_frame_cells_counts", c && d_totals && (d_counts || n <= 0), d_bgr, n, 0, src_h, src_w, pitch, frame_stride,
+                      d_state) ||
+        !check_area("vse_frame_cells_counts", "region", y0, y1, x0, x1, src_h, src_w) ||
+        !check_rule("vse_frame_cells_counts", ratio_num, ratio_den, min_frames, max_frames))
+        return VSE_E_INVAL;
+    if (!thresholds || nt < 1 || nt > vse_frame_cells_multi_max()) {
+        set_err("vse_frame_cells_counts: %d thresholds (1..%d, not NULL)", nt, vse_frame_cells_multi_max());
+        return VSE_E_INVAL;
+    }
+    for (int q = 0; q < nt; ++q) {
+        if (thresholds[q] < 1 || thresholds[q] > 255 || (q && thresholds[q] <= thresholds[q - 1])) {
+            set_err("vse_frame_cells_counts: threshold %d of %d is %d (each 1..255, ascending and distinct)", q, nt, thresholds[q]);
+            return VSE_E_INVAL;
+        }
+    }
+    if (n == 0 && !reset && !flush) return VSE_OK;
+    const int rc = vse_frame_cells_counts_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, thresholds, nt, min_edges, ratio_num,
+                                                 ratio_den, min_frames, max_frames, d_state, reset, flush, d_totals, d_counts, stream);
+    if (rc != VSE_OK) set_err("vse_frame_cells_counts: launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+int vse_frame_cells_export_state(vse_ctx* c, const void* d_cells_state, int area_h, int area_w, int nt, int q, void* d_change_state,
+                                 void* stream) {
+    if (!c || !d_cells_state || !d_change_state || area_h < 3 || area_w < 3 || nt < 1 || nt > vse_frame_cells_multi_max() || q < 0 ||
+        q >= nt || ((reinterpret_cast<uintptr_t>(d_cells_state) | reinterpret_cast<uintptr_t>(d_change_state)) & 7)) {
+        set_err("vse_frame_cells_export_state: bad arguments (area %d x %d of at least 3 x 3, slice %d of %d thresholds (1..%d), states "
+                "8-byte aligned, no NULL pointer)", area_h, area_w, q, nt, vse_frame_cells_multi_max());
+        return VSE_E_INVAL;
+    }
+    const int rc = vse_frame_cells_export_launch(d_cells_state, area_h, area_w, q, d_change_state, stream);
+    if (rc != VSE_OK) set_err("vse_frame_cells_export_state: launch failed: %s", hipGetErrorString(hipGetLastError()));
     return rc;
 }
 

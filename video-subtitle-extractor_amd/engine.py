@@ -34,7 +34,7 @@ EXPORTS = [
     "vse_interval_stream_state_bytes", "vse_interval_stream", "vse_interval_ring_rank",
     "vse_yuv_frame_bytes", "vse_yuv_to_bgr_format", "vse_yuv_deinterlace", "vse_yuv_field_match",
     "vse_yuv_tonemap_table_bytes", "vse_yuv_to_bgr_tonemap", "vse_yuv_resample_table_bytes", "vse_yuv_resample",
-    "vse_yuv_vscale",
+    "vse_yuv_vscale", "vse_frame_cells_counts", "vse_frame_cells_export_state",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -192,6 +192,8 @@ def load_library(path=None):
     lib.vse_frame_cells_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                           C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.vse_frame_cells_counts.argtypes = lib.vse_frame_cells_multi.argtypes[:-1] + [C.c_void_p, C.c_void_p]
+    lib.vse_frame_cells_export_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.vse_frame_hold_state_bytes.restype = C.c_size_t
     lib.vse_frame_hold_state_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.vse_frame_hold.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
@@ -636,6 +638,44 @@ class Context:
                                               int(bool(reset)), int(bool(flush)), C.c_void_p(state.totals.data_ptr()), self.stream()),
                "vse_frame_cells_multi")
         return state.totals
+
+    def frame_cells_counts(self, frames_u8, area, thresholds, params, state, reset=False, flush=False):
+        """frame_cells_multi that also counts for the selector: every argument as there, and the state is that call's
+        (frame_cells_multi_state; it may pass between the two) -> (state.totals, cuda int32 [n,nt,3]): row [f][q] is frame_change's
+        edges / appeared / vanished of frame f on the same area at edge_thresh = thresholds[q] (include/vse_hip.h
+        vse_frame_cells_counts)."""
+        t = self.torch
+        frames = self._frames_args(frames_u8, allow_empty=True)
+        n = frames[1]
+        y0, y1, x0, x1 = (int(v) for v in area)
+        th = [int(v) for v in thresholds]
+        nt = len(th)
+        gy, gx = self.frame_cells_dims(y1 - y0, x1 - x0)
+        nbytes = self.lib.vse_frame_cells_multi_state_bytes(y1 - y0, x1 - x0, nt)
+        assert nbytes and state.words.numel() >= nbytes and tuple(state.totals.shape) == (nt, gy, gx, 4)
+        counts = t.empty((n, nt, 3), dtype=t.int32, device=self.tdev)
+        p = CellParams(*(int(v) for v in params))
+        _check(self.lib.vse_frame_cells_counts(self.handle, *frames, y0, y1, x0, x1, (C.c_int * nt)(*th), nt, p.min_edges, p.ratio_num,
+                                               p.ratio_den, p.min_frames, p.max_frames, C.c_void_p(state.words.data_ptr()),
+                                               int(bool(reset)), int(bool(flush)), C.c_void_p(state.totals.data_ptr()),
+                                               C.c_void_p(counts.data_ptr()) if n else None, self.stream()), "vse_frame_cells_counts")
+        return state.totals, counts
+
+    def frame_cells_export_state(self, state, area_h, area_w, q, out=None):
+        """Slice q of a frame_cells_multi_state of an area_h x area_w region -> a frame_change state of the same area (`out`, or a new
+        one) holding that threshold's last mask, so that frame_change / frame_focus at thresholds[q] continue the clip (include/vse_hip.h
+        vse_frame_cells_export_state)."""
+        t = self.torch
+        nt = int(state.totals.shape[0])
+        nbytes = self.lib.vse_frame_change_state_bytes(int(area_h), int(area_w))
+        if out is None and nbytes:
+            out = t.zeros(nbytes, dtype=t.uint8, device=self.tdev)
+        assert out is None or (out.dtype == t.uint8 and out.is_contiguous() and out.numel() >= nbytes)
+        assert state.words.numel() >= self.lib.vse_frame_cells_multi_state_bytes(int(area_h), int(area_w), nt)
+        _check(self.lib.vse_frame_cells_export_state(self.handle, C.c_void_p(state.words.data_ptr()), int(area_h), int(area_w), nt, int(q),
+                                                     C.c_void_p(out.data_ptr()) if out is not None else None, self.stream()),
+               "vse_frame_cells_export_state")
+        return out
 
     # ---- held-edge frame selector ---------------------------------------------------------------------------------
     def frame_hold_state(self, area_h, area_w, hold):

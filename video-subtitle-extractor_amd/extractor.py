@@ -312,6 +312,21 @@ class SubtitleExtractor:
     a busy background that stands still behind the subtitles needs: on held edges alone its cells fall to the logo rule and neither
     an area nor a threshold is found.  It is NOT inherited from change_params as hold_seconds is: runs that set the selector's
     max_hold_* together with automaton="hold" keep their results, and the locator bounds its runs only when area_params says so.
+    area_params={"streaming": True} with change_params={"edge_thresh": "auto"}, frame_selector="change" and a given area: the threshold is
+    chosen in the selector's own pass instead of a calibration pass of its own (frame_select.CalibratingChangeSelector: the calibration's
+    cells tile the selector's area and share its mask, so one kernel, vse_frame_cells_counts, gives the calibration's totals and the
+    selector's counts at every candidate threshold), which saves a decode and an upload of the band in several passes and is what makes
+    "auto" work in one pass (a pipe).  `calibrate_seconds`: S decides after round(S * fps) frames, None (several passes only) after the
+    whole clip; the threshold, intervals, recognised frames, raw_lines and SRT are those of the run without the key whose area_params
+    say probe=(1, that many frames).  In one pass S must be given: until the decision a frame is kept while ANY of the eight candidates'
+    trackers may still want it (by the rule below, per candidate, plus the middle frames of the intervals a candidate has closed), and the
+    window bounds that; `retain_bytes` stays the fallback behind it, `peak_retained` reports what was held, and after the decision the
+    frames only other thresholds wanted go.  The command line takes 300 s for a pipe: a policy, not a measurement.  `streaming`,
+    `calibrate_seconds`, `cells_counts_fn` and `export_fn` (the selector's callables; default the GPU's) are this class's own and are taken
+    out before the rest reaches the locator; `edge_scores` and `frames_calibrated` say what the choice rests on.  Refused with the key,
+    by name: frame_selector other than "change", automaton="hold" / max_hold_* in area_params, sub_area="auto" or None, mode="accurate",
+    interval_frame="sharpest", composite_params' streaming, shard, probe; the key without edge_thresh="auto", and the other three keys
+    without the key, mean nothing and are refused too.
     one_pass (None: exactly when the source has no `read`, e.g. ingest.Y4mStream over a pipe; True forces it on a seekable source and
     halves its decode work; False on a sequential source is a ValueError): the clip is read once, in decode order.  frame_selector="fps":
     frame `no` is a task iff (no - 1) % max(1, int(fps // extract_frequency)) == 0 (fps_tasks' rule without the frame count); tasks go
@@ -326,7 +341,7 @@ class SubtitleExtractor:
     intervals, the frames recognised, raw_lines and the SRT equal those of the multi-pass run() on the same frames with the same
     arguments (recognition does not depend on how frames are grouped into batches: tests/test_gpu_ragged.py).  Refused in one pass,
     because they need a second look at frames already gone: sub_area="auto", mode="accurate" with an area, interval_image other than
-    "middle" (unless composite_params says "streaming": min / max / mean and the quantile), interval_text="fused", shard, change_params' edge_thresh="auto".
+    "middle" (unless composite_params says "streaming": min / max / mean and the quantile), interval_text="fused", shard, change_params' edge_thresh="auto" (unless area_params says "streaming").
     interval_frame="sharpest" (change / hold selector with interval_image="middle" and interval_text="single" only; default "middle", all
     of the above): the one frame an interval is recognised on is chosen instead of being the middle one, which in compressed video is as
     likely as any other to be a coarse B-frame, a half-faded frame or a flash.  In the selector's own pass over the staged area rows the
@@ -404,6 +419,17 @@ class SubtitleExtractor:
                 raise ValueError(f"frame_params takes trim_seconds and focus_fn, not {sorted(unknown)}")
         self.interval_frame, self.frame_params, self.focus = interval_frame, frame_params, None
         self.source, self.ocr, self.detect_batch = source, ocr, detect_batch
+        # area_params={"streaming": True}: the threshold of edge_thresh="auto" is chosen in the selector's own pass
+        # (frame_select.CalibratingChangeSelector).  The keys that are this class's own, `streaming`, `calibrate_seconds`, `cells_counts_fn`
+        # and `export_fn`, are taken out here; what remains goes to the locator.
+        area_params = None if area_params is None else dict(area_params)
+        self.calibrating = bool(area_params.pop("streaming", False)) if area_params else False
+        if not self.calibrating:
+            own = sorted(set(area_params or {}) & {"calibrate_seconds", "cells_counts_fn", "export_fn"})
+            if own:
+                raise ValueError(f"area_params: {own} belong to area_params={{'streaming': True}} and mean nothing without it")
+        self.calibrate_seconds = area_params.pop("calibrate_seconds", None) if self.calibrating else None
+        self._calibrate_fns = (area_params.pop("cells_counts_fn", None), area_params.pop("export_fn", None)) if self.calibrating else None
         self.auto_area, self.area_params, self.located_area = isinstance(sub_area, str) and sub_area == "auto", area_params, None
         self.sub_area, self.mode, self.language = None if self.auto_area else sub_area, mode, language
         self.extract_frequency, self.default_subtitle_area = extract_frequency, default_subtitle_area
@@ -431,14 +457,39 @@ class SubtitleExtractor:
         self.intervals = None
         self.one_pass = (not hasattr(source, "read")) if one_pass is None else bool(one_pass)
         self.retain_bytes, self.clamped_intervals, self.peak_retained = retain_bytes, 0, 0
+        self.edge_scores, self.frames_calibrated = None, 0       # area_params' streaming: the scores and the frames the choice rests on
         self.clamped_quantiles = 0        # streaming quantile: intervals that reached back beyond the ring (StreamingQuantile.clamped)
         if not self.one_pass and not hasattr(source, "read"):
             raise ValueError("one_pass=False needs a source with read(frame_no): this one is sequential and its frames cannot be looked at a second time")
+        if self.calibrating:
+            option = "area_params={'streaming': True}"
+            if not self.auto_thresh:
+                raise ValueError(f"{option} chooses the threshold of change_params={{'edge_thresh': 'auto'}} in the selector's own pass and means "
+                                 "nothing without it")
+            held = sorted(set(self.area_params) & {"max_hold_seconds", "max_hold_frames"})
+            refused = [(f"frame_selector={frame_selector!r}", frame_selector != "change"),
+                       (f"automaton={self.area_params.get('automaton')!r}", self.area_params.get("automaton", "change") != "change"),
+                       (f"{held[0] if held else 'max_hold_seconds'} in area_params", bool(held)),
+                       ("sub_area='auto'", self.auto_area), ("sub_area=None", sub_area is None),
+                       (f"mode={mode!r}", mode not in ("fast", "auto")),
+                       (f"interval_frame={interval_frame!r}", interval_frame != "middle"),
+                       ("composite_params={'streaming': True}", self.streaming), (f"shard={shard!r}", shard is not None),
+                       ("probe in area_params (calibrate_seconds says how many frames decide)", "probe" in self.area_params)]
+            for what, hit in refused:
+                if hit:
+                    raise ValueError(f"{option} decides the threshold of frame_selector='change' over a given sub_area while that selector "
+                                     f"runs, with the change automaton on every frame; it does not combine with {what}, which needs the "
+                                     "threshold from the first frame or has a calibration of its own")
+            if self.calibrate_seconds is not None and not self.calibrate_seconds > 0:
+                raise ValueError(f"{option}: calibrate_seconds must be positive, not {self.calibrate_seconds!r}")
+            if self.one_pass and self.calibrate_seconds is None:
+                raise ValueError(f"{option} in one pass needs calibrate_seconds: the window bounds the frames kept while eight thresholds "
+                                 "are undecided (the command line takes 300 for a pipe)")
         if self.one_pass:
             refused = [("sub_area='auto'", self.auto_area), ("mode='accurate' with a subtitle area", mode == "accurate" and sub_area is not None),
                        (f"interval_image={interval_image!r}", interval_image != "middle" and not self.streaming),
                        (f"interval_text={interval_text!r}", interval_text != "single"), (f"shard={shard!r}", shard is not None),
-                       ("edge_thresh='auto'", self.auto_thresh)]
+                       ("edge_thresh='auto'", self.auto_thresh and not self.calibrating)]
             for what, hit in refused:
                 if hit:
                     raise ValueError(f"{what} is not available in one pass (a sequential source, or one_pass=True): it needs a second look "
@@ -496,6 +547,12 @@ class SubtitleExtractor:
         self._keep_edge_thresh(loc)
         return self.edge_thresh
 
+    def _keep_calibration(self, sel):
+        """area_params' streaming: what the selector decided in its own pass (128 for a clip without a frame)."""
+        from . import area_locator
+        self.edge_thresh = area_locator.DEFAULT_EDGE_THRESH if sel.edge_thresh is None else sel.edge_thresh
+        self.edge_scores, self.frames_calibrated = sel.scores, sel.frames_scanned
+
     def _change_params(self):
         """The selector's keyword arguments, edge_thresh="auto" resolved to the integer."""
         if not self.auto_thresh:
@@ -504,6 +561,14 @@ class SubtitleExtractor:
 
     def _interval_selector(self):
         """The change or hold selector of this run (`_selects_intervals`); both take run / iter_run(frames, sub_area, fps, uploader)."""
+        if self.calibrating:
+            window = None if self.calibrate_seconds is None else int(round(self.calibrate_seconds * self.source.fps))
+            if window is not None and window < 1:
+                raise ValueError(f"area_params: calibrate_seconds={self.calibrate_seconds!r} is less than one frame at {self.source.fps} fps")
+            params = {k: v for k, v in (self.change_params or {}).items() if k != "edge_thresh"}
+            return frame_select.CalibratingChangeSelector(self.change_counter, *self._calibrate_fns, window=window, batch=self.batch,
+                                                          locator_params={k: v for k, v in self.area_params.items() if k != "cells_fn"},
+                                                          **params)
         cls = frame_select.ChangeFrameSelector if self.frame_selector == "change" else frame_select.HoldFrameSelector
         more = {}
         if self.interval_frame == "sharpest":
@@ -532,6 +597,8 @@ class SubtitleExtractor:
             up = self._uploader()
             sel = self._interval_selector()
             self.intervals = sel.run(self._decode_order(up), self.sub_area, s.fps, uploader=up)
+            if self.calibrating:
+                self._keep_calibration(sel)
             if self.streaming:
                 self.interval_patches = self._compositor.patches
                 self.clamped_quantiles = getattr(self._compositor, "clamped", 0)
@@ -616,6 +683,12 @@ class SubtitleExtractor:
                     comp.patches.pop(no, None)
             return got
 
+        def still_kept(start, end, rep):
+            """retain_bytes took frame `rep`: the oldest frame still kept at or behind it, inside the interval when there is one (of an
+            interval that a candidate threshold closed long before the decision every frame may be gone: None)."""
+            inside = [k for k in kept if rep <= k <= end] or [k for k in kept if start <= k < rep][-1:]
+            return min(inside or [k for k in kept if k >= rep], default=None)
+
         sharpest = self.interval_frame == "sharpest"
         trim = int(round(self._trim_seconds() * self.source.fps)) if sharpest else 0
         # interval_frame="sharpest": the best frame so far of the open run starting at best_of, among its frames best_of + trim .. best_to
@@ -632,13 +705,16 @@ class SubtitleExtractor:
                     if sharpest:
                         rep = frame_select.sharpest_rep(start, end, sel.focus, self.source.fps, self._trim_seconds())
                     if rep not in kept:                   # the cap took it: the oldest frame of the interval that is still there
-                        rep = min(k for k in kept if k >= rep)
+                        gone, rep = rep, still_kept(start, end, rep)
                         self.clamped_intervals += 1
                         if self.clamped_intervals == 1:
                             logging.getLogger(__name__).warning(
-                                "one pass: the interval %d..%d outgrew retain_bytes=%d; it is recognised on frame %d instead of its %s "
+                                "one pass: the interval %d..%d outgrew retain_bytes=%d; it is recognised on frame %s instead of its %s "
                                 "frame (its times are untouched; further such intervals are counted in clamped_intervals)",
                                 start, end, self.retain_bytes, rep, self.interval_frame)
+                        if rep is None:                   # nothing of it is left to recognise: it keeps its times and has no text
+                            self.intervals.append((start, end, gone))
+                            continue
                     if comp is not None and rep != (start + end) // 2:
                         comp.patches[rep] = comp.patches.pop((start + end) // 2)      # (a clamped interval: its picture goes with the frame shown)
                     self.intervals.append((start, end, rep))
@@ -646,6 +722,20 @@ class SubtitleExtractor:
                 while len(queue) >= self.batch:
                     lines += recognise(queue[:self.batch])
                     del queue[:self.batch]
+                if self.calibrating and not sel.decided:
+                    # the threshold is open: a frame stays while ANY candidate may still want it, by the rule below per candidate
+                    # (at or behind the middle of its open run) or as the middle frame of an interval it has closed
+                    t = sel.trackers[0].fed
+                    floor = min(t + 1 if tr.open_start is None else (tr.open_start + t) // 2 for tr in sel.trackers)
+                    reps = {rep for closed_by in sel.pending for _s, _e, rep in closed_by}
+                    for k in [k for k in kept if k < floor and k not in reps]:
+                        nbytes -= _frame_nbytes(kept.pop(k))
+                    if nbytes > self.retain_bytes:
+                        for k in sorted(k for k in kept if k < t):                          # frame t itself always stays
+                            nbytes -= _frame_nbytes(kept.pop(k))
+                            if nbytes <= self.retain_bytes:
+                                break
+                    continue
                 t, open_start = sel.tracker.fed, sel.tracker.open_start
                 floor = t + 1 if open_start is None else (open_start + t) // 2
                 if sharpest and open_start is not None:
@@ -673,6 +763,8 @@ class SubtitleExtractor:
             self.clamped_quantiles = getattr(comp, "clamped", 0)
             if sharpest:
                 self.focus = getattr(sel, "focus", None)
+            if self.calibrating:
+                self._keep_calibration(sel)
         finally:
             batches.close()
             if ocr_up is not None:
@@ -715,7 +807,7 @@ class SubtitleExtractor:
             self.edge_thresh = None
         if self.auto_area:
             self.locate_area()
-        elif self.auto_thresh and self._selects_intervals():
+        elif self.auto_thresh and self._selects_intervals() and not self.calibrating:
             self.calibrate_edge_thresh()
         self.interval_patches = None
         tasks = self.select_tasks()
@@ -824,13 +916,15 @@ def square_arguments(args):
     return out
 
 
-def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, focus_fn=None, stream_fn=None, ring_fn=None):
+def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, focus_fn=None, stream_fn=None, ring_fn=None,
+         cells_counts_fn=None, export_fn=None):
     """ocr: the recogniser (None: shim.OcrRecogniser on the GPU, frames staged through staging.default_uploader, YUV 4:2:0 converted
     on the device); counter: the change / hold selector's count_fn (None: the GPU's); cells_fn: the locator's (None: the GPU's);
     composite_fn: what makes the picture of `--interval-image`, the compositor's accumulate_fn for min / max / mean and the quantile's
     rank_fn for quantile (None: the GPU's); focus_fn: what scores the frames of `--interval-frame sharpest` (None: the GPU's);
     stream_fn: what makes the min / max / mean pictures of `--streaming-composite`, StreamingCompositor's stream_fn (None: the GPU's);
-    ring_fn: what makes its quantile pictures, StreamingQuantile's ring_fn (None: the GPU's)."""
+    ring_fn: what makes its quantile pictures, StreamingQuantile's ring_fn (None: the GPU's); cells_counts_fn, export_fn: what counts
+    and hands over for `--streaming-calibration`, CalibratingChangeSelector's cells_fn and export_fn (None: the GPU's)."""
     p = argparse.ArgumentParser(prog="python -m vse_amd.extractor", description="Extract a video's hard subtitles to SRT on the GPU.  "
                                 "`-` reads YUV4MPEG2 from standard input in one pass, e.g. "
                                 "`ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m vse_amd.extractor - -o film.srt`.")
@@ -872,6 +966,11 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
     p.add_argument("--selector", default="fps", choices=("fps", "change", "hold"), help="which frames go to OCR [fps]")
     p.add_argument("--edge-thresh", default="128", metavar="auto|N", help="change / hold selector: the luma gradient that makes an edge "
                    "pixel, or `auto` to choose it for this clip first (not in one pass) [128]")
+    p.add_argument("--streaming-calibration", action="store_true", help="--selector change --edge-thresh auto with a given --area: choose "
+                   "the threshold in the selector's own pass instead of a pass of its own, which also works in one pass (a pipe)")
+    p.add_argument("--calibrate-seconds", type=float, default=None, metavar="S", help="--streaming-calibration: the threshold is chosen "
+                   "on the first S seconds; until then one pass keeps the frames any of the eight candidate thresholds may want [a file: "
+                   "the whole clip; `-`: 300, a policy, not a measurement: nobody has tried it on real films]")
     p.add_argument("--max-hold-seconds", type=float, default=None, metavar="S", help="--selector hold: count only edges that hold still for "
                    "at most S seconds, so a static busy background, a logo or a watermark drops out; a subtitle shown for longer drops out "
                    "too, and one pass keeps S seconds more of frames [none: no bound]")
@@ -924,6 +1023,14 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
         if args.locator_max_hold_seconds is not None and args.locator_automaton != "hold":
             raise ValueError(f"--locator-max-hold-seconds bounds the runs of `--locator-automaton hold`, not of `--locator-automaton "
                              f"{args.locator_automaton}`")
+        calibration = {}
+        if args.streaming_calibration:
+            calibrate_seconds = 300.0 if args.calibrate_seconds is None and args.video == "-" else args.calibrate_seconds
+            calibration = {"streaming": True, **({} if calibrate_seconds is None else {"calibrate_seconds": calibrate_seconds}),
+                           **({} if cells_counts_fn is None else {"cells_counts_fn": cells_counts_fn}),
+                           **({} if export_fn is None else {"export_fn": export_fn})}
+        elif args.calibrate_seconds is not None:
+            raise ValueError("--calibrate-seconds sets the window of --streaming-calibration and means nothing without it")
         ring = args.streaming_composite and args.interval_image == "quantile"
         if args.streaming_composite and not ring and args.interval_image not in frame_select.COMPOSITE_MODES:
             raise ValueError(f"--streaming-composite makes the picture of `--interval-image min`, `max` or `mean`, not of "
@@ -969,7 +1076,7 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
                                composite_params=composite_params, interval_frame=args.interval_frame,
                                frame_params=None if focus_fn is None else {"focus_fn": focus_fn},
                                change_params=change_params or None,
-                               area_params={**({} if cells_fn is None else {"cells_fn": cells_fn}),
+                               area_params={**calibration, **({} if cells_fn is None else {"cells_fn": cells_fn}),
                                             **({} if args.locator_automaton == "change" else {"automaton": args.locator_automaton}),
                                             **({} if args.locator_max_hold_seconds is None
                                                else {"max_hold_seconds": args.locator_max_hold_seconds})} or None)

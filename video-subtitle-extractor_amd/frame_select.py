@@ -18,7 +18,8 @@ one run / iter_run body of ChangeFrameSelector and HoldFrameSelector; and the En
 `engine.DeviceState`.  area_locator.AreaLocator and keyframes.scan stand on the same pieces.  A selector given a `focus_fn` (EngineFocus,
 vse_frame_focus) also scores every frame in the same pass, and `sharpest_rep` picks an interval's frame by that score.  A selector given
 a `compositor` (StreamingCompositor, vse_interval_stream) also makes each interval's min / max / mean picture in that pass, or
-(StreamingQuantile, vse_interval_ring_rank) its quantile picture.
+(StreamingQuantile, vse_interval_ring_rank) its quantile picture.  CalibratingChangeSelector (vse_frame_cells_counts) is the change
+selector that chooses its edge threshold per clip in that same pass.
 """
 from collections import deque
 from contextlib import closing
@@ -415,6 +416,141 @@ class ChangeFrameSelector(_IntervalSelector):
 
     def _flush(self, data, area, fed):
         return ()                         # every row came with its frame
+
+
+# ---- the change selector that chooses its own edge threshold while the frames go by ------------------------------------------------
+class EngineCellsCounts(DeviceState):
+    """cells_fn of CalibratingChangeSelector on the GPU (Context.frame_cells_counts), beside area_locator.EngineCells: keeps the device
+    state of the last region and threshold count between calls; (frames | None, area, engine.CellParams, reset, flush, thresholds) ->
+    (totals [nt,gy,gx,4], counts [n,nt,3]), frames None with flush closing the open runs.  `export(area, q, counter)` makes slice q of
+    that state the state of an EngineCounter (Context.frame_cells_export_state), whose next call then continues the clip."""
+
+    def __call__(self, frames, area, params, reset, flush, thresholds):
+        t = self.ctx.torch
+        y0, y1, x0, x1 = area
+        frames = t.empty((0, y1, x1, 3), dtype=t.uint8, device=self.ctx.tdev) if frames is None else self._device(frames)
+        reset = self._fresh((y1 - y0, x1 - x0, len(thresholds)), self.ctx.frame_cells_multi_state) or reset
+        return self.ctx.frame_cells_counts(frames, area, thresholds, params, self._state, reset, flush)
+
+    def export(self, area, q, counter):
+        y0, y1, x0, x1 = area
+        if self._key is None or self._key[:2] != (y1 - y0, x1 - x0):
+            raise ValueError(f"EngineCellsCounts: no state of a {y1 - y0} x {x1 - x0} region to export")
+        counter._fresh((y1 - y0, x1 - x0), self.ctx.frame_change_state)
+        self.ctx.frame_cells_export_state(self._state, y1 - y0, x1 - x0, q, out=counter._state)
+
+
+class CalibratingChangeSelector(_IntervalSelector):
+    """ChangeFrameSelector with change_params' edge_thresh="auto" and a given area, in ONE pass over the frames: what
+    area_locator.AreaLocator(edge_thresh="auto", search_area=the area) decides in a pass of its own is decided here while the selector
+    runs, so a pipe, which cannot be read twice, gets a calibrated threshold, and a file is decoded once less.  The calibration's cells
+    tile the interior of the selector's area and their mask is the selector's, so one kernel (vse_frame_cells_counts) hands back both
+    the calibration's totals and, per frame and candidate threshold, exactly the counts vse_frame_change would write at that threshold.
+    Up to the decision the batches go through cells_fn, one IntervalTracker per threshold is fed its row of the counts (each built as
+    ChangeFrameSelector builds its one: default_min_edges, change_ratio, min_frames), and no interval is yielded.  The decision falls
+    after the row of frame `window` (None: after the clip's last frame; a clip that ends sooner decides at its end; a batch that
+    straddles it is split there): the cells are flushed, the totals read once, area_locator.pick_edge_thresh chooses with frames_scanned
+    = the frames of the window, so the choice is AreaLocator(search_area=the area, probe=(1, window))'s; when no threshold scores, the
+    locator's warning is given and 128 is used (which must therefore be among the thresholds).  export_fn then hands the chosen
+    threshold's last mask to count_fn, `tracker` becomes that threshold's tracker, the intervals it has closed so far are yielded in
+    order with that batch, and from there on this is a plain ChangeFrameSelector at the chosen threshold.  The intervals and counts are
+    those of ChangeFrameSelector(edge_thresh=the choice) over the whole clip.  How the choice or a window behaves on real footage is not
+    measured here (no real clips).
+
+    cells_fn(frames [n,h,w,3] uint8 | None, area, engine.CellParams, reset, flush, thresholds) -> (totals [nt,gy,gx,4], counts [n,nt,3]);
+    default EngineCellsCounts on the shim's device.  export_fn(area, q, count_fn): count_fn's next call continues from threshold q's
+    last mask; default cells_fn.export.  count_fn: ChangeFrameSelector's; it is never called with reset.  locator_params: AreaLocator's
+    keyword arguments (thresholds, min_edges, change_ratio, min_seconds, max_seconds, plateau_frac, static_frac), the cells' rule.
+    Before the decision `tracker` is None, `trackers` are the candidates' and `pending[q]` the intervals candidate q has closed; after
+    it `edge_thresh`, `scores`, `totals`, `frames_scanned` and `chosen` (the index) say what was decided and on what."""
+
+    def __init__(self, count_fn=None, cells_fn=None, export_fn=None, window=None, locator_params=None, change_ratio=0.5, min_edges=None,
+                 min_frames=2, batch=64):
+        super().__init__(count_fn, None, change_ratio, min_edges, min_frames, batch)
+        from . import area_locator
+        if window is not None and int(window) < 1:
+            raise ValueError(f"CalibratingChangeSelector: window must be at least 1 frame or None, not {window}")
+        self.window = None if window is None else int(window)
+        self.cells_fn, self.export_fn = cells_fn, export_fn
+        self.locator = area_locator.AreaLocator(**{**(locator_params or {}), "edge_thresh": "auto"})
+        if self.locator.automaton != "change":
+            raise ValueError("CalibratingChangeSelector: the calibration in the selector's pass counts with the change automaton, not "
+                             f"automaton={self.locator.automaton!r}")
+        if area_locator.DEFAULT_EDGE_THRESH not in self.locator.thresholds:
+            raise ValueError(f"CalibratingChangeSelector: thresholds {self.locator.thresholds} must contain {area_locator.DEFAULT_EDGE_THRESH}, "
+                             "the threshold used when none scores")
+        self.trackers, self.pending, self.tracker, self.decided = [], [], None, False
+        self.scores = self.totals = self.chosen = None
+        self.frames_scanned = 0
+
+    def iter_run(self, frames, sub_area, fps=None, uploader=None):
+        """ChangeFrameSelector.iter_run; up to the decision every batch is yielded with no closed interval and `tracker` is None."""
+        import logging
+
+        import numpy as np
+        from . import area_locator
+        if self.count_fn is None or self.cells_fn is None:
+            from . import shim
+            self.count_fn = EngineCounter(shim._context()) if self.count_fn is None else self.count_fn
+            self.cells_fn = EngineCellsCounts(shim._context()) if self.cells_fn is None else self.cells_fn
+        export = self.cells_fn.export if self.export_fn is None else self.export_fn
+        loc, ths = self.locator, self.locator.thresholds
+        self.counts, self.intervals, self.tracker, self.decided = np.zeros((0, 3), np.int32), [], None, False
+        self.trackers, self.pending = [], []
+        self.edge_thresh = self.scores = self.totals = self.chosen = None
+        self.frames_scanned = 0
+        bands = band_batches(frames, sub_area, self.batch, type(self).__name__)
+        if bands.area is None:
+            return
+        area, params = bands.area, loc.params(fps)
+        min_edges = default_min_edges(area[1], area[3] - area[2]) if self.min_edges is None else self.min_edges
+        self.trackers = [IntervalTracker(min_edges, self.change_ratio, self.min_frames) for _ in ths]
+        self.pending = [[] for _ in ths]
+        seen, rows = [], []                   # the counts of the window [n,nt,3] and of the frames behind it [n,3], batch by batch
+
+        def host(c, shape):
+            return np.asarray(c.cpu() if hasattr(c, "cpu") else c, np.int32).reshape(shape)
+
+        def decide(scanned):
+            totals, _none = self.cells_fn(None, area, params, False, True, ths)
+            self.totals, self.frames_scanned = host(totals, tuple(totals.shape)), scanned
+            static_frac = loc.locate_kwargs.get("static_frac", 0.95)
+            self.scores = area_locator.edge_thresh_scores(self.totals, scanned, static_frac)
+            k = area_locator.pick_edge_thresh(self.totals, ths, scanned, static_frac, loc.plateau_frac)
+            if k is None:
+                logging.getLogger(area_locator.__name__).warning(
+                    "edge_thresh='auto': none of the thresholds %s scores with the %s automaton in %d frames; falling back to %d", ths,
+                    loc.describe_automaton(), scanned, area_locator.DEFAULT_EDGE_THRESH)
+                k = ths.index(area_locator.DEFAULT_EDGE_THRESH)
+            self.chosen, self.edge_thresh = k, ths[k]
+            export(area, k, self.count_fn)
+            self.tracker, self.intervals, self.decided = self.trackers[k], list(self.pending[k]), True
+            return list(self.pending[k])
+
+        fed = 0
+        with closing(staging.staged_batches(bands, uploader)) as staged:
+            for items, data in staged:
+                n, head, closed = len(items), 0, []
+                if not self.decided:
+                    head = n if self.window is None else min(n, self.window - fed)
+                    _totals, c = self.cells_fn(data if head == n else data[:head], area, params, fed == 0, False, ths)
+                    seen.append(host(c, (-1, len(ths), 3)))
+                    for q, tracker in enumerate(self.trackers):
+                        self.pending[q] += tracker.feed(seen[-1][:, q])
+                    if self.window is not None and fed + head >= self.window:
+                        closed = decide(fed + head)
+                if self.decided and head < n:
+                    rows.append(host(self.count_fn(data[head:] if head else data, area, self.edge_thresh, False), (-1, 3)))
+                    got = self.tracker.feed(rows[-1])
+                    self.intervals += got
+                    closed = closed + got
+                fed += n
+                yield items, closed
+        closed = [] if self.decided else decide(fed)
+        last = self.tracker.flush()
+        self.intervals += last
+        self.counts = np.concatenate([c[:, self.chosen] for c in seen] + rows)
+        yield [], closed + last
 
 
 # ---- held-edge selection (the change selector for footage whose background moves) ------------------------------------------
