@@ -360,6 +360,46 @@ int vse_frame_cells_counts(vse_ctx* ctx, const void* d_bgr, int n, int src_h, in
  * 1..8, q outside 0..nt - 1, a NULL or misaligned pointer. */
 int vse_frame_cells_export_state(vse_ctx* ctx, const void* d_cells_state, int area_h, int area_w, int nt, int q, void* d_change_state,
                                  void* stream);
+/* Replaces: nothing in the reference; it serves a selector that has to FIND its area while the frames go by (a pipe, which cannot be
+ * read twice: vse_amd.frame_select.LocatingChangeSelector).  The counts of vse_frame_change on a rectangle that is not known yet cannot
+ * be summed from the cells (the located rectangle's interior lies one row and one column off the cell grid), but the edge MASK of a
+ * pixel depends on its four neighbours and the threshold only, so the locator's pass keeps its mask words, one bit per pixel and
+ * threshold, and vse_frame_masks_replay counts any rectangle out of them once the area is decided.
+ * vse_frame_masks_bytes: the bytes of a mask buffer of `cap` frame slots for a region of area_h x area_w pixels at nt thresholds,
+ *   cap * nt * gy * gx * 64 (gy, gx: vse_frame_cells_dims); 0 for an area below 3 x 3, nt outside 1..8 or cap < 1.
+ * vse_frame_cells_masks: vse_frame_cells_multi with one more output.  Arguments, checks, d_state (vse_frame_cells_multi_state_bytes;
+ *   it may pass between the two entries in the middle of a clip) and d_totals are that entry's, bit for bit.  d_masks: the caller's
+ *   buffer of `cap` slots, 8-byte aligned; frame i of the call lands in slot slot0 + i (no wrap).  Layout, cell-major, in 64-bit words:
+ *     slot f, threshold q, cell (cy, cx), row k of the cell -> word (((f * nt + q) * gy + cy) * gx + cx) * 8 + k;
+ *     bit b of that word = region-interior pixel (8 cy + k, 64 cx + b) is an edge pixel of that frame at thresholds[q] (the interior
+ *     pixel (iy, ix) is region pixel (1 + iy, 1 + ix)); zero beyond the interior, in rows and in columns.
+ *   Every word of the slots slot0 .. slot0 + n - 1 is written and no other; n == 0 writes none (d_masks may then be NULL).  One launch
+ *   on `stream`, no allocation, no device sync.  Returns VSE_E_INVAL, without touching the device, for everything
+ *   vse_frame_cells_multi refuses, d_masks NULL or misaligned with n > 0, cap < 1, slot0 < 0 or slot0 + n > cap.
+ * vse_frame_masks_replay: slots [f0, f1) of such a buffer at threshold index q, and a rectangle [ry0, ry1) x [rx0, rx1) in REGION
+ *   coordinates (at least 3 x 3, inside the region) ->
+ *     d_counts int32 [f1 - f0, 3]: edges, appeared, vanished, integer for integer what vse_frame_change writes for those frames at
+ *       edge_thresh = thresholds[q] on that rectangle of the frames, fed from frame f0 on;
+ *     d_change_state: a vse_frame_change state of the rectangle (vse_frame_change_state_bytes(ry1 - ry0, rx1 - rx0) bytes, 8-byte
+ *       aligned) holding the mask of slot f1 - 1 as that entry keeps it, every word written, the flag set: vse_frame_change or
+ *       vse_frame_focus on the following frames then give the rows of an uninterrupted run.
+ *   reset != 0: the mask before frame f0 is empty; reset == 0: it is slot f0 - 1's (f0 >= 1), so a long window can be replayed in
+ *   pieces.  The buffer is only read: slots f0 - 1 (without reset) .. f1 - 1, and only words of cells the rectangle touches.  d_counts
+ *   is cleared on `stream` ahead of the kernel (one launch per 65535 frames), whose integer sums do not depend on the order of the
+ *   blocks; no allocation, no device sync.  Returns VSE_E_INVAL, launching nothing, for an area or rectangle below 3 x 3, a rectangle
+ *   outside the region, nt outside 1..8, q outside 0..nt - 1, f0 < 0, f1 <= f0, f1 > cap, reset == 0 with f0 == 0, a NULL or
+ *   misaligned pointer. */
+size_t vse_frame_masks_bytes(int area_h, int area_w, int nt, int cap);
+int vse_frame_cells_masks(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride,
+                          int y0, int y1, int x0, int x1, const int* thresholds /* host, [nt] */, int nt,
+                          int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
+                          void* d_state, int reset, int flush,
+                          int32_t* d_totals /* [nt,gy,gx,4], as vse_frame_cells_multi */,
+                          void* d_masks /* cap slots of vse_frame_masks_bytes(y1 - y0, x1 - x0, nt, 1) bytes */, int cap, int slot0,
+                          void* stream);
+int vse_frame_masks_replay(vse_ctx* ctx, const void* d_masks, int area_h, int area_w, int nt, int cap, int q, int f0, int f1,
+                           int ry0, int ry1, int rx0, int rx1, int reset,
+                           int32_t* d_counts /* [f1 - f0, 3] */, void* d_change_state, void* stream);
 
 /* ---- held-edge frame selector ------------------------------------------------------------------------------------------- */
 /* Replaces: the same frame search of VideoSubFinder as vse_frame_change (backend/main.py:378-505, extract_frame_by_vsf), for

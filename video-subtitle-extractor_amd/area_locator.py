@@ -33,6 +33,13 @@ That calibration also runs inside the change selector's own pass, without a pass
 vse_frame_cells_counts; SubtitleExtractor's area_params={"streaming": True}): the cells of search_area tile the interior of the
 selector's area and their mask is the selector's, so the kernel that keeps these totals also hands back the selector's counts at every
 threshold, and `edge_thresh_scores` / `pick_edge_thresh` below decide on the same integers after the window's last frame.
+The locator itself runs inside the change selector's pass as well (frame_select.LocatingChangeSelector; SubtitleExtractor's
+area_params={"streaming_locate": True} with sub_area="auto"), which is what a pipe needs.  There the identity above fails by one pixel:
+`locate_area` returns ymin = y0 + 1 + 8 (j0 - pad) and xmin = x0 + 1 + 64 (i0 - pad), so the interior of the located rectangle starts one
+row and one column off the whole-frame cell grid (unless the clamp to 0 hits) and ends one short of it, and no sum of the cells' counts
+is vse_frame_change's count on it.  A pixel's edge mask, however, depends on its four neighbours and the threshold only, so the cells'
+kernel keeps its mask words, one bit per pixel and threshold (vse_frame_cells_masks), these totals decide as they always do after the
+window's last frame, and vse_frame_masks_replay counts the located rectangle out of the kept words.
 Known limits: the locator and the calibration run the CHANGE automaton unless `automaton="hold"`.  On a moving textured background
 every frame is a cut in every cell at every threshold, nothing scores, no area is found and "auto" falls back to 128 with a warning.
 How the rule behaves on real footage is unmeasured: there are no real clips here.

@@ -18,6 +18,11 @@
 // Threshold calibration (vse_frame_cells_multi): vse_frame_cells for several edge thresholds in one pass over the frames
 // (frame_cells_multi_kernel below).
 //
+// The locator's masks kept for an area decided later (vse_frame_cells_masks, vse_frame_masks_replay): frame_cells_multi_kernel that also
+// writes the mask words of every frame to the caller's buffer, one bit per pixel and threshold, and a small kernel that counts any
+// rectangle of the region out of those words as frame_change_kernel would have counted it on the frames (frame_cells_masks_kernel and
+// frame_masks_replay_kernel below).
+//
 // Held-edge selector (vse_frame_hold): the same tiles and the same mask again, but only edge pixels that hold still for `hold` frames
 // are counted, so that the edges of a moving background drop out (frame_hold_kernel below).
 //
@@ -456,6 +461,141 @@ __global__ __launch_bounds__(256) void frame_cells_export_kernel(const unsigned 
         words[i] = cell_state[cell * CELL_STATE_WORDS + iy % FC_ROWS];
     }
     if (i == 0) *flag = 1u;
+}
+
+// ---- vse_frame_cells_masks ------------------------------------------------------------------------------------------------------
+// frame_cells_multi_kernel with one more output: the mask words a chunk leaves in LDS are also written to the caller's buffer, so that
+// the counts of ANY rectangle of the region can be made later without the frames (frame_masks_replay_kernel below).  Cell-major: slot f,
+// threshold q, cell c, row k -> word ((f * NT + q) * cells + c) * FC_ROWS + k, which is msk[q][tl][k] of frame f: wave q copies its own
+// slice, lane l of pass p writing word l % 8 of frame 8 p + l / 8 of the chunk, so one store instruction writes eight whole 64-byte
+// lines and the LDS reads of a pass are 64 consecutive words.  Words of rows and columns beyond the interior are zero in LDS
+// (tile_masks_multi) and are written as such.  A block writes only its own cell's words; the launcher has checked slot0 + n <= cap.
+// Everything else is frame_cells_multi_kernel line for line, which keeps its own copy: that kernel is not this one's to change.  No
+// LDS beyond that kernel's ((FC_CHUNK + 1) * NT * FC_ROWS words, 4160 B at NT = 1, 33280 B at NT = 8), no scratch, no atomics; 99 VGPRs
+// at NT = 1, 107 at NT = 8 (the compiler's resource usage for gfx950; frame_cells_multi_kernel<NT> has 92 and 102), 4 waves per SIMD at
+// every NT where that kernel has 5 at NT <= 3: a block is two waves per SIMD, so both hold two blocks on a CU, also at NT = 8 (65 KiB of
+// its 160 KiB LDS).  The store loop is kept rolled: unrolled, its eight addresses cost 127-129 VGPRs and the second block at NT = 5..7.
+// Runs with n == 0 too (reset and flush only; no slot is written).
+template <int NT>
+__global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_masks_kernel(const uint8_t* __restrict__ src, int n, long pitch, long fstride,
+                                                                          int x0, int ih, int iw, CellThresholds th, CellRule rule,
+                                                                          unsigned long long* __restrict__ state, int reset, int flush,
+                                                                          int* __restrict__ totals, unsigned long long* __restrict__ masks,
+                                                                          long slot0) {
+    __shared__ unsigned long long msk[NT * FC_CHUNK * FC_ROWS];           // [NT][FC_CHUNK][FC_ROWS]
+    __shared__ unsigned long long prv[NT * FC_ROWS];
+    static_assert(FC_CHUNK == 64, "the frames of a chunk are the lanes of a wave");
+    static_assert(NT >= 1 && NT <= FC_WAVES, "wave q owns threshold q");
+    static_assert(FC_ROWS == 8, "a lane's word of a store pass is lane % 8 of frame lane / 8");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int iy0 = blockIdx.y * FC_ROWS;
+    const long cell = (long)blockIdx.y * gridDim.x + blockIdx.x, cells = (long)gridDim.y * gridDim.x;
+    const TileLane t = tile_lane(blockIdx.x, iy0, ih, iw, x0);
+    const bool mine = wave < NT;            // wave q owns threshold q
+    unsigned long long* st = state + ((long)wave * cells + cell) * CELL_STATE_WORDS;
+    int* tot = totals + ((long)wave * cells + cell) * 4;
+    unsigned long long* mq = msk + wave * FC_CHUNK * FC_ROWS;
+    unsigned long long* pq = prv + wave * FC_ROWS;
+    if (mine && lane < FC_ROWS) pq[lane] = reset ? 0ull : st[lane];
+    CellRuns cr = {0, 0, 0, 0, 0};
+    if (mine && !reset) cr = {(int)st[FC_ROWS], tot[0], tot[1], tot[2], tot[3]};
+
+    for (int c0 = 0; c0 < n; c0 += FC_CHUNK) {
+        const int cn = min(FC_CHUNK, n - c0);
+        tile_masks_multi<NT>(src + (long)iy0 * pitch, c0, cn, pitch, fstride, t, th, msk);
+        __syncthreads();
+        if (mine) {                                // lane = frame of the chunk
+            // the chunk's words of threshold `wave`: frame c0 + tl < n of the call is slot slot0 + c0 + tl < cap
+            const long slot_words = NT * cells * FC_ROWS;
+            unsigned long long* out = masks + (slot0 + c0 + (lane >> 3)) * slot_words + (wave * cells + cell) * FC_ROWS + (lane & 7);
+#pragma unroll 1
+            for (int i = lane; i < cn * FC_ROWS; i += 64, out += (FC_CHUNK / FC_ROWS) * slot_words) *out = mq[i];
+            const bool live = lane < cn;
+            int e = 0, a = 0, v = 0, ep = 0;
+            if (live) {
+#pragma unroll
+                for (int k = 0; k < FC_ROWS; ++k) {
+                    const unsigned long long cur = mq[lane * FC_ROWS + k], pre = lane ? mq[(lane - 1) * FC_ROWS + k] : pq[k];
+                    e += __popcll(cur);
+                    a += __popcll(cur & ~pre);
+                    v += __popcll(pre & ~cur);
+                    ep += __popcll(pre);           // edges[t-1]
+                }
+            }
+            const long long uni = ep + a;          // |E' or E|
+            const unsigned long long present = __ballot(live && e >= rule.min_edges);
+            const unsigned long long ratio = __ballot(live && uni > 0 && (long long)(a + v) * rule.ratio_den >= (long long)rule.ratio_num * uni);
+            for (int f = 0; f < cn; ++f) cr.step((present >> f) & 1, (ratio >> f) & 1, rule);
+        }
+        __syncthreads();
+        if (mine && lane < FC_ROWS) pq[lane] = mq[(cn - 1) * FC_ROWS + lane];
+        __syncthreads();
+    }
+    if (mine && lane < FC_ROWS) st[lane] = pq[lane];
+    if (mine && lane == 0) {
+        if (flush) cr.close(rule);
+        st[FC_ROWS] = (unsigned long long)cr.run;
+        tot[0] = cr.covered;
+        tot[1] = cr.runs;
+        tot[2] = cr.present;
+        tot[3] = cr.cuts;
+    }
+}
+
+// ---- vse_frame_masks_replay -----------------------------------------------------------------------------------------------------
+// The counts frame_change_kernel would write on a rectangle of the region, from the words frame_cells_masks_kernel kept: an edge pixel
+// depends on its four neighbours and the threshold only, not on the area it is counted in, so interior pixel (iy, ix) of the rectangle
+// [ry0, ry1) x [rx0, rx1) (region coordinates) is interior pixel (ry0 + iy, rx0 + ix) of the region.
+struct ReplayRect {
+    int ry0, rx0;       // the rectangle's first row and column in the region
+    int ih, iw, wpr;    // its interior, and the 64-bit words of an interior row
+};
+
+// Word w of the rectangle's interior row iy in one slot's slice of threshold q (`slice` points at its first cell; gx cells per grid row):
+// two neighbouring region words funnel-shifted by rx0 % 64, the bits at and beyond the interior width cleared.  The upper word is read
+// only where it holds a column of the rectangle's interior, which is inside the region's, so no cell beside the rectangle is touched.
+__device__ __forceinline__ unsigned long long replay_word(const unsigned long long* __restrict__ slice, int gx, const ReplayRect& r, int iy,
+                                                          int w) {
+    const int row = r.ry0 + iy, col = r.rx0 + 64 * w;          // region-interior row, and column of the word's bit 0
+    const int cx = col >> 6, s = col & 63, left = r.iw - 64 * w;          // left >= 1: interior columns from bit 0 on
+    const unsigned long long* p = slice + ((long)(row >> 3) * gx + cx) * FC_ROWS + (row & 7);
+    unsigned long long v = p[0] >> s;
+    if (s && 64 - s < left) v |= p[FC_ROWS] << (64 - s);
+    return left >= 64 ? v : v & ((1ull << left) - 1);
+}
+
+// grid: x over the rectangle's ih * wpr words in blocks of 256, y over the frames f0 .. f1 - 1.  slot_words = nt * cells * FC_ROWS;
+// masks points at slot 0's slice of threshold q.  The previous mask of slot f is slot f - 1, or empty for f == f0 with `reset`.  counts
+// [f1 - f0, 3] were cleared by the launcher; each wave adds its sums, zeros skipped.  The blocks of the last frame also write its words
+// as frame_change_kernel keeps them (words[iy * wpr + w], every one of them) and the flag.
+__global__ __launch_bounds__(256) void frame_masks_replay_kernel(const unsigned long long* __restrict__ masks, long slot_words, int gx,
+                                                                 ReplayRect r, int f0, int f1, int reset, int* __restrict__ counts,
+                                                                 unsigned long long* __restrict__ words, unsigned* flag) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int f = f0 + (int)blockIdx.y;
+    int e = 0, a = 0, v = 0;
+    if (i < (long)r.ih * r.wpr) {
+        const int iy = (int)(i / r.wpr), w = (int)(i % r.wpr);
+        const unsigned long long cur = replay_word(masks + (long)f * slot_words, gx, r, iy, w);
+        const unsigned long long pre = (reset && f == f0) ? 0ull : replay_word(masks + (long)(f - 1) * slot_words, gx, r, iy, w);
+        e = __popcll(cur);
+        a = __popcll(cur & ~pre);
+        v = __popcll(pre & ~cur);
+        if (f == f1 - 1) words[i] = cur;
+    }
+    if (i == 0 && f == f1 - 1) *flag = 1u;
+#pragma unroll
+    for (int d = 32; d; d >>= 1) {
+        e += __shfl_down(e, d);
+        a += __shfl_down(a, d);
+        v += __shfl_down(v, d);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        int* o = counts + (long)(f - f0) * 3;
+        if (e) atomicAdd(o, e);
+        if (a) atomicAdd(o + 1, a);
+        if (v) atomicAdd(o + 2, v);
+    }
 }
 
 // ---- vse_frame_hold -------------------------------------------------------------------------------------------------------------
@@ -900,6 +1040,61 @@ int vse_frame_cells_export_launch(const void* d_cells_state, int area_h, int are
     unsigned long long* words = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(d_change_state) + 16);
     hipLaunchKernelGGL(frame_cells_export_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        slice, ih, wpr, words, flag);
+    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+}
+
+// Called by vse_frame_cells_masks (vse_runtime.hip) after it has checked the arguments as vse_frame_cells_multi does and 0 <= slot0,
+// slot0 + n <= cap of d_masks.
+int vse_frame_cells_masks_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                                 const int* thresholds, int nt, int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
+                                 void* d_state, int reset, int flush, int32_t* d_totals, void* d_masks, int slot0, void* stream) {
+    const int ih = y1 - y0 - 2, iw = x1 - x0 - 2;
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
+    const CellRule rule = {min_edges, ratio_num, ratio_den, min_frames, max_frames};
+    CellThresholds th = {};
+    for (int q = 0; q < nt; ++q) th.t[q] = thresholds[q];
+    const dim3 grid((iw + 63) / 64, (ih + FC_ROWS - 1) / FC_ROWS), block(FC_WAVES * 64);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    unsigned long long* state = reinterpret_cast<unsigned long long*>(d_state);
+    int* totals = reinterpret_cast<int*>(d_totals);
+    unsigned long long* masks = reinterpret_cast<unsigned long long*>(d_masks);
+#define VSE_CELLS_MASKS(NT)                                                                                                              \
+    case NT:                                                                                                                             \
+        hipLaunchKernelGGL(frame_cells_masks_kernel<NT>, grid, block, 0, st, src, n, (long)pitch, (long)frame_stride, x0, ih, iw, th, rule, \
+                           state, reset, flush, totals, masks, (long)slot0);                                                             \
+        break;
+    switch (nt) {
+        VSE_CELLS_MASKS(1) VSE_CELLS_MASKS(2) VSE_CELLS_MASKS(3) VSE_CELLS_MASKS(4)
+        VSE_CELLS_MASKS(5) VSE_CELLS_MASKS(6) VSE_CELLS_MASKS(7) VSE_CELLS_MASKS(8)
+        default: return VSE_E_INVAL;
+    }
+#undef VSE_CELLS_MASKS
+    static_assert(FC_WAVES == 8, "one instantiation per number of thresholds");
+    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+}
+
+// Called by vse_frame_masks_replay (vse_runtime.hip) after it has checked the region, 0 <= q < nt <= vse_frame_cells_multi_max(), the
+// slots 0 <= f0 < f1 <= cap (f0 >= 1 without reset) and the rectangle, at least 3 x 3 and inside the region.  d_counts is cleared on
+// the stream ahead of the kernel, which adds into it.
+int vse_frame_masks_replay_launch(const void* d_masks, int area_h, int area_w, int nt, int q, int f0, int f1, int ry0, int ry1, int rx0,
+                                  int rx1, int reset, int32_t* d_counts, void* d_change_state, void* stream) {
+    const int gy = (area_h - 2 + FC_ROWS - 1) / FC_ROWS, gx = (area_w - 2 + 63) / 64;
+    const long cells = (long)gy * gx;
+    ReplayRect r;
+    r.ry0 = ry0, r.rx0 = rx0, r.ih = ry1 - ry0 - 2, r.iw = rx1 - rx0 - 2, r.wpr = (r.iw + 63) / 64;
+    const long nwords = (long)r.ih * r.wpr;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const unsigned long long* slice = reinterpret_cast<const unsigned long long*>(d_masks) + (long)q * cells * FC_ROWS;
+    unsigned* flag = reinterpret_cast<unsigned*>(d_change_state);
+    unsigned long long* words = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(d_change_state) + 16);
+    if (hipMemsetAsync(d_counts, 0, (size_t)(f1 - f0) * 3 * sizeof(int32_t), st) != hipSuccess) return VSE_E_HIP;
+    // grid.y holds at most 65535 frames: a longer window goes in pieces, each continuing from the slot before it
+    for (int g0 = f0; g0 < f1; g0 += 65535) {
+        const int g1 = min(f1, g0 + 65535);
+        hipLaunchKernelGGL(frame_masks_replay_kernel, dim3((unsigned)((nwords + 255) / 256), (unsigned)(g1 - g0)), dim3(256), 0, st, slice,
+                           (long)nt * cells * FC_ROWS, gx, r, g0, g1, reset && g0 == f0, reinterpret_cast<int*>(d_counts) + (long)(g0 - f0) * 3,
+                           words, flag);
+    }
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
 

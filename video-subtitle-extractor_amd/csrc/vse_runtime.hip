@@ -68,6 +68,11 @@ int vse_frame_cells_counts_launch(const void* d_bgr, int n, int64_t pitch, int64
                                   const int* thresholds, int nt, int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
                                   void* d_state, int reset, int flush, int32_t* d_totals, int32_t* d_counts, void* stream);   // frame_change.hip
 int vse_frame_cells_export_launch(const void* d_cells_state, int area_h, int area_w, int q, void* d_change_state, void* stream);   // frame_change.hip
+int vse_frame_cells_masks_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                                 const int* thresholds, int nt, int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
+                                 void* d_state, int reset, int flush, int32_t* d_totals, void* d_masks, int slot0, void* stream);   // frame_change.hip
+int vse_frame_masks_replay_launch(const void* d_masks, int area_h, int area_w, int nt, int q, int f0, int f1, int ry0, int ry1, int rx0,
+                                  int rx1, int reset, int32_t* d_counts, void* d_change_state, void* stream);   // frame_change.hip
 size_t vse_frame_hold_word_bytes();                                                                                    // frame_change.hip
 int vse_frame_hold_launch(const void* d_bgr, int n, int steps, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
                           int edge_thresh, int hold, int skip, void* d_state, int fresh, int32_t* d_counts, void* stream);   // frame_change.hip
@@ -616,6 +621,68 @@ int vse_frame_cells_export_state(vse_ctx* c, const void* d_cells_state, int area
     }
     const int rc = vse_frame_cells_export_launch(d_cells_state, area_h, area_w, q, d_change_state, stream);
     if (rc != VSE_OK) set_err("vse_frame_cells_export_state: launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+// ---- the locator's masks kept for a rectangle decided later (frame_change.hip) ------------------------------------------------------
+size_t vse_frame_masks_bytes(int area_h, int area_w, int nt, int cap) {
+    int gy, gx;
+    if (nt < 1 || nt > vse_frame_cells_multi_max() || cap < 1 || vse_frame_cells_dims(area_h, area_w, &gy, &gx) != VSE_OK) return 0;
+    return (size_t)cap * nt * gy * gx * 64;
+}
+
+int vse_frame_cells_masks(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0, int y1,
+                          int x0, int x1, const int* thresholds, int nt, int min_edges, int ratio_num, int ratio_den, int min_frames,
+                          int max_frames, void* d_state, int reset, int flush, int32_t* d_totals, void* d_masks, int cap, int slot0,
+                          void* stream) {
+    if (!check_frames("vse_frame_cells_masks", c && d_totals && (d_masks || n <= 0) && !(reinterpret_cast<uintptr_t>(d_masks) & 7), d_bgr, n,
+                      0, src_h, src_w, pitch, frame_stride, d_state) ||
+        !check_area("vse_frame_cells_masks", "region", y0, y1, x0, x1, src_h, src_w) ||
+        !check_rule("vse_frame_cells_masks", ratio_num, ratio_den, min_frames, max_frames))
+        return VSE_E_INVAL;
+    if (!thresholds || nt < 1 || nt > vse_frame_cells_multi_max()) {
+        set_err("vse_frame_cells_masks: %d thresholds (1..%d, not NULL)", nt, vse_frame_cells_multi_max());
+        return VSE_E_INVAL;
+    }
+    for (int q = 0; q < nt; ++q) {
+        if (thresholds[q] < 1 || thresholds[q] > 255 || (q && thresholds[q] <= thresholds[q - 1])) {
+            set_err("vse_frame_cells_masks: threshold %d of %d is %d (each 1..255, ascending and distinct)", q, nt, thresholds[q]);
+            return VSE_E_INVAL;
+        }
+    }
+    if (cap < 1 || slot0 < 0 || (int64_t)slot0 + n > cap) {
+        set_err("vse_frame_cells_masks: %d frames from slot %d on do not fit a mask buffer of %d slots (no wrap)", n, slot0, cap);
+        return VSE_E_INVAL;
+    }
+    if (n == 0 && !reset && !flush) return VSE_OK;
+    const int rc = vse_frame_cells_masks_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, thresholds, nt, min_edges, ratio_num,
+                                                ratio_den, min_frames, max_frames, d_state, reset, flush, d_totals, d_masks, slot0, stream);
+    if (rc != VSE_OK) set_err("vse_frame_cells_masks: launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+int vse_frame_masks_replay(vse_ctx* c, const void* d_masks, int area_h, int area_w, int nt, int cap, int q, int f0, int f1, int ry0,
+                           int ry1, int rx0, int rx1, int reset, int32_t* d_counts, void* d_change_state, void* stream) {
+    if (!c || !d_masks || !d_counts || !d_change_state || area_h < 3 || area_w < 3 || nt < 1 || nt > vse_frame_cells_multi_max() || q < 0 ||
+        q >= nt || ((reinterpret_cast<uintptr_t>(d_masks) | reinterpret_cast<uintptr_t>(d_change_state)) & 7) ||
+        (reinterpret_cast<uintptr_t>(d_counts) & 3)) {
+        set_err("vse_frame_masks_replay: bad arguments (region %d x %d of at least 3 x 3, threshold %d of %d (1..%d), masks and state 8-byte "
+                "aligned, no NULL pointer)", area_h, area_w, q, nt, vse_frame_cells_multi_max());
+        return VSE_E_INVAL;
+    }
+    if (f0 < 0 || f1 <= f0 || f1 > cap || (!reset && f0 == 0)) {
+        set_err("vse_frame_masks_replay: slots [%d, %d) of a buffer of %d (0 <= f0 < f1 <= cap; without reset the mask before f0 is slot "
+                "f0 - 1, so f0 >= 1)", f0, f1, cap);
+        return VSE_E_INVAL;
+    }
+    if (ry0 < 0 || rx0 < 0 || ry1 > area_h || rx1 > area_w || ry1 - ry0 < 3 || rx1 - rx0 < 3) {
+        set_err("vse_frame_masks_replay: rectangle [%d, %d) x [%d, %d) is degenerate or outside the %d x %d region", ry0, ry1, rx0, rx1,
+                area_h, area_w);
+        return VSE_E_INVAL;
+    }
+    const int rc = vse_frame_masks_replay_launch(d_masks, area_h, area_w, nt, q, f0, f1, ry0, ry1, rx0, rx1, reset, d_counts,
+                                                 d_change_state, stream);
+    if (rc != VSE_OK) set_err("vse_frame_masks_replay: launch failed: %s", hipGetErrorString(hipGetLastError()));
     return rc;
 }
 

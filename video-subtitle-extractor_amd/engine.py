@@ -35,6 +35,7 @@ EXPORTS = [
     "vse_yuv_frame_bytes", "vse_yuv_to_bgr_format", "vse_yuv_deinterlace", "vse_yuv_field_match",
     "vse_yuv_tonemap_table_bytes", "vse_yuv_to_bgr_tonemap", "vse_yuv_resample_table_bytes", "vse_yuv_resample",
     "vse_yuv_vscale", "vse_frame_cells_counts", "vse_frame_cells_export_state",
+    "vse_frame_masks_bytes", "vse_frame_cells_masks", "vse_frame_masks_replay",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -56,6 +57,14 @@ class CellsState:
 
     def __init__(self, words, totals):
         self.words, self.totals = words, totals
+
+
+class MasksBuffer:
+    """The mask buffer of vse_frame_cells_masks (include/vse_hip.h): `words`, cuda uint8 of vse_frame_masks_bytes(area_h, area_w, nt, cap),
+    `cap` frame slots of the edge masks of a region of area_h x area_w pixels at nt thresholds, one bit per interior pixel."""
+
+    def __init__(self, words, area_h, area_w, nt, cap):
+        self.words, self.area_h, self.area_w, self.nt, self.cap = words, int(area_h), int(area_w), int(nt), int(cap)
 
 
 class DeviceState:
@@ -194,6 +203,10 @@ def load_library(path=None):
                                           C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.vse_frame_cells_counts.argtypes = lib.vse_frame_cells_multi.argtypes[:-1] + [C.c_void_p, C.c_void_p]
     lib.vse_frame_cells_export_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.vse_frame_masks_bytes.restype = C.c_size_t
+    lib.vse_frame_masks_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.vse_frame_cells_masks.argtypes = lib.vse_frame_cells_multi.argtypes[:-1] + [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.vse_frame_masks_replay.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 12 + [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vse_frame_hold_state_bytes.restype = C.c_size_t
     lib.vse_frame_hold_state_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.vse_frame_hold.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
@@ -676,6 +689,56 @@ class Context:
                                                      C.c_void_p(out.data_ptr()) if out is not None else None, self.stream()),
                "vse_frame_cells_export_state")
         return out
+
+    # ---- the locator's masks, kept for a rectangle decided later ------------------------------------------------------
+    def frame_masks_buffer(self, area_h, area_w, nt, cap):
+        """A MasksBuffer of `cap` frame slots for frame_cells_masks over a region of area_h x area_w pixels with nt thresholds.  It is
+        not cleared: frame_cells_masks writes every word of the slots it fills, and frame_masks_replay reads only filled slots."""
+        nbytes = self.lib.vse_frame_masks_bytes(int(area_h), int(area_w), int(nt), int(cap))
+        if not nbytes:
+            raise VseError(f"frame_masks_buffer: a region of {area_h} x {area_w} pixels, {nt} thresholds (1..8), {cap} slots (at least 1)")
+        return MasksBuffer(self.torch.empty(nbytes, dtype=self.torch.uint8, device=self.tdev), area_h, area_w, nt, cap)
+
+    def frame_cells_masks(self, frames_u8, area, thresholds, params, state, masks, slot0, reset=False, flush=False):
+        """frame_cells_multi that also keeps the masks: every argument as there, and the state is that call's (frame_cells_multi_state;
+        it may pass between the two); masks: frame_masks_buffer of the area's size and len(thresholds), whose slots slot0 .. slot0 + n - 1
+        take the n frames -> state.totals (include/vse_hip.h vse_frame_cells_masks)."""
+        frames = self._frames_args(frames_u8, allow_empty=True)
+        y0, y1, x0, x1 = (int(v) for v in area)
+        th = [int(v) for v in thresholds]
+        nt = len(th)
+        gy, gx = self.frame_cells_dims(y1 - y0, x1 - x0)
+        nbytes = self.lib.vse_frame_cells_multi_state_bytes(y1 - y0, x1 - x0, nt)
+        assert nbytes and state.words.numel() >= nbytes and tuple(state.totals.shape) == (nt, gy, gx, 4)
+        assert (masks.area_h, masks.area_w, masks.nt) == (y1 - y0, x1 - x0, nt)
+        assert masks.words.numel() >= self.lib.vse_frame_masks_bytes(masks.area_h, masks.area_w, nt, masks.cap)
+        p = CellParams(*(int(v) for v in params))
+        _check(self.lib.vse_frame_cells_masks(self.handle, *frames, y0, y1, x0, x1, (C.c_int * nt)(*th), nt, p.min_edges, p.ratio_num,
+                                              p.ratio_den, p.min_frames, p.max_frames, C.c_void_p(state.words.data_ptr()),
+                                              int(bool(reset)), int(bool(flush)), C.c_void_p(state.totals.data_ptr()),
+                                              C.c_void_p(masks.words.data_ptr()), masks.cap, int(slot0), self.stream()),
+               "vse_frame_cells_masks")
+        return state.totals
+
+    def frame_masks_replay(self, masks, q, f0, f1, rect, reset=True, out=None):
+        """Slots [f0, f1) of a MasksBuffer at threshold index q, counted on rect = (ry0, ry1, rx0, rx1) in the region's pixels ->
+        (cuda int32 [f1 - f0, 3], change_state): frame_change's edges / appeared / vanished of those frames on that rectangle, and a
+        frame_change state of the rectangle (`out`, or a new one) holding slot f1 - 1's mask, so that frame_change / frame_focus
+        continue the clip.  reset: nothing precedes slot f0; else slot f0 - 1 does (include/vse_hip.h vse_frame_masks_replay)."""
+        t = self.torch
+        ry0, ry1, rx0, rx1 = (int(v) for v in rect)
+        nbytes = self.lib.vse_frame_change_state_bytes(ry1 - ry0, rx1 - rx0)
+        if out is None and nbytes:
+            out = t.zeros(nbytes, dtype=t.uint8, device=self.tdev)
+        assert out is None or (out.dtype == t.uint8 and out.is_contiguous() and out.numel() >= nbytes)
+        assert masks.words.numel() >= self.lib.vse_frame_masks_bytes(masks.area_h, masks.area_w, masks.nt, masks.cap)
+        counts = t.empty((max(0, int(f1) - int(f0)), 3), dtype=t.int32, device=self.tdev)
+        _check(self.lib.vse_frame_masks_replay(self.handle, C.c_void_p(masks.words.data_ptr()), masks.area_h, masks.area_w, masks.nt,
+                                               masks.cap, int(q), int(f0), int(f1), ry0, ry1, rx0, rx1, int(bool(reset)),
+                                               C.c_void_p(counts.data_ptr()) if counts.numel() else None,
+                                               C.c_void_p(out.data_ptr()) if out is not None else None, self.stream()),
+               "vse_frame_masks_replay")
+        return counts, out
 
     # ---- held-edge frame selector ---------------------------------------------------------------------------------
     def frame_hold_state(self, area_h, area_w, hold):

@@ -21,6 +21,7 @@ a pipe from any decoder) is sequential: SubtitleExtractor then works in one pass
 Command line: python -m vse_amd.extractor VIDEO|- [-o OUT.srt]   (main below).
 """
 import argparse
+import itertools
 import logging
 import re
 import sys
@@ -92,6 +93,13 @@ class RetainedSource:
     def read(self, frame_no):
         f = self._frames.get(frame_no)
         return f.to_bgr() if hasattr(f, "to_bgr") else f
+
+
+def _drain(frames):
+    """The frames of a list, front to back, each let go of as it is handed out."""
+    frames.reverse()
+    while frames:
+        yield frames.pop()
 
 
 def _frame_nbytes(frame):
@@ -327,6 +335,25 @@ class SubtitleExtractor:
     by name: frame_selector other than "change", automaton="hold" / max_hold_* in area_params, sub_area="auto" or None, mode="accurate",
     interval_frame="sharpest", composite_params' streaming, shard, probe; the key without edge_thresh="auto", and the other three keys
     without the key, mean nothing and are refused too.
+    area_params={"streaming_locate": True} with sub_area="auto", frame_selector="change" and mode "fast" or "auto": the area is found in the
+    selector's own pass instead of the locator's (frame_select.LocatingChangeSelector: the located rectangle lies a pixel off the locator's
+    cell grid, so the cells' counts cannot be summed for it; instead the locator's kernel keeps its edge masks, one bit per pixel and
+    threshold, vse_frame_cells_masks, and once the area is decided vse_frame_masks_replay counts it out of them, integer for integer
+    vse_frame_change's rows), which saves a decode and an upload in several passes and is what makes sub_area="auto" work in one pass (a
+    pipe).  change_params' edge_thresh may be an integer or "auto", which is then decided in the same pass and needs no "streaming" key;
+    the two keys together are refused.  `locate_seconds`: S decides after round(S * fps) frames, None (several passes only) after the
+    whole clip; located area, threshold, intervals, recognised frames, raw_lines and SRT are those of the run without the key whose
+    area_params say probe=(1, that many frames).  In one pass S must be given: any frame of the window may become a middle frame, so all of
+    them are kept until the decision, and a window whose frames exceed `retain_bytes` is a ValueError as soon as the frame size is
+    known (nothing is clamped silently inside the window; after the decision the rule below applies).  `mask_gib` (default 8: a policy,
+    not a measurement; 33140 frames of 1080p at one threshold, 4142 at eight) bounds the masks on the device the same way.  No area found:
+    the warning above, and the run continues without one, in one pass over the frames kept, in order, and the rest of the source.  The
+    command line takes for a pipe the largest whole number of seconds up to 300 that fits both bounds: a policy, not a measurement.
+    `streaming_locate`, `locate_seconds`, `mask_gib`, `cells_masks_fn` and `replay_fn` (the selector's callables; default the GPU's) are
+    this class's own; `frames_located` says how many frames the area rests on.  Refused with the key, by name: frame_selector other than
+    "change", automaton="hold" / max_hold_* / search_area / probe in area_params, area_params' streaming, interval_frame="sharpest",
+    composite_params' streaming, shard, mode="accurate", a sub_area that is not "auto"; the other keys without the key mean nothing and are
+    refused too.
     one_pass (None: exactly when the source has no `read`, e.g. ingest.Y4mStream over a pipe; True forces it on a seekable source and
     halves its decode work; False on a sequential source is a ValueError): the clip is read once, in decode order.  frame_selector="fps":
     frame `no` is a task iff (no - 1) % max(1, int(fps // extract_frequency)) == 0 (fps_tasks' rule without the frame count); tasks go
@@ -340,7 +367,7 @@ class SubtitleExtractor:
     SRT times, are untouched; `clamped_intervals` counts them and one warning is logged per run.  Where no interval was clamped, the
     intervals, the frames recognised, raw_lines and the SRT equal those of the multi-pass run() on the same frames with the same
     arguments (recognition does not depend on how frames are grouped into batches: tests/test_gpu_ragged.py).  Refused in one pass,
-    because they need a second look at frames already gone: sub_area="auto", mode="accurate" with an area, interval_image other than
+    because they need a second look at frames already gone: sub_area="auto" (unless area_params says "streaming_locate"), mode="accurate" with an area, interval_image other than
     "middle" (unless composite_params says "streaming": min / max / mean and the quantile), interval_text="fused", shard, change_params' edge_thresh="auto" (unless area_params says "streaming").
     interval_frame="sharpest" (change / hold selector with interval_image="middle" and interval_text="single" only; default "middle", all
     of the above): the one frame an interval is recognised on is chosen instead of being the middle one, which in compressed video is as
@@ -430,6 +457,16 @@ class SubtitleExtractor:
                 raise ValueError(f"area_params: {own} belong to area_params={{'streaming': True}} and mean nothing without it")
         self.calibrate_seconds = area_params.pop("calibrate_seconds", None) if self.calibrating else None
         self._calibrate_fns = (area_params.pop("cells_counts_fn", None), area_params.pop("export_fn", None)) if self.calibrating else None
+        # area_params={"streaming_locate": True}: sub_area="auto" is found in the selector's own pass (frame_select.LocatingChangeSelector).
+        # Its keys, `streaming_locate`, `locate_seconds`, `mask_gib`, `cells_masks_fn` and `replay_fn`, are taken out here as well.
+        self.locating = bool(area_params.pop("streaming_locate", False)) if area_params else False
+        if not self.locating:
+            own = sorted(set(area_params or {}) & {"locate_seconds", "mask_gib", "cells_masks_fn", "replay_fn"})
+            if own:
+                raise ValueError(f"area_params: {own} belong to area_params={{'streaming_locate': True}} and mean nothing without it")
+        self.locate_seconds = area_params.pop("locate_seconds", None) if self.locating else None
+        self.mask_gib = area_params.pop("mask_gib", 8) if self.locating else None
+        self._locate_fns = (area_params.pop("cells_masks_fn", None), area_params.pop("replay_fn", None)) if self.locating else None
         self.auto_area, self.area_params, self.located_area = isinstance(sub_area, str) and sub_area == "auto", area_params, None
         self.sub_area, self.mode, self.language = None if self.auto_area else sub_area, mode, language
         self.extract_frequency, self.default_subtitle_area = extract_frequency, default_subtitle_area
@@ -461,6 +498,32 @@ class SubtitleExtractor:
         self.clamped_quantiles = 0        # streaming quantile: intervals that reached back beyond the ring (StreamingQuantile.clamped)
         if not self.one_pass and not hasattr(source, "read"):
             raise ValueError("one_pass=False needs a source with read(frame_no): this one is sequential and its frames cannot be looked at a second time")
+        self.frames_located = 0           # area_params' streaming_locate: the frames the located area rests on
+        if self.locating:
+            option = "area_params={'streaming_locate': True}"
+            held = sorted(set(self.area_params) & {"max_hold_seconds", "max_hold_frames"})
+            refused = [(f"frame_selector={frame_selector!r}", frame_selector != "change"),
+                       (f"automaton={self.area_params.get('automaton')!r}", self.area_params.get("automaton", "change") != "change"),
+                       (f"{held[0] if held else 'max_hold_seconds'} in area_params", bool(held)),
+                       ("search_area in area_params", "search_area" in self.area_params),
+                       ("probe in area_params (locate_seconds says how many frames decide)", "probe" in self.area_params),
+                       ("area_params={'streaming': True}", self.calibrating),
+                       (f"interval_frame={interval_frame!r}", interval_frame != "middle"),
+                       ("composite_params={'streaming': True}", self.streaming), (f"shard={shard!r}", shard is not None),
+                       (f"mode={mode!r}", mode not in ("fast", "auto")),
+                       (f"sub_area={sub_area!r} (the key finds the area of sub_area='auto' and means nothing with another)", not self.auto_area)]
+            for what, hit in refused:
+                if hit:
+                    raise ValueError(f"{option} finds the area of sub_area='auto' for frame_selector='change' while that selector runs, with "
+                                     f"the change automaton on whole frames; it does not combine with {what}, which needs the area from the "
+                                     "first frame or has a pass of its own")
+            if self.locate_seconds is not None and not self.locate_seconds > 0:
+                raise ValueError(f"{option}: locate_seconds must be positive, not {self.locate_seconds!r}")
+            if not self.mask_gib > 0:
+                raise ValueError(f"{option}: mask_gib must be positive, not {self.mask_gib!r}")
+            if self.one_pass and self.locate_seconds is None:
+                raise ValueError(f"{option} in one pass needs locate_seconds: every frame of the window is kept until the area is decided, "
+                                 "and the window bounds that (the command line takes what fits retain_bytes and mask_gib, at most 300, for a pipe)")
         if self.calibrating:
             option = "area_params={'streaming': True}"
             if not self.auto_thresh:
@@ -486,10 +549,11 @@ class SubtitleExtractor:
                 raise ValueError(f"{option} in one pass needs calibrate_seconds: the window bounds the frames kept while eight thresholds "
                                  "are undecided (the command line takes 300 for a pipe)")
         if self.one_pass:
-            refused = [("sub_area='auto'", self.auto_area), ("mode='accurate' with a subtitle area", mode == "accurate" and sub_area is not None),
+            refused = [("sub_area='auto'", self.auto_area and not self.locating),
+                       ("mode='accurate' with a subtitle area", mode == "accurate" and sub_area is not None),
                        (f"interval_image={interval_image!r}", interval_image != "middle" and not self.streaming),
                        (f"interval_text={interval_text!r}", interval_text != "single"), (f"shard={shard!r}", shard is not None),
-                       ("edge_thresh='auto'", self.auto_thresh and not self.calibrating)]
+                       ("edge_thresh='auto'", self.auto_thresh and not self.calibrating and not self.locating)]
             for what, hit in refused:
                 if hit:
                     raise ValueError(f"{what} is not available in one pass (a sequential source, or one_pass=True): it needs a second look "
@@ -553,6 +617,53 @@ class SubtitleExtractor:
         self.edge_thresh = area_locator.DEFAULT_EDGE_THRESH if sel.edge_thresh is None else sel.edge_thresh
         self.edge_scores, self.frames_calibrated = sel.scores, sel.frames_scanned
 
+    def _locate_window(self, first):
+        """area_params' streaming_locate: the frames that decide, checked against what keeps them, as soon as the first frame says how
+        large a frame is: the device mask buffer (mask_gib) and, in one pass, the frames themselves (retain_bytes)."""
+        from . import area_locator
+        fps = self.source.fps
+        if self.locate_seconds is None:
+            window = max(1, int(self.source.frame_count))
+        else:
+            window = int(round(self.locate_seconds * fps))
+            if window < 1:
+                raise ValueError(f"area_params: locate_seconds={self.locate_seconds!r} is less than one frame at {fps} fps")
+        if first is None:
+            return window
+        h, w = first.shape[:2]
+        if h >= 3 and w >= 3:
+            gy, gx = area_locator.cells_dims(h, w)
+            nt = len(self.area_params.get("thresholds", area_locator.AUTO_THRESHOLDS)) if self.auto_thresh else 1
+            need, bound = window * nt * gy * gx * 64, int(self.mask_gib * (1 << 30))
+            if need > bound:
+                raise ValueError(f"area_params={{'streaming_locate': True}}: the masks of a window of {window} frames of {h} x {w} pixels at "
+                                 f"{nt} threshold{'s' if nt > 1 else ''} take {need} bytes on the device, more than mask_gib={self.mask_gib} "
+                                 f"({bound} bytes): give a shorter locate_seconds or a larger mask_gib / --mask-gib")
+        if self.one_pass:
+            need = window * _frame_nbytes(first)
+            if need > self.retain_bytes:
+                raise ValueError(f"area_params={{'streaming_locate': True}}: one pass keeps every frame of the window until the area is decided, "
+                                 f"and {window} frames of {_frame_nbytes(first)} bytes are {need} bytes, more than retain_bytes={self.retain_bytes}: "
+                                 "give a shorter locate_seconds or a larger retain_bytes / --retain-gib")
+        return window
+
+    def _keep_location(self, sel):
+        """area_params' streaming_locate: what the selector decided in its own pass (AreaLocator's results by another road)."""
+        from . import area_locator
+        self.sub_area = self.located_area = sel.area
+        if self.auto_thresh:
+            self.edge_thresh = area_locator.DEFAULT_EDGE_THRESH if sel.edge_thresh is None else sel.edge_thresh
+            self.edge_scores = sel.scores
+        self.frames_located = sel.frames_scanned
+        if sel.area is None:
+            logging.getLogger(__name__).warning("sub_area='auto': no subtitle area found in %d frames; continuing without one "
+                                                "(fps sampler, scene-text filtering)", sel.frames_scanned)
+
+    def _locating_selector(self, window):
+        return frame_select.LocatingChangeSelector(self.change_counter, *self._locate_fns, window=window, batch=self.batch,
+                                                   locator_params={k: v for k, v in self.area_params.items() if k not in ("cells_fn", "batch")},
+                                                   **(self.change_params or {}))
+
     def _change_params(self):
         """The selector's keyword arguments, edge_thresh="auto" resolved to the integer."""
         if not self.auto_thresh:
@@ -593,6 +704,18 @@ class SubtitleExtractor:
                                                      detect_stream=self.detect_stream,
                                                      predict_with_dets=getattr(self.ocr, "predict_with_dets", None))
             return [(t[0], t[1], t[2], t[3], None, None) for t in sel.run(self._decode_order(up), uploader=up)]
+        if self.locating and self.sub_area is None and self.located_area is None:
+            # the locator's pass folded into the selector's: one decode, and the area is known after the window
+            up = self._uploader()
+            frames = iter(self._decode_order(up))
+            first = next(frames, None)
+            sel = self._locating_selector(self._locate_window(first))
+            intervals = sel.run(frames if first is None else itertools.chain([first], frames), None, s.fps, uploader=up)
+            self._keep_location(sel)
+            if sel.area is None:
+                return fps_tasks(s.frame_count, s.fps, self.extract_frequency, self.default_subtitle_area)
+            self.intervals = intervals
+            return [(s.frame_count, rep, None, None, None, self.default_subtitle_area) for _start, _end, rep in self.intervals]
         if self._selects_intervals():
             up = self._uploader()
             sel = self._interval_selector()
@@ -664,7 +787,18 @@ class SubtitleExtractor:
         return lines
 
     def _one_pass_intervals(self, frames, uploader):
-        sel = self._interval_selector()
+        if self.locating:
+            # the area is found in this pass: until it is decided every frame of the window is kept, any of them may become a middle frame
+            self.sub_area = self.located_area = None
+            self.frames_located = 0
+            frames = iter(frames)
+            first = next(frames, None)
+            sel = self._locating_selector(self._locate_window(first))
+            if first is not None:
+                frames = itertools.chain([first], frames)
+            del first
+        else:
+            sel = self._interval_selector()
         batches = sel.iter_run(frames, self.sub_area, self.source.fps, uploader=uploader)
         # the recogniser's batches are staged while the selector's producer thread stages the next bands: a slab ring of their own
         ocr_up = uploader.sibling() if uploader is not None else None
@@ -701,6 +835,11 @@ class SubtitleExtractor:
                     kept[no] = full
                     nbytes += _frame_nbytes(full)
                 self.peak_retained = max(self.peak_retained, len(kept))
+                if self.locating:
+                    if sel.decided and self.frames_located == 0:
+                        self._keep_location(sel)
+                    if sel.area is None:                 # undecided, or decided that there is none: nothing closes, everything stays
+                        continue
                 for start, end, rep in closed:
                     if sharpest:
                         rep = frame_select.sharpest_rep(start, end, sel.focus, self.source.fps, self._trim_seconds())
@@ -756,6 +895,14 @@ class SubtitleExtractor:
                         nbytes -= _frame_nbytes(kept.pop(k))
                         if nbytes <= self.retain_bytes:
                             break
+            if self.locating and self.frames_located == 0:
+                self._keep_location(sel)               # (a clip that ended inside the window decides behind its last batch)
+            if self.locating and sel.area is None:
+                # no area: the run continues as it does without one, over the frames kept, in order, and the rest of the source
+                self.intervals = None
+                batches.close()
+                held = [kept.pop(k) for k in sorted(kept)]
+                return self._one_pass_fps(itertools.chain(_drain(held), frames), uploader)
             if queue:
                 lines += recognise(queue)
             if keep_patches:
@@ -775,7 +922,7 @@ class SubtitleExtractor:
         self.clamped_intervals = self.peak_retained = 0
         up = self._uploader()
         frames = self._decode_order(up)
-        if self._selects_intervals():
+        if self._selects_intervals() or self.locating:
             return self._one_pass_intervals(frames, up)
         return self._one_pass_fps(frames, up)
 
@@ -805,7 +952,10 @@ class SubtitleExtractor:
     def _run_multi_pass(self):
         if self.auto_thresh:
             self.edge_thresh = None
-        if self.auto_area:
+        if self.auto_area and self.locating:
+            self.sub_area = self.located_area = None          # select_tasks finds it
+            self.frames_located = 0
+        elif self.auto_area:
             self.locate_area()
         elif self.auto_thresh and self._selects_intervals() and not self.calibrating:
             self.calibrate_edge_thresh()
@@ -916,15 +1066,36 @@ def square_arguments(args):
     return out
 
 
+def default_locate_seconds(source, raw, auto_thresh, retain_bytes, mask_gib, limit=300):
+    """--streaming-locate on a pipe without --locate-seconds: the largest whole number of seconds, at most `limit`, whose frames fit
+    retain_bytes on the host (`raw`: kept as the stream's own YUV bytes, else as BGR) and whose masks fit mask_gib on the device.  A
+    policy, not a measurement: nobody has tried whether that much of a real film finds its band."""
+    from . import area_locator
+    h, w = int(source.height), int(source.width)
+    if getattr(source, "resample", None) is not None and not raw:
+        w = source.resample.out_width
+    fmt = getattr(source, "fmt", None)
+    per = 3 * h * w if not raw else (h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2) if fmt is None else fmt.frame_bytes(h, w))
+    if raw and getattr(source, "deinterlace", None) is not None:
+        per *= 2                          # (an interlaced frame pins its previous picture)
+    gy, gx = area_locator.cells_dims(max(3, h), max(3, w))
+    frames = min(retain_bytes // per, int(mask_gib * (1 << 30)) // ((len(area_locator.AUTO_THRESHOLDS) if auto_thresh else 1) * gy * gx * 64))
+    seconds = min(int(limit), int(frames / source.fps))
+    if seconds < 1:
+        raise ValueError(f"--streaming-locate: not one second of {h} x {w} frames at {source.fps} fps fits --retain-gib and --mask-gib")
+    return float(seconds)
+
+
 def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, focus_fn=None, stream_fn=None, ring_fn=None,
-         cells_counts_fn=None, export_fn=None):
+         cells_counts_fn=None, export_fn=None, cells_masks_fn=None, replay_fn=None):
     """ocr: the recogniser (None: shim.OcrRecogniser on the GPU, frames staged through staging.default_uploader, YUV 4:2:0 converted
     on the device); counter: the change / hold selector's count_fn (None: the GPU's); cells_fn: the locator's (None: the GPU's);
     composite_fn: what makes the picture of `--interval-image`, the compositor's accumulate_fn for min / max / mean and the quantile's
     rank_fn for quantile (None: the GPU's); focus_fn: what scores the frames of `--interval-frame sharpest` (None: the GPU's);
     stream_fn: what makes the min / max / mean pictures of `--streaming-composite`, StreamingCompositor's stream_fn (None: the GPU's);
     ring_fn: what makes its quantile pictures, StreamingQuantile's ring_fn (None: the GPU's); cells_counts_fn, export_fn: what counts
-    and hands over for `--streaming-calibration`, CalibratingChangeSelector's cells_fn and export_fn (None: the GPU's)."""
+    and hands over for `--streaming-calibration`, CalibratingChangeSelector's cells_fn and export_fn (None: the GPU's); cells_masks_fn,
+    replay_fn: what keeps and replays the masks for `--streaming-locate`, LocatingChangeSelector's cells_fn and replay_fn (None: the GPU's)."""
     p = argparse.ArgumentParser(prog="python -m vse_amd.extractor", description="Extract a video's hard subtitles to SRT on the GPU.  "
                                 "`-` reads YUV4MPEG2 from standard input in one pass, e.g. "
                                 "`ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m vse_amd.extractor - -o film.srt`.")
@@ -971,6 +1142,14 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
     p.add_argument("--calibrate-seconds", type=float, default=None, metavar="S", help="--streaming-calibration: the threshold is chosen "
                    "on the first S seconds; until then one pass keeps the frames any of the eight candidate thresholds may want [a file: "
                    "the whole clip; `-`: 300, a policy, not a measurement: nobody has tried it on real films]")
+    p.add_argument("--streaming-locate", action="store_true", help="--area auto --selector change: find the area in the selector's own pass "
+                   "instead of a pass of its own, which also works in one pass (a pipe); --edge-thresh auto is chosen in that pass too")
+    p.add_argument("--locate-seconds", type=float, default=None, metavar="S", help="--streaming-locate: the area is found on the first S "
+                   "seconds; until then one pass keeps every frame and the device one bit per pixel and threshold [a file: the whole "
+                   "clip; `-`: the largest whole number of seconds up to 300 whose frames fit --retain-gib and --mask-gib, about 57 for "
+                   "1080p 4:2:0 at 24 fps, a policy, not a measurement: nobody has tried whether a minute of a real film finds its band]")
+    p.add_argument("--mask-gib", type=float, default=None, metavar="G", help="--streaming-locate: bound on the masks kept on the device "
+                   "until the area is found, GiB [8, a policy, not a measurement]")
     p.add_argument("--max-hold-seconds", type=float, default=None, metavar="S", help="--selector hold: count only edges that hold still for "
                    "at most S seconds, so a static busy background, a logo or a watermark drops out; a subtitle shown for longer drops out "
                    "too, and one pass keeps S seconds more of frames [none: no bound]")
@@ -1031,6 +1210,9 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
                            **({} if export_fn is None else {"export_fn": export_fn})}
         elif args.calibrate_seconds is not None:
             raise ValueError("--calibrate-seconds sets the window of --streaming-calibration and means nothing without it")
+        if not args.streaming_locate and (args.locate_seconds is not None or args.mask_gib is not None):
+            raise ValueError("--locate-seconds and --mask-gib set the window and the device bound of --streaming-locate and mean nothing "
+                             "without it")
         ring = args.streaming_composite and args.interval_image == "quantile"
         if args.streaming_composite and not ring and args.interval_image not in frame_select.COMPOSITE_MODES:
             raise ValueError(f"--streaming-composite makes the picture of `--interval-image min`, `max` or `mean`, not of "
@@ -1070,13 +1252,24 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
                 shim.config.allow_standin_weights = True
             shim.config.language, shim.config.mode = args.language, args.mode
             ocr, uploader = shim.OcrRecogniser(), staging.default_uploader()
+        location = {}
+        if args.streaming_locate:
+            locate_seconds, mask_gib = args.locate_seconds, 8.0 if args.mask_gib is None else args.mask_gib
+            if locate_seconds is None and args.video == "-" and area == "auto" and mask_gib > 0:
+                locate_seconds = default_locate_seconds(source, uploader is not None and hasattr(source, "raw_frames"), edge_thresh == "auto",
+                                                        int(args.retain_gib * (1 << 30)), mask_gib)
+                logging.getLogger(__name__).info("--streaming-locate: the area is found on the first %d seconds (what fits --retain-gib "
+                                                 "%g and --mask-gib %g, at most 300)", int(locate_seconds), args.retain_gib, mask_gib)
+            location = {"streaming_locate": True, "mask_gib": mask_gib, **({} if locate_seconds is None else {"locate_seconds": locate_seconds}),
+                        **({} if cells_masks_fn is None else {"cells_masks_fn": cells_masks_fn}),
+                        **({} if replay_fn is None else {"replay_fn": replay_fn})}
         ex = SubtitleExtractor(source, ocr, sub_area=area, mode=args.mode, language=args.language, extract_frequency=args.frequency,
                                batch=args.batch, uploader=uploader, frame_selector=args.selector, change_counter=counter,
                                retain_bytes=int(args.retain_gib * (1 << 30)), interval_image=args.interval_image,
                                composite_params=composite_params, interval_frame=args.interval_frame,
                                frame_params=None if focus_fn is None else {"focus_fn": focus_fn},
                                change_params=change_params or None,
-                               area_params={**calibration, **({} if cells_fn is None else {"cells_fn": cells_fn}),
+                               area_params={**calibration, **location, **({} if cells_fn is None else {"cells_fn": cells_fn}),
                                             **({} if args.locator_automaton == "change" else {"automaton": args.locator_automaton}),
                                             **({} if args.locator_max_hold_seconds is None
                                                else {"max_hold_seconds": args.locator_max_hold_seconds})} or None)

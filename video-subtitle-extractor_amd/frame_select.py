@@ -19,7 +19,8 @@ one run / iter_run body of ChangeFrameSelector and HoldFrameSelector; and the En
 vse_frame_focus) also scores every frame in the same pass, and `sharpest_rep` picks an interval's frame by that score.  A selector given
 a `compositor` (StreamingCompositor, vse_interval_stream) also makes each interval's min / max / mean picture in that pass, or
 (StreamingQuantile, vse_interval_ring_rank) its quantile picture.  CalibratingChangeSelector (vse_frame_cells_counts) is the change
-selector that chooses its edge threshold per clip in that same pass.
+selector that chooses its edge threshold per clip in that same pass, and LocatingChangeSelector (vse_frame_cells_masks,
+vse_frame_masks_replay) the one that finds its area there.
 """
 from collections import deque
 from contextlib import closing
@@ -550,6 +551,169 @@ class CalibratingChangeSelector(_IntervalSelector):
         last = self.tracker.flush()
         self.intervals += last
         self.counts = np.concatenate([c[:, self.chosen] for c in seen] + rows)
+        yield [], closed + last
+
+
+# ---- the change selector that finds its own area while the frames go by -------------------------------------------------------------
+class EngineCellsMasks(DeviceState):
+    """cells_fn of LocatingChangeSelector on the GPU (Context.frame_cells_masks), beside area_locator.EngineCells: keeps the device state
+    and the mask buffer of the last region, threshold count and `cap`, and `fed`, the frames fed since the last reset, which is the slot
+    the next frame takes; (frames | None, area, engine.CellParams, reset, flush, thresholds, cap) -> totals [nt,gy,gx,4], frames None with
+    flush closing the open runs.  `replay(area, q, rect, counter)` counts the slots 0 .. fed - 1 at threshold index q on `rect` (y0, y1,
+    x0, x1 in the region's pixels) at once (Context.frame_masks_replay) -> counts [fed,3], and makes the result state the state of an
+    EngineCounter, whose next call then continues the clip on that rectangle."""
+
+    def __init__(self, ctx):
+        super().__init__(ctx)
+        self.fed, self._masks = 0, None
+
+    def __call__(self, frames, area, params, reset, flush, thresholds, cap):
+        t = self.ctx.torch
+        y0, y1, x0, x1 = area
+        frames = t.empty((0, y1, x1, 3), dtype=t.uint8, device=self.ctx.tdev) if frames is None else self._device(frames)
+        if self._fresh((y1 - y0, x1 - x0, len(thresholds), int(cap)), lambda h, w, nt, _cap: self.ctx.frame_cells_multi_state(h, w, nt)):
+            self._masks, reset = self.ctx.frame_masks_buffer(y1 - y0, x1 - x0, len(thresholds), cap), True
+        if reset:
+            self.fed = 0
+        totals = self.ctx.frame_cells_masks(frames, area, thresholds, params, self._state, self._masks, self.fed, reset, flush)
+        self.fed += len(frames)
+        return totals
+
+    def replay(self, area, q, rect, counter):
+        y0, y1, x0, x1 = area
+        if self._key is None or self._key[:2] != (y1 - y0, x1 - x0) or not self.fed:
+            raise ValueError(f"EngineCellsMasks: no masks of a {y1 - y0} x {x1 - x0} region to replay")
+        ry0, ry1, rx0, rx1 = rect
+        counter._fresh((ry1 - ry0, rx1 - rx0), self.ctx.frame_change_state)
+        counts, _state = self.ctx.frame_masks_replay(self._masks, q, 0, self.fed, rect, True, out=counter._state)
+        return counts
+
+
+class LocatingChangeSelector(_IntervalSelector):
+    """ChangeFrameSelector with sub_area="auto", in ONE pass over the frames: what area_locator.AreaLocator(probe=(1, window)) decides in
+    a pass of its own is decided here while the selector runs, so a pipe, which cannot be read twice, gets its area, and a file is
+    decoded once less.  The located rectangle's interior lies a row and a column off the locator's cell grid, so no sum of the cells'
+    counts gives the selector's counts on it; but a pixel's edge mask does not depend on the area, so up to the decision the batches
+    (whole frames) go through cells_fn, which keeps every frame's mask words beside the locator's totals (vse_frame_cells_masks), and
+    nothing is yielded as closed.  The decision falls after frame `window` (a clip that ends sooner decides at its end): the cells are
+    flushed, the totals read once, with edge_thresh="auto" area_locator.pick_edge_thresh chooses with frames_scanned = the frames of the
+    window, and area_locator.locate_area decides on that threshold's totals, so area, threshold, `scores`, `totals` and `frames_scanned`
+    are AreaLocator(probe=(1, window)).run(...)'s, its warning and no area when no threshold scores included.  With an area, replay_fn
+    counts the kept masks of frames 1 .. window on it (vse_frame_masks_replay: integer for integer vse_frame_change's counts) and hands
+    the last mask to count_fn; one IntervalTracker, built as ChangeFrameSelector builds its own, is fed them, the intervals it has
+    closed are yielded with the deciding batch, and the rest of the frames run over the area's rows through count_fn like a plain
+    ChangeFrameSelector: the intervals and counts are ChangeFrameSelector(edge_thresh=the choice)'s over the whole clip on the located
+    area.  Without an area, `area` stays None, `decided` is True and the generator ends, having consumed min(window, clip) frames
+    exactly: the first `window` frames are a staged run of their own, so neither this nor an uploader's producer thread reads beyond
+    them before the area is known.  Whether a window of some length finds the band of a real film is not measured here (no real clips).
+
+    cells_fn(frames [n,h,w,3] uint8 | None, area, engine.CellParams, reset, flush, thresholds, cap) -> totals [nt,gy,gx,4]; default
+    EngineCellsMasks on the shim's device.  replay_fn(area, q, rect, count_fn) -> counts [frames fed,3] at threshold index q on rect (y0,
+    y1, x0, x1 in the region's pixels), after which count_fn's next call continues from the last mask; default cells_fn.replay.
+    count_fn: ChangeFrameSelector's; it is never called with reset.  window: frames, required.  edge_thresh: an integer or "auto".
+    locator_params: AreaLocator's keyword arguments (thresholds, min_edges, change_ratio, min_seconds, max_seconds, plateau_frac and
+    locate_area's); automaton="hold", max_hold_*, search_area and probe are refused.  Before the decision `tracker` is None."""
+
+    def __init__(self, count_fn=None, cells_fn=None, replay_fn=None, window=None, locator_params=None, edge_thresh=128, change_ratio=0.5,
+                 min_edges=None, min_frames=2, batch=64):
+        super().__init__(count_fn, edge_thresh, change_ratio, min_edges, min_frames, batch)
+        from . import area_locator
+        if window is None or int(window) < 1:
+            raise ValueError(f"LocatingChangeSelector: window must be at least 1 frame, not {window}")
+        self.window, self.cells_fn, self.replay_fn = int(window), cells_fn, replay_fn
+        params = dict(locator_params or {})
+        refused = [f"automaton={params['automaton']!r}"] if params.get("automaton", "change") != "change" else []
+        refused += sorted(set(params) & {"max_hold_seconds", "max_hold_frames", "search_area", "probe"})
+        if refused:
+            raise ValueError("LocatingChangeSelector: the locator in the selector's pass counts whole frames with the change automaton and "
+                             f"`window` says how many decide; it does not take {', '.join(refused)}")
+        self.locator = area_locator.AreaLocator(**{**params, "edge_thresh": edge_thresh})
+        self.area, self.tracker, self.decided = None, None, False
+        self.scores = self.totals = None
+        self.frames_scanned = 0
+
+    def iter_run(self, frames, sub_area=None, fps=None, uploader=None):
+        """ChangeFrameSelector.iter_run over whole frames (sub_area must be None: this finds it); up to the decision every batch is
+        yielded with no closed interval and `tracker` is None."""
+        import logging
+
+        import numpy as np
+        from . import area_locator
+        if sub_area is not None:
+            raise ValueError(f"LocatingChangeSelector: it finds the area itself and takes none, not {sub_area}")
+        if self.count_fn is None or self.cells_fn is None:
+            from . import shim
+            self.count_fn = EngineCounter(shim._context()) if self.count_fn is None else self.count_fn
+            self.cells_fn = EngineCellsMasks(shim._context()) if self.cells_fn is None else self.cells_fn
+        replay = self.cells_fn.replay if self.replay_fn is None else self.replay_fn
+        loc = self.locator
+        ths = loc.thresholds if loc.auto else (loc.edge_thresh,)
+        self.counts, self.intervals, self.tracker, self.decided, self.area = np.zeros((0, 3), np.int32), [], None, False, None
+        self.edge_thresh = None if loc.auto else loc.edge_thresh
+        self.scores = self.totals = None
+        self.frames_scanned = 0
+        it = iter(frames)
+        bands = band_batches(islice(it, self.window), None, self.batch, type(self).__name__)
+        if bands.area is None:
+            return
+        region, params = bands.area, loc.params(fps)
+        rows = []                             # the counts of the window [n,3], then of the frames behind it, batch by batch
+
+        def host(c, shape):
+            return np.asarray(c.cpu() if hasattr(c, "cpu") else c, np.int32).reshape(shape)
+
+        def decide(scanned):
+            totals = self.cells_fn(None, region, params, False, True, ths, self.window)
+            self.totals, self.frames_scanned, self.decided = host(totals, tuple(totals.shape)), scanned, True
+            q, chosen = 0, self.totals[0]
+            if loc.auto:
+                static_frac = loc.locate_kwargs.get("static_frac", 0.95)
+                self.scores = area_locator.edge_thresh_scores(self.totals, scanned, static_frac)
+                q = area_locator.pick_edge_thresh(self.totals, ths, scanned, static_frac, loc.plateau_frac)
+                if q is None:
+                    logging.getLogger(area_locator.__name__).warning(
+                        "edge_thresh='auto': none of the thresholds %s scores with the %s automaton in %d frames; falling back to %d", ths,
+                        loc.describe_automaton(), scanned, area_locator.DEFAULT_EDGE_THRESH)
+                    return []
+                self.edge_thresh, chosen = ths[q], self.totals[q]
+            else:
+                self.totals = chosen          # (AreaLocator's totals at one threshold are [gy,gx,4])
+            self.area = area_locator.locate_area(chosen, scanned, bands.geometry, bands.frame_hw, **loc.locate_kwargs)
+            if self.area is None:
+                return []
+            y0, y1, x0, x1 = clip_area(self.area, *bands.frame_hw)
+            rows.append(host(replay(region, q, (y0 - bands.geometry[0], y1 - bands.geometry[0], x0 - region[2], x1 - region[2]),
+                                    self.count_fn), (-1, 3)))
+            min_edges = default_min_edges(y1 - y0, x1 - x0) if self.min_edges is None else self.min_edges
+            self.tracker = IntervalTracker(min_edges, self.change_ratio, self.min_frames)
+            self.intervals = self.tracker.feed(rows[-1])
+            return list(self.intervals)
+
+        fed, closed = 0, []
+        with closing(staging.staged_batches(bands, uploader)) as staged:
+            for items, data in staged:
+                self.cells_fn(data, region, params, fed == 0, False, ths, self.window)
+                fed += len(items)
+                if fed >= self.window:
+                    closed = decide(fed)
+                yield items, closed
+        if not self.decided:                  # the clip ended inside the window
+            closed = decide(fed)
+        elif self.area is not None:
+            closed = []                       # (they went out with the deciding batch)
+            rest = band_batches(it, self.area, self.batch, type(self).__name__)
+            if rest.area is not None:
+                with closing(staging.staged_batches(rest, uploader)) as staged:
+                    for items, data in staged:
+                        rows.append(host(self.count_fn(data, rest.area, self.edge_thresh, False), (-1, 3)))
+                        got = self.tracker.feed(rows[-1])
+                        self.intervals += got
+                        yield items, got
+        if self.area is None:
+            return
+        last = self.tracker.flush()
+        self.intervals += last
+        self.counts = np.concatenate(rows)
         yield [], closed + last
 
 
