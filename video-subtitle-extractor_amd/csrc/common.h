@@ -182,3 +182,10 @@ int launch_simple_op(const vse_op& op, const TView& in0, const TView& in1, const
 int launch_gap_finish(const float* part, const TView& in0, const TView& out, int splits, int slots, hipStream_t st);
 // OP_SCALE + the OP_BINARY add behind it as one pass (scale_add_select): x * gate, rounded to fp16, + res -> activation -> out
 int launch_scale_add(const TView& x, const TView& gate, const TView& res, const TView& out, int act, hipStream_t st);
+
+// The per-cell interval rule of the subtitle-area locator (frame_change.hip), as vse_runtime.hip hands it to the vse_frame_cells*
+// launchers and as their kernels take it: a cell is present in a frame with min_edges edge pixels, a run of present frames is cut where
+// (appeared + vanished) * ratio_den >= ratio_num * |union|, and a run counts with min_frames .. max_frames frames.
+struct CellRule {
+    int min_edges, ratio_num, ratio_den, min_frames, max_frames;
+};

@@ -12,32 +12,34 @@
 // before it.  The previous mask of the tile is read from the caller's state at the start and written back at the end by the
 // same block: no block reads what another block writes, so a batch needs no second pass and no grid-wide ordering.
 //
-// Subtitle-area locator (vse_frame_cells): the same tiles and the same mask, but a tile is a CELL that keeps its own counts and runs
-// the interval automaton of frame_select.change_intervals on them (frame_cells_kernel below).
+// The other entry points work on the same tiles and the same mask.  The kernels, in the order of the file:
+//   frame_change_kernel               vse_frame_change, above.
+//   frame_cells_kernel                vse_frame_cells, the subtitle-area locator: a tile is a CELL that keeps its own counts and runs the
+//                                     interval automaton of frame_select.change_intervals on them.
+//   frame_cells_multi_kernel          vse_frame_cells_multi, _counts and _masks: the cells for several edge thresholds in one pass over the
+//                                     frames (threshold calibration), optionally with the whole region's counts per threshold or with the mask
+//                                     words of every frame kept in the caller's buffer.  One template, the extra output a compile-time kind.
+//   frame_cells_export_kernel,        one threshold's slice of a cells state as a vse_frame_change state, and the counts of any rectangle
+//   frame_masks_replay_kernel         of the region out of the kept mask words, as frame_change_kernel would have counted them on the frames.
+//   frame_hold_kernel                 vse_frame_hold: only edge pixels that hold still for `hold` frames are counted, so that the edges of a
+//                                     moving background drop out.
+//   frame_cells_hold_kernel           vse_frame_cells_hold: the cells and their automaton at several thresholds on the held masks.
+//   frame_focus_kernel                vse_frame_focus: per frame, the number of edge pixels that were edge pixels one frame earlier and the
+//                                     sum of their gradients.
+//   frame_hold_bounded_kernel,        vse_frame_hold_bounded: the held-edge walk, but only runs of hold .. max_hold frames are counted, so that
+//   frame_hold_rows_kernel            the edges of a background that stands still drop out too.
+//   frame_cells_hold_bounded_kernel   vse_frame_cells_hold_bounded: the cells and their automaton at several thresholds on the bounded masks.
+// The launchers of the first eight follow frame_focus_kernel; the two bounded sections each end with their own.
 //
-// Threshold calibration (vse_frame_cells_multi): vse_frame_cells for several edge thresholds in one pass over the frames
-// (frame_cells_multi_kernel below).
-//
-// The locator's masks kept for an area decided later (vse_frame_cells_masks, vse_frame_masks_replay): frame_cells_multi_kernel that also
-// writes the mask words of every frame to the caller's buffer, one bit per pixel and threshold, and a small kernel that counts any
-// rectangle of the region out of those words as frame_change_kernel would have counted it on the frames (frame_cells_masks_kernel and
-// frame_masks_replay_kernel below).
-//
-// Held-edge selector (vse_frame_hold): the same tiles and the same mask again, but only edge pixels that hold still for `hold` frames
-// are counted, so that the edges of a moving background drop out (frame_hold_kernel below).
-//
-// Locator and calibration on held edges (vse_frame_cells_hold): the cells and their automaton at several thresholds, counted on the
-// held masks (frame_cells_hold_kernel below).
-//
-// Sharpness of the edges that stand still (vse_frame_focus): the same tiles, mask and state as vse_frame_change, but per frame the
-// number of edge pixels that were edge pixels one frame earlier and the sum of their gradients (frame_focus_kernel below).
-//
-// Held-edge selector with bounded runs (vse_frame_hold_bounded): frame_hold_kernel's tiles, mask and walk, but only edge pixels whose run
-// is hold .. max_hold frames long are counted, so that the edges of a background that stands still drop out too (frame_hold_bounded_kernel
-// and frame_hold_rows_kernel, near the end of the file).
-//
-// Locator and calibration on bounded runs (vse_frame_cells_hold_bounded): the cells and their automaton at several thresholds, counted on
-// the bounded masks (frame_cells_hold_bounded_kernel, at the end of the file).
+// What the kernels share is written once where that leaves their code as it was: the tile (tile_lane, tile_masks, tile_masks_multi), the
+// automaton (CellRuns, with the load and store of its state), the small pieces of a chunk (zero_steps, edge_bit), and on the host what
+// the launchers of the several-threshold kernels build and the choice of the instantiation (CellsLaunch, launch_for_nt).  Two pieces stay
+// written out in each kernel that has them, because every shared form that was tried compiled those kernels to other code than the inline
+// text does (EXPERIMENTS.md, "One cells kernel template"): the popcount loop over a step's words, and the two ballots with the stepping
+// of CellRuns behind them.  A change to either is a change to each of: frame_cells_kernel, frame_cells_multi_kernel, frame_cells_hold_kernel,
+// frame_cells_hold_bounded_kernel (the ballots) and frame_hold_kernel (the loop).
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -120,10 +122,10 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_change_kernel(const uint8
     if (threadIdx.x == 0) *flag = 1u;
 }
 
-// ---- vse_frame_cells ------------------------------------------------------------------------------------------------------------
+// ---- the tile, shared by every kernel below ------------------------------------------------------------------------------------------
 // The tile and its mask words are frame_change_kernel's above, statement for statement, as two helpers.  frame_change_kernel keeps its
 // own inline copy: routed through these helpers it compiled to slightly different code and measured 0.3-0.6 % slower (64 x 1080p,
-// alternating with the inline build in one process), and that kernel's behaviour is not this one's to change.
+// alternating with the inline build in one process).
 // What a lane reads of its block's tile; fixed for the whole kernel.
 struct TileLane {
     int rows;       // interior rows of the tile that lie in the area
@@ -173,17 +175,88 @@ __device__ __forceinline__ void tile_masks(const uint8_t* __restrict__ src, int 
     }
 }
 
+// Up to FC_WAVES edge thresholds at once: a frame's bytes are read and its lumas and gradients computed once; per threshold only the
+// compare / ballot differs.
+struct CellThresholds {
+    int t[FC_WAVES];        // ascending, each 1..255; those beyond the kernel's NT unused
+};
+
+// tile_masks with the ballot repeated per threshold (tile_masks itself stays as it is: split into shared pieces it compiled
+// frame_cells_kernel and frame_hold_kernel to different code).
+// msk[(q * FC_CHUNK + tl) * FC_ROWS + k] = packed mask at threshold q of the tile's interior row k in frame c0 + tl, for tl < cn.
+template <int NT>
+__device__ __forceinline__ void tile_masks_multi(const uint8_t* __restrict__ src, int c0, int cn, long pitch, long fstride, const TileLane& t,
+                                                 const CellThresholds& th, unsigned long long* msk) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int rows = t.rows;
+    for (int tl = wave; tl < cn; tl += FC_WAVES) {
+        const uint8_t* f = src + (long)(c0 + tl) * fstride;
+        int yc[FC_ROWS + 2], ye[FC_ROWS];
+#pragma unroll
+        for (int k = 0; k < FC_ROWS + 2; ++k) yc[k] = (k < rows + 2 && t.own) ? luma(f + (long)k * pitch + t.x * 3) : 0;
+#pragma unroll
+        for (int k = 0; k < FC_ROWS; ++k) ye[k] = (k < rows && t.extra) ? luma(f + (long)(k + 1) * pitch + t.xe * 3) : 0;
+#pragma unroll
+        for (int k = 0; k < FC_ROWS; ++k) {
+            int e = -1;                    // below every threshold: the words of rows outside the area are zero
+            if (k < rows) {                // block-uniform
+                const int l = __shfl_up(yc[k + 1], 1), r = __shfl_down(yc[k + 1], 1);
+                const int left = lane == 0 ? ye[k] : l, right = lane == 63 ? ye[k] : r;
+                if (t.inner) e = max(abs(right - left), abs(yc[k + 2] - yc[k]));
+            }
+            unsigned long long b[NT];
+#pragma unroll
+            for (int q = 0; q < NT; ++q) b[q] = __ballot(e >= th.t[q]);
+            if (lane == 0) {
+#pragma unroll
+                for (int q = 0; q < NT; ++q) msk[(q * FC_CHUNK + tl) * FC_ROWS + k] = b[q];
+            }
+        }
+    }
+}
+
+// ---- the pieces of a chunk, shared by the kernels that walk its words ---------------------------------------------------------------------
+// The steps real .. cn - 1 of a chunk are the flush, without an edge anywhere: their words are zero at every threshold.  (The kernels of
+// one threshold keep msk as [FC_CHUNK][FC_ROWS] and zero it by that index: through this helper their address took one instruction more.)
+template <int NT>
+__device__ __forceinline__ void zero_steps(unsigned long long* msk, int real, int cn) {
+    for (int i = real * FC_ROWS + threadIdx.x; i < cn * FC_ROWS; i += FC_WAVES * 64) {
+#pragma unroll
+        for (int q = 0; q < NT; ++q) msk[q * FC_CHUNK * FC_ROWS + i] = 0ull;
+    }
+}
+
+// A wave that walks a row with lane = column holds the row's words with lane = step, as halves lo / hi: the lane's own bit of step tl.
+// (`lane` is the kernel's own value: recomputed here from threadIdx.x it changed the compare in all four kernels.)
+__device__ __forceinline__ bool edge_bit(int lo, int hi, int tl, int lane) {
+    const unsigned half = (unsigned)(lane < 32 ? __builtin_amdgcn_readlane(lo, tl) : __builtin_amdgcn_readlane(hi, tl));
+    return (half >> (lane & 31)) & 1u;
+}
+
+// ---- the cells' automaton --------------------------------------------------------------------------------------------------------------
 // Per-cell state of vse_frame_cells: the FC_ROWS mask words of the cell's last frame, then the length of its open run.
 constexpr int CELL_STATE_WORDS = FC_ROWS + 1;
-
-struct CellRule {
-    int min_edges, ratio_num, ratio_den, min_frames, max_frames;
-};
 
 // One cell's interval automaton: frame_select.change_intervals in integers, with the run lengths summed instead of listed.
 // Every value here is the same in all lanes of the wave that walks it.
 struct CellRuns {
     int run, covered, runs, present, cuts;
+    // from the state a call left: the open run (a word of the cells state, or an int of the held states) and the cell's four totals
+    template <class R>
+    __device__ __forceinline__ void load(const R* open_run, const int* tot) {
+        *this = {(int)*open_run, tot[0], tot[1], tot[2], tot[3]};
+    }
+    // ... and back, by one lane; a flush closes the open run first (frame_cells_hold_bounded_kernel stores its carry between the two and
+    // keeps the statements inline: through this function its registers were numbered otherwise)
+    template <class R>
+    __device__ __forceinline__ void store(R* open_run, int* tot, int flush, const CellRule& r) {
+        if (flush) close(r);
+        *open_run = (R)run;
+        tot[0] = covered;
+        tot[1] = runs;
+        tot[2] = present;
+        tot[3] = cuts;
+    }
     __device__ __forceinline__ void close(const CellRule& r) {
         if (run >= r.min_frames && run <= r.max_frames) {
             covered += run;
@@ -206,6 +279,7 @@ struct CellRuns {
     }
 };
 
+// ---- vse_frame_cells ------------------------------------------------------------------------------------------------------------
 // The grid is gx x gy cells; block (cx, cy) owns cell cy * gx + cx in state, totals and cell_counts alike, for all frames of the call.
 // src points at row y0 of frame 0.  Runs with n == 0 too (reset and flush only).
 __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_kernel(const uint8_t* __restrict__ src, int n, long pitch, long fstride,
@@ -224,7 +298,7 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_kernel(const uint8_
     // words of rows outside the region are zero in every frame, so all FC_ROWS words are kept
     if (threadIdx.x < FC_ROWS) prv[threadIdx.x] = reset ? 0ull : st[threadIdx.x];
     CellRuns cr = {0, 0, 0, 0, 0};
-    if (wave == 0 && !reset) cr = {(int)st[FC_ROWS], tot[0], tot[1], tot[2], tot[3]};
+    if (wave == 0 && !reset) cr.load(st + FC_ROWS, tot);
 
     for (int c0 = 0; c0 < n; c0 += FC_CHUNK) {
         const int cn = min(FC_CHUNK, n - c0);
@@ -259,72 +333,53 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_kernel(const uint8_
         __syncthreads();
     }
     if (threadIdx.x < FC_ROWS) st[threadIdx.x] = prv[threadIdx.x];
-    if (threadIdx.x == 0) {
-        if (flush) cr.close(rule);
-        st[FC_ROWS] = (unsigned long long)cr.run;
-        tot[0] = cr.covered;
-        tot[1] = cr.runs;
-        tot[2] = cr.present;
-        tot[3] = cr.cuts;
-    }
+    if (threadIdx.x == 0) cr.store(st + FC_ROWS, tot, flush, rule);
 }
 
-// ---- vse_frame_cells_multi -------------------------------------------------------------------------------------------------------
-// frame_cells_kernel for up to FC_WAVES edge thresholds in one pass: a frame's bytes are read and its lumas and gradients computed once;
-// per threshold only the compare / ballot differs, and then the cell's mask words, counts and automaton.  The tile is tile_lane's; the mask
-// loop below is tile_masks' with the ballot repeated per threshold (tile_masks itself stays as it is: split into shared pieces it
-// compiled frame_cells_kernel and frame_hold_kernel to different code, and those kernels are not this one's to change).
-// Wave q then walks threshold q's automaton exactly as wave 0 does above, the thresholds side by side.  State and totals are nt
-// slices, each laid out as vse_frame_cells lays out its own.
-struct CellThresholds {
-    int t[FC_WAVES];        // ascending, each 1..255; those beyond the kernel's NT unused
-};
+// ---- vse_frame_cells_multi, vse_frame_cells_counts, vse_frame_cells_masks ------------------------------------------------------------------
+// frame_cells_kernel for NT = 1 .. FC_WAVES edge thresholds in one pass (a template parameter: the ballots of a row unroll without a branch
+// per threshold).  tile_masks_multi leaves the mask words of the NT thresholds side by side in LDS; wave q then walks threshold q's automaton
+// exactly as wave 0 does above.  Grid and cell ownership as frame_cells_kernel; threshold q's state is state[(q * cells + cell) *
+// CELL_STATE_WORDS ..] and its totals totals[(q * cells + cell) * 4 ..], each slice laid out as vse_frame_cells lays out its own.  Runs with
+// n == 0 too (reset and flush only; no extra output is touched).
+// OUT names what else a pass writes, with its arguments as the trailing pack x (instantiated with the explicit types of the launcher, so
+// that the pointers keep their __restrict__; arguments that a kind lacks are not in its signature, which keeps each kind's code as if it
+// were written alone):
+//   CELLS_ONLY    nothing.
+//   CELLS_COUNTS  int* counts: the cells tile the interior of the region exactly as frame_change_kernel's tiles tile the interior of its
+//                 area, and the mask is the same statement for statement, so a frame's (e, a, v) summed over all cells at threshold q is
+//                 what frame_change_kernel counts on that area at th.t[q].  Each live lane adds its cell's three integers into
+//                 counts[((c0 + lane) * NT + q) * 3 ..] (cleared by the launcher ahead of the kernel); zeros are skipped as
+//                 frame_change_kernel skips them, and integer sums do not depend on the order the blocks arrive in.
+//   CELLS_MASKS   unsigned long long* masks, long slot0: the mask words a chunk leaves in LDS are also written to the caller's buffer, so
+//                 that the counts of ANY rectangle of the region can be made later without the frames (frame_masks_replay_kernel below).
+//                 Cell-major: slot f, threshold q, cell c, row k -> word ((f * NT + q) * cells + c) * FC_ROWS + k, which is msk[q][tl][k]
+//                 of frame f: wave q copies its own slice, lane l of pass p writing word l % 8 of frame 8 p + l / 8 of the chunk, so one
+//                 store instruction writes eight whole 64-byte lines and the LDS reads of a pass are 64 consecutive words.  Words of rows
+//                 and columns beyond the interior are zero in LDS (tile_masks_multi) and are written as such.  A block writes only its own
+//                 cell's words; the launcher has checked slot0 + n <= cap.  No atomics.  The store loop is kept rolled: unrolled, its
+//                 eight addresses cost 127-129 VGPRs and the second block at NT = 5..7.
+// LDS is the same for every kind: (FC_CHUNK + 1) * NT * FC_ROWS words, 4160 B at NT = 1 and 33280 B at NT = 8; no scratch.  VGPRs at NT = 1
+// and NT = 8 (the compiler's resource usage for gfx950): 92 and 102 alone, 95 and 107 with counts, 99 and 107 with masks.  That is 5 waves
+// per SIMD at NT <= 3 and 4 above for the first two, 4 at every NT with masks; a block is two waves per SIMD, so every kind holds two blocks
+// on a CU, also at NT = 8 (65 KiB of its 160 KiB LDS).
+enum { CELLS_ONLY, CELLS_COUNTS, CELLS_MASKS };
 
-// msk[(q * FC_CHUNK + tl) * FC_ROWS + k] = packed mask at threshold q of the tile's interior row k in frame c0 + tl, for tl < cn.
-template <int NT>
-__device__ __forceinline__ void tile_masks_multi(const uint8_t* __restrict__ src, int c0, int cn, long pitch, long fstride, const TileLane& t,
-                                                 const CellThresholds& th, unsigned long long* msk) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int rows = t.rows;
-    for (int tl = wave; tl < cn; tl += FC_WAVES) {
-        const uint8_t* f = src + (long)(c0 + tl) * fstride;
-        int yc[FC_ROWS + 2], ye[FC_ROWS];
-#pragma unroll
-        for (int k = 0; k < FC_ROWS + 2; ++k) yc[k] = (k < rows + 2 && t.own) ? luma(f + (long)k * pitch + t.x * 3) : 0;
-#pragma unroll
-        for (int k = 0; k < FC_ROWS; ++k) ye[k] = (k < rows && t.extra) ? luma(f + (long)(k + 1) * pitch + t.xe * 3) : 0;
-#pragma unroll
-        for (int k = 0; k < FC_ROWS; ++k) {
-            int e = -1;                    // below every threshold: the words of rows outside the area are zero
-            if (k < rows) {                // block-uniform
-                const int l = __shfl_up(yc[k + 1], 1), r = __shfl_down(yc[k + 1], 1);
-                const int left = lane == 0 ? ye[k] : l, right = lane == 63 ? ye[k] : r;
-                if (t.inner) e = max(abs(right - left), abs(yc[k + 2] - yc[k]));
-            }
-            unsigned long long b[NT];
-#pragma unroll
-            for (int q = 0; q < NT; ++q) b[q] = __ballot(e >= th.t[q]);
-            if (lane == 0) {
-#pragma unroll
-                for (int q = 0; q < NT; ++q) msk[(q * FC_CHUNK + tl) * FC_ROWS + k] = b[q];
-            }
-        }
-    }
-}
+template <class A, class... R>
+__device__ __forceinline__ A first_of(A a, R...) { return a; }
+template <class A, class B>
+__device__ __forceinline__ B second_of(A, B b) { return b; }
 
-// Grid and cell ownership as frame_cells_kernel; threshold q's state is state[(q * cells + cell) * CELL_STATE_WORDS ..] and its totals
-// totals[(q * cells + cell) * 4 ..].  NT = the number of thresholds, 1 .. FC_WAVES (a template parameter: the ballots of a row unroll
-// without a branch per threshold).  LDS: (FC_CHUNK + 1) * NT * FC_ROWS words, 32.5 KiB at NT = 8; at the 83 VGPRs of this kernel a CU
-// holds two blocks, which is 65 KiB of its 160.  Runs with n == 0 too (reset and flush only).
-template <int NT>
+template <int NT, int OUT, class... X>
 __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_multi_kernel(const uint8_t* __restrict__ src, int n, long pitch, long fstride,
                                                                           int x0, int ih, int iw, CellThresholds th, CellRule rule,
                                                                           unsigned long long* __restrict__ state, int reset, int flush,
-                                                                          int* __restrict__ totals) {
+                                                                          int* __restrict__ totals, X... x) {
     __shared__ unsigned long long msk[NT * FC_CHUNK * FC_ROWS];           // [NT][FC_CHUNK][FC_ROWS]
     __shared__ unsigned long long prv[NT * FC_ROWS];
     static_assert(FC_CHUNK == 64, "the frames of a chunk are the lanes of a wave");
     static_assert(NT >= 1 && NT <= FC_WAVES, "wave q owns threshold q");
+    static_assert(sizeof...(X) == (OUT == CELLS_ONLY ? 0 : OUT == CELLS_COUNTS ? 1 : 2), "the pack is the kind's arguments");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int iy0 = blockIdx.y * FC_ROWS;
     const long cell = (long)blockIdx.y * gridDim.x + blockIdx.x, cells = (long)gridDim.y * gridDim.x;
@@ -336,13 +391,22 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_multi_kernel(const 
     unsigned long long* pq = prv + wave * FC_ROWS;
     if (mine && lane < FC_ROWS) pq[lane] = reset ? 0ull : st[lane];
     CellRuns cr = {0, 0, 0, 0, 0};
-    if (mine && !reset) cr = {(int)st[FC_ROWS], tot[0], tot[1], tot[2], tot[3]};
+    if (mine && !reset) cr.load(st + FC_ROWS, tot);
 
     for (int c0 = 0; c0 < n; c0 += FC_CHUNK) {
         const int cn = min(FC_CHUNK, n - c0);
         tile_masks_multi<NT>(src + (long)iy0 * pitch, c0, cn, pitch, fstride, t, th, msk);
         __syncthreads();
         if (mine) {                                // lane = frame of the chunk
+            if constexpr (OUT == CELLS_MASKS) {
+                static_assert(FC_ROWS == 8, "a lane's word of a store pass is lane % 8 of frame lane / 8");
+                // the chunk's words of threshold `wave`: frame c0 + tl < n of the call is slot slot0 + c0 + tl < cap
+                const long slot_words = NT * cells * FC_ROWS;
+                unsigned long long* out =
+                    first_of(x...) + (second_of(x...) + c0 + (lane >> 3)) * slot_words + (wave * cells + cell) * FC_ROWS + (lane & 7);
+#pragma unroll 1
+                for (int i = lane; i < cn * FC_ROWS; i += 64, out += (FC_CHUNK / FC_ROWS) * slot_words) *out = mq[i];
+            }
             const bool live = lane < cn;
             int e = 0, a = 0, v = 0, ep = 0;
             if (live) {
@@ -353,6 +417,13 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_multi_kernel(const 
                     a += __popcll(cur & ~pre);
                     v += __popcll(pre & ~cur);
                     ep += __popcll(pre);           // edges[t-1]
+                }
+                if constexpr (OUT == CELLS_COUNTS) {
+                    // the whole area's counts of frame c0 + lane at threshold `wave`: c0 + lane < n and wave < NT, inside [n][NT][3]
+                    int* o = first_of(x...) + ((long)(c0 + lane) * NT + wave) * 3;
+                    if (e) atomicAdd(o, e);
+                    if (a) atomicAdd(o + 1, a);
+                    if (v) atomicAdd(o + 2, v);
                 }
             }
             const long long uni = ep + a;          // |E' or E|
@@ -365,88 +436,7 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_multi_kernel(const 
         __syncthreads();
     }
     if (mine && lane < FC_ROWS) st[lane] = pq[lane];
-    if (mine && lane == 0) {
-        if (flush) cr.close(rule);
-        st[FC_ROWS] = (unsigned long long)cr.run;
-        tot[0] = cr.covered;
-        tot[1] = cr.runs;
-        tot[2] = cr.present;
-        tot[3] = cr.cuts;
-    }
-}
-
-// ---- vse_frame_cells_counts -----------------------------------------------------------------------------------------------------
-// frame_cells_multi_kernel with one more output: the cells tile the interior of the region exactly as frame_change_kernel's tiles tile the
-// interior of its area, and the mask is the same statement for statement, so a frame's (e, a, v) summed over all cells at threshold q is
-// what frame_change_kernel counts on that area at th.t[q].  Each live lane adds its cell's three integers into
-// counts[((c0 + lane) * NT + q) * 3 ..] (cleared by the launcher ahead of the kernel); zeros are skipped as frame_change_kernel skips
-// them, and integer sums do not depend on the order the blocks arrive in.  Everything else is frame_cells_multi_kernel line for line,
-// which keeps its own copy: that kernel is not this one's to change.  No LDS beyond that kernel's ((FC_CHUNK + 1) * NT * FC_ROWS words,
-// 4160 B at NT = 1, 33280 B at NT = 8), no scratch; 95 VGPRs at NT = 1, 107 at NT = 8 (the compiler's resource usage for gfx950;
-// frame_cells_multi_kernel<NT> has 92 and 102), which leaves the waves per SIMD where that kernel has them, 5 and 4, and two blocks of
-// NT = 8 on a CU.  Runs with n == 0 too (reset and flush only; nothing is added to counts).
-template <int NT>
-__global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_counts_kernel(const uint8_t* __restrict__ src, int n, long pitch, long fstride,
-                                                                           int x0, int ih, int iw, CellThresholds th, CellRule rule,
-                                                                           unsigned long long* __restrict__ state, int reset, int flush,
-                                                                           int* __restrict__ totals, int* __restrict__ counts) {
-    __shared__ unsigned long long msk[NT * FC_CHUNK * FC_ROWS];           // [NT][FC_CHUNK][FC_ROWS]
-    __shared__ unsigned long long prv[NT * FC_ROWS];
-    static_assert(FC_CHUNK == 64, "the frames of a chunk are the lanes of a wave");
-    static_assert(NT >= 1 && NT <= FC_WAVES, "wave q owns threshold q");
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int iy0 = blockIdx.y * FC_ROWS;
-    const long cell = (long)blockIdx.y * gridDim.x + blockIdx.x, cells = (long)gridDim.y * gridDim.x;
-    const TileLane t = tile_lane(blockIdx.x, iy0, ih, iw, x0);
-    const bool mine = wave < NT;            // wave q owns threshold q
-    unsigned long long* st = state + ((long)wave * cells + cell) * CELL_STATE_WORDS;
-    int* tot = totals + ((long)wave * cells + cell) * 4;
-    unsigned long long* mq = msk + wave * FC_CHUNK * FC_ROWS;
-    unsigned long long* pq = prv + wave * FC_ROWS;
-    if (mine && lane < FC_ROWS) pq[lane] = reset ? 0ull : st[lane];
-    CellRuns cr = {0, 0, 0, 0, 0};
-    if (mine && !reset) cr = {(int)st[FC_ROWS], tot[0], tot[1], tot[2], tot[3]};
-
-    for (int c0 = 0; c0 < n; c0 += FC_CHUNK) {
-        const int cn = min(FC_CHUNK, n - c0);
-        tile_masks_multi<NT>(src + (long)iy0 * pitch, c0, cn, pitch, fstride, t, th, msk);
-        __syncthreads();
-        if (mine) {                                // lane = frame of the chunk
-            const bool live = lane < cn;
-            int e = 0, a = 0, v = 0, ep = 0;
-            if (live) {
-#pragma unroll
-                for (int k = 0; k < FC_ROWS; ++k) {
-                    const unsigned long long cur = mq[lane * FC_ROWS + k], pre = lane ? mq[(lane - 1) * FC_ROWS + k] : pq[k];
-                    e += __popcll(cur);
-                    a += __popcll(cur & ~pre);
-                    v += __popcll(pre & ~cur);
-                    ep += __popcll(pre);           // edges[t-1]
-                }
-                // the whole area's counts of frame c0 + lane at threshold `wave`: c0 + lane < n and wave < NT, inside [n][NT][3]
-                int* o = counts + ((long)(c0 + lane) * NT + wave) * 3;
-                if (e) atomicAdd(o, e);
-                if (a) atomicAdd(o + 1, a);
-                if (v) atomicAdd(o + 2, v);
-            }
-            const long long uni = ep + a;          // |E' or E|
-            const unsigned long long present = __ballot(live && e >= rule.min_edges);
-            const unsigned long long ratio = __ballot(live && uni > 0 && (long long)(a + v) * rule.ratio_den >= (long long)rule.ratio_num * uni);
-            for (int f = 0; f < cn; ++f) cr.step((present >> f) & 1, (ratio >> f) & 1, rule);
-        }
-        __syncthreads();
-        if (mine && lane < FC_ROWS) pq[lane] = mq[(cn - 1) * FC_ROWS + lane];
-        __syncthreads();
-    }
-    if (mine && lane < FC_ROWS) st[lane] = pq[lane];
-    if (mine && lane == 0) {
-        if (flush) cr.close(rule);
-        st[FC_ROWS] = (unsigned long long)cr.run;
-        tot[0] = cr.covered;
-        tot[1] = cr.runs;
-        tot[2] = cr.present;
-        tot[3] = cr.cuts;
-    }
+    if (mine && lane == 0) cr.store(st + FC_ROWS, tot, flush, rule);
 }
 
 // Slice q of a vse_frame_cells_multi state -> a vse_frame_change state of the same area: a thread per interior row and word copies mask
@@ -463,87 +453,8 @@ __global__ __launch_bounds__(256) void frame_cells_export_kernel(const unsigned 
     if (i == 0) *flag = 1u;
 }
 
-// ---- vse_frame_cells_masks ------------------------------------------------------------------------------------------------------
-// frame_cells_multi_kernel with one more output: the mask words a chunk leaves in LDS are also written to the caller's buffer, so that
-// the counts of ANY rectangle of the region can be made later without the frames (frame_masks_replay_kernel below).  Cell-major: slot f,
-// threshold q, cell c, row k -> word ((f * NT + q) * cells + c) * FC_ROWS + k, which is msk[q][tl][k] of frame f: wave q copies its own
-// slice, lane l of pass p writing word l % 8 of frame 8 p + l / 8 of the chunk, so one store instruction writes eight whole 64-byte
-// lines and the LDS reads of a pass are 64 consecutive words.  Words of rows and columns beyond the interior are zero in LDS
-// (tile_masks_multi) and are written as such.  A block writes only its own cell's words; the launcher has checked slot0 + n <= cap.
-// Everything else is frame_cells_multi_kernel line for line, which keeps its own copy: that kernel is not this one's to change.  No
-// LDS beyond that kernel's ((FC_CHUNK + 1) * NT * FC_ROWS words, 4160 B at NT = 1, 33280 B at NT = 8), no scratch, no atomics; 99 VGPRs
-// at NT = 1, 107 at NT = 8 (the compiler's resource usage for gfx950; frame_cells_multi_kernel<NT> has 92 and 102), 4 waves per SIMD at
-// every NT where that kernel has 5 at NT <= 3: a block is two waves per SIMD, so both hold two blocks on a CU, also at NT = 8 (65 KiB of
-// its 160 KiB LDS).  The store loop is kept rolled: unrolled, its eight addresses cost 127-129 VGPRs and the second block at NT = 5..7.
-// Runs with n == 0 too (reset and flush only; no slot is written).
-template <int NT>
-__global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_masks_kernel(const uint8_t* __restrict__ src, int n, long pitch, long fstride,
-                                                                          int x0, int ih, int iw, CellThresholds th, CellRule rule,
-                                                                          unsigned long long* __restrict__ state, int reset, int flush,
-                                                                          int* __restrict__ totals, unsigned long long* __restrict__ masks,
-                                                                          long slot0) {
-    __shared__ unsigned long long msk[NT * FC_CHUNK * FC_ROWS];           // [NT][FC_CHUNK][FC_ROWS]
-    __shared__ unsigned long long prv[NT * FC_ROWS];
-    static_assert(FC_CHUNK == 64, "the frames of a chunk are the lanes of a wave");
-    static_assert(NT >= 1 && NT <= FC_WAVES, "wave q owns threshold q");
-    static_assert(FC_ROWS == 8, "a lane's word of a store pass is lane % 8 of frame lane / 8");
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int iy0 = blockIdx.y * FC_ROWS;
-    const long cell = (long)blockIdx.y * gridDim.x + blockIdx.x, cells = (long)gridDim.y * gridDim.x;
-    const TileLane t = tile_lane(blockIdx.x, iy0, ih, iw, x0);
-    const bool mine = wave < NT;            // wave q owns threshold q
-    unsigned long long* st = state + ((long)wave * cells + cell) * CELL_STATE_WORDS;
-    int* tot = totals + ((long)wave * cells + cell) * 4;
-    unsigned long long* mq = msk + wave * FC_CHUNK * FC_ROWS;
-    unsigned long long* pq = prv + wave * FC_ROWS;
-    if (mine && lane < FC_ROWS) pq[lane] = reset ? 0ull : st[lane];
-    CellRuns cr = {0, 0, 0, 0, 0};
-    if (mine && !reset) cr = {(int)st[FC_ROWS], tot[0], tot[1], tot[2], tot[3]};
-
-    for (int c0 = 0; c0 < n; c0 += FC_CHUNK) {
-        const int cn = min(FC_CHUNK, n - c0);
-        tile_masks_multi<NT>(src + (long)iy0 * pitch, c0, cn, pitch, fstride, t, th, msk);
-        __syncthreads();
-        if (mine) {                                // lane = frame of the chunk
-            // the chunk's words of threshold `wave`: frame c0 + tl < n of the call is slot slot0 + c0 + tl < cap
-            const long slot_words = NT * cells * FC_ROWS;
-            unsigned long long* out = masks + (slot0 + c0 + (lane >> 3)) * slot_words + (wave * cells + cell) * FC_ROWS + (lane & 7);
-#pragma unroll 1
-            for (int i = lane; i < cn * FC_ROWS; i += 64, out += (FC_CHUNK / FC_ROWS) * slot_words) *out = mq[i];
-            const bool live = lane < cn;
-            int e = 0, a = 0, v = 0, ep = 0;
-            if (live) {
-#pragma unroll
-                for (int k = 0; k < FC_ROWS; ++k) {
-                    const unsigned long long cur = mq[lane * FC_ROWS + k], pre = lane ? mq[(lane - 1) * FC_ROWS + k] : pq[k];
-                    e += __popcll(cur);
-                    a += __popcll(cur & ~pre);
-                    v += __popcll(pre & ~cur);
-                    ep += __popcll(pre);           // edges[t-1]
-                }
-            }
-            const long long uni = ep + a;          // |E' or E|
-            const unsigned long long present = __ballot(live && e >= rule.min_edges);
-            const unsigned long long ratio = __ballot(live && uni > 0 && (long long)(a + v) * rule.ratio_den >= (long long)rule.ratio_num * uni);
-            for (int f = 0; f < cn; ++f) cr.step((present >> f) & 1, (ratio >> f) & 1, rule);
-        }
-        __syncthreads();
-        if (mine && lane < FC_ROWS) pq[lane] = mq[(cn - 1) * FC_ROWS + lane];
-        __syncthreads();
-    }
-    if (mine && lane < FC_ROWS) st[lane] = pq[lane];
-    if (mine && lane == 0) {
-        if (flush) cr.close(rule);
-        st[FC_ROWS] = (unsigned long long)cr.run;
-        tot[0] = cr.covered;
-        tot[1] = cr.runs;
-        tot[2] = cr.present;
-        tot[3] = cr.cuts;
-    }
-}
-
 // ---- vse_frame_masks_replay -----------------------------------------------------------------------------------------------------
-// The counts frame_change_kernel would write on a rectangle of the region, from the words frame_cells_masks_kernel kept: an edge pixel
+// The counts frame_change_kernel would write on a rectangle of the region, from the words frame_cells_multi_kernel kept (CELLS_MASKS): an edge pixel
 // depends on its four neighbours and the threshold only, not on the area it is counted in, so interior pixel (iy, ix) of the rectangle
 // [ry0, ry1) x [rx0, rx1) (region coordinates) is interior pixel (ry0 + iy, rx0 + ix) of the region.
 struct ReplayRect {
@@ -654,8 +565,7 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_hold_kernel(const uint8_t
             const int lo = (int)(unsigned)col, hi = (int)(unsigned)(col >> 32);
             unsigned long long out = 0ull;
             for (int tl = 0; tl < cn; ++tl) {
-                const unsigned half = (unsigned)(lane < 32 ? __builtin_amdgcn_readlane(lo, tl) : __builtin_amdgcn_readlane(hi, tl));
-                const bool edge = (half >> (lane & 31)) & 1u;
+                const bool edge = edge_bit(lo, hi, tl, lane);
                 run = edge ? min(run + 1, hold) : 0;
                 cover = run == hold ? hold : max(cover - 1, 0);
                 held = cover > 0;
@@ -735,16 +645,13 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_hold_kernel(const u
         rc[q] = (int)(s & 0xfffu);
     }
     CellRuns cr = {0, 0, 0, 0, 0};
-    if (mine && !fresh) cr = {open_runs[(long)wave * cells + cell], tot[0], tot[1], tot[2], tot[3]};
+    if (mine && !fresh) cr.load(open_runs + ((long)wave * cells + cell), tot);
 
     for (int c0 = 0; c0 < steps; c0 += FC_CHUNK) {
         const int cn = min(FC_CHUNK, steps - c0);
         const int real = max(0, min(cn, n - c0));          // the steps after frame n are the flush: no edge anywhere
         tile_masks_multi<NT>(src + (long)iy0 * pitch, c0, real, pitch, fstride, t, th, msk);
-        for (int i = real * FC_ROWS + threadIdx.x; i < cn * FC_ROWS; i += FC_WAVES * 64) {
-#pragma unroll
-            for (int q = 0; q < NT; ++q) msk[q * FC_CHUNK * FC_ROWS + i] = 0ull;
-        }
+        zero_steps<NT>(msk, real, cn);
         __syncthreads();
         if (walks) {
             // lane = step of the chunk for the words going in and out, lane = column for the walk: the walk itself stays out of LDS
@@ -762,8 +669,7 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_hold_kernel(const u
             for (int tl = 0; tl < cn; ++tl) {
 #pragma unroll
                 for (int q = 0; q < NT; ++q) {
-                    const unsigned half = (unsigned)(lane < 32 ? __builtin_amdgcn_readlane(lo[q], tl) : __builtin_amdgcn_readlane(hi[q], tl));
-                    const bool edge = (half >> (lane & 31)) & 1u;
+                    const bool edge = edge_bit(lo[q], hi[q], tl, lane);
                     run[q] = edge ? min(run[q] + 1, hold) : 0;
                     cover[q] = run[q] == hold ? hold : max(cover[q] - 1, 0);
                     const unsigned long long b = __ballot(cover[q] > 0);
@@ -810,14 +716,7 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_hold_kernel(const u
 #pragma unroll
         for (int q = 0; q < NT; ++q) ps[q * pslice] = (unsigned short)(rc[q] | ((rc[q] >> 6) ? 1 << 12 : 0));
     }
-    if (mine && lane == 0) {
-        if (flush) cr.close(rule);
-        open_runs[(long)wave * cells + cell] = cr.run;
-        tot[0] = cr.covered;
-        tot[1] = cr.runs;
-        tot[2] = cr.present;
-        tot[3] = cr.cuts;
-    }
+    if (mine && lane == 0) cr.store(open_runs + ((long)wave * cells + cell), tot, flush, rule);
 }
 
 // ---- vse_frame_focus ------------------------------------------------------------------------------------------------------------
@@ -957,11 +856,10 @@ int vse_frame_cells_state_words() { return CELL_STATE_WORDS; }
 
 // Called by vse_frame_cells (vse_runtime.hip) after it has checked the arguments.
 int vse_frame_cells_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
-                           int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames, void* d_state, int reset, int flush,
-                           int32_t* d_totals, int32_t* d_cell_counts, void* stream) {
+                           const CellRule& rule, void* d_state, int reset, int flush, int32_t* d_totals, int32_t* d_cell_counts,
+                           void* stream) {
     const int ih = y1 - y0 - 2, iw = x1 - x0 - 2;
     const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
-    const CellRule rule = {min_edges, ratio_num, ratio_den, min_frames, max_frames};
     hipLaunchKernelGGL(frame_cells_kernel, dim3((iw + 63) / 64, (ih + FC_ROWS - 1) / FC_ROWS), dim3(FC_WAVES * 64), 0,
                        reinterpret_cast<hipStream_t>(stream), src, n, (long)pitch, (long)frame_stride, x0, ih, iw, edge_thresh, rule,
                        reinterpret_cast<unsigned long long*>(d_state), reset, flush, reinterpret_cast<int*>(d_totals),
@@ -971,64 +869,82 @@ int vse_frame_cells_launch(const void* d_bgr, int n, int64_t pitch, int64_t fram
 
 int vse_frame_cells_multi_max() { return FC_WAVES; }
 
-// Called by vse_frame_cells_multi (vse_runtime.hip) after it has checked the arguments (1 <= nt <= vse_frame_cells_multi_max()).
-int vse_frame_cells_multi_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
-                                 const int* thresholds, int nt, int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
-                                 void* d_state, int reset, int flush, int32_t* d_totals, void* stream) {
-    const int ih = y1 - y0 - 2, iw = x1 - x0 - 2;
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
-    const CellRule rule = {min_edges, ratio_num, ratio_den, min_frames, max_frames};
-    CellThresholds th = {};
-    for (int q = 0; q < nt; ++q) th.t[q] = thresholds[q];
-    const dim3 grid((iw + 63) / 64, (ih + FC_ROWS - 1) / FC_ROWS), block(FC_WAVES * 64);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    unsigned long long* state = reinterpret_cast<unsigned long long*>(d_state);
-    int* totals = reinterpret_cast<int*>(d_totals);
-#define VSE_CELLS_MULTI(NT)                                                                                                              \
-    case NT:                                                                                                                             \
-        hipLaunchKernelGGL(frame_cells_multi_kernel<NT>, grid, block, 0, st, src, n, (long)pitch, (long)frame_stride, x0, ih, iw, th, rule, \
-                           state, reset, flush, totals);                                                                                 \
-        break;
+namespace {
+
+// What the launchers of the kernels that take several thresholds share: the region's interior, its first row in frame 0, the thresholds
+// as the kernels take them, and a block per cell.
+struct CellsLaunch {
+    int ih, iw;
+    const uint8_t* src;
+    CellThresholds th;
+    dim3 grid, block;
+    hipStream_t st;
+    CellsLaunch(const void* d_bgr, int64_t pitch, int y0, int y1, int x0, int x1, const int* thresholds, int nt, void* stream)
+        : ih(y1 - y0 - 2), iw(x1 - x0 - 2), src(reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch), th{},
+          grid((iw + 63) / 64, (ih + FC_ROWS - 1) / FC_ROWS), block(FC_WAVES * 64), st(reinterpret_cast<hipStream_t>(stream)) {
+        for (int q = 0; q < nt; ++q) th.t[q] = thresholds[q];          // the caller has checked nt <= FC_WAVES
+    }
+};
+
+// launch(std::integral_constant<int, NT>) for NT == nt, which picks a kernel's instantiation for that many thresholds
+template <class F>
+int launch_for_nt(int nt, F launch) {
+    static_assert(FC_WAVES == 8, "one instantiation per number of thresholds");
     switch (nt) {
-        VSE_CELLS_MULTI(1) VSE_CELLS_MULTI(2) VSE_CELLS_MULTI(3) VSE_CELLS_MULTI(4)
-        VSE_CELLS_MULTI(5) VSE_CELLS_MULTI(6) VSE_CELLS_MULTI(7) VSE_CELLS_MULTI(8)
+        case 1: launch(std::integral_constant<int, 1>()); break;
+        case 2: launch(std::integral_constant<int, 2>()); break;
+        case 3: launch(std::integral_constant<int, 3>()); break;
+        case 4: launch(std::integral_constant<int, 4>()); break;
+        case 5: launch(std::integral_constant<int, 5>()); break;
+        case 6: launch(std::integral_constant<int, 6>()); break;
+        case 7: launch(std::integral_constant<int, 7>()); break;
+        case 8: launch(std::integral_constant<int, 8>()); break;
         default: return VSE_E_INVAL;
     }
-#undef VSE_CELLS_MULTI
-    static_assert(FC_WAVES == 8, "one instantiation per number of thresholds");
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+}
+
+// frame_cells_multi_kernel<nt, OUT, X...> with the kind's arguments x; X is given explicitly, so that the pointers keep their __restrict__
+template <int OUT, class... X>
+int cells_multi_launch(const CellsLaunch& l, int n, int64_t pitch, int64_t frame_stride, int x0, int nt, const CellRule& rule, void* d_state,
+                       int reset, int flush, int32_t* d_totals, X... x) {
+    return launch_for_nt(nt, [&](auto nt_c) {
+        hipLaunchKernelGGL((frame_cells_multi_kernel<decltype(nt_c)::value, OUT, X...>), l.grid, l.block, 0, l.st, l.src, n, (long)pitch,
+                           (long)frame_stride, x0, l.ih, l.iw, l.th, rule, reinterpret_cast<unsigned long long*>(d_state), reset, flush,
+                           reinterpret_cast<int*>(d_totals), x...);
+    });
+}
+
+}  // namespace
+
+// Called by vse_frame_cells_multi (vse_runtime.hip) after it has checked the arguments (1 <= nt <= vse_frame_cells_multi_max()).
+int vse_frame_cells_multi_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                                 const int* thresholds, int nt, const CellRule& rule, void* d_state, int reset, int flush,
+                                 int32_t* d_totals, void* stream) {
+    const CellsLaunch l(d_bgr, pitch, y0, y1, x0, x1, thresholds, nt, stream);
+    return cells_multi_launch<CELLS_ONLY>(l, n, pitch, frame_stride, x0, nt, rule, d_state, reset, flush, d_totals);
 }
 
 // Called by vse_frame_cells_counts (vse_runtime.hip) after it has checked the arguments as vse_frame_cells_multi does.  d_counts is
 // cleared on the stream ahead of the kernel, which adds into it.
 int vse_frame_cells_counts_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
-                                  const int* thresholds, int nt, int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
-                                  void* d_state, int reset, int flush, int32_t* d_totals, int32_t* d_counts, void* stream) {
-    const int ih = y1 - y0 - 2, iw = x1 - x0 - 2;
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
-    const CellRule rule = {min_edges, ratio_num, ratio_den, min_frames, max_frames};
-    CellThresholds th = {};
-    for (int q = 0; q < nt; ++q) th.t[q] = thresholds[q];
-    const dim3 grid((iw + 63) / 64, (ih + FC_ROWS - 1) / FC_ROWS), block(FC_WAVES * 64);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    unsigned long long* state = reinterpret_cast<unsigned long long*>(d_state);
-    int* totals = reinterpret_cast<int*>(d_totals);
-    int* counts = reinterpret_cast<int*>(d_counts);
+                                  const int* thresholds, int nt, const CellRule& rule, void* d_state, int reset, int flush,
+                                  int32_t* d_totals, int32_t* d_counts, void* stream) {
+    const CellsLaunch l(d_bgr, pitch, y0, y1, x0, x1, thresholds, nt, stream);
     if (nt < 1 || nt > FC_WAVES) return VSE_E_INVAL;
-    if (n > 0 && hipMemsetAsync(d_counts, 0, (size_t)n * nt * 3 * sizeof(int32_t), st) != hipSuccess) return VSE_E_HIP;
-#define VSE_CELLS_COUNTS(NT)                                                                                                             \
-    case NT:                                                                                                                             \
-        hipLaunchKernelGGL(frame_cells_counts_kernel<NT>, grid, block, 0, st, src, n, (long)pitch, (long)frame_stride, x0, ih, iw, th, rule, \
-                           state, reset, flush, totals, counts);                                                                         \
-        break;
-    switch (nt) {
-        VSE_CELLS_COUNTS(1) VSE_CELLS_COUNTS(2) VSE_CELLS_COUNTS(3) VSE_CELLS_COUNTS(4)
-        VSE_CELLS_COUNTS(5) VSE_CELLS_COUNTS(6) VSE_CELLS_COUNTS(7) VSE_CELLS_COUNTS(8)
-        default: return VSE_E_INVAL;
-    }
-#undef VSE_CELLS_COUNTS
-    static_assert(FC_WAVES == 8, "one instantiation per number of thresholds");
-    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+    if (n > 0 && hipMemsetAsync(d_counts, 0, (size_t)n * nt * 3 * sizeof(int32_t), l.st) != hipSuccess) return VSE_E_HIP;
+    return cells_multi_launch<CELLS_COUNTS, int* __restrict__>(l, n, pitch, frame_stride, x0, nt, rule, d_state, reset, flush, d_totals,
+                                                               reinterpret_cast<int*>(d_counts));
+}
+
+// Called by vse_frame_cells_masks (vse_runtime.hip) after it has checked the arguments as vse_frame_cells_multi does and 0 <= slot0,
+// slot0 + n <= cap of d_masks.
+int vse_frame_cells_masks_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                                 const int* thresholds, int nt, const CellRule& rule, void* d_state, int reset, int flush,
+                                 int32_t* d_totals, void* d_masks, int slot0, void* stream) {
+    const CellsLaunch l(d_bgr, pitch, y0, y1, x0, x1, thresholds, nt, stream);
+    return cells_multi_launch<CELLS_MASKS, unsigned long long* __restrict__, long>(
+        l, n, pitch, frame_stride, x0, nt, rule, d_state, reset, flush, d_totals, reinterpret_cast<unsigned long long*>(d_masks), (long)slot0);
 }
 
 // Called by vse_frame_cells_export_state (vse_runtime.hip) after it has checked the area and 0 <= q < nt <= vse_frame_cells_multi_max().
@@ -1040,36 +956,6 @@ int vse_frame_cells_export_launch(const void* d_cells_state, int area_h, int are
     unsigned long long* words = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(d_change_state) + 16);
     hipLaunchKernelGGL(frame_cells_export_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        slice, ih, wpr, words, flag);
-    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
-}
-
-// Called by vse_frame_cells_masks (vse_runtime.hip) after it has checked the arguments as vse_frame_cells_multi does and 0 <= slot0,
-// slot0 + n <= cap of d_masks.
-int vse_frame_cells_masks_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
-                                 const int* thresholds, int nt, int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
-                                 void* d_state, int reset, int flush, int32_t* d_totals, void* d_masks, int slot0, void* stream) {
-    const int ih = y1 - y0 - 2, iw = x1 - x0 - 2;
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
-    const CellRule rule = {min_edges, ratio_num, ratio_den, min_frames, max_frames};
-    CellThresholds th = {};
-    for (int q = 0; q < nt; ++q) th.t[q] = thresholds[q];
-    const dim3 grid((iw + 63) / 64, (ih + FC_ROWS - 1) / FC_ROWS), block(FC_WAVES * 64);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    unsigned long long* state = reinterpret_cast<unsigned long long*>(d_state);
-    int* totals = reinterpret_cast<int*>(d_totals);
-    unsigned long long* masks = reinterpret_cast<unsigned long long*>(d_masks);
-#define VSE_CELLS_MASKS(NT)                                                                                                              \
-    case NT:                                                                                                                             \
-        hipLaunchKernelGGL(frame_cells_masks_kernel<NT>, grid, block, 0, st, src, n, (long)pitch, (long)frame_stride, x0, ih, iw, th, rule, \
-                           state, reset, flush, totals, masks, (long)slot0);                                                             \
-        break;
-    switch (nt) {
-        VSE_CELLS_MASKS(1) VSE_CELLS_MASKS(2) VSE_CELLS_MASKS(3) VSE_CELLS_MASKS(4)
-        VSE_CELLS_MASKS(5) VSE_CELLS_MASKS(6) VSE_CELLS_MASKS(7) VSE_CELLS_MASKS(8)
-        default: return VSE_E_INVAL;
-    }
-#undef VSE_CELLS_MASKS
-    static_assert(FC_WAVES == 8, "one instantiation per number of thresholds");
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
 
@@ -1127,33 +1013,16 @@ size_t vse_frame_cells_hold_bytes(int ih, int iw, int nt) {
 // 32); steps = n (+ hold - 1 with a flush) >= 0, skip = the steps whose frame lies before frame 1, count_rows = the rows of d_cell_counts
 // per threshold.
 int vse_frame_cells_hold_launch(const void* d_bgr, int n, int steps, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
-                                const int* thresholds, int nt, int hold, int skip, int min_edges, int ratio_num, int ratio_den, int min_frames,
-                                int max_frames, void* d_state, int fresh, int flush, int32_t* d_totals, int32_t* d_cell_counts, int count_rows,
-                                void* stream) {
-    const int ih = y1 - y0 - 2, iw = x1 - x0 - 2;
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
-    const CellRule rule = {min_edges, ratio_num, ratio_den, min_frames, max_frames};
-    CellThresholds th = {};
-    for (int q = 0; q < nt; ++q) th.t[q] = thresholds[q];
-    const dim3 grid((iw + 63) / 64, (ih + FC_ROWS - 1) / FC_ROWS), block(FC_WAVES * 64);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+                                const int* thresholds, int nt, int hold, int skip, const CellRule& rule, void* d_state, int fresh, int flush,
+                                int32_t* d_totals, int32_t* d_cell_counts, int count_rows, void* stream) {
+    const CellsLaunch l(d_bgr, pitch, y0, y1, x0, x1, thresholds, nt, stream);
     unsigned short* pix = reinterpret_cast<unsigned short*>(d_state);
-    int* open_runs = reinterpret_cast<int*>(reinterpret_cast<char*>(d_state) + cells_hold_pixel_bytes(ih, iw, nt));
-    int* totals = reinterpret_cast<int*>(d_totals);
-    int* cell_counts = reinterpret_cast<int*>(d_cell_counts);
-#define VSE_CELLS_HOLD(NT)                                                                                                               \
-    case NT:                                                                                                                             \
-        hipLaunchKernelGGL(frame_cells_hold_kernel<NT>, grid, block, 0, st, src, n, steps, (long)pitch, (long)frame_stride, x0, ih, iw, th, \
-                           rule, hold, skip, pix, open_runs, fresh, flush, totals, cell_counts, count_rows);                             \
-        break;
-    switch (nt) {
-        VSE_CELLS_HOLD(1) VSE_CELLS_HOLD(2) VSE_CELLS_HOLD(3) VSE_CELLS_HOLD(4)
-        VSE_CELLS_HOLD(5) VSE_CELLS_HOLD(6) VSE_CELLS_HOLD(7) VSE_CELLS_HOLD(8)
-        default: return VSE_E_INVAL;
-    }
-#undef VSE_CELLS_HOLD
-    static_assert(FC_WAVES == 8, "one instantiation per number of thresholds");
-    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+    int* open_runs = reinterpret_cast<int*>(reinterpret_cast<char*>(d_state) + cells_hold_pixel_bytes(l.ih, l.iw, nt));
+    return launch_for_nt(nt, [&](auto nt_c) {
+        hipLaunchKernelGGL(frame_cells_hold_kernel<decltype(nt_c)::value>, l.grid, l.block, 0, l.st, l.src, n, steps, (long)pitch,
+                           (long)frame_stride, x0, l.ih, l.iw, l.th, rule, hold, skip, pix, open_runs, fresh, flush,
+                           reinterpret_cast<int*>(d_totals), reinterpret_cast<int*>(d_cell_counts), count_rows);
+    });
 }
 
 // ---- vse_frame_hold_bounded -----------------------------------------------------------------------------------------------------
@@ -1203,8 +1072,7 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_hold_bounded_kernel(const
         int ended = 0;                         // runs of this row that ended in range at step `lane`
         int slot = slot0;                      // ring slot of this step's frame
         for (int tl = 0; tl < steps; ++tl) {
-            const unsigned half = (unsigned)(lane < 32 ? __builtin_amdgcn_readlane(lo, tl) : __builtin_amdgcn_readlane(hi, tl));
-            const bool edge = (half >> (lane & 31)) & 1u;
+            const bool edge = edge_bit(lo, hi, tl, lane);
             const int len = run;
             run = edge ? min(run + 1, max_hold + 1) : 0;
             const bool ends = !edge && len >= hold && len <= max_hold;
@@ -1356,7 +1224,7 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_hold_bounded_kernel
     CellRuns cr = {0, 0, 0, 0, 0};
     int ecar = 0;                              // |B| of the last finished row
     if (mine && !fresh) {
-        cr = {open_runs[mycell], tot[0], tot[1], tot[2], tot[3]};
+        cr.load(open_runs + mycell, tot);
         ecar = carry[mycell];
     }
     long done_rows = 0;                        // rows of this call that are finished
@@ -1366,10 +1234,7 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_hold_bounded_kernel
         const int real = max(0, min(cn, n - c0));          // the step after frame n is the flush: no edge anywhere
         const int cslot = (int)(((long)slot_w + lagged + c0) % ring_slots);     // ring slot of the chunk's first step
         tile_masks_multi<NT>(src + (long)iy0 * pitch, c0, real, pitch, fstride, t, th, msk);
-        for (int i = real * FC_ROWS + threadIdx.x; i < cn * FC_ROWS; i += FC_WAVES * 64) {
-#pragma unroll
-            for (int q = 0; q < NT; ++q) msk[q * FC_CHUNK * FC_ROWS + i] = 0ull;
-        }
+        zero_steps<NT>(msk, real, cn);
         __syncthreads();
         if (walks) {
             // lane = step of the chunk for the words going in and the counts going out, lane = column for the walk
@@ -1385,8 +1250,7 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_hold_bounded_kernel
             for (int tl = 0; tl < cn; ++tl) {
 #pragma unroll
                 for (int q = 0; q < NT; ++q) {
-                    const unsigned half = (unsigned)(lane < 32 ? __builtin_amdgcn_readlane(lo[q], tl) : __builtin_amdgcn_readlane(hi[q], tl));
-                    const bool edge = (half >> (lane & 31)) & 1u;
+                    const bool edge = edge_bit(lo[q], hi[q], tl, lane);
                     const int len = run[q];
                     run[q] = edge ? min(len + 1, max_hold + 1) : 0;
                     const bool ends = !edge && len >= hold && len <= max_hold;
@@ -1488,40 +1352,23 @@ size_t vse_frame_cells_hold_bounded_bytes(int ih, int iw, int nt, int max_hold) 
 // hold <= max_hold <= 4000, n + flush >= 1, n + max_hold fits an int); count_rows = the rows of d_cell_counts per threshold.  One launch, and
 // before a clip's first one a clear of everything in the state but the run lengths.
 int vse_frame_cells_hold_bounded_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
-                                        const int* thresholds, int nt, int hold, int max_hold, int min_edges, int ratio_num, int ratio_den,
-                                        int min_frames, int max_frames, void* d_state, int64_t fed, int flush, int32_t* d_totals,
-                                        int32_t* d_cell_counts, int count_rows, void* stream) {
-    const int ih = y1 - y0 - 2, iw = x1 - x0 - 2;
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
-    const CellRule rule = {min_edges, ratio_num, ratio_den, min_frames, max_frames};
-    CellThresholds th = {};
-    for (int q = 0; q < nt; ++q) th.t[q] = thresholds[q];
-    const dim3 grid((iw + 63) / 64, (ih + FC_ROWS - 1) / FC_ROWS), block(FC_WAVES * 64);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const CellsHoldBoundedLayout l = cells_hold_bounded_layout(ih, iw, nt, max_hold);
+                                        const int* thresholds, int nt, int hold, int max_hold, const CellRule& rule, void* d_state,
+                                        int64_t fed, int flush, int32_t* d_totals, int32_t* d_cell_counts, int count_rows, void* stream) {
+    const CellsLaunch l(d_bgr, pitch, y0, y1, x0, x1, thresholds, nt, stream);
+    const CellsHoldBoundedLayout lay = cells_hold_bounded_layout(l.ih, l.iw, nt, max_hold);
     char* base = reinterpret_cast<char*>(d_state);
     unsigned short* pix = reinterpret_cast<unsigned short*>(base);
-    unsigned* ring = reinterpret_cast<unsigned*>(base + l.pix_bytes);
-    int* carry = reinterpret_cast<int*>(base + l.pix_bytes + l.ring_bytes);
-    int* open_runs = reinterpret_cast<int*>(base + l.pix_bytes + l.ring_bytes + l.per_cell_bytes);
-    if (fed == 0 && hipMemsetAsync(ring, 0, l.ring_bytes + 2 * l.per_cell_bytes, st) != hipSuccess) return VSE_E_HIP;
+    unsigned* ring = reinterpret_cast<unsigned*>(base + lay.pix_bytes);
+    int* carry = reinterpret_cast<int*>(base + lay.pix_bytes + lay.ring_bytes);
+    int* open_runs = reinterpret_cast<int*>(base + lay.pix_bytes + lay.ring_bytes + lay.per_cell_bytes);
+    if (fed == 0 && hipMemsetAsync(ring, 0, lay.ring_bytes + 2 * lay.per_cell_bytes, l.st) != hipSuccess) return VSE_E_HIP;
     const int ring_slots = max_hold + FC_CHUNK;
     const int64_t first = fed > max_hold ? fed - max_hold : 0;         // rows up to this frame went out with earlier calls
     const int steps = n + (flush ? 1 : 0);
-    int* totals = reinterpret_cast<int*>(d_totals);
-    int* cell_counts = reinterpret_cast<int*>(d_cell_counts);
-#define VSE_CELLS_HOLD_BOUNDED(NT)                                                                                                       \
-    case NT:                                                                                                                             \
-        hipLaunchKernelGGL(frame_cells_hold_bounded_kernel<NT>, grid, block, 0, st, src, n, steps, (long)pitch, (long)frame_stride, x0, ih, iw, \
-                           th, rule, hold, max_hold, ring_slots, (int)((first + 1) % ring_slots), (int)(fed - first), pix, ring, carry,    \
-                           open_runs, fed == 0, flush, totals, cell_counts, count_rows);                                                 \
-        break;
-    switch (nt) {
-        VSE_CELLS_HOLD_BOUNDED(1) VSE_CELLS_HOLD_BOUNDED(2) VSE_CELLS_HOLD_BOUNDED(3) VSE_CELLS_HOLD_BOUNDED(4)
-        VSE_CELLS_HOLD_BOUNDED(5) VSE_CELLS_HOLD_BOUNDED(6) VSE_CELLS_HOLD_BOUNDED(7) VSE_CELLS_HOLD_BOUNDED(8)
-        default: return VSE_E_INVAL;
-    }
-#undef VSE_CELLS_HOLD_BOUNDED
-    static_assert(FC_WAVES == 8, "one instantiation per number of thresholds");
-    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+    return launch_for_nt(nt, [&](auto nt_c) {
+        hipLaunchKernelGGL(frame_cells_hold_bounded_kernel<decltype(nt_c)::value>, l.grid, l.block, 0, l.st, l.src, n, steps, (long)pitch,
+                           (long)frame_stride, x0, l.ih, l.iw, l.th, rule, hold, max_hold, ring_slots, (int)((first + 1) % ring_slots),
+                           (int)(fed - first), pix, ring, carry, open_runs, fed == 0, flush, reinterpret_cast<int*>(d_totals),
+                           reinterpret_cast<int*>(d_cell_counts), count_rows);
+    });
 }

@@ -58,19 +58,19 @@ int vse_frame_focus_launch(const void* d_bgr, int n, int64_t pitch, int64_t fram
                            void* d_state, int reset, int32_t* d_focus, void* stream);      // frame_change.hip
 int vse_frame_cells_state_words();                                                                                     // frame_change.hip
 int vse_frame_cells_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
-                           int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames, void* d_state, int reset, int flush,
-                           int32_t* d_totals, int32_t* d_cell_counts, void* stream);                                    // frame_change.hip
+                           const CellRule& rule, void* d_state, int reset, int flush, int32_t* d_totals, int32_t* d_cell_counts,
+                           void* stream);                                                                               // frame_change.hip
 int vse_frame_cells_multi_max();                                                                                       // frame_change.hip
 int vse_frame_cells_multi_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
-                                 const int* thresholds, int nt, int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
-                                 void* d_state, int reset, int flush, int32_t* d_totals, void* stream);
+                                 const int* thresholds, int nt, const CellRule& rule, void* d_state, int reset, int flush,
+                                 int32_t* d_totals, void* stream);                                                      // frame_change.hip
 int vse_frame_cells_counts_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
-                                  const int* thresholds, int nt, int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
-                                  void* d_state, int reset, int flush, int32_t* d_totals, int32_t* d_counts, void* stream);   // frame_change.hip
+                                  const int* thresholds, int nt, const CellRule& rule, void* d_state, int reset, int flush,
+                                  int32_t* d_totals, int32_t* d_counts, void* stream);                                  // frame_change.hip
 int vse_frame_cells_export_launch(const void* d_cells_state, int area_h, int area_w, int q, void* d_change_state, void* stream);   // frame_change.hip
 int vse_frame_cells_masks_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
-                                 const int* thresholds, int nt, int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
-                                 void* d_state, int reset, int flush, int32_t* d_totals, void* d_masks, int slot0, void* stream);   // frame_change.hip
+                                 const int* thresholds, int nt, const CellRule& rule, void* d_state, int reset, int flush,
+                                 int32_t* d_totals, void* d_masks, int slot0, void* stream);                            // frame_change.hip
 int vse_frame_masks_replay_launch(const void* d_masks, int area_h, int area_w, int nt, int q, int f0, int f1, int ry0, int ry1, int rx0,
                                   int rx1, int reset, int32_t* d_counts, void* d_change_state, void* stream);   // frame_change.hip
 size_t vse_frame_hold_word_bytes();                                                                                    // frame_change.hip
@@ -81,14 +81,13 @@ int vse_frame_hold_bounded_launch(const void* d_bgr, int n, int64_t pitch, int64
                                   int hold, int max_hold, void* d_state, int64_t fed, int flush, int32_t* d_counts, void* stream);
 size_t vse_frame_cells_hold_bytes(int ih, int iw, int nt);                                                               // frame_change.hip
 int vse_frame_cells_hold_launch(const void* d_bgr, int n, int steps, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
-                                const int* thresholds, int nt, int hold, int skip, int min_edges, int ratio_num, int ratio_den, int min_frames,
-                                int max_frames, void* d_state, int fresh, int flush, int32_t* d_totals, int32_t* d_cell_counts, int count_rows,
-                                void* stream);                                                                         // frame_change.hip
+                                const int* thresholds, int nt, int hold, int skip, const CellRule& rule, void* d_state, int fresh, int flush,
+                                int32_t* d_totals, int32_t* d_cell_counts, int count_rows, void* stream);               // frame_change.hip
 size_t vse_frame_cells_hold_bounded_bytes(int ih, int iw, int nt, int max_hold);                                        // frame_change.hip
 int vse_frame_cells_hold_bounded_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
-                                        const int* thresholds, int nt, int hold, int max_hold, int min_edges, int ratio_num, int ratio_den,
-                                        int min_frames, int max_frames, void* d_state, int64_t fed, int flush, int32_t* d_totals,
-                                        int32_t* d_cell_counts, int count_rows, void* stream);                         // frame_change.hip
+                                        const int* thresholds, int nt, int hold, int max_hold, const CellRule& rule, void* d_state,
+                                        int64_t fed, int flush, int32_t* d_totals, int32_t* d_cell_counts, int count_rows,
+                                        void* stream);                                                                 // frame_change.hip
 int vse_scene_change_plane_pitch(int aw);                                                                              // scene_cut.hip
 int vse_scene_change_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int scale, int ah, int aw, int search, int bias,
                             void* d_state, int reset, void* d_ws, int32_t* d_counts, void* stream);
@@ -499,6 +498,42 @@ static bool check_rule(const char* who, int ratio_num, int ratio_den, int min_fr
     return false;
 }
 
+// the edge thresholds of the entry points that take several: 1 .. vse_frame_cells_multi_max() of them, each 1..255, ascending
+static bool check_thresholds(const char* who, const int* thresholds, int nt) {
+    if (!thresholds || nt < 1 || nt > vse_frame_cells_multi_max()) {
+        set_err("%s: %d thresholds (1..%d, not NULL)", who, nt, vse_frame_cells_multi_max());
+        return false;
+    }
+    for (int q = 0; q < nt; ++q) {
+        if (thresholds[q] < 1 || thresholds[q] > 255 || (q && thresholds[q] <= thresholds[q - 1])) {
+            set_err("%s: threshold %d of %d is %d (each 1..255, ascending and distinct)", who, q, nt, thresholds[q]);
+            return false;
+        }
+    }
+    return true;
+}
+
+constexpr int FRAME_HOLD_BOUNDED_MAX = 4000;       // the per-pixel run length is a uint16 and the ring of pending rows stays small
+
+// the frames an edge pixel must hold still, and with bounded runs the most it may
+static bool check_hold(const char* who, int hold) {
+    if (hold >= 1 && hold <= 32) return true;
+    set_err("%s: hold %d outside 1..32", who, hold);
+    return false;
+}
+
+static bool check_hold_bounded(const char* who, int hold, int max_hold) {
+    if (hold >= 1 && hold <= 32 && max_hold >= hold && max_hold <= FRAME_HOLD_BOUNDED_MAX) return true;
+    set_err("%s: hold %d outside 1..32, or max_hold %d outside hold..%d", who, hold, max_hold, FRAME_HOLD_BOUNDED_MAX);
+    return false;
+}
+
+// the end of an entry point: rc of its launcher, with the error text set where the launch failed
+static int launched(const char* who, int rc) {
+    if (rc != VSE_OK) set_err("%s: launch failed: %s", who, hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
 // ---- subtitle-change frame selector (frame_change.hip) ---------------------------------------------------------------------
 size_t vse_frame_change_state_bytes(int area_h, int area_w) {
     if (area_h < 3 || area_w < 3) return 0;
@@ -549,10 +584,8 @@ int vse_frame_cells(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, 
         !check_rule("vse_frame_cells", ratio_num, ratio_den, min_frames, max_frames))
         return VSE_E_INVAL;
     if (n == 0 && !reset && !flush) return VSE_OK;
-    const int rc = vse_frame_cells_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, min_edges, ratio_num, ratio_den,
-                                          min_frames, max_frames, d_state, reset, flush, d_totals, d_cell_counts, stream);
-    if (rc != VSE_OK) set_err("vse_frame_cells: launch failed: %s", hipGetErrorString(hipGetLastError()));
-    return rc;
+    return launched("vse_frame_cells", vse_frame_cells_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, edge_thresh,
+                    {min_edges, ratio_num, ratio_den, min_frames, max_frames}, d_state, reset, flush, d_totals, d_cell_counts, stream));
 }
 
 // ---- edge-threshold calibration: the locator's cells at several thresholds in one pass (frame_change.hip) ---------------------------
@@ -568,21 +601,10 @@ int vse_frame_cells_multi(vse_ctx* c, const void* d_bgr, int n, int src_h, int s
         !check_area("vse_frame_cells_multi", "region", y0, y1, x0, x1, src_h, src_w) ||
         !check_rule("vse_frame_cells_multi", ratio_num, ratio_den, min_frames, max_frames))
         return VSE_E_INVAL;
-    if (!thresholds || nt < 1 || nt > vse_frame_cells_multi_max()) {
-        set_err("vse_frame_cells_multi: %d thresholds (1..%d, not NULL)", nt, vse_frame_cells_multi_max());
-        return VSE_E_INVAL;
-    }
-    for (int q = 0; q < nt; ++q) {
-        if (thresholds[q] < 1 || thresholds[q] > 255 || (q && thresholds[q] <= thresholds[q - 1])) {
-            set_err("vse_frame_cells_multi: threshold %d of %d is %d (each 1..255, ascending and distinct)", q, nt, thresholds[q]);
-            return VSE_E_INVAL;
-        }
-    }
+    if (!check_thresholds("vse_frame_cells_multi", thresholds, nt)) return VSE_E_INVAL;
     if (n == 0 && !reset && !flush) return VSE_OK;
-    const int rc = vse_frame_cells_multi_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, thresholds, nt, min_edges, ratio_num,
-                                                ratio_den, min_frames, max_frames, d_state, reset, flush, d_totals, stream);
-    if (rc != VSE_OK) set_err("vse_frame_cells_multi: launch failed: %s", hipGetErrorString(hipGetLastError()));
-    return rc;
+    return launched("vse_frame_cells_multi", vse_frame_cells_multi_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, thresholds, nt,
+                    {min_edges, ratio_num, ratio_den, min_frames, max_frames}, d_state, reset, flush, d_totals, stream));
 }
 
 // ---- calibration and selector counts in one pass (frame_change.hip) -------------------------------------------------------------------
@@ -594,21 +616,10 @@ int vse_frame_cells_counts(vse_ctx* c, const void* d_bgr, int n, int src_h, int 
         !check_area("vse_frame_cells_counts", "region", y0, y1, x0, x1, src_h, src_w) ||
         !check_rule("vse_frame_cells_counts", ratio_num, ratio_den, min_frames, max_frames))
         return VSE_E_INVAL;
-    if (!thresholds || nt < 1 || nt > vse_frame_cells_multi_max()) {
-        set_err("vse_frame_cells_counts: %d thresholds (1..%d, not NULL)", nt, vse_frame_cells_multi_max());
-        return VSE_E_INVAL;
-    }
-    for (int q = 0; q < nt; ++q) {
-        if (thresholds[q] < 1 || thresholds[q] > 255 || (q && thresholds[q] <= thresholds[q - 1])) {
-            set_err("vse_frame_cells_counts: threshold %d of %d is %d (each 1..255, ascending and distinct)", q, nt, thresholds[q]);
-            return VSE_E_INVAL;
-        }
-    }
+    if (!check_thresholds("vse_frame_cells_counts", thresholds, nt)) return VSE_E_INVAL;
     if (n == 0 && !reset && !flush) return VSE_OK;
-    const int rc = vse_frame_cells_counts_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, thresholds, nt, min_edges, ratio_num,
-                                                 ratio_den, min_frames, max_frames, d_state, reset, flush, d_totals, d_counts, stream);
-    if (rc != VSE_OK) set_err("vse_frame_cells_counts: launch failed: %s", hipGetErrorString(hipGetLastError()));
-    return rc;
+    return launched("vse_frame_cells_counts", vse_frame_cells_counts_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, thresholds, nt,
+                    {min_edges, ratio_num, ratio_den, min_frames, max_frames}, d_state, reset, flush, d_totals, d_counts, stream));
 }
 
 int vse_frame_cells_export_state(vse_ctx* c, const void* d_cells_state, int area_h, int area_w, int nt, int q, void* d_change_state,
@@ -619,9 +630,7 @@ int vse_frame_cells_export_state(vse_ctx* c, const void* d_cells_state, int area
                 "8-byte aligned, no NULL pointer)", area_h, area_w, q, nt, vse_frame_cells_multi_max());
         return VSE_E_INVAL;
     }
-    const int rc = vse_frame_cells_export_launch(d_cells_state, area_h, area_w, q, d_change_state, stream);
-    if (rc != VSE_OK) set_err("vse_frame_cells_export_state: launch failed: %s", hipGetErrorString(hipGetLastError()));
-    return rc;
+    return launched("vse_frame_cells_export_state", vse_frame_cells_export_launch(d_cells_state, area_h, area_w, q, d_change_state, stream));
 }
 
 // ---- the locator's masks kept for a rectangle decided later (frame_change.hip) ------------------------------------------------------
@@ -640,25 +649,14 @@ int vse_frame_cells_masks(vse_ctx* c, const void* d_bgr, int n, int src_h, int s
         !check_area("vse_frame_cells_masks", "region", y0, y1, x0, x1, src_h, src_w) ||
         !check_rule("vse_frame_cells_masks", ratio_num, ratio_den, min_frames, max_frames))
         return VSE_E_INVAL;
-    if (!thresholds || nt < 1 || nt > vse_frame_cells_multi_max()) {
-        set_err("vse_frame_cells_masks: %d thresholds (1..%d, not NULL)", nt, vse_frame_cells_multi_max());
-        return VSE_E_INVAL;
-    }
-    for (int q = 0; q < nt; ++q) {
-        if (thresholds[q] < 1 || thresholds[q] > 255 || (q && thresholds[q] <= thresholds[q - 1])) {
-            set_err("vse_frame_cells_masks: threshold %d of %d is %d (each 1..255, ascending and distinct)", q, nt, thresholds[q]);
-            return VSE_E_INVAL;
-        }
-    }
+    if (!check_thresholds("vse_frame_cells_masks", thresholds, nt)) return VSE_E_INVAL;
     if (cap < 1 || slot0 < 0 || (int64_t)slot0 + n > cap) {
         set_err("vse_frame_cells_masks: %d frames from slot %d on do not fit a mask buffer of %d slots (no wrap)", n, slot0, cap);
         return VSE_E_INVAL;
     }
     if (n == 0 && !reset && !flush) return VSE_OK;
-    const int rc = vse_frame_cells_masks_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, thresholds, nt, min_edges, ratio_num,
-                                                ratio_den, min_frames, max_frames, d_state, reset, flush, d_totals, d_masks, slot0, stream);
-    if (rc != VSE_OK) set_err("vse_frame_cells_masks: launch failed: %s", hipGetErrorString(hipGetLastError()));
-    return rc;
+    return launched("vse_frame_cells_masks", vse_frame_cells_masks_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, thresholds, nt,
+                    {min_edges, ratio_num, ratio_den, min_frames, max_frames}, d_state, reset, flush, d_totals, d_masks, slot0, stream));
 }
 
 int vse_frame_masks_replay(vse_ctx* c, const void* d_masks, int area_h, int area_w, int nt, int cap, int q, int f0, int f1, int ry0,
@@ -680,10 +678,8 @@ int vse_frame_masks_replay(vse_ctx* c, const void* d_masks, int area_h, int area
                 area_h, area_w);
         return VSE_E_INVAL;
     }
-    const int rc = vse_frame_masks_replay_launch(d_masks, area_h, area_w, nt, q, f0, f1, ry0, ry1, rx0, rx1, reset, d_counts,
-                                                 d_change_state, stream);
-    if (rc != VSE_OK) set_err("vse_frame_masks_replay: launch failed: %s", hipGetErrorString(hipGetLastError()));
-    return rc;
+    return launched("vse_frame_masks_replay", vse_frame_masks_replay_launch(d_masks, area_h, area_w, nt, q, f0, f1, ry0, ry1, rx0, rx1, reset,
+                    d_counts, d_change_state, stream));
 }
 
 // ---- held-edge frame selector (frame_change.hip) ------------------------------------------------------------------------------
@@ -697,10 +693,7 @@ int vse_frame_hold(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, i
     if (!check_frames("vse_frame_hold", c && fed >= 0, d_bgr, n, 0, src_h, src_w, pitch, frame_stride, d_state) ||
         !check_area("vse_frame_hold", "area", y0, y1, x0, x1, src_h, src_w))
         return VSE_E_INVAL;
-    if (hold < 1 || hold > 32) {
-        set_err("vse_frame_hold: hold %d outside 1..32", hold);
-        return VSE_E_INVAL;
-    }
+    if (!check_hold("vse_frame_hold", hold)) return VSE_E_INVAL;
     // the mask of a frame is known hold - 1 frames later: a flush feeds that many frames without an edge, and the first
     // hold - 1 steps of a clip belong to no frame
     const int64_t steps = (int64_t)n + (flush ? hold - 1 : 0);
@@ -710,15 +703,11 @@ int vse_frame_hold(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, i
         set_err("vse_frame_hold: %lld steps need d_counts and must fit an int", (long long)steps);
         return VSE_E_INVAL;
     }
-    const int rc = vse_frame_hold_launch(d_bgr, n, (int)steps, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, hold, skip, d_state,
-                                         fed == 0, d_counts, stream);
-    if (rc != VSE_OK) set_err("vse_frame_hold: launch failed: %s", hipGetErrorString(hipGetLastError()));
-    return rc;
+    return launched("vse_frame_hold", vse_frame_hold_launch(d_bgr, n, (int)steps, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, hold, skip,
+                    d_state, fed == 0, d_counts, stream));
 }
 
 // ---- held-edge frame selector with bounded runs (frame_change.hip) -------------------------------------------------------------
-constexpr int FRAME_HOLD_BOUNDED_MAX = 4000;       // the per-pixel run length is a uint16 and the ring of pending rows stays small
-
 size_t vse_frame_hold_bounded_state_bytes(int area_h, int area_w, int max_hold) {
     if (area_h < 3 || area_w < 3 || max_hold < 1 || max_hold > FRAME_HOLD_BOUNDED_MAX) return 0;
     return vse_frame_hold_bounded_bytes(area_h - 2, area_w - 2, max_hold);
@@ -730,10 +719,7 @@ int vse_frame_hold_bounded(vse_ctx* c, const void* d_bgr, int n, int src_h, int 
     if (!check_frames("vse_frame_hold_bounded", c && fed >= 0, d_bgr, n, 0, src_h, src_w, pitch, frame_stride, d_state) ||
         !check_area("vse_frame_hold_bounded", "area", y0, y1, x0, x1, src_h, src_w))
         return VSE_E_INVAL;
-    if (hold < 1 || hold > 32 || max_hold < hold || max_hold > FRAME_HOLD_BOUNDED_MAX) {
-        set_err("vse_frame_hold_bounded: hold %d outside 1..32, or max_hold %d outside hold..%d", hold, max_hold, FRAME_HOLD_BOUNDED_MAX);
-        return VSE_E_INVAL;
-    }
+    if (!check_hold_bounded("vse_frame_hold_bounded", hold, max_hold)) return VSE_E_INVAL;
     if (n == 0 && !flush) return VSE_OK;
     // the row of a frame is final max_hold frames later, or at the flush
     const int64_t rows = (flush ? fed + n : std::max<int64_t>(0, fed + n - max_hold)) - std::max<int64_t>(0, fed - max_hold);
@@ -741,10 +727,8 @@ int vse_frame_hold_bounded(vse_ctx* c, const void* d_bgr, int n, int src_h, int 
         set_err("vse_frame_hold_bounded: %lld rows need d_counts, and n + 1 must fit an int", (long long)rows);
         return VSE_E_INVAL;
     }
-    const int rc = vse_frame_hold_bounded_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, hold, max_hold, d_state, fed,
-                                                 flush != 0, d_counts, stream);
-    if (rc != VSE_OK) set_err("vse_frame_hold_bounded: launch failed: %s", hipGetErrorString(hipGetLastError()));
-    return rc;
+    return launched("vse_frame_hold_bounded", vse_frame_hold_bounded_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, edge_thresh, hold,
+                    max_hold, d_state, fed, flush != 0, d_counts, stream));
 }
 
 // ---- locator and calibration on held edges (frame_change.hip) -------------------------------------------------------------------
@@ -761,20 +745,8 @@ int vse_frame_cells_hold(vse_ctx* c, const void* d_bgr, int n, int src_h, int sr
         !check_area("vse_frame_cells_hold", "region", y0, y1, x0, x1, src_h, src_w) ||
         !check_rule("vse_frame_cells_hold", ratio_num, ratio_den, min_frames, max_frames))
         return VSE_E_INVAL;
-    if (!thresholds || nt < 1 || nt > vse_frame_cells_multi_max()) {
-        set_err("vse_frame_cells_hold: %d thresholds (1..%d, not NULL)", nt, vse_frame_cells_multi_max());
-        return VSE_E_INVAL;
-    }
-    for (int q = 0; q < nt; ++q) {
-        if (thresholds[q] < 1 || thresholds[q] > 255 || (q && thresholds[q] <= thresholds[q - 1])) {
-            set_err("vse_frame_cells_hold: threshold %d of %d is %d (each 1..255, ascending and distinct)", q, nt, thresholds[q]);
-            return VSE_E_INVAL;
-        }
-    }
-    if (hold < 1 || hold > 32) {
-        set_err("vse_frame_cells_hold: hold %d outside 1..32", hold);
-        return VSE_E_INVAL;
-    }
+    if (!check_thresholds("vse_frame_cells_hold", thresholds, nt)) return VSE_E_INVAL;
+    if (!check_hold("vse_frame_cells_hold", hold)) return VSE_E_INVAL;
     // as vse_frame_hold: the held mask of a frame is known hold - 1 frames later, a flush feeds that many frames without an edge, and
     // the first hold - 1 steps of a clip belong to no frame
     const int64_t steps = (int64_t)n + (flush ? hold - 1 : 0);
@@ -784,11 +756,9 @@ int vse_frame_cells_hold(vse_ctx* c, const void* d_bgr, int n, int src_h, int sr
         return VSE_E_INVAL;
     }
     if (n == 0 && !flush) return VSE_OK;
-    const int rc = vse_frame_cells_hold_launch(d_bgr, n, (int)steps, pitch, frame_stride, y0, y1, x0, x1, thresholds, nt, hold, skip, min_edges,
-                                               ratio_num, ratio_den, min_frames, max_frames, d_state, fed == 0, flush != 0, d_totals,
-                                               d_cell_counts, n + hold - 1, stream);
-    if (rc != VSE_OK) set_err("vse_frame_cells_hold: launch failed: %s", hipGetErrorString(hipGetLastError()));
-    return rc;
+    return launched("vse_frame_cells_hold", vse_frame_cells_hold_launch(d_bgr, n, (int)steps, pitch, frame_stride, y0, y1, x0, x1, thresholds, nt,
+                    hold, skip, {min_edges, ratio_num, ratio_den, min_frames, max_frames}, d_state, fed == 0, flush != 0, d_totals, d_cell_counts,
+                    n + hold - 1, stream));
 }
 
 // ---- locator and calibration on bounded runs (frame_change.hip) -----------------------------------------------------------------
@@ -805,31 +775,17 @@ int vse_frame_cells_hold_bounded(vse_ctx* c, const void* d_bgr, int n, int src_h
         !check_area("vse_frame_cells_hold_bounded", "region", y0, y1, x0, x1, src_h, src_w) ||
         !check_rule("vse_frame_cells_hold_bounded", ratio_num, ratio_den, min_frames, max_frames))
         return VSE_E_INVAL;
-    if (!thresholds || nt < 1 || nt > vse_frame_cells_multi_max()) {
-        set_err("vse_frame_cells_hold_bounded: %d thresholds (1..%d, not NULL)", nt, vse_frame_cells_multi_max());
-        return VSE_E_INVAL;
-    }
-    for (int q = 0; q < nt; ++q) {
-        if (thresholds[q] < 1 || thresholds[q] > 255 || (q && thresholds[q] <= thresholds[q - 1])) {
-            set_err("vse_frame_cells_hold_bounded: threshold %d of %d is %d (each 1..255, ascending and distinct)", q, nt, thresholds[q]);
-            return VSE_E_INVAL;
-        }
-    }
-    if (hold < 1 || hold > 32 || max_hold < hold || max_hold > FRAME_HOLD_BOUNDED_MAX) {
-        set_err("vse_frame_cells_hold_bounded: hold %d outside 1..32, or max_hold %d outside hold..%d", hold, max_hold, FRAME_HOLD_BOUNDED_MAX);
-        return VSE_E_INVAL;
-    }
+    if (!check_thresholds("vse_frame_cells_hold_bounded", thresholds, nt)) return VSE_E_INVAL;
+    if (!check_hold_bounded("vse_frame_cells_hold_bounded", hold, max_hold)) return VSE_E_INVAL;
     // as vse_frame_hold_bounded: the row of a frame is final max_hold frames later, or at the flush, which is one step of its own
     if ((int64_t)n + max_hold > INT32_MAX) {
         set_err("vse_frame_cells_hold_bounded: %lld rows do not fit an int", (long long)n + max_hold);
         return VSE_E_INVAL;
     }
     if (n == 0 && !flush) return VSE_OK;
-    const int rc = vse_frame_cells_hold_bounded_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, thresholds, nt, hold, max_hold, min_edges,
-                                                       ratio_num, ratio_den, min_frames, max_frames, d_state, fed, flush != 0, d_totals,
-                                                       d_cell_counts, n + max_hold, stream);
-    if (rc != VSE_OK) set_err("vse_frame_cells_hold_bounded: launch failed: %s", hipGetErrorString(hipGetLastError()));
-    return rc;
+    return launched("vse_frame_cells_hold_bounded", vse_frame_cells_hold_bounded_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, thresholds,
+                    nt, hold, max_hold, {min_edges, ratio_num, ratio_den, min_frames, max_frames}, d_state, fed, flush != 0, d_totals,
+                    d_cell_counts, n + max_hold, stream));
 }
 
 // ---- timeline sync: scene cuts for keyframe snapping (scene_cut.hip) ---------------------------------------------------------
