@@ -87,6 +87,16 @@ def test_bit_for_bit_with_sentinels(ctx, fmt):
                 assert woven == 0 and inter > 0                      # no picture is compared: everything is interpolated
 
 
+def test_small_planes_and_a_base_two_bytes_in(ctx):
+    """Two frames each: 10-bit semi-planar high-bit words, 5 x 8, from a base 2 bytes into the buffer (one sample: the planes' offsets
+    keep that shift); grey, one plane, 3 x 5 and a single row."""
+    rng = np.random.default_rng(58)
+    for fmt, h, w, variant in (((1, 1, 2, 10, 1, 2, 0), 5, 8, ("base + 2 bytes", 2, "chain", 0, 1)), ((0, 0, 0, 8, 0, 0, 0), 3, 5, ("chained", 2, "chain", 0, 0)),
+                               ((0, 0, 0, 8, 0, 0, 0), 1, 5, ("chained", 2, "chain", 0, 0))):
+        for keep, mode in ((0, 0), (1, 0), (1, 1)):
+            run_variant(ctx, rng, fmt, h, w, variant, keep, mode)
+
+
 def test_random_words_and_every_threshold_edge(ctx):
     """Unrelated random pictures (nearly everything moved), identical ones (nothing moved), and thresholds 0 and 255."""
     import torch

@@ -132,6 +132,13 @@ def test_counts_add_up_over_blocks(ctx, fmt, h, w):
         run_case(ctx, case)
 
 
+def test_one_call_makes_both_weave_launches(ctx):
+    """8-bit 4:2:0 planar, 6 x 48, two frames: the 48-byte luma rows take the 16-byte weave, the 24-byte chroma rows the quads."""
+    rng = np.random.default_rng(648)
+    for keep, kind in ((0, "film"), (1, "film"), (0, "video")):
+        run_case(ctx, build_case(rng, (1, 1, 1, 8, 0, 0, 0), 6, 48, ("chained", 2, "chain", 0, 0), keep, kind))
+
+
 def test_threshold_edges_and_limits(ctx):
     """Rows that alternate between b and b + d with d = T in some columns and T + 1 in others, at comb_thresh 0 and 255 (at 8 bits T + 1 =
     256 does not exist: nothing combs), under comb_limit 0 (one combed sample falls back), 1000 (nothing can) and < 0 (never)."""

@@ -81,6 +81,13 @@ def test_bit_for_bit_with_sentinels(ctx, fmt):
     assert seen_y == seen_c == set(TAPS) and low > 100 and high > 100 and off_left > 20 and off_right > 20, (low, high, off_left, off_right)
 
 
+@pytest.mark.parametrize("fmt", [f for f in FORMATS if f[1] == 1], ids=ident)
+def test_three_rows_of_odd_parity(ctx, fmt):
+    """4:2:0 rows 1..3 of their picture (two chroma rows for three luma rows), 10 -> 7 columns, two frames."""
+    rng = np.random.default_rng(sum(fmt) + 107)
+    run_variant(ctx, rng, fmt, 3, 10, 7, ("packed", 2, 0, 0), 1, RR.random_table(rng, 10, 7, 4), RR.random_table(rng, 5, 4, 6))
+
+
 @pytest.mark.parametrize("fmt", FORMATS, ids=ident)
 def test_identity_and_filter_tables(ctx, fmt):
     """The identity table gives the input bytes (valid samples: the low bits of a high-bit word are zero); ingest.Resample's own tables,

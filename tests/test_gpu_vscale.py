@@ -109,6 +109,15 @@ def test_bit_for_bit_with_sentinels(ctx, fmt):
     assert stats.band > 20 and banded > 10 and parities == {(0, 0), (0, 1), (1, 0), (1, 1)}, (vars(stats), banded, parities)
 
 
+@pytest.mark.parametrize("fmt", [f for f in FORMATS if f[1] == 1], ids=ident)
+def test_bands_of_odd_parity_on_both_sides(ctx, fmt):
+    """4:2:0, 8 -> 6 rows, two frames: stored rows 1:7 in and output rows 1:5 out both begin on an odd row, so each band has one chroma
+    row more than half its luma rows.  Straight through the library: the band need not cover the support, the clamp to it is the rule."""
+    rng = np.random.default_rng(sum(fmt) + 86)
+    luma, chroma = random_tables(rng, fmt, 8, 6, 4, 2)
+    run_variant(ctx, rng, fmt, 10, 8, 6, ("packed", 2, 0, 0), luma, chroma, (1, 5), (1, 7), direct=True)
+
+
 @pytest.mark.parametrize("fmt", FORMATS, ids=ident)
 def test_identity_and_filter_tables(ctx, fmt):
     """The identity table gives the input bytes (valid samples: the low bits of a high-bit word are zero); ingest.VScale's own tables,

@@ -102,9 +102,12 @@
 //            load per tap and one store
 //   general  any width, pitch and byte alignment: the run is four samples through load_quad / store_quad
 #include <algorithm>
+#include <cstdarg>
 #include <cstdio>
+#include <type_traits>
 
 #include "common.h"
+#include "yuv_planes.h"
 
 void vse_set_error(const char* msg);      // vse_runtime.hip
 
@@ -114,7 +117,6 @@ constexpr int YUV_I420 = 0, YUV_NV12 = 1;
 constexpr int BT601 = 0, BT709 = 1;
 constexpr int FAST_THREADS = 256, FAST_MAX_BLOCKS = 2048;
 constexpr int GEN_LANES = 64, GEN_ROWS = 4;        // block of the general kernel: 64 pixel groups x 4 rows
-constexpr long MAX_PIXELS = 0x7fffffffL;           // per frame: the per-frame work-item index stays an int
 
 struct ChromaTerms {
     int b, g, r;      // the chroma part of each channel's sum, rounding constant included
@@ -253,8 +255,6 @@ __global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void yuv420_general_kernel(co
 }
 
 // ---- any format (vse_yuv_to_bgr_format) -----------------------------------------------------------------------------------------
-constexpr int CHROMA_NONE = 0, CHROMA_PLANAR = 1, CHROMA_SEMI = 2;
-
 struct YuvParams {
     int shift, maxv;              // sample = min(word >> shift, maxv)
     int yoff, coff;               // 16 << s (0: full range), 128 << s
@@ -475,96 +475,6 @@ __global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void yuv_general_kernel(const
                 for (int k = 0; k < 3 * npx; ++k) op[k] = (uint8_t)(o[k >> 2] >> (8 * (k & 3)));
             }
         }
-    }
-}
-
-// {KY, BU, GU, GV, RV}_0 of [full_range][matrix]
-constexpr int YUV_K0[2][3][5] = {{{1220542, 2116026, -409993, -852492, 1673527},
-                                  {1220542, 2215014, -223607, -558796, 1879825},
-                                  {1220542, 2245811, -196426, -682019, 1760217}},
-                                 {{1 << 20, 1858077, -360853, -748826, 1470104},
-                                  {1 << 20, 1945738, -196424, -490864, 1651297},
-                                  {1 << 20, 1972791, -172546, -599107, 1546230}}};
-
-int scaled_factor(int k0, int s) {
-    const int m = ((k0 < 0 ? -k0 : k0) + ((1 << s) >> 1)) >> s;
-    return k0 < 0 ? -m : m;
-}
-
-bool format_ok(int sub_x, int sub_y, int chroma, int depth) {
-    const bool sub = (sub_x == 0 && sub_y == 0) || (sub_x == 1 && sub_y == 0) || (sub_x == 1 && sub_y == 1);
-    return sub && chroma >= CHROMA_NONE && chroma <= CHROMA_SEMI && depth >= 8 && depth <= 16 && (chroma != CHROMA_NONE || sub_x + sub_y == 0) &&
-           (chroma != CHROMA_SEMI || sub_x + sub_y == 2);
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-YuvParams yuv_params(int depth, int msb, int matrix, int full_range) {
-    const int s = depth - 8;
-    const int* k0 = YUV_K0[full_range][matrix];
-    YuvParams p;
-    p.shift = msb ? 16 - depth : 0;
-    p.maxv = (1 << depth) - 1;
-    p.yoff = full_range ? 0 : 16 << s;
-    p.coff = 128 << s;
-    p.ky = scaled_factor(k0[0], s);
-    p.bu = scaled_factor(k0[1], s);
-    p.gu = scaled_factor(k0[2], s);
-    p.gv = scaled_factor(k0[3], s);
-    p.rv = scaled_factor(k0[4], s);
-    return p;
-}
-
-// what vse_yuv_to_bgr_format and vse_yuv_to_bgr_tonemap both refuse; frame = vse_yuv_frame_bytes of the call
-bool format_call_ok(const vse_ctx* c, const void* d_yuv, int n, int h, int w, int depth, int msb, int matrix, int full_range, size_t frame,
-                    int64_t yuv_frame_stride, const void* d_bgr, int64_t pitch, int64_t bgr_frame_stride) {
-    const int ss = depth > 8 ? 2 : 1;
-    return c && d_yuv && d_bgr && n >= 1 && frame && msb >= 0 && msb <= (ss == 2 ? 1 : 0) && matrix >= 0 && matrix <= 2 && full_range >= 0 &&
-           full_range <= 1 && pitch >= (int64_t)w * 3 && yuv_frame_stride >= (int64_t)frame &&
-           bgr_frame_stride >= (int64_t)(h - 1) * pitch + (int64_t)w * 3 &&
-           !(ss == 2 && ((reinterpret_cast<uintptr_t>(d_yuv) & 1) || (yuv_frame_stride & 1)));
-}
-
-// Blocks of a tone-mapped launch: each stages the 16 128-byte table before its first pixel, so the grid is capped and blocks stride the
-// work.  Measured on 64 x 1080p / 16 x 2160p P010 (us per frame, 16-byte kernel; general kernel): 512 4.5 / 17.7; 12.4 / 43.5, 1024 3.9 /
-// 15.6; 8.6 / 29.5, 4096 3.4 / 14.1; 6.7 / 21.3, 8192 3.4 / 13.7; 5.6 / 20.8, 16384 3.4 / 13.7; 5.5 / 21.1: the copies cost less than idle
-// CUs do, and past 8192 nothing is gained.
-constexpr int TONE_MAX_BLOCKS = 8192;
-
-// The launch of an accepted call.  PlainOut: one block per 256 work items, as ever.  ToneOut: at most about TONE_MAX_BLOCKS blocks in all,
-// which stride the items, rows and frames.
-template <class OUT>
-void launch_format(const uint8_t* src, int n, int h, int w, int sub_x, int sub_y, int chroma, int ss, int row_parity, int64_t yuv_frame_stride,
-                   uint8_t* dst, int64_t pitch, int64_t bgr_frame_stride, const YuvParams& p, const typename OUT::Args& oa, hipStream_t st) {
-    constexpr bool tone = OUT::TONE;
-    const bool fast = ss == 2 && sub_x == 1 && sub_y == 1 && chroma != CHROMA_NONE && w % 16 == 0 && h % 2 == 0 && row_parity == 0 &&
-                      pitch % 16 == 0 && yuv_frame_stride % 16 == 0 && bgr_frame_stride % 16 == 0 && aligned16(src) && aligned16(dst);
-    if (fast) {
-        const long items = (long)(h / 2) * (w / 16);
-        const long gx = std::min<long>((items + FAST_THREADS - 1) / FAST_THREADS, tone ? TONE_MAX_BLOCKS : FAST_MAX_BLOCKS);
-        const long gy = tone ? std::min<long>(n, std::max<long>(TONE_MAX_BLOCKS / gx, 1)) : std::min(n, 65535);
-        const auto kernel = chroma == CHROMA_PLANAR ? yuv420_wide_fast_kernel<CHROMA_PLANAR, OUT> : yuv420_wide_fast_kernel<CHROMA_SEMI, OUT>;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)gy), dim3(FAST_THREADS), 0, st, src, n, h, w, (long)yuv_frame_stride, dst,
-                           (long)pitch, (long)bgr_frame_stride, p, oa);
-        return;
-    }
-    const long groups = ((long)w + 3) / 4;
-    long gx = (groups + GEN_LANES - 1) / GEN_LANES, gy = std::min((h + GEN_ROWS - 1) / GEN_ROWS, 65535), gz = std::min(n, 65535);
-    if (tone) {
-        gy = std::min(gy, std::max<long>(TONE_MAX_BLOCKS / gx, 1));
-        gz = std::min(gz, std::max<long>(TONE_MAX_BLOCKS / (gx * gy), 1));
-    }
-    const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)gz), block(GEN_LANES, GEN_ROWS);
-    const long sstride = (long)yuv_frame_stride / ss;          // in samples
-    if (ss == 1) {
-        const auto kernel = chroma == CHROMA_NONE ? yuv_general_kernel<uint8_t, CHROMA_NONE, OUT>
-                          : chroma == CHROMA_PLANAR ? yuv_general_kernel<uint8_t, CHROMA_PLANAR, OUT> : yuv_general_kernel<uint8_t, CHROMA_SEMI, OUT>;
-        hipLaunchKernelGGL(kernel, grid, block, 0, st, src, n, h, w, sub_x, sub_y, row_parity, sstride, dst, (long)pitch, (long)bgr_frame_stride, p, oa);
-    } else {
-        const auto kernel = chroma == CHROMA_NONE ? yuv_general_kernel<uint16_t, CHROMA_NONE, OUT>
-                          : chroma == CHROMA_PLANAR ? yuv_general_kernel<uint16_t, CHROMA_PLANAR, OUT> : yuv_general_kernel<uint16_t, CHROMA_SEMI, OUT>;
-        hipLaunchKernelGGL(kernel, grid, block, 0, st, reinterpret_cast<const uint16_t*>(src), n, h, w, sub_x, sub_y, row_parity, sstride, dst,
-                           (long)pitch, (long)bgr_frame_stride, p, oa);
     }
 }
 
@@ -1122,25 +1032,6 @@ __global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void resample_kernel(const S*
     }
 }
 
-bool resample_table_ok(int columns, int taps) { return columns >= 1 && taps >= 2 && taps <= RES_MAX_TAPS && taps % 2 == 0; }
-
-// The instantiation of an accepted call: tap pairs 1, 2, 3, 4 (what bilinear, bicubic and Lanczos-3 need up to a reduction of 4 : 3) or 8.
-template <typename S, int TP>
-auto resample_kernel_of(bool semi, bool fast) -> decltype(&resample_kernel<S, false, false, TP>) {
-    return fast ? (semi ? resample_kernel<S, true, true, TP> : resample_kernel<S, false, true, TP>)
-                : (semi ? resample_kernel<S, true, false, TP> : resample_kernel<S, false, false, TP>);
-}
-
-template <typename S>
-void launch_resample(const void* d_yuv, int n, long sstride, void* d_out, long dstride, const ResPlanes& pl, int shift, int maxv, bool semi,
-                     bool fast, int pairs, dim3 grid, dim3 block, hipStream_t st) {
-    const auto kernel = pairs <= 1 ? resample_kernel_of<S, 1>(semi, fast) : pairs == 2 ? resample_kernel_of<S, 2>(semi, fast)
-                      : pairs == 3 ? resample_kernel_of<S, 3>(semi, fast) : pairs == 4 ? resample_kernel_of<S, 4>(semi, fast)
-                      : resample_kernel_of<S, RES_MAX_TAPS / 2>(semi, fast);
-    hipLaunchKernelGGL(kernel, grid, block, 0, st, reinterpret_cast<const S*>(d_yuv), n, sstride, reinterpret_cast<S*>(d_out), dstride, pl, shift,
-                       maxv);
-}
-
 // ---- vertical scale (vse_yuv_vscale) ----------------------------------------------------------------------------------------------------
 // The planes of the packed input and output bands, in samples.  rl: samples per row (an interleaved UV row has 2 cw); ph: the rows of the
 // WHOLE input picture's plane, [b0, b1) the rows of it the input band holds, [o0, o1) the output rows to make, all in whole-picture rows
@@ -1236,39 +1127,324 @@ __global__ __launch_bounds__(GEN_LANES * GEN_ROWS) void vscale_kernel(const S* _
     }
 }
 
-// The instantiation of an accepted call: tap pairs 1, 2, 3, 4, 6 (bilinear, bicubic and Lanczos-3 down to a reduction of 2 : 1) or 8.
+// ==== host: what the entry points below share ===============================================================================================
+// ---- one copy of each argument check
+int sample_bytes(int depth) { return depth > 8 ? 2 : 1; }
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+bool msb_ok(int msb, int ss) { return msb >= 0 && msb <= (ss == 2 ? 1 : 0); }
+bool odd(const void* p, int64_t stride) { return (reinterpret_cast<uintptr_t>(p) & 1) || (stride & 1); }
+bool holds(int64_t stride, size_t frame) { return stride >= (int64_t)frame; }
+bool bgr_ok(int h, int w, int64_t pitch, int64_t bgr_frame_stride) {
+    return pitch >= (int64_t)w * 3 && bgr_frame_stride >= (int64_t)(h - 1) * pitch + (int64_t)w * 3;
+}
+bool table_ok(const void* p, size_t bytes) { return bytes && p && aligned16(p); }
+// the `bytes` at p (nullptr: nothing) do not meet [lo, hi)
+bool apart(uintptr_t lo, uintptr_t hi, const void* p, uintptr_t bytes) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    return !p || hi <= a || a + bytes <= lo;
+}
+
+// what vse_yuv_deinterlace and vse_yuv_field_match both refuse: pictures, optional previous pictures and an output of the same packing
+bool fields_call_ok(const vse_ctx* c, const void* d_yuv, const void* d_prev, const void* d_out, int n, size_t frame, int ss, int msb, int keep,
+                    int thresh, int64_t yuv_frame_stride, int64_t prev_frame_stride, int64_t out_frame_stride) {
+    return c && d_yuv && d_out && n >= 1 && frame && msb_ok(msb, ss) && keep >= 0 && keep <= 1 && thresh >= 0 && thresh <= 255 &&
+           holds(yuv_frame_stride, frame) && holds(out_frame_stride, frame) && (!d_prev || holds(prev_frame_stride, frame)) && d_out != d_yuv &&
+           d_out != d_prev &&
+           !(ss == 2 && (odd(d_yuv, yuv_frame_stride) || odd(d_out, out_frame_stride) || (d_prev && odd(d_prev, prev_frame_stride))));
+}
+
+bool resample_table_ok(int columns, int taps) { return columns >= 1 && taps >= 2 && taps <= RES_MAX_TAPS && taps % 2 == 0; }
+
+// what vse_yuv_resample and vse_yuv_vscale both refuse: pictures of frame_in bytes, an output of frame_out bytes, a luma table and, where
+// the format has chroma, a chroma table (table_y, table_c: their bytes, 0 for a table that cannot be)
+bool scaler_call_ok(const vse_ctx* c, const void* d_yuv, const void* d_out, int n, size_t frame_in, size_t frame_out, int ss, int msb,
+                    const void* d_table_y, size_t table_y, const void* d_table_c, size_t table_c, bool has_chroma, int64_t yuv_frame_stride,
+                    int64_t out_frame_stride) {
+    if (!(c && d_yuv && d_out && n >= 1 && frame_in && frame_out && msb_ok(msb, ss) && table_ok(d_table_y, table_y) &&
+          (!has_chroma || table_ok(d_table_c, table_c)) && holds(yuv_frame_stride, frame_in) && holds(out_frame_stride, frame_out) &&
+          !(ss == 2 && (odd(d_yuv, yuv_frame_stride) || odd(d_out, out_frame_stride)))))
+        return false;
+    // the output lies apart from the input pictures (first byte of the first to last byte of the last) and from both tables
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + (uintptr_t)(n - 1) * (uintptr_t)out_frame_stride + frame_out;
+    const auto clear = [&](const void* p, size_t bytes) { return !bytes || apart(o0, o1, p, bytes); };
+    return clear(d_yuv, (size_t)(n - 1) * (size_t)yuv_frame_stride + frame_in) && clear(d_table_y, table_y) &&
+           clear(has_chroma ? d_table_c : nullptr, table_c);
+}
+
+// ---- the refusal message: "<entry point>: bad arguments (n ..., " and what the caller adds, cut at `cap` bytes as one snprintf would
+class Refusal {
+    char text[1024];
+    size_t cap, len;
+
+  public:
+    Refusal(size_t cap_, const char* who, int n) : cap(cap_), len(0) { add("%s: bad arguments (n %d, ", who, n); }
+    __attribute__((format(printf, 2, 3))) Refusal& add(const char* fmt, ...) {
+        va_list ap;
+        va_start(ap, fmt);
+        const int more = vsnprintf(text + len, cap - len, fmt, ap);
+        va_end(ap);
+        len = std::min(len + (size_t)std::max(more, 0), cap - 1);
+        return *this;
+    }
+    Refusal& picture(int h, int w) { return add("frame %d x %d of at most 2^31 - 1 pixels, ", h, w); }
+    Refusal& format(int sub_x, int sub_y, int chroma, int depth, int msb) {
+        return add("subsampling %d, %d of 0, 0 | 1, 0 | 1, 1, chroma %d of 0 (with subsampling 0, 0) | 1 | 2 (with subsampling 1, 1), depth %d of "
+                   "8..16, msb %d of 0 | 1 (0 at depth 8), ", sub_x, sub_y, chroma, depth, msb);
+    }
+    // what vse_yuv_deinterlace's and vse_yuv_field_match's messages share
+    Refusal& fields(int64_t yuv_frame_stride, int64_t prev_frame_stride, int64_t out_frame_stride, size_t frame, const void* d_yuv,
+                    const void* d_prev, const void* d_out) {
+        return add("frame strides %lld, %lld (previous pictures) and %lld (output) of at least %zu, bases %p, %p, %p and strides 2-byte aligned for "
+                   "2-byte samples, the output none of the inputs", (long long)yuv_frame_stride, (long long)prev_frame_stride,
+                   (long long)out_frame_stride, frame, d_yuv, d_prev, d_out);
+    }
+    // vse_yuv_resample's and vse_yuv_vscale's, to the end
+    Refusal& scaler(int taps_y, int taps_c, const void* d_table_y, const void* d_table_c, int64_t yuv_frame_stride, size_t frame_in,
+                    int64_t out_frame_stride, size_t frame_out, const void* d_yuv, const void* d_out) {
+        return add("taps %d (luma) and %d (chroma) even and of 2..16, tables %p and %p 16-byte aligned (the chroma table only where the format has "
+                   "chroma), frame strides %lld of at least %zu and %lld (output) of at least %zu, bases %p, %p and strides 2-byte aligned for "
+                   "2-byte samples, the output apart from the pictures and the tables)", taps_y, taps_c, d_table_y, d_table_c,
+                   (long long)yuv_frame_stride, frame_in, (long long)out_frame_stride, frame_out, d_yuv, d_out);
+    }
+    int send() {
+        vse_set_error(text);
+        return VSE_E_INVAL;
+    }
+};
+
+// ---- the launches
+// blocks of FAST_THREADS lanes that stride `items` work items per frame, blockIdx.y the frames
+dim3 fast_grid(long items, int n) {
+    return dim3((unsigned)std::min<long>((items + FAST_THREADS - 1) / FAST_THREADS, FAST_MAX_BLOCKS), (unsigned)std::min(n, 65535));
+}
+
+// blocks of GEN_LANES x GEN_ROWS lanes: one lane per group of a row, blockIdx.y strides the rows (or strips of rows), blockIdx.z the frames
+dim3 general_grid(long groups, long rows, int n) {
+    return dim3((unsigned)((groups + GEN_LANES - 1) / GEN_LANES), (unsigned)std::min<long>((rows + GEN_ROWS - 1) / GEN_ROWS, 65535),
+                (unsigned)std::min(n, 65535));
+}
+
+int strips_of(int rows) { return (rows + DEINT_STRIP - 1) / DEINT_STRIP; }
+
+// The pictures of a call as a kernel on samples S takes them: typed pointers, the frame strides in samples.
 template <typename S>
-void launch_vscale(const void* d_yuv, int n, long sstride, void* d_out, long dstride, const VsPlanes& pl, int shift, int maxv, bool fast,
-                   int pairs, dim3 grid, dim3 block, hipStream_t st) {
+struct Pictures {
+    const S* src;
+    const S* prev;
+    S* dst;
+    long sstride, pstride, dstride;
+};
+
+// f(Pictures<uint8_t>) or f(Pictures<uint16_t>) by the sample bytes ss; the strides come in bytes
+template <class F>
+void with_samples(int ss, const void* src, const void* prev, void* dst, int64_t sstride, int64_t pstride, int64_t dstride, F&& f) {
+    if (ss == 1)
+        f(Pictures<uint8_t>{reinterpret_cast<const uint8_t*>(src), reinterpret_cast<const uint8_t*>(prev), reinterpret_cast<uint8_t*>(dst), (long)sstride,
+                            (long)pstride, (long)dstride});
+    else
+        f(Pictures<uint16_t>{reinterpret_cast<const uint16_t*>(src), reinterpret_cast<const uint16_t*>(prev), reinterpret_cast<uint16_t*>(dst),
+                             (long)sstride / 2, (long)pstride / 2, (long)dstride / 2});
+}
+
+// the end of every entry point that launched: `failure` is its "<entry point>: launch failed"
+int launched(const char* failure) {
+    if (hipGetLastError() == hipSuccess) return VSE_OK;
+    vse_set_error(failure);
+    return VSE_E_HIP;
+}
+
+// ---- conversion (vse_yuv_to_bgr_format, vse_yuv_to_bgr_tonemap)
+// {KY, BU, GU, GV, RV}_0 of [full_range][matrix]
+constexpr int YUV_K0[2][3][5] = {{{1220542, 2116026, -409993, -852492, 1673527},
+                                  {1220542, 2215014, -223607, -558796, 1879825},
+                                  {1220542, 2245811, -196426, -682019, 1760217}},
+                                 {{1 << 20, 1858077, -360853, -748826, 1470104},
+                                  {1 << 20, 1945738, -196424, -490864, 1651297},
+                                  {1 << 20, 1972791, -172546, -599107, 1546230}}};
+
+int scaled_factor(int k0, int s) {
+    const int m = ((k0 < 0 ? -k0 : k0) + ((1 << s) >> 1)) >> s;
+    return k0 < 0 ? -m : m;
+}
+
+YuvParams yuv_params(int depth, int msb, int matrix, int full_range) {
+    const int s = depth - 8;
+    const int* k0 = YUV_K0[full_range][matrix];
+    YuvParams p;
+    p.shift = msb ? 16 - depth : 0;
+    p.maxv = (1 << depth) - 1;
+    p.yoff = full_range ? 0 : 16 << s;
+    p.coff = 128 << s;
+    p.ky = scaled_factor(k0[0], s);
+    p.bu = scaled_factor(k0[1], s);
+    p.gu = scaled_factor(k0[2], s);
+    p.gv = scaled_factor(k0[3], s);
+    p.rv = scaled_factor(k0[4], s);
+    return p;
+}
+
+// Blocks of a tone-mapped launch: each stages the 16 128-byte table before its first pixel, so the grid is capped and blocks stride the
+// work.  Measured on 64 x 1080p / 16 x 2160p P010 (us per frame, 16-byte kernel; general kernel): 512 4.5 / 17.7; 12.4 / 43.5, 1024 3.9 /
+// 15.6; 8.6 / 29.5, 4096 3.4 / 14.1; 6.7 / 21.3, 8192 3.4 / 13.7; 5.6 / 20.8, 16384 3.4 / 13.7; 5.5 / 21.1: the copies cost less than idle
+// CUs do, and past 8192 nothing is gained.
+constexpr int TONE_MAX_BLOCKS = 8192;
+
+// The launch of an accepted call.  PlainOut: one block per 256 work items, as ever.  ToneOut: at most about TONE_MAX_BLOCKS blocks in all,
+// which stride the items, rows and frames.
+template <class OUT>
+void launch_format(const uint8_t* src, int n, int h, int w, int sub_x, int sub_y, int chroma, int ss, int row_parity, int64_t yuv_frame_stride,
+                   uint8_t* dst, int64_t pitch, int64_t bgr_frame_stride, const YuvParams& p, const typename OUT::Args& oa, hipStream_t st) {
+    constexpr bool tone = OUT::TONE;
+    const bool fast = ss == 2 && sub_x == 1 && sub_y == 1 && chroma != CHROMA_NONE && w % 16 == 0 && h % 2 == 0 && row_parity == 0 &&
+                      pitch % 16 == 0 && yuv_frame_stride % 16 == 0 && bgr_frame_stride % 16 == 0 && aligned16(src) && aligned16(dst);
+    if (fast) {
+        const long items = (long)(h / 2) * (w / 16);
+        dim3 grid = fast_grid(items, n);
+        if (tone) {
+            const long gx = std::min<long>((items + FAST_THREADS - 1) / FAST_THREADS, TONE_MAX_BLOCKS);
+            grid = dim3((unsigned)gx, (unsigned)std::min<long>(n, std::max<long>(TONE_MAX_BLOCKS / gx, 1)));
+        }
+        const auto kernel = chroma == CHROMA_PLANAR ? yuv420_wide_fast_kernel<CHROMA_PLANAR, OUT> : yuv420_wide_fast_kernel<CHROMA_SEMI, OUT>;
+        hipLaunchKernelGGL(kernel, grid, dim3(FAST_THREADS), 0, st, src, n, h, w, (long)yuv_frame_stride, dst, (long)pitch, (long)bgr_frame_stride, p,
+                           oa);
+        return;
+    }
+    dim3 grid = general_grid(((long)w + 3) / 4, h, n);
+    if (tone) {
+        grid.y = std::min<long>(grid.y, std::max<long>(TONE_MAX_BLOCKS / grid.x, 1));
+        grid.z = std::min<long>(grid.z, std::max<long>(TONE_MAX_BLOCKS / ((long)grid.x * grid.y), 1));
+    }
+    with_samples(ss, src, nullptr, nullptr, yuv_frame_stride, 0, 0, [&](auto pics) {
+        using S = std::remove_cv_t<std::remove_pointer_t<decltype(pics.src)>>;
+        const auto kernel = chroma == CHROMA_NONE ? yuv_general_kernel<S, CHROMA_NONE, OUT>
+                          : chroma == CHROMA_PLANAR ? yuv_general_kernel<S, CHROMA_PLANAR, OUT> : yuv_general_kernel<S, CHROMA_SEMI, OUT>;
+        hipLaunchKernelGGL(kernel, grid, dim3(GEN_LANES, GEN_ROWS), 0, st, pics.src, n, h, w, sub_x, sub_y, row_parity, pics.sstride, dst, (long)pitch,
+                           (long)bgr_frame_stride, p, oa);
+    });
+}
+
+// vse_yuv_to_bgr_format (OUT PlainOut; no table, no gamut) and vse_yuv_to_bgr_tonemap (OUT ToneOut): `who` and `cap` are the entry point's
+// name and the bytes its message is cut at
+template <class OUT>
+int convert(const char* who, size_t cap, vse_ctx* c, const void* d_yuv, int n, int h, int w, int sub_x, int sub_y, int chroma, int depth, int msb,
+            int matrix, int full_range, int row_parity, int64_t yuv_frame_stride, void* d_bgr, int64_t pitch, int64_t bgr_frame_stride,
+            const void* d_table, const int32_t* gamut, void* stream) {
+    const size_t frame = vse_yuv_frame_bytes(h, w, sub_x, sub_y, chroma, depth, row_parity);
+    const int ss = sample_bytes(depth);
+    bool ok = c && d_yuv && d_bgr && n >= 1 && frame && msb_ok(msb, ss) && matrix >= 0 && matrix <= 2 && full_range >= 0 && full_range <= 1 &&
+              holds(yuv_frame_stride, frame) && bgr_ok(h, w, pitch, bgr_frame_stride) && !(ss == 2 && odd(d_yuv, yuv_frame_stride)) &&
+              (!OUT::TONE || (table_ok(d_table, TONE_BYTES) && gamut));
+    for (int r = 0; OUT::TONE && ok && r < 3; ++r) {
+        long pos = 0, neg = 0;
+        for (int k = 0; k < 3; ++k) (gamut[3 * r + k] > 0 ? pos : neg) += gamut[3 * r + k];
+        ok = pos <= 32767 && neg >= -32768;
+    }
+    if (!ok) {
+        Refusal r(cap, who, n);
+        r.picture(h, w).format(sub_x, sub_y, chroma, depth, msb)
+            .add("matrix %d of 0 | 1 | 2, full range %d of 0 | 1, row parity %d of 0..%d, packed frame stride %lld of at least %zu, pitch %lld, output "
+                 "frame stride %lld, base %p and stride 2-byte aligned for 2-byte samples", matrix, full_range, row_parity, sub_y == 1 ? 1 : 0,
+                 (long long)yuv_frame_stride, frame, (long long)pitch, (long long)bgr_frame_stride, d_yuv);
+        int g[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (int k = 0; gamut && k < 9; ++k) g[k] = gamut[k];
+        if (OUT::TONE)
+            r.add(", table %p 16-byte aligned, gamut %p [%d %d %d; %d %d %d; %d %d %d] with each row's positive entries summing to at most 32767 and "
+                  "its negative ones to at least -32768", d_table, (const void*)gamut, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8]);
+        return r.add(")").send();
+    }
+    // what the 8-bit 4:2:0 kernels convert stays theirs
+    if (!OUT::TONE && ss == 1 && sub_x == 1 && sub_y == 1 && chroma != CHROMA_NONE && !full_range && matrix <= BT709)
+        return vse_yuv_to_bgr_matrix(c, d_yuv, n, h, w, chroma - 1, row_parity, yuv_frame_stride, d_bgr, pitch, bgr_frame_stride, matrix, stream);
+    typename OUT::Args oa = {};
+    if constexpr (OUT::TONE) {
+        oa.table = reinterpret_cast<const uint4*>(d_table);
+        for (int k = 0; k < 9; ++k) oa.m[k] = gamut[k];
+    }
+    launch_format<OUT>(reinterpret_cast<const uint8_t*>(d_yuv), n, h, w, sub_x, sub_y, chroma, ss, row_parity, yuv_frame_stride,
+                       reinterpret_cast<uint8_t*>(d_bgr), pitch, bgr_frame_stride, yuv_params(depth, msb, matrix, full_range), oa,
+                       reinterpret_cast<hipStream_t>(stream));
+    return launched(OUT::TONE ? "vse_yuv_to_bgr_tonemap: launch failed" : "vse_yuv_to_bgr_format: launch failed");
+}
+
+// ---- deinterlace and field match: the kernels' planes from the picture's
+// plane p of the picture joins pl, counted in samples (unit 1) or bytes (unit: the sample bytes)
+void add_plane(DeintPlanes& pl, const YuvPlanes& pic, int p, int unit) {
+    const int k = pl.count++;
+    pl.rows[k] = pic.rows[p];
+    pl.off[k] = pic.off[p] * unit;
+    pl.row[k] = pic.row[p] * unit;
+}
+
+// the fast kernels' work items of planes counted in bytes: sets pl.first and returns the total
+long deint_items(DeintPlanes& pl) {
+    long items = 0;
+    for (int p = 0; p < 3; ++p) {
+        pl.first[p] = (unsigned)items;
+        if (p < pl.count) items += (pl.row[p] / 16) * strips_of(pl.rows[p]);
+    }
+    pl.first[3] = (unsigned)items;
+    return items;
+}
+
+// the general kernels' grid over planes counted in samples: the widest row and the tallest plane
+dim3 deint_general_grid(const DeintPlanes& pl, int n) {
+    long row = 0;
+    int rows = 0;
+    for (int p = 0; p < pl.count; ++p) {
+        row = std::max(row, pl.row[p]);
+        rows = std::max(rows, pl.rows[p]);
+    }
+    return general_grid((row + 3) / 4, strips_of(rows), n);
+}
+
+// ---- resample and vscale: the instantiation of an accepted call
+// tap pairs 1, 2, 3, 4 (what bilinear, bicubic and Lanczos-3 need up to a reduction of 4 : 3) or 8
+template <typename S, int TP>
+auto resample_kernel_of(bool semi, bool fast) -> decltype(&resample_kernel<S, false, false, TP>) {
+    return fast ? (semi ? resample_kernel<S, true, true, TP> : resample_kernel<S, false, true, TP>)
+                : (semi ? resample_kernel<S, true, false, TP> : resample_kernel<S, false, false, TP>);
+}
+
+template <typename S>
+void launch_resample(const Pictures<S>& pics, int n, const ResPlanes& pl, int shift, int maxv, bool semi, bool fast, int pairs, dim3 grid,
+                     hipStream_t st) {
+    const auto kernel = pairs <= 1 ? resample_kernel_of<S, 1>(semi, fast) : pairs == 2 ? resample_kernel_of<S, 2>(semi, fast)
+                      : pairs == 3 ? resample_kernel_of<S, 3>(semi, fast) : pairs == 4 ? resample_kernel_of<S, 4>(semi, fast)
+                      : resample_kernel_of<S, RES_MAX_TAPS / 2>(semi, fast);
+    hipLaunchKernelGGL(kernel, grid, dim3(GEN_LANES, GEN_ROWS), 0, st, pics.src, n, pics.sstride, pics.dst, pics.dstride, pl, shift, maxv);
+}
+
+// tap pairs 1, 2, 3, 4, 6 (bilinear, bicubic and Lanczos-3 down to a reduction of 2 : 1) or 8
+template <typename S>
+void launch_vscale(const Pictures<S>& pics, int n, const VsPlanes& pl, int shift, int maxv, bool fast, int pairs, dim3 grid, hipStream_t st) {
 #define VSE_VS(TP) (fast ? vscale_kernel<S, true, TP> : vscale_kernel<S, false, TP>)
     const auto kernel = pairs <= 1 ? VSE_VS(1) : pairs == 2 ? VSE_VS(2) : pairs == 3 ? VSE_VS(3) : pairs == 4 ? VSE_VS(4)
                       : pairs <= 6 ? VSE_VS(6) : VSE_VS(RES_MAX_TAPS / 2);
 #undef VSE_VS
-    hipLaunchKernelGGL(kernel, grid, block, 0, st, reinterpret_cast<const S*>(d_yuv), n, sstride, reinterpret_cast<S*>(d_out), dstride, pl, shift,
-                       maxv);
+    hipLaunchKernelGGL(kernel, grid, dim3(GEN_LANES, GEN_ROWS), 0, st, pics.src, n, pics.sstride, pics.dst, pics.dstride, pl, shift, maxv);
+}
+
+// a plane's table on the device: `entries` int32 (left / top), then the coefficient rows as dwords
+void set_table(const int*& first, const unsigned*& coef, const void* d_table, long entries) {
+    const uint8_t* table = reinterpret_cast<const uint8_t*>(d_table);
+    first = reinterpret_cast<const int*>(table);
+    coef = reinterpret_cast<const unsigned*>(table + 4L * entries);
 }
 
 }  // namespace
 
 extern "C" {
 
-size_t vse_yuv420_frame_bytes(int h, int w, int row_parity) {
-    if (h < 1 || w < 1 || row_parity < 0 || row_parity > 1 || (long)h * w > MAX_PIXELS) return 0;
-    const size_t cw = ((size_t)w + 1) >> 1, ch = ((size_t)h + row_parity + 1) >> 1;
-    return (size_t)h * w + 2 * cw * ch;
-}
+size_t vse_yuv420_frame_bytes(int h, int w, int row_parity) { return (size_t)yuv_planes(h, w, 1, 1, CHROMA_PLANAR, 8, row_parity).total; }
 
 int vse_yuv_to_bgr_matrix(vse_ctx* c, const void* d_yuv, int n, int h, int w, int layout, int row_parity, int64_t yuv_frame_stride,
                           void* d_bgr, int64_t pitch, int64_t bgr_frame_stride, int matrix, void* stream) {
     const size_t frame = vse_yuv420_frame_bytes(h, w, row_parity);
     if (!c || !d_yuv || !d_bgr || n < 1 || !frame || (layout != YUV_I420 && layout != YUV_NV12) || (matrix != BT601 && matrix != BT709) ||
-        pitch < (int64_t)w * 3 || yuv_frame_stride < (int64_t)frame || bgr_frame_stride < (int64_t)(h - 1) * pitch + (int64_t)w * 3) {
-        char msg[360];
-        snprintf(msg, sizeof msg, "vse_yuv420_to_bgr: bad arguments (n %d, frame %d x %d of at most 2^31 - 1 pixels, layout %d of 0 | 1, row parity %d "
-                 "of 0 | 1, packed frame stride %lld of at least %zu, pitch %lld, output frame stride %lld, matrix %d of 0 | 1)", n, h, w, layout,
-                 row_parity, (long long)yuv_frame_stride, frame, (long long)pitch, (long long)bgr_frame_stride, matrix);
-        vse_set_error(msg);
-        return VSE_E_INVAL;
+        !holds(yuv_frame_stride, frame) || !bgr_ok(h, w, pitch, bgr_frame_stride)) {
+        return Refusal(360, "vse_yuv420_to_bgr", n).picture(h, w)
+            .add("layout %d of 0 | 1, row parity %d of 0 | 1, packed frame stride %lld of at least %zu, pitch %lld, output frame stride %lld, matrix %d "
+                 "of 0 | 1)", layout, row_parity, (long long)yuv_frame_stride, frame, (long long)pitch, (long long)bgr_frame_stride, matrix).send();
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const uint8_t* src = reinterpret_cast<const uint8_t*>(d_yuv);
@@ -1277,25 +1453,17 @@ int vse_yuv_to_bgr_matrix(vse_ctx* c, const void* d_yuv, int n, int h, int w, in
                       bgr_frame_stride % 16 == 0 && aligned16(src) && aligned16(dst);
     const int which = 2 * matrix + layout;
     if (fast) {
-        const long items = (long)(h / 2) * (w / 16);
-        const dim3 grid((unsigned)std::min<long>((items + FAST_THREADS - 1) / FAST_THREADS, FAST_MAX_BLOCKS), (unsigned)std::min(n, 65535));
         const auto kernel = which == 0 ? yuv420_fast_kernel<YUV_I420, BT601> : which == 1 ? yuv420_fast_kernel<YUV_NV12, BT601>
                           : which == 2 ? yuv420_fast_kernel<YUV_I420, BT709> : yuv420_fast_kernel<YUV_NV12, BT709>;
-        hipLaunchKernelGGL(kernel, grid, dim3(FAST_THREADS), 0, st, src, n, h, w, (long)yuv_frame_stride, dst, (long)pitch, (long)bgr_frame_stride);
+        hipLaunchKernelGGL(kernel, fast_grid((long)(h / 2) * (w / 16), n), dim3(FAST_THREADS), 0, st, src, n, h, w, (long)yuv_frame_stride, dst,
+                           (long)pitch, (long)bgr_frame_stride);
     } else {
-        const long groups = ((long)w + 3) / 4;
-        const dim3 grid((unsigned)((groups + GEN_LANES - 1) / GEN_LANES), (unsigned)std::min((h + GEN_ROWS - 1) / GEN_ROWS, 65535),
-                        (unsigned)std::min(n, 65535));
         const auto kernel = which == 0 ? yuv420_general_kernel<YUV_I420, BT601> : which == 1 ? yuv420_general_kernel<YUV_NV12, BT601>
                           : which == 2 ? yuv420_general_kernel<YUV_I420, BT709> : yuv420_general_kernel<YUV_NV12, BT709>;
-        hipLaunchKernelGGL(kernel, grid, dim3(GEN_LANES, GEN_ROWS), 0, st, src, n, h, w, row_parity, (long)yuv_frame_stride, dst, (long)pitch,
-                           (long)bgr_frame_stride);
+        hipLaunchKernelGGL(kernel, general_grid(((long)w + 3) / 4, h, n), dim3(GEN_LANES, GEN_ROWS), 0, st, src, n, h, w, row_parity,
+                           (long)yuv_frame_stride, dst, (long)pitch, (long)bgr_frame_stride);
     }
-    if (hipGetLastError() != hipSuccess) {
-        vse_set_error("vse_yuv420_to_bgr: launch failed");
-        return VSE_E_HIP;
-    }
-    return VSE_OK;
+    return launched("vse_yuv420_to_bgr: launch failed");
 }
 
 int vse_yuv420_to_bgr(vse_ctx* c, const void* d_yuv, int n, int h, int w, int layout, int row_parity, int64_t yuv_frame_stride,
@@ -1304,38 +1472,14 @@ int vse_yuv420_to_bgr(vse_ctx* c, const void* d_yuv, int n, int h, int w, int la
 }
 
 size_t vse_yuv_frame_bytes(int h, int w, int sub_x, int sub_y, int chroma, int depth, int row_parity) {
-    if (h < 1 || w < 1 || !format_ok(sub_x, sub_y, chroma, depth) || row_parity < 0 || row_parity > sub_y || (long)h * w > MAX_PIXELS) return 0;
-    const size_t cw = ((size_t)w + sub_x) >> sub_x, ch = (((size_t)h - 1 + row_parity) >> sub_y) + 1;
-    return (depth > 8 ? 2 : 1) * ((size_t)h * w + (chroma ? 2 * cw * ch : 0));
+    return (size_t)yuv_planes(h, w, sub_x, sub_y, chroma, depth, row_parity).total * sample_bytes(depth);
 }
 
 int vse_yuv_to_bgr_format(vse_ctx* c, const void* d_yuv, int n, int h, int w, int sub_x, int sub_y, int chroma, int depth, int msb, int matrix,
                           int full_range, int row_parity, int64_t yuv_frame_stride, void* d_bgr, int64_t pitch, int64_t bgr_frame_stride,
                           void* stream) {
-    const size_t frame = vse_yuv_frame_bytes(h, w, sub_x, sub_y, chroma, depth, row_parity);
-    const int ss = depth > 8 ? 2 : 1;
-    if (!format_call_ok(c, d_yuv, n, h, w, depth, msb, matrix, full_range, frame, yuv_frame_stride, d_bgr, pitch, bgr_frame_stride)) {
-        char msg[560];
-        snprintf(msg, sizeof msg, "vse_yuv_to_bgr_format: bad arguments (n %d, frame %d x %d of at most 2^31 - 1 pixels, subsampling %d, %d of 0, 0 | "
-                 "1, 0 | 1, 1, chroma %d of 0 (with subsampling 0, 0) | 1 | 2 (with subsampling 1, 1), depth %d of 8..16, msb %d of 0 | 1 (0 at "
-                 "depth 8), matrix %d of 0 | 1 | 2, full range %d of 0 | 1, row parity %d of 0..%d, packed frame stride %lld of at least %zu, "
-                 "pitch %lld, output frame stride %lld, base %p and stride 2-byte aligned for 2-byte samples)", n, h, w, sub_x, sub_y, chroma,
-                 depth, msb, matrix, full_range, row_parity, sub_y == 1 ? 1 : 0, (long long)yuv_frame_stride, frame, (long long)pitch,
-                 (long long)bgr_frame_stride, d_yuv);
-        vse_set_error(msg);
-        return VSE_E_INVAL;
-    }
-    // what the 8-bit 4:2:0 kernels convert stays theirs
-    if (ss == 1 && sub_x == 1 && sub_y == 1 && chroma != CHROMA_NONE && !full_range && matrix <= BT709)
-        return vse_yuv_to_bgr_matrix(c, d_yuv, n, h, w, chroma - 1, row_parity, yuv_frame_stride, d_bgr, pitch, bgr_frame_stride, matrix, stream);
-    launch_format<PlainOut>(reinterpret_cast<const uint8_t*>(d_yuv), n, h, w, sub_x, sub_y, chroma, ss, row_parity, yuv_frame_stride,
-                            reinterpret_cast<uint8_t*>(d_bgr), pitch, bgr_frame_stride, yuv_params(depth, msb, matrix, full_range), PlainOut::Args(),
-                            reinterpret_cast<hipStream_t>(stream));
-    if (hipGetLastError() != hipSuccess) {
-        vse_set_error("vse_yuv_to_bgr_format: launch failed");
-        return VSE_E_HIP;
-    }
-    return VSE_OK;
+    return convert<PlainOut>("vse_yuv_to_bgr_format", 560, c, d_yuv, n, h, w, sub_x, sub_y, chroma, depth, msb, matrix, full_range, row_parity,
+                             yuv_frame_stride, d_bgr, pitch, bgr_frame_stride, nullptr, nullptr, stream);
 }
 
 size_t vse_yuv_tonemap_table_bytes(void) { return TONE_BYTES; }
@@ -1343,153 +1487,66 @@ size_t vse_yuv_tonemap_table_bytes(void) { return TONE_BYTES; }
 int vse_yuv_to_bgr_tonemap(vse_ctx* c, const void* d_yuv, int n, int h, int w, int sub_x, int sub_y, int chroma, int depth, int msb, int matrix,
                            int full_range, int row_parity, int64_t yuv_frame_stride, void* d_bgr, int64_t pitch, int64_t bgr_frame_stride,
                            const void* d_table, const int32_t* gamut, void* stream) {
-    const size_t frame = vse_yuv_frame_bytes(h, w, sub_x, sub_y, chroma, depth, row_parity);
-    bool ok = format_call_ok(c, d_yuv, n, h, w, depth, msb, matrix, full_range, frame, yuv_frame_stride, d_bgr, pitch, bgr_frame_stride) &&
-              d_table && aligned16(d_table) && gamut;
-    for (int r = 0; ok && r < 3; ++r) {
-        long pos = 0, neg = 0;
-        for (int k = 0; k < 3; ++k) (gamut[3 * r + k] > 0 ? pos : neg) += gamut[3 * r + k];
-        ok = pos <= 32767 && neg >= -32768;
-    }
-    if (!ok) {
-        char msg[1024];
-        int g[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int k = 0; gamut && k < 9; ++k) g[k] = gamut[k];
-        snprintf(msg, sizeof msg, "vse_yuv_to_bgr_tonemap: bad arguments (n %d, frame %d x %d of at most 2^31 - 1 pixels, subsampling %d, %d of 0, 0 | "
-                 "1, 0 | 1, 1, chroma %d of 0 (with subsampling 0, 0) | 1 | 2 (with subsampling 1, 1), depth %d of 8..16, msb %d of 0 | 1 (0 at "
-                 "depth 8), matrix %d of 0 | 1 | 2, full range %d of 0 | 1, row parity %d of 0..%d, packed frame stride %lld of at least %zu, "
-                 "pitch %lld, output frame stride %lld, base %p and stride 2-byte aligned for 2-byte samples, table %p 16-byte aligned, gamut %p "
-                 "[%d %d %d; %d %d %d; %d %d %d] with each row's positive entries summing to at most 32767 and its negative ones to at least "
-                 "-32768)", n, h, w, sub_x, sub_y, chroma, depth, msb, matrix, full_range, row_parity, sub_y == 1 ? 1 : 0,
-                 (long long)yuv_frame_stride, frame, (long long)pitch, (long long)bgr_frame_stride, d_yuv, d_table, (const void*)gamut, g[0], g[1],
-                 g[2], g[3], g[4], g[5], g[6], g[7], g[8]);
-        vse_set_error(msg);
-        return VSE_E_INVAL;
-    }
-    ToneOut::Args oa;
-    oa.table = reinterpret_cast<const uint4*>(d_table);
-    for (int k = 0; k < 9; ++k) oa.m[k] = gamut[k];
-    launch_format<ToneOut>(reinterpret_cast<const uint8_t*>(d_yuv), n, h, w, sub_x, sub_y, chroma, depth > 8 ? 2 : 1, row_parity, yuv_frame_stride,
-                           reinterpret_cast<uint8_t*>(d_bgr), pitch, bgr_frame_stride, yuv_params(depth, msb, matrix, full_range), oa,
-                           reinterpret_cast<hipStream_t>(stream));
-    if (hipGetLastError() != hipSuccess) {
-        vse_set_error("vse_yuv_to_bgr_tonemap: launch failed");
-        return VSE_E_HIP;
-    }
-    return VSE_OK;
+    return convert<ToneOut>("vse_yuv_to_bgr_tonemap", 1024, c, d_yuv, n, h, w, sub_x, sub_y, chroma, depth, msb, matrix, full_range, row_parity,
+                            yuv_frame_stride, d_bgr, pitch, bgr_frame_stride, d_table, gamut, stream);
 }
 
 int vse_yuv_deinterlace(vse_ctx* c, const void* d_yuv, const void* d_prev, int n, int h, int w, int sub_x, int sub_y, int chroma, int depth,
                         int msb, int keep, int mode, int thresh, int64_t yuv_frame_stride, int64_t prev_frame_stride, void* d_out,
                         int64_t out_frame_stride, void* stream) {
-    const size_t frame = vse_yuv_frame_bytes(h, w, sub_x, sub_y, chroma, depth, 0);
-    const int ss = depth > 8 ? 2 : 1;
-    const auto odd = [](const void* p, int64_t stride) { return (reinterpret_cast<uintptr_t>(p) & 1) || (stride & 1); };
-    if (!c || !d_yuv || !d_out || n < 1 || !frame || msb < 0 || msb > (ss == 2 ? 1 : 0) || keep < 0 || keep > 1 || mode < 0 || mode > 1 ||
-        thresh < 0 || thresh > 255 || yuv_frame_stride < (int64_t)frame || out_frame_stride < (int64_t)frame ||
-        (d_prev && prev_frame_stride < (int64_t)frame) || d_out == d_yuv || d_out == d_prev ||
-        (ss == 2 && (odd(d_yuv, yuv_frame_stride) || odd(d_out, out_frame_stride) || (d_prev && odd(d_prev, prev_frame_stride))))) {
-        char msg[560];
-        snprintf(msg, sizeof msg, "vse_yuv_deinterlace: bad arguments (n %d, frame %d x %d of at most 2^31 - 1 pixels, subsampling %d, %d of 0, 0 | "
-                 "1, 0 | 1, 1, chroma %d of 0 (with subsampling 0, 0) | 1 | 2 (with subsampling 1, 1), depth %d of 8..16, msb %d of 0 | 1 (0 at "
-                 "depth 8), keep %d of 0 | 1, mode %d of 0 | 1, thresh %d of 0..255, frame strides %lld, %lld (previous pictures) and %lld "
-                 "(output) of at least %zu, bases %p, %p, %p and strides 2-byte aligned for 2-byte samples, the output none of the inputs)",
-                 n, h, w, sub_x, sub_y, chroma, depth, msb, keep, mode, thresh, (long long)yuv_frame_stride, (long long)prev_frame_stride,
-                 (long long)out_frame_stride, frame, d_yuv, d_prev, d_out);
-        vse_set_error(msg);
-        return VSE_E_INVAL;
-    }
-    const long cw = ((long)w + sub_x) >> sub_x, ch = (((long)h - 1) >> sub_y) + 1, luma = (long)h * w;
-    DeintPlanes pl = {};
-    pl.count = chroma == CHROMA_NONE ? 1 : chroma == CHROMA_PLANAR ? 3 : 2;
-    pl.rows[0] = h;
-    pl.off[0] = 0;
-    pl.row[0] = w;
-    for (int p = 1; p < pl.count; ++p) {
-        pl.rows[p] = (int)ch;
-        pl.off[p] = luma + (p - 1) * ch * cw;
-        pl.row[p] = chroma == CHROMA_SEMI ? 2 * cw : cw;
+    const YuvPlanes pic = yuv_planes(h, w, sub_x, sub_y, chroma, depth, 0);
+    const int ss = sample_bytes(depth);
+    const size_t frame = (size_t)pic.total * ss;
+    if (!fields_call_ok(c, d_yuv, d_prev, d_out, n, frame, ss, msb, keep, thresh, yuv_frame_stride, prev_frame_stride, out_frame_stride) || mode < 0 ||
+        mode > 1) {
+        return Refusal(560, "vse_yuv_deinterlace", n).picture(h, w).format(sub_x, sub_y, chroma, depth, msb)
+            .add("keep %d of 0 | 1, mode %d of 0 | 1, thresh %d of 0..255, ", keep, mode, thresh)
+            .fields(yuv_frame_stride, prev_frame_stride, out_frame_stride, frame, d_yuv, d_prev, d_out).add(")").send();
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_yuv);
-    const uint8_t* prev = mode == 0 ? reinterpret_cast<const uint8_t*>(d_prev) : nullptr;       // interpolate: no picture is compared
-    uint8_t* dst = reinterpret_cast<uint8_t*>(d_out);
-    bool fast = aligned16(src) && aligned16(dst) && yuv_frame_stride % 16 == 0 && out_frame_stride % 16 == 0 &&
+    const void* prev = mode == 0 ? d_prev : nullptr;       // interpolate: no picture is compared
+    bool fast = aligned16(d_yuv) && aligned16(d_out) && yuv_frame_stride % 16 == 0 && out_frame_stride % 16 == 0 &&
                 (!prev || (aligned16(prev) && prev_frame_stride % 16 == 0));
-    for (int p = 0; p < pl.count; ++p) fast = fast && (pl.row[p] * ss) % 16 == 0;          // then every plane's offset is a multiple of 16 too
+    for (int p = 0; p < pic.count; ++p) fast = fast && (pic.row[p] * ss) % 16 == 0;          // then every plane's offset is a multiple of 16 too
     const int T = thresh << (depth - 8 + (msb ? 16 - depth : 0));
+    DeintPlanes pl = {};
+    for (int p = 0; p < pic.count; ++p) add_plane(pl, pic, p, fast ? ss : 1);
     if (fast) {
-        long items = 0;
-        for (int p = 0; p < 3; ++p) {
-            pl.first[p] = (unsigned)items;
-            if (p >= pl.count) continue;
-            pl.off[p] *= ss;
-            pl.row[p] *= ss;
-            items += (pl.row[p] / 16) * ((pl.rows[p] + DEINT_STRIP - 1) / DEINT_STRIP);
-        }
-        pl.first[3] = (unsigned)items;
-        const dim3 grid((unsigned)std::min<long>((items + FAST_THREADS - 1) / FAST_THREADS, FAST_MAX_BLOCKS), (unsigned)std::min(n, 65535));
+        const dim3 grid = fast_grid(deint_items(pl), n);
         const auto kernel = ss == 1 ? deinterlace_fast_kernel<uint8_t> : deinterlace_fast_kernel<uint16_t>;
-        hipLaunchKernelGGL(kernel, grid, dim3(FAST_THREADS), 0, st, src, prev, n, (long)yuv_frame_stride, (long)prev_frame_stride, dst,
-                           (long)out_frame_stride, pl, keep, T);
+        hipLaunchKernelGGL(kernel, grid, dim3(FAST_THREADS), 0, st, reinterpret_cast<const uint8_t*>(d_yuv), reinterpret_cast<const uint8_t*>(prev), n,
+                           (long)yuv_frame_stride, (long)prev_frame_stride, reinterpret_cast<uint8_t*>(d_out), (long)out_frame_stride, pl, keep, T);
     } else {
-        const long groups = (std::max(pl.row[0], pl.row[pl.count - 1]) + 3) / 4;
-        const int strips = (h + DEINT_STRIP - 1) / DEINT_STRIP;
-        const dim3 grid((unsigned)((groups + GEN_LANES - 1) / GEN_LANES), (unsigned)std::min((strips + GEN_ROWS - 1) / GEN_ROWS, 65535),
-                        (unsigned)std::min(n, 65535));
-        const dim3 block(GEN_LANES, GEN_ROWS);
-        if (ss == 1) {
-            hipLaunchKernelGGL(deinterlace_general_kernel<uint8_t>, grid, block, 0, st, src, prev, n, (long)yuv_frame_stride, (long)prev_frame_stride,
-                               dst, (long)out_frame_stride, pl, keep, T);
-        } else {
-            hipLaunchKernelGGL(deinterlace_general_kernel<uint16_t>, grid, block, 0, st, reinterpret_cast<const uint16_t*>(src),
-                               reinterpret_cast<const uint16_t*>(prev), n, (long)yuv_frame_stride / 2, (long)prev_frame_stride / 2,
-                               reinterpret_cast<uint16_t*>(dst), (long)out_frame_stride / 2, pl, keep, T);
-        }
+        with_samples(ss, d_yuv, prev, d_out, yuv_frame_stride, prev_frame_stride, out_frame_stride, [&](auto pics) {
+            using S = std::remove_pointer_t<decltype(pics.dst)>;
+            hipLaunchKernelGGL(deinterlace_general_kernel<S>, deint_general_grid(pl, n), dim3(GEN_LANES, GEN_ROWS), 0, st, pics.src, pics.prev, n,
+                               pics.sstride, pics.pstride, pics.dst, pics.dstride, pl, keep, T);
+        });
     }
-    if (hipGetLastError() != hipSuccess) {
-        vse_set_error("vse_yuv_deinterlace: launch failed");
-        return VSE_E_HIP;
-    }
-    return VSE_OK;
+    return launched("vse_yuv_deinterlace: launch failed");
 }
 
 int vse_yuv_field_match(vse_ctx* c, const void* d_yuv, const void* d_prev, int n, int h, int w, int sub_x, int sub_y, int chroma, int depth,
                         int msb, int keep, int comb_thresh, int comb_limit, int thresh, int64_t yuv_frame_stride, int64_t prev_frame_stride,
                         void* d_out, int64_t out_frame_stride, void* d_stats, void* stream) {
-    const size_t frame = vse_yuv_frame_bytes(h, w, sub_x, sub_y, chroma, depth, 0);
-    const int ss = depth > 8 ? 2 : 1;
-    const auto odd = [](const void* p, int64_t stride) { return (reinterpret_cast<uintptr_t>(p) & 1) || (stride & 1); };
-    bool ok = c && d_yuv && d_out && d_stats && n >= 1 && frame && msb >= 0 && msb <= (ss == 2 ? 1 : 0) && keep >= 0 && keep <= 1 &&
-              comb_thresh >= 0 && comb_thresh <= 255 && comb_limit <= 1000 && thresh >= 0 && thresh <= 255 &&
-              (reinterpret_cast<uintptr_t>(d_stats) & 3) == 0 && yuv_frame_stride >= (int64_t)frame && out_frame_stride >= (int64_t)frame &&
-              (!d_prev || prev_frame_stride >= (int64_t)frame) && d_out != d_yuv && d_out != d_prev &&
-              !(ss == 2 && (odd(d_yuv, yuv_frame_stride) || odd(d_out, out_frame_stride) || (d_prev && odd(d_prev, prev_frame_stride))));
+    const YuvPlanes pic = yuv_planes(h, w, sub_x, sub_y, chroma, depth, 0);
+    const int ss = sample_bytes(depth);
+    const size_t frame = (size_t)pic.total * ss;
+    bool ok = fields_call_ok(c, d_yuv, d_prev, d_out, n, frame, ss, msb, keep, thresh, yuv_frame_stride, prev_frame_stride, out_frame_stride) &&
+              d_stats && comb_thresh >= 0 && comb_thresh <= 255 && comb_limit <= 1000 && (reinterpret_cast<uintptr_t>(d_stats) & 3) == 0;
     if (ok) {
         // the stats lie apart from every picture: from the first byte of a run's first picture to the last byte of its last one
         const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_stats), s1 = s0 + 16 * (uintptr_t)n;
-        const auto apart = [&](const void* p, int64_t stride) {
-            const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = a + (uintptr_t)(n - 1) * (uintptr_t)stride + frame;
-            return !p || s1 <= a || b <= s0;
-        };
-        ok = apart(d_yuv, yuv_frame_stride) && apart(d_prev, prev_frame_stride) && apart(d_out, out_frame_stride);
+        const auto run = [&](int64_t stride) { return (uintptr_t)(n - 1) * (uintptr_t)stride + frame; };
+        ok = apart(s0, s1, d_yuv, run(yuv_frame_stride)) && apart(s0, s1, d_prev, run(prev_frame_stride)) &&
+             apart(s0, s1, d_out, run(out_frame_stride));
     }
     if (!ok) {
-        char msg[720];
-        snprintf(msg, sizeof msg, "vse_yuv_field_match: bad arguments (n %d, frame %d x %d of at most 2^31 - 1 pixels, subsampling %d, %d of 0, 0 | "
-                 "1, 0 | 1, 1, chroma %d of 0 (with subsampling 0, 0) | 1 | 2 (with subsampling 1, 1), depth %d of 8..16, msb %d of 0 | 1 (0 at "
-                 "depth 8), keep %d of 0 | 1, comb_thresh %d of 0..255, comb_limit %d of at most 1000, thresh %d of 0..255, frame strides %lld, "
-                 "%lld (previous pictures) and %lld (output) of at least %zu, bases %p, %p, %p and strides 2-byte aligned for 2-byte samples, "
-                 "the output none of the inputs, stats %p 4-byte aligned and apart from the pictures)",
-                 n, h, w, sub_x, sub_y, chroma, depth, msb, keep, comb_thresh, comb_limit, thresh, (long long)yuv_frame_stride,
-                 (long long)prev_frame_stride, (long long)out_frame_stride, frame, d_yuv, d_prev, d_out, d_stats);
-        vse_set_error(msg);
-        return VSE_E_INVAL;
+        return Refusal(720, "vse_yuv_field_match", n).picture(h, w).format(sub_x, sub_y, chroma, depth, msb)
+            .add("keep %d of 0 | 1, comb_thresh %d of 0..255, comb_limit %d of at most 1000, thresh %d of 0..255, ", keep, comb_thresh, comb_limit, thresh)
+            .fields(yuv_frame_stride, prev_frame_stride, out_frame_stride, frame, d_yuv, d_prev, d_out)
+            .add(", stats %p 4-byte aligned and apart from the pictures)", d_stats).send();
     }
-    const long cw = ((long)w + sub_x) >> sub_x, ch = (((long)h - 1) >> sub_y) + 1, luma = (long)h * w;
-    const int count = chroma == CHROMA_NONE ? 1 : chroma == CHROMA_PLANAR ? 3 : 2;
-    int rows[3] = {h, (int)ch, (int)ch};
-    long off[3] = {0, luma, luma + ch * cw}, row[3] = {w, chroma == CHROMA_SEMI ? 2 * cw : cw, cw};          // in samples
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const uint8_t* src = reinterpret_cast<const uint8_t*>(d_yuv);
     const uint8_t* prev = reinterpret_cast<const uint8_t*>(d_prev);
@@ -1504,80 +1561,41 @@ int vse_yuv_field_match(vse_ctx* c, const void* d_yuv, const void* d_prev, int n
     // ---- the count, over luma: 16-byte columns where the inputs allow them
     const bool in16 = aligned16(src) && yuv_frame_stride % 16 == 0 && (!prev || (aligned16(prev) && prev_frame_stride % 16 == 0));
     if (h >= 3) {
-        const int strips = (h + DEINT_STRIP - 1) / DEINT_STRIP;
         if (in16 && ((long)w * ss) % 16 == 0) {
-            const long items = ((long)w * ss / 16) * strips;
-            const dim3 grid((unsigned)std::min<long>((items + FAST_THREADS - 1) / FAST_THREADS, FAST_MAX_BLOCKS), (unsigned)std::min(n, 65535));
             const auto kernel = ss == 1 ? field_count_fast_kernel<uint8_t> : field_count_fast_kernel<uint16_t>;
-            hipLaunchKernelGGL(kernel, grid, dim3(FAST_THREADS), 0, st, src, prev, n, (long)yuv_frame_stride, (long)prev_frame_stride, h,
-                               (long)w * ss, keep, comb_t, stats);
+            hipLaunchKernelGGL(kernel, fast_grid(((long)w * ss / 16) * strips_of(h), n), dim3(FAST_THREADS), 0, st, src, prev, n,
+                               (long)yuv_frame_stride, (long)prev_frame_stride, h, (long)w * ss, keep, comb_t, stats);
         } else {
-            const long groups = ((long)w + 3) / 4;
-            const dim3 grid((unsigned)((groups + GEN_LANES - 1) / GEN_LANES), (unsigned)std::min((strips + GEN_ROWS - 1) / GEN_ROWS, 65535),
-                            (unsigned)std::min(n, 65535));
-            const dim3 block(GEN_LANES, GEN_ROWS);
-            if (ss == 1) {
-                hipLaunchKernelGGL(field_count_general_kernel<uint8_t>, grid, block, 0, st, src, prev, n, (long)yuv_frame_stride,
-                                   (long)prev_frame_stride, h, (long)w, keep, comb_t, stats);
-            } else {
-                hipLaunchKernelGGL(field_count_general_kernel<uint16_t>, grid, block, 0, st, reinterpret_cast<const uint16_t*>(src),
-                                   reinterpret_cast<const uint16_t*>(prev), n, (long)yuv_frame_stride / 2, (long)prev_frame_stride / 2, h, (long)w,
-                                   keep, comb_t, stats);
-            }
+            with_samples(ss, d_yuv, d_prev, nullptr, yuv_frame_stride, prev_frame_stride, 0, [&](auto pics) {
+                using S = std::remove_pointer_t<decltype(pics.dst)>;
+                hipLaunchKernelGGL(field_count_general_kernel<S>, general_grid(((long)w + 3) / 4, strips_of(h), n), dim3(GEN_LANES, GEN_ROWS), 0, st,
+                                   pics.src, pics.prev, n, pics.sstride, pics.pstride, h, (long)w, keep, comb_t, stats);
+            });
         }
     }
     // ---- the weave: every plane on its own takes 16-byte moves where its base and row bytes allow them, quads otherwise
     const bool all16 = in16 && aligned16(dst) && out_frame_stride % 16 == 0;
     DeintPlanes fast = {}, gen = {};
     MatchRule fast_rule = {(long)comb_limit * w * ((long)h - 2), comb_limit >= 0 ? 1 : 0, 0}, gen_rule = fast_rule;
-    long items = 0, gen_row = 0;
-    int gen_rows = 0;
-    for (int p = 0; p < count; ++p) {
-        if (all16 && (off[p] * ss) % 16 == 0 && (row[p] * ss) % 16 == 0) {
-            const int k = fast.count++;
-            fast.rows[k] = rows[p];
-            fast.off[k] = off[p] * ss;
-            fast.row[k] = row[p] * ss;
-            fast.first[k] = (unsigned)items;
-            items += (fast.row[k] / 16) * ((rows[p] + DEINT_STRIP - 1) / DEINT_STRIP);
-            if (p == 0) fast_rule.store = 1;
-        } else {
-            const int k = gen.count++;
-            gen.rows[k] = rows[p];
-            gen.off[k] = off[p];
-            gen.row[k] = row[p];
-            gen_row = std::max(gen_row, row[p]);
-            gen_rows = std::max(gen_rows, rows[p]);
-            if (p == 0) gen_rule.store = 1;
-        }
+    for (int p = 0; p < pic.count; ++p) {
+        const bool p16 = all16 && (pic.off[p] * ss) % 16 == 0 && (pic.row[p] * ss) % 16 == 0;
+        add_plane(p16 ? fast : gen, pic, p, p16 ? ss : 1);
+        if (p == 0) (p16 ? fast_rule : gen_rule).store = 1;
     }
-    for (int k = fast.count; k < 4; ++k) fast.first[k] = (unsigned)items;
     if (fast.count) {
-        const dim3 grid((unsigned)std::min<long>((items + FAST_THREADS - 1) / FAST_THREADS, FAST_MAX_BLOCKS), (unsigned)std::min(n, 65535));
+        const dim3 grid = fast_grid(deint_items(fast), n);
         const auto kernel = ss == 1 ? field_weave_fast_kernel<uint8_t> : field_weave_fast_kernel<uint16_t>;
         hipLaunchKernelGGL(kernel, grid, dim3(FAST_THREADS), 0, st, src, prev, n, (long)yuv_frame_stride, (long)prev_frame_stride, dst,
                            (long)out_frame_stride, fast, keep, T, stats, fast_rule);
     }
     if (gen.count) {
-        const long groups = (gen_row + 3) / 4;
-        const int strips = (gen_rows + DEINT_STRIP - 1) / DEINT_STRIP;
-        const dim3 grid((unsigned)((groups + GEN_LANES - 1) / GEN_LANES), (unsigned)std::min((strips + GEN_ROWS - 1) / GEN_ROWS, 65535),
-                        (unsigned)std::min(n, 65535));
-        const dim3 block(GEN_LANES, GEN_ROWS);
-        if (ss == 1) {
-            hipLaunchKernelGGL(field_weave_general_kernel<uint8_t>, grid, block, 0, st, src, prev, n, (long)yuv_frame_stride,
-                               (long)prev_frame_stride, dst, (long)out_frame_stride, gen, keep, T, stats, gen_rule);
-        } else {
-            hipLaunchKernelGGL(field_weave_general_kernel<uint16_t>, grid, block, 0, st, reinterpret_cast<const uint16_t*>(src),
-                               reinterpret_cast<const uint16_t*>(prev), n, (long)yuv_frame_stride / 2, (long)prev_frame_stride / 2,
-                               reinterpret_cast<uint16_t*>(dst), (long)out_frame_stride / 2, gen, keep, T, stats, gen_rule);
-        }
+        with_samples(ss, d_yuv, d_prev, d_out, yuv_frame_stride, prev_frame_stride, out_frame_stride, [&](auto pics) {
+            using S = std::remove_pointer_t<decltype(pics.dst)>;
+            hipLaunchKernelGGL(field_weave_general_kernel<S>, deint_general_grid(gen, n), dim3(GEN_LANES, GEN_ROWS), 0, st, pics.src, pics.prev, n,
+                               pics.sstride, pics.pstride, pics.dst, pics.dstride, gen, keep, T, stats, gen_rule);
+        });
     }
-    if (hipGetLastError() != hipSuccess) {
-        vse_set_error("vse_yuv_field_match: launch failed");
-        return VSE_E_HIP;
-    }
-    return VSE_OK;
+    return launched("vse_yuv_field_match: launch failed");
 }
 
 size_t vse_yuv_resample_table_bytes(int columns, int taps) {
@@ -1587,166 +1605,92 @@ size_t vse_yuv_resample_table_bytes(int columns, int taps) {
 int vse_yuv_resample(vse_ctx* c, const void* d_yuv, int n, int h, int w_in, int w_out, int sub_x, int sub_y, int chroma, int depth, int msb,
                      int row_parity, const void* d_table_y, int taps_y, const void* d_table_c, int taps_c, int64_t yuv_frame_stride, void* d_out,
                      int64_t out_frame_stride, void* stream) {
-    const size_t frame_in = vse_yuv_frame_bytes(h, w_in, sub_x, sub_y, chroma, depth, row_parity);
-    const size_t frame_out = vse_yuv_frame_bytes(h, w_out, sub_x, sub_y, chroma, depth, row_parity);
-    const int ss = depth > 8 ? 2 : 1;
-    const bool has_chroma = frame_in && chroma != CHROMA_NONE;
-    const long cw_in = ((long)w_in + (sub_x & 1)) >> (sub_x & 1), cw_out = ((long)w_out + (sub_x & 1)) >> (sub_x & 1);
+    const YuvPlanes in = yuv_planes(h, w_in, sub_x, sub_y, chroma, depth, row_parity), out = yuv_planes(h, w_out, sub_x, sub_y, chroma, depth, row_parity);
+    const int ss = sample_bytes(depth), comps = chroma == CHROMA_SEMI ? 2 : 1;
+    const size_t frame_in = (size_t)in.total * ss, frame_out = (size_t)out.total * ss;
+    const bool has_chroma = in.count > 1;
     const size_t table_y = frame_out ? vse_yuv_resample_table_bytes(w_out, taps_y) : 0;
-    const size_t table_c = has_chroma && frame_out ? vse_yuv_resample_table_bytes((int)cw_out, taps_c) : 0;
-    const auto odd = [](const void* p, int64_t stride) { return (reinterpret_cast<uintptr_t>(p) & 1) || (stride & 1); };
-    bool ok = c && d_yuv && d_out && n >= 1 && frame_in && frame_out && msb >= 0 && msb <= (ss == 2 ? 1 : 0) && table_y && d_table_y &&
-              aligned16(d_table_y) && (!has_chroma || (table_c && d_table_c && aligned16(d_table_c))) && yuv_frame_stride >= (int64_t)frame_in &&
-              out_frame_stride >= (int64_t)frame_out && !(ss == 2 && (odd(d_yuv, yuv_frame_stride) || odd(d_out, out_frame_stride)));
-    if (ok) {
-        // the output lies apart from the input pictures (first byte of the first to last byte of the last) and from both tables
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + (uintptr_t)(n - 1) * (uintptr_t)out_frame_stride + frame_out;
-        const auto apart = [&](const void* p, size_t bytes) {
-            const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-            return !p || !bytes || o1 <= a || a + bytes <= o0;
-        };
-        ok = apart(d_yuv, (size_t)(n - 1) * (size_t)yuv_frame_stride + frame_in) && apart(d_table_y, table_y) &&
-             apart(has_chroma ? d_table_c : nullptr, table_c);
+    const size_t table_c = has_chroma && frame_out ? vse_yuv_resample_table_bytes((int)(out.row[1] / comps), taps_c) : 0;
+    if (!scaler_call_ok(c, d_yuv, d_out, n, frame_in, frame_out, ss, msb, d_table_y, table_y, d_table_c, table_c, has_chroma, yuv_frame_stride,
+                        out_frame_stride)) {
+        return Refusal(900, "vse_yuv_resample", n).add("frame %d x %d -> %d columns, each of at most 2^31 - 1 pixels, ", h, w_in, w_out)
+            .format(sub_x, sub_y, chroma, depth, msb).add("row parity %d of 0..%d, ", row_parity, sub_y == 1 ? 1 : 0)
+            .scaler(taps_y, taps_c, d_table_y, d_table_c, yuv_frame_stride, frame_in, out_frame_stride, frame_out, d_yuv, d_out).send();
     }
-    if (!ok) {
-        char msg[900];
-        snprintf(msg, sizeof msg, "vse_yuv_resample: bad arguments (n %d, frame %d x %d -> %d columns, each of at most 2^31 - 1 pixels, subsampling "
-                 "%d, %d of 0, 0 | 1, 0 | 1, 1, chroma %d of 0 (with subsampling 0, 0) | 1 | 2 (with subsampling 1, 1), depth %d of 8..16, msb %d of "
-                 "0 | 1 (0 at depth 8), row parity %d of 0..%d, taps %d (luma) and %d (chroma) even and of 2..16, tables %p and %p 16-byte aligned "
-                 "(the chroma table only where the format has chroma), frame strides %lld of at least %zu and %lld (output) of at least %zu, bases "
-                 "%p, %p and strides 2-byte aligned for 2-byte samples, the output apart from the pictures and the tables)",
-                 n, h, w_in, w_out, sub_x, sub_y, chroma, depth, msb, row_parity, sub_y == 1 ? 1 : 0, taps_y, taps_c, d_table_y, d_table_c,
-                 (long long)yuv_frame_stride, frame_in, (long long)out_frame_stride, frame_out, d_yuv, d_out);
-        vse_set_error(msg);
-        return VSE_E_INVAL;
-    }
-    const long ch = (((long)h - 1 + row_parity) >> sub_y) + 1;
     ResPlanes pl = {};
-    pl.count = chroma == CHROMA_NONE ? 1 : chroma == CHROMA_PLANAR ? 3 : 2;
-    const int comps = chroma == CHROMA_SEMI ? 2 : 1;
-    for (int p = 0; p < pl.count; ++p) {
-        const bool luma = p == 0;
-        const uint8_t* table = reinterpret_cast<const uint8_t*>(luma ? d_table_y : d_table_c);
-        pl.rows[p] = luma ? h : (int)ch;
-        pl.pin[p] = luma ? w_in : (int)cw_in;
-        pl.pout[p] = luma ? w_out : (int)cw_out;
-        pl.taps[p] = luma ? taps_y : taps_c;
-        pl.off_in[p] = luma ? 0 : (long)h * w_in + (p - 1) * ch * cw_in;
-        pl.off_out[p] = luma ? 0 : (long)h * w_out + (p - 1) * ch * cw_out;
-        pl.left[p] = reinterpret_cast<const int*>(table);
-        pl.coef[p] = reinterpret_cast<const unsigned*>(table + 4L * pl.pout[p]);
-    }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    pl.count = in.count;
     // the fast kernel: every output quad whole and on a 4-sample boundary
     bool fast = aligned16(d_yuv) && aligned16(d_out) && yuv_frame_stride % 16 == 0 && out_frame_stride % 16 == 0;
     for (int p = 0; p < pl.count; ++p) {
-        const long cs = p == 0 ? 1 : comps;
-        fast = fast && (pl.pin[p] * cs * ss) % 16 == 0 && (pl.pout[p] * cs * ss) % 16 == 0 && (pl.off_in[p] * ss) % 16 == 0 &&
-               (pl.off_out[p] * ss) % 16 == 0;
+        const int cs = p ? comps : 1;
+        pl.rows[p] = in.rows[p];
+        pl.pin[p] = (int)(in.row[p] / cs);
+        pl.pout[p] = (int)(out.row[p] / cs);
+        pl.taps[p] = p ? taps_c : taps_y;
+        pl.off_in[p] = in.off[p];
+        pl.off_out[p] = out.off[p];
+        set_table(pl.left[p], pl.coef[p], p ? d_table_c : d_table_y, pl.pout[p]);
+        fast = fast && (in.row[p] * ss) % 16 == 0 && (out.row[p] * ss) % 16 == 0 && (in.off[p] * ss) % 16 == 0 && (out.off[p] * ss) % 16 == 0;
     }
-    const long groups = ((long)w_out + 3) / 4;          // (no chroma row has more quads than the luma row: 2 cw_out <= w_out + 1)
-    const int strips = (h + RES_STRIP - 1) / RES_STRIP;
-    const dim3 grid((unsigned)((groups + GEN_LANES - 1) / GEN_LANES), (unsigned)std::min((strips + GEN_ROWS - 1) / GEN_ROWS, 65535),
-                    (unsigned)std::min(n, 65535));
-    const dim3 block(GEN_LANES, GEN_ROWS);
+    // (no chroma row has more quads than the luma row: 2 cw_out <= w_out + 1)
+    const dim3 grid = general_grid(((long)w_out + 3) / 4, (h + RES_STRIP - 1) / RES_STRIP, n);
     const int shift = msb ? 16 - depth : 0, maxv = (1 << depth) - 1;
-    const bool semi = chroma == CHROMA_SEMI;
     const int pairs = std::max(taps_y, has_chroma ? taps_c : 0) / 2;
-    if (ss == 1)
-        launch_resample<uint8_t>(d_yuv, n, (long)yuv_frame_stride, d_out, (long)out_frame_stride, pl, shift, maxv, semi, fast, pairs, grid, block, st);
-    else
-        launch_resample<uint16_t>(d_yuv, n, (long)yuv_frame_stride / 2, d_out, (long)out_frame_stride / 2, pl, shift, maxv, semi, fast, pairs, grid,
-                                  block, st);
-    if (hipGetLastError() != hipSuccess) {
-        vse_set_error("vse_yuv_resample: launch failed");
-        return VSE_E_HIP;
-    }
-    return VSE_OK;
+    with_samples(ss, d_yuv, nullptr, d_out, yuv_frame_stride, 0, out_frame_stride, [&](auto pics) {
+        launch_resample(pics, n, pl, shift, maxv, chroma == CHROMA_SEMI, fast, pairs, grid, reinterpret_cast<hipStream_t>(stream));
+    });
+    return launched("vse_yuv_resample: launch failed");
 }
 
 int vse_yuv_vscale(vse_ctx* c, const void* d_yuv, int n, int w, int h_in, int h_out, int s0, int s1, int y0, int y1, int sub_x, int sub_y,
                    int chroma, int depth, int msb, const void* d_table_y, int taps_y, const void* d_table_c, int taps_c, int64_t yuv_frame_stride,
                    void* d_out, int64_t out_frame_stride, void* stream) {
-    // the whole pictures bound the products of rows and columns; the bands are parts of them
-    const bool whole = vse_yuv_frame_bytes(h_in, w, sub_x, sub_y, chroma, depth, 0) && vse_yuv_frame_bytes(h_out, w, sub_x, sub_y, chroma, depth, 0);
-    const bool bands = whole && s0 >= 0 && s0 < s1 && s1 <= h_in && y0 >= 0 && y0 < y1 && y1 <= h_out;
-    const size_t frame_in = bands ? vse_yuv_frame_bytes(s1 - s0, w, sub_x, sub_y, chroma, depth, s0 & sub_y) : 0;
-    const size_t frame_out = bands ? vse_yuv_frame_bytes(y1 - y0, w, sub_x, sub_y, chroma, depth, y0 & sub_y) : 0;
-    const int ss = depth > 8 ? 2 : 1;
-    const bool has_chroma = frame_in && chroma != CHROMA_NONE;
-    const int sy = sub_y & 1;
-    const int ch_out = (int)(((long)h_out + sy) >> sy);
+    // the whole pictures bound the products of rows and columns; the bands are parts of them, pictures of their own by their first row's parity
+    const YuvPlanes whole_in = yuv_planes(h_in, w, sub_x, sub_y, chroma, depth, 0), whole_out = yuv_planes(h_out, w, sub_x, sub_y, chroma, depth, 0);
+    const bool bands = whole_in.count && whole_out.count && s0 >= 0 && s0 < s1 && s1 <= h_in && y0 >= 0 && y0 < y1 && y1 <= h_out;
+    const YuvPlanes in = bands ? yuv_planes(s1 - s0, w, sub_x, sub_y, chroma, depth, s0 & sub_y) : YuvPlanes{};
+    const YuvPlanes out = bands ? yuv_planes(y1 - y0, w, sub_x, sub_y, chroma, depth, y0 & sub_y) : YuvPlanes{};
+    const int ss = sample_bytes(depth);
+    const size_t frame_in = (size_t)in.total * ss, frame_out = (size_t)out.total * ss;
+    const bool has_chroma = in.count > 1;
     const size_t table_y = frame_out ? vse_yuv_resample_table_bytes(h_out, taps_y) : 0;
-    const size_t table_c = has_chroma && frame_out ? vse_yuv_resample_table_bytes(ch_out, taps_c) : 0;
-    const auto odd = [](const void* p, int64_t stride) { return (reinterpret_cast<uintptr_t>(p) & 1) || (stride & 1); };
-    bool ok = c && d_yuv && d_out && n >= 1 && frame_in && frame_out && msb >= 0 && msb <= (ss == 2 ? 1 : 0) && table_y && d_table_y &&
-              aligned16(d_table_y) && (!has_chroma || (table_c && d_table_c && aligned16(d_table_c))) && yuv_frame_stride >= (int64_t)frame_in &&
-              out_frame_stride >= (int64_t)frame_out && !(ss == 2 && (odd(d_yuv, yuv_frame_stride) || odd(d_out, out_frame_stride)));
-    if (ok) {
-        // the output lies apart from the input pictures (first byte of the first to last byte of the last) and from both tables
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + (uintptr_t)(n - 1) * (uintptr_t)out_frame_stride + frame_out;
-        const auto apart = [&](const void* p, size_t bytes) {
-            const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-            return !p || !bytes || o1 <= a || a + bytes <= o0;
-        };
-        ok = apart(d_yuv, (size_t)(n - 1) * (size_t)yuv_frame_stride + frame_in) && apart(d_table_y, table_y) &&
-             apart(has_chroma ? d_table_c : nullptr, table_c);
+    const size_t table_c = has_chroma && frame_out ? vse_yuv_resample_table_bytes(whole_out.rows[1], taps_c) : 0;
+    if (!scaler_call_ok(c, d_yuv, d_out, n, frame_in, frame_out, ss, msb, d_table_y, table_y, d_table_c, table_c, has_chroma, yuv_frame_stride,
+                        out_frame_stride)) {
+        return Refusal(1000, "vse_yuv_vscale", n)
+            .add("frames of %d columns and %d -> %d rows, each of at most 2^31 - 1 pixels, stored rows %d:%d and output rows %d:%d inside them and "
+                 "not empty, ", w, h_in, h_out, s0, s1, y0, y1)
+            .format(sub_x, sub_y, chroma, depth, msb)
+            .scaler(taps_y, taps_c, d_table_y, d_table_c, yuv_frame_stride, frame_in, out_frame_stride, frame_out, d_yuv, d_out).send();
     }
-    if (!ok) {
-        char msg[1000];
-        snprintf(msg, sizeof msg, "vse_yuv_vscale: bad arguments (n %d, frames of %d columns and %d -> %d rows, each of at most 2^31 - 1 pixels, "
-                 "stored rows %d:%d and output rows %d:%d inside them and not empty, subsampling %d, %d of 0, 0 | 1, 0 | 1, 1, chroma %d of 0 (with "
-                 "subsampling 0, 0) | 1 | 2 (with subsampling 1, 1), depth %d of 8..16, msb %d of 0 | 1 (0 at depth 8), taps %d (luma) and %d "
-                 "(chroma) even and of 2..16, tables %p and %p 16-byte aligned (the chroma table only where the format has chroma), frame strides "
-                 "%lld of at least %zu and %lld (output) of at least %zu, bases %p, %p and strides 2-byte aligned for 2-byte samples, the output "
-                 "apart from the pictures and the tables)",
-                 n, w, h_in, h_out, s0, s1, y0, y1, sub_x, sub_y, chroma, depth, msb, taps_y, taps_c, d_table_y, d_table_c,
-                 (long long)yuv_frame_stride, frame_in, (long long)out_frame_stride, frame_out, d_yuv, d_out);
-        vse_set_error(msg);
-        return VSE_E_INVAL;
-    }
-    const int cw = (int)(((long)w + (sub_x & 1)) >> (sub_x & 1));
-    const int rlc = chroma == CHROMA_SEMI ? 2 * cw : cw;
-    const int cb0 = s0 >> sy, cb1 = ((s1 - 1) >> sy) + 1, co0 = y0 >> sy, co1 = ((y1 - 1) >> sy) + 1;
     VsPlanes pl = {};
-    pl.count = chroma == CHROMA_NONE ? 1 : chroma == CHROMA_PLANAR ? 3 : 2;
-    for (int p = 0; p < pl.count; ++p) {
-        const bool luma = p == 0;
-        const uint8_t* table = reinterpret_cast<const uint8_t*>(luma ? d_table_y : d_table_c);
-        pl.rl[p] = luma ? w : rlc;
-        pl.ph[p] = luma ? h_in : (int)(((long)h_in + sy) >> sy);
-        pl.b0[p] = luma ? s0 : cb0;
-        pl.b1[p] = luma ? s1 : cb1;
-        pl.o0[p] = luma ? y0 : co0;
-        pl.o1[p] = luma ? y1 : co1;
-        pl.taps[p] = luma ? taps_y : taps_c;
-        pl.off_in[p] = luma ? 0 : (long)(s1 - s0) * w + (long)(p - 1) * (cb1 - cb0) * rlc;
-        pl.off_out[p] = luma ? 0 : (long)(y1 - y0) * w + (long)(p - 1) * (co1 - co0) * rlc;
-        pl.top[p] = reinterpret_cast<const int*>(table);
-        pl.coef[p] = reinterpret_cast<const unsigned*>(table + 4L * (luma ? h_out : ch_out));
-    }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    pl.count = in.count;
     // the fast kernel: every plane's rows of both bands start on a 16-byte boundary and are whole 16-byte runs
     bool fast = aligned16(d_yuv) && aligned16(d_out) && yuv_frame_stride % 16 == 0 && out_frame_stride % 16 == 0;
-    for (int p = 0; p < pl.count; ++p)
-        fast = fast && ((long)pl.rl[p] * ss) % 16 == 0 && (pl.off_in[p] * ss) % 16 == 0 && (pl.off_out[p] * ss) % 16 == 0;
-    const long widest = std::max((long)w, (long)(pl.count > 1 ? rlc : 0)), per = fast ? 16 / ss : 4;
-    const long groups = (widest + per - 1) / per;
-    const int rows = y1 - y0;                                     // (no chroma plane has more output rows than luma)
-    const dim3 grid((unsigned)((groups + GEN_LANES - 1) / GEN_LANES), (unsigned)std::min((rows + GEN_ROWS - 1) / GEN_ROWS, 65535),
-                    (unsigned)std::min(n, 65535));
-    const dim3 block(GEN_LANES, GEN_ROWS);
+    long widest = 0;
+    for (int p = 0; p < pl.count; ++p) {
+        const int sy = p ? sub_y : 0;
+        pl.rl[p] = (int)in.row[p];
+        pl.ph[p] = whole_in.rows[p];
+        pl.b0[p] = s0 >> sy;
+        pl.b1[p] = pl.b0[p] + in.rows[p];
+        pl.o0[p] = y0 >> sy;
+        pl.o1[p] = pl.o0[p] + out.rows[p];
+        pl.taps[p] = p ? taps_c : taps_y;
+        pl.off_in[p] = in.off[p];
+        pl.off_out[p] = out.off[p];
+        set_table(pl.top[p], pl.coef[p], p ? d_table_c : d_table_y, whole_out.rows[p]);
+        fast = fast && (in.row[p] * ss) % 16 == 0 && (in.off[p] * ss) % 16 == 0 && (out.off[p] * ss) % 16 == 0;
+        widest = std::max(widest, in.row[p]);
+    }
+    const long per = fast ? 16 / ss : 4;
+    const dim3 grid = general_grid((widest + per - 1) / per, y1 - y0, n);          // (no chroma plane has more output rows than luma)
     const int shift = msb ? 16 - depth : 0, maxv = (1 << depth) - 1;
     const int pairs = std::max(taps_y, has_chroma ? taps_c : 0) / 2;
-    if (ss == 1)
-        launch_vscale<uint8_t>(d_yuv, n, (long)yuv_frame_stride, d_out, (long)out_frame_stride, pl, shift, maxv, fast, pairs, grid, block, st);
-    else
-        launch_vscale<uint16_t>(d_yuv, n, (long)yuv_frame_stride / 2, d_out, (long)out_frame_stride / 2, pl, shift, maxv, fast, pairs, grid, block, st);
-    if (hipGetLastError() != hipSuccess) {
-        vse_set_error("vse_yuv_vscale: launch failed");
-        return VSE_E_HIP;
-    }
-    return VSE_OK;
+    with_samples(ss, d_yuv, nullptr, d_out, yuv_frame_stride, 0, out_frame_stride, [&](auto pics) {
+        launch_vscale(pics, n, pl, shift, maxv, fast, pairs, grid, reinterpret_cast<hipStream_t>(stream));
+    });
+    return launched("vse_yuv_vscale: launch failed");
 }
 
 }  // extern "C"

@@ -318,6 +318,25 @@ def _torch():
     return torch
 
 
+def _packed_stride(a, n, frame, what):
+    """The frame stride in bytes of the uint8 tensor `a` that holds n packed pictures of `frame` bytes: 1-D (back to back) or 2-D
+    [n, stride]."""
+    assert str(a.dtype) == "torch.uint8" and a.dim() in (1, 2) and a.stride(-1) == 1, what
+    if a.dim() == 2:
+        assert a.shape[0] == n and a.shape[1] >= frame, (what, tuple(a.shape), n, frame)
+        return a.stride(0) if n > 1 else max(a.stride(0), frame)
+    assert a.numel() >= n * frame, (what, a.numel(), n, frame)
+    return frame
+
+
+def _prev_pictures(prev, prev_stride, n, sstride):
+    """(pointer, frame stride) of the previous pictures of yuv_deinterlace / yuv_field_match; (None, 0) without any"""
+    if prev is None:
+        return None, 0
+    assert str(prev.dtype) == "torch.uint8" and prev.stride(-1) == 1
+    return C.c_void_p(prev.data_ptr()), int(prev_stride) if prev_stride is not None else (prev.stride(0) if prev.dim() == 2 and n > 1 else sstride)
+
+
 class Context:
     """One per (process, device)."""
 
@@ -1097,14 +1116,8 @@ class Context:
             raise VseError(f"yuv420_to_bgr: matrix {matrix!r} is not one of {sorted(YUV_MATRICES)} (0 | 1)")
         if layout not in YUV_LAYOUTS:
             raise VseError(f"yuv420_to_bgr: layout {layout!r} is not one of {sorted(YUV_LAYOUTS)}")
-        assert packed_u8.dtype == t.uint8 and packed_u8.dim() in (1, 2) and packed_u8.stride(-1) == 1
         frame = self.lib.vse_yuv420_frame_bytes(h, w, row_parity)
-        if packed_u8.dim() == 2:
-            assert packed_u8.shape[0] == n and packed_u8.shape[1] >= frame, (tuple(packed_u8.shape), n, frame)
-            sstride = packed_u8.stride(0) if n > 1 else max(packed_u8.stride(0), frame)
-        else:
-            assert packed_u8.numel() >= n * frame, (packed_u8.numel(), n, frame)
-            sstride = frame
+        sstride = _packed_stride(packed_u8, n, frame, "packed_u8")
         if out is None:
             out = t.empty((max(n, 0), max(h, 0), max(w, 0), 3), dtype=t.uint8, device=self.tdev)
         assert out.dtype == t.uint8 and tuple(out.shape) == (n, h, w, 3) and out.stride(3) == 1 and out.stride(2) == 3
@@ -1143,14 +1156,8 @@ class Context:
         matrix = YUV_FORMAT_MATRICES.get(fmt.matrix, fmt.matrix)
         if matrix not in (0, 1, 2):
             raise VseError(f"yuv_to_bgr: matrix {fmt.matrix!r} is not one of {sorted(YUV_FORMAT_MATRICES)} (0 | 1 | 2)")
-        assert packed.dtype == t.uint8 and packed.dim() in (1, 2) and packed.stride(-1) == 1
         frame = self.lib.vse_yuv_frame_bytes(h, w, int(fmt.sub_x), int(fmt.sub_y), int(fmt.chroma), int(fmt.depth), row_parity)
-        if packed.dim() == 2:
-            assert packed.shape[0] == n and packed.shape[1] >= frame, (tuple(packed.shape), n, frame)
-            sstride = packed.stride(0) if n > 1 else max(packed.stride(0), frame)
-        else:
-            assert packed.numel() >= n * frame, (packed.numel(), n, frame)
-            sstride = frame
+        sstride = _packed_stride(packed, n, frame, "packed")
         if out is None:
             out = t.empty((max(n, 0), max(h, 0), max(w, 0), 3), dtype=t.uint8, device=self.tdev)
         assert out.dtype == t.uint8 and tuple(out.shape) == (n, h, w, 3) and out.stride(3) == 1 and out.stride(2) == 3
@@ -1181,23 +1188,11 @@ class Context:
         if mode not in (0, 1):
             raise VseError(f"yuv_deinterlace: mode {mode!r} is not one of {sorted(DEINTERLACE_MODES)} (0 | 1)")
         frame = self.lib.vse_yuv_frame_bytes(h, w, int(fmt.sub_x), int(fmt.sub_y), int(fmt.chroma), int(fmt.depth), 0)
-
-        def stride_of(a, what):
-            assert a.dtype == t.uint8 and a.dim() in (1, 2) and a.stride(-1) == 1, what
-            if a.dim() == 2:
-                assert a.shape[0] == n and a.shape[1] >= frame, (what, tuple(a.shape), n, frame)
-                return a.stride(0) if n > 1 else max(a.stride(0), frame)
-            assert a.numel() >= n * frame, (what, a.numel(), n, frame)
-            return frame
-        sstride = stride_of(packed, "packed")
+        sstride = _packed_stride(packed, n, frame, "packed")
         if out is None:
             out = t.empty((max(n, 0), (frame + 15) & ~15), dtype=t.uint8, device=self.tdev)
-        ostride = stride_of(out, "out")
-        pptr, pstride = None, 0
-        if prev is not None:
-            assert prev.dtype == t.uint8 and prev.stride(-1) == 1
-            pptr = C.c_void_p(prev.data_ptr())
-            pstride = int(prev_stride) if prev_stride is not None else (prev.stride(0) if prev.dim() == 2 and n > 1 else sstride)
+        ostride = _packed_stride(out, n, frame, "out")
+        pptr, pstride = _prev_pictures(prev, prev_stride, n, sstride)
         _check(self.lib.vse_yuv_deinterlace(self.handle, C.c_void_p(packed.data_ptr()), pptr, n, h, w, int(fmt.sub_x), int(fmt.sub_y),
                                             int(fmt.chroma), int(fmt.depth), int(fmt.msb), int(keep), mode, int(thresh), sstride, pstride,
                                             C.c_void_p(out.data_ptr()), ostride, self.stream()), "vse_yuv_deinterlace")
@@ -1213,26 +1208,14 @@ class Context:
         t = self.torch
         n, h, w = int(n), int(h), int(w)
         frame = self.lib.vse_yuv_frame_bytes(h, w, int(fmt.sub_x), int(fmt.sub_y), int(fmt.chroma), int(fmt.depth), 0)
-
-        def stride_of(a, what):
-            assert a.dtype == t.uint8 and a.dim() in (1, 2) and a.stride(-1) == 1, what
-            if a.dim() == 2:
-                assert a.shape[0] == n and a.shape[1] >= frame, (what, tuple(a.shape), n, frame)
-                return a.stride(0) if n > 1 else max(a.stride(0), frame)
-            assert a.numel() >= n * frame, (what, a.numel(), n, frame)
-            return frame
-        sstride = stride_of(packed, "packed")
+        sstride = _packed_stride(packed, n, frame, "packed")
         if out is None:
             out = t.empty((max(n, 0), (frame + 15) & ~15), dtype=t.uint8, device=self.tdev)
-        ostride = stride_of(out, "out")
+        ostride = _packed_stride(out, n, frame, "out")
         if stats is None:
             stats = t.empty((max(n, 0), 4), dtype=t.int32, device=self.tdev)
         assert stats.dtype == t.int32 and tuple(stats.shape) == (n, 4) and stats.is_contiguous()
-        pptr, pstride = None, 0
-        if prev is not None:
-            assert prev.dtype == t.uint8 and prev.stride(-1) == 1
-            pptr = C.c_void_p(prev.data_ptr())
-            pstride = int(prev_stride) if prev_stride is not None else (prev.stride(0) if prev.dim() == 2 and n > 1 else sstride)
+        pptr, pstride = _prev_pictures(prev, prev_stride, n, sstride)
         _check(self.lib.vse_yuv_field_match(self.handle, C.c_void_p(packed.data_ptr()), pptr, n, h, w, int(fmt.sub_x), int(fmt.sub_y),
                                             int(fmt.chroma), int(fmt.depth), int(fmt.msb), int(keep), int(comb_thresh),
                                             -1 if comb_limit is None else int(comb_limit), int(thresh), sstride, pstride,
@@ -1240,38 +1223,48 @@ class Context:
                "vse_yuv_field_match")
         return out, stats
 
+    def _upload_tables(self, who, cache, key, source, fmt, axis, edge, lengths, support=None):
+        """resample_tables and vscale_tables: source.tables(fmt) / source.packed(fmt) checked, uploaded once under `key` and kept in
+        `cache`.  axis, edge: the words of the messages ("columns", "left" | "rows", "top"); lengths: the entries of the luma and the
+        chroma table; support: the stored rows of the two planes, where each entry gets its ingest.table_support(edge, coef, rows)."""
+        with self._tone_lock:
+            hit = cache.get(key)
+            if hit is None:
+                t = self.torch
+                devs = []
+                for p, (what, tab, raw, size) in enumerate(zip(("luma", "chroma"), source.tables(fmt), source.packed(fmt), lengths)):
+                    if tab is None:
+                        devs.append(None)
+                        continue
+                    first, coef = np.asarray(tab[0]), np.asarray(tab[1])
+                    taps = int(coef.shape[1]) if coef.ndim == 2 else 0
+                    host = np.frombuffer(raw, np.uint8)
+                    want = self.lib.vse_yuv_resample_table_bytes(size, taps)
+                    if not want or first.shape != (size,) or coef.shape != (size, taps) or host.size != want:
+                        raise VseError(f"{who}: the {what} table of {size} {axis} has {edge} {first.shape}, coef {coef.shape} (taps even, "
+                                       f"2..16) and {host.size} bytes of {want}")
+                    if np.abs(first.astype(np.int64)).max() > 1 << 30 or np.abs(coef.astype(np.int64)).sum(axis=1).max() > 32767:
+                        raise VseError(f"{who}: the {what} table breaks |{edge}| <= 2^30 or a row's sum of |coef| <= 32767 (max "
+                                       f"{int(np.abs(coef.astype(np.int64)).sum(axis=1).max())}): int32 would not be exact")
+                    dev = (t.from_numpy(host.copy()).to(self.tdev), taps)
+                    if support is not None:
+                        from .ingest import table_support
+                        dev += table_support(first, coef, support[p])
+                    devs.append(dev)
+                if devs[0] is None or (devs[1] is None) != (not fmt.chroma):
+                    raise VseError(f"{who}: {fmt} takes a luma table and {'a' if fmt.chroma else 'no'} chroma table")
+                t.cuda.current_stream(self.tdev).synchronize()          # any stream may read them from here on
+                hit = cache[key] = tuple(devs)
+            return hit
+
     def resample_tables(self, resample, fmt):
         """The device copies of an ingest.Resample's tables for the format `fmt` (anything hashable with in_width, out_width, tables(fmt)
         -> ((left, coef), (left, coef) | None) and packed(fmt) -> (luma bytes, chroma bytes | None)): ((cuda uint8 table, taps), the same
         for chroma or None), uploaded on first use and kept for the context's life.  vse_yuv_resample cannot read them, so the bounds
         that keep its int32 sums exact are checked here: |left| <= 2^30 and every row's sum of |coef| <= 32767."""
-        key = (resample, int(fmt.sub_x), bool(fmt.chroma))
-        with self._tone_lock:
-            hit = self._resample_tables.get(key)
-            if hit is None:
-                t = self.torch
-                cw = (int(resample.out_width) + int(fmt.sub_x)) >> int(fmt.sub_x)
-                devs = []
-                for what, tab, raw, cols in zip(("luma", "chroma"), resample.tables(fmt), resample.packed(fmt), (int(resample.out_width), cw)):
-                    if tab is None:
-                        devs.append(None)
-                        continue
-                    left, coef = np.asarray(tab[0]), np.asarray(tab[1])
-                    taps = int(coef.shape[1]) if coef.ndim == 2 else 0
-                    host = np.frombuffer(raw, np.uint8)
-                    want = self.lib.vse_yuv_resample_table_bytes(cols, taps)
-                    if not want or left.shape != (cols,) or coef.shape != (cols, taps) or host.size != want:
-                        raise VseError(f"resample_tables: the {what} table of {cols} columns has left {left.shape}, coef {coef.shape} (taps even, "
-                                       f"2..16) and {host.size} bytes of {want}")
-                    if np.abs(left.astype(np.int64)).max() > 1 << 30 or np.abs(coef.astype(np.int64)).sum(axis=1).max() > 32767:
-                        raise VseError(f"resample_tables: the {what} table breaks |left| <= 2^30 or a row's sum of |coef| <= 32767 (max "
-                                       f"{int(np.abs(coef.astype(np.int64)).sum(axis=1).max())}): int32 would not be exact")
-                    devs.append((t.from_numpy(host.copy()).to(self.tdev), taps))
-                if devs[0] is None or (devs[1] is None) != (not fmt.chroma):
-                    raise VseError(f"resample_tables: {fmt} takes a luma table and {'a' if fmt.chroma else 'no'} chroma table")
-                t.cuda.current_stream(self.tdev).synchronize()          # any stream may read them from here on
-                hit = self._resample_tables[key] = tuple(devs)
-            return hit
+        sx, w_out = int(fmt.sub_x), int(resample.out_width)
+        return self._upload_tables("resample_tables", self._resample_tables, (resample, sx, bool(fmt.chroma)), resample, fmt, "columns", "left",
+                                   (w_out, (w_out + sx) >> sx))
 
     def yuv_resample(self, packed, n, h, w_in, fmt, resample, row_parity=0, out=None):
         """packed: cuda uint8 holding n packed (sub-)frames of h x w_in pixels of the format `fmt` (as yuv_to_bgr's), 1-D (back to back) or
@@ -1286,18 +1279,10 @@ class Context:
         form = (int(fmt.sub_x), int(fmt.sub_y), int(fmt.chroma), int(fmt.depth))
         frame_in = self.lib.vse_yuv_frame_bytes(h, w_in, *form, row_parity)
         frame_out = self.lib.vse_yuv_frame_bytes(h, w_out, *form, row_parity)
-
-        def stride_of(a, frame, what):
-            assert a.dtype == t.uint8 and a.dim() in (1, 2) and a.stride(-1) == 1, what
-            if a.dim() == 2:
-                assert a.shape[0] == n and a.shape[1] >= frame, (what, tuple(a.shape), n, frame)
-                return a.stride(0) if n > 1 else max(a.stride(0), frame)
-            assert a.numel() >= n * frame, (what, a.numel(), n, frame)
-            return frame
-        sstride = stride_of(packed, frame_in, "packed")
+        sstride = _packed_stride(packed, n, frame_in, "packed")
         if out is None:
             out = t.empty((max(n, 0), (frame_out + 15) & ~15), dtype=t.uint8, device=self.tdev)
-        ostride = stride_of(out, frame_out, "out")
+        ostride = _packed_stride(out, n, frame_out, "out")
         luma, chroma = self.resample_tables(resample, fmt)
         _check(self.lib.vse_yuv_resample(self.handle, C.c_void_p(packed.data_ptr()), n, h, w_in, w_out, *form, int(fmt.msb), row_parity,
                                          C.c_void_p(luma[0].data_ptr()), luma[1], None if chroma is None else C.c_void_p(chroma[0].data_ptr()),
@@ -1312,36 +1297,9 @@ class Context:
         of the plane that it reads with a coefficient other than zero (ingest.table_support), for the band check of yuv_vscale.
         vse_yuv_vscale cannot read the tables, so the bounds that keep its int32 sums exact are checked here: |top| <= 2^30 and every
         row's sum of |coef| <= 32767."""
-        from .ingest import table_support
-        sy = int(fmt.sub_y)
-        key = (vscale, sy, bool(fmt.chroma))
-        with self._tone_lock:
-            hit = self._vscale_tables.get(key)
-            if hit is None:
-                t = self.torch
-                h_in, h_out = int(vscale.in_height), int(vscale.out_height)
-                devs = []
-                for what, tab, raw, rows, ph in zip(("luma", "chroma"), vscale.tables(fmt), vscale.packed(fmt), (h_out, (h_out + sy) >> sy),
-                                                    (h_in, (h_in + sy) >> sy)):
-                    if tab is None:
-                        devs.append(None)
-                        continue
-                    top, coef = np.asarray(tab[0]), np.asarray(tab[1])
-                    taps = int(coef.shape[1]) if coef.ndim == 2 else 0
-                    host = np.frombuffer(raw, np.uint8)
-                    want = self.lib.vse_yuv_resample_table_bytes(rows, taps)
-                    if not want or top.shape != (rows,) or coef.shape != (rows, taps) or host.size != want:
-                        raise VseError(f"vscale_tables: the {what} table of {rows} rows has top {top.shape}, coef {coef.shape} (taps even, "
-                                       f"2..16) and {host.size} bytes of {want}")
-                    if np.abs(top.astype(np.int64)).max() > 1 << 30 or np.abs(coef.astype(np.int64)).sum(axis=1).max() > 32767:
-                        raise VseError(f"vscale_tables: the {what} table breaks |top| <= 2^30 or a row's sum of |coef| <= 32767 (max "
-                                       f"{int(np.abs(coef.astype(np.int64)).sum(axis=1).max())}): int32 would not be exact")
-                    devs.append((t.from_numpy(host.copy()).to(self.tdev), taps) + table_support(top, coef, ph))
-                if devs[0] is None or (devs[1] is None) != (not fmt.chroma):
-                    raise VseError(f"vscale_tables: {fmt} takes a luma table and {'a' if fmt.chroma else 'no'} chroma table")
-                t.cuda.current_stream(self.tdev).synchronize()          # any stream may read them from here on
-                hit = self._vscale_tables[key] = tuple(devs)
-            return hit
+        sy, h_in, h_out = int(fmt.sub_y), int(vscale.in_height), int(vscale.out_height)
+        return self._upload_tables("vscale_tables", self._vscale_tables, (vscale, sy, bool(fmt.chroma)), vscale, fmt, "rows", "top",
+                                   (h_out, (h_out + sy) >> sy), support=(h_in, (h_in + sy) >> sy))
 
     def yuv_vscale(self, packed, n, h_in, w, fmt, vscale, s0, s1, y0, y1, out=None):
         """packed: cuda uint8 holding n packed bands of stored luma rows [s0, s1) of pictures of h_in x w pixels of the format `fmt` (what
@@ -1371,18 +1329,10 @@ class Context:
                                f"rows {lo}:{hi}: the band does not cover the support")
         frame_in = self.lib.vse_yuv_frame_bytes(s1 - s0, w, *form, s0 & sy)
         frame_out = self.lib.vse_yuv_frame_bytes(y1 - y0, w, *form, y0 & sy)
-
-        def stride_of(a, frame, what):
-            assert a.dtype == t.uint8 and a.dim() in (1, 2) and a.stride(-1) == 1, what
-            if a.dim() == 2:
-                assert a.shape[0] == n and a.shape[1] >= frame, (what, tuple(a.shape), n, frame)
-                return a.stride(0) if n > 1 else max(a.stride(0), frame)
-            assert a.numel() >= n * frame, (what, a.numel(), n, frame)
-            return frame
-        sstride = stride_of(packed, frame_in, "packed")
+        sstride = _packed_stride(packed, n, frame_in, "packed")
         if out is None:
             out = t.empty((max(n, 0), (frame_out + 15) & ~15), dtype=t.uint8, device=self.tdev)
-        ostride = stride_of(out, frame_out, "out")
+        ostride = _packed_stride(out, n, frame_out, "out")
         _check(self.lib.vse_yuv_vscale(self.handle, C.c_void_p(packed.data_ptr()), n, w, h_in, h_out, s0, s1, y0, y1, *form, int(fmt.msb),
                                        C.c_void_p(luma[0].data_ptr()), luma[1], None if chroma is None else C.c_void_p(chroma[0].data_ptr()),
                                        0 if chroma is None else chroma[1], sstride, C.c_void_p(out.data_ptr()), ostride, self.stream()),
