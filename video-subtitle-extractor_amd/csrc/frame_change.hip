@@ -21,15 +21,17 @@
 //                                     words of every frame kept in the caller's buffer.  One template, the extra output a compile-time kind.
 //   frame_cells_export_kernel,        one threshold's slice of a cells state as a vse_frame_change state, and the counts of any rectangle
 //   frame_masks_replay_kernel         of the region out of the kept mask words, as frame_change_kernel would have counted them on the frames.
-//   frame_hold_kernel                 vse_frame_hold: only edge pixels that hold still for `hold` frames are counted, so that the edges of a
-//                                     moving background drop out.
-//   frame_cells_hold_kernel           vse_frame_cells_hold: the cells and their automaton at several thresholds on the held masks.
+//   frame_hold_kernel,                vse_frame_hold: only edge pixels that hold still for `hold` frames are counted, so that the edges of a
+//   frame_masks_replay_hold_kernel    moving background drop out; and vse_frame_masks_replay_hold, the same walk (frame_hold_body) on a
+//                                     rectangle of the region with the kept mask words in place of the frames.
+//   frame_cells_hold_kernel           vse_frame_cells_hold and _hold_masks: the cells and their automaton at several thresholds on the held
+//                                     masks, optionally with the EDGE words of every frame kept in the caller's buffer.
 //   frame_focus_kernel                vse_frame_focus: per frame, the number of edge pixels that were edge pixels one frame earlier and the
 //                                     sum of their gradients.
 //   frame_hold_bounded_kernel,        vse_frame_hold_bounded: the held-edge walk, but only runs of hold .. max_hold frames are counted, so that
 //   frame_hold_rows_kernel            the edges of a background that stands still drop out too.
 //   frame_cells_hold_bounded_kernel   vse_frame_cells_hold_bounded: the cells and their automaton at several thresholds on the bounded masks.
-// The launchers of the first eight follow frame_focus_kernel; the two bounded sections each end with their own.
+// The launchers of the first nine follow frame_focus_kernel; the two bounded sections each end with their own.
 //
 // What the kernels share is written once where that leaves their code as it was: the tile (tile_lane, tile_masks, tile_masks_multi), the
 // automaton (CellRuns, with the load and store of its state), the small pieces of a chunk (zero_steps, edge_bit), and on the host what
@@ -528,17 +530,47 @@ __global__ __launch_bounds__(256) void frame_masks_replay_kernel(const unsigned 
 // the pixel's bit in the last mask that was counted.  Zero is the state before frame 1.
 constexpr int HOLD_WORD_BYTES = 64 * 2;
 
-__global__ __launch_bounds__(FC_WAVES * 64) void frame_hold_kernel(const uint8_t* __restrict__ src, int n, int steps, long pitch, long fstride,
-                                                                   int x0, int ih, int iw, int wpr, int thresh, int hold, int skip,
-                                                                   unsigned short* __restrict__ state, int fresh, int* __restrict__ counts) {
+// Where the edge words of a chunk's real steps come from is a policy of the body, which is otherwise one text for both kernels:
+//   HoldFrames  the frames (tile_masks): frame_hold_kernel;
+//   HoldSlots   the words vse_frame_cells_masks / vse_frame_cells_hold_masks kept (replay_word): frame_masks_replay_hold_kernel.
+// fill(c0, real, msk) leaves msk[tl][k] = the edge word of the tile's interior row k at step c0 + tl for tl < real, zero for the rows
+// beyond the area; `rows` are the tile's interior rows that lie in the area.
+struct HoldFrames {
+    const uint8_t* __restrict__ src;          // the tile's first halo row in frame 0
+    long pitch, fstride;
+    int thresh;
+    TileLane t;
+    __device__ __forceinline__ int rows() const { return t.rows; }
+    __device__ __forceinline__ void fill(int c0, int real, unsigned long long (*msk)[FC_ROWS]) const {
+        tile_masks(src, c0, real, pitch, fstride, t, thresh, msk);
+    }
+};
+
+struct HoldSlots {
+    const unsigned long long* __restrict__ slice;          // threshold q's first cell in the slot of step 0
+    long slot_words;
+    int gx;
+    ReplayRect r;
+    int iy0, w;                               // the tile's first interior row in the rectangle, and its word of a row
+    __device__ __forceinline__ int rows() const { return min(FC_ROWS, r.ih - iy0); }
+    // thread 8 tl + k fetches the word of step tl and row k: eight lanes read the one or two 64-byte lines of a slot's cell row group
+    __device__ __forceinline__ void fill(int c0, int real, unsigned long long (*msk)[FC_ROWS]) const {
+        static_assert(FC_WAVES * 64 == FC_CHUNK * FC_ROWS, "a thread per step and row of the chunk");
+        const int tl = threadIdx.x / FC_ROWS, k = threadIdx.x % FC_ROWS;
+        if (tl < real) msk[tl][k] = iy0 + k < r.ih ? replay_word(slice + (long)(c0 + tl) * slot_words, gx, r, iy0 + k, w) : 0ull;
+    }
+};
+
+// block (w, iy0 / FC_ROWS) owns the tile's state words state[((iy0 + k) * wpr + w) * 64 ..] for all steps of the call
+template <class SRC>
+__device__ __forceinline__ void frame_hold_body(const SRC& source, int n, int steps, int iy0, int w, int wpr, int hold, int skip,
+                                                unsigned short* __restrict__ state, int fresh, int* __restrict__ counts) {
     __shared__ unsigned long long msk[FC_CHUNK][FC_ROWS];
     __shared__ unsigned long long prv[FC_ROWS];
     static_assert(FC_WAVES == FC_ROWS, "wave k walks interior row k of the tile");
     static_assert(FC_CHUNK == 64, "the frames of a chunk are the lanes of a wave");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int w = blockIdx.x, iy0 = blockIdx.y * FC_ROWS;
-    const TileLane t = tile_lane(w, iy0, ih, iw, x0);
-    const bool mine = wave < t.rows;           // wave-uniform; the words of the other rows stay zero
+    const bool mine = wave < source.rows();    // wave-uniform; the words of the other rows stay zero
     unsigned short* st = state + ((long)(iy0 + wave) * wpr + w) * 64 + lane;
     int run = 0, cover = 0;
     bool held = false;
@@ -556,7 +588,7 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_hold_kernel(const uint8_t
     for (int c0 = 0; c0 < steps; c0 += FC_CHUNK) {
         const int cn = min(FC_CHUNK, steps - c0);
         const int real = max(0, min(cn, n - c0));          // the steps after frame n are the flush: no edge anywhere
-        tile_masks(src + (long)iy0 * pitch, c0, real, pitch, fstride, t, thresh, msk);
+        source.fill(c0, real, msk);
         for (int i = real * FC_ROWS + threadIdx.x; i < cn * FC_ROWS; i += FC_WAVES * 64) msk[i / FC_ROWS][i % FC_ROWS] = 0ull;
         __syncthreads();
         if (mine) {
@@ -600,6 +632,29 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_hold_kernel(const uint8_t
     if (mine) *st = (unsigned short)(run | (cover << 6) | ((int)held << 12));
 }
 
+__global__ __launch_bounds__(FC_WAVES * 64) void frame_hold_kernel(const uint8_t* __restrict__ src, int n, int steps, long pitch, long fstride,
+                                                                   int x0, int ih, int iw, int wpr, int thresh, int hold, int skip,
+                                                                   unsigned short* __restrict__ state, int fresh, int* __restrict__ counts) {
+    const int w = blockIdx.x, iy0 = blockIdx.y * FC_ROWS;
+    const HoldFrames source = {src + (long)iy0 * pitch, pitch, fstride, thresh, tile_lane(w, iy0, ih, iw, x0)};
+    frame_hold_body(source, n, steps, iy0, w, wpr, hold, skip, state, fresh, counts);
+}
+
+// ---- vse_frame_masks_replay_hold --------------------------------------------------------------------------------------------------
+// frame_hold_kernel on a rectangle of the region, its edge words taken from the kept masks instead of the frames (an edge pixel depends on
+// its four neighbours and the threshold only, not on the area it is counted in: frame_masks_replay_kernel above).  Grid and block are
+// frame_hold_kernel's on the rectangle: block (w, j) owns word w of the interior rows 8 j .. 8 j + 7 of the rectangle, and the walk, the
+// ballots, the counting and the state are frame_hold_body's, so the state this leaves is vse_frame_hold's of that rectangle.  `slice`
+// points at threshold q's first cell in the slot of step 0; the n real steps read the slots of steps 0 .. n - 1, the flush steps none.
+__global__ __launch_bounds__(FC_WAVES * 64) void frame_masks_replay_hold_kernel(const unsigned long long* __restrict__ slice, long slot_words,
+                                                                                int gx, ReplayRect r, int n, int steps, int hold, int skip,
+                                                                                unsigned short* __restrict__ state, int fresh,
+                                                                                int* __restrict__ counts) {
+    const int w = blockIdx.x, iy0 = blockIdx.y * FC_ROWS;
+    const HoldSlots source = {slice, slot_words, gx, r, iy0, w};
+    frame_hold_body(source, n, steps, iy0, w, r.wpr, hold, skip, state, fresh, counts);
+}
+
 // ---- vse_frame_cells_hold --------------------------------------------------------------------------------------------------------
 // The locator's cells (frame_cells_multi_kernel) on the held masks of frame_hold_kernel, for moving backgrounds: a block is a cell for all
 // frames of the call and for NT thresholds.  Three stages per chunk of steps, all pieces of the kernels above:
@@ -614,17 +669,31 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_hold_kernel(const uint8_t
 // State: pix[((q * ih + interior row) * wpr + word) * 64 + lane] = frame_hold_kernel's uint16 of threshold q (held: the pixel's bit in the
 // last word that was counted), and open_runs[q * cells + cell] = the length of the cell's open run.  Totals as frame_cells_multi_kernel.
 // cell_counts (nullable): [NT][count_rows][cells][3] = e, a, v of row `row` of this call, each written by the one block that owns it.
-template <int NT>
+// OUT and the trailing pack x are frame_cells_multi_kernel's: CELLS_ONLY (vse_frame_cells_hold; no argument, and the code this kernel
+// compiled to before it had the parameter: the same registers, LDS and scratch at every NT) or CELLS_MASKS (vse_frame_cells_hold_masks;
+// unsigned long long* masks, long slot0): the EDGE words a chunk's real steps leave in LDS, before the walk replaces them by held words,
+// go to the caller's buffer in that kernel's layout and by its store loop, so a call writes bit for bit what frame_cells_multi_kernel<NT,
+// CELLS_MASKS> writes for the same frames.  The loop has wave q reading all eight rows of threshold q while the walk has wave k
+// overwriting row k of every threshold, so this kind has one more barrier per chunk, between the stores and the walk.  Only the `real`
+// steps are stored (step c0 + tl < n of the call is slot slot0 + c0 + tl < cap, checked by the launcher's caller); a flush's steps have
+// no slot.  The other form, each walking wave storing its own row's words from the registers it holds them in (lane = step, 8-byte stores
+// a slot apart, no barrier), was built and measured: 1.000-1.002x the kernel without masks at NT = 1 against 1.007x for this form, but
+// 1.032-1.034x against 1.018-1.021x at NT = 8 (EXPERIMENTS.md, "Area found in the hold selector's pass").  VGPRs with masks at NT = 1 .. 8: 107 109 109 112 113 113 115 121 against 101 103 103 107 108 109 110 116 without; LDS as
+// without; no scratch; four waves per SIMD either way.
+template <int NT, int OUT, class... X>
 __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_hold_kernel(const uint8_t* __restrict__ src, int n, int steps, long pitch,
                                                                          long fstride, int x0, int ih, int iw, CellThresholds th, CellRule rule,
                                                                          int hold, int skip, unsigned short* __restrict__ pix,
                                                                          int* __restrict__ open_runs, int fresh, int flush,
-                                                                         int* __restrict__ totals, int* __restrict__ cell_counts, int count_rows) {
+                                                                         int* __restrict__ totals, int* __restrict__ cell_counts, int count_rows,
+                                                                         X... x) {
     __shared__ unsigned long long msk[NT * FC_CHUNK * FC_ROWS];           // [NT][FC_CHUNK][FC_ROWS]
     __shared__ unsigned long long prv[NT * FC_ROWS];
     static_assert(FC_WAVES == FC_ROWS, "wave k walks interior row k of the tile");
     static_assert(FC_CHUNK == 64, "the steps of a chunk are the lanes of a wave");
     static_assert(NT >= 1 && NT <= FC_WAVES, "wave q owns threshold q");
+    static_assert(OUT == CELLS_ONLY || OUT == CELLS_MASKS, "the held cells keep masks or nothing");
+    static_assert(sizeof...(X) == (OUT == CELLS_ONLY ? 0 : 2), "the pack is the kind's arguments");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int iy0 = blockIdx.y * FC_ROWS, wpr = gridDim.x;
     const long cell = (long)blockIdx.y * gridDim.x + blockIdx.x, cells = (long)gridDim.y * gridDim.x;
@@ -653,6 +722,19 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_hold_kernel(const u
         tile_masks_multi<NT>(src + (long)iy0 * pitch, c0, real, pitch, fstride, t, th, msk);
         zero_steps<NT>(msk, real, cn);
         __syncthreads();
+        if constexpr (OUT == CELLS_MASKS) {
+            // frame_cells_multi_kernel's store loop on the EDGE words of the chunk's real steps, before the walk replaces them by held words:
+            // wave q reads all eight rows of threshold q, which eight walking waves are about to overwrite, hence the barrier behind it
+            static_assert(FC_ROWS == 8, "a lane's word of a store pass is lane % 8 of frame lane / 8");
+            if (mine) {
+                const long slot_words = NT * cells * FC_ROWS;
+                unsigned long long* out =
+                    first_of(x...) + (second_of(x...) + c0 + (lane >> 3)) * slot_words + (wave * cells + cell) * FC_ROWS + (lane & 7);
+#pragma unroll 1
+                for (int i = lane; i < real * FC_ROWS; i += 64, out += (FC_CHUNK / FC_ROWS) * slot_words) *out = mq[i];
+            }
+            __syncthreads();
+        }
         if (walks) {
             // lane = step of the chunk for the words going in and out, lane = column for the walk: the walk itself stays out of LDS
             int lo[NT], hi[NT], run[NT], cover[NT];
@@ -1009,6 +1091,20 @@ size_t vse_frame_cells_hold_bytes(int ih, int iw, int nt) {
     return cells_hold_pixel_bytes(ih, iw, nt) + ((nt * cells * sizeof(int32_t) + 7) & ~(size_t)7);
 }
 
+// frame_cells_hold_kernel<nt, OUT, X...> with the kind's arguments x (X given explicitly, as for cells_multi_launch)
+template <int OUT, class... X>
+static int cells_hold_launch(const CellsLaunch& l, int n, int steps, int64_t pitch, int64_t frame_stride, int x0, int nt, int hold, int skip,
+                             const CellRule& rule, void* d_state, int fresh, int flush, int32_t* d_totals, int32_t* d_cell_counts,
+                             int count_rows, X... x) {
+    unsigned short* pix = reinterpret_cast<unsigned short*>(d_state);
+    int* open_runs = reinterpret_cast<int*>(reinterpret_cast<char*>(d_state) + cells_hold_pixel_bytes(l.ih, l.iw, nt));
+    return launch_for_nt(nt, [&](auto nt_c) {
+        hipLaunchKernelGGL((frame_cells_hold_kernel<decltype(nt_c)::value, OUT, X...>), l.grid, l.block, 0, l.st, l.src, n, steps, (long)pitch,
+                           (long)frame_stride, x0, l.ih, l.iw, l.th, rule, hold, skip, pix, open_runs, fresh, flush,
+                           reinterpret_cast<int*>(d_totals), reinterpret_cast<int*>(d_cell_counts), count_rows, x...);
+    });
+}
+
 // Called by vse_frame_cells_hold (vse_runtime.hip) after it has checked the arguments (1 <= nt <= vse_frame_cells_multi_max(), 1 <= hold <=
 // 32); steps = n (+ hold - 1 with a flush) >= 0, skip = the steps whose frame lies before frame 1, count_rows = the rows of d_cell_counts
 // per threshold.
@@ -1016,13 +1112,37 @@ int vse_frame_cells_hold_launch(const void* d_bgr, int n, int steps, int64_t pit
                                 const int* thresholds, int nt, int hold, int skip, const CellRule& rule, void* d_state, int fresh, int flush,
                                 int32_t* d_totals, int32_t* d_cell_counts, int count_rows, void* stream) {
     const CellsLaunch l(d_bgr, pitch, y0, y1, x0, x1, thresholds, nt, stream);
-    unsigned short* pix = reinterpret_cast<unsigned short*>(d_state);
-    int* open_runs = reinterpret_cast<int*>(reinterpret_cast<char*>(d_state) + cells_hold_pixel_bytes(l.ih, l.iw, nt));
-    return launch_for_nt(nt, [&](auto nt_c) {
-        hipLaunchKernelGGL(frame_cells_hold_kernel<decltype(nt_c)::value>, l.grid, l.block, 0, l.st, l.src, n, steps, (long)pitch,
-                           (long)frame_stride, x0, l.ih, l.iw, l.th, rule, hold, skip, pix, open_runs, fresh, flush,
-                           reinterpret_cast<int*>(d_totals), reinterpret_cast<int*>(d_cell_counts), count_rows);
-    });
+    return cells_hold_launch<CELLS_ONLY>(l, n, steps, pitch, frame_stride, x0, nt, hold, skip, rule, d_state, fresh, flush, d_totals,
+                                         d_cell_counts, count_rows);
+}
+
+// Called by vse_frame_cells_hold_masks (vse_runtime.hip) after it has checked the arguments as vse_frame_cells_hold does and 0 <= slot0,
+// slot0 + n <= cap of d_masks: the n frames are the steps 0 .. n - 1 and take the slots slot0 .. slot0 + n - 1, the flush steps none.
+int vse_frame_cells_hold_masks_launch(const void* d_bgr, int n, int steps, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                                      const int* thresholds, int nt, int hold, int skip, const CellRule& rule, void* d_state, int fresh,
+                                      int flush, int32_t* d_totals, int32_t* d_cell_counts, int count_rows, void* d_masks, int slot0,
+                                      void* stream) {
+    const CellsLaunch l(d_bgr, pitch, y0, y1, x0, x1, thresholds, nt, stream);
+    return cells_hold_launch<CELLS_MASKS, unsigned long long* __restrict__, long>(
+        l, n, steps, pitch, frame_stride, x0, nt, hold, skip, rule, d_state, fresh, flush, d_totals, d_cell_counts, count_rows,
+        reinterpret_cast<unsigned long long*>(d_masks), (long)slot0);
+}
+
+// Called by vse_frame_masks_replay_hold (vse_runtime.hip) after it has checked the region, 0 <= q < nt <= vse_frame_cells_multi_max(), the
+// slots 0 <= f0 <= f1 <= cap, the rectangle, at least 3 x 3 and inside the region, and 1 <= hold <= 32; n = f1 - f0, steps = n (+ hold - 1
+// with a flush) > 0 and skip as for vse_frame_hold_launch.  d_counts is cleared on the stream ahead of the kernel, which adds into it.
+int vse_frame_masks_replay_hold_launch(const void* d_masks, int area_h, int area_w, int nt, int q, int f0, int n, int steps, int ry0, int ry1,
+                                       int rx0, int rx1, int hold, int skip, void* d_state, int fresh, int32_t* d_counts, void* stream) {
+    const int gy = (area_h - 2 + FC_ROWS - 1) / FC_ROWS, gx = (area_w - 2 + 63) / 64;
+    const long cells = (long)gy * gx, slot_words = (long)nt * cells * FC_ROWS;
+    ReplayRect r;
+    r.ry0 = ry0, r.rx0 = rx0, r.ih = ry1 - ry0 - 2, r.iw = rx1 - rx0 - 2, r.wpr = (r.iw + 63) / 64;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (steps > skip && hipMemsetAsync(d_counts, 0, (size_t)(steps - skip) * 3 * sizeof(int32_t), st) != hipSuccess) return VSE_E_HIP;
+    const unsigned long long* slice = reinterpret_cast<const unsigned long long*>(d_masks) + (long)f0 * slot_words + (long)q * cells * FC_ROWS;
+    hipLaunchKernelGGL(frame_masks_replay_hold_kernel, dim3(r.wpr, (r.ih + FC_ROWS - 1) / FC_ROWS), dim3(FC_WAVES * 64), 0, st, slice, slot_words,
+                       gx, r, n, steps, hold, skip, reinterpret_cast<unsigned short*>(d_state), fresh, reinterpret_cast<int*>(d_counts));
+    return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
 }
 
 // ---- vse_frame_hold_bounded -----------------------------------------------------------------------------------------------------

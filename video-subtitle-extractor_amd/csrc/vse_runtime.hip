@@ -83,6 +83,13 @@ size_t vse_frame_cells_hold_bytes(int ih, int iw, int nt);                      
 int vse_frame_cells_hold_launch(const void* d_bgr, int n, int steps, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
                                 const int* thresholds, int nt, int hold, int skip, const CellRule& rule, void* d_state, int fresh, int flush,
                                 int32_t* d_totals, int32_t* d_cell_counts, int count_rows, void* stream);               // frame_change.hip
+int vse_frame_cells_hold_masks_launch(const void* d_bgr, int n, int steps, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                                      const int* thresholds, int nt, int hold, int skip, const CellRule& rule, void* d_state, int fresh,
+                                      int flush, int32_t* d_totals, int32_t* d_cell_counts, int count_rows, void* d_masks, int slot0,
+                                      void* stream);                                                                    // frame_change.hip
+int vse_frame_masks_replay_hold_launch(const void* d_masks, int area_h, int area_w, int nt, int q, int f0, int n, int steps, int ry0, int ry1,
+                                       int rx0, int rx1, int hold, int skip, void* d_state, int fresh, int32_t* d_counts,
+                                       void* stream);                                                                   // frame_change.hip
 size_t vse_frame_cells_hold_bounded_bytes(int ih, int iw, int nt, int max_hold);                                        // frame_change.hip
 int vse_frame_cells_hold_bounded_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
                                         const int* thresholds, int nt, int hold, int max_hold, const CellRule& rule, void* d_state,
@@ -528,6 +535,13 @@ static bool check_hold_bounded(const char* who, int hold, int max_hold) {
     return false;
 }
 
+// the steps of a held-edge call and those of them that belong to no frame: the mask of a frame is known hold - 1 frames later, so a flush
+// feeds that many frames without an edge, and the first hold - 1 steps of a clip come before frame 1
+static int64_t hold_steps(int n, int hold, int64_t fed, int flush, int* skip) {
+    *skip = fed >= hold - 1 ? 0 : (int)(hold - 1 - fed);
+    return (int64_t)n + (flush ? hold - 1 : 0);
+}
+
 // the end of an entry point: rc of its launcher, with the error text set where the launch failed
 static int launched(const char* who, int rc) {
     if (rc != VSE_OK) set_err("%s: launch failed: %s", who, hipGetErrorString(hipGetLastError()));
@@ -694,10 +708,8 @@ int vse_frame_hold(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, i
         !check_area("vse_frame_hold", "area", y0, y1, x0, x1, src_h, src_w))
         return VSE_E_INVAL;
     if (!check_hold("vse_frame_hold", hold)) return VSE_E_INVAL;
-    // the mask of a frame is known hold - 1 frames later: a flush feeds that many frames without an edge, and the first
-    // hold - 1 steps of a clip belong to no frame
-    const int64_t steps = (int64_t)n + (flush ? hold - 1 : 0);
-    const int skip = fed >= hold - 1 ? 0 : (int)(hold - 1 - fed);
+    int skip;
+    const int64_t steps = hold_steps(n, hold, fed, flush, &skip);
     if (steps == 0) return VSE_OK;
     if (steps > INT32_MAX || (steps > skip && !d_counts)) {
         set_err("vse_frame_hold: %lld steps need d_counts and must fit an int", (long long)steps);
@@ -747,10 +759,8 @@ int vse_frame_cells_hold(vse_ctx* c, const void* d_bgr, int n, int src_h, int sr
         return VSE_E_INVAL;
     if (!check_thresholds("vse_frame_cells_hold", thresholds, nt)) return VSE_E_INVAL;
     if (!check_hold("vse_frame_cells_hold", hold)) return VSE_E_INVAL;
-    // as vse_frame_hold: the held mask of a frame is known hold - 1 frames later, a flush feeds that many frames without an edge, and
-    // the first hold - 1 steps of a clip belong to no frame
-    const int64_t steps = (int64_t)n + (flush ? hold - 1 : 0);
-    const int skip = fed >= hold - 1 ? 0 : (int)(hold - 1 - fed);
+    int skip;
+    const int64_t steps = hold_steps(n, hold, fed, flush, &skip);
     if ((int64_t)n + hold - 1 > INT32_MAX) {
         set_err("vse_frame_cells_hold: %lld steps do not fit an int", (long long)n + hold - 1);
         return VSE_E_INVAL;
@@ -759,6 +769,65 @@ int vse_frame_cells_hold(vse_ctx* c, const void* d_bgr, int n, int src_h, int sr
     return launched("vse_frame_cells_hold", vse_frame_cells_hold_launch(d_bgr, n, (int)steps, pitch, frame_stride, y0, y1, x0, x1, thresholds, nt,
                     hold, skip, {min_edges, ratio_num, ratio_den, min_frames, max_frames}, d_state, fed == 0, flush != 0, d_totals, d_cell_counts,
                     n + hold - 1, stream));
+}
+
+// ---- the held locator's edge masks kept, and the held selector's rows out of them (frame_change.hip) ----------------------------------
+int vse_frame_cells_hold_masks(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0,
+                               int y1, int x0, int x1, const int* thresholds, int nt, int hold, int min_edges, int ratio_num, int ratio_den,
+                               int min_frames, int max_frames, void* d_state, int64_t fed, int flush, int32_t* d_totals,
+                               int32_t* d_cell_counts, void* d_masks, int cap, int slot0, void* stream) {
+    if (!check_frames("vse_frame_cells_hold_masks", c && d_totals && fed >= 0 && (d_masks || n <= 0) && !(reinterpret_cast<uintptr_t>(d_masks) & 7),
+                      d_bgr, n, 0, src_h, src_w, pitch, frame_stride, d_state) ||
+        !check_area("vse_frame_cells_hold_masks", "region", y0, y1, x0, x1, src_h, src_w) ||
+        !check_rule("vse_frame_cells_hold_masks", ratio_num, ratio_den, min_frames, max_frames))
+        return VSE_E_INVAL;
+    if (!check_thresholds("vse_frame_cells_hold_masks", thresholds, nt)) return VSE_E_INVAL;
+    if (!check_hold("vse_frame_cells_hold_masks", hold)) return VSE_E_INVAL;
+    int skip;
+    const int64_t steps = hold_steps(n, hold, fed, flush, &skip);
+    if ((int64_t)n + hold - 1 > INT32_MAX) {
+        set_err("vse_frame_cells_hold_masks: %lld steps do not fit an int", (long long)n + hold - 1);
+        return VSE_E_INVAL;
+    }
+    if (cap < 1 || slot0 < 0 || (int64_t)slot0 + n > cap) {
+        set_err("vse_frame_cells_hold_masks: %d frames from slot %d on do not fit a mask buffer of %d slots (no wrap)", n, slot0, cap);
+        return VSE_E_INVAL;
+    }
+    if (n == 0 && !flush) return VSE_OK;
+    return launched("vse_frame_cells_hold_masks", vse_frame_cells_hold_masks_launch(d_bgr, n, (int)steps, pitch, frame_stride, y0, y1, x0, x1,
+                    thresholds, nt, hold, skip, {min_edges, ratio_num, ratio_den, min_frames, max_frames}, d_state, fed == 0, flush != 0,
+                    d_totals, d_cell_counts, n + hold - 1, d_masks, slot0, stream));
+}
+
+int vse_frame_masks_replay_hold(vse_ctx* c, const void* d_masks, int area_h, int area_w, int nt, int cap, int q, int f0, int f1, int ry0,
+                                int ry1, int rx0, int rx1, int hold, void* d_hold_state, int64_t fed, int flush, int32_t* d_counts,
+                                void* stream) {
+    if (!c || !d_masks || !d_hold_state || area_h < 3 || area_w < 3 || nt < 1 || nt > vse_frame_cells_multi_max() || q < 0 || q >= nt ||
+        fed < 0 || ((reinterpret_cast<uintptr_t>(d_masks) | reinterpret_cast<uintptr_t>(d_hold_state)) & 7) ||
+        (reinterpret_cast<uintptr_t>(d_counts) & 3)) {
+        set_err("vse_frame_masks_replay_hold: bad arguments (region %d x %d of at least 3 x 3, threshold %d of %d (1..%d), fed %lld, masks and "
+                "state 8-byte aligned, no NULL pointer)", area_h, area_w, q, nt, vse_frame_cells_multi_max(), (long long)fed);
+        return VSE_E_INVAL;
+    }
+    if (f0 < 0 || f1 < f0 || f1 > cap || (f1 == f0 && !flush)) {
+        set_err("vse_frame_masks_replay_hold: slots [%d, %d) of a buffer of %d (0 <= f0 < f1 <= cap; f1 == f0 only with flush)", f0, f1, cap);
+        return VSE_E_INVAL;
+    }
+    if (ry0 < 0 || rx0 < 0 || ry1 > area_h || rx1 > area_w || ry1 - ry0 < 3 || rx1 - rx0 < 3) {
+        set_err("vse_frame_masks_replay_hold: rectangle [%d, %d) x [%d, %d) is degenerate or outside the %d x %d region", ry0, ry1, rx0, rx1,
+                area_h, area_w);
+        return VSE_E_INVAL;
+    }
+    if (!check_hold("vse_frame_masks_replay_hold", hold)) return VSE_E_INVAL;
+    int skip;
+    const int64_t steps = hold_steps(f1 - f0, hold, fed, flush, &skip);
+    if (steps > INT32_MAX || (steps > skip && !d_counts)) {
+        set_err("vse_frame_masks_replay_hold: %lld steps need d_counts and must fit an int", (long long)steps);
+        return VSE_E_INVAL;
+    }
+    if (steps == 0) return VSE_OK;
+    return launched("vse_frame_masks_replay_hold", vse_frame_masks_replay_hold_launch(d_masks, area_h, area_w, nt, q, f0, f1 - f0, (int)steps,
+                    ry0, ry1, rx0, rx1, hold, skip, d_hold_state, fed == 0, d_counts, stream));
 }
 
 // ---- locator and calibration on bounded runs (frame_change.hip) -----------------------------------------------------------------

@@ -354,6 +354,21 @@ class SubtitleExtractor:
     "change", automaton="hold" / max_hold_* / search_area / probe in area_params, area_params' streaming, interval_frame="sharpest",
     composite_params' streaming, shard, mode="accurate", a sub_area that is not "auto"; the other keys without the key mean nothing and are
     refused too.
+    area_params={"streaming_locate_hold": True} with sub_area="auto", frame_selector="hold" and mode "fast" or "auto": the same for the hold
+    selector, the only one that works when a textured background moves behind the subtitle, where the change automaton finds neither an
+    area nor a threshold (frame_select.LocatingHoldSelector: the held locator's kernel keeps the EDGE words it builds anyway,
+    vse_frame_cells_hold_masks, and once the area is decided vse_frame_masks_replay_hold walks the located rectangle's pixels through
+    them with the selector's hold, integer for integer vse_frame_hold's rows and state).  A sibling key, because "streaming_locate" keeps
+    refusing frame_selector="hold" and automaton="hold" by name; the two together are refused.  The key implies automaton="hold" for the
+    locator (giving it is accepted), whose hold follows the selector's hold_seconds / hold_frames unless area_params sets its own.
+    `locate_seconds` and `mask_gib` are the other key's, with its meaning, bounds and error texts; `cells_hold_masks_fn` and
+    `replay_hold_fn` are the selector's callables (default the GPU's); `located_area`, `edge_thresh`, `edge_scores` and `frames_located`
+    are filled as there, and the results are those of the run without the key whose area_params say automaton="hold" and probe=(1, that
+    many frames).  In one pass sub_area="auto" and edge_thresh="auto" are accepted with it; the window's frames are kept on the host until
+    the decision, after which the hold selector's rows trail its frames by hold - 1 as always.  The held locator's limits carry over, and
+    nothing is measured on real footage.  Refused with the key, by name: streaming_locate together with it, frame_selector other than
+    "hold", an automaton other than "hold", max_hold_* in area_params or change_params, search_area, probe, area_params' streaming,
+    interval_frame="sharpest", composite_params' streaming, shard, mode="accurate", a sub_area that is not "auto".
     one_pass (None: exactly when the source has no `read`, e.g. ingest.Y4mStream over a pipe; True forces it on a seekable source and
     halves its decode work; False on a sequential source is a ValueError): the clip is read once, in decode order.  frame_selector="fps":
     frame `no` is a task iff (no - 1) % max(1, int(fps // extract_frequency)) == 0 (fps_tasks' rule without the frame count); tasks go
@@ -367,8 +382,8 @@ class SubtitleExtractor:
     SRT times, are untouched; `clamped_intervals` counts them and one warning is logged per run.  Where no interval was clamped, the
     intervals, the frames recognised, raw_lines and the SRT equal those of the multi-pass run() on the same frames with the same
     arguments (recognition does not depend on how frames are grouped into batches: tests/test_gpu_ragged.py).  Refused in one pass,
-    because they need a second look at frames already gone: sub_area="auto" (unless area_params says "streaming_locate"), mode="accurate" with an area, interval_image other than
-    "middle" (unless composite_params says "streaming": min / max / mean and the quantile), interval_text="fused", shard, change_params' edge_thresh="auto" (unless area_params says "streaming").
+    because they need a second look at frames already gone: sub_area="auto" (unless area_params says "streaming_locate" or "streaming_locate_hold"), mode="accurate" with an area, interval_image other than
+    "middle" (unless composite_params says "streaming": min / max / mean and the quantile), interval_text="fused", shard, change_params' edge_thresh="auto" (unless area_params says "streaming" or one of the two locate keys).
     interval_frame="sharpest" (change / hold selector with interval_image="middle" and interval_text="single" only; default "middle", all
     of the above): the one frame an interval is recognised on is chosen instead of being the middle one, which in compressed video is as
     likely as any other to be a coarse B-frame, a half-faded frame or a flash.  In the selector's own pass over the staged area rows the
@@ -459,14 +474,29 @@ class SubtitleExtractor:
         self._calibrate_fns = (area_params.pop("cells_counts_fn", None), area_params.pop("export_fn", None)) if self.calibrating else None
         # area_params={"streaming_locate": True}: sub_area="auto" is found in the selector's own pass (frame_select.LocatingChangeSelector).
         # Its keys, `streaming_locate`, `locate_seconds`, `mask_gib`, `cells_masks_fn` and `replay_fn`, are taken out here as well.
+        # area_params={"streaming_locate_hold": True}: the same for frame_selector="hold" on held edges (frame_select.LocatingHoldSelector),
+        # a sibling key with callables of its own, `cells_hold_masks_fn` and `replay_hold_fn`; `locate_seconds` and `mask_gib` go with either.
+        # `locating` is set by both keys, `locating_hold` says which.
+        self.locating_hold = bool(area_params.pop("streaming_locate_hold", False)) if area_params else False
         self.locating = bool(area_params.pop("streaming_locate", False)) if area_params else False
+        if self.locating and self.locating_hold:
+            raise ValueError("area_params={'streaming_locate_hold': True} finds the area for frame_selector='hold' and area_params="
+                             "{'streaming_locate': True} for frame_selector='change'; it does not combine with streaming_locate, give one of them")
+        self.locating = self.locating or self.locating_hold
+        self._locate_key = "streaming_locate_hold" if self.locating_hold else "streaming_locate"
+        change_fns, hold_fns = {"cells_masks_fn", "replay_fn"}, {"cells_hold_masks_fn", "replay_hold_fn"}
         if not self.locating:
-            own = sorted(set(area_params or {}) & {"locate_seconds", "mask_gib", "cells_masks_fn", "replay_fn"})
+            own = sorted(set(area_params or {}) & ({"locate_seconds", "mask_gib"} | change_fns))
             if own:
                 raise ValueError(f"area_params: {own} belong to area_params={{'streaming_locate': True}} and mean nothing without it")
+        other, fns = ("streaming_locate", change_fns) if self.locating_hold else ("streaming_locate_hold", hold_fns)
+        own = sorted(set(area_params or {}) & fns)
+        if own:                                   # the callables of the key that is not set
+            raise ValueError(f"area_params: {own} belong to area_params={{'{other}': True}} and mean nothing without it")
         self.locate_seconds = area_params.pop("locate_seconds", None) if self.locating else None
         self.mask_gib = area_params.pop("mask_gib", 8) if self.locating else None
-        self._locate_fns = (area_params.pop("cells_masks_fn", None), area_params.pop("replay_fn", None)) if self.locating else None
+        names = ("cells_hold_masks_fn", "replay_hold_fn") if self.locating_hold else ("cells_masks_fn", "replay_fn")
+        self._locate_fns = tuple(area_params.pop(k, None) for k in names) if self.locating else None
         self.auto_area, self.area_params, self.located_area = isinstance(sub_area, str) and sub_area == "auto", area_params, None
         self.sub_area, self.mode, self.language = None if self.auto_area else sub_area, mode, language
         self.extract_frequency, self.default_subtitle_area = extract_frequency, default_subtitle_area
@@ -499,7 +529,28 @@ class SubtitleExtractor:
         if not self.one_pass and not hasattr(source, "read"):
             raise ValueError("one_pass=False needs a source with read(frame_no): this one is sequential and its frames cannot be looked at a second time")
         self.frames_located = 0           # area_params' streaming_locate: the frames the located area rests on
-        if self.locating:
+        if self.locating_hold:
+            option = "area_params={'streaming_locate_hold': True}"
+            held = sorted(set(self.area_params) & {"max_hold_seconds", "max_hold_frames"})
+            held_sel = sorted(set(change_params or {}) & {"max_hold_seconds", "max_hold_frames"})
+            refused = [(f"frame_selector={frame_selector!r}", frame_selector != "hold"),
+                       (f"automaton={self.area_params.get('automaton')!r}", self.area_params.get("automaton", "hold") != "hold"),
+                       (f"{held[0] if held else 'max_hold_seconds'} in area_params", bool(held)),
+                       (f"{held_sel[0] if held_sel else 'max_hold_seconds'} in change_params", bool(held_sel)),
+                       ("search_area in area_params", "search_area" in self.area_params),
+                       ("probe in area_params (locate_seconds says how many frames decide)", "probe" in self.area_params),
+                       ("area_params={'streaming': True}", self.calibrating),
+                       (f"interval_frame={interval_frame!r}", interval_frame != "middle"),
+                       ("composite_params={'streaming': True}", self.streaming), (f"shard={shard!r}", shard is not None),
+                       (f"mode={mode!r}", mode not in ("fast", "auto")),
+                       (f"sub_area={sub_area!r} (the key finds the area of sub_area='auto' and means nothing with another)", not self.auto_area)]
+            for what, hit in refused:
+                if hit:
+                    raise ValueError(f"{option} finds the area of sub_area='auto' for frame_selector='hold' while that selector runs, with "
+                                     f"the held automaton on whole frames and unbounded runs; it does not combine with {what}, which needs "
+                                     "the area from the first frame, bounds the runs or has a pass of its own")
+            self.area_params["automaton"] = "hold"            # (implied by the key)
+        elif self.locating:
             option = "area_params={'streaming_locate': True}"
             held = sorted(set(self.area_params) & {"max_hold_seconds", "max_hold_frames"})
             refused = [(f"frame_selector={frame_selector!r}", frame_selector != "change"),
@@ -517,6 +568,7 @@ class SubtitleExtractor:
                     raise ValueError(f"{option} finds the area of sub_area='auto' for frame_selector='change' while that selector runs, with "
                                      f"the change automaton on whole frames; it does not combine with {what}, which needs the area from the "
                                      "first frame or has a pass of its own")
+        if self.locating:
             if self.locate_seconds is not None and not self.locate_seconds > 0:
                 raise ValueError(f"{option}: locate_seconds must be positive, not {self.locate_seconds!r}")
             if not self.mask_gib > 0:
@@ -636,13 +688,13 @@ class SubtitleExtractor:
             nt = len(self.area_params.get("thresholds", area_locator.AUTO_THRESHOLDS)) if self.auto_thresh else 1
             need, bound = window * nt * gy * gx * 64, int(self.mask_gib * (1 << 30))
             if need > bound:
-                raise ValueError(f"area_params={{'streaming_locate': True}}: the masks of a window of {window} frames of {h} x {w} pixels at "
+                raise ValueError(f"area_params={{'{self._locate_key}': True}}: the masks of a window of {window} frames of {h} x {w} pixels at "
                                  f"{nt} threshold{'s' if nt > 1 else ''} take {need} bytes on the device, more than mask_gib={self.mask_gib} "
                                  f"({bound} bytes): give a shorter locate_seconds or a larger mask_gib / --mask-gib")
         if self.one_pass:
             need = window * _frame_nbytes(first)
             if need > self.retain_bytes:
-                raise ValueError(f"area_params={{'streaming_locate': True}}: one pass keeps every frame of the window until the area is decided, "
+                raise ValueError(f"area_params={{'{self._locate_key}': True}}: one pass keeps every frame of the window until the area is decided, "
                                  f"and {window} frames of {_frame_nbytes(first)} bytes are {need} bytes, more than retain_bytes={self.retain_bytes}: "
                                  "give a shorter locate_seconds or a larger retain_bytes / --retain-gib")
         return window
@@ -660,6 +712,13 @@ class SubtitleExtractor:
                                                 "(fps sampler, scene-text filtering)", sel.frames_scanned)
 
     def _locating_selector(self, window):
+        if self.locating_hold:
+            params = {k: v for k, v in self.area_params.items() if k not in ("cells_fn", "batch")}
+            if "hold_seconds" not in params and "hold_frames" not in params:
+                # _locator's rule: the locator holds as long as the selector does, unless area_params says otherwise
+                params.update({k: v for k, v in (self.change_params or {}).items() if k in ("hold_seconds", "hold_frames")})
+            return frame_select.LocatingHoldSelector(self.change_counter, *self._locate_fns, window=window, batch=self.batch,
+                                                     locator_params=params, **(self.change_params or {}))
         return frame_select.LocatingChangeSelector(self.change_counter, *self._locate_fns, window=window, batch=self.batch,
                                                    locator_params={k: v for k, v in self.area_params.items() if k not in ("cells_fn", "batch")},
                                                    **(self.change_params or {}))
@@ -1087,7 +1146,7 @@ def default_locate_seconds(source, raw, auto_thresh, retain_bytes, mask_gib, lim
 
 
 def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, focus_fn=None, stream_fn=None, ring_fn=None,
-         cells_counts_fn=None, export_fn=None, cells_masks_fn=None, replay_fn=None):
+         cells_counts_fn=None, export_fn=None, cells_masks_fn=None, replay_fn=None, cells_hold_masks_fn=None, replay_hold_fn=None):
     """ocr: the recogniser (None: shim.OcrRecogniser on the GPU, frames staged through staging.default_uploader, YUV 4:2:0 converted
     on the device); counter: the change / hold selector's count_fn (None: the GPU's); cells_fn: the locator's (None: the GPU's);
     composite_fn: what makes the picture of `--interval-image`, the compositor's accumulate_fn for min / max / mean and the quantile's
@@ -1095,7 +1154,9 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
     stream_fn: what makes the min / max / mean pictures of `--streaming-composite`, StreamingCompositor's stream_fn (None: the GPU's);
     ring_fn: what makes its quantile pictures, StreamingQuantile's ring_fn (None: the GPU's); cells_counts_fn, export_fn: what counts
     and hands over for `--streaming-calibration`, CalibratingChangeSelector's cells_fn and export_fn (None: the GPU's); cells_masks_fn,
-    replay_fn: what keeps and replays the masks for `--streaming-locate`, LocatingChangeSelector's cells_fn and replay_fn (None: the GPU's)."""
+    replay_fn: what keeps and replays the masks for `--streaming-locate`, LocatingChangeSelector's cells_fn and replay_fn (None: the GPU's);
+    cells_hold_masks_fn, replay_hold_fn: the same for `--streaming-locate-hold`, LocatingHoldSelector's cells_fn and replay_fn (None: the
+    GPU's)."""
     p = argparse.ArgumentParser(prog="python -m vse_amd.extractor", description="Extract a video's hard subtitles to SRT on the GPU.  "
                                 "`-` reads YUV4MPEG2 from standard input in one pass, e.g. "
                                 "`ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m vse_amd.extractor - -o film.srt`.")
@@ -1144,11 +1205,14 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
                    "the whole clip; `-`: 300, a policy, not a measurement: nobody has tried it on real films]")
     p.add_argument("--streaming-locate", action="store_true", help="--area auto --selector change: find the area in the selector's own pass "
                    "instead of a pass of its own, which also works in one pass (a pipe); --edge-thresh auto is chosen in that pass too")
-    p.add_argument("--locate-seconds", type=float, default=None, metavar="S", help="--streaming-locate: the area is found on the first S "
+    p.add_argument("--streaming-locate-hold", action="store_true", help="--area auto --selector hold: the same on held edges, for a "
+                   "textured background that moves behind the subtitles (the locator counts with the hold automaton); takes --locate-seconds "
+                   "and --mask-gib as --streaming-locate does")
+    p.add_argument("--locate-seconds", type=float, default=None, metavar="S", help="--streaming-locate / --streaming-locate-hold: the area is found on the first S "
                    "seconds; until then one pass keeps every frame and the device one bit per pixel and threshold [a file: the whole "
                    "clip; `-`: the largest whole number of seconds up to 300 whose frames fit --retain-gib and --mask-gib, about 57 for "
                    "1080p 4:2:0 at 24 fps, a policy, not a measurement: nobody has tried whether a minute of a real film finds its band]")
-    p.add_argument("--mask-gib", type=float, default=None, metavar="G", help="--streaming-locate: bound on the masks kept on the device "
+    p.add_argument("--mask-gib", type=float, default=None, metavar="G", help="--streaming-locate / --streaming-locate-hold: bound on the masks kept on the device "
                    "until the area is found, GiB [8, a policy, not a measurement]")
     p.add_argument("--max-hold-seconds", type=float, default=None, metavar="S", help="--selector hold: count only edges that hold still for "
                    "at most S seconds, so a static busy background, a logo or a watermark drops out; a subtitle shown for longer drops out "
@@ -1210,7 +1274,10 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
                            **({} if export_fn is None else {"export_fn": export_fn})}
         elif args.calibrate_seconds is not None:
             raise ValueError("--calibrate-seconds sets the window of --streaming-calibration and means nothing without it")
-        if not args.streaming_locate and (args.locate_seconds is not None or args.mask_gib is not None):
+        if args.streaming_locate and args.streaming_locate_hold:
+            raise ValueError("--streaming-locate finds the area for `--selector change` and --streaming-locate-hold for `--selector hold`: "
+                             "give one of them")
+        if not args.streaming_locate and not args.streaming_locate_hold and (args.locate_seconds is not None or args.mask_gib is not None):
             raise ValueError("--locate-seconds and --mask-gib set the window and the device bound of --streaming-locate and mean nothing "
                              "without it")
         ring = args.streaming_composite and args.interval_image == "quantile"
@@ -1253,16 +1320,18 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
             shim.config.language, shim.config.mode = args.language, args.mode
             ocr, uploader = shim.OcrRecogniser(), staging.default_uploader()
         location = {}
-        if args.streaming_locate:
+        if args.streaming_locate or args.streaming_locate_hold:
+            flag, key = ("--streaming-locate-hold", "streaming_locate_hold") if args.streaming_locate_hold else ("--streaming-locate", "streaming_locate")
+            fns = ({"cells_hold_masks_fn": cells_hold_masks_fn, "replay_hold_fn": replay_hold_fn} if args.streaming_locate_hold else
+                   {"cells_masks_fn": cells_masks_fn, "replay_fn": replay_fn})
             locate_seconds, mask_gib = args.locate_seconds, 8.0 if args.mask_gib is None else args.mask_gib
             if locate_seconds is None and args.video == "-" and area == "auto" and mask_gib > 0:
                 locate_seconds = default_locate_seconds(source, uploader is not None and hasattr(source, "raw_frames"), edge_thresh == "auto",
                                                         int(args.retain_gib * (1 << 30)), mask_gib)
-                logging.getLogger(__name__).info("--streaming-locate: the area is found on the first %d seconds (what fits --retain-gib "
-                                                 "%g and --mask-gib %g, at most 300)", int(locate_seconds), args.retain_gib, mask_gib)
-            location = {"streaming_locate": True, "mask_gib": mask_gib, **({} if locate_seconds is None else {"locate_seconds": locate_seconds}),
-                        **({} if cells_masks_fn is None else {"cells_masks_fn": cells_masks_fn}),
-                        **({} if replay_fn is None else {"replay_fn": replay_fn})}
+                logging.getLogger(__name__).info("%s: the area is found on the first %d seconds (what fits --retain-gib "
+                                                 "%g and --mask-gib %g, at most 300)", flag, int(locate_seconds), args.retain_gib, mask_gib)
+            location = {key: True, "mask_gib": mask_gib, **({} if locate_seconds is None else {"locate_seconds": locate_seconds}),
+                        **{k: v for k, v in fns.items() if v is not None}}
         ex = SubtitleExtractor(source, ocr, sub_area=area, mode=args.mode, language=args.language, extract_frequency=args.frequency,
                                batch=args.batch, uploader=uploader, frame_selector=args.selector, change_counter=counter,
                                retain_bytes=int(args.retain_gib * (1 << 30)), interval_image=args.interval_image,

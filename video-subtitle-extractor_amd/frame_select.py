@@ -825,6 +825,197 @@ class HoldFrameSelector(_IntervalSelector):
         return self.count_fn(data[:0], area, self.edge_thresh, *self._args(), fed, True)
 
 
+# ---- the hold selector that finds its own area while the frames go by ---------------------------------------------------------------
+class EngineCellsHoldMasks(DeviceState):
+    """cells_fn of LocatingHoldSelector on the GPU (Context.frame_cells_hold_masks), the counterpart of EngineCellsMasks: keeps the device
+    state and the mask buffer of the last region, threshold count, hold and `cap`, and `fed`, the frames fed since the last reset, which
+    is the slot the next frame takes; (frames | None, area, engine.CellParams, reset, flush, thresholds, cap, hold) -> totals
+    [nt,gy,gx,4], frames None with flush draining and closing the open runs.  `replay(area, q, rect, counter, hold, flush)` walks the
+    slots 0 .. fed - 1 at threshold index q on `rect` (y0, y1, x0, x1 in the region's pixels) with the SELECTOR's hold at once
+    (Context.frame_masks_replay_hold) -> frame_hold's rows of those frames, and sets up an EngineHoldCounter, its state, key and `fed`, so
+    that its next call continues the clip on that rectangle."""
+
+    def __init__(self, ctx):
+        super().__init__(ctx)
+        self.fed, self._masks = 0, None
+
+    def __call__(self, frames, area, params, reset, flush, thresholds, cap, hold):
+        t = self.ctx.torch
+        y0, y1, x0, x1 = area
+        frames = t.empty((0, y1, x1, 3), dtype=t.uint8, device=self.ctx.tdev) if frames is None else self._device(frames)
+        if self._fresh((y1 - y0, x1 - x0, len(thresholds), int(hold), int(cap)),
+                       lambda h, w, nt, hold, _cap: self.ctx.frame_cells_hold_state(h, w, nt, hold)):
+            self._masks, reset = self.ctx.frame_masks_buffer(y1 - y0, x1 - x0, len(thresholds), cap), True
+        if reset:
+            self.fed = 0
+        totals = self.ctx.frame_cells_hold_masks(frames, area, thresholds, hold, params, self._state, self._masks, self.fed, self.fed, flush)
+        self.fed += len(frames)
+        return totals
+
+    def replay(self, area, q, rect, counter, hold, flush):
+        y0, y1, x0, x1 = area
+        if self._key is None or self._key[:2] != (y1 - y0, x1 - x0) or not self.fed:
+            raise ValueError(f"EngineCellsHoldMasks: no masks of a {y1 - y0} x {x1 - x0} region to replay")
+        ry0, ry1, rx0, rx1 = rect
+        counter._fresh((ry1 - ry0, rx1 - rx0, hold), self.ctx.frame_hold_state)
+        counter.fed = self.fed
+        return self.ctx.frame_masks_replay_hold(self._masks, q, 0, self.fed, rect, hold, counter._state, 0, flush)
+
+
+class LocatingHoldSelector(_IntervalSelector):
+    """HoldFrameSelector with sub_area="auto", in ONE pass over the frames: LocatingChangeSelector's shape for footage whose textured
+    background moves behind the subtitle, where only the held automaton finds an area or a threshold.  The held mask of a rectangle is a
+    walk along the frames over its pixels' EDGE bits, and an edge bit does not depend on the area, so up to the decision the batches
+    (whole frames) go through cells_fn with the held automaton, which keeps every frame's edge words beside the locator's totals
+    (vse_frame_cells_hold_masks), and nothing is yielded as closed.  The decision falls after frame `window` (a clip that ends sooner
+    decides at its end): the cells are flushed, the totals read once, with edge_thresh="auto" area_locator.pick_edge_thresh chooses, and
+    area_locator.locate_area decides on that threshold's totals, so area, threshold, `scores`, `totals` and `frames_scanned` are
+    AreaLocator(automaton="hold", probe=(1, window)).run(...)'s, its warning and no area when no threshold scores included.  With an
+    area, replay_fn walks the kept words of frames 1 .. window on it with the SELECTOR's hold (vse_frame_masks_replay_hold: integer for
+    integer vse_frame_hold's rows) and leaves count_fn where it would stand after those frames: without a flush while the clip goes on,
+    so the tracker has seen the rows 1 .. window - hold + 1 (iter_run's `tracker.fed`), with one when the clip ended inside the window.
+    One IntervalTracker, built as HoldFrameSelector builds its own (min_frames at least hold), is fed them, the intervals it has closed
+    are yielded with the deciding batch, and the rest of the frames run over the area's rows through count_fn like a plain
+    HoldFrameSelector, the usual flush behind them: the intervals and counts are HoldFrameSelector(edge_thresh=the choice)'s over the
+    whole clip on the located area.  Without an area, `area` stays None, `decided` is True and the generator ends, having consumed
+    min(window, clip) frames exactly (the first `window` frames are a staged run of their own).  The held locator's limits carry over
+    (area_locator's module text); whether a window of some length finds the band of a real film is not measured here (no real clips).
+
+    cells_fn(frames [n,h,w,3] uint8 | None, area, engine.CellParams, reset, flush, thresholds, cap, hold) -> totals [nt,gy,gx,4]; default
+    EngineCellsHoldMasks on the shim's device.  replay_fn(area, q, rect, count_fn, hold, flush) -> rows [.,3] at threshold index q on rect
+    (y0, y1, x0, x1 in the region's pixels), after which count_fn's next call (fed = the frames replayed) continues the clip; default
+    cells_fn.replay.  count_fn, hold_seconds, hold_frames: HoldFrameSelector's; count_fn is never called with fed = 0.  window: frames,
+    required.  edge_thresh: an integer or "auto".  locator_params: AreaLocator's keyword arguments (thresholds, min_edges, change_ratio,
+    min_seconds, max_seconds, plateau_frac, hold_seconds, hold_frames and locate_area's; automaton="hold" is implied and may be given);
+    another automaton, max_hold_*, search_area and probe are refused, max_hold_* for the selector too.  Before the decision `tracker` is
+    None."""
+
+    def __init__(self, count_fn=None, cells_fn=None, replay_fn=None, window=None, locator_params=None, hold_seconds=0.3, hold_frames=None,
+                 edge_thresh=128, change_ratio=0.5, min_edges=None, min_frames=2, batch=64, max_hold_seconds=None, max_hold_frames=None):
+        super().__init__(count_fn, edge_thresh, change_ratio, min_edges, min_frames, batch)
+        from . import area_locator
+        if window is None or int(window) < 1:
+            raise ValueError(f"LocatingHoldSelector: window must be at least 1 frame, not {window}")
+        self.window, self.cells_fn, self.replay_fn = int(window), cells_fn, replay_fn
+        self.hold_seconds, self.hold_frames, self.hold = hold_seconds, hold_frames, None
+        params = dict(locator_params or {})
+        refused = [f"automaton={params['automaton']!r}"] if params.get("automaton", "hold") != "hold" else []
+        refused += sorted(set(params) & {"max_hold_seconds", "max_hold_frames", "search_area", "probe"})
+        refused += [f"the selector's {k}" for k, v in (("max_hold_seconds", max_hold_seconds), ("max_hold_frames", max_hold_frames))
+                    if v is not None]
+        if refused:
+            raise ValueError("LocatingHoldSelector: the locator in the selector's pass counts whole frames with the held automaton, the "
+                             f"kept words are replayed with unbounded runs and `window` says how many frames decide; it does not take "
+                             f"{', '.join(refused)}")
+        self.locator = area_locator.AreaLocator(**{**params, "automaton": "hold", "edge_thresh": edge_thresh})
+        self.area, self.tracker, self.decided = None, None, False
+        self.scores = self.totals = None
+        self.frames_scanned = 0
+
+    # `hold` from hold_frames / hold_seconds and the frame rate, and the tracker's min_frames, by HoldFrameSelector's own rule (which
+    # reads the two bounds: runs are never bounded here)
+    _min_frames = HoldFrameSelector._min_frames
+    max_hold_seconds = max_hold_frames = None
+
+    def _lag(self):
+        return self.hold - 1
+
+    def iter_run(self, frames, sub_area=None, fps=None, uploader=None):
+        """HoldFrameSelector.iter_run over whole frames (sub_area must be None: this finds it); up to the decision every batch is yielded
+        with no closed interval and `tracker` is None."""
+        import logging
+
+        import numpy as np
+        from . import area_locator
+        if sub_area is not None:
+            raise ValueError(f"LocatingHoldSelector: it finds the area itself and takes none, not {sub_area}")
+        if self.count_fn is None or self.cells_fn is None:
+            from . import shim
+            self.count_fn = EngineHoldCounter(shim._context()) if self.count_fn is None else self.count_fn
+            self.cells_fn = EngineCellsHoldMasks(shim._context()) if self.cells_fn is None else self.cells_fn
+        replay = self.cells_fn.replay if self.replay_fn is None else self.replay_fn
+        loc = self.locator
+        ths = loc.thresholds if loc.auto else (loc.edge_thresh,)
+        self.counts, self.intervals, self.tracker, self.decided, self.area = np.zeros((0, 3), np.int32), [], None, False, None
+        self.edge_thresh = None if loc.auto else loc.edge_thresh
+        self.scores = self.totals = None
+        self.frames_scanned = 0
+        it = iter(frames)
+        bands = band_batches(islice(it, self.window), None, self.batch, type(self).__name__)
+        if bands.area is None:
+            return
+        min_frames = self._min_frames(fps)    # (sets `hold`, the selector's)
+        region, params = bands.area, loc.params(fps)
+        loc.hold = loc.hold_for(fps)          # the locator's, which area_params may set apart
+        rows = []                             # the rows of the window [.,3], then of the frames behind it, batch by batch
+        target = None                         # the located area in the pixels of its own rows, as count_fn takes it
+
+        def host(c, shape):
+            return np.asarray(c.cpu() if hasattr(c, "cpu") else c, np.int32).reshape(shape)
+
+        def decide(scanned, ended):
+            nonlocal target
+            totals = self.cells_fn(None, region, params, False, True, ths, self.window, loc.hold)
+            self.totals, self.frames_scanned, self.decided = host(totals, tuple(totals.shape)), scanned, True
+            q, chosen = 0, self.totals[0]
+            if loc.auto:
+                static_frac = loc.locate_kwargs.get("static_frac", 0.95)
+                self.scores = area_locator.edge_thresh_scores(self.totals, scanned, static_frac)
+                q = area_locator.pick_edge_thresh(self.totals, ths, scanned, static_frac, loc.plateau_frac)
+                if q is None:
+                    logging.getLogger(area_locator.__name__).warning(
+                        "edge_thresh='auto': none of the thresholds %s scores with the %s automaton in %d frames; falling back to %d", ths,
+                        loc.describe_automaton(), scanned, area_locator.DEFAULT_EDGE_THRESH)
+                    return []
+                self.edge_thresh, chosen = ths[q], self.totals[q]
+            else:
+                self.totals = chosen          # (AreaLocator's totals at one threshold are [gy,gx,4])
+            self.area = area_locator.locate_area(chosen, scanned, bands.geometry, bands.frame_hw, **loc.locate_kwargs)
+            if self.area is None:
+                return []
+            y0, y1, x0, x1 = clip_area(self.area, *bands.frame_hw)
+            target = (0, y1 - y0, x0, x1)
+            rows.append(host(replay(region, q, (y0 - bands.geometry[0], y1 - bands.geometry[0], x0 - region[2], x1 - region[2]),
+                                    self.count_fn, self.hold, ended), (-1, 3)))
+            min_edges = default_min_edges(y1 - y0, x1 - x0) if self.min_edges is None else self.min_edges
+            self.tracker = IntervalTracker(min_edges, self.change_ratio, min_frames)
+            self.intervals = self.tracker.feed(rows[-1])
+            return list(self.intervals)
+
+        fed, closed = 0, []
+        with closing(staging.staged_batches(bands, uploader)) as staged:
+            for items, data in staged:
+                self.cells_fn(data, region, params, fed == 0, False, ths, self.window, loc.hold)
+                fed += len(items)
+                if fed >= self.window:
+                    closed = decide(fed, False)
+                yield items, closed
+        if not self.decided:                  # the clip ended inside the window: the replay has flushed
+            closed = decide(fed, True)
+        elif self.area is not None:
+            closed = []                       # (they went out with the deciding batch)
+            empty = np.zeros((0, target[1], bands.frame_hw[1], 3), np.uint8)
+            rest = band_batches(it, self.area, self.batch, type(self).__name__)
+            if rest.area is not None:
+                with closing(staging.staged_batches(rest, uploader)) as staged:
+                    for items, data in staged:
+                        rows.append(host(self.count_fn(data, target, self.edge_thresh, self.hold, fed, False), (-1, 3)))
+                        got = self.tracker.feed(rows[-1])
+                        self.intervals += got
+                        fed += len(items)
+                        empty = data[:0]
+                        yield items, got
+            rows.append(host(self.count_fn(empty, target, self.edge_thresh, self.hold, fed, True), (-1, 3)))
+            closed = self.tracker.feed(rows[-1])
+            self.intervals += closed
+        if self.area is None:
+            return
+        last = self.tracker.flush()
+        self.intervals += last
+        self.counts = np.concatenate(rows)
+        yield [], closed + last
+
+
 # ---- interval composite (one picture per interval of the change selector) ------------------------------------------------
 COMPOSITE_MODES = ("min", "max", "mean")
 
