@@ -567,6 +567,43 @@ int vse_frame_cells_hold_bounded(vse_ctx* ctx, const void* d_bgr, int n, int src
                                  void* d_state, int64_t fed, int flush,
                                  int32_t* d_totals /* [nt,gy,gx,4]: covered, runs, present, cuts; accumulated across calls */,
                                  int32_t* d_cell_counts /* nullable: [nt, n + max_hold, gy, gx, 3] */, void* stream);
+/* Replaces: nothing in the reference; it serves the hold selector with bounded runs when it has to FIND its area while the frames go by
+ * (a pipe: vse_amd.frame_select.LocatingBoundedHoldSelector), as vse_frame_cells_hold_masks / vse_frame_masks_replay_hold serve the
+ * unbounded one.  A bounded mask is a walk along the frames over a pixel's EDGE bits, so the bounded locator's pass keeps the edge words
+ * it builds anyway, and once the area is decided a second kernel walks the rectangle's pixels through them.
+ * vse_frame_cells_hold_bounded_masks: vse_frame_cells_hold_bounded with one more output.  Arguments, checks, d_state
+ *   (vse_frame_cells_hold_bounded_state_bytes; it may pass between the two entries in the middle of a clip), d_totals and d_cell_counts
+ *   are that entry's, bit for bit.  d_masks, cap and slot0 are vse_frame_cells_masks': frame i of the call lands in slot slot0 + i of a
+ *   buffer of vse_frame_masks_bytes, in that entry's layout; what is kept are the edge words E_t: a call writes, bit for bit, the words
+ *   vse_frame_cells_masks writes for the same frames, region and thresholds.  Only frames get a slot: the flush step gets none, n == 0
+ *   writes none (d_masks may then be NULL), and no slot beside slot0 .. slot0 + n - 1 is touched.  One kernel launch on `stream`, no
+ *   allocation, no device sync.  Returns VSE_E_INVAL, without touching the device, for everything vse_frame_cells_hold_bounded refuses,
+ *   d_masks NULL or misaligned with n > 0, cap < 1, slot0 < 0 or slot0 + n > cap.
+ * vse_frame_masks_replay_hold_bounded: vse_frame_hold_bounded with the kept words in place of frames.  Slots [f0, f1) of such a buffer
+ *   at threshold index q on the rectangle [ry0, ry1) x [rx0, rx1) in REGION coordinates (at least 3 x 3, inside the region) are the
+ *   next f1 - f0 frames of a clip of which `fed` went to earlier calls ->
+ *     d_counts int32 [f1 - f0 + max_hold, 3]: from row 0 on the rows vse_frame_hold_bounded writes for those frames, integer for
+ *       integer: that entry on that rectangle of the frames at edge_thresh = thresholds[q] with the same hold, max_hold, fed and flush;
+ *     d_bounded_state: a vse_frame_hold_bounded state of the rectangle (vse_frame_hold_bounded_state_bytes(ry1 - ry0, rx1 - rx0,
+ *       max_hold) bytes, 8-byte aligned), read unless fed == 0 and left byte for byte as that entry leaves it, so that
+ *       vse_frame_hold_bounded on the following frames gives the rows of an uninterrupted run.
+ *   A window replayed in pieces, with fed advancing, gives the rows of one call; f1 == f0 with `flush` only drains the pending rows.
+ *   The buffer is only read, and only words of cells the rectangle touches.  Launches as vse_frame_hold_bounded (per 64 slots the walk
+ *   over the rectangle's tiles and one wave that finishes the rows), integer atomics and single-owner stores only; no allocation, no
+ *   device sync.  Returns VSE_E_INVAL, launching nothing, for everything vse_frame_masks_replay_hold refuses, max_hold < hold or
+ *   max_hold > 4000. */
+int vse_frame_cells_hold_bounded_masks(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride,
+                                       int y0, int y1, int x0, int x1, const int* thresholds /* host, [nt] */, int nt, int hold,
+                                       int max_hold, int min_edges, int ratio_num, int ratio_den, int min_frames, int max_frames,
+                                       void* d_state, int64_t fed, int flush,
+                                       int32_t* d_totals /* [nt,gy,gx,4], as vse_frame_cells_hold_bounded */,
+                                       int32_t* d_cell_counts /* nullable: [nt, n + max_hold, gy, gx, 3] */,
+                                       void* d_masks /* cap slots of vse_frame_masks_bytes(y1 - y0, x1 - x0, nt, 1) bytes */, int cap,
+                                       int slot0, void* stream);
+int vse_frame_masks_replay_hold_bounded(vse_ctx* ctx, const void* d_masks, int area_h, int area_w, int nt, int cap, int q, int f0, int f1,
+                                        int ry0, int ry1, int rx0, int rx1, int hold, int max_hold, void* d_bounded_state, int64_t fed,
+                                        int flush, int32_t* d_counts /* [f1 - f0 + max_hold, 3]: bounded edges, appeared, vanished */,
+                                        void* stream);
 
 /* ---- interval composite ------------------------------------------------------------------------------------------------- */
 /* Replaces: the picture VideoSubFinder hands to OCR for each subtitle it finds (the RGBImages the reference reads back at

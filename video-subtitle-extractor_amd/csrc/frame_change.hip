@@ -29,8 +29,10 @@
 //   frame_focus_kernel                vse_frame_focus: per frame, the number of edge pixels that were edge pixels one frame earlier and the
 //                                     sum of their gradients.
 //   frame_hold_bounded_kernel,        vse_frame_hold_bounded: the held-edge walk, but only runs of hold .. max_hold frames are counted, so that
-//   frame_hold_rows_kernel            the edges of a background that stands still drop out too.
-//   frame_cells_hold_bounded_kernel   vse_frame_cells_hold_bounded: the cells and their automaton at several thresholds on the bounded masks.
+//   frame_hold_rows_kernel,           the edges of a background that stands still drop out too; and vse_frame_masks_replay_hold_bounded,
+//   frame_masks_replay_hold_bounded_kernel  the same walk (frame_hold_bounded_body) on a rectangle of the region with the kept mask words.
+//   frame_cells_hold_bounded_kernel   vse_frame_cells_hold_bounded and _bounded_masks: the cells and their automaton at several thresholds
+//                                     on the bounded masks, optionally with the EDGE words of every frame kept in the caller's buffer.
 // The launchers of the first nine follow frame_focus_kernel; the two bounded sections each end with their own.
 //
 // What the kernels share is written once where that leaves their code as it was: the tile (tile_lane, tile_masks, tile_masks_multi), the
@@ -1168,21 +1170,21 @@ namespace {
 constexpr int HB_HEAD_BYTES = 16;
 
 // n frames, then steps - n steps without an edge (the flush), steps <= FC_CHUNK; slot0 = the ring slot of the first step's frame.
-__global__ __launch_bounds__(FC_WAVES * 64) void frame_hold_bounded_kernel(const uint8_t* __restrict__ src, int n, int steps, long pitch,
-                                                                           long fstride, int x0, int ih, int iw, int wpr, int thresh, int hold,
-                                                                           int max_hold, int slot0, int ring_slots,
-                                                                           unsigned short* __restrict__ state, int fresh, int* __restrict__ ring) {
+// The edge words come from frame_hold_body's policies, HoldFrames (frame_hold_bounded_kernel) or HoldSlots
+// (frame_masks_replay_hold_bounded_kernel): one text for both kernels, block (w, iy0 / FC_ROWS) owning the tile's run lengths.
+template <class SRC>
+__device__ __forceinline__ void frame_hold_bounded_body(const SRC& source, int n, int steps, int iy0, int w, int wpr, int hold, int max_hold,
+                                                        int slot0, int ring_slots, unsigned short* __restrict__ state, int fresh,
+                                                        int* __restrict__ ring) {
     __shared__ unsigned long long msk[FC_CHUNK][FC_ROWS];
     static_assert(FC_WAVES == FC_ROWS, "wave k walks interior row k of the tile");
     static_assert(FC_CHUNK == 64, "the steps of a launch are the lanes of a wave");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int w = blockIdx.x, iy0 = blockIdx.y * FC_ROWS;
-    const TileLane t = tile_lane(w, iy0, ih, iw, x0);
-    const bool mine = wave < t.rows;           // wave-uniform; the words of the other rows stay zero
+    const bool mine = wave < source.rows();    // wave-uniform; the words of the other rows stay zero
     unsigned short* st = state + ((long)(iy0 + wave) * wpr + w) * 64 + lane;
     int run = (mine && !fresh) ? (int)*st : 0;
 
-    tile_masks(src + (long)iy0 * pitch, 0, n, pitch, fstride, t, thresh, msk);
+    source.fill(0, n, msk);
     for (int i = n * FC_ROWS + threadIdx.x; i < steps * FC_ROWS; i += FC_WAVES * 64) msk[i / FC_ROWS][i % FC_ROWS] = 0ull;
     __syncthreads();
     if (mine) {
@@ -1224,6 +1226,32 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_hold_bounded_kernel(const
     }
 }
 
+// A gfx950 compile before the body became a template: 68 VGPRs, 96 SGPRs, 4096 bytes of LDS, no scratch, 7 waves per SIMD; after it the
+// same five figures.  (frame_masks_replay_hold_bounded_kernel below, which has no gradients to compute: 18 VGPRs, 40 SGPRs, 4096 bytes.)
+__global__ __launch_bounds__(FC_WAVES * 64) void frame_hold_bounded_kernel(const uint8_t* __restrict__ src, int n, int steps, long pitch,
+                                                                           long fstride, int x0, int ih, int iw, int wpr, int thresh, int hold,
+                                                                           int max_hold, int slot0, int ring_slots,
+                                                                           unsigned short* __restrict__ state, int fresh, int* __restrict__ ring) {
+    const int w = blockIdx.x, iy0 = blockIdx.y * FC_ROWS;
+    const HoldFrames source = {src + (long)iy0 * pitch, pitch, fstride, thresh, tile_lane(w, iy0, ih, iw, x0)};
+    frame_hold_bounded_body(source, n, steps, iy0, w, wpr, hold, max_hold, slot0, ring_slots, state, fresh, ring);
+}
+
+// vse_frame_masks_replay_hold_bounded: frame_hold_bounded_kernel on a rectangle of the region, its edge words taken from the kept masks
+// (frame_masks_replay_hold_kernel's argument: an edge bit does not depend on the area it is counted in).  Grid and block are
+// frame_hold_bounded_kernel's on the rectangle, the walk, the ring and the run lengths are frame_hold_bounded_body's, so the state this
+// leaves is vse_frame_hold_bounded's of that rectangle.  `slice` points at threshold q's first cell in the slot of step 0; the n real
+// steps read the slots of steps 0 .. n - 1, the flush step none.
+__global__ __launch_bounds__(FC_WAVES * 64) void frame_masks_replay_hold_bounded_kernel(const unsigned long long* __restrict__ slice,
+                                                                                        long slot_words, int gx, ReplayRect r, int n, int steps,
+                                                                                        int hold, int max_hold, int slot0, int ring_slots,
+                                                                                        unsigned short* __restrict__ state, int fresh,
+                                                                                        int* __restrict__ ring) {
+    const int w = blockIdx.x, iy0 = blockIdx.y * FC_ROWS;
+    const HoldSlots source = {slice, slot_words, gx, r, iy0, w};
+    frame_hold_bounded_body(source, n, steps, iy0, w, r.wpr, hold, max_hold, slot0, ring_slots, state, fresh, ring);
+}
+
 // One wave: the `rows` rows from ring slot `slot` on (rows <= ring_slots) -> out [rows][3] = |B|, appeared, vanished; their slots cleared.
 __global__ __launch_bounds__(64) void frame_hold_rows_kernel(int* __restrict__ ring, int* __restrict__ carry, int ring_slots, int slot, int rows,
                                                              int* __restrict__ out) {
@@ -1259,18 +1287,16 @@ size_t vse_frame_hold_bounded_bytes(int ih, int iw, int max_hold) {
     return HB_HEAD_BYTES + (size_t)(max_hold + FC_CHUNK) * 2 * sizeof(int32_t) + (size_t)ih * ((iw + 63) / 64) * HOLD_WORD_BYTES;
 }
 
-// Called by vse_frame_hold_bounded (vse_runtime.hip) after it has checked the arguments (1 <= hold <= max_hold, n + flush >= 1).  The call
-// is worked through in pieces of FC_CHUNK steps, each a launch of the walk and, where it completes rows, one of the finishing kernel.
-int vse_frame_hold_bounded_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
-                                  int hold, int max_hold, void* d_state, int64_t fed, int flush, int32_t* d_counts, void* stream) {
-    const int ih = y1 - y0 - 2, iw = x1 - x0 - 2, wpr = (iw + 63) / 64;
+// The loop of both bounded launchers: the call is worked through in pieces of FC_CHUNK steps, each a launch of the walk, walk(at, frames,
+// steps, slot0, ring_slots, pix, fresh, ring) over the frames at .. at + frames - 1 of the call, and, where it completes rows, one of the
+// finishing kernel.
+template <class WALK>
+static int hold_bounded_pieces(int n, int max_hold, void* d_state, int64_t fed, int flush, int32_t* d_counts, hipStream_t st, WALK walk) {
     const int ring_slots = max_hold + FC_CHUNK;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     int* carry = reinterpret_cast<int*>(d_state);
     int* ring = reinterpret_cast<int*>(reinterpret_cast<char*>(d_state) + HB_HEAD_BYTES);
     unsigned short* pix = reinterpret_cast<unsigned short*>(ring + 2 * (size_t)ring_slots);
     if (fed == 0 && hipMemsetAsync(d_state, 0, HB_HEAD_BYTES + (size_t)ring_slots * 2 * sizeof(int32_t), st) != hipSuccess) return VSE_E_HIP;
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
     const int64_t first = fed > max_hold ? fed - max_hold : 0;         // rows up to this frame went out with earlier calls
     int64_t written = first;
     const int64_t total = (int64_t)n + (flush ? 1 : 0);
@@ -1278,9 +1304,7 @@ int vse_frame_hold_bounded_launch(const void* d_bgr, int n, int64_t pitch, int64
         const int steps = (int)(total - at < FC_CHUNK ? total - at : FC_CHUNK);
         const int frames = (int)(n - at < steps ? n - at : steps);
         const int64_t done = fed + at + frames;                        // frames of the clip seen after this piece
-        hipLaunchKernelGGL(frame_hold_bounded_kernel, dim3(wpr, (ih + FC_ROWS - 1) / FC_ROWS), dim3(FC_WAVES * 64), 0, st,
-                           src + at * frame_stride, frames, steps, (long)pitch, (long)frame_stride, x0, ih, iw, wpr, edge_thresh, hold, max_hold,
-                           (int)((fed + at + 1) % ring_slots), ring_slots, pix, fed == 0 && at == 0, ring);
+        walk(at, frames, steps, (int)((fed + at + 1) % ring_slots), ring_slots, pix, (int)(fed == 0 && at == 0), ring);
         // a row is final once max_hold further frames have been seen: a run that still covers it is then too long
         const int64_t upto = (flush && at + steps == total) ? done : (done > max_hold ? done - max_hold : 0);
         if (upto > written) {                                          // at most max_hold + FC_CHUNK - 1 rows, the flush's
@@ -1290,6 +1314,38 @@ int vse_frame_hold_bounded_launch(const void* d_bgr, int n, int64_t pitch, int64
         }
     }
     return hipGetLastError() == hipSuccess ? VSE_OK : VSE_E_HIP;
+}
+
+// Called by vse_frame_hold_bounded (vse_runtime.hip) after it has checked the arguments (1 <= hold <= max_hold, n + flush >= 1).
+int vse_frame_hold_bounded_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1, int edge_thresh,
+                                  int hold, int max_hold, void* d_state, int64_t fed, int flush, int32_t* d_counts, void* stream) {
+    const int ih = y1 - y0 - 2, iw = x1 - x0 - 2, wpr = (iw + 63) / 64;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(d_bgr) + (long)y0 * pitch;
+    return hold_bounded_pieces(n, max_hold, d_state, fed, flush, d_counts, st,
+                               [&](int64_t at, int frames, int steps, int slot0, int ring_slots, unsigned short* pix, int fresh, int* ring) {
+        hipLaunchKernelGGL(frame_hold_bounded_kernel, dim3(wpr, (ih + FC_ROWS - 1) / FC_ROWS), dim3(FC_WAVES * 64), 0, st,
+                           src + at * frame_stride, frames, steps, (long)pitch, (long)frame_stride, x0, ih, iw, wpr, edge_thresh, hold, max_hold,
+                           slot0, ring_slots, pix, fresh, ring);
+    });
+}
+
+// Called by vse_frame_masks_replay_hold_bounded (vse_runtime.hip) after it has checked what vse_frame_masks_replay_hold_launch's caller
+// checks and 1 <= hold <= max_hold <= 4000; n = f1 - f0, n + flush >= 1.  The slice pointer of a piece advances by slots.
+int vse_frame_masks_replay_hold_bounded_launch(const void* d_masks, int area_h, int area_w, int nt, int q, int f0, int n, int ry0, int ry1,
+                                               int rx0, int rx1, int hold, int max_hold, void* d_state, int64_t fed, int flush,
+                                               int32_t* d_counts, void* stream) {
+    const int gy = (area_h - 2 + FC_ROWS - 1) / FC_ROWS, gx = (area_w - 2 + 63) / 64;
+    const long cells = (long)gy * gx, slot_words = (long)nt * cells * FC_ROWS;
+    ReplayRect r;
+    r.ry0 = ry0, r.rx0 = rx0, r.ih = ry1 - ry0 - 2, r.iw = rx1 - rx0 - 2, r.wpr = (r.iw + 63) / 64;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const unsigned long long* slice = reinterpret_cast<const unsigned long long*>(d_masks) + (long)f0 * slot_words + (long)q * cells * FC_ROWS;
+    return hold_bounded_pieces(n, max_hold, d_state, fed, flush, d_counts, st,
+                               [&](int64_t at, int frames, int steps, int slot0, int ring_slots, unsigned short* pix, int fresh, int* ring) {
+        hipLaunchKernelGGL(frame_masks_replay_hold_bounded_kernel, dim3(r.wpr, (r.ih + FC_ROWS - 1) / FC_ROWS), dim3(FC_WAVES * 64), 0, st,
+                           slice + at * slot_words, slot_words, gx, r, frames, steps, hold, max_hold, slot0, ring_slots, pix, fresh, ring);
+    });
 }
 
 // ---- vse_frame_cells_hold_bounded -------------------------------------------------------------------------------------------------
@@ -1316,18 +1372,36 @@ int vse_frame_hold_bounded_launch(const void* d_bgr, int n, int64_t pitch, int64
 // carry and open runs cleared by the launcher and ignores pix.
 namespace {
 
-template <int NT>
+// OUT and the trailing pack x are frame_cells_multi_kernel's: CELLS_ONLY (vse_frame_cells_hold_bounded; no argument, and the code this
+// kernel compiled to before it had the parameter) or CELLS_MASKS (vse_frame_cells_hold_bounded_masks; unsigned long long* masks, long
+// slot0): the edge words a chunk's real steps leave in LDS go to the caller's buffer in that kernel's layout and by its store loop, wave q
+// storing threshold q's rows in 64-byte lines, so a call writes bit for bit what frame_cells_multi_kernel<NT, CELLS_MASKS> writes for the
+// same frames.  Only the `real` steps are stored (step c0 + tl < n of the call is slot slot0 + c0 + tl < cap, checked by the launcher's
+// caller); the flush step has no slot.  This kind adds NO barrier: unlike the held walk, the bounded walk only reads msk (its words go to
+// registers once, its counts leave through the ring), so the words stay what tile_masks_multi left until the next chunk refills them.
+// The stores stand between the barrier behind the fill and the walk, and every wave, those with wave >= NT that skip the tail included,
+// passes the barrier behind the walk before it refills msk; a storing wave reaches that barrier only with its LDS reads done.  Issued
+// ahead of the walk, the stores drain under it.
+// VGPRs at NT = 1 .. 8 of a gfx950 compile:
+//   CELLS_ONLY before the parameter   85  98  96 100 103 102 114 112
+//   CELLS_ONLY with it                85  98  96 100 103 102 114 112
+//   CELLS_MASKS                       91 102 102 104 107 106 118 116
+// 106 SGPRs, 4096 NT bytes of LDS and no scratch in all three rows.  Waves per SIMD 5 4 5 4 4 4 4 4 without masks; with them NT = 3
+// drops from 5 to 4 (102 VGPRs), the other counts stay.
+template <int NT, int OUT, class... X>
 __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_hold_bounded_kernel(const uint8_t* __restrict__ src, int n, int steps, long pitch,
                                                                                  long fstride, int x0, int ih, int iw, CellThresholds th,
                                                                                  CellRule rule, int hold, int max_hold, int ring_slots, int slot_w,
                                                                                  int lagged, unsigned short* __restrict__ pix, unsigned* ring,
                                                                                  int* __restrict__ carry, int* __restrict__ open_runs, int fresh,
                                                                                  int flush, int* __restrict__ totals, int* __restrict__ cell_counts,
-                                                                                 int count_rows) {
+                                                                                 int count_rows, X... x) {
     __shared__ unsigned long long msk[NT * FC_CHUNK * FC_ROWS];           // [NT][FC_CHUNK][FC_ROWS]
     static_assert(FC_WAVES == FC_ROWS, "wave k walks interior row k of the tile");
     static_assert(FC_CHUNK == 64, "the steps of a chunk are the lanes of a wave");
     static_assert(NT >= 1 && NT <= FC_WAVES, "wave q owns threshold q");
+    static_assert(OUT == CELLS_ONLY || OUT == CELLS_MASKS, "the bounded cells keep masks or nothing");
+    static_assert(sizeof...(X) == (OUT == CELLS_ONLY ? 0 : 2), "the pack is the kind's arguments");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int iy0 = blockIdx.y * FC_ROWS, wpr = gridDim.x;
     const long cell = (long)blockIdx.y * gridDim.x + blockIdx.x, cells = (long)gridDim.y * gridDim.x;
@@ -1356,6 +1430,19 @@ __global__ __launch_bounds__(FC_WAVES * 64) void frame_cells_hold_bounded_kernel
         tile_masks_multi<NT>(src + (long)iy0 * pitch, c0, real, pitch, fstride, t, th, msk);
         zero_steps<NT>(msk, real, cn);
         __syncthreads();
+        if constexpr (OUT == CELLS_MASKS) {
+            // frame_cells_multi_kernel's store loop on the edge words of the chunk's real steps; nothing writes msk before the barrier
+            // behind the walk, which every wave passes before the next fill
+            static_assert(FC_ROWS == 8, "a lane's word of a store pass is lane % 8 of frame lane / 8");
+            if (mine) {
+                const unsigned long long* mq = msk + wave * FC_CHUNK * FC_ROWS;
+                const long slot_words = NT * cells * FC_ROWS;
+                unsigned long long* out =
+                    first_of(x...) + (second_of(x...) + c0 + (lane >> 3)) * slot_words + (wave * cells + cell) * FC_ROWS + (lane & 7);
+#pragma unroll 1
+                for (int i = lane; i < real * FC_ROWS; i += 64, out += (FC_CHUNK / FC_ROWS) * slot_words) *out = mq[i];
+            }
+        }
         if (walks) {
             // lane = step of the chunk for the words going in and the counts going out, lane = column for the walk
             int lo[NT], hi[NT], ended[NT];
@@ -1468,13 +1555,12 @@ CellsHoldBoundedLayout cells_hold_bounded_layout(int ih, int iw, int nt, int max
 
 size_t vse_frame_cells_hold_bounded_bytes(int ih, int iw, int nt, int max_hold) { return cells_hold_bounded_layout(ih, iw, nt, max_hold).total; }
 
-// Called by vse_frame_cells_hold_bounded (vse_runtime.hip) after it has checked the arguments (1 <= nt <= vse_frame_cells_multi_max(), 1 <=
-// hold <= max_hold <= 4000, n + flush >= 1, n + max_hold fits an int); count_rows = the rows of d_cell_counts per threshold.  One launch, and
-// before a clip's first one a clear of everything in the state but the run lengths.
-int vse_frame_cells_hold_bounded_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
-                                        const int* thresholds, int nt, int hold, int max_hold, const CellRule& rule, void* d_state,
-                                        int64_t fed, int flush, int32_t* d_totals, int32_t* d_cell_counts, int count_rows, void* stream) {
-    const CellsLaunch l(d_bgr, pitch, y0, y1, x0, x1, thresholds, nt, stream);
+// frame_cells_hold_bounded_kernel<nt, OUT, X...> with the kind's arguments x (X given explicitly, as for cells_multi_launch).  One launch,
+// and before a clip's first one a clear of everything in the state but the run lengths.
+template <int OUT, class... X>
+static int cells_hold_bounded_launch(const CellsLaunch& l, int n, int64_t pitch, int64_t frame_stride, int x0, int nt, int hold, int max_hold,
+                                     const CellRule& rule, void* d_state, int64_t fed, int flush, int32_t* d_totals, int32_t* d_cell_counts,
+                                     int count_rows, X... x) {
     const CellsHoldBoundedLayout lay = cells_hold_bounded_layout(l.ih, l.iw, nt, max_hold);
     char* base = reinterpret_cast<char*>(d_state);
     unsigned short* pix = reinterpret_cast<unsigned short*>(base);
@@ -1486,9 +1572,31 @@ int vse_frame_cells_hold_bounded_launch(const void* d_bgr, int n, int64_t pitch,
     const int64_t first = fed > max_hold ? fed - max_hold : 0;         // rows up to this frame went out with earlier calls
     const int steps = n + (flush ? 1 : 0);
     return launch_for_nt(nt, [&](auto nt_c) {
-        hipLaunchKernelGGL(frame_cells_hold_bounded_kernel<decltype(nt_c)::value>, l.grid, l.block, 0, l.st, l.src, n, steps, (long)pitch,
-                           (long)frame_stride, x0, l.ih, l.iw, l.th, rule, hold, max_hold, ring_slots, (int)((first + 1) % ring_slots),
-                           (int)(fed - first), pix, ring, carry, open_runs, fed == 0, flush, reinterpret_cast<int*>(d_totals),
-                           reinterpret_cast<int*>(d_cell_counts), count_rows);
+        hipLaunchKernelGGL((frame_cells_hold_bounded_kernel<decltype(nt_c)::value, OUT, X...>), l.grid, l.block, 0, l.st, l.src, n, steps,
+                           (long)pitch, (long)frame_stride, x0, l.ih, l.iw, l.th, rule, hold, max_hold, ring_slots,
+                           (int)((first + 1) % ring_slots), (int)(fed - first), pix, ring, carry, open_runs, fed == 0, flush,
+                           reinterpret_cast<int*>(d_totals), reinterpret_cast<int*>(d_cell_counts), count_rows, x...);
     });
+}
+
+// Called by vse_frame_cells_hold_bounded (vse_runtime.hip) after it has checked the arguments (1 <= nt <= vse_frame_cells_multi_max(), 1 <=
+// hold <= max_hold <= 4000, n + flush >= 1, n + max_hold fits an int); count_rows = the rows of d_cell_counts per threshold.
+int vse_frame_cells_hold_bounded_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                                        const int* thresholds, int nt, int hold, int max_hold, const CellRule& rule, void* d_state,
+                                        int64_t fed, int flush, int32_t* d_totals, int32_t* d_cell_counts, int count_rows, void* stream) {
+    const CellsLaunch l(d_bgr, pitch, y0, y1, x0, x1, thresholds, nt, stream);
+    return cells_hold_bounded_launch<CELLS_ONLY>(l, n, pitch, frame_stride, x0, nt, hold, max_hold, rule, d_state, fed, flush, d_totals,
+                                                 d_cell_counts, count_rows);
+}
+
+// Called by vse_frame_cells_hold_bounded_masks (vse_runtime.hip) after it has checked the arguments as vse_frame_cells_hold_bounded does and
+// 0 <= slot0, slot0 + n <= cap of d_masks: the n frames are the steps 0 .. n - 1 and take the slots slot0 .. slot0 + n - 1, the flush none.
+int vse_frame_cells_hold_bounded_masks_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                                              const int* thresholds, int nt, int hold, int max_hold, const CellRule& rule, void* d_state,
+                                              int64_t fed, int flush, int32_t* d_totals, int32_t* d_cell_counts, int count_rows, void* d_masks,
+                                              int slot0, void* stream) {
+    const CellsLaunch l(d_bgr, pitch, y0, y1, x0, x1, thresholds, nt, stream);
+    return cells_hold_bounded_launch<CELLS_MASKS, unsigned long long* __restrict__, long>(
+        l, n, pitch, frame_stride, x0, nt, hold, max_hold, rule, d_state, fed, flush, d_totals, d_cell_counts, count_rows,
+        reinterpret_cast<unsigned long long*>(d_masks), (long)slot0);
 }

@@ -95,6 +95,13 @@ int vse_frame_cells_hold_bounded_launch(const void* d_bgr, int n, int64_t pitch,
                                         const int* thresholds, int nt, int hold, int max_hold, const CellRule& rule, void* d_state,
                                         int64_t fed, int flush, int32_t* d_totals, int32_t* d_cell_counts, int count_rows,
                                         void* stream);                                                                 // frame_change.hip
+int vse_frame_cells_hold_bounded_masks_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0, int x1,
+                                              const int* thresholds, int nt, int hold, int max_hold, const CellRule& rule, void* d_state,
+                                              int64_t fed, int flush, int32_t* d_totals, int32_t* d_cell_counts, int count_rows, void* d_masks,
+                                              int slot0, void* stream);                                                // frame_change.hip
+int vse_frame_masks_replay_hold_bounded_launch(const void* d_masks, int area_h, int area_w, int nt, int q, int f0, int n, int ry0, int ry1,
+                                               int rx0, int rx1, int hold, int max_hold, void* d_state, int64_t fed, int flush,
+                                               int32_t* d_counts, void* stream);                                       // frame_change.hip
 int vse_scene_change_plane_pitch(int aw);                                                                              // scene_cut.hip
 int vse_scene_change_launch(const void* d_bgr, int n, int64_t pitch, int64_t frame_stride, int scale, int ah, int aw, int search, int bias,
                             void* d_state, int reset, void* d_ws, int32_t* d_counts, void* stream);
@@ -799,25 +806,34 @@ int vse_frame_cells_hold_masks(vse_ctx* c, const void* d_bgr, int n, int src_h, 
                     d_totals, d_cell_counts, n + hold - 1, d_masks, slot0, stream));
 }
 
-int vse_frame_masks_replay_hold(vse_ctx* c, const void* d_masks, int area_h, int area_w, int nt, int cap, int q, int f0, int f1, int ry0,
-                                int ry1, int rx0, int rx1, int hold, void* d_hold_state, int64_t fed, int flush, int32_t* d_counts,
-                                void* stream) {
+// what vse_frame_masks_replay_hold and vse_frame_masks_replay_hold_bounded check alike: the buffer, the slots and the rectangle
+static bool check_replay_hold(const char* who, vse_ctx* c, const void* d_masks, int area_h, int area_w, int nt, int cap, int q, int f0, int f1,
+                              int ry0, int ry1, int rx0, int rx1, const void* d_hold_state, int64_t fed, int flush, const int32_t* d_counts) {
     if (!c || !d_masks || !d_hold_state || area_h < 3 || area_w < 3 || nt < 1 || nt > vse_frame_cells_multi_max() || q < 0 || q >= nt ||
         fed < 0 || ((reinterpret_cast<uintptr_t>(d_masks) | reinterpret_cast<uintptr_t>(d_hold_state)) & 7) ||
         (reinterpret_cast<uintptr_t>(d_counts) & 3)) {
-        set_err("vse_frame_masks_replay_hold: bad arguments (region %d x %d of at least 3 x 3, threshold %d of %d (1..%d), fed %lld, masks and "
-                "state 8-byte aligned, no NULL pointer)", area_h, area_w, q, nt, vse_frame_cells_multi_max(), (long long)fed);
-        return VSE_E_INVAL;
+        set_err("%s: bad arguments (region %d x %d of at least 3 x 3, threshold %d of %d (1..%d), fed %lld, masks and "
+                "state 8-byte aligned, no NULL pointer)", who, area_h, area_w, q, nt, vse_frame_cells_multi_max(), (long long)fed);
+        return false;
     }
     if (f0 < 0 || f1 < f0 || f1 > cap || (f1 == f0 && !flush)) {
-        set_err("vse_frame_masks_replay_hold: slots [%d, %d) of a buffer of %d (0 <= f0 < f1 <= cap; f1 == f0 only with flush)", f0, f1, cap);
-        return VSE_E_INVAL;
+        set_err("%s: slots [%d, %d) of a buffer of %d (0 <= f0 < f1 <= cap; f1 == f0 only with flush)", who, f0, f1, cap);
+        return false;
     }
     if (ry0 < 0 || rx0 < 0 || ry1 > area_h || rx1 > area_w || ry1 - ry0 < 3 || rx1 - rx0 < 3) {
-        set_err("vse_frame_masks_replay_hold: rectangle [%d, %d) x [%d, %d) is degenerate or outside the %d x %d region", ry0, ry1, rx0, rx1,
+        set_err("%s: rectangle [%d, %d) x [%d, %d) is degenerate or outside the %d x %d region", who, ry0, ry1, rx0, rx1,
                 area_h, area_w);
-        return VSE_E_INVAL;
+        return false;
     }
+    return true;
+}
+
+int vse_frame_masks_replay_hold(vse_ctx* c, const void* d_masks, int area_h, int area_w, int nt, int cap, int q, int f0, int f1, int ry0,
+                                int ry1, int rx0, int rx1, int hold, void* d_hold_state, int64_t fed, int flush, int32_t* d_counts,
+                                void* stream) {
+    if (!check_replay_hold("vse_frame_masks_replay_hold", c, d_masks, area_h, area_w, nt, cap, q, f0, f1, ry0, ry1, rx0, rx1, d_hold_state,
+                           fed, flush, d_counts))
+        return VSE_E_INVAL;
     if (!check_hold("vse_frame_masks_replay_hold", hold)) return VSE_E_INVAL;
     int skip;
     const int64_t steps = hold_steps(f1 - f0, hold, fed, flush, &skip);
@@ -855,6 +871,50 @@ int vse_frame_cells_hold_bounded(vse_ctx* c, const void* d_bgr, int n, int src_h
     return launched("vse_frame_cells_hold_bounded", vse_frame_cells_hold_bounded_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, thresholds,
                     nt, hold, max_hold, {min_edges, ratio_num, ratio_den, min_frames, max_frames}, d_state, fed, flush != 0, d_totals,
                     d_cell_counts, n + max_hold, stream));
+}
+
+// ---- the bounded locator's edge masks kept, and the bounded selector's rows out of them (frame_change.hip) ----------------------------
+int vse_frame_cells_hold_bounded_masks(vse_ctx* c, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride,
+                                       int y0, int y1, int x0, int x1, const int* thresholds, int nt, int hold, int max_hold, int min_edges,
+                                       int ratio_num, int ratio_den, int min_frames, int max_frames, void* d_state, int64_t fed, int flush,
+                                       int32_t* d_totals, int32_t* d_cell_counts, void* d_masks, int cap, int slot0, void* stream) {
+    const char* who = "vse_frame_cells_hold_bounded_masks";
+    if (!check_frames(who, c && d_totals && fed >= 0 && (d_masks || n <= 0) && !(reinterpret_cast<uintptr_t>(d_masks) & 7), d_bgr, n, 0, src_h,
+                      src_w, pitch, frame_stride, d_state) ||
+        !check_area(who, "region", y0, y1, x0, x1, src_h, src_w) || !check_rule(who, ratio_num, ratio_den, min_frames, max_frames))
+        return VSE_E_INVAL;
+    if (!check_thresholds(who, thresholds, nt)) return VSE_E_INVAL;
+    if (!check_hold_bounded(who, hold, max_hold)) return VSE_E_INVAL;
+    if ((int64_t)n + max_hold > INT32_MAX) {
+        set_err("%s: %lld rows do not fit an int", who, (long long)n + max_hold);
+        return VSE_E_INVAL;
+    }
+    if (cap < 1 || slot0 < 0 || (int64_t)slot0 + n > cap) {
+        set_err("%s: %d frames from slot %d on do not fit a mask buffer of %d slots (no wrap)", who, n, slot0, cap);
+        return VSE_E_INVAL;
+    }
+    if (n == 0 && !flush) return VSE_OK;
+    return launched(who, vse_frame_cells_hold_bounded_masks_launch(d_bgr, n, pitch, frame_stride, y0, y1, x0, x1, thresholds, nt, hold, max_hold,
+                    {min_edges, ratio_num, ratio_den, min_frames, max_frames}, d_state, fed, flush != 0, d_totals, d_cell_counts, n + max_hold,
+                    d_masks, slot0, stream));
+}
+
+int vse_frame_masks_replay_hold_bounded(vse_ctx* c, const void* d_masks, int area_h, int area_w, int nt, int cap, int q, int f0, int f1, int ry0,
+                                        int ry1, int rx0, int rx1, int hold, int max_hold, void* d_bounded_state, int64_t fed, int flush,
+                                        int32_t* d_counts, void* stream) {
+    const char* who = "vse_frame_masks_replay_hold_bounded";
+    if (!check_replay_hold(who, c, d_masks, area_h, area_w, nt, cap, q, f0, f1, ry0, ry1, rx0, rx1, d_bounded_state, fed, flush, d_counts))
+        return VSE_E_INVAL;
+    if (!check_hold_bounded(who, hold, max_hold)) return VSE_E_INVAL;
+    // as vse_frame_hold_bounded: the row of a frame is final max_hold frames later, or at the flush
+    const int64_t n = f1 - f0;
+    const int64_t rows = (flush ? fed + n : std::max<int64_t>(0, fed + n - max_hold)) - std::max<int64_t>(0, fed - max_hold);
+    if (n == INT32_MAX || (rows > 0 && !d_counts)) {
+        set_err("%s: %lld rows need d_counts, and the slots + 1 must fit an int", who, (long long)rows);
+        return VSE_E_INVAL;
+    }
+    return launched(who, vse_frame_masks_replay_hold_bounded_launch(d_masks, area_h, area_w, nt, q, f0, (int)n, ry0, ry1, rx0, rx1, hold,
+                    max_hold, d_bounded_state, fed, flush != 0, d_counts, stream));
 }
 
 // ---- timeline sync: scene cuts for keyframe snapping (scene_cut.hip) ---------------------------------------------------------

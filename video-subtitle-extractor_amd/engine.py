@@ -37,6 +37,7 @@ EXPORTS = [
     "vse_yuv_vscale", "vse_frame_cells_counts", "vse_frame_cells_export_state",
     "vse_frame_masks_bytes", "vse_frame_cells_masks", "vse_frame_masks_replay",
     "vse_frame_cells_hold_masks", "vse_frame_masks_replay_hold",
+    "vse_frame_cells_hold_bounded_masks", "vse_frame_masks_replay_hold_bounded",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -229,6 +230,9 @@ def load_library(path=None):
     lib.vse_frame_cells_hold_bounded.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                                  C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                  C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vse_frame_cells_hold_bounded_masks.argtypes = lib.vse_frame_cells_hold_bounded.argtypes[:-1] + [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.vse_frame_masks_replay_hold_bounded.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 13 + [C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
+                                                                                                      C.c_void_p]
     lib.vse_interval_state_bytes.restype = C.c_size_t
     lib.vse_interval_state_bytes.argtypes = [C.c_int, C.c_int]
     lib.vse_interval_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
@@ -938,6 +942,57 @@ class Context:
                                                      self.stream()),
                "vse_frame_cells_hold_bounded")
         return (state.totals, counts[:, :rows]) if want_counts else state.totals
+
+    # ---- the bounded locator's edge masks, kept for a rectangle decided later ------------------------------------------
+    def frame_cells_hold_bounded_masks(self, frames_u8, area, thresholds, hold, max_hold, params, state, masks, slot0, fed, flush=False,
+                                       want_counts=False):
+        """frame_cells_hold_bounded that also keeps the EDGE masks: every argument as there, and the state is that call's
+        (frame_cells_hold_bounded_state; it may pass between the two); masks: frame_masks_buffer of the area's size and len(thresholds),
+        whose slots slot0 .. slot0 + n - 1 take the n frames exactly as frame_cells_masks fills them (the flush step takes none) ->
+        frame_cells_hold_bounded's result (include/vse_hip.h vse_frame_cells_hold_bounded_masks)."""
+        t = self.torch
+        frames = self._frames_args(frames_u8, allow_empty=True)
+        n = frames[1]
+        y0, y1, x0, x1 = (int(v) for v in area)
+        th = [int(v) for v in thresholds]
+        nt, hold, max_hold, fed = len(th), int(hold), int(max_hold), int(fed)
+        gy, gx = self.frame_cells_dims(y1 - y0, x1 - x0)
+        nbytes = self.lib.vse_frame_cells_hold_bounded_state_bytes(y1 - y0, x1 - x0, nt, max_hold)
+        assert nbytes and state.words.numel() >= nbytes and tuple(state.totals.shape) == (nt, gy, gx, 4)
+        assert (masks.area_h, masks.area_w, masks.nt) == (y1 - y0, x1 - x0, nt)
+        assert masks.words.numel() >= self.lib.vse_frame_masks_bytes(masks.area_h, masks.area_w, nt, masks.cap)
+        rows = (fed + n if flush else max(0, fed + n - max_hold)) - max(0, fed - max_hold)
+        counts = t.empty((nt, n + max_hold, gy, gx, 3), dtype=t.int32, device=self.tdev) if want_counts else None
+        p = CellParams(*(int(v) for v in params))
+        _check(self.lib.vse_frame_cells_hold_bounded_masks(self.handle, *frames, y0, y1, x0, x1, (C.c_int * nt)(*th), nt, hold, max_hold,
+                                                           p.min_edges, p.ratio_num, p.ratio_den, p.min_frames, p.max_frames,
+                                                           C.c_void_p(state.words.data_ptr()), fed, int(bool(flush)),
+                                                           C.c_void_p(state.totals.data_ptr()),
+                                                           C.c_void_p(counts.data_ptr()) if want_counts and counts.numel() else None,
+                                                           C.c_void_p(masks.words.data_ptr()), masks.cap, int(slot0), self.stream()),
+               "vse_frame_cells_hold_bounded_masks")
+        return (state.totals, counts[:, :rows]) if want_counts else state.totals
+
+    def frame_masks_replay_hold_bounded(self, masks, q, f0, f1, rect, hold, max_hold, state, fed, flush=False):
+        """Slots [f0, f1) of a MasksBuffer at threshold index q on rect = (ry0, ry1, rx0, rx1) in the region's pixels, as the next
+        f1 - f0 frames of a clip of which `fed` went to earlier calls; state: frame_hold_bounded_state of the rectangle's size and
+        `max_hold` -> cuda int32 [rows,3]: frame_hold_bounded's rows for those frames on that rectangle, and the state is left as
+        frame_hold_bounded leaves it, so that frame_hold_bounded continues the clip (include/vse_hip.h
+        vse_frame_masks_replay_hold_bounded)."""
+        t = self.torch
+        ry0, ry1, rx0, rx1 = (int(v) for v in rect)
+        hold, max_hold, fed, n = int(hold), int(max_hold), int(fed), int(f1) - int(f0)
+        nbytes = self.lib.vse_frame_hold_bounded_state_bytes(ry1 - ry0, rx1 - rx0, max_hold)
+        assert nbytes and state.dtype == t.uint8 and state.is_contiguous() and state.numel() >= nbytes
+        assert masks.words.numel() >= self.lib.vse_frame_masks_bytes(masks.area_h, masks.area_w, masks.nt, masks.cap)
+        rows = (fed + n if flush else max(0, fed + n - max_hold)) - max(0, fed - max_hold)
+        out = t.empty((max(0, n) + max_hold, 3), dtype=t.int32, device=self.tdev)
+        _check(self.lib.vse_frame_masks_replay_hold_bounded(self.handle, C.c_void_p(masks.words.data_ptr()), masks.area_h, masks.area_w,
+                                                            masks.nt, masks.cap, int(q), int(f0), int(f1), ry0, ry1, rx0, rx1, hold,
+                                                            max_hold, C.c_void_p(state.data_ptr()), fed, int(bool(flush)),
+                                                            C.c_void_p(out.data_ptr()), self.stream()),
+               "vse_frame_masks_replay_hold_bounded")
+        return out[:max(0, rows)]
 
     # ---- interval composite ---------------------------------------------------------------------------------------
     def interval_state(self, area_h, area_w):

@@ -369,6 +369,23 @@ class SubtitleExtractor:
     nothing is measured on real footage.  Refused with the key, by name: streaming_locate together with it, frame_selector other than
     "hold", an automaton other than "hold", max_hold_* in area_params or change_params, search_area, probe, area_params' streaming,
     interval_frame="sharpest", composite_params' streaming, shard, mode="accurate", a sub_area that is not "auto".
+    area_params={"streaming_locate_bounded": True} with sub_area="auto", frame_selector="hold", max_hold_seconds / max_hold_frames in
+    change_params AND in area_params, and mode "fast" or "auto": the same for the hold selector with bounded runs, the one for a busy
+    background that stands still behind the subtitle (an interview, a news desk, an animation still, a logo in the band), where the
+    unbounded selector merges the subtitles and the held locator scores nothing (frame_select.LocatingBoundedHoldSelector: the bounded
+    locator's kernel keeps the EDGE words it builds anyway, vse_frame_cells_hold_bounded_masks, and once the area is decided
+    vse_frame_masks_replay_hold_bounded walks the located rectangle's pixels through them with the selector's hold and max_hold, integer
+    for integer vse_frame_hold_bounded's rows and state).  A third sibling key, because the two others keep refusing max_hold_* by name;
+    any two together are refused.  The key implies automaton="hold"; the locator's bound is area_params' own and is NOT inherited from
+    change_params' (nor the other way round): both are required.  `locate_seconds` and `mask_gib` are the other keys', with their
+    meaning, bounds and error texts; `cells_bounded_masks_fn` and `replay_bounded_fn` are the selector's callables (default the GPU's);
+    the results are those of the run without the key whose area_params say automaton="hold", max_hold_* and probe=(1, that many frames).
+    In one pass sub_area="auto" and edge_thresh="auto" are accepted with it; the window's frames are kept on the host until the decision,
+    after which the selector's rows trail its frames by max_hold as always with a bound.  The bounded locator's limits carry over (a gap
+    between two subtitles shorter than max_hold comes back as an interval, a subtitle shown for longer than max_hold vanishes); max_hold
+    12-15 s and the window are guesses, nothing is measured on real footage.  Refused with the key, by name: either other locate key
+    together with it, frame_selector other than "hold", an automaton other than "hold", search_area, probe, area_params' streaming,
+    interval_frame="sharpest", composite_params' streaming, shard, mode="accurate", a sub_area that is not "auto".
     one_pass (None: exactly when the source has no `read`, e.g. ingest.Y4mStream over a pipe; True forces it on a seekable source and
     halves its decode work; False on a sequential source is a ValueError): the clip is read once, in decode order.  frame_selector="fps":
     frame `no` is a task iff (no - 1) % max(1, int(fps // extract_frequency)) == 0 (fps_tasks' rule without the frame count); tasks go
@@ -382,8 +399,8 @@ class SubtitleExtractor:
     SRT times, are untouched; `clamped_intervals` counts them and one warning is logged per run.  Where no interval was clamped, the
     intervals, the frames recognised, raw_lines and the SRT equal those of the multi-pass run() on the same frames with the same
     arguments (recognition does not depend on how frames are grouped into batches: tests/test_gpu_ragged.py).  Refused in one pass,
-    because they need a second look at frames already gone: sub_area="auto" (unless area_params says "streaming_locate" or "streaming_locate_hold"), mode="accurate" with an area, interval_image other than
-    "middle" (unless composite_params says "streaming": min / max / mean and the quantile), interval_text="fused", shard, change_params' edge_thresh="auto" (unless area_params says "streaming" or one of the two locate keys).
+    because they need a second look at frames already gone: sub_area="auto" (unless area_params says "streaming_locate", "streaming_locate_hold" or "streaming_locate_bounded"), mode="accurate" with an area, interval_image other than
+    "middle" (unless composite_params says "streaming": min / max / mean and the quantile), interval_text="fused", shard, change_params' edge_thresh="auto" (unless area_params says "streaming" or one of the three locate keys).
     interval_frame="sharpest" (change / hold selector with interval_image="middle" and interval_text="single" only; default "middle", all
     of the above): the one frame an interval is recognised on is chosen instead of being the middle one, which in compressed video is as
     likely as any other to be a coarse B-frame, a half-faded frame or a flash.  In the selector's own pass over the staged area rows the
@@ -476,26 +493,39 @@ class SubtitleExtractor:
         # Its keys, `streaming_locate`, `locate_seconds`, `mask_gib`, `cells_masks_fn` and `replay_fn`, are taken out here as well.
         # area_params={"streaming_locate_hold": True}: the same for frame_selector="hold" on held edges (frame_select.LocatingHoldSelector),
         # a sibling key with callables of its own, `cells_hold_masks_fn` and `replay_hold_fn`; `locate_seconds` and `mask_gib` go with either.
-        # `locating` is set by both keys, `locating_hold` says which.
+        # area_params={"streaming_locate_bounded": True}: the same for frame_selector="hold" with max_hold_* on bounded runs
+        # (frame_select.LocatingBoundedHoldSelector), a third sibling with `cells_bounded_masks_fn` and `replay_bounded_fn`.
+        # `locating` is set by all three keys, `locating_hold` and `locating_bounded` say which.
+        self.locating_bounded = bool(area_params.pop("streaming_locate_bounded", False)) if area_params else False
         self.locating_hold = bool(area_params.pop("streaming_locate_hold", False)) if area_params else False
         self.locating = bool(area_params.pop("streaming_locate", False)) if area_params else False
+        if self.locating_bounded and (self.locating or self.locating_hold):
+            other = "streaming_locate" if self.locating else "streaming_locate_hold"
+            raise ValueError("area_params={'streaming_locate_bounded': True} finds the area for frame_selector='hold' with max_hold_* and "
+                             f"area_params={{'{other}': True}} for frame_selector={'change' if self.locating else 'hold'!r}"
+                             f"{'' if self.locating else ' with unbounded runs'}; it does not combine with {other}, give one of them")
         if self.locating and self.locating_hold:
             raise ValueError("area_params={'streaming_locate_hold': True} finds the area for frame_selector='hold' and area_params="
                              "{'streaming_locate': True} for frame_selector='change'; it does not combine with streaming_locate, give one of them")
-        self.locating = self.locating or self.locating_hold
-        self._locate_key = "streaming_locate_hold" if self.locating_hold else "streaming_locate"
+        locating_change = self.locating
+        self.locating = self.locating or self.locating_hold or self.locating_bounded
+        self._locate_key = ("streaming_locate_bounded" if self.locating_bounded else
+                            "streaming_locate_hold" if self.locating_hold else "streaming_locate")
         change_fns, hold_fns = {"cells_masks_fn", "replay_fn"}, {"cells_hold_masks_fn", "replay_hold_fn"}
+        bounded_fns = {"cells_bounded_masks_fn", "replay_bounded_fn"}
         if not self.locating:
             own = sorted(set(area_params or {}) & ({"locate_seconds", "mask_gib"} | change_fns))
             if own:
                 raise ValueError(f"area_params: {own} belong to area_params={{'streaming_locate': True}} and mean nothing without it")
-        other, fns = ("streaming_locate", change_fns) if self.locating_hold else ("streaming_locate_hold", hold_fns)
-        own = sorted(set(area_params or {}) & fns)
-        if own:                                   # the callables of the key that is not set
-            raise ValueError(f"area_params: {own} belong to area_params={{'{other}': True}} and mean nothing without it")
+        for other, fns, given in (("streaming_locate", change_fns, locating_change), ("streaming_locate_hold", hold_fns, self.locating_hold),
+                                  ("streaming_locate_bounded", bounded_fns, self.locating_bounded)):
+            own = sorted(set(area_params or {}) & fns)
+            if own and not given:                 # the callables of a key that is not set
+                raise ValueError(f"area_params: {own} belong to area_params={{'{other}': True}} and mean nothing without it")
         self.locate_seconds = area_params.pop("locate_seconds", None) if self.locating else None
         self.mask_gib = area_params.pop("mask_gib", 8) if self.locating else None
-        names = ("cells_hold_masks_fn", "replay_hold_fn") if self.locating_hold else ("cells_masks_fn", "replay_fn")
+        names = (("cells_bounded_masks_fn", "replay_bounded_fn") if self.locating_bounded else
+                 ("cells_hold_masks_fn", "replay_hold_fn") if self.locating_hold else ("cells_masks_fn", "replay_fn"))
         self._locate_fns = tuple(area_params.pop(k, None) for k in names) if self.locating else None
         self.auto_area, self.area_params, self.located_area = isinstance(sub_area, str) and sub_area == "auto", area_params, None
         self.sub_area, self.mode, self.language = None if self.auto_area else sub_area, mode, language
@@ -529,7 +559,30 @@ class SubtitleExtractor:
         if not self.one_pass and not hasattr(source, "read"):
             raise ValueError("one_pass=False needs a source with read(frame_no): this one is sequential and its frames cannot be looked at a second time")
         self.frames_located = 0           # area_params' streaming_locate: the frames the located area rests on
-        if self.locating_hold:
+        if self.locating_bounded:
+            option = "area_params={'streaming_locate_bounded': True}"
+            bounds = {"max_hold_seconds", "max_hold_frames"}
+            refused = [(f"frame_selector={frame_selector!r}", frame_selector != "hold"),
+                       (f"automaton={self.area_params.get('automaton')!r}", self.area_params.get("automaton", "hold") != "hold"),
+                       ("search_area in area_params", "search_area" in self.area_params),
+                       ("probe in area_params (locate_seconds says how many frames decide)", "probe" in self.area_params),
+                       ("area_params={'streaming': True}", self.calibrating),
+                       (f"interval_frame={interval_frame!r}", interval_frame != "middle"),
+                       ("composite_params={'streaming': True}", self.streaming), (f"shard={shard!r}", shard is not None),
+                       (f"mode={mode!r}", mode not in ("fast", "auto")),
+                       (f"sub_area={sub_area!r} (the key finds the area of sub_area='auto' and means nothing with another)", not self.auto_area)]
+            for what, hit in refused:
+                if hit:
+                    raise ValueError(f"{option} finds the area of sub_area='auto' for frame_selector='hold' with max_hold_* while that "
+                                     f"selector runs, with the held automaton on whole frames and bounded runs; it does not combine with "
+                                     f"{what}, which needs the area from the first frame, counts other runs or has a pass of its own")
+            for where, given in (("change_params", change_params or {}), ("area_params", self.area_params)):
+                if all(given.get(k) is None for k in bounds):
+                    raise ValueError(f"{option} needs max_hold_seconds or max_hold_frames in {where}: the selector's bound and the locator's "
+                                     "are given each in its own place, neither is inherited from the other (without a bound the key is "
+                                     "streaming_locate_hold)")
+            self.area_params["automaton"] = "hold"            # (implied by the key)
+        elif self.locating_hold:
             option = "area_params={'streaming_locate_hold': True}"
             held = sorted(set(self.area_params) & {"max_hold_seconds", "max_hold_frames"})
             held_sel = sorted(set(change_params or {}) & {"max_hold_seconds", "max_hold_frames"})
@@ -712,13 +765,14 @@ class SubtitleExtractor:
                                                 "(fps sampler, scene-text filtering)", sel.frames_scanned)
 
     def _locating_selector(self, window):
-        if self.locating_hold:
+        if self.locating_hold or self.locating_bounded:
             params = {k: v for k, v in self.area_params.items() if k not in ("cells_fn", "batch")}
             if "hold_seconds" not in params and "hold_frames" not in params:
                 # _locator's rule: the locator holds as long as the selector does, unless area_params says otherwise
                 params.update({k: v for k, v in (self.change_params or {}).items() if k in ("hold_seconds", "hold_frames")})
-            return frame_select.LocatingHoldSelector(self.change_counter, *self._locate_fns, window=window, batch=self.batch,
-                                                     locator_params=params, **(self.change_params or {}))
+            cls = frame_select.LocatingBoundedHoldSelector if self.locating_bounded else frame_select.LocatingHoldSelector
+            return cls(self.change_counter, *self._locate_fns, window=window, batch=self.batch, locator_params=params,
+                       **(self.change_params or {}))
         return frame_select.LocatingChangeSelector(self.change_counter, *self._locate_fns, window=window, batch=self.batch,
                                                    locator_params={k: v for k, v in self.area_params.items() if k not in ("cells_fn", "batch")},
                                                    **(self.change_params or {}))
@@ -1146,7 +1200,8 @@ def default_locate_seconds(source, raw, auto_thresh, retain_bytes, mask_gib, lim
 
 
 def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, focus_fn=None, stream_fn=None, ring_fn=None,
-         cells_counts_fn=None, export_fn=None, cells_masks_fn=None, replay_fn=None, cells_hold_masks_fn=None, replay_hold_fn=None):
+         cells_counts_fn=None, export_fn=None, cells_masks_fn=None, replay_fn=None, cells_hold_masks_fn=None, replay_hold_fn=None,
+         cells_bounded_masks_fn=None, replay_bounded_fn=None):
     """ocr: the recogniser (None: shim.OcrRecogniser on the GPU, frames staged through staging.default_uploader, YUV 4:2:0 converted
     on the device); counter: the change / hold selector's count_fn (None: the GPU's); cells_fn: the locator's (None: the GPU's);
     composite_fn: what makes the picture of `--interval-image`, the compositor's accumulate_fn for min / max / mean and the quantile's
@@ -1156,6 +1211,7 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
     and hands over for `--streaming-calibration`, CalibratingChangeSelector's cells_fn and export_fn (None: the GPU's); cells_masks_fn,
     replay_fn: what keeps and replays the masks for `--streaming-locate`, LocatingChangeSelector's cells_fn and replay_fn (None: the GPU's);
     cells_hold_masks_fn, replay_hold_fn: the same for `--streaming-locate-hold`, LocatingHoldSelector's cells_fn and replay_fn (None: the
+    GPU's); cells_bounded_masks_fn, replay_bounded_fn: the same for `--streaming-locate-bounded`, LocatingBoundedHoldSelector's (None: the
     GPU's)."""
     p = argparse.ArgumentParser(prog="python -m vse_amd.extractor", description="Extract a video's hard subtitles to SRT on the GPU.  "
                                 "`-` reads YUV4MPEG2 from standard input in one pass, e.g. "
@@ -1208,11 +1264,15 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
     p.add_argument("--streaming-locate-hold", action="store_true", help="--area auto --selector hold: the same on held edges, for a "
                    "textured background that moves behind the subtitles (the locator counts with the hold automaton); takes --locate-seconds "
                    "and --mask-gib as --streaming-locate does")
-    p.add_argument("--locate-seconds", type=float, default=None, metavar="S", help="--streaming-locate / --streaming-locate-hold: the area is found on the first S "
+    p.add_argument("--streaming-locate-bounded", action="store_true", help="--area auto --selector hold --max-hold-seconds S: the same on "
+                   "bounded runs, for a busy background that stands still behind the subtitles (an interview, a news desk, a logo in the "
+                   "band); the locator's bound is --locator-max-hold-seconds, and --max-hold-seconds when that is not given; takes "
+                   "--locate-seconds and --mask-gib as --streaming-locate does")
+    p.add_argument("--locate-seconds", type=float, default=None, metavar="S", help="--streaming-locate / --streaming-locate-hold / --streaming-locate-bounded: the area is found on the first S "
                    "seconds; until then one pass keeps every frame and the device one bit per pixel and threshold [a file: the whole "
                    "clip; `-`: the largest whole number of seconds up to 300 whose frames fit --retain-gib and --mask-gib, about 57 for "
                    "1080p 4:2:0 at 24 fps, a policy, not a measurement: nobody has tried whether a minute of a real film finds its band]")
-    p.add_argument("--mask-gib", type=float, default=None, metavar="G", help="--streaming-locate / --streaming-locate-hold: bound on the masks kept on the device "
+    p.add_argument("--mask-gib", type=float, default=None, metavar="G", help="--streaming-locate / --streaming-locate-hold / --streaming-locate-bounded: bound on the masks kept on the device "
                    "until the area is found, GiB [8, a policy, not a measurement]")
     p.add_argument("--max-hold-seconds", type=float, default=None, metavar="S", help="--selector hold: count only edges that hold still for "
                    "at most S seconds, so a static busy background, a logo or a watermark drops out; a subtitle shown for longer drops out "
@@ -1263,7 +1323,7 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
             if args.selector != "hold":
                 raise ValueError(f"--max-hold-seconds bounds the runs of `--selector hold`, not of `--selector {args.selector}`")
             change_params["max_hold_seconds"] = args.max_hold_seconds
-        if args.locator_max_hold_seconds is not None and args.locator_automaton != "hold":
+        if args.locator_max_hold_seconds is not None and args.locator_automaton != "hold" and not args.streaming_locate_bounded:
             raise ValueError(f"--locator-max-hold-seconds bounds the runs of `--locator-automaton hold`, not of `--locator-automaton "
                              f"{args.locator_automaton}`")
         calibration = {}
@@ -1277,7 +1337,18 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
         if args.streaming_locate and args.streaming_locate_hold:
             raise ValueError("--streaming-locate finds the area for `--selector change` and --streaming-locate-hold for `--selector hold`: "
                              "give one of them")
-        if not args.streaming_locate and not args.streaming_locate_hold and (args.locate_seconds is not None or args.mask_gib is not None):
+        if args.streaming_locate_bounded and (args.streaming_locate or args.streaming_locate_hold):
+            other = "--streaming-locate" if args.streaming_locate else "--streaming-locate-hold"
+            raise ValueError(f"--streaming-locate-bounded finds the area for `--selector hold --max-hold-seconds S` and {other} for `--selector "
+                             f"{'change' if args.streaming_locate else 'hold'}`{'' if args.streaming_locate else ' without a bound'}: give one "
+                             "of them")
+        locator_max_hold_seconds = args.locator_max_hold_seconds
+        if args.streaming_locate_bounded and locator_max_hold_seconds is None and args.max_hold_seconds is not None:
+            locator_max_hold_seconds = args.max_hold_seconds
+            logging.getLogger(__name__).info("--streaming-locate-bounded: the locator bounds its runs as the selector does, --max-hold-seconds "
+                                             "%g (a policy; --locator-max-hold-seconds sets it apart)", locator_max_hold_seconds)
+        if (not args.streaming_locate and not args.streaming_locate_hold and not args.streaming_locate_bounded
+                and (args.locate_seconds is not None or args.mask_gib is not None)):
             raise ValueError("--locate-seconds and --mask-gib set the window and the device bound of --streaming-locate and mean nothing "
                              "without it")
         ring = args.streaming_composite and args.interval_image == "quantile"
@@ -1320,10 +1391,13 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
             shim.config.language, shim.config.mode = args.language, args.mode
             ocr, uploader = shim.OcrRecogniser(), staging.default_uploader()
         location = {}
-        if args.streaming_locate or args.streaming_locate_hold:
+        if args.streaming_locate or args.streaming_locate_hold or args.streaming_locate_bounded:
             flag, key = ("--streaming-locate-hold", "streaming_locate_hold") if args.streaming_locate_hold else ("--streaming-locate", "streaming_locate")
             fns = ({"cells_hold_masks_fn": cells_hold_masks_fn, "replay_hold_fn": replay_hold_fn} if args.streaming_locate_hold else
                    {"cells_masks_fn": cells_masks_fn, "replay_fn": replay_fn})
+            if args.streaming_locate_bounded:
+                flag, key = "--streaming-locate-bounded", "streaming_locate_bounded"
+                fns = {"cells_bounded_masks_fn": cells_bounded_masks_fn, "replay_bounded_fn": replay_bounded_fn}
             locate_seconds, mask_gib = args.locate_seconds, 8.0 if args.mask_gib is None else args.mask_gib
             if locate_seconds is None and args.video == "-" and area == "auto" and mask_gib > 0:
                 locate_seconds = default_locate_seconds(source, uploader is not None and hasattr(source, "raw_frames"), edge_thresh == "auto",
@@ -1340,8 +1414,8 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
                                change_params=change_params or None,
                                area_params={**calibration, **location, **({} if cells_fn is None else {"cells_fn": cells_fn}),
                                             **({} if args.locator_automaton == "change" else {"automaton": args.locator_automaton}),
-                                            **({} if args.locator_max_hold_seconds is None
-                                               else {"max_hold_seconds": args.locator_max_hold_seconds})} or None)
+                                            **({} if locator_max_hold_seconds is None
+                                               else {"max_hold_seconds": locator_max_hold_seconds})} or None)
         text = ex.run()
         if args.output is None:
             sys.stdout.write(text)

@@ -895,10 +895,21 @@ class LocatingHoldSelector(_IntervalSelector):
         super().__init__(count_fn, edge_thresh, change_ratio, min_edges, min_frames, batch)
         from . import area_locator
         if window is None or int(window) < 1:
-            raise ValueError(f"LocatingHoldSelector: window must be at least 1 frame, not {window}")
+            raise ValueError(f"{type(self).__name__}: window must be at least 1 frame, not {window}")
         self.window, self.cells_fn, self.replay_fn = int(window), cells_fn, replay_fn
         self.hold_seconds, self.hold_frames, self.hold = hold_seconds, hold_frames, None
         params = dict(locator_params or {})
+        self._check_params(params, max_hold_seconds, max_hold_frames)
+        self.locator = area_locator.AreaLocator(**{**params, "automaton": "hold", "edge_thresh": edge_thresh})
+        self.area, self.tracker, self.decided = None, None, False
+        self.scores = self.totals = None
+        self.frames_scanned = 0
+
+    # What LocatingBoundedHoldSelector changes: the default callables, what the constructor refuses, the bounds, the lag, and the
+    # arguments that follow `cap` for cells_fn and stand in place of `hold` for replay_fn and count_fn.
+    engine_count_fn, engine_cells_fn = EngineHoldCounter, EngineCellsHoldMasks
+
+    def _check_params(self, params, max_hold_seconds, max_hold_frames):
         refused = [f"automaton={params['automaton']!r}"] if params.get("automaton", "hold") != "hold" else []
         refused += sorted(set(params) & {"max_hold_seconds", "max_hold_frames", "search_area", "probe"})
         refused += [f"the selector's {k}" for k, v in (("max_hold_seconds", max_hold_seconds), ("max_hold_frames", max_hold_frames))
@@ -907,10 +918,6 @@ class LocatingHoldSelector(_IntervalSelector):
             raise ValueError("LocatingHoldSelector: the locator in the selector's pass counts whole frames with the held automaton, the "
                              f"kept words are replayed with unbounded runs and `window` says how many frames decide; it does not take "
                              f"{', '.join(refused)}")
-        self.locator = area_locator.AreaLocator(**{**params, "automaton": "hold", "edge_thresh": edge_thresh})
-        self.area, self.tracker, self.decided = None, None, False
-        self.scores = self.totals = None
-        self.frames_scanned = 0
 
     # `hold` from hold_frames / hold_seconds and the frame rate, and the tracker's min_frames, by HoldFrameSelector's own rule (which
     # reads the two bounds: runs are never bounded here)
@@ -920,6 +927,14 @@ class LocatingHoldSelector(_IntervalSelector):
     def _lag(self):
         return self.hold - 1
 
+    def _args(self):
+        return (self.hold,)
+
+    def _locator_args(self, fps):
+        loc = self.locator
+        loc.hold = loc.hold_for(fps)          # the locator's, which area_params may set apart
+        return (loc.hold,)
+
     def iter_run(self, frames, sub_area=None, fps=None, uploader=None):
         """HoldFrameSelector.iter_run over whole frames (sub_area must be None: this finds it); up to the decision every batch is yielded
         with no closed interval and `tracker` is None."""
@@ -928,11 +943,11 @@ class LocatingHoldSelector(_IntervalSelector):
         import numpy as np
         from . import area_locator
         if sub_area is not None:
-            raise ValueError(f"LocatingHoldSelector: it finds the area itself and takes none, not {sub_area}")
+            raise ValueError(f"{type(self).__name__}: it finds the area itself and takes none, not {sub_area}")
         if self.count_fn is None or self.cells_fn is None:
             from . import shim
-            self.count_fn = EngineHoldCounter(shim._context()) if self.count_fn is None else self.count_fn
-            self.cells_fn = EngineCellsHoldMasks(shim._context()) if self.cells_fn is None else self.cells_fn
+            self.count_fn = self.engine_count_fn(shim._context()) if self.count_fn is None else self.count_fn
+            self.cells_fn = self.engine_cells_fn(shim._context()) if self.cells_fn is None else self.cells_fn
         replay = self.cells_fn.replay if self.replay_fn is None else self.replay_fn
         loc = self.locator
         ths = loc.thresholds if loc.auto else (loc.edge_thresh,)
@@ -946,7 +961,7 @@ class LocatingHoldSelector(_IntervalSelector):
             return
         min_frames = self._min_frames(fps)    # (sets `hold`, the selector's)
         region, params = bands.area, loc.params(fps)
-        loc.hold = loc.hold_for(fps)          # the locator's, which area_params may set apart
+        cells_args, args = self._locator_args(fps), self._args()
         rows = []                             # the rows of the window [.,3], then of the frames behind it, batch by batch
         target = None                         # the located area in the pixels of its own rows, as count_fn takes it
 
@@ -955,7 +970,7 @@ class LocatingHoldSelector(_IntervalSelector):
 
         def decide(scanned, ended):
             nonlocal target
-            totals = self.cells_fn(None, region, params, False, True, ths, self.window, loc.hold)
+            totals = self.cells_fn(None, region, params, False, True, ths, self.window, *cells_args)
             self.totals, self.frames_scanned, self.decided = host(totals, tuple(totals.shape)), scanned, True
             q, chosen = 0, self.totals[0]
             if loc.auto:
@@ -976,7 +991,7 @@ class LocatingHoldSelector(_IntervalSelector):
             y0, y1, x0, x1 = clip_area(self.area, *bands.frame_hw)
             target = (0, y1 - y0, x0, x1)
             rows.append(host(replay(region, q, (y0 - bands.geometry[0], y1 - bands.geometry[0], x0 - region[2], x1 - region[2]),
-                                    self.count_fn, self.hold, ended), (-1, 3)))
+                                    self.count_fn, *args, ended), (-1, 3)))
             min_edges = default_min_edges(y1 - y0, x1 - x0) if self.min_edges is None else self.min_edges
             self.tracker = IntervalTracker(min_edges, self.change_ratio, min_frames)
             self.intervals = self.tracker.feed(rows[-1])
@@ -985,7 +1000,7 @@ class LocatingHoldSelector(_IntervalSelector):
         fed, closed = 0, []
         with closing(staging.staged_batches(bands, uploader)) as staged:
             for items, data in staged:
-                self.cells_fn(data, region, params, fed == 0, False, ths, self.window, loc.hold)
+                self.cells_fn(data, region, params, fed == 0, False, ths, self.window, *cells_args)
                 fed += len(items)
                 if fed >= self.window:
                     closed = decide(fed, False)
@@ -999,13 +1014,13 @@ class LocatingHoldSelector(_IntervalSelector):
             if rest.area is not None:
                 with closing(staging.staged_batches(rest, uploader)) as staged:
                     for items, data in staged:
-                        rows.append(host(self.count_fn(data, target, self.edge_thresh, self.hold, fed, False), (-1, 3)))
+                        rows.append(host(self.count_fn(data, target, self.edge_thresh, *args, fed, False), (-1, 3)))
                         got = self.tracker.feed(rows[-1])
                         self.intervals += got
                         fed += len(items)
                         empty = data[:0]
                         yield items, got
-            rows.append(host(self.count_fn(empty, target, self.edge_thresh, self.hold, fed, True), (-1, 3)))
+            rows.append(host(self.count_fn(empty, target, self.edge_thresh, *args, fed, True), (-1, 3)))
             closed = self.tracker.feed(rows[-1])
             self.intervals += closed
         if self.area is None:
@@ -1014,6 +1029,97 @@ class LocatingHoldSelector(_IntervalSelector):
         self.intervals += last
         self.counts = np.concatenate(rows)
         yield [], closed + last
+
+
+# ---- the same with bounded runs, for a busy background that stands still ------------------------------------------------------------
+class EngineCellsHoldBoundedMasks(DeviceState):
+    """cells_fn of LocatingBoundedHoldSelector on the GPU (Context.frame_cells_hold_bounded_masks), EngineCellsHoldMasks with the locator's
+    max_hold: keeps the device state and the mask buffer of the last region, threshold count, max_hold and `cap`, and `fed`; (frames |
+    None, area, engine.CellParams, reset, flush, thresholds, cap, hold, max_hold) -> totals [nt,gy,gx,4], frames None with flush draining
+    and closing the open runs.  `replay(area, q, rect, counter, hold, max_hold, flush)` walks the slots 0 .. fed - 1 at threshold index q
+    on `rect` (y0, y1, x0, x1 in the region's pixels) with the SELECTOR's hold and max_hold at once
+    (Context.frame_masks_replay_hold_bounded) -> frame_hold_bounded's rows of those frames, and sets up an EngineBoundedHoldCounter, its
+    state, key, hold and `fed`, so that its next call continues the clip on that rectangle."""
+
+    def __init__(self, ctx):
+        super().__init__(ctx)
+        self.fed, self._masks = 0, None
+
+    def __call__(self, frames, area, params, reset, flush, thresholds, cap, hold, max_hold):
+        t = self.ctx.torch
+        y0, y1, x0, x1 = area
+        frames = t.empty((0, y1, x1, 3), dtype=t.uint8, device=self.ctx.tdev) if frames is None else self._device(frames)
+        if self._fresh((y1 - y0, x1 - x0, len(thresholds), int(max_hold), int(cap)),
+                       lambda h, w, nt, max_hold, _cap: self.ctx.frame_cells_hold_bounded_state(h, w, nt, max_hold)):
+            self._masks, reset = self.ctx.frame_masks_buffer(y1 - y0, x1 - x0, len(thresholds), cap), True
+        if reset:
+            self.fed = 0
+        totals = self.ctx.frame_cells_hold_bounded_masks(frames, area, thresholds, hold, max_hold, params, self._state, self._masks,
+                                                         self.fed, self.fed, flush)
+        self.fed += len(frames)
+        return totals
+
+    def replay(self, area, q, rect, counter, hold, max_hold, flush):
+        y0, y1, x0, x1 = area
+        if self._key is None or self._key[:2] != (y1 - y0, x1 - x0) or not self.fed:
+            raise ValueError(f"EngineCellsHoldBoundedMasks: no masks of a {y1 - y0} x {x1 - x0} region to replay")
+        ry0, ry1, rx0, rx1 = rect
+        counter._fresh((ry1 - ry0, rx1 - rx0, max_hold), self.ctx.frame_hold_bounded_state)
+        counter._hold, counter.fed = hold, self.fed
+        return self.ctx.frame_masks_replay_hold_bounded(self._masks, q, 0, self.fed, rect, hold, max_hold, counter._state, 0, flush)
+
+
+class LocatingBoundedHoldSelector(LocatingHoldSelector):
+    """HoldFrameSelector(max_hold_*) with sub_area="auto", in ONE pass over the frames: LocatingHoldSelector for the footage of bounded
+    runs, a busy background that stands still behind the subtitle (an interview, a news desk, a logo in the band), where the unbounded
+    held automaton finds no area and the unbounded selector merges the subtitles.  iter_run is LocatingHoldSelector's, text for text;
+    what differs are the hooks: the locator counts bounded masks and keeps the edge words (vse_frame_cells_hold_bounded_masks), the
+    replay walks them with the SELECTOR's hold and max_hold (vse_frame_masks_replay_hold_bounded: integer for integer
+    vse_frame_hold_bounded's rows and state), count_fn has the bounded counter's signature, and the rows trail the frames by the
+    selector's max_hold: after a window of W frames without a flush the tracker has seen the rows 1 .. max(0, W - max_hold).  So area,
+    threshold, `scores`, `totals` and `frames_scanned` are AreaLocator(automaton="hold", max_hold_*=the locator's, probe=(1,
+    window)).run(...)'s, and the intervals and counts HoldFrameSelector(max_hold_*=the selector's, edge_thresh=the choice)'s over the
+    whole clip on the located area.  The bounded locator's limits carry over (area_locator's module text: a gap shorter than max_hold
+    stays present, a subtitle shown for longer than max_hold vanishes); max_hold and the window are guesses, nothing is measured on
+    real footage.
+
+    cells_fn(frames | None, area, engine.CellParams, reset, flush, thresholds, cap, hold, max_hold) -> totals; default
+    EngineCellsHoldBoundedMasks.  replay_fn(area, q, rect, count_fn, hold, max_hold, flush) -> rows; default cells_fn.replay.  count_fn:
+    HoldFrameSelector's with max_hold_* (frames, area, edge_thresh, hold, max_hold, fed, flush); default EngineBoundedHoldCounter.
+    max_hold_seconds / max_hold_frames: the selector's, one of them required.  locator_params: as LocatingHoldSelector's, and
+    max_hold_seconds / max_hold_frames for the LOCATOR, one of them required too (they are not inherited from the selector's: the two
+    may differ); another automaton, search_area and probe are refused."""
+    engine_count_fn, engine_cells_fn = EngineBoundedHoldCounter, EngineCellsHoldBoundedMasks
+
+    def __init__(self, count_fn=None, cells_fn=None, replay_fn=None, window=None, locator_params=None, hold_seconds=0.3, hold_frames=None,
+                 edge_thresh=128, change_ratio=0.5, min_edges=None, min_frames=2, batch=64, max_hold_seconds=None, max_hold_frames=None):
+        super().__init__(count_fn, cells_fn, replay_fn, window, locator_params, hold_seconds, hold_frames, edge_thresh, change_ratio,
+                         min_edges, min_frames, batch, max_hold_seconds, max_hold_frames)
+        self.max_hold_seconds, self.max_hold_frames, self.max_hold = max_hold_seconds, max_hold_frames, None
+
+    def _check_params(self, params, max_hold_seconds, max_hold_frames):
+        refused = [f"automaton={params['automaton']!r}"] if params.get("automaton", "hold") != "hold" else []
+        refused += sorted(set(params) & {"search_area", "probe"})
+        if refused:
+            raise ValueError("LocatingBoundedHoldSelector: the locator in the selector's pass counts whole frames with the held automaton "
+                             f"on bounded runs and `window` says how many frames decide; it does not take {', '.join(refused)}")
+        if max_hold_seconds is None and max_hold_frames is None:
+            raise ValueError("LocatingBoundedHoldSelector: the selector's max_hold_seconds or max_hold_frames is required (without a "
+                             "bound it is LocatingHoldSelector)")
+        if params.get("max_hold_seconds") is None and params.get("max_hold_frames") is None:
+            raise ValueError("LocatingBoundedHoldSelector: locator_params' max_hold_seconds or max_hold_frames is required: the locator's "
+                             "bound is not inherited from the selector's")
+
+    def _lag(self):
+        return self.max_hold
+
+    def _args(self):
+        return (self.hold, self.max_hold)
+
+    def _locator_args(self, fps):
+        loc = self.locator
+        loc.hold, loc.max_hold = loc.hold_for(fps), loc.max_hold_for(fps)
+        return (loc.hold, loc.max_hold)
 
 
 # ---- interval composite (one picture per interval of the change selector) ------------------------------------------------
