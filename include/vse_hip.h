@@ -1064,6 +1064,28 @@ int vse_yuv_vscale(vse_ctx* ctx, const void* d_yuv, int n, int w, int h_in, int 
                    const void* d_table_c /* device, 16-byte aligned; NULL for grey */, int taps_c, int64_t yuv_frame_stride, void* d_out,
                    int64_t out_frame_stride, void* stream);
 
+/* ---- colour key of the selectors' band (coloured subtitles) --------------------------------------------------------------------------- */
+/* uint8 BGR frames [n, src_h, src_w, 3] (row pitch `pitch` bytes, frame stride `frame_stride` bytes) and the area [y0, y1) x [x0, x1)
+ * (not empty, inside the frame; 1 x 1 is allowed) -> the same area of d_out, in the input's coordinates: pixel (y, x) of frame f is at
+ * d_out + f out_frame_stride + y out_pitch + 3 x, so one `area` addresses both sides.  Exact integers:
+ *   d = max(|B - key_b|, |G - key_g|, |R - key_r|);   K = max(0, 255 - ((d * slope) >> 8));   out pixel = (K, K, K)
+ * The selectors' luma of (K, K, K) is K itself (29 + 150 + 77 = 256), so vse_frame_change and every other entry point that builds an edge
+ * mask runs on the keyed frames unchanged: its gradient is K's.  The device knows integers, not tolerances: slope = ceil(255 * 256 / tol)
+ * gives K = 255 at d = 0 and K = 0 from d = tol on (vse_amd.frame_select.ColourKey).
+ * One launch on `stream`, no allocation, no device sync, no LDS.  Every pixel of the area is written.  The call may widen the columns to
+ * 16-pixel boundaries inside [0, src_w) of the same rows, and what it writes there is the key of the pixel there; it reads and writes
+ * nothing in rows outside [y0, y1), nothing beyond 3 * src_w bytes of a row and nothing outside the n frames, so a caller may pass the
+ * area's rows alone, as with vse_frame_change.  The input is only read.  Where both bases, both pitches and (n > 1) both frame strides
+ * are 16-byte aligned a lane owns 16 pixels (three 16-byte loads, three 16-byte stores); otherwise a lane owns one pixel of the area and
+ * moves it byte by byte, at any alignment.  n == 0 is VSE_OK without a launch.
+ * Returns VSE_E_INVAL, with the values in vse_last_error, and touches nothing on the device, for an empty or out-of-frame area, a key
+ * component outside 0..255, slope outside 256..65280, a pitch below 3 * src_w on either side, n < 0, (n > 1) a frame stride below a
+ * frame's bytes on either side, a NULL pointer with n > 0, and input and output byte ranges (rows [y0, y1) of the first frame to the
+ * last frame) that overlap. */
+int vse_colour_key(vse_ctx* ctx, const void* d_bgr, int n, int src_h, int src_w, int64_t pitch, int64_t frame_stride, int y0, int y1, int x0,
+                   int x1, int key_b, int key_g, int key_r, int slope, void* d_out, int64_t out_pitch, int64_t out_frame_stride,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,11 +219,14 @@ class AreaLocator:
     * fps))) when that is None.  With "change" cells_fn gets no such keyword.
     max_hold_seconds / max_hold_frames (with automaton="hold" only; both None: the call above, keyword for keyword): cells_fn gets
     max_hold=`max_hold` as well and counts bounded masks; `max_hold` is kept on the object: max_hold_frames, or round(max_hold_seconds *
-    fps) when that is None (HoldFrameSelector's rule); below `hold` or above 4000 is a ValueError."""
+    fps) when that is None (HoldFrameSelector's rule); below `hold` or above 4000 is a ValueError.
+    key_fn(frames, area) -> frames of the same shape (frame_select.ColourKey.apply, EngineKey): when given, every staged batch goes
+    through it and cells_fn counts on its result, so the cells see the colour key's gradient (coloured subtitles).  None: cells_fn
+    receives the staged data itself."""
 
     def __init__(self, cells_fn=None, edge_thresh=128, min_edges=16, change_ratio=0.5, min_seconds=0.3, max_seconds=20.0, batch=64,
                  probe=None, search_area=None, thresholds=AUTO_THRESHOLDS, plateau_frac=0.9, automaton="change", hold_seconds=0.3,
-                 hold_frames=None, max_hold_seconds=None, max_hold_frames=None, **locate_kwargs):
+                 hold_frames=None, max_hold_seconds=None, max_hold_frames=None, key_fn=None, **locate_kwargs):
         if automaton not in ("change", "hold"):
             raise ValueError(f"AreaLocator: automaton must be 'change' or 'hold', not {automaton!r}")
         if hold_frames is not None and not 1 <= int(hold_frames) <= 32:
@@ -237,7 +240,7 @@ class AreaLocator:
             raise ValueError(f"AreaLocator: max_hold_frames {max_hold_frames} is below hold_frames {hold_frames}")
         self.automaton, self.hold_seconds, self.hold_frames, self.hold = automaton, hold_seconds, hold_frames, None
         self.max_hold_seconds, self.max_hold_frames, self.max_hold = max_hold_seconds, max_hold_frames, None
-        self.cells_fn = cells_fn
+        self.cells_fn, self.key_fn = cells_fn, key_fn
         self.auto = isinstance(edge_thresh, str) and edge_thresh == "auto"
         self.thresholds = tuple(int(v) for v in thresholds)
         if self.auto and not (1 <= len(self.thresholds) <= 8 and all(1 <= v <= 255 for v in self.thresholds)
@@ -306,7 +309,7 @@ class AreaLocator:
               **({"max_hold": self.max_hold} if self.max_hold is not None else {})}
         cells = self.cells_fn if not kw else (lambda *a: self.cells_fn(*a, **kw))
         for items, data in staging.staged_batches(bands, uploader):
-            cells(data, area, params, not self.frames_scanned, False)
+            cells(data if self.key_fn is None else self.key_fn(data, area), area, params, not self.frames_scanned, False)
             self.frames_scanned += len(items)
         totals = cells(None, area, params, False, True)
         self.totals = np.asarray(totals.cpu() if hasattr(totals, "cpu") else totals).astype(np.int32)
@@ -334,8 +337,9 @@ def parse_edge_thresh(text):
     return int(text)
 
 
-def main(argv=None, cells_fn=None):
-    """cells_fn: see AreaLocator (None: the GPU, frames staged through an uploader, YUV 4:2:0 converted on the device)."""
+def main(argv=None, cells_fn=None, key_fn=None):
+    """cells_fn: see AreaLocator (None: the GPU, frames staged through an uploader, YUV 4:2:0 converted on the device); key_fn: given the
+    frame_select.ColourKey of `--text-colour`, what takes the key (None: frame_select.EngineKey on the GPU)."""
     p = argparse.ArgumentParser(prog="python -m vse_amd.area_locator", description="Find a video's subtitle area on the GPU and print "
                                 "it as `ymin ymax xmin xmax` (what SubtitleExtractor takes as sub_area).")
     p.add_argument("video", help="uncompressed BGR24 or Motion-JPEG AVI, a .npy frame stack, .y4m, or headerless .yuv / .i420 / .nv12")
@@ -355,9 +359,10 @@ def main(argv=None, cells_fn=None):
                    "Y4M header's]")
     p.add_argument("--deinterlace-thresh", type=int, default=10, metavar="N", help="--deinterlace adaptive: a sample that changed by more "
                    "than N 8-bit levels since the previous frame has moved, 0..255 [10]")
-    from .extractor import add_match_arguments, add_square_arguments, match_arguments, square_arguments
+    from .extractor import add_colour_arguments, add_match_arguments, add_square_arguments, colour_arguments, match_arguments, square_arguments
     add_match_arguments(p)
     add_square_arguments(p)
+    add_colour_arguments(p)
     p.add_argument("--transfer", default=None, choices=("pq", "hlg"), help="HDR video (needs --wide-yuv or --pix-fmt): undo PQ or HLG and "
                    "tone-map to SDR on the GPU [none]")
     p.add_argument("--white-nits", type=float, default=None, metavar="N", help="--transfer: the luminance that becomes SDR white [203]")
@@ -391,6 +396,10 @@ def main(argv=None, cells_fn=None):
                 raise ValueError(f"--size takes WIDTHxHEIGHT, not {args.size!r}")
             size = (int(w), int(h))
         from .extractor import tone_arguments
+        colour = colour_arguments(args)
+        if colour is not None:
+            from .frame_select import EngineKey
+            colour = EngineKey(None, colour) if key_fn is None else key_fn(colour)
         if args.deinterlace is None and (args.field_order != "auto" or args.deinterlace_thresh != 10):
             raise ValueError("--field-order and --deinterlace-thresh belong to --deinterlace adaptive | interpolate | match")
         fields = {} if args.deinterlace is None else dict(deinterlace=args.deinterlace, field_order=args.field_order,
@@ -400,7 +409,7 @@ def main(argv=None, cells_fn=None):
                                     **fields, **match_arguments(args), **tone_arguments(args), **square_arguments(args))
         loc = AreaLocator(cells_fn, probe=args.probe, edge_thresh=parse_edge_thresh(args.edge_thresh), automaton=args.locator_automaton,
                           hold_seconds=args.hold_seconds, hold_frames=args.hold_frames, max_hold_seconds=args.max_hold_seconds,
-                          max_hold_frames=args.max_hold_frames)
+                          max_hold_frames=args.max_hold_frames, key_fn=colour)
         if cells_fn is None:
             from . import staging
             up = staging.default_uploader()

@@ -37,7 +37,7 @@ EXPORTS = [
     "vse_yuv_vscale", "vse_frame_cells_counts", "vse_frame_cells_export_state",
     "vse_frame_masks_bytes", "vse_frame_cells_masks", "vse_frame_masks_replay",
     "vse_frame_cells_hold_masks", "vse_frame_masks_replay_hold",
-    "vse_frame_cells_hold_bounded_masks", "vse_frame_masks_replay_hold_bounded",
+    "vse_frame_cells_hold_bounded_masks", "vse_frame_masks_replay_hold_bounded", "vse_colour_key",
 ]
 # Entry points whose names carry a digit.  tests/test_abi.py reads the header's function names with a letters-only pattern and holds
 # them equal to EXPORTS, so these are listed apart; load_library checks both lists, tests/test_yuv_ingest.py holds header = library =
@@ -192,6 +192,8 @@ def load_library(path=None):
     lib.vse_frame_change.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.vse_frame_focus.argtypes = lib.vse_frame_change.argtypes
+    lib.vse_colour_key.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
     lib.vse_frame_cells_dims.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.vse_frame_cells_state_bytes.restype = C.c_size_t
     lib.vse_frame_cells_state_bytes.argtypes = [C.c_int, C.c_int]
@@ -613,6 +615,23 @@ class Context:
         out = t.empty((frames[1], 2), dtype=t.int32, device=self.tdev)
         _check(self.lib.vse_frame_focus(self.handle, *frames, y0, y1, x0, x1, int(edge_thresh), C.c_void_p(state.data_ptr()),
                                         int(bool(reset)), C.c_void_p(out.data_ptr()), self.stream()), "vse_frame_focus")
+        return out
+
+    def colour_key(self, frames_u8, area, key, out=None):
+        """frames_u8 and area as for frame_change (an area of 1 x 1 is allowed); key: .bgr = (B, G, R) and .slope (frame_select.ColourKey)
+        -> cuda uint8 of the input's shape (`out`, or a new tensor; pixels packed, any row pitch / frame stride): inside the area, and
+        where the call widens its columns, every pixel is (K, K, K), K = max(0, 255 - ((max |channel - key| * slope) >> 8)); the other
+        bytes are not written (include/vse_hip.h vse_colour_key).  The frames are only read."""
+        t = self.torch
+        frames = self._frames_args(frames_u8, allow_empty=True)
+        y0, y1, x0, x1 = (int(v) for v in area)
+        if out is None:
+            out = t.empty(tuple(frames_u8.shape), dtype=t.uint8, device=self.tdev)
+        assert out.dtype == t.uint8 and tuple(out.shape) == tuple(frames_u8.shape) and out.is_cuda, (out.dtype, tuple(out.shape))
+        dst = self._frames_args(out, allow_empty=True)
+        b, g, r = (int(v) for v in key.bgr)
+        _check(self.lib.vse_colour_key(self.handle, *frames, y0, y1, x0, x1, b, g, r, int(key.slope), dst[0], dst[4], dst[5], self.stream()),
+               "vse_colour_key")
         return out
 
     # ---- subtitle-area locator ------------------------------------------------------------------------------------

@@ -229,6 +229,33 @@ def _stack(frames):
         return np.stack(frames)
 
 
+def _key_names(params):
+    """The colour-key names among change_params / area_params."""
+    return sorted(set(params or {}) & {"text_colour", "colour_tol", "key_fn"})
+
+
+def _key_params(params, where):
+    """change_params / area_params with `text_colour` (frame_select.parse_colour's forms) and `colour_tol` (1..255, default 48) ->
+    (the params with a `key_fn` in their place, the frame_select.ColourKey or None): an EngineKey on the shim's device, made when it is
+    first called.  A `key_fn` given instead, a callable (frames, area) -> frames, is kept as it is."""
+    names = _key_names(params)
+    if not names:
+        return params, None
+    if "key_fn" in names:
+        if len(names) > 1:
+            raise ValueError(f"{where}: key_fn is a colour key of the caller's own; it does not combine with {names}")
+        return params, None
+    if "text_colour" not in names:
+        raise ValueError(f"{where}: colour_tol needs a text_colour")
+    params = dict(params)
+    try:
+        key = frame_select.ColourKey(params.pop("text_colour"), params.pop("colour_tol", 48))
+    except ValueError as e:
+        raise ValueError(f"{where}: {e}") from None
+    params["key_fn"] = frame_select.EngineKey(None, key)
+    return params, key
+
+
 def _boxes_array(dt_box):
     return np.asarray(dt_box, np.float32).reshape(-1, 4, 2)
 
@@ -312,6 +339,14 @@ class SubtitleExtractor:
     yields the area and the threshold, with a given area one calibration pass runs over the area's rows.  When no threshold scores
     (no subtitles, or a textured background that moves behind them: the calibration uses the change automaton unless
     `automaton="hold"`) it warns and uses 128.  How the choice behaves on real footage is not measured here.
+    change_params={"text_colour": "#RRGGBB" | a name | (B, G, R), "colour_tol": 48} (frame_selector "change" or "hold", in several passes
+    and in one): coloured subtitles over a background with many luma edges.  The selector, whichever of the classes above it is, builds
+    its masks on the colour key of the band (frame_select.ColourKey, vse_colour_key: 255 on the colour, 0 from colour_tol levels away in
+    any channel) instead of on its luma; the locator and the calibration do the same, with area_params' own text_colour / colour_tol
+    where it names them (not with a locator or calibration in the selector's own pass, whose key is the selector's).  The compositors,
+    the quantile, the fuser and the recogniser keep the frames as they are.  `colour_key` is the ColourKey, `key_fn` what takes it (an
+    EngineKey on the shim's device; change_params={"key_fn": callable} gives another).  colour_tol=48 is a guess checked on a synthetic
+    clip only; the colour is not chosen automatically, BGR is the only colour space, and accurate mode and the fps sampler build no mask.
     area_params={"automaton": "hold"}: the locator and the calibration count held edges (area_locator's module text), which is what a
     textured background that moves behind the subtitles needs; with frame_selector="hold" they take the selector's hold_seconds /
     hold_frames from change_params unless area_params sets its own.  Opt-in: without it nothing changes.
@@ -540,6 +575,17 @@ class SubtitleExtractor:
         # detector of the next chunks stays in flight); ocr.predict_with_dets, when it exists, recognises from those boxes
         self.detect_stream = detect_stream
         self.word_segmentation, self.segment = word_segmentation, segment      # config.wordSegmentation (main.py:181-182)
+        # change_params={"text_colour": ..., "colour_tol": ...}: the selector, and the locator and calibration unless area_params names a
+        # colour of its own, build their masks on the colour key of the band (frame_select.ColourKey).  Both pairs become a `key_fn` here.
+        if _key_names(change_params) and frame_selector not in ("change", "hold"):
+            raise ValueError(f"change_params: {_key_names(change_params)} key the band of frame_selector='change' or 'hold', which build a "
+                             f"mask; frame_selector={frame_selector!r} builds none")
+        if _key_names(self.area_params) and (self.locating or self.calibrating):
+            raise ValueError(f"area_params: {_key_names(self.area_params)} do not combine with a locator or calibration that runs in the "
+                             "selector's own pass (streaming, streaming_locate*): there the key is the selector's, change_params' text_colour")
+        change_params, self.colour_key = _key_params(change_params, "change_params")
+        self.area_params, _own = _key_params(self.area_params, "area_params")
+        self.key_fn = (change_params or {}).get("key_fn")
         self.frame_selector, self.change_params, self.change_counter = frame_selector, change_params, change_counter
         et = (change_params or {}).get("edge_thresh", 128)
         self.auto_thresh = isinstance(et, str) and et == "auto"
@@ -687,6 +733,8 @@ class SubtitleExtractor:
             params.update({k: v for k, v in (self.change_params or {}).items() if k in ("hold_seconds", "hold_frames")})
         if self.auto_thresh and self.frame_selector in ("change", "hold"):
             params["edge_thresh"] = "auto"
+        if self.key_fn is not None and "key_fn" not in own:
+            params["key_fn"] = self.key_fn            # the locator and the calibration key as the selector does, unless area_params says otherwise
         return area_locator.AreaLocator(**params)
 
     def _keep_edge_thresh(self, loc):
@@ -1137,6 +1185,32 @@ def match_arguments(args):
     return out
 
 
+def add_colour_arguments(p):
+    """--text-colour / --colour-tol of both command lines (colour_arguments reads them)."""
+    p.add_argument("--text-colour", default=None, metavar="RRGGBB|name", help="coloured subtitles: build the edge masks on how near each "
+                   "pixel is to this fill colour instead of on its luma, which tells the text from a background with many luma edges; "
+                   "RRGGBB, #RRGGBB, or one of " + ", ".join(sorted(frame_select.COLOUR_NAMES)) + " [none: luma]")
+    p.add_argument("--colour-tol", default=None, metavar="N", help="--text-colour: the largest channel difference, 1..255, at which a "
+                   "pixel no longer counts as that colour [48, a guess checked on a synthetic clip only]")
+
+
+def colour_arguments(args):
+    """-> the frame_select.ColourKey the two options ask for, or None; ValueError, naming the option, for a bad value."""
+    if args.text_colour is None:
+        if args.colour_tol is not None:
+            raise ValueError("--colour-tol is the tolerance of --text-colour and means nothing without it")
+        return None
+    tol = 48 if args.colour_tol is None else args.colour_tol
+    if isinstance(tol, str):
+        if not (tol.isdigit() and 1 <= int(tol) <= 255):
+            raise ValueError(f"--colour-tol takes an integer 1..255, not {tol!r}")
+        tol = int(tol)
+    try:
+        return frame_select.ColourKey(args.text_colour, tol)
+    except ValueError as e:
+        raise ValueError(f"--text-colour: {e}") from None
+
+
 def add_square_arguments(p):
     """--square-pixels, --sar, --scale and --resample-filter, for the command lines that take them."""
     p.add_argument("--square-pixels", action="store_true", help="anamorphic YUV (DVD, HDV, DVCPRO HD, 1440-column broadcast): resample "
@@ -1201,7 +1275,7 @@ def default_locate_seconds(source, raw, auto_thresh, retain_bytes, mask_gib, lim
 
 def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, focus_fn=None, stream_fn=None, ring_fn=None,
          cells_counts_fn=None, export_fn=None, cells_masks_fn=None, replay_fn=None, cells_hold_masks_fn=None, replay_hold_fn=None,
-         cells_bounded_masks_fn=None, replay_bounded_fn=None):
+         cells_bounded_masks_fn=None, replay_bounded_fn=None, key_fn=None):
     """ocr: the recogniser (None: shim.OcrRecogniser on the GPU, frames staged through staging.default_uploader, YUV 4:2:0 converted
     on the device); counter: the change / hold selector's count_fn (None: the GPU's); cells_fn: the locator's (None: the GPU's);
     composite_fn: what makes the picture of `--interval-image`, the compositor's accumulate_fn for min / max / mean and the quantile's
@@ -1212,7 +1286,7 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
     replay_fn: what keeps and replays the masks for `--streaming-locate`, LocatingChangeSelector's cells_fn and replay_fn (None: the GPU's);
     cells_hold_masks_fn, replay_hold_fn: the same for `--streaming-locate-hold`, LocatingHoldSelector's cells_fn and replay_fn (None: the
     GPU's); cells_bounded_masks_fn, replay_bounded_fn: the same for `--streaming-locate-bounded`, LocatingBoundedHoldSelector's (None: the
-    GPU's)."""
+    GPU's); key_fn: given the frame_select.ColourKey of `--text-colour`, what takes the key (None: frame_select.EngineKey on the GPU)."""
     p = argparse.ArgumentParser(prog="python -m vse_amd.extractor", description="Extract a video's hard subtitles to SRT on the GPU.  "
                                 "`-` reads YUV4MPEG2 from standard input in one pass, e.g. "
                                 "`ffmpeg -i film.mkv -pix_fmt yuv420p -f yuv4mpegpipe - | python -m vse_amd.extractor - -o film.srt`.")
@@ -1254,6 +1328,7 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
     p.add_argument("--selector", default="fps", choices=("fps", "change", "hold"), help="which frames go to OCR [fps]")
     p.add_argument("--edge-thresh", default="128", metavar="auto|N", help="change / hold selector: the luma gradient that makes an edge "
                    "pixel, or `auto` to choose it for this clip first (not in one pass) [128]")
+    add_colour_arguments(p)
     p.add_argument("--streaming-calibration", action="store_true", help="--selector change --edge-thresh auto with a given --area: choose "
                    "the threshold in the selector's own pass instead of a pass of its own, which also works in one pass (a pipe)")
     p.add_argument("--calibrate-seconds", type=float, default=None, metavar="S", help="--streaming-calibration: the threshold is chosen "
@@ -1319,6 +1394,12 @@ def main(argv=None, ocr=None, counter=None, cells_fn=None, composite_fn=None, fo
         from .area_locator import parse_edge_thresh
         edge_thresh = parse_edge_thresh(args.edge_thresh)
         change_params = {} if edge_thresh == 128 else {"edge_thresh": edge_thresh}
+        colour = colour_arguments(args)
+        if colour is not None:
+            if args.selector == "fps":
+                raise ValueError("--text-colour keys the band of `--selector change` or `--selector hold`, which build a mask; `--selector "
+                                 "fps` builds none")
+            change_params.update({"text_colour": colour.bgr, "colour_tol": colour.tol} if key_fn is None else {"key_fn": key_fn(colour)})
         if args.max_hold_seconds is not None:
             if args.selector != "hold":
                 raise ValueError(f"--max-hold-seconds bounds the runs of `--selector hold`, not of `--selector {args.selector}`")

@@ -20,7 +20,8 @@ vse_frame_focus) also scores every frame in the same pass, and `sharpest_rep` pi
 a `compositor` (StreamingCompositor, vse_interval_stream) also makes each interval's min / max / mean picture in that pass, or
 (StreamingQuantile, vse_interval_ring_rank) its quantile picture.  CalibratingChangeSelector (vse_frame_cells_counts) is the change
 selector that chooses its edge threshold per clip in that same pass, and LocatingChangeSelector (vse_frame_cells_masks,
-vse_frame_masks_replay) the one that finds its area there.
+vse_frame_masks_replay) the one that finds its area there.  Any of them given a `key_fn` (ColourKey.apply, EngineKey: vse_colour_key)
+builds its masks on the colour key of the band, for coloured subtitles, and leaves pictures and text to the frames as they are.
 """
 from collections import deque
 from contextlib import closing
@@ -291,6 +292,81 @@ class band_batches:
         return iter(self._take, [])           # (no generator frame that would hold on to the list it yielded last)
 
 
+# ---- colour key (coloured subtitles over a background with many luma edges) ----------------------------------------------------------
+COLOUR_NAMES = {"white": (255, 255, 255), "yellow": (0, 255, 255), "cyan": (255, 255, 0), "green": (0, 255, 0), "black": (0, 0, 0)}      # B, G, R
+
+
+def parse_colour(colour):
+    """The one place a text colour is read: (B, G, R) of three integers 0..255, "#RRGGBB" / "RRGGBB", or a name of COLOUR_NAMES ->
+    (B, G, R).  ValueError for anything else."""
+    if isinstance(colour, str):
+        text = colour.strip().lower()
+        if text in COLOUR_NAMES:
+            return COLOUR_NAMES[text]
+        digits = text[1:] if text.startswith("#") else text
+        if len(digits) == 6 and all(c in "0123456789abcdef" for c in digits):
+            return int(digits[4:6], 16), int(digits[2:4], 16), int(digits[0:2], 16)
+        raise ValueError(f"text colour {colour!r} is not RRGGBB, #RRGGBB or one of {', '.join(sorted(COLOUR_NAMES))}")
+    try:
+        bgr = tuple(int(v) for v in colour)
+        exact = all(int(v) == v for v in colour)
+    except (TypeError, ValueError):
+        bgr, exact = (), False
+    if len(bgr) != 3 or not exact or not all(0 <= v <= 255 for v in bgr):
+        raise ValueError(f"text colour {colour!r} is not (B, G, R) of three integers 0..255")
+    return bgr
+
+
+class ColourKey:
+    """The selectors' second cue beside the luma gradient: how near a pixel is to the subtitle's fill colour.  With
+    d = max(|B - b|, |G - g|, |R - r|) against colour = (b, g, r), a pixel becomes (K, K, K), K = max(0, 255 - ((d * slope) >> 8)) and
+    slope = ceil(255 * 256 / tol): K is 255 on the colour itself, falls with d and is 0 from d = tol on.  The selectors' luma of (K, K,
+    K) is K (29 + 150 + 77 = 256), so a selector, locator or calibration given a key_fn runs unchanged on K's gradient: a background of
+    other colours is flat there however many luma edges it has.  colour: see parse_colour; tol: 1..255.  tol=48 is a guess, checked on
+    the synthetic clip only (no real clips).  Known limit: a background whose colours saturate to the corners of the colour cube passes
+    the key where it meets the text's corner (3 to 10 % of random cells at amplitude 250), and the keyed selector then fails as well.
+    `bgr`, `slope`: what vse_colour_key takes.  apply(frames, area) is the key_fn in numpy, the same integers as the device's."""
+
+    def __init__(self, colour, tol=48):
+        self.bgr = parse_colour(colour)
+        if isinstance(tol, bool) or int(tol) != tol or not 1 <= int(tol) <= 255:
+            raise ValueError(f"colour tolerance {tol!r} is not an integer 1..255")
+        self.tol = int(tol)
+        self.slope = -(-255 * 256 // self.tol)
+
+    def apply(self, frames, area):
+        """frames uint8 [n,h,w,3], area (y0, y1, x0, x1) in their pixels -> uint8 of the same shape: the key inside the area, 0 elsewhere."""
+        import numpy as np
+        frames = np.asarray(frames)
+        y0, y1, x0, x1 = area
+        out = np.zeros(frames.shape, np.uint8)
+        d = np.abs(frames[:, y0:y1, x0:x1].astype(np.int32) - np.asarray(self.bgr, np.int32)).max(-1)
+        out[:, y0:y1, x0:x1] = np.maximum(0, 255 - ((d * self.slope) >> 8))[..., None]
+        return out
+
+
+class EngineKey(DeviceState):
+    """key_fn of the selectors and the locator on the GPU (Context.colour_key): (frames [n,h,w,3] uint8, area) -> the keyed frames, a
+    device tensor of the same shape, launched on the current stream, so in front of the count that reads it.  One output tensor is kept
+    per shape and written again by the next call with that shape: the result is for the kernels launched before that call.
+    ctx None: the shim's device, asked for at the first call.  key: a ColourKey (default: white at its default tolerance)."""
+
+    def __init__(self, ctx, key=None):
+        super().__init__(ctx)
+        self.key = ColourKey("white") if key is None else key
+        self._outs = {}
+
+    def __call__(self, frames, area):
+        if self.ctx is None:
+            from . import shim
+            self.ctx = shim._context()
+        frames = self._device(frames)
+        out = self._outs.get(tuple(frames.shape))
+        if out is None:
+            out = self._outs[tuple(frames.shape)] = self.ctx.torch.empty(tuple(frames.shape), dtype=self.ctx.torch.uint8, device=self.ctx.tdev)
+        return self.ctx.colour_key(frames, area, self.key, out=out)
+
+
 class EngineCounter(DeviceState):
     """count_fn of ChangeFrameSelector on the GPU (Context.frame_change): keeps the device state of the last area between calls."""
 
@@ -319,11 +395,15 @@ class _IntervalSelector:
     frames fed: they do not trail like the hold selector's counts.  None: no call, and `focus` is not touched.
     compositor (StreamingCompositor or StreamingQuantile): when given, begin(fps, lag) is called before the first batch, with `lag` the number of frames by
     which the rows trail (`_lag`), then compositor(data, area, n, tracker, closed) once per staged batch, after the tracker has been
-    fed and while the batch is still resident, and once more after the flush with n = 0 and the last closings.  None: nothing changes."""
+    fed and while the batch is still resident, and once more after the flush with n = 0 and the last closings.  None: nothing changes.
+    key_fn(frames [n,h,w,3] uint8, area) -> frames of the same shape (ColourKey.apply, EngineKey): when given, it is called once per
+    staged batch (or once per slice a body cuts from a batch), with the area the mask is about to be built on, and its result goes to
+    whatever builds a mask (count_fn, focus_fn, cells_fn); the compositor and the yielded items keep the staged band and the frames.
+    None: count_fn, focus_fn and cells_fn receive the staged data itself."""
 
     def __init__(self, count_fn=None, edge_thresh=128, change_ratio=0.5, min_edges=None, min_frames=2, batch=64, focus_fn=None,
-                 compositor=None):
-        self.count_fn, self.focus_fn, self.compositor = count_fn, focus_fn, compositor
+                 compositor=None, key_fn=None):
+        self.count_fn, self.focus_fn, self.compositor, self.key_fn = count_fn, focus_fn, compositor, key_fn
         self.edge_thresh, self.change_ratio, self.min_edges, self.min_frames = edge_thresh, change_ratio, min_edges, min_frames
         self.batch = batch
         self.counts = None
@@ -370,9 +450,10 @@ class _IntervalSelector:
         room = np.zeros((0, 2), np.int64)
         with closing(staging.staged_batches(bands, uploader)) as staged:
             for items, data in staged:
-                counts = self._count(data, bands.area, fed)
+                keyed = data if self.key_fn is None else self.key_fn(data, bands.area)
+                counts = self._count(keyed, bands.area, fed)
                 if self.focus_fn is not None:             # (launched before the counts are read back: one wait for both)
-                    rows = self.focus_fn(data, bands.area, self.edge_thresh, fed == 0)
+                    rows = self.focus_fn(keyed, bands.area, self.edge_thresh, fed == 0)
                 closed = feed(counts)
                 if self.focus_fn is not None:
                     rows = np.asarray(rows.cpu() if hasattr(rows, "cpu") else rows, np.int64).reshape(-1, 2)
@@ -384,7 +465,7 @@ class _IntervalSelector:
                     self.compositor(data, bands.area, len(items), self.tracker, closed)
                 fed += len(items)
                 yield items, closed
-        closed = feed(self._flush(data, bands.area, fed))
+        closed = feed(self._flush(data, bands.area, fed))         # (no frames: nothing to key)
         self.counts = np.concatenate(out)
         last = self.tracker.flush()
         self.intervals += last
@@ -466,8 +547,8 @@ class CalibratingChangeSelector(_IntervalSelector):
     it `edge_thresh`, `scores`, `totals`, `frames_scanned` and `chosen` (the index) say what was decided and on what."""
 
     def __init__(self, count_fn=None, cells_fn=None, export_fn=None, window=None, locator_params=None, change_ratio=0.5, min_edges=None,
-                 min_frames=2, batch=64):
-        super().__init__(count_fn, None, change_ratio, min_edges, min_frames, batch)
+                 min_frames=2, batch=64, key_fn=None):
+        super().__init__(count_fn, None, change_ratio, min_edges, min_frames, batch, key_fn=key_fn)
         from . import area_locator
         if window is not None and int(window) < 1:
             raise ValueError(f"CalibratingChangeSelector: window must be at least 1 frame or None, not {window}")
@@ -534,14 +615,17 @@ class CalibratingChangeSelector(_IntervalSelector):
                 n, head, closed = len(items), 0, []
                 if not self.decided:
                     head = n if self.window is None else min(n, self.window - fed)
-                    _totals, c = self.cells_fn(data if head == n else data[:head], area, params, fed == 0, False, ths)
+                    part = data if head == n else data[:head]
+                    _totals, c = self.cells_fn(part if self.key_fn is None else self.key_fn(part, area), area, params, fed == 0, False, ths)
                     seen.append(host(c, (-1, len(ths), 3)))
                     for q, tracker in enumerate(self.trackers):
                         self.pending[q] += tracker.feed(seen[-1][:, q])
                     if self.window is not None and fed + head >= self.window:
                         closed = decide(fed + head)
                 if self.decided and head < n:
-                    rows.append(host(self.count_fn(data[head:] if head else data, area, self.edge_thresh, False), (-1, 3)))
+                    part = data[head:] if head else data
+                    rows.append(host(self.count_fn(part if self.key_fn is None else self.key_fn(part, area), area, self.edge_thresh, False),
+                                     (-1, 3)))
                     got = self.tracker.feed(rows[-1])
                     self.intervals += got
                     closed = closed + got
@@ -615,8 +699,8 @@ class LocatingChangeSelector(_IntervalSelector):
     locate_area's); automaton="hold", max_hold_*, search_area and probe are refused.  Before the decision `tracker` is None."""
 
     def __init__(self, count_fn=None, cells_fn=None, replay_fn=None, window=None, locator_params=None, edge_thresh=128, change_ratio=0.5,
-                 min_edges=None, min_frames=2, batch=64):
-        super().__init__(count_fn, edge_thresh, change_ratio, min_edges, min_frames, batch)
+                 min_edges=None, min_frames=2, batch=64, key_fn=None):
+        super().__init__(count_fn, edge_thresh, change_ratio, min_edges, min_frames, batch, key_fn=key_fn)
         from . import area_locator
         if window is None or int(window) < 1:
             raise ValueError(f"LocatingChangeSelector: window must be at least 1 frame, not {window}")
@@ -692,7 +776,7 @@ class LocatingChangeSelector(_IntervalSelector):
         fed, closed = 0, []
         with closing(staging.staged_batches(bands, uploader)) as staged:
             for items, data in staged:
-                self.cells_fn(data, region, params, fed == 0, False, ths, self.window)
+                self.cells_fn(data if self.key_fn is None else self.key_fn(data, region), region, params, fed == 0, False, ths, self.window)
                 fed += len(items)
                 if fed >= self.window:
                     closed = decide(fed)
@@ -705,7 +789,8 @@ class LocatingChangeSelector(_IntervalSelector):
             if rest.area is not None:
                 with closing(staging.staged_batches(rest, uploader)) as staged:
                     for items, data in staged:
-                        rows.append(host(self.count_fn(data, rest.area, self.edge_thresh, False), (-1, 3)))
+                        keyed = data if self.key_fn is None else self.key_fn(data, rest.area)        # (over the located rectangle)
+                        rows.append(host(self.count_fn(keyed, rest.area, self.edge_thresh, False), (-1, 3)))
                         got = self.tracker.feed(rows[-1])
                         self.intervals += got
                         yield items, got
@@ -790,8 +875,8 @@ class HoldFrameSelector(_IntervalSelector):
     engine_count_fn = EngineHoldCounter
 
     def __init__(self, count_fn=None, hold_seconds=0.3, hold_frames=None, edge_thresh=128, change_ratio=0.5, min_edges=None,
-                 min_frames=2, batch=64, focus_fn=None, max_hold_seconds=None, max_hold_frames=None, compositor=None):
-        super().__init__(count_fn, edge_thresh, change_ratio, min_edges, min_frames, batch, focus_fn, compositor)
+                 min_frames=2, batch=64, focus_fn=None, max_hold_seconds=None, max_hold_frames=None, compositor=None, key_fn=None):
+        super().__init__(count_fn, edge_thresh, change_ratio, min_edges, min_frames, batch, focus_fn, compositor, key_fn)
         self.hold_seconds, self.hold_frames = hold_seconds, hold_frames
         self.max_hold_seconds, self.max_hold_frames = max_hold_seconds, max_hold_frames
         if max_hold_seconds is not None or max_hold_frames is not None:
@@ -891,8 +976,9 @@ class LocatingHoldSelector(_IntervalSelector):
     None."""
 
     def __init__(self, count_fn=None, cells_fn=None, replay_fn=None, window=None, locator_params=None, hold_seconds=0.3, hold_frames=None,
-                 edge_thresh=128, change_ratio=0.5, min_edges=None, min_frames=2, batch=64, max_hold_seconds=None, max_hold_frames=None):
-        super().__init__(count_fn, edge_thresh, change_ratio, min_edges, min_frames, batch)
+                 edge_thresh=128, change_ratio=0.5, min_edges=None, min_frames=2, batch=64, max_hold_seconds=None, max_hold_frames=None,
+                 key_fn=None):
+        super().__init__(count_fn, edge_thresh, change_ratio, min_edges, min_frames, batch, key_fn=key_fn)
         from . import area_locator
         if window is None or int(window) < 1:
             raise ValueError(f"{type(self).__name__}: window must be at least 1 frame, not {window}")
@@ -1000,7 +1086,8 @@ class LocatingHoldSelector(_IntervalSelector):
         fed, closed = 0, []
         with closing(staging.staged_batches(bands, uploader)) as staged:
             for items, data in staged:
-                self.cells_fn(data, region, params, fed == 0, False, ths, self.window, *cells_args)
+                self.cells_fn(data if self.key_fn is None else self.key_fn(data, region), region, params, fed == 0, False, ths, self.window,
+                              *cells_args)
                 fed += len(items)
                 if fed >= self.window:
                     closed = decide(fed, False)
@@ -1014,7 +1101,8 @@ class LocatingHoldSelector(_IntervalSelector):
             if rest.area is not None:
                 with closing(staging.staged_batches(rest, uploader)) as staged:
                     for items, data in staged:
-                        rows.append(host(self.count_fn(data, target, self.edge_thresh, *args, fed, False), (-1, 3)))
+                        keyed = data if self.key_fn is None else self.key_fn(data, target)       # (over the located rectangle)
+                        rows.append(host(self.count_fn(keyed, target, self.edge_thresh, *args, fed, False), (-1, 3)))
                         got = self.tracker.feed(rows[-1])
                         self.intervals += got
                         fed += len(items)
@@ -1092,9 +1180,10 @@ class LocatingBoundedHoldSelector(LocatingHoldSelector):
     engine_count_fn, engine_cells_fn = EngineBoundedHoldCounter, EngineCellsHoldBoundedMasks
 
     def __init__(self, count_fn=None, cells_fn=None, replay_fn=None, window=None, locator_params=None, hold_seconds=0.3, hold_frames=None,
-                 edge_thresh=128, change_ratio=0.5, min_edges=None, min_frames=2, batch=64, max_hold_seconds=None, max_hold_frames=None):
+                 edge_thresh=128, change_ratio=0.5, min_edges=None, min_frames=2, batch=64, max_hold_seconds=None, max_hold_frames=None,
+                 key_fn=None):
         super().__init__(count_fn, cells_fn, replay_fn, window, locator_params, hold_seconds, hold_frames, edge_thresh, change_ratio,
-                         min_edges, min_frames, batch, max_hold_seconds, max_hold_frames)
+                         min_edges, min_frames, batch, max_hold_seconds, max_hold_frames, key_fn)
         self.max_hold_seconds, self.max_hold_frames, self.max_hold = max_hold_seconds, max_hold_frames, None
 
     def _check_params(self, params, max_hold_seconds, max_hold_frames):

@@ -117,7 +117,8 @@ def make_clip(schedule, height=360, width=640, seed=0):
     return frames, truth
 
 
-def make_moving_clip(schedule, height=120, width=320, pan=(2, 3), amp=(110, 60), cells=(16, 4), noise=3, seed=0):
+def make_moving_clip(schedule, height=120, width=320, pan=(2, 3), amp=(110, 60), cells=(16, 4), noise=3, seed=0, text_bgr=(255, 255, 255),
+                     outline=True, chroma=False):
     """A clip with held subtitles over a textured background that moves, for the held-edge selector: uint8 BGR [n,height,width,3] +
     the true [(start, end, text)] (1-based frame numbers).  make_clip's background has no edge at the selectors' threshold; this one
     has hundreds in the subtitle band, and they move every frame.
@@ -125,14 +126,17 @@ def make_moving_clip(schedule, height=120, width=320, pan=(2, 3), amp=(110, 60),
     schedule: list of (text, frames); text None is a gap.  The background is a window into one grey world of random cells
     (`cells` pixels wide with amplitudes `amp`, summed around 128 and clipped to 8..247) that moves by |pan| = (dy, dx) pixels per
     frame, plus fresh noise of +-`noise` levels per frame; a text is one line of height 20 (white, its outline black) that always
-    stands at the same place, centred, 10 pixels above the bottom edge."""
+    stands at the same place, centred, 10 pixels above the bottom edge.
+    text_bgr: the fill colour (B, G, R); outline=False leaves the outline's pixels to the background; chroma=True draws the random cells
+    with three channels instead of one, so the world is coloured (what a colour key tells from the text, frame_select.ColourKey).  The
+    defaults give the grey clip, draw for draw."""
     rng = np.random.default_rng(seed)
     n = sum(int(s[1]) for s in schedule)
     dy, dx = abs(int(pan[0])), abs(int(pan[1]))
     wh, ww = height + dy * n + 1, width + dx * n + 1
     world = np.full((wh, ww, 3), 128, np.int32)
     for cell, a in zip(cells, amp):
-        t = rng.integers(-a, a + 1, (-(-wh // cell), -(-ww // cell), 1))
+        t = rng.integers(-a, a + 1, (-(-wh // cell), -(-ww // cell), 3 if chroma else 1))
         world += np.repeat(np.repeat(t, cell, 0), cell, 1)[:wh, :ww]
     np.clip(world, 8, 247, out=world)
     frames = np.empty((n, height, width, 3), np.uint8)
@@ -143,19 +147,20 @@ def make_moving_clip(schedule, height=120, width=320, pan=(2, 3), amp=(110, 60),
         count = int(count)
         if text is not None:
             if text not in glyphs:
-                fill, outline = render_line(text, 20, np.random.default_rng([seed, *text.encode()]))
+                fill, edge = render_line(text, 20, np.random.default_rng([seed, *text.encode()]))
                 lw = min(fill.shape[1], int(0.88 * width))
-                glyphs[text] = (fill[:, :lw], outline[:, :lw])
+                glyphs[text] = (fill[:, :lw], edge[:, :lw])
             truth.append((f + 1, f + count, text))
         for _ in range(count):
             img = world[dy * f:dy * f + height, dx * f:dx * f + width] + rng.integers(-noise, noise + 1, (height, width, 3))
             if text is not None:
-                fill, outline = glyphs[text]
+                fill, edge = glyphs[text]
                 lh, lw = fill.shape
                 x, y = (width - lw) // 2, height - lh - 10
                 reg = img[y:y + lh, x:x + lw]
-                reg[outline > 0] = 0
-                reg[fill > 0] = 255
+                if outline:
+                    reg[edge > 0] = 0
+                reg[fill > 0] = text_bgr
             frames[f] = np.clip(img, 0, 255).astype(np.uint8)
             f += 1
     return frames, truth
